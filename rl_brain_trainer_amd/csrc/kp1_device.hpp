@@ -103,18 +103,6 @@ __device__ __forceinline__ const T& uniform_block(const T* p) {
   return *(const T*)(const_space_ptr)p;
 }
 
-// The same block seen through a per-lane pointer (block + a zero the compiler cannot see through): its reads become VECTOR loads of a
-// wave-uniform address -- one cache line broadcast to all lanes -- with the SGPR-base + immediate-offset addressing form.  Why one would
-// want that for uniform data: scalar loads return out of order, so every use waits for ALL outstanding ones (s_waitcnt lgkmcnt(0)), and
-// 102 SGPRs hold only a few batches ahead; vector loads return in order (vmcnt(N) waits for exactly the one needed) and a wave that is
-// alone on its SIMD has 512 vector registers to prefetch into.
-template <typename T>
-__device__ __forceinline__ const T& lane_view(const T& block) {
-  uint32_t zero;
-  asm("v_mov_b32 %0, 0" : "=v"(zero));
-  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(&block) + zero);
-}
-
 // Warm the scalar data cache with a block the wave is about to read through scalar loads.  The step kernel reads ~400 scalars of DevCfg, and
 // the compiler (102 SGPRs) can only load them a few at a time next to their uses: each batch is then a dependent round trip to L2
 // (~200-500 cycles), and with ONE wave per SIMD nothing else runs meanwhile -- SQ_WAIT_ANY was 53 % of the wave's cycles
@@ -122,13 +110,9 @@ __device__ __forceinline__ const T& lane_view(const T& block) {
 // hits for the price of a single one.  Returns the block pointer made dependent on the loaded words (plus a run-time zero), so that every
 // later read of the block is ordered behind the warm-up without a volatile asm (a volatile asm counts as a store to everything for the
 // compiler, which then reads the whole block with uniform-address VECTOR loads).
-#ifndef KP1_CFG_WARM
-#define KP1_CFG_WARM 2
-#endif
 #define KP1_WARM_BYTES 4096   // blocks handed to scalar_cache_warm are allocated in multiples of this
 template <typename T>
 __device__ __forceinline__ const T* scalar_cache_warm(const T* __restrict__ block) {
-#if KP1_CFG_WARM == 2
   // ONE asm statement: 64 loads (4 KB, the block's allocation is padded to that) into the same scratch SGPR -- the words are never used --,
   // one wait, and the scratch register forced to zero as the statement's only output
   static_assert(KP1_WARM_BYTES == 4096, "the load list below covers 4 KB");
@@ -202,9 +186,6 @@ __device__ __forceinline__ const T* scalar_cache_warm(const T* __restrict__ bloc
       "s_mov_b32 %0, 0"
       : "=&s"(zero) : "s"(block));
   return reinterpret_cast<const T*>(reinterpret_cast<const char*>(block) + zero);
-#else
-  return block;
-#endif
 }
 
 // sampler configuration, always fp64 (reset path only)
@@ -247,32 +228,22 @@ struct EnvState {
   // VIOLATION at the first in-launch route reset (round 3, gpurun_out/r03_dbg1.log).  kp1_create bounds n so that the offset fits 32 bits.
   template <typename T>
   static __device__ __forceinline__ T& at(T* base, int f, int64_t n, int64_t i) {
-#ifdef KP1_OLD_PLANE_ADDR
-    return base[(int64_t)f * n + i];
-#else
     return *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + ((uint32_t)f * (uint32_t)n + (uint32_t)i) * (uint32_t)sizeof(T));
-#endif
   }
   __device__ __forceinline__ R& r(int f, int64_t i) const { return at<R>(real, f, n, i); }
-#ifndef KP1_ENV_LD_AUX
-#define KP1_ENV_LD_AUX 16  // cache-policy bits of the step's state loads (fp32 handle; 0 = plain loads): sc1, not allocated in the CU's L1: 7.9 -> 7.7 us at 4096 envs, 10.09 -> 9.89 us at 32768 (profiles/r03_ab_env_load_policy.log)
-#endif
-  // state loads of the step path: every field is read once per step, nothing is reused through the CU's L1
+  // state loads of the step path: every field is read once per step, nothing is reused through the CU's L1.  fp32 handle: sc1 buffer loads,
+  // not allocated in the CU's L1: 7.9 -> 7.7 us at 4096 envs, 10.09 -> 9.89 us at 32768 (profiles/r03_ab_env_load_policy.log); fp64: plain loads
   __device__ __forceinline__ R rl(int f, int64_t i) const {
-    if constexpr (KP1_ENV_LD_AUX == 0 || sizeof(R) != 4) {
+    if constexpr (sizeof(R) != 4) {
       return at<R>(real, f, n, i);
     } else {
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(real, 0, 0x7fffffff, 0x00020000);
-      return __builtin_bit_cast(R, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(((uint32_t)f * (uint32_t)n + (uint32_t)i) * 4u), 0, KP1_ENV_LD_AUX));
+      return __builtin_bit_cast(R, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(((uint32_t)f * (uint32_t)n + (uint32_t)i) * 4u), 0, 16));
     }
   }
   __device__ __forceinline__ int32_t ivl(int f, int64_t i) const {
-    if constexpr (KP1_ENV_LD_AUX == 0) {
-      return at<int32_t>(ints, f, n, i);
-    } else {
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(ints, 0, 0x7fffffff, 0x00020000);
-      return __builtin_bit_cast(int32_t, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(((uint32_t)f * (uint32_t)n + (uint32_t)i) * 4u), 0, KP1_ENV_LD_AUX));
-    }
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(ints, 0, 0x7fffffff, 0x00020000);
+    return __builtin_bit_cast(int32_t, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(((uint32_t)f * (uint32_t)n + (uint32_t)i) * 4u), 0, 16));
   }
   __device__ __forceinline__ double q_loadl(int k, int64_t i) const {
     if constexpr (sizeof(R) == 4) return (double)rl(F_Q + k, i) + (double)rl(F_QLO + k, i);
@@ -323,27 +294,22 @@ __device__ __forceinline__ void kp_sincos_kin(double x, double* s, double* c) {
 
 // the same chain as straight-line code specialised to the robot constants (tools/gen_fk_chain.py): what the fp32 handle runs
 #include "kp1_fk_generated.inc"
-#ifndef KP1_FK_GENERATED
-#define KP1_FK_GENERATED 1   // 0: the fp32 handle runs the generic chain on the constants of DevFk (A/B switch; the fp64 handle always does)
-#endif
 
-// Rotation and position of the chain.  FAST selects kp_sincos_kin (fp32 handle); the fp64 handle keeps the library sincos it is pinned with.
-template <typename R, bool FAST>
+// Rotation and position of the chain (the fp64 handle: the library sincos it is pinned with; the fp32 handle runs fk_chain_generated).
+template <typename R>
 __device__ __forceinline__ void fk_chain(const DevFk<R>& __restrict__ k, const R* __restrict__ q, R* __restrict__ p, R* __restrict__ Rm) {
 #pragma clang fp contract(off)
   R s, c;
   // joint 0 (prismatic) + joint 1 origin: pure translation
 #pragma unroll
   for (int i = 0; i < 3; ++i) p[i] = kp_fma(k.v0[i], q[0], k.p01[i]);
-  if constexpr (FAST) kp_sincos_kin(q[1], &s, &c);
-  else kp_sincos(q[1], &s, &c);
+  kp_sincos(q[1], &s, &c);
 #pragma unroll
   for (int e = 0; e < 9; ++e) Rm[e] = kp_fma(s, k.ks[0][e], kp_fma(c, k.kc[0][e], k.k1[0][e]));
 #pragma unroll
   for (int j = 2; j < NJ; ++j) {
     const int m = j - 1;
-    if constexpr (FAST) kp_sincos_kin(q[j], &s, &c);
-    else kp_sincos(q[j], &s, &c);
+    kp_sincos(q[j], &s, &c);
     R D[9], Rn[9];
 #pragma unroll
     for (int e = 0; e < 9; ++e) D[e] = kp_fma(s, k.ks[m][e], kp_fma(c, k.kc[m][e], k.k1[m][e]));
@@ -363,7 +329,7 @@ template <typename R>
 __device__ __forceinline__ void fk_pose6(const DevFk<R>& __restrict__ k, const R* __restrict__ q, R* __restrict__ pose) {
 #pragma clang fp contract(off)
   R Rm[9], p[3];
-  fk_chain<R, false>(k, q, p, Rm);
+  fk_chain<R>(k, q, p, Rm);
   pose[0] = p[0];
   pose[1] = p[1];
   pose[2] = p[2];
@@ -384,11 +350,7 @@ __device__ __forceinline__ void fk_pose6_kin(const DevFk<double>& __restrict__ k
   } else {
 #pragma clang fp contract(off)
     double Rm[9], p[3];
-#if KP1_FK_GENERATED
     fk_chain_generated(q, p, Rm);      // (k is not read: kp1_create has checked that the generated constants are fold_fk's, bit for bit)
-#else
-    fk_chain<double, true>(k, q, p, Rm);
-#endif
     const float r0 = (float)Rm[0], r3 = (float)Rm[3], r6 = (float)Rm[6], r7 = (float)Rm[7], r8 = (float)Rm[8];
     pose[0] = (R)p[0];
     pose[1] = (R)p[1];

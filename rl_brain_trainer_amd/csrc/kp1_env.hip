@@ -31,7 +31,7 @@ namespace {
 #include "kp1_env_step.inc"
 
 template <typename R, int MODE, bool COMPS>
-__global__ void __launch_bounds__(256, KP1_STEP_MIN_WAVES) kp1_step_kernel(const StepArgs<R> a) {
+__global__ void __launch_bounds__(256, 1) kp1_step_kernel(const StepArgs<R> a) {
   extern __shared__ float obs_tiles[];   // OBS_TILE_FLOATS per wave of the workgroup
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 #ifdef KP1_ENV_TRACE   // slots 11 / 12: the chip-wide 100 MHz clock at wave entry / exit (the shader clock of slots 0..10 is not comparable across the chip)
@@ -449,11 +449,8 @@ namespace {
 
 // One wave per workgroup at every size: the step kernel holds 500 vector registers, so a CU runs four waves (one per SIMD), and a 256-thread
 // workgroup can only be replaced when all four of its waves have finished.  64-thread workgroups let every SIMD take its next wave by itself:
-// 117.5 -> 99.1 us at 524 288 envs, 33.8 -> 31.3 us at 131 072 (profiles/r03_ab_env_block_size.log; KP1_BIG_BLOCK is the A/B switch).
-#ifndef KP1_BIG_BLOCK
-#define KP1_BIG_BLOCK 64
-#endif
-int block_for(int64_t n) { return n <= 65536 ? 64 : KP1_BIG_BLOCK; }
+// 117.5 -> 99.1 us at 524 288 envs, 33.8 -> 31.3 us at 131 072 (profiles/r03_ab_env_block_size.log).
+int block_for(int64_t) { return 64; }
 
 
 template <typename R>

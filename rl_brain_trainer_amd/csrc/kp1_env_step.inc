@@ -316,9 +316,6 @@ struct StepArgs {
   const int32_t* stage_ptr;  // device-resident curriculum stage (kp1_bind_stage_ptr) or nullptr
 };
 
-#ifndef KP1_STEP_MIN_WAVES
-#define KP1_STEP_MIN_WAVES 1   // minimum waves per SIMD the register allocation must leave room for (launch_bounds' second argument)
-#endif
 // One env step of lane i, auto-reset of a finished env included (VecEnv semantics).
 // [round 3, measured and removed] A split form for large batches -- this body without the reset branch under launch_bounds(256, 2), i.e. two
 // waves per SIMD instead of one, plus a second kernel that resets the finished envs -- is bit-identical and NOT faster: 116.9 us for the step
@@ -332,19 +329,9 @@ template <typename R, int MODE, bool COMPS>
 __device__ __forceinline__ void step_env_lane(const StepArgs<R>& a, const int64_t i, const R* __restrict__ act_src, float* __restrict__ o) {
   const int64_t n = a.st.n;
   KP1_ETR(0)
-#ifndef KP1_CFG_VEC
-#define KP1_CFG_VEC 0     // 0: config through scalar loads; 1: the FK constants through lane_view; 2: the whole block through lane_view
-#endif
-#if KP1_CFG_VEC == 2
-  const DevCfg<R>& __restrict__ cfg = lane_view(*a.cfg);
-  const DevFk<double>& __restrict__ fkc = cfg.kin.fk;
-#elif KP1_CFG_VEC == 1
-  const DevCfg<R>& __restrict__ cfg = *scalar_cache_warm(a.cfg);
-  const DevFk<double>& __restrict__ fkc = lane_view(cfg.kin.fk);
-#else
+  // config through scalar loads (reading it through per-lane vector loads was measured and removed: DESIGN.md 4.7)
   const DevCfg<R>& __restrict__ cfg = *scalar_cache_warm(a.cfg);
   const DevFk<double>& __restrict__ fkc = cfg.kin.fk;
-#endif
   KP1_ETR(1)
   const EnvState<R>& st = a.st;
   const R Z = (R)0;

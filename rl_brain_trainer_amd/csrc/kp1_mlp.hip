@@ -77,53 +77,24 @@ __device__ unsigned long long kp1_clk_buf[2 * 1024 * 4];   // [kernel: 0 tile, 1
 #define KP1_CLK(kern, at)
 #endif
 
-// Cache policy of the big once-written / once-read streams (build switches; the defaults are the measured optimum).
-// aux bits of the gfx950 buffer instructions: 1 = sc0, 2 = nt, 16 = sc1.  sc1 stores are write-through: the line leaves the XCD's L2 when it
-// is written instead of at the kernel's end-of-launch write-back, and the consumer (another launch, mostly on another XCD) reads it from
-// HBM / the memory-side cache either way.
-#ifndef KP1_FU_ST_AUX
-#define KP1_FU_ST_AUX 0    // tile kernel: X / h1 / dZ2 / dZ1 activation stores
-#endif
-#ifndef KP1_TNF_ST_AUX
-#define KP1_TNF_ST_AUX 16  // weight-gradient kernel: partial-slab stores (write-through: 30.4 -> 29.0 us in situ, profiles/r02_ab_cache_policy.log)
-#endif
-#ifndef KP1_TNF_LD_NT
-#define KP1_TNF_LD_NT 0    // weight-gradient kernel: activation operand loads non-temporal
-#endif
-#ifndef KP1_TNS_LD_AUX
-#define KP1_TNS_LD_AUX 16  // wave-split weight-gradient kernel: the activation-fragment loads bypass the CU's L1 (sc1; no reuse inside a CU): 25.4 -> 24.4 us in situ, nt 26.5 (profiles/r03_ab_tn_load_policy.log)
-#endif
-#ifndef KP1_FIN_LD_NT
-#define KP1_FIN_LD_NT 0    // finalize kernel: partial-slab loads non-temporal
-#endif
-#ifndef KP1_FIN_SPLIT
-#define KP1_FIN_SPLIT 1    // finalize kernel: adjacent lanes that share one float4 item and split its batch chunks (1, 2 or 4)
-#endif
+// Cache policy of the big once-written / once-read streams (the measured optimum): aux bits of the gfx950 buffer instructions,
+// 1 = sc0, 2 = nt, 16 = sc1.  sc1 stores are write-through: the line leaves the XCD's L2 when it is written instead of at the kernel's
+// end-of-launch write-back, and the consumer (another launch, mostly on another XCD) reads it from HBM / the memory-side cache either way.
+//   weight-gradient partial-slab stores: sc1 (write-through: 30.4 -> 29.0 us in situ, profiles/r02_ab_cache_policy.log)
+//   weight-gradient activation-fragment loads: sc1, they bypass the CU's L1 (no reuse inside a CU): 25.4 -> 24.4 us in situ, nt 26.5
+//     (profiles/r03_ab_tn_load_policy.log)
+//   tile-kernel activation stores and finalize-kernel slab loads: plain
+constexpr int AUX_SC1 = 16;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// 16-byte store of `v` at float index `idx` of the (wave-uniform) base pointer with cache policy AUX; AUX = 0 is a plain global store
-template <int AUX>
-__device__ __forceinline__ void store16(float* __restrict__ base, int64_t idx, const f32x4 v) {
-  if constexpr (AUX == 0) {
-    *reinterpret_cast<f32x4*>(base + idx) = v;
-  } else {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)(idx * 4), 0, AUX);
-  }
+// 16-byte sc1 store of `v` at float index `idx` of the (wave-uniform) base pointer
+__device__ __forceinline__ void store16_sc1(float* __restrict__ base, int64_t idx, const f32x4 v) {
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)(idx * 4), 0, AUX_SC1);
 }
-// 16-byte load at base[off] (floats) with cache-policy bits (raw buffer load: 1 sc0, 2 nt, 16 sc1); AUX = 0: a plain global load
-template <int AUX>
-__device__ __forceinline__ f32x4 load16_aux(const float* __restrict__ base, int64_t off) {
-  if constexpr (AUX == 0) {
-    return *reinterpret_cast<const f32x4*>(base + off);
-  } else {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(off * 4), 0, AUX));
-  }
-}
-template <int NT>
-__device__ __forceinline__ f32x4 load16(const float* __restrict__ p) {
-  if constexpr (NT == 0) return *reinterpret_cast<const f32x4*>(p);
-  else return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
+// 16-byte sc1 load at base[off] (floats)
+__device__ __forceinline__ f32x4 load16_sc1(const float* __restrict__ base, int64_t off) {
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(off * 4), 0, AUX_SC1));
 }
 
 // tanh(x) = 2 / (1 + 2^(-2 log2(e) x)) - 1 in FIVE vector instructions (v_mul, v_exp_f32, v_add, v_rcp_f32, v_fma = 28 issue cycles).
@@ -940,10 +911,7 @@ __device__ __forceinline__ int64_t finalize_wide_index(const ParamLayout& L, int
 // LDS combines the 8 strands in a fixed order -- a single thread summing 256 tiles was the tail of this kernel (8 dependent load rounds).
 // Every block leaves the sum of squares of what it wrote in sumsq[blockIdx.x] for clip_grad_norm_.
 __host__ __device__ inline int64_t finalize_vec_items(const ParamLayout& L) { return 2 * ((int64_t)L.H * L.H / 4 + (int64_t)L.H * L.IN / 4); }
-// KP1_FIN_SPLIT adjacent lanes share one item: lane part p sums the chunks [p * ceil(n / SPLIT), ...) in order and the parts are added in
-// part order by shuffles -- a fixed order, so still bitwise reproducible; more workgroups pull on the 25 MB of slabs at once
-constexpr int FIN_SPLIT = KP1_FIN_SPLIT;
-static_assert(FIN_SPLIT == 1 || FIN_SPLIT == 2 || FIN_SPLIT == 4, "KP1_FIN_SPLIT must be 1, 2 or 4");
+// (a form with 2 or 4 lanes splitting the chunks of one item was measured and removed: DESIGN.md 4.3)
 
 __global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a, int n_main) {
   const ParamLayout& L = a.L;
@@ -952,8 +920,7 @@ __global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a
   float gval = 0.f;
   double gsq = 0.0;
   if ((int)blockIdx.x < n_main) {
-    const int64_t j = (int64_t)((blockIdx.x * 256u + threadIdx.x) / (unsigned)FIN_SPLIT);
-    const int part = threadIdx.x % FIN_SPLIT;
+    const int64_t j = (int64_t)(blockIdx.x * 256u + threadIdx.x);
     const int64_t per2 = (int64_t)L.H * L.H / 4, per1 = (int64_t)L.H * L.IN / 4;
     if (j < 2 * (per2 + per1)) {
       const float* src;
@@ -973,11 +940,6 @@ __global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a
         stride = a.s1_chunk; n = a.s1_n;
         dst = (net ? L.v_w1 : L.p_w1) + (int64_t)row * L.IN + 4 * c4;
       }
-      if (FIN_SPLIT > 1) {   // this lane's share of the chunks
-        const int per = (n + FIN_SPLIT - 1) / FIN_SPLIT, c0 = min(part * per, n);
-        src += (int64_t)c0 * stride;
-        n = min(per, n - c0);
-      }
       f32x4 s = {0.f, 0.f, 0.f, 0.f};
       int c = 0;
       // the kernel is bound by memory round trips, not bandwidth: 32 partials (one whole dW2 element at the default batch split) are in
@@ -985,40 +947,29 @@ __global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a
       for (; c + 32 <= n; c += 32) {
         f32x4 v[32];
 #pragma unroll
-        for (int u = 0; u < 32; ++u) v[u] = load16<KP1_FIN_LD_NT>(src + (int64_t)(c + u) * stride);
+        for (int u = 0; u < 32; ++u) v[u] = *reinterpret_cast<const f32x4*>(src + (int64_t)(c + u) * stride);
 #pragma unroll
         for (int u = 0; u < 32; ++u) s += v[u];
       }
       for (; c + 16 <= n; c += 16) {
         f32x4 v[16];
 #pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = load16<KP1_FIN_LD_NT>(src + (int64_t)(c + u) * stride);
+        for (int u = 0; u < 16; ++u) v[u] = *reinterpret_cast<const f32x4*>(src + (int64_t)(c + u) * stride);
 #pragma unroll
         for (int u = 0; u < 16; ++u) s += v[u];
       }
       for (; c + 8 <= n; c += 8) {
         f32x4 v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = load16<KP1_FIN_LD_NT>(src + (int64_t)(c + u) * stride);
+        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4*>(src + (int64_t)(c + u) * stride);
 #pragma unroll
         for (int u = 0; u < 8; ++u) s += v[u];
       }
-      for (; c < n; ++c) s += load16<KP1_FIN_LD_NT>(src + (int64_t)c * stride);
-      if (FIN_SPLIT > 1) {   // parts added in part order: ((p0 + p1) + p2) + p3
+      for (; c < n; ++c) s += *reinterpret_cast<const f32x4*>(src + (int64_t)c * stride);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float t = __shfl(s[q], (threadIdx.x & 63) - part);
-#pragma unroll
-          for (int k = 1; k < FIN_SPLIT; ++k) t += __shfl(s[q], (threadIdx.x & 63) - part + k);
-          s[q] = t;
-        }
-      }
-      if (part == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          a.grad[dst + q] = s[q];
-          gsq += (double)s[q] * (double)s[q];
-        }
+      for (int q = 0; q < 4; ++q) {
+        a.grad[dst + q] = s[q];
+        gsq += (double)s[q] * (double)s[q];
       }
     }
     if (a.step_counter && blockIdx.x == 0 && threadIdx.x == 0) *a.step_counter += 1;  // read by the adam kernel that follows
@@ -1093,35 +1044,24 @@ __global__ void __launch_bounds__(256) sumsq_partials_kernel(const float* __rest
 // torch.nn.utils.clip_grad_norm_ (coef = max_norm / (norm + 1e-6), clamped to 1) + torch.optim.Adam
 // The same pass repacks the updated element into the kernel-format weights and (zero_grad) clears the gradient, so the
 // next minibatch's atomic accumulation starts from zero without a memset launch.
-// VEC = 4: a thread owns four consecutive elements (float4 loads / stores of p, g, m, v; the caller checks 16-byte alignment): a quarter of
-// the workgroups -- each of them sums the norm partials again -- and of the load instructions; per-element arithmetic unchanged.
-#ifndef KP1_ADAM_VEC
-#define KP1_ADAM_VEC 1     // 4 measured SLOWER (8.1 -> 12.9 us in situ, profiles/r02_ab_adam_vec4.log): the kernel is a latency chain per thread
-#endif                     // (scattered repack stores behind div / sqrt), so it wants more threads, not fatter ones
-#ifndef KP1_ADAM_BLOCK
-#define KP1_ADAM_BLOCK 256
-#endif
-template <int VEC>
-__global__ void __launch_bounds__(KP1_ADAM_BLOCK) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+// One thread per element: a float4-per-thread form measured SLOWER (8.1 -> 12.9 us in situ, profiles/r02_ab_adam_vec4.log): the kernel is a
+// latency chain per thread (scattered repack stores behind div / sqrt), so it wants more threads, not fatter ones.
+// (The loops over VEC = 1 are one trip.  Written without them -- one `i`, its `i < n` shared by the load clamp and the store guard -- the kernel
+// compiles to a different register assignment and load order than the measured one, so this form is kept.)
+constexpr int ADAM_BLOCK = 256, VEC = 1;
+__global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                    int64_t n, const double* __restrict__ partials, int n_partials, float lr, float eps, float max_norm,
                                                    float bc1, float bc2_sqrt, const ParamLayout L, const Packed k, int zero_grad,
                                                    const int* __restrict__ step_counter, int host_step, const int* __restrict__ actor_extra) {
   __shared__ float scale_s;
   // this thread's elements: their loads do not depend on the norm, so they go out first and share one memory round trip with the
   // step count and the norm partials below (the kernel is a chain of round trips: it moves 2.6 MB)
-  const int64_t i0 = ((int64_t)blockIdx.x * KP1_ADAM_BLOCK + threadIdx.x) * VEC;
+  const int64_t i0 = ((int64_t)blockIdx.x * ADAM_BLOCK + threadIdx.x) * VEC;
   float g_in[VEC], m_in[VEC], v_in[VEC], p_in[VEC];
-  if (VEC == 4 && i0 + 3 < n) {
-    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i0), mv = *reinterpret_cast<const f32x4*>(m + i0);
-    const f32x4 vv = *reinterpret_cast<const f32x4*>(v + i0), pv = *reinterpret_cast<const f32x4*>(p + i0);
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) { g_in[j] = gv[j]; m_in[j] = mv[j]; v_in[j] = vv[j]; p_in[j] = pv[j]; }
-  } else {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      const int64_t il = i0 + j < n ? i0 + j : n - 1;
-      g_in[j] = g[il]; m_in[j] = m[il]; v_in[j] = v[il]; p_in[j] = p[il];
-    }
+  for (int j = 0; j < VEC; ++j) {
+    const int64_t il = i0 + j < n ? i0 + j : n - 1;
+    g_in[j] = g[il]; m_in[j] = m[il]; v_in[j] = v[il]; p_in[j] = p[il];
   }
   const int extra = *actor_extra;
   float base_step = (float)host_step;
@@ -1161,22 +1101,13 @@ __global__ void __launch_bounds__(KP1_ADAM_BLOCK) adam_kernel(float* __restrict_
     const float denom = sqrtf(vn[j]) / b2 + eps;
     pn[j] = p_in[j] - (lr / b1) * (mn[j] / denom);
   }
-  if (VEC == 4 && i0 + 3 < n) {
-    *reinterpret_cast<f32x4*>(m + i0) = f32x4{mn[0], mn[1], mn[2], mn[3]};
-    *reinterpret_cast<f32x4*>(v + i0) = f32x4{vn[0], vn[1], vn[2], vn[3]};
-    *reinterpret_cast<f32x4*>(p + i0) = f32x4{pn[0], pn[1], pn[2], pn[3]};
-    if (zero_grad) *reinterpret_cast<f32x4*>(g + i0) = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) pack_one(i0 + j, pn[j], L, k);
-  } else {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      const int64_t i = i0 + j;
-      if (i < n) {
-        m[i] = mn[j]; v[i] = vn[j]; p[i] = pn[j];
-        pack_one(i, pn[j], L, k);
-        if (zero_grad) g[i] = 0.f;
-      }
+  for (int j = 0; j < VEC; ++j) {
+    const int64_t i = i0 + j;
+    if (i < n) {
+      m[i] = mn[j]; v[i] = vn[j]; p[i] = pn[j];
+      pack_one(i, pn[j], L, k);
+      if (zero_grad) g[i] = 0.f;
     }
   }
 }
@@ -1273,18 +1204,9 @@ struct ProfScope {
 namespace {
 
 constexpr int N_PARTIALS = 128;
-#ifndef KP1_TN_FORM
-#define KP1_TN_FORM 1      // 0: gemm_tn_frag_kernel (128 x 128 tiles, 32 batch chunks), 1: gemm_tn_split_kernel (64 x 64 tiles, 8 chunks, waves split the rows; default: profiles/r02_ab_tn_wave_split.log)
-#endif
-#ifndef KP1_TN_SPLIT2
-#if KP1_TN_FORM == 1
-#define KP1_TN_SPLIT2 8    // batch chunks of the dW2 / dW1 partial tiles
-#define KP1_TN_SPLIT1 16
-#else
-#define KP1_TN_SPLIT2 32
-#define KP1_TN_SPLIT1 64
-#endif
-#endif
+// batch chunks of the dW2 / dW1 partial tiles of gemm_tn_split_kernel: 8 chunks x 32 tiles = one dW2 workgroup per CU, 16 chunks x 16 tiles of
+// quarter-size dW1 workgroups (profiles/r02_ab_tn_wave_split.log)
+constexpr int TN_SPLIT2 = 8, TN_SPLIT1 = 16;
 
 // rows of the batch each TN workgroup reduces: aim at ~256 workgroups (one per CU) for the H x H gradient
 int tn_chunk_rows(int n, int tiles) {
@@ -1343,7 +1265,6 @@ int launch_nt(const GemmNT& g, hipStream_t stream) {
 int launch_tn(kp1_mlp* m, GemmTN t, int n_o_tiles, int slab_cols, float* slab, int* n_chunks_out, hipStream_t stream);
 
 int launch_fused(const FusedArgs& fa_in, hipStream_t stream) {
-  using G = FuGeom<true>;
   FusedArgs fa = fa_in;
   static const int stagger_us = [] { const char* e = std::getenv("KP1_FU_STAGGER_US"); return e ? std::atoi(e) : 11; }();  // tuning knob; re-swept in round 3 (profiles/r03_ab_tile_stagger.log): 10-13 us within 0.4 us of each other, a cliff at 14 (+6 us)
   static const int n_cus = [] {
@@ -1351,78 +1272,68 @@ int launch_fused(const FusedArgs& fa_in, hipStream_t stream) {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
     return n;
   }();
-  const dim3 grid((fa.n + G::BM - 1) / G::BM, 1, 2);
+  const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, 2);
   fa.n_cus = n_cus;
-  fa.stagger_ticks = (G::RB == 1 && (int)(grid.x * grid.z) > n_cus) ? stagger_us * 100 : 0;   // only when CUs hold two workgroups at once
-  const size_t bytes = sizeof(float) * G::LDS_FLOATS;
+  fa.stagger_ticks = (int)(grid.x * grid.z) > n_cus ? stagger_us * 100 : 0;   // only when CUs hold two workgroups at once
+  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;
   if (fa.sp_h1 != nullptr) {   // [r3 experiment] bf16 x 3 planes instead of the fp32 activation copies
     if (fa.inp == 64) {
       HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<true, 2, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-      KP1_LAUNCH((mlp_tile_kernel<true, 2, 0, true>), grid, dim3(G::NTH), bytes, stream, fa);
+      KP1_LAUNCH((mlp_tile_kernel<true, 2, 0, true>), grid, dim3(FU_NTH), bytes, stream, fa);
     } else {
       HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<true, 4, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-      KP1_LAUNCH((mlp_tile_kernel<true, 4, 0, true>), grid, dim3(G::NTH), bytes, stream, fa);
+      KP1_LAUNCH((mlp_tile_kernel<true, 4, 0, true>), grid, dim3(FU_NTH), bytes, stream, fa);
     }
     return KP1_OK;
   }
   if (fa.inp == 64) {
     HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    KP1_LAUNCH((mlp_tile_kernel<true, 2>), grid, dim3(G::NTH), bytes, stream, fa);
+    KP1_LAUNCH((mlp_tile_kernel<true, 2>), grid, dim3(FU_NTH), bytes, stream, fa);
   } else {
     HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    KP1_LAUNCH((mlp_tile_kernel<true, 4>), grid, dim3(G::NTH), bytes, stream, fa);
+    KP1_LAUNCH((mlp_tile_kernel<true, 4>), grid, dim3(FU_NTH), bytes, stream, fa);
   }
   return KP1_OK;
 }
 
 // policy forward + env step in one launch (kp1_mlp_forward_env_step): env_mode = KP1_MODE_APPROACH / KP1_MODE_DOCK, 64-float observation rows
 int launch_fused_infer_env(const FusedArgs& fa, int env_mode, hipStream_t stream) {
-  using G = FuGeom<false>;
-  const size_t bytes = sizeof(float) * G::LDS_FLOATS;
-  const dim3 grid((fa.n + G::BM - 1) / G::BM, 1, fa.value ? 2 : 1);
+  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;
+  const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, fa.value ? 2 : 1);
   if (env_mode == KP1_MODE_DOCK) {
     HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 2>), grid, dim3(G::NTH), bytes, stream, fa);
+    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 2>), grid, dim3(FU_NTH), bytes, stream, fa);
   } else {
     HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 1>), grid, dim3(G::NTH), bytes, stream, fa);
+    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 1>), grid, dim3(FU_NTH), bytes, stream, fa);
   }
   return KP1_OK;
 }
 
 int launch_fused_infer(const FusedArgs& fa, hipStream_t stream) {
-  using G = FuGeom<false>;  // 32-row tiles, 4 waves, two workgroups per CU
-  const size_t bytes = sizeof(float) * G::LDS_FLOATS;
+  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;   // 32-row tiles, 4 waves, two workgroups per CU
   // the value net is skipped when no value is asked for (deterministic evaluators), the policy net when only values are
   const bool want_pi = fa.mean || fa.action || fa.clipped || fa.log_prob;
   if (!want_pi && !fa.value) return KP1_OK;
   FusedArgs f = fa;
   const bool both = want_pi && fa.value;
   if (!both) f.net_base = want_pi ? 0 : 1;
-  const dim3 grid((fa.n + G::BM - 1) / G::BM, 1, both ? 2 : 1);
+  const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, both ? 2 : 1);
   if (fa.inp == 64) {
     HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2>), grid, dim3(G::NTH), bytes, stream, f);
+    hipLaunchKernelGGL((mlp_tile_kernel<false, 2>), grid, dim3(FU_NTH), bytes, stream, f);
   } else {
     HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 4>), grid, dim3(G::NTH), bytes, stream, f);
+    hipLaunchKernelGGL((mlp_tile_kernel<false, 4>), grid, dim3(FU_NTH), bytes, stream, f);
   }
   return KP1_OK;
 }
 
 int launch_tn_frag(const TnFragArgs& t, hipStream_t stream) {
   if (t.n_chunks2 > 64 || t.n_chunks1 > 64) return fail(KP1_ERR_INVALID, "too many batch chunks for the partial-gradient slabs");
-#if KP1_TN_FORM == 1
-  {
-    const size_t bytes = sizeof(float) * TN_SPLIT_LDS_FLOATS;
-    HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    KP1_LAUNCH(gemm_tn_split_kernel, dim3(32 * t.n_chunks2 + 16 * t.n_chunks1), dim3(256), bytes, stream, t);
-    return KP1_OK;
-  }
-#endif
-  const size_t bytes = sizeof(float) * 128 * (128 + 4);
-  HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_frag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  hipLaunchKernelGGL(gemm_tn_frag_kernel, dim3(8 * t.n_chunks2 + 4 * t.n_chunks1), dim3(256), bytes, stream, t);
+  const size_t bytes = sizeof(float) * TN_SPLIT_LDS_FLOATS;
+  HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  KP1_LAUNCH(gemm_tn_split_kernel, dim3(32 * t.n_chunks2 + 16 * t.n_chunks1), dim3(256), bytes, stream, t);
   return KP1_OK;
 }
 
@@ -1756,10 +1667,10 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     t.dz2 = m->dz2; t.h1 = m->h1; t.dz1 = m->dz1; t.act_stride = act_stride; t.xf = m->xf;
     t.slab2 = m->slab; t.s2_net = (int64_t)Hp * Hp; t.s2_chunk = 2 * t.s2_net;
     t.slab1 = m->slab1; t.s1_net = (int64_t)Hp * INP; t.s1_chunk = 2 * t.s1_net;
-    t.groups = (n + FU_BM_TRAIN - 1) / FU_BM_TRAIN * (FU_BM_TRAIN / 8);   // the tile kernel writes whole 64-row tiles
+    t.groups = (n + FU_BM - 1) / FU_BM * (FU_BM / 8);   // the tile kernel writes whole 32-row tiles
     auto up8 = [](int v) { return (v + 7) / 8 * 8; };
-    t.cg2 = up8((t.groups + KP1_TN_SPLIT2 - 1) / KP1_TN_SPLIT2);   // form 0: ~32 chunks x 8 tiles, form 1: 8 chunks x 32 tiles = one dW2 workgroup per CU
-    t.cg1 = up8((t.groups + KP1_TN_SPLIT1 - 1) / KP1_TN_SPLIT1);   // form 0: ~64 chunks x 4 tiles, form 1: 16 chunks x 16 tiles of quarter-size dW1 workgroups
+    t.cg2 = up8((t.groups + TN_SPLIT2 - 1) / TN_SPLIT2);
+    t.cg1 = up8((t.groups + TN_SPLIT1 - 1) / TN_SPLIT1);
     t.n_chunks2 = (t.groups + t.cg2 - 1) / t.cg2;
     t.n_chunks1 = (t.groups + t.cg1 - 1) / t.cg1;
     if (m->bf16x3) {   // [r3 experiment] same slabs, same chunking in 16-row fragments
@@ -1801,12 +1712,12 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
   f.L = L;
   f.slab2 = m->slab; f.s2_ld = Hp; f.s2_net = (int64_t)Hp * Hp; f.s2_chunk = 2 * f.s2_net; f.s2_n = s2_n;
   f.slab1 = m->slab1; f.s1_ld = INP; f.s1_net = (int64_t)Hp * INP; f.s1_chunk = 2 * f.s1_net; f.s1_n = s1_n;
-  f.bslab = m->bslab; f.b_net = Hp; f.b_tile = 2 * Hp; f.b_n = fused ? (n + FU_BM_TRAIN - 1) / FU_BM_TRAIN * (FU_BM_TRAIN / 32) : nt_row_tiles(n, Hp);
+  f.bslab = m->bslab; f.b_net = Hp; f.b_tile = 2 * Hp; f.b_n = fused ? (n + FU_BM - 1) / FU_BM * (FU_BM / 32) : nt_row_tiles(n, Hp);
   f.hpart = m->hpart; f.h_stride = 10 * Hp + 32; f.h_n = (n + HEAD_ROWS - 1) / HEAD_ROWS;
   f.ent_coef = ent_coef; f.inv_count = inv_count; f.log_std = m->k.log_std;
   f.grad = grad_out; f.stats = stats_out; f.sumsq = m->partials + 2 * N_PARTIALS;
   f.step_counter = m->step_dev;
-  const int n_main = (int)((finalize_vec_items(L) * FIN_SPLIT + 255) / 256);
+  const int n_main = (int)((finalize_vec_items(L) + 255) / 256);
   m->n_finalize_blocks = n_main + (int)((finalize_wide_count(L) + 3 + 31) / 32);
   if (m->n_finalize_blocks > 2048) return fail(KP1_ERR_INVALID, "parameter vector too large for the sum-of-squares partial buffer");
   {
@@ -1891,9 +1802,9 @@ int kp1_mlp_time_kernels(kp1_mlp* m, const float* obs, int32_t obs_stride, int32
         t.dz2 = m->dz2; t.h1 = m->h1; t.dz1 = m->dz1; t.act_stride = act_stride; t.xf = m->xf;
         t.slab2 = m->slab; t.s2_net = (int64_t)Hp * Hp; t.s2_chunk = 2 * t.s2_net;
         t.slab1 = m->slab1; t.s1_net = (int64_t)Hp * INP; t.s1_chunk = 2 * t.s1_net;
-        t.groups = (n + FU_BM_TRAIN - 1) / FU_BM_TRAIN * (FU_BM_TRAIN / 8);   // the tile kernel writes whole 64-row tiles
-        t.cg2 = ((t.groups + KP1_TN_SPLIT2 - 1) / KP1_TN_SPLIT2 + 7) / 8 * 8;
-        t.cg1 = ((t.groups + KP1_TN_SPLIT1 - 1) / KP1_TN_SPLIT1 + 7) / 8 * 8;
+        t.groups = (n + FU_BM - 1) / FU_BM * (FU_BM / 8);   // the tile kernel writes whole 32-row tiles
+        t.cg2 = ((t.groups + TN_SPLIT2 - 1) / TN_SPLIT2 + 7) / 8 * 8;
+        t.cg1 = ((t.groups + TN_SPLIT1 - 1) / TN_SPLIT1 + 7) / 8 * 8;
         t.n_chunks2 = (t.groups + t.cg2 - 1) / t.cg2;
         t.n_chunks1 = (t.groups + t.cg1 - 1) / t.cg1;
         if (launch_tn_frag(t, stream) != KP1_OK) return KP1_ERR_NO_DEVICE;
@@ -1938,8 +1849,7 @@ int kp1_mlp_time_kernels(kp1_mlp* m, const float* obs, int32_t obs_stride, int32
 // of a CU), and the weight-gradient kernel makes the batch chunk the fast block index on the assumption that block b runs on XCD b % 8.  This
 // probe launches a kernel with the training tile's launch shape (grid, block, dynamic LDS, two workgroups per CU), keeps every workgroup resident
 // until all have arrived (bounded wait), and records where each one ran.
-__global__ void __launch_bounds__(FuGeom<true>::NTH, FuGeom<true>::WG_PER_CU * FuGeom<true>::NTH / 256) placement_probe_kernel(unsigned int* __restrict__ where, unsigned int* __restrict__ arrived,
-                                                                                                                            unsigned int total) {
+__global__ void __launch_bounds__(FU_NTH, 2) placement_probe_kernel(unsigned int* __restrict__ where, unsigned int* __restrict__ arrived, unsigned int total) {
   extern __shared__ float lds[];
   if (threadIdx.x == 0) {
     const unsigned int hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);      // HW_REG_HW_ID: wave, SIMD, pipe, CU, SH, SE
@@ -1960,18 +1870,17 @@ int kp1_mlp_placement_check(int32_t device, int32_t n_rows, int32_t* out, void* 
   if (!out || n_rows <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_mlp_placement_check");
   HIP_TRY(hipSetDevice(device));
   hipStream_t stream = (hipStream_t)stream_;
-  using G = FuGeom<true>;
   int n_cus = 0;
   HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
-  const dim3 grid((n_rows + G::BM - 1) / G::BM, 1, 2);
+  const dim3 grid((n_rows + FU_BM - 1) / FU_BM, 1, 2);
   const unsigned int total = grid.x * grid.z;
-  if ((int)total > G::WG_PER_CU * n_cus) return fail(KP1_ERR_UNSUPPORTED, "placement probe: the grid must be resident at once");
+  if ((int)total > 2 * n_cus) return fail(KP1_ERR_UNSUPPORTED, "placement probe: the grid must be resident at once");
   unsigned int* dev = nullptr;
   HIP_TRY(hipMalloc(&dev, sizeof(unsigned int) * (total + 1)));
   HIP_TRY(hipMemsetAsync(dev, 0, sizeof(unsigned int) * (total + 1), stream));
-  const size_t bytes = sizeof(float) * G::LDS_FLOATS;
+  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;
   HIP_TRY(hipFuncSetAttribute((const void*)placement_probe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  hipLaunchKernelGGL(placement_probe_kernel, grid, dim3(G::NTH), bytes, stream, dev, dev + total, total);
+  hipLaunchKernelGGL(placement_probe_kernel, grid, dim3(FU_NTH), bytes, stream, dev, dev + total, total);
   std::vector<unsigned int> host(total + 1);
   hipError_t e = hipMemcpyAsync(host.data(), dev, sizeof(unsigned int) * (total + 1), hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
@@ -2043,15 +1952,9 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   kfmt.formats = frag_only ? PACK_FRAG : (PACK_SLAB | PACK_FRAG);
   m->last_params = params;
   if (frag_only) m->slab_stale = true;
-  const bool vec4 = KP1_ADAM_VEC == 4 && ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-                                          reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0;
   const int* step_arg = step > 0 ? (const int*)nullptr : (const int*)m->step_dev;
-  if (vec4)
-    KP1_LAUNCH(adam_kernel<4>, dim3((unsigned)((n + 4 * KP1_ADAM_BLOCK - 1) / (4 * KP1_ADAM_BLOCK))), dim3(KP1_ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
-                       n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1);
-  else
-    KP1_LAUNCH(adam_kernel<1>, dim3((unsigned)((n + KP1_ADAM_BLOCK - 1) / KP1_ADAM_BLOCK)), dim3(KP1_ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
-                       n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1);
+  KP1_LAUNCH(adam_kernel, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK)), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
+             n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }

@@ -1,21 +1,22 @@
 // kp1_mlp_fused.inc -- the weight-gradient GEMMs of the fused PPO update (H = 256): they read the k8-fragment-major activation tiles
 // mlp_tile_kernel (kp1_mlp_tile.inc, included before this file) wrote.  Included by kp1_mlp.hip inside its anonymous namespace.
 //
-// [r2] A "uniform" variant -- one 8-wave workgroup per CU, waves 0-3 / 4-7 splitting the batch rows of a chunk and adding their partial
-// tiles in LDS, then a quarter-size dW1 unit in the same workgroup -- was built to put two operand-streaming waves on every SIMD.  It
-// measured SLOWER than this round-1 arrangement (4-wave workgroups, two per CU, quarter-size dW1 workgroups co-resident with the dW2
-// ones): 33.0 vs 29.9 us back to back, 34.1 vs 30.3 us in situ (profiles/r02_ab_tn_round1_vs_uniform.log) -- the two extra barriers and
-// the LDS add of the combine, and a second prologue for the dW1 unit, cost more than the second wave per SIMD hides.  Reverted.
+// (An 8-wave "uniform" variant with both batch halves and a dW1 unit in one workgroup measured slower in round 2 and was reverted:
+// profiles/r02_ab_tn_round1_vs_uniform.log.)
 
 // ---------------------------------------------------------------------------------------------- weight gradients
 // dW2[o][i] = sum_b dZ2[b][o] h1[b][i] and dW1[o][i] = sum_b dZ1[b][o] X[b][i] for both nets in ONE launch, reading the
 // k8-fragment-major activations the tile kernel wrote: a lane's A operand (column o of dZ) and B operand (column i of h1 / X)
 // for four consecutive MFMAs is one float4, one 8-row group of one 32-column block is one coalesced 1 KB wave load, and
 // nothing is staged through LDS -- no barrier in the reduction loop, two workgroups per CU.
-// Workgroups [0, 8 * n_chunks2): dW2, tile 128 x 128 (4 waves 2 x 2, wave tile 64 x 64) over `cg2` 8-row groups each;
-// then 4 * n_chunks1 workgroups: dW1, tile 128 x 64 (wave tile 64 x 32) over `cg1` groups -- sized a quarter of a dW2
-// workgroup so every CU ends up with 1 + 1/4 units of MFMA work.  Each workgroup writes its partial tile with plain
-// float4 stores (through an LDS transpose) into the slabs grad_finalize_kernel sums in fixed order.
+// A workgroup owns a 64 x 64 tile of dW2 (32 x inp of dW1) over 1/8 (1/16) of the batch and its four waves split those batch rows:
+// every wave accumulates the WHOLE tile over its quarter of the rows (wave tile 64 x 64), the four partial tiles are added through LDS
+// in wave order (fixed order: bitwise reproducible) and ONE tile leaves the workgroup, as float4 stores into the slabs
+// grad_finalize_kernel sums in fixed order: 8 dW2 + 16 dW1 slabs, 6.3 MB per step.  (The round-1 form -- 128 x 128 tiles over 1/32 of
+// the batch, 32 partial slabs per weight, 24.6 MB -- was measured slower and removed: DESIGN.md 4.3.)  Every operand column block is read
+// by four workgroups; the block index is laid out so that those four run on ONE XCD under the round-robin dispatch (chunk = blockIdx % 8:
+// an XCD's 32 + 32 workgroups stream the same 1024 batch rows through its L2 together) -- placement is a speed assumption only, a
+// different one costs L2 hits, never correctness.
 struct TnFragArgs {
   const float* dz2; const float* h1; const float* dz1; int64_t act_stride;  // [2][rows x 256] k8-fragment major
   const float* xf; int inp;                                                 // [rows x inp], inp = 64 or 128
@@ -24,129 +25,6 @@ struct TnFragArgs {
   int groups, cg2, n_chunks2, cg1, n_chunks1;
 };
 
-template <int CI>
-__device__ __forceinline__ void tn_frag_tile(const float* __restrict__ Af, int a_ncb, const float* __restrict__ Bf, int b_ncb, int g_begin, int g_end,
-                                             float* __restrict__ out, int out_ld, float* lds) {
-  constexpr int SG = 4;  // 8-row groups per register set; two sets alternate (loads of one under the MFMAs of the other)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
-  // this wave's column blocks: A (o) blocks 2*wr, 2*wr+1 of the tile; B (i) blocks CI*wc .. of the tile
-  const float* __restrict__ ap = Af + ((2 * wr) * 64 + lane) * 4;
-  const float* __restrict__ bp = Bf + ((CI * wc) * 64 + lane) * 4;
-  const int64_t a_gs = (int64_t)a_ncb * 256, b_gs = (int64_t)b_ncb * 256;  // floats per 8-row group
-  f32x4 ra[2][SG][2], rb[2][SG][CI];
-  f32x16 acc[2][CI];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int c = 0; c < CI; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[r][c][e] = 0.f;
-  const int g_last = g_end - 1;
-  KP1_TR(12)
-  KP1_TR_HW(11)
-  // Groups past the end of the chunk are clamped to its last group and their A operand is multiplied by 0: the loop body
-  // has no branch (a conditional MFMA block made the compiler copy all accumulators through v_mov after every group).
-  // The multiply is not overhead: with global loads in flight, MFMAs that read the loaded registers directly and issue back
-  // to back run at 40-55 ns each instead of 30 (tools/mfma_load_mix.hip, profiles/r01_mfma_load_mix.log); one VALU
-  // instruction per MFMA pair restores the pipe rate (an unmasked fast path for full chunks measured 42 us against 29 us).
-#define KP1_TNF_LOAD(set, g0)                                                                           \
-  _Pragma("unroll") for (int u = 0; u < SG; ++u) {                                                      \
-    const int gg_ = min((g0) + u, g_last);                                                              \
-    _Pragma("unroll") for (int r = 0; r < 2; ++r) ra[set][u][r] = load16<KP1_TNF_LD_NT>(ap + gg_ * a_gs + r * 256); \
-    _Pragma("unroll") for (int c = 0; c < CI; ++c) rb[set][u][c] = load16<KP1_TNF_LD_NT>(bp + gg_ * b_gs + c * 256); \
-  }
-#ifdef KP1_TNF_NOMFMA   // developer experiment (tools/nt_timeline.py): memory stream only
-#define KP1_TNF_MFMA(set, g0)                                                                           \
-  _Pragma("unroll") for (int u = 0; u < SG; ++u)                                                        \
-    _Pragma("unroll") for (int r = 0; r < 2; ++r)                                                       \
-      _Pragma("unroll") for (int c = 0; c < CI; ++c) acc[r][c][0] += ra[set][u][r][0] * rb[set][u][c][0] + ra[set][u][r][3] * rb[set][u][c][3];
-#else
-#define KP1_TNF_MFMA(set, g0)                                                                           \
-  _Pragma("unroll") for (int u = 0; u < SG; ++u) {                                                      \
-    const float keep_ = (g0) + u < g_end ? 1.f : 0.f;                                                   \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                       \
-      _Pragma("unroll") for (int r = 0; r < 2; ++r)                                                     \
-        _Pragma("unroll") for (int c = 0; c < CI; ++c)                                                  \
-          acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[set][u][r][i] * keep_, rb[set][u][c][i], acc[r][c], 0, 0, 0); \
-  }
-#endif
-  KP1_TNF_LOAD(0, g_begin)
-  for (int g = g_begin; g < g_end; g += 2 * SG) {
-    KP1_TNF_LOAD(1, g + SG)
-    __builtin_amdgcn_sched_barrier(0);
-    KP1_TNF_MFMA(0, g)
-    __builtin_amdgcn_sched_barrier(0);
-    KP1_TNF_LOAD(0, g + 2 * SG)
-    __builtin_amdgcn_sched_barrier(0);
-    KP1_TNF_MFMA(1, g + SG)
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#undef KP1_TNF_LOAD
-#undef KP1_TNF_MFMA
-  KP1_TR(13)
-  // partial tile -> slab through LDS so rows leave as float4
-  constexpr int TI = 64 * CI, LDP = TI + 4;
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int c = 0; c < CI; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int o = wr * 64 + r * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        lds[o * LDP + wc * 32 * CI + c * 32 + (lane & 31)] = acc[r][c][e];
-      }
-  __syncthreads();
-  KP1_TR(14)
-  constexpr int Q = TI / 4;
-#pragma unroll
-  for (int j = 0; j < 128 * Q / 256; ++j) {
-    const int f = tid + 256 * j, o = f / Q, q = f % Q;
-    store16<KP1_TNF_ST_AUX>(out, (int64_t)o * out_ld + 4 * q, *reinterpret_cast<const f32x4*>(lds + o * LDP + 4 * q));
-  }
-  KP1_TR(15)
-}
-
-__global__ void __launch_bounds__(256, 2) gemm_tn_frag_kernel(const TnFragArgs a) {
-  extern __shared__ float lds[];
-  const int n2 = 8 * a.n_chunks2;
-  if ((int)blockIdx.x < n2) {
-    const int tile = blockIdx.x / a.n_chunks2, chunk = blockIdx.x % a.n_chunks2;
-    const int net = tile >> 2, ot = (tile >> 1) & 1, it = tile & 1;
-    const int g0 = chunk * a.cg2, g1 = min(g0 + a.cg2, a.groups);
-    float* out = a.slab2 + chunk * a.s2_chunk + net * a.s2_net + (int64_t)(ot * 128) * FU_HP + it * 128;
-    if (g0 >= g1) {  // empty chunk: the finalize kernel still reads this slot
-      for (int f = threadIdx.x; f < 128 * 32; f += 256) *reinterpret_cast<f32x4*>(out + (int64_t)(f >> 5) * FU_HP + 4 * (f & 31)) = f32x4{0.f, 0.f, 0.f, 0.f};
-      return;
-    }
-    tn_frag_tile<2>(a.dz2 + net * a.act_stride + (ot * 4) * 256, 8, a.h1 + net * a.act_stride + (it * 4) * 256, 8, g0, g1, out, FU_HP, lds);
-  } else {
-    const int id = blockIdx.x - n2;
-    const int tile = id / a.n_chunks1, chunk = id % a.n_chunks1;
-    const int net = tile >> 1, ot = tile & 1;
-    const int g0 = chunk * a.cg1, g1 = min(g0 + a.cg1, a.groups);
-    const int inp = a.inp, q4 = inp >> 2;
-    float* out = a.slab1 + chunk * a.s1_chunk + net * a.s1_net + (int64_t)(ot * 128) * inp;
-    if (g0 >= g1) {
-      for (int f = threadIdx.x; f < 128 * q4; f += 256) *reinterpret_cast<f32x4*>(out + (int64_t)(f / q4) * inp + 4 * (f % q4)) = f32x4{0.f, 0.f, 0.f, 0.f};
-      return;
-    }
-    if (inp == 64)   // uniform per launch
-      tn_frag_tile<1>(a.dz1 + net * a.act_stride + (ot * 4) * 256, 8, a.xf, 2, g0, g1, out, 64, lds);
-    else
-      tn_frag_tile<2>(a.dz1 + net * a.act_stride + (ot * 4) * 256, 8, a.xf, 4, g0, g1, out, 128, lds);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------- weight gradients, wave-split form
-// [r2] Same GEMMs, same operands, other decomposition (KP1_TN_FORM = 1).  The arrangement above gives every workgroup a 128 x 128 output
-// tile over 1/32 of the batch, i.e. 32 partial slabs per weight (24.6 MB written and read back by grad_finalize_kernel per optimiser
-// step, 50 x the size of the result).  Here a workgroup owns a 64 x 64 tile of dW2 (32 x inp of dW1) over 1/8 (1/16) of the batch and
-// its four waves split those batch rows: every wave accumulates the WHOLE tile over its quarter of the rows (wave tile 64 x 64, the same
-// registers, loads per MFMA and MFMAs per wave as before), the four partial tiles are added through LDS in wave order (fixed order:
-// still bitwise reproducible) and ONE tile leaves the workgroup: 8 dW2 + 16 dW1 slabs, 6.3 MB per step.  The smaller tile reads every
-// operand column block from four workgroups instead of two; the block index is laid out so that those four run on ONE XCD under the
-// round-robin dispatch (chunk = blockIdx % 8: an XCD's 32 + 32 workgroups stream the same 1024 batch rows through its L2 together) --
-// placement is a speed assumption only, a different one costs L2 hits, never correctness.
 template <int RA, int CB>
 __device__ __forceinline__ void tn_split_tile(const float* __restrict__ Af, int a_ncb, const float* __restrict__ Bf, int b_ncb, int g_begin, int g_end,
                                               float* __restrict__ out, int out_ld, float* lds) {
@@ -167,13 +45,16 @@ __device__ __forceinline__ void tn_split_tile(const float* __restrict__ Af, int 
   KP1_TR_HW(11)
   if (gb < ge) {   // wave-uniform
     const int g_last = ge - 1;
-    // groups past the end of the range are clamped to its last group and their A operand is multiplied by 0 (see tn_frag_tile: the
-    // multiply also keeps the MFMA pipe at its rate while global loads are in flight)
+    // Groups past the end of the range are clamped to its last group and their A operand is multiplied by 0: the loop body
+    // has no branch (a conditional MFMA block made the compiler copy all accumulators through v_mov after every group).
+    // The multiply is not overhead: with global loads in flight, MFMAs that read the loaded registers directly and issue back
+    // to back run at 40-55 ns each instead of 30 (tools/mfma_load_mix.hip, profiles/r01_mfma_load_mix.log); one VALU
+    // instruction per MFMA pair restores the pipe rate (an unmasked fast path for full chunks measured 42 us against 29 us).
 #define KP1_TNS_LOAD(set, g0)                                                                           \
   _Pragma("unroll") for (int u = 0; u < SG; ++u) {                                                      \
     const int gg_ = min((g0) + u, g_last);                                                              \
-    _Pragma("unroll") for (int r = 0; r < RA; ++r) ra[set][u][r] = load16_aux<KP1_TNS_LD_AUX>(Af, lane * 4 + gg_ * a_gs + r * 256); \
-    _Pragma("unroll") for (int c = 0; c < CB; ++c) rb[set][u][c] = load16_aux<KP1_TNS_LD_AUX>(Bf, lane * 4 + gg_ * b_gs + c * 256); \
+    _Pragma("unroll") for (int r = 0; r < RA; ++r) ra[set][u][r] = load16_sc1(Af, lane * 4 + gg_ * a_gs + r * 256); \
+    _Pragma("unroll") for (int c = 0; c < CB; ++c) rb[set][u][c] = load16_sc1(Bf, lane * 4 + gg_ * b_gs + c * 256); \
   }
 #define KP1_TNS_MFMA(set, g0)                                                                           \
   _Pragma("unroll") for (int u = 0; u < SG; ++u) {                                                      \
@@ -218,11 +99,11 @@ __device__ __forceinline__ void tn_split_tile(const float* __restrict__ Af, int 
     const float* p0 = lds + o * LDP + 4 * q;
     const f32x4 v = ((*reinterpret_cast<const f32x4*>(p0) + *reinterpret_cast<const f32x4*>(p0 + TO * LDP)) +
                      *reinterpret_cast<const f32x4*>(p0 + 2 * TO * LDP)) + *reinterpret_cast<const f32x4*>(p0 + 3 * TO * LDP);
-    store16<KP1_TNF_ST_AUX>(out, (int64_t)o * out_ld + 4 * q, v);
+    store16_sc1(out, (int64_t)o * out_ld + 4 * q, v);
   }
   KP1_TR(15)
 }
-constexpr int TN_SPLIT_LDS_FLOATS = 4 * 64 * (64 + 8);   // the largest of the three tile forms: 4 x 64 x 72 (dW2), 4 x 32 x 72, 4 x 32 x 104
+constexpr int TN_SPLIT_LDS_FLOATS = 4 * 64 * (64 + 8);   // the largest of the three tile shapes: 4 x 64 x 72 (dW2), 4 x 32 x 72, 4 x 32 x 104
 
 __global__ void __launch_bounds__(256, 2) gemm_tn_split_kernel(const TnFragArgs a) {
   extern __shared__ float lds[];
@@ -267,15 +148,10 @@ struct TnBf16Args {
   int frags, cf2, n_chunks2, cf1, n_chunks1;                                                          // 16-row fragments; per-chunk counts
 };
 
-// 16 bytes (8 bf16) at base[off] with the cache-policy bits of the exact kernel's operand loads
-template <int AUX>
+// 16 bytes (8 bf16) at base[off] with the cache-policy bits of the exact kernel's operand loads (sc1)
 __device__ __forceinline__ bf16x8 tnb_load(const unsigned short* __restrict__ base, int64_t off) {
-  if constexpr (AUX == 0) {
-    return *reinterpret_cast<const bf16x8*>(base + off);
-  } else {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(base), 0, 0x7fffffff, 0x00020000);
-    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(off * 2), 0, AUX));
-  }
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(base), 0, 0x7fffffff, 0x00020000);
+  return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(off * 2), 0, AUX_SC1));
 }
 
 template <int RA, int CB>
@@ -299,8 +175,8 @@ __device__ __forceinline__ void tn_bf16_tile(const unsigned short* __restrict__ 
   {                                                                                                     \
     const int ff_ = min((f0), f_last);                                                                  \
     _Pragma("unroll") for (int pl = 0; pl < 3; ++pl) {                                                  \
-      _Pragma("unroll") for (int r = 0; r < RA; ++r) ra[set][pl][r] = tnb_load<KP1_TNS_LD_AUX>(Af, lane * 8 + pl * a_plane + ff_ * a_fs + r * 512); \
-      _Pragma("unroll") for (int c = 0; c < CB; ++c) rb[set][pl][c] = tnb_load<KP1_TNS_LD_AUX>(Bf, lane * 8 + pl * b_plane + ff_ * b_fs + c * 512); \
+      _Pragma("unroll") for (int r = 0; r < RA; ++r) ra[set][pl][r] = tnb_load(Af, lane * 8 + pl * a_plane + ff_ * a_fs + r * 512); \
+      _Pragma("unroll") for (int c = 0; c < CB; ++c) rb[set][pl][c] = tnb_load(Bf, lane * 8 + pl * b_plane + ff_ * b_fs + c * 512); \
     }                                                                                                   \
   }
 #define KP1_TNB_MFMA(set)                                                                               \
@@ -348,7 +224,7 @@ __device__ __forceinline__ void tn_bf16_tile(const unsigned short* __restrict__ 
     const float* p0 = lds + o * LDP + 4 * q;
     const f32x4 v = ((*reinterpret_cast<const f32x4*>(p0) + *reinterpret_cast<const f32x4*>(p0 + TO * LDP)) +
                      *reinterpret_cast<const f32x4*>(p0 + 2 * TO * LDP)) + *reinterpret_cast<const f32x4*>(p0 + 3 * TO * LDP);
-    store16<KP1_TNF_ST_AUX>(out, (int64_t)o * out_ld + 4 * q, v);
+    store16_sc1(out, (int64_t)o * out_ld + 4 * q, v);
   }
 }
 

@@ -12,7 +12,7 @@
 // X / h1 / dZ2 / dZ1 tiles are also written to HBM (fire-and-forget stores that drain under the next GEMM) because the
 // weight-gradient GEMMs (dW2 = dZ2^T h1, dW1 = dZ1^T X) reduce over the whole minibatch; h2 never leaves LDS.  They are
 // written "k8-fragment major" (frag8_at below): [row/8][col/32][lane = col%32 + 32*((row%8)/4)][row%4], the float4 a lane
-// of gemm_tn_frag_kernel feeds to four consecutive MFMAs as A or B operand, so that kernel needs no LDS staging either.
+// of gemm_tn_split_kernel feeds to four consecutive MFMAs as A or B operand, so that kernel needs no LDS staging either.
 // That order is also the order a lane holds a 32x32 MFMA accumulator block in (elements 4g .. 4g+3 = rows 8g + 4*(lane/32) .. +3
 // of column lane%32), so h1 and dZ1 leave straight from the accumulator registers as coalesced 1 KB wave stores.
 // The policy loss needs only the policy net's outputs and the value loss only the value net's, so the two nets are
@@ -25,19 +25,14 @@
 // streams only the weight columns it owns: there is NO barrier inside a GEMM, waves drift apart freely, and the
 // stream runs two stages ahead ACROSS the three GEMMs (18 stages, register ring of 3).
 //
-// Geometry (FuGeom): RB 32-row blocks per wave, 4 * RB waves, 8 / (4 * RB) column blocks per wave.
-//   RB = 1 (inference, and training by default): BM = 32 rows, 4 waves x 2 column blocks, 78.6 KB LDS -> TWO workgroups per CU, so one
-//     tile's epilogue / head phase / load latency hides under the other tile's MFMAs; training holds the second workgroup of a CU back
-//     by 11 us (12 in rounds 1-2) so the two do not run their phases in lockstep.  Every weight float4 serves 32 rows: 302 MB pulled from L2 per 8192-row
-//     launch (the kernel with the MFMAs removed still takes 29.7 of its 51.2 us, profiles/r02_ab_tile32_decomposition.log).
-//   RB = 2 (-DKP1_FU_TRAIN_RB=2, built and measured in round 2, NOT the default): BM = 64 rows, 8 waves, a wave owns one column block
-//     and both row blocks, one workgroup per CU (149 KB LDS).  Each weight float4 feeds two MFMAs and the L2 stream halves (the
-//     MFMA-less kernel drops to 24.2 us), but the CU's eight waves now run every phase in step and nothing covers the non-GEMM
-//     phases: 53.5 us back to back, 56.7 us in situ against 52-53 us for RB = 1 (profiles/r02_ab_tile_geometry_in_situ.log,
-//     timeline profiles/r02_tile64_timeline.log: prologue 2.1, G1 6.1, G2 19.0, heads 6.2 / 2.9, G3 17.8 us; 32.2 us of that is MFMA).
+// Geometry: BM = 32 rows, 4 waves x 2 column blocks, 78.6 KB LDS -> TWO workgroups per CU, so one tile's epilogue / head phase / load
+// latency hides under the other tile's MFMAs; training holds the second workgroup of a CU back by 11 us (12 in rounds 1-2) so the two
+// do not run their phases in lockstep.  Every weight float4 serves 32 rows: 302 MB pulled from L2 per 8192-row launch (the kernel with
+// the MFMAs removed still takes 29.7 of its 51.2 us, profiles/r02_ab_tile32_decomposition.log).  64-row training tiles (one 8-wave
+// workgroup per CU) and 8 waves per 32-row tile were measured slower and removed (DESIGN.md 4.1, 4.7).
 //
 // Every per-tile gradient partial (head weights, biases, log_std, loss sums) is written with plain stores into the same
-// hpart / bslab layout head_train_kernel and the dtanh epilogue use, one slot per 32 ROWS (a 64-row workgroup fills two);
+// hpart / bslab layout head_train_kernel and the dtanh epilogue use, one slot per 32-row tile;
 // sums inside the workgroup use shuffles / LDS in a fixed order (no float atomics anywhere => bitwise reproducible).
 
 struct FusedArgs {
@@ -94,49 +89,21 @@ __host__ __device__ inline int64_t frag8_at(int64_t b, int64_t col, int64_t C) {
   return ((b >> 3) * (C >> 5) + (col >> 5)) * 256 + ((col & 31) + 32 * ((b & 7) >> 2)) * 4 + (b & 3);
 }
 
-#ifndef KP1_FU_LD_AUX
-// cache policy bits of the weight-fragment loads (buffer loads; 0 = plain global loads, 1 sc0, 2 nt, 16 sc1).  The weight stream has no reuse
-// inside a CU (every wave streams its own columns once per tile), and pulled through the CU's L1 it evicts what does (observation rows, loss
-// inputs): sc1 / sc0 loads -- served by the L2, not allocated in the L1 -- take the training tile from 48.2 to 47.4 us and the rollout tile along
-// with it; nt is 2 us SLOWER (profiles/r03_ab_tile_weight_load_policy.log).
-#define KP1_FU_LD_AUX 16
-#endif
-template <int AUX>
+// The weight-fragment loads are sc1 buffer loads.  The weight stream has no reuse inside a CU (every wave streams its own columns once per
+// tile), and pulled through the CU's L1 it evicts what does (observation rows, loss inputs): sc1 / sc0 loads -- served by the L2, not
+// allocated in the L1 -- take the training tile from 48.2 to 47.4 us and the rollout tile along with it; nt is 2 us SLOWER
+// (profiles/r03_ab_tile_weight_load_policy.log).
 __device__ __forceinline__ f32x4 fu_wload(const char* __restrict__ base, unsigned off) {
-  if constexpr (AUX == 0) {
-    return *reinterpret_cast<const f32x4*>(base + off);
-  } else {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, 0x7fffffff, 0x00020000);
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, AUX));
-  }
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, 0x7fffffff, 0x00020000);
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, AUX_SC1));
 }
 constexpr int FU_HP = 256, FU_BKS = 32, FU_AP = FU_HP + 4;
 constexpr int FU_STAGE = FU_HP * FU_BKS;  // floats of one 32-deep weight stage of one net
-#ifndef KP1_FU_TRAIN_RB
-#define KP1_FU_TRAIN_RB 1   // 1: 32-row training tiles, two staggered workgroups per CU; 2: 64-row tiles, one 8-wave workgroup per CU
-#endif
-// [r3] KP1_FU_TRAIN_WPB: waves per 32-row block of a training tile.  4 (rounds 1-2): a wave owns two 32-column blocks, a CU's two tiles put TWO
-// waves on a SIMD while both run and ONE while a tile runs alone (the first 12 us and the last ~10 us of a launch, at ~43 % matrix utilisation:
-// DESIGN.md 4.5).  8: a wave owns one column block, the same two tiles per CU are FOUR waves per SIMD together and two alone -- the lone phases
-// have a second instruction stream to cover LDS / weight-load / barrier latency with.  Same arithmetic per output element (one wave, same k order).
-#ifndef KP1_FU_TRAIN_WPB
-#define KP1_FU_TRAIN_WPB 4
-#endif
-template <bool TRAIN>
-struct FuGeom {
-  static constexpr int RB = TRAIN ? KP1_FU_TRAIN_RB : 1;   // 32-row blocks per wave (= per workgroup)
-  static constexpr int WPB = (TRAIN && KP1_FU_TRAIN_RB == 1) ? KP1_FU_TRAIN_WPB : 4;   // waves per 32-row block
-  static constexpr int NW = WPB * RB;        // waves
-  static constexpr int CB = 8 / NW;          // 32-column blocks per wave
-  static constexpr int BM = 32 * RB, NTH = 64 * NW;
-  static constexpr int WG_PER_CU = RB == 1 ? 2 : 1;
-  // dot partials [4 k-quarters][BM][8], dOut [BM][8], per-wave sums [NW][24], misc [64]
-  static constexpr int SCRATCH = 4 * BM * 8 + BM * 8 + NW * 24 + 64;
-  static constexpr int LDS_FLOATS = 2 * BM * FU_AP + HEADS * FU_HP + SCRATCH;
-};
-static_assert(KP1_FU_TRAIN_WPB == 4 || KP1_FU_TRAIN_WPB == 8, "waves per 32-row block: 4 or 8");
-constexpr int FU_BM_TRAIN = FuGeom<true>::BM, FU_BM_INFER = FuGeom<false>::BM;
-static_assert(FuGeom<true>::LDS_FLOATS * 4 * FuGeom<true>::WG_PER_CU <= 160 * 1024, "the training tiles of one CU must fit its LDS");
+constexpr int FU_BM = 32, FU_NW = 4, FU_CB = 2, FU_NTH = 64 * FU_NW;   // rows, waves, 32-column blocks per wave, threads
+// dot partials [4 k-quarters][BM][8], dOut [BM][8], per-wave sums [NW][24], misc [64]
+constexpr int FU_SCRATCH = 4 * FU_BM * 8 + FU_BM * 8 + FU_NW * 24 + 64;
+constexpr int FU_LDS_FLOATS = 2 * FU_BM * FU_AP + HEADS * FU_HP + FU_SCRATCH;
+static_assert(FU_LDS_FLOATS * 4 * 2 <= 160 * 1024, "the two training tiles of one CU must fit its LDS");
 
 // TRAIN = false stops after the heads: layer 1 + layer 2 + heads + Gaussian sampling in one launch (replaces two gemm_nt
 // launches and head_infer_kernel in the rollout), nothing but the requested outputs is written.
@@ -148,19 +115,15 @@ static_assert(FuGeom<true>::LDS_FLOATS * 4 * FuGeom<true>::WG_PER_CU <= 160 * 10
 // SPLIT (training only, [r3 experiment]): the activations leave as three bf16 planes instead of the fp32 k8-fragment copies.  A separate
 // instantiation: the exact kernel carries none of its code (as run-time branches in one kernel the extra stores cost the exact path 1 us per launch).
 template <bool TRAIN, int K1S, int ENV = 0, bool SPLIT = false>
-__global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::WG_PER_CU * FuGeom<TRAIN>::NTH / 256) mlp_tile_kernel(const FusedArgs a) {
+__global__ void __launch_bounds__(FU_NTH, ENV ? 1 : 2) mlp_tile_kernel(const FusedArgs a) {
   static_assert(!(TRAIN && ENV), "the env step rides on the inference tile only");
   static_assert(TRAIN || !SPLIT, "split planes are written by the training tile");
-  using G = FuGeom<TRAIN>;
-  constexpr int RB = G::RB, NW = G::NW, CB = G::CB, BM = G::BM, NTH = G::NTH, CW = 32 * CB, WPB = G::WPB;
+  constexpr int NW = FU_NW, CB = FU_CB, BM = FU_BM, NTH = FU_NTH, CW = 32 * CB;
   constexpr int INP = K1S * FU_BKS, FU_XP = INP + 4, GS_L2 = K1S, GS_BW = K1S + 8, GS_END = K1S + 16;
   constexpr int KG = FU_BKS / 8, NB = CB * KG;  // B-operand float4 per lane per stage
   // 8-deep k groups of layer 1 that hold observation columns: 56 floats = 7 of the 8 groups of the 64-deep layout, 80 (route keys) = 10 of 16;
   // the rest is zero padding on both operands, and its MFMAs (1.4 % of a training tile's, 19 % of layer 1's with the route keys) are skipped
-#ifndef KP1_FU_L1_TRIM
-#define KP1_FU_L1_TRIM 1
-#endif
-  constexpr int L1_REAL_GROUPS = KP1_FU_L1_TRIM ? (K1S == 2 ? (KP1_MLP_IN + 7) / 8 : (KP1_MLP_IN_ROUTE + 7) / 8) : K1S * KG;
+  constexpr int L1_REAL_GROUPS = K1S == 2 ? (KP1_MLP_IN + 7) / 8 : (KP1_MLP_IN_ROUTE + 7) / 8;
   extern __shared__ float lds[];
   float* bufA = lds;
   float* bufB = bufA + BM * FU_AP;
@@ -170,11 +133,8 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
   float* wsum = dout + BM * 8;         // [NW waves][24] per-wave sums
   float* misc = wsum + NW * 24;        // [0] adv mean, [1] adv 1/std
 
-#ifndef KP1_FU_SWAP_NETS
-#define KP1_FU_SWAP_NETS 0   // 1: the value-net tiles are dispatched first and the policy-net tiles are the held-back ones (A/B switch)
-#endif
-  const int z = (TRAIN && KP1_FU_SWAP_NETS && gridDim.z == 2 ? 1 - (int)blockIdx.z : (int)blockIdx.z) + a.net_base;
-  const int m0 = blockIdx.x * BM, slot0 = blockIdx.x * RB;  // slot = 32-row partial slot
+  const int z = (int)blockIdx.z + a.net_base;
+  const int m0 = blockIdx.x * BM, slot = blockIdx.x;  // 32-row partial slot
   // the wave index is wave-uniform: taking it through readfirstlane puts it (and every address derived from it) into scalar registers, so
   // the weight-fragment loads use the scalar-base + 32-bit lane offset form and need no 64-bit vector address arithmetic
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -189,14 +149,14 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
 #define FU_BLOAD(gs)                                                                                    \
   if ((gs) < GS_END) {                                                                                  \
     const char* p_ = (gs) < GS_L2 ? W1F + (gs) * (FU_STAGE * 4) : ((gs) < GS_BW ? W2F + ((gs) - GS_L2) * (FU_STAGE * 4) : W2TF + ((gs) - GS_BW) * (FU_STAGE * 4)); \
-    _Pragma("unroll") for (int q = 0; q < NB; ++q) bf[(gs) % 3][q] = fu_wload<KP1_FU_LD_AUX>(p_, q * 1024 + lane_off); \
+    _Pragma("unroll") for (int q = 0; q < NB; ++q) bf[(gs) % 3][q] = fu_wload(p_, q * 1024 + lane_off); \
   }
-  f32x16 acc[RB][CB];
+  f32x16 acc[CB];
   // accumulators start at the layer bias of their column (a lane's 16 elements of a column block share one column): the bias add costs
   // no vector instruction in the epilogue -- vector instructions are paid in MFMA time on this hardware (see kp_tanh)
 #define FU_INIT_ACC(bias)                                                                               \
-  _Pragma("unroll") for (int r = 0; r < RB; ++r) _Pragma("unroll") for (int c = 0; c < CB; ++c)         \
-    _Pragma("unroll") for (int e = 0; e < 16; ++e) acc[r][c][e] = (bias)[c];
+  _Pragma("unroll") for (int c = 0; c < CB; ++c)                                                        \
+    _Pragma("unroll") for (int e = 0; e < 16; ++e) acc[c][e] = (bias)[c];
   // one GEMM of KT stages starting at global stage GS0; A rows from `abuf` (pitch ap).  The sched_barrier after the
   // weight loads keeps them at the top of the stage: left alone, the scheduler sinks every load down to its first use two
   // stages later ("load; s_waitcnt vmcnt(0); mfma"), which turns the prefetch ring into a chain of exposed L2 round trips.
@@ -207,7 +167,7 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
 #define KP1_TR_G2(slot) KP1_TR(slot)
 #define KP1_TR_HD(slot)
 #endif
-#ifdef KP1_FU_NOMFMA   // developer experiment (tools/ab_local.sh): everything but the matrix instructions
+#ifdef KP1_FU_NOMFMA   // developer experiment (tools/ab_build.sh): everything but the matrix instructions
 #define FU_MFMA(acc_, a_, b_) acc_[0] += (a_) * (b_);
 #else
 #define FU_MFMA(acc_, a_, b_) acc_ = __builtin_amdgcn_mfma_f32_32x32x2f32(a_, b_, acc_, 0, 0, 0);
@@ -217,56 +177,27 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
 #else
 #define FU_TANH(x) kp_tanh(x)
 #endif
-// KP1_FU_APREF = 1 reads the A fragments of stage s+1 from LDS BEFORE the matrix instructions of stage s are issued (two register sets):
-// measured slower in both geometries (32-row tiles in situ 53.6 vs 51.0 us, profiles/r02_ab_tile32_prefetch_copyb.log; 64-row 55.1 vs 53.5).
-#define FU_ALOAD(set, as_, ap, s_)                                                                      \
-  _Pragma("unroll") for (int r = 0; r < RB; ++r)                                                        \
-    _Pragma("unroll") for (int kg = 0; kg < KG; ++kg)                                                   \
-      av[set][r][kg] = *reinterpret_cast<const f32x4*>((as_) + r * 32 * (ap) + (s_) * FU_BKS + kg * 8);
-#ifndef KP1_FU_APREF
-#define KP1_FU_APREF 0
-#endif
-#if KP1_FU_APREF
+// (reading the A fragments of stage s+1 before the MFMAs of stage s was measured slower and removed: DESIGN.md 4.1)
 #define FU_GEMM(abuf, ap, KT, GS0)                                                                      \
   {                                                                                                     \
     const float* as = (abuf) + (lane & 31) * (ap) + 4 * (lane >> 5);                                     \
-    f32x4 av[2][RB][KG];                                                                                \
-    FU_ALOAD(0, as, ap, 0)                                                                              \
     _Pragma("unroll") for (int s = 0; s < (KT); ++s) {                                                  \
       FU_BLOAD((GS0) + s + 2)                                                                           \
-      if (s + 1 < (KT)) { FU_ALOAD((s + 1) & 1, as, ap, s + 1) }                                        \
       __builtin_amdgcn_sched_barrier(0);                                                                \
+      f32x4 av[KG];                                                                                     \
       _Pragma("unroll") for (int kg = 0; kg < KG; ++kg)                                                 \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                   \
-          _Pragma("unroll") for (int r = 0; r < RB; ++r)                                                \
-            _Pragma("unroll") for (int c = 0; c < CB; ++c)                                              \
-              FU_MFMA(acc[r][c], av[s & 1][r][kg][i], bf[((GS0) + s) % 3][c * KG + kg][i])              \
-      __builtin_amdgcn_sched_barrier(0);                                                                \
-      if ((GS0) == GS_L2) { KP1_TR_G2(7 + s) }                                                          \
-    }                                                                                                   \
-  }
-#else
-#define FU_GEMM(abuf, ap, KT, GS0)                                                                      \
-  {                                                                                                     \
-    const float* as = (abuf) + (lane & 31) * (ap) + 4 * (lane >> 5);                                     \
-    _Pragma("unroll") for (int s = 0; s < (KT); ++s) {                                                  \
-      FU_BLOAD((GS0) + s + 2)                                                                           \
-      __builtin_amdgcn_sched_barrier(0);                                                                \
-      f32x4 av[1][RB][KG];                                                                              \
-      FU_ALOAD(0, as, ap, s)                                                                            \
+        av[kg] = *reinterpret_cast<const f32x4*>(as + s * FU_BKS + kg * 8);                              \
       _Pragma("unroll") for (int kg = 0; kg < KG; ++kg)                                                 \
         if (!((GS0) == 0 && s * KG + kg >= L1_REAL_GROUPS))   /* layer 1: the k groups past the observation width are zero padding */ \
         _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                   \
-          _Pragma("unroll") for (int r = 0; r < RB; ++r)                                                \
-            _Pragma("unroll") for (int c = 0; c < CB; ++c)                                              \
-              FU_MFMA(acc[r][c], av[0][r][kg][i], bf[((GS0) + s) % 3][c * KG + kg][i])                  \
+          _Pragma("unroll") for (int c = 0; c < CB; ++c)                                                \
+            FU_MFMA(acc[c], av[kg][i], bf[((GS0) + s) % 3][c * KG + kg][i])                              \
       __builtin_amdgcn_sched_barrier(0);                                                                \
       if ((GS0) == GS_L2) { KP1_TR_G2(7 + s) }                                                          \
     }                                                                                                   \
   }
-#endif
-  // element e of block (r, c) of this lane's accumulators sits at (row, col) of the BM x 256 tile
-#define FU_ROW(r, e) (32 * (r) + ((e) & 3) + 8 * ((e) >> 2) + 4 * (lane >> 5))
+  // element e of block c of this lane's accumulators sits at (row, col) of the BM x 256 tile
+#define FU_ROW(e) (((e) & 3) + 8 * ((e) >> 2) + 4 * (lane >> 5))
 #define FU_COL(c) (wave * CW + (c) * 32 + (lane & 31))
   // accumulator blocks -> k8-fragment-major rows m0 .. m0+BM-1 of dst (256 columns): elements 4g .. 4g+3 of a block are one float4 of
   // that order, so every store instruction is one coalesced 1 KB wave store and nothing goes through LDS
@@ -274,20 +205,20 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
 #define FU_STORE_ACC(dst)
 #else
 #define FU_STORE_ACC(dst)                                                                               \
-  _Pragma("unroll") for (int r = 0; r < RB; ++r) _Pragma("unroll") for (int c = 0; c < CB; ++c)         \
+  _Pragma("unroll") for (int c = 0; c < CB; ++c)                                                        \
     _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                     \
-      const f32x4 v_ = {acc[r][c][4 * g], acc[r][c][4 * g + 1], acc[r][c][4 * g + 2], acc[r][c][4 * g + 3]}; \
-      store16<KP1_FU_ST_AUX>((dst), ((int64_t)((m0 >> 3) + 4 * r + g) * (FU_HP / 32) + wave * CB + c) * 256 + lane * 4, v_); \
+      const f32x4 v_ = {acc[c][4 * g], acc[c][4 * g + 1], acc[c][4 * g + 2], acc[c][4 * g + 3]};        \
+      *reinterpret_cast<f32x4*>((dst) + ((int64_t)((m0 >> 3) + g) * (FU_HP / 32) + wave * CB + c) * 256 + lane * 4) = v_; \
     }
 #endif
   // [r3 experiment] accumulator blocks -> the three bf16 planes (two 16-row fragments per 32-row block)
 #define FU_STORE_ACC_SPLIT(dst, plane)                                                                  \
   if constexpr (SPLIT) {                                                                               \
-    _Pragma("unroll") for (int r = 0; r < RB; ++r) _Pragma("unroll") for (int c = 0; c < CB; ++c)       \
+    _Pragma("unroll") for (int c = 0; c < CB; ++c)                                                      \
       _Pragma("unroll") for (int f = 0; f < 2; ++f) {                                                   \
         float v8_[8];                                                                                   \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) v8_[j] = acc[r][c][8 * f + j];                    \
-        store_split3((dst) + (int64_t)z * ((plane) / 2), (plane), (int64_t)(m0 >> 4) + 2 * r + f, FU_HP / 32, wave * CB + c, lane, split3(v8_)); \
+        _Pragma("unroll") for (int j = 0; j < 8; ++j) v8_[j] = acc[c][8 * f + j];                       \
+        store_split3((dst) + (int64_t)z * ((plane) / 2), (plane), (int64_t)(m0 >> 4) + f, FU_HP / 32, wave * CB + c, lane, split3(v8_)); \
       }                                                                                                 \
   }
   // [r3 experiment] LDS tile [BM][pitch] (C columns) -> the three bf16 planes; `zoff` selects the net's half of a plane (0 for X)
@@ -313,7 +244,7 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
     const float* t_ = (tile) + (8 * g_ + 4 * (lane >> 5)) * (pitch) + 32 * cb_ + (lane & 31);           \
     f32x4 v_;                                                                                           \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) v_[i] = t_[i * (pitch)];                              \
-    store16<KP1_FU_ST_AUX>((dst), ((int64_t)((m0 >> 3) + g_) * ((C) / 32) + cb_) * 256 + lane * 4, v_); \
+    *reinterpret_cast<f32x4*>((dst) + ((int64_t)((m0 >> 3) + g_) * ((C) / 32) + cb_) * 256 + lane * 4) = v_; \
   }
 #endif
 
@@ -323,7 +254,7 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
   // 32-row tiles: the first two workgroups of a CU (dispatch order k and k + #CUs) start together and, left alone, run every phase in
   // lockstep -- two tiles in an epilogue at once leave the matrix pipes idle.  Holding the second one back by more than the longest
   // non-GEMM phase keeps them apart for the whole tile (measured at M = 8192: 0 us -> 54.8, 6 -> 52.9, 12 -> 51.2 us per launch).
-  if (TRAIN && RB == 1 && a.stagger_ticks > 0) {
+  if (TRAIN && a.stagger_ticks > 0) {
     const int linear = blockIdx.x + gridDim.x * blockIdx.z;
     if (linear >= a.n_cus && linear < 2 * a.n_cus) {
       const unsigned long long t0_ = wall_clock64();
@@ -334,7 +265,7 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
   FU_BLOAD(1)
   __builtin_amdgcn_sched_barrier(0);
   {
-    constexpr int XQ = INP / 4, X_LOADS = BM * XQ / NTH;  // 2 (or 4; 1 or 2 with 8 waves per block) float4 per thread
+    constexpr int XQ = INP / 4, X_LOADS = BM * XQ / NTH;  // 2 (or 4) float4 per thread
     constexpr int W3_LOADS = HEADS * FU_HP / 4 / NTH;     // head weights: 2 (or 1) float4 per thread
     static_assert(X_LOADS >= 1 && X_LOADS * NTH == BM * XQ && W3_LOADS >= 1 && W3_LOADS * NTH == HEADS * FU_HP / 4, "prologue loads must tile the workgroup");
     int64_t xrow[X_LOADS];
@@ -396,12 +327,10 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
     bias1[c] = a.k.b1[z * FU_HP + FU_COL(c)];
     bias2[c] = a.k.b2[z * FU_HP + FU_COL(c)];
   }
-  // loss phase mapping: thread = (row tid>>3, head output tid&7); a wave covers 8 rows, waves 4s .. 4s+3 the 32-row slot s
-  // (with 8 waves per block the threads past BM * 8 have no row: l_ok is false for them and they only keep the barriers company)
+  // loss phase mapping: thread = (row tid>>3, head output tid&7); a wave covers 8 rows
   const int l_row = tid >> 3, l_out = tid & 7;
-  const bool l_has_row = l_row < BM;
-  const bool l_ok = l_has_row && m0 + l_row < a.n;
-  const int64_t l_src = a.idx ? a.idx[min(m0 + min(l_row, BM - 1), a.n - 1)] : (int64_t)min(m0 + min(l_row, BM - 1), a.n - 1);
+  const bool l_ok = m0 + l_row < a.n;
+  const int64_t l_src = a.idx ? a.idx[min(m0 + l_row, a.n - 1)] : (int64_t)min(m0 + l_row, a.n - 1);
   __syncthreads();
   KP1_TR(1)
   // (experiment mode writes ONLY the bf16 planes: the fp32 k8-fragment copies feed the exact weight-gradient kernel, which then does not run)
@@ -413,14 +342,12 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
   FU_INIT_ACC(bias1)
   FU_GEMM(bufB, FU_XP, K1S, 0)
 #pragma unroll
-  for (int r = 0; r < RB; ++r)
+  for (int c = 0; c < CB; ++c)
 #pragma unroll
-    for (int c = 0; c < CB; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        acc[r][c][e] = FU_TANH(acc[r][c][e]);
-        bufA[FU_ROW(r, e) * FU_AP + FU_COL(c)] = acc[r][c][e];
-      }
+    for (int e = 0; e < 16; ++e) {
+      acc[c][e] = FU_TANH(acc[c][e]);
+      bufA[FU_ROW(e) * FU_AP + FU_COL(c)] = acc[c][e];
+    }
   if (TRAIN && fp32_out) { FU_STORE_ACC(a.h1 + z * a.act_stride) }  // h1 tile -> HBM for the dW2 GEMM; nothing waits on these stores
   if (TRAIN) { FU_STORE_ACC_SPLIT(a.sp_h1, a.sp_plane) }
   __syncthreads();
@@ -444,26 +371,20 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
   FU_GEMM(bufA, FU_AP, 8, GS_L2)
   // bufB (X) was last read in G1, which every wave left before the barrier above
 #pragma unroll
-  for (int r = 0; r < RB; ++r)
+  for (int c = 0; c < CB; ++c)
 #pragma unroll
-    for (int c = 0; c < CB; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) bufB[FU_ROW(r, e) * FU_AP + FU_COL(c)] = FU_TANH(acc[r][c][e]);
+    for (int e = 0; e < 16; ++e) bufB[FU_ROW(e) * FU_AP + FU_COL(c)] = FU_TANH(acc[c][e]);
   __syncthreads();
   KP1_TR(3)
 
   // ------------------------------------------------------------------------------------------------ heads + loss
   {
-    // partial dot products: lane = (row of the wave's 32-row block, k half), wave = (32-row block, k quarter); the W3 reads are LDS broadcasts.
-    // Four waves per 32-row block do this (with WPB = 8 the other four wait at the barrier: the LDS budget of two tiles per CU has no room
-    // for eight sets of partials, and the phase is a fiftieth of the tile).
-    const int row = 32 * (wave >> 2) + (lane & 31), kq = wave & 3, part = kq * 2 + (lane >> 5);
+    // partial dot products: lane = (row, k half), wave = k quarter; the W3 reads are LDS broadcasts
+    const int row = lane & 31, kq = wave, part = kq * 2 + (lane >> 5);
     const float* hrow = bufB + row * FU_AP + part * 32;
     f32x4 hv[8];
-    if (wave < 4 * RB) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) hv[q] = *reinterpret_cast<const f32x4*>(hrow + 4 * q);
-    }
     auto dot = [&](int o) {
       const float* w = w3s + o * FU_HP + part * 32;
       float s = 0.f;
@@ -478,20 +399,18 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
       s += __shfl_xor(s, 32);
       if (lane < 32) dotred[(kq * BM + row) * 8 + o] = s;
     };
-    if (wave < 4 * RB) {
-      if (z == 0) {
+    if (z == 0) {
 #pragma unroll
-        for (int o = 0; o < ACT; ++o) dot(o);
-      } else {
-        dot(7);
-      }
+      for (int o = 0; o < ACT; ++o) dot(o);
+    } else {
+      dot(7);
     }
   }
   __syncthreads();
   KP1_TR_HD(7)
   if (!TRAIN) {
     // policy.forward tail (SB3 DiagGaussianDistribution): thread = (row, head output)
-    const bool mine = l_has_row && (z == 0 ? l_out < ACT : l_out == 7);
+    const bool mine = z == 0 ? l_out < ACT : l_out == 7;
     float v = 0.f;
     if (mine) {
 #pragma unroll
@@ -516,7 +435,7 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
       if (l_ok && l_out == 0 && a.log_prob) a.log_prob[l_src] = lp;
       if constexpr (ENV != 0) {
         // the tile's actions -> LDS (dout: [BM][8], idle in inference), then lane r of wave 0 steps env m0 + r; the other waves are done
-        if (l_has_row) dout[l_row * 8 + l_out] = (l_ok && l_out < ACT) ? act : 0.f;    // step_env_lane clips to [-1, 1] itself (arm_kinematic_env.py:214)
+        dout[l_row * 8 + l_out] = (l_ok && l_out < ACT) ? act : 0.f;    // step_env_lane clips to [-1, 1] itself (arm_kinematic_env.py:214)
         __syncthreads();
         if (wave == 0) {
           const bool live = lane < BM && m0 + lane < a.n;
@@ -534,7 +453,7 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
   {
     const int row_l = l_row, out = l_out;
     const bool ok = l_ok;
-    const bool mine = l_has_row && (z == 0 ? out < ACT : out == 7);
+    const bool mine = z == 0 ? out < ACT : out == 7;
     float v = 0.f;
     if (mine) {
 #pragma unroll
@@ -570,7 +489,7 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
       d = a.vf_coef * 2.f * (v - l_ret) * a.inv_count;
       vl = (l_ret - v) * (l_ret - v);
     }
-    if (l_has_row) dout[row_l * 8 + out] = (ok && mine) ? d : 0.f;
+    dout[row_l * 8 + out] = (ok && mine) ? d : 0.f;
     // per-wave sums over this wave's 8 rows (lanes with equal out): bias grads, log_std grads, loss terms
     float gls = (z == 0 && ok && out < ACT) ? g_logp * (zs * zs - 1.f) : 0.f;
     float dsum = (ok && mine) ? d : 0.f;
@@ -596,22 +515,20 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
   KP1_TR_HD(8)
   __syncthreads();
   KP1_TR_HD(9)
-  if (tid < 18 * RB) {
-    // per 32-row slot: 0..7 head-bias grads, 8..14 log_std grads, 15..17 loss sums (policy, value, kl); each net writes its own
-    const int s = tid / 18, k = tid % 18;
+  if (tid < 18) {
+    // 0..7 head-bias grads, 8..14 log_std grads, 15..17 loss sums (policy, value, kl); each net writes its own
+    const int k = tid;
     const int w = k < 8 ? k : (k < 15 ? 8 + (k - 8) : 16 + (k - 15));
-    const float* ws = wsum + 4 * s * 24;   // the slot's four waves, summed in wave order
-    const float v = ((ws[w] + ws[24 + w]) + ws[48 + w]) + ws[72 + w];
+    const float v = ((wsum[w] + wsum[24 + w]) + wsum[48 + w]) + wsum[72 + w];   // the four waves, summed in wave order
     const bool pi_slot = (k < 7) || (k >= 8 && k < 15) || k == 15 || k == 17;
-    if (pi_slot == (z == 0)) a.hpart[(int64_t)(slot0 + s) * a.hpart_stride + 10 * FU_HP + k] = v;
+    if (pi_slot == (z == 0)) a.hpart[(int64_t)slot * a.hpart_stride + 10 * FU_HP + k] = v;
   }
   {
-    // dZ2 = (dOut W3) * (1 - h2^2) in place.  Wave = (32-row block, 256 / WPB-column range), lane = (column group cg of 4, row group rg):
-    // 16 column groups x 4 row groups of 8 rows (WPB = 4) or 8 x 8 of 4 rows (WPB = 8); the head-weight and bias-2 gradient partials are then
-    // summed over the row groups by shuffles -- no LDS, no barrier.
-    constexpr int DZ_COLS = FU_HP / WPB, DZ_CG = DZ_COLS / 4, DZ_RG = 64 / DZ_CG, DZ_ROWS = 32 / DZ_RG;
-    const int cg = lane % DZ_CG, rg = lane / DZ_CG, rh = wave / WPB, col = (wave % WPB) * DZ_COLS + 4 * cg;
-    float* part = a.hpart + (int64_t)(slot0 + rh) * a.hpart_stride;
+    // dZ2 = (dOut W3) * (1 - h2^2) in place.  Wave = 64-column range, lane = (column group cg of 4, row group rg): 16 column groups x
+    // 4 row groups of 8 rows; the head-weight and bias-2 gradient partials are then summed over the row groups by shuffles -- no LDS, no barrier.
+    constexpr int DZ_COLS = FU_HP / NW, DZ_CG = DZ_COLS / 4, DZ_RG = 64 / DZ_CG, DZ_ROWS = 32 / DZ_RG;
+    const int cg = lane % DZ_CG, rg = lane / DZ_CG, col = wave * DZ_COLS + 4 * cg;
+    float* part = a.hpart + (int64_t)slot * a.hpart_stride;
     f32x4 gw[ACT], gb2 = {0.f, 0.f, 0.f, 0.f}, w3c[ACT];
 #pragma unroll
     for (int o = 0; o < ACT; ++o) {
@@ -626,7 +543,7 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
     }
 #pragma unroll
     for (int j = 0; j < DZ_ROWS; ++j) {
-      const int row = 32 * rh + rg * DZ_ROWS + j;
+      const int row = rg * DZ_ROWS + j;
       const f32x4 h = *reinterpret_cast<const f32x4*>(bufB + row * FU_AP + col);
       f32x4 dp = {0.f, 0.f, 0.f, 0.f};
       if (z == 0) {
@@ -683,20 +600,19 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
     FU_INIT_ACC(zero)
   }
   FU_GEMM(bufB, FU_AP, 8, GS_BW)
-  // dZ1 = acc * (1 - h1^2) with h1 read back from the positions this lane wrote after G1; column sums of each 32-row block are the
-  // bias-1 gradient partials of its slot; dZ1 leaves from the registers
-#pragma unroll
-  for (int r = 0; r < RB; ++r) {
-    float* __restrict__ bs = a.bslab + ((int64_t)(slot0 + r) * 2 + z) * FU_HP;
+  // dZ1 = acc * (1 - h1^2) with h1 read back from the positions this lane wrote after G1; column sums of the tile are the bias-1
+  // gradient partials of its slot; dZ1 leaves from the registers
+  {
+    float* __restrict__ bs = a.bslab + ((int64_t)slot * 2 + z) * FU_HP;
 #pragma unroll
     for (int c = 0; c < CB; ++c) {
       float csum = 0.f;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const float h = bufA[FU_ROW(r, e) * FU_AP + FU_COL(c)];
-        const float v = acc[r][c][e] * (1.f - h * h);   // rows >= n carry dZ2 = 0, hence 0 here
+        const float h = bufA[FU_ROW(e) * FU_AP + FU_COL(c)];
+        const float v = acc[c][e] * (1.f - h * h);   // rows >= n carry dZ2 = 0, hence 0 here
         csum += v;
-        acc[r][c][e] = v;
+        acc[c][e] = v;
       }
       csum += __shfl_xor(csum, 32);
       if (lane < 32) bs[FU_COL(c)] = csum;
@@ -710,7 +626,6 @@ __global__ void __launch_bounds__(FuGeom<TRAIN>::NTH, ENV ? 1 : FuGeom<TRAIN>::W
 #undef FU_BLOAD
 #undef FU_INIT_ACC
 #undef FU_GEMM
-#undef FU_ALOAD
 #undef FU_MFMA
 #undef FU_TANH
 #undef FU_ROW

@@ -94,10 +94,8 @@ __device__ __forceinline__ void tracker_store(kp1_curriculum_state* __restrict__
 // sum after EVERY episode at once, the first episode that satisfies the promotion rule is a wave-min, and the ring / length / head / sum after
 // appending a run of episodes follow in closed form (entry j of a run lands in slot (head + len + j) mod window, full or not).  A promotion
 // empties the window and the search continues behind it.  Wave-uniform in, wave-uniform out; LDS scratch: 4096 bits-as-bytes + prefix counts.
-#ifndef KP1_TRK_PARALLEL_MIN
-#define KP1_TRK_PARALLEL_MIN 192          // finished episodes per 4096-env block from which the whole-wave path is taken (A/B: 1 << 30 = never)
-#endif
-constexpr int TRK_BLOCK = 64 * 64, TRK_PARALLEL_MIN = KP1_TRK_PARALLEL_MIN;
+// TRK_PARALLEL_MIN: finished episodes per 4096-env block from which the whole-wave path is taken
+constexpr int TRK_BLOCK = 64 * 64, TRK_PARALLEL_MIN = 192;
 struct TrackerScratch { uint8_t* sbit; uint16_t* pfx; };
 
 // append episodes [pos, pos + R) of sbit to the window; no promotion check
@@ -304,10 +302,7 @@ __global__ void __launch_bounds__(64) curriculum_kernel(kp1_curriculum_state* __
   const TrackerScratch ws = {sbit, pfx};
   // [r3] the common VecEnv step ends no episode: then the only state that changes is num_timesteps, and the kernel is ONE round of loads (the
   // done bytes) + a fire-and-forget add instead of three dependent round trips (state -> window -> done bytes) + the state stores
-#ifndef KP1_TRK_FAST_EMPTY
-#define KP1_TRK_FAST_EMPTY 1
-#endif
-  if (KP1_TRK_FAST_EMPTY) {
+  {
     const int lane = threadIdx.x;
     bool any = false;
     for (int base = 0; base < n; base += 64 * 64) {

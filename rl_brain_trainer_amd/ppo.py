@@ -409,6 +409,8 @@ class Dist:
 class PPO:
     def __init__(self, env: ArmKinematicVecEnv, cfg: PPOConfig, *, curriculum: PointCurriculum | None = None,
                  dist: Dist | None = None, backend: str = "hip", use_graphs: bool = True) -> None:
+        if backend != "hip":
+            raise ValueError("backend must be 'hip': the HIP kernels are the only training path")
         self.env = env
         self.cfg = cfg
         self.device = env.device
@@ -430,10 +432,9 @@ class PPO:
             curriculum.attach(env)
         T, N = cfg.n_steps, self.n_envs
         dev = self.device
-        # hip backend: observation rows are written with pitch 64 / 128 (zero padded) so the MFMA GEMMs read them directly
-        self.obs_w = (64 if self.obs_dim <= 64 else 128) if backend == "hip" else self.obs_dim
-        if backend == "hip":
-            env.set_obs_stride(self.obs_w)
+        # observation rows are written with pitch 64 / 128 (zero padded) so the MFMA GEMMs read them directly
+        self.obs_w = 64 if self.obs_dim <= 64 else 128
+        env.set_obs_stride(self.obs_w)
         self.obs_buf = torch.zeros((T + 1, N, self.obs_w), dtype=torch.float32, device=dev)
         self.term_obs_buf = torch.zeros((T, N, self.obs_w), dtype=torch.float32, device=dev)
         self.act_buf = torch.zeros((T, N, ACT_DIM), dtype=torch.float32, device=dev)
@@ -452,26 +453,21 @@ class PPO:
         self._last_stats_host: dict[str, float] = {}
         if env.dtype != torch.float32:
             raise ValueError("PPO drives the production f32 env")
-        self._mlp = None
-        if backend == "hip":
-            from . import mlp as _mlp
+        from . import mlp as _mlp
 
-            local_bs = max(cfg.batch_size // self.dist.world_size, 1)
-            self._mlp = _mlp.MlpKernels(cfg.hidden, self.device, max_batch=max(N, local_bs, 8192), obs_dim=self.obs_dim)
-            self._mlp.pack(self.policy.flat)
-            if os.environ.get("KP1_BF16X3_WGRAD", "0") == "1" and cfg.hidden == 256:
-                # round-3 EXPERIMENT (off by default, never used by bench.py's value): weight-gradient GEMMs on bf16 x 3 operands
-                self._mlp.set_bf16x3_wgrad(True)
-            self.grad = torch.zeros_like(self.policy.flat)
-            self.stats_dev = torch.zeros(4, dtype=torch.float32, device=dev)
-            self.noise = torch.zeros((N, ACT_DIM), dtype=torch.float32, device=dev)
-        elif backend != "torch":
-            raise ValueError("backend must be 'hip' or 'torch'")
+        local_bs = max(cfg.batch_size // self.dist.world_size, 1)
+        self._mlp = _mlp.MlpKernels(cfg.hidden, self.device, max_batch=max(N, local_bs, 8192), obs_dim=self.obs_dim)
+        self._mlp.pack(self.policy.flat)
+        if os.environ.get("KP1_BF16X3_WGRAD", "0") == "1" and cfg.hidden == 256:
+            # round-3 EXPERIMENT (off by default, never used by bench.py's value): weight-gradient GEMMs on bf16 x 3 operands
+            self._mlp.set_bf16x3_wgrad(True)
+        self.grad = torch.zeros_like(self.policy.flat)
+        self.stats_dev = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.noise = torch.zeros((N, ACT_DIM), dtype=torch.float32, device=dev)
         # hipGraph replay of the rollout (T x 3 launches) and of one update epoch.  Data parallel: graph segments with eager collectives
         # between them, or (opt-in) the RCCL collectives captured inside the graphs: Dist.graph_mode.
-        self.use_graphs = bool(use_graphs and backend == "hip")
-        if backend == "hip":
-            self.dist.use_stream_collectives(self.device)     # nccl: the training collectives go on the launch stream (rccl.py); else a no-op
+        self.use_graphs = bool(use_graphs)
+        self.dist.use_stream_collectives(self.device)     # nccl: the training collectives go on the launch stream (rccl.py); else a no-op
         self.graph_mode = self.dist.graph_mode(self.device) if self.use_graphs else "none"
         self._first_replay_checked = {"rollout": not (self.dist.enabled and self.graph_mode == "captured"),
                                       "epoch": not (self.dist.enabled and self.graph_mode == "captured")}
@@ -493,16 +489,15 @@ class PPO:
             self._done_gather = torch.zeros((self.dist.world_size, self.done_chunk, N), dtype=torch.uint8, device=dev)
         # one launch per rollout step for policy forward + env step where the env is the plain fp32 vectorised env and the tile kernels run
         # (KP1_FUSED_ROLLOUT=0: the two-launch form, kept as the A/B and test reference)
-        self._fused_env_step = bool(backend == "hip" and type(env) is ArmKinematicVecEnv and env.dtype == torch.float32 and cfg.hidden == 256
+        self._fused_env_step = bool(type(env) is ArmKinematicVecEnv and env.dtype == torch.float32 and cfg.hidden == 256
                                     and self.obs_dim <= 64 and not getattr(env, "_reward_components_on", False)
                                     and os.environ.get("KP1_FUSED_ROLLOUT", "1") != "0")
         # optional host hook after every env step (done bits of that step, device tensor): what SB3 callbacks' _on_step sees.
         # Setting it makes the rollout eager (a host hook cannot live inside a hipGraph replay).
         self.step_callback = None
-        if backend == "hip":
-            # exploration noise of a whole rollout is drawn in ONE call, graphs or not: the eager and the replayed rollout then consume the
-            # generator identically and stay bit-identical (tests/test_distributed_gpu.py compares them)
-            self.noise_all = torch.zeros((T, N, ACT_DIM), dtype=torch.float32, device=dev)
+        # exploration noise of a whole rollout is drawn in ONE call, graphs or not: the eager and the replayed rollout then consume the
+        # generator identically and stay bit-identical (tests/test_distributed_gpu.py compares them)
+        self.noise_all = torch.zeros((T, N, ACT_DIM), dtype=torch.float32, device=dev)
         if self.use_graphs:
             self.perm = torch.zeros(T * N, dtype=torch.int64, device=dev)
 
@@ -510,11 +505,11 @@ class PPO:
     # iteration (2.5 %); drawing them on a side stream under the rollout only moved that time (the sort kernels fill the chip and the
     # rollout's launches queue behind them: rollout +1.3 ms for update -1.7 ms).  From PERM_CIPHER_MIN samples on, the permutation is a keyed
     # bijection evaluated per element (kp1_random_permutation: one elementwise launch); below it torch.randperm stays -- it is cheap there.
-    PERM_CIPHER_MIN = (1 << 17) if os.environ.get("KP1_PERM_CIPHER", "1") != "0" else (1 << 62)   # KP1_PERM_CIPHER=0: developer A/B switch
+    PERM_CIPHER_MIN = 1 << 17
 
     def _draw_perm(self, total: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """indices of one epoch's minibatches: a random permutation of [0, total) on the device (SB3: np.random.permutation in RolloutBuffer.get)"""
-        if self._mlp is None or total < self.PERM_CIPHER_MIN:
+        if total < self.PERM_CIPHER_MIN:
             if out is None:
                 return torch.randperm(total, device=self.device, generator=self.gen)
             return torch.randperm(total, device=self.device, generator=self.gen, out=out)
@@ -582,10 +577,9 @@ class PPO:
                 raise ValueError(f"unsupported per-tensor Adam step pattern {steps}")
             self.adam_t, self.actor_extra_steps = rest[0], actor[0] - rest[0]
             restored.update({"optimizer": True, "adam_steps": self.adam_t, "actor_extra_steps": self.actor_extra_steps})
-        if self._mlp is not None:
-            self._mlp.pack(self.policy.flat)
-            self._mlp.set_step_count(self.adam_t)
-            self._mlp.set_actor_extra_steps(self.actor_extra_steps)
+        self._mlp.pack(self.policy.flat)
+        self._mlp.set_step_count(self.adam_t)
+        self._mlp.set_actor_extra_steps(self.actor_extra_steps)
         if restore_timesteps or restore_hyperparameters:
             data = checkpoint.load_data(path)
             if restore_timesteps:
@@ -614,9 +608,7 @@ class PPO:
     # ------------------------------------------------------------------ policy evaluation
     def _forward(self, obs: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         """mean[n,7], value[n] for obs [n, 56 or 64]"""
-        if self._mlp is not None:
-            return self._mlp.mean_value(obs.contiguous())
-        return mlp_forward(self.policy.views, obs[:, :self.obs_dim])
+        return self._mlp.mean_value(obs.contiguous())
 
     def predict(self, obs: torch.Tensor, deterministic: bool = True) -> torch.Tensor:
         """model.predict(obs, deterministic): mean (or a sample) clipped to the action space (eval_three_stage.py:25-27)."""
@@ -632,13 +624,13 @@ class PPO:
 
     def _bootstrap_truncated(self, dense: bool = False) -> None:
         """SB3 collect_rollouts time-limit bootstrap: rewards[t, i] += gamma * V(terminal_observation) where step t of env i was
-        truncated and not terminated.  ``dense`` = critic over all T * N terminal observations + kp1_bootstrap_truncated (the
-        torch backend's path, kept as the reference for the compacted one)."""
+        truncated and not terminated.  ``dense`` = critic over all T * N terminal observations + kp1_bootstrap_truncated (kept as the
+        reference for the compacted one)."""
         cfg, env = self.cfg, self.env
         T, N = cfg.n_steps, self.n_envs
         stream = torch.cuda.current_stream(self.device).cuda_stream
         dev = self.device.index or 0
-        if self._mlp is not None and not dense:
+        if not dense:
             # Only truncated steps need the critic.  An env truncates at most T // max_episode_steps + 1 times per rollout, so the
             # truncated positions fit a fixed-size index list (torch.nonzero_static: no device->host size query) and the value net
             # runs on N * (that bound) terminal observations instead of all T * N.
@@ -669,12 +661,9 @@ class PPO:
             self._needs_reset = False
         else:
             self.obs_buf[0].copy_(self.obs_buf[T])
-        log_std = self.policy.views["log_std"]
-        std = torch.exp(log_std)
         world = self.dist.world_size
         graph_rollout = self.use_graphs and self.step_callback is None
-        if self._mlp is not None:
-            self.noise_all.normal_(generator=self.gen)
+        self.noise_all.normal_(generator=self.gen)
         if graph_rollout:
             key = (getattr(env, "launch_args_version", 0), self.curriculum is not None, cfg.gamma, cfg.gae_lambda)   # what a capture freezes
             if self._rollout_graph is None or self._rollout_graph_key != key:
@@ -682,21 +671,7 @@ class PPO:
                 self._rollout_graph_key = key
             self._replay_checked("rollout", self._rollout_graph)
         for t in range(0 if not graph_rollout else T, T):
-            if self._mlp is not None:
-                self._rollout_step_hip(t)      # the launch sequence the captured rollout replays
-                if self.step_callback is not None:
-                    self.step_callback(self.done_buf[t])
-                continue
-            else:
-                mean, value = self._forward(self.obs_buf[t])
-                noise = torch.randn((N, ACT_DIM), dtype=torch.float32, device=self.device, generator=self.gen)
-                action = torch.addcmul(mean, std, noise)
-                self.act_buf[t].copy_(action)
-                self.logp_buf[t].copy_((-0.5 * noise * noise - log_std - LOG_SQRT_2PI).sum(-1))
-                self.val_buf[t].copy_(value)
-                torch.clamp(action, -1.0, 1.0, out=self.clip_act)
-            env.step_into(self.clip_act, self.obs_buf[t + 1], self.rew_buf[t], self.done_buf[t], self.term_obs_buf[t], True)
-            self._curriculum_observe(t)
+            self._rollout_step_hip(t)      # the launch sequence the captured rollout replays
             if self.step_callback is not None:
                 self.step_callback(self.done_buf[t])
         if not graph_rollout:
@@ -714,12 +689,8 @@ class PPO:
         self._bootstrap_truncated()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         dev = self.device.index or 0
-        if self._mlp is not None:
-            last_v = torch.empty(N, dtype=torch.float32, device=self.device)
-            self._mlp.forward(self.obs_buf[T], value=last_v)   # value net only
-        else:
-            _, last_v = self._forward(self.obs_buf[T])
-            last_v = last_v.contiguous()
+        last_v = torch.empty(N, dtype=torch.float32, device=self.device)
+        self._mlp.forward(self.obs_buf[T], value=last_v)   # value net only
         native.check(self.L.kp1_gae_scan(dev, C.c_void_p(self.rew_buf.data_ptr()), C.c_void_p(self.val_buf.data_ptr()),
                                          C.c_void_p(self.done_buf.data_ptr()), C.c_void_p(last_v.data_ptr()), cfg.gamma, cfg.gae_lambda,
                                          C.c_void_p(self.adv_buf.data_ptr()), C.c_void_p(self.ret_buf.data_ptr()), T, N, C.c_void_p(stream)))
@@ -842,11 +813,9 @@ class PPO:
         ret = self.ret_buf.view(total)
         world = self.dist.world_size
         local_bs = max(cfg.batch_size // world, 1)
-        stats = torch.zeros(4, device=self.device)
         n_updates = 0
         self.n_train_calls += 1
-        if self._mlp is not None:
-            self.stats_dev.zero_()
+        self.stats_dev.zero_()
         for _epoch in range(cfg.n_epochs):
             if self.use_graphs:
                 self._draw_perm(total, out=self.perm)     # the epoch graph reads the fixed address self.perm
@@ -883,22 +852,17 @@ class PPO:
                 self.adam_t += (total + local_bs - 1) // local_bs
                 continue
             perm = self._draw_perm(total)
-            mb_stats = self._epoch_adv_stats(adv, perm, total, local_bs) if self._mlp is not None else None
-            if self._mlp is not None:
-                # the eager loop steps Adam from the device-resident step count too, exactly as the captured epoch does (bias corrections
-                # computed by the same device arithmetic): eager and replayed training stay bit-identical.  The count is set from the host
-                # mirror first, so loss_grad calls made outside train() cannot have moved it.
-                self._mlp.set_step_count(self.adam_t)
+            mb_stats = self._epoch_adv_stats(adv, perm, total, local_bs)
+            # the eager loop steps Adam from the device-resident step count too, exactly as the captured epoch does (bias corrections
+            # computed by the same device arithmetic): eager and replayed training stay bit-identical.  The count is set from the host
+            # mirror first, so loss_grad calls made outside train() cannot have moved it.
+            self._mlp.set_step_count(self.adam_t)
             for i, start in enumerate(range(0, total, local_bs)):
                 idx = perm[start:start + local_bs]
-                if self._mlp is not None:
-                    self._hip_minibatch_step(obs, idx, act, old_logp, adv, ret, device_step=True, adv_stats=None if mb_stats is None else mb_stats[i])
-                    self.adam_t += 1
-                else:
-                    stats += self._minibatch_step(obs[idx], act[idx], old_logp[idx], adv[idx], ret[idx])
+                self._hip_minibatch_step(obs, idx, act, old_logp, adv, ret, device_step=True, adv_stats=None if mb_stats is None else mb_stats[i])
+                self.adam_t += 1
                 n_updates += 1
-        if self._mlp is not None:
-            stats = self.stats_dev.clone()
+        stats = self.stats_dev.clone()
         # read back lazily (last_stats): a .tolist() here would make every iteration wait for its own update before the host can enqueue
         # the next rollout
         self._last_stats_dev = (stats, n_updates)
@@ -985,73 +949,6 @@ class PPO:
         # launch sequence can be replayed from a hipGraph; the host mirror self.adam_t is advanced by the caller
         self._mlp.adam_step(self.policy.flat, self.grad, self.adam_m, self.adam_v, lr=cfg.learning_rate, eps=cfg.adam_eps,
                             max_grad_norm=cfg.max_grad_norm, step=0 if device_step else self.adam_t, fused_norm=not self.dist.enabled)
-
-    def _normalize_adv(self, adv: torch.Tensor) -> torch.Tensor:
-        if not self.cfg.normalize_advantage or adv.numel() * self.dist.world_size <= 1:
-            return adv
-        if not self.dist.enabled:
-            return (adv - adv.mean()) / (adv.std() + 1e-8)
-        # GPU-count invariant normalisation: global (sum, sum^2, count)
-        s = torch.stack([adv.sum(), (adv * adv).sum(), torch.tensor(float(adv.numel()), device=adv.device)])
-        self.dist.all_reduce_sum(s)
-        mean = s[0] / s[2]
-        var = (s[1] - s[2] * mean * mean) / (s[2] - 1.0)
-        return (adv - mean) / (var.clamp_min(0).sqrt() + 1e-8)
-
-    def _minibatch_step(self, obs, act, old_logp, adv, ret) -> torch.Tensor:
-        cfg = self.cfg
-        adv = self._normalize_adv(adv)
-        grad, terms = self._torch_loss_and_grad(obs[:, :self.obs_dim], act, old_logp, adv, ret)
-        self.dist.all_reduce_sum(grad)
-        self._clip_and_adam(grad)
-        return terms
-
-    def _torch_loss_and_grad(self, obs, act, old_logp, adv, ret) -> tuple[torch.Tensor, torch.Tensor]:
-        cfg = self.cfg
-        flat = self.policy.flat.detach().requires_grad_(True)
-        P, off = {}, 0
-        for name, shape in self.policy.spec:
-            n = math.prod(shape)
-            P[name] = flat[off:off + n].view(shape)
-            off += n
-        mean, value = mlp_forward(P, obs)
-        log_std = P["log_std"]
-        logp = gaussian_log_prob(act, mean, log_std)
-        ratio = torch.exp(logp - old_logp)
-        denom = float(obs.shape[0] * self.dist.world_size)
-        pl = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - cfg.clip_range, 1 + cfg.clip_range)).sum() / denom
-        vl = ((ret - value) ** 2).sum() / denom
-        ent = (0.5 + LOG_SQRT_2PI + log_std).sum()  # per-sample entropy is constant: mean == value
-        loss = pl + cfg.vf_coef * vl - cfg.ent_coef * ent / self.dist.world_size
-        (grad,) = torch.autograd.grad(loss, flat)
-        with torch.no_grad():
-            kl = ((ratio - 1) - (logp - old_logp)).mean()
-            terms = torch.stack([pl.detach(), vl.detach(), ent.detach(), kl])
-        return grad, terms
-
-    def _clip_and_adam(self, grad: torch.Tensor) -> None:
-        cfg = self.cfg
-        with torch.no_grad():
-            norm = torch.linalg.vector_norm(grad)
-            scale = torch.clamp(cfg.max_grad_norm / (norm + 1e-6), max=1.0)  # clip_grad_norm_
-            grad = grad * scale
-            self.adam_t += 1
-            b1, b2 = 0.9, 0.999
-            self.adam_m.mul_(b1).add_(grad, alpha=1 - b1)
-            self.adam_v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-            # torch.optim.Adam counts steps per tensor: the actor tensors are `actor_extra_steps` ahead after teacher-anchor side updates
-            steps = torch.full_like(self.policy.flat, float(self.adam_t))
-            if self.actor_extra_steps:
-                off = 0
-                for name, shape in self.policy.spec:
-                    n = math.prod(shape)
-                    if name.startswith(("mlp_extractor.policy_net", "action_net")):
-                        steps[off:off + n] += float(self.actor_extra_steps)
-                    off += n
-            bc1 = 1 - b1 ** steps
-            bc2 = 1 - b2 ** steps
-            denom = (self.adam_v.sqrt() / bc2.sqrt()).add_(cfg.adam_eps)
-            self.policy.flat.sub_(cfg.learning_rate * self.adam_m / (bc1 * denom))
 
     # ------------------------------------------------------------------ driver
     def learn(self, total_timesteps: int | None = None, log_every: int = 0) -> "PPO":

@@ -131,9 +131,8 @@ class RouteTeacherAnchor:
                 ppo.policy.flat[sl].addcdiv_(m, denom, value=-cfg.learning_rate / bc1)
         self.actor_extra_steps += 1
         ppo.actor_extra_steps = self.actor_extra_steps
-        if ppo._mlp is not None:
-            ppo._mlp.pack(ppo.policy.flat)
-            ppo._mlp.set_actor_extra_steps(self.actor_extra_steps)
+        ppo._mlp.pack(ppo.policy.flat)
+        ppo._mlp.set_actor_extra_steps(self.actor_extra_steps)
         return float(loss.detach().item())
 
     def summary(self) -> dict[str, Any]:

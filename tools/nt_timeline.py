@@ -19,8 +19,8 @@ out_dir = os.path.join(ROOT, "gpurun_out")
 os.makedirs(out_dir, exist_ok=True)
 lib = os.path.join(out_dir, "libkp1_trace.so")
 srcs = [os.path.join(ROOT, "rl_brain_trainer_amd/csrc", f) for f in ("kp1_env.hip", "kp1_ppo.hip", "kp1_mlp.hip")]
-extra = [f"-D{d}" for d in os.environ.get("KP1_TRACE_DEFS", "").split() if d]   # e.g. KP1_TNF_NOMFMA, KP1_TNF_NOLOAD
-if os.environ.get("KP1_TRACE_LIB"):      # a library already built with -DKP1_NT_TRACE (tools/ab_local.sh build trace=-DKP1_NT_TRACE)
+extra = [f"-D{d}" for d in os.environ.get("KP1_TRACE_DEFS", "").split() if d]   # e.g. KP1_FU_NOMFMA
+if os.environ.get("KP1_TRACE_LIB"):      # a library already built with -DKP1_NT_TRACE (tools/ab_build.sh)
     lib = os.path.join(ROOT, os.environ["KP1_TRACE_LIB"])
 else:
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-DKP1_NT_TRACE", "-shared", "-o", lib] + extra + srcs)
