@@ -141,6 +141,21 @@ int kp1_route_curriculum_create(kp1_route* r, const int32_t* prefix_end_index, i
 int kp1_route_curriculum_destroy(kp1_route* r, kp1_route_curriculum_state* st_dev);
 /* _on_step: dones[0..N) = the KP1_DONE_* bytes kp1_route_step just wrote; steps_per_call = env steps this call stands for */
 int kp1_route_curriculum_observe(kp1_route* r, kp1_route_curriculum_state* st_dev, const uint8_t* dones, int32_t steps_per_call, void* stream);
+
+/* ---- data parallel: per-step episode records and the chunked multi-rank tracker ----------------------------------------------
+ * The tracker reads the wrapper's flag planes, which every kp1_route_step rewrites, so a chunk of steps cannot be replayed from them.
+ * kp1_route_episode_records keeps one byte per env and step instead: bits 0-3 = the KP1_DONE_* bits of the step, then the wrapper's
+ * flags of the same step.  It reads the planes on the device (capturable in a hipGraph, like the tracker). */
+#define KP1_ROUTE_REC_READY       16
+#define KP1_ROUTE_REC_ORI_HIT     32
+#define KP1_ROUTE_REC_REGRESSION  64
+int kp1_route_episode_records(kp1_route* r, const uint8_t* dones, uint8_t* records /* [N] */, void* stream);
+/* records = the all-gathered [world][chunk_steps][n_local] bytes of kp1_route_episode_records (rank-major).  Replayed step by step and,
+ * inside a step, rank by rank = global env id order: the (done, info) sequence RoutePrefixCurriculumCallback sees on ONE VecEnv of
+ * world * n_local envs.  The clock advances by world * n_local per env step.  A promotion rewrites the reset window of THIS rank's device
+ * route config; it takes effect for the resets of the next chunk. */
+int kp1_route_curriculum_observe_chunk(kp1_route* r, kp1_route_curriculum_state* st_dev, const uint8_t* records, int32_t n_local,
+                                       int32_t chunk_steps, int32_t world, void* stream);
 /* copy the tracker to the host (synchronises the stream) and bring the host copy of the reset window up to date */
 int kp1_route_curriculum_read(kp1_route* r, const kp1_route_curriculum_state* st_dev, kp1_route_curriculum_state* out_host, void* stream);
 

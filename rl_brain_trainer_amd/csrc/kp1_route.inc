@@ -598,20 +598,104 @@ int route_seed_streams(kp1_route* r, uint64_t seed0, uint64_t first_env_id) {
 // ---------------------------------------------------------------------------------------------- prefix curriculum on the device
 // RoutePrefixCurriculumCallback._on_step (route_curriculum.py:84-121).  One wave.  Each lane condenses 64 consecutive envs into a
 // done mask and four flag masks; a ballot skips steps in which no episode ended; finished episodes are then replayed strictly in env
-// order by lane 0 (the masks of lane k arrive by shuffle), which is what the reference's sequential scan over `dones` does.
+// order by lane 0 (the masks of lane k arrive by shuffle), which is what the reference's sequential scan over `dones` does.  The
+// single-process tracker (route_curriculum_kernel) and the data-parallel chunk tracker (route_curriculum_chunk_kernel) differ only in
+// where the masks come from; the replay below is theirs in common.
 namespace {
+
+// the tracker fields lane 0 keeps in registers while it replays
+struct RouteTrk {
+  int stage, count, len, head, window;
+  int sums[4];
+};
+
+__device__ __forceinline__ void route_trk_load(const kp1_route_curriculum_state* st, RouteTrk& c) {
+  c.stage = st->stage_index; c.count = st->stage_episode_count; c.len = st->ring_len; c.head = st->ring_head; c.window = st->window_episodes;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) c.sums[q] = st->ring_sums[q];
+}
+
+__device__ __forceinline__ void route_trk_store(kp1_route_curriculum_state* st, const RouteTrk& c) {
+  st->stage_index = c.stage; st->stage_episode_count = c.count; st->ring_len = c.len; st->ring_head = c.head;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) st->ring_sums[q] = c.sums[q];
+}
+
+// one finished episode (success, route_ready, orientation hit, regression): the four deque appends, the window rates, the promotion with its
+// event record and the reset-window write.  `now` = the callback's num_timesteps at this env step.
+__device__ __forceinline__ void route_trk_append(kp1_route_curriculum_state* __restrict__ st, RouteDevCfg* __restrict__ cfg, RouteTrk& c,
+                                                 const uint8_t v[4], int64_t now) {
+  c.count += 1;
+  const int slot = c.len < c.window ? (c.head + c.len) % c.window : c.head;   // deque(maxlen = window).append
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (c.len >= c.window) c.sums[q] -= st->ring[q][slot];                   // the evicted oldest entry
+    st->ring[q][slot] = v[q];
+    c.sums[q] += v[q];
+  }
+  if (c.len < c.window) c.len += 1;
+  else c.head = (c.head + 1) % c.window;
+  if (c.count < st->min_episodes_per_stage || c.len < c.window) return;
+  double rate[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) rate[q] = (double)c.sums[q] / (double)c.len;
+  if (!(rate[0] >= st->promotion_success_rate && rate[1] >= st->promotion_route_ready_hit_rate && rate[2] >= st->promotion_orientation_hit_rate &&
+        rate[3] <= st->promotion_max_regression_rate))
+    return;
+  if (c.stage >= st->n_stages - 1) return;   // _promote returns without touching anything on the last stage
+  if (st->n_events < KP1_ROUTE_CURRICULUM_MAX_HISTORY) {
+    kp1_route_curriculum_event& ev = st->events[st->n_events];
+    ev.total_timesteps = now;
+    ev.from_stage = c.stage; ev.to_stage = c.stage + 1;
+    ev.from_prefix_end_index = st->prefix_end_index[c.stage]; ev.to_prefix_end_index = st->prefix_end_index[c.stage + 1];
+    ev.recent_success_rate = rate[0]; ev.recent_route_ready_hit_rate = rate[1]; ev.recent_orientation_hit_rate = rate[2];
+    ev.recent_regression_rate = rate[3];
+  }
+  st->n_events += 1;
+  c.stage += 1;
+  c.count = 0; c.len = 0; c.head = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) c.sums[q] = 0;
+  cfg->c.reset.min_route_index = 1;                            // env_method("set_route_window", max_route_index = prefix, min_route_index = 1)
+  cfg->c.reset.max_route_index = st->prefix_end_index[c.stage];
+}
+
+// the masks of one 64-env group per lane: bit b = env (group start + b)
+struct RouteMasks {
+  unsigned long long done, succ, ready, ori, regr;
+};
+
+// lane 0 appends the finished episodes of the 64 groups of the wave in env order (lane k's masks arrive by shuffle)
+__device__ __forceinline__ void route_trk_replay(kp1_route_curriculum_state* __restrict__ st, RouteDevCfg* __restrict__ cfg, RouteTrk& c, int lane,
+                                                 const RouteMasks& mk, int64_t now) {
+  for (int src = 0; src < 64; ++src) {
+    unsigned long long m = __shfl(mk.done, src);
+    const unsigned long long ms = __shfl(mk.succ, src), mr = __shfl(mk.ready, src), mo = __shfl(mk.ori, src), mg = __shfl(mk.regr, src);
+    if (lane != 0) continue;
+    while (m) {
+      const int b = __ffsll((long long)m) - 1;
+      m &= m - 1;
+      const uint8_t v[4] = {(uint8_t)((ms >> b) & 1ull), (uint8_t)((mr >> b) & 1ull), (uint8_t)((mo >> b) & 1ull), (uint8_t)((mg >> b) & 1ull)};
+      route_trk_append(st, cfg, c, v, now);
+    }
+  }
+}
 
 __global__ void __launch_bounds__(64) route_curriculum_kernel(kp1_route_curriculum_state* __restrict__ st, RouteDevCfg* __restrict__ cfg,
                                                               const uint8_t* __restrict__ dones, const uint8_t* __restrict__ ready,
                                                               const uint8_t* __restrict__ ori_hit, const uint8_t* __restrict__ regression, int n,
                                                               int steps_per_call) {
   const int lane = threadIdx.x;
-  if (lane == 0) st->num_timesteps += steps_per_call;
+  int64_t now = 0;
+  if (lane == 0) {
+    now = st->num_timesteps + steps_per_call;
+    st->num_timesteps = now;
+  }
   const bool words_ok = ((reinterpret_cast<uintptr_t>(dones) | reinterpret_cast<uintptr_t>(ready) | reinterpret_cast<uintptr_t>(ori_hit) |
                           reinterpret_cast<uintptr_t>(regression)) & 3) == 0;   // the flag planes sit at multiples of N inside one buffer
   for (int base = 0; base < n; base += 64 * 64) {
     const int first = base + lane * 64;
-    unsigned long long dmask = 0ull, m_succ = 0ull, m_ready = 0ull, m_ori = 0ull, m_regr = 0ull;
+    RouteMasks mk = {0ull, 0ull, 0ull, 0ull, 0ull};
     for (int b = 0; b < 64 && first + b < n; b += 4) {
       if (words_ok && first + b + 4 <= n) {   // 4 envs per 32-bit load (the arrays are 256-byte aligned device buffers)
         const unsigned int d4 = *reinterpret_cast<const unsigned int*>(dones + first + b);
@@ -624,11 +708,11 @@ __global__ void __launch_bounds__(64) route_curriculum_kernel(kp1_route_curricul
           const unsigned int d = (d4 >> (8 * k)) & 0xffu;
           if (d & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) {
             const unsigned long long bit = 1ull << (b + k);
-            dmask |= bit;
-            if (d & KP1_DONE_SUCCESS) m_succ |= bit;
-            if ((r4 >> (8 * k)) & 0xffu) m_ready |= bit;
-            if ((o4 >> (8 * k)) & 0xffu) m_ori |= bit;
-            if ((g4 >> (8 * k)) & 0xffu) m_regr |= bit;
+            mk.done |= bit;
+            if (d & KP1_DONE_SUCCESS) mk.succ |= bit;
+            if ((r4 >> (8 * k)) & 0xffu) mk.ready |= bit;
+            if ((o4 >> (8 * k)) & 0xffu) mk.ori |= bit;
+            if ((g4 >> (8 * k)) & 0xffu) mk.regr |= bit;
           }
         }
       } else {
@@ -636,71 +720,109 @@ __global__ void __launch_bounds__(64) route_curriculum_kernel(kp1_route_curricul
           const uint8_t d = dones[first + b + k];
           if (d & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) {
             const unsigned long long bit = 1ull << (b + k);
-            dmask |= bit;
-            if (d & KP1_DONE_SUCCESS) m_succ |= bit;
-            if (ready[first + b + k]) m_ready |= bit;
-            if (ori_hit[first + b + k]) m_ori |= bit;
-            if (regression[first + b + k]) m_regr |= bit;
+            mk.done |= bit;
+            if (d & KP1_DONE_SUCCESS) mk.succ |= bit;
+            if (ready[first + b + k]) mk.ready |= bit;
+            if (ori_hit[first + b + k]) mk.ori |= bit;
+            if (regression[first + b + k]) mk.regr |= bit;
           }
         }
       }
     }
-    if (__ballot(dmask != 0ull) == 0ull) continue;
-    int stage = 0, count = 0, len = 0, head = 0, window = 1;
-    int sums[4] = {0, 0, 0, 0};
-    if (lane == 0) {
-      stage = st->stage_index; count = st->stage_episode_count; len = st->ring_len; head = st->ring_head; window = st->window_episodes;
+    if (__ballot(mk.done != 0ull) == 0ull) continue;
+    RouteTrk c = {};
+    if (lane == 0) route_trk_load(st, c);
+    route_trk_replay(st, cfg, c, lane, mk, now);
+    if (lane == 0) route_trk_store(st, c);
+  }
+}
+
+// ---- per-step episode records (data parallel) ----------------------------------------------------------------------------------
+// The wrapper's flag planes are rewritten by every step, so a chunk of steps cannot be replayed from them: after each step one byte per
+// env keeps that step's done bits and the three flags the tracker reads.  Elementwise, 4 envs per lane: 32-bit loads of the done bytes
+// and of the three planes (one scalar base, the planes at 32-bit offsets k * N from it), one 32-bit store.
+// nonzero byte -> 0x01 in the same byte, for the four bytes of a word at once
+__device__ __forceinline__ unsigned int route_bytes_nonzero(unsigned int x) {
+  return ((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u) >> 7;
+}
+
+__global__ void __launch_bounds__(256) route_episode_records_kernel(const uint8_t* __restrict__ dones, const uint8_t* __restrict__ flags,
+                                                                    uint8_t* __restrict__ records, unsigned int n, int words_ok) {
+  // flags = the wrapper's byte block: route_ready at [0, N), route_regression at [2N, 3N), orientation_hit at [3N, 4N) (kp1_route_get_info)
+  const unsigned int i = (blockIdx.x * 256u + threadIdx.x) * 4u;
+  if (i >= n) return;
+  if (words_ok) {   // N % 4 == 0 and every base 4-byte aligned: every lane's 4 envs are one aligned word in each array
+    const unsigned int d4 = *reinterpret_cast<const unsigned int*>(dones + i);
+    const unsigned int r4 = *reinterpret_cast<const unsigned int*>(flags + i);
+    const unsigned int g4 = *reinterpret_cast<const unsigned int*>(flags + (2u * n + i));
+    const unsigned int o4 = *reinterpret_cast<const unsigned int*>(flags + (3u * n + i));
+    *reinterpret_cast<unsigned int*>(records + i) = (d4 & 0x0f0f0f0fu) | (route_bytes_nonzero(r4) << 4) | (route_bytes_nonzero(o4) << 5) |
+                                                    (route_bytes_nonzero(g4) << 6);
+    return;
+  }
+  for (unsigned int k = i; k < i + 4u && k < n; ++k)
+    records[k] = (uint8_t)((dones[k] & 0x0fu) | (flags[k] ? KP1_ROUTE_REC_READY : 0) | (flags[3u * n + k] ? KP1_ROUTE_REC_ORI_HIT : 0) |
+                           (flags[2u * n + k] ? KP1_ROUTE_REC_REGRESSION : 0));
+}
+
+// one record word (4 envs starting at bit b of the lane's group) into the lane's masks
+__device__ __forceinline__ void route_rec_word(unsigned int w, int b, RouteMasks& mk) {
+  if ((w & (0x01010101u * (unsigned)(KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED))) == 0u) return;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) sums[q] = st->ring_sums[q];
+  for (int k = 0; k < 4; ++k) {
+    const unsigned int d = (w >> (8 * k)) & 0xffu;
+    if (d & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) {
+      const unsigned long long bit = 1ull << (b + k);
+      mk.done |= bit;
+      if (d & KP1_DONE_SUCCESS) mk.succ |= bit;
+      if (d & KP1_ROUTE_REC_READY) mk.ready |= bit;
+      if (d & KP1_ROUTE_REC_ORI_HIT) mk.ori |= bit;
+      if (d & KP1_ROUTE_REC_REGRESSION) mk.regr |= bit;
     }
-    for (int src = 0; src < 64; ++src) {
-      unsigned long long m = __shfl(dmask, src);
-      const unsigned long long ms = __shfl(m_succ, src), mr = __shfl(m_ready, src), mo = __shfl(m_ori, src), mg = __shfl(m_regr, src);
-      if (lane != 0) continue;
-      while (m) {
-        const int b = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const uint8_t v[4] = {(uint8_t)((ms >> b) & 1ull), (uint8_t)((mr >> b) & 1ull), (uint8_t)((mo >> b) & 1ull), (uint8_t)((mg >> b) & 1ull)};
-        count += 1;
-        const int slot = len < window ? (head + len) % window : head;   // deque(maxlen = window).append
+  }
+}
+
+// Data-parallel form: `records` = the all-gathered [world][chunk_steps][n_local] record bytes (rank-major).  Replayed step by step and,
+// inside a step, rank by rank = global env id order; the clock advances by world * n_local per env step before that step's episodes, as
+// the callback's num_timesteps does on one VecEnv of world * n_local envs.  Lane 0 holds the tracker in registers for the whole chunk.
+__global__ void __launch_bounds__(64) route_curriculum_chunk_kernel(kp1_route_curriculum_state* __restrict__ st, RouteDevCfg* __restrict__ cfg,
+                                                                    const uint8_t* __restrict__ records, int n_local, int chunk_steps, int world) {
+  const int lane = threadIdx.x;
+  RouteTrk c = {};
+  int64_t now = 0;
+  if (lane == 0) {
+    route_trk_load(st, c);
+    now = st->num_timesteps;
+  }
+  const int64_t per_step = (int64_t)world * n_local;
+  for (int t = 0; t < chunk_steps; ++t) {
+    now += per_step;
+    for (int r = 0; r < world; ++r) {
+      const uint8_t* __restrict__ rec = records + ((int64_t)r * chunk_steps + t) * n_local;
+      for (int base = 0; base < n_local; base += 64 * 64) {
+        const int first = base + lane * 64;
+        RouteMasks mk = {0ull, 0ull, 0ull, 0ull, 0ull};
+        if (first + 64 <= n_local && (reinterpret_cast<uintptr_t>(rec + first) & 15) == 0) {   // 64 envs in four 16-byte loads
+          const uint4* p = reinterpret_cast<const uint4*>(rec + first);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (len >= window) sums[q] -= st->ring[q][slot];             // the evicted oldest entry
-          st->ring[q][slot] = v[q];
-          sums[q] += v[q];
-        }
-        if (len < window) len += 1;
-        else head = (head + 1) % window;
-        if (count < st->min_episodes_per_stage || len < window) continue;
-        double rate[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) rate[q] = (double)sums[q] / (double)len;
-        if (rate[0] >= st->promotion_success_rate && rate[1] >= st->promotion_route_ready_hit_rate && rate[2] >= st->promotion_orientation_hit_rate &&
-            rate[3] <= st->promotion_max_regression_rate) {
-          if (stage >= st->n_stages - 1) continue;   // _promote returns without touching anything on the last stage
-          if (st->n_events < KP1_ROUTE_CURRICULUM_MAX_HISTORY) {
-            kp1_route_curriculum_event& ev = st->events[st->n_events];
-            ev.total_timesteps = st->num_timesteps;
-            ev.from_stage = stage; ev.to_stage = stage + 1;
-            ev.from_prefix_end_index = st->prefix_end_index[stage]; ev.to_prefix_end_index = st->prefix_end_index[stage + 1];
-            ev.recent_success_rate = rate[0]; ev.recent_route_ready_hit_rate = rate[1]; ev.recent_orientation_hit_rate = rate[2];
-            ev.recent_regression_rate = rate[3];
+          for (int j = 0; j < 4; ++j) {
+            const uint4 w = p[j];
+            route_rec_word(w.x, 16 * j, mk);
+            route_rec_word(w.y, 16 * j + 4, mk);
+            route_rec_word(w.z, 16 * j + 8, mk);
+            route_rec_word(w.w, 16 * j + 12, mk);
           }
-          st->n_events += 1;
-          stage += 1;
-          count = 0; len = 0; head = 0;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) sums[q] = 0;
-          cfg->c.reset.min_route_index = 1;                            // env_method("set_route_window", max_route_index = prefix, min_route_index = 1)
-          cfg->c.reset.max_route_index = st->prefix_end_index[stage];
+        } else {
+          for (int b = 0; b < 64 && first + b < n_local; ++b) route_rec_word(rec[first + b], b, mk);
         }
+        if (__ballot(mk.done != 0ull) == 0ull) continue;
+        route_trk_replay(st, cfg, c, lane, mk, now);
       }
     }
-    if (lane == 0) {
-      st->stage_index = stage; st->stage_episode_count = count; st->ring_len = len; st->ring_head = head;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) st->ring_sums[q] = sums[q];
-    }
+  }
+  if (lane == 0) {
+    route_trk_store(st, c);
+    st->num_timesteps = now;
   }
 }
 
@@ -955,6 +1077,27 @@ int kp1_route_curriculum_observe(kp1_route* r, kp1_route_curriculum_state* st_de
   const int64_t n = r->base->n;
   hipLaunchKernelGGL(route_curriculum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, r->dev_cfg, dones, r->bytes, r->bytes + 3 * n, r->bytes + 2 * n,
                      (int)n, (int)steps_per_call);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_route_episode_records(kp1_route* r, const uint8_t* dones, uint8_t* records, void* stream) {
+  if (!r || !dones || !records) return fail(KP1_ERR_INVALID, "NULL argument to kp1_route_episode_records");
+  const int64_t n = r->base->n;
+  if (n > (int64_t)(UINT32_MAX / 4u)) return fail(KP1_ERR_INVALID, "kp1_route_episode_records: N too large for 32-bit plane offsets");
+  const int words_ok = (n % 4 == 0) && ((reinterpret_cast<uintptr_t>(dones) | reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(r->bytes)) & 3) == 0;
+  hipLaunchKernelGGL(route_episode_records_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, dones, r->bytes, records,
+                     (unsigned int)n, words_ok);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_route_curriculum_observe_chunk(kp1_route* r, kp1_route_curriculum_state* st_dev, const uint8_t* records, int32_t n_local, int32_t chunk_steps,
+                                       int32_t world, void* stream) {
+  if (!r || !st_dev || !records || n_local <= 0 || chunk_steps <= 0 || world <= 0)
+    return fail(KP1_ERR_INVALID, "bad argument to kp1_route_curriculum_observe_chunk");
+  hipLaunchKernelGGL(route_curriculum_chunk_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, r->dev_cfg, records, (int)n_local, (int)chunk_steps,
+                     (int)world);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }

@@ -487,6 +487,11 @@ class PPO:
 
             self.done_chunk = math.gcd(T, max(int(_os.environ.get("KP1_DONE_EXCHANGE_STEPS", "16")), 1))
             self._done_gather = torch.zeros((self.dist.world_size, self.done_chunk, N), dtype=torch.uint8, device=dev)
+            # a route tracker also reads per-env flags that every step overwrites: each step's episode records are staged in slot t % chunk
+            # and the staging buffer is exchanged instead of the done bytes
+            self._record_stage = None
+            if curriculum is not None and getattr(curriculum, "needs_episode_records", False):
+                self._record_stage = torch.zeros((self.done_chunk, N), dtype=torch.uint8, device=dev)
         # one launch per rollout step for policy forward + env step where the env is the plain fp32 vectorised env and the tile kernels run
         # (KP1_FUSED_ROLLOUT=0: the two-launch form, kept as the A/B and test reference)
         self._fused_env_step = bool(type(env) is ArmKinematicVecEnv and env.dtype == torch.float32 and cfg.hidden == 256
@@ -533,15 +538,19 @@ class PPO:
                 self.dist.world_size)
 
     def _curriculum_observe(self, t: int) -> None:
-        """after env step t: feed the done bytes to the device tracker (single process: every step; data parallel: once per chunk)"""
+        """after env step t: feed the done bytes to the device tracker (single process: every step; data parallel: once per chunk -- a route
+        tracker gets the step's episode records, written every step, in place of the done bytes)"""
         if self.curriculum is None:
             return
         if not self.dist.enabled:
             self.curriculum.observe(self.done_buf[t], self.n_envs)
             return
         c = self.done_chunk
+        if self._record_stage is not None:
+            self.curriculum.record(self.done_buf[t], self._record_stage[t % c])
         if (t + 1) % c == 0:
-            self.dist.all_gather_into(self._done_gather, self.done_buf[t + 1 - c:t + 1])
+            src = self.done_buf[t + 1 - c:t + 1] if self._record_stage is None else self._record_stage
+            self.dist.all_gather_into(self._done_gather, src)
             self.curriculum.observe_chunk(self._done_gather, self.n_envs, c, self.dist.world_size)
 
     # ------------------------------------------------------------------ PPO.load

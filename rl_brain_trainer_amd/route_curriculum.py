@@ -54,7 +54,13 @@ class _CurriculumState(C.Structure):
 
 class RoutePrefixCurriculumDevice:
     """RoutePrefixCurriculum with the per-step scan on the device (include/kp1_route.h, kp1_route_curriculum_*): same promotion rule and
-    history, no host synchronisation per step, so the PPO rollout stays one hipGraph replay.  Plugs into ``PPO(curriculum=...)``."""
+    history, no host synchronisation per step, so the PPO rollout stays one hipGraph replay.  Plugs into ``PPO(curriculum=...)``.
+
+    Data parallel: the tracker needs the wrapper's per-env flags as well as the done bytes, and the flags are overwritten by every step, so
+    PPO records each step (``record``: one byte per env, done bits + flags) and exchanges those records once per chunk (``observe_chunk``)."""
+
+    # PPO's data-parallel rollout exchanges per-step episode records (record / observe_chunk) for this tracker instead of the done bytes
+    needs_episode_records = True
 
     def __init__(self, *, stages: list[RouteCurriculumStage], promotion_success_rate: float, promotion_route_ready_hit_rate: float,
                  promotion_orientation_hit_rate: float, promotion_max_regression_rate: float, window_episodes: int, min_episodes_per_stage: int = 128) -> None:
@@ -100,6 +106,8 @@ class RoutePrefixCurriculumDevice:
         L.kp1_route_curriculum_create.argtypes = [vp, C.POINTER(i32), i32, f64, f64, f64, f64, i32, i32, C.POINTER(vp)]
         L.kp1_route_curriculum_destroy.argtypes = [vp, vp]
         L.kp1_route_curriculum_observe.argtypes = [vp, vp, vp, i32, vp]
+        L.kp1_route_episode_records.argtypes = [vp, vp, vp, vp]
+        L.kp1_route_curriculum_observe_chunk.argtypes = [vp, vp, vp, i32, i32, i32, vp]
         L.kp1_route_curriculum_read.argtypes = [vp, vp, C.POINTER(_CurriculumState), vp]
         prefixes = (i32 * len(self.stages))(*[int(s.prefix_end_index) for s in self.stages])
         with torch.cuda.device(env.device):
@@ -110,9 +118,31 @@ class RoutePrefixCurriculumDevice:
         from . import native
 
         if dones.numel() != self.env.n_envs:
-            raise ValueError("the device route curriculum tracks one process's envs (no data-parallel gather of the route flags)")
+            raise ValueError("observe() tracks one process's envs from the env's own flags; data parallel goes through record() + observe_chunk()")
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
         native.check(self.env.L.kp1_route_curriculum_observe(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), int(steps_per_call), C.c_void_p(stream)))
+
+    def record(self, dones: torch.Tensor, out: torch.Tensor) -> None:
+        """out[N] <- this step's episode records: the KP1_DONE_* bits of ``dones`` | route_ready << 4 | orientation hit << 5 | regression << 6,
+        the flags read from the env's planes on the device (call after the step, before the next one rewrites them)"""
+        from . import native
+
+        n = self.env.n_envs
+        if dones.numel() != n or out.numel() != n or out.dtype != torch.uint8 or not (dones.is_contiguous() and out.is_contiguous()):
+            raise ValueError(f"record() takes the {n} done bytes of one step and a contiguous uint8 [{n}] output")
+        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        native.check(self.env.L.kp1_route_episode_records(self.env._handle, C.c_void_p(dones.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+
+    def observe_chunk(self, records_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
+        """data-parallel rollouts: the all-gathered [world, chunk_steps, n_local] episode records of a chunk of env steps, replayed in the
+        reference's order (step by step, global env id order inside a step); a promotion moves this rank's reset window"""
+        from . import native
+
+        if not (records_all.numel() == world * chunk_steps * n_local and records_all.dtype == torch.uint8 and records_all.is_contiguous()):
+            raise ValueError(f"observe_chunk() takes contiguous uint8 records of shape [{world}, {chunk_steps}, {n_local}]")
+        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        native.check(self.env.L.kp1_route_curriculum_observe_chunk(self.env._handle, self._st, C.c_void_p(records_all.data_ptr()), int(n_local),
+                                                                   int(chunk_steps), int(world), C.c_void_p(stream)))
 
     def read(self) -> _CurriculumState:
         from . import native

@@ -1,4 +1,4 @@
-"""Route-curriculum trainer on one MI355X.
+"""Route-curriculum trainer on one or several MI355X (data parallel under torchrun, like train.py).
 
 Mirror of ``kinematic_phase1/train_route_curriculum.py:69-199``: same YAML chain (approach_default <- ppo_default <- overlay), same
 CLI flags, same artefacts (``model_latest.zip``, ``curriculum_history.json``, ``route_eval_sequential/``, ``route_gate/``,
@@ -9,11 +9,17 @@ sequence wrapper, 56- or 80-float observation as the YAML says); the PPO update 
 
     python -m rl_brain_trainer_amd.train_route --config <route yaml> --route-path <route_q_dense.json> --run-id route \
         --output-dir /tmp/route --total-timesteps 1000000 --n-envs 1024
+
+Data parallel: ``torchrun --nproc_per_node N -m rl_brain_trainer_amd.train_route ...`` (``--n-envs`` per rank, ``--batch-size`` the global
+minibatch).  Rank r steps the envs r * n_envs .. (r + 1) * n_envs - 1 of the single-process run; the prefix curriculum replays every rank's
+episode records in global env order (PPO._curriculum_observe), so all ranks promote together.  Rank 0 alone writes the artefacts and runs
+the sequential evaluation and the gate.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import os
 import shutil
 import time
 from pathlib import Path
@@ -51,19 +57,34 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--n-steps", type=int, default=0, help="rollout length (0 = the YAML's n_steps)")
     p.add_argument("--batch-size", type=int, default=0, help="minibatch (0 = the YAML's batch_size)")
     p.add_argument("--hidden", type=int, default=256)
-    p.add_argument("--device", type=int, default=0)
+    p.add_argument("--device", type=int, default=0, help="GPU of a single-process run (under torchrun: LOCAL_RANK)")
     p.add_argument("--log-every", type=int, default=0)
     return p
 
 
 def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
+    import torch.distributed as dist
+
+    # WORLD_SIZE / RANK / LOCAL_RANK as torchrun sets them; a process group the caller already initialised is used as it is
+    own_group = False
+    if dist.is_available() and dist.is_initialized():
+        world, rank = dist.get_world_size(), dist.get_rank()
+    else:
+        world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    device = int(os.environ["LOCAL_RANK"]) if "LOCAL_RANK" in os.environ else args.device
+    torch.cuda.set_device(device)
+    if world > 1 and not dist.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group(backend="nccl", device_id=torch.device("cuda", device))
+        own_group = True
     cfg = load_route_training_config(args.config)
     route_cfg = cfg.get("route", {}) or {}
     route_path = Path(args.route_path or route_cfg["route_path"])
     init_checkpoint = args.init_checkpoint or route_cfg.get("init_checkpoint")
     root = Path(args.output_dir) if args.output_dir else kcfg.repo_root() / "artifacts" / "kinematic_phase1" / "route_curriculum" / args.run_id
-    root.mkdir(parents=True, exist_ok=True)
+    if rank == 0:
+        root.mkdir(parents=True, exist_ok=True)
 
     route_q = rcfg.load_route_q(route_path)
     W = int(route_q.shape[0])
@@ -76,26 +97,29 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     if args.seed is not None:
         algo["seed"] = args.seed
     seed = int(algo.get("seed") or 0)
-    n_envs = int(args.n_envs or runtime_cfg.get("n_envs", 1))
-    torch.cuda.set_device(args.device)
-    env = RouteVecEnv(env_cfg, rcfg.route_config_from_dict(cfg, max_route_index=prefixes[0]), route_q, n_envs, device=args.device, seed=seed)
+    n_envs = int(args.n_envs or runtime_cfg.get("n_envs", 1))     # per rank
+    env = RouteVecEnv(env_cfg, rcfg.route_config_from_dict(cfg, max_route_index=prefixes[0]), route_q, n_envs, device=device, seed=seed,
+                      first_env_id=rank * n_envs)
 
     total = int(algo.get("total_timesteps", 100_000))
     model_kwargs = {k: v for k, v in algo.items() if k not in ("total_timesteps", "n_steps", "batch_size")}
     n_steps = int(args.n_steps or algo.get("n_steps", 2048))
-    batch = int(args.batch_size or algo.get("batch_size", 64))
+    batch = int(args.batch_size or algo.get("batch_size", 64))     # the global minibatch: PPO takes batch // world rows per rank
     pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=n_steps, batch_size=batch, hidden=checkpoint.hidden_for_run(args.hidden, init_checkpoint))
-    # the prefix curriculum: a device tracker after every env step (the rollout stays one hipGraph replay)
+    # the prefix curriculum: a device tracker after every env step (the rollout stays one hipGraph replay); data parallel: per-step episode
+    # records, exchanged and replayed once per chunk of KP1_DONE_EXCHANGE_STEPS steps
     curriculum = RoutePrefixCurriculumDevice.from_config(cfg, W)
     ppo = PPO(env, pcfg, curriculum=curriculum, dist=Dist(), backend="hip")
     if init_checkpoint:
         # PPO.load(..., env=vec_env) + learn(reset_num_timesteps=False): weights, Adam state, step clock; the YAML's learning rate wins
         ppo.load_checkpoint(init_checkpoint, restore_timesteps=True, restore_hyperparameters=True)
-        print(f"Resuming route policy from {init_checkpoint}")
+        if rank == 0:
+            print(f"Resuming route policy from {init_checkpoint}")
 
     anchor = None
     anchor_cfg = TeacherAnchorConfig(**(route_cfg.get("teacher_anchor", {}) or {}))
     if anchor_cfg.enabled:
+        # every rank draws the same batch from the same default_rng(0) stream and steps identical parameters: the ranks stay in step
         anchor = RouteTeacherAnchor(anchor_cfg)
         anchor.on_training_start(ppo)
     checkpoint_freq = max(int(runtime_cfg.get("checkpoint_freq", 250_000)), 1)
@@ -110,56 +134,67 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
         ppo.train()
         it += 1
         if ppo.num_timesteps - start_steps >= next_checkpoint:   # PeriodicCheckpointCallback (callbacks.py)
-            checkpoint.save(root / "checkpoints" / f"model_{ppo.num_timesteps - start_steps}_steps", ppo, env_cfg)
+            if rank == 0:
+                checkpoint.save(root / "checkpoints" / f"model_{ppo.num_timesteps - start_steps}_steps", ppo, env_cfg)
             next_checkpoint += checkpoint_freq
-        if args.log_every and it % args.log_every == 0:
+        if args.log_every and it % args.log_every == 0 and rank == 0:
             s = curriculum.summary()
             print(f"[route] it={it} steps={ppo.num_timesteps} fps={(ppo.num_timesteps - start_steps) / (time.time() - t0):,.0f} prefix={s['prefix_end_index']} "
                   f"succ={s['recent_success_rate']:.3f} rew={ppo.rew_buf.mean().item():.4f} anchor={anchor.last_loss if anchor else 0.0:.5f}", flush=True)
     torch.cuda.synchronize()
     wall = time.time() - t0
-    latest = root / "model_latest"
-    checkpoint.save(latest, ppo, env_cfg)
-    curriculum_summary = curriculum.summary()
-    (root / "curriculum_history.json").write_text(json.dumps(curriculum_summary, indent=2))
+    summary: dict[str, Any] = {}
+    if rank == 0:     # the artefacts, the sequential evaluation and the gate
+        latest = root / "model_latest"
+        checkpoint.save(latest, ppo, env_cfg)
+        curriculum_summary = curriculum.summary()
+        (root / "curriculum_history.json").write_text(json.dumps(curriculum_summary, indent=2))
 
-    def policy(obs: torch.Tensor) -> torch.Tensor:
-        return ppo.predict(obs.float().contiguous(), deterministic=True)
+        def policy(obs: torch.Tensor) -> torch.Tensor:
+            return ppo.predict(obs.float().contiguous(), deterministic=True)
 
-    def evaluate(*, artifact_root: Path, start_index: int, end_index: int) -> dict[str, Any]:
-        out = evaluate_sequential_route(policy=policy, cfg=cfg, route_q=route_q, artifact_root=artifact_root, start_index=start_index, end_index=end_index,
-                                        device=args.device)
-        return {k: v for k, v in out.items() if k not in ("rows", "chunk_metrics", "final_q")}
+        def evaluate(*, artifact_root: Path, start_index: int, end_index: int) -> dict[str, Any]:
+            out = evaluate_sequential_route(policy=policy, cfg=cfg, route_q=route_q, artifact_root=artifact_root, start_index=start_index, end_index=end_index,
+                                            device=device)
+            return {k: v for k, v in out.items() if k not in ("rows", "chunk_metrics", "final_q")}
 
-    eval_end = min(int(curriculum_summary["prefix_end_index"]), W - 1)
-    eval_summary = evaluate(artifact_root=root / "route_eval_sequential", start_index=1, end_index=eval_end)
-    gate_summary: dict[str, Any] = {"enabled": False}
-    gate_cfg = route_cfg.get("sequential_gate", {}) or {}
-    if bool(gate_cfg.get("enabled", False)):
-        gate_summary = evaluate_route_gate(evaluate=evaluate, artifact_root=root / "route_gate", prefixes=[int(x) for x in gate_cfg.get("prefixes", [20, 40, 80, 120, 180])],
-                                           full_end_index=gate_cfg.get("full_end_index"),
-                                           min_prefix120_success_rate=float(gate_cfg.get("min_prefix120_success_rate", 0.98)),
-                                           best_full_longest_prefix=int(gate_cfg.get("best_full_longest_prefix", 170)),
-                                           full_prefix_tolerance=int(gate_cfg.get("full_prefix_tolerance", 20)), checkpoint=str(latest), config=str(args.config),
-                                           route_path=str(route_path))
-        if bool(gate_summary.get("accepted", False)):
-            src = Path(str(latest) + ".zip")
-            dst = root / "model_sequential_gate_accepted.zip"
-            if src.exists():
-                shutil.copy2(src, dst)
-                gate_summary["accepted_model_path"] = str(dst)
-    summary = {
-        "schema_version": "v5.route_curriculum.training_summary.v1", "run_id": args.run_id, "route_path": str(route_path),
-        "init_checkpoint": str(init_checkpoint) if init_checkpoint else None, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "model_path": str(latest), "n_envs": n_envs, "device": "MI355X",
-        "curriculum_summary": curriculum_summary, "teacher_anchor_summary": anchor.summary() if anchor is not None else {"enabled": False},
-        "route_eval_sequential_summary": eval_summary, "route_gate_summary": gate_summary, "config": cfg,
-        "num_timesteps": int(ppo.num_timesteps), "wall_seconds": wall, "env_steps_per_second": (ppo.num_timesteps - start_steps) / max(wall, 1e-9),
-        "observation_dim": int(ppo.obs_dim),
-    }
-    (root / "training_summary.json").write_text(json.dumps(summary, indent=2, default=str))
-    print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "model_latest": str(latest) + ".zip", "prefix_end_index": curriculum_summary["prefix_end_index"],
-                      "env_steps_per_second": summary["env_steps_per_second"]}, indent=2))
+        eval_end = min(int(curriculum_summary["prefix_end_index"]), W - 1)
+        eval_summary = evaluate(artifact_root=root / "route_eval_sequential", start_index=1, end_index=eval_end)
+        gate_summary: dict[str, Any] = {"enabled": False}
+        gate_cfg = route_cfg.get("sequential_gate", {}) or {}
+        if bool(gate_cfg.get("enabled", False)):
+            gate_summary = evaluate_route_gate(evaluate=evaluate, artifact_root=root / "route_gate", prefixes=[int(x) for x in gate_cfg.get("prefixes", [20, 40, 80, 120, 180])],
+                                               full_end_index=gate_cfg.get("full_end_index"),
+                                               min_prefix120_success_rate=float(gate_cfg.get("min_prefix120_success_rate", 0.98)),
+                                               best_full_longest_prefix=int(gate_cfg.get("best_full_longest_prefix", 170)),
+                                               full_prefix_tolerance=int(gate_cfg.get("full_prefix_tolerance", 20)), checkpoint=str(latest), config=str(args.config),
+                                               route_path=str(route_path))
+            if bool(gate_summary.get("accepted", False)):
+                src = Path(str(latest) + ".zip")
+                dst = root / "model_sequential_gate_accepted.zip"
+                if src.exists():
+                    shutil.copy2(src, dst)
+                    gate_summary["accepted_model_path"] = str(dst)
+        rate = (ppo.num_timesteps - start_steps) / max(wall, 1e-9)     # all ranks' env steps over the training loop
+        summary = {
+            "schema_version": "v5.route_curriculum.training_summary.v1", "run_id": args.run_id, "route_path": str(route_path),
+            "init_checkpoint": str(init_checkpoint) if init_checkpoint else None, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "model_path": str(latest), "n_envs": n_envs * world, "device": "MI355X" if world == 1 else f"{world}x MI355X",
+            "world_size": world,
+            "curriculum_summary": curriculum_summary, "teacher_anchor_summary": anchor.summary() if anchor is not None else {"enabled": False},
+            "route_eval_sequential_summary": eval_summary, "route_gate_summary": gate_summary, "config": cfg,
+            "num_timesteps": int(ppo.num_timesteps), "wall_seconds": wall, "env_steps_per_second": rate, "env_steps_per_s": rate,
+            "observation_dim": int(ppo.obs_dim),
+        }
+        (root / "training_summary.json").write_text(json.dumps(summary, indent=2, default=str))
+        print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "model_latest": str(latest) + ".zip", "prefix_end_index": curriculum_summary["prefix_end_index"],
+                          "env_steps_per_second": summary["env_steps_per_second"]}, indent=2))
+    if ppo.dist.enabled:
+        dist.barrier()                           # the other ranks wait for rank 0's evaluation and artefacts
+        ppo.dist.close()
+    curriculum.close()
     env.close()
+    if own_group:
+        dist.destroy_process_group()
     return summary
 
 
