@@ -153,6 +153,22 @@ int kp1_mlp_create(int32_t device, int32_t hidden, int32_t max_batch, kp1_mlp** 
 /* same, for an observation of obs_dim floats: 56 (ArmKinematicEnv, observation_builder.py:29-94) or 80 (the route wrappers with
  * include_route_keys, route/route_env.py:186-207).  Rows are read with pitch obs_dim or the padded width (64 / 128). */
 int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batch, kp1_mlp** out);
+/* Population handle: K = `replicas` (1..KP1_MLP_MAX_REPLICAS) independent copies of the net -- K weight packs, activation workspaces and
+ * gradient partials -- trained through ONE launch sequence with the replica on a grid axis (z = 2 * replica + net, or grid.y).  hidden 64 or
+ * 128 (the layer-wise Hp = 128 kernels) and 56-float observations only.  Each replica computes exactly what a K = 1 handle computes on the same
+ * inputs: reductions keep a single handle's order and chunking per replica.  kp1_mlp_create / _create_ex make K = 1 handles.
+ * Buffer layout of the entry points below for a K-replica handle (K = 1: the layouts documented at each entry point):
+ *   kp1_mlp_pack_weights, kp1_mlp_adam_step: params, grad, exp_avg, exp_avg_sq are [K][num_params]; one clip norm per replica, one shared
+ *     Adam step count (all replicas step together);
+ *   kp1_mlp_forward: obs holds K * n rows, replica-major (replica r = rows [r n, (r + 1) n)); n = rows per replica; every output likewise
+ *     [K][n][...];
+ *   kp1_mlp_loss_grad: idx (required) is int64 [K][n], row indices into the shared obs / actions / old_log_prob / advantages / returns
+ *     buffers; grad_out [K][num_params]; stats_out [K][4]; adv_stats_dev [K][2] (mean, 1/(std + 1e-8) of each replica's minibatch);
+ *   kp1_mlp_forward_env_step, kp1_mlp_time_kernels and the KP1_MLP_OPT_BF16X3_WGRAD option return KP1_ERR_UNSUPPORTED. */
+#define KP1_MLP_MAX_REPLICAS 16
+int kp1_mlp_create_population(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batch, int32_t replicas, kp1_mlp** out);
+/* K of the handle (1 for kp1_mlp_create / _create_ex), 0 for NULL */
+int32_t kp1_mlp_replicas(const kp1_mlp* m);
 int kp1_mlp_destroy(kp1_mlp* m);
 /* number of f32 parameters in SB3 state_dict order (log_std, pi.0.w, pi.0.b, pi.2.w, pi.2.b, vf.0.w, ..., action_net.w/b, value_net.w/b) */
 int64_t kp1_mlp_num_params(int32_t hidden);

@@ -122,6 +122,9 @@ struct GemmNT {
   float* colsum; int64_t strideColsum;                 // EPI_DTANH: per-row-block column sums of C (bias-gradient partials)
                                                        //   written to colsum[blockIdx.x * 2*strideColsum + z*strideColsum + n]
   int M, N, K, Kreal;                                  // K multiple of 32; A columns >= Kreal read as 0
+  // population handles (POP kernels): grid.z = 2 * reps, z = 2 * replica + net; replica r reads / writes at base + r * r_* (elements)
+  int reps;
+  unsigned r_A, r_gather, r_W, r_bias, r_C, r_aux, r_colsum;
 };
 
 // C = epi(A W^T).  One workgroup owns 64 rows x BN columns (BN = 256: the whole hidden width, or 128 for small
@@ -130,7 +133,7 @@ struct GemmNT {
 // never re-read.  4 waves, each 64 columns wide (2 MFMA column blocks) and RB row blocks tall.
 // amdgpu_waves_per_eu(1, 2): the 140 KB LDS footprint allows one workgroup (one wave per SIMD) per CU anyway; without
 // the hint hipcc spills the prefetch registers to scratch to stay under the 256-register budget of two waves per SIMD.
-template <int BN, int EPI, int K, int NTH, int BM, int BKS>
+template <int BN, int EPI, int K, int NTH, int BM, int BKS, bool POP = false>
 __global__ void __launch_bounds__(NTH) gemm_nt_kernel(const GemmNT g) {
   constexpr int NW = NTH / 64, LDS_T = BKS + 4, KC = BKS / 4;  // BKS = k depth of one W stage, LDS_T its LDS pitch  // NTH = 512: two waves per SIMD share the MFMA pipe and split the epilogue VALU work
   constexpr int KQ = K / 4, A_LOADS = BM * KQ / NTH;  // float4 per A row / per thread: all issued before any is used
@@ -143,10 +146,12 @@ __global__ void __launch_bounds__(NTH) gemm_nt_kernel(const GemmNT g) {
   float* Ws0 = lds + BM * lda_s;
   float* Ws1 = Ws0 + BN * LDS_T;
 
-  const int z = blockIdx.z;
+  const int z = POP ? (int)(blockIdx.z & 1u) : (int)blockIdx.z;
+  const unsigned rep = POP ? blockIdx.z >> 1 : 0u;   // replica of a population handle (0: single handle)
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const float* __restrict__ A = g.A + z * g.strideA;
-  const float* __restrict__ W = g.W + z * g.strideW + (int64_t)n0 * 32;  // k-slab major: [K/32][N][32]
+  const float* __restrict__ A = g.A + (POP ? rep * g.r_A : 0u) + z * g.strideA;
+  const float* __restrict__ W = g.W + (POP ? rep * g.r_W : 0u) + z * g.strideW + (int64_t)n0 * 32;  // k-slab major: [K/32][N][32]
+  const int64_t* __restrict__ gather = (POP && g.gather) ? g.gather + rep * g.r_gather : g.gather;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave / WN, wc = wave % WN;
 
@@ -178,7 +183,7 @@ __global__ void __launch_bounds__(NTH) gemm_nt_kernel(const GemmNT g) {
 #pragma unroll
     for (int j = 0; j < A_LOADS; ++j) {
       const int m = min(m0 + (tid + NTH * j) / KQ, g.M - 1);
-      arow[j] = g.gather ? g.gather[m] : (int64_t)m;
+      arow[j] = gather ? gather[m] : (int64_t)m;
     }
 #pragma unroll
     for (int j = 0; j < A_LOADS; ++j) {
@@ -255,17 +260,17 @@ __global__ void __launch_bounds__(NTH) gemm_nt_kernel(const GemmNT g) {
       }
   __syncthreads();
   KP1_TR(10)
-  float* __restrict__ C = g.C + z * g.strideC;
+  float* __restrict__ C = g.C + (POP ? rep * g.r_C : 0u) + z * g.strideC;
   const int c4 = tid % CQ;                      // fixed column group per thread
   const int ncol = n0 + 4 * c4;
   f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (EPI == EPI_BIAS_TANH) bias4 = *reinterpret_cast<const f32x4*>(g.bias + z * g.strideBias + ncol);
+  if constexpr (EPI == EPI_BIAS_TANH) bias4 = *reinterpret_cast<const f32x4*>(g.bias + (POP ? rep * g.r_bias : 0u) + z * g.strideBias + ncol);
   f32x4 hv[EPI == EPI_DTANH ? C_ITERS : 1];
   if constexpr (EPI == EPI_DTANH) {
 #pragma unroll
     for (int j = 0; j < C_ITERS; ++j) {
       const int m = min(m0 + (tid + NTH * j) / CQ, g.M - 1);
-      hv[j] = *reinterpret_cast<const f32x4*>(g.aux + z * g.strideAux + (int64_t)m * g.ldc + ncol);
+      hv[j] = *reinterpret_cast<const f32x4*>(g.aux + (POP ? rep * g.r_aux : 0u) + z * g.strideAux + (int64_t)m * g.ldc + ncol);
     }
   }
   f32x4 csum = {0.f, 0.f, 0.f, 0.f};
@@ -295,7 +300,7 @@ __global__ void __launch_bounds__(NTH) gemm_nt_kernel(const GemmNT g) {
         float t = 0.f;
 #pragma unroll
         for (int k = 0; k < NTH / CQ; ++k) t += red[k * BN + tid];
-        g.colsum[(int64_t)blockIdx.x * 2 * g.strideColsum + z * g.strideColsum + n0 + tid] = t;
+        g.colsum[(POP ? rep * g.r_colsum : 0u) + (int64_t)blockIdx.x * 2 * g.strideColsum + z * g.strideColsum + n0 + tid] = t;
       }
     }
   }
@@ -310,6 +315,8 @@ struct GemmTN {
   int B, Nload;                                      // X columns < Nload are readable (the rest of the tile is zero)
   int chunk;                                         // rows of B reduced per workgroup (multiple of 64)
   int n_i_tiles;
+  int reps;                                          // population: grid.z = 2 * reps, z = 2 * replica + net
+  unsigned r_D, r_X, r_gather, r_slab;               // per-replica element offsets
 };
 
 // partial[chunk][net][o][i] = sum_{b in chunk} D[b][o] X[b][i].   Block tile 128(o) x 128(i), 4 waves 2x2, wave tile
@@ -320,16 +327,18 @@ struct GemmTN {
 // writes its partial tile with plain coalesced stores and tn_reduce_kernel sums the partials in fixed order, so weight
 // gradients are bitwise reproducible (float atomics are not).
 // grid: x = B chunk, y = o_tile * n_i_tiles + i_tile, z = net.
-template <bool GATHER>
+template <bool GATHER, bool POP = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) gemm_tn_kernel(const GemmTN g) {
   constexpr int TB = 64, TT = 128, LDW = TT + 4, LOADS = TB * TT / 4 / 256;  // 8 float4 per thread per operand
   extern __shared__ float lds[];
-  const int z = blockIdx.z;
+  const int z = POP ? (int)(blockIdx.z & 1u) : (int)blockIdx.z;
+  const unsigned rep = POP ? blockIdx.z >> 1 : 0u;
   const int o0 = (blockIdx.y / g.n_i_tiles) * TT, i0 = (blockIdx.y % g.n_i_tiles) * TT;
   const int b_begin = blockIdx.x * g.chunk;
   const int b_end = min(b_begin + g.chunk, g.B);
-  const float* __restrict__ D = g.D + z * g.strideD + o0;
-  const float* __restrict__ X = g.X + z * g.strideX;
+  const float* __restrict__ D = g.D + (POP ? rep * g.r_D : 0u) + z * g.strideD + o0;
+  const float* __restrict__ X = g.X + (POP ? rep * g.r_X : 0u) + z * g.strideX;
+  const int64_t* __restrict__ gatherX = (POP && GATHER) ? g.gatherX + rep * g.r_gather : g.gatherX;   // (no arithmetic on the null pointer of GATHER = false)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   const int srow = tid >> 5, sc4 = tid & 31;  // staging: f = tid + 256*j -> row = srow + 8*j, c4 = sc4
@@ -345,7 +354,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     int64_t xrow[LOADS];                                                                                  \
     _Pragma("unroll") for (int j = 0; j < LOADS; ++j) {                                                   \
       const int b = min((b0) + srow + 8 * j, b_last);                                                     \
-      xrow[j] = GATHER ? g.gatherX[b] : (int64_t)b;                                                       \
+      xrow[j] = GATHER ? gatherX[b] : (int64_t)b;                                                       \
     }                                                                                                     \
     _Pragma("unroll") for (int j = 0; j < LOADS; ++j) {                                                   \
       const int b = min((b0) + srow + 8 * j, b_last);                                                     \
@@ -421,7 +430,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
       }
   __syncthreads();
   KP1_TR(11)
-  float* __restrict__ P = g.slab + blockIdx.x * g.slab_chunk_stride + z * g.slab_net_stride;
+  float* __restrict__ P = g.slab + (POP ? rep * g.r_slab : 0u) + blockIdx.x * g.slab_chunk_stride + z * g.slab_net_stride;
 #pragma unroll
   for (int j = 0; j < TT * TT / 4 / 256; ++j) {
     const int f = tid + 256 * j, o = f >> 5, q = f & 31;
@@ -450,7 +459,30 @@ struct HeadArgs {
   float* hpart;           // per-block partials [n_blocks][hpart_stride]: dW action [7][Hp], dW value [Hp], db2 pi [Hp], db2 vf [Hp],
   int hpart_stride;       //   then 8 head-bias grads, 7 log_std grads, 3 loss sums (policy, value, kl)
   int H;                  // real hidden (<= Hp)
+  // population (POP kernels, grid.y = replica): activations / dz2 at + r * r_act, head partials at + r * r_hpart, advantage partials at
+  // + r * r_partials, head weights at + r * 8 Hp (w3) / + r * 8 (b3, log_std), adv_stats at + 2 r; per-row inputs and outputs (idx, noise,
+  // mean, value, action, clipped, log_prob) at row + r * n
+  unsigned r_act, r_hpart, r_partials;
 };
+
+// HeadArgs of replica `rep` of a population handle
+__device__ __forceinline__ HeadArgs head_args_replica(HeadArgs a, unsigned rep) {
+  const unsigned rows = rep * (unsigned)a.n, heads = rep * (unsigned)(HEADS * a.Hp);
+  a.h2 += rep * a.r_act;
+  a.w3 += heads; a.b3 += rep * HEADS; a.log_std += rep * HEADS;
+  if (a.noise) a.noise += rows * ACT;
+  if (a.mean) a.mean += rows * ACT;
+  if (a.value) a.value += rows;
+  if (a.action) a.action += rows * ACT;
+  if (a.clipped) a.clipped += rows * ACT;
+  if (a.log_prob) a.log_prob += rows;
+  if (a.idx) a.idx += rows;
+  if (a.adv_partials) a.adv_partials += rep * a.r_partials;
+  if (a.adv_stats) a.adv_stats += 2 * rep;
+  if (a.dz2) a.dz2 += rep * a.r_act;
+  if (a.hpart) a.hpart += rep * a.r_hpart;
+  return a;
+}
 
 constexpr int HEAD_ROWS = 32;  // rows per 256-thread block: thread = (row = t/8, out = t%8)
 
@@ -468,7 +500,9 @@ __device__ __forceinline__ float head_dot(const float* __restrict__ h, const flo
 }
 
 // policy.forward tail: heads + Gaussian sampling (SB3 DiagGaussianDistribution)
-__global__ void __launch_bounds__(256) head_infer_kernel(const HeadArgs a) {
+template <bool POP = false>
+__global__ void __launch_bounds__(256) head_infer_kernel(const HeadArgs a_) {
+  const HeadArgs a = POP ? head_args_replica(a_, blockIdx.y) : a_;
   extern __shared__ float w3s[];  // [8][Hp]
   for (int k = threadIdx.x; k < HEADS * a.Hp; k += 256) w3s[k] = a.w3[k];
   __syncthreads();
@@ -501,8 +535,14 @@ __global__ void __launch_bounds__(256) head_infer_kernel(const HeadArgs a) {
 }
 
 // per-block partial (sum, sum of squares) of the gathered advantages, fp64, fixed order => deterministic
-__global__ void __launch_bounds__(256) adv_partials_kernel(const float* __restrict__ adv, const int64_t* __restrict__ idx, int n, double* __restrict__ partials) {
+template <bool POP = false>
+__global__ void __launch_bounds__(256) adv_partials_kernel(const float* __restrict__ adv, const int64_t* __restrict__ idx, int n, double* __restrict__ partials,
+                                                           unsigned r_partials) {
   __shared__ double s1[256], s2[256];
+  if constexpr (POP) {   // replica blockIdx.y: its own index row and partials
+    idx += blockIdx.y * (unsigned)n;
+    partials += blockIdx.y * r_partials;
+  }
   double a = 0.0, b = 0.0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     const double v = (double)adv[idx ? idx[i] : (int64_t)i];
@@ -526,8 +566,9 @@ __global__ void __launch_bounds__(256) adv_partials_kernel(const float* __restri
 }
 
 // heads forward + PPO loss gradient + dZ2 for both nets + head weight/bias gradients
-template <int HP>
-__global__ void __launch_bounds__(256) head_train_kernel(const HeadArgs a) {
+template <int HP, bool POP = false>
+__global__ void __launch_bounds__(256) head_train_kernel(const HeadArgs a_) {
+  const HeadArgs a = POP ? head_args_replica(a_, blockIdx.y) : a_;
   // all LDS is one dynamic array (16-B aligned base: head_dot reads float4; guide G17)
   extern __shared__ float smem[];
   const int hpitch = a.Hp + 4;             // row pitch of the staged activations: conflict-free float4 row reads
@@ -802,9 +843,26 @@ __device__ __forceinline__ void pack_one(int64_t i, float v, const ParamLayout& 
   }
 }
 
+// the kernel-format weights of replica `rep` of a population handle: every array holds one copy per replica back to back
+__device__ __forceinline__ Packed packed_replica(Packed k, const ParamLayout& L, unsigned rep) {
+  const unsigned hp = (unsigned)L.Hp, w1 = rep * 2u * hp * (unsigned)L.INP, w2 = rep * 2u * hp * hp, b = rep * 2u * hp;
+  k.w1p += w1; k.w1f += w1;
+  k.w2 += w2; k.w2t += w2; k.w2f += w2; k.w2tf += w2;
+  k.b1 += b; k.b2 += b;
+  k.w3 += rep * (unsigned)HEADS * hp;
+  k.b3 += rep * (unsigned)HEADS; k.log_std += rep * (unsigned)HEADS;
+  return k;
+}
+
+// POP: grid.y = replica, params [K][total]
+template <bool POP = false>
 __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ p, const ParamLayout L, const Packed k) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < L.total) pack_one(i, p[i], L, k);
+  if constexpr (POP) {
+    if (i < L.total) pack_one(i, p[blockIdx.y * (unsigned)L.total + i], L, packed_replica(k, L, blockIdx.y));
+  } else {
+    if (i < L.total) pack_one(i, p[i], L, k);
+  }
 }
 
 // Gradient finalisation: every producer kernel (TN GEMMs, backward-GEMM epilogue, head kernel) wrote per-workgroup
@@ -821,7 +879,20 @@ struct FinalizeArgs {
   const float* log_std;
   float* grad; float* stats; double* sumsq;
   int* step_counter;  // Adam step count kept on the device (hipGraph replays cannot change a scalar kernel argument)
+  // population (POP kernel, grid.y = replica): partials at + r * r_*, grad at + r * total, stats at + 4 r, log_std at + 8 r; the shared
+  // step counter is advanced by replica 0 only
+  unsigned r_slab2, r_slab1, r_bslab, r_hpart, r_sumsq;
 };
+
+__device__ __forceinline__ FinalizeArgs finalize_args_replica(FinalizeArgs a, unsigned rep) {
+  a.slab2 += rep * a.r_slab2; a.slab1 += rep * a.r_slab1; a.bslab += rep * a.r_bslab; a.hpart += rep * a.r_hpart;
+  a.log_std += rep * (unsigned)HEADS;
+  a.grad += rep * (unsigned)a.L.total;
+  if (a.stats) a.stats += 4u * rep;
+  a.sumsq += rep * a.r_sumsq;
+  if (rep != 0) a.step_counter = nullptr;
+  return a;
+}
 
 template <int UNROLL>
 __device__ __forceinline__ float sum_strided(const float* __restrict__ p, int64_t stride, int n) {
@@ -913,7 +984,9 @@ __device__ __forceinline__ int64_t finalize_wide_index(const ParamLayout& L, int
 __host__ __device__ inline int64_t finalize_vec_items(const ParamLayout& L) { return 2 * ((int64_t)L.H * L.H / 4 + (int64_t)L.H * L.IN / 4); }
 // (a form with 2 or 4 lanes splitting the chunks of one item was measured and removed: DESIGN.md 4.3)
 
-__global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a, int n_main) {
+template <bool POP = false>
+__global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a_, int n_main) {
+  const FinalizeArgs a = POP ? finalize_args_replica(a_, blockIdx.y) : a_;
   const ParamLayout& L = a.L;
   __shared__ double sq[4];
   __shared__ float red[8][32];
@@ -1028,8 +1101,13 @@ __global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a
   if (threadIdx.x == 0) a.sumsq[blockIdx.x] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
 }
 
-__global__ void __launch_bounds__(256) sumsq_partials_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partials) {
+template <bool POP = false>
+__global__ void __launch_bounds__(256) sumsq_partials_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partials, unsigned r_partials) {
   __shared__ double s[256];
+  if constexpr (POP) {   // replica blockIdx.y: grad [K][n]
+    g += blockIdx.y * (unsigned)n;
+    partials += blockIdx.y * r_partials;
+  }
   double a = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) a += (double)g[i] * (double)g[i];
   s[threadIdx.x] = a;
@@ -1048,12 +1126,22 @@ __global__ void __launch_bounds__(256) sumsq_partials_kernel(const float* __rest
 // latency chain per thread (scattered repack stores behind div / sqrt), so it wants more threads, not fatter ones.
 // (The loops over VEC = 1 are one trip.  Written without them -- one `i`, its `i < n` shared by the load clamp and the store guard -- the kernel
 // compiles to a different register assignment and load order than the measured one, so this form is kept.)
+// POP: grid.y = replica; p, g, m, v are [K][n], the norm partials of replica r sit at + r * r_partials, one clip norm per replica, one
+// shared step count
 constexpr int ADAM_BLOCK = 256, VEC = 1;
+template <bool POP = false>
 __global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                    int64_t n, const double* __restrict__ partials, int n_partials, float lr, float eps, float max_norm,
-                                                   float bc1, float bc2_sqrt, const ParamLayout L, const Packed k, int zero_grad,
-                                                   const int* __restrict__ step_counter, int host_step, const int* __restrict__ actor_extra) {
+                                                   float bc1, float bc2_sqrt, const ParamLayout L, const Packed k_, int zero_grad,
+                                                   const int* __restrict__ step_counter, int host_step, const int* __restrict__ actor_extra,
+                                                   unsigned r_partials) {
   __shared__ float scale_s;
+  const Packed k = POP ? packed_replica(k_, L, blockIdx.y) : k_;
+  if constexpr (POP) {
+    const unsigned o = blockIdx.y * (unsigned)n;
+    p += o; g += o; m += o; v += o;
+    partials += blockIdx.y * r_partials;
+  }
   // this thread's elements: their loads do not depend on the norm, so they go out first and share one memory round trip with the
   // step count and the norm partials below (the kernel is a chain of round trips: it moves 2.6 MB)
   const int64_t i0 = ((int64_t)blockIdx.x * ADAM_BLOCK + threadIdx.x) * VEC;
@@ -1121,6 +1209,9 @@ __global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(float* __restrict__ p,
 // ============================================================================================ host
 struct kp1_mlp {
   int device = 0, H = 0, Hp = 0, max_batch = 0;
+  // Population handle (kp1_mlp_create_population): K independent replicas of the layer-wise (Hp = 128) path, launched together with the
+  // replica on a grid axis.  Every array below except xf and step_dev holds K copies back to back (replica r at + r * its per-replica size).
+  int K = 1;
   ParamLayout L;
   Packed k{};
   float* h1 = nullptr;   // [2][max_batch][Hp]
@@ -1204,6 +1295,7 @@ struct ProfScope {
 namespace {
 
 constexpr int N_PARTIALS = 128;
+constexpr int PARTIALS_STRIDE = 2 * N_PARTIALS + 2048;   // doubles of kp1_mlp::partials per replica
 // batch chunks of the dW2 / dW1 partial tiles of gemm_tn_split_kernel: 8 chunks x 32 tiles = one dW2 workgroup per CU, 16 chunks x 16 tiles of
 // quarter-size dW1 workgroups (profiles/r02_ab_tn_wave_split.log)
 constexpr int TN_SPLIT2 = 8, TN_SPLIT1 = 16;
@@ -1230,7 +1322,7 @@ constexpr size_t TN_LDS_BYTES = sizeof(float) * 2 * 2 * 64 * (128 + 4);
 // 64 rows x 128 columns, 256 threads.  Measured alternatives at M = 8192 (all within 7 %): 32 x 256 tiles with 16-deep
 // stages and two workgroups per CU 29.9 us, 64 x 256 / 256 threads 28.9 us, this one 28.0 us -- the three GEMM kinds all
 // plateau near 75 TFLOP/s, see DESIGN.md section 5.
-template <int BN, int EPI, int K>
+template <int BN, int EPI, int K, bool POP = false>
 int launch_nt_inst(const GemmNT& g, hipStream_t stream) {
   constexpr int NTH = BN == 256 ? 512 : 256;
   constexpr int BM = 64;
@@ -1238,8 +1330,8 @@ int launch_nt_inst(const GemmNT& g, hipStream_t stream) {
   size_t bytes = sizeof(float) * (BM * (size_t)(K + 4) + 2 * (size_t)BN * (BKS + 4));
   const size_t epi = sizeof(float) * (BM * (size_t)(BN + 4) + (size_t)(NTH / (BN / 4)) * BN);  // C tile + bias-partial scratch
   if (epi > bytes) bytes = epi;
-  HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_kernel<BN, EPI, K, NTH, BM, BKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  hipLaunchKernelGGL((gemm_nt_kernel<BN, EPI, K, NTH, BM, BKS>), dim3((g.M + BM - 1) / BM, g.N / BN, 2), dim3(NTH), bytes, stream, g);
+  HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_kernel<BN, EPI, K, NTH, BM, BKS, POP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  hipLaunchKernelGGL((gemm_nt_kernel<BN, EPI, K, NTH, BM, BKS, POP>), dim3((g.M + BM - 1) / BM, g.N / BN, POP ? 2 * g.reps : 2), dim3(NTH), bytes, stream, g);
   return KP1_OK;
 }
 
@@ -1252,6 +1344,12 @@ int nt_row_tiles(int n, int Hp) {
 template <int EPI>
 int launch_nt(const GemmNT& g, hipStream_t stream) {
   if (g.N % 128 != 0) return fail(KP1_ERR_INVALID, "gemm_nt needs N % 128 == 0");
+  if (g.reps > 1) {   // population handles: Hp = 128 (narrow tiles, as a single handle of that width uses), 64-float observations
+    if (g.N != 128) return fail(KP1_ERR_UNSUPPORTED, "population gemm_nt is instantiated for N = 128");
+    if (g.K == 64) return launch_nt_inst<128, EPI, 64, true>(g, stream);
+    if (g.K == 128) return launch_nt_inst<128, EPI, 128, true>(g, stream);
+    return fail(KP1_ERR_UNSUPPORTED, "population gemm_nt is instantiated for K in {64, 128}");
+  }
   // 256-column workgroups (A read once per row block) when that still fills the chip, else 128-column ones
   const int row_tiles = (g.M + 63) / 64;
   const bool wide = (g.N % 256 == 0) && row_tiles * 2 >= 200;
@@ -1338,10 +1436,14 @@ int launch_tn_frag(const TnFragArgs& t, hipStream_t stream) {
 }
 
 // forward layers 1 and 2 for n rows (both nets): h1, h2 filled
+// (population: n rows per replica; without idx replica r reads obs rows [r n, (r + 1) n), with idx its index row idx[r][0..n))
 int launch_forward_layers(kp1_mlp* m, const float* obs, int obs_stride, const int64_t* idx, int n, hipStream_t stream) {
   const int Hp = m->Hp, IN = m->L.IN, INP = m->L.INP;
   const int64_t act_stride = (int64_t)m->max_batch * Hp;
   GemmNT g{};
+  g.reps = m->K;
+  g.r_A = idx ? 0u : (unsigned)(n * obs_stride); g.r_gather = (unsigned)n;
+  g.r_W = (unsigned)(2 * Hp * INP); g.r_bias = (unsigned)(2 * Hp); g.r_C = (unsigned)(2 * act_stride);
   g.A = obs; g.lda = obs_stride; g.strideA = 0; g.gather = idx;
   g.W = m->k.w1p; g.strideW = (int64_t)Hp * INP;
   g.bias = m->k.b1; g.strideBias = Hp;
@@ -1351,6 +1453,7 @@ int launch_forward_layers(kp1_mlp* m, const float* obs, int obs_stride, const in
   int rc = launch_nt<EPI_BIAS_TANH>(g, stream);
   if (rc != KP1_OK) return rc;
   g.A = m->h1; g.lda = Hp; g.strideA = act_stride; g.gather = nullptr;
+  g.r_A = (unsigned)(2 * act_stride); g.r_W = (unsigned)(2 * Hp * Hp);
   g.W = m->k.w2; g.strideW = (int64_t)Hp * Hp;
   g.bias = m->k.b2;
   g.C = m->h2;
@@ -1372,8 +1475,21 @@ int launch_tn(kp1_mlp* m, GemmTN t, int n_o_tiles, int slab_cols, float* slab, i
   t.slab_ld = slab_cols;
   t.slab_net_stride = (int64_t)Hp * slab_cols;
   t.slab_chunk_stride = 2 * t.slab_net_stride;
-  const dim3 grid(n_chunks, n_o_tiles * t.n_i_tiles, 2);
-  if (t.gatherX) {
+  const dim3 grid(n_chunks, n_o_tiles * t.n_i_tiles, 2 * m->K);
+  if (m->K > 1) {   // population: replica r's activations at + r * 2 act_stride, its gather row at + r * B, its slab at + r * 64 chunks
+    t.reps = m->K;
+    t.r_D = (unsigned)(2 * (int64_t)m->max_batch * Hp);
+    t.r_X = t.gatherX ? 0u : t.r_D;
+    t.r_gather = (unsigned)t.B;
+    t.r_slab = (unsigned)(64 * t.slab_chunk_stride);
+    if (t.gatherX) {
+      HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES));
+      hipLaunchKernelGGL((gemm_tn_kernel<true, true>), grid, dim3(256), TN_LDS_BYTES, stream, t);
+    } else {
+      HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES));
+      hipLaunchKernelGGL((gemm_tn_kernel<false, true>), grid, dim3(256), TN_LDS_BYTES, stream, t);
+    }
+  } else if (t.gatherX) {
     HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES));
     hipLaunchKernelGGL(gemm_tn_kernel<true>, grid, dim3(256), TN_LDS_BYTES, stream, t);
   } else {
@@ -1392,7 +1508,32 @@ int64_t kp1_mlp_num_params_ex(int32_t hidden, int32_t obs_dim) { return hidden >
 
 int kp1_mlp_create(int32_t device, int32_t hidden, int32_t max_batch, kp1_mlp** out) { return kp1_mlp_create_ex(device, hidden, KP1_MLP_IN, max_batch, out); }
 
+namespace {
+int mlp_create(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batch, int32_t replicas, kp1_mlp** out);
+}
+
 int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batch, kp1_mlp** out) {
+  return mlp_create(device, hidden, obs_dim, max_batch, 1, out);
+}
+
+int kp1_mlp_create_population(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batch, int32_t replicas, kp1_mlp** out) {
+  if (replicas < 1 || replicas > KP1_MLP_MAX_REPLICAS) return fail(KP1_ERR_INVALID, "replicas must be in [1, KP1_MLP_MAX_REPLICAS]");
+  if (hidden != 64 && hidden != 128)
+    return fail(KP1_ERR_UNSUPPORTED, "population handles run the layer-wise kernels: hidden must be 64 or 128");
+  if (obs_dim != KP1_MLP_IN) return fail(KP1_ERR_UNSUPPORTED, "population handles take the 56-float observation");
+  // per-replica element offsets are 32-bit: the largest array (the dW2 partial slab, 64 chunks x 2 nets x 128 x 128) and the activations
+  // of K replicas must stay below 2^31 elements
+  const int64_t mb = ((int64_t)max_batch + 127) / 128 * 128;
+  if (max_batch <= 0 || (int64_t)replicas * 2 * mb * 128 >= ((int64_t)1 << 31)) return fail(KP1_ERR_INVALID, "max_batch too large for a population handle");
+  return mlp_create(device, hidden, obs_dim, max_batch, replicas, out);
+}
+
+int32_t kp1_mlp_replicas(const kp1_mlp* m) { return m ? m->K : 0; }
+
+}  // extern "C"
+
+namespace {
+int mlp_create(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batch, int32_t replicas, kp1_mlp** out) {
   if (!out || hidden <= 0 || hidden > 1024 || max_batch <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_mlp_create");
   if (obs_dim != KP1_MLP_IN && obs_dim != KP1_MLP_IN_ROUTE)
     return fail(KP1_ERR_UNSUPPORTED, "obs_dim must be 56 (ArmKinematicEnv) or 80 (route observation keys)");
@@ -1407,11 +1548,12 @@ int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t m
   HIP_TRY(hipSetDevice(device));
   kp1_mlp* m = new kp1_mlp();
   m->device = device;
+  m->K = replicas;
   m->H = hidden;
   m->L = make_layout(hidden, obs_dim);
   m->Hp = m->L.Hp;
   m->max_batch = (max_batch + 127) / 128 * 128;
-  const int64_t Hp = m->Hp, mb = m->max_batch, INP = m->L.INP;
+  const int64_t Hp = m->Hp, mb = m->max_batch, INP = m->L.INP, K = m->K;
   auto alloc = [&](void** p, size_t bytes) -> int {
     if (hipMalloc(p, bytes) != hipSuccess) return fail(KP1_ERR_ALLOC, "hipMalloc failed in kp1_mlp_create");
     m->allocs.push_back(*p);
@@ -1419,28 +1561,28 @@ int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t m
   };
   int rc = KP1_OK;
 #define MLP_ALLOC(ptr, count) if (rc == KP1_OK) rc = alloc((void**)&(ptr), sizeof(*(ptr)) * (size_t)(count))
-  MLP_ALLOC(m->k.w1p, 2 * Hp * INP);
-  MLP_ALLOC(m->k.b1, 2 * Hp);
-  MLP_ALLOC(m->k.w2, 2 * Hp * Hp);
-  MLP_ALLOC(m->k.w2t, 2 * Hp * Hp);
-  MLP_ALLOC(m->k.w1f, 2 * Hp * INP);
-  MLP_ALLOC(m->k.w2f, 2 * Hp * Hp);
-  MLP_ALLOC(m->k.w2tf, 2 * Hp * Hp);
-  MLP_ALLOC(m->k.b2, 2 * Hp);
-  MLP_ALLOC(m->k.w3, HEADS * Hp);
-  MLP_ALLOC(m->k.b3, HEADS);
-  MLP_ALLOC(m->k.log_std, HEADS);
-  MLP_ALLOC(m->h1, 2 * mb * Hp);
-  MLP_ALLOC(m->h2, 2 * mb * Hp);
-  MLP_ALLOC(m->dz2, 2 * mb * Hp);
-  MLP_ALLOC(m->dz1, 2 * mb * Hp);
+  MLP_ALLOC(m->k.w1p, K * 2 * Hp * INP);
+  MLP_ALLOC(m->k.b1, K * 2 * Hp);
+  MLP_ALLOC(m->k.w2, K * 2 * Hp * Hp);
+  MLP_ALLOC(m->k.w2t, K * 2 * Hp * Hp);
+  MLP_ALLOC(m->k.w1f, K * 2 * Hp * INP);
+  MLP_ALLOC(m->k.w2f, K * 2 * Hp * Hp);
+  MLP_ALLOC(m->k.w2tf, K * 2 * Hp * Hp);
+  MLP_ALLOC(m->k.b2, K * 2 * Hp);
+  MLP_ALLOC(m->k.w3, K * HEADS * Hp);
+  MLP_ALLOC(m->k.b3, K * HEADS);
+  MLP_ALLOC(m->k.log_std, K * HEADS);
+  MLP_ALLOC(m->h1, K * 2 * mb * Hp);
+  MLP_ALLOC(m->h2, K * 2 * mb * Hp);
+  MLP_ALLOC(m->dz2, K * 2 * mb * Hp);
+  MLP_ALLOC(m->dz1, K * 2 * mb * Hp);
   MLP_ALLOC(m->xf, mb * INP);
-  MLP_ALLOC(m->partials, 2 * N_PARTIALS + 2048);
-  MLP_ALLOC(m->slab, (int64_t)64 * 2 * Hp * Hp);
-  MLP_ALLOC(m->slab1, (int64_t)64 * 2 * Hp * INP);
+  MLP_ALLOC(m->partials, K * PARTIALS_STRIDE);
+  MLP_ALLOC(m->slab, K * 64 * 2 * Hp * Hp);
+  MLP_ALLOC(m->slab1, K * 64 * 2 * Hp * INP);
   MLP_ALLOC(m->step_dev, 4);
-  MLP_ALLOC(m->bslab, (mb / 32) * 2 * Hp);
-  MLP_ALLOC(m->hpart, (mb / 32) * (10 * Hp + 32));
+  MLP_ALLOC(m->bslab, K * (mb / 32) * 2 * Hp);
+  MLP_ALLOC(m->hpart, K * (mb / 32) * (10 * Hp + 32));
 #undef MLP_ALLOC
   if (rc != KP1_OK) {
     kp1_mlp_destroy(m);
@@ -1449,6 +1591,9 @@ int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t m
   *out = m;
   return KP1_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int kp1_mlp_destroy(kp1_mlp* m) {
   if (!m) return KP1_OK;
@@ -1474,7 +1619,7 @@ int kp1_mlp_set_option(kp1_mlp* m, int32_t option, int32_t value) {
       HIP_TRY(hipDeviceSynchronize());
       Packed k = m->k;
       k.formats = PACK_SLAB | PACK_FRAG;
-      hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((m->L.total + 255) / 256)), dim3(256), 0, (hipStream_t)0, m->last_params, m->L, k);
+      hipLaunchKernelGGL(pack_kernel<false>, dim3((unsigned)((m->L.total + 255) / 256)), dim3(256), 0, (hipStream_t)0, m->last_params, m->L, k);
       HIP_TRY(kp1::launch_status());
       HIP_TRY(hipDeviceSynchronize());
       m->slab_stale = false;
@@ -1482,6 +1627,7 @@ int kp1_mlp_set_option(kp1_mlp* m, int32_t option, int32_t value) {
     return KP1_OK;
   }
   if (option == KP1_MLP_OPT_BF16X3_WGRAD) {
+    if (value && m->K > 1) return fail(KP1_ERR_UNSUPPORTED, "the bf16x3 weight-gradient experiment is not available on population handles");
     if (value && !(m->fused && m->Hp == FU_HP)) return fail(KP1_ERR_UNSUPPORTED, "the bf16x3 weight-gradient experiment needs the 2x256 tile kernels");
     if (value && !m->sp_h1) {
       HIP_TRY(hipSetDevice(m->device));
@@ -1522,7 +1668,10 @@ int kp1_mlp_pack_weights(kp1_mlp* m, const float* params, void* stream) {
   if (rc != KP1_OK) return rc;
   Packed k = m->k;
   k.formats = PACK_SLAB | PACK_FRAG;
-  hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((m->L.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, m->L, k);
+  if (m->K > 1)
+    hipLaunchKernelGGL(pack_kernel<true>, dim3((unsigned)((m->L.total + 255) / 256), m->K), dim3(256), 0, (hipStream_t)stream, params, m->L, k);
+  else
+    hipLaunchKernelGGL(pack_kernel<false>, dim3((unsigned)((m->L.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, m->L, k);
   HIP_TRY(kp1::launch_status());
   m->last_params = params;
   m->slab_stale = false;
@@ -1553,7 +1702,12 @@ int kp1_mlp_forward(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n,
   a.h2 = m->h2; a.strideH = (int64_t)m->max_batch * m->Hp; a.Hp = m->Hp; a.n = n; a.H = m->H;
   a.w3 = m->k.w3; a.b3 = m->k.b3; a.log_std = m->k.log_std;
   a.noise = noise; a.mean = mean; a.value = value; a.action = action; a.clipped = clipped_action; a.log_prob = log_prob;
-  hipLaunchKernelGGL(head_infer_kernel, dim3((n + HEAD_ROWS - 1) / HEAD_ROWS), dim3(256), sizeof(float) * HEADS * m->Hp, (hipStream_t)stream, a);
+  if (m->K > 1) {
+    a.r_act = (unsigned)(2 * a.strideH);
+    hipLaunchKernelGGL(head_infer_kernel<true>, dim3((n + HEAD_ROWS - 1) / HEAD_ROWS, m->K), dim3(256), sizeof(float) * HEADS * m->Hp, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(head_infer_kernel<false>, dim3((n + HEAD_ROWS - 1) / HEAD_ROWS), dim3(256), sizeof(float) * HEADS * m->Hp, (hipStream_t)stream, a);
+  }
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
@@ -1561,6 +1715,7 @@ int kp1_mlp_forward(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n,
 int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t obs_stride, const float* noise, float* value, float* action,
                              float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream) {
   if (!m || !env || !obs || !action || !next_obs || !reward || !done) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_forward_env_step");
+  if (m->K > 1) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_env_step is not available on population handles");
   if (!(m->fused && m->Hp == FU_HP) || m->L.INP != 64)
     return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_env_step needs the 2x256 tile kernels and the 56-float observation (padded to 64)");
   if (obs_stride != m->L.IN && obs_stride != m->L.INP) return fail(KP1_ERR_INVALID, "obs_stride must be 56 or 64");
@@ -1598,11 +1753,19 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
   const ParamLayout& L = m->L;
   (void)grad_is_zero;  // every gradient element is written (not accumulated) by grad_finalize_kernel
   const bool fused = m->fused && Hp == FU_HP;
+  const bool pop = m->K > 1;
+  if (pop && !idx) return fail(KP1_ERR_INVALID, "population handles gather their rows through idx [K][n]");
+  const int64_t hpart_rep = (int64_t)(m->max_batch / 32) * (10 * Hp + 32);
   int adv_mode = 0;
   if (adv_stats_dev) adv_mode = 2;
   else if (adv_inv_std > 0.f) adv_mode = 3;
   else if (adv_inv_std == 0.f) adv_mode = 1;
-  if (adv_mode == 1) hipLaunchKernelGGL(adv_partials_kernel, dim3(N_PARTIALS), dim3(256), 0, stream, advantages, idx, n, m->partials);
+  if (adv_mode == 1) {
+    if (pop)
+      hipLaunchKernelGGL(adv_partials_kernel<true>, dim3(N_PARTIALS, m->K), dim3(256), 0, stream, advantages, idx, n, m->partials, (unsigned)PARTIALS_STRIDE);
+    else
+      hipLaunchKernelGGL(adv_partials_kernel<false>, dim3(N_PARTIALS), dim3(256), 0, stream, advantages, idx, n, m->partials, 0u);
+  }
   const int hpart_stride = 10 * Hp + 32;
   if (fused) {
     FusedArgs fa{};
@@ -1635,10 +1798,14 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     a.clip_range = clip_range; a.ent_coef = ent_coef; a.vf_coef = vf_coef; a.inv_count = inv_count;
     a.dz2 = m->dz2;
     a.hpart = m->hpart; a.hpart_stride = hpart_stride;
+    a.r_act = (unsigned)(2 * act_stride); a.r_hpart = (unsigned)hpart_rep; a.r_partials = (unsigned)PARTIALS_STRIDE;
     {
-      const dim3 hgrid((n + HEAD_ROWS - 1) / HEAD_ROWS);
+      const dim3 hgrid((n + HEAD_ROWS - 1) / HEAD_ROWS, m->K);
       const size_t hbytes = sizeof(float) * (HEADS * Hp + HEAD_ROWS * 8 + 84 + 2 * HEAD_ROWS * (Hp + 4));
-      if (Hp == 256) {
+      if (pop) {   // Hp = 128 (kp1_mlp_create_population)
+        HIP_TRY(hipFuncSetAttribute((const void*)head_train_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hbytes));
+        hipLaunchKernelGGL((head_train_kernel<128, true>), hgrid, dim3(256), hbytes, stream, a);
+      } else if (Hp == 256) {
         HIP_TRY(hipFuncSetAttribute((const void*)head_train_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hbytes));
         hipLaunchKernelGGL(head_train_kernel<256>, hgrid, dim3(256), hbytes, stream, a);
       } else {
@@ -1655,6 +1822,9 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     g.aux = m->h1; g.strideAux = act_stride;
     g.colsum = m->bslab; g.strideColsum = Hp;
     g.M = n; g.N = Hp; g.K = Hp; g.Kreal = Hp;
+    g.reps = m->K;
+    g.r_A = g.r_C = g.r_aux = (unsigned)(2 * act_stride); g.r_W = (unsigned)(2 * Hp * Hp);
+    g.r_colsum = (unsigned)((m->max_batch / 32) * 2 * Hp);
     rc = launch_nt<EPI_DTANH>(g, stream);
     if (rc != KP1_OK) return rc;
   }
@@ -1717,12 +1887,17 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
   f.ent_coef = ent_coef; f.inv_count = inv_count; f.log_std = m->k.log_std;
   f.grad = grad_out; f.stats = stats_out; f.sumsq = m->partials + 2 * N_PARTIALS;
   f.step_counter = m->step_dev;
+  f.r_slab2 = (unsigned)(64 * f.s2_chunk); f.r_slab1 = (unsigned)(64 * f.s1_chunk); f.r_bslab = (unsigned)((m->max_batch / 32) * 2 * Hp);
+  f.r_hpart = (unsigned)hpart_rep; f.r_sumsq = (unsigned)PARTIALS_STRIDE;
   const int n_main = (int)((finalize_vec_items(L) + 255) / 256);
   m->n_finalize_blocks = n_main + (int)((finalize_wide_count(L) + 3 + 31) / 32);
   if (m->n_finalize_blocks > 2048) return fail(KP1_ERR_INVALID, "parameter vector too large for the sum-of-squares partial buffer");
   {
     ProfScope ps(m, KP1_MLP_PROFILE_FINALIZE, stream);
-    KP1_LAUNCH(grad_finalize_kernel, dim3(m->n_finalize_blocks), dim3(256), 0, stream, f, n_main);
+    if (pop)
+      KP1_LAUNCH(grad_finalize_kernel<true>, dim3(m->n_finalize_blocks, m->K), dim3(256), 0, stream, f, n_main);
+    else
+      KP1_LAUNCH(grad_finalize_kernel<false>, dim3(m->n_finalize_blocks), dim3(256), 0, stream, f, n_main);
   }
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
@@ -1750,6 +1925,7 @@ int kp1_mlp_profile_read(kp1_mlp* m, float* out_us, int32_t* out_launches) {
 int kp1_mlp_time_kernels(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n, int32_t iters, float* out_ms, double* out_flops,
                          void* stream_) {
   if (!m || !obs || !out_ms || !out_flops || iters <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_mlp_time_kernels");
+  if (m->K > 1) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_time_kernels is not available on population handles");
   if (n <= 0 || n > m->max_batch) return fail(KP1_ERR_INVALID, "n exceeds the workspace max_batch");
   int rc = mlp_check_device(m);
   if (rc != KP1_OK) return rc;
@@ -1941,7 +2117,13 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   const double* norm_partials = fused_norm ? m->partials + 2 * N_PARTIALS : m->partials + N_PARTIALS;
   const int n_norm_partials = fused_norm ? m->n_finalize_blocks : N_PARTIALS;
   ProfScope ps(m, KP1_MLP_PROFILE_ADAM, stream);
-  if (!fused_norm) hipLaunchKernelGGL(sumsq_partials_kernel, dim3(N_PARTIALS), dim3(256), 0, stream, grad, n, m->partials + N_PARTIALS);
+  const bool pop = m->K > 1;
+  if (!fused_norm) {
+    if (pop)
+      hipLaunchKernelGGL(sumsq_partials_kernel<true>, dim3(N_PARTIALS, m->K), dim3(256), 0, stream, grad, n, m->partials + N_PARTIALS, (unsigned)PARTIALS_STRIDE);
+    else
+      hipLaunchKernelGGL(sumsq_partials_kernel<false>, dim3(N_PARTIALS), dim3(256), 0, stream, grad, n, m->partials + N_PARTIALS, 0u);
+  }
   zero_grad = 0;  // gradients are overwritten by the next finalize; nothing to clear
   // step <= 0: use the device-resident counter that kp1_mlp_loss_grad's finalize kernel increments (graph-replay safe)
   const int host_step = step > 0 ? step : 1;
@@ -1953,8 +2135,13 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   m->last_params = params;
   if (frag_only) m->slab_stale = true;
   const int* step_arg = step > 0 ? (const int*)nullptr : (const int*)m->step_dev;
-  KP1_LAUNCH(adam_kernel, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK)), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
-             n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1);
+  if (pop)
+    KP1_LAUNCH(adam_kernel<true>, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK), m->K), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n,
+               norm_partials, n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step,
+               (const int*)m->step_dev + 1, (unsigned)PARTIALS_STRIDE);
+  else
+    KP1_LAUNCH(adam_kernel<false>, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK)), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
+               n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1, 0u);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }

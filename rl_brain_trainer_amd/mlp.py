@@ -15,11 +15,16 @@ def _p(t: torch.Tensor | None):
 
 
 class MlpKernels:
-    def __init__(self, hidden: int, device: torch.device, max_batch: int = 8192, obs_dim: int = OBS_DIM) -> None:
+    def __init__(self, hidden: int, device: torch.device, max_batch: int = 8192, obs_dim: int = OBS_DIM, replicas: int = 1) -> None:
+        """replicas > 1: a population handle (kp1_mlp_create_population) -- K independent nets trained through one launch sequence; every
+        per-net buffer gains a leading replica axis (include/kp1_ppo.h documents the layouts)."""
         self.L = native.load()
         L = self.L
         vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
         L.kp1_mlp_create_ex.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
+        L.kp1_mlp_create_population.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
+        L.kp1_mlp_replicas.argtypes = [vp]
+        L.kp1_mlp_replicas.restype = i32
         L.kp1_mlp_destroy.argtypes = [vp]
         L.kp1_mlp_num_params_ex.argtypes = [i32, i32]
         L.kp1_mlp_num_params_ex.restype = C.c_int64
@@ -38,7 +43,11 @@ class MlpKernels:
         self._h = vp()
         self.obs_dim = int(obs_dim)                      # 56, or 80 with the route observation keys
         self.obs_pad = 64 if self.obs_dim <= 64 else 128   # row pitch the kernels also accept (zero padded)
-        native.check(L.kp1_mlp_create_ex(device.index or 0, hidden, self.obs_dim, self.max_batch, C.byref(self._h)))
+        if replicas == 1:
+            native.check(L.kp1_mlp_create_ex(device.index or 0, hidden, self.obs_dim, self.max_batch, C.byref(self._h)))
+        else:
+            native.check(L.kp1_mlp_create_population(device.index or 0, hidden, self.obs_dim, self.max_batch, int(replicas), C.byref(self._h)))
+        self.replicas = int(L.kp1_mlp_replicas(self._h))
         self.num_params = int(L.kp1_mlp_num_params_ex(hidden, self.obs_dim))
 
     def close(self) -> None:
@@ -89,12 +98,14 @@ class MlpKernels:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def pack(self, flat_params: torch.Tensor) -> None:
-        assert flat_params.numel() == self.num_params and flat_params.dtype == torch.float32 and flat_params.is_contiguous()
+        assert flat_params.numel() == self.replicas * self.num_params and flat_params.dtype == torch.float32 and flat_params.is_contiguous()
         native.check(self.L.kp1_mlp_pack_weights(self._h, _p(flat_params), self._stream()))
 
     def forward(self, obs: torch.Tensor, *, noise=None, mean=None, value=None, action=None, clipped=None, log_prob=None) -> None:
-        """obs [n, obs_dim | obs_pad] contiguous f32; outputs written in place (None = skip)."""
-        n, stride = obs.shape[0], obs.shape[1]
+        """obs [n, obs_dim | obs_pad] contiguous f32; outputs written in place (None = skip).  Population handles: obs holds K * n rows,
+        replica-major, and so does every output."""
+        assert obs.shape[0] % self.replicas == 0
+        n, stride = obs.shape[0] // self.replicas, obs.shape[1]
         assert obs.is_contiguous() and obs.dtype == torch.float32
         native.check(self.L.kp1_mlp_forward(self._h, _p(obs), stride, n, _p(noise), _p(mean), _p(value), _p(action), _p(clipped), _p(log_prob), self._stream()))
 
@@ -117,7 +128,8 @@ class MlpKernels:
     def loss_grad(self, obs: torch.Tensor, idx: torch.Tensor | None, n: int, actions, old_logp, adv, ret, *, clip_range: float, ent_coef: float,
                   vf_coef: float, inv_count: float, grad_out: torch.Tensor, stats_out: torch.Tensor | None, adv_stats: torch.Tensor | None = None,
                   normalize: bool = True, grad_is_zero: bool = False) -> None:
-        assert obs.is_contiguous() and grad_out.numel() == self.num_params
+        assert obs.is_contiguous() and grad_out.numel() == self.replicas * self.num_params
+        assert self.replicas == 1 or (idx is not None and idx.numel() == self.replicas * n)
         inv_std = 0.0 if normalize else -1.0
         native.check(self.L.kp1_mlp_loss_grad(self._h, _p(obs), obs.shape[-1], _p(idx), n, _p(actions), _p(old_logp), _p(adv), _p(ret), 0.0, inv_std,
                                               _p(adv_stats), clip_range, ent_coef, vf_coef, inv_count, _p(grad_out), _p(stats_out), int(grad_is_zero), self._stream()))

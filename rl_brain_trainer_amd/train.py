@@ -36,7 +36,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--run-id", default="workspace_expand_mi355x_001")
     p.add_argument("--artifact-root")
     p.add_argument("--total-timesteps", type=int)
-    p.add_argument("--seed", type=int)
+    seeds = p.add_mutually_exclusive_group()
+    seeds.add_argument("--seed", type=int)
+    seeds.add_argument("--seeds", help="comma-separated seeds trained together as one population (2x64 / 2x128 nets, one GPU); seed s writes "
+                                       "the artefacts of a --seed s run under <artifact-root>/seed_<s>/, plus population_summary.json")
     p.add_argument("--resume-from")
     p.add_argument("--no-gate-callback", action="store_true")
     p.add_argument("--n-envs", type=int, default=4096, help="environments per GPU")
@@ -128,27 +131,19 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     seed = int(algo.get("seed", 0))
 
     root = Path(args.artifact_root) if args.artifact_root else kcfg.repo_root() / "artifacts/kinematic_phase1/workspace_expansion" / args.run_id
-    if rank == 0:
-        root.mkdir(parents=True, exist_ok=True)
-        (root / "latest_checkpoint").mkdir(exist_ok=True)
-        shutil.copyfile(args.config, root / "config_resolved.yaml")
-        write_json(root / "training_launch_summary.json", {"run_id": args.run_id, "config": cfg})
-
     n_envs = args.n_envs
-    env = ArmKinematicVecEnv(env_cfg, n_envs, device=local_rank, seed=seed, first_env_id=rank * n_envs)
-    cur = cfg["env"].get("curriculum", {})
-    curriculum = None
-    if env_cfg.c.curriculum_enabled and env_cfg.n_stages:
-        curriculum = PointCurriculum(success_rate_threshold=float(cur.get("success_rate_threshold", 0.80)),
-                                     window_episodes=int(cur.get("window_episodes", 20)),
-                                     min_episodes_per_stage=int(cur.get("min_episodes_per_stage", 30)),
-                                     max_stage_index=env_cfg.n_stages - 1,
-                                     initial_stage_index=int(ws.get("start_stage_index", 0)), device=local_rank)
     batch = args.batch_size or max(n_envs * args.n_steps * world // 64, 64)
-    model_kwargs = {k: v for k, v in algo.items() if k not in ("total_timesteps", "n_steps", "batch_size")}
+    model_kwargs = {k: v for k, v in algo.items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
     resume = args.resume_from or ws.get("init_approach_checkpoint", "")
     hidden = checkpoint.hidden_for_run(args.hidden, resume)     # a reference-trained zip is 2x64: the model takes the checkpoint's width
-    pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=hidden)
+    if args.seeds is not None:
+        return _main_population(args, cfg, env_cfg, algo, ws, root, batch, model_kwargs, resume, hidden, world, local_rank)
+    if rank == 0:
+        _start_artifacts(root, args, cfg)
+
+    env = ArmKinematicVecEnv(env_cfg, n_envs, device=local_rank, seed=seed, first_env_id=rank * n_envs)
+    curriculum = _make_curriculum(cfg, env_cfg, ws, local_rank)
+    pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=hidden, seed=seed)
     ppo = PPO(env, pcfg, curriculum=curriculum, dist=Dist(), backend="hip")     # 2x64 / 2x128 / 2x256 all run on the MFMA kernels
     if resume and Path(resume).exists():
         # PPO.load(resume, env=vec_env): weights, Adam state and the saved algorithm constants; the YAML's learning rate is re-applied
@@ -157,18 +152,10 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
             print(f"Resuming workspace expansion from {resume}")
 
     gate = None
-    finisher_policy = finisher_cfg = None
+    finisher_policy, finisher_cfg = _load_finisher(ws, local_rank)
     gate_cfg = dict(ws.get("gate", {}) or {})
-    if ws.get("finisher_checkpoint") and Path(str(ws["finisher_checkpoint"])).exists():
-        from .ppo import InferencePolicy
-
-        finisher_policy = InferencePolicy.load(str(ws["finisher_checkpoint"]), device=local_rank)
-        finisher_cfg = kcfg.to_env_config(kcfg.load_yaml_file(ws["finisher_config"]), handoff_base_dirs=(Path(str(ws["finisher_config"])).parent,))
     if rank == 0 and not args.no_gate_callback and finisher_policy is not None:
-        gate = WorkspaceEvalGate(artifact_root=root, approach_cfg=env_cfg, finisher_policy=finisher_policy, finisher_cfg=finisher_cfg,
-                                 eval_interval=int(ws.get("eval_interval", 200_000)), episodes=int(ws.get("gate_eval_episodes", 24)),
-                                 seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)), gate_config=gate_cfg,
-                                 device=local_rank)
+        gate = _make_gate(root, env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, local_rank)
 
     t0 = time.time()
     total = int(algo.get("total_timesteps", 100_000))
@@ -187,37 +174,122 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     wall = time.time() - t0
     summary: dict[str, Any] = {}
     if rank == 0:
-        latest = root / "latest_checkpoint" / "model_latest"
-        checkpoint.save(latest, ppo, env_cfg)
-        checkpoint.save(root / "model_latest", ppo, env_cfg)
-        final_eval = None
-        if finisher_policy is not None:   # train_workspace_expansion.py:243-259
-            from . import evaluate as ev
-
-            final_eval = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, finisher_policy=finisher_policy, approach_cfg=env_cfg,
-                                                         finisher_cfg=finisher_cfg, episodes=int(ws.get("final_eval_episodes", 80)),
-                                                         seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)),
-                                                         gate_config=gate_cfg, artifact_root=root / "final_eval", device=local_rank, obs_stride=ppo.obs_w)
-            final_eval = {k: v for k, v in final_eval.items() if k != "target_rows"}
-            for name in ("stage_metrics.json", "workspace_failure_report.json", "best_model_selection_summary.json"):
-                if (root / "final_eval" / name).exists():
-                    shutil.copyfile(root / "final_eval" / name, root / name)
-        summary = {
-            "policy_type": "approach", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "model_path": str(latest) + ".zip",
-            "resume_from": str(resume) if resume else None, "n_envs": n_envs * world, "device": f"{world}x MI355X",
-            "curriculum_summary": curriculum.summary() if curriculum is not None else None,
-            "final_workspace_eval": final_eval, "num_timesteps": ppo.num_timesteps, "wall_seconds": wall,
-            "env_steps_per_second": ppo.num_timesteps / wall, "last_update_stats": ppo.last_stats,
-        }
-        write_json(root / "training_summary.json", summary)
-        print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "model_latest": str(latest) + ".zip",
-                          "env_steps_per_second": summary["env_steps_per_second"]}, indent=2))
+        summary = _final_artifacts(root, ppo, env_cfg, args=args, resume=resume, n_envs=n_envs * world, world=world, curriculum=curriculum,
+                                   finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, ws=ws, gate_cfg=gate_cfg, device=local_rank, wall=wall)
     if world > 1:
         import torch.distributed as dist
 
         dist.barrier()
         ppo.dist.close()
         dist.destroy_process_group()
+    return summary
+
+
+def _start_artifacts(root: Path, args, cfg: dict[str, Any]) -> None:
+    root.mkdir(parents=True, exist_ok=True)
+    (root / "latest_checkpoint").mkdir(exist_ok=True)
+    shutil.copyfile(args.config, root / "config_resolved.yaml")
+    write_json(root / "training_launch_summary.json", {"run_id": args.run_id, "config": cfg})
+
+
+def _make_curriculum(cfg: dict[str, Any], env_cfg: kcfg.EnvConfig, ws: dict[str, Any], device: int) -> PointCurriculum | None:
+    cur = cfg["env"].get("curriculum", {})
+    if not (env_cfg.c.curriculum_enabled and env_cfg.n_stages):
+        return None
+    return PointCurriculum(success_rate_threshold=float(cur.get("success_rate_threshold", 0.80)), window_episodes=int(cur.get("window_episodes", 20)),
+                           min_episodes_per_stage=int(cur.get("min_episodes_per_stage", 30)), max_stage_index=env_cfg.n_stages - 1,
+                           initial_stage_index=int(ws.get("start_stage_index", 0)), device=device)
+
+
+def _load_finisher(ws: dict[str, Any], device: int):
+    if not (ws.get("finisher_checkpoint") and Path(str(ws["finisher_checkpoint"])).exists()):
+        return None, None
+    from .ppo import InferencePolicy
+
+    finisher_policy = InferencePolicy.load(str(ws["finisher_checkpoint"]), device=device)
+    finisher_cfg = kcfg.to_env_config(kcfg.load_yaml_file(ws["finisher_config"]), handoff_base_dirs=(Path(str(ws["finisher_config"])).parent,))
+    return finisher_policy, finisher_cfg
+
+
+def _make_gate(root: Path, env_cfg: kcfg.EnvConfig, finisher_policy, finisher_cfg, ws: dict[str, Any], gate_cfg: dict[str, Any], device: int) -> WorkspaceEvalGate:
+    return WorkspaceEvalGate(artifact_root=root, approach_cfg=env_cfg, finisher_policy=finisher_policy, finisher_cfg=finisher_cfg,
+                             eval_interval=int(ws.get("eval_interval", 200_000)), episodes=int(ws.get("gate_eval_episodes", 24)),
+                             seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)), gate_config=gate_cfg, device=device)
+
+
+def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, n_envs: int, world: int, curriculum, finisher_policy, finisher_cfg,
+                     ws: dict[str, Any], gate_cfg: dict[str, Any], device: int, wall: float, extra: dict[str, Any] | None = None) -> dict[str, Any]:
+    """what a run leaves at its end: model_latest (twice), the final Approach -> Finisher evaluation when a Finisher is configured, and
+    training_summary.json (`ppo` is a PPO or a population replica)"""
+    latest = root / "latest_checkpoint" / "model_latest"
+    checkpoint.save(latest, ppo, env_cfg)
+    checkpoint.save(root / "model_latest", ppo, env_cfg)
+    final_eval = None
+    if finisher_policy is not None:   # train_workspace_expansion.py:243-259
+        from . import evaluate as ev
+
+        final_eval = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, finisher_policy=finisher_policy, approach_cfg=env_cfg,
+                                                     finisher_cfg=finisher_cfg, episodes=int(ws.get("final_eval_episodes", 80)),
+                                                     seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)),
+                                                     gate_config=gate_cfg, artifact_root=root / "final_eval", device=device, obs_stride=ppo.obs_w)
+        final_eval = {k: v for k, v in final_eval.items() if k != "target_rows"}
+        for name in ("stage_metrics.json", "workspace_failure_report.json", "best_model_selection_summary.json"):
+            if (root / "final_eval" / name).exists():
+                shutil.copyfile(root / "final_eval" / name, root / name)
+    summary = {
+        "policy_type": "approach", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "model_path": str(latest) + ".zip",
+        "resume_from": str(resume) if resume else None, "n_envs": n_envs, "device": f"{world}x MI355X",
+        "curriculum_summary": curriculum.summary() if curriculum is not None else None,
+        "final_workspace_eval": final_eval, "num_timesteps": ppo.num_timesteps, "wall_seconds": wall,
+        "env_steps_per_second": ppo.num_timesteps / wall, "last_update_stats": ppo.last_stats, **(extra or {}),
+    }
+    write_json(root / "training_summary.json", summary)
+    print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "model_latest": str(latest) + ".zip",
+                      "env_steps_per_second": summary["env_steps_per_second"]}, indent=2))
+    return summary
+
+
+def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model_kwargs, resume, hidden: int, world: int, device: int) -> dict[str, Any]:
+    """--seeds: the seeds train together as one PopulationPPO; seed s writes what a --seed s run writes, under root/seed_<s>/"""
+    from .population import PopulationPPO, learn_population, parse_seeds, population_summary
+
+    seeds = parse_seeds(args.seeds)
+    if world > 1:
+        raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
+    if resume and Path(resume).exists():
+        raise ValueError("--seeds starts every seed from its own initialisation; it does not resume from a checkpoint (--resume-from / "
+                         "workspace_expansion.init_approach_checkpoint)")
+    roots = {s: root / f"seed_{s}" for s in seeds}
+    pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=hidden)
+    pop = PopulationPPO(seeds, pcfg, lambda s: ArmKinematicVecEnv(env_cfg, args.n_envs, device=device, seed=s),
+                        curriculum_factory=lambda s: _make_curriculum(cfg, env_cfg, ws, device))
+    for s in seeds:
+        _start_artifacts(roots[s], args, cfg)
+    finisher_policy, finisher_cfg = _load_finisher(ws, device)
+    gate_cfg = dict(ws.get("gate", {}) or {})
+    gates = {}
+    if not args.no_gate_callback and finisher_policy is not None:
+        gates = {s: _make_gate(roots[s], env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, device) for s in seeds}
+
+    def on_iteration(p) -> None:
+        for k, s in enumerate(seeds):
+            if s in gates:
+                gates[s].on_iteration(p.replica(k), env_cfg)
+
+    wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), on_iteration=on_iteration, log_every=args.log_every, tag="ppo-population")
+    rows = []
+    for k, s in enumerate(seeds):
+        rep = pop.replica(k)
+        summ = _final_artifacts(roots[s], rep, env_cfg, args=args, resume=None, n_envs=args.n_envs, world=1, curriculum=pop.curricula[k],
+                                finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, ws=ws, gate_cfg=gate_cfg, device=device, wall=wall,
+                                extra={"seed": s})
+        best = gates[s].best_score if s in gates and gates[s].best_score != float("-inf") else None
+        rows.append({"seed": s, "artifact_root": str(roots[s]), "final_curriculum_stage": pop.curricula[k].read().stage_index if pop.curricula[k] else None,
+                     "last_update_stats": summ["last_update_stats"], "best_score": best, "model_latest": summ["model_path"],
+                     "model_best_by_gate": str(roots[s] / "best_checkpoint" / "model_best_by_gate.zip") if best is not None else None})
+    summary = population_summary(pop, rows, wall_seconds=wall, selection="workspace eval gate score (best_model_selection.score)")
+    write_json(root / "population_summary.json", summary)
+    pop.close()
     return summary
 
 

@@ -31,7 +31,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--run-id", default="dock_policy")
     p.add_argument("--artifact-root")
     p.add_argument("--total-timesteps", type=int)
-    p.add_argument("--seed", type=int)
+    seeds = p.add_mutually_exclusive_group()
+    seeds.add_argument("--seed", type=int)
+    seeds.add_argument("--seeds", help="comma-separated seeds trained together as one population (2x64 / 2x128 nets, one GPU); seed s writes "
+                                       "the artefacts of a --seed s run under <artifact-root>/seed_<s>/, plus population_summary.json")
     p.add_argument("--resume-from")
     p.add_argument("--n-envs", type=int, default=4096, help="environments per GPU")
     p.add_argument("--n-steps", type=int, default=64)
@@ -79,6 +82,8 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
         algo["seed"] = args.seed
     seed = int(algo.get("seed", 0))
     root = Path(args.artifact_root) if args.artifact_root else kcfg.repo_root() / "artifacts/kinematic_phase1/phase1b_dock" / args.run_id
+    if args.seeds is not None:
+        return _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root, world, local_rank)
     if rank == 0:
         root.mkdir(parents=True, exist_ok=True)
 
@@ -132,6 +137,54 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
         dist.barrier()
         ppo.dist.close()
         dist.destroy_process_group()
+    return summary
+
+
+def _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root: Path, world: int, device: int) -> dict[str, Any]:
+    """--seeds: the seeds train together as one PopulationPPO; seed s writes what a --seed s run writes, under root/seed_<s>/.  The selection
+    score of population_summary.json is each seed's dock evaluation success rate."""
+    from .population import PopulationPPO, learn_population, parse_seeds, population_summary
+
+    seeds = parse_seeds(args.seeds)
+    if world > 1:
+        raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
+    if args.resume_from and Path(args.resume_from).exists():
+        raise ValueError("--seeds starts every seed from its own initialisation; it does not resume from a checkpoint")
+    n_envs = args.n_envs
+    batch = args.batch_size or max(n_envs * args.n_steps // 64, 64)
+    model_kwargs = {k: v for k, v in algo.items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
+    pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=checkpoint.hidden_for_run(args.hidden, None))
+    cur_cfg = runtime.get("dock_reverse_curriculum", {}) or {}
+
+    def curriculum_factory(seed: int):
+        if not bool(cur_cfg.get("enabled", False)):
+            return None
+        return DockReverseCurriculum(stages=list(cur_cfg.get("stages", [])), window_episodes=int(cur_cfg.get("window_episodes", 100)),
+                                     handoff_base_dirs=base_dirs)
+
+    pop = PopulationPPO(seeds, pcfg, lambda s: ArmKinematicVecEnv(env_cfg, n_envs, device=device, seed=s), curriculum_factory=curriculum_factory)
+    roots = {s: root / f"seed_{s}" for s in seeds}
+    for r in roots.values():
+        r.mkdir(parents=True, exist_ok=True)
+    wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), log_every=args.log_every, tag="ppo-dock-population")
+    rows = []
+    for k, s in enumerate(seeds):
+        rep, r, curriculum = pop.replica(k), roots[s], pop.curricula[k]
+        latest = r / "model_latest"
+        checkpoint.save(latest, rep, env_cfg)
+        eval_summary = evaluate_dock(rep, env_cfg, episodes=args.eval_episodes, seed=s + 10_000, device=device)
+        (r / "dock_eval").mkdir(exist_ok=True)
+        (r / "dock_eval" / "dock_eval_summary.json").write_text(json.dumps(eval_summary, indent=2))
+        summary = {"policy_type": "dock", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "config": cfg, "model_path": str(latest) + ".zip",
+                   "resume_from": None, "n_envs": n_envs, "device": "1x MI355X",
+                   "dock_eval_summary": eval_summary, "dock_reverse_curriculum": curriculum.summary() if curriculum is not None else None,
+                   "num_timesteps": rep.num_timesteps, "wall_seconds": wall, "env_steps_per_second": rep.num_timesteps / wall, "seed": s}
+        (r / "training_summary.json").write_text(json.dumps(summary, indent=2))
+        rows.append({"seed": s, "artifact_root": str(r), "final_curriculum_stage": curriculum.current_stage_index if curriculum is not None else None,
+                     "last_update_stats": rep.last_stats, "best_score": eval_summary["success_rate"], "model_latest": str(latest) + ".zip"})
+    summary = population_summary(pop, rows, wall_seconds=wall, selection="dock evaluation success_rate")
+    (root / "population_summary.json").write_text(json.dumps(summary, indent=2))
+    pop.close()
     return summary
 
 

@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Population PPO at the reference's training scale (developer tool, not bench.py).
+
+The Approach iteration of workspace_expansion_bigtrain.yaml as the reference trains it -- 16 envs x 1024 steps, minibatch 256, the 2x64 net,
+curriculum on -- for a population of K seeds (rl_brain_trainer_amd/population.py), K in {1, 2, 4, 8}.  Per K: rollout ms and update ms per
+iteration (device-synchronised, captured graphs), aggregate env-steps/s over all replicas, and the in-situ per-launch duration of the
+optimiser-step kernels KP1_MLP_OPT_PROFILE times on this path (grad_finalize, adam) from one eager update.
+
+    python tools/population_bench.py [--ks 1,2,4,8] [--iters 3] [--out profiles/r04_population_refscale.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+import torch  # noqa: E402
+
+from rl_brain_trainer_amd import config as kcfg  # noqa: E402
+from rl_brain_trainer_amd.curriculum import PointCurriculum  # noqa: E402
+from rl_brain_trainer_amd.population import PopulationPPO  # noqa: E402
+from rl_brain_trainer_amd.ppo import PPOConfig  # noqa: E402
+from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv  # noqa: E402
+
+
+def build(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool) -> PopulationPPO:
+    cfg = kcfg.load_workspace_expansion_config(kcfg.builtin_config_dir() / "workspace_expansion_bigtrain.yaml")
+    env_cfg = kcfg.to_env_config(cfg)
+    cur = cfg["env"].get("curriculum", {})
+    algo = {k: v for k, v in kcfg.to_algorithm_kwargs(cfg, "ppo").items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
+    pcfg = PPOConfig.from_algo_kwargs(algo, n_steps=n_steps, batch_size=batch, hidden=hidden)
+
+    def cur_factory(seed: int):
+        if not (env_cfg.c.curriculum_enabled and env_cfg.n_stages):
+            return None
+        return PointCurriculum(success_rate_threshold=float(cur.get("success_rate_threshold", 0.80)), window_episodes=int(cur.get("window_episodes", 20)),
+                               min_episodes_per_stage=int(cur.get("min_episodes_per_stage", 30)), max_stage_index=env_cfg.n_stages - 1)
+
+    return PopulationPPO(list(range(7, 7 + K)), pcfg, lambda s: ArmKinematicVecEnv(env_cfg, n_envs, seed=s), curriculum_factory=cur_factory,
+                         use_graphs=use_graphs)
+
+
+def measure(K: int, args) -> dict:
+    pop = build(K, args.n_envs, args.n_steps, args.batch, args.hidden, True)
+    pop.collect_rollouts()
+    pop.train()      # warm-up: captures both graphs
+    torch.cuda.synchronize()
+    ro, up = [], []
+    for _ in range(args.iters):
+        t0 = time.perf_counter()
+        pop.collect_rollouts()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        pop.train()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        ro.append(t1 - t0)
+        up.append(t2 - t1)
+    rollout_ms, update_ms = 1e3 * sum(ro) / len(ro), 1e3 * sum(up) / len(up)
+    steps = K * args.n_envs * args.n_steps
+    pop.close()
+    # per-kernel durations from one eager update with event pairs on the launches
+    eager = build(K, args.n_envs, args.n_steps, args.batch, args.hidden, False)
+    eager.collect_rollouts()
+    torch.cuda.synchronize()
+    eager._mlp.set_profile(True)
+    eager.train()
+    prof = {k: v for k, v in eager._mlp.profile_read().items() if v["launches"] > 0}
+    eager._mlp.set_profile(False)
+    eager.close()
+    return {"K": K, "rollout_ms": rollout_ms, "update_ms": update_ms, "iteration_ms": rollout_ms + update_ms,
+            "aggregate_env_steps_per_s": steps / ((rollout_ms + update_ms) * 1e-3), "env_steps_per_iteration": steps, "kernel_us_in_situ": prof}
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--ks", default="1,2,4,8")
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--n-envs", type=int, default=16)
+    ap.add_argument("--n-steps", type=int, default=1024)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--hidden", type=int, default=64)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    rows = []
+    for K in (int(k) for k in args.ks.split(",")):
+        rows.append(measure(K, args))
+        print(json.dumps(rows[-1]), flush=True)
+    base = rows[0]["aggregate_env_steps_per_s"]
+    for r in rows:
+        r["aggregate_vs_first"] = r["aggregate_env_steps_per_s"] / base
+    result = {"workload": f"workspace_expansion_bigtrain.yaml Approach iteration, {args.n_envs} envs x {args.n_steps} steps per replica, "
+                          f"minibatch {args.batch}, 2x{args.hidden}, curriculum on; seeds 7..7+K-1", "device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
+    print(json.dumps({"aggregate_env_steps_per_s": {r["K"]: round(r["aggregate_env_steps_per_s"]) for r in rows}}))
+
+
+if __name__ == "__main__":
+    main()
