@@ -406,86 +406,37 @@ class Dist:
         return bool(verdict.item() > 0.5)
 
 
+def _bind_policy(policy: ActorCritic, flat: torch.Tensor) -> None:
+    """make `policy` a view on row `flat` of a population's [K, P] parameter buffer (values copied in first)"""
+    flat.copy_(policy.flat)
+    policy.flat = flat
+    off = 0
+    for name, shape in policy.spec:
+        n = math.prod(shape)
+        policy.views[name] = flat[off:off + n].view(shape)
+        off += n
+
+
 class PPO:
+    """One PPO run.  PopulationPPO (population.py) is the same engine with K replicas: everything per replica below is a list (``envs``,
+    ``curricula``, ``policies``, ``gens``) or a replica axis (rollout columns [k N, (k + 1) N), ``perm[k]``, ``stats_dev[k]``); here K = 1."""
+
     def __init__(self, env: ArmKinematicVecEnv, cfg: PPOConfig, *, curriculum: PointCurriculum | None = None,
                  dist: Dist | None = None, backend: str = "hip", use_graphs: bool = True) -> None:
         if backend != "hip":
             raise ValueError("backend must be 'hip': the HIP kernels are the only training path")
-        self.env = env
-        self.cfg = cfg
-        self.device = env.device
-        self.dist = dist or Dist()
-        self.backend = backend
-        self.L = native.load()
-        self.n_envs = env.n_envs
-        self.obs_dim = int(getattr(env, "obs_dim", OBS_DIM))   # 80 for the route envs with include_route_keys
-        self.policy = ActorCritic(cfg.hidden, self.device, seed=cfg.seed, obs_dim=self.obs_dim)
-        self.dist.broadcast(self.policy.flat)
-        self.adam_m = torch.zeros_like(self.policy.flat)
-        self.adam_v = torch.zeros_like(self.policy.flat)
-        self.adam_t = 0
-        self.n_train_calls = 0         # train() calls so far: SB3's _n_updates = n_train_calls * n_epochs
-        self.actor_extra_steps = 0    # optimiser steps only the actor tensors took (teacher-anchor side updates)
-        self._epoch_warm = False       # one eager epoch has run (kernel attributes set, code objects loaded) before the epoch graph is captured
-        self.curriculum = curriculum
-        if curriculum is not None:
-            curriculum.attach(env)
-        T, N = cfg.n_steps, self.n_envs
-        dev = self.device
-        # observation rows are written with pitch 64 / 128 (zero padded) so the MFMA GEMMs read them directly
-        self.obs_w = 64 if self.obs_dim <= 64 else 128
-        env.set_obs_stride(self.obs_w)
-        self.obs_buf = torch.zeros((T + 1, N, self.obs_w), dtype=torch.float32, device=dev)
-        self.term_obs_buf = torch.zeros((T, N, self.obs_w), dtype=torch.float32, device=dev)
-        self.act_buf = torch.zeros((T, N, ACT_DIM), dtype=torch.float32, device=dev)
-        self.clip_act = torch.zeros((N, ACT_DIM), dtype=torch.float32, device=dev)
-        self.logp_buf = torch.zeros((T, N), dtype=torch.float32, device=dev)
-        self.val_buf = torch.zeros((T, N), dtype=torch.float32, device=dev)
-        self.rew_buf = torch.zeros((T, N), dtype=torch.float32, device=dev)
-        self.done_buf = torch.zeros((T, N), dtype=torch.uint8, device=dev)
-        self.adv_buf = torch.zeros((T, N), dtype=torch.float32, device=dev)
-        self.ret_buf = torch.zeros((T, N), dtype=torch.float32, device=dev)
-        self.gen = torch.Generator(device=dev).manual_seed(int(cfg.seed) + 7919 * self.dist.rank)
-        self._perm_rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(cfg.seed), self.dist.rank, 0x6B7031])))   # shuffle keys
-        self.num_timesteps = 0
-        self._needs_reset = True
-        self._last_stats_dev: tuple[torch.Tensor, int] | None = None    # (loss sums of the last train() on the device, number of updates)
-        self._last_stats_host: dict[str, float] = {}
         if env.dtype != torch.float32:
             raise ValueError("PPO drives the production f32 env")
-        from . import mlp as _mlp
-
-        local_bs = max(cfg.batch_size // self.dist.world_size, 1)
-        self._mlp = _mlp.MlpKernels(cfg.hidden, self.device, max_batch=max(N, local_bs, 8192), obs_dim=self.obs_dim)
-        self._mlp.pack(self.policy.flat)
-        if os.environ.get("KP1_BF16X3_WGRAD", "0") == "1" and cfg.hidden == 256:
-            # round-3 EXPERIMENT (off by default, never used by bench.py's value): weight-gradient GEMMs on bf16 x 3 operands
-            self._mlp.set_bf16x3_wgrad(True)
-        self.grad = torch.zeros_like(self.policy.flat)
-        self.stats_dev = torch.zeros(4, dtype=torch.float32, device=dev)
-        self.noise = torch.zeros((N, ACT_DIM), dtype=torch.float32, device=dev)
-        # hipGraph replay of the rollout (T x 3 launches) and of one update epoch.  Data parallel: graph segments with eager collectives
-        # between them, or (opt-in) the RCCL collectives captured inside the graphs: Dist.graph_mode.
-        self.use_graphs = bool(use_graphs)
-        self.dist.use_stream_collectives(self.device)     # nccl: the training collectives go on the launch stream (rccl.py); else a no-op
-        self.graph_mode = self.dist.graph_mode(self.device) if self.use_graphs else "none"
-        self._first_replay_checked = {"rollout": not (self.dist.enabled and self.graph_mode == "captured"),
-                                      "epoch": not (self.dist.enabled and self.graph_mode == "captured")}
-        self._rollout_graph = None
-        self._epoch_graph = None
-        self._epoch_policy = os.environ.get("KP1_DP_EPOCH", "auto")     # segmented mode only: "auto" (measured), "graph", "eager"
-        self._epoch_auto = None
-        self.epoch_form = "one graph" if self.graph_mode == "captured" else ("eager launches" if self.graph_mode == "none" or self._epoch_policy == "eager" else "graph segments")
-        self._rollout_graph_key = None     # (env.launch_args_version, curriculum attached?) the rollout graph was captured with
-        self._epoch_graph_key = None       # hyper-parameters baked into the epoch graph's kernel arguments
-        self._kernels_warm = False         # the rollout kernels have run once (code objects loaded, attributes set)
+        self.env = env
+        self.curriculum = curriculum
+        self._setup(cfg, [cfg.seed], [env], [curriculum], dist or Dist(), use_graphs, min_batch=8192, stacked=False)
+        self.policy = self.policies[0]
+        T, N, dev = cfg.n_steps, self.n_envs, self.device
         # data parallel: done bytes are exchanged once per `done_chunk` env steps (one all-gather of chunk x N bytes instead of one
         # latency-bound collective per 45 us env step); the device tracker replays the chunk in the reference's order
         self.done_chunk = 1
         if self.dist.enabled:
-            import os as _os
-
-            self.done_chunk = math.gcd(T, max(int(_os.environ.get("KP1_DONE_EXCHANGE_STEPS", "16")), 1))
+            self.done_chunk = math.gcd(T, max(int(os.environ.get("KP1_DONE_EXCHANGE_STEPS", "16")), 1))
             self._done_gather = torch.zeros((self.dist.world_size, self.done_chunk, N), dtype=torch.uint8, device=dev)
             # a route tracker also reads per-env flags that every step overwrites: each step's episode records are staged in slot t % chunk
             # and the staging buffer is exchanged instead of the done bytes
@@ -497,14 +448,95 @@ class PPO:
         self._fused_env_step = bool(type(env) is ArmKinematicVecEnv and env.dtype == torch.float32 and cfg.hidden == 256
                                     and self.obs_dim <= 64 and not getattr(env, "_reward_components_on", False)
                                     and os.environ.get("KP1_FUSED_ROLLOUT", "1") != "0")
+
+    def _setup(self, cfg: PPOConfig, seeds: list[int], envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool, *,
+               min_batch: int, stacked: bool) -> None:
+        """What a run of K = len(seeds) replicas holds.  Replica k owns what PPO(seed=s_k) owns: the env handle envs[k] and its tracker
+        curricula[k], the parameter init and the generators of rollout noise and shuffles.  Rollout buffers are [T(+1), K N, ...] with replica
+        k's envs in columns [k N, (k + 1) N); one MLP handle with K replicas trains all of them.  ``min_batch``: lower bound of that handle's
+        max_batch.  ``stacked``: parameters, Adam moments and gradient are [K, P] (a population, any K) instead of one run's [P]."""
+        self.cfg = cfg
+        self.dist = dist
+        self.backend = "hip"
+        self.L = native.load()
+        self.K = K = len(seeds)
+        self.envs, self.curricula = envs, curricula
+        self.device = dev = envs[0].device
+        self.n_envs = N = envs[0].n_envs                        # per replica
+        self.obs_dim = int(getattr(envs[0], "obs_dim", OBS_DIM))   # 80 for the route envs with include_route_keys
+        # observation rows are written with pitch 64 / 128 (zero padded) so the MFMA GEMMs read them directly
+        self.obs_w = 64 if self.obs_dim <= 64 else 128
+        for env, cur in zip(envs, curricula):
+            if cur is not None:
+                cur.attach(env)
+            env.set_obs_stride(self.obs_w)
+        # row k of the [K, P] buffers = what PPO(seed=s_k) holds
+        self.policies = [ActorCritic(cfg.hidden, dev, seed=s, obs_dim=self.obs_dim) for s in seeds]
+        self.flat = self.policies[0].flat
+        if stacked:
+            self.flat = torch.zeros((K, self.policies[0].numel), dtype=torch.float32, device=dev)
+            for k, pol in enumerate(self.policies):
+                _bind_policy(pol, self.flat[k])
+        self.dist.broadcast(self.flat)
+        self.adam_m = torch.zeros_like(self.flat)
+        self.adam_v = torch.zeros_like(self.flat)
+        self.grad = torch.zeros_like(self.flat)
+        self.stats_dev = torch.zeros((K, 4), dtype=torch.float32, device=dev)
+        self.adam_t = 0                # one Adam step count for all replicas
+        self.n_train_calls = 0         # train() calls so far: SB3's _n_updates = n_train_calls * n_epochs
+        self.actor_extra_steps = 0    # optimiser steps only the actor tensors took (teacher-anchor side updates)
+        self.num_timesteps = 0         # per replica
+        T, KN = cfg.n_steps, K * N
+        self.obs_buf = torch.zeros((T + 1, KN, self.obs_w), dtype=torch.float32, device=dev)
+        self.term_obs_buf = torch.zeros((T, KN, self.obs_w), dtype=torch.float32, device=dev)
+        self.act_buf = torch.zeros((T, KN, ACT_DIM), dtype=torch.float32, device=dev)
+        self.clip_act = torch.zeros((KN, ACT_DIM), dtype=torch.float32, device=dev)
+        self.logp_buf = torch.zeros((T, KN), dtype=torch.float32, device=dev)
+        self.val_buf = torch.zeros((T, KN), dtype=torch.float32, device=dev)
+        self.rew_buf = torch.zeros((T, KN), dtype=torch.float32, device=dev)
+        self.done_buf = torch.zeros((T, KN), dtype=torch.uint8, device=dev)
+        self.adv_buf = torch.zeros((T, KN), dtype=torch.float32, device=dev)
+        self.ret_buf = torch.zeros((T, KN), dtype=torch.float32, device=dev)
+        # exploration noise of a whole rollout is drawn in ONE call, graphs or not: the eager and the replayed rollout then consume the
+        # generator identically and stay bit-identical (tests/test_distributed_gpu.py compares them)
+        self.noise_all = torch.zeros((T, KN, ACT_DIM), dtype=torch.float32, device=dev)
+        self.perm = torch.zeros((K, T * N), dtype=torch.int64, device=dev)     # replica k's shuffle of the epoch (the epoch graph reads it)
+        self.gens = [torch.Generator(device=dev).manual_seed(int(s) + 7919 * self.dist.rank) for s in seeds]
+        self._perm_rngs = [np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(s), self.dist.rank, 0x6B7031]))) for s in seeds]   # shuffle keys
+        self._needs_reset = True
+        self._last_stats_dev: tuple[torch.Tensor, int] | None = None    # (loss sums of the last train() on the device, number of updates)
+        self._last_stats_host: list[dict[str, float]] = [{} for _ in range(K)]
+        from . import mlp as _mlp
+
+        local_bs = max(cfg.batch_size // self.dist.world_size, 1)
+        self._mlp = _mlp.MlpKernels(cfg.hidden, dev, max_batch=max(N, local_bs, min_batch), obs_dim=self.obs_dim, replicas=K)
+        self._mlp.pack(self.flat)
+        if os.environ.get("KP1_BF16X3_WGRAD", "0") == "1" and cfg.hidden == 256:
+            # round-3 EXPERIMENT (off by default, never used by bench.py's value): weight-gradient GEMMs on bf16 x 3 operands
+            self._mlp.set_bf16x3_wgrad(True)
+        # hipGraph replay of the rollout (T x 3 launches) and of one update epoch.  Data parallel: graph segments with eager collectives
+        # between them, or (opt-in) the RCCL collectives captured inside the graphs: Dist.graph_mode.
+        self.use_graphs = bool(use_graphs)
+        self.dist.use_stream_collectives(dev)     # nccl: the training collectives go on the launch stream (rccl.py); else a no-op
+        self.graph_mode = self.dist.graph_mode(dev) if self.use_graphs else "none"
+        self._first_replay_checked = {"rollout": not (self.dist.enabled and self.graph_mode == "captured"),
+                                      "epoch": not (self.dist.enabled and self.graph_mode == "captured")}
+        self._rollout_graph = None
+        self._epoch_graph = None
+        self._epoch_policy = os.environ.get("KP1_DP_EPOCH", "auto")     # segmented mode only: "auto" (measured), "graph", "eager"
+        self._epoch_auto = None
+        self.epoch_form = "one graph" if self.graph_mode == "captured" else ("eager launches" if self.graph_mode == "none" or self._epoch_policy == "eager" else "graph segments")
+        self._rollout_graph_key = None     # (launch_args_version of every env, which trackers are attached, gamma, lambda) the rollout graph froze
+        self._epoch_graph_key = None       # hyper-parameters baked into the epoch graph's kernel arguments
+        self._epoch_warm = False           # one eager epoch has run (kernel attributes set, code objects loaded) before the epoch graph is captured
+        self._kernels_warm = False         # the rollout kernels have run once (code objects loaded, attributes set)
         # optional host hook after every env step (done bits of that step, device tensor): what SB3 callbacks' _on_step sees.
         # Setting it makes the rollout eager (a host hook cannot live inside a hipGraph replay).
         self.step_callback = None
-        # exploration noise of a whole rollout is drawn in ONE call, graphs or not: the eager and the replayed rollout then consume the
-        # generator identically and stay bit-identical (tests/test_distributed_gpu.py compares them)
-        self.noise_all = torch.zeros((T, N, ACT_DIM), dtype=torch.float32, device=dev)
-        if self.use_graphs:
-            self.perm = torch.zeros(T * N, dtype=torch.int64, device=dev)
+
+    def _sl(self, k: int) -> slice:
+        """replica k's columns of the rollout buffers"""
+        return slice(k * self.n_envs, (k + 1) * self.n_envs)
 
     # Minibatch shuffles.  At the benchmarked size (524288 samples) a sort-based torch.randperm is 0.16 ms of full-chip kernels, eight times per
     # iteration (2.5 %); drawing them on a side stream under the rollout only moved that time (the sort kernels fill the chip and the
@@ -512,18 +544,21 @@ class PPO:
     # bijection evaluated per element (kp1_random_permutation: one elementwise launch); below it torch.randperm stays -- it is cheap there.
     PERM_CIPHER_MIN = 1 << 17
 
-    def _draw_perm(self, total: int, out: torch.Tensor | None = None) -> torch.Tensor:
-        """indices of one epoch's minibatches: a random permutation of [0, total) on the device (SB3: np.random.permutation in RolloutBuffer.get)"""
+    def _draw_perm(self, k: int) -> None:
+        """replica k's indices of one epoch's minibatches into self.perm[k]: a random permutation of [0, T N) on the device (SB3:
+        np.random.permutation in RolloutBuffer.get)"""
+        out = self.perm[k]
+        total = out.numel()
         if total < self.PERM_CIPHER_MIN:
-            if out is None:
-                return torch.randperm(total, device=self.device, generator=self.gen)
-            return torch.randperm(total, device=self.device, generator=self.gen, out=out)
-        if out is None:
-            out = torch.empty(total, dtype=torch.int64, device=self.device)
-        keys = self._perm_rng.integers(0, 1 << 32, size=8, dtype=np.uint64).astype(np.uint32)
+            torch.randperm(total, device=self.device, generator=self.gens[k], out=out)
+            return
+        keys = self._perm_rngs[k].integers(0, 1 << 32, size=8, dtype=np.uint64).astype(np.uint32)
         native.check(self.L.kp1_random_permutation(self.device.index or 0, total, keys.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
                                                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-        return out
+
+    def _draw_noise(self) -> None:
+        """the exploration noise of the whole rollout"""
+        self.noise_all.normal_(generator=self.gens[0])
 
     def invalidate_graphs(self) -> None:
         """Drop the captured hipGraphs: a capture freezes host-side scalars into kernel arguments (env stage / mode / config pointers; learning
@@ -624,7 +659,7 @@ class PPO:
         with torch.no_grad():
             mean, _ = self._forward(obs)
             if not deterministic:
-                mean = mean + torch.exp(self.policy.views["log_std"]) * torch.randn(mean.shape, device=mean.device, generator=self.gen)
+                mean = mean + torch.exp(self.policy.views["log_std"]) * torch.randn(mean.shape, device=mean.device, generator=self.gens[0])
             return mean.clamp(-1.0, 1.0)
 
     def predict_unclipped(self, obs: torch.Tensor) -> torch.Tensor:
@@ -663,18 +698,20 @@ class PPO:
     # ------------------------------------------------------------------ rollout
     @torch.no_grad()
     def collect_rollouts(self) -> None:
-        cfg, env = self.cfg, self.env
+        cfg = self.cfg
         T, N = cfg.n_steps, self.n_envs
         if self._needs_reset:
-            self.obs_buf[0].copy_(env.reset())
+            for k, env in enumerate(self.envs):
+                self.obs_buf[0, self._sl(k)].copy_(env.reset())
             self._needs_reset = False
         else:
             self.obs_buf[0].copy_(self.obs_buf[T])
         world = self.dist.world_size
         graph_rollout = self.use_graphs and self.step_callback is None
-        self.noise_all.normal_(generator=self.gen)
+        self._draw_noise()
         if graph_rollout:
-            key = (getattr(env, "launch_args_version", 0), self.curriculum is not None, cfg.gamma, cfg.gae_lambda)   # what a capture freezes
+            key = (tuple(getattr(env, "launch_args_version", 0) for env in self.envs), tuple(cur is not None for cur in self.curricula),
+                   cfg.gamma, cfg.gae_lambda)   # what a capture freezes
             if self._rollout_graph is None or self._rollout_graph_key != key:
                 self._capture_rollout()
                 self._rollout_graph_key = key
@@ -694,15 +731,16 @@ class PPO:
         and no host synchronisation, so the captured rollout graph carries it as its tail (a dozen small launches whose host latency
         was 0.5 ms per iteration)."""
         cfg = self.cfg
-        T, N = cfg.n_steps, self.n_envs
+        T, KN = cfg.n_steps, self.K * self.n_envs
         self._bootstrap_truncated()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         dev = self.device.index or 0
-        last_v = torch.empty(N, dtype=torch.float32, device=self.device)
+        last_v = torch.empty(KN, dtype=torch.float32, device=self.device)
         self._mlp.forward(self.obs_buf[T], value=last_v)   # value net only
+        # GAE runs per column: one launch covers every replica
         native.check(self.L.kp1_gae_scan(dev, C.c_void_p(self.rew_buf.data_ptr()), C.c_void_p(self.val_buf.data_ptr()),
                                          C.c_void_p(self.done_buf.data_ptr()), C.c_void_p(last_v.data_ptr()), cfg.gamma, cfg.gae_lambda,
-                                         C.c_void_p(self.adv_buf.data_ptr()), C.c_void_p(self.ret_buf.data_ptr()), T, N, C.c_void_p(stream)))
+                                         C.c_void_p(self.adv_buf.data_ptr()), C.c_void_p(self.ret_buf.data_ptr()), T, KN, C.c_void_p(stream)))
 
     def _rollout_step_hip(self, t: int) -> None:
         # (running the tracker on a side stream under the next policy forward was measured: the fork / join inside the graph
@@ -724,29 +762,31 @@ class PPO:
     def _capture_rollout(self) -> None:
         """Record the T-step rollout (policy forward, env step, curriculum tracker; data parallel: the done-byte all-gather of every chunk)
         once; every later rollout is one replay.  The kernels must have run once before a capture (code objects loaded, attributes set).  At
-        the very start that is a warm-up step between a device snapshot of the env state and its restore; a RE-capture in the middle of
+        the very start that is a warm-up step between a device snapshot of every env's state and its restore; a RE-capture in the middle of
         training (an env setter or a hyper-parameter changed, a step callback was removed) finds them warm from the rollouts already done.
         Either way the running episodes and random streams are untouched."""
         T = self.cfg.n_steps
         if not self._kernels_warm:
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
-            can_snapshot = hasattr(self.env, "snapshot")
             with torch.cuda.stream(side):
-                self.env.use_current_stream()
-                if can_snapshot:
-                    self.env.snapshot()      # the warm-up step below must not move the episodes or the random streams
+                for env in self.envs:
+                    env.use_current_stream()
+                    if hasattr(env, "snapshot"):
+                        env.snapshot()       # the warm-up step below must not move the episodes or the random streams
                 self._policy_env_step(0)
-                if self.curriculum is not None:
-                    self.curriculum.observe(self.done_buf[0].zero_(), 0)   # also loads the module the chunk form of the tracker lives in
-                self._post_rollout()                                        # the graph's tail, once eagerly (its buffers are rewritten by the real rollout)
-                self.env.use_current_stream()
-                if can_snapshot:
-                    self.env.restore()       # a captured rollout therefore continues exactly like an eager one (tests/test_distributed_gpu.py)
-                else:
-                    # wrappers without a device snapshot (the route env keeps state of its own): start the episodes again instead, at the
-                    # price of one extra reset() draw per env stream
-                    self.obs_buf[0].copy_(self.env.reset())
+                for k, cur in enumerate(self.curricula):
+                    if cur is not None:      # also loads the module the chunk form of the tracker lives in
+                        cur.observe(self.done_buf[0, self._sl(k)].zero_(), 0)
+                self._post_rollout()         # the graph's tail, once eagerly (its buffers are rewritten by the real rollout)
+                for k, env in enumerate(self.envs):
+                    env.use_current_stream()
+                    if hasattr(env, "snapshot"):
+                        env.restore()        # a captured rollout therefore continues exactly like an eager one (tests/test_distributed_gpu.py)
+                    else:
+                        # wrappers without a device snapshot (the route env keeps state of its own): start the episodes again instead, at
+                        # the price of one extra reset() draw per env stream
+                        self.obs_buf[0, self._sl(k)].copy_(env.reset())
             torch.cuda.current_stream(self.device).wait_stream(side)
             self._kernels_warm = True
         torch.cuda.synchronize(self.device)
@@ -756,21 +796,12 @@ class PPO:
                 self._rollout_step_hip(t)
             self._post_rollout()
 
-        self._rollout_graph = self._capture(body, on_begin=self.env.use_current_stream)
-        self.env.use_current_stream()
+        self._rollout_graph = self._capture(body, on_begin=self._envs_use_current_stream)
+        self._envs_use_current_stream()
 
-    def _capture_epoch(self, obs, act, old_logp, adv, ret, total: int, local_bs: int) -> None:
-        """one update epoch = advantage statistics of all minibatches (+ ONE all-reduce of them), then per minibatch: tile kernel, weight
-        gradients, finalize, [flat gradient all-reduce, sum of squares], Adam -- captured with the collectives inside"""
-        torch.cuda.synchronize(self.device)
-
-        def body() -> None:
-            mb_stats = self._epoch_adv_stats(adv, self.perm, total, local_bs)
-            for i, start in enumerate(range(0, total, local_bs)):
-                self._hip_minibatch_step(obs, self.perm[start:start + local_bs], act, old_logp, adv, ret, device_step=True,
-                                         adv_stats=None if mb_stats is None else mb_stats[i])
-
-        self._epoch_graph = self._capture(body)
+    def _envs_use_current_stream(self) -> None:
+        for env in self.envs:
+            env.use_current_stream()
 
     def _capture(self, body, on_begin=None):
         """record `body` once: ONE hipGraph (single process, or collectives captured inside), or a GraphSegments chain cut at every collective"""
@@ -813,68 +844,57 @@ class PPO:
     # ------------------------------------------------------------------ update
     def train(self) -> None:
         cfg = self.cfg
-        T, N = cfg.n_steps, self.n_envs
-        total = T * N
-        obs = self.obs_buf[:T].view(total, self.obs_w)
-        act = self.act_buf.view(total, ACT_DIM)
-        old_logp = self.logp_buf.view(total)
-        adv = self.adv_buf.view(total)
-        ret = self.ret_buf.view(total)
-        world = self.dist.world_size
-        local_bs = max(cfg.batch_size // world, 1)
-        n_updates = 0
+        total = cfg.n_steps * self.n_envs
+        local_bs = max(cfg.batch_size // self.dist.world_size, 1)
+        n_mb = (total + local_bs - 1) // local_bs     # optimiser steps per epoch
         self.n_train_calls += 1
         self.stats_dev.zero_()
         for _epoch in range(cfg.n_epochs):
-            if self.use_graphs:
-                self._draw_perm(total, out=self.perm)     # the epoch graph reads the fixed address self.perm
-                if self._epoch_graph is not None and self._epoch_graph_key != self._epoch_key():
-                    self._epoch_graph = None     # a hyper-parameter baked into the captured kernel arguments changed: capture again
-                if self._epoch_graph is None:
-                    # one eager epoch first (warm-up + it is a real epoch), then capture for the following ones
-                    if not self._epoch_warm:
-                        self._epoch_warm = True
-                        mb_stats = self._epoch_adv_stats(adv, self.perm, total, local_bs)
-                        for i, start in enumerate(range(0, total, local_bs)):
-                            self._hip_minibatch_step(obs, self.perm[start:start + local_bs], act, old_logp, adv, ret, device_step=True,
-                                                     adv_stats=None if mb_stats is None else mb_stats[i])
-                            n_updates += 1
-                            self.adam_t += 1
-                        continue
-                    self._capture_epoch(obs, act, old_logp, adv, ret, total, local_bs)
-                    self._epoch_graph_key = self._epoch_key()
-                    self._epoch_auto = {"phase": 0} if (self.graph_mode == "segmented" and self._epoch_policy == "auto") else None
-                    self._replay_checked("epoch", self._epoch_graph)      # the first replay carries one-time costs: never the timed one
-                    n_updates += (total + local_bs - 1) // local_bs
-                    self.adam_t += (total + local_bs - 1) // local_bs
-                    continue
+            for k in range(self.K):
+                self._draw_perm(k)
+            if not self.use_graphs:
+                # the eager epoch steps Adam from the device-resident step count too, exactly as the captured epoch does (bias corrections
+                # computed by the same device arithmetic): eager and replayed training stay bit-identical.  The count is set from the host
+                # mirror first, so loss_grad calls made outside train() cannot have moved it.
+                self._mlp.set_step_count(self.adam_t)
+                self._epoch_body()
+            elif self._epoch_graph is None and not self._epoch_warm:
+                self._epoch_warm = True      # one eager epoch first (warm-up + it is a real epoch), then capture for the following ones
+                self._epoch_body()
+            elif self._epoch_graph is None or self._epoch_graph_key != self._epoch_key():
+                self._epoch_graph = None     # (a hyper-parameter baked into the captured kernel arguments changed: capture again)
+                torch.cuda.synchronize(self.device)
+                self._epoch_graph = self._capture(self._epoch_body)
+                self._epoch_graph_key = self._epoch_key()
+                self._epoch_auto = {"phase": 0} if (self.graph_mode == "segmented" and self._epoch_policy == "auto") else None
+                self._replay_checked("epoch", self._epoch_graph)      # the first replay carries one-time costs: never the timed one
+            else:
                 if self.graph_mode == "segmented" and self._segmented_epoch_eager():
-                    # data parallel, segments measured slower than eager launches on this box (same bits either way)
-                    mb_stats = self._epoch_adv_stats(adv, self.perm, total, local_bs)
-                    for i, start in enumerate(range(0, total, local_bs)):
-                        self._hip_minibatch_step(obs, self.perm[start:start + local_bs], act, old_logp, adv, ret, device_step=True,
-                                                 adv_stats=None if mb_stats is None else mb_stats[i])
+                    self._epoch_body()     # data parallel, segments measured slower than eager launches on this box (same bits either way)
                 else:
                     self._replay_checked("epoch", self._epoch_graph)
                 self._segmented_epoch_timed()
-                n_updates += (total + local_bs - 1) // local_bs
-                self.adam_t += (total + local_bs - 1) // local_bs
-                continue
-            perm = self._draw_perm(total)
-            mb_stats = self._epoch_adv_stats(adv, perm, total, local_bs)
-            # the eager loop steps Adam from the device-resident step count too, exactly as the captured epoch does (bias corrections
-            # computed by the same device arithmetic): eager and replayed training stay bit-identical.  The count is set from the host
-            # mirror first, so loss_grad calls made outside train() cannot have moved it.
-            self._mlp.set_step_count(self.adam_t)
-            for i, start in enumerate(range(0, total, local_bs)):
-                idx = perm[start:start + local_bs]
-                self._hip_minibatch_step(obs, idx, act, old_logp, adv, ret, device_step=True, adv_stats=None if mb_stats is None else mb_stats[i])
-                self.adam_t += 1
-                n_updates += 1
-        stats = self.stats_dev.clone()
+            self.adam_t += n_mb
         # read back lazily (last_stats): a .tolist() here would make every iteration wait for its own update before the host can enqueue
         # the next rollout
-        self._last_stats_dev = (stats, n_updates)
+        self._last_stats_dev = (self.stats_dev.clone(), n_mb * cfg.n_epochs)
+
+    def _epoch_body(self) -> None:
+        """one update epoch from the shuffle in self.perm: advantage statistics of all minibatches (+ ONE all-reduce of them), then per
+        minibatch tile kernel, weight gradients, finalize, [flat gradient all-reduce, sum of squares], Adam.  The epoch graph records it; the
+        warm-up, segmented-eager and eager epochs call it directly."""
+        cfg = self.cfg
+        T = cfg.n_steps
+        total = T * self.n_envs
+        local_bs = max(cfg.batch_size // self.dist.world_size, 1)
+        obs = self.obs_buf[:T].view(total, self.obs_w)
+        act, old_logp = self.act_buf.view(total, ACT_DIM), self.logp_buf.view(total)
+        adv, ret = self.adv_buf.view(total), self.ret_buf.view(total)
+        perm = self.perm[0]
+        mb_stats = self._epoch_adv_stats(adv, perm, total, local_bs)
+        for i, start in enumerate(range(0, total, local_bs)):
+            self._hip_minibatch_step(obs, perm[start:start + local_bs], act, old_logp, adv, ret, device_step=True,
+                                     adv_stats=None if mb_stats is None else mb_stats[i])
 
     # Data parallel, graph_mode "segmented": an update epoch is 64 graph segments of four kernels with a collective between them.  A hipGraph
     # launch boundary costs more on the GPU timeline than a kernel boundary of an eager launch (one-rank RCCL group on one MI355X, collectives
@@ -914,10 +934,14 @@ class PPO:
     def last_stats(self) -> dict[str, float]:
         """mean policy loss / value loss / entropy / approx_kl over the minibatches of the last train() call, and their number (SB3 logger keys
         train/policy_gradient_loss, train/value_loss, train/entropy_loss, train/approx_kl); reading it synchronises with that update"""
+        return self._stats_rows()[0]
+
+    def _stats_rows(self) -> list[dict[str, float]]:
+        """last_stats of every replica"""
         if self._last_stats_dev is not None:
             stats, n_updates = self._last_stats_dev
-            self._last_stats_host = dict(zip(("policy_loss", "value_loss", "entropy", "approx_kl"), (stats / max(n_updates, 1)).tolist()))
-            self._last_stats_host["n_updates"] = n_updates
+            rows = (stats / max(n_updates, 1)).tolist()
+            self._last_stats_host = [dict(zip(("policy_loss", "value_loss", "entropy", "approx_kl"), r), n_updates=n_updates) for r in rows]
             self._last_stats_dev = None
         return self._last_stats_host
 
@@ -961,6 +985,7 @@ class PPO:
 
     # ------------------------------------------------------------------ driver
     def learn(self, total_timesteps: int | None = None, log_every: int = 0) -> "PPO":
+        """``total_timesteps`` and the logged steps / fps count each replica's own env steps"""
         total = int(total_timesteps if total_timesteps is not None else self.cfg.total_timesteps)
         start_steps = self.num_timesteps
         it = 0
@@ -971,9 +996,11 @@ class PPO:
             it += 1
             if log_every and it % log_every == 0 and self.dist.rank == 0:
                 dt = time.time() - t0
-                stage = self.curriculum.read().stage_index if self.curriculum is not None else -1
-                print(f"[ppo] it={it} steps={self.num_timesteps} fps={(self.num_timesteps - start_steps) / dt:,.0f} stage={stage} "
-                      f"rew={self.rew_buf.mean().item():.4f} {self.last_stats}", flush=True)
+                stages = [cur.read().stage_index if cur is not None else -1 for cur in self.curricula]
+                stats = self._stats_rows()
+                print(f"[ppo] it={it} steps={self.num_timesteps} fps={(self.num_timesteps - start_steps) / dt:,.0f} "
+                      f"stage={stages[0] if self.K == 1 else stages} rew={self.rew_buf.mean().item():.4f} {stats[0] if self.K == 1 else stats}",
+                      flush=True)
         return self
 
 

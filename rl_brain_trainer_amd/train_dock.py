@@ -120,23 +120,32 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     wall = time.time() - t0
     summary: dict[str, Any] = {}
     if rank == 0:
-        latest = root / "model_latest"
-        checkpoint.save(latest, ppo, env_cfg)
-        eval_summary = evaluate_dock(ppo, env_cfg, episodes=args.eval_episodes, seed=seed + 10_000, device=local_rank)
-        (root / "dock_eval").mkdir(exist_ok=True)
-        (root / "dock_eval" / "dock_eval_summary.json").write_text(json.dumps(eval_summary, indent=2))
-        summary = {"policy_type": "dock", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "config": cfg, "model_path": str(latest) + ".zip",
-                   "resume_from": str(args.resume_from) if args.resume_from else None, "n_envs": n_envs * world, "device": f"{world}x MI355X",
-                   "dock_eval_summary": eval_summary, "dock_reverse_curriculum": curriculum.summary() if curriculum is not None else None,
-                   "num_timesteps": ppo.num_timesteps, "wall_seconds": wall, "env_steps_per_second": ppo.num_timesteps / wall}
-        (root / "training_summary.json").write_text(json.dumps(summary, indent=2))
-        print(json.dumps(eval_summary, indent=2))
+        summary = _final_artifacts(root, ppo, env_cfg, args=args, cfg=cfg, curriculum=curriculum, resume=args.resume_from, n_envs=n_envs * world,
+                                   world=world, seed=seed, device=local_rank, wall=wall)
+        print(json.dumps(summary["dock_eval_summary"], indent=2))
     if world > 1:
         import torch.distributed as dist
 
         dist.barrier()
         ppo.dist.close()
         dist.destroy_process_group()
+    return summary
+
+
+def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, cfg: dict[str, Any], curriculum, resume, n_envs: int, world: int,
+                     seed: int, device: int, wall: float, extra: dict[str, Any] | None = None) -> dict[str, Any]:
+    """what a run leaves at its end: model_latest, the dock evaluation (dock_eval/) and training_summary.json (`ppo` is a PPO or a
+    population replica)"""
+    latest = root / "model_latest"
+    checkpoint.save(latest, ppo, env_cfg)
+    eval_summary = evaluate_dock(ppo, env_cfg, episodes=args.eval_episodes, seed=seed + 10_000, device=device)
+    (root / "dock_eval").mkdir(exist_ok=True)
+    (root / "dock_eval" / "dock_eval_summary.json").write_text(json.dumps(eval_summary, indent=2))
+    summary = {"policy_type": "dock", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "config": cfg, "model_path": str(latest) + ".zip",
+               "resume_from": str(resume) if resume else None, "n_envs": n_envs, "device": f"{world}x MI355X",
+               "dock_eval_summary": eval_summary, "dock_reverse_curriculum": curriculum.summary() if curriculum is not None else None,
+               "num_timesteps": ppo.num_timesteps, "wall_seconds": wall, "env_steps_per_second": ppo.num_timesteps / wall, **(extra or {})}
+    (root / "training_summary.json").write_text(json.dumps(summary, indent=2))
     return summary
 
 
@@ -169,19 +178,11 @@ def _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root: Path, w
     wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), log_every=args.log_every, tag="ppo-dock-population")
     rows = []
     for k, s in enumerate(seeds):
-        rep, r, curriculum = pop.replica(k), roots[s], pop.curricula[k]
-        latest = r / "model_latest"
-        checkpoint.save(latest, rep, env_cfg)
-        eval_summary = evaluate_dock(rep, env_cfg, episodes=args.eval_episodes, seed=s + 10_000, device=device)
-        (r / "dock_eval").mkdir(exist_ok=True)
-        (r / "dock_eval" / "dock_eval_summary.json").write_text(json.dumps(eval_summary, indent=2))
-        summary = {"policy_type": "dock", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "config": cfg, "model_path": str(latest) + ".zip",
-                   "resume_from": None, "n_envs": n_envs, "device": "1x MI355X",
-                   "dock_eval_summary": eval_summary, "dock_reverse_curriculum": curriculum.summary() if curriculum is not None else None,
-                   "num_timesteps": rep.num_timesteps, "wall_seconds": wall, "env_steps_per_second": rep.num_timesteps / wall, "seed": s}
-        (r / "training_summary.json").write_text(json.dumps(summary, indent=2))
-        rows.append({"seed": s, "artifact_root": str(r), "final_curriculum_stage": curriculum.current_stage_index if curriculum is not None else None,
-                     "last_update_stats": rep.last_stats, "best_score": eval_summary["success_rate"], "model_latest": str(latest) + ".zip"})
+        rep, curriculum = pop.replica(k), pop.curricula[k]
+        summ = _final_artifacts(roots[s], rep, env_cfg, args=args, cfg=cfg, curriculum=curriculum, resume=None, n_envs=n_envs, world=1, seed=s,
+                                device=device, wall=wall, extra={"seed": s})
+        rows.append({"seed": s, "artifact_root": str(roots[s]), "final_curriculum_stage": curriculum.current_stage_index if curriculum is not None else None,
+                     "last_update_stats": rep.last_stats, "best_score": summ["dock_eval_summary"]["success_rate"], "model_latest": summ["model_path"]})
     summary = population_summary(pop, rows, wall_seconds=wall, selection="dock evaluation success_rate")
     (root / "population_summary.json").write_text(json.dumps(summary, indent=2))
     pop.close()

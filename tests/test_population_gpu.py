@@ -227,6 +227,11 @@ def test_population_checkpoint_hand_over(tmp_path):
     obs = torch.zeros((32, 64), device=pop.device)
     obs[:, :56] = torch.randn((32, 56), device=pop.device)
     assert torch.equal(InferencePolicy.load(str(path)).predict(obs), pop.replica(1).predict(obs))
+    # what acts on one policy is refused on the population handle itself: it points to replica(k) / infer_policy(k)
+    for single_policy_call in (lambda: pop.predict(obs), lambda: pop.predict_unclipped(obs), lambda: pop.load_checkpoint(str(path)),
+                               lambda: pop.last_stats):
+        with pytest.raises(TypeError, match=r"replica\(k\).*infer_policy\(k\)"):
+            single_policy_call()
 
     # a single run with the same seed is at the same point in its streams once it has done the same iteration; then it takes the archive
     single = PPO(env_factory(8), dataclasses.replace(pcfg, seed=8), use_graphs=True)
