@@ -459,6 +459,8 @@ int kp1_update_config(kp1_env* env, const kp1_config* cfg);
 int kp1_set_handoff_states(kp1_env* env, const kp1_handoff_state* states_host, int32_t n_states);
 /* re-seed env streams: env i <- default_rng(seed0 + first_env_id + i); reset(seed=...) :103-104 */
 int kp1_seed(kp1_env* env, uint64_t seed0, uint64_t first_env_id);
+/* block-structured seeding: env i of block k = i / n_per_block gets default_rng(seeds[k] + i % n_per_block); blocks * n_per_block = N */
+int kp1_seed_blocks(kp1_env* env, const uint64_t* seeds_host, int32_t blocks, int32_t n_per_block);
 
 /* reset(); :102-211.  mask_dev: u8[N] device (NULL = all envs).  opts: explicit options for ALL N envs
  * (rows of masked-out envs ignored) or NULL to sample.  obs_dev: f32[N][56] device (NULL = skip). */

@@ -155,7 +155,8 @@ int kp1_mlp_create(int32_t device, int32_t hidden, int32_t max_batch, kp1_mlp** 
 int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batch, kp1_mlp** out);
 /* Population handle: K = `replicas` (1..KP1_MLP_MAX_REPLICAS) independent copies of the net -- K weight packs, activation workspaces and
  * gradient partials -- trained through ONE launch sequence with the replica on a grid axis (z = 2 * replica + net, or grid.y).  hidden 64 or
- * 128 (the layer-wise Hp = 128 kernels) and 56-float observations only.  Each replica computes exactly what a K = 1 handle computes on the same
+ * 128 (the layer-wise Hp = 128 kernels); obs_dim 56 (padded to 64) or 80 (the route observation, padded to 128: layer 1 and dW1 then run
+ * over 128 input columns per replica).  Each replica computes exactly what a K = 1 handle computes on the same
  * inputs: reductions keep a single handle's order and chunking per replica.  kp1_mlp_create / _create_ex make K = 1 handles.
  * Buffer layout of the entry points below for a K-replica handle (K = 1: the layouts documented at each entry point):
  *   kp1_mlp_pack_weights, kp1_mlp_adam_step: params, grad, exp_avg, exp_avg_sq are [K][num_params]; one clip norm per replica, one shared

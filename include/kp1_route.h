@@ -75,6 +75,18 @@ int kp1_route_get_dataset(kp1_route* r, double* poses6_host, double* progress_ho
 int kp1_route_set_window(kp1_route* r, int32_t min_route_index, int32_t max_route_index);
 int kp1_route_seed(kp1_route* r, uint64_t seed, uint64_t first_env_id);
 
+/* ---- population handle: K replicas of N envs in one handle (block k = envs [k N, (k + 1) N)) -------------------------------------
+ * base_env holds K * N envs.  Env i of replica k owns default_rng(seeds[k] + i) for both PCG64 streams, the base env's (re-seeded here with
+ * kp1_seed_blocks) and the wrapper's: block k is bit for bit the handle kp1_route_create(seed = seeds[k], first_env_id = 0) makes on N envs.
+ * Everything in the config is shared except the reset window: each replica has its own min / max route index, read by the resets of its
+ * block.  kp1_route_set_window sets every window; a single handle is a population of one.  f32 base envs only. */
+#define KP1_ROUTE_MAX_REPLICAS 16
+int kp1_route_create_population(kp1_env* base_env, const kp1_route_config* cfg, const double* route_q_host, int32_t n_waypoints,
+                                const uint64_t* seeds_host, int32_t replicas, kp1_route** out);
+int kp1_route_num_replicas(const kp1_route* r);
+/* set_route_window of replica k alone */
+int kp1_route_set_replica_window(kp1_route* r, int32_t replica, int32_t min_route_index, int32_t max_route_index);
+
 /* explicit reset (options{"route_index", "start_route_index", "initial_q", ...}); NULL members fall back as the wrappers do */
 typedef struct kp1_route_reset_opts {
   const int32_t* route_index;       /* [N] or NULL = sample with the route stream */
@@ -158,6 +170,21 @@ int kp1_route_curriculum_observe_chunk(kp1_route* r, kp1_route_curriculum_state*
                                        int32_t chunk_steps, int32_t world, void* stream);
 /* copy the tracker to the host (synchronises the stream) and bring the host copy of the reset window up to date */
 int kp1_route_curriculum_read(kp1_route* r, const kp1_route_curriculum_state* st_dev, kp1_route_curriculum_state* out_host, void* stream);
+
+/* ---- population tracker: one kp1_route_curriculum_state per replica of a population handle ------------------------------------------
+ * st_dev = K states back to back.  observe_population launches K workgroups: workgroup k scans the envs [k N, (k + 1) N) of the step in env
+ * order, advances replica k's clock by steps_per_call and on promotion rewrites window k only -- replica k's tracker is the one a single
+ * handle of N envs with seed seeds[k] would run.  The single-handle entry points (create / observe / observe_chunk) refuse a population
+ * handle of K > 1: the data-parallel chunk tracker has no population form. */
+int kp1_route_curriculum_create_population(kp1_route* r, const int32_t* prefix_end_index, int32_t n_stages, double promotion_success_rate,
+                                           double promotion_route_ready_hit_rate, double promotion_orientation_hit_rate,
+                                           double promotion_max_regression_rate, int32_t window_episodes, int32_t min_episodes_per_stage,
+                                           kp1_route_curriculum_state** out_dev);
+int kp1_route_curriculum_observe_population(kp1_route* r, kp1_route_curriculum_state* st_dev, const uint8_t* dones /* [K N] */,
+                                            int32_t steps_per_call, void* stream);
+/* replica k's tracker to the host (synchronises the stream); brings the host copy of window k up to date */
+int kp1_route_curriculum_read_replica(kp1_route* r, const kp1_route_curriculum_state* st_dev, int32_t replica, kp1_route_curriculum_state* out_host,
+                                      void* stream);
 
 #ifdef __cplusplus
 }

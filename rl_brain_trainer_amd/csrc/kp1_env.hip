@@ -483,13 +483,15 @@ int upload_cfg(kp1_env* e) {
   return reapply_dock_stage(e);
 }
 
-int seed_streams(kp1_env* e, uint64_t seed0, uint64_t first_env_id) {
+// env i <- default_rng(seed_of(i))
+template <typename SeedOf>
+int seed_streams_by(kp1_env* e, SeedOf seed_of) {
   const int64_t n = e->n;
   std::vector<uint64_t> r64(4 * (size_t)n);
   std::vector<uint32_t> r32(2 * (size_t)n, 0u);
   for (int64_t i = 0; i < n; ++i) {
     kp1_rng_state s;
-    pcg64_seed(seed0 + first_env_id + (uint64_t)i, &s);
+    pcg64_seed(seed_of(i), &s);
     r64[0 * n + i] = s.state_hi;
     r64[1 * n + i] = s.state_lo;
     r64[2 * n + i] = s.inc_hi;
@@ -499,6 +501,10 @@ int seed_streams(kp1_env* e, uint64_t seed0, uint64_t first_env_id) {
   HIP_TRY(hipMemcpyAsync(e->rng32, r32.data(), r32.size() * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return KP1_OK;
+}
+
+int seed_streams(kp1_env* e, uint64_t seed0, uint64_t first_env_id) {
+  return seed_streams_by(e, [=](int64_t i) { return seed0 + first_env_id + (uint64_t)i; });
 }
 
 template <typename R>
@@ -810,6 +816,14 @@ int kp1_seed(kp1_env* e, uint64_t seed0, uint64_t first_env_id) {
   if (!e) return fail(KP1_ERR_INVALID, "env is NULL");
   HIP_TRY(hipSetDevice(e->device));
   return seed_streams(e, seed0, first_env_id);
+}
+
+int kp1_seed_blocks(kp1_env* e, const uint64_t* seeds, int32_t blocks, int32_t n_per_block) {
+  if (!e || !seeds || blocks < 1 || n_per_block < 1 || (int64_t)blocks * n_per_block != e->n)
+    return fail(KP1_ERR_INVALID, "kp1_seed_blocks: need blocks * n_per_block == N and one seed per block");
+  HIP_TRY(hipSetDevice(e->device));
+  const std::vector<uint64_t> sd(seeds, seeds + blocks);
+  return seed_streams_by(e, [&](int64_t i) { return sd[(size_t)(i / n_per_block)] + (uint64_t)(i % n_per_block); });
 }
 
 int kp1_reset(kp1_env* e, const uint8_t* mask_dev, const kp1_reset_opts* opts, float* obs_dev) {

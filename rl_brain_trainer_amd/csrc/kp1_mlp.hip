@@ -1344,7 +1344,7 @@ int nt_row_tiles(int n, int Hp) {
 template <int EPI>
 int launch_nt(const GemmNT& g, hipStream_t stream) {
   if (g.N % 128 != 0) return fail(KP1_ERR_INVALID, "gemm_nt needs N % 128 == 0");
-  if (g.reps > 1) {   // population handles: Hp = 128 (narrow tiles, as a single handle of that width uses), 64-float observations
+  if (g.reps > 1) {   // population handles: Hp = 128 (narrow tiles, as a single handle of that width uses); K = INP (64 / 128) or Hp
     if (g.N != 128) return fail(KP1_ERR_UNSUPPORTED, "population gemm_nt is instantiated for N = 128");
     if (g.K == 64) return launch_nt_inst<128, EPI, 64, true>(g, stream);
     if (g.K == 128) return launch_nt_inst<128, EPI, 128, true>(g, stream);
@@ -1520,9 +1520,10 @@ int kp1_mlp_create_population(int32_t device, int32_t hidden, int32_t obs_dim, i
   if (replicas < 1 || replicas > KP1_MLP_MAX_REPLICAS) return fail(KP1_ERR_INVALID, "replicas must be in [1, KP1_MLP_MAX_REPLICAS]");
   if (hidden != 64 && hidden != 128)
     return fail(KP1_ERR_UNSUPPORTED, "population handles run the layer-wise kernels: hidden must be 64 or 128");
-  if (obs_dim != KP1_MLP_IN) return fail(KP1_ERR_UNSUPPORTED, "population handles take the 56-float observation");
-  // per-replica element offsets are 32-bit: the largest array (the dW2 partial slab, 64 chunks x 2 nets x 128 x 128) and the activations
-  // of K replicas must stay below 2^31 elements
+  if (obs_dim != KP1_MLP_IN && obs_dim != KP1_MLP_IN_ROUTE)
+    return fail(KP1_ERR_UNSUPPORTED, "population handles take the 56-float or the 80-float (route) observation");
+  // per-replica element offsets are 32-bit: the largest arrays (the dW2 / dW1 partial slabs, 64 chunks x 2 nets x 128 x INP with INP <= 128)
+  // and the activations of K replicas must stay below 2^31 elements
   const int64_t mb = ((int64_t)max_batch + 127) / 128 * 128;
   if (max_batch <= 0 || (int64_t)replicas * 2 * mb * 128 >= ((int64_t)1 << 31)) return fail(KP1_ERR_INVALID, "max_batch too large for a population handle");
   return mlp_create(device, hidden, obs_dim, max_batch, replicas, out);

@@ -66,9 +66,20 @@ struct RouteState {
 constexpr int RP_Q = 0, RP_DQ = 7, RP_ACT = 14, RP_POSE = 21, RP_NUM = 27;
 
 struct RouteDevCfg {
-  kp1_route_config c;
+  kp1_route_config c;   // (c.reset.min / max_route_index: the host's last set_window; the kernels read `window`)
   int success_dwell_steps, terminate_on_success;
+  // reset window of each replica of a population handle: env i resets inside window[i / n_per_replica] (a single handle: n_per_replica = N,
+  // window 0).  The prefix tracker of replica k rewrites window[k] on promotion.
+  int n_per_replica, pad_;
+  int32_t window[KP1_ROUTE_MAX_REPLICAS][2];   // [min_route_index, max_route_index]
 };
+
+// the reset window of env i
+__device__ __forceinline__ void route_window_of(const RouteDevCfg& rc, int64_t i, int& lo, int& hi) {
+  const int k = (int)i / rc.n_per_replica;
+  lo = rc.window[k][0];
+  hi = rc.window[k][1];
+}
 
 __device__ __forceinline__ int rclipi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -77,10 +88,12 @@ struct RouteSampleDev {
   double initial_q[NJ], initial_dq[NJ], initial_prev_action[NJ];
   int route_index, start_index, mode;
 };
-__device__ __forceinline__ void sample_route_reset_dev(Pcg& g, const RouteTable& rt, const DevSampler& smp, const kp1_route_reset_cfg& c, RouteSampleDev& out) {
+// (win_min / win_max: the env's reset window, in place of c.min_route_index / c.max_route_index)
+__device__ __forceinline__ void sample_route_reset_dev(Pcg& g, const RouteTable& rt, const DevSampler& smp, const kp1_route_reset_cfg& c, int win_min,
+                                                       int win_max, RouteSampleDev& out) {
   const int max_index = rt.n - 1;
-  const int lo = rclipi(c.min_route_index, 1, max_index);
-  const int hi = rclipi(c.max_route_index, lo, max_index);
+  const int lo = rclipi(win_min, 1, max_index);
+  const int hi = rclipi(win_max, lo, max_index);
   double ratios[5] = {fmax(c.prefix_start_reset_ratio, 0.0), fmax(c.random_prefix_reset_ratio, 0.0), fmax(c.segment_reset_ratio, 0.0),
                       fmax(c.replay_reset_ratio, 0.0), fmax(c.recovery_reset_ratio, 0.0)};
   double total = 0.0;
@@ -174,11 +187,11 @@ __device__ __forceinline__ void store_route_obs(float* __restrict__ obs, int64_t
 template <typename R>
 __device__ __forceinline__ void route_reset_env(const EnvState<R>& st, const DevCfg<R>& cfg, const DevSampler& smp, const RouteDevCfg& rc, const RouteTable& rt,
                                                 const RouteState<R>& rs, int64_t i, int first_target, int start_index, int mode, const double* q0,
-                                                const double* dq0, const double* pa0, float* obs, int obs_dim, int obs_stride) {
+                                                const double* dq0, const double* pa0, float* obs, int obs_dim, int obs_stride, int win_max) {
   const int64_t n = st.n;
   int cur = first_target, last = first_target;
   if (rc.c.sequence_enabled) {
-    const int max_index = rc.c.reset.max_route_index < rt.n - 1 ? rc.c.reset.max_route_index : rt.n - 1;
+    const int max_index = win_max < rt.n - 1 ? win_max : rt.n - 1;
     const int seq_len = rc.c.sequence_length > 1 ? rc.c.sequence_length : 1;
     cur = rclipi(first_target, 1, max_index);
     last = max_index < cur + seq_len - 1 ? max_index : cur + seq_len - 1;
@@ -225,6 +238,8 @@ __global__ void __launch_bounds__(256) kp1_route_reset_kernel(const RouteResetAr
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.st.n || (a.mask && !a.mask[i])) return;
   const RouteDevCfg& rc = *a.rc;
+  int win_min, win_max;
+  route_window_of(rc, i, win_min, win_max);
   double q0[NJ], dq0[NJ], pa0[NJ];
   int first_target, start, mode;
   if (a.route_index) {  // explicit (route_env.py:53-60 / route_sequence_env.py:103-109)
@@ -243,7 +258,7 @@ __global__ void __launch_bounds__(256) kp1_route_reset_kernel(const RouteResetAr
     Pcg g;
     rng_load(a.rs.rng64, a.rs.rng32, a.st.n, i, g);
     RouteSampleDev s;
-    sample_route_reset_dev(g, a.rt, *a.smp, rc.c.reset, s);
+    sample_route_reset_dev(g, a.rt, *a.smp, rc.c.reset, win_min, win_max, s);
     rng_store(a.rs.rng64, a.rs.rng32, a.st.n, i, g);
     first_target = s.route_index; start = s.start_index; mode = s.mode;
 #pragma unroll
@@ -251,7 +266,7 @@ __global__ void __launch_bounds__(256) kp1_route_reset_kernel(const RouteResetAr
       q0[k] = s.initial_q[k]; dq0[k] = s.initial_dq[k]; pa0[k] = s.initial_prev_action[k];
     }
   }
-  route_reset_env<R>(a.st, *a.cfg, *a.smp, rc, a.rt, a.rs, i, first_target, start, mode, q0, dq0, pa0, a.obs, a.obs_dim, a.obs_stride);
+  route_reset_env<R>(a.st, *a.cfg, *a.smp, rc, a.rt, a.rs, i, first_target, start, mode, q0, dq0, pa0, a.obs, a.obs_dim, a.obs_stride, win_max);
 }
 
 template <typename R>
@@ -466,11 +481,13 @@ __global__ void __launch_bounds__(256) kp1_route_step_kernel(const RouteStepArgs
     if (a.terminal_obs) store_route_obs<R>(a.terminal_obs, i, a.obs_dim, a.obs_stride, o, cfg, a.rt, cur, q);
     Pcg g;
     rng_load(rs.rng64, rs.rng32, n, i, g);
+    int win_min, win_max;
+    route_window_of(rc, i, win_min, win_max);
     RouteSampleDev s;
-    sample_route_reset_dev(g, a.rt, *a.smp, rc.c.reset, s);
+    sample_route_reset_dev(g, a.rt, *a.smp, rc.c.reset, win_min, win_max, s);
     rng_store(rs.rng64, rs.rng32, n, i, g);
     route_reset_env<R>(st, cfg, *a.smp, rc, a.rt, rs, i, s.route_index, s.start_index, s.mode, s.initial_q, s.initial_dq, s.initial_prev_action, a.obs,
-                       a.obs_dim, a.obs_stride);
+                       a.obs_dim, a.obs_stride, win_max);
     // the finished episode's info stays readable, like the base env's auto-reset
     rs.cur[i] = rs.cur[i];
   } else {
@@ -510,6 +527,8 @@ struct kp1_route {
   void* comps = nullptr;       // R[17][N]
   bool comps_enabled = false;
   int32_t obs_stride = 0;      // row pitch of caller observation buffers (kp1_route_set_obs_stride; default = obs_dim)
+  int32_t n_replicas = 1, n_per_replica = 0;   // population handle: K blocks of N envs (a single handle: 1 x N)
+  std::vector<int32_t> win;    // host copy of the reset windows [K][2]
   std::vector<void*> allocs;
 };
 
@@ -533,6 +552,13 @@ int route_upload_cfg(kp1_route* r) {
   d.c = r->cfg;
   d.success_dwell_steps = r->base->cfg.termination.success_dwell_steps;
   d.terminate_on_success = r->base->cfg.termination.terminate_on_success;
+  d.n_per_replica = r->n_per_replica;
+  d.pad_ = 0;
+  std::memset(d.window, 0, sizeof d.window);
+  for (int k = 0; k < r->n_replicas; ++k) {
+    d.window[k][0] = r->win[2 * k];
+    d.window[k][1] = r->win[2 * k + 1];
+  }
   HIP_TRY(hipMemcpyAsync(r->dev_cfg, &d, sizeof d, hipMemcpyHostToDevice, r->base->stream));
   HIP_TRY(hipStreamSynchronize(r->base->stream));
   return KP1_OK;
@@ -622,8 +648,9 @@ __device__ __forceinline__ void route_trk_store(kp1_route_curriculum_state* st, 
 }
 
 // one finished episode (success, route_ready, orientation hit, regression): the four deque appends, the window rates, the promotion with its
-// event record and the reset-window write.  `now` = the callback's num_timesteps at this env step.
-__device__ __forceinline__ void route_trk_append(kp1_route_curriculum_state* __restrict__ st, RouteDevCfg* __restrict__ cfg, RouteTrk& c,
+// event record and the reset-window write (`win`: the tracker's replica window in the device route config).  `now` = the callback's
+// num_timesteps at this env step.
+__device__ __forceinline__ void route_trk_append(kp1_route_curriculum_state* __restrict__ st, int32_t* __restrict__ win, RouteTrk& c,
                                                  const uint8_t v[4], int64_t now) {
   c.count += 1;
   const int slot = c.len < c.window ? (c.head + c.len) % c.window : c.head;   // deque(maxlen = window).append
@@ -656,8 +683,8 @@ __device__ __forceinline__ void route_trk_append(kp1_route_curriculum_state* __r
   c.count = 0; c.len = 0; c.head = 0;
 #pragma unroll
   for (int q = 0; q < 4; ++q) c.sums[q] = 0;
-  cfg->c.reset.min_route_index = 1;                            // env_method("set_route_window", max_route_index = prefix, min_route_index = 1)
-  cfg->c.reset.max_route_index = st->prefix_end_index[c.stage];
+  win[0] = 1;                                                  // env_method("set_route_window", max_route_index = prefix, min_route_index = 1)
+  win[1] = st->prefix_end_index[c.stage];
 }
 
 // the masks of one 64-env group per lane: bit b = env (group start + b)
@@ -666,7 +693,7 @@ struct RouteMasks {
 };
 
 // lane 0 appends the finished episodes of the 64 groups of the wave in env order (lane k's masks arrive by shuffle)
-__device__ __forceinline__ void route_trk_replay(kp1_route_curriculum_state* __restrict__ st, RouteDevCfg* __restrict__ cfg, RouteTrk& c, int lane,
+__device__ __forceinline__ void route_trk_replay(kp1_route_curriculum_state* __restrict__ st, int32_t* __restrict__ win, RouteTrk& c, int lane,
                                                  const RouteMasks& mk, int64_t now) {
   for (int src = 0; src < 64; ++src) {
     unsigned long long m = __shfl(mk.done, src);
@@ -676,16 +703,25 @@ __device__ __forceinline__ void route_trk_replay(kp1_route_curriculum_state* __r
       const int b = __ffsll((long long)m) - 1;
       m &= m - 1;
       const uint8_t v[4] = {(uint8_t)((ms >> b) & 1ull), (uint8_t)((mr >> b) & 1ull), (uint8_t)((mo >> b) & 1ull), (uint8_t)((mg >> b) & 1ull)};
-      route_trk_append(st, cfg, c, v, now);
+      route_trk_append(st, win, c, v, now);
     }
   }
 }
 
-__global__ void __launch_bounds__(64) route_curriculum_kernel(kp1_route_curriculum_state* __restrict__ st, RouteDevCfg* __restrict__ cfg,
-                                                              const uint8_t* __restrict__ dones, const uint8_t* __restrict__ ready,
-                                                              const uint8_t* __restrict__ ori_hit, const uint8_t* __restrict__ regression, int n,
+// Workgroup k = replica k (a single handle: one workgroup): tracker st[k], envs [k n, (k + 1) n), window k.
+__global__ void __launch_bounds__(64) route_curriculum_kernel(kp1_route_curriculum_state* __restrict__ st_all, RouteDevCfg* __restrict__ cfg,
+                                                              const uint8_t* __restrict__ dones_all, const uint8_t* __restrict__ ready_all,
+                                                              const uint8_t* __restrict__ ori_hit_all, const uint8_t* __restrict__ regression_all, int n,
                                                               int steps_per_call) {
   const int lane = threadIdx.x;
+  const int rep = (int)blockIdx.x;
+  kp1_route_curriculum_state* __restrict__ st = st_all + rep;
+  int32_t* __restrict__ win = cfg->window[rep];
+  const int64_t off = (int64_t)rep * n;
+  const uint8_t* __restrict__ dones = dones_all + off;
+  const uint8_t* __restrict__ ready = ready_all + off;
+  const uint8_t* __restrict__ ori_hit = ori_hit_all + off;
+  const uint8_t* __restrict__ regression = regression_all + off;
   int64_t now = 0;
   if (lane == 0) {
     now = st->num_timesteps + steps_per_call;
@@ -732,7 +768,7 @@ __global__ void __launch_bounds__(64) route_curriculum_kernel(kp1_route_curricul
     if (__ballot(mk.done != 0ull) == 0ull) continue;
     RouteTrk c = {};
     if (lane == 0) route_trk_load(st, c);
-    route_trk_replay(st, cfg, c, lane, mk, now);
+    route_trk_replay(st, win, c, lane, mk, now);
     if (lane == 0) route_trk_store(st, c);
   }
 }
@@ -816,7 +852,7 @@ __global__ void __launch_bounds__(64) route_curriculum_chunk_kernel(kp1_route_cu
           for (int b = 0; b < 64 && first + b < n_local; ++b) route_rec_word(rec[first + b], b, mk);
         }
         if (__ballot(mk.done != 0ull) == 0ull) continue;
-        route_trk_replay(st, cfg, c, lane, mk, now);
+        route_trk_replay(st, cfg->window[0], c, lane, mk, now);
       }
     }
   }
@@ -825,6 +861,10 @@ __global__ void __launch_bounds__(64) route_curriculum_chunk_kernel(kp1_route_cu
     st->num_timesteps = now;
   }
 }
+
+int route_curriculum_alloc(kp1_route* r, const int32_t* prefix_end_index, int32_t n_stages, double promotion_success_rate,
+                           double promotion_route_ready_hit_rate, double promotion_orientation_hit_rate, double promotion_max_regression_rate,
+                           int32_t window_episodes, int32_t min_episodes_per_stage, kp1_route_curriculum_state** out_dev);
 
 }  // namespace
 
@@ -863,6 +903,8 @@ int kp1_route_create(kp1_env* base, const kp1_route_config* cfg, const double* r
   r->cfg = *cfg;
   r->obs_stride = cfg->include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM;
   r->n_waypoints = n_waypoints;
+  r->n_per_replica = (int32_t)base->n;
+  r->win = {cfg->reset.min_route_index, cfg->reset.max_route_index};
   const int64_t n = base->n, W = n_waypoints;
   int rc = KP1_OK;
   auto alloc = [&](void** p, size_t bytes) {
@@ -946,7 +988,60 @@ int kp1_route_set_window(kp1_route* r, int32_t min_route_index, int32_t max_rout
   if (!r) return fail(KP1_ERR_INVALID, "NULL route");
   r->cfg.reset.min_route_index = min_route_index;
   r->cfg.reset.max_route_index = max_route_index;
+  for (int k = 0; k < r->n_replicas; ++k) {
+    r->win[2 * k] = min_route_index;
+    r->win[2 * k + 1] = max_route_index;
+  }
   return route_upload_cfg(r);
+}
+
+int kp1_route_set_replica_window(kp1_route* r, int32_t replica, int32_t min_route_index, int32_t max_route_index) {
+  if (!r) return fail(KP1_ERR_INVALID, "NULL route");
+  if (replica < 0 || replica >= r->n_replicas) return fail(KP1_ERR_INVALID, "kp1_route_set_replica_window: replica out of range");
+  r->win[2 * replica] = min_route_index;
+  r->win[2 * replica + 1] = max_route_index;
+  return route_upload_cfg(r);
+}
+
+int kp1_route_num_replicas(const kp1_route* r) { return r ? r->n_replicas : 0; }
+
+int kp1_route_create_population(kp1_env* base, const kp1_route_config* cfg, const double* route_q_host, int32_t n_waypoints, const uint64_t* seeds,
+                                int32_t replicas, kp1_route** out) {
+  if (!base || !seeds || !out) return fail(KP1_ERR_INVALID, "bad argument to kp1_route_create_population");
+  if (replicas < 1 || replicas > KP1_ROUTE_MAX_REPLICAS || base->n % replicas != 0)
+    return fail(KP1_ERR_INVALID, "kp1_route_create_population: replicas must be in [1, KP1_ROUTE_MAX_REPLICAS] and divide the base env's N");
+  if (base->real_type != KP1_REAL_F32) return fail(KP1_ERR_UNSUPPORTED, "population route handles drive an f32 base env");
+  const int32_t npb = (int32_t)(base->n / replicas);
+  kp1_route* r = nullptr;
+  int rc = kp1_route_create(base, cfg, route_q_host, n_waypoints, seeds[0], 0, &r);
+  if (rc != KP1_OK) return rc;
+  r->n_replicas = replicas;
+  r->n_per_replica = npb;
+  r->win.resize(2 * (size_t)replicas);
+  for (int k = 0; k < replicas; ++k) {
+    r->win[2 * k] = cfg->reset.min_route_index;
+    r->win[2 * k + 1] = cfg->reset.max_route_index;
+  }
+  rc = route_upload_cfg(r);
+  // both streams of env i in block k <- default_rng(seeds[k] + i), the base env's (reset(seed=) semantics of kp1_route_seed) and the wrapper's
+  if (rc == KP1_OK) rc = kp1_seed_blocks(base, seeds, replicas, npb);
+  if (rc == KP1_OK) {
+    const int64_t n = base->n;
+    std::vector<uint64_t> r64(4 * (size_t)n);
+    std::vector<uint32_t> r32(2 * (size_t)n, 0u);
+    for (int64_t i = 0; i < n; ++i) {
+      kp1_rng_state st;
+      pcg64_seed(seeds[i / npb] + (uint64_t)(i % npb), &st);
+      r64[0 * n + i] = st.state_hi; r64[1 * n + i] = st.state_lo; r64[2 * n + i] = st.inc_hi; r64[3 * n + i] = st.inc_lo;
+    }
+    if (hipMemcpyAsync(r->rng64, r64.data(), r64.size() * 8, hipMemcpyHostToDevice, base->stream) != hipSuccess ||
+        hipMemcpyAsync(r->rng32, r32.data(), r32.size() * 4, hipMemcpyHostToDevice, base->stream) != hipSuccess ||
+        hipStreamSynchronize(base->stream) != hipSuccess)
+      rc = fail(KP1_ERR_RUNTIME, "kp1_route_create_population: seeding the wrapper streams failed");
+  }
+  if (rc != KP1_OK) { kp1_route_destroy(r); return rc; }
+  *out = r;
+  return KP1_OK;
 }
 
 int kp1_route_seed(kp1_route* r, uint64_t seed, uint64_t first_env_id) {
@@ -1044,6 +1139,30 @@ int kp1_route_curriculum_create(kp1_route* r, const int32_t* prefix_end_index, i
   if (!r || !prefix_end_index || !out_dev) return fail(KP1_ERR_INVALID, "NULL argument");
   if (n_stages < 1 || n_stages > KP1_ROUTE_CURRICULUM_MAX_STAGES) return fail(KP1_ERR_INVALID, "RoutePrefixCurriculumCallback requires 1..16 stages");
   if (window_episodes > KP1_ROUTE_CURRICULUM_MAX_WINDOW) return fail(KP1_ERR_INVALID, "promotion window larger than KP1_ROUTE_CURRICULUM_MAX_WINDOW");
+  if (r->n_replicas != 1) return fail(KP1_ERR_UNSUPPORTED, "a population route handle takes kp1_route_curriculum_create_population");
+  return route_curriculum_alloc(r, prefix_end_index, n_stages, promotion_success_rate, promotion_route_ready_hit_rate, promotion_orientation_hit_rate,
+                                promotion_max_regression_rate, window_episodes, min_episodes_per_stage, out_dev);
+}
+
+int kp1_route_curriculum_create_population(kp1_route* r, const int32_t* prefix_end_index, int32_t n_stages, double promotion_success_rate,
+                                           double promotion_route_ready_hit_rate, double promotion_orientation_hit_rate,
+                                           double promotion_max_regression_rate, int32_t window_episodes, int32_t min_episodes_per_stage,
+                                           kp1_route_curriculum_state** out_dev) {
+  if (!r || !prefix_end_index || !out_dev) return fail(KP1_ERR_INVALID, "NULL argument");
+  if (n_stages < 1 || n_stages > KP1_ROUTE_CURRICULUM_MAX_STAGES) return fail(KP1_ERR_INVALID, "RoutePrefixCurriculumCallback requires 1..16 stages");
+  if (window_episodes > KP1_ROUTE_CURRICULUM_MAX_WINDOW) return fail(KP1_ERR_INVALID, "promotion window larger than KP1_ROUTE_CURRICULUM_MAX_WINDOW");
+  return route_curriculum_alloc(r, prefix_end_index, n_stages, promotion_success_rate, promotion_route_ready_hit_rate, promotion_orientation_hit_rate,
+                                promotion_max_regression_rate, window_episodes, min_episodes_per_stage, out_dev);
+}
+
+}  // extern "C"
+
+namespace {
+// K = r->n_replicas identical initial trackers in device memory, every window set to the first stage (_on_training_start)
+int route_curriculum_alloc(kp1_route* r, const int32_t* prefix_end_index, int32_t n_stages, double promotion_success_rate,
+                           double promotion_route_ready_hit_rate, double promotion_orientation_hit_rate, double promotion_max_regression_rate,
+                           int32_t window_episodes, int32_t min_episodes_per_stage, kp1_route_curriculum_state** out_dev) {
+  const int K = r->n_replicas;
   HIP_TRY(hipSetDevice(r->base->device));
   kp1_route_curriculum_state* h = new kp1_route_curriculum_state();
   std::memset(h, 0, sizeof *h);
@@ -1054,8 +1173,9 @@ int kp1_route_curriculum_create(kp1_route* r, const int32_t* prefix_end_index, i
   h->promotion_success_rate = promotion_success_rate; h->promotion_route_ready_hit_rate = promotion_route_ready_hit_rate;
   h->promotion_orientation_hit_rate = promotion_orientation_hit_rate; h->promotion_max_regression_rate = promotion_max_regression_rate;
   kp1_route_curriculum_state* d = nullptr;
-  if (hipMalloc((void**)&d, sizeof *d) != hipSuccess) { delete h; return fail(KP1_ERR_ALLOC, "hipMalloc failed in kp1_route_curriculum_create"); }
-  const hipError_t e = hipMemcpy(d, h, sizeof *h, hipMemcpyHostToDevice);
+  if (hipMalloc((void**)&d, sizeof *d * K) != hipSuccess) { delete h; return fail(KP1_ERR_ALLOC, "hipMalloc failed in kp1_route_curriculum_create"); }
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < K && e == hipSuccess; ++k) e = hipMemcpy(d + k, h, sizeof *h, hipMemcpyHostToDevice);
   delete h;
   if (e != hipSuccess) { (void)hipFree(d); return fail(KP1_ERR_NO_DEVICE, "hipMemcpy failed in kp1_route_curriculum_create"); }
   const int rc = kp1_route_set_window(r, 1, prefix_end_index[0]);   // _on_training_start -> _apply_stage
@@ -1063,6 +1183,9 @@ int kp1_route_curriculum_create(kp1_route* r, const int32_t* prefix_end_index, i
   *out_dev = d;
   return KP1_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int kp1_route_curriculum_destroy(kp1_route* r, kp1_route_curriculum_state* st_dev) {
   if (!r || !st_dev) return KP1_OK;
@@ -1074,6 +1197,7 @@ int kp1_route_curriculum_destroy(kp1_route* r, kp1_route_curriculum_state* st_de
 
 int kp1_route_curriculum_observe(kp1_route* r, kp1_route_curriculum_state* st_dev, const uint8_t* dones, int32_t steps_per_call, void* stream) {
   if (!r || !st_dev || !dones) return fail(KP1_ERR_INVALID, "bad argument to kp1_route_curriculum_observe");
+  if (r->n_replicas != 1) return fail(KP1_ERR_UNSUPPORTED, "a population route handle takes kp1_route_curriculum_observe_population");
   const int64_t n = r->base->n;
   hipLaunchKernelGGL(route_curriculum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, r->dev_cfg, dones, r->bytes, r->bytes + 3 * n, r->bytes + 2 * n,
                      (int)n, (int)steps_per_call);
@@ -1096,6 +1220,7 @@ int kp1_route_curriculum_observe_chunk(kp1_route* r, kp1_route_curriculum_state*
                                        int32_t world, void* stream) {
   if (!r || !st_dev || !records || n_local <= 0 || chunk_steps <= 0 || world <= 0)
     return fail(KP1_ERR_INVALID, "bad argument to kp1_route_curriculum_observe_chunk");
+  if (r->n_replicas != 1) return fail(KP1_ERR_UNSUPPORTED, "the data-parallel chunk tracker has no population form");
   hipLaunchKernelGGL(route_curriculum_chunk_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, r->dev_cfg, records, (int)n_local, (int)chunk_steps,
                      (int)world);
   HIP_TRY(kp1::launch_status());
@@ -1109,6 +1234,32 @@ int kp1_route_curriculum_read(kp1_route* r, const kp1_route_curriculum_state* st
   // promotions rewrote the window in the device copy of the route config: keep the host copy (re-uploaded by later setters) in step
   r->cfg.reset.min_route_index = 1;
   r->cfg.reset.max_route_index = out_host->prefix_end_index[out_host->stage_index];
+  r->win[0] = r->cfg.reset.min_route_index;
+  r->win[1] = r->cfg.reset.max_route_index;
+  return KP1_OK;
+}
+
+int kp1_route_curriculum_observe_population(kp1_route* r, kp1_route_curriculum_state* st_dev, const uint8_t* dones, int32_t steps_per_call, void* stream) {
+  if (!r || !st_dev || !dones) return fail(KP1_ERR_INVALID, "bad argument to kp1_route_curriculum_observe_population");
+  const int64_t n = r->base->n;
+  hipLaunchKernelGGL(route_curriculum_kernel, dim3((unsigned)r->n_replicas), dim3(64), 0, (hipStream_t)stream, st_dev, r->dev_cfg, dones, r->bytes,
+                     r->bytes + 3 * n, r->bytes + 2 * n, (int)r->n_per_replica, (int)steps_per_call);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_route_curriculum_read_replica(kp1_route* r, const kp1_route_curriculum_state* st_dev, int32_t replica, kp1_route_curriculum_state* out_host,
+                                      void* stream) {
+  if (!r || !st_dev || !out_host) return fail(KP1_ERR_INVALID, "NULL argument");
+  if (replica < 0 || replica >= r->n_replicas) return fail(KP1_ERR_INVALID, "kp1_route_curriculum_read_replica: replica out of range");
+  HIP_TRY(hipMemcpyAsync(out_host, st_dev + replica, sizeof *out_host, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  r->win[2 * replica] = 1;
+  r->win[2 * replica + 1] = out_host->prefix_end_index[out_host->stage_index];
+  if (r->n_replicas == 1) {
+    r->cfg.reset.min_route_index = 1;
+    r->cfg.reset.max_route_index = r->win[1];
+  }
   return KP1_OK;
 }
 

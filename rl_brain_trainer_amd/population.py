@@ -50,6 +50,7 @@ class ReplicaView:
         self.env = pop.envs[k]
         self.curriculum = pop.curricula[k]
         self.n_envs = pop.n_envs
+        self.obs_dim = pop.obs_dim
         self.obs_w = pop.obs_w
         self.dist = _ReplicaDist()
         self.actor_extra_steps = 0
@@ -90,21 +91,7 @@ class PopulationPPO(PPO):
     def __init__(self, seeds: list[int], cfg: PPOConfig, env_factory: Callable[[int], Any], *,
                  curriculum_factory: Callable[[int], Any] | None = None, dist: Dist | None = None, use_graphs: bool = True,
                  teacher_anchor: Any = None) -> None:
-        seeds = [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError("PopulationPPO needs at least one seed")
-        if len(seeds) > MAX_REPLICAS:
-            raise ValueError(f"PopulationPPO trains at most {MAX_REPLICAS} replicas at once (got {len(seeds)} seeds)")
-        if len(set(seeds)) != len(seeds):
-            raise ValueError(f"PopulationPPO seeds must be distinct (got {seeds}): equal seeds train identical replicas")
-        if cfg.hidden not in (64, 128):
-            raise ValueError(f"PopulationPPO runs the layer-wise kernels of the 2x64 / 2x128 nets; hidden={cfg.hidden} is not supported "
-                             "(the 2x256 tile kernels have no replica axis)")
-        if teacher_anchor is not None:
-            raise ValueError("PopulationPPO does not support the teacher-anchor side loss (per-replica actor step counts)")
-        dist = dist or Dist()
-        if dist.enabled:
-            raise ValueError("PopulationPPO is single-process: data parallel (a torch.distributed process group) is not supported")
+        seeds, dist = self._check_population_args(seeds, cfg, dist, teacher_anchor)
         envs: list[Any] = []
         try:
             for s in seeds:
@@ -120,10 +107,34 @@ class PopulationPPO(PPO):
             for e in envs:
                 e.close()
             raise
+        curricula = [curriculum_factory(s) if curriculum_factory is not None else None for s in seeds]
+        self._init_population(seeds, cfg, envs, curricula, dist, use_graphs)
+
+    @staticmethod
+    def _check_population_args(seeds: list[int], cfg: PPOConfig, dist: Dist | None, teacher_anchor: Any) -> tuple[list[int], Dist]:
+        """the refusals every population shares; returns (seeds as ints, the Dist)"""
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError("PopulationPPO needs at least one seed")
+        if len(seeds) > MAX_REPLICAS:
+            raise ValueError(f"PopulationPPO trains at most {MAX_REPLICAS} replicas at once (got {len(seeds)} seeds)")
+        if len(set(seeds)) != len(seeds):
+            raise ValueError(f"PopulationPPO seeds must be distinct (got {seeds}): equal seeds train identical replicas")
+        if cfg.hidden not in (64, 128):
+            raise ValueError(f"PopulationPPO runs the layer-wise kernels of the 2x64 / 2x128 nets; hidden={cfg.hidden} is not supported "
+                             "(the 2x256 tile kernels have no replica axis)")
+        if teacher_anchor is not None:
+            raise ValueError("PopulationPPO does not support the teacher-anchor side loss (per-replica actor step counts)")
+        dist = dist or Dist()
+        if dist.enabled:
+            raise ValueError("PopulationPPO is single-process: data parallel (a torch.distributed process group) is not supported")
+        return seeds, dist
+
+    def _init_population(self, seeds: list[int], cfg: PPOConfig, envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool) -> None:
+        """what a population holds once its K env views and trackers exist"""
         T, N, K = cfg.n_steps, envs[0].n_envs, len(seeds)
         max_steps = max(int(envs[0].config.c.termination.max_episode_steps), 1)
         self._trunc_cap = min(N * (T // max_steps + 1), T * N)
-        curricula = [curriculum_factory(s) if curriculum_factory is not None else None for s in seeds]
         # the MLP handle's max_batch holds the `_trunc_cap` rows per replica of the bootstrap's one forward
         self._setup(cfg, seeds, envs, curricula, dist, use_graphs, min_batch=self._trunc_cap, stacked=True)
         self.seeds = seeds
@@ -233,6 +244,106 @@ class PopulationPPO(PPO):
                                 normalize=cfg.normalize_advantage)
             self._mlp.adam_step(self.flat, self.grad, self.adam_m, self.adam_v, lr=cfg.learning_rate, eps=cfg.adam_eps,
                                 max_grad_norm=cfg.max_grad_norm, step=0, fused_norm=True)
+
+
+class RoutePopulationPPO(PopulationPPO):
+    """K route-curriculum runs of one PPOConfig on ONE RoutePopulationVecEnv (route_env.py): block k of its K N envs is replica k, which is the
+    rollout buffers' replica-major layout, so every env step is one route step and one tracker launch (RoutePrefixCurriculumPopulation)
+    whatever K is.  Everything else -- noise, truncation bootstrap, the epoch body, graph capture -- is PopulationPPO's.
+
+    Replica k is bit-identical to ``PPO(RouteVecEnv(..., seed=s_k), curriculum=RoutePrefixCurriculumDevice)`` on the same config
+    (tests/test_route_population_gpu.py).  ``load_init_checkpoint`` starts every replica from one checkpoint as train_route does.  The caller
+    owns (and closes) the env and the tracker."""
+
+    def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
+                 teacher_anchor: Any = None) -> None:
+        from .route_curriculum import RoutePrefixCurriculumPopulation
+        from .route_env import RoutePopulationVecEnv
+
+        seeds, dist = self._check_population_args(seeds, cfg, dist, teacher_anchor)
+        if not isinstance(env, RoutePopulationVecEnv):
+            raise TypeError("RoutePopulationPPO drives a RoutePopulationVecEnv (one handle for all replicas)")
+        if env.seeds != seeds:
+            raise ValueError(f"the RoutePopulationVecEnv was made for seeds {env.seeds}, not {seeds}")
+        if curriculum is not None and not isinstance(curriculum, RoutePrefixCurriculumPopulation):
+            raise TypeError("RoutePopulationPPO takes a RoutePrefixCurriculumPopulation (one tracker launch for all replicas)")
+        self.route_env, self.route_curriculum = env, curriculum
+        if curriculum is not None:
+            curriculum.attach(env)
+        K = len(seeds)
+        views = [env.replica(k) for k in range(K)]
+        curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs)
+
+    @staticmethod
+    def check_init_checkpoint(path: str) -> None:
+        """refuse (on the host, before any device work) a checkpoint whose Adam state carries teacher-anchor actor steps"""
+        import math
+
+        from . import checkpoint
+        from .ppo import load_adam_state, param_spec
+
+        opt = checkpoint.load_optimizer_state_dict(path)
+        if not (opt and opt.get("state")):
+            return
+        hidden, obs_dim = (int(v) for v in checkpoint.load_policy_state_dict(path)["mlp_extractor.policy_net.0.weight"].shape)
+        spec = param_spec(hidden, obs_dim)
+        n = sum(math.prod(shape) for _, shape in spec)
+        _, extra = load_adam_state(opt, spec, torch.zeros(n), torch.zeros(n))
+        if extra:
+            raise ValueError(f"{path} carries {extra} teacher-anchor actor steps (actor_extra_steps); a route population keeps one Adam step "
+                             "count for every tensor and cannot resume it")
+
+    def load_init_checkpoint(self, path: str) -> dict[str, Any]:
+        """``PPO.load_checkpoint(path, restore_timesteps=True, restore_hyperparameters=True)`` into every replica (train_route's
+        --init-checkpoint): weights, Adam moments, the Adam step count, the step clock and the saved algorithm constants; the learning rate
+        stays the config's.  A checkpoint with teacher-anchor actor steps is refused: a population has one Adam step count for every tensor."""
+        from . import checkpoint
+        from .ppo import load_adam_state, restore_saved_hyperparameters
+
+        if self.adam_t or self.n_train_calls or self._epoch_graph is not None:
+            raise RuntimeError("load_init_checkpoint must happen before the first update")
+        self.check_init_checkpoint(path)
+        sd = checkpoint.load_policy_state_dict(path)
+        for pol in self.policies:
+            pol.load_state_dict(sd)
+        restored: dict[str, Any] = {"policy": True, "optimizer": False}
+        opt = checkpoint.load_optimizer_state_dict(path)
+        if opt and opt.get("state"):
+            adam_t, _ = load_adam_state(opt, self.policies[0].spec, self.adam_m[0], self.adam_v[0])
+            self.adam_m[1:].copy_(self.adam_m[0].expand_as(self.adam_m[1:]))
+            self.adam_v[1:].copy_(self.adam_v[0].expand_as(self.adam_v[1:]))
+            self.adam_t = adam_t
+            restored.update({"optimizer": True, "adam_steps": adam_t, "actor_extra_steps": 0})
+        self._mlp.pack(self.flat)
+        self._mlp.set_step_count(self.adam_t)
+        data = checkpoint.load_data(path)
+        self.num_timesteps = int(data.get("num_timesteps", 0))
+        restored["num_timesteps"] = self.num_timesteps
+        saved_epochs = data.get("n_epochs")
+        if isinstance(data.get("_n_updates"), int) and isinstance(saved_epochs, int) and saved_epochs > 0:
+            self.n_train_calls = int(data["_n_updates"]) // saved_epochs
+        restored["hyperparameters"] = restore_saved_hyperparameters(self.cfg, data)
+        self.cfgs = [dataclasses.replace(self.cfg, seed=s) for s in self.seeds]
+        return restored
+
+    # ------------------------------------------------------------------ one launch per env step for all replicas
+    def _reset_envs(self, which: list[int] | None = None) -> None:
+        if which is None or which:
+            self.obs_buf[0].copy_(self.route_env.reset())
+
+    def _policy_env_step(self, t: int) -> None:
+        self._mlp.forward(self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t], clipped=self.clip_act,
+                          log_prob=self.logp_buf[t])
+        self.route_env.step_into(self.clip_act, self.obs_buf[t + 1], self.rew_buf[t], self.done_buf[t], self.term_obs_buf[t], True)
+
+    def _curriculum_observe(self, t: int) -> None:
+        if self.route_curriculum is not None:
+            self.route_curriculum.observe(self.done_buf[t], self.n_envs)
+
+    def _warm_curricula(self) -> None:
+        if self.route_curriculum is not None:
+            self.route_curriculum.observe(self.done_buf[0].zero_(), 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------- trainer CLI (--seeds)

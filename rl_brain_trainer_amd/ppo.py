@@ -417,6 +417,41 @@ def _bind_policy(policy: ActorCritic, flat: torch.Tensor) -> None:
         off += n
 
 
+def load_adam_state(opt: dict[str, Any], spec, adam_m: torch.Tensor, adam_v: torch.Tensor) -> tuple[int, int]:
+    """``policy.optimizer.pth`` state into the flat first / second moments; returns (common step count, extra steps of the actor tensors)"""
+    steps, off = [], 0
+    for i, (name, shape) in enumerate(spec):
+        n = math.prod(shape)
+        st = opt["state"].get(i)
+        if st is None or tuple(st["exp_avg"].shape) != tuple(shape):
+            raise ValueError(f"optimizer state of parameter {i} ({name}) does not match the policy")
+        adam_m[off:off + n].copy_(st["exp_avg"].to(adam_m.device, torch.float32).reshape(-1))
+        adam_v[off:off + n].copy_(st["exp_avg_sq"].to(adam_v.device, torch.float32).reshape(-1))
+        steps.append((name, int(float(st["step"]))))
+        off += n
+    actor = [s_ for n_, s_ in steps if n_.startswith(("mlp_extractor.policy_net", "action_net"))]
+    rest = [s_ for n_, s_ in steps if not n_.startswith(("mlp_extractor.policy_net", "action_net"))]
+    if len(set(actor)) != 1 or len(set(rest)) != 1 or actor[0] < rest[0]:
+        raise ValueError(f"unsupported per-tensor Adam step pattern {steps}")
+    return rest[0], actor[0] - rest[0]
+
+
+def restore_saved_hyperparameters(cfg: "PPOConfig", data: dict[str, Any]) -> dict[str, Any]:
+    """the algorithm constants a loaded SB3 model keeps (see PPO.load_checkpoint) into cfg; returns what was taken"""
+    taken = {}
+    for key, cast in (("gamma", float), ("gae_lambda", float), ("ent_coef", float), ("vf_coef", float), ("max_grad_norm", float),
+                      ("n_epochs", int), ("normalize_advantage", bool)):
+        v = data.get(key)
+        if isinstance(v, (int, float, bool)) and not (isinstance(v, bool) and cast is not bool):
+            setattr(cfg, key, cast(v))
+            taken[key] = cast(v)
+    clip = data.get("clip_range")
+    if isinstance(clip, dict) and isinstance(clip.get("value"), (int, float)):   # this engine's writer; SB3 pickles the schedule
+        cfg.clip_range = float(clip["value"])
+        taken["clip_range"] = cfg.clip_range
+    return taken
+
+
 class PPO:
     """One PPO run.  PopulationPPO (population.py) is the same engine with K replicas: everything per replica below is a list (``envs``,
     ``curricula``, ``policies``, ``gens``) or a replica axis (rollout columns [k N, (k + 1) N), ``perm[k]``, ``stats_dev[k]``); here K = 1."""
@@ -605,21 +640,7 @@ class PPO:
         restored: dict[str, Any] = {"policy": True, "optimizer": False}
         opt = checkpoint.load_optimizer_state_dict(path) if restore_optimizer else None
         if opt and opt.get("state"):
-            steps, off = [], 0
-            for i, (name, shape) in enumerate(self.policy.spec):
-                n = math.prod(shape)
-                st = opt["state"].get(i)
-                if st is None or tuple(st["exp_avg"].shape) != tuple(shape):
-                    raise ValueError(f"optimizer state of parameter {i} ({name}) does not match the policy")
-                self.adam_m[off:off + n].copy_(st["exp_avg"].to(self.device, torch.float32).reshape(-1))
-                self.adam_v[off:off + n].copy_(st["exp_avg_sq"].to(self.device, torch.float32).reshape(-1))
-                steps.append((name, int(float(st["step"]))))
-                off += n
-            actor = [s_ for n_, s_ in steps if n_.startswith(("mlp_extractor.policy_net", "action_net"))]
-            rest = [s_ for n_, s_ in steps if not n_.startswith(("mlp_extractor.policy_net", "action_net"))]
-            if len(set(actor)) != 1 or len(set(rest)) != 1 or actor[0] < rest[0]:
-                raise ValueError(f"unsupported per-tensor Adam step pattern {steps}")
-            self.adam_t, self.actor_extra_steps = rest[0], actor[0] - rest[0]
+            self.adam_t, self.actor_extra_steps = load_adam_state(opt, self.policy.spec, self.adam_m, self.adam_v)
             restored.update({"optimizer": True, "adam_steps": self.adam_t, "actor_extra_steps": self.actor_extra_steps})
         self._mlp.pack(self.policy.flat)
         self._mlp.set_step_count(self.adam_t)
@@ -635,18 +656,7 @@ class PPO:
             if restore_hyperparameters:
                 if self._epoch_graph is not None or self.adam_t != restored.get("adam_steps", self.adam_t):
                     raise RuntimeError("restore_hyperparameters must happen before the first update")
-                taken = {}
-                for key, cast in (("gamma", float), ("gae_lambda", float), ("ent_coef", float), ("vf_coef", float), ("max_grad_norm", float),
-                                  ("n_epochs", int), ("normalize_advantage", bool)):
-                    v = data.get(key)
-                    if isinstance(v, (int, float, bool)) and not (isinstance(v, bool) and cast is not bool):
-                        setattr(self.cfg, key, cast(v))
-                        taken[key] = cast(v)
-                clip = data.get("clip_range")
-                if isinstance(clip, dict) and isinstance(clip.get("value"), (int, float)):   # this engine's writer; SB3 pickles the schedule
-                    self.cfg.clip_range = float(clip["value"])
-                    taken["clip_range"] = self.cfg.clip_range
-                restored["hyperparameters"] = taken
+                restored["hyperparameters"] = restore_saved_hyperparameters(self.cfg, data)
         return restored
 
     # ------------------------------------------------------------------ policy evaluation
@@ -701,8 +711,7 @@ class PPO:
         cfg = self.cfg
         T, N = cfg.n_steps, self.n_envs
         if self._needs_reset:
-            for k, env in enumerate(self.envs):
-                self.obs_buf[0, self._sl(k)].copy_(env.reset())
+            self._reset_envs()
             self._needs_reset = False
         else:
             self.obs_buf[0].copy_(self.obs_buf[T])
@@ -775,10 +784,9 @@ class PPO:
                     if hasattr(env, "snapshot"):
                         env.snapshot()       # the warm-up step below must not move the episodes or the random streams
                 self._policy_env_step(0)
-                for k, cur in enumerate(self.curricula):
-                    if cur is not None:      # also loads the module the chunk form of the tracker lives in
-                        cur.observe(self.done_buf[0, self._sl(k)].zero_(), 0)
+                self._warm_curricula()
                 self._post_rollout()         # the graph's tail, once eagerly (its buffers are rewritten by the real rollout)
+                fresh = []
                 for k, env in enumerate(self.envs):
                     env.use_current_stream()
                     if hasattr(env, "snapshot"):
@@ -786,7 +794,9 @@ class PPO:
                     else:
                         # wrappers without a device snapshot (the route env keeps state of its own): start the episodes again instead, at
                         # the price of one extra reset() draw per env stream
-                        self.obs_buf[0, self._sl(k)].copy_(env.reset())
+                        fresh.append(k)
+                if fresh:
+                    self._reset_envs(fresh)
             torch.cuda.current_stream(self.device).wait_stream(side)
             self._kernels_warm = True
         torch.cuda.synchronize(self.device)
@@ -798,6 +808,18 @@ class PPO:
 
         self._rollout_graph = self._capture(body, on_begin=self._envs_use_current_stream)
         self._envs_use_current_stream()
+
+    def _reset_envs(self, which: list[int] | None = None) -> None:
+        """obs_buf[0] <- reset() of the env handles `which` (default: all), each into its replica's columns"""
+        for k in range(len(self.envs)) if which is None else which:
+            self.obs_buf[0, self._sl(k)].copy_(self.envs[k].reset())
+
+    def _warm_curricula(self) -> None:
+        """the capture warm-up's tracker launch: every tracker once on zeroed done bytes with a zero clock step (moves nothing; also loads
+        the module the chunk form of the tracker lives in)"""
+        for k, cur in enumerate(self.curricula):
+            if cur is not None:
+                cur.observe(self.done_buf[0, self._sl(k)].zero_(), 0)
 
     def _envs_use_current_stream(self) -> None:
         for env in self.envs:

@@ -21,7 +21,7 @@ import torch
 
 from . import config as kcfg
 from . import route_config as rcfg
-from .route_env import RouteVecEnv
+from .route_env import RoutePopulationVecEnv, RouteVecEnv
 
 
 @dataclass(frozen=True)
@@ -154,7 +154,9 @@ class RoutePrefixCurriculumDevice:
         return out
 
     def summary(self) -> dict[str, object]:
-        st = self.read()
+        return self._summary_of(self.read())
+
+    def _summary_of(self, st: _CurriculumState) -> dict[str, object]:
         n = int(st.ring_len)
 
         def mean(q: int) -> float:
@@ -177,6 +179,92 @@ class RoutePrefixCurriculumDevice:
         if self.env is not None and self._st.value:
             self.env.L.kp1_route_curriculum_destroy(self.env._handle, self._st)
             self._st = C.c_void_p()
+
+
+class RoutePrefixCurriculumPopulation(RoutePrefixCurriculumDevice):
+    """K device trackers, one per replica of a RoutePopulationVecEnv (include/kp1_route.h, kp1_route_curriculum_*_population).  ONE
+    ``observe(dones[K N])`` launch per env step: workgroup k scans replica k's envs in env order, advances its clock by N and on promotion moves
+    replica k's reset window only.  ``read(k)`` / ``summary(k)`` are RoutePrefixCurriculumDevice's of replica k; ``replica(k)`` is a view
+    with read() / summary() for the per-replica lists of a population run.  There is no data-parallel (chunk) form."""
+
+    needs_episode_records = False
+
+    def attach(self, env: RoutePopulationVecEnv) -> None:
+        """_on_training_start of every replica: K trackers next to the population env, every window set to the first prefix"""
+        from . import native
+
+        if not isinstance(env, RoutePopulationVecEnv):
+            raise TypeError("RoutePrefixCurriculumPopulation tracks the replicas of a RoutePopulationVecEnv")
+        self.env = env
+        L = env.L
+        vp, i32, f64 = C.c_void_p, C.c_int32, C.c_double
+        L.kp1_route_curriculum_create_population.argtypes = [vp, C.POINTER(i32), i32, f64, f64, f64, f64, i32, i32, C.POINTER(vp)]
+        L.kp1_route_curriculum_destroy.argtypes = [vp, vp]
+        L.kp1_route_curriculum_observe_population.argtypes = [vp, vp, vp, i32, vp]
+        L.kp1_route_curriculum_read_replica.argtypes = [vp, vp, i32, C.POINTER(_CurriculumState), vp]
+        prefixes = (i32 * len(self.stages))(*[int(s.prefix_end_index) for s in self.stages])
+        with torch.cuda.device(env.device):
+            native.check(L.kp1_route_curriculum_create_population(env._handle, prefixes, len(self.stages), *self._args, C.byref(self._st)))
+        env.route_cfg.reset.min_route_index, env.route_cfg.reset.max_route_index = 1, int(self.stages[0].prefix_end_index)
+        env._windows = [(1, int(self.stages[0].prefix_end_index))] * env.K
+
+    @property
+    def K(self) -> int:
+        return self.env.K
+
+    def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
+        """dones: the K N done bytes of one population step; steps_per_call: env steps per replica this call stands for (N)"""
+        from . import native
+
+        if dones.numel() != self.env.n_envs or dones.dtype != torch.uint8 or not dones.is_contiguous():
+            raise ValueError(f"observe() takes the contiguous uint8 done bytes of all {self.env.n_envs} envs of the population")
+        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        native.check(self.env.L.kp1_route_curriculum_observe_population(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), int(steps_per_call),
+                                                                        C.c_void_p(stream)))
+
+    def record(self, dones: torch.Tensor, out: torch.Tensor) -> None:
+        raise TypeError("the population tracker has no data-parallel form")
+
+    def observe_chunk(self, records_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
+        raise TypeError("the population tracker has no data-parallel form")
+
+    def read(self, k: int = 0) -> _CurriculumState:
+        from . import native
+
+        out = _CurriculumState()
+        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        native.check(self.env.L.kp1_route_curriculum_read_replica(self.env._handle, self._st, int(k), C.byref(out), C.c_void_p(stream)))
+        self.env._windows[k] = (1, int(out.prefix_end_index[out.stage_index]))
+        return out
+
+    def summary(self, k: int = 0) -> dict[str, object]:
+        return self._summary_of(self.read(k))
+
+    def replica(self, k: int) -> "RouteCurriculumReplica":
+        return RouteCurriculumReplica(self, k)
+
+
+class RouteCurriculumReplica:
+    """Replica k of a RoutePrefixCurriculumPopulation: read() / summary() of its tracker.  The population observes all replicas at once."""
+
+    def __init__(self, pop: RoutePrefixCurriculumPopulation, k: int) -> None:
+        self.pop, self.k = pop, int(k)
+        self.stages = pop.stages
+
+    def attach(self, env: Any) -> None:
+        """(the population tracker is attached to the population env)"""
+
+    def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
+        raise TypeError("replica trackers are observed through RoutePrefixCurriculumPopulation.observe (one launch for all replicas)")
+
+    def read(self) -> _CurriculumState:
+        return self.pop.read(self.k)
+
+    def summary(self) -> dict[str, object]:
+        return self.pop.summary(self.k)
+
+    def close(self) -> None:
+        """(the population tracker owns the device state)"""
 
 
 # --------------------------------------------------------------------------------------------- sequential evaluator

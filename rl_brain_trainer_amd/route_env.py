@@ -53,6 +53,10 @@ def _bind(L) -> None:
     L.kp1_route_rng_get.argtypes = [vp, vp]
     L.kp1_route_rng_set.argtypes = [vp, vp]
     L.kp1_route_config_default.argtypes = [C.POINTER(rcfg.RouteConfig)]
+    L.kp1_seed_blocks.argtypes = [vp, vp, i32, i32]
+    L.kp1_route_create_population.argtypes = [vp, C.POINTER(rcfg.RouteConfig), vp, i32, vp, i32, C.POINTER(vp)]
+    L.kp1_route_num_replicas.argtypes = [vp]
+    L.kp1_route_set_replica_window.argtypes = [vp, i32, i32, i32]
     L._kp1_route_bound = True
 
 
@@ -76,8 +80,7 @@ class RouteVecEnv:
         self.n_waypoints = int(self.route_q.shape[0])
         self._handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            native.check(self.L.kp1_route_create(self.base._handle, C.byref(route_cfg), C.c_void_p(self.route_q.ctypes.data), self.n_waypoints, int(seed),
-                                                 int(first_env_id), C.byref(self._handle)))
+            self._create(route_cfg, seed, first_env_id)
         self.obs_dim = int(self.L.kp1_route_obs_dim(self._handle))
         self.obs_stride = self.obs_dim
         n = self.n_envs
@@ -95,6 +98,10 @@ class RouteVecEnv:
         self._keep: list[Any] = []
         if reward_components:
             self.enable_reward_components(True)
+
+    def _create(self, route_cfg: rcfg.RouteConfig, seed: int, first_env_id: int) -> None:
+        native.check(self.L.kp1_route_create(self.base._handle, C.byref(route_cfg), C.c_void_p(self.route_q.ctypes.data), self.n_waypoints, int(seed),
+                                             int(first_env_id), C.byref(self._handle)))
 
     def close(self) -> None:
         if getattr(self, "_handle", None) is not None and self._handle.value:
@@ -232,3 +239,86 @@ class RouteVecEnv:
 
     def get_state(self) -> dict[str, np.ndarray]:
         return self.base.get_state()
+
+
+class RoutePopulationVecEnv(RouteVecEnv):
+    """K route envs of ``n_per_replica`` envs each in ONE handle (include/kp1_route.h, kp1_route_create_population): block k = rows
+    [k N, (k + 1) N) is replica k, and is bit for bit ``RouteVecEnv(..., n_per_replica, seed=seeds[k])``.  One ``step_into`` / ``reset``
+    covers all K N rows, so a population rollout is one route step per env step whatever K is -- the [K N, obs_w] buffers are the population
+    rollout's replica-major layout.  The config is shared except the reset window, which each replica has of its own (``set_route_window``
+    sets every window, ``set_replica_window`` one).  ``replica(k)`` is a view with what PPO's setup and ``checkpoint.save`` read."""
+
+    def __init__(self, base_config: kcfg.EnvConfig, route_cfg: rcfg.RouteConfig, route_q: np.ndarray, seeds: list[int], n_per_replica: int, *,
+                 device: int | torch.device = 0, reward_components: bool = False) -> None:
+        self.seeds = [int(s) for s in seeds]
+        if not self.seeds:
+            raise ValueError("RoutePopulationVecEnv needs at least one seed")
+        self.K = len(self.seeds)
+        self.n_per_replica = int(n_per_replica)
+        if self.n_per_replica < 1:
+            raise ValueError("n_per_replica must be positive")
+        self._windows = [(int(route_cfg.reset.min_route_index), int(route_cfg.reset.max_route_index))] * self.K
+        super().__init__(base_config, route_cfg, route_q, self.K * self.n_per_replica, device=device, seed=self.seeds[0], real="f32",
+                         reward_components=reward_components)
+
+    def _create(self, route_cfg: rcfg.RouteConfig, seed: int, first_env_id: int) -> None:
+        seeds = (C.c_uint64 * self.K)(*self.seeds)
+        native.check(self.L.kp1_route_create_population(self.base._handle, C.byref(route_cfg), C.c_void_p(self.route_q.ctypes.data), self.n_waypoints,
+                                                        C.cast(seeds, C.c_void_p), self.K, C.byref(self._handle)))
+
+    def replica(self, k: int) -> "RouteReplicaEnv":
+        return RouteReplicaEnv(self, k)
+
+    def rows(self, k: int) -> slice:
+        return slice(k * self.n_per_replica, (k + 1) * self.n_per_replica)
+
+    def set_route_window(self, *, max_route_index: int, min_route_index: int = 1) -> None:
+        super().set_route_window(max_route_index=max_route_index, min_route_index=min_route_index)
+        self._windows = [(int(min_route_index), int(max_route_index))] * self.K
+
+    def set_replica_window(self, k: int, *, max_route_index: int, min_route_index: int = 1) -> None:
+        native.check(self.L.kp1_route_set_replica_window(self._handle, int(k), int(min_route_index), int(max_route_index)))
+        self._windows[k] = (int(min_route_index), int(max_route_index))
+
+    def window(self, k: int) -> tuple[int, int]:
+        """host copy of replica k's reset window (a tracker promotion moves the device copy; RoutePrefixCurriculumPopulation.read(k) syncs it)"""
+        return self._windows[k]
+
+    def seed(self, seed: int, first_env_id: int = 0) -> None:
+        raise ValueError("a population route env keeps the per-block seeds it was created with (env i of replica k: seeds[k] + i)")
+
+
+class RouteReplicaEnv:
+    """Replica k of a RoutePopulationVecEnv: the attributes PPO's setup, ReplicaView and ``checkpoint.save`` read.  Stepping and resetting
+    go through the population handle (one launch for all replicas)."""
+
+    def __init__(self, pop: RoutePopulationVecEnv, k: int) -> None:
+        self.pop, self.k = pop, int(k)
+        self.n_envs = pop.n_per_replica
+        self.device, self.dtype, self.obs_dim, self.config = pop.device, pop.dtype, pop.obs_dim, pop.config
+        self.route_q, self.n_waypoints, self.route_progress_m = pop.route_q, pop.n_waypoints, pop.route_progress_m
+        self.seed = pop.seeds[self.k]
+        self.launch_args_version = 0
+
+    @property
+    def route_cfg(self) -> rcfg.RouteConfig:
+        cfg = rcfg.RouteConfig.from_buffer_copy(self.pop.route_cfg)
+        cfg.reset.min_route_index, cfg.reset.max_route_index = self.pop.window(self.k)
+        return cfg
+
+    @property
+    def obs_stride(self) -> int:
+        return self.pop.obs_stride
+
+    def set_obs_stride(self, stride: int) -> None:
+        if int(stride) != self.pop.obs_stride:
+            self.pop.set_obs_stride(stride)
+
+    def use_current_stream(self) -> None:
+        self.pop.use_current_stream()
+
+    def reset(self, **_: Any) -> torch.Tensor:
+        raise TypeError("a replica of a RoutePopulationVecEnv is reset through the population handle (one reset of all replicas)")
+
+    def close(self) -> None:
+        """(the population handle owns the envs)"""

@@ -10,6 +10,11 @@ sequence wrapper, 56- or 80-float observation as the YAML says); the PPO update 
     python -m rl_brain_trainer_amd.train_route --config <route yaml> --route-path <route_q_dense.json> --run-id route \
         --output-dir /tmp/route --total-timesteps 1000000 --n-envs 1024
 
+Population: ``--seeds 7,8,9,10`` trains the seeds together on one GPU (RoutePopulationPPO: one route env handle and one tracker launch
+per env step for all of them; 2x64 / 2x128 nets).  Seed s writes under ``<output-dir>/seed_<s>/`` what a ``--seed s`` run writes, and
+``population_summary.json`` names the best seed: gate accepted first, then the final sequential evaluation's longest success prefix, then
+its success rate.
+
 Data parallel: ``torchrun --nproc_per_node N -m rl_brain_trainer_amd.train_route ...`` (``--n-envs`` per rank, ``--batch-size`` the global
 minibatch).  Rank r steps the envs r * n_envs .. (r + 1) * n_envs - 1 of the single-process run; the prefix curriculum replays every rank's
 episode records in global env order (PPO._curriculum_observe), so all ranks promote together.  Rank 0 alone writes the artefacts and runs
@@ -52,7 +57,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--run-id", default="route_curriculum")
     p.add_argument("--output-dir")
     p.add_argument("--total-timesteps", type=int)
-    p.add_argument("--seed", type=int)
+    seeds = p.add_mutually_exclusive_group()
+    seeds.add_argument("--seed", type=int)
+    seeds.add_argument("--seeds", help="comma-separated seeds trained together as one population (2x64 / 2x128 nets, one GPU); seed s writes "
+                                       "the artefacts of a --seed s run under <output-dir>/seed_<s>/, plus population_summary.json")
     p.add_argument("--n-envs", type=int, default=0, help="device environments (0 = training.n_envs of the YAML)")
     p.add_argument("--n-steps", type=int, default=0, help="rollout length (0 = the YAML's n_steps)")
     p.add_argument("--batch-size", type=int, default=0, help="minibatch (0 = the YAML's batch_size)")
@@ -98,6 +106,13 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
         algo["seed"] = args.seed
     seed = int(algo.get("seed") or 0)
     n_envs = int(args.n_envs or runtime_cfg.get("n_envs", 1))     # per rank
+    if args.seeds is not None:
+        try:
+            return _main_population(args, cfg, route_cfg, route_path, route_q, prefixes, env_cfg, runtime_cfg, algo, init_checkpoint, root, n_envs,
+                                    world, device)
+        finally:
+            if own_group:
+                dist.destroy_process_group()
     env = RouteVecEnv(env_cfg, rcfg.route_config_from_dict(cfg, max_route_index=prefixes[0]), route_q, n_envs, device=device, seed=seed,
                       first_env_id=rank * n_envs)
 
@@ -145,49 +160,9 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     wall = time.time() - t0
     summary: dict[str, Any] = {}
     if rank == 0:     # the artefacts, the sequential evaluation and the gate
-        latest = root / "model_latest"
-        checkpoint.save(latest, ppo, env_cfg)
-        curriculum_summary = curriculum.summary()
-        (root / "curriculum_history.json").write_text(json.dumps(curriculum_summary, indent=2))
-
-        def policy(obs: torch.Tensor) -> torch.Tensor:
-            return ppo.predict(obs.float().contiguous(), deterministic=True)
-
-        def evaluate(*, artifact_root: Path, start_index: int, end_index: int) -> dict[str, Any]:
-            out = evaluate_sequential_route(policy=policy, cfg=cfg, route_q=route_q, artifact_root=artifact_root, start_index=start_index, end_index=end_index,
-                                            device=device)
-            return {k: v for k, v in out.items() if k not in ("rows", "chunk_metrics", "final_q")}
-
-        eval_end = min(int(curriculum_summary["prefix_end_index"]), W - 1)
-        eval_summary = evaluate(artifact_root=root / "route_eval_sequential", start_index=1, end_index=eval_end)
-        gate_summary: dict[str, Any] = {"enabled": False}
-        gate_cfg = route_cfg.get("sequential_gate", {}) or {}
-        if bool(gate_cfg.get("enabled", False)):
-            gate_summary = evaluate_route_gate(evaluate=evaluate, artifact_root=root / "route_gate", prefixes=[int(x) for x in gate_cfg.get("prefixes", [20, 40, 80, 120, 180])],
-                                               full_end_index=gate_cfg.get("full_end_index"),
-                                               min_prefix120_success_rate=float(gate_cfg.get("min_prefix120_success_rate", 0.98)),
-                                               best_full_longest_prefix=int(gate_cfg.get("best_full_longest_prefix", 170)),
-                                               full_prefix_tolerance=int(gate_cfg.get("full_prefix_tolerance", 20)), checkpoint=str(latest), config=str(args.config),
-                                               route_path=str(route_path))
-            if bool(gate_summary.get("accepted", False)):
-                src = Path(str(latest) + ".zip")
-                dst = root / "model_sequential_gate_accepted.zip"
-                if src.exists():
-                    shutil.copy2(src, dst)
-                    gate_summary["accepted_model_path"] = str(dst)
         rate = (ppo.num_timesteps - start_steps) / max(wall, 1e-9)     # all ranks' env steps over the training loop
-        summary = {
-            "schema_version": "v5.route_curriculum.training_summary.v1", "run_id": args.run_id, "route_path": str(route_path),
-            "init_checkpoint": str(init_checkpoint) if init_checkpoint else None, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "model_path": str(latest), "n_envs": n_envs * world, "device": "MI355X" if world == 1 else f"{world}x MI355X",
-            "world_size": world,
-            "curriculum_summary": curriculum_summary, "teacher_anchor_summary": anchor.summary() if anchor is not None else {"enabled": False},
-            "route_eval_sequential_summary": eval_summary, "route_gate_summary": gate_summary, "config": cfg,
-            "num_timesteps": int(ppo.num_timesteps), "wall_seconds": wall, "env_steps_per_second": rate, "env_steps_per_s": rate,
-            "observation_dim": int(ppo.obs_dim),
-        }
-        (root / "training_summary.json").write_text(json.dumps(summary, indent=2, default=str))
-        print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "model_latest": str(latest) + ".zip", "prefix_end_index": curriculum_summary["prefix_end_index"],
-                          "env_steps_per_second": summary["env_steps_per_second"]}, indent=2))
+        summary = _write_run_artifacts(args, cfg, route_cfg, route_path, route_q, env_cfg, init_checkpoint, root, ppo, curriculum.summary(),
+                                       anchor.summary() if anchor is not None else {"enabled": False}, n_envs * world, world, wall, rate, device)
     if ppo.dist.enabled:
         dist.barrier()                           # the other ranks wait for rank 0's evaluation and artefacts
         ppo.dist.close()
@@ -195,6 +170,139 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     env.close()
     if own_group:
         dist.destroy_process_group()
+    return summary
+
+
+# ------------------------------------------------------------------------------------------------------------------------ --seeds
+POPULATION_SELECTION = ("route gate accepted first, then the longest_success_prefix of the final sequential evaluation, then its success_rate")
+
+
+def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route_path: Path, route_q, prefixes: list[int], env_cfg, runtime_cfg,
+                     algo: dict[str, Any], init_checkpoint, root: Path, n_envs: int, world: int, device: int) -> dict[str, Any]:
+    """--seeds: the seeds train together as one RoutePopulationPPO; seed s writes what a --seed s run writes under root/seed_<s>/"""
+    from .population import RoutePopulationPPO, parse_seeds, population_summary
+    from .route_curriculum import RoutePrefixCurriculumPopulation
+    from .route_env import RoutePopulationVecEnv
+
+    seeds = parse_seeds(args.seeds)
+    if world > 1:
+        raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
+    hidden = checkpoint.hidden_for_run(args.hidden, init_checkpoint)
+    if hidden not in (64, 128):
+        raise ValueError(f"--seeds trains 2x64 / 2x128 nets: pass --hidden 64 or 128, or an --init-checkpoint of such a net (got a 2x{hidden} policy)")
+    if TeacherAnchorConfig(**(route_cfg.get("teacher_anchor", {}) or {})).enabled:
+        raise ValueError("--seeds does not support the teacher-anchor side loss (route.teacher_anchor.enabled): train those seeds one by one")
+    if init_checkpoint:
+        RoutePopulationPPO.check_init_checkpoint(init_checkpoint)
+    W = int(route_q.shape[0])
+    total = int(algo.get("total_timesteps", 100_000))
+    model_kwargs = {k: v for k, v in algo.items() if k not in ("total_timesteps", "n_steps", "batch_size")}
+    n_steps = int(args.n_steps or algo.get("n_steps", 2048))
+    batch = int(args.batch_size or algo.get("batch_size", 64))
+    pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=n_steps, batch_size=batch, hidden=hidden)
+    roots = {s: root / f"seed_{s}" for s in seeds}
+    for r in roots.values():
+        r.mkdir(parents=True, exist_ok=True)
+    env = RoutePopulationVecEnv(env_cfg, rcfg.route_config_from_dict(cfg, max_route_index=prefixes[0]), route_q, seeds, n_envs, device=device)
+    curriculum = RoutePrefixCurriculumPopulation.from_config(cfg, W)
+    pop = None
+    try:
+        pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=curriculum)
+        if init_checkpoint:
+            pop.load_init_checkpoint(init_checkpoint)
+            print(f"Resuming every route policy of the population from {init_checkpoint}")
+        checkpoint_freq = max(int(runtime_cfg.get("checkpoint_freq", 250_000)), 1)
+        next_checkpoint = checkpoint_freq
+        t0 = time.time()
+        start_steps, it = pop.num_timesteps, 0
+        while pop.num_timesteps - start_steps < total:
+            pop.collect_rollouts()
+            pop.train()
+            it += 1
+            if pop.num_timesteps - start_steps >= next_checkpoint:
+                for k, s in enumerate(seeds):
+                    checkpoint.save(roots[s] / "checkpoints" / f"model_{pop.num_timesteps - start_steps}_steps", pop.replica(k), env_cfg)
+                next_checkpoint += checkpoint_freq
+            if args.log_every and it % args.log_every == 0:
+                stages = [curriculum.summary(k)["prefix_end_index"] for k in range(pop.K)]
+                print(f"[route-population] it={it} steps/replica={pop.num_timesteps} aggregate fps="
+                      f"{pop.K * (pop.num_timesteps - start_steps) / (time.time() - t0):,.0f} prefixes={stages}", flush=True)
+        torch.cuda.synchronize()
+        wall = time.time() - t0
+        rate = (pop.num_timesteps - start_steps) / max(wall, 1e-9)     # env steps of one replica per second of the population's training loop
+        rows = []
+        for k, s in enumerate(seeds):   # the sequential evaluations and gates run one seed after another, as single runs do
+            summary = _write_run_artifacts(args, cfg, route_cfg, route_path, route_q, env_cfg, init_checkpoint, roots[s], pop.replica(k),
+                                           curriculum.summary(k), {"enabled": False}, n_envs, 1, wall, rate, device)
+            ev, gate = summary["route_eval_sequential_summary"], summary["route_gate_summary"]
+            accepted = bool(gate.get("accepted", False))
+            score = [int(accepted), int(ev.get("longest_success_prefix", 0) or 0), float(ev.get("success_rate", 0.0) or 0.0)]
+            rows.append({"seed": s, "prefix_end_index": summary["curriculum_summary"]["prefix_end_index"], "gate_accepted": accepted,
+                         "longest_success_prefix": score[1], "success_rate": score[2], "best_score": score,
+                         "model_path": str(roots[s] / "model_latest.zip"), "evaluation_wall_seconds": summary["evaluation_wall_seconds"],
+                         "last_stats": pop.replica_stats(k)})
+        out = population_summary(pop, rows, wall_seconds=wall, selection=POPULATION_SELECTION)
+        out["aggregate_env_steps_per_second"] = pop.K * rate     # the steps of this run, not the init checkpoint's clock
+        (root / "population_summary.json").write_text(json.dumps(out, indent=2, default=str))
+        print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "seeds": seeds, "best_seed": out["best_seed"],
+                          "aggregate_env_steps_per_second": out["aggregate_env_steps_per_second"]}, indent=2))
+        return out
+    finally:
+        if pop is not None:
+            pop.close()
+        curriculum.close()
+        env.close()
+
+
+def _write_run_artifacts(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route_path: Path, route_q, env_cfg, init_checkpoint, root: Path, ppo,
+                         curriculum_summary: dict[str, Any], anchor_summary: dict[str, Any], n_envs_total: int, world: int, wall: float, rate: float,
+                         device: int) -> dict[str, Any]:
+    """What a run leaves under `root` once training ends: model_latest.zip, curriculum_history.json, the sequential evaluation of the
+    reached prefix, the gate (and model_sequential_gate_accepted.zip) and training_summary.json.  `ppo` is a PPO or a population replica."""
+    W = int(route_q.shape[0])
+    latest = root / "model_latest"
+    checkpoint.save(latest, ppo, env_cfg)
+    (root / "curriculum_history.json").write_text(json.dumps(curriculum_summary, indent=2))
+
+    def policy(obs: torch.Tensor) -> torch.Tensor:
+        return ppo.predict(obs.float().contiguous(), deterministic=True)
+
+    def evaluate(*, artifact_root: Path, start_index: int, end_index: int) -> dict[str, Any]:
+        out = evaluate_sequential_route(policy=policy, cfg=cfg, route_q=route_q, artifact_root=artifact_root, start_index=start_index, end_index=end_index,
+                                        device=device)
+        return {k: v for k, v in out.items() if k not in ("rows", "chunk_metrics", "final_q")}
+
+    eval_end = min(int(curriculum_summary["prefix_end_index"]), W - 1)
+    t_eval = time.time()
+    eval_summary = evaluate(artifact_root=root / "route_eval_sequential", start_index=1, end_index=eval_end)
+    gate_summary: dict[str, Any] = {"enabled": False}
+    gate_cfg = route_cfg.get("sequential_gate", {}) or {}
+    if bool(gate_cfg.get("enabled", False)):
+        gate_summary = evaluate_route_gate(evaluate=evaluate, artifact_root=root / "route_gate", prefixes=[int(x) for x in gate_cfg.get("prefixes", [20, 40, 80, 120, 180])],
+                                           full_end_index=gate_cfg.get("full_end_index"),
+                                           min_prefix120_success_rate=float(gate_cfg.get("min_prefix120_success_rate", 0.98)),
+                                           best_full_longest_prefix=int(gate_cfg.get("best_full_longest_prefix", 170)),
+                                           full_prefix_tolerance=int(gate_cfg.get("full_prefix_tolerance", 20)), checkpoint=str(latest), config=str(args.config),
+                                           route_path=str(route_path))
+        if bool(gate_summary.get("accepted", False)):
+            src = Path(str(latest) + ".zip")
+            dst = root / "model_sequential_gate_accepted.zip"
+            if src.exists():
+                shutil.copy2(src, dst)
+                gate_summary["accepted_model_path"] = str(dst)
+    summary = {
+        "schema_version": "v5.route_curriculum.training_summary.v1", "run_id": args.run_id, "route_path": str(route_path),
+        "init_checkpoint": str(init_checkpoint) if init_checkpoint else None, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "model_path": str(latest), "n_envs": n_envs_total, "device": "MI355X" if world == 1 else f"{world}x MI355X",
+        "world_size": world,
+        "curriculum_summary": curriculum_summary, "teacher_anchor_summary": anchor_summary,
+        "route_eval_sequential_summary": eval_summary, "route_gate_summary": gate_summary, "config": cfg,
+        "num_timesteps": int(ppo.num_timesteps), "wall_seconds": wall, "env_steps_per_second": rate, "env_steps_per_s": rate,
+        "observation_dim": int(ppo.obs_dim),
+    }
+    summary["evaluation_wall_seconds"] = time.time() - t_eval   # the sequential evaluation and the gate, after training
+    (root / "training_summary.json").write_text(json.dumps(summary, indent=2, default=str))
+    print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "model_latest": str(latest) + ".zip", "prefix_end_index": curriculum_summary["prefix_end_index"],
+                      "env_steps_per_second": summary["env_steps_per_second"]}, indent=2))
     return summary
 
 

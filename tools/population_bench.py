@@ -7,6 +7,12 @@ iteration (device-synchronised, captured graphs), aggregate env-steps/s over all
 optimiser-step kernels KP1_MLP_OPT_PROFILE times on this path (grad_finalize, adam) from one eager update.
 
     python tools/population_bench.py [--ks 1,2,4,8] [--iters 3] [--out profiles/r04_population_refscale.json]
+
+--route: the route reference-scale iteration instead -- route_curriculum_prefix120_routeobs_sequence2 on tests/golden/synthetic_route.json,
+16 envs x 1024 steps, minibatch 512, 2x64, graphs on -- as a RoutePopulationPPO: one route env handle of K x 16 envs and one tracker launch
+per env step for all replicas (K in {1, 2, 4, 8, 16} by default).
+
+    python tools/population_bench.py --route [--ks 1,2,4,8,16] [--out profiles/r05_route_population_refscale.json]
 """
 from __future__ import annotations
 
@@ -16,7 +22,8 @@ import sys
 import time
 from pathlib import Path
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
 
 import torch  # noqa: E402
 
@@ -27,7 +34,7 @@ from rl_brain_trainer_amd.ppo import PPOConfig  # noqa: E402
 from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv  # noqa: E402
 
 
-def build(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool) -> PopulationPPO:
+def build_approach(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool) -> PopulationPPO:
     cfg = kcfg.load_workspace_expansion_config(kcfg.builtin_config_dir() / "workspace_expansion_bigtrain.yaml")
     env_cfg = kcfg.to_env_config(cfg)
     cur = cfg["env"].get("curriculum", {})
@@ -44,7 +51,37 @@ def build(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs
                          use_graphs=use_graphs)
 
 
+ROUTE_CONFIG = ROOT / "tests" / "golden" / "configs" / "route_curriculum_prefix120_routeobs_sequence2.json"
+ROUTE_PATH = ROOT / "tests" / "golden" / "synthetic_route.json"
+
+
+def build_route(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool) -> PopulationPPO:
+    from rl_brain_trainer_amd import route_config as rcfg
+    from rl_brain_trainer_amd.population import RoutePopulationPPO
+    from rl_brain_trainer_amd.route_curriculum import RoutePrefixCurriculumPopulation
+    from rl_brain_trainer_amd.route_env import RoutePopulationVecEnv
+
+    cfg = json.loads(ROUTE_CONFIG.read_text())
+    route_q = rcfg.load_route_q(ROUTE_PATH)
+    prefixes = rcfg.prefix_stages(cfg, int(route_q.shape[0]))
+    algo = {k: v for k, v in kcfg.to_algorithm_kwargs(cfg, "ppo").items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
+    pcfg = PPOConfig.from_algo_kwargs(algo, n_steps=n_steps, batch_size=batch, hidden=hidden)
+    seeds = list(range(7, 7 + K))
+    env = RoutePopulationVecEnv(kcfg.to_env_config(cfg), rcfg.route_config_from_dict(cfg, max_route_index=prefixes[0]), route_q, seeds, n_envs)
+    cur = RoutePrefixCurriculumPopulation.from_config(cfg, int(route_q.shape[0]))
+    pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=cur, use_graphs=use_graphs)
+    pop._bench_owned = [cur, env]     # closed after the population (the caller owns a route population's env and tracker)
+    return pop
+
+
+def _close(pop) -> None:
+    pop.close()
+    for obj in getattr(pop, "_bench_owned", []):
+        obj.close()
+
+
 def measure(K: int, args) -> dict:
+    build = build_route if args.route else build_approach
     pop = build(K, args.n_envs, args.n_steps, args.batch, args.hidden, True)
     pop.collect_rollouts()
     pop.train()      # warm-up: captures both graphs
@@ -62,7 +99,7 @@ def measure(K: int, args) -> dict:
         up.append(t2 - t1)
     rollout_ms, update_ms = 1e3 * sum(ro) / len(ro), 1e3 * sum(up) / len(up)
     steps = K * args.n_envs * args.n_steps
-    pop.close()
+    _close(pop)
     # per-kernel durations from one eager update with event pairs on the launches
     eager = build(K, args.n_envs, args.n_steps, args.batch, args.hidden, False)
     eager.collect_rollouts()
@@ -71,21 +108,24 @@ def measure(K: int, args) -> dict:
     eager.train()
     prof = {k: v for k, v in eager._mlp.profile_read().items() if v["launches"] > 0}
     eager._mlp.set_profile(False)
-    eager.close()
+    _close(eager)
     return {"K": K, "rollout_ms": rollout_ms, "update_ms": update_ms, "iteration_ms": rollout_ms + update_ms,
             "aggregate_env_steps_per_s": steps / ((rollout_ms + update_ms) * 1e-3), "env_steps_per_iteration": steps, "kernel_us_in_situ": prof}
 
 
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--ks", default="1,2,4,8")
+    ap.add_argument("--route", action="store_true", help="the route reference-scale iteration (RoutePopulationPPO)")
+    ap.add_argument("--ks", default="")
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--n-envs", type=int, default=16)
     ap.add_argument("--n-steps", type=int, default=1024)
-    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--batch", type=int, default=0, help="minibatch (0 = 256, or 512 with --route)")
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    args.ks = args.ks or ("1,2,4,8,16" if args.route else "1,2,4,8")
+    args.batch = args.batch or (512 if args.route else 256)
     rows = []
     for K in (int(k) for k in args.ks.split(",")):
         rows.append(measure(K, args))
@@ -93,7 +133,9 @@ def main() -> None:
     base = rows[0]["aggregate_env_steps_per_s"]
     for r in rows:
         r["aggregate_vs_first"] = r["aggregate_env_steps_per_s"] / base
-    result = {"workload": f"workspace_expansion_bigtrain.yaml Approach iteration, {args.n_envs} envs x {args.n_steps} steps per replica, "
+    workload = (f"route_curriculum_prefix120_routeobs_sequence2 on synthetic_route.json (RoutePopulationPPO: one route env handle of K x {args.n_envs} envs)"
+                if args.route else "workspace_expansion_bigtrain.yaml Approach iteration")
+    result = {"workload": f"{workload}, {args.n_envs} envs x {args.n_steps} steps per replica, "
                           f"minibatch {args.batch}, 2x{args.hidden}, curriculum on; seeds 7..7+K-1", "device": torch.cuda.get_device_name(0), "rows": rows}
     if args.out:
         Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
