@@ -91,6 +91,25 @@ int kp1_curriculum_read(int32_t device, const kp1_curriculum_state* st_dev, kp1_
 /* make kp1_step take its curriculum stage from *stage_dev (e.g. &tracker->stage_index) instead of kp1_set_stage */
 int kp1_bind_stage_ptr(kp1_env* env, const int32_t* stage_dev);
 
+/* Population of K trackers for a population env handle (block k = envs [k N, (k + 1) N) is replica k): K contiguous states, tracker k
+ * starting on initial_stages[k] (host memory; clipped like kp1_curriculum_create's); the other settings are shared.  Free with
+ * kp1_curriculum_destroy.  1 <= K <= KP1_CURRICULUM_MAX_REPLICAS. */
+#define KP1_CURRICULUM_MAX_REPLICAS 16
+int kp1_curriculum_create_population(int32_t device, int32_t n_replicas, double success_rate_threshold, int32_t window_episodes,
+                                     int32_t min_episodes_per_stage, int32_t max_stage_index, const int32_t* initial_stages,
+                                     kp1_curriculum_state** out_dev);
+/* ONE launch of K one-wave workgroups: workgroup k replays dones[k N, (k + 1) N) into tracker k by kp1_curriculum_observe's rule (its
+ * no-episode-ended early-out included); every clock advances by steps_per_call.  There is no data-parallel (chunk) form. */
+int kp1_curriculum_observe_population(int32_t device, kp1_curriculum_state* states_dev, const uint8_t* dones, int32_t n_per_replica,
+                                      int32_t n_replicas, int32_t steps_per_call, void* stream);
+/* kp1_curriculum_read of tracker k of a population of n_replicas */
+int kp1_curriculum_read_replica(int32_t device, const kp1_curriculum_state* states_dev, int32_t n_replicas, int32_t k,
+                                kp1_curriculum_state* out_host, void* stream);
+/* Population env handle: from now on env i of kp1_step's auto-reset takes its stage from states_dev[i / (N / n_replicas)].stage_index
+ * (one launch of the population form of the step kernel for all K replicas); kp1_reset keeps the handle's host stage.  Needs
+ * N % n_replicas == 0, the approach mode and the f32 handle; the fused policy + env step refuses a bound handle.  states_dev NULL unbinds. */
+int kp1_bind_population_stages(kp1_env* env, const kp1_curriculum_state* states_dev, int32_t n_replicas);
+
 /* ---- device-resident DockReverseCurriculumCallback (kinematic_phase1/training/callbacks.py:104-212) -------------
  * The Finisher's reverse curriculum: after every VecEnv step the callback scans (done, info["success"]) in env order, keeps the last
  * `window_episodes` success bits and, when the current stage has seen `min_episodes` episodes and the newest `stage window` of them reach

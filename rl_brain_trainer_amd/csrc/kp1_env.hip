@@ -15,6 +15,7 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/kp1_ppo.h"
@@ -30,7 +31,8 @@ namespace {
 
 #include "kp1_env_step.inc"
 
-template <typename R, int MODE, bool COMPS>
+// POP (f32 approach only): a population handle, env i auto-resets on the stage of tracker i / n_per_replica (kp1_bind_population_stages)
+template <typename R, int MODE, bool COMPS, bool POP>
 __global__ void __launch_bounds__(256, 1) kp1_step_kernel(const StepArgs<R> a) {
   extern __shared__ float obs_tiles[];   // OBS_TILE_FLOATS per wave of the workgroup
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -39,7 +41,7 @@ __global__ void __launch_bounds__(256, 1) kp1_step_kernel(const StepArgs<R> a) {
 #endif
   const bool live = i < a.st.n;
   float o[KP1_OBS_DIM];
-  if (live) step_env_lane<R, MODE, COMPS>(a, i, a.actions + i * NJ, o);
+  if (live) step_env_lane<R, MODE, COMPS, POP>(a, i, a.actions + i * NJ, o);
   const int64_t i0 = i - (int64_t)(threadIdx.x & 63u);
   const int64_t left = a.st.n - i0;
   store_obs_tile(a.obs, i0, left >= 64 ? 64 : (left > 0 ? (int)left : 0), o, live, a.obs_stride, obs_tiles + (threadIdx.x >> 6) * OBS_TILE_FLOATS);
@@ -439,6 +441,8 @@ struct kp1_env {
   kp1_dock_curriculum_state* dock_tracker = nullptr;   // device tracker attached by kp1_dock_curriculum_create (its stage survives upload_cfg)
   double* opt_scratch = nullptr;  // 4*[N][7] + [N][6] doubles for explicit reset options / set_state
   const int32_t* stage_ptr = nullptr;  // kp1_bind_stage_ptr
+  const kp1_curriculum_state* pop_states = nullptr;   // kp1_bind_population_stages: K trackers, env i on tracker i / (n / pop_replicas)
+  int32_t pop_replicas = 0;
   int32_t obs_stride = KP1_OBS_DIM;    // kp1_set_obs_stride
   void* comps = nullptr;          // R[64][N] when enabled
   bool comps_enabled = false;
@@ -524,6 +528,8 @@ StepArgs<R> make_step_args(kp1_env* e, const void* actions, float* obs, void* re
   a.stage_index = e->stage;
   a.obs_stride = e->obs_stride;
   a.stage_ptr = e->cfg.curriculum_enabled ? e->stage_ptr : nullptr;
+  a.pop_states = e->pop_states;
+  a.n_per_replica = e->pop_replicas > 0 ? e->n / e->pop_replicas : 0;
   return a;
 }
 
@@ -534,12 +540,27 @@ int launch_step(kp1_env* e, const void* actions, float* obs, void* reward, uint8
   const dim3 grid((unsigned)((e->n + block - 1) / block));
   const bool comps = e->comps_enabled && e->comps;
   const size_t lds = sizeof(float) * OBS_TILE_FLOATS * (size_t)(block / 64);   // one observation tile per wave (store_obs_tile)
+  if (e->pop_states) {
+    // per-replica stages: only the f32 approach form exists (kp1_bind_population_stages checks type and mode; kp1_set_mode may change the
+    // mode later).  Without curriculum stages the stage is never read, and the ordinary form below does the same work.
+    if (e->mode != KP1_MODE_APPROACH) return fail(KP1_ERR_UNSUPPORTED, "a population env handle steps in the approach mode only");
+    if constexpr (std::is_same<R, float>::value) {
+      if (e->cfg.curriculum_enabled) {
+        if (comps) hipLaunchKernelGGL((kp1_step_kernel<float, KP1_MODE_APPROACH, true, true>), grid, dim3(block), lds, e->stream, a);
+        else hipLaunchKernelGGL((kp1_step_kernel<float, KP1_MODE_APPROACH, false, true>), grid, dim3(block), lds, e->stream, a);
+        HIP_TRY(kp1::launch_status());
+        return KP1_OK;
+      }
+    } else {
+      return fail(KP1_ERR_UNSUPPORTED, "a population env handle is f32");
+    }
+  }
   if (e->mode == KP1_MODE_DOCK) {
-    if (comps) hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_DOCK, true>), grid, dim3(block), lds, e->stream, a);
-    else hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_DOCK, false>), grid, dim3(block), lds, e->stream, a);
+    if (comps) hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_DOCK, true, false>), grid, dim3(block), lds, e->stream, a);
+    else hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_DOCK, false, false>), grid, dim3(block), lds, e->stream, a);
   } else {
-    if (comps) hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_APPROACH, true>), grid, dim3(block), lds, e->stream, a);
-    else hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_APPROACH, false>), grid, dim3(block), lds, e->stream, a);
+    if (comps) hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_APPROACH, true, false>), grid, dim3(block), lds, e->stream, a);
+    else hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_APPROACH, false, false>), grid, dim3(block), lds, e->stream, a);
   }
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
@@ -654,6 +675,7 @@ int env_step_args_f32(kp1_env* e, void* out, size_t out_bytes, const void* actio
   if (!e || !out) return fail(KP1_ERR_INVALID, "NULL argument");
   if (e->real_type != KP1_REAL_F32) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step runs on the fp32 handle");
   if (e->comps_enabled && e->comps) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step does not record reward components");
+  if (e->pop_states) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step has no per-replica stage (population env handle)");
   if (out_bytes != sizeof(StepArgs<float>)) return fail(KP1_ERR_INVALID, "StepArgs<float> layout mismatch between translation units");
   const StepArgs<float> a = make_step_args<float>(e, actions, obs, reward, done, terminal_obs, auto_reset);
   std::memcpy(out, &a, sizeof a);
@@ -768,6 +790,22 @@ int kp1_set_stage(kp1_env* e, int32_t stage_index) {
 int kp1_bind_stage_ptr(kp1_env* e, const int32_t* stage_dev) {
   if (!e) return fail(KP1_ERR_INVALID, "env is NULL");
   e->stage_ptr = stage_dev;
+  return KP1_OK;
+}
+int kp1_bind_population_stages(kp1_env* e, const kp1_curriculum_state* states_dev, int32_t n_replicas) {
+  if (!e) return fail(KP1_ERR_INVALID, "env is NULL");
+  if (!states_dev) {
+    e->pop_states = nullptr;
+    e->pop_replicas = 0;
+    return KP1_OK;
+  }
+  if (n_replicas < 1 || e->n % n_replicas != 0)
+    return fail(KP1_ERR_INVALID, "kp1_bind_population_stages: the env count must be a multiple of the replica count");
+  if (e->real_type != KP1_REAL_F32) return fail(KP1_ERR_UNSUPPORTED, "kp1_bind_population_stages: a population env handle is f32");
+  if (e->cfg.env.mode != KP1_MODE_APPROACH || e->mode != KP1_MODE_APPROACH)
+    return fail(KP1_ERR_UNSUPPORTED, "kp1_bind_population_stages: a population env handle runs the approach mode");
+  e->pop_states = states_dev;
+  e->pop_replicas = n_replicas;
   return KP1_OK;
 }
 int kp1_set_stream(kp1_env* e, void* stream) {

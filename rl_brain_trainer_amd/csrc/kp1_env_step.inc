@@ -314,6 +314,10 @@ struct StepArgs {
   int stage_index;
   int obs_stride;
   const int32_t* stage_ptr;  // device-resident curriculum stage (kp1_bind_stage_ptr) or nullptr
+  // population handle (kp1_bind_population_stages): env i resets on the stage of tracker i / n_per_replica.  Read only by the POP kernels;
+  // appended so the fields above keep their kernarg offsets
+  const kp1_curriculum_state* pop_states;
+  int n_per_replica;
 };
 
 // One env step of lane i, auto-reset of a finished env included (VecEnv semantics).
@@ -325,7 +329,9 @@ struct StepArgs {
 // `act_src`: this env's 7 action values (a.actions + 7 i in kp1_step_kernel; the rollout kernel hands them over through LDS).
 // `o`: the observation row after the step (after the reset, for a finished env under auto-reset) -- left to the caller, whose whole wave
 // stores its rows together (store_obs_tile).
-template <typename R, int MODE, bool COMPS>
+// POP: a population handle, whose env i takes its auto-reset stage from its own replica's tracker (a replica boundary can fall inside a wave,
+// so the stage is a per-lane load).
+template <typename R, int MODE, bool COMPS, bool POP = false>
 __device__ __forceinline__ void step_env_lane(const StepArgs<R>& a, const int64_t i, const R* __restrict__ act_src, float* __restrict__ o) {
   const int64_t n = a.st.n;
   KP1_ETR(0)
@@ -476,7 +482,8 @@ __device__ __forceinline__ void step_env_lane(const StepArgs<R>& a, const int64_
     ResetOptsDev none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     int stage = a.stage_index;
     const DevSampler& smp = uniform_block(a.smp);
-    if (a.stage_ptr) stage = kp_clipi(*a.stage_ptr, 0, kp_maxi(smp.n_stages - 1, 0));
+    if constexpr (POP) stage = kp_clipi(a.pop_states[(uint32_t)i / (uint32_t)a.n_per_replica].stage_index, 0, kp_maxi(smp.n_stages - 1, 0));
+    else if (a.stage_ptr) stage = kp_clipi(*a.stage_ptr, 0, kp_maxi(smp.n_stages - 1, 0));
     reset_env<R, MODE>(st, cfg, smp, a.handoff, none, stage, i, o);
     // info of the finished episode stays readable (SB3 infos[i] of a done env is the terminal info)
     st.r(F_POS_ERR, i) = curr_pos;

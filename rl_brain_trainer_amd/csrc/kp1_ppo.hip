@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <vector>
 
 #include "../../include/kp1_ppo.h"
 #include "kp1_host.hpp"
@@ -349,6 +350,46 @@ __global__ void __launch_bounds__(64) curriculum_chunk_kernel(kp1_curriculum_sta
   tracker_store(st, ring, c);
 }
 
+// K trackers in one launch (kp1_curriculum_observe_population): workgroup k is curriculum_kernel on tracker k and the done bytes
+// [k n, (k + 1) n) of its replica, early-out included.  (curriculum_kernel keeps its own copy of the early-out: the single tracker runs
+// the benchmark's rollout, and its code stays as it was.)
+__global__ void __launch_bounds__(64) curriculum_population_kernel(kp1_curriculum_state* __restrict__ states, const uint8_t* __restrict__ dones_all,
+                                                                   int n, int steps_per_call) {
+  __shared__ int ring[KP1_CURRICULUM_MAX_WINDOW];
+  __shared__ uint8_t sbit[TRK_BLOCK];
+  __shared__ uint16_t pfx[TRK_BLOCK + KP1_CURRICULUM_MAX_WINDOW + 1];
+  const TrackerScratch ws = {sbit, pfx};
+  kp1_curriculum_state* __restrict__ st = states + blockIdx.x;
+  const uint8_t* __restrict__ dones = dones_all + (int64_t)blockIdx.x * n;
+  {
+    const int lane = threadIdx.x;
+    bool any = false;
+    for (int base = 0; base < n; base += 64 * 64) {
+      const int first = base + lane * 64;
+      if (first + 64 <= n && (reinterpret_cast<uintptr_t>(dones + first) & 15) == 0) {
+        const uint4* p = reinterpret_cast<const uint4*>(dones + first);
+        unsigned int acc = 0u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint4 w = p[q];
+          acc |= w.x | w.y | w.z | w.w;
+        }
+        any |= (acc & (0x01010101u * (unsigned)(KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED))) != 0u;
+      } else {
+        for (int b = 0; b < 64 && first + b < n; ++b) any |= (dones[first + b] & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) != 0;
+      }
+    }
+    if (__ballot(any) == 0ull) {
+      if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&st->num_timesteps), (unsigned long long)(long long)steps_per_call);
+      return;
+    }
+  }
+  TrackerCtx c;
+  tracker_load(st, ring, c);
+  curriculum_scan(st, ring, c, ws, dones, n, steps_per_call);
+  tracker_store(st, ring, c);
+}
+
 int check_device(int device) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(KP1_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
@@ -490,21 +531,31 @@ int kp1_bootstrap_truncated(int32_t device, float* rewards, const float* termina
 
 int kp1_curriculum_create(int32_t device, double success_rate_threshold, int32_t window_episodes, int32_t min_episodes_per_stage,
                           int32_t max_stage_index, int32_t initial_stage_index, kp1_curriculum_state** out_dev) {
-  if (!out_dev) return fail(KP1_ERR_INVALID, "out_dev is NULL");
+  return kp1_curriculum_create_population(device, 1, success_rate_threshold, window_episodes, min_episodes_per_stage, max_stage_index,
+                                          &initial_stage_index, out_dev);
+}
+int kp1_curriculum_create_population(int32_t device, int32_t n_replicas, double success_rate_threshold, int32_t window_episodes,
+                                     int32_t min_episodes_per_stage, int32_t max_stage_index, const int32_t* initial_stages,
+                                     kp1_curriculum_state** out_dev) {
+  if (!out_dev || !initial_stages) return fail(KP1_ERR_INVALID, "NULL argument");
+  if (n_replicas < 1 || n_replicas > KP1_CURRICULUM_MAX_REPLICAS) return fail(KP1_ERR_INVALID, "n_replicas must be in [1, KP1_CURRICULUM_MAX_REPLICAS]");
   int rc = check_device(device);
   if (rc != KP1_OK) return rc;
-  kp1_curriculum_state h;
-  std::memset(&h, 0, sizeof h);
-  h.success_rate_threshold = success_rate_threshold;
-  h.window_episodes = window_episodes < 1 ? 1 : window_episodes;  // callbacks.py:45-47 max(..., 1)
-  if (h.window_episodes > KP1_CURRICULUM_MAX_WINDOW) return fail(KP1_ERR_INVALID, "window_episodes exceeds KP1_CURRICULUM_MAX_WINDOW");
-  h.min_episodes_per_stage = min_episodes_per_stage < 1 ? 1 : min_episodes_per_stage;
-  h.max_stage_index = max_stage_index < 0 ? 0 : max_stage_index;
-  int init = initial_stage_index < h.max_stage_index ? initial_stage_index : h.max_stage_index;
-  h.stage_index = init < 0 ? 0 : init;  // callbacks.py:48
+  std::vector<kp1_curriculum_state> h((size_t)n_replicas);
+  for (int k = 0; k < n_replicas; ++k) {
+    kp1_curriculum_state& s = h[(size_t)k];
+    std::memset(&s, 0, sizeof s);
+    s.success_rate_threshold = success_rate_threshold;
+    s.window_episodes = window_episodes < 1 ? 1 : window_episodes;  // callbacks.py:45-47 max(..., 1)
+    if (s.window_episodes > KP1_CURRICULUM_MAX_WINDOW) return fail(KP1_ERR_INVALID, "window_episodes exceeds KP1_CURRICULUM_MAX_WINDOW");
+    s.min_episodes_per_stage = min_episodes_per_stage < 1 ? 1 : min_episodes_per_stage;
+    s.max_stage_index = max_stage_index < 0 ? 0 : max_stage_index;
+    int init = initial_stages[k] < s.max_stage_index ? initial_stages[k] : s.max_stage_index;
+    s.stage_index = init < 0 ? 0 : init;  // callbacks.py:48
+  }
   kp1_curriculum_state* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, sizeof h));
-  HIP_TRY(hipMemcpy(d, &h, sizeof h, hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc((void**)&d, sizeof(kp1_curriculum_state) * h.size()));
+  HIP_TRY(hipMemcpy(d, h.data(), sizeof(kp1_curriculum_state) * h.size(), hipMemcpyHostToDevice));
   *out_dev = d;
   return KP1_OK;
 }
@@ -530,6 +581,23 @@ int kp1_curriculum_observe_chunk(int32_t device, kp1_curriculum_state* st_dev, c
   hipLaunchKernelGGL(curriculum_chunk_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, dones, n_local, chunk_steps, world, n_local * world);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
+}
+int kp1_curriculum_observe_population(int32_t device, kp1_curriculum_state* states_dev, const uint8_t* dones, int32_t n_per_replica,
+                                      int32_t n_replicas, int32_t steps_per_call, void* stream) {
+  if (!states_dev || !dones || n_per_replica <= 0 || n_replicas < 1 || n_replicas > KP1_CURRICULUM_MAX_REPLICAS)
+    return fail(KP1_ERR_INVALID, "bad argument to kp1_curriculum_observe_population");
+  int rc = check_device(device);
+  if (rc != KP1_OK) return rc;
+  hipLaunchKernelGGL(curriculum_population_kernel, dim3((unsigned)n_replicas), dim3(64), 0, (hipStream_t)stream, states_dev, dones, n_per_replica,
+                     steps_per_call);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+int kp1_curriculum_read_replica(int32_t device, const kp1_curriculum_state* states_dev, int32_t n_replicas, int32_t k, kp1_curriculum_state* out_host,
+                                void* stream) {
+  if (!states_dev || !out_host) return fail(KP1_ERR_INVALID, "NULL argument");
+  if (k < 0 || k >= n_replicas) return fail(KP1_ERR_INVALID, "replica index out of range");
+  return kp1_curriculum_read(device, states_dev + k, out_host, stream);
 }
 int kp1_curriculum_read(int32_t device, const kp1_curriculum_state* st_dev, kp1_curriculum_state* out_host, void* stream) {
   if (!st_dev || !out_host) return fail(KP1_ERR_INVALID, "NULL argument");

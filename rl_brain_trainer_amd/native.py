@@ -104,6 +104,11 @@ def load() -> C.CDLL:
     L.kp1_curriculum_observe_chunk.argtypes = [i32, vp, vp, i32, i32, i32, vp]
     L.kp1_curriculum_read.argtypes = [i32, vp, vp, vp]
     L.kp1_bind_stage_ptr.argtypes = [vp, vp]
+    L.kp1_curriculum_create_population.argtypes = [i32, i32, C.c_double, i32, i32, i32, vp, C.POINTER(vp)]
+    L.kp1_curriculum_observe_population.argtypes = [i32, vp, vp, i32, i32, i32, vp]
+    L.kp1_curriculum_read_replica.argtypes = [i32, vp, i32, i32, vp, vp]
+    L.kp1_bind_population_stages.argtypes = [vp, vp, i32]
+    L.kp1_seed_blocks.argtypes = [vp, vp, i32, i32]
     L.kp1_set_obs_stride.argtypes = [vp, i32]
     if L.kp1_config_size() != C.sizeof(kcfg.Kp1Config):
         raise Kp1Error(f"kp1_config layout mismatch: library {L.kp1_config_size()} vs binding {C.sizeof(kcfg.Kp1Config)}")

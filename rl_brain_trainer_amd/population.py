@@ -14,6 +14,9 @@ Replica k of a population is bit-identical to ``PPO(seed=s_k)`` on the same conf
 * a replica's minibatch index p in [0, T N) maps to the global row t K N + k N + n; the kernels keep each replica's reduction order and
   chunking (the per-replica minibatch geometry is a single run's), and all replicas share one Adam step count.
 
+The one-handle forms (``ApproachPopulationPPO``, ``RoutePopulationPPO``) step all replicas in ONE env handle of K N envs instead, block k
+being replica k, with one population tracker: every env step is one env launch and one tracker launch whatever K is.
+
 ``PopulationPPO`` is a ``PPO`` with K replicas: it runs PPO's rollout, graph capture and update loop and overrides only the steps that
 depend on K.  ``replica(k)`` is a view with what ``checkpoint.save`` and the evaluators read, so a replica saves as an ordinary
 single-policy archive.
@@ -246,7 +249,63 @@ class PopulationPPO(PPO):
                                 max_grad_norm=cfg.max_grad_norm, step=0, fused_norm=True)
 
 
-class RoutePopulationPPO(PopulationPPO):
+class OneHandlePopulationPPO(PopulationPPO):
+    """A population whose K replicas share ONE env handle of K N envs (block k = replica k, the rollout buffers' replica-major layout) and
+    ONE population tracker: every env step is one env step launch and one tracker launch whatever K is.  Subclasses set ``pop_env`` /
+    ``pop_curriculum`` and build the per-replica views; noise, truncation bootstrap, the epoch body and graph capture are PopulationPPO's.
+    The caller owns (and closes) the env and the tracker."""
+
+    pop_env: Any = None
+    pop_curriculum: Any = None
+
+    def _reset_envs(self, which: list[int] | None = None) -> None:
+        if which is None or which:
+            self.obs_buf[0].copy_(self.pop_env.reset())
+
+    def _policy_env_step(self, t: int) -> None:
+        self._mlp.forward(self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t], clipped=self.clip_act,
+                          log_prob=self.logp_buf[t])
+        self.pop_env.step_into(self.clip_act, self.obs_buf[t + 1], self.rew_buf[t], self.done_buf[t], self.term_obs_buf[t], True)
+
+    def _curriculum_observe(self, t: int) -> None:
+        if self.pop_curriculum is not None:
+            self.pop_curriculum.observe(self.done_buf[t], self.n_envs)
+
+    def _warm_curricula(self) -> None:
+        if self.pop_curriculum is not None:
+            self.pop_curriculum.observe(self.done_buf[0].zero_(), 0)
+
+
+class ApproachPopulationPPO(OneHandlePopulationPPO):
+    """K Approach runs of one PPOConfig on ONE ArmKinematicPopulationVecEnv (vec_env.py) with ONE PointCurriculumPopulation
+    (curriculum.py): the env step kernel reads each env's stage from its own replica's tracker, so replicas on different stages share a
+    launch (and a wave).  Replica k is bit-identical to ``PPO(ArmKinematicVecEnv(..., seed=s_k), curriculum=PointCurriculum)`` on the same
+    config (tests/test_approach_population_gpu.py), and to replica k of the K-handle ``PopulationPPO``."""
+
+    def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
+                 teacher_anchor: Any = None) -> None:
+        from .curriculum import PointCurriculumPopulation
+        from .vec_env import ArmKinematicPopulationVecEnv
+
+        seeds, dist = self._check_population_args(seeds, cfg, dist, teacher_anchor)
+        if not isinstance(env, ArmKinematicPopulationVecEnv):
+            raise TypeError("ApproachPopulationPPO drives an ArmKinematicPopulationVecEnv (one handle for all replicas)")
+        if env.seeds != seeds:
+            raise ValueError(f"the ArmKinematicPopulationVecEnv was made for seeds {env.seeds}, not {seeds}")
+        if curriculum is not None and not isinstance(curriculum, PointCurriculumPopulation):
+            raise TypeError("ApproachPopulationPPO takes a PointCurriculumPopulation (one tracker launch for all replicas)")
+        if curriculum is not None and curriculum.K != len(seeds):
+            raise ValueError(f"the PointCurriculumPopulation holds {curriculum.K} trackers for {len(seeds)} seeds")
+        self.pop_env, self.pop_curriculum = env, curriculum
+        if curriculum is not None:
+            curriculum.attach(env)
+        K = len(seeds)
+        views = [env.replica(k) for k in range(K)]
+        curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs)
+
+
+class RoutePopulationPPO(OneHandlePopulationPPO):
     """K route-curriculum runs of one PPOConfig on ONE RoutePopulationVecEnv (route_env.py): block k of its K N envs is replica k, which is the
     rollout buffers' replica-major layout, so every env step is one route step and one tracker launch (RoutePrefixCurriculumPopulation)
     whatever K is.  Everything else -- noise, truncation bootstrap, the epoch body, graph capture -- is PopulationPPO's.
@@ -267,7 +326,7 @@ class RoutePopulationPPO(PopulationPPO):
             raise ValueError(f"the RoutePopulationVecEnv was made for seeds {env.seeds}, not {seeds}")
         if curriculum is not None and not isinstance(curriculum, RoutePrefixCurriculumPopulation):
             raise TypeError("RoutePopulationPPO takes a RoutePrefixCurriculumPopulation (one tracker launch for all replicas)")
-        self.route_env, self.route_curriculum = env, curriculum
+        self.pop_env, self.pop_curriculum = env, curriculum
         if curriculum is not None:
             curriculum.attach(env)
         K = len(seeds)
@@ -326,24 +385,6 @@ class RoutePopulationPPO(PopulationPPO):
         restored["hyperparameters"] = restore_saved_hyperparameters(self.cfg, data)
         self.cfgs = [dataclasses.replace(self.cfg, seed=s) for s in self.seeds]
         return restored
-
-    # ------------------------------------------------------------------ one launch per env step for all replicas
-    def _reset_envs(self, which: list[int] | None = None) -> None:
-        if which is None or which:
-            self.obs_buf[0].copy_(self.route_env.reset())
-
-    def _policy_env_step(self, t: int) -> None:
-        self._mlp.forward(self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t], clipped=self.clip_act,
-                          log_prob=self.logp_buf[t])
-        self.route_env.step_into(self.clip_act, self.obs_buf[t + 1], self.rew_buf[t], self.done_buf[t], self.term_obs_buf[t], True)
-
-    def _curriculum_observe(self, t: int) -> None:
-        if self.route_curriculum is not None:
-            self.route_curriculum.observe(self.done_buf[t], self.n_envs)
-
-    def _warm_curricula(self) -> None:
-        if self.route_curriculum is not None:
-            self.route_curriculum.observe(self.done_buf[0].zero_(), 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------- trainer CLI (--seeds)

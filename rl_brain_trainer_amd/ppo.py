@@ -460,6 +460,8 @@ class PPO:
                  dist: Dist | None = None, backend: str = "hip", use_graphs: bool = True) -> None:
         if backend != "hip":
             raise ValueError("backend must be 'hip': the HIP kernels are the only training path")
+        if getattr(env, "is_population", False):
+            raise TypeError("PPO trains one seed; a population env (K replicas in one handle) is trained by population.ApproachPopulationPPO")
         if env.dtype != torch.float32:
             raise ValueError("PPO drives the production f32 env")
         self.env = env

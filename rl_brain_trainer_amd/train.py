@@ -192,13 +192,20 @@ def _start_artifacts(root: Path, args, cfg: dict[str, Any]) -> None:
     write_json(root / "training_launch_summary.json", {"run_id": args.run_id, "config": cfg})
 
 
-def _make_curriculum(cfg: dict[str, Any], env_cfg: kcfg.EnvConfig, ws: dict[str, Any], device: int) -> PointCurriculum | None:
+def _curriculum_kwargs(cfg: dict[str, Any], env_cfg: kcfg.EnvConfig) -> dict[str, Any] | None:
+    """PointCurriculumCallback's settings from the YAML (None: the env has no curriculum stages)"""
     cur = cfg["env"].get("curriculum", {})
     if not (env_cfg.c.curriculum_enabled and env_cfg.n_stages):
         return None
-    return PointCurriculum(success_rate_threshold=float(cur.get("success_rate_threshold", 0.80)), window_episodes=int(cur.get("window_episodes", 20)),
-                           min_episodes_per_stage=int(cur.get("min_episodes_per_stage", 30)), max_stage_index=env_cfg.n_stages - 1,
-                           initial_stage_index=int(ws.get("start_stage_index", 0)), device=device)
+    return {"success_rate_threshold": float(cur.get("success_rate_threshold", 0.80)), "window_episodes": int(cur.get("window_episodes", 20)),
+            "min_episodes_per_stage": int(cur.get("min_episodes_per_stage", 30)), "max_stage_index": env_cfg.n_stages - 1}
+
+
+def _make_curriculum(cfg: dict[str, Any], env_cfg: kcfg.EnvConfig, ws: dict[str, Any], device: int) -> PointCurriculum | None:
+    kw = _curriculum_kwargs(cfg, env_cfg)
+    if kw is None:
+        return None
+    return PointCurriculum(**kw, initial_stage_index=int(ws.get("start_stage_index", 0)), device=device)
 
 
 def _load_finisher(ws: dict[str, Any], device: int):
@@ -250,8 +257,11 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, 
 
 
 def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model_kwargs, resume, hidden: int, world: int, device: int) -> dict[str, Any]:
-    """--seeds: the seeds train together as one PopulationPPO; seed s writes what a --seed s run writes, under root/seed_<s>/"""
-    from .population import PopulationPPO, learn_population, parse_seeds, population_summary
+    """--seeds: the seeds train together as one ApproachPopulationPPO -- one env handle of K x n_envs envs and one tracker launch per env
+    step for all seeds; seed s writes what a --seed s run writes, under root/seed_<s>/"""
+    from .curriculum import PointCurriculumPopulation
+    from .population import ApproachPopulationPPO, learn_population, parse_seeds, population_summary
+    from .vec_env import ArmKinematicPopulationVecEnv
 
     seeds = parse_seeds(args.seeds)
     if world > 1:
@@ -261,8 +271,13 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
                          "workspace_expansion.init_approach_checkpoint)")
     roots = {s: root / f"seed_{s}" for s in seeds}
     pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=hidden)
-    pop = PopulationPPO(seeds, pcfg, lambda s: ArmKinematicVecEnv(env_cfg, args.n_envs, device=device, seed=s),
-                        curriculum_factory=lambda s: _make_curriculum(cfg, env_cfg, ws, device))
+    ApproachPopulationPPO._check_population_args(seeds, pcfg, None, None)     # refusals before any device work
+    env = ArmKinematicPopulationVecEnv(env_cfg, seeds, args.n_envs, device=device)
+    kw = _curriculum_kwargs(cfg, env_cfg)
+    curriculum = None
+    if kw is not None:
+        curriculum = PointCurriculumPopulation(**kw, initial_stage_indices=[int(ws.get("start_stage_index", 0))] * len(seeds), device=device)
+    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=curriculum)
     for s in seeds:
         _start_artifacts(roots[s], args, cfg)
     finisher_policy, finisher_cfg = _load_finisher(ws, device)
@@ -290,6 +305,9 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
     summary = population_summary(pop, rows, wall_seconds=wall, selection="workspace eval gate score (best_model_selection.score)")
     write_json(root / "population_summary.json", summary)
     pop.close()
+    if curriculum is not None:
+        curriculum.close()
+    env.close()
     return summary
 
 

@@ -296,6 +296,106 @@ class ArmKinematicVecEnv:
         native.check(self.L.kp1_rng_set(self._handle, C.cast(arr, C.c_void_p)))
 
 
+
+MAX_REPLICAS = 16     # KP1_CURRICULUM_MAX_REPLICAS / KP1_MLP_MAX_REPLICAS
+
+
+class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
+    """K Approach envs of ``n_per_replica`` envs each in ONE handle: block k = rows [k N, (k + 1) N) is replica k, and is bit for bit
+    ``ArmKinematicVecEnv(config, n_per_replica, seed=seeds[k])`` (env i of replica k owns ``default_rng(seeds[k] + i)``, kp1_seed_blocks).
+    One ``step_into`` covers all K N rows, so a population rollout is one env step launch per step whatever K is -- the [K N, obs_w] buffers
+    are the population rollout's replica-major layout.
+
+    A PointCurriculumPopulation attached to it gives every replica its own curriculum stage: the auto-reset of env i reads the stage of
+    tracker i / N (the population form of the step kernel).  ``reset()`` uses the handle's host stage, which K single handles made from one
+    config share.  f32 and the Approach mode only; the handle keeps its per-block seeds (``seed()`` is refused).  ``replica(k)`` is a view
+    with what PPO's setup, ReplicaView and ``checkpoint.save`` read."""
+
+    is_population = True
+
+    def __init__(self, config: kcfg.EnvConfig, seeds: list[int], n_per_replica: int, *, device: int | torch.device = 0, real: str = "f32",
+                 reward_components: bool = False) -> None:
+        self.seeds = [int(s) for s in seeds]
+        if not self.seeds:
+            raise ValueError("ArmKinematicPopulationVecEnv needs at least one seed")
+        if len(self.seeds) > MAX_REPLICAS:
+            raise ValueError(f"ArmKinematicPopulationVecEnv holds at most {MAX_REPLICAS} replicas (got {len(self.seeds)} seeds)")
+        if len(set(self.seeds)) != len(self.seeds):
+            raise ValueError(f"ArmKinematicPopulationVecEnv seeds must be distinct (got {self.seeds})")
+        if config.mode_name != "approach":
+            raise ValueError("ArmKinematicPopulationVecEnv runs the Approach env; a dock-mode config rewrites the handle's config per replica "
+                             "on promotion (DockReverseCurriculum) and needs one handle per replica")
+        if real != "f32":
+            raise ValueError("ArmKinematicPopulationVecEnv is the f32 env (the population step kernel has no f64 form)")
+        self.K = len(self.seeds)
+        self.n_per_replica = int(n_per_replica)
+        if self.n_per_replica < 1:
+            raise ValueError("n_per_replica must be positive")
+        super().__init__(config, self.K * self.n_per_replica, device=device, seed=self.seeds[0], real="f32", reward_components=reward_components)
+        seeds_c = (C.c_uint64 * self.K)(*self.seeds)
+        native.check(self.L.kp1_seed_blocks(self._handle, C.cast(seeds_c, C.c_void_p), self.K, self.n_per_replica))
+
+    def replica(self, k: int) -> "ArmKinematicReplicaEnv":
+        if not 0 <= int(k) < self.K:
+            raise IndexError(f"replica {k} of a population of {self.K}")
+        return ArmKinematicReplicaEnv(self, int(k))
+
+    def rows(self, k: int) -> slice:
+        return slice(k * self.n_per_replica, (k + 1) * self.n_per_replica)
+
+    def seed(self, seed: int, first_env_id: int = 0) -> None:
+        raise ValueError("a population env keeps the per-block seeds it was created with (env i of replica k: seeds[k] + i)")
+
+    def set_policy_mode(self, mode_name: str) -> None:
+        if mode_name != "approach":
+            raise ValueError("a population env runs the Approach mode only")
+        super().set_policy_mode(mode_name)
+
+    def reset(self, *, seed: int | None = None, options: dict[str, Any] | None = None, mask: torch.Tensor | None = None) -> torch.Tensor:
+        if options and options.get("policy_mode") not in (None, "approach"):
+            raise ValueError("a population env runs the Approach mode only")
+        return super().reset(seed=seed, options=options, mask=mask)
+
+
+class ArmKinematicReplicaEnv:
+    """Replica k of an ArmKinematicPopulationVecEnv: the attributes PPO's setup, ReplicaView and ``checkpoint.save`` read.  Stepping,
+    resetting and snapshots go through the population handle (one launch for all replicas)."""
+
+    def __init__(self, pop: ArmKinematicPopulationVecEnv, k: int) -> None:
+        self.pop, self.k = pop, int(k)
+        self.n_envs = pop.n_per_replica
+        self.device, self.dtype, self.config = pop.device, pop.dtype, pop.config
+        self.obs_dim = kcfg.OBS_DIM
+        self.seed = pop.seeds[self.k]
+
+    @property
+    def launch_args_version(self) -> int:
+        return self.pop.launch_args_version
+
+    @property
+    def obs_stride(self) -> int:
+        return self.pop.obs_stride
+
+    def set_obs_stride(self, stride: int) -> None:
+        if int(stride) != self.pop.obs_stride:
+            self.pop.set_obs_stride(stride)
+
+    def use_current_stream(self) -> None:
+        self.pop.use_current_stream()
+
+    def snapshot(self) -> None:
+        """(the whole population handle: every replica's view takes the same snapshot)"""
+        self.pop.snapshot()
+
+    def restore(self) -> None:
+        self.pop.restore()
+
+    def reset(self, **_: Any) -> torch.Tensor:
+        raise TypeError("a replica of an ArmKinematicPopulationVecEnv is reset through the population handle (one reset of all replicas)")
+
+    def close(self) -> None:
+        """(the population handle owns the envs)"""
+
 def fk_pose6(q: torch.Tensor) -> torch.Tensor:
     """compute_ee_pose6 batched on the GPU (kinematics/fk_interface.py:21-22): q[n,7] -> pose6[n,6]."""
     if q.ndim != 2 or q.shape[1] != kcfg.NJ:

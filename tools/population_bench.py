@@ -8,6 +8,12 @@ optimiser-step kernels KP1_MLP_OPT_PROFILE times on this path (grad_finalize, ad
 
     python tools/population_bench.py [--ks 1,2,4,8] [--iters 3] [--out profiles/r04_population_refscale.json]
 
+--one-handle: the same Approach iteration as an ApproachPopulationPPO: one env handle of K x 16 envs and one PointCurriculumPopulation, so
+every env step is one env launch and one tracker launch for all replicas (K in {1, 2, 4, 8, 16} by default).  Without it every replica has
+its own handle and tracker (PopulationPPO), which is the comparison.
+
+    python tools/population_bench.py --one-handle [--ks 1,2,4,8,16] [--out profiles/r06_approach_population_refscale.json]
+
 --route: the route reference-scale iteration instead -- route_curriculum_prefix120_routeobs_sequence2 on tests/golden/synthetic_route.json,
 16 envs x 1024 steps, minibatch 512, 2x64, graphs on -- as a RoutePopulationPPO: one route env handle of K x 16 envs and one tracker launch
 per env step for all replicas (K in {1, 2, 4, 8, 16} by default).
@@ -34,21 +40,37 @@ from rl_brain_trainer_amd.ppo import PPOConfig  # noqa: E402
 from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv  # noqa: E402
 
 
-def build_approach(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool) -> PopulationPPO:
+def _approach_setup(n_steps: int, batch: int, hidden: int):
     cfg = kcfg.load_workspace_expansion_config(kcfg.builtin_config_dir() / "workspace_expansion_bigtrain.yaml")
     env_cfg = kcfg.to_env_config(cfg)
     cur = cfg["env"].get("curriculum", {})
     algo = {k: v for k, v in kcfg.to_algorithm_kwargs(cfg, "ppo").items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
     pcfg = PPOConfig.from_algo_kwargs(algo, n_steps=n_steps, batch_size=batch, hidden=hidden)
+    tracker = None
+    if env_cfg.c.curriculum_enabled and env_cfg.n_stages:
+        tracker = {"success_rate_threshold": float(cur.get("success_rate_threshold", 0.80)), "window_episodes": int(cur.get("window_episodes", 20)),
+                   "min_episodes_per_stage": int(cur.get("min_episodes_per_stage", 30)), "max_stage_index": env_cfg.n_stages - 1}
+    return env_cfg, pcfg, tracker
 
-    def cur_factory(seed: int):
-        if not (env_cfg.c.curriculum_enabled and env_cfg.n_stages):
-            return None
-        return PointCurriculum(success_rate_threshold=float(cur.get("success_rate_threshold", 0.80)), window_episodes=int(cur.get("window_episodes", 20)),
-                               min_episodes_per_stage=int(cur.get("min_episodes_per_stage", 30)), max_stage_index=env_cfg.n_stages - 1)
 
-    return PopulationPPO(list(range(7, 7 + K)), pcfg, lambda s: ArmKinematicVecEnv(env_cfg, n_envs, seed=s), curriculum_factory=cur_factory,
-                         use_graphs=use_graphs)
+def build_approach(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool) -> PopulationPPO:
+    env_cfg, pcfg, tracker = _approach_setup(n_steps, batch, hidden)
+    return PopulationPPO(list(range(7, 7 + K)), pcfg, lambda s: ArmKinematicVecEnv(env_cfg, n_envs, seed=s),
+                         curriculum_factory=lambda s: PointCurriculum(**tracker) if tracker else None, use_graphs=use_graphs)
+
+
+def build_approach_one_handle(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool) -> PopulationPPO:
+    from rl_brain_trainer_amd.curriculum import PointCurriculumPopulation
+    from rl_brain_trainer_amd.population import ApproachPopulationPPO
+    from rl_brain_trainer_amd.vec_env import ArmKinematicPopulationVecEnv
+
+    env_cfg, pcfg, tracker = _approach_setup(n_steps, batch, hidden)
+    seeds = list(range(7, 7 + K))
+    env = ArmKinematicPopulationVecEnv(env_cfg, seeds, n_envs)
+    cur = PointCurriculumPopulation(**tracker, initial_stage_indices=[0] * K) if tracker else None
+    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=cur, use_graphs=use_graphs)
+    pop._bench_owned = [c for c in (cur, env) if c is not None]     # closed after the population (the caller owns them)
+    return pop
 
 
 ROUTE_CONFIG = ROOT / "tests" / "golden" / "configs" / "route_curriculum_prefix120_routeobs_sequence2.json"
@@ -81,7 +103,7 @@ def _close(pop) -> None:
 
 
 def measure(K: int, args) -> dict:
-    build = build_route if args.route else build_approach
+    build = build_route if args.route else (build_approach_one_handle if args.one_handle else build_approach)
     pop = build(K, args.n_envs, args.n_steps, args.batch, args.hidden, True)
     pop.collect_rollouts()
     pop.train()      # warm-up: captures both graphs
@@ -116,6 +138,7 @@ def measure(K: int, args) -> dict:
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--route", action="store_true", help="the route reference-scale iteration (RoutePopulationPPO)")
+    ap.add_argument("--one-handle", action="store_true", help="the Approach iteration on one env handle (ApproachPopulationPPO)")
     ap.add_argument("--ks", default="")
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--n-envs", type=int, default=16)
@@ -124,7 +147,9 @@ def main() -> None:
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
-    args.ks = args.ks or ("1,2,4,8,16" if args.route else "1,2,4,8")
+    if args.route and args.one_handle:
+        ap.error("--one-handle is the Approach form; --route is always one handle")
+    args.ks = args.ks or ("1,2,4,8,16" if args.route or args.one_handle else "1,2,4,8")
     args.batch = args.batch or (512 if args.route else 256)
     rows = []
     for K in (int(k) for k in args.ks.split(",")):
@@ -134,7 +159,9 @@ def main() -> None:
     for r in rows:
         r["aggregate_vs_first"] = r["aggregate_env_steps_per_s"] / base
     workload = (f"route_curriculum_prefix120_routeobs_sequence2 on synthetic_route.json (RoutePopulationPPO: one route env handle of K x {args.n_envs} envs)"
-                if args.route else "workspace_expansion_bigtrain.yaml Approach iteration")
+                if args.route else
+                f"workspace_expansion_bigtrain.yaml Approach iteration (ApproachPopulationPPO: one env handle of K x {args.n_envs} envs)"
+                if args.one_handle else "workspace_expansion_bigtrain.yaml Approach iteration (PopulationPPO: one env handle per replica)")
     result = {"workload": f"{workload}, {args.n_envs} envs x {args.n_steps} steps per replica, "
                           f"minibatch {args.batch}, 2x{args.hidden}, curriculum on; seeds 7..7+K-1", "device": torch.cuda.get_device_name(0), "rows": rows}
     if args.out:
