@@ -154,6 +154,21 @@ int kp1_dock_curriculum_observe(kp1_env* env, kp1_dock_curriculum_state* st_dev,
                                 void* stream);
 /* copy the tracker to the host; also brings the env handle's host-side config mirror in step with the stage the device applied */
 int kp1_dock_curriculum_read(kp1_env* env, const kp1_dock_curriculum_state* st_dev, kp1_dock_curriculum_state* out_host, void* stream);
+/* Dock population: K trackers for a dock-mode population env handle (block k = envs [k N, (k + 1) N) is replica k), each set up as
+ * kp1_dock_curriculum_create sets one up, followed in the same allocation by K live stage records (record k = the stage tracker k is on,
+ * stage 0 to begin with).  Applies stage 0 to the shared config before the first reset and binds the handle: kp1_step and kp1_reset then run
+ * their dock population forms, env i reading what a stage overrides from live record i / N.  Needs the dock mode, the f32 handle,
+ * N % n_replicas == 0, 1 <= n_replicas <= KP1_CURRICULUM_MAX_REPLICAS, a handle bound to no population and carrying no single dock tracker;
+ * the fused policy + env step refuses a bound handle.  Free (and unbind) with kp1_dock_curriculum_destroy. */
+int kp1_dock_curriculum_create_population(kp1_env* env, const kp1_dock_curriculum_stage* stages_host, int32_t n_stages, int32_t window_episodes,
+                                          int32_t n_replicas, kp1_dock_curriculum_state** out_dev);
+/* ONE launch of K one-wave workgroups: workgroup k replays dones[k N, (k + 1) N) into tracker k by kp1_dock_curriculum_observe's rule, its
+ * clock advancing by N; a promotion rewrites only tracker k and live record k (never the shared config) */
+int kp1_dock_curriculum_observe_population(kp1_env* env, kp1_dock_curriculum_state* states_dev, const uint8_t* dones, int32_t n_per_replica,
+                                           int32_t n_replicas, void* stream);
+/* copy tracker k of a population of n_replicas to the host; the handle's shared host config mirror is left as it is */
+int kp1_dock_curriculum_read_replica(kp1_env* env, const kp1_dock_curriculum_state* states_dev, int32_t n_replicas, int32_t k,
+                                     kp1_dock_curriculum_state* out_host, void* stream);
 
 /* ---- actor-critic MLP on the matrix cores (fp32-in / fp32-accumulate MFMA, exact f32) ---------------------------
  * SB3 MultiInputActorCriticPolicy with net_arch pi = vf = [H, H], tanh:

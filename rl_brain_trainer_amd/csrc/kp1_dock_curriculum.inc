@@ -33,10 +33,11 @@ __device__ __forceinline__ void dock_apply_stage(const kp1_dock_curriculum_stage
   }
 }
 
-// one block of n done bytes (KP1_DONE_* bits) in index order; lane 0 carries the tracker state
-template <typename R>
+// one block of n done bytes (KP1_DONE_* bits) in index order; lane 0 carries the tracker state.  apply(stage) is what a promotion does with the
+// next stage's record: dock_apply_stage on the handle's config (single tracker), or a copy into the replica's live record (population).
+template <typename Apply>
 __device__ __forceinline__ void dock_curriculum_scan(kp1_dock_curriculum_state* __restrict__ st, const uint8_t* __restrict__ dones, int n, int clock_steps,
-                                                     DevCfg<R>* __restrict__ cfg, DevSampler* __restrict__ smp) {
+                                                     Apply apply) {
   const int lane = threadIdx.x;
   if (lane == 0) st->num_timesteps += clock_steps;
   for (int base = 0; base < n; base += 64 * 64) {
@@ -93,7 +94,7 @@ __device__ __forceinline__ void dock_curriculum_scan(kp1_dock_curriculum_state* 
         for (int j = 0; j < take; ++j) wins += st->ring[(st->ring_head + st->ring_len - 1 - j) % cap];
         const double rate = (double)wins / (double)take;
         if (rate < cur.success_rate_threshold) continue;
-        dock_apply_stage<R>(st->stages[k + 1], cfg, smp);
+        apply(st->stages[k + 1]);
         if (st->n_events < KP1_DOCK_CURRICULUM_MAX_HISTORY) {
           kp1_dock_curriculum_event& ev = st->events[st->n_events];
           ev.from_stage = k;
@@ -119,7 +120,18 @@ __global__ void __launch_bounds__(64) dock_curriculum_kernel(kp1_dock_curriculum
                                                              DevSampler* __restrict__ smp) {
   for (int t = 0; t < chunk_steps; ++t)
     for (int r = 0; r < world; ++r)
-      dock_curriculum_scan<R>(st, dones + ((int64_t)r * chunk_steps + t) * n_local, n_local, r == 0 ? clock_steps : 0, cfg, smp);
+      dock_curriculum_scan(st, dones + ((int64_t)r * chunk_steps + t) * n_local, n_local, r == 0 ? clock_steps : 0,
+                           [&](const kp1_dock_curriculum_stage& s) { dock_apply_stage<R>(s, cfg, smp); });
+}
+
+// K trackers in one launch (kp1_dock_curriculum_observe_population): workgroup k is dock_curriculum_kernel's rule on tracker k and the done
+// bytes [k n, (k + 1) n) of its replica, its clock advancing by n as a single tracker's does.  A promotion writes only replica k: its tracker
+// and its live stage record live[k], which the dock population forms of the step and reset kernels read.  The shared config is not touched.
+__global__ void __launch_bounds__(64) dock_curriculum_population_kernel(kp1_dock_curriculum_state* __restrict__ states, kp1_dock_curriculum_stage* __restrict__ live,
+                                                                        const uint8_t* __restrict__ dones_all, int n) {
+  const int k = blockIdx.x;
+  kp1_dock_curriculum_stage* __restrict__ rec = live + k;
+  dock_curriculum_scan(states + k, dones_all + (int64_t)k * n, n, n, [&](const kp1_dock_curriculum_stage& s) { *rec = s; });
 }
 
 template <typename R>
@@ -147,6 +159,7 @@ int kp1_dock_curriculum_create(kp1_env* env, const kp1_dock_curriculum_stage* st
                                kp1_dock_curriculum_state** out_dev) {
   if (!env || !stages_host || !out_dev) return fail(KP1_ERR_INVALID, "NULL argument to kp1_dock_curriculum_create");
   if (env->mode != KP1_MODE_DOCK) return fail(KP1_ERR_INVALID, "the dock reverse curriculum drives a dock-mode env");
+  if (env->pop_dock_states) return fail(KP1_ERR_UNSUPPORTED, "the handle is bound to a dock population: its stages are per replica");
   if (n_stages < 1 || n_stages > KP1_DOCK_CURRICULUM_MAX_STAGES) return fail(KP1_ERR_INVALID, "DockReverseCurriculumCallback requires 1..16 stages");
   const int window = window_episodes < 1 ? 1 : window_episodes;   // callbacks.py:116 max(..., 1)
   if (window > KP1_DOCK_CURRICULUM_MAX_WINDOW) return fail(KP1_ERR_INVALID, "window_episodes exceeds KP1_DOCK_CURRICULUM_MAX_WINDOW");
@@ -182,11 +195,91 @@ int kp1_dock_curriculum_create(kp1_env* env, const kp1_dock_curriculum_stage* st
   return KP1_OK;
 }
 
+int kp1_dock_curriculum_create_population(kp1_env* env, const kp1_dock_curriculum_stage* stages_host, int32_t n_stages, int32_t window_episodes,
+                                          int32_t n_replicas, kp1_dock_curriculum_state** out_dev) {
+  if (!env || !stages_host || !out_dev) return fail(KP1_ERR_INVALID, "NULL argument to kp1_dock_curriculum_create_population");
+  if (env->mode != KP1_MODE_DOCK || env->cfg.env.mode != KP1_MODE_DOCK)
+    return fail(KP1_ERR_UNSUPPORTED, "kp1_dock_curriculum_create_population: the dock reverse curriculum drives a dock-mode env");
+  if (env->real_type != KP1_REAL_F32) return fail(KP1_ERR_UNSUPPORTED, "kp1_dock_curriculum_create_population: a population env handle is f32");
+  if (n_replicas < 1 || n_replicas > KP1_CURRICULUM_MAX_REPLICAS)
+    return fail(KP1_ERR_INVALID, "kp1_dock_curriculum_create_population: n_replicas must be in [1, KP1_CURRICULUM_MAX_REPLICAS]");
+  if (env->n % n_replicas != 0)
+    return fail(KP1_ERR_INVALID, "kp1_dock_curriculum_create_population: the env count must be a multiple of the replica count");
+  if (env->pop_states || env->pop_dock_states)
+    return fail(KP1_ERR_UNSUPPORTED, "kp1_dock_curriculum_create_population: the handle is already bound to a population");
+  if (env->dock_tracker)
+    return fail(KP1_ERR_UNSUPPORTED, "kp1_dock_curriculum_create_population: the handle carries a single dock tracker (kp1_dock_curriculum_create)");
+  if (n_stages < 1 || n_stages > KP1_DOCK_CURRICULUM_MAX_STAGES) return fail(KP1_ERR_INVALID, "DockReverseCurriculumCallback requires 1..16 stages");
+  const int window = window_episodes < 1 ? 1 : window_episodes;
+  if (window > KP1_DOCK_CURRICULUM_MAX_WINDOW) return fail(KP1_ERR_INVALID, "window_episodes exceeds KP1_DOCK_CURRICULUM_MAX_WINDOW");
+  for (int k = 0; k < n_stages; ++k)
+    if (stages_host[k].handoff_count >= 0 && (stages_host[k].handoff_offset < 0 || stages_host[k].handoff_offset + stages_host[k].handoff_count > env->n_handoff))
+      return fail(KP1_ERR_INVALID, "a stage's handoff slice lies outside the buffer given to kp1_set_handoff_states");
+  HIP_TRY(hipSetDevice(env->device));
+  // K trackers set up as kp1_dock_curriculum_create sets up one, then the K live stage records (stage 0 to begin with)
+  static_assert(sizeof(kp1_dock_curriculum_state) % alignof(kp1_dock_curriculum_stage) == 0, "live records follow the trackers");
+  const size_t bytes = (sizeof(kp1_dock_curriculum_state) + sizeof(kp1_dock_curriculum_stage)) * (size_t)n_replicas;
+  std::vector<unsigned char> h(bytes, 0);
+  kp1_dock_curriculum_state* hs = reinterpret_cast<kp1_dock_curriculum_state*>(h.data());
+  kp1_dock_curriculum_stage* hl = reinterpret_cast<kp1_dock_curriculum_stage*>(hs + n_replicas);
+  for (int r = 0; r < n_replicas; ++r) {
+    kp1_dock_curriculum_state& t = hs[r];
+    t.n_stages = n_stages;
+    t.window_episodes = window;
+    for (int k = 0; k < n_stages; ++k) {
+      t.stages[k] = stages_host[k];
+      if (t.stages[k].min_episodes < 1) t.stages[k].min_episodes = 1;
+      if (t.stages[k].window_episodes < 1) t.stages[k].window_episodes = 1;
+    }
+    hl[r] = t.stages[0];
+  }
+  kp1_dock_curriculum_state* d = nullptr;
+  hipError_t e = hipMalloc((void**)&d, bytes);
+  if (e == hipSuccess) e = hipMemcpy(d, h.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (d) (void)hipFree(d);
+    return fail(kp1::status_of(e), std::string("kp1_dock_curriculum_create_population: ") + hipGetErrorString(e));
+  }
+  // _on_training_start of every replica: stage 0 into the shared config before the first reset, as kp1_dock_curriculum_create does (what no
+  // stage overrides is read from there; the population forms read the rest from the live records)
+  hipLaunchKernelGGL(dock_curriculum_apply_kernel<float>, dim3(1), dim3(64), 0, env->stream, d, (DevCfg<float>*)env->dev_cfg, env->dev_smp);
+  HIP_TRY(kp1::launch_status());
+  env->pop_dock_states = d;   // not env->dock_tracker: upload_cfg must not copy one replica's stage into the shared config
+  env->pop_replicas = n_replicas;
+  *out_dev = d;
+  return KP1_OK;
+}
+
+int kp1_dock_curriculum_observe_population(kp1_env* env, kp1_dock_curriculum_state* states_dev, const uint8_t* dones, int32_t n_per_replica,
+                                           int32_t n_replicas, void* stream) {
+  if (!env || !states_dev || !dones || n_per_replica <= 0 || n_replicas < 1 || n_replicas > KP1_CURRICULUM_MAX_REPLICAS)
+    return fail(KP1_ERR_INVALID, "bad argument to kp1_dock_curriculum_observe_population");
+  HIP_TRY(hipSetDevice(env->device));
+  hipLaunchKernelGGL(dock_curriculum_population_kernel, dim3((unsigned)n_replicas), dim3(64), 0, (hipStream_t)stream, states_dev,
+                     reinterpret_cast<kp1_dock_curriculum_stage*>(states_dev + n_replicas), dones, n_per_replica);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_dock_curriculum_read_replica(kp1_env* env, const kp1_dock_curriculum_state* states_dev, int32_t n_replicas, int32_t k,
+                                     kp1_dock_curriculum_state* out_host, void* stream) {
+  if (!env || !states_dev || !out_host) return fail(KP1_ERR_INVALID, "NULL argument");
+  if (k < 0 || k >= n_replicas) return fail(KP1_ERR_INVALID, "replica index out of range");
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipMemcpyAsync(out_host, states_dev + k, sizeof *out_host, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return KP1_OK;   // (the handle's shared host mirror stays as it is: the replicas' stages differ)
+}
+
 int kp1_dock_curriculum_destroy(kp1_env* env, kp1_dock_curriculum_state* st_dev) {
   if (!env) return fail(KP1_ERR_INVALID, "NULL env");
   HIP_TRY(hipSetDevice(env->device));
   HIP_TRY(hipStreamSynchronize(env->stream));
   if (env->dock_tracker == st_dev) env->dock_tracker = nullptr;
+  if (st_dev && env->pop_dock_states == st_dev) {   // a dock population: the handle steps in the ordinary dock form again
+    env->pop_dock_states = nullptr;
+    env->pop_replicas = 0;
+  }
   HIP_TRY(hipFree(st_dev));
   return KP1_OK;
 }

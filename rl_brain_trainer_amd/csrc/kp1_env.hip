@@ -31,7 +31,8 @@ namespace {
 
 #include "kp1_env_step.inc"
 
-// POP (f32 approach only): a population handle, env i auto-resets on the stage of tracker i / n_per_replica (kp1_bind_population_stages)
+// POP (f32 only): a population handle.  Approach mode: env i auto-resets on the stage of tracker i / n_per_replica (kp1_bind_population_stages);
+// dock mode: env i steps and resets with the live stage record of replica i / n_per_replica (kp1_dock_curriculum_create_population)
 template <typename R, int MODE, bool COMPS, bool POP>
 __global__ void __launch_bounds__(256, 1) kp1_step_kernel(const StepArgs<R> a) {
   extern __shared__ float obs_tiles[];   // OBS_TILE_FLOATS per wave of the workgroup
@@ -53,14 +54,21 @@ __global__ void __launch_bounds__(256, 1) kp1_step_kernel(const StepArgs<R> a) {
 #endif
 }
 
-template <typename R, int MODE>
+// POP (f32 dock only): a dock population handle, env i samples with the live stage record pop_dock[i / n_per_replica] (the step's reset branch)
+template <typename R, int MODE, bool POP = false>
 __global__ void __launch_bounds__(256) kp1_reset_kernel(const EnvState<R> st, const DevCfg<R>* cfg, const DevSampler* smp, const kp1_handoff_state* handoff,
-                                 const uint8_t* mask, const ResetOptsDev opts, int stage_index, float* obs, int obs_stride) {
+                                 const uint8_t* mask, const ResetOptsDev opts, int stage_index, float* obs, int obs_stride,
+                                 const kp1_dock_curriculum_stage* pop_dock, int n_per_replica) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= st.n) return;
   if (mask && !mask[i]) return;
   float o[KP1_OBS_DIM];
-  reset_env<R, MODE>(st, uniform_block(cfg), uniform_block(smp), handoff, opts, stage_index, i, o);
+  if constexpr (POP) {
+    static_assert(MODE == KP1_MODE_DOCK, "the reset kernel's population form is the dock mode's");
+    reset_env<R, MODE, true>(st, uniform_block(cfg), uniform_block(smp), handoff, opts, stage_index, i, o, pop_dock + (uint32_t)i / (uint32_t)n_per_replica);
+  } else {
+    reset_env<R, MODE>(st, uniform_block(cfg), uniform_block(smp), handoff, opts, stage_index, i, o);
+  }
   if (obs) store_obs_row(obs, i, o, obs_stride);
 }
 
@@ -442,7 +450,8 @@ struct kp1_env {
   double* opt_scratch = nullptr;  // 4*[N][7] + [N][6] doubles for explicit reset options / set_state
   const int32_t* stage_ptr = nullptr;  // kp1_bind_stage_ptr
   const kp1_curriculum_state* pop_states = nullptr;   // kp1_bind_population_stages: K trackers, env i on tracker i / (n / pop_replicas)
-  int32_t pop_replicas = 0;
+  kp1_dock_curriculum_state* pop_dock_states = nullptr;   // kp1_dock_curriculum_create_population: K trackers, then their K live stage records
+  int32_t pop_replicas = 0;   // K of whichever population is bound
   int32_t obs_stride = KP1_OBS_DIM;    // kp1_set_obs_stride
   void* comps = nullptr;          // R[64][N] when enabled
   bool comps_enabled = false;
@@ -511,6 +520,11 @@ int seed_streams(kp1_env* e, uint64_t seed0, uint64_t first_env_id) {
   return seed_streams_by(e, [=](int64_t i) { return seed0 + first_env_id + (uint64_t)i; });
 }
 
+// the K live stage records of a bound dock population (kp1_dock_curriculum_create_population), or nullptr
+const kp1_dock_curriculum_stage* dock_population_live(const kp1_env* e) {
+  return e->pop_dock_states ? reinterpret_cast<const kp1_dock_curriculum_stage*>(e->pop_dock_states + e->pop_replicas) : nullptr;
+}
+
 template <typename R>
 StepArgs<R> make_step_args(kp1_env* e, const void* actions, float* obs, void* reward, uint8_t* done, float* terminal_obs, int auto_reset) {
   StepArgs<R> a;
@@ -530,6 +544,7 @@ StepArgs<R> make_step_args(kp1_env* e, const void* actions, float* obs, void* re
   a.stage_ptr = e->cfg.curriculum_enabled ? e->stage_ptr : nullptr;
   a.pop_states = e->pop_states;
   a.n_per_replica = e->pop_replicas > 0 ? e->n / e->pop_replicas : 0;
+  a.pop_dock = dock_population_live(e);
   return a;
 }
 
@@ -540,6 +555,18 @@ int launch_step(kp1_env* e, const void* actions, float* obs, void* reward, uint8
   const dim3 grid((unsigned)((e->n + block - 1) / block));
   const bool comps = e->comps_enabled && e->comps;
   const size_t lds = sizeof(float) * OBS_TILE_FLOATS * (size_t)(block / 64);   // one observation tile per wave (store_obs_tile)
+  if (e->pop_dock_states) {
+    // per-replica dock stages: the f32 dock form (kp1_dock_curriculum_create_population checks type and mode; kp1_set_mode may change the mode)
+    if (e->mode != KP1_MODE_DOCK) return fail(KP1_ERR_UNSUPPORTED, "a dock population env handle steps in the dock mode only");
+    if constexpr (std::is_same<R, float>::value) {
+      if (comps) hipLaunchKernelGGL((kp1_step_kernel<float, KP1_MODE_DOCK, true, true>), grid, dim3(block), lds, e->stream, a);
+      else hipLaunchKernelGGL((kp1_step_kernel<float, KP1_MODE_DOCK, false, true>), grid, dim3(block), lds, e->stream, a);
+      HIP_TRY(kp1::launch_status());
+      return KP1_OK;
+    } else {
+      return fail(KP1_ERR_UNSUPPORTED, "a population env handle is f32");
+    }
+  }
   if (e->pop_states) {
     // per-replica stages: only the f32 approach form exists (kp1_bind_population_stages checks type and mode; kp1_set_mode may change the
     // mode later).  Without curriculum stages the stage is never read, and the ordinary form below does the same work.
@@ -570,12 +597,21 @@ template <typename R>
 int launch_reset(kp1_env* e, const uint8_t* mask, const ResetOptsDev& opts, int mode, float* obs) {
   const int block = block_for(e->n);
   const dim3 grid((unsigned)((e->n + block - 1) / block));
-  if (mode == KP1_MODE_DOCK)
+  const kp1_dock_curriculum_stage* live = dock_population_live(e);
+  const int n_per_replica = e->pop_replicas > 0 ? e->n / e->pop_replicas : 0;
+  if (mode == KP1_MODE_DOCK && live) {
+    // a dock population samples each replica's resets with its own live stage (the shared config holds stage 0 only)
+    if constexpr (std::is_same<R, float>::value)
+      hipLaunchKernelGGL((kp1_reset_kernel<float, KP1_MODE_DOCK, true>), grid, dim3(block), 0, e->stream, state_of<float>(e),
+                         (const DevCfg<float>*)e->dev_cfg, e->dev_smp, e->dev_handoff, mask, opts, e->stage, obs, e->obs_stride, live, n_per_replica);
+    else
+      return fail(KP1_ERR_UNSUPPORTED, "a population env handle is f32");
+  } else if (mode == KP1_MODE_DOCK)
     hipLaunchKernelGGL((kp1_reset_kernel<R, KP1_MODE_DOCK>), grid, dim3(block), 0, e->stream, state_of<R>(e),
-                       (const DevCfg<R>*)e->dev_cfg, e->dev_smp, e->dev_handoff, mask, opts, e->stage, obs, e->obs_stride);
+                       (const DevCfg<R>*)e->dev_cfg, e->dev_smp, e->dev_handoff, mask, opts, e->stage, obs, e->obs_stride, nullptr, 0);
   else
     hipLaunchKernelGGL((kp1_reset_kernel<R, KP1_MODE_APPROACH>), grid, dim3(block), 0, e->stream, state_of<R>(e),
-                       (const DevCfg<R>*)e->dev_cfg, e->dev_smp, e->dev_handoff, mask, opts, e->stage, obs, e->obs_stride);
+                       (const DevCfg<R>*)e->dev_cfg, e->dev_smp, e->dev_handoff, mask, opts, e->stage, obs, e->obs_stride, nullptr, 0);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
@@ -676,6 +712,7 @@ int env_step_args_f32(kp1_env* e, void* out, size_t out_bytes, const void* actio
   if (e->real_type != KP1_REAL_F32) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step runs on the fp32 handle");
   if (e->comps_enabled && e->comps) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step does not record reward components");
   if (e->pop_states) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step has no per-replica stage (population env handle)");
+  if (e->pop_dock_states) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step has no per-replica dock stage (dock population env handle)");
   if (out_bytes != sizeof(StepArgs<float>)) return fail(KP1_ERR_INVALID, "StepArgs<float> layout mismatch between translation units");
   const StepArgs<float> a = make_step_args<float>(e, actions, obs, reward, done, terminal_obs, auto_reset);
   std::memcpy(out, &a, sizeof a);
@@ -795,10 +832,11 @@ int kp1_bind_stage_ptr(kp1_env* e, const int32_t* stage_dev) {
 int kp1_bind_population_stages(kp1_env* e, const kp1_curriculum_state* states_dev, int32_t n_replicas) {
   if (!e) return fail(KP1_ERR_INVALID, "env is NULL");
   if (!states_dev) {
+    if (e->pop_states) e->pop_replicas = 0;   // (a bound dock population keeps its replica count)
     e->pop_states = nullptr;
-    e->pop_replicas = 0;
     return KP1_OK;
   }
+  if (e->pop_dock_states) return fail(KP1_ERR_UNSUPPORTED, "kp1_bind_population_stages: the handle is bound to a dock population");
   if (n_replicas < 1 || e->n % n_replicas != 0)
     return fail(KP1_ERR_INVALID, "kp1_bind_population_stages: the env count must be a multiple of the replica count");
   if (e->real_type != KP1_REAL_F32) return fail(KP1_ERR_UNSUPPORTED, "kp1_bind_population_stages: a population env handle is f32");

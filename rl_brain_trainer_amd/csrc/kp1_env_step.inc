@@ -115,16 +115,23 @@ __device__ __forceinline__ void store_obs_tile(float* __restrict__ obs, int64_t 
 }
 
 // Sampling half of reset(): fills a ResetSample in fp64.  KP1/envs/reset_samplers.py:168-210, 426-515.
-template <int MODE>
+// LIVE (dock population handle): the values a dock reverse-curriculum stage overrides come from this env's replica's live stage record `live`
+// (per-lane loads: a replica boundary can fall inside a wave) as dock_apply_stage would have written them into the sampler; the rest from `s`.
+template <int MODE, bool LIVE = false>
 __device__ __forceinline__ void sample_reset(const DevSampler& __restrict__ s, const kp1_handoff_state* __restrict__ handoff, Pcg& rng,
-                                          int stage_index, ResetSample& o, bool& has_dq_pa, bool& has_goal_pose) {
+                                          int stage_index, ResetSample& o, bool& has_dq_pa, bool& has_goal_pose,
+                                          const kp1_dock_curriculum_stage* __restrict__ live = nullptr) {
   has_dq_pa = false;
   has_goal_pose = false;
   o.stage = 0;
   if constexpr (MODE == KP1_MODE_DOCK) {
     const kp1_dock_reset& c = s.dr;
-    if (c.handoff_state_probability > 0.0 && s.n_handoff > 0 && pcg_double(rng) < c.handoff_state_probability) {
-      const kp1_handoff_state& h = handoff[s.handoff_offset + pcg_integers(rng, 0, s.n_handoff)];
+#define KP1_DOCK_STAGE(f) (LIVE ? live->f : c.f)
+    // dock_apply_stage's handoff slice: only a stage with handoff_count >= 0 replaces the sampler's own
+#define KP1_DOCK_SLICE(stage_f, own_f) (LIVE && live->handoff_count >= 0 ? live->stage_f : s.own_f)
+    if (KP1_DOCK_STAGE(handoff_state_probability) > 0.0 && KP1_DOCK_SLICE(handoff_count, n_handoff) > 0 &&
+        pcg_double(rng) < KP1_DOCK_STAGE(handoff_state_probability)) {
+      const kp1_handoff_state& h = handoff[KP1_DOCK_SLICE(handoff_offset, handoff_offset) + pcg_integers(rng, 0, KP1_DOCK_SLICE(handoff_count, n_handoff))];
       for (int k = 0; k < NJ; ++k) {
         o.initial_q[k] = h.initial_q[k];
         o.goal_q[k] = h.goal_q[k];
@@ -143,7 +150,7 @@ __device__ __forceinline__ void sample_reset(const DevSampler& __restrict__ s, c
     } else {
       sample_stage_joint_target(s, rng, c.goal_q, c.goal_noise, o.goal_q);
     }
-    if (c.close_bucket_probability > 0.0 && pcg_double(rng) < c.close_bucket_probability) {
+    if (KP1_DOCK_STAGE(close_bucket_probability) > 0.0 && pcg_double(rng) < KP1_DOCK_STAGE(close_bucket_probability)) {
       // _sample_close_bucket_initial_q :474-515 (fp64 FK decides acceptance)
       double goal_pose[6];
       fk_pose6<double>(s.fk, o.goal_q, goal_pose);
@@ -154,20 +161,20 @@ __device__ __forceinline__ void sample_reset(const DevSampler& __restrict__ s, c
       bool accepted = false;
       for (int a = 0; a < attempts && !accepted; ++a) {
         double d[NJ], cand[NJ], pose[6], pe[3], oe[3], pn, on;
-        pcg_uniform_sym7(rng, c.close_init_q_noise, d);
+        pcg_uniform_sym7(rng, KP1_DOCK_STAGE(close_init_q_noise), d);
         for (int k = 0; k < NJ; ++k) cand[k] = dclip(o.goal_q[k] + d[k], s.lower[k], s.upper[k]);
         fk_pose6<double>(s.fk, cand, pose);
         pose_error_norms<double>(pose, goal_pose, pe, oe, &pn, &on);
-        if (c.close_bucket_min_pos_error_m <= pn && pn <= c.close_bucket_max_pos_error_m &&
-            on >= c.close_bucket_min_ori_error_rad && on <= c.close_bucket_max_ori_error_rad) {
+        if (KP1_DOCK_STAGE(close_bucket_min_pos_error_m) <= pn && pn <= KP1_DOCK_STAGE(close_bucket_max_pos_error_m) &&
+            on >= c.close_bucket_min_ori_error_rad && on <= KP1_DOCK_STAGE(close_bucket_max_ori_error_rad)) {
           for (int k = 0; k < NJ; ++k) o.initial_q[k] = cand[k];
           accepted = true;
           break;
         }
         double bd;
-        if (pn < c.close_bucket_min_pos_error_m) bd = c.close_bucket_min_pos_error_m - pn;
-        else if (pn > c.close_bucket_max_pos_error_m) bd = pn - c.close_bucket_max_pos_error_m;
-        else bd = fmax(fmax(c.close_bucket_min_ori_error_rad - on, on - c.close_bucket_max_ori_error_rad), 0.0);
+        if (pn < KP1_DOCK_STAGE(close_bucket_min_pos_error_m)) bd = KP1_DOCK_STAGE(close_bucket_min_pos_error_m) - pn;
+        else if (pn > KP1_DOCK_STAGE(close_bucket_max_pos_error_m)) bd = pn - KP1_DOCK_STAGE(close_bucket_max_pos_error_m);
+        else bd = fmax(fmax(c.close_bucket_min_ori_error_rad - on, on - KP1_DOCK_STAGE(close_bucket_max_ori_error_rad)), 0.0);
         if (bd < best_dist) {
           for (int k = 0; k < NJ; ++k) best_q[k] = cand[k];
           have_best = true;
@@ -180,8 +187,10 @@ __device__ __forceinline__ void sample_reset(const DevSampler& __restrict__ s, c
       return;
     }
     double d[NJ];
-    pcg_uniform_sym7(rng, c.init_q_noise, d);
+    pcg_uniform_sym7(rng, KP1_DOCK_STAGE(init_q_noise), d);
     for (int k = 0; k < NJ; ++k) o.initial_q[k] = dclip(o.goal_q[k] + d[k], s.lower[k], s.upper[k]);
+#undef KP1_DOCK_SLICE
+#undef KP1_DOCK_STAGE
   } else {
     if (s.rs.enabled && s.curriculum_enabled && s.n_stages > 0) {
       sample_random_start_pair(s, rng, stage_index, o);
@@ -201,10 +210,11 @@ __device__ __forceinline__ void sample_reset(const DevSampler& __restrict__ s, c
 }
 
 // reset() for one env.  Writes the state and returns the first observation in o[].
-template <typename R, int MODE>
+// LIVE: a dock population handle, sampling with this env's replica's live stage record `live` (sample_reset).
+template <typename R, int MODE, bool LIVE = false>
 __device__ __forceinline__ void reset_env(const EnvState<R>& st, const DevCfg<R>& __restrict__ cfg, const DevSampler& __restrict__ smp,
                                           const kp1_handoff_state* __restrict__ handoff, const ResetOptsDev& opts, int stage_index,
-                                          int64_t i, float* o) {
+                                          int64_t i, float* o, const kp1_dock_curriculum_stage* __restrict__ live = nullptr) {
   const int64_t n = st.n;
   R q[NJ], dq[NJ], pa[NJ], goal_q[NJ], goal_pose[6], ee[6];
   double q64[NJ], gq64[NJ];   // the kinematic chain is fp64 on both handles (DevCfg::Kin)
@@ -219,7 +229,7 @@ __device__ __forceinline__ void reset_env(const EnvState<R>& st, const DevCfg<R>
   } else {
     rng_load(st.rng64, st.rng32, n, i, rng);
     rng_used = true;
-    sample_reset<MODE>(smp, handoff, rng, stage_index, rs, has_dq_pa, sampled_goal_pose);
+    sample_reset<MODE, LIVE>(smp, handoff, rng, stage_index, rs, has_dq_pa, sampled_goal_pose, live);
     have_sample = true;
 #pragma unroll
     for (int k = 0; k < NJ; ++k) q64[k] = rs.initial_q[k];
@@ -318,6 +328,9 @@ struct StepArgs {
   // appended so the fields above keep their kernarg offsets
   const kp1_curriculum_state* pop_states;
   int n_per_replica;
+  // dock population handle (kp1_dock_curriculum_create_population): env i steps and resets with the live stage record of replica
+  // i / n_per_replica.  Read only by the dock POP kernels; appended like the two above
+  const kp1_dock_curriculum_stage* pop_dock;
 };
 
 // One env step of lane i, auto-reset of a finished env included (VecEnv semantics).
@@ -329,8 +342,10 @@ struct StepArgs {
 // `act_src`: this env's 7 action values (a.actions + 7 i in kp1_step_kernel; the rollout kernel hands them over through LDS).
 // `o`: the observation row after the step (after the reset, for a finished env under auto-reset) -- left to the caller, whose whole wave
 // stores its rows together (store_obs_tile).
-// POP: a population handle, whose env i takes its auto-reset stage from its own replica's tracker (a replica boundary can fall inside a wave,
-// so the stage is a per-lane load).
+// POP: a population handle (f32).  Approach mode: env i takes its auto-reset stage from its own replica's tracker (a replica boundary can fall
+// inside a wave, so the stage is a per-lane load).  Dock mode: env i reads what a dock reverse-curriculum stage overrides -- the fp64 action
+// delta scale and the two residual limits here, the dock reset values and the handoff slice in the reset branch -- from its replica's live
+// stage record a.pop_dock[i / n_per_replica] (per-lane loads), converted as dock_apply_stage converts them for the shared config.
 template <typename R, int MODE, bool COMPS, bool POP = false>
 __device__ __forceinline__ void step_env_lane(const StepArgs<R>& a, const int64_t i, const R* __restrict__ act_src, float* __restrict__ o) {
   const int64_t n = a.st.n;
@@ -364,22 +379,27 @@ __device__ __forceinline__ void step_env_lane(const StepArgs<R>& a, const int64_
   pose_error_norms<R>(ee, goal, pe, oe, &prev_pos, &prev_ori);  // :219-221
   KP1_ETR_PIN(2, prev_pos, prev_ori)
 
+  constexpr bool LIVE = POP && MODE == KP1_MODE_DOCK;
+  const kp1_dock_curriculum_stage* __restrict__ live = nullptr;
+  if constexpr (LIVE) live = a.pop_dock + (uint32_t)i / (uint32_t)a.n_per_replica;
   R dyn_limit = kp_clip<R>(cfg.env.dock_residual_action_limit, Z, (R)1);
   R dyn_dqc = kp_max<R>(cfg.env.dock_delta_q_change_limit_scale, Z);
   if constexpr (MODE == KP1_MODE_DOCK) {  // :224-228, 508-528
+    const R residual_limit = LIVE ? (R)live->dock_residual_action_limit : cfg.env.dock_residual_action_limit;
+    const R dqc_limit_scale = LIVE ? (R)live->dock_delta_q_change_limit_scale : cfg.env.dock_delta_q_change_limit_scale;
     dyn_limit = kp_clip<R>(interpolate_control<R>(prev_pos, cfg.env.dock_dynamic_action_limit_near_pos_threshold_m,
                                                   cfg.env.dock_dynamic_action_limit_far_pos_threshold_m,
                                                   cfg.env.dock_dynamic_residual_action_limit_near,
-                                                  cfg.env.dock_dynamic_residual_action_limit_far, cfg.env.dock_residual_action_limit), Z, (R)1);
+                                                  cfg.env.dock_dynamic_residual_action_limit_far, residual_limit), Z, (R)1);
     dyn_dqc = kp_max<R>(interpolate_control<R>(prev_pos, cfg.env.dock_dynamic_action_limit_near_pos_threshold_m,
                                                cfg.env.dock_dynamic_action_limit_far_pos_threshold_m,
                                                cfg.env.dock_dynamic_delta_q_change_limit_scale_near,
-                                               cfg.env.dock_dynamic_delta_q_change_limit_scale_far, cfg.env.dock_delta_q_change_limit_scale), Z);
+                                               cfg.env.dock_dynamic_delta_q_change_limit_scale_far, dqc_limit_scale), Z);
 #pragma unroll
     for (int k = 0; k < NJ; ++k) act[k] = kp_clip<R>(act[k], -dyn_limit, dyn_limit);
   }
   const bool prev_in_near = is_near_goal<R>(cfg, prev_pos, prev_ori);  // :231
-  double scale = cfg.kin.action_delta_scale;                           // :232-236
+  double scale = LIVE ? live->action_delta_scale : cfg.kin.action_delta_scale;   // :232-236
   if constexpr (MODE == KP1_MODE_DOCK) {
     if (cfg.kin.dock_action_delta_scale > 0.0) scale = cfg.kin.dock_action_delta_scale;
   } else {
@@ -482,9 +502,9 @@ __device__ __forceinline__ void step_env_lane(const StepArgs<R>& a, const int64_
     ResetOptsDev none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     int stage = a.stage_index;
     const DevSampler& smp = uniform_block(a.smp);
-    if constexpr (POP) stage = kp_clipi(a.pop_states[(uint32_t)i / (uint32_t)a.n_per_replica].stage_index, 0, kp_maxi(smp.n_stages - 1, 0));
+    if constexpr (POP && !LIVE) stage = kp_clipi(a.pop_states[(uint32_t)i / (uint32_t)a.n_per_replica].stage_index, 0, kp_maxi(smp.n_stages - 1, 0));
     else if (a.stage_ptr) stage = kp_clipi(*a.stage_ptr, 0, kp_maxi(smp.n_stages - 1, 0));
-    reset_env<R, MODE>(st, cfg, smp, a.handoff, none, stage, i, o);
+    reset_env<R, MODE, LIVE>(st, cfg, smp, a.handoff, none, stage, i, o, live);
     // info of the finished episode stays readable (SB3 infos[i] of a done env is the terminal info)
     st.r(F_POS_ERR, i) = curr_pos;
     st.r(F_ORI_ERR, i) = curr_ori;

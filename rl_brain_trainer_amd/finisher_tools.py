@@ -169,7 +169,9 @@ class DockReverseCurriculum:
         return self.stages[index].get("name", f"stage_{index}")
 
     def summary(self) -> dict[str, object]:
-        st = self.read()
+        return self._summary_of(self.read())
+
+    def _summary_of(self, st: _State) -> dict[str, object]:
         n, cap, head = int(st.ring_len), int(st.window_episodes), int(st.ring_head)
         wins = sum(int(st.ring[(head + j) % cap]) for j in range(n))
         events = [st.events[k] for k in range(min(int(st.n_events), MAX_HISTORY))]
@@ -183,6 +185,139 @@ class DockReverseCurriculum:
         if self.env is not None and self._st.value:
             self.env.L.kp1_dock_curriculum_destroy(self.env._handle, self._st)
             self._st = C.c_void_p()
+
+
+class DockReverseCurriculumPopulation(DockReverseCurriculum):
+    """K DockReverseCurriculum trackers of one stage table, one per replica of a dock-mode ArmKinematicPopulationVecEnv (include/kp1_ppo.h,
+    kp1_dock_curriculum_*_population).  ``attach(env)`` builds the stage buffers and the resolved table once, applies stage 0 to the shared
+    config and binds the handle: env i then steps and resets with replica i / N's live stage record, which only that replica's promotions
+    rewrite.  ONE ``observe(dones[K N])`` launch per env step; like ``DockReverseCurriculum.observe`` it ignores ``steps_per_call`` and advances
+    every clock by N (so the capture warm-up moves each clock by N, as it moves a single tracker's).
+
+    Each replica owns an ``EnvConfig`` copy of the attached env's config (concatenated handoff list included): ``replica(k).read()`` brings
+    copy k in step with tracker k's stage, as ``DockReverseCurriculum.read()`` does with a single run's config, so replica k is evaluated on
+    its own stage.  ``replica(k)`` has ``read()``, ``current_stage_index`` and ``summary()`` with DockReverseCurriculum's keys."""
+
+    def __init__(self, *, stages: list[dict[str, object]], window_episodes: int, n_replicas: int, handoff_base_dirs: tuple[Path, ...] = ()) -> None:
+        from .vec_env import MAX_REPLICAS
+
+        super().__init__(stages=stages, window_episodes=window_episodes, handoff_base_dirs=handoff_base_dirs)
+        if not 1 <= int(n_replicas) <= MAX_REPLICAS:
+            raise ValueError(f"DockReverseCurriculumPopulation holds 1 to {MAX_REPLICAS} trackers (got {n_replicas})")
+        self.K = int(n_replicas)
+        self.configs: list[kcfg.EnvConfig] = []
+
+    def attach(self, env: Any) -> None:
+        from . import native
+
+        if not getattr(env, "is_population", False):
+            raise TypeError("DockReverseCurriculumPopulation tracks the replicas of an ArmKinematicPopulationVecEnv")
+        if env.config.mode_name != "dock":
+            raise ValueError("the dock reverse curriculum drives a dock-mode env")
+        if getattr(env, "K", self.K) != self.K or env.n_envs % self.K != 0:
+            raise ValueError(f"a population env of {env.n_envs} envs does not split into this tracker's {self.K} replicas")
+        L = env.L
+        vp, i32 = C.c_void_p, C.c_int32
+        L.kp1_dock_curriculum_create_population.argtypes = [vp, C.POINTER(_Stage), i32, i32, i32, C.POINTER(vp)]
+        L.kp1_dock_curriculum_observe_population.argtypes = [vp, vp, vp, i32, i32, vp]
+        L.kp1_dock_curriculum_read_replica.argtypes = [vp, vp, i32, i32, C.POINTER(_State), vp]
+        L.kp1_dock_curriculum_destroy.argtypes = [vp, vp]
+        buffers = self.stage_buffers(env.config)
+        if buffers is not None:
+            env.set_handoff_states([state for stage_states in buffers for state in stage_states])
+        table = self.resolved_stages(env.config, buffers)
+        with torch.cuda.device(env.device):
+            native.check(L.kp1_dock_curriculum_create_population(env._handle, table, len(self.stages), self.window_episodes, self.K, C.byref(self._st)))
+        self.env = env
+        env.dock_population = self
+        env.launch_args_version += 1     # a captured rollout froze the step kernel (and its stage source) into the graph
+        self.configs = [env.config.clone() for _ in range(self.K)]
+
+    on_training_start = attach
+
+    def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
+        """dones: the K N done bytes of one population step (replica-major); every clock advances by N whatever ``steps_per_call`` says"""
+        from . import native
+
+        if dones.numel() % self.K != 0 or dones.dtype != torch.uint8 or not dones.is_contiguous():
+            raise ValueError(f"observe() takes the contiguous uint8 done bytes of all {self.K} replicas")
+        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        native.check(self.env.L.kp1_dock_curriculum_observe_population(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), dones.numel() // self.K,
+                                                                       self.K, C.c_void_p(stream)))
+
+    def observe_chunk(self, dones_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
+        raise TypeError("the dock population tracker has no data-parallel form")
+
+    def read(self, k: int = 0) -> _State:
+        """tracker k; brings replica k's config copy in step with its stage (the handle's shared config is left as it is)"""
+        from . import native
+
+        out = _State()
+        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        native.check(self.env.L.kp1_dock_curriculum_read_replica(self.env._handle, self._st, self.K, int(k), C.byref(out), C.c_void_p(stream)))
+        live, c = out.stages[out.stage_index], self.configs[int(k)].c
+        for key in _STAGE_ENV_KEYS:
+            setattr(c.env, key, float(getattr(live, key)))
+        for key in _STAGE_RESET_SCALARS:
+            setattr(c.dock_reset, key, float(getattr(live, key)))
+        for key in _STAGE_RESET_VECTORS:
+            getattr(c.dock_reset, key)[:] = list(getattr(live, key)[:])
+        return out
+
+    @property
+    def current_stage_index(self) -> int:
+        raise TypeError("a population tracker has one stage per replica: use replica(k).current_stage_index")
+
+    def live_records(self) -> list[_Stage]:
+        """host copies of the K live stage records the population kernels read (record k = the stage tracker k is on)"""
+        from .vec_env import _view
+
+        ptr = self._st.value + self.K * C.sizeof(_State)
+        raw = _view(ptr, (self.K * C.sizeof(_Stage),), "|u1", self.env.device).cpu().numpy().tobytes()
+        return [_Stage.from_buffer_copy(raw, k * C.sizeof(_Stage)) for k in range(self.K)]
+
+    def summary(self, k: int = 0) -> dict[str, object]:
+        return self._summary_of(self.read(k))
+
+    def replica(self, k: int) -> "DockReverseCurriculumReplica":
+        if not 0 <= int(k) < self.K:
+            raise IndexError(f"replica {k} of a population of {self.K}")
+        return DockReverseCurriculumReplica(self, int(k))
+
+    def close(self) -> None:
+        if self.env is not None and self._st.value:
+            self.env.L.kp1_dock_curriculum_destroy(self.env._handle, self._st)
+            self._st = C.c_void_p()
+            self.env.dock_population = None
+            self.env.launch_args_version += 1
+
+
+class DockReverseCurriculumReplica:
+    """Replica k of a DockReverseCurriculumPopulation: read() / current_stage_index / summary() of its tracker, and ``config``, the replica's
+    own EnvConfig copy that read() keeps in step.  The population observes all replicas at once."""
+
+    def __init__(self, pop: DockReverseCurriculumPopulation, k: int) -> None:
+        self.pop, self.k = pop, int(k)
+
+    @property
+    def config(self) -> kcfg.EnvConfig:
+        return self.pop.configs[self.k]
+
+    def attach(self, env: Any) -> None:
+        """(the population tracker is attached to the population env)"""
+
+    def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
+        raise TypeError("replica trackers are observed through DockReverseCurriculumPopulation.observe (one launch for all replicas)")
+
+    def read(self) -> _State:
+        return self.pop.read(self.k)
+
+    @property
+    def current_stage_index(self) -> int:
+        return int(self.read().stage_index)
+
+    def summary(self) -> dict[str, object]:
+        return self.pop.summary(self.k)
 
 
 def build_finisher_handoff_state_buffer(*, approach_policy, approach_cfg: kcfg.EnvConfig, artifact_root: str | Path | None = None, episodes: int = 500,

@@ -275,6 +275,89 @@ class OneHandlePopulationPPO(PopulationPPO):
         if self.pop_curriculum is not None:
             self.pop_curriculum.observe(self.done_buf[0].zero_(), 0)
 
+    @staticmethod
+    def check_init_checkpoint(path: str) -> dict[str, int]:
+        """refuse (on the host, before any device work) a checkpoint whose Adam state carries teacher-anchor actor steps; returns what a
+        population must share with the other replicas' checkpoints: hidden width, Adam step count (0 without an Adam state), num_timesteps"""
+        import math
+
+        from . import checkpoint
+        from .ppo import load_adam_state, param_spec
+
+        hidden, obs_dim = (int(v) for v in checkpoint.load_policy_state_dict(path)["mlp_extractor.policy_net.0.weight"].shape)
+        out = {"hidden": hidden, "adam_steps": 0}
+        opt = checkpoint.load_optimizer_state_dict(path)
+        if opt and opt.get("state"):
+            spec = param_spec(hidden, obs_dim)
+            n = sum(math.prod(shape) for _, shape in spec)
+            adam_t, extra = load_adam_state(opt, spec, torch.zeros(n), torch.zeros(n))
+            if extra:
+                raise ValueError(f"{path} carries {extra} teacher-anchor actor steps (actor_extra_steps); a population keeps one Adam step "
+                                 "count for every tensor and cannot resume it")
+            out["adam_steps"] = int(adam_t)
+        try:
+            out["num_timesteps"] = int(checkpoint.load_data(path).get("num_timesteps", 0))
+        except KeyError:        # an archive without SB3's data member (a bare policy + optimizer zip)
+            out["num_timesteps"] = 0
+        return out
+
+    @classmethod
+    def check_init_checkpoints(cls, paths: list[str]) -> dict[str, int]:
+        """check_init_checkpoint of every replica's checkpoint, and the refusals of a per-replica start: the replicas must agree on the Adam
+        step count and num_timesteps (a population shares one of each), and the width must be one a population trains (64 or 128)"""
+        infos = [cls.check_init_checkpoint(p) for p in paths]
+        for key, what in (("adam_steps", "Adam step counts"), ("num_timesteps", "num_timesteps"), ("hidden", "hidden widths")):
+            values = sorted({i[key] for i in infos})
+            if len(values) > 1:
+                raise ValueError(f"the replicas' checkpoints differ in their {what} ({values}); a population shares one")
+        if infos and infos[0]["hidden"] not in (64, 128):
+            raise ValueError(f"the checkpoints hold a 2x{infos[0]['hidden']} policy; a population trains 2x64 or 2x128 nets")
+        return infos[0] if infos else {}
+
+    def load_init_checkpoint(self, path: str) -> dict[str, Any]:
+        """``PPO.load_checkpoint(path, restore_timesteps=True, restore_hyperparameters=True)`` into every replica (train_route's
+        --init-checkpoint, train_dock's --seeds --resume-from <zip>): weights, Adam moments, the Adam step count, the step clock and the
+        saved algorithm constants; the learning rate stays the config's.  A checkpoint with teacher-anchor actor steps is refused: a
+        population has one Adam step count for every tensor."""
+        return self.load_init_checkpoints([path] * self.K)
+
+    def load_init_checkpoints(self, paths: list[str]) -> dict[str, Any]:
+        """the per-replica form: replica k starts from ``paths[k]`` (weights and Adam moments); the step count, the clock and the saved
+        algorithm constants are shared, so check_init_checkpoints refuses checkpoints that disagree on them"""
+        from . import checkpoint
+        from .ppo import load_adam_state, restore_saved_hyperparameters
+
+        if len(paths) != self.K:
+            raise ValueError(f"{len(paths)} checkpoints for {self.K} replicas")
+        if self.adam_t or self.n_train_calls or self._epoch_graph is not None:
+            raise RuntimeError("load_init_checkpoint must happen before the first update")
+        self.check_init_checkpoints(paths)
+        restored: dict[str, Any] = {"policy": True, "optimizer": False}
+        for k, path in enumerate(paths):
+            if k > 0 and path == paths[0]:
+                self.policies[k].load_state_dict(self.policies[0].state_dict())
+                if restored["optimizer"]:
+                    self.adam_m[k].copy_(self.adam_m[0])
+                    self.adam_v[k].copy_(self.adam_v[0])
+                continue
+            self.policies[k].load_state_dict(checkpoint.load_policy_state_dict(path))
+            opt = checkpoint.load_optimizer_state_dict(path)
+            if opt and opt.get("state"):
+                adam_t, _ = load_adam_state(opt, self.policies[k].spec, self.adam_m[k], self.adam_v[k])
+                self.adam_t = adam_t
+                restored.update({"optimizer": True, "adam_steps": adam_t, "actor_extra_steps": 0})
+        self._mlp.pack(self.flat)
+        self._mlp.set_step_count(self.adam_t)
+        data = checkpoint.load_data(paths[0])
+        self.num_timesteps = int(data.get("num_timesteps", 0))
+        restored["num_timesteps"] = self.num_timesteps
+        saved_epochs = data.get("n_epochs")
+        if isinstance(data.get("_n_updates"), int) and isinstance(saved_epochs, int) and saved_epochs > 0:
+            self.n_train_calls = int(data["_n_updates"]) // saved_epochs
+        restored["hyperparameters"] = restore_saved_hyperparameters(self.cfg, data)
+        self.cfgs = [dataclasses.replace(self.cfg, seed=s) for s in self.seeds]
+        return restored
+
 
 class ApproachPopulationPPO(OneHandlePopulationPPO):
     """K Approach runs of one PPOConfig on ONE ArmKinematicPopulationVecEnv (vec_env.py) with ONE PointCurriculumPopulation
@@ -311,8 +394,8 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
     whatever K is.  Everything else -- noise, truncation bootstrap, the epoch body, graph capture -- is PopulationPPO's.
 
     Replica k is bit-identical to ``PPO(RouteVecEnv(..., seed=s_k), curriculum=RoutePrefixCurriculumDevice)`` on the same config
-    (tests/test_route_population_gpu.py).  ``load_init_checkpoint`` starts every replica from one checkpoint as train_route does.  The caller
-    owns (and closes) the env and the tracker."""
+    (tests/test_route_population_gpu.py).  ``load_init_checkpoint`` (OneHandlePopulationPPO's) starts every replica from one checkpoint as
+    train_route does.  The caller owns (and closes) the env and the tracker."""
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
                  teacher_anchor: Any = None) -> None:
@@ -334,57 +417,58 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
         curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
         self._init_population(seeds, cfg, views, curricula, dist, use_graphs)
 
-    @staticmethod
-    def check_init_checkpoint(path: str) -> None:
-        """refuse (on the host, before any device work) a checkpoint whose Adam state carries teacher-anchor actor steps"""
-        import math
+class DockPopulationPPO(OneHandlePopulationPPO):
+    """K Finisher (dock-mode) runs of one PPOConfig on ONE ArmKinematicPopulationVecEnv with ONE DockReverseCurriculumPopulation
+    (finisher_tools.py): a promotion rewrites only its replica's live stage record, which the dock population forms of the step and reset
+    kernels read per env, so replicas on different reverse-curriculum stages share a launch (and a wave).  Without a tracker the env is the
+    plain dock step over K N envs.  Replica k is bit-identical to ``PPO(ArmKinematicVecEnv(..., seed=s_k), curriculum=DockReverseCurriculum)``
+    on the same config (tests/test_dock_population_gpu.py).  ``load_init_checkpoint`` / ``load_init_checkpoints`` start the replicas from one
+    checkpoint or one each (train_dock --seeds --resume-from).  The caller owns (and closes) the env and the tracker."""
 
-        from . import checkpoint
-        from .ppo import load_adam_state, param_spec
+    def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
+                 teacher_anchor: Any = None) -> None:
+        from .finisher_tools import DockReverseCurriculumPopulation
+        from .vec_env import ArmKinematicPopulationVecEnv
 
-        opt = checkpoint.load_optimizer_state_dict(path)
-        if not (opt and opt.get("state")):
-            return
-        hidden, obs_dim = (int(v) for v in checkpoint.load_policy_state_dict(path)["mlp_extractor.policy_net.0.weight"].shape)
-        spec = param_spec(hidden, obs_dim)
-        n = sum(math.prod(shape) for _, shape in spec)
-        _, extra = load_adam_state(opt, spec, torch.zeros(n), torch.zeros(n))
-        if extra:
-            raise ValueError(f"{path} carries {extra} teacher-anchor actor steps (actor_extra_steps); a route population keeps one Adam step "
-                             "count for every tensor and cannot resume it")
+        seeds, dist = self._check_population_args(seeds, cfg, dist, teacher_anchor)
+        if not isinstance(env, ArmKinematicPopulationVecEnv) or env.config.mode_name != "dock":
+            raise TypeError("DockPopulationPPO drives a dock-mode ArmKinematicPopulationVecEnv (one handle for all replicas)")
+        if env.seeds != seeds:
+            raise ValueError(f"the ArmKinematicPopulationVecEnv was made for seeds {env.seeds}, not {seeds}")
+        if curriculum is not None and not isinstance(curriculum, DockReverseCurriculumPopulation):
+            raise TypeError("DockPopulationPPO takes a DockReverseCurriculumPopulation (one tracker launch for all replicas)")
+        if curriculum is not None and curriculum.K != len(seeds):
+            raise ValueError(f"the DockReverseCurriculumPopulation holds {curriculum.K} trackers for {len(seeds)} seeds")
+        self.pop_env, self.pop_curriculum = env, curriculum
+        if curriculum is not None:
+            curriculum.attach(env)
+        K = len(seeds)
+        views = [env.replica(k) for k in range(K)]
+        curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs)
 
-    def load_init_checkpoint(self, path: str) -> dict[str, Any]:
-        """``PPO.load_checkpoint(path, restore_timesteps=True, restore_hyperparameters=True)`` into every replica (train_route's
-        --init-checkpoint): weights, Adam moments, the Adam step count, the step clock and the saved algorithm constants; the learning rate
-        stays the config's.  A checkpoint with teacher-anchor actor steps is refused: a population has one Adam step count for every tensor."""
-        from . import checkpoint
-        from .ppo import load_adam_state, restore_saved_hyperparameters
 
-        if self.adam_t or self.n_train_calls or self._epoch_graph is not None:
-            raise RuntimeError("load_init_checkpoint must happen before the first update")
-        self.check_init_checkpoint(path)
-        sd = checkpoint.load_policy_state_dict(path)
-        for pol in self.policies:
-            pol.load_state_dict(sd)
-        restored: dict[str, Any] = {"policy": True, "optimizer": False}
-        opt = checkpoint.load_optimizer_state_dict(path)
-        if opt and opt.get("state"):
-            adam_t, _ = load_adam_state(opt, self.policies[0].spec, self.adam_m[0], self.adam_v[0])
-            self.adam_m[1:].copy_(self.adam_m[0].expand_as(self.adam_m[1:]))
-            self.adam_v[1:].copy_(self.adam_v[0].expand_as(self.adam_v[1:]))
-            self.adam_t = adam_t
-            restored.update({"optimizer": True, "adam_steps": adam_t, "actor_extra_steps": 0})
-        self._mlp.pack(self.flat)
-        self._mlp.set_step_count(self.adam_t)
-        data = checkpoint.load_data(path)
-        self.num_timesteps = int(data.get("num_timesteps", 0))
-        restored["num_timesteps"] = self.num_timesteps
-        saved_epochs = data.get("n_epochs")
-        if isinstance(data.get("_n_updates"), int) and isinstance(saved_epochs, int) and saved_epochs > 0:
-            self.n_train_calls = int(data["_n_updates"]) // saved_epochs
-        restored["hyperparameters"] = restore_saved_hyperparameters(self.cfg, data)
-        self.cfgs = [dataclasses.replace(self.cfg, seed=s) for s in self.seeds]
-        return restored
+def resolve_resume_population(resume_from: str | None, seeds: list[int]) -> list[str] | None:
+    """train_dock --seeds --resume-from X, resolved on the host: None when X is not given or does not exist (a --seed run then starts from
+    scratch too), [X] * K when X is a checkpoint zip (every seed starts from it), and X/seed_<s>/model_latest.zip per seed when X is the root
+    of an earlier --seeds run.  Refuses a missing seed and, through check_init_checkpoints, checkpoints a population cannot resume together."""
+    from pathlib import Path
+
+    if not resume_from:
+        return None
+    root = Path(resume_from)
+    if root.is_dir():
+        paths = [root / f"seed_{s}" / "model_latest.zip" for s in seeds]
+        missing = [s for s, p in zip(seeds, paths) if not p.is_file()]
+        if missing:
+            raise ValueError(f"--resume-from {root}: no seed_<s>/model_latest.zip for seeds {missing} (a --seeds run root holds one per seed)")
+        out = [str(p) for p in paths]
+    elif root.exists():
+        out = [str(root)] * len(seeds)
+    else:
+        return None
+    OneHandlePopulationPPO.check_init_checkpoints(out)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------- trainer CLI (--seeds)

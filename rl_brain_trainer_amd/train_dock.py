@@ -35,7 +35,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
     seeds.add_argument("--seed", type=int)
     seeds.add_argument("--seeds", help="comma-separated seeds trained together as one population (2x64 / 2x128 nets, one GPU); seed s writes "
                                        "the artefacts of a --seed s run under <artifact-root>/seed_<s>/, plus population_summary.json")
-    p.add_argument("--resume-from")
+    p.add_argument("--resume-from", help="a checkpoint zip; with --seeds also the artifact root of an earlier --seeds run (seed s resumes "
+                                          "from seed_<s>/model_latest.zip)")
     p.add_argument("--n-envs", type=int, default=4096, help="environments per GPU")
     p.add_argument("--n-steps", type=int, default=64)
     p.add_argument("--batch-size", type=int, default=0, help="global minibatch; 0 = n_envs*n_steps*world/64")
@@ -150,42 +151,56 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, cfg: dic
 
 
 def _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root: Path, world: int, device: int) -> dict[str, Any]:
-    """--seeds: the seeds train together as one PopulationPPO; seed s writes what a --seed s run writes, under root/seed_<s>/.  The selection
-    score of population_summary.json is each seed's dock evaluation success rate."""
-    from .population import PopulationPPO, learn_population, parse_seeds, population_summary
+    """--seeds: the seeds train together as one DockPopulationPPO -- one env handle of K x n_envs envs and one tracker launch per env step for
+    all seeds; seed s writes what a --seed s run writes, under root/seed_<s>/, plus population_summary.json.  Every seed is evaluated on its
+    own config copy (its own reverse-curriculum stage).  --resume-from takes a checkpoint zip (every seed starts from it) or the root of an
+    earlier --seeds run (seed s starts from seed_<s>/model_latest.zip).  The selection score of population_summary.json is each seed's dock
+    evaluation success rate."""
+    from .finisher_tools import DockReverseCurriculumPopulation
+    from .population import DockPopulationPPO, learn_population, parse_seeds, population_summary, resolve_resume_population
+    from .vec_env import ArmKinematicPopulationVecEnv
 
     seeds = parse_seeds(args.seeds)
     if world > 1:
         raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
-    if args.resume_from and Path(args.resume_from).exists():
-        raise ValueError("--seeds starts every seed from its own initialisation; it does not resume from a checkpoint")
+    # refusals before any device work: the seeds, the width, and the checkpoints a population cannot resume together
+    resume_paths = resolve_resume_population(args.resume_from, seeds)
     n_envs = args.n_envs
     batch = args.batch_size or max(n_envs * args.n_steps // 64, 64)
     model_kwargs = {k: v for k, v in algo.items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
-    pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=checkpoint.hidden_for_run(args.hidden, None))
+    hidden = checkpoint.hidden_for_run(args.hidden, resume_paths[0] if resume_paths else None)
+    pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=hidden)
+    DockPopulationPPO._check_population_args(seeds, pcfg, None, None)
     cur_cfg = runtime.get("dock_reverse_curriculum", {}) or {}
-
-    def curriculum_factory(seed: int):
-        if not bool(cur_cfg.get("enabled", False)):
-            return None
-        return DockReverseCurriculum(stages=list(cur_cfg.get("stages", [])), window_episodes=int(cur_cfg.get("window_episodes", 100)),
-                                     handoff_base_dirs=base_dirs)
-
-    pop = PopulationPPO(seeds, pcfg, lambda s: ArmKinematicVecEnv(env_cfg, n_envs, device=device, seed=s), curriculum_factory=curriculum_factory)
+    env = ArmKinematicPopulationVecEnv(env_cfg, seeds, n_envs, device=device, mode="dock")
+    curriculum = None
+    if bool(cur_cfg.get("enabled", False)):
+        curriculum = DockReverseCurriculumPopulation(stages=list(cur_cfg.get("stages", [])), window_episodes=int(cur_cfg.get("window_episodes", 100)),
+                                                     n_replicas=len(seeds), handoff_base_dirs=base_dirs)
+    pop = DockPopulationPPO(seeds, pcfg, env, curriculum=curriculum)
+    if resume_paths is not None:
+        pop.load_init_checkpoints(resume_paths)
+        print(f"Resuming dock policies from {args.resume_from}")
     roots = {s: root / f"seed_{s}" for s in seeds}
     for r in roots.values():
         r.mkdir(parents=True, exist_ok=True)
     wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), log_every=args.log_every, tag="ppo-dock-population")
     rows = []
     for k, s in enumerate(seeds):
-        rep, curriculum = pop.replica(k), pop.curricula[k]
-        summ = _final_artifacts(roots[s], rep, env_cfg, args=args, cfg=cfg, curriculum=curriculum, resume=None, n_envs=n_envs, world=1, seed=s,
+        rep = pop.replica(k)
+        cur = curriculum.replica(k) if curriculum is not None else None
+        cfg_k = cur.config if cur is not None else env_cfg
+        resume = resume_paths[k] if resume_paths is not None else args.resume_from
+        summ = _final_artifacts(roots[s], rep, cfg_k, args=args, cfg=cfg, curriculum=cur, resume=resume, n_envs=n_envs, world=1, seed=s,
                                 device=device, wall=wall, extra={"seed": s})
-        rows.append({"seed": s, "artifact_root": str(roots[s]), "final_curriculum_stage": curriculum.current_stage_index if curriculum is not None else None,
+        rows.append({"seed": s, "artifact_root": str(roots[s]), "final_curriculum_stage": cur.current_stage_index if cur is not None else None,
                      "last_update_stats": rep.last_stats, "best_score": summ["dock_eval_summary"]["success_rate"], "model_latest": summ["model_path"]})
     summary = population_summary(pop, rows, wall_seconds=wall, selection="dock evaluation success_rate")
     (root / "population_summary.json").write_text(json.dumps(summary, indent=2))
     pop.close()
+    if curriculum is not None:
+        curriculum.close()
+    env.close()
     return summary
 
 

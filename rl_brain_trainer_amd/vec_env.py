@@ -301,20 +301,22 @@ MAX_REPLICAS = 16     # KP1_CURRICULUM_MAX_REPLICAS / KP1_MLP_MAX_REPLICAS
 
 
 class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
-    """K Approach envs of ``n_per_replica`` envs each in ONE handle: block k = rows [k N, (k + 1) N) is replica k, and is bit for bit
-    ``ArmKinematicVecEnv(config, n_per_replica, seed=seeds[k])`` (env i of replica k owns ``default_rng(seeds[k] + i)``, kp1_seed_blocks).
-    One ``step_into`` covers all K N rows, so a population rollout is one env step launch per step whatever K is -- the [K N, obs_w] buffers
-    are the population rollout's replica-major layout.
+    """K Approach or Finisher (dock-mode) envs of ``n_per_replica`` envs each in ONE handle: block k = rows [k N, (k + 1) N) is replica k, and
+    is bit for bit ``ArmKinematicVecEnv(config, n_per_replica, seed=seeds[k])`` (env i of replica k owns ``default_rng(seeds[k] + i)``,
+    kp1_seed_blocks).  One ``step_into`` covers all K N rows, so a population rollout is one env step launch per step whatever K is -- the
+    [K N, obs_w] buffers are the population rollout's replica-major layout.
 
-    A PointCurriculumPopulation attached to it gives every replica its own curriculum stage: the auto-reset of env i reads the stage of
-    tracker i / N (the population form of the step kernel).  ``reset()`` uses the handle's host stage, which K single handles made from one
-    config share.  f32 and the Approach mode only; the handle keeps its per-block seeds (``seed()`` is refused).  ``replica(k)`` is a view
-    with what PPO's setup, ReplicaView and ``checkpoint.save`` read."""
+    Approach: a PointCurriculumPopulation attached to it gives every replica its own curriculum stage: the auto-reset of env i reads the stage
+    of tracker i / N (the population form of the step kernel).  ``reset()`` uses the handle's host stage, which K single handles made from one
+    config share.  Dock: a DockReverseCurriculumPopulation gives every replica its own reverse-curriculum stage; the step and ``reset()`` of
+    env i read what a stage overrides from replica i / N's live stage record, and the shared config is never rewritten by a promotion.
+    Without a tracker a dock population is the plain dock step over K N envs.  ``mode`` names the config's mode ("approach" by default, "dock"
+    for a Finisher population).  f32 only; the handle keeps its per-block seeds (``seed()`` is refused) and runs its config's mode.  ``replica(k)`` is a view with what PPO's setup, ReplicaView and ``checkpoint.save`` read."""
 
     is_population = True
 
     def __init__(self, config: kcfg.EnvConfig, seeds: list[int], n_per_replica: int, *, device: int | torch.device = 0, real: str = "f32",
-                 reward_components: bool = False) -> None:
+                 reward_components: bool = False, mode: str = "approach") -> None:
         self.seeds = [int(s) for s in seeds]
         if not self.seeds:
             raise ValueError("ArmKinematicPopulationVecEnv needs at least one seed")
@@ -322,9 +324,11 @@ class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
             raise ValueError(f"ArmKinematicPopulationVecEnv holds at most {MAX_REPLICAS} replicas (got {len(self.seeds)} seeds)")
         if len(set(self.seeds)) != len(self.seeds):
             raise ValueError(f"ArmKinematicPopulationVecEnv seeds must be distinct (got {self.seeds})")
-        if config.mode_name != "approach":
-            raise ValueError("ArmKinematicPopulationVecEnv runs the Approach env; a dock-mode config rewrites the handle's config per replica "
-                             "on promotion (DockReverseCurriculum) and needs one handle per replica")
+        if mode not in ("approach", "dock"):
+            raise ValueError(f"ArmKinematicPopulationVecEnv runs the Approach or the dock mode, not {mode!r}")
+        if config.mode_name != mode:
+            raise ValueError(f"ArmKinematicPopulationVecEnv(mode={mode!r}) got a {config.mode_name}-mode config: a dock-mode population is asked for "
+                             "with mode='dock' (its per-replica stages come from a DockReverseCurriculumPopulation, not from K DockReverseCurriculum)")
         if real != "f32":
             raise ValueError("ArmKinematicPopulationVecEnv is the f32 env (the population step kernel has no f64 form)")
         self.K = len(self.seeds)
@@ -334,6 +338,7 @@ class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
         super().__init__(config, self.K * self.n_per_replica, device=device, seed=self.seeds[0], real="f32", reward_components=reward_components)
         seeds_c = (C.c_uint64 * self.K)(*self.seeds)
         native.check(self.L.kp1_seed_blocks(self._handle, C.cast(seeds_c, C.c_void_p), self.K, self.n_per_replica))
+        self.dock_population: Any = None     # the DockReverseCurriculumPopulation attached to a dock-mode population
 
     def replica(self, k: int) -> "ArmKinematicReplicaEnv":
         if not 0 <= int(k) < self.K:
@@ -347,14 +352,20 @@ class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
         raise ValueError("a population env keeps the per-block seeds it was created with (env i of replica k: seeds[k] + i)")
 
     def set_policy_mode(self, mode_name: str) -> None:
-        if mode_name != "approach":
-            raise ValueError("a population env runs the Approach mode only")
+        if mode_name != self.config.mode_name:
+            raise ValueError(f"a population env runs its config's mode ({self.config.mode_name}) only")
         super().set_policy_mode(mode_name)
 
     def reset(self, *, seed: int | None = None, options: dict[str, Any] | None = None, mask: torch.Tensor | None = None) -> torch.Tensor:
-        if options and options.get("policy_mode") not in (None, "approach"):
-            raise ValueError("a population env runs the Approach mode only")
+        if options and options.get("policy_mode") not in (None, self.config.mode_name):
+            raise ValueError(f"a population env runs its config's mode ({self.config.mode_name}) only")
         return super().reset(seed=seed, options=options, mask=mask)
+
+    def apply_dock_training_stage(self, stage_updates: dict[str, Any]) -> None:
+        if self.dock_population is not None:
+            raise ValueError("a DockReverseCurriculumPopulation is attached: each replica's stage lives in its own live record, and a "
+                             "stage applied to the shared config would reach no replica")
+        super().apply_dock_training_stage(stage_updates)
 
 
 class ArmKinematicReplicaEnv:

@@ -19,6 +19,14 @@ its own handle and tracker (PopulationPPO), which is the comparison.
 per env step for all replicas (K in {1, 2, 4, 8, 16} by default).
 
     python tools/population_bench.py --route [--ks 1,2,4,8,16] [--out profiles/r05_route_population_refscale.json]
+
+--dock: the Finisher's reference shape -- the dock_workspace_handoff_noop_ft_12env iteration with the handoff-state buffer of tests/golden,
+12 envs x 256 steps per replica, minibatch 256, 2x64, graphs on -- measured both ways for every K (K in {1, 2, 4, 8, 16} by default): as a
+DockPopulationPPO (one env handle of K x 12 envs and one DockReverseCurriculumPopulation launch per env step) and as the K-handle
+PopulationPPO (one handle and one DockReverseCurriculum per replica).  No shipped YAML has a reverse curriculum, so the tracker runs a small
+synthetic stage table (DOCK_STAGES); --no-curriculum measures the plain dock step without a tracker.
+
+    python tools/population_bench.py --dock [--no-curriculum] [--ks 1,2,4,8,16] [--out profiles/r07_dock_population_refscale.json]
 """
 from __future__ import annotations
 
@@ -96,14 +104,61 @@ def build_route(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_
     return pop
 
 
+DOCK_CONFIG = ROOT / "tests" / "golden" / "configs" / "dock_workspace_handoff_noop_ft_12env_raw.json"
+# a small synthetic reverse curriculum: promotions on episode counts (threshold 0), every overridable value, a per-stage handoff filter
+DOCK_STAGES = [
+    {"name": "close", "min_episodes": 48, "window_episodes": 12, "success_rate_threshold": 0.0, "dock_residual_action_limit": 0.2,
+     "close_bucket_probability": 1.0, "close_bucket_max_pos_error_m": 0.003, "handoff_state_probability": 0.3},
+    {"name": "mid", "min_episodes": 96, "success_rate_threshold": 0.0, "action_delta_scale": 0.012, "close_bucket_probability": 0.5,
+     "handoff_state_probability": 0.6, "handoff_state_max_action_l2": 0.3},
+    {"name": "wide", "dock_delta_q_change_limit_scale": 0.5, "dock_residual_action_limit": 0.35, "close_bucket_probability": 0.15,
+     "handoff_state_probability": 0.95},
+]
+
+
+def _dock_setup(n_steps: int, batch: int, hidden: int):
+    cfg = json.loads(DOCK_CONFIG.read_text())
+    env_cfg = kcfg.to_env_config(cfg, handoff_base_dirs=(DOCK_CONFIG.parents[1],))
+    algo = {k: v for k, v in kcfg.to_algorithm_kwargs(cfg, "ppo").items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
+    return env_cfg, PPOConfig.from_algo_kwargs(algo, n_steps=n_steps, batch_size=batch, hidden=hidden)
+
+
+def build_dock_one_handle(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool, curriculum: bool) -> PopulationPPO:
+    from rl_brain_trainer_amd.finisher_tools import DockReverseCurriculumPopulation
+    from rl_brain_trainer_amd.population import DockPopulationPPO
+    from rl_brain_trainer_amd.vec_env import ArmKinematicPopulationVecEnv
+
+    env_cfg, pcfg = _dock_setup(n_steps, batch, hidden)
+    seeds = list(range(7, 7 + K))
+    env = ArmKinematicPopulationVecEnv(env_cfg, seeds, n_envs, mode="dock")
+    cur = None
+    if curriculum:
+        cur = DockReverseCurriculumPopulation(stages=DOCK_STAGES, window_episodes=12, n_replicas=K, handoff_base_dirs=(DOCK_CONFIG.parents[1],))
+    pop = DockPopulationPPO(seeds, pcfg, env, curriculum=cur, use_graphs=use_graphs)
+    pop._bench_owned = [c for c in (cur, env) if c is not None]
+    return pop
+
+
+def build_dock_k_handles(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool, curriculum: bool) -> PopulationPPO:
+    from rl_brain_trainer_amd.finisher_tools import DockReverseCurriculum
+
+    def make_cur(_s):
+        return DockReverseCurriculum(stages=DOCK_STAGES, window_episodes=12, handoff_base_dirs=(DOCK_CONFIG.parents[1],)) if curriculum else None
+
+    # every replica its own config object: a single tracker writes its stage into its handle's config
+    _, pcfg = _dock_setup(n_steps, batch, hidden)
+    return PopulationPPO(list(range(7, 7 + K)), pcfg, lambda s: ArmKinematicVecEnv(_dock_setup(n_steps, batch, hidden)[0], n_envs, seed=s),
+                         curriculum_factory=make_cur, use_graphs=use_graphs)
+
+
 def _close(pop) -> None:
     pop.close()
     for obj in getattr(pop, "_bench_owned", []):
         obj.close()
 
 
-def measure(K: int, args) -> dict:
-    build = build_route if args.route else (build_approach_one_handle if args.one_handle else build_approach)
+def measure(K: int, args, build=None) -> dict:
+    build = build or (build_route if args.route else (build_approach_one_handle if args.one_handle else build_approach))
     pop = build(K, args.n_envs, args.n_steps, args.batch, args.hidden, True)
     pop.collect_rollouts()
     pop.train()      # warm-up: captures both graphs
@@ -139,16 +194,24 @@ def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--route", action="store_true", help="the route reference-scale iteration (RoutePopulationPPO)")
     ap.add_argument("--one-handle", action="store_true", help="the Approach iteration on one env handle (ApproachPopulationPPO)")
+    ap.add_argument("--dock", action="store_true", help="the Finisher reference shape, one handle (DockPopulationPPO) and K handles")
+    ap.add_argument("--no-curriculum", action="store_true", help="with --dock: no reverse-curriculum tracker")
     ap.add_argument("--ks", default="")
     ap.add_argument("--iters", type=int, default=3)
-    ap.add_argument("--n-envs", type=int, default=16)
-    ap.add_argument("--n-steps", type=int, default=1024)
+    ap.add_argument("--n-envs", type=int, default=0, help="envs per replica (0 = 16, or 12 with --dock)")
+    ap.add_argument("--n-steps", type=int, default=0, help="steps per rollout (0 = 1024, or 256 with --dock)")
     ap.add_argument("--batch", type=int, default=0, help="minibatch (0 = 256, or 512 with --route)")
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if args.route and args.one_handle:
         ap.error("--one-handle is the Approach form; --route is always one handle")
+    if args.dock and (args.route or args.one_handle):
+        ap.error("--dock measures the Finisher iteration in both forms")
+    args.n_envs = args.n_envs or (12 if args.dock else 16)
+    args.n_steps = args.n_steps or (256 if args.dock else 1024)
+    if args.dock:
+        return main_dock(args)
     args.ks = args.ks or ("1,2,4,8,16" if args.route or args.one_handle else "1,2,4,8")
     args.batch = args.batch or (512 if args.route else 256)
     rows = []
@@ -167,6 +230,32 @@ def main() -> None:
     if args.out:
         Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
     print(json.dumps({"aggregate_env_steps_per_s": {r["K"]: round(r["aggregate_env_steps_per_s"]) for r in rows}}))
+
+
+def main_dock(args) -> None:
+    import functools
+
+    args.ks = args.ks or "1,2,4,8,16"
+    args.batch = args.batch or 256
+    cur = not args.no_curriculum
+    rows = []
+    for K in (int(k) for k in args.ks.split(",")):
+        row = {"K": K}
+        for form, build in (("one_handle", build_dock_one_handle), ("k_handles", build_dock_k_handles)):
+            row[form] = measure(K, args, functools.partial(build, curriculum=cur))
+        rows.append(row)
+        print(json.dumps({"K": K, **{f: {k: round(v, 2) for k, v in row[f].items() if k.endswith("_ms")} for f in ("one_handle", "k_handles")}}), flush=True)
+    for form in ("one_handle", "k_handles"):
+        for r in rows:
+            r[form]["rollout_vs_first"] = r[form]["rollout_ms"] / rows[0][form]["rollout_ms"]
+    result = {"workload": f"dock_workspace_handoff_noop_ft_12env (golden handoff buffer), {args.n_envs} envs x {args.n_steps} steps per replica, "
+                          f"minibatch {args.batch}, 2x{args.hidden}, graphs; "
+                          + ("a 3-stage synthetic reverse curriculum (tools/population_bench.py DOCK_STAGES)" if cur else "no reverse curriculum")
+                          + "; one_handle = DockPopulationPPO, k_handles = PopulationPPO with one handle per replica; seeds 7..7+K-1",
+              "device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
+    print(json.dumps({f: {r["K"]: round(r[f]["rollout_ms"], 2) for r in rows} for f in ("one_handle", "k_handles")}))
 
 
 if __name__ == "__main__":
