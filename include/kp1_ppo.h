@@ -28,6 +28,12 @@ extern "C" {
 int kp1_gae_scan(int32_t device, const float* rewards, const float* values, const uint8_t* dones, const float* last_values,
                  float gamma, float gae_lambda, float* advantages, float* returns, int32_t T, int32_t N, void* stream);
 
+/* kp1_gae_scan for a population whose replicas discount differently: N = K * n_per_replica columns, column i (replica i / n_per_replica)
+ * uses gamma = gamma_lambda[2 r], lambda = gamma_lambda[2 r + 1] (device memory, f32 [K][2]) in kp1_gae_scan's expression order, so
+ * column i equals a kp1_gae_scan of replica r's columns with those two scalars, bit for bit.  N % n_per_replica == 0. */
+int kp1_gae_scan_replicas(int32_t device, const float* rewards, const float* values, const uint8_t* dones, const float* last_values,
+                          const float* gamma_lambda, int32_t n_per_replica, float* advantages, float* returns, int32_t T, int32_t N, void* stream);
+
 /* Time-limit bootstrap (SB3 on_policy_algorithm.collect_rollouts): rewards[t][i] += gamma * terminal_values[t][i]
  * where step t of env i was truncated and not terminated. */
 int kp1_bootstrap_truncated(int32_t device, float* rewards, const float* terminal_values, const uint8_t* dones, float gamma,
@@ -204,6 +210,17 @@ int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t m
 int kp1_mlp_create_population(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batch, int32_t replicas, kp1_mlp** out);
 /* K of the handle (1 for kp1_mlp_create / _create_ex), 0 for NULL */
 int32_t kp1_mlp_replicas(const kp1_mlp* m);
+/* Per-replica PPO hyper-parameters of a population handle (a hyper-parameter sweep in one launch sequence).  The handle owns a device copy
+ * of `host` [n]; n must equal K, n = 0 clears it, a K = 1 handle refuses a table.  While a table is set, replica k's kernels read entry k
+ * (once per workgroup, at kernel entry) in place of the scalar arguments: kp1_mlp_loss_grad's clip_range, vf_coef and ent_coef,
+ * kp1_mlp_adam_step's lr, eps and max_grad_norm.  Only the operand source changes: replica k with entry h computes bit for bit what a
+ * K = 1 handle computes when called with h's scalars.  The table lives in device memory, so a captured graph holds only its address and
+ * sees a later kp1_mlp_set_replica_hparams; setting or clearing it after a capture changes which source a re-capture uses.  Copies in
+ * stream order and waits for the copy; not while `stream` is being captured. */
+typedef struct kp1_replica_hparams {
+  float learning_rate, adam_eps, max_grad_norm, clip_range, ent_coef, vf_coef;
+} kp1_replica_hparams;
+int kp1_mlp_set_replica_hparams(kp1_mlp* m, const kp1_replica_hparams* host, int32_t n, void* stream);
 int kp1_mlp_destroy(kp1_mlp* m);
 /* number of f32 parameters in SB3 state_dict order (log_std, pi.0.w, pi.0.b, pi.2.w, pi.2.b, vf.0.w, ..., action_net.w/b, value_net.w/b) */
 int64_t kp1_mlp_num_params(int32_t hidden);

@@ -16,6 +16,7 @@
 #include <hip/hip_ext.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -463,11 +464,21 @@ struct HeadArgs {
   // + r * r_partials, head weights at + r * 8 Hp (w3) / + r * 8 (b3, log_std), adv_stats at + 2 r; per-row inputs and outputs (idx, noise,
   // mean, value, action, clipped, log_prob) at row + r * n
   unsigned r_act, r_hpart, r_partials;
+  // population with a per-replica hyper-parameter table (kp1_mlp_set_replica_hparams): [K][HP_FIELDS] floats, or NULL = the scalars above
+  const float* hparams;
 };
+
+// the per-replica hyper-parameter table of a population handle: entry r = kp1_replica_hparams of replica r (include/kp1_ppo.h)
+constexpr int HP_FIELDS = 6, HP_LR = 0, HP_EPS = 1, HP_MAX_NORM = 2, HP_CLIP = 3, HP_ENT = 4, HP_VF = 5;
 
 // HeadArgs of replica `rep` of a population handle
 __device__ __forceinline__ HeadArgs head_args_replica(HeadArgs a, unsigned rep) {
   const unsigned rows = rep * (unsigned)a.n, heads = rep * (unsigned)(HEADS * a.Hp);
+  if (a.hparams) {   // kernarg pointer + blockIdx.y, read at kernel entry before any divergence: a uniform load once per workgroup
+    const float* e = a.hparams + rep * (unsigned)HP_FIELDS;
+    a.clip_range = e[HP_CLIP];
+    a.vf_coef = e[HP_VF];
+  }
   a.h2 += rep * a.r_act;
   a.w3 += heads; a.b3 += rep * HEADS; a.log_std += rep * HEADS;
   if (a.noise) a.noise += rows * ACT;
@@ -882,9 +893,11 @@ struct FinalizeArgs {
   // population (POP kernel, grid.y = replica): partials at + r * r_*, grad at + r * total, stats at + 4 r, log_std at + 8 r; the shared
   // step counter is advanced by replica 0 only
   unsigned r_slab2, r_slab1, r_bslab, r_hpart, r_sumsq;
+  const float* hparams;   // per-replica hyper-parameter table [K][HP_FIELDS] or NULL (ent_coef above); POP kernel only
 };
 
 __device__ __forceinline__ FinalizeArgs finalize_args_replica(FinalizeArgs a, unsigned rep) {
+  if (a.hparams) a.ent_coef = a.hparams[rep * (unsigned)HP_FIELDS + HP_ENT];   // uniform load at kernel entry
   a.slab2 += rep * a.r_slab2; a.slab1 += rep * a.r_slab1; a.bslab += rep * a.r_bslab; a.hpart += rep * a.r_hpart;
   a.log_std += rep * (unsigned)HEADS;
   a.grad += rep * (unsigned)a.L.total;
@@ -1134,13 +1147,19 @@ __global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(float* __restrict__ p,
                                                    int64_t n, const double* __restrict__ partials, int n_partials, float lr, float eps, float max_norm,
                                                    float bc1, float bc2_sqrt, const ParamLayout L, const Packed k_, int zero_grad,
                                                    const int* __restrict__ step_counter, int host_step, const int* __restrict__ actor_extra,
-                                                   unsigned r_partials) {
+                                                   unsigned r_partials, const float* __restrict__ hparams) {
   __shared__ float scale_s;
   const Packed k = POP ? packed_replica(k_, L, blockIdx.y) : k_;
   if constexpr (POP) {
     const unsigned o = blockIdx.y * (unsigned)n;
     p += o; g += o; m += o; v += o;
     partials += blockIdx.y * r_partials;
+    if (hparams) {   // replica blockIdx.y's entry of the hyper-parameter table (uniform load at kernel entry); same arithmetic below
+      const float* e = hparams + blockIdx.y * (unsigned)HP_FIELDS;
+      lr = e[HP_LR];
+      eps = e[HP_EPS];
+      max_norm = e[HP_MAX_NORM];
+    }
   }
   // this thread's elements: their loads do not depend on the norm, so they go out first and share one memory round trip with the
   // step count and the norm partials below (the kernel is a chain of round trips: it moves 2.6 MB)
@@ -1229,6 +1248,9 @@ struct kp1_mlp {
   float* hpart = nullptr;      // [max_batch/32 blocks][10 Hp + 32] head partials
   int n_finalize_blocks = 0;   // sum-of-squares partials written by the last grad_finalize_kernel
   int* step_dev = nullptr;     // device Adam step counter
+  // population: per-replica hyper-parameter table [K][HP_FIELDS] (kp1_mlp_set_replica_hparams); the kernels read it while hparams_on
+  float* hparams_dev = nullptr;
+  bool hparams_on = false;
   int last_s2_n = 0, last_s1_n = 0;
   int fused = 1;               // KP1_MLP_OPT_FUSED: one workgroup carries a row tile through the whole chain (H = 256 only)
   // While the fused path is selected the Adam kernel refreshes only the fragment-major weight copies (the transposed / slab copies are
@@ -1582,6 +1604,7 @@ int mlp_create(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batc
   MLP_ALLOC(m->slab, K * 64 * 2 * Hp * Hp);
   MLP_ALLOC(m->slab1, K * 64 * 2 * Hp * INP);
   MLP_ALLOC(m->step_dev, 4);
+  if (K > 1) MLP_ALLOC(m->hparams_dev, K * HP_FIELDS);
   MLP_ALLOC(m->bslab, K * (mb / 32) * 2 * Hp);
   MLP_ALLOC(m->hpart, K * (mb / 32) * (10 * Hp + 32));
 #undef MLP_ALLOC
@@ -1661,6 +1684,33 @@ int kp1_mlp_set_option(kp1_mlp* m, int32_t option, int32_t value) {
     return KP1_OK;
   }
   return fail(KP1_ERR_INVALID, "unknown kp1_mlp option");
+}
+
+int kp1_mlp_set_replica_hparams(kp1_mlp* m, const kp1_replica_hparams* host, int32_t n, void* stream) {
+  static_assert(sizeof(kp1_replica_hparams) == sizeof(float) * HP_FIELDS, "kp1_replica_hparams is HP_FIELDS floats");
+  static_assert(offsetof(kp1_replica_hparams, learning_rate) == sizeof(float) * HP_LR && offsetof(kp1_replica_hparams, adam_eps) == sizeof(float) * HP_EPS &&
+                offsetof(kp1_replica_hparams, max_grad_norm) == sizeof(float) * HP_MAX_NORM && offsetof(kp1_replica_hparams, clip_range) == sizeof(float) * HP_CLIP &&
+                offsetof(kp1_replica_hparams, ent_coef) == sizeof(float) * HP_ENT && offsetof(kp1_replica_hparams, vf_coef) == sizeof(float) * HP_VF,
+                "kp1_replica_hparams field order");
+  if (!m) return fail(KP1_ERR_INVALID, "NULL argument");
+  if (n == 0) {   // back to the scalar arguments of kp1_mlp_loss_grad / kp1_mlp_adam_step
+    m->hparams_on = false;
+    return KP1_OK;
+  }
+  if (m->K == 1) return fail(KP1_ERR_UNSUPPORTED, "a K = 1 handle takes its hyper-parameters as scalar arguments, not a per-replica table");
+  if (n != m->K || !host) return fail(KP1_ERR_INVALID, "kp1_mlp_set_replica_hparams needs one entry per replica (n = K)");
+  for (int r = 0; r < n; ++r) {
+    const kp1_replica_hparams& h = host[r];
+    for (float v : {h.learning_rate, h.adam_eps, h.max_grad_norm, h.clip_range, h.ent_coef, h.vf_coef})
+      if (!std::isfinite(v)) return fail(KP1_ERR_INVALID, "replica hyper-parameters must be finite");
+  }
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  // stream order: launches already queued on `stream` read the previous table; the copy is complete (host buffer released) on return
+  HIP_TRY(hipMemcpyAsync(m->hparams_dev, host, sizeof(kp1_replica_hparams) * (size_t)n, hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  m->hparams_on = true;
+  return KP1_OK;
 }
 
 int kp1_mlp_pack_weights(kp1_mlp* m, const float* params, void* stream) {
@@ -1800,6 +1850,7 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     a.dz2 = m->dz2;
     a.hpart = m->hpart; a.hpart_stride = hpart_stride;
     a.r_act = (unsigned)(2 * act_stride); a.r_hpart = (unsigned)hpart_rep; a.r_partials = (unsigned)PARTIALS_STRIDE;
+    a.hparams = pop && m->hparams_on ? m->hparams_dev : nullptr;
     {
       const dim3 hgrid((n + HEAD_ROWS - 1) / HEAD_ROWS, m->K);
       const size_t hbytes = sizeof(float) * (HEADS * Hp + HEAD_ROWS * 8 + 84 + 2 * HEAD_ROWS * (Hp + 4));
@@ -1890,6 +1941,7 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
   f.step_counter = m->step_dev;
   f.r_slab2 = (unsigned)(64 * f.s2_chunk); f.r_slab1 = (unsigned)(64 * f.s1_chunk); f.r_bslab = (unsigned)((m->max_batch / 32) * 2 * Hp);
   f.r_hpart = (unsigned)hpart_rep; f.r_sumsq = (unsigned)PARTIALS_STRIDE;
+  f.hparams = pop && m->hparams_on ? m->hparams_dev : nullptr;
   const int n_main = (int)((finalize_vec_items(L) + 255) / 256);
   m->n_finalize_blocks = n_main + (int)((finalize_wide_count(L) + 3 + 31) / 32);
   if (m->n_finalize_blocks > 2048) return fail(KP1_ERR_INVALID, "parameter vector too large for the sum-of-squares partial buffer");
@@ -2139,10 +2191,11 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   if (pop)
     KP1_LAUNCH(adam_kernel<true>, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK), m->K), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n,
                norm_partials, n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step,
-               (const int*)m->step_dev + 1, (unsigned)PARTIALS_STRIDE);
+               (const int*)m->step_dev + 1, (unsigned)PARTIALS_STRIDE, m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr);
   else
     KP1_LAUNCH(adam_kernel<false>, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK)), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
-               n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1, 0u);
+               n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1, 0u,
+               (const float*)nullptr);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }

@@ -34,6 +34,30 @@ __global__ void __launch_bounds__(256) gae_scan_kernel(const float* __restrict__
   }
 }
 
+// gae_scan_kernel with (gamma, lambda) of column i's replica read from gamma_lambda [K][2]; the loop body is gae_scan_kernel's, expression for
+// expression, so a column computes bit for bit what the single scan computes with its replica's two scalars
+__global__ void __launch_bounds__(256) gae_scan_replicas_kernel(const float* __restrict__ rewards, const float* __restrict__ values,
+                                                                const uint8_t* __restrict__ dones, const float* __restrict__ last_values,
+                                                                const float* __restrict__ gamma_lambda, int n_per_replica, float* __restrict__ adv,
+                                                                float* __restrict__ ret, int T, int N) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int r = i / n_per_replica;
+  const float gamma = gamma_lambda[2 * r], lam = gamma_lambda[2 * r + 1];
+  float next_value = last_values[i];
+  float last_gae = 0.0f;
+  for (int t = T - 1; t >= 0; --t) {
+    const int64_t k = (int64_t)t * N + i;
+    const float nonterm = (dones[k] & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) ? 0.0f : 1.0f;
+    const float v = values[k];
+    const float delta = rewards[k] + gamma * next_value * nonterm - v;
+    last_gae = delta + gamma * lam * nonterm * last_gae;
+    adv[k] = last_gae;
+    ret[k] = last_gae + v;
+    next_value = v;
+  }
+}
+
 __global__ void __launch_bounds__(256) bootstrap_kernel(float* __restrict__ rewards, const float* __restrict__ tv,
                                                         const uint8_t* __restrict__ dones, float gamma, int64_t count) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -410,6 +434,20 @@ int kp1_gae_scan(int32_t device, const float* rewards, const float* values, cons
   const int block = N <= 16384 ? 64 : 256;
   hipLaunchKernelGGL(gae_scan_kernel, dim3((N + block - 1) / block), dim3(block), 0, (hipStream_t)stream, rewards, values, dones, last_values,
                      gamma, gae_lambda, advantages, returns, T, N);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_gae_scan_replicas(int32_t device, const float* rewards, const float* values, const uint8_t* dones, const float* last_values,
+                          const float* gamma_lambda, int32_t n_per_replica, float* advantages, float* returns, int32_t T, int32_t N, void* stream) {
+  if (!rewards || !values || !dones || !last_values || !gamma_lambda || !advantages || !returns || T <= 0 || N <= 0)
+    return fail(KP1_ERR_INVALID, "bad argument to kp1_gae_scan_replicas");
+  if (n_per_replica <= 0 || N % n_per_replica != 0) return fail(KP1_ERR_INVALID, "kp1_gae_scan_replicas: N must be a multiple of n_per_replica");
+  int rc = check_device(device);
+  if (rc != KP1_OK) return rc;
+  const int block = N <= 16384 ? 64 : 256;
+  hipLaunchKernelGGL(gae_scan_replicas_kernel, dim3((N + block - 1) / block), dim3(block), 0, (hipStream_t)stream, rewards, values, dones,
+                     last_values, gamma_lambda, n_per_replica, advantages, returns, T, N);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }

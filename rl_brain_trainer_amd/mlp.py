@@ -37,6 +37,7 @@ class MlpKernels:
         L.kp1_mlp_placement_check.argtypes = [i32, i32, vp, vp]
         L.kp1_mlp_set_option.argtypes = [vp, i32, i32]
         L.kp1_mlp_profile_read.argtypes = [vp, vp, vp]
+        L.kp1_mlp_set_replica_hparams.argtypes = [vp, vp, i32, vp]
         self.hidden = hidden
         self.device = device
         self.max_batch = int(max_batch)
@@ -93,6 +94,17 @@ class MlpKernels:
         cnt = (C.c_int32 * 4)()
         native.check(self.L.kp1_mlp_profile_read(self._h, C.cast(us, C.c_void_p), C.cast(cnt, C.c_void_p)))
         return {name: {"us": float(us[i]), "launches": int(cnt[i])} for i, name in enumerate(self.PROFILE_SLOTS)}
+
+    HPARAM_FIELDS = ("learning_rate", "adam_eps", "max_grad_norm", "clip_range", "ent_coef", "vf_coef")   # kp1_replica_hparams
+
+    def set_replica_hparams(self, rows: list[dict[str, float]] | None) -> None:
+        """Population handles: per-replica PPO hyper-parameters (kp1_mlp_set_replica_hparams), one dict with every HPARAM_FIELDS key per
+        replica; replica k's loss / Adam kernels then read row k in place of the scalar arguments.  None clears the table."""
+        if rows is None:
+            native.check(self.L.kp1_mlp_set_replica_hparams(self._h, None, 0, self._stream()))
+            return
+        table = (C.c_float * (len(rows) * len(self.HPARAM_FIELDS)))(*[float(r[f]) for r in rows for f in self.HPARAM_FIELDS])
+        native.check(self.L.kp1_mlp_set_replica_hparams(self._h, C.cast(table, C.c_void_p), len(rows), self._stream()))
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

@@ -94,6 +94,7 @@ def load() -> C.CDLL:
     L.kp1_rng_seed_state.argtypes = [u64, C.POINTER(kcfg.RngState)]
     f32 = C.c_float
     L.kp1_gae_scan.argtypes = [i32, vp, vp, vp, vp, f32, f32, vp, vp, i32, i32, vp]
+    L.kp1_gae_scan_replicas.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp]
     L.kp1_bootstrap_truncated.argtypes = [i32, vp, vp, vp, f32, i64, vp]
     L.kp1_adv_minibatch_sums.argtypes = [i32, vp, vp, i64, i64, vp, vp]
     L.kp1_adv_minibatch_stats.argtypes = [i32, vp, i64, vp, vp]

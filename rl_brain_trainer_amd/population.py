@@ -35,6 +35,49 @@ from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig
 
 MAX_REPLICAS = 16     # KP1_MLP_MAX_REPLICAS
 
+# Per-replica PPO hyper-parameters a population can sweep (``overrides``): the six the MLP kernels read from the handle's table
+# (kp1_mlp_set_replica_hparams) and the two of the per-replica GAE scan / bootstrap.  The geometry the replicas share is refused.
+SWEEPABLE = ("learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "adam_eps", "gamma", "gae_lambda")
+SHAPE_KEYS = ("n_steps", "batch_size", "n_epochs", "hidden", "normalize_advantage")
+
+
+def check_overrides(seeds: list[int], overrides: list[dict[str, float]] | None) -> list[dict[str, float]]:
+    """The host-side refusals of per-replica overrides (before any device work): one dict per replica, sweepable keys only, finite values,
+    distinct (seed, overrides) pairs.  Returns the overrides as {key: float} dicts ([{}] * K when None)."""
+    import math
+
+    K = len(seeds)
+    if overrides is None:
+        out: list[dict[str, float]] = [{} for _ in range(K)]
+    else:
+        if len(overrides) != K:
+            raise ValueError(f"{len(overrides)} override dicts for {K} replicas: a population takes one per replica")
+        out = []
+        for k, o in enumerate(overrides):
+            row: dict[str, float] = {}
+            for key, v in dict(o).items():
+                if key == "seed":
+                    raise ValueError("overrides cannot set 'seed': a replica's seed is its entry of the seed list")
+                if key in SHAPE_KEYS:
+                    raise ValueError(f"overrides cannot set {key!r}: the replicas of a population share the rollout and minibatch geometry "
+                                     f"({', '.join(SHAPE_KEYS)})")
+                if key not in SWEEPABLE:
+                    raise ValueError(f"unknown override {key!r} (sweepable: {', '.join(SWEEPABLE)})")
+                if isinstance(v, bool):
+                    raise ValueError(f"override {key}={v!r} of replica {k} is not a number")
+                try:
+                    fv = float(v)
+                except (TypeError, ValueError) as exc:
+                    raise ValueError(f"override {key}={v!r} of replica {k} is not a number") from exc
+                if not math.isfinite(fv):
+                    raise ValueError(f"override {key}={v!r} of replica {k} is not finite")
+                row[key] = fv
+            out.append(row)
+    pairs = [(s, tuple(sorted(o.items()))) for s, o in zip(seeds, out)]
+    if len(set(pairs)) != len(pairs):
+        raise ValueError(f"(seed, overrides) pairs must be distinct (seeds {list(seeds)}, overrides {out}): equal pairs train identical replicas")
+    return out
+
 
 class _ReplicaDist:
     enabled, world_size, rank = False, 1, 0
@@ -93,8 +136,8 @@ class PopulationPPO(PPO):
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env_factory: Callable[[int], Any], *,
                  curriculum_factory: Callable[[int], Any] | None = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None) -> None:
-        seeds, dist = self._check_population_args(seeds, cfg, dist, teacher_anchor)
+                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:
+        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides)
         envs: list[Any] = []
         try:
             for s in seeds:
@@ -111,18 +154,18 @@ class PopulationPPO(PPO):
                 e.close()
             raise
         curricula = [curriculum_factory(s) if curriculum_factory is not None else None for s in seeds]
-        self._init_population(seeds, cfg, envs, curricula, dist, use_graphs)
+        self._init_population(seeds, cfg, envs, curricula, dist, use_graphs, overrides)
 
     @staticmethod
-    def _check_population_args(seeds: list[int], cfg: PPOConfig, dist: Dist | None, teacher_anchor: Any) -> tuple[list[int], Dist]:
-        """the refusals every population shares; returns (seeds as ints, the Dist)"""
+    def _check_population_args(seeds: list[int], cfg: PPOConfig, dist: Dist | None, teacher_anchor: Any,
+                               overrides: list[dict[str, float]] | None = None) -> tuple[list[int], Dist, list[dict[str, float]]]:
+        """the refusals every population shares; returns (seeds as ints, the Dist, the per-replica overrides)"""
         seeds = [int(s) for s in seeds]
         if not seeds:
             raise ValueError("PopulationPPO needs at least one seed")
         if len(seeds) > MAX_REPLICAS:
             raise ValueError(f"PopulationPPO trains at most {MAX_REPLICAS} replicas at once (got {len(seeds)} seeds)")
-        if len(set(seeds)) != len(seeds):
-            raise ValueError(f"PopulationPPO seeds must be distinct (got {seeds}): equal seeds train identical replicas")
+        overrides = check_overrides(seeds, overrides)
         if cfg.hidden not in (64, 128):
             raise ValueError(f"PopulationPPO runs the layer-wise kernels of the 2x64 / 2x128 nets; hidden={cfg.hidden} is not supported "
                              "(the 2x256 tile kernels have no replica axis)")
@@ -131,9 +174,10 @@ class PopulationPPO(PPO):
         dist = dist or Dist()
         if dist.enabled:
             raise ValueError("PopulationPPO is single-process: data parallel (a torch.distributed process group) is not supported")
-        return seeds, dist
+        return seeds, dist, overrides
 
-    def _init_population(self, seeds: list[int], cfg: PPOConfig, envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool) -> None:
+    def _init_population(self, seeds: list[int], cfg: PPOConfig, envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool,
+                         overrides: list[dict[str, float]] | None = None) -> None:
         """what a population holds once its K env views and trackers exist"""
         T, N, K = cfg.n_steps, envs[0].n_envs, len(seeds)
         max_steps = max(int(envs[0].config.c.termination.max_episode_steps), 1)
@@ -141,8 +185,14 @@ class PopulationPPO(PPO):
         # the MLP handle's max_batch holds the `_trunc_cap` rows per replica of the bootstrap's one forward
         self._setup(cfg, seeds, envs, curricula, dist, use_graphs, min_batch=self._trunc_cap, stacked=True)
         self.seeds = seeds
-        self.cfgs = [dataclasses.replace(cfg, seed=s) for s in seeds]
+        self.overrides = overrides if overrides is not None else [{} for _ in seeds]
+        # a population with overrides keeps its per-replica constants on the device: the MLP handle's hyper-parameter table, (gamma, lambda)
+        # per replica for the GAE scan and gamma per replica for the bootstrap.  Captured graphs hold their addresses, so the values are
+        # refreshed in place (_apply_overrides) and never re-allocated.
+        self.has_overrides = any(self.overrides)
         dev = self.device
+        self._gamma_lambda = torch.zeros((K, 2), dtype=torch.float32, device=dev) if self.has_overrides else None
+        self._apply_overrides()
         self.noise_rep = torch.zeros((K, T, N, ACT_DIM), dtype=torch.float32, device=dev)   # replica k's draw, as PPO.noise_all
         # minibatch i of replica k = local positions [start_i, end_i) of its shuffle; the kernels read minibatch i as ONE [K][n_i] index
         # block at K * start_i of the gathered index vector
@@ -152,6 +202,15 @@ class PopulationPPO(PPO):
         self._mb_src = torch.cat(src).to(dev)
         self._rep_off = (torch.arange(K, device=dev, dtype=torch.int64) * N).view(K, 1)
         self._infer: dict[int, Any] = {}
+
+    def _apply_overrides(self) -> None:
+        """cfgs[k] = cfg with replica k's seed and overrides; a population with overrides writes them to the device (at construction and
+        after load_init_checkpoints, always before the first capture)"""
+        self.cfgs = [dataclasses.replace(self.cfg, seed=s, **o) for s, o in zip(self.seeds, self.overrides)]
+        if not self.has_overrides:
+            return
+        self._mlp.set_replica_hparams([{f: getattr(c, f) for f in self._mlp.HPARAM_FIELDS} for c in self.cfgs])
+        self._gamma_lambda.copy_(torch.tensor([[c.gamma, c.gae_lambda] for c in self.cfgs], dtype=torch.float32))
 
     # ------------------------------------------------------------------ views
     def replica(self, k: int) -> ReplicaView:
@@ -213,12 +272,30 @@ class PopulationPPO(PPO):
         # one forward of `cap` rows per replica: the handle's max_batch is sized to hold them (min_batch in __init__), so unlike PPO nothing
         # is chunked here -- shrinking max_batch below _trunc_cap would make this call fail
         self._mlp.forward(sel, value=tv)
-        self.rew_buf.view(-1).index_add_(0, gidx.view(-1), torch.where(valid.view(-1), self.cfg.gamma * tv, torch.zeros_like(tv)))
+        # replica k's rows times replica k's gamma: the fp32 product of PPO's cfg.gamma * tv
+        disc = self.cfg.gamma * tv if not self.has_overrides else (self._gamma_lambda[:, :1] * tv.view(K, cap)).view(-1)
+        self.rew_buf.view(-1).index_add_(0, gidx.view(-1), torch.where(valid.view(-1), disc, torch.zeros_like(tv)))
+
+    def _post_rollout(self) -> None:
+        """PPO._post_rollout; with overrides the GAE scan reads each replica's (gamma, lambda) (kp1_gae_scan_replicas, one launch)"""
+        if not self.has_overrides:
+            super()._post_rollout()
+            return
+        T, N, KN = self.cfg.n_steps, self.n_envs, self.K * self.n_envs
+        self._bootstrap_truncated()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        last_v = torch.empty(KN, dtype=torch.float32, device=self.device)
+        self._mlp.forward(self.obs_buf[T], value=last_v)   # value net only
+        native.check(self.L.kp1_gae_scan_replicas(self.device.index or 0, C.c_void_p(self.rew_buf.data_ptr()), C.c_void_p(self.val_buf.data_ptr()),
+                                                  C.c_void_p(self.done_buf.data_ptr()), C.c_void_p(last_v.data_ptr()),
+                                                  C.c_void_p(self._gamma_lambda.data_ptr()), N, C.c_void_p(self.adv_buf.data_ptr()),
+                                                  C.c_void_p(self.ret_buf.data_ptr()), T, KN, C.c_void_p(stream)))
 
     # ------------------------------------------------------------------ update
     def _epoch_body(self) -> None:
         """one update epoch from the shuffles in self.perm: global row indices, per-replica minibatch advantage statistics, then per minibatch
-        loss_grad + Adam of all replicas"""
+        loss_grad + Adam of all replicas (with overrides the kernels read each replica's constants from the handle's table; the shared
+        scalars below are then unused)"""
         cfg, K, N = self.cfg, self.K, self.n_envs
         T = cfg.n_steps
         total = T * N
@@ -321,9 +398,11 @@ class OneHandlePopulationPPO(PopulationPPO):
         population has one Adam step count for every tensor."""
         return self.load_init_checkpoints([path] * self.K)
 
-    def load_init_checkpoints(self, paths: list[str]) -> dict[str, Any]:
+    def load_init_checkpoints(self, paths: list[str], *, restore_timesteps: bool = True) -> dict[str, Any]:
         """the per-replica form: replica k starts from ``paths[k]`` (weights and Adam moments); the step count, the clock and the saved
-        algorithm constants are shared, so check_init_checkpoints refuses checkpoints that disagree on them"""
+        algorithm constants are shared, so check_init_checkpoints refuses checkpoints that disagree on them.  Per-replica overrides apply
+        after the saved constants.  ``restore_timesteps=False`` keeps the step clock and the update count at zero, as train.py's
+        ``PPO.load_checkpoint(restore_hyperparameters=True)`` does."""
         from . import checkpoint
         from .ppo import load_adam_state, restore_saved_hyperparameters
 
@@ -349,13 +428,14 @@ class OneHandlePopulationPPO(PopulationPPO):
         self._mlp.pack(self.flat)
         self._mlp.set_step_count(self.adam_t)
         data = checkpoint.load_data(paths[0])
-        self.num_timesteps = int(data.get("num_timesteps", 0))
-        restored["num_timesteps"] = self.num_timesteps
-        saved_epochs = data.get("n_epochs")
-        if isinstance(data.get("_n_updates"), int) and isinstance(saved_epochs, int) and saved_epochs > 0:
-            self.n_train_calls = int(data["_n_updates"]) // saved_epochs
+        if restore_timesteps:
+            self.num_timesteps = int(data.get("num_timesteps", 0))
+            restored["num_timesteps"] = self.num_timesteps
+            saved_epochs = data.get("n_epochs")
+            if isinstance(data.get("_n_updates"), int) and isinstance(saved_epochs, int) and saved_epochs > 0:
+                self.n_train_calls = int(data["_n_updates"]) // saved_epochs
         restored["hyperparameters"] = restore_saved_hyperparameters(self.cfg, data)
-        self.cfgs = [dataclasses.replace(self.cfg, seed=s) for s in self.seeds]
+        self._apply_overrides()     # swept values beat both the config and the checkpoint
         return restored
 
 
@@ -366,11 +446,11 @@ class ApproachPopulationPPO(OneHandlePopulationPPO):
     config (tests/test_approach_population_gpu.py), and to replica k of the K-handle ``PopulationPPO``."""
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None) -> None:
+                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:
         from .curriculum import PointCurriculumPopulation
         from .vec_env import ArmKinematicPopulationVecEnv
 
-        seeds, dist = self._check_population_args(seeds, cfg, dist, teacher_anchor)
+        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides)
         if not isinstance(env, ArmKinematicPopulationVecEnv):
             raise TypeError("ApproachPopulationPPO drives an ArmKinematicPopulationVecEnv (one handle for all replicas)")
         if env.seeds != seeds:
@@ -385,7 +465,7 @@ class ApproachPopulationPPO(OneHandlePopulationPPO):
         K = len(seeds)
         views = [env.replica(k) for k in range(K)]
         curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
-        self._init_population(seeds, cfg, views, curricula, dist, use_graphs)
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides)
 
 
 class RoutePopulationPPO(OneHandlePopulationPPO):
@@ -398,11 +478,11 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
     train_route does.  The caller owns (and closes) the env and the tracker."""
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None) -> None:
+                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:
         from .route_curriculum import RoutePrefixCurriculumPopulation
         from .route_env import RoutePopulationVecEnv
 
-        seeds, dist = self._check_population_args(seeds, cfg, dist, teacher_anchor)
+        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides)
         if not isinstance(env, RoutePopulationVecEnv):
             raise TypeError("RoutePopulationPPO drives a RoutePopulationVecEnv (one handle for all replicas)")
         if env.seeds != seeds:
@@ -415,7 +495,7 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
         K = len(seeds)
         views = [env.replica(k) for k in range(K)]
         curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
-        self._init_population(seeds, cfg, views, curricula, dist, use_graphs)
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides)
 
 class DockPopulationPPO(OneHandlePopulationPPO):
     """K Finisher (dock-mode) runs of one PPOConfig on ONE ArmKinematicPopulationVecEnv with ONE DockReverseCurriculumPopulation
@@ -426,11 +506,11 @@ class DockPopulationPPO(OneHandlePopulationPPO):
     checkpoint or one each (train_dock --seeds --resume-from).  The caller owns (and closes) the env and the tracker."""
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None) -> None:
+                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:
         from .finisher_tools import DockReverseCurriculumPopulation
         from .vec_env import ArmKinematicPopulationVecEnv
 
-        seeds, dist = self._check_population_args(seeds, cfg, dist, teacher_anchor)
+        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides)
         if not isinstance(env, ArmKinematicPopulationVecEnv) or env.config.mode_name != "dock":
             raise TypeError("DockPopulationPPO drives a dock-mode ArmKinematicPopulationVecEnv (one handle for all replicas)")
         if env.seeds != seeds:
@@ -445,20 +525,22 @@ class DockPopulationPPO(OneHandlePopulationPPO):
         K = len(seeds)
         views = [env.replica(k) for k in range(K)]
         curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
-        self._init_population(seeds, cfg, views, curricula, dist, use_graphs)
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides)
 
 
-def resolve_resume_population(resume_from: str | None, seeds: list[int]) -> list[str] | None:
-    """train_dock --seeds --resume-from X, resolved on the host: None when X is not given or does not exist (a --seed run then starts from
-    scratch too), [X] * K when X is a checkpoint zip (every seed starts from it), and X/seed_<s>/model_latest.zip per seed when X is the root
-    of an earlier --seeds run.  Refuses a missing seed and, through check_init_checkpoints, checkpoints a population cannot resume together."""
+def resolve_resume_population(resume_from: str | None, seeds: list[int], names: list[str] | None = None) -> list[str] | None:
+    """train_dock / train --seeds --resume-from X, resolved on the host: None when X is not given or does not exist (a --seed run then starts
+    from scratch too), [X] * K when X is a checkpoint zip (every seed starts from it), and X/<name_k>/model_latest.zip per replica when X is the
+    root of an earlier --seeds run (``names``: the replica directories, seed_<s> by default).  Refuses a missing replica and, through
+    check_init_checkpoints, checkpoints a population cannot resume together."""
     from pathlib import Path
 
     if not resume_from:
         return None
     root = Path(resume_from)
     if root.is_dir():
-        paths = [root / f"seed_{s}" / "model_latest.zip" for s in seeds]
+        names = names or [f"seed_{s}" for s in seeds]
+        paths = [root / n / "model_latest.zip" for n in names]
         missing = [s for s, p in zip(seeds, paths) if not p.is_file()]
         if missing:
             raise ValueError(f"--resume-from {root}: no seed_<s>/model_latest.zip for seeds {missing} (a --seeds run root holds one per seed)")
@@ -483,6 +565,61 @@ def parse_seeds(text: str) -> list[int]:
     return seeds
 
 
+def parse_sweep(specs: list[str] | None) -> list[tuple[str, list[float]]]:
+    """``--sweep KEY=v1,v2[,...]`` (repeatable) -> [(key, [v1, v2, ...]), ...] in the order given; refuses unknown and shape keys, a key
+    given twice and values that are not finite numbers"""
+    import math
+
+    out: list[tuple[str, list[float]]] = []
+    for spec in specs or []:
+        key, sep, values = str(spec).partition("=")
+        key = key.strip()
+        if not sep or not key:
+            raise ValueError(f"--sweep takes KEY=v1,v2[,...], got {spec!r}")
+        if key == "seed" or key in SHAPE_KEYS:
+            raise ValueError(f"--sweep {key}: the replicas share the seed list and the rollout / minibatch geometry; sweepable: {', '.join(SWEEPABLE)}")
+        if key not in SWEEPABLE:
+            raise ValueError(f"--sweep: unknown key {key!r} (sweepable: {', '.join(SWEEPABLE)})")
+        if any(k == key for k, _ in out):
+            raise ValueError(f"--sweep {key} is given twice: list all its values in one --sweep {key}=v1,v2")
+        try:
+            vals = [float(v) for v in values.split(",") if v.strip()]
+        except ValueError as exc:
+            raise ValueError(f"--sweep {key}: values must be numbers, got {values!r}") from exc
+        if not vals or not all(math.isfinite(v) for v in vals):
+            raise ValueError(f"--sweep {key}: needs at least one finite value, got {values!r}")
+        out.append((key, vals))
+    return out
+
+
+def replica_name(seed: int, overrides: dict[str, float]) -> str:
+    """the artifact directory of a replica: seed_<s> without overrides, else seed_<s>_<key>_<repr(value)> per override in order
+    (seed_7_learning_rate_0.0001)"""
+    return "_".join([f"seed_{int(seed)}"] + [f"{k}_{float(v)!r}" for k, v in overrides.items()])
+
+
+def plan_replicas(seeds_text: str | None, sweep_specs: list[str] | None) -> tuple[list[int], list[dict[str, float]] | None, list[str]]:
+    """the trainers' ``--seeds`` [+ ``--sweep``] on the host: (replica seeds, per-replica overrides or None without --sweep, replica
+    directory names).  Replicas are the Cartesian product seeds x sweep values, seed-major, at most MAX_REPLICAS; refused before any device
+    work."""
+    import itertools
+
+    if sweep_specs and seeds_text is None:
+        raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
+    seeds = parse_seeds(seeds_text)
+    sweep = parse_sweep(sweep_specs)
+    if not sweep:
+        check_overrides(seeds, None)
+        return seeds, None, [replica_name(s, {}) for s in seeds]
+    combos = [dict(zip([k for k, _ in sweep], vals)) for vals in itertools.product(*[v for _, v in sweep])]
+    rep_seeds = [s for s in seeds for _ in combos]
+    overrides = [dict(c) for _ in seeds for c in combos]
+    if len(rep_seeds) > MAX_REPLICAS:
+        raise ValueError(f"--seeds x --sweep makes {len(rep_seeds)} replicas; a population trains at most {MAX_REPLICAS}")
+    overrides = check_overrides(rep_seeds, overrides)
+    return rep_seeds, overrides, [replica_name(s, o) for s, o in zip(rep_seeds, overrides)]
+
+
 def learn_population(pop: PopulationPPO, total_timesteps: int, *, on_iteration=None, log_every: int = 0, tag: str = "population") -> float:
     """The trainers' loop for a population: iterations until every replica has taken `total_timesteps` env steps; ``on_iteration(pop)``
     after each (per-replica gates).  Returns the wall time in seconds."""
@@ -503,11 +640,16 @@ def learn_population(pop: PopulationPPO, total_timesteps: int, *, on_iteration=N
 
 
 def population_summary(pop: PopulationPPO, rows: list[dict[str, Any]], *, wall_seconds: float, selection: str) -> dict[str, Any]:
-    """population_summary.json: one row per seed (final curriculum stage, last update stats, model paths, best score when a selection ran),
-    the seed with the best score, the wall time and the aggregate env-steps/s of all replicas"""
+    """population_summary.json: one row per replica (its directory name and overrides, final curriculum stage, last update stats, model
+    paths, best score when a selection ran), the seed and overrides with the best score, the wall time and the aggregate env-steps/s of all
+    replicas"""
+    for k, r in enumerate(rows):
+        r.setdefault("replica", replica_name(pop.seeds[k], pop.overrides[k]))
+        r.setdefault("overrides", dict(pop.overrides[k]))
     scored = [r for r in rows if r.get("best_score") is not None]
     best = max(scored, key=lambda r: r["best_score"]) if scored else None
     return {"seeds": list(pop.seeds), "replicas": pop.K, "selection": selection,
-            "best_seed": best["seed"] if best else None, "best_score": best["best_score"] if best else None,
+            "best_seed": best["seed"] if best else None, "best_overrides": best["overrides"] if best else None,
+            "best_replica": best["replica"] if best else None, "best_score": best["best_score"] if best else None,
             "per_seed": rows, "num_timesteps_per_seed": int(pop.num_timesteps), "wall_seconds": wall_seconds,
             "aggregate_env_steps_per_second": pop.K * pop.num_timesteps / max(wall_seconds, 1e-9)}

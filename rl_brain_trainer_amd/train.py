@@ -41,6 +41,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     seeds.add_argument("--seeds", help="comma-separated seeds trained together as one population (2x64 / 2x128 nets, one GPU); seed s writes "
                                        "the artefacts of a --seed s run under <artifact-root>/seed_<s>/, plus population_summary.json")
     p.add_argument("--resume-from")
+    p.add_argument("--sweep", action="append", metavar="KEY=v1,v2", help="with --seeds: train every seed with each value of a PPO hyper-parameter "
+                   "(repeatable; replicas = seeds x values, seed-major, at most 16); each replica writes what --seed s with those settings writes "
+                   "under <artifact-root>/seed_<s>_<key>_<value>/")
     p.add_argument("--no-gate-callback", action="store_true")
     p.add_argument("--n-envs", type=int, default=4096, help="environments per GPU")
     p.add_argument("--n-steps", type=int, default=128)
@@ -108,6 +111,8 @@ class WorkspaceEvalGate:
 
 def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
+    if args.sweep and args.seeds is None:
+        raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -135,9 +140,9 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     batch = args.batch_size or max(n_envs * args.n_steps * world // 64, 64)
     model_kwargs = {k: v for k, v in algo.items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
     resume = args.resume_from or ws.get("init_approach_checkpoint", "")
-    hidden = checkpoint.hidden_for_run(args.hidden, resume)     # a reference-trained zip is 2x64: the model takes the checkpoint's width
     if args.seeds is not None:
-        return _main_population(args, cfg, env_cfg, algo, ws, root, batch, model_kwargs, resume, hidden, world, local_rank)
+        return _main_population(args, cfg, env_cfg, algo, ws, root, batch, model_kwargs, resume, world, local_rank)
+    hidden = checkpoint.hidden_for_run(args.hidden, resume)     # a reference-trained zip is 2x64: the model takes the checkpoint's width
     if rank == 0:
         _start_artifacts(root, args, cfg)
 
@@ -256,52 +261,59 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, 
     return summary
 
 
-def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model_kwargs, resume, hidden: int, world: int, device: int) -> dict[str, Any]:
-    """--seeds: the seeds train together as one ApproachPopulationPPO -- one env handle of K x n_envs envs and one tracker launch per env
-    step for all seeds; seed s writes what a --seed s run writes, under root/seed_<s>/"""
+def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model_kwargs, resume, world: int, device: int) -> dict[str, Any]:
+    """--seeds [--sweep]: the replicas train together as one ApproachPopulationPPO -- one env handle of K x n_envs envs and one tracker launch
+    per env step for all of them; replica k writes what a --seed s_k run with its overrides writes, under root/<replica name>/ (seed_<s>
+    without --sweep).  --resume-from / workspace_expansion.init_approach_checkpoint: a checkpoint zip every replica starts from, or the root
+    of an earlier --seeds run (replica k starts from its own directory's model_latest.zip), as a --seed run resumes (weights, Adam state,
+    the saved algorithm constants; the step clock starts at zero)."""
     from .curriculum import PointCurriculumPopulation
-    from .population import ApproachPopulationPPO, learn_population, parse_seeds, population_summary
+    from .population import ApproachPopulationPPO, learn_population, plan_replicas, population_summary, resolve_resume_population
     from .vec_env import ArmKinematicPopulationVecEnv
 
-    seeds = parse_seeds(args.seeds)
+    seeds, overrides, names = plan_replicas(args.seeds, args.sweep)
     if world > 1:
         raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
-    if resume and Path(resume).exists():
-        raise ValueError("--seeds starts every seed from its own initialisation; it does not resume from a checkpoint (--resume-from / "
-                         "workspace_expansion.init_approach_checkpoint)")
-    roots = {s: root / f"seed_{s}" for s in seeds}
+    # refusals before any device work: the replicas, the width, and the checkpoints a population cannot resume together
+    resume_paths = resolve_resume_population(resume, seeds, names) if resume and Path(resume).exists() else None
+    hidden = checkpoint.hidden_for_run(args.hidden, resume_paths[0] if resume_paths else None)
+    roots = [root / n for n in names]
     pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=hidden)
-    ApproachPopulationPPO._check_population_args(seeds, pcfg, None, None)     # refusals before any device work
-    env = ArmKinematicPopulationVecEnv(env_cfg, seeds, args.n_envs, device=device)
+    ApproachPopulationPPO._check_population_args(seeds, pcfg, None, None, overrides)
+    env = ArmKinematicPopulationVecEnv(env_cfg, seeds, args.n_envs, device=device, repeated_seeds=True)
     kw = _curriculum_kwargs(cfg, env_cfg)
     curriculum = None
     if kw is not None:
         curriculum = PointCurriculumPopulation(**kw, initial_stage_indices=[int(ws.get("start_stage_index", 0))] * len(seeds), device=device)
-    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=curriculum)
-    for s in seeds:
-        _start_artifacts(roots[s], args, cfg)
+    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides)
+    if resume_paths is not None:
+        pop.load_init_checkpoints(resume_paths, restore_timesteps=False)
+        print(f"Resuming workspace expansion of every replica from {resume}")
+    for r in roots:
+        _start_artifacts(r, args, cfg)
     finisher_policy, finisher_cfg = _load_finisher(ws, device)
     gate_cfg = dict(ws.get("gate", {}) or {})
     gates = {}
     if not args.no_gate_callback and finisher_policy is not None:
-        gates = {s: _make_gate(roots[s], env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, device) for s in seeds}
+        gates = {k: _make_gate(roots[k], env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, device) for k in range(len(seeds))}
 
     def on_iteration(p) -> None:
-        for k, s in enumerate(seeds):
-            if s in gates:
-                gates[s].on_iteration(p.replica(k), env_cfg)
+        for k in range(len(seeds)):
+            if k in gates:
+                gates[k].on_iteration(p.replica(k), env_cfg)
 
     wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), on_iteration=on_iteration, log_every=args.log_every, tag="ppo-population")
     rows = []
     for k, s in enumerate(seeds):
         rep = pop.replica(k)
-        summ = _final_artifacts(roots[s], rep, env_cfg, args=args, resume=None, n_envs=args.n_envs, world=1, curriculum=pop.curricula[k],
-                                finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, ws=ws, gate_cfg=gate_cfg, device=device, wall=wall,
-                                extra={"seed": s})
-        best = gates[s].best_score if s in gates and gates[s].best_score != float("-inf") else None
-        rows.append({"seed": s, "artifact_root": str(roots[s]), "final_curriculum_stage": pop.curricula[k].read().stage_index if pop.curricula[k] else None,
+        extra = {"seed": s} if overrides is None else {"seed": s, "replica": names[k], "overrides": dict(overrides[k])}
+        summ = _final_artifacts(roots[k], rep, env_cfg, args=args, resume=resume_paths[k] if resume_paths else None, n_envs=args.n_envs, world=1,
+                                curriculum=pop.curricula[k], finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, ws=ws, gate_cfg=gate_cfg,
+                                device=device, wall=wall, extra=extra)
+        best = gates[k].best_score if k in gates and gates[k].best_score != float("-inf") else None
+        rows.append({"seed": s, "artifact_root": str(roots[k]), "final_curriculum_stage": pop.curricula[k].read().stage_index if pop.curricula[k] else None,
                      "last_update_stats": summ["last_update_stats"], "best_score": best, "model_latest": summ["model_path"],
-                     "model_best_by_gate": str(roots[s] / "best_checkpoint" / "model_best_by_gate.zip") if best is not None else None})
+                     "model_best_by_gate": str(roots[k] / "best_checkpoint" / "model_best_by_gate.zip") if best is not None else None})
     summary = population_summary(pop, rows, wall_seconds=wall, selection="workspace eval gate score (best_model_selection.score)")
     write_json(root / "population_summary.json", summary)
     pop.close()

@@ -35,6 +35,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     seeds.add_argument("--seed", type=int)
     seeds.add_argument("--seeds", help="comma-separated seeds trained together as one population (2x64 / 2x128 nets, one GPU); seed s writes "
                                        "the artefacts of a --seed s run under <artifact-root>/seed_<s>/, plus population_summary.json")
+    p.add_argument("--sweep", action="append", metavar="KEY=v1,v2", help="with --seeds: train every seed with each value of a PPO hyper-parameter "
+                   "(repeatable; replicas = seeds x values, seed-major, at most 16); each replica writes what --seed s with those settings writes "
+                   "under seed_<s>_<key>_<value>/")
     p.add_argument("--resume-from", help="a checkpoint zip; with --seeds also the artifact root of an earlier --seeds run (seed s resumes "
                                           "from seed_<s>/model_latest.zip)")
     p.add_argument("--n-envs", type=int, default=4096, help="environments per GPU")
@@ -63,6 +66,8 @@ def evaluate_dock(ppo: PPO, env_cfg: kcfg.EnvConfig, *, episodes: int, seed: int
 
 def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
+    if args.sweep and args.seeds is None:
+        raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -157,32 +162,32 @@ def _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root: Path, w
     earlier --seeds run (seed s starts from seed_<s>/model_latest.zip).  The selection score of population_summary.json is each seed's dock
     evaluation success rate."""
     from .finisher_tools import DockReverseCurriculumPopulation
-    from .population import DockPopulationPPO, learn_population, parse_seeds, population_summary, resolve_resume_population
+    from .population import DockPopulationPPO, learn_population, plan_replicas, population_summary, resolve_resume_population
     from .vec_env import ArmKinematicPopulationVecEnv
 
-    seeds = parse_seeds(args.seeds)
+    seeds, overrides, names = plan_replicas(args.seeds, args.sweep)
     if world > 1:
         raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
     # refusals before any device work: the seeds, the width, and the checkpoints a population cannot resume together
-    resume_paths = resolve_resume_population(args.resume_from, seeds)
+    resume_paths = resolve_resume_population(args.resume_from, seeds, names)
     n_envs = args.n_envs
     batch = args.batch_size or max(n_envs * args.n_steps // 64, 64)
     model_kwargs = {k: v for k, v in algo.items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
     hidden = checkpoint.hidden_for_run(args.hidden, resume_paths[0] if resume_paths else None)
     pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=hidden)
-    DockPopulationPPO._check_population_args(seeds, pcfg, None, None)
+    DockPopulationPPO._check_population_args(seeds, pcfg, None, None, overrides)
     cur_cfg = runtime.get("dock_reverse_curriculum", {}) or {}
-    env = ArmKinematicPopulationVecEnv(env_cfg, seeds, n_envs, device=device, mode="dock")
+    env = ArmKinematicPopulationVecEnv(env_cfg, seeds, n_envs, device=device, mode="dock", repeated_seeds=True)
     curriculum = None
     if bool(cur_cfg.get("enabled", False)):
         curriculum = DockReverseCurriculumPopulation(stages=list(cur_cfg.get("stages", [])), window_episodes=int(cur_cfg.get("window_episodes", 100)),
                                                      n_replicas=len(seeds), handoff_base_dirs=base_dirs)
-    pop = DockPopulationPPO(seeds, pcfg, env, curriculum=curriculum)
+    pop = DockPopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides)
     if resume_paths is not None:
         pop.load_init_checkpoints(resume_paths)
         print(f"Resuming dock policies from {args.resume_from}")
-    roots = {s: root / f"seed_{s}" for s in seeds}
-    for r in roots.values():
+    roots = [root / n for n in names]
+    for r in roots:
         r.mkdir(parents=True, exist_ok=True)
     wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), log_every=args.log_every, tag="ppo-dock-population")
     rows = []
@@ -191,9 +196,9 @@ def _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root: Path, w
         cur = curriculum.replica(k) if curriculum is not None else None
         cfg_k = cur.config if cur is not None else env_cfg
         resume = resume_paths[k] if resume_paths is not None else args.resume_from
-        summ = _final_artifacts(roots[s], rep, cfg_k, args=args, cfg=cfg, curriculum=cur, resume=resume, n_envs=n_envs, world=1, seed=s,
-                                device=device, wall=wall, extra={"seed": s})
-        rows.append({"seed": s, "artifact_root": str(roots[s]), "final_curriculum_stage": cur.current_stage_index if cur is not None else None,
+        summ = _final_artifacts(roots[k], rep, cfg_k, args=args, cfg=cfg, curriculum=cur, resume=resume, n_envs=n_envs, world=1, seed=s,
+                                device=device, wall=wall, extra={"seed": s} if overrides is None else {"seed": s, "replica": names[k], "overrides": dict(overrides[k])})
+        rows.append({"seed": s, "artifact_root": str(roots[k]), "final_curriculum_stage": cur.current_stage_index if cur is not None else None,
                      "last_update_stats": rep.last_stats, "best_score": summ["dock_eval_summary"]["success_rate"], "model_latest": summ["model_path"]})
     summary = population_summary(pop, rows, wall_seconds=wall, selection="dock evaluation success_rate")
     (root / "population_summary.json").write_text(json.dumps(summary, indent=2))

@@ -54,6 +54,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--config", required=True)
     p.add_argument("--route-path")
     p.add_argument("--init-checkpoint")
+    p.add_argument("--sweep", action="append", metavar="KEY=v1,v2", help="with --seeds: train every seed with each value of a PPO hyper-parameter "
+                   "(repeatable; replicas = seeds x values, seed-major, at most 16); each replica writes what --seed s with those settings writes "
+                   "under seed_<s>_<key>_<value>/")
     p.add_argument("--run-id", default="route_curriculum")
     p.add_argument("--output-dir")
     p.add_argument("--total-timesteps", type=int)
@@ -72,6 +75,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
 
 def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
+    if args.sweep and args.seeds is None:
+        raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
     import torch.distributed as dist
 
     # WORLD_SIZE / RANK / LOCAL_RANK as torchrun sets them; a process group the caller already initialised is used as it is
@@ -179,12 +184,13 @@ POPULATION_SELECTION = ("route gate accepted first, then the longest_success_pre
 
 def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route_path: Path, route_q, prefixes: list[int], env_cfg, runtime_cfg,
                      algo: dict[str, Any], init_checkpoint, root: Path, n_envs: int, world: int, device: int) -> dict[str, Any]:
-    """--seeds: the seeds train together as one RoutePopulationPPO; seed s writes what a --seed s run writes under root/seed_<s>/"""
-    from .population import RoutePopulationPPO, parse_seeds, population_summary
+    """--seeds [--sweep]: the replicas train together as one RoutePopulationPPO; replica k writes what a --seed s_k run with its overrides
+    writes under root/<replica name>/ (seed_<s> without --sweep)"""
+    from .population import RoutePopulationPPO, plan_replicas, population_summary
     from .route_curriculum import RoutePrefixCurriculumPopulation
     from .route_env import RoutePopulationVecEnv
 
-    seeds = parse_seeds(args.seeds)
+    seeds, overrides, names = plan_replicas(args.seeds, args.sweep)
     if world > 1:
         raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
     hidden = checkpoint.hidden_for_run(args.hidden, init_checkpoint)
@@ -200,14 +206,15 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
     n_steps = int(args.n_steps or algo.get("n_steps", 2048))
     batch = int(args.batch_size or algo.get("batch_size", 64))
     pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=n_steps, batch_size=batch, hidden=hidden)
-    roots = {s: root / f"seed_{s}" for s in seeds}
-    for r in roots.values():
+    RoutePopulationPPO._check_population_args(seeds, pcfg, None, None, overrides)     # refusals before any device work
+    roots = [root / n for n in names]
+    for r in roots:
         r.mkdir(parents=True, exist_ok=True)
     env = RoutePopulationVecEnv(env_cfg, rcfg.route_config_from_dict(cfg, max_route_index=prefixes[0]), route_q, seeds, n_envs, device=device)
     curriculum = RoutePrefixCurriculumPopulation.from_config(cfg, W)
     pop = None
     try:
-        pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=curriculum)
+        pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides)
         if init_checkpoint:
             pop.load_init_checkpoint(init_checkpoint)
             print(f"Resuming every route policy of the population from {init_checkpoint}")
@@ -220,8 +227,8 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
             pop.train()
             it += 1
             if pop.num_timesteps - start_steps >= next_checkpoint:
-                for k, s in enumerate(seeds):
-                    checkpoint.save(roots[s] / "checkpoints" / f"model_{pop.num_timesteps - start_steps}_steps", pop.replica(k), env_cfg)
+                for k in range(pop.K):
+                    checkpoint.save(roots[k] / "checkpoints" / f"model_{pop.num_timesteps - start_steps}_steps", pop.replica(k), env_cfg)
                 next_checkpoint += checkpoint_freq
             if args.log_every and it % args.log_every == 0:
                 stages = [curriculum.summary(k)["prefix_end_index"] for k in range(pop.K)]
@@ -232,14 +239,14 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
         rate = (pop.num_timesteps - start_steps) / max(wall, 1e-9)     # env steps of one replica per second of the population's training loop
         rows = []
         for k, s in enumerate(seeds):   # the sequential evaluations and gates run one seed after another, as single runs do
-            summary = _write_run_artifacts(args, cfg, route_cfg, route_path, route_q, env_cfg, init_checkpoint, roots[s], pop.replica(k),
+            summary = _write_run_artifacts(args, cfg, route_cfg, route_path, route_q, env_cfg, init_checkpoint, roots[k], pop.replica(k),
                                            curriculum.summary(k), {"enabled": False}, n_envs, 1, wall, rate, device)
             ev, gate = summary["route_eval_sequential_summary"], summary["route_gate_summary"]
             accepted = bool(gate.get("accepted", False))
             score = [int(accepted), int(ev.get("longest_success_prefix", 0) or 0), float(ev.get("success_rate", 0.0) or 0.0)]
             rows.append({"seed": s, "prefix_end_index": summary["curriculum_summary"]["prefix_end_index"], "gate_accepted": accepted,
                          "longest_success_prefix": score[1], "success_rate": score[2], "best_score": score,
-                         "model_path": str(roots[s] / "model_latest.zip"), "evaluation_wall_seconds": summary["evaluation_wall_seconds"],
+                         "model_path": str(roots[k] / "model_latest.zip"), "evaluation_wall_seconds": summary["evaluation_wall_seconds"],
                          "last_stats": pop.replica_stats(k)})
         out = population_summary(pop, rows, wall_seconds=wall, selection=POPULATION_SELECTION)
         out["aggregate_env_steps_per_second"] = pop.K * rate     # the steps of this run, not the init checkpoint's clock

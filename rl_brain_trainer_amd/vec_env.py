@@ -303,7 +303,8 @@ MAX_REPLICAS = 16     # KP1_CURRICULUM_MAX_REPLICAS / KP1_MLP_MAX_REPLICAS
 class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
     """K Approach or Finisher (dock-mode) envs of ``n_per_replica`` envs each in ONE handle: block k = rows [k N, (k + 1) N) is replica k, and
     is bit for bit ``ArmKinematicVecEnv(config, n_per_replica, seed=seeds[k])`` (env i of replica k owns ``default_rng(seeds[k] + i)``,
-    kp1_seed_blocks).  One ``step_into`` covers all K N rows, so a population rollout is one env step launch per step whatever K is -- the
+    kp1_seed_blocks; with ``repeated_seeds=True`` seeds may repeat -- a hyper-parameter sweep runs several replicas on one seed -- and equal
+    seeds give equal env streams).  One ``step_into`` covers all K N rows, so a population rollout is one env step launch per step whatever K is -- the
     [K N, obs_w] buffers are the population rollout's replica-major layout.
 
     Approach: a PointCurriculumPopulation attached to it gives every replica its own curriculum stage: the auto-reset of env i reads the stage
@@ -316,14 +317,15 @@ class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
     is_population = True
 
     def __init__(self, config: kcfg.EnvConfig, seeds: list[int], n_per_replica: int, *, device: int | torch.device = 0, real: str = "f32",
-                 reward_components: bool = False, mode: str = "approach") -> None:
+                 reward_components: bool = False, mode: str = "approach", repeated_seeds: bool = False) -> None:
         self.seeds = [int(s) for s in seeds]
         if not self.seeds:
             raise ValueError("ArmKinematicPopulationVecEnv needs at least one seed")
         if len(self.seeds) > MAX_REPLICAS:
             raise ValueError(f"ArmKinematicPopulationVecEnv holds at most {MAX_REPLICAS} replicas (got {len(self.seeds)} seeds)")
-        if len(set(self.seeds)) != len(self.seeds):
-            raise ValueError(f"ArmKinematicPopulationVecEnv seeds must be distinct (got {self.seeds})")
+        if not repeated_seeds and len(set(self.seeds)) != len(self.seeds):
+            raise ValueError(f"ArmKinematicPopulationVecEnv seeds must be distinct (got {self.seeds}); a hyper-parameter sweep that runs several "
+                             "replicas on one seed passes repeated_seeds=True")
         if mode not in ("approach", "dock"):
             raise ValueError(f"ArmKinematicPopulationVecEnv runs the Approach or the dock mode, not {mode!r}")
         if config.mode_name != mode:

@@ -67,6 +67,13 @@ def build_approach(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, u
                          curriculum_factory=lambda s: PointCurriculum(**tracker) if tracker else None, use_graphs=use_graphs)
 
 
+SWEEP: list[tuple[str, list[float]]] = []     # --sweep: replica k takes value k % len(values) of every swept key
+
+
+def _sweep_overrides(K: int) -> list[dict[str, float]] | None:
+    return [{key: vals[k % len(vals)] for key, vals in SWEEP} for k in range(K)] if SWEEP else None
+
+
 def build_approach_one_handle(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool) -> PopulationPPO:
     from rl_brain_trainer_amd.curriculum import PointCurriculumPopulation
     from rl_brain_trainer_amd.population import ApproachPopulationPPO
@@ -76,7 +83,7 @@ def build_approach_one_handle(K: int, n_envs: int, n_steps: int, batch: int, hid
     seeds = list(range(7, 7 + K))
     env = ArmKinematicPopulationVecEnv(env_cfg, seeds, n_envs)
     cur = PointCurriculumPopulation(**tracker, initial_stage_indices=[0] * K) if tracker else None
-    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=cur, use_graphs=use_graphs)
+    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=cur, use_graphs=use_graphs, overrides=_sweep_overrides(K))
     pop._bench_owned = [c for c in (cur, env) if c is not None]     # closed after the population (the caller owns them)
     return pop
 
@@ -202,8 +209,16 @@ def main() -> None:
     ap.add_argument("--n-steps", type=int, default=0, help="steps per rollout (0 = 1024, or 256 with --dock)")
     ap.add_argument("--batch", type=int, default=0, help="minibatch (0 = 256, or 512 with --route)")
     ap.add_argument("--hidden", type=int, default=64)
+    ap.add_argument("--sweep", action="append", metavar="KEY=v1,v2", help="with --one-handle: per-replica hyper-parameters (replica k takes value "
+                    "k %% n of each key; the per-replica table and GAE scan of a population with overrides)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.sweep:
+        from rl_brain_trainer_amd.population import parse_sweep
+
+        if not args.one_handle:
+            ap.error("--sweep is measured on the --one-handle Approach iteration")
+        SWEEP[:] = parse_sweep(args.sweep)
     if args.route and args.one_handle:
         ap.error("--one-handle is the Approach form; --route is always one handle")
     if args.dock and (args.route or args.one_handle):
@@ -226,7 +241,8 @@ def main() -> None:
                 f"workspace_expansion_bigtrain.yaml Approach iteration (ApproachPopulationPPO: one env handle of K x {args.n_envs} envs)"
                 if args.one_handle else "workspace_expansion_bigtrain.yaml Approach iteration (PopulationPPO: one env handle per replica)")
     result = {"workload": f"{workload}, {args.n_envs} envs x {args.n_steps} steps per replica, "
-                          f"minibatch {args.batch}, 2x{args.hidden}, curriculum on; seeds 7..7+K-1", "device": torch.cuda.get_device_name(0), "rows": rows}
+                          f"minibatch {args.batch}, 2x{args.hidden}, curriculum on; seeds 7..7+K-1"
+                          + (f"; sweep {dict(SWEEP)} (replica k takes value k % n)" if SWEEP else ""), "device": torch.cuda.get_device_name(0), "rows": rows}
     if args.out:
         Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
     print(json.dumps({"aggregate_env_steps_per_s": {r["K"]: round(r["aggregate_env_steps_per_s"]) for r in rows}}))
