@@ -243,6 +243,24 @@ int kp1_mlp_forward(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n,
 int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t obs_stride, const float* noise, float* value, float* action,
                              float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream);
 
+/* One step of the batched deterministic evaluator (kp1_eval_accumulate's episodes) in ONE launch: the deterministic policy of `m` on the
+ * current observations of ALL envs of `env`, action = clip(mean, -1, 1), its fp64 norm sqrt(a0^2 + ... + a6^2) (products and sums in index
+ * order, uncontracted), the env step without auto-reset, and kp1_eval_accumulate's bookkeeping of env step number `step` for every buffer
+ * of `buffers`, n_alive included.  Same results, bit for bit, as kp1_mlp_forward (noise NULL, clipped_action) + that norm + kp1_step
+ * (auto_reset 0) + kp1_eval_accumulate (tests/test_population_eval_gpu.py).
+ *   m         a K = 1 or a population handle, hidden 64 or 128, 56-float observations; only the policy net runs, no activation workspace
+ *             is used (max_batch does not bound the env count)
+ *   env       fp32 handle of K * n envs in approach or dock mode, reward components off, no bound tracker / population stages;
+ *             row m of replica k is env k n + m
+ *   obs       f32 [K n][the handle's obs stride, 56 or 64]: read (this step's observations) and overwritten (the next step's); a workgroup
+ *             reads its own rows before it writes them.  reward f32 [K n] and done u8 [K n] are written as kp1_step writes them.  These
+ *             are the buffers kp1_reset / kp1_step take: the handle itself owns none
+ *   step      >= 1; step 0 (initialisation after a reset, with the `active` mask) stays with kp1_eval_accumulate
+ *   stream    the launch stream (NULL: the default stream)
+ * Everything it cannot run is refused with a status and kp1_last_error text before any launch. */
+int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* done, const kp1_eval_buffers* buffers, int32_t step,
+                  const double* ready_thresholds /* [4] or NULL */, int32_t confirm_steps, void* stream);
+
 /* one PPO minibatch: forward + loss + full backward.  Rows are gathered through idx (int64 [n] into the [total] axis, or
  * NULL = rows 0..n).  grad_out f32 [num_params] receives d loss / d params in SB3 order (overwritten), with
  *   loss = sum_i[-min(r_i A_i, clip(r_i, 1-c, 1+c) A_i)] * inv_count + vf_coef * sum_i (R_i - V_i)^2 * inv_count - ent_coef * H,

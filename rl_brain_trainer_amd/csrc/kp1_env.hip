@@ -617,9 +617,8 @@ int launch_reset(kp1_env* e, const uint8_t* mask, const ResetOptsDev& opts, int 
 }
 
 // ---------------------------------------------------------------------------------------------- evaluator bookkeeping (kp1_eval_accumulate)
-// One lane per episode.  STATE_W = the 34 leading real fields of the handle (q, dq, prev_action, goal_q, goal_pose6: F_Q .. F_GOAL_POSE + 5).
-constexpr int EVAL_STATE_W = F_GOAL_POSE + 6;
-static_assert(EVAL_STATE_W == 34 && F_Q == 0, "kp1_eval_buffers::state is the leading 34 fields of the handle");
+// One lane per episode.  The bookkeeping of a step (step >= 1) is eval_account_step, shared with eval_step_kernel (kp1_eval_step.inc).
+#include "kp1_eval_account.inc"
 template <typename R>
 __global__ void __launch_bounds__(256) eval_accumulate_kernel(const R* __restrict__ real, int n, kp1_eval_buffers b, const double* __restrict__ action_norm,
                                                               const uint8_t* __restrict__ done, const uint8_t* __restrict__ active, int step, bool track_ready,
@@ -645,49 +644,8 @@ __global__ void __launch_bounds__(256) eval_accumulate_kernel(const R* __restric
         for (int f = 0; f < EVAL_STATE_W; ++f) b.hand_state[(size_t)i * EVAL_STATE_W + f] = 0.0;
       }
       alive_after = a;
-    } else if (F[i]) {
-      const double an = action_norm[i], dqn = (double)real[(size_t)F_EXEC_DQ * n + i];
-      const uint8_t d = done[i];
-      const uint8_t succ = (d & KP1_DONE_SUCCESS) ? 1 : 0;
-      C[i] = step;
-      M[6 * (size_t)n + i] += an;
-      M[7 * (size_t)n + i] += dqn;
-      M[0 * (size_t)n + i] = pos; M[1 * (size_t)n + i] = ori; M[4 * (size_t)n + i] = an; M[5 * (size_t)n + i] = dqn;
-      const double mp = fmin(M[2 * (size_t)n + i], pos), mo = fmin(M[3 * (size_t)n + i], ori);
-      M[2 * (size_t)n + i] = mp; M[3 * (size_t)n + i] = mo;
-      F[1 * (size_t)n + i] = succ;
-      double st[EVAL_STATE_W];
-      for (int f = 0; f < EVAL_STATE_W; ++f) {
-        st[f] = (double)real[(size_t)f * n + i];
-        b.state[(size_t)i * EVAL_STATE_W + f] = st[f];
-      }
-      if (track_ready) {
-        bool rdy = thr_pos > 0.0 && thr_ori > 0.0 && pos <= thr_pos && ori <= thr_ori;
-        if (thr_act > 0.0) rdy = rdy && an <= thr_act;
-        if (thr_dq > 0.0) rdy = rdy && dqn <= thr_dq;
-        if (rdy) {
-          F[2 * (size_t)n + i] = 1;
-          if (C[2 * (size_t)n + i] < 0) C[2 * (size_t)n + i] = step;
-        }
-        const int streak = rdy ? C[3 * (size_t)n + i] + 1 : 0;
-        C[3 * (size_t)n + i] = streak;
-        if (streak > C[1 * (size_t)n + i]) C[1 * (size_t)n + i] = streak;
-        // first-confirmed handoff snapshot.  `ready_streak >= handoff_confirm_steps` as the reference writes it (eval_pipeline_ablation.py:103):
-        // with confirm <= 0 it holds at step 1 whatever the streak.  Whether a snapshot is wanted at all is "hand_metrics given".
-        if (b.hand_metrics && !F[3 * (size_t)n + i] && streak >= confirm) {
-          F[3 * (size_t)n + i] = 1;
-          double* H = b.hand_metrics;
-          H[0 * (size_t)n + i] = pos; H[1 * (size_t)n + i] = ori; H[2 * (size_t)n + i] = an; H[3 * (size_t)n + i] = dqn;
-          H[4 * (size_t)n + i] = mp; H[5 * (size_t)n + i] = mo;
-          H[6 * (size_t)n + i] = M[6 * (size_t)n + i]; H[7 * (size_t)n + i] = M[7 * (size_t)n + i];   // sums up to and including this step (:111-112)
-          b.hand_step[i] = step;
-          b.hand_success[i] = succ;
-          for (int f = 0; f < EVAL_STATE_W; ++f) b.hand_state[(size_t)i * EVAL_STATE_W + f] = st[f];
-        }
-      }
-      const uint8_t still = (d & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) ? 0 : 1;
-      F[i] = still;
-      alive_after = still;
+    } else {
+      alive_after = eval_account_step<R>(real, n, i, b, action_norm[i], done[i], step, track_ready, thr_pos, thr_ori, thr_act, thr_dq, confirm);
     }
   }
   // episodes still alive: wave ballot, one atomic per wave (an integer count: order does not matter)

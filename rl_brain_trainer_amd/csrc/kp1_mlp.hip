@@ -1220,6 +1220,7 @@ __global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(float* __restrict__ p,
 }
 
 #include "kp1_env_step.inc"
+#include "kp1_eval_step.inc"
 #include "kp1_mlp_tile.inc"
 #include "kp1_mlp_fused.inc"
 
@@ -1784,6 +1785,47 @@ int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t
   fa.noise = noise; fa.value = value; fa.action = action; fa.log_prob = log_prob;
   rc = launch_fused_infer_env(fa, mode, (hipStream_t)stream);
   if (rc != KP1_OK) return rc;
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* done, const kp1_eval_buffers* b, int32_t step,
+                  const double* ready_thresholds, int32_t confirm_steps, void* stream) {
+  if (!m || !env || !obs || !reward || !done || !b) return fail(KP1_ERR_INVALID, "NULL argument to kp1_eval_step");
+  if (!b->metrics || !b->counters || !b->flags || !b->state || !b->n_alive) return fail(KP1_ERR_INVALID, "kp1_eval_step: NULL buffer");
+  if (b->hand_metrics && (!b->hand_step || !b->hand_success || !b->hand_state)) return fail(KP1_ERR_INVALID, "kp1_eval_step: incomplete handoff buffers");
+  if (step < 1) return fail(KP1_ERR_INVALID, "kp1_eval_step accounts env steps 1, 2, ...: step 0 (the initialisation after a reset) is kp1_eval_accumulate's");
+  if (m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step covers the layer-wise widths (hidden 64 / 128); a 2x256 policy is evaluated through kp1_mlp_forward");
+  if (m->L.INP != ES_INP) return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step needs the 56-float observation (padded to 64)");
+  EvalStepArgs a{};
+  int mode = 0, device = 0;
+  int64_t n_envs = 0;
+  // refuses f64 handles, recorded reward components and env handles with bound population stages
+  int rc = kp1::env_step_args_f32(env, &a.env, sizeof a.env, nullptr, obs, reward, done, nullptr, 0, &mode, &n_envs, &device);
+  if (rc != KP1_OK) return rc;
+  if (a.env.stage_ptr) return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step: the env handle is bound to a curriculum tracker (an evaluation handle has none)");
+  if (device != m->device) return fail(KP1_ERR_INVALID, "the env handle and the MLP workspace live on different devices");
+  if (mode != KP1_MODE_APPROACH && mode != KP1_MODE_DOCK) return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step steps the approach or the dock mode");
+  if (n_envs <= 0 || n_envs % m->K != 0) return fail(KP1_ERR_INVALID, "kp1_eval_step: the env count must be a multiple of the handle's replica count");
+  rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  const int Hp = m->Hp, INP = m->L.INP;
+  a.b = *b;
+  a.w1 = m->k.w1p; a.b1 = m->k.b1; a.w2 = m->k.w2; a.b2 = m->k.b2; a.w3 = m->k.w3; a.b3 = m->k.b3;   // net 0 (policy) leads every array
+  a.r_w1 = (unsigned)(2 * Hp * INP); a.r_w2 = (unsigned)(2 * Hp * Hp); a.r_b = (unsigned)(2 * Hp); a.r_w3 = (unsigned)(HEADS * Hp); a.r_b3 = (unsigned)HEADS;
+  a.n = (int)(n_envs / m->K);
+  a.Kreal = a.env.obs_stride >= INP ? INP : m->L.IN;
+  a.step = step; a.confirm = confirm_steps;
+  a.track_ready = ready_thresholds != nullptr;
+  if (ready_thresholds) { a.thr_pos = ready_thresholds[0]; a.thr_ori = ready_thresholds[1]; a.thr_act = ready_thresholds[2]; a.thr_dq = ready_thresholds[3]; }
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(b->n_alive, 0, sizeof(int32_t), st));
+  const dim3 grid((unsigned)((a.n + ES_BM - 1) / ES_BM), (unsigned)m->K);
+  const bool pop = m->K > 1, dock = mode == KP1_MODE_DOCK;
+  if (pop && dock) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_DOCK, true>), grid, dim3(ES_NTH), 0, st, a);
+  else if (pop) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_APPROACH, true>), grid, dim3(ES_NTH), 0, st, a);
+  else if (dock) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_DOCK, false>), grid, dim3(ES_NTH), 0, st, a);
+  else hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_APPROACH, false>), grid, dim3(ES_NTH), 0, st, a);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }

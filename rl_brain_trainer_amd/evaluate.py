@@ -354,6 +354,75 @@ def _run_episodes_reference(env: ArmKinematicVecEnv, policy: PolicyFn, reset_opt
     return res, hand
 
 
+def _is_fused_width(mlp: Any) -> bool:
+    """an MlpKernels the one-launch evaluation step covers: the layer-wise widths on the 56-float observation"""
+    return mlp is not None and int(getattr(mlp, "hidden", 0)) in (64, 128) and int(getattr(mlp, "obs_dim", 0)) == kcfg.OBS_DIM
+
+
+def run_episodes_fused(env: ArmKinematicVecEnv, mlp: Any, reset_options: dict[str, Any], *, ready_cfg=None, handoff_confirm_steps: int | None = None,
+                       active: torch.Tensor | None = None, max_steps: int | None = None) -> tuple[dict[str, torch.Tensor], dict[str, torch.Tensor] | None]:
+    """run_episodes with the whole env step in ONE launch (kp1_eval_step): the deterministic policy of ``mlp`` (an MlpKernels of hidden 64 /
+    128: a K = 1 handle, or a population handle of K replicas over ``env``'s K x n envs, block k of the envs stepping under replica k's
+    weights), the fp64 norm of the clipped action, the env step and the per-episode bookkeeping.  The observations stay in the env's own
+    buffer, which the launch reads and overwrites.  Same return value as run_episodes; every tensor not derived from the action norm is
+    bit-equal to it, and the action-norm tensors are the norm summed in index order (tests/test_population_eval_gpu.py)."""
+    if not isinstance(env, ArmKinematicVecEnv):
+        raise TypeError("run_episodes_fused drives an ArmKinematicVecEnv (kp1_eval_step steps its handle)")
+    E = env.n_envs
+    dev = env.device
+    L = native.load()
+    env.use_current_stream()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    env.reset(options=reset_options)
+    f64, i32, u8 = torch.float64, torch.int32, torch.uint8
+    metrics = torch.empty((8, E), dtype=f64, device=dev)
+    counters = torch.empty((4, E), dtype=i32, device=dev)
+    flags = torch.empty((4, E), dtype=u8, device=dev)
+    state = torch.empty((E, 34), dtype=f64, device=dev)
+    n_alive = torch.zeros(1, dtype=i32, device=dev)
+    want_hand = handoff_confirm_steps is not None and ready_cfg is not None
+    confirm = int(handoff_confirm_steps or 0)
+    hand_metrics = torch.empty((8, E), dtype=f64, device=dev) if want_hand else None
+    hand_step = torch.empty(E, dtype=i32, device=dev) if want_hand else None
+    hand_success = torch.empty(E, dtype=u8, device=dev) if want_hand else None
+    hand_state = torch.empty((E, 34), dtype=f64, device=dev) if want_hand else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    bufs = native.EvalBuffers(ptr(metrics), ptr(counters), ptr(flags), ptr(state), ptr(hand_metrics), ptr(hand_step), ptr(hand_success), ptr(hand_state),
+                              ptr(n_alive))
+    thr = None
+    if ready_cfg is not None:
+        thr = (C.c_double * 4)(ready_cfg.dock_coarse_ready_pos_threshold_m, ready_cfg.dock_coarse_ready_ori_threshold_rad,
+                               ready_cfg.dock_coarse_ready_action_threshold, ready_cfg.dock_coarse_ready_dq_threshold)
+    act_mask = None if active is None else active.to(dev).to(u8).contiguous()
+    native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs), None, None, ptr(act_mask), 0, thr, confirm, stream))
+    limit = int(max_steps or (env.config.c.termination.max_episode_steps + 1))
+    for step in range(1, limit + 1):
+        if (step - 1) % _ALIVE_CHECK_EVERY == 0 and int(n_alive.item()) == 0:
+            break
+        native.check(L.kp1_eval_step(mlp._h, env._handle, ptr(env.obs), ptr(env.reward), ptr(env.done), C.byref(bufs), step, thr, confirm, stream))
+    res = {
+        "success": flags[1].bool(), "final_position_error": metrics[0], "final_orientation_error": metrics[1], "min_position_error": metrics[2],
+        "min_orientation_error": metrics[3], "final_action_magnitude": metrics[4], "final_dq_norm": metrics[5], "sum_action": metrics[6],
+        "sum_dq": metrics[7], "ready_hit": flags[2].bool(), "max_ready_streak": counters[1], "first_ready_step": counters[2], "step_count": counters[0],
+    }
+    steps = res["step_count"].clamp_min(1).double()
+    res["mean_action_magnitude"] = res["sum_action"] / steps
+    res["mean_dq_norm"] = res["sum_dq"] / steps
+    for k, lo, hi in _STATE_SLICES:
+        res["state_" + k] = state[:, lo:hi].contiguous()
+    hand = None
+    if want_hand:
+        hand = {"valid": flags[3].bool(), "final_position_error": hand_metrics[0], "final_orientation_error": hand_metrics[1],
+                "final_action_magnitude": hand_metrics[2], "final_dq_norm": hand_metrics[3], "min_position_error": hand_metrics[4],
+                "min_orientation_error": hand_metrics[5], "step_count": hand_step, "success": hand_success.bool()}
+        hsteps = hand_step.clamp_min(1).double()
+        hand["mean_action_magnitude"] = hand_metrics[6] / hsteps
+        hand["mean_dq_norm"] = hand_metrics[7] / hsteps
+        for k, lo, hi in _STATE_SLICES:
+            hand["state_" + k] = hand_state[:, lo:hi].contiguous()
+    return res, hand
+
+
 def _handoff_options(src: dict[str, torch.Tensor], mode: str) -> dict[str, Any]:
     """_state_reset_options; eval_three_stage.py:30-38"""
     return {"initial_q": src["state_q"].cpu().numpy(), "initial_dq": src["state_dq"].cpu().numpy(),
@@ -385,15 +454,8 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
     a_res, hand = run_episodes(env, approach_policy, {"initial_q": cat["initial_q"], "goal_q": cat["goal_q"], "goal_pose6": cat["goal_pose6"],
                                                       "policy_mode": "approach"}, ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps)
     env.close()
-    final_ready = finisher_ready(a_res["final_position_error"], a_res["final_orientation_error"], a_res["final_action_magnitude"], a_res["final_dq_norm"], r)
-    # handoff source: the final state if it is finisher-ready, else the first confirmed-ready snapshot (eval_workspace_expansion.py:138-139)
-    has_hand = final_ready | hand["valid"]
-    src = {}
-    for k in ("state_q", "state_dq", "state_prev_action", "state_goal_q", "state_goal_pose6"):
-        hk = hand.get(k, torch.zeros_like(a_res[k]))
-        src[k] = torch.where(final_ready[:, None], a_res[k], hk)
-    final = {k: a_res[k].clone() for k in ("final_position_error", "final_orientation_error", "final_action_magnitude", "final_dq_norm")}
-    success = a_res["success"].clone()
+    final_ready, has_hand, src = _handoff_sources(a_res, hand, r)
+    f_res = None
     if finisher_policy is not None and finisher_cfg is not None and bool(has_hand.any()):
         fenv = ArmKinematicVecEnv(finisher_cfg, E, device=device, seed=seed)
         if obs_stride != 56:
@@ -402,6 +464,30 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
         safe = {k: torch.where(has_hand[:, None], v, a_res[k]) for k, v in src.items()}
         f_res, _ = run_episodes(fenv, finisher_policy, _handoff_options(safe, "dock"), active=has_hand)
         fenv.close()
+    cols = _eval_columns(a_res, final_ready, has_hand, f_res, handoff_confirm_steps)
+    return _workspace_payload(cols, cat["goal_pose6"], approach_cfg=approach_cfg, stages=stages, episodes=episodes, seed=seed,
+                              handoff_confirm_steps=handoff_confirm_steps, gate_config=gate_config, artifact_root=artifact_root)
+
+
+def _handoff_sources(a_res: dict[str, torch.Tensor], hand: dict[str, torch.Tensor], r) -> tuple[torch.Tensor, torch.Tensor, dict[str, torch.Tensor]]:
+    """(final_ready, has_hand, src) of an Approach phase: the handoff source of a row is its final state if that is finisher-ready, else the
+    first confirmed-ready snapshot (eval_workspace_expansion.py:138-139)"""
+    final_ready = finisher_ready(a_res["final_position_error"], a_res["final_orientation_error"], a_res["final_action_magnitude"], a_res["final_dq_norm"], r)
+    has_hand = final_ready | hand["valid"]
+    src = {}
+    for k in ("state_q", "state_dq", "state_prev_action", "state_goal_q", "state_goal_pose6"):
+        hk = hand.get(k, torch.zeros_like(a_res[k]))
+        src[k] = torch.where(final_ready[:, None], a_res[k], hk)
+    return final_ready, has_hand, src
+
+
+def _eval_columns(a_res: dict[str, torch.Tensor], final_ready: torch.Tensor, has_hand: torch.Tensor, f_res: dict[str, torch.Tensor] | None,
+                  handoff_confirm_steps: int, rows: slice = slice(None)) -> dict[str, Any]:
+    """the per-episode host columns the row / summary code reads, for episodes ``rows`` of the run (a replica's block of a population run):
+    the Approach results (A), the finals after the Finisher where one ran (F), success, ready hit / dwell and the two regression flags"""
+    final = {k: a_res[k].clone() for k in ("final_position_error", "final_orientation_error", "final_action_magnitude", "final_dq_norm")}
+    success = a_res["success"].clone()
+    if f_res is not None:
         for k in final:
             final[k] = torch.where(has_hand, f_res[k], final[k])
         success = torch.where(has_hand, f_res["success"], success)
@@ -411,11 +497,20 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
     ori_reg = a_res["final_orientation_error"] > a_res["min_orientation_error"] + 0.01
 
     def cpu(t):
-        return t.detach().cpu().numpy()
+        return t[rows].detach().cpu().numpy()
 
-    A = {k: cpu(v) for k, v in a_res.items() if v.ndim == 1}
-    F = {k: cpu(v) for k, v in final.items()}
-    succ, rh, rd, pr, orr = cpu(success), cpu(ready_hit), cpu(ready_dwell), cpu(pos_reg), cpu(ori_reg)
+    return {"A": {k: cpu(v) for k, v in a_res.items() if v.ndim == 1}, "F": {k: cpu(v) for k, v in final.items()}, "success": cpu(success),
+            "ready_hit": cpu(ready_hit), "ready_dwell": cpu(ready_dwell), "position_regression": cpu(pos_reg), "orientation_regression": cpu(ori_reg)}
+
+
+def _workspace_payload(cols: dict[str, Any], goal_pose6: np.ndarray, *, approach_cfg: kcfg.EnvConfig, stages: list[int], episodes: int, seed: int,
+                       handoff_confirm_steps: int, gate_config: dict[str, Any] | None, artifact_root: str | Path | None) -> dict[str, Any]:
+    """target rows, per-stage summaries and the gated selection of one policy's evaluation from its host columns (_eval_columns; episode
+    e of stage number si is column si * episodes + e), written under ``artifact_root`` when one is given"""
+    r = approach_cfg.c.reward
+    A, F = cols["A"], cols["F"]
+    succ, rh, rd, pr, orr = cols["success"], cols["ready_hit"], cols["ready_dwell"], cols["position_regression"], cols["orientation_regression"]
+    cat = {"goal_pose6": goal_pose6}
     rows: list[dict[str, Any]] = []
     stage_summaries: dict[int, dict[str, Any]] = {}
     for si, s in enumerate(stages):
@@ -470,3 +565,70 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
         (root / "best_model_selection_summary.json").write_text(json.dumps(selection, indent=2))
         (root / "workspace_eval_summary.json").write_text(json.dumps(payload, indent=2))
     return payload
+
+
+def check_population_eval(population: Any, artifact_roots: list[Any] | None) -> int:
+    """the host-side refusals of evaluate_workspace_expansion_population, before any device call; returns K"""
+    K = int(population.K)
+    if artifact_roots is not None and len(artifact_roots) != K:
+        raise ValueError(f"{len(artifact_roots)} artifact roots for a population of {K} replicas: the evaluator writes one set of files per replica")
+    if int(getattr(population, "obs_dim", kcfg.OBS_DIM)) != kcfg.OBS_DIM:
+        raise ValueError("evaluate_workspace_expansion_population evaluates Approach populations (56-float observation); a route population has "
+                         "its own evaluator")
+    hidden = int(population.cfg.hidden)
+    if hidden not in (64, 128):
+        raise ValueError(f"evaluate_workspace_expansion_population runs the one-launch evaluation step of the 2x64 / 2x128 nets; hidden={hidden} "
+                         "is evaluated per policy with evaluate_workspace_expansion")
+    return K
+
+
+def evaluate_workspace_expansion_population(*, population: Any, finisher_policy: Any, approach_cfg: kcfg.EnvConfig, finisher_cfg: kcfg.EnvConfig | None,
+                                            episodes: int = 50, seed: int = 700001, stage_indices: list[int] | None = None,
+                                            handoff_confirm_steps: int = 2, gate_config: dict[str, Any] | None = None,
+                                            artifact_roots: list[str | Path] | None = None, device: int = 0) -> list[dict[str, Any]]:
+    """evaluate_workspace_expansion of every replica of a PopulationPPO at once: K payloads (and K sets of JSON files under
+    ``artifact_roots[k]``), each what ``evaluate_workspace_expansion(approach_policy=population.replica(k).predict, ...)`` returns up to
+    the summation order of the action norm.
+
+    The suite is built once and tiled K times into one Approach handle of K x E envs; block k steps under replica k's weights as the
+    population's own training handle holds them (no parameter copy, no repack), one kp1_eval_step launch per env step for all replicas.
+    The Finisher phase is one run over all K x E rows with the shared Finisher policy (``finisher_policy``: an InferencePolicy, stepped in
+    one launch when its net is 64 / 128 wide and through run_episodes otherwise).  Episodes of different replicas run in lock step until
+    none of any replica is alive; a finished episode's bookkeeping is frozen, so the extra steps change nothing in its block."""
+    K = check_population_eval(population, artifact_roots)
+    n_stages = approach_cfg.n_stages
+    stages = stage_indices if stage_indices is not None else list(range(n_stages))
+    stages = [int(np.clip(s, 0, n_stages - 1)) for s in stages]
+    suites = [build_curriculum_local_eval_suite(approach_cfg, seed=seed + s * 1009, stage_index=s, n_episodes=episodes, device=device) for s in stages]
+    cat = {k: np.concatenate([su[k] for su in suites]) for k in suites[0]}
+    E = cat["initial_q"].shape[0]
+    r = approach_cfg.c.reward
+    obs_stride = int(population.obs_w)
+
+    env = ArmKinematicVecEnv(approach_cfg, K * E, device=device, seed=seed)
+    if obs_stride != 56:
+        env.set_obs_stride(obs_stride)
+    tiled = {k: np.tile(cat[k], (K, 1)) for k in ("initial_q", "goal_q", "goal_pose6")}
+    a_res, hand = run_episodes_fused(env, population._mlp, {**tiled, "policy_mode": "approach"}, ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps)
+    env.close()
+    final_ready, has_hand, src = _handoff_sources(a_res, hand, r)
+    f_res = None
+    if finisher_policy is not None and finisher_cfg is not None and bool(has_hand.any()):
+        fenv = ArmKinematicVecEnv(finisher_cfg, K * E, device=device, seed=seed)
+        if obs_stride != 56:
+            fenv.set_obs_stride(obs_stride)
+        # rows without a handoff still need finite reset inputs; they are masked out of every result
+        safe = {k: torch.where(has_hand[:, None], v, a_res[k]) for k, v in src.items()}
+        fmlp = getattr(finisher_policy, "_mlp", None)
+        if _is_fused_width(fmlp) and int(getattr(fmlp, "replicas", 1)) == 1:
+            f_res, _ = run_episodes_fused(fenv, fmlp, _handoff_options(safe, "dock"), active=has_hand)
+        else:
+            f_res, _ = run_episodes(fenv, finisher_policy, _handoff_options(safe, "dock"), active=has_hand)
+        fenv.close()
+    payloads = []
+    for k in range(K):
+        cols = _eval_columns(a_res, final_ready, has_hand, f_res, handoff_confirm_steps, rows=slice(k * E, (k + 1) * E))
+        payloads.append(_workspace_payload(cols, cat["goal_pose6"], approach_cfg=approach_cfg, stages=stages, episodes=episodes, seed=seed,
+                                           handoff_confirm_steps=handoff_confirm_steps, gate_config=gate_config,
+                                           artifact_root=None if artifact_roots is None else artifact_roots[k]))
+    return payloads

@@ -77,6 +77,7 @@ def load() -> C.CDLL:
     L.kp1_observe.argtypes = [vp, vp]
     L.kp1_get_info.argtypes = [vp, C.POINTER(kcfg.InfoView)]
     L.kp1_eval_accumulate.argtypes = [vp, C.POINTER(EvalBuffers), vp, vp, vp, i32, vp, i32, vp]
+    L.kp1_eval_step.argtypes = [vp, vp, vp, vp, vp, C.POINTER(EvalBuffers), i32, vp, i32, vp]
     L.kp1_get_reward_components.argtypes = [vp, C.POINTER(vp), C.POINTER(i32)]
     L.kp1_enable_reward_components.argtypes = [vp, i32]
     L.kp1_component_name.argtypes = [i32, i32]

@@ -45,6 +45,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
                    "(repeatable; replicas = seeds x values, seed-major, at most 16); each replica writes what --seed s with those settings writes "
                    "under <artifact-root>/seed_<s>_<key>_<value>/")
     p.add_argument("--no-gate-callback", action="store_true")
+    p.add_argument("--per-replica-eval", action="store_true", help="with --seeds: evaluate the replicas one after another (K gate evaluations per gate "
+                   "instant) instead of all of them in one population evaluation")
     p.add_argument("--n-envs", type=int, default=4096, help="environments per GPU")
     p.add_argument("--n-steps", type=int, default=128)
     p.add_argument("--batch-size", type=int, default=0, help="global minibatch; 0 = n_envs*n_steps*world/64")
@@ -84,19 +86,24 @@ class WorkspaceEvalGate:
         self.best_score = float("-inf")
         self.next_eval_timesteps = self.eval_interval
 
-    def on_iteration(self, ppo: PPO, env_cfg: kcfg.EnvConfig) -> dict[str, Any] | None:
-        from . import evaluate as ev
-
-        if ppo.num_timesteps < self.next_eval_timesteps:
-            return None
-        while self.next_eval_timesteps <= ppo.num_timesteps:
+    def due(self, num_timesteps: int) -> bool:
+        """whether an evaluation falls at this step count (then the next one is scheduled)"""
+        if num_timesteps < self.next_eval_timesteps:
+            return False
+        while self.next_eval_timesteps <= num_timesteps:
             self.next_eval_timesteps += self.eval_interval
+        return True
+
+    def save_candidate(self, ppo, env_cfg: kcfg.EnvConfig) -> Path:
         candidate = self.candidates_dir / f"candidate_step_{ppo.num_timesteps}"
         checkpoint.save(candidate, ppo, env_cfg)
-        summary = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, finisher_policy=self.finisher_policy, approach_cfg=self.approach_cfg,
-                                                  finisher_cfg=self.finisher_cfg, episodes=self.episodes, seed=self.seed, stage_indices=self.stage_indices,
-                                                  gate_config=self.gate_config, artifact_root=self.eval_dir / f"eval_step_{ppo.num_timesteps}",
-                                                  device=self.device, obs_stride=ppo.obs_w)
+        return candidate
+
+    def eval_root(self, num_timesteps: int) -> Path:
+        return self.eval_dir / f"eval_step_{num_timesteps}"
+
+    def record(self, ppo, env_cfg: kcfg.EnvConfig, candidate: Path, summary: dict[str, Any]) -> dict[str, Any]:
+        """an evaluation's selection -> eval_history.jsonl; a retention-ok best score -> best_checkpoint/model_best_by_gate.zip"""
         selection = summary["best_model_selection"]
         record = {"timesteps": int(ppo.num_timesteps), "candidate": str(candidate) + ".zip", **selection}
         with self.eval_history_path.open("a", encoding="utf-8") as handle:
@@ -107,6 +114,37 @@ class WorkspaceEvalGate:
             checkpoint.save(self.best_dir / "model_best_by_gate", ppo, env_cfg)
             write_json(self.artifact_root / "best_model_selection_summary.json", record)
         return record
+
+    def on_iteration(self, ppo: PPO, env_cfg: kcfg.EnvConfig) -> dict[str, Any] | None:
+        from . import evaluate as ev
+
+        if not self.due(ppo.num_timesteps):
+            return None
+        candidate = self.save_candidate(ppo, env_cfg)
+        summary = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, finisher_policy=self.finisher_policy, approach_cfg=self.approach_cfg,
+                                                  finisher_cfg=self.finisher_cfg, episodes=self.episodes, seed=self.seed, stage_indices=self.stage_indices,
+                                                  gate_config=self.gate_config, artifact_root=self.eval_root(ppo.num_timesteps),
+                                                  device=self.device, obs_stride=ppo.obs_w)
+        return self.record(ppo, env_cfg, candidate, summary)
+
+
+def population_gate_iteration(gates: dict[int, WorkspaceEvalGate], pop, env_cfg: kcfg.EnvConfig) -> list[dict[str, Any]] | None:
+    """the gate instant of a population whose every replica has a gate (all on one clock): K candidates, ONE population evaluation
+    (evaluate.evaluate_workspace_expansion_population: one launch per env step for all replicas), K history records"""
+    from . import evaluate as ev
+
+    due = [g.due(pop.num_timesteps) for g in gates.values()]
+    if not any(due):
+        return None
+    assert all(due) and sorted(gates) == list(range(pop.K)), "the replicas' gates share one clock"
+    g0 = gates[0]
+    reps = [pop.replica(k) for k in range(pop.K)]
+    candidates = [gates[k].save_candidate(reps[k], env_cfg) for k in range(pop.K)]
+    payloads = ev.evaluate_workspace_expansion_population(population=pop, finisher_policy=g0.finisher_policy, approach_cfg=g0.approach_cfg,
+                                                          finisher_cfg=g0.finisher_cfg, episodes=g0.episodes, seed=g0.seed, stage_indices=g0.stage_indices,
+                                                          gate_config=g0.gate_config, artifact_roots=[gates[k].eval_root(pop.num_timesteps) for k in range(pop.K)],
+                                                          device=g0.device)
+    return [gates[k].record(reps[k], env_cfg, candidates[k], payloads[k]) for k in range(pop.K)]
 
 
 def main(argv: list[str] | None = None) -> dict[str, Any]:
@@ -230,9 +268,11 @@ def _make_gate(root: Path, env_cfg: kcfg.EnvConfig, finisher_policy, finisher_cf
 
 
 def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, n_envs: int, world: int, curriculum, finisher_policy, finisher_cfg,
-                     ws: dict[str, Any], gate_cfg: dict[str, Any], device: int, wall: float, extra: dict[str, Any] | None = None) -> dict[str, Any]:
+                     ws: dict[str, Any], gate_cfg: dict[str, Any], device: int, wall: float, extra: dict[str, Any] | None = None,
+                     final_eval_payload: dict[str, Any] | None = None) -> dict[str, Any]:
     """what a run leaves at its end: model_latest (twice), the final Approach -> Finisher evaluation when a Finisher is configured, and
-    training_summary.json (`ppo` is a PPO or a population replica)"""
+    training_summary.json (`ppo` is a PPO or a population replica; ``final_eval_payload``: this replica's share of a population's final
+    evaluation, already written under root/final_eval)"""
     latest = root / "latest_checkpoint" / "model_latest"
     checkpoint.save(latest, ppo, env_cfg)
     checkpoint.save(root / "model_latest", ppo, env_cfg)
@@ -240,10 +280,12 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, 
     if finisher_policy is not None:   # train_workspace_expansion.py:243-259
         from . import evaluate as ev
 
-        final_eval = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, finisher_policy=finisher_policy, approach_cfg=env_cfg,
-                                                     finisher_cfg=finisher_cfg, episodes=int(ws.get("final_eval_episodes", 80)),
-                                                     seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)),
-                                                     gate_config=gate_cfg, artifact_root=root / "final_eval", device=device, obs_stride=ppo.obs_w)
+        final_eval = final_eval_payload
+        if final_eval is None:
+            final_eval = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, finisher_policy=finisher_policy, approach_cfg=env_cfg,
+                                                         finisher_cfg=finisher_cfg, episodes=int(ws.get("final_eval_episodes", 80)),
+                                                         seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)),
+                                                         gate_config=gate_cfg, artifact_root=root / "final_eval", device=device, obs_stride=ppo.obs_w)
         final_eval = {k: v for k, v in final_eval.items() if k != "target_rows"}
         for name in ("stage_metrics.json", "workspace_failure_report.json", "best_model_selection_summary.json"):
             if (root / "final_eval" / name).exists():
@@ -266,7 +308,8 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
     per env step for all of them; replica k writes what a --seed s_k run with its overrides writes, under root/<replica name>/ (seed_<s>
     without --sweep).  --resume-from / workspace_expansion.init_approach_checkpoint: a checkpoint zip every replica starts from, or the root
     of an earlier --seeds run (replica k starts from its own directory's model_latest.zip), as a --seed run resumes (weights, Adam state,
-    the saved algorithm constants; the step clock starts at zero)."""
+    the saved algorithm constants; the step clock starts at zero).  The gate and the final evaluation run once per gate instant for all
+    replicas (evaluate_workspace_expansion_population); --per-replica-eval evaluates them one after another."""
     from .curriculum import PointCurriculumPopulation
     from .population import ApproachPopulationPPO, learn_population, plan_replicas, population_summary, resolve_resume_population
     from .vec_env import ArmKinematicPopulationVecEnv
@@ -297,19 +340,32 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
     if not args.no_gate_callback and finisher_policy is not None:
         gates = {k: _make_gate(roots[k], env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, device) for k in range(len(seeds))}
 
+    fused_eval = not args.per_replica_eval
+
     def on_iteration(p) -> None:
+        if gates and fused_eval:
+            population_gate_iteration(gates, p, env_cfg)
+            return
         for k in range(len(seeds)):
             if k in gates:
                 gates[k].on_iteration(p.replica(k), env_cfg)
 
     wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), on_iteration=on_iteration, log_every=args.log_every, tag="ppo-population")
     rows = []
+    finals: list[Any] = [None] * len(seeds)
+    if finisher_policy is not None and fused_eval:      # the final evaluation of every replica: one population evaluation
+        from . import evaluate as ev
+
+        finals = ev.evaluate_workspace_expansion_population(population=pop, finisher_policy=finisher_policy, approach_cfg=env_cfg, finisher_cfg=finisher_cfg,
+                                                            episodes=int(ws.get("final_eval_episodes", 80)), seed=int(ws.get("eval_seed", 700001)),
+                                                            stage_indices=list(range(env_cfg.n_stages)), gate_config=gate_cfg,
+                                                            artifact_roots=[r / "final_eval" for r in roots], device=device)
     for k, s in enumerate(seeds):
         rep = pop.replica(k)
         extra = {"seed": s} if overrides is None else {"seed": s, "replica": names[k], "overrides": dict(overrides[k])}
         summ = _final_artifacts(roots[k], rep, env_cfg, args=args, resume=resume_paths[k] if resume_paths else None, n_envs=args.n_envs, world=1,
                                 curriculum=pop.curricula[k], finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, ws=ws, gate_cfg=gate_cfg,
-                                device=device, wall=wall, extra=extra)
+                                device=device, wall=wall, extra=extra, final_eval_payload=finals[k])
         best = gates[k].best_score if k in gates and gates[k].best_score != float("-inf") else None
         rows.append({"seed": s, "artifact_root": str(roots[k]), "final_curriculum_stage": pop.curricula[k].read().stage_index if pop.curricula[k] else None,
                      "last_update_stats": summ["last_update_stats"], "best_score": best, "model_latest": summ["model_path"],

@@ -27,6 +27,15 @@ PopulationPPO (one handle and one DockReverseCurriculum per replica).  No shippe
 synthetic stage table (DOCK_STAGES); --no-curriculum measures the plain dock step without a tracker.
 
     python tools/population_bench.py --dock [--no-curriculum] [--ks 1,2,4,8,16] [--out profiles/r07_dock_population_refscale.json]
+
+--eval: the wall time of one gate evaluation of a --seeds run -- n_stages x 24 episodes of workspace_expansion_bigtrain, Approach then
+Finisher (a freshly initialised 2x64 Finisher on dock_workspace_handoff_noop_ft_12env: the reference's checkpoint is not shipped) -- for an
+ApproachPopulationPPO of K replicas after one training iteration, both ways, alternately in one process, --repeats times each: K sequential
+evaluate_workspace_expansion calls through replica(k).predict (per_replica) and one evaluate_workspace_expansion_population (population).
+Also the iteration time at the reference scale, and from both the share of a run's wall time that gate evaluation takes at the shipped
+eval_interval.
+
+    python tools/population_bench.py --eval [--ks 1,8,16] [--repeats 5] [--out profiles/r09_population_eval.json]
 """
 from __future__ import annotations
 
@@ -197,8 +206,86 @@ def measure(K: int, args, build=None) -> dict:
             "aggregate_env_steps_per_s": steps / ((rollout_ms + update_ms) * 1e-3), "env_steps_per_iteration": steps, "kernel_us_in_situ": prof}
 
 
+def main_eval(args) -> None:
+    import statistics
+
+    from rl_brain_trainer_amd import evaluate as ev
+    from rl_brain_trainer_amd.ppo import ActorCritic, InferencePolicy
+
+    args.ks = args.ks or "1,8,16"
+    args.batch = args.batch or 256
+    cfg = kcfg.load_workspace_expansion_config(kcfg.builtin_config_dir() / "workspace_expansion_bigtrain.yaml")
+    ws = cfg.get("workspace_expansion", {})
+    env_cfg = kcfg.to_env_config(cfg)
+    dock = kcfg.load_yaml_file(kcfg.builtin_config_dir() / "dock_workspace_handoff_noop_ft_12env.yaml")
+    dock["env"]["dock_reset"]["handoff_state_probability"] = 0.0      # the reference's handoff buffer file is not shipped
+    fcfg = kcfg.to_env_config(dock)
+    dev = torch.device("cuda", 0)
+    fin = InferencePolicy(ActorCritic(64, dev, seed=1).state_dict(), device=dev)
+    episodes, interval = int(ws.get("gate_eval_episodes", 24)), int(ws.get("eval_interval", 200_000))
+    kw = dict(finisher_policy=fin, approach_cfg=env_cfg, finisher_cfg=fcfg, episodes=episodes, seed=int(ws.get("eval_seed", 700001)),
+              stage_indices=list(range(env_cfg.n_stages)), gate_config=dict(ws.get("gate", {}) or {}), handoff_confirm_steps=args.handoff_confirm_steps)
+
+    def timed(fn) -> float:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    rows = []
+    for K in (int(k) for k in args.ks.split(",")):
+        pop = build_approach_one_handle(K, args.n_envs, args.n_steps, args.batch, args.hidden, True)
+        pop.collect_rollouts()
+        pop.train()      # warm-up: captures both graphs, and the replicas' weights differ
+        iters = [timed(lambda: (pop.collect_rollouts(), pop.train())) for _ in range(args.iters)]
+
+        def per_replica():
+            for k in range(K):
+                ev.evaluate_workspace_expansion(approach_policy=pop.replica(k).predict, obs_stride=pop.obs_w, **kw)
+
+        def population():
+            return ev.evaluate_workspace_expansion_population(population=pop, **kw)
+
+        per_replica()                    # warm-up of both forms
+        # rows that hand over to the Finisher (the Finisher phase steps all rows while any of them is alive)
+        handoffs = sum(bool(r["finisher_ready_dwell"]) for p in population() for r in p["target_rows"])
+        t = {"per_replica": [], "population": []}
+        for _ in range(args.repeats):
+            t["per_replica"].append(timed(per_replica))
+            t["population"].append(timed(population))
+        _close(pop)
+        iteration_ms = statistics.median(iters)
+        # evaluations land on iteration boundaries: one per ceil(eval_interval / steps per iteration) iterations
+        iters_per_eval = -(-interval // (args.n_envs * args.n_steps))
+        row = {"K": K, "episodes": env_cfg.n_stages * episodes, "handoff_confirm_steps": args.handoff_confirm_steps,
+               "handoff_rows_of_all_replicas": handoffs, "iteration_ms": iteration_ms, "iterations_per_evaluation": iters_per_eval}
+        for form, ms in t.items():
+            med = statistics.median(ms)
+            row[form] = {"ms": ms, "median_ms": med, "spread_ms": max(ms) - min(ms),
+                         "share_of_run_wall_time": med / (med + iters_per_eval * iteration_ms)}
+        row["speedup_median"] = row["per_replica"]["median_ms"] / row["population"]["median_ms"]
+        row["faster_by_more_than_per_replica_spread"] = row["per_replica"]["median_ms"] - row["population"]["median_ms"] > row["per_replica"]["spread_ms"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    result = {"workload": f"one gate evaluation of workspace_expansion_bigtrain ({env_cfg.n_stages} stages x {episodes} episodes, Approach + a fresh 2x64 "
+                          f"Finisher on dock_workspace_handoff_noop_ft_12env) of an ApproachPopulationPPO, {args.n_envs} envs x {args.n_steps} steps per "
+                          f"replica, minibatch {args.batch}, 2x{args.hidden}, after one iteration; per_replica = K evaluate_workspace_expansion calls "
+                          f"through replica(k).predict, population = one evaluate_workspace_expansion_population; alternated, {args.repeats} repeats; "
+                          f"handoff_confirm_steps {args.handoff_confirm_steps}; "
+                          f"share_of_run_wall_time = evaluation / (evaluation + iterations_per_evaluation x iteration) at eval_interval {interval}",
+              "device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
+    print(json.dumps({"gate_evaluation_median_ms": {r["K"]: {f: round(r[f]["median_ms"], 1) for f in ("per_replica", "population")} for r in rows}}))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--eval", action="store_true", help="one gate evaluation of a --seeds run: K per-replica evaluations against one population evaluation")
+    ap.add_argument("--repeats", type=int, default=5, help="with --eval: timed repeats of each form")
+    ap.add_argument("--handoff-confirm-steps", type=int, default=2, help="with --eval: the evaluator's handoff_confirm_steps (2, the gate's; 0 hands "
+                    "every episode over at step 1, so the Finisher phase runs over all rows whatever the policy has learnt)")
     ap.add_argument("--route", action="store_true", help="the route reference-scale iteration (RoutePopulationPPO)")
     ap.add_argument("--one-handle", action="store_true", help="the Approach iteration on one env handle (ApproachPopulationPPO)")
     ap.add_argument("--dock", action="store_true", help="the Finisher reference shape, one handle (DockPopulationPPO) and K handles")
@@ -221,12 +308,16 @@ def main() -> None:
         SWEEP[:] = parse_sweep(args.sweep)
     if args.route and args.one_handle:
         ap.error("--one-handle is the Approach form; --route is always one handle")
+    if args.eval and (args.route or args.dock or args.sweep):
+        ap.error("--eval measures the Approach population's gate evaluation")
     if args.dock and (args.route or args.one_handle):
         ap.error("--dock measures the Finisher iteration in both forms")
     args.n_envs = args.n_envs or (12 if args.dock else 16)
     args.n_steps = args.n_steps or (256 if args.dock else 1024)
     if args.dock:
         return main_dock(args)
+    if args.eval:
+        return main_eval(args)
     args.ks = args.ks or ("1,2,4,8,16" if args.route or args.one_handle else "1,2,4,8")
     args.batch = args.batch or (512 if args.route else 256)
     rows = []
