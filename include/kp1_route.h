@@ -186,6 +186,42 @@ int kp1_route_curriculum_observe_population(kp1_route* r, kp1_route_curriculum_s
 int kp1_route_curriculum_read_replica(kp1_route* r, const kp1_route_curriculum_state* st_dev, int32_t replica, kp1_route_curriculum_state* out_host,
                                       void* stream);
 
+/* ---- chained sequential evaluation on the device (eval/eval_route_curriculum.py:57-248, evaluate_sequential_route) ---------------------------
+ * The sequential evaluator runs waypoint after waypoint on one env: the episode of waypoint w + 1 starts from the final (q, dq, prev_action) of
+ * waypoint w.  A chain does that for every row of a route handle at once, with the bookkeeping and the hand-over to the next waypoint in
+ * kp1_route_chain_kernel after each route step, so R chains advance in lock step without a host read.  Rows are replica-major: R = K * C rows,
+ * row r runs the chain start_index[r] .. end_index[r] (the caller feeds row r's observations to replica r / C's policy).
+ * One kp1_route_chain_record per finished waypoint, float planes widened to double (exact).  min_q_error is the minimum over the episode's STEPS;
+ * the evaluator's value also covers the episode's start state, whose joint error the host forms from start_q with the evaluator's own
+ * np.linalg.norm call. */
+typedef struct kp1_route_chain_record {
+  int32_t route_index, success, route_ready_hit, max_ready_streak, first_ready_step /* -1 = none */, steps;
+  double final_position_error, final_orientation_error, final_q_error, min_position_error, min_orientation_error, min_q_error;
+  double final_action_magnitude, final_dq_norm;
+  double final_q[7], final_dq[7], final_prev_action[7];
+  double start_q[7];   /* q as the episode's reset left it (get_state after the reset), written when the episode opens */
+} kp1_route_chain_record;
+typedef struct kp1_route_chain kp1_route_chain;
+/* start_index / end_index: host arrays [n_rows], 1 <= start <= end < n_waypoints; n_rows = the handle's env count.  stop_on_failure != 0: a row
+ * ends at its first waypoint that does not succeed (the teacher recorder).  f32 handles without `sequence`, recorded reward components or an
+ * attached prefix tracker. */
+int kp1_route_chain_create(kp1_route* r, const int32_t* start_index_host, const int32_t* end_index_host, int32_t n_rows, int32_t stop_on_failure,
+                           kp1_route_chain** out);
+int kp1_route_chain_destroy(kp1_route* r, kp1_route_chain* chain);
+/* every row -> waypoint start_index[row] from q = route_q[start - 1], dq = prev_action = 0, start_route_index 0, mode EXPLICIT (kp1_route_reset
+ * with evaluator_state); obs [n_rows][stride] */
+int kp1_route_chain_begin(kp1_route* r, kp1_route_chain* chain, float* obs);
+/* kp1_route_step(auto_reset = 0) then kp1_route_chain_kernel, on the handle's stream.  tags: NULL or [n_rows][2] int32 = {route_index, step
+ * inside the episode} of the step just taken, {-1, -1} for rows whose chain has ended.  A finished row keeps being stepped; nothing of it is read. */
+int kp1_route_chain_step(kp1_route* r, kp1_route_chain* chain, const float* actions, float* obs, float* reward, uint8_t* done, int32_t* tags);
+typedef struct kp1_route_chain_view {  /* device pointers, valid until kp1_route_chain_destroy */
+  const kp1_route_chain_record* records;  /* [n_rows][max_len]; row r holds n_records[r] records, waypoints start_index[r] .. in order */
+  const int32_t* n_records;               /* [n_rows] */
+  const int32_t* n_alive;                 /* rows still running after the last kp1_route_chain_step */
+  int32_t n_rows, max_len;
+} kp1_route_chain_view;
+int kp1_route_chain_get_view(kp1_route_chain* chain, kp1_route_chain_view* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -529,6 +529,7 @@ struct kp1_route {
   int32_t obs_stride = 0;      // row pitch of caller observation buffers (kp1_route_set_obs_stride; default = obs_dim)
   int32_t n_replicas = 1, n_per_replica = 0;   // population handle: K blocks of N envs (a single handle: 1 x N)
   std::vector<int32_t> win;    // host copy of the reset windows [K][2]
+  int32_t n_trackers = 0;      // prefix trackers created on this handle and not yet destroyed (a chain refuses a tracked handle)
   std::vector<void*> allocs;
 };
 
@@ -1180,6 +1181,7 @@ int route_curriculum_alloc(kp1_route* r, const int32_t* prefix_end_index, int32_
   if (e != hipSuccess) { (void)hipFree(d); return fail(KP1_ERR_NO_DEVICE, "hipMemcpy failed in kp1_route_curriculum_create"); }
   const int rc = kp1_route_set_window(r, 1, prefix_end_index[0]);   // _on_training_start -> _apply_stage
   if (rc != KP1_OK) { (void)hipFree(d); return rc; }
+  r->n_trackers += 1;
   *out_dev = d;
   return KP1_OK;
 }
@@ -1192,6 +1194,7 @@ int kp1_route_curriculum_destroy(kp1_route* r, kp1_route_curriculum_state* st_de
   (void)hipSetDevice(r->base->device);
   (void)hipStreamSynchronize(r->base->stream);
   (void)hipFree(st_dev);
+  if (r->n_trackers > 0) r->n_trackers -= 1;
   return KP1_OK;
 }
 
@@ -1260,6 +1263,238 @@ int kp1_route_curriculum_read_replica(kp1_route* r, const kp1_route_curriculum_s
     r->cfg.reset.min_route_index = 1;
     r->cfg.reset.max_route_index = r->win[1];
   }
+  return KP1_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- chained sequential evaluation
+// evaluate_sequential_route (route_curriculum.py, _roll_one) for every row of a handle at once.  After the unchanged route step
+// (auto_reset = 0) kp1_route_chain_kernel, one lane per row, does what the evaluator's host loop does between two steps: the per-episode
+// bookkeeping from the planes the step has just written, and at the end of an episode the record of the waypoint and the explicit-state reset
+// to the next one (route_reset_env from the row's own q / dq / prev_action, read as get_state reads them).  Nothing here draws from a PCG64
+// stream: an explicit-state reset with a goal takes no branch of reset_env that loads one.
+namespace {
+
+struct RouteChainDev {   // device arrays [R] unless noted
+  const int32_t *start, *end;
+  int32_t *wp, *steps, *first_ready, *max_streak, *n_records;
+  uint8_t* alive;
+  float *min_pos, *min_ori, *min_q;
+  kp1_route_chain_record* records;   // [R][max_len]
+  int32_t* n_alive;                  // [1]
+  int max_len, stop_on_failure;
+};
+
+template <typename R>
+struct RouteChainArgs {
+  EnvState<R> st; const DevCfg<R>* cfg; const DevSampler* smp; const RouteDevCfg* rc; RouteTable rt; RouteState<R> rs;
+  RouteChainDev ch; const uint8_t* done; float* obs; int32_t* tags; int obs_dim, obs_stride;
+};
+
+// the bookkeeping of a fresh episode: the minima of position and orientation error start from the planes reset_env wrote, and the record
+// keeps q as the reset left it (the evaluator's initial joint-space error is taken from it on the host)
+template <typename R>
+__device__ __forceinline__ void route_chain_open(const EnvState<R>& st, const RouteChainDev& ch, int64_t i, int waypoint) {
+  ch.wp[i] = waypoint; ch.steps[i] = 0; ch.first_ready[i] = -1; ch.max_streak[i] = 0;
+  ch.min_pos[i] = (float)st.r(F_POS_ERR, i);
+  ch.min_ori[i] = (float)st.r(F_ORI_ERR, i);
+  ch.min_q[i] = std::numeric_limits<float>::infinity();
+  const int slot = waypoint - ch.start[i];
+  if (slot >= 0 && slot < ch.max_len) {
+#pragma unroll
+    for (int k = 0; k < NJ; ++k) ch.records[i * ch.max_len + slot].start_q[k] = st.q_load(k, i);
+  }
+}
+
+template <typename R>
+__global__ void __launch_bounds__(64) kp1_route_chain_begin_kernel(const EnvState<R> st, const RouteChainDev ch) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= st.n) return;
+  route_chain_open<R>(st, ch, i, ch.start[i]);
+  ch.n_records[i] = 0;
+  ch.alive[i] = 1;
+  if (i == 0) *ch.n_alive = (int32_t)st.n;
+}
+
+template <typename R>
+__global__ void __launch_bounds__(64) kp1_route_chain_kernel(const RouteChainArgs<R> a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const EnvState<R>& st = a.st;
+  const RouteChainDev& ch = a.ch;
+  int alive_after = 0;
+  if (i < st.n) {
+    if (!ch.alive[i]) {
+      if (a.tags) { a.tags[2 * i] = -1; a.tags[2 * i + 1] = -1; }
+    } else {
+      // 1. the step just taken (_roll_one's loop body)
+      const int waypoint = ch.wp[i];
+      const int steps = ch.steps[i] + 1;
+      const float pos = (float)st.r(F_POS_ERR, i), ori = (float)st.r(F_ORI_ERR, i), qerr = (float)a.rs.q_error[i];
+      const float min_pos = fminf(ch.min_pos[i], pos), min_ori = fminf(ch.min_ori[i], ori), min_q = fminf(ch.min_q[i], qerr);
+      int first_ready = ch.first_ready[i];
+      if (a.rs.ready[i] != 0 && first_ready < 0) first_ready = steps;
+      const int streak = a.rs.streak[i];
+      const int max_streak = ch.max_streak[i] > streak ? ch.max_streak[i] : streak;
+      if (a.tags) { a.tags[2 * i] = waypoint; a.tags[2 * i + 1] = steps - 1; }
+      const uint8_t d = a.done[i];
+      alive_after = 1;
+      if (!(d & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED))) {
+        ch.steps[i] = steps; ch.first_ready[i] = first_ready; ch.max_streak[i] = max_streak;
+        ch.min_pos[i] = min_pos; ch.min_ori[i] = min_ori; ch.min_q[i] = min_q;
+      } else {
+        // 2. the waypoint's record, then the hand-over
+        const bool success = (d & KP1_DONE_SUCCESS) != 0;
+        double q0[NJ], dq0[NJ], pa0[NJ];
+#pragma unroll
+        for (int k = 0; k < NJ; ++k) {
+          q0[k] = st.q_load(k, i);
+          dq0[k] = (double)st.r(F_DQ + k, i);
+          pa0[k] = (double)st.r(F_PREV_ACTION + k, i);
+        }
+        const int slot = waypoint - ch.start[i];
+        if (slot >= 0 && slot < ch.max_len) {
+          kp1_route_chain_record& rec = ch.records[i * ch.max_len + slot];
+          rec.route_index = waypoint; rec.success = success ? 1 : 0; rec.route_ready_hit = first_ready >= 0 ? 1 : 0;
+          rec.max_ready_streak = max_streak; rec.first_ready_step = first_ready; rec.steps = steps;
+          rec.final_position_error = (double)pos; rec.final_orientation_error = (double)ori; rec.final_q_error = (double)qerr;
+          rec.min_position_error = (double)min_pos; rec.min_orientation_error = (double)min_ori; rec.min_q_error = (double)min_q;
+          rec.final_action_magnitude = (double)st.r(F_ACTION_L2, i); rec.final_dq_norm = (double)st.r(F_EXEC_DQ, i);
+#pragma unroll
+          for (int k = 0; k < NJ; ++k) { rec.final_q[k] = q0[k]; rec.final_dq[k] = dq0[k]; rec.final_prev_action[k] = pa0[k]; }
+          ch.n_records[i] = slot + 1;
+        }
+        if (waypoint >= ch.end[i] || (ch.stop_on_failure && !success)) {
+          ch.alive[i] = 0;
+          alive_after = 0;
+        } else {
+          int win_min, win_max;
+          route_window_of(*a.rc, i, win_min, win_max);
+          route_reset_env<R>(st, *a.cfg, *a.smp, *a.rc, a.rt, a.rs, i, waypoint + 1, 0, KP1_ROUTE_MODE_EXPLICIT, q0, dq0, pa0, a.obs, a.obs_dim,
+                             a.obs_stride, win_max);
+          route_chain_open<R>(st, ch, i, waypoint + 1);
+        }
+      }
+    }
+  }
+  const unsigned long long bal = __ballot(alive_after != 0);
+  if (threadIdx.x == 0 && bal) atomicAdd(ch.n_alive, __popcll(bal));
+}
+
+}  // namespace
+
+struct kp1_route_chain {
+  RouteChainDev d{};
+  int32_t n_rows = 0;
+  double* init_q = nullptr;    // [R][7] route_q[max(start - 1, 0)]
+  int32_t* zeros = nullptr;    // [R] start_route_index = 0
+  std::vector<void*> allocs;
+};
+
+namespace {
+// what a chain cannot run on; text for kp1_last_error, or nullptr
+const char* route_chain_refusal(const kp1_route* r) {
+  if (r->base->real_type != KP1_REAL_F32) return "a route chain drives an f32 base env (the f64 handle keeps the host evaluator)";
+  if (r->cfg.sequence_enabled) return "a route chain runs the single-waypoint wrapper: the handle has route.sequence enabled";
+  if (r->comps_enabled) return "a route chain does not record reward components (kp1_route_enable_reward_components is on)";
+  if (r->n_trackers > 0) return "a route chain cannot run on a handle with a prefix curriculum tracker attached";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+int kp1_route_chain_create(kp1_route* r, const int32_t* start_host, const int32_t* end_host, int32_t n_rows, int32_t stop_on_failure,
+                           kp1_route_chain** out) {
+  if (!r || !start_host || !end_host || !out) return fail(KP1_ERR_INVALID, "NULL argument to kp1_route_chain_create");
+  if (const char* why = route_chain_refusal(r)) return fail(KP1_ERR_UNSUPPORTED, why);
+  if ((int64_t)n_rows != r->base->n) return fail(KP1_ERR_INVALID, "kp1_route_chain_create: n_rows must equal the handle's env count");
+  int max_len = 0;
+  for (int32_t i = 0; i < n_rows; ++i) {
+    if (start_host[i] < 1) return fail(KP1_ERR_INVALID, "kp1_route_chain_create: start_index < 1");
+    if (end_host[i] < start_host[i]) return fail(KP1_ERR_INVALID, "kp1_route_chain_create: end_index < start_index");
+    if (end_host[i] >= r->n_waypoints) return fail(KP1_ERR_INVALID, "kp1_route_chain_create: end_index >= n_waypoints");
+    max_len = std::max(max_len, (int)(end_host[i] - start_host[i] + 1));
+  }
+  HIP_TRY(hipSetDevice(r->base->device));
+  kp1_route_chain* c = new kp1_route_chain();
+  c->n_rows = n_rows;
+  const size_t n = (size_t)n_rows;
+  int rc = KP1_OK;
+  auto alloc = [&](void** p, size_t bytes) {
+    if (rc != KP1_OK) return;
+    if (hipMalloc(p, bytes) != hipSuccess) { rc = fail(KP1_ERR_ALLOC, "hipMalloc failed in kp1_route_chain_create"); return; }
+    c->allocs.push_back(*p);
+    if (hipMemset(*p, 0, bytes) != hipSuccess) rc = fail(KP1_ERR_NO_DEVICE, "hipMemset failed");
+  };
+  int32_t* ints = nullptr;     // start, end, wp, steps, first_ready, max_streak, n_records, zeros, n_alive
+  float* mins = nullptr;
+  alloc((void**)&ints, sizeof(int32_t) * (8 * n + 1));
+  alloc((void**)&mins, sizeof(float) * 3 * n);
+  alloc((void**)&c->d.alive, n);
+  alloc((void**)&c->d.records, sizeof(kp1_route_chain_record) * n * (size_t)max_len);
+  alloc((void**)&c->init_q, sizeof(double) * NJ * n);
+  if (rc != KP1_OK) { kp1_route_chain_destroy(r, c); return rc; }
+  c->d.start = ints; c->d.end = ints + n; c->d.wp = ints + 2 * n; c->d.steps = ints + 3 * n; c->d.first_ready = ints + 4 * n;
+  c->d.max_streak = ints + 5 * n; c->d.n_records = ints + 6 * n; c->zeros = ints + 7 * n; c->d.n_alive = ints + 8 * n;
+  c->d.min_pos = mins; c->d.min_ori = mins + n; c->d.min_q = mins + 2 * n;
+  c->d.max_len = max_len; c->d.stop_on_failure = stop_on_failure != 0;
+  std::vector<double> q0(NJ * n);
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < NJ; ++k) q0[i * NJ + k] = r->h_q[(size_t)(start_host[i] - 1) * NJ + k];
+  if (hipMemcpy(ints, start_host, sizeof(int32_t) * n, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(ints + n, end_host, sizeof(int32_t) * n, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(c->init_q, q0.data(), sizeof(double) * NJ * n, hipMemcpyHostToDevice) != hipSuccess) {
+    kp1_route_chain_destroy(r, c);
+    return fail(KP1_ERR_NO_DEVICE, "hipMemcpy failed in kp1_route_chain_create");
+  }
+  *out = c;
+  return KP1_OK;
+}
+
+int kp1_route_chain_destroy(kp1_route* r, kp1_route_chain* c) {
+  if (!c) return KP1_OK;
+  if (r && r->base) { (void)hipSetDevice(r->base->device); (void)hipStreamSynchronize(r->base->stream); }
+  for (void* p : c->allocs) (void)hipFree(p);
+  delete c;
+  return KP1_OK;
+}
+
+int kp1_route_chain_begin(kp1_route* r, kp1_route_chain* c, float* obs) {
+  if (!r || !c || !obs) return fail(KP1_ERR_INVALID, "NULL argument to kp1_route_chain_begin");
+  if (const char* why = route_chain_refusal(r)) return fail(KP1_ERR_UNSUPPORTED, why);
+  if ((int64_t)c->n_rows != r->base->n) return fail(KP1_ERR_INVALID, "kp1_route_chain_begin: the chain was created for another env count");
+  kp1_env* e = r->base;
+  HIP_TRY(hipSetDevice(e->device));
+  const int rc = route_launch_reset<float>(r, nullptr, c->d.start, c->zeros, c->init_q, nullptr, nullptr, 1, obs);
+  if (rc != KP1_OK) return rc;
+  hipLaunchKernelGGL(kp1_route_chain_begin_kernel<float>, dim3((unsigned)((e->n + 63) / 64)), dim3(64), 0, e->stream, state_of<float>(e), c->d);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_route_chain_step(kp1_route* r, kp1_route_chain* c, const float* actions, float* obs, float* reward, uint8_t* done, int32_t* tags) {
+  if (!r || !c || !actions || !obs || !reward || !done) return fail(KP1_ERR_INVALID, "NULL argument to kp1_route_chain_step");
+  if (const char* why = route_chain_refusal(r)) return fail(KP1_ERR_UNSUPPORTED, why);
+  if ((int64_t)c->n_rows != r->base->n) return fail(KP1_ERR_INVALID, "kp1_route_chain_step: the chain was created for another env count");
+  kp1_env* e = r->base;
+  HIP_TRY(hipSetDevice(e->device));
+  const int rc = route_launch_step<float>(r, actions, obs, reward, done, nullptr, 0);
+  if (rc != KP1_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->d.n_alive, 0, sizeof(int32_t), e->stream));
+  RouteChainArgs<float> a;
+  a.st = state_of<float>(e); a.cfg = (const DevCfg<float>*)e->dev_cfg; a.smp = e->dev_smp; a.rc = r->dev_cfg; a.rt = route_table_of(r);
+  a.rs = route_state_of<float>(r); a.ch = c->d; a.done = done; a.obs = obs; a.tags = tags;
+  a.obs_dim = r->cfg.include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM; a.obs_stride = r->obs_stride;
+  hipLaunchKernelGGL(kp1_route_chain_kernel<float>, dim3((unsigned)((e->n + 63) / 64)), dim3(64), 0, e->stream, a);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_route_chain_get_view(kp1_route_chain* c, kp1_route_chain_view* out) {
+  if (!c || !out) return fail(KP1_ERR_INVALID, "NULL argument to kp1_route_chain_get_view");
+  out->records = c->d.records; out->n_records = c->d.n_records; out->n_alive = c->d.n_alive;
+  out->n_rows = c->n_rows; out->max_len = c->d.max_len;
   return KP1_OK;
 }
 

@@ -26,6 +26,11 @@ class EvalBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("metrics", "counters", "flags", "state", "hand_metrics", "hand_step", "hand_success", "hand_state", "n_alive")]
 
 
+class RouteChainView(C.Structure):
+    """include/kp1_route.h kp1_route_chain_view: device pointers of a chain's record table and counters"""
+    _fields_ = [("records", C.c_void_p), ("n_records", C.c_void_p), ("n_alive", C.c_void_p), ("n_rows", C.c_int32), ("max_len", C.c_int32)]
+
+
 class Kp1Error(RuntimeError):
     pass
 
@@ -112,6 +117,11 @@ def load() -> C.CDLL:
     L.kp1_bind_population_stages.argtypes = [vp, vp, i32]
     L.kp1_seed_blocks.argtypes = [vp, vp, i32, i32]
     L.kp1_set_obs_stride.argtypes = [vp, i32]
+    L.kp1_route_chain_create.argtypes = [vp, vp, vp, i32, i32, C.POINTER(vp)]
+    L.kp1_route_chain_destroy.argtypes = [vp, vp]
+    L.kp1_route_chain_begin.argtypes = [vp, vp, vp]
+    L.kp1_route_chain_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.kp1_route_chain_get_view.argtypes = [vp, C.POINTER(RouteChainView)]
     if L.kp1_config_size() != C.sizeof(kcfg.Kp1Config):
         raise Kp1Error(f"kp1_config layout mismatch: library {L.kp1_config_size()} vs binding {C.sizeof(kcfg.Kp1Config)}")
     _lib = L

@@ -395,9 +395,19 @@ def evaluate_sequential_route(*, policy: PolicyFn | Callable[[RouteVecEnv], Poli
         cq, cdq, cpa = row["final_q"], row["final_dq"], row["final_prev_action"]
     progress = env.route_progress_m.copy()
     env.close()
-    summary = summarize_rows(rows, progress)
+    return sequential_result(rows, progress, start_index=int(start_index), end_index=int(final_end), final_q=cq, artifact_root=artifact_root)
+
+
+_SEQUENTIAL_EXTRA = ("rows", "chunk_metrics", "final_q")
+
+
+def sequential_result(rows: list[dict[str, Any]], route_progress_m: np.ndarray, *, start_index: int, end_index: int, final_q,
+                      artifact_root: str | Path | None = None) -> dict[str, Any]:
+    """what evaluate_sequential_route returns for the per-waypoint ``rows`` of one chain, and its four files under ``artifact_root``
+    (summary, chunk metrics, the per-waypoint jsonl and the failure report)"""
+    summary = summarize_rows(rows, route_progress_m)
     summary.update({"schema_version": "v5.route_curriculum.sequential_eval.v1", "mode": "sequential_actual_final_q_to_next_dense_q_goal",
-                    "start_index": int(start_index), "end_index": int(final_end)})
+                    "start_index": int(start_index), "end_index": int(end_index)})
     if artifact_root is not None:
         root = Path(artifact_root)
         root.mkdir(parents=True, exist_ok=True)
@@ -409,7 +419,146 @@ def evaluate_sequential_route(*, policy: PolicyFn | Callable[[RouteVecEnv], Poli
         failure = next((row for row in rows if not row["success"]), None)
         (root / "route_failure_report.json").write_text(json.dumps({"first_failure_index": summary["first_failure_index"],
                                                                     "first_failure_reason": summary["first_failure_reason"], "first_failure": failure}, indent=2))
-    return {**summary, "rows": rows, "chunk_metrics": chunk_metrics(rows), "final_q": np.asarray(cq).tolist()}
+    return {**summary, "rows": rows, "chunk_metrics": chunk_metrics(rows), "final_q": np.asarray(final_q).tolist()}
+
+
+# --------------------------------------------------------------------------------------------- chained evaluation of many rows at once
+_ALIVE_CHECK_EVERY = 32     # lock steps between two reads of the device's alive counter (the only host synchronisation of the loop)
+
+
+def rows_from_chain_records(records: np.ndarray, route_q: np.ndarray, success_dwell_steps: int) -> list[dict[str, Any]]:
+    """the evaluator's per-waypoint rows (_roll_one's keys and order) from one row's chain records (route_env.CHAIN_RECORD).  The device
+    keeps the minimum joint error over the episode's steps; the start state's error is formed here from the record's ``start_q`` with
+    _roll_one's own 1-D ``np.linalg.norm`` call, so the field is the same double."""
+    W = int(route_q.shape[0])
+    rows = []
+    for rec in records:
+        idx = int(rec["route_index"])
+        first = int(rec["first_ready_step"])
+        start_err = float(np.linalg.norm(route_q[min(max(idx, 0), W - 1)] - rec["start_q"]))
+        streak = int(rec["max_ready_streak"])
+        rows.append({
+            "route_index": idx, "success": bool(rec["success"]), "route_ready_hit": bool(rec["route_ready_hit"]),
+            "route_ready_dwell": bool(streak >= success_dwell_steps), "first_ready_step": first if first >= 0 else None, "max_ready_streak": streak,
+            "steps": int(rec["steps"]), "final_position_error": float(rec["final_position_error"]),
+            "final_orientation_error": float(rec["final_orientation_error"]), "final_q_error": float(rec["final_q_error"]),
+            "min_position_error": float(rec["min_position_error"]), "min_orientation_error": float(rec["min_orientation_error"]),
+            "min_q_error": min(start_err, float(rec["min_q_error"])), "final_action_magnitude": float(rec["final_action_magnitude"]),
+            "final_dq_norm": float(rec["final_dq_norm"])})
+    return rows
+
+
+def check_chain_request(*, replicas: int, n_waypoints: int, start_index, end_indices, rows_per_replica: int) -> tuple[np.ndarray, np.ndarray]:
+    """the host-side refusals of evaluate_sequential_route_batch, before any device work; returns (start, end) per row"""
+    C_ = int(rows_per_replica)
+    if C_ < 1:
+        raise ValueError("rows_per_replica must be positive")
+    end = np.asarray(end_indices, dtype=np.int64).reshape(-1)
+    if end.size != int(replicas) * C_:
+        raise ValueError(f"end_indices holds {end.size} chains for a policy handle of {int(replicas)} replicas x {C_} rows per replica "
+                         f"(expected {int(replicas) * C_}, replica-major)")
+    start = np.broadcast_to(np.asarray(start_index, dtype=np.int64), end.shape)
+    if (start < 1).any():
+        raise ValueError("start_index must be at least 1 (waypoint 0 is where the route starts)")
+    if (end < start).any() or (end >= int(n_waypoints)).any():
+        raise ValueError(f"end index out of range: every chain needs start_index <= end_index <= {int(n_waypoints) - 1} (got {end.tolist()})")
+    return start.astype(np.int32), end.astype(np.int32)
+
+
+def evaluate_sequential_route_batch(*, mlp, cfg: dict[str, Any], route_q: np.ndarray, start_index=1, end_indices: Sequence[int],
+                                    rows_per_replica: int = 1, device: int | torch.device = 0, artifact_roots: Sequence[str | Path | None] | None = None,
+                                    **single_only: Any) -> list[dict[str, Any]]:
+    """evaluate_sequential_route for K * C chains in lock step: ``mlp`` is a kp1_mlp wrapper (mlp.MlpKernels) of K replicas whose packed
+    weights are the policies under test; row r = k C + c runs waypoints ``start_index .. end_indices[r]`` under replica k's policy.  One f32
+    route handle of K C envs with ``sequence`` forced off; per lock step one policy forward over all rows and one kp1_route_chain_step, and
+    the alive counter is read every _ALIVE_CHECK_EVERY steps.  Returns, per row, what evaluate_sequential_route returns, plus ``final_qs``
+    (the final q of every waypoint, for sliced_evaluate) and ``lock_steps``."""
+    if single_only:
+        raise TypeError(f"evaluate_sequential_route_batch takes packed policy handles and per-row end indices; {sorted(single_only)} belong to "
+                        "evaluate_sequential_route (one policy callable, one chain)")
+    route_q = np.ascontiguousarray(route_q, dtype=np.float64)
+    W = int(route_q.shape[0])
+    K, C_ = int(mlp.replicas), int(rows_per_replica)
+    start, end = check_chain_request(replicas=K, n_waypoints=W, start_index=start_index, end_indices=end_indices, rows_per_replica=C_)
+    R = K * C_
+    if artifact_roots is not None and len(artifact_roots) != R:
+        raise ValueError(f"{len(artifact_roots)} artifact roots for {R} chains")
+    if C_ > int(mlp.max_batch):
+        raise ValueError(f"rows_per_replica {C_} exceeds the policy handle's max_batch {int(mlp.max_batch)}")
+    seq_off = {**cfg, "route": {**(cfg.get("route", {}) or {}), "sequence": {**((cfg.get("route", {}) or {}).get("sequence", {}) or {}), "enabled": False}}}
+    rc = rcfg.route_config_from_dict(seq_off, max_route_index=int(end.max()))
+    obs_dim = rcfg.ROUTE_OBS_DIM if rc.include_route_keys else kcfg.OBS_DIM
+    if int(mlp.obs_dim) != obs_dim:
+        raise ValueError(f"the policy handle reads {int(mlp.obs_dim)}-float observations, the route config produces {obs_dim}")
+    from . import native
+
+    base = kcfg.to_env_config(cfg)
+    env = RouteVecEnv(base, rc, route_q, R, device=device, seed=0, real="f32")
+    chain = None
+    try:
+        # every row's two PCG64 streams start as the single evaluator's env does (default_rng(0), env 0); nothing in a chain draws from them
+        words = np.repeat(env.rng_state()[:1], R, axis=0)
+        env.set_rng_state(words)
+        env.base.set_rng_state(np.repeat(env.base.rng_state()[:1], R, axis=0))
+        env.use_current_stream()
+        pitch = int(mlp.obs_pad)
+        env.set_obs_stride(pitch)
+        dev = env.device
+        obs = torch.zeros((R, pitch), dtype=torch.float32, device=dev)
+        act = torch.zeros((R, kcfg.NJ), dtype=torch.float32, device=dev)
+        reward = torch.zeros(R, dtype=torch.float32, device=dev)
+        done = torch.zeros(R, dtype=torch.uint8, device=dev)
+        chain = env.chain(start, end)
+        max_steps = max(int(base.c.termination.max_episode_steps), 1)
+        bound = int((end - start + 1).max()) * max_steps
+        chain.begin(obs)
+        steps = 0
+        while steps < bound:
+            mlp.forward(obs, clipped=act)
+            chain.step(act, obs, reward, done)
+            steps += 1
+            if steps % _ALIVE_CHECK_EVERY == 0 and chain.alive() == 0:
+                break
+        records = chain.records()
+        progress = env.route_progress_m.copy()
+    finally:
+        if chain is not None:
+            chain.close()
+        env.close()
+    dwell = int(base.c.termination.success_dwell_steps)
+    out = []
+    for r in range(R):
+        rows = rows_from_chain_records(records[r], route_q, dwell)
+        if len(rows) != int(end[r]) - int(start[r]) + 1:
+            raise native.Kp1Error(f"chain {r} finished {len(rows)} of {int(end[r]) - int(start[r]) + 1} waypoints inside the step bound")
+        result = sequential_result(rows, progress, start_index=int(start[r]), end_index=int(end[r]), final_q=records[r][-1]["final_q"],
+                                   artifact_root=None if artifact_roots is None else artifact_roots[r])
+        result["final_qs"] = [rec["final_q"].tolist() for rec in records[r]]     # per waypoint: what a sliced evaluation reports as final_q
+        result["lock_steps"] = steps
+        out.append(result)
+    return out
+
+
+def sliced_evaluate(rows: list[dict[str, Any]], final_qs: Sequence[Any], route_progress_m: np.ndarray, *, chain_start: int = 1
+                    ) -> Callable[..., dict[str, Any]]:
+    """the ``evaluate(artifact_root=, start_index=, end_index=)`` callable of _write_run_artifacts / evaluate_route_gate bound to ONE chain's
+    rows: with ``sequence`` off an explicit reset never reads the reset window, so the evaluation to ``end_index`` is the first
+    ``end_index - start + 1`` rows of the evaluation to any larger index (tests/test_route_chain_gpu.py proves the prefix property).
+    ``final_qs[j]``: the final q of row j."""
+    last = len(route_progress_m) - 1
+
+    def evaluate(*, artifact_root: str | Path | None, start_index: int, end_index: int | None) -> dict[str, Any]:
+        if int(start_index) != int(chain_start):
+            raise ValueError(f"the chain started at waypoint {chain_start}; an evaluation from {start_index} is not a slice of it")
+        end_index = min(int(end_index or last), last)     # evaluate_sequential_route's clamp
+        count = int(end_index) - int(chain_start) + 1
+        if not 1 <= count <= len(rows):
+            raise ValueError(f"end_index {end_index} lies outside the chain ({chain_start} .. {chain_start + len(rows) - 1})")
+        out = sequential_result(rows[:count], route_progress_m, start_index=int(start_index), end_index=int(end_index), final_q=final_qs[count - 1],
+                                artifact_root=artifact_root)
+        return {k: v for k, v in out.items() if k not in _SEQUENTIAL_EXTRA}
+
+    return evaluate
 
 
 # --------------------------------------------------------------------------------------------- sequential gate

@@ -32,6 +32,14 @@ class _RouteInfoView(C.Structure):
                                           "nearest_route_q_distance")]
 
 
+# include/kp1_route.h kp1_route_chain_record
+CHAIN_RECORD = np.dtype([(n, "<i4") for n in ("route_index", "success", "route_ready_hit", "max_ready_streak", "first_ready_step", "steps")] +
+                        [(n, "<f8") for n in ("final_position_error", "final_orientation_error", "final_q_error", "min_position_error",
+                                              "min_orientation_error", "min_q_error", "final_action_magnitude", "final_dq_norm")] +
+                        [(n, "<f8", (kcfg.NJ,)) for n in ("final_q", "final_dq", "final_prev_action", "start_q")])
+assert CHAIN_RECORD.itemsize == 312
+
+
 def _bind(L) -> None:
     if getattr(L, "_kp1_route_bound", False):
         return
@@ -237,8 +245,68 @@ class RouteVecEnv:
         native.check(self.L.kp1_route_rng_get(self._handle, C.cast(arr, C.c_void_p)))
         return np.array([[s.state_hi, s.state_lo, s.inc_hi, s.inc_lo, s.has_uint32, s.uinteger] for s in arr], dtype=np.uint64)
 
+    def set_rng_state(self, words: np.ndarray) -> None:
+        """the wrapper's PCG64 streams <- [N, 6] words in rng_state()'s layout"""
+        arr = (kcfg.RngState * self.n_envs)()
+        for i in range(self.n_envs):
+            (arr[i].state_hi, arr[i].state_lo, arr[i].inc_hi, arr[i].inc_lo) = (int(w) for w in words[i][:4])
+            arr[i].has_uint32, arr[i].uinteger = int(words[i][4]), int(words[i][5])
+        native.check(self.L.kp1_route_rng_set(self._handle, C.cast(arr, C.c_void_p)))
+
     def get_state(self) -> dict[str, np.ndarray]:
         return self.base.get_state()
+
+    def chain(self, start_index, end_index, *, stop_on_failure: bool = False) -> "RouteChain":
+        """a chained sequential evaluation over every env of this handle (RouteChain); indices are ints or one per env"""
+        return RouteChain(self, start_index, end_index, stop_on_failure=stop_on_failure)
+
+
+class RouteChain:
+    """Chain state of a route handle (include/kp1_route.h, kp1_route_chain_*): row r runs the sequential evaluation of the waypoints
+    ``start_index[r] .. end_index[r]``, each episode starting from the previous one's final (q, dq, prev_action).  ``begin`` resets every row to
+    its first waypoint; ``step`` is one route step of all rows plus kp1_route_chain_kernel (bookkeeping, records, hand-over), with no host read.
+    ``alive()`` reads the device counter of running rows; ``records()`` the finished waypoints of every row."""
+
+    def __init__(self, env: RouteVecEnv, start_index, end_index, *, stop_on_failure: bool = False) -> None:
+        n = env.n_envs
+        self.env = env
+        self.start = np.ascontiguousarray(np.broadcast_to(np.asarray(start_index, dtype=np.int32), (n,)))
+        self.end = np.ascontiguousarray(np.broadcast_to(np.asarray(end_index, dtype=np.int32), (n,)))
+        self.stop_on_failure = bool(stop_on_failure)
+        self._h = C.c_void_p()
+        with torch.cuda.device(env.device):
+            native.check(env.L.kp1_route_chain_create(env._handle, C.c_void_p(self.start.ctypes.data), C.c_void_p(self.end.ctypes.data), n,
+                                                      int(self.stop_on_failure), C.byref(self._h)))
+        v = native.RouteChainView()
+        native.check(env.L.kp1_route_chain_get_view(self._h, C.byref(v)))
+        self.max_len = int(v.max_len)
+        self._records = _view(v.records, (n * self.max_len * CHAIN_RECORD.itemsize,), "|u1", env.device)
+        self._n_records = _view(v.n_records, (n,), "<i4", env.device)
+        self._n_alive = _view(v.n_alive, (1,), "<i4", env.device)
+
+    def begin(self, obs: torch.Tensor) -> None:
+        native.check(self.env.L.kp1_route_chain_begin(self.env._handle, self._h, C.c_void_p(obs.data_ptr())))
+
+    def step(self, actions: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, tags: torch.Tensor | None = None) -> None:
+        """actions [R, 7] f32 (read), obs [R, stride] (next observations), reward [R], done [R] uint8, tags [R, 2] int32 or None"""
+        native.check(self.env.L.kp1_route_chain_step(self.env._handle, self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
+                                                     C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()),
+                                                     C.c_void_p(tags.data_ptr()) if tags is not None else None))
+
+    def alive(self) -> int:
+        """rows still running after the last step (synchronises)"""
+        return int(self._n_alive.item())
+
+    def records(self) -> list[np.ndarray]:
+        """per row, the CHAIN_RECORD array of its finished waypoints in route order (synchronises)"""
+        counts = self._n_records.cpu().numpy()
+        table = np.frombuffer(self._records.cpu().numpy().tobytes(), dtype=CHAIN_RECORD).reshape(self.env.n_envs, self.max_len)
+        return [table[r, :int(counts[r])].copy() for r in range(self.env.n_envs)]
+
+    def close(self) -> None:
+        if self._h.value:
+            self.env.L.kp1_route_chain_destroy(self.env._handle, self._h)
+            self._h = C.c_void_p()
 
 
 class RoutePopulationVecEnv(RouteVecEnv):

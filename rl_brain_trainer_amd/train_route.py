@@ -36,7 +36,8 @@ from . import checkpoint
 from . import config as kcfg
 from . import route_config as rcfg
 from .ppo import PPO, Dist, PPOConfig
-from .route_curriculum import RoutePrefixCurriculumDevice, evaluate_route_gate, evaluate_sequential_route
+from .route_curriculum import (RoutePrefixCurriculumDevice, evaluate_route_gate, evaluate_sequential_route, evaluate_sequential_route_batch,
+                               sliced_evaluate)
 from .route_env import RouteVecEnv
 from .teacher_anchor import RouteTeacherAnchor, TeacherAnchorConfig
 
@@ -70,6 +71,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--device", type=int, default=0, help="GPU of a single-process run (under torchrun: LOCAL_RANK)")
     p.add_argument("--log-every", type=int, default=0)
+    p.add_argument("--per-replica-eval", action="store_true", help="with --seeds: run the final sequential evaluations and gates one replica and "
+                   "one prefix after another on the host-driven evaluator, instead of one device chain per replica in lock step")
     return p
 
 
@@ -238,9 +241,21 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
         wall = time.time() - t0
         rate = (pop.num_timesteps - start_steps) / max(wall, 1e-9)     # env steps of one replica per second of the population's training loop
         rows = []
-        for k, s in enumerate(seeds):   # the sequential evaluations and gates run one seed after another, as single runs do
+        curriculum_summaries = [curriculum.summary(k) for k in range(pop.K)]
+        evaluators: list[Any] = [None] * pop.K
+        batch_share = 0.0
+        if not args.per_replica_eval:
+            # ONE chain per replica to the largest index any of its evaluations asks for; every evaluation of the replica (the reached prefix,
+            # the gate's prefixes, the full route) is then a slice of that chain's rows
+            t_batch = time.time()
+            ends = [_chain_end_index(route_cfg, cs, W) for cs in curriculum_summaries]
+            chains = evaluate_sequential_route_batch(mlp=pop._mlp, cfg=cfg, route_q=route_q, start_index=1, end_indices=ends, device=device)
+            evaluators = [sliced_evaluate(c["rows"], c["final_qs"], env.route_progress_m) for c in chains]
+            batch_share = (time.time() - t_batch) / pop.K
+        for k, s in enumerate(seeds):   # the artefacts and the gate verdicts are written one seed after another, as single runs write them
             summary = _write_run_artifacts(args, cfg, route_cfg, route_path, route_q, env_cfg, init_checkpoint, roots[k], pop.replica(k),
-                                           curriculum.summary(k), {"enabled": False}, n_envs, 1, wall, rate, device)
+                                           curriculum_summaries[k], {"enabled": False}, n_envs, 1, wall, rate, device, evaluate=evaluators[k],
+                                           evaluation_wall_offset=batch_share)
             ev, gate = summary["route_eval_sequential_summary"], summary["route_gate_summary"]
             accepted = bool(gate.get("accepted", False))
             score = [int(accepted), int(ev.get("longest_success_prefix", 0) or 0), float(ev.get("success_rate", 0.0) or 0.0)]
@@ -261,11 +276,30 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
         env.close()
 
 
+def _gate_config(route_cfg: dict[str, Any]) -> dict[str, Any]:
+    return route_cfg.get("sequential_gate", {}) or {}
+
+
+def _chain_end_index(route_cfg: dict[str, Any], curriculum_summary: dict[str, Any], n_waypoints: int) -> int:
+    """the largest end index _write_run_artifacts evaluates for one replica: the reached prefix and, with the gate on, its prefixes and the
+    full route (every index clamped to the route as evaluate_sequential_route clamps it)"""
+    last = n_waypoints - 1
+    ends = [min(int(curriculum_summary["prefix_end_index"]), last)]
+    gate_cfg = _gate_config(route_cfg)
+    if bool(gate_cfg.get("enabled", False)):
+        ends += [min(int(x) or last, last) for x in gate_cfg.get("prefixes", [20, 40, 80, 120, 180])]
+        if gate_cfg.get("full_end_index") is not None:
+            ends.append(min(int(gate_cfg["full_end_index"]) or last, last))
+    return max(ends)
+
+
 def _write_run_artifacts(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route_path: Path, route_q, env_cfg, init_checkpoint, root: Path, ppo,
                          curriculum_summary: dict[str, Any], anchor_summary: dict[str, Any], n_envs_total: int, world: int, wall: float, rate: float,
-                         device: int) -> dict[str, Any]:
+                         device: int, evaluate=None, evaluation_wall_offset: float = 0.0) -> dict[str, Any]:
     """What a run leaves under `root` once training ends: model_latest.zip, curriculum_history.json, the sequential evaluation of the
-    reached prefix, the gate (and model_sequential_gate_accepted.zip) and training_summary.json.  `ppo` is a PPO or a population replica."""
+    reached prefix, the gate (and model_sequential_gate_accepted.zip) and training_summary.json.  `ppo` is a PPO or a population replica.
+    ``evaluate``: a ready ``evaluate(artifact_root=, start_index=, end_index=)`` (the population's sliced chain) in place of the host-driven
+    evaluator on ``ppo.predict``; ``evaluation_wall_offset``: this replica's share of the wall time that callable's chain took."""
     W = int(route_q.shape[0])
     latest = root / "model_latest"
     checkpoint.save(latest, ppo, env_cfg)
@@ -274,16 +308,18 @@ def _write_run_artifacts(args, cfg: dict[str, Any], route_cfg: dict[str, Any], r
     def policy(obs: torch.Tensor) -> torch.Tensor:
         return ppo.predict(obs.float().contiguous(), deterministic=True)
 
-    def evaluate(*, artifact_root: Path, start_index: int, end_index: int) -> dict[str, Any]:
+    def evaluate_on_host(*, artifact_root: Path, start_index: int, end_index: int) -> dict[str, Any]:
         out = evaluate_sequential_route(policy=policy, cfg=cfg, route_q=route_q, artifact_root=artifact_root, start_index=start_index, end_index=end_index,
                                         device=device)
         return {k: v for k, v in out.items() if k not in ("rows", "chunk_metrics", "final_q")}
+
+    evaluate = evaluate or evaluate_on_host
 
     eval_end = min(int(curriculum_summary["prefix_end_index"]), W - 1)
     t_eval = time.time()
     eval_summary = evaluate(artifact_root=root / "route_eval_sequential", start_index=1, end_index=eval_end)
     gate_summary: dict[str, Any] = {"enabled": False}
-    gate_cfg = route_cfg.get("sequential_gate", {}) or {}
+    gate_cfg = _gate_config(route_cfg)
     if bool(gate_cfg.get("enabled", False)):
         gate_summary = evaluate_route_gate(evaluate=evaluate, artifact_root=root / "route_gate", prefixes=[int(x) for x in gate_cfg.get("prefixes", [20, 40, 80, 120, 180])],
                                            full_end_index=gate_cfg.get("full_end_index"),
@@ -306,7 +342,8 @@ def _write_run_artifacts(args, cfg: dict[str, Any], route_cfg: dict[str, Any], r
         "num_timesteps": int(ppo.num_timesteps), "wall_seconds": wall, "env_steps_per_second": rate, "env_steps_per_s": rate,
         "observation_dim": int(ppo.obs_dim),
     }
-    summary["evaluation_wall_seconds"] = time.time() - t_eval   # the sequential evaluation and the gate, after training
+    # the sequential evaluation and the gate, after training (a population's chained evaluation: its share of the one batch call + its own files)
+    summary["evaluation_wall_seconds"] = time.time() - t_eval + evaluation_wall_offset
     (root / "training_summary.json").write_text(json.dumps(summary, indent=2, default=str))
     print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "model_latest": str(latest) + ".zip", "prefix_end_index": curriculum_summary["prefix_end_index"],
                       "env_steps_per_second": summary["env_steps_per_second"]}, indent=2))

@@ -36,6 +36,14 @@ Also the iteration time at the reference scale, and from both the share of a run
 eval_interval.
 
     python tools/population_bench.py --eval [--ks 1,8,16] [--repeats 5] [--out profiles/r09_population_eval.json]
+
+--route-eval: the wall time of the final sequential evaluations of a `train_route --seeds` run -- the default gate's prefixes up to
+--end-index plus the full route taken as --end-index (40: prefixes 20 and 40, then 40 again) -- for a RoutePopulationPPO of K replicas after
+one training iteration of the --route shape, both ways, alternately in one process, --repeats times each: K x (prefixes + full)
+evaluate_sequential_route calls through replica(k).predict (per_replica) and one evaluate_sequential_route_batch with one chain per replica,
+every evaluation a slice of it (batch).  Also the batch form's time per lock step.
+
+    python tools/population_bench.py --route-eval [--ks 1,8,16] [--end-index 40] [--repeats 5] [--out profiles/r10_route_population_eval.json]
 """
 from __future__ import annotations
 
@@ -280,8 +288,85 @@ def main_eval(args) -> None:
     print(json.dumps({"gate_evaluation_median_ms": {r["K"]: {f: round(r[f]["median_ms"], 1) for f in ("per_replica", "population")} for r in rows}}))
 
 
+def main_route_eval(args) -> None:
+    import statistics
+
+    from rl_brain_trainer_amd import route_config as rcfg
+    from rl_brain_trainer_amd.route_curriculum import evaluate_sequential_route, evaluate_sequential_route_batch, sliced_evaluate
+
+    args.ks = args.ks or "1,8,16"
+    args.batch = args.batch or 512
+    cfg = json.loads(ROUTE_CONFIG.read_text())
+    route_q = rcfg.load_route_q(ROUTE_PATH)
+    E = int(args.end_index)
+    ends = [p for p in (20, 40, 80, 120, 180) if p <= E] + [E]      # the default gate's prefixes inside the bound, then the "full route"
+
+    def timed(fn) -> float:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    rows = []
+    for K in (int(k) for k in args.ks.split(",")):
+        pop = build_route(K, args.n_envs, args.n_steps, args.batch, args.hidden, True)
+        pop.collect_rollouts()
+        pop.train()      # one training iteration: the replicas' weights differ
+        torch.cuda.synchronize()
+        progress = pop.pop_env.route_progress_m
+        seen = {}
+
+        def per_replica():
+            out = []
+            for k in range(K):
+                policy = pop.replica(k).predict
+                out.append([evaluate_sequential_route(policy=lambda o: policy(o.float().contiguous()), cfg=cfg, route_q=route_q, start_index=1, end_index=e)
+                            for e in ends])
+            seen["per_replica"] = out
+
+        def batch():
+            chains = evaluate_sequential_route_batch(mlp=pop._mlp, cfg=cfg, route_q=route_q, start_index=1, end_indices=[E] * K)
+            seen["lock_steps"] = chains[0]["lock_steps"]
+            seen["batch"] = [[sliced_evaluate(c["rows"], c["final_qs"], progress)(artifact_root=None, start_index=1, end_index=e) for e in ends] for c in chains]
+
+        per_replica()      # warm-up of both forms; the two forms must agree before either is timed
+        batch()
+        for k in range(K):
+            for a, b in zip(seen["per_replica"][k], seen["batch"][k]):
+                assert {key: a[key] for key in b} == b, (K, k)
+        t = {"per_replica": [], "batch": []}
+        for _ in range(args.repeats):
+            t["per_replica"].append(timed(per_replica))
+            t["batch"].append(timed(batch))
+        _close(pop)
+        row = {"K": K, "end_index": E, "evaluations_per_replica": ends, "waypoint_episodes_per_replica": {"per_replica": sum(ends), "batch": E},
+               "lock_steps": seen["lock_steps"]}
+        for form, ms in t.items():
+            med = statistics.median(ms)
+            row[form] = {"ms": ms, "median_ms": med, "spread_ms": max(ms) - min(ms)}
+        row["batch"]["us_per_lock_step"] = 1e3 * row["batch"]["median_ms"] / max(seen["lock_steps"], 1)
+        row["speedup_median"] = row["per_replica"]["median_ms"] / row["batch"]["median_ms"]
+        row["faster_by_more_than_per_replica_spread"] = row["per_replica"]["median_ms"] - row["batch"]["median_ms"] > row["per_replica"]["spread_ms"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    result = {"workload": f"final sequential evaluations of a train_route --seeds run on synthetic_route.json (route_curriculum_prefix120_routeobs_sequence2), "
+                          f"end indices {ends} per replica (the default gate's prefixes up to {E}, then the full route taken as {E}), for a "
+                          f"RoutePopulationPPO of K replicas, {args.n_envs} envs x {args.n_steps} steps per replica, minibatch {args.batch}, 2x{args.hidden}, "
+                          f"after one iteration; per_replica = K x {len(ends)} evaluate_sequential_route calls through replica(k).predict, batch = one "
+                          f"evaluate_sequential_route_batch (one chain per replica to {E}) + {len(ends)} slices per replica; alternated, {args.repeats} "
+                          "repeats; no artifact files in either form",
+              "device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
+    print(json.dumps({"route_evaluation_median_ms": {r["K"]: {f: round(r[f]["median_ms"], 1) for f in ("per_replica", "batch")} for r in rows}}))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--route-eval", action="store_true", help="the final sequential evaluations of a route --seeds run: K x (prefixes + full) "
+                    "per-replica evaluations against one chained batch evaluation")
+    ap.add_argument("--end-index", type=int, default=40, help="with --route-eval: the largest route index evaluated (the 'full route' of the bench)")
     ap.add_argument("--eval", action="store_true", help="one gate evaluation of a --seeds run: K per-replica evaluations against one population evaluation")
     ap.add_argument("--repeats", type=int, default=5, help="with --eval: timed repeats of each form")
     ap.add_argument("--handoff-confirm-steps", type=int, default=2, help="with --eval: the evaluator's handoff_confirm_steps (2, the gate's; 0 hands "
@@ -310,12 +395,16 @@ def main() -> None:
         ap.error("--one-handle is the Approach form; --route is always one handle")
     if args.eval and (args.route or args.dock or args.sweep):
         ap.error("--eval measures the Approach population's gate evaluation")
+    if args.route_eval and (args.eval or args.route or args.dock or args.one_handle or args.sweep):
+        ap.error("--route-eval measures the route population's final evaluations on its own")
     if args.dock and (args.route or args.one_handle):
         ap.error("--dock measures the Finisher iteration in both forms")
     args.n_envs = args.n_envs or (12 if args.dock else 16)
     args.n_steps = args.n_steps or (256 if args.dock else 1024)
     if args.dock:
         return main_dock(args)
+    if args.route_eval:
+        return main_route_eval(args)
     if args.eval:
         return main_eval(args)
     args.ks = args.ks or ("1,2,4,8,16" if args.route or args.one_handle else "1,2,4,8")
