@@ -312,6 +312,26 @@ int kp1_mlp_profile_read(kp1_mlp* m, float* out_us /* [KP1_MLP_PROFILE_SLOTS] */
 int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, float* exp_avg_sq, float lr, float eps,
                       float max_grad_norm, int32_t step, int32_t flags, void* stream);
 
+/* The route trainer's teacher-anchor side loss as a device step (handles on the layer-wise path: hidden 64 or 128, K = 1 or a population;
+ * hidden 256 returns KP1_ERR_UNSUPPORTED).  For replica k
+ *   loss_k = loss_weight * mean_{i < n, d < 7} (mean_k(obs[idx[k][i]])_d - teacher_actions[idx[k][i]][d])^2
+ * on the unclipped deterministic policy mean.  obs [M][obs_stride] and teacher_actions [M][7] are the shared dataset; idx is int64 [K][n]
+ * for a population (required) and [n] or NULL (rows 0..n) for K = 1.  grad_out f32 [K][num_params] is overwritten: the gradient of the six
+ * actor tensors (mlp_extractor.policy_net.{0,2}.{weight,bias}, action_net.{weight,bias}), 0 everywhere else.  loss_out f32 [K] is
+ * overwritten.  Partials are summed in a fixed order (no float atomics): bitwise reproducible.  Unlike kp1_mlp_loss_grad it does NOT advance
+ * the device-resident step count. */
+int kp1_mlp_anchor_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const int64_t* idx, int32_t n, const float* teacher_actions,
+                             float loss_weight, float* grad_out, float* loss_out, void* stream);
+
+/* clip_grad_norm_(max_grad_norm) over the six actor tensors + Adam(beta 0.9/0.999) on those tensors only, for the gradient the preceding
+ * kp1_mlp_anchor_loss_grad call on this handle wrote (its norm partials are reused).  The bias corrections use the step count
+ * common + actor_extra + 1: common = step if step > 0, else the device-resident counter; actor_extra = the KP1_MLP_OPT_ACTOR_EXTRA_STEPS value.
+ * No other element of params / exp_avg / exp_avg_sq is written; the kernel-format weights of the changed elements are repacked.  With a
+ * replica hyper-parameter table set, replica k uses its learning_rate and adam_eps; the norm bound is always the argument.  Afterwards
+ * actor_extra is one larger (stream ordered, so a kp1_mlp_adam_step replayed from an already captured graph sees it). */
+int kp1_mlp_anchor_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, float* exp_avg_sq, float lr, float eps,
+                             float max_grad_norm, int32_t step, void* stream);
+
 /* HIP-event timing of the MFMA kernels at minibatch size n (for bench.py's roofline block): runs each kernel `iters` times back
  * to back on `stream` between hipEventRecord pairs and returns the mean duration in milliseconds (out_ms / out_flops hold 6):
  *   out_ms[0] gemm_nt fwd layer 2 (H x H, bias+tanh)    out_ms[1] gemm_nt bwd dZ1 (H x H, dtanh)

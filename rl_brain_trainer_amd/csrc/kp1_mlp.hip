@@ -1219,6 +1219,217 @@ __global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(float* __restrict__ p,
   }
 }
 
+// ---------------------------------------------------------------------------------------------- teacher-anchor side loss
+// loss = loss_weight * mean_{i < n, d < 7} (mean(obs[idx[i]])_d - teacher[idx[i]][d])^2 on the unclipped policy mean (the route trainer's
+// RouteTeacherAnchorCallback).  Only the policy net and action_net get a gradient; the forward layers, dZ1 and the weight-gradient GEMMs are
+// the layer-wise launches of kp1_mlp_loss_grad, the head, the finalize and the Adam step are the kernels below.
+struct AnchorHeadArgs {
+  const float* h2;        // [2][n][HP]
+  int64_t strideH;
+  int n;
+  const float* w3;        // [8][HP]
+  const float* b3;        // [8]
+  const int64_t* idx;     // rows of the teacher dataset (NULL: rows 0..n)
+  const float* teacher;   // [M][7]
+  float dcoef, lcoef;     // loss_weight * 2 / (7 n), loss_weight / (7 n)
+  float* dz2;             // [2][n][HP]
+  float* hpart;           // head_train_kernel's layout: dW action at [o][HP], db2 pi at 8 HP, head-bias grads at 10 HP, the loss sum at 10 HP + 15
+  int hpart_stride;
+  unsigned r_act, r_hpart;   // POP: grid.y = replica
+};
+
+// head_train_kernel's shape for the anchor loss: 32 rows per 256-thread block, w3 and the block's policy-net h2 rows staged in LDS once (all
+// loads in flight before the first LDS store), thread = (row, out) for d loss / d mean, then one thread per hidden column for the policy
+// net's dZ2 tile and the action_net partials; the value net's dZ2 tile is written as zeros (its gradient GEMMs then produce zeros).
+template <int HP, bool POP = false>
+__global__ void __launch_bounds__(256) head_anchor_kernel(const AnchorHeadArgs a_) {
+  AnchorHeadArgs a = a_;
+  if constexpr (POP) {
+    const unsigned rep = blockIdx.y;
+    a.h2 += rep * a.r_act; a.dz2 += rep * a.r_act; a.hpart += rep * a.r_hpart;
+    a.w3 += rep * (unsigned)(HEADS * HP); a.b3 += rep * (unsigned)HEADS;
+    if (a.idx) a.idx += rep * (unsigned)a.n;
+  }
+  // all LDS is one dynamic array (16-B aligned base; every carve below is a multiple of 4 floats: head_dot reads float4)
+  extern __shared__ float smem[];
+  constexpr int hpitch = HP + 4, Q = HP / 4, LOADS = HEAD_ROWS * Q / 256, WLOADS = HEADS * Q / 256;
+  static_assert(HEAD_ROWS * Q % 256 == 0 && HEADS * Q % 256 == 0 && 2 * HP % 256 == 0, "head_anchor_kernel staging");
+  float* w3s = smem;                        // [8][HP]
+  float* dout = smem + HEADS * HP;          // [HEAD_ROWS][8]: d loss / d mean_0..6 (slot 7 = 0)
+  float* red = dout + HEAD_ROWS * 8;        // [4 waves][12]: 7 bias grads, pad, the loss sum at +8
+  float* h2s = red + 48;                    // [HEAD_ROWS][hpitch]
+  {
+    f32x4 wv[WLOADS], hv[LOADS];
+#pragma unroll
+    for (int j = 0; j < WLOADS; ++j) wv[j] = *reinterpret_cast<const f32x4*>(a.w3 + 4 * (threadIdx.x + 256 * j));
+#pragma unroll
+    for (int j = 0; j < LOADS; ++j) {
+      const int f = threadIdx.x + 256 * j, r = f / Q, c4 = f % Q;
+      const int grow = min(blockIdx.x * HEAD_ROWS + r, a.n - 1);
+      hv[j] = *reinterpret_cast<const f32x4*>(a.h2 + (int64_t)grow * HP + 4 * c4);
+    }
+#pragma unroll
+    for (int j = 0; j < WLOADS; ++j) *reinterpret_cast<f32x4*>(w3s + 4 * (threadIdx.x + 256 * j)) = wv[j];
+#pragma unroll
+    for (int j = 0; j < LOADS; ++j) {
+      const int f = threadIdx.x + 256 * j, r = f / Q, c4 = f % Q;
+      *reinterpret_cast<f32x4*>(h2s + r * hpitch + 4 * c4) = hv[j];
+    }
+  }
+  __syncthreads();
+  const int row_l = threadIdx.x >> 3, out = threadIdx.x & 7;
+  const int row = blockIdx.x * HEAD_ROWS + row_l;
+  const bool ok = row < a.n && out < ACT;     // tail rows and the eighth lane of a row contribute 0
+  float d = 0.f, l = 0.f;
+  if (ok) {
+    const int64_t src = a.idx ? a.idx[row] : (int64_t)row;
+    const float mean = head_dot(h2s + row_l * hpitch, w3s + out * HP, HP) + a.b3[out];
+    const float diff = mean - a.teacher[src * ACT + out];
+    d = a.dcoef * diff;
+    l = a.lcoef * diff * diff;
+  }
+  dout[row_l * 8 + out] = d;
+  // per-wave sums (lanes with equal t & 7 hold the same `out`; the loss over the whole wave), combined across the 4 waves in a fixed order
+  float dsum = d;
+  dsum += __shfl_xor(dsum, 8);
+  dsum += __shfl_xor(dsum, 16);
+  dsum += __shfl_xor(dsum, 32);
+  float lsum = l;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) lsum += __shfl_xor(lsum, off);
+  const int wave_ = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) < 8) red[wave_ * 12 + out] = dsum;
+  if ((threadIdx.x & 63) == 0) red[wave_ * 12 + 8] = lsum;
+  __syncthreads();
+  float* part = a.hpart + (int64_t)blockIdx.x * a.hpart_stride;
+  if (threadIdx.x < 8) {   // 0..6 action_net bias grads, 7 the loss
+    const int slot = threadIdx.x < ACT ? threadIdx.x : 8;
+    part[10 * HP + (threadIdx.x < ACT ? threadIdx.x : 15)] = ((red[slot] + red[12 + slot]) + red[24 + slot]) + red[36 + slot];
+  }
+  // phase 2: threads [0, HP) own one hidden column of the policy net, threads [HP, 2 HP) zero the same column of the value net's dZ2
+  const int rows_here = min(HEAD_ROWS, a.n - blockIdx.x * HEAD_ROWS);
+  for (int hh = threadIdx.x; hh < 2 * HP; hh += 256) {
+    const int h = hh % HP;
+    if (hh >= HP) {
+      for (int r = 0; r < rows_here; ++r) a.dz2[a.strideH + (int64_t)(blockIdx.x * HEAD_ROWS + r) * HP + h] = 0.f;
+      continue;
+    }
+    float wcol[ACT], gw[ACT];
+#pragma unroll
+    for (int o = 0; o < ACT; ++o) {
+      wcol[o] = w3s[o * HP + h];
+      gw[o] = 0.f;
+    }
+    float gb2 = 0.f;
+    for (int r = 0; r < rows_here; ++r) {
+      const float hp = h2s[r * hpitch + h];
+      float dp = 0.f;
+#pragma unroll
+      for (int o = 0; o < ACT; ++o) {
+        const float dd = dout[r * 8 + o];
+        dp = fmaf(dd, wcol[o], dp);
+        gw[o] = fmaf(dd, hp, gw[o]);
+      }
+      const float dz = dp * (1.f - hp * hp);
+      a.dz2[(int64_t)(blockIdx.x * HEAD_ROWS + r) * HP + h] = dz;
+      gb2 += dz;
+    }
+#pragma unroll
+    for (int o = 0; o < ACT; ++o) part[o * HP + h] = gw[o];
+    part[8 * HP + h] = gb2;
+  }
+}
+
+__device__ __forceinline__ bool is_actor_element(const ParamLayout& L, int64_t i) {
+  return (i >= L.p_w1 && i < L.v_w1) || (i >= L.a_w && i < L.c_w);   // policy_net.{0,2}.{weight,bias}, action_net.{weight,bias}
+}
+
+// The anchor gradient in SB3 order: an actor element is the fixed-order sum of its producers' partials (finalize_source: the same places
+// grad_finalize_kernel reads), every other element is written as 0.  Block b leaves the f64 sum of squares of what it wrote in sumsq[b]
+// (the norm of the six actor tensors: the rest is zero), thread 0 of block 0 sums the loss partials.  Does not touch the step count.
+struct AnchorFinalizeArgs {
+  FinalizeArgs f;      // stats, step_counter, hparams unused (NULL); sumsq = the handle's anchor partials
+  float* loss_out;     // [K]
+};
+
+template <bool POP = false>
+__global__ void __launch_bounds__(256) anchor_finalize_kernel(const AnchorFinalizeArgs a_) {
+  const FinalizeArgs a = POP ? finalize_args_replica(a_.f, blockIdx.y) : a_.f;
+  const ParamLayout& L = a.L;
+  __shared__ double sq[4];
+  const int64_t i = (int64_t)(blockIdx.x * 256u + threadIdx.x);
+  float gval = 0.f;
+  if (i < L.total) {
+    if (is_actor_element(L, i)) {
+      const PartialSrc s = finalize_source(a, i);
+      for (int c = 0; c < s.n; ++c) gval += s.p[(int64_t)c * s.stride];
+    }
+    a.grad[i] = gval;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {   // element 0 is log_std: this thread has no gradient to sum
+    float t = 0.f;
+    for (int c = 0; c < a.h_n; ++c) t += a.hpart[(int64_t)c * a.h_stride + 10 * L.Hp + 15];
+    a_.loss_out[POP ? blockIdx.y : 0u] = t;
+  }
+  double w = (double)gval * (double)gval;
+  for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off);
+  if ((threadIdx.x & 63) == 0) sq[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) a.sumsq[blockIdx.x] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
+}
+
+// clip_grad_norm_(max_norm) over the actor tensors + torch.optim.Adam on the actor ranges only, with the per-tensor step count
+// common + actor_extra + 1 (common = host_step, or the device counter when host_step <= 0); the changed elements are repacked in the same
+// pass.  Nothing outside the actor ranges is written.  The bias corrections are formed once per block in f64, as the host-side torch step
+// forms them (step size lr / (1 - 0.9^t) and sqrt(1 - 0.999^t) rounded to fp32).  POP: grid.y = replica; lr / eps from the table when set.
+template <bool POP = false>
+__global__ void __launch_bounds__(ADAM_BLOCK) anchor_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                          const double* __restrict__ partials, int n_partials, float lr, float eps, float max_norm,
+                                                          const ParamLayout L, const Packed k_, const int* __restrict__ step_dev, int host_step,
+                                                          unsigned r_partials, const float* __restrict__ hparams) {
+  __shared__ float sh[3];   // clip scale, lr / bc1, sqrt(bc2)
+  const Packed k = POP ? packed_replica(k_, L, blockIdx.y) : k_;
+  if constexpr (POP) {
+    const unsigned o = blockIdx.y * (unsigned)L.total;
+    p += o; g += o; m += o; v += o;
+    partials += blockIdx.y * r_partials;
+    if (hparams) {
+      const float* e = hparams + blockIdx.y * (unsigned)HP_FIELDS;
+      lr = e[HP_LR];
+      eps = e[HP_EPS];
+    }
+  }
+  const int64_t i = (int64_t)blockIdx.x * ADAM_BLOCK + threadIdx.x;
+  const bool actor = i < L.total && is_actor_element(L, i);
+  const int64_t il = actor ? i : L.p_w1;   // the loads go out before the norm is known; threads without an element read a valid one
+  const float g_in = g[il], m_in = m[il], v_in = v[il], p_in = p[il];
+  double s = 0.0;
+  if (threadIdx.x < 64) {
+    for (int q = threadIdx.x; q < n_partials; q += 64) s += partials[q];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(s);
+    const int st = (host_step > 0 ? host_step : step_dev[0]) + step_dev[1] + 1;
+    sh[0] = max_norm > 0.f ? fminf(max_norm / (norm + 1e-6f), 1.f) : 1.f;
+    sh[1] = (float)((double)lr / (1.0 - pow(0.9, (double)st)));
+    sh[2] = (float)sqrt(1.0 - pow(0.999, (double)st));
+  }
+  __syncthreads();
+  if (actor) {
+    const float gi = g_in * sh[0];
+    const float mn = 0.9f * m_in + 0.1f * gi;
+    const float vn = 0.999f * v_in + 0.001f * gi * gi;
+    const float denom = sqrtf(vn) / sh[2] + eps;
+    const float pn = p_in - sh[1] * (mn / denom);
+    m[i] = mn; v[i] = vn; p[i] = pn;
+    pack_one(i, pn, L, k);
+  }
+}
+
+// the actor tensors have taken one more step than the rest: a launch of its own, after every block of anchor_adam_kernel has read the count
+__global__ void anchor_count_kernel(int* __restrict__ actor_extra) { *actor_extra += 1; }
+
 #include "kp1_env_step.inc"
 #include "kp1_eval_step.inc"
 #include "kp1_mlp_tile.inc"
@@ -1243,6 +1454,7 @@ struct kp1_mlp {
   int bf16x3 = 0;
   unsigned short* sp_h1 = nullptr; unsigned short* sp_dz2 = nullptr; unsigned short* sp_dz1 = nullptr; unsigned short* sp_xf = nullptr;
   double* partials = nullptr;  // [512]
+  double* anchor_partials = nullptr;   // [K][ANCHOR_PARTIALS] sum-of-squares partials of kp1_mlp_anchor_loss_grad (Hp = 128 handles)
   float* slab = nullptr;       // [64 chunks][2 nets][Hp][Hp] partial dW2
   float* slab1 = nullptr;      // [64 chunks][2 nets][Hp][64] partial dW1
   float* bslab = nullptr;      // [max_batch/64 row tiles][2 nets][Hp] partial db1
@@ -1318,6 +1530,7 @@ struct ProfScope {
 namespace {
 
 constexpr int N_PARTIALS = 128;
+constexpr int ANCHOR_PARTIALS = 256;   // blocks of anchor_finalize_kernel: 256 parameters each, 215 for the largest layer-wise net (2x128, 80 inputs)
 constexpr int PARTIALS_STRIDE = 2 * N_PARTIALS + 2048;   // doubles of kp1_mlp::partials per replica
 // batch chunks of the dW2 / dW1 partial tiles of gemm_tn_split_kernel: 8 chunks x 32 tiles = one dW2 workgroup per CU, 16 chunks x 16 tiles of
 // quarter-size dW1 workgroups (profiles/r02_ab_tn_wave_split.log)
@@ -1602,6 +1815,7 @@ int mlp_create(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batc
   MLP_ALLOC(m->dz1, K * 2 * mb * Hp);
   MLP_ALLOC(m->xf, mb * INP);
   MLP_ALLOC(m->partials, K * PARTIALS_STRIDE);
+  if (Hp == 128) MLP_ALLOC(m->anchor_partials, K * ANCHOR_PARTIALS);
   MLP_ALLOC(m->slab, K * 64 * 2 * Hp * Hp);
   MLP_ALLOC(m->slab1, K * 64 * 2 * Hp * INP);
   MLP_ALLOC(m->step_dev, 4);
@@ -2238,6 +2452,114 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
     KP1_LAUNCH(adam_kernel<false>, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK)), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
                n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1, 0u,
                (const float*)nullptr);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_mlp_anchor_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const int64_t* idx, int32_t n, const float* teacher_actions,
+                             float loss_weight, float* grad_out, float* loss_out, void* stream_) {
+  if (!m || !obs || !teacher_actions || !grad_out || !loss_out) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_anchor_loss_grad");
+  if (n <= 0 || n > m->max_batch) return fail(KP1_ERR_INVALID, "n exceeds the workspace max_batch");
+  const int IN = m->L.IN, INP = m->L.INP;
+  if (obs_stride != IN && obs_stride != INP) return fail(KP1_ERR_INVALID, "obs_stride must be the observation width or its padded width (56 / 64, or 80 / 128)");
+  if (m->Hp != 128) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step runs on the layer-wise kernels: hidden must be 64 or 128");
+  const bool pop = m->K > 1;
+  if (pop && !idx) return fail(KP1_ERR_INVALID, "population handles gather their rows through idx [K][n]");
+  const int n_blocks = (int)((m->L.total + 255) / 256);
+  if (n_blocks > ANCHOR_PARTIALS) return fail(KP1_ERR_INVALID, "parameter vector too large for the anchor sum-of-squares partials");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  constexpr int Hp = 128;
+  const int64_t act_stride = (int64_t)m->max_batch * Hp;
+  const int hpart_stride = 10 * Hp + 32;
+  const int64_t hpart_rep = (int64_t)(m->max_batch / 32) * hpart_stride;
+  rc = launch_forward_layers(m, obs, obs_stride, idx, n, stream);
+  if (rc != KP1_OK) return rc;
+  AnchorHeadArgs a{};
+  a.h2 = m->h2; a.strideH = act_stride; a.n = n;
+  a.w3 = m->k.w3; a.b3 = m->k.b3;
+  a.idx = idx; a.teacher = teacher_actions;
+  a.dcoef = loss_weight * 2.f / (float)(ACT * n); a.lcoef = loss_weight / (float)(ACT * n);
+  a.dz2 = m->dz2; a.hpart = m->hpart; a.hpart_stride = hpart_stride;
+  a.r_act = (unsigned)(2 * act_stride); a.r_hpart = (unsigned)hpart_rep;
+  {
+    const dim3 hgrid((n + HEAD_ROWS - 1) / HEAD_ROWS, m->K);
+    const size_t hbytes = sizeof(float) * (HEADS * Hp + HEAD_ROWS * 8 + 48 + HEAD_ROWS * (Hp + 4));
+    if (pop)
+      hipLaunchKernelGGL((head_anchor_kernel<Hp, true>), hgrid, dim3(256), hbytes, stream, a);
+    else
+      hipLaunchKernelGGL((head_anchor_kernel<Hp, false>), hgrid, dim3(256), hbytes, stream, a);
+  }
+  // dZ1 = (dZ2 W2) * (1 - h1^2) and the bias-1 partials, then dW2 and dW1: kp1_mlp_loss_grad's launches (the value net's are all zeros)
+  GemmNT g{};
+  g.A = m->dz2; g.lda = Hp; g.strideA = act_stride; g.gather = nullptr;
+  g.W = m->k.w2t; g.strideW = (int64_t)Hp * Hp;
+  g.bias = nullptr; g.strideBias = 0;
+  g.C = m->dz1; g.ldc = Hp; g.strideC = act_stride;
+  g.aux = m->h1; g.strideAux = act_stride;
+  g.colsum = m->bslab; g.strideColsum = Hp;
+  g.M = n; g.N = Hp; g.K = Hp; g.Kreal = Hp;
+  g.reps = m->K;
+  g.r_A = g.r_C = g.r_aux = (unsigned)(2 * act_stride); g.r_W = (unsigned)(2 * Hp * Hp);
+  g.r_colsum = (unsigned)((m->max_batch / 32) * 2 * Hp);
+  rc = launch_nt<EPI_DTANH>(g, stream);
+  if (rc != KP1_OK) return rc;
+  int s2_n = 0, s1_n = 0;
+  GemmTN t{};
+  t.B = n;
+  t.chunk = tn_chunk_rows(n, 2);
+  t.D = m->dz2; t.ldd = Hp; t.strideD = act_stride;
+  t.X = m->h1; t.ldx = Hp; t.strideX = act_stride; t.gatherX = nullptr;
+  t.Nload = Hp; t.n_i_tiles = 1;
+  rc = launch_tn(m, t, 1, Hp, m->slab, &s2_n, stream);
+  if (rc != KP1_OK) return rc;
+  t.D = m->dz1;
+  t.X = obs; t.ldx = obs_stride; t.strideX = 0; t.gatherX = idx;
+  t.Nload = obs_stride >= INP ? INP : IN;
+  rc = launch_tn(m, t, 1, INP, m->slab1, &s1_n, stream);
+  if (rc != KP1_OK) return rc;
+  AnchorFinalizeArgs fa{};
+  FinalizeArgs& f = fa.f;
+  f.L = m->L;
+  f.slab2 = m->slab; f.s2_ld = Hp; f.s2_net = (int64_t)Hp * Hp; f.s2_chunk = 2 * f.s2_net; f.s2_n = s2_n;
+  f.slab1 = m->slab1; f.s1_ld = INP; f.s1_net = (int64_t)Hp * INP; f.s1_chunk = 2 * f.s1_net; f.s1_n = s1_n;
+  f.bslab = m->bslab; f.b_net = Hp; f.b_tile = 2 * Hp; f.b_n = nt_row_tiles(n, Hp);
+  f.hpart = m->hpart; f.h_stride = hpart_stride; f.h_n = (n + HEAD_ROWS - 1) / HEAD_ROWS;
+  f.log_std = m->k.log_std;
+  f.grad = grad_out; f.sumsq = m->anchor_partials;
+  f.r_slab2 = (unsigned)(64 * f.s2_chunk); f.r_slab1 = (unsigned)(64 * f.s1_chunk); f.r_bslab = (unsigned)((m->max_batch / 32) * 2 * Hp);
+  f.r_hpart = (unsigned)hpart_rep; f.r_sumsq = (unsigned)ANCHOR_PARTIALS;
+  fa.loss_out = loss_out;
+  if (pop)
+    hipLaunchKernelGGL(anchor_finalize_kernel<true>, dim3(n_blocks, m->K), dim3(256), 0, stream, fa);
+  else
+    hipLaunchKernelGGL(anchor_finalize_kernel<false>, dim3(n_blocks), dim3(256), 0, stream, fa);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_mlp_anchor_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, float* exp_avg_sq, float lr, float eps, float max_grad_norm,
+                             int32_t step, void* stream_) {
+  if (!m || !params || !grad || !exp_avg || !exp_avg_sq) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_anchor_adam_step");
+  if (m->Hp != 128) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step runs on the layer-wise kernels: hidden must be 64 or 128");
+  const int n_blocks = (int)((m->L.total + 255) / 256);
+  if (n_blocks > ANCHOR_PARTIALS) return fail(KP1_ERR_INVALID, "parameter vector too large for the anchor sum-of-squares partials");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  Packed kfmt = m->k;
+  kfmt.formats = PACK_SLAB | PACK_FRAG;
+  m->last_params = params;
+  if (m->K > 1)
+    hipLaunchKernelGGL(anchor_adam_kernel<true>, dim3(n_blocks, m->K), dim3(ADAM_BLOCK), 0, stream, params, (const float*)grad, exp_avg, exp_avg_sq,
+                       (const double*)m->anchor_partials, n_blocks, lr, eps, max_grad_norm, m->L, kfmt, (const int*)m->step_dev, (int)step,
+                       (unsigned)ANCHOR_PARTIALS, m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr);
+  else
+    hipLaunchKernelGGL(anchor_adam_kernel<false>, dim3(n_blocks), dim3(ADAM_BLOCK), 0, stream, params, (const float*)grad, exp_avg, exp_avg_sq,
+                       (const double*)m->anchor_partials, n_blocks, lr, eps, max_grad_norm, m->L, kfmt, (const int*)m->step_dev, (int)step, 0u,
+                       (const float*)nullptr);
+  hipLaunchKernelGGL(anchor_count_kernel, dim3(1), dim3(1), 0, stream, m->step_dev + 1);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }

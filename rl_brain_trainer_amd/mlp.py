@@ -153,6 +153,24 @@ class MlpKernels:
         native.check(self.L.kp1_mlp_adam_step(self._h, _p(params), _p(grad), _p(exp_avg), _p(exp_avg_sq), lr, eps, max_grad_norm, step,
                                               2 if fused_norm else 0, self._stream()))
 
+    def anchor_loss_grad(self, obs: torch.Tensor, idx: torch.Tensor | None, n: int, teacher_actions: torch.Tensor, *, loss_weight: float,
+                         grad_out: torch.Tensor, loss_out: torch.Tensor) -> None:
+        """The teacher-anchor side loss (kp1_mlp_anchor_loss_grad): obs [M, obs_dim | obs_pad] and teacher_actions [M, 7] are the dataset, idx
+        int64 [K, n] its rows per replica ([n] or None for K = 1).  grad_out [K, P] gets the gradient of the six actor tensors and zeros
+        elsewhere, loss_out [K] the losses.  The device step count is not advanced."""
+        assert obs.is_contiguous() and obs.dtype == torch.float32 and teacher_actions.is_contiguous() and teacher_actions.dtype == torch.float32
+        assert teacher_actions.shape == (obs.shape[0], ACT_DIM) and grad_out.numel() == self.replicas * self.num_params
+        assert loss_out.numel() == self.replicas and loss_out.dtype == torch.float32
+        assert idx is None or (idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == self.replicas * n)
+        native.check(self.L.kp1_mlp_anchor_loss_grad(self._h, _p(obs), obs.shape[-1], _p(idx), n, _p(teacher_actions), loss_weight, _p(grad_out),
+                                                     _p(loss_out), self._stream()))
+
+    def anchor_adam_step(self, params, grad, exp_avg, exp_avg_sq, *, lr: float, eps: float, max_grad_norm: float, step: int) -> None:
+        """clip_grad_norm_ + Adam on the actor tensors for the gradient the last anchor_loss_grad wrote (kp1_mlp_anchor_adam_step); the
+        handle's actor-extra step count is one larger afterwards."""
+        native.check(self.L.kp1_mlp_anchor_adam_step(self._h, _p(params), _p(grad), _p(exp_avg), _p(exp_avg_sq), lr, eps, max_grad_norm, step,
+                                                     self._stream()))
+
     def placement_check(self, n_rows: int) -> dict[str, int | float]:
         """where the hardware puts the workgroups of a training-tile launch for an n_rows minibatch (the two placement assumptions the update
         kernels' SPEED rests on: include/kp1_ppo.h kp1_mlp_placement_check)"""

@@ -99,11 +99,11 @@ class ReplicaView:
         self.obs_dim = pop.obs_dim
         self.obs_w = pop.obs_w
         self.dist = _ReplicaDist()
-        self.actor_extra_steps = 0
         self.backend = "hip"
         self.device = pop.device
 
     adam_t = property(lambda self: self._pop.adam_t)
+    actor_extra_steps = property(lambda self: int(self._pop.actor_extra_steps))   # shared: every replica takes the same teacher-anchor steps
     num_timesteps = property(lambda self: self._pop.num_timesteps)
     n_train_calls = property(lambda self: self._pop.n_train_calls)
     last_stats = property(lambda self: self._pop.replica_stats(self.k))
@@ -158,8 +158,10 @@ class PopulationPPO(PPO):
 
     @staticmethod
     def _check_population_args(seeds: list[int], cfg: PPOConfig, dist: Dist | None, teacher_anchor: Any,
-                               overrides: list[dict[str, float]] | None = None) -> tuple[list[int], Dist, list[dict[str, float]]]:
-        """the refusals every population shares; returns (seeds as ints, the Dist, the per-replica overrides)"""
+                               overrides: list[dict[str, float]] | None = None, *,
+                               accepts_anchor: bool = False) -> tuple[list[int], Dist, list[dict[str, float]]]:
+        """the refusals every population shares; returns (seeds as ints, the Dist, the per-replica overrides).  ``accepts_anchor``: a
+        PopulationTeacherAnchor passes (RoutePopulationPPO); anything else given as ``teacher_anchor`` is refused"""
         seeds = [int(s) for s in seeds]
         if not seeds:
             raise ValueError("PopulationPPO needs at least one seed")
@@ -170,20 +172,27 @@ class PopulationPPO(PPO):
             raise ValueError(f"PopulationPPO runs the layer-wise kernels of the 2x64 / 2x128 nets; hidden={cfg.hidden} is not supported "
                              "(the 2x256 tile kernels have no replica axis)")
         if teacher_anchor is not None:
-            raise ValueError("PopulationPPO does not support the teacher-anchor side loss (per-replica actor step counts)")
+            from .teacher_anchor import PopulationTeacherAnchor
+
+            if not accepts_anchor:
+                raise ValueError("this population does not support the teacher-anchor side loss: it is a route feature "
+                                 "(RoutePopulationPPO with a PopulationTeacherAnchor)")
+            if not isinstance(teacher_anchor, PopulationTeacherAnchor):
+                raise ValueError("the teacher-anchor side loss of a route population is a PopulationTeacherAnchor "
+                                 f"(got {type(teacher_anchor).__name__}; RouteTeacherAnchor steps one PPO)")
         dist = dist or Dist()
         if dist.enabled:
             raise ValueError("PopulationPPO is single-process: data parallel (a torch.distributed process group) is not supported")
         return seeds, dist, overrides
 
     def _init_population(self, seeds: list[int], cfg: PPOConfig, envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool,
-                         overrides: list[dict[str, float]] | None = None) -> None:
-        """what a population holds once its K env views and trackers exist"""
+                         overrides: list[dict[str, float]] | None = None, *, min_batch: int = 0) -> None:
+        """what a population holds once its K env views and trackers exist (``min_batch``: rows the MLP handle must hold besides its own needs)"""
         T, N, K = cfg.n_steps, envs[0].n_envs, len(seeds)
         max_steps = max(int(envs[0].config.c.termination.max_episode_steps), 1)
         self._trunc_cap = min(N * (T // max_steps + 1), T * N)
         # the MLP handle's max_batch holds the `_trunc_cap` rows per replica of the bootstrap's one forward
-        self._setup(cfg, seeds, envs, curricula, dist, use_graphs, min_batch=self._trunc_cap, stacked=True)
+        self._setup(cfg, seeds, envs, curricula, dist, use_graphs, min_batch=max(self._trunc_cap, int(min_batch)), stacked=True)
         self.seeds = seeds
         self.overrides = overrides if overrides is not None else [{} for _ in seeds]
         # a population with overrides keeps its per-replica constants on the device: the MLP handle's hyper-parameter table, (gamma, lambda)
@@ -472,6 +481,8 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
     """K route-curriculum runs of one PPOConfig on ONE RoutePopulationVecEnv (route_env.py): block k of its K N envs is replica k, which is the
     rollout buffers' replica-major layout, so every env step is one route step and one tracker launch (RoutePrefixCurriculumPopulation)
     whatever K is.  Everything else -- noise, truncation bootstrap, the epoch body, graph capture -- is PopulationPPO's.
+    ``teacher_anchor``: a ``PopulationTeacherAnchor`` (teacher_anchor.py); the caller runs ``anchor.on_rollout_end(pop)`` between
+    ``collect_rollouts()`` and ``train()``, as train_route does.
 
     Replica k is bit-identical to ``PPO(RouteVecEnv(..., seed=s_k), curriculum=RoutePrefixCurriculumDevice)`` on the same config
     (tests/test_route_population_gpu.py).  ``load_init_checkpoint`` (OneHandlePopulationPPO's) starts every replica from one checkpoint as
@@ -482,7 +493,7 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
         from .route_curriculum import RoutePrefixCurriculumPopulation
         from .route_env import RoutePopulationVecEnv
 
-        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides)
+        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides, accepts_anchor=True)
         if not isinstance(env, RoutePopulationVecEnv):
             raise TypeError("RoutePopulationPPO drives a RoutePopulationVecEnv (one handle for all replicas)")
         if env.seeds != seeds:
@@ -495,7 +506,13 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
         K = len(seeds)
         views = [env.replica(k) for k in range(K)]
         curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
-        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides)
+        # the MLP handle also holds one teacher-anchor batch per replica (PopulationTeacherAnchor steps it between rollout and update)
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides,
+                              min_batch=teacher_anchor.batch_rows if teacher_anchor is not None else 0)
+        self.teacher_anchor = teacher_anchor
+        if teacher_anchor is not None:
+            teacher_anchor.on_training_start(self)
+
 
 class DockPopulationPPO(OneHandlePopulationPPO):
     """K Finisher (dock-mode) runs of one PPOConfig on ONE ArmKinematicPopulationVecEnv with ONE DockReverseCurriculumPopulation

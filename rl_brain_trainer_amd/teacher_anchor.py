@@ -142,3 +142,90 @@ class RouteTeacherAnchor:
         out["enabled"] = True
         out["sample_count"] = int(self._actions.shape[0]) if self._actions is not None else 0
         return out
+
+
+def check_anchor_dataset(path: str | Path, max_route_index: int) -> int:
+    """Open and validate a teacher-anchor dataset on the host (no device work): the number of samples inside the protected prefix.  A
+    missing, unreadable or empty dataset is a ``ValueError`` that names the teacher-anchor dataset."""
+    try:
+        with np.load(Path(path), allow_pickle=False) as data:
+            if "route_index" not in data.files or "actions" not in data.files or not any(n.startswith("obs__") for n in data.files):
+                raise ValueError("it needs route_index, actions and obs__<key> arrays")
+            rows = int((np.asarray(data["route_index"], dtype=np.int32) <= max_route_index).sum())
+    except (OSError, ValueError, KeyError, EOFError) as exc:
+        raise ValueError(f"teacher-anchor dataset {path} cannot be read: {exc}") from exc
+    except Exception as exc:       # zipfile.BadZipFile and the like: not an npz archive
+        raise ValueError(f"teacher-anchor dataset {path} is not an npz archive: {exc}") from exc
+    if rows == 0:
+        raise ValueError(f"teacher-anchor dataset {path}: no samples left after max_route_index={max_route_index}")
+    return rows
+
+
+class PopulationTeacherAnchor:
+    """The teacher-anchor side loss of a ``RoutePopulationPPO``: every replica takes the reference callback's step on the SAME batch (the
+    callback draws from ``default_rng(0)``, so K one-by-one runs see the same rows too), as two device entry points on the population's MLP
+    handle (kp1_mlp_anchor_loss_grad, kp1_mlp_anchor_adam_step) -- the launches of one anchor step whatever K is.  All replicas take the same
+    number of anchor steps, so the handle's one actor-extra step count serves them all.
+
+    The dataset is opened and validated on the host at construction (before any device work); ``on_training_start(pop)`` puts it on the
+    device at the handle's observation pitch.  ``RoutePopulationPPO(..., teacher_anchor=this)`` sizes its MLP handle for ``batch_rows``."""
+
+    def __init__(self, config: TeacherAnchorConfig) -> None:
+        if not config.dataset_path:
+            raise ValueError("TeacherAnchorConfig.dataset_path is required when enabled (the teacher-anchor dataset)")
+        self.config = config
+        self.rows = check_anchor_dataset(config.dataset_path, int(config.max_route_index))
+        self.batch_rows = min(int(config.batch_size), self.rows)     # rows of one anchor batch: the MLP handle's max_batch must cover them
+        self._rng = np.random.default_rng(0)
+        self._rollout_count = 0
+        self._obs: torch.Tensor | None = None
+        self._actions: torch.Tensor | None = None
+        self._loss_dev: torch.Tensor | None = None
+        self._grad: torch.Tensor | None = None
+        self.actor_extra_steps = 0
+        self.last_loss: list[float] = []
+
+    def on_training_start(self, pop) -> None:
+        flat_obs, actions = load_anchor_dataset(self.config.dataset_path, int(self.config.max_route_index), pop.obs_dim)
+        if pop._mlp.max_batch < self.batch_rows:
+            raise ValueError(f"the population's MLP handle holds {pop._mlp.max_batch} rows; the teacher-anchor batch needs {self.batch_rows} "
+                             "(pass the anchor to RoutePopulationPPO(teacher_anchor=...))")
+        obs = torch.zeros((len(flat_obs), pop.obs_w), dtype=torch.float32, device=pop.device)
+        obs[:, :pop.obs_dim] = torch.as_tensor(flat_obs, device=pop.device)
+        self._obs, self._actions = obs, torch.as_tensor(actions, device=pop.device).contiguous()
+        self._loss_dev = torch.zeros(pop.K, dtype=torch.float32, device=pop.device)
+        self._grad = torch.zeros_like(pop.flat)       # the PPO gradient buffer's addresses are frozen in the captured update graph
+        self.actor_extra_steps = int(pop.actor_extra_steps)
+        self.last_loss = [0.0] * pop.K
+
+    def sample_indices(self) -> np.ndarray:
+        """RouteTeacherAnchor.sample_indices: ``rng.integers(0, M, size=min(batch_size, M))`` on the callback's default_rng(0) stream"""
+        return self._rng.integers(0, self.rows, size=self.batch_rows)
+
+    def on_rollout_end(self, pop) -> None:
+        self._rollout_count += 1
+        if self._rollout_count % max(int(self.config.every_rollouts), 1):
+            return
+        for _step in range(max(int(self.config.gradient_steps), 1)):
+            self.gradient_step(pop, self.sample_indices())
+        self.last_loss = [float(v) for v in self._loss_dev.tolist()]
+
+    def gradient_step(self, pop, pick: np.ndarray) -> None:
+        """one clip_grad_norm_(0.5) + Adam step of the imitation loss on every replica's actor tensors, on the batch ``pick``"""
+        n = int(len(pick))
+        idx = torch.as_tensor(np.ascontiguousarray(pick, dtype=np.int64), device=pop.device).repeat(pop.K).contiguous()   # [K][n]: the shared batch
+        cfg = pop.cfg
+        pop._mlp.anchor_loss_grad(self._obs, idx, n, self._actions, loss_weight=float(self.config.loss_weight), grad_out=self._grad,
+                                  loss_out=self._loss_dev)
+        pop._mlp.anchor_adam_step(pop.flat, self._grad, pop.adam_m, pop.adam_v, lr=cfg.learning_rate, eps=cfg.adam_eps, max_grad_norm=0.5,
+                                  step=pop.adam_t)
+        self.actor_extra_steps += 1
+        pop.actor_extra_steps = self.actor_extra_steps
+
+    def summary(self) -> dict[str, Any]:
+        import dataclasses
+
+        out = {f.name: getattr(self.config, f.name) for f in dataclasses.fields(self.config)}
+        out["enabled"] = True
+        out["sample_count"] = int(self.rows)
+        return out

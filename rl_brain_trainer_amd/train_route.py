@@ -11,7 +11,8 @@ sequence wrapper, 56- or 80-float observation as the YAML says); the PPO update 
         --output-dir /tmp/route --total-timesteps 1000000 --n-envs 1024
 
 Population: ``--seeds 7,8,9,10`` trains the seeds together on one GPU (RoutePopulationPPO: one route env handle and one tracker launch
-per env step for all of them; 2x64 / 2x128 nets).  Seed s writes under ``<output-dir>/seed_<s>/`` what a ``--seed s`` run writes, and
+per env step for all of them; 2x64 / 2x128 nets; with ``route.teacher_anchor.enabled`` every seed takes the anchor step on the same batch
+through one launch sequence, PopulationTeacherAnchor).  Seed s writes under ``<output-dir>/seed_<s>/`` what a ``--seed s`` run writes, and
 ``population_summary.json`` names the best seed: gate accepted first, then the final sequential evaluation's longest success prefix, then
 its success rate.
 
@@ -39,7 +40,7 @@ from .ppo import PPO, Dist, PPOConfig
 from .route_curriculum import (RoutePrefixCurriculumDevice, evaluate_route_gate, evaluate_sequential_route, evaluate_sequential_route_batch,
                                sliced_evaluate)
 from .route_env import RouteVecEnv
-from .teacher_anchor import RouteTeacherAnchor, TeacherAnchorConfig
+from .teacher_anchor import PopulationTeacherAnchor, RouteTeacherAnchor, TeacherAnchorConfig
 
 
 def load_route_training_config(path: str | Path | None) -> dict[str, Any]:
@@ -199,8 +200,11 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
     hidden = checkpoint.hidden_for_run(args.hidden, init_checkpoint)
     if hidden not in (64, 128):
         raise ValueError(f"--seeds trains 2x64 / 2x128 nets: pass --hidden 64 or 128, or an --init-checkpoint of such a net (got a 2x{hidden} policy)")
-    if TeacherAnchorConfig(**(route_cfg.get("teacher_anchor", {}) or {})).enabled:
-        raise ValueError("--seeds does not support the teacher-anchor side loss (route.teacher_anchor.enabled): train those seeds one by one")
+    anchor = None
+    anchor_cfg = TeacherAnchorConfig(**(route_cfg.get("teacher_anchor", {}) or {}))
+    if anchor_cfg.enabled:
+        # the dataset is opened and validated here, on the host, before any device work; every replica steps the same default_rng(0) batches
+        anchor = PopulationTeacherAnchor(anchor_cfg)
     if init_checkpoint:
         RoutePopulationPPO.check_init_checkpoint(init_checkpoint)
     W = int(route_q.shape[0])
@@ -217,7 +221,7 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
     curriculum = RoutePrefixCurriculumPopulation.from_config(cfg, W)
     pop = None
     try:
-        pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides)
+        pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides, teacher_anchor=anchor)
         if init_checkpoint:
             pop.load_init_checkpoint(init_checkpoint)
             print(f"Resuming every route policy of the population from {init_checkpoint}")
@@ -227,6 +231,8 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
         start_steps, it = pop.num_timesteps, 0
         while pop.num_timesteps - start_steps < total:
             pop.collect_rollouts()
+            if anchor is not None:
+                anchor.on_rollout_end(pop)            # after the rollout, before the update, as the --seed loop does
             pop.train()
             it += 1
             if pop.num_timesteps - start_steps >= next_checkpoint:
@@ -236,7 +242,8 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
             if args.log_every and it % args.log_every == 0:
                 stages = [curriculum.summary(k)["prefix_end_index"] for k in range(pop.K)]
                 print(f"[route-population] it={it} steps/replica={pop.num_timesteps} aggregate fps="
-                      f"{pop.K * (pop.num_timesteps - start_steps) / (time.time() - t0):,.0f} prefixes={stages}", flush=True)
+                      f"{pop.K * (pop.num_timesteps - start_steps) / (time.time() - t0):,.0f} prefixes={stages}"
+                      + (f" anchor={[round(v, 5) for v in anchor.last_loss]}" if anchor is not None else ""), flush=True)
         torch.cuda.synchronize()
         wall = time.time() - t0
         rate = (pop.num_timesteps - start_steps) / max(wall, 1e-9)     # env steps of one replica per second of the population's training loop
@@ -254,7 +261,8 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
             batch_share = (time.time() - t_batch) / pop.K
         for k, s in enumerate(seeds):   # the artefacts and the gate verdicts are written one seed after another, as single runs write them
             summary = _write_run_artifacts(args, cfg, route_cfg, route_path, route_q, env_cfg, init_checkpoint, roots[k], pop.replica(k),
-                                           curriculum_summaries[k], {"enabled": False}, n_envs, 1, wall, rate, device, evaluate=evaluators[k],
+                                           curriculum_summaries[k], anchor.summary() if anchor is not None else {"enabled": False}, n_envs, 1, wall,
+                                           rate, device, evaluate=evaluators[k],
                                            evaluation_wall_offset=batch_share)
             ev, gate = summary["route_eval_sequential_summary"], summary["route_gate_summary"]
             accepted = bool(gate.get("accepted", False))
@@ -265,6 +273,7 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
                          "last_stats": pop.replica_stats(k)})
         out = population_summary(pop, rows, wall_seconds=wall, selection=POPULATION_SELECTION)
         out["aggregate_env_steps_per_second"] = pop.K * rate     # the steps of this run, not the init checkpoint's clock
+        out["teacher_anchor_steps"] = int(pop.actor_extra_steps)   # anchor steps every replica's actor tensors took on top of the common count
         (root / "population_summary.json").write_text(json.dumps(out, indent=2, default=str))
         print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "seeds": seeds, "best_seed": out["best_seed"],
                           "aggregate_env_steps_per_second": out["aggregate_env_steps_per_second"]}, indent=2))

@@ -44,6 +44,14 @@ evaluate_sequential_route calls through replica(k).predict (per_replica) and one
 every evaluation a slice of it (batch).  Also the batch form's time per lock step.
 
     python tools/population_bench.py --route-eval [--ks 1,8,16] [--end-index 40] [--repeats 5] [--out profiles/r10_route_population_eval.json]
+
+--route-anchor: the teacher-anchor side loss of a `train_route --seeds` run at the --route shape (minibatch 512, anchor batch 256, one
+gradient step after every rollout) on a servo dataset recorded from the device env: the wall time of one training iteration of a
+RoutePopulationPPO of K replicas without and with a PopulationTeacherAnchor, the time of one device anchor step (all K replicas), and the
+time of RouteTeacherAnchor.gradient_step (torch autograd + repack) on one single PPO in the same process -- K times that is what training
+the seeds one by one pays per rollout.  The variants alternate, --repeats times each; median and max - min are reported.
+
+    python tools/population_bench.py --route-anchor [--ks 1,8,16] [--repeats 5] [--out profiles/r11_route_anchor.json]
 """
 from __future__ import annotations
 
@@ -109,7 +117,7 @@ ROUTE_CONFIG = ROOT / "tests" / "golden" / "configs" / "route_curriculum_prefix1
 ROUTE_PATH = ROOT / "tests" / "golden" / "synthetic_route.json"
 
 
-def build_route(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool) -> PopulationPPO:
+def build_route(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool, anchor=None) -> PopulationPPO:
     from rl_brain_trainer_amd import route_config as rcfg
     from rl_brain_trainer_amd.population import RoutePopulationPPO
     from rl_brain_trainer_amd.route_curriculum import RoutePrefixCurriculumPopulation
@@ -123,7 +131,7 @@ def build_route(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_
     seeds = list(range(7, 7 + K))
     env = RoutePopulationVecEnv(kcfg.to_env_config(cfg), rcfg.route_config_from_dict(cfg, max_route_index=prefixes[0]), route_q, seeds, n_envs)
     cur = RoutePrefixCurriculumPopulation.from_config(cfg, int(route_q.shape[0]))
-    pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=cur, use_graphs=use_graphs)
+    pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=cur, use_graphs=use_graphs, teacher_anchor=anchor)
     pop._bench_owned = [cur, env]     # closed after the population (the caller owns a route population's env and tracker)
     return pop
 
@@ -362,8 +370,130 @@ def main_route_eval(args) -> None:
     print(json.dumps({"route_evaluation_median_ms": {r["K"]: {f: round(r[f]["median_ms"], 1) for f in ("per_replica", "batch")} for r in rows}}))
 
 
+def _record_servo_dataset(path: Path, max_route_index: int) -> None:
+    """a teacher-anchor dataset as collect_route_teacher writes it: 64 device envs under a servo toward the route goal, 32 steps"""
+    import numpy as np
+
+    from rl_brain_trainer_amd import route_config as rcfg
+    from rl_brain_trainer_amd.route_env import RouteVecEnv
+
+    cfg = json.loads(ROUTE_CONFIG.read_text())
+    env = RouteVecEnv(kcfg.to_env_config(cfg), rcfg.route_config_from_dict(cfg, max_route_index=max_route_index), rcfg.load_route_q(ROUTE_PATH), 64, seed=3)
+    rows, acts, ridx = [], [], []
+    obs = env.reset()
+    for _ in range(32):
+        a = (0.8 * RouteVecEnv.obs_dict(obs)["route_q_error"]).clamp(-1, 1)
+        rows.append(obs[:, :env.obs_dim].cpu().numpy().copy())
+        acts.append(a.cpu().numpy().copy())
+        ridx.append(env.info()["route_index"].cpu().numpy().copy())
+        obs, _, _ = env.step(a)
+    env.close()
+    rows, acts, ridx = np.concatenate(rows), np.concatenate(acts), np.concatenate(ridx)
+    np.savez(path, actions=acts.astype(np.float32), route_index=ridx.astype(np.int32),
+             **{f"obs__{k}": rows[:, o:o + w] for k, (o, w) in rcfg.ROUTE_OBS_LAYOUT.items()})
+
+
+def main_route_anchor(args) -> None:
+    import statistics
+    import tempfile
+
+    from rl_brain_trainer_amd import route_config as rcfg
+    from rl_brain_trainer_amd.ppo import PPO
+    from rl_brain_trainer_amd.route_env import RouteVecEnv
+    from rl_brain_trainer_amd.teacher_anchor import PopulationTeacherAnchor, RouteTeacherAnchor, TeacherAnchorConfig
+
+    args.ks = args.ks or "1,8,16"
+    args.batch = args.batch or 512
+    STEPS = 20     # anchor steps per timed repeat
+
+    def timed(fn) -> float:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    def stat(ms: list[float], scale: float = 1.0) -> dict:
+        v = [x * scale for x in ms]
+        return {"values": v, "median": statistics.median(v), "spread": max(v) - min(v)}
+
+    rows = []
+    with tempfile.TemporaryDirectory() as tmp:
+        npz = Path(tmp) / "teacher_route_anchor_dataset.npz"
+        _record_servo_dataset(npz, 40)
+        acfg = TeacherAnchorConfig(enabled=True, dataset_path=str(npz), loss_weight=0.02, batch_size=256, max_route_index=40)
+        # the parent's step: one single PPO of the same shape, RouteTeacherAnchor (torch autograd on the flat vector, then a full repack)
+        cfg = json.loads(ROUTE_CONFIG.read_text())
+        route_q = rcfg.load_route_q(ROUTE_PATH)
+        algo = {k: v for k, v in kcfg.to_algorithm_kwargs(cfg, "ppo").items() if k not in ("total_timesteps", "n_steps", "batch_size", "seed")}
+        senv = RouteVecEnv(kcfg.to_env_config(cfg), rcfg.route_config_from_dict(cfg, max_route_index=rcfg.prefix_stages(cfg, int(route_q.shape[0]))[0]),
+                           route_q, args.n_envs, seed=7)
+        single = PPO(senv, PPOConfig.from_algo_kwargs(algo, n_steps=args.n_steps, batch_size=args.batch, hidden=args.hidden))
+        single.collect_rollouts()
+        single.train()
+        sanchor = RouteTeacherAnchor(acfg)
+        sanchor.on_training_start(single)
+
+        def torch_steps():
+            for _ in range(STEPS):
+                pick = torch.as_tensor(sanchor.sample_indices(), device=single.device)
+                sanchor.gradient_step(single, sanchor._obs.index_select(0, pick), sanchor._actions.index_select(0, pick))
+
+        torch_steps()      # warm-up
+        for K in (int(k) for k in args.ks.split(",")):
+            anchor = PopulationTeacherAnchor(acfg)
+            on = build_route(K, args.n_envs, args.n_steps, args.batch, args.hidden, True, anchor=anchor)
+            off = build_route(K, args.n_envs, args.n_steps, args.batch, args.hidden, True)
+
+            def iteration(pop, a=None):
+                pop.collect_rollouts()
+                if a is not None:
+                    a.on_rollout_end(pop)
+                pop.train()
+
+            def device_steps():
+                for _ in range(STEPS):
+                    anchor.gradient_step(on, anchor.sample_indices())
+
+            for _ in range(2):      # warm-up: both graphs of both populations captured, the anchor kernels loaded
+                iteration(off)
+                iteration(on, anchor)
+            device_steps()
+            t = {"iteration_anchor_off_ms": [], "iteration_anchor_on_ms": [], "device_anchor_step": [], "torch_anchor_step": []}
+            for _ in range(args.repeats):
+                t["iteration_anchor_off_ms"].append(timed(lambda: iteration(off)))
+                t["iteration_anchor_on_ms"].append(timed(lambda: iteration(on, anchor)))
+                t["device_anchor_step"].append(timed(device_steps))
+                t["torch_anchor_step"].append(timed(torch_steps))
+            row = {"K": K, "anchor_rows": anchor.batch_rows, "anchor_steps_per_timed_repeat": STEPS,
+                   "iteration_anchor_off_ms": stat(t["iteration_anchor_off_ms"]), "iteration_anchor_on_ms": stat(t["iteration_anchor_on_ms"]),
+                   "device_anchor_step_us": stat(t["device_anchor_step"], 1e3 / STEPS),             # all K replicas
+                   "torch_anchor_step_single_ppo_us": stat(t["torch_anchor_step"], 1e3 / STEPS)}    # one replica
+            row["one_by_one_anchor_us_per_rollout"] = K * row["torch_anchor_step_single_ppo_us"]["median"]
+            row["anchor_cost_in_iteration_ms"] = row["iteration_anchor_on_ms"]["median"] - row["iteration_anchor_off_ms"]["median"]
+            gain = row["one_by_one_anchor_us_per_rollout"] - row["device_anchor_step_us"]["median"]
+            row["device_step_faster_by_more_than_spread"] = gain > K * row["torch_anchor_step_single_ppo_us"]["spread"] + row["device_anchor_step_us"]["spread"]
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            _close(on)
+            _close(off)
+        senv.close()
+    result = {"workload": f"teacher-anchor side loss at the --route shape: route_curriculum_prefix120_routeobs_sequence2 on synthetic_route.json, "
+                          f"{args.n_envs} envs x {args.n_steps} steps per replica, minibatch {args.batch}, 2x{args.hidden}, graphs on, anchor batch 256 on a "
+                          f"servo dataset of the device env, one gradient step per rollout; iteration = collect_rollouts [+ anchor] + train, "
+                          f"device-synchronised; anchor step times are means over {STEPS} consecutive steps; variants alternated, {args.repeats} repeats, "
+                          "median and spread = max - min; torch_anchor_step_single_ppo = RouteTeacherAnchor.gradient_step on ONE PPO",
+              "device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
+    print(json.dumps({"anchor_step_us": {r["K"]: {"device_all_replicas": round(r["device_anchor_step_us"]["median"], 1),
+                                                  "torch_one_replica": round(r["torch_anchor_step_single_ppo_us"]["median"], 1)} for r in rows}}))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--route-anchor", action="store_true", help="the teacher-anchor side loss of a route --seeds run: iteration time without and "
+                    "with the device anchor step, and the device step against the torch step of one single PPO")
     ap.add_argument("--route-eval", action="store_true", help="the final sequential evaluations of a route --seeds run: K x (prefixes + full) "
                     "per-replica evaluations against one chained batch evaluation")
     ap.add_argument("--end-index", type=int, default=40, help="with --route-eval: the largest route index evaluated (the 'full route' of the bench)")
@@ -397,12 +527,16 @@ def main() -> None:
         ap.error("--eval measures the Approach population's gate evaluation")
     if args.route_eval and (args.eval or args.route or args.dock or args.one_handle or args.sweep):
         ap.error("--route-eval measures the route population's final evaluations on its own")
+    if args.route_anchor and (args.eval or args.route_eval or args.route or args.dock or args.one_handle or args.sweep):
+        ap.error("--route-anchor measures the route population's teacher-anchor step on its own")
     if args.dock and (args.route or args.one_handle):
         ap.error("--dock measures the Finisher iteration in both forms")
     args.n_envs = args.n_envs or (12 if args.dock else 16)
     args.n_steps = args.n_steps or (256 if args.dock else 1024)
     if args.dock:
         return main_dock(args)
+    if args.route_anchor:
+        return main_route_anchor(args)
     if args.route_eval:
         return main_route_eval(args)
     if args.eval:
