@@ -1299,3 +1299,29 @@ double kp1o_reward_eval(const kp1_config* cfg, int mode, const double prev_pose6
   *n_components = N_APPROACH_COMPONENTS;
   return compute_approach_reward(&cfg->reward, &ri, components);
 }
+
+/* n envs stepped once without auto-reset, each env's full kp1o_step_out kept (the lockstep parity helper resets finished envs itself) */
+void kp1o_batch_step_out(kp1o_env* envs, int n, const double* actions, float* obs, kp1o_step_out* outs) {
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+  for (int i = 0; i < n; ++i) kp1o_env_step(&envs[i], actions + 7 * (size_t)i, obs + KP1_OBS_DIM * (size_t)i, &outs[i]);
+}
+
+/* kp1o_reward_eval over n rows of arguments: prev / curr / goal pose6 [n][6], action / prev_action [n][7], flags [n][7], scalars [n][8]
+ * -> reward [n], components [n][KP1O_MAX_COMPONENTS] */
+void kp1o_reward_eval_batch(const kp1_config* cfg, int mode, int n, const double* prev_pose6, const double* curr_pose6,
+                            const double* goal_pose6, const double* action, const double* prev_action, const int32_t* flags,
+                            const double* scalars, double* reward, double* components) {
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+  for (int i = 0; i < n; ++i) {
+    int32_t nc = 0;
+    size_t s = (size_t)i;
+    double* c = components + s * KP1O_MAX_COMPONENTS;
+    memset(c, 0, sizeof(double) * KP1O_MAX_COMPONENTS);
+    reward[i] = kp1o_reward_eval(cfg, mode, prev_pose6 + 6 * s, curr_pose6 + 6 * s, goal_pose6 + 6 * s, action + 7 * s, prev_action + 7 * s,
+                                 flags + 7 * s, scalars + 8 * s, c, &nc);
+  }
+}

@@ -124,6 +124,12 @@ void kp1o_batch_step(kp1o_env* envs, int n, const double* actions /*[n][7]*/, fl
                      double* reward, uint8_t* done, int auto_reset, int n_threads);
 void kp1o_batch_step_components(kp1o_env* envs, int n, const double* actions, float* obs, double* reward, uint8_t* done, int auto_reset,
                                 int n_threads, double* components /*[n][KP1O_MAX_COMPONENTS] or NULL*/);
+/* one step of n envs without auto-reset, every env's kp1o_step_out kept */
+void kp1o_batch_step_out(kp1o_env* envs, int n, const double* actions, float* obs, kp1o_step_out* outs /*[n]*/);
+/* kp1o_reward_eval over n rows of arguments -> reward [n], components [n][KP1O_MAX_COMPONENTS] */
+void kp1o_reward_eval_batch(const kp1_config* cfg, int mode, int n, const double* prev_pose6, const double* curr_pose6,
+                            const double* goal_pose6, const double* action, const double* prev_action, const int32_t* flags,
+                            const double* scalars, double* reward, double* components);
 
 #ifdef __cplusplus
 }

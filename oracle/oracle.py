@@ -78,6 +78,15 @@ class OStepOut(C.Structure):
     ]
 
 
+# kp1o_step_out as a numpy record (np.ctypeslib cannot size the nested array member on every Python version)
+STEP_OUT_DTYPE = np.dtype({
+    "names": [n for n, _ in OStepOut._fields_],
+    "formats": [(np.float64, (MAX_COMPONENTS,)) if n == "components" else (np.int32 if t is C.c_int else np.float64) for n, t in OStepOut._fields_],
+    "offsets": [getattr(OStepOut, n).offset for n, _ in OStepOut._fields_],
+    "itemsize": C.sizeof(OStepOut),
+})
+
+
 class OTracker(C.Structure):
     _fields_ = [
         ("threshold", C.c_double), ("window", C.c_int), ("min_episodes", C.c_int), ("max_stage_index", C.c_int),
@@ -135,6 +144,10 @@ def lib() -> C.CDLL:
             assert L.kp1o_offsetof_env(k) == getattr(OEnv, name).offset, name
         L.kp1o_batch_step.argtypes = [C.POINTER(OEnv), C.c_int, dp, C.POINTER(C.c_float), dp, C.POINTER(C.c_uint8), C.c_int, C.c_int]
         L.kp1o_batch_step_components.argtypes = [C.POINTER(OEnv), C.c_int, dp, C.POINTER(C.c_float), dp, C.POINTER(C.c_uint8), C.c_int, C.c_int, dp]
+        L.kp1o_batch_step_out.argtypes = [C.POINTER(OEnv), C.c_int, dp, C.POINTER(C.c_float), C.POINTER(OStepOut)]
+        L.kp1o_reward_eval.restype = C.c_double
+        L.kp1o_reward_eval.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, dp, dp, C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int32)]
+        L.kp1o_reward_eval_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp, dp, dp, dp, C.POINTER(C.c_int32), dp, dp, dp]
         _lib = L
     return _lib
 
@@ -290,3 +303,57 @@ class OracleVecEnv:
 
     def field(self, name: str) -> np.ndarray:
         return np.array([np.array(getattr(self.envs[i], name)) for i in range(self.n)])
+
+    def fields(self, *names: str) -> list[np.ndarray]:
+        """the named kp1o_env members of every env, read from the env array's bytes in one pass (field() walks the envs in Python)"""
+        raw = np.frombuffer(self.envs, dtype=np.uint8).reshape(self.n, C.sizeof(OEnv))
+        out = []
+        for name in names:
+            f = getattr(OEnv, name)
+            ctype = dict(OEnv._fields_)[name]
+            dt = np.int32 if ctype is C.c_int else np.float64
+            a = np.ascontiguousarray(raw[:, f.offset:f.offset + f.size]).view(dt)
+            out.append(a[:, 0].copy() if a.shape[1] == 1 else a.copy())
+        return out
+
+    def rng_words(self, idx=None) -> np.ndarray:
+        idx = range(self.n) if idx is None else idx
+        return np.array([rng_words(self.envs[int(i)].rng) for i in idx], dtype=np.uint64).reshape(-1, 6)
+
+    def reset_env(self, i: int, options: dict[str, Any] | None = None) -> np.ndarray:
+        """reset of env i alone, as reset() does it for every env; options as in OracleEnv.reset (kp1o_reset_opts)"""
+        opts, keep = None, []
+        if options:
+            o = OResetOpts()
+            o.policy_mode = -1
+            for key in ("initial_q", "initial_dq", "initial_prev_action", "goal_q", "goal_pose6"):
+                if options.get(key) is not None:
+                    arr = np.ascontiguousarray(options[key], dtype=np.float64)
+                    keep.append(arr)
+                    setattr(o, key, _dp(arr))
+            if options.get("policy_mode") is not None:
+                o.policy_mode = kcfg.MODE_NAMES[options["policy_mode"]]
+            opts = C.byref(o)
+        self.L.kp1o_env_reset(C.byref(self.envs[i]), opts, self.obs[i].ctypes.data_as(C.POINTER(C.c_float)))
+        return self.obs[i]
+
+    def step_out(self, actions: np.ndarray) -> np.ndarray:
+        """one step without auto-reset -> the envs' kp1o_step_out records as a structured array [n]; self.obs holds the observations"""
+        a = np.ascontiguousarray(actions, dtype=np.float64)
+        assert a.shape == (self.n, kcfg.NJ)
+        if getattr(self, "_outs", None) is None:
+            self._outs = (OStepOut * self.n)()
+        self.L.kp1o_batch_step_out(self.envs, self.n, _dp(a), self.obs.ctypes.data_as(C.POINTER(C.c_float)), self._outs)
+        return np.frombuffer(self._outs, dtype=STEP_OUT_DTYPE).copy()
+
+
+def reward_eval_batch(cfg: kcfg.EnvConfig, mode: int, prev_pose6, curr_pose6, goal_pose6, action, prev_action, flags, scalars) -> tuple[np.ndarray, np.ndarray]:
+    """kp1o_reward_eval on n rows of arguments (flags [n,7] int32, scalars [n,8]; see kp1_oracle.c) -> (reward [n], components [n, n_components])"""
+    f64 = [np.ascontiguousarray(x, dtype=np.float64) for x in (prev_pose6, curr_pose6, goal_pose6, action, prev_action, scalars)]
+    flags = np.ascontiguousarray(flags, dtype=np.int32)
+    n = flags.shape[0]
+    reward, comps = np.empty(n), np.empty((n, MAX_COMPONENTS))
+    L = lib()
+    L.kp1o_reward_eval_batch(C.byref(cfg.c), int(mode), n, _dp(f64[0]), _dp(f64[1]), _dp(f64[2]), _dp(f64[3]), _dp(f64[4]),
+                             flags.ctypes.data_as(C.POINTER(C.c_int32)), _dp(f64[5]), _dp(reward), _dp(comps))
+    return reward, comps[:, :L.kp1o_num_components(int(mode))]
