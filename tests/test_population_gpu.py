@@ -13,7 +13,7 @@ def _dev():
 
 # ---------------------------------------------------------------------------------------------------------------- kernel level
 @pytest.mark.parametrize("hidden", [64, 128])
-@pytest.mark.parametrize("n", [256, 200])
+@pytest.mark.parametrize("n", [256, 200, 33, 1])
 @pytest.mark.parametrize("normalize_mode", [1, 2])
 def test_population_kernels_match_single_handles(hidden, n, normalize_mode):
     from rl_brain_trainer_amd import mlp
@@ -58,7 +58,8 @@ def test_population_kernels_match_single_handles(hidden, n, normalize_mode):
     adv_stats = None
     if normalize_mode == 2:
         a = adv[idx]
-        adv_stats = torch.stack([a.mean(1), 1.0 / (a.std(1) + 1e-8)], dim=1).float().contiguous()      # [K][2]
+        std = a.std(1) if n > 1 else torch.zeros(K, device=a.device)     # one row: the kernels' own definition, 1 / (0 + 1e-8)
+        adv_stats = torch.stack([a.mean(1), 1.0 / (std + 1e-8)], dim=1).float().contiguous()      # [K][2]
     kw = dict(clip_range=0.2, ent_coef=1e-3, vf_coef=0.5, inv_count=1.0 / n)
     grad = torch.zeros((K, P), device=dev)
     stats = torch.zeros((K, 4), device=dev)
