@@ -247,9 +247,11 @@ int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t
  * current observations of ALL envs of `env`, action = clip(mean, -1, 1), its fp64 norm sqrt(a0^2 + ... + a6^2) (products and sums in index
  * order, uncontracted), the env step without auto-reset, and kp1_eval_accumulate's bookkeeping of env step number `step` for every buffer
  * of `buffers`, n_alive included.  Same results, bit for bit, as kp1_mlp_forward (noise NULL, clipped_action) + that norm + kp1_step
- * (auto_reset 0) + kp1_eval_accumulate (tests/test_population_eval_gpu.py).
- *   m         a K = 1 or a population handle, hidden 64 or 128, 56-float observations; only the policy net runs, no activation workspace
- *             is used (max_batch does not bound the env count)
+ * (auto_reset 0) + kp1_eval_accumulate (tests/test_population_eval_gpu.py, tests/test_eval_step_h256_gpu.py).
+ *   m         56-float observations.  Hidden 64 or 128: a K = 1 or a population handle (eval_step_kernel).  Hidden 256: a K = 1 handle
+ *             with the tile path on (the default; KP1_ERR_UNSUPPORTED after it was switched to the layer-wise kernels), which runs the
+ *             evaluation form of the 2x256 inference tile.  Only the policy net runs, no activation workspace is used (max_batch does not
+ *             bound the env count)
  *   env       fp32 handle of K * n envs in approach or dock mode, reward components off, no bound tracker / population stages;
  *             row m of replica k is env k n + m
  *   obs       f32 [K n][the handle's obs stride, 56 or 64]: read (this step's observations) and overwritten (the next step's); a workgroup

@@ -1644,6 +1644,20 @@ int launch_fused_infer_env(const FusedArgs& fa, int env_mode, hipStream_t stream
   return KP1_OK;
 }
 
+// deterministic evaluation step of a 2x256 policy in one launch (kp1_eval_step): policy net only, the bookkeeping of fa.ev in the tail
+int launch_fused_eval_env(const FusedArgs& fa, int env_mode, hipStream_t stream) {
+  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;
+  const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, 1);
+  if (env_mode == KP1_MODE_DOCK) {
+    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 4>), grid, dim3(FU_NTH), bytes, stream, fa);
+  } else {
+    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 3>), grid, dim3(FU_NTH), bytes, stream, fa);
+  }
+  return KP1_OK;
+}
+
 int launch_fused_infer(const FusedArgs& fa, hipStream_t stream) {
   const size_t bytes = sizeof(float) * FU_LDS_FLOATS;   // 32-row tiles, 4 waves, two workgroups per CU
   // the value net is skipped when no value is asked for (deterministic evaluators), the policy net when only values are
@@ -2009,7 +2023,10 @@ int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* 
   if (!b->metrics || !b->counters || !b->flags || !b->state || !b->n_alive) return fail(KP1_ERR_INVALID, "kp1_eval_step: NULL buffer");
   if (b->hand_metrics && (!b->hand_step || !b->hand_success || !b->hand_state)) return fail(KP1_ERR_INVALID, "kp1_eval_step: incomplete handoff buffers");
   if (step < 1) return fail(KP1_ERR_INVALID, "kp1_eval_step accounts env steps 1, 2, ...: step 0 (the initialisation after a reset) is kp1_eval_accumulate's");
-  if (m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step covers the layer-wise widths (hidden 64 / 128); a 2x256 policy is evaluated through kp1_mlp_forward");
+  const bool tile = m->Hp == FU_HP;    // hidden 256: the evaluation form of the tile kernel; hidden 64 / 128: eval_step_kernel
+  if (!tile && m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step covers hidden 64 / 128 (layer-wise layout) and 256 (tile kernels)");
+  if (tile && (m->K > 1 || !m->fused))
+    return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step: the 256 form needs the tile kernels (a K = 1 handle with the tile path on); this handle runs the layer-wise kernels");
   if (m->L.INP != ES_INP) return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step needs the 56-float observation (padded to 64)");
   EvalStepArgs a{};
   int mode = 0, device = 0;
@@ -2024,6 +2041,22 @@ int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* 
   rc = mlp_check_device(m);
   if (rc != KP1_OK) return rc;
   const int Hp = m->Hp, INP = m->L.INP;
+  hipStream_t st = (hipStream_t)stream;
+  if (tile) {
+    FusedArgs fa{};
+    fa.env = a.env;
+    fa.obs = obs; fa.obs_stride = a.env.obs_stride; fa.Kreal = a.env.obs_stride >= INP ? INP : m->L.IN; fa.inp = INP; fa.idx = nullptr; fa.n = (int)n_envs;
+    fa.k = m->k;
+    fa.ev.b = *b;
+    fa.ev.step = step; fa.ev.confirm = confirm_steps;
+    fa.ev.track_ready = ready_thresholds != nullptr;
+    if (ready_thresholds) { fa.ev.thr_pos = ready_thresholds[0]; fa.ev.thr_ori = ready_thresholds[1]; fa.ev.thr_act = ready_thresholds[2]; fa.ev.thr_dq = ready_thresholds[3]; }
+    HIP_TRY(hipMemsetAsync(b->n_alive, 0, sizeof(int32_t), st));
+    rc = launch_fused_eval_env(fa, mode, st);   // obs is read (x tile, before the first barrier) and overwritten (after the last) in place
+    if (rc != KP1_OK) return rc;
+    HIP_TRY(kp1::launch_status());
+    return KP1_OK;
+  }
   a.b = *b;
   a.w1 = m->k.w1p; a.b1 = m->k.b1; a.w2 = m->k.w2; a.b2 = m->k.b2; a.w3 = m->k.w3; a.b3 = m->k.b3;   // net 0 (policy) leads every array
   a.r_w1 = (unsigned)(2 * Hp * INP); a.r_w2 = (unsigned)(2 * Hp * Hp); a.r_b = (unsigned)(2 * Hp); a.r_w3 = (unsigned)(HEADS * Hp); a.r_b3 = (unsigned)HEADS;
@@ -2032,7 +2065,6 @@ int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* 
   a.step = step; a.confirm = confirm_steps;
   a.track_ready = ready_thresholds != nullptr;
   if (ready_thresholds) { a.thr_pos = ready_thresholds[0]; a.thr_ori = ready_thresholds[1]; a.thr_act = ready_thresholds[2]; a.thr_dq = ready_thresholds[3]; }
-  hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(b->n_alive, 0, sizeof(int32_t), st));
   const dim3 grid((unsigned)((a.n + ES_BM - 1) / ES_BM), (unsigned)m->K);
   const bool pop = m->K > 1, dock = mode == KP1_MODE_DOCK;

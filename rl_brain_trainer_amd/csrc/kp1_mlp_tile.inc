@@ -35,6 +35,13 @@
 // hpart / bslab layout head_train_kernel and the dtanh epilogue use, one slot per 32-row tile;
 // sums inside the workgroup use shuffles / LDS in a fixed order (no float atomics anywhere => bitwise reproducible).
 
+// what the evaluation forms of the tile (ENV = 3 / 4) need beyond the rollout forms: kp1_eval_accumulate's buffers and step arguments
+struct FusedEvalArgs {
+  kp1_eval_buffers b;
+  int step, confirm, track_ready;
+  double thr_pos, thr_ori, thr_act, thr_dq;
+};
+
 struct FusedArgs {
   const float* obs; int64_t obs_stride; int Kreal;   // [rows][obs_stride]; columns >= Kreal read as 0
   int inp;                                            // padded observation width the weights were packed for (64 or 128): picks K1S
@@ -52,6 +59,7 @@ struct FusedArgs {
   int net_base;                                       // grid.z == 1 launches: which net (0 policy, 1 value) the workgroups run
   int stagger_ticks, n_cus;                           // 32-row training tiles: the second workgroup of every CU starts this many 10 ns ticks late
   StepArgs<float> env;                                // ENV != 0 (kp1_mlp_forward_env_step): row m of the tile IS env m, stepped in this launch
+  FusedEvalArgs ev;                                   // ENV = 3 / 4 (kp1_eval_step): the evaluator's bookkeeping of the env step this launch makes
   // [r3, experiment KP1_MLP_OPT_BF16X3_WGRAD] when non-NULL the tile ALSO leaves X / h1 / dZ2 / dZ1 as three bf16 planes (x = hi + mid + lo to 24 bits)
   // in "k16-fragment-major" order for the bf16-MFMA weight-gradient kernel: [plane][net][row/16][col/32][lane][8 bf16], sp_plane elements per plane
   unsigned short* sp_h1; unsigned short* sp_dz2; unsigned short* sp_dz1; unsigned short* sp_xf; int64_t sp_plane, sp_plane_x;
@@ -108,10 +116,18 @@ static_assert(FU_LDS_FLOATS * 4 * 2 <= 160 * 1024, "the two training tiles of on
 // TRAIN = false stops after the heads: layer 1 + layer 2 + heads + Gaussian sampling in one launch (replaces two gemm_nt
 // launches and head_infer_kernel in the rollout), nothing but the requested outputs is written.
 // K1S = 32-deep stages of layer 1: 2 (56-float observation padded to 64) or 4 (80-float route observation padded to 128).
-// ENV (inference only) = 1 / 2: the rollout step in ONE launch.  The policy workgroup of a tile, once its 32 rows' actions are sampled, hands
+// ENV (inference only) = 1 / 2: the rollout step in ONE launch (approach / dock mode).  The policy workgroup of a tile, once its 32 rows' actions are sampled, hands
 // the clipped actions to one lane per row through LDS and that lane runs the whole env step of its env (step_env_lane of kp1_env_step.inc:
 // approach / dock mode) -- the action never travels through HBM and the step needs no launch of its own (rollout: 3 -> 2 launches per env
 // step).  Such a kernel carries the env step's register footprint (one workgroup per CU: the rollout has one tile per CU anyway).
+// ENV = 3 / 4: the deterministic evaluation step in ONE launch (kp1_eval_step for hidden 256; approach / dock mode).  Same forward, policy net
+// only (grid.z = 1, net_base 0, noise NULL: every instruction up to the head sum v is the one mlp_tile_kernel<false, 2> issues, so v is the
+// mean kp1_mlp_forward writes, bit for bit).  The tail hands clip(v, -1, 1) to the row's lane, which takes its fp64 norm (es_action_norm),
+// steps the env without auto-reset and does the evaluator's bookkeeping of that step (eval_account_step) on the fields it has just stored;
+// one ballot + one atomicAdd per workgroup counts the episodes still alive.  No action, mean, value or log-prob goes to HBM.
+// In place: a.obs is read only by the x-tile load of the prologue (before the first barrier; rows past n re-read row n - 1, a row of the
+// same last tile) and observations are written only by store_obs_tile at the very end, each workgroup its own rows, and no value-net
+// plane reads them in another workgroup -- a.env.obs == a.obs is legal, and is how kp1_eval_step launches it.
 // SPLIT (training only, [r3 experiment]): the activations leave as three bf16 planes instead of the fp32 k8-fragment copies.  A separate
 // instantiation: the exact kernel carries none of its code (as run-time branches in one kernel the extra stores cost the exact path 1 us per launch).
 template <bool TRAIN, int K1S, int ENV = 0, bool SPLIT = false>
@@ -433,7 +449,7 @@ __global__ void __launch_bounds__(FU_NTH, ENV ? 1 : 2) mlp_tile_kernel(const Fus
       lp += __shfl_xor(lp, 2);
       lp += __shfl_xor(lp, 4);
       if (l_ok && l_out == 0 && a.log_prob) a.log_prob[l_src] = lp;
-      if constexpr (ENV != 0) {
+      if constexpr (ENV == 1 || ENV == 2) {
         // the tile's actions -> LDS (dout: [BM][8], idle in inference), then lane r of wave 0 steps env m0 + r; the other waves are done
         dout[l_row * 8 + l_out] = (l_ok && l_out < ACT) ? act : 0.f;    // step_env_lane clips to [-1, 1] itself (arm_kinematic_env.py:214)
         __syncthreads();
@@ -442,6 +458,28 @@ __global__ void __launch_bounds__(FU_NTH, ENV ? 1 : 2) mlp_tile_kernel(const Fus
           float o[KP1_OBS_DIM];
           if (live) step_env_lane<float, ENV == 1 ? KP1_MODE_APPROACH : KP1_MODE_DOCK, false>(a.env, (int64_t)(m0 + lane), dout + lane * 8, o);
           // the tile's observation rows leave as whole-line stores; bufA (h1) was last read in G2, two barriers ago
+          store_obs_tile(a.env.obs, (int64_t)m0, min(BM, a.n - m0), o, live, a.env.obs_stride, bufA);
+        }
+      }
+      if constexpr (ENV == 3 || ENV == 4) {
+        // evaluation step: the clamped mean (the clamp a.clipped gets above) -> LDS, then lane r of wave 0 is episode m0 + r
+        dout[l_row * 8 + l_out] = (l_ok && l_out < ACT) ? fminf(fmaxf(v, -1.f), 1.f) : 0.f;
+        __syncthreads();
+        if (wave == 0) {
+          const bool live = lane < BM && m0 + lane < a.n;
+          float o[KP1_OBS_DIM];
+          int alive_after = 0;
+          if (live) {
+            const int64_t i = (int64_t)(m0 + lane);
+            const double an = es_action_norm(dout + lane * 8);
+            step_env_lane<float, ENV == 3 ? KP1_MODE_APPROACH : KP1_MODE_DOCK, false>(a.env, i, dout + lane * 8, o);
+            // the fields the step has just stored are read back from the handle by the lane that stored them
+            alive_after = eval_account_step<float>(a.env.st.real, (int)a.env.st.n, (int)i, a.ev.b, an, a.env.done[i], a.ev.step, a.ev.track_ready != 0,
+                                                   a.ev.thr_pos, a.ev.thr_ori, a.ev.thr_act, a.ev.thr_dq, a.ev.confirm);
+          }
+          const unsigned long long bal = __ballot(alive_after != 0);
+          if (lane == 0 && bal) atomicAdd(a.ev.b.n_alive, __popcll(bal));
+          // the tile's next observations; bufA (h1) was last read in G2, two barriers ago.  This is the launch's only write to a.env.obs
           store_obs_tile(a.env.obs, (int64_t)m0, min(BM, a.n - m0), o, live, a.env.obs_stride, bufA);
         }
       }

@@ -355,17 +355,59 @@ def _run_episodes_reference(env: ArmKinematicVecEnv, policy: PolicyFn, reset_opt
 
 
 def _is_fused_width(mlp: Any) -> bool:
-    """an MlpKernels the one-launch evaluation step covers: the layer-wise widths on the 56-float observation"""
-    return mlp is not None and int(getattr(mlp, "hidden", 0)) in (64, 128) and int(getattr(mlp, "obs_dim", 0)) == kcfg.OBS_DIM
+    """an MlpKernels the one-launch evaluation step covers, on the 56-float observation: the layer-wise widths (K = 1 or a population), or a
+    K = 1 handle of hidden 256 whose tile path is on (kp1_eval_step refuses a 2x256 handle switched to the layer-wise kernels)"""
+    if mlp is None or int(getattr(mlp, "obs_dim", 0)) != kcfg.OBS_DIM:
+        return False
+    hidden = int(getattr(mlp, "hidden", 0))
+    if hidden == 256:
+        return int(getattr(mlp, "replicas", 1)) == 1 and bool(getattr(mlp, "fused", True))
+    return hidden in (64, 128)
+
+
+def policy_mlp(policy: Any) -> Any:
+    """the MlpKernels behind a policy callable, or None: an InferencePolicy or a PPO exposes it as ``_mlp``, a bound ``predict`` method of one
+    through ``__self__``; any other callable (a function, a lambda, a wrapper around predict) is not looked into"""
+    owner = getattr(policy, "__self__", None)
+    if owner is None:
+        return getattr(policy, "_mlp", None)
+    return getattr(owner, "_mlp", None) if getattr(policy, "__name__", "") == "predict" else None
+
+
+def _one_launch_mlp(policy: Any, env: Any, one_launch: bool | None, what: str) -> Any:
+    """the handle run_episodes_fused steps ``env`` with, or None for run_episodes.  ``one_launch``: None = the one-launch step where it is
+    covered (a K = 1 handle _is_fused_width accepts behind ``policy``, an fp32 ArmKinematicVecEnv), False = never, True = ValueError when not"""
+    if one_launch is False:
+        return None
+    mlp = policy_mlp(policy)
+    covered = (_is_fused_width(mlp) and int(getattr(mlp, "replicas", 1)) == 1 and isinstance(env, ArmKinematicVecEnv)
+               and env.dtype == torch.float32)
+    if covered:
+        return mlp
+    if one_launch:
+        raise ValueError(f"one_launch=True: the {what} phase is not covered by the one-launch evaluation step (it takes a policy backed by a "
+                         "K = 1 MlpKernels of hidden 64 / 128 / 256 on the 56-float observation, tile path on for 256, and an fp32 "
+                         "ArmKinematicVecEnv)")
+    return None
+
+
+def run_phase(env: ArmKinematicVecEnv, policy: Any, reset_options: dict[str, Any], *, one_launch: bool | None, what: str, **kw):
+    """one evaluation phase through run_episodes_fused when ``one_launch`` allows it and the phase is covered, else through run_episodes"""
+    mlp = _one_launch_mlp(policy, env, one_launch, what)
+    if mlp is not None:
+        return run_episodes_fused(env, mlp, reset_options, **kw)
+    return run_episodes(env, policy, reset_options, **kw)
 
 
 def run_episodes_fused(env: ArmKinematicVecEnv, mlp: Any, reset_options: dict[str, Any], *, ready_cfg=None, handoff_confirm_steps: int | None = None,
                        active: torch.Tensor | None = None, max_steps: int | None = None) -> tuple[dict[str, torch.Tensor], dict[str, torch.Tensor] | None]:
     """run_episodes with the whole env step in ONE launch (kp1_eval_step): the deterministic policy of ``mlp`` (an MlpKernels of hidden 64 /
     128: a K = 1 handle, or a population handle of K replicas over ``env``'s K x n envs, block k of the envs stepping under replica k's
-    weights), the fp64 norm of the clipped action, the env step and the per-episode bookkeeping.  The observations stay in the env's own
+    weights; or a K = 1 handle of hidden 256 with the tile path on, a training handle included: the step reads its packed weights and
+    touches no workspace), the fp64 norm of the clipped action, the env step and the per-episode bookkeeping.  The observations stay in the env's own
     buffer, which the launch reads and overwrites.  Same return value as run_episodes; every tensor not derived from the action norm is
-    bit-equal to it, and the action-norm tensors are the norm summed in index order (tests/test_population_eval_gpu.py)."""
+    bit-equal to it, and the action-norm tensors are the norm summed in index order (tests/test_population_eval_gpu.py,
+    tests/test_eval_step_h256_gpu.py)."""
     if not isinstance(env, ArmKinematicVecEnv):
         raise TypeError("run_episodes_fused drives an ArmKinematicVecEnv (kp1_eval_step steps its handle)")
     E = env.n_envs
@@ -438,8 +480,14 @@ def _mean(x) -> float:
 def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: PolicyFn | None, approach_cfg: kcfg.EnvConfig,
                                  finisher_cfg: kcfg.EnvConfig | None, episodes: int = 50, seed: int = 700001,
                                  stage_indices: list[int] | None = None, handoff_confirm_steps: int = 2, gate_config: dict[str, Any] | None = None,
-                                 artifact_root: str | Path | None = None, device: int = 0, obs_stride: int = 56) -> dict[str, Any]:
-    """evaluate_workspace_expansion_checkpoint with policies passed as callables (checkpoint loading is the caller's)."""
+                                 artifact_root: str | Path | None = None, device: int = 0, obs_stride: int = 56,
+                                 one_launch: bool | None = None) -> dict[str, Any]:
+    """evaluate_workspace_expansion_checkpoint with policies passed as callables (checkpoint loading is the caller's).
+
+    ``one_launch``: None (default) runs a phase through run_episodes_fused -- one launch per env step -- when its policy is an InferencePolicy /
+    PPO (or a bound ``predict`` of one) on a handle the step covers, and through run_episodes otherwise; False always takes run_episodes; True
+    raises ValueError for a phase that is not covered.  The two forms agree bit for bit except in the action-magnitude floats, which may
+    differ by an ulp (the norm is summed in index order instead of vector_norm's reduction)."""
     n_stages = approach_cfg.n_stages
     stages = stage_indices if stage_indices is not None else list(range(n_stages))
     stages = [int(np.clip(s, 0, n_stages - 1)) for s in stages]
@@ -451,8 +499,9 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
     env = ArmKinematicVecEnv(approach_cfg, E, device=device, seed=seed)
     if obs_stride != 56:
         env.set_obs_stride(obs_stride)
-    a_res, hand = run_episodes(env, approach_policy, {"initial_q": cat["initial_q"], "goal_q": cat["goal_q"], "goal_pose6": cat["goal_pose6"],
-                                                      "policy_mode": "approach"}, ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps)
+    a_res, hand = run_phase(env, approach_policy, {"initial_q": cat["initial_q"], "goal_q": cat["goal_q"], "goal_pose6": cat["goal_pose6"],
+                                                   "policy_mode": "approach"}, one_launch=one_launch, what="Approach", ready_cfg=r,
+                            handoff_confirm_steps=handoff_confirm_steps)
     env.close()
     final_ready, has_hand, src = _handoff_sources(a_res, hand, r)
     f_res = None
@@ -462,7 +511,7 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
             fenv.set_obs_stride(obs_stride)
         # rows without a handoff still need finite reset inputs; they are masked out of every result
         safe = {k: torch.where(has_hand[:, None], v, a_res[k]) for k, v in src.items()}
-        f_res, _ = run_episodes(fenv, finisher_policy, _handoff_options(safe, "dock"), active=has_hand)
+        f_res, _ = run_phase(fenv, finisher_policy, _handoff_options(safe, "dock"), one_launch=one_launch, what="Finisher", active=has_hand)
         fenv.close()
     cols = _eval_columns(a_res, final_ready, has_hand, f_res, handoff_confirm_steps)
     return _workspace_payload(cols, cat["goal_pose6"], approach_cfg=approach_cfg, stages=stages, episodes=episodes, seed=seed,
@@ -593,8 +642,9 @@ def evaluate_workspace_expansion_population(*, population: Any, finisher_policy:
     The suite is built once and tiled K times into one Approach handle of K x E envs; block k steps under replica k's weights as the
     population's own training handle holds them (no parameter copy, no repack), one kp1_eval_step launch per env step for all replicas.
     The Finisher phase is one run over all K x E rows with the shared Finisher policy (``finisher_policy``: an InferencePolicy, stepped in
-    one launch when its net is 64 / 128 wide and through run_episodes otherwise).  Episodes of different replicas run in lock step until
-    none of any replica is alive; a finished episode's bookkeeping is frozen, so the extra steps change nothing in its block."""
+    one launch when kp1_eval_step covers its handle -- 64 / 128 wide, or 2x256 on the tile kernels -- and through run_episodes otherwise).
+    Episodes of different replicas run in lock step until none of any replica is alive; a finished episode's bookkeeping is frozen, so the
+    extra steps change nothing in its block."""
     K = check_population_eval(population, artifact_roots)
     n_stages = approach_cfg.n_stages
     stages = stage_indices if stage_indices is not None else list(range(n_stages))

@@ -44,6 +44,7 @@ class MlpKernels:
         self._h = vp()
         self.obs_dim = int(obs_dim)                      # 56, or 80 with the route observation keys
         self.obs_pad = 64 if self.obs_dim <= 64 else 128   # row pitch the kernels also accept (zero padded)
+        self.fused = True                                # what set_fused last set (hidden 256: the tile kernels; the handle's default is on)
         if replicas == 1:
             native.check(L.kp1_mlp_create_ex(device.index or 0, hidden, self.obs_dim, self.max_batch, C.byref(self._h)))
         else:
@@ -61,6 +62,7 @@ class MlpKernels:
     def set_fused(self, on: bool) -> None:
         """hidden = 256: whole activation chain of a 32-row tile in one workgroup (default) vs the layer-wise kernels."""
         native.check(self.L.kp1_mlp_set_option(self._h, self.OPT_FUSED, int(bool(on))))
+        self.fused = bool(on)
 
     OPT_ACTOR_EXTRA_STEPS = 2
 

@@ -53,6 +53,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--learning-rate", type=float)
     p.add_argument("--log-every", type=int, default=1)
+    p.add_argument("--multi-launch-eval", action="store_true",
+                   help="with --seed: run the gate and final evaluations as the launch sequence per env step (evaluate.run_episodes) instead of "
+                        "the one-launch step (kp1_eval_step); the two forms agree bit for bit except in the action-magnitude floats "
+                        "(final / mean action magnitude), which may differ by an ulp (and a ready bit, should a norm sit on its threshold to the last bit)")
     return p
 
 
@@ -68,7 +72,7 @@ class WorkspaceEvalGate:
     envs; here the check runs after every PPO iteration (n_envs * n_steps timesteps), so evaluations land on iteration boundaries."""
 
     def __init__(self, *, artifact_root: Path, approach_cfg: kcfg.EnvConfig, finisher_policy, finisher_cfg: kcfg.EnvConfig | None, eval_interval: int,
-                 episodes: int, seed: int, stage_indices: list[int], gate_config: dict[str, Any], device: int = 0) -> None:
+                 episodes: int, seed: int, stage_indices: list[int], gate_config: dict[str, Any], device: int = 0, one_launch: bool | None = None) -> None:
         self.artifact_root = artifact_root
         self.approach_cfg, self.finisher_policy, self.finisher_cfg = approach_cfg, finisher_policy, finisher_cfg
         self.eval_interval = max(int(eval_interval), 1)
@@ -77,6 +81,7 @@ class WorkspaceEvalGate:
         self.stage_indices = list(stage_indices)
         self.gate_config = dict(gate_config)
         self.device = device
+        self.one_launch = one_launch        # evaluate.evaluate_workspace_expansion's switch (None: the one-launch step where covered)
         self.candidates_dir = artifact_root / "gate_candidates"
         self.eval_dir = artifact_root / "gate_evals"
         self.best_dir = artifact_root / "best_checkpoint"
@@ -124,7 +129,7 @@ class WorkspaceEvalGate:
         summary = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, finisher_policy=self.finisher_policy, approach_cfg=self.approach_cfg,
                                                   finisher_cfg=self.finisher_cfg, episodes=self.episodes, seed=self.seed, stage_indices=self.stage_indices,
                                                   gate_config=self.gate_config, artifact_root=self.eval_root(ppo.num_timesteps),
-                                                  device=self.device, obs_stride=ppo.obs_w)
+                                                  device=self.device, obs_stride=ppo.obs_w, one_launch=self.one_launch)
         return self.record(ppo, env_cfg, candidate, summary)
 
 
@@ -198,7 +203,7 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     finisher_policy, finisher_cfg = _load_finisher(ws, local_rank)
     gate_cfg = dict(ws.get("gate", {}) or {})
     if rank == 0 and not args.no_gate_callback and finisher_policy is not None:
-        gate = _make_gate(root, env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, local_rank)
+        gate = _make_gate(root, env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, local_rank, one_launch=False if args.multi_launch_eval else None)
 
     t0 = time.time()
     total = int(algo.get("total_timesteps", 100_000))
@@ -261,10 +266,12 @@ def _load_finisher(ws: dict[str, Any], device: int):
     return finisher_policy, finisher_cfg
 
 
-def _make_gate(root: Path, env_cfg: kcfg.EnvConfig, finisher_policy, finisher_cfg, ws: dict[str, Any], gate_cfg: dict[str, Any], device: int) -> WorkspaceEvalGate:
+def _make_gate(root: Path, env_cfg: kcfg.EnvConfig, finisher_policy, finisher_cfg, ws: dict[str, Any], gate_cfg: dict[str, Any], device: int,
+               one_launch: bool | None = None) -> WorkspaceEvalGate:
     return WorkspaceEvalGate(artifact_root=root, approach_cfg=env_cfg, finisher_policy=finisher_policy, finisher_cfg=finisher_cfg,
                              eval_interval=int(ws.get("eval_interval", 200_000)), episodes=int(ws.get("gate_eval_episodes", 24)),
-                             seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)), gate_config=gate_cfg, device=device)
+                             seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)), gate_config=gate_cfg, device=device,
+                             one_launch=one_launch)
 
 
 def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, n_envs: int, world: int, curriculum, finisher_policy, finisher_cfg,
@@ -285,7 +292,8 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, 
             final_eval = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, finisher_policy=finisher_policy, approach_cfg=env_cfg,
                                                          finisher_cfg=finisher_cfg, episodes=int(ws.get("final_eval_episodes", 80)),
                                                          seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)),
-                                                         gate_config=gate_cfg, artifact_root=root / "final_eval", device=device, obs_stride=ppo.obs_w)
+                                                         gate_config=gate_cfg, artifact_root=root / "final_eval", device=device, obs_stride=ppo.obs_w,
+                                                         one_launch=False if getattr(args, "multi_launch_eval", False) else None)
         final_eval = {k: v for k, v in final_eval.items() if k != "target_rows"}
         for name in ("stage_metrics.json", "workspace_failure_report.json", "best_model_selection_summary.json"):
             if (root / "final_eval" / name).exists():

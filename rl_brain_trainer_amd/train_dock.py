@@ -46,17 +46,22 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--eval-episodes", type=int, default=512)
     p.add_argument("--log-every", type=int, default=1)
+    p.add_argument("--one-launch-eval", action="store_true",
+                   help="run the final dock evaluation with the one-launch step (kp1_eval_step) instead of the launch sequence per env step "
+                        "(evaluate.run_episodes, the default here: the one-launch form has not been timed on this workload); the summaries "
+                        "are equal, the two forms differ only in the action-magnitude floats, by an ulp")
     return p
 
 
-def evaluate_dock(ppo: PPO, env_cfg: kcfg.EnvConfig, *, episodes: int, seed: int, device: int) -> dict[str, Any]:
-    """Deterministic dock evaluation on freshly sampled dock resets (eval_dock.py's summary keys that downstream scripts read)."""
+def evaluate_dock(ppo: PPO, env_cfg: kcfg.EnvConfig, *, episodes: int, seed: int, device: int, one_launch: bool | None = None) -> dict[str, Any]:
+    """Deterministic dock evaluation on freshly sampled dock resets (eval_dock.py's summary keys that downstream scripts read).
+    ``one_launch`` as in evaluate.evaluate_workspace_expansion; either way the resets are drawn by env.reset(options=None) from the env's RNG."""
     from . import evaluate as ev
 
     env = ArmKinematicVecEnv(env_cfg, episodes, device=device, seed=seed)
     if ppo.obs_w != 56:
         env.set_obs_stride(ppo.obs_w)
-    res, _ = ev.run_episodes(env, ppo.predict, None)
+    res, _ = ev.run_phase(env, ppo.predict, None, one_launch=one_launch, what="dock")
     env.close()
     succ = res["success"].float()
     return {"episodes": int(episodes), "success_rate": float(succ.mean()), "mean_final_position_error": float(res["final_position_error"].mean()),
@@ -144,7 +149,8 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, cfg: dic
     population replica)"""
     latest = root / "model_latest"
     checkpoint.save(latest, ppo, env_cfg)
-    eval_summary = evaluate_dock(ppo, env_cfg, episodes=args.eval_episodes, seed=seed + 10_000, device=device)
+    eval_summary = evaluate_dock(ppo, env_cfg, episodes=args.eval_episodes, seed=seed + 10_000, device=device,
+                                 one_launch=None if getattr(args, "one_launch_eval", False) else False)
     (root / "dock_eval").mkdir(exist_ok=True)
     (root / "dock_eval" / "dock_eval_summary.json").write_text(json.dumps(eval_summary, indent=2))
     summary = {"policy_type": "dock", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "config": cfg, "model_path": str(latest) + ".zip",
