@@ -205,7 +205,8 @@ int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t m
  *     [K][n][...];
  *   kp1_mlp_loss_grad: idx (required) is int64 [K][n], row indices into the shared obs / actions / old_log_prob / advantages / returns
  *     buffers; grad_out [K][num_params]; stats_out [K][4]; adv_stats_dev [K][2] (mean, 1/(std + 1e-8) of each replica's minibatch);
- *   kp1_mlp_forward_env_step, kp1_mlp_time_kernels and the KP1_MLP_OPT_BF16X3_WGRAD option return KP1_ERR_UNSUPPORTED. */
+ *   kp1_mlp_forward_env_step: the layer-wise form below, replica k owning rows [k n, (k + 1) n) of every buffer;
+ *   kp1_mlp_time_kernels and the KP1_MLP_OPT_BF16X3_WGRAD option return KP1_ERR_UNSUPPORTED. */
 #define KP1_MLP_MAX_REPLICAS 16
 int kp1_mlp_create_population(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batch, int32_t replicas, kp1_mlp** out);
 /* K of the handle (1 for kp1_mlp_create / _create_ex), 0 for NULL */
@@ -238,8 +239,20 @@ int kp1_mlp_forward(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n,
 /* One rollout step in ONE launch: policy.forward on the current observations of ALL envs of `env` (row m = env m; obs f32 [N][obs_stride]),
  * Gaussian sampling, then VecEnv.step(clip(action)) of every env with the auto-reset -- SB3's collect_rollouts body
  * (on_policy_algorithm.py: policy(obs) -> clip -> env.step) without the action round trip through HBM and without a launch for the env.
- * Same results as kp1_mlp_forward followed by kp1_step (tests/test_ppo_kernels_gpu.py).  fp32 handles, hidden 256, 56-float observations;
- * reward components must be off.  value / log_prob may be NULL (value NULL skips the value net); terminal_obs may be NULL. */
+ * Same results, bit for bit, as kp1_mlp_forward followed by kp1_step (tests/test_ppo_kernels_gpu.py, tests/test_rollout_step_layerwise_gpu.py).
+ * fp32 env handles in approach or dock mode, 56-float observations (obs_stride 56 or 64); reward components must be off.  value / log_prob may
+ * be NULL (value NULL skips the value net); terminal_obs may be NULL.
+ *   hidden 256       a K = 1 handle with the tile path on (the rollout form of the 2x256 inference tile); env handles with bound population
+ *                    stages or dock stage records are refused.
+ *   hidden 64 / 128  a K = 1 or a population handle (rollout_step_kernel: grid = row tiles x K x {policy net + env step, value net}).  The env
+ *                    handle holds K * n envs, row m of replica k being env k n + m; noise and every output are replica-major.  A handle with
+ *                    bound population stages (kp1_bind_population_stages) or dock stage records (kp1_dock_curriculum_create_population) is
+ *                    accepted when its replica count is K: env i then resets / steps on the stage of replica i / n, as kp1_step does.  On an
+ *                    unbound handle the replicas share the host stage.  noise is required, and next_obs and terminal_obs must not overlap obs anywhere
+ *                    (the value net's workgroups read rows that the policy net's workgroups would overwrite).
+ * Refused before any launch: the 80-float route observation, f64 env handles, recorded reward components, modes other than approach and
+ * dock, a replica-count mismatch, an env count that is no multiple of K, next_obs == obs or any overlap of next_obs / terminal_obs with obs (layer-wise form), different devices, NULL required
+ * arguments, obs_stride other than 56 or 64.  (A kp1_route handle is not a kp1_env and has no step of its own here.) */
 int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t obs_stride, const float* noise, float* value, float* action,
                              float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream);
 

@@ -664,6 +664,25 @@ int ensure_scratch(kp1_env* e) {
 // C ABI
 // ============================================================================================
 namespace kp1 {
+int env_step_args_f32_population(kp1_env* e, void* out, size_t out_bytes, float* obs, void* reward, uint8_t* done, float* terminal_obs,
+                                 int auto_reset, int* mode, int64_t* n_envs, int* device, int* pop_replicas, int* pop_form) {
+  if (!e || !out) return fail(KP1_ERR_INVALID, "NULL argument");
+  if (e->real_type != KP1_REAL_F32) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step runs on the fp32 handle");
+  if (e->comps_enabled && e->comps) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step does not record reward components");
+  if (out_bytes != sizeof(StepArgs<float>)) return fail(KP1_ERR_INVALID, "StepArgs<float> layout mismatch between translation units");
+  // the forms launch_step chooses between
+  if (e->pop_dock_states && e->mode != KP1_MODE_DOCK) return fail(KP1_ERR_UNSUPPORTED, "a dock population env handle steps in the dock mode only");
+  if (e->pop_states && e->mode != KP1_MODE_APPROACH) return fail(KP1_ERR_UNSUPPORTED, "a population env handle steps in the approach mode only");
+  const StepArgs<float> a = make_step_args<float>(e, nullptr, obs, reward, done, terminal_obs, auto_reset);
+  std::memcpy(out, &a, sizeof a);
+  *mode = e->mode;
+  *n_envs = e->n;
+  *device = e->device;
+  *pop_replicas = (e->pop_dock_states || e->pop_states) ? e->pop_replicas : 0;
+  *pop_form = (e->pop_dock_states || (e->pop_states && e->cfg.curriculum_enabled)) ? 1 : 0;
+  return KP1_OK;
+}
+
 int env_step_args_f32(kp1_env* e, void* out, size_t out_bytes, const void* actions, float* obs, void* reward, uint8_t* done, float* terminal_obs,
                       int auto_reset, int* mode, int64_t* n_envs, int* device) {
   if (!e || !out) return fail(KP1_ERR_INVALID, "NULL argument");
@@ -671,13 +690,10 @@ int env_step_args_f32(kp1_env* e, void* out, size_t out_bytes, const void* actio
   if (e->comps_enabled && e->comps) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step does not record reward components");
   if (e->pop_states) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step has no per-replica stage (population env handle)");
   if (e->pop_dock_states) return fail(KP1_ERR_UNSUPPORTED, "the fused policy + env step has no per-replica dock stage (dock population env handle)");
-  if (out_bytes != sizeof(StepArgs<float>)) return fail(KP1_ERR_INVALID, "StepArgs<float> layout mismatch between translation units");
-  const StepArgs<float> a = make_step_args<float>(e, actions, obs, reward, done, terminal_obs, auto_reset);
-  std::memcpy(out, &a, sizeof a);
-  *mode = e->mode;
-  *n_envs = e->n;
-  *device = e->device;
-  return KP1_OK;
+  int pop_replicas = 0, pop_form = 0;   // both 0: the population refusals above
+  const int rc = env_step_args_f32_population(e, out, out_bytes, obs, reward, done, terminal_obs, auto_reset, mode, n_envs, device, &pop_replicas, &pop_form);
+  if (rc == KP1_OK) static_cast<StepArgs<float>*>(out)->actions = (const float*)actions;
+  return rc;
 }
 }  // namespace kp1
 

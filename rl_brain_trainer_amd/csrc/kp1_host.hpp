@@ -49,6 +49,11 @@ inline hipError_t launch_status() {
 // rollout kernel that runs the policy forward and the env step in one launch.  Fails for fp64 handles and while reward components are on.
 int env_step_args_f32(kp1_env* env, void* out, size_t out_bytes, const void* actions, float* obs, void* reward, uint8_t* done, float* terminal_obs,
                       int auto_reset, int* mode, int64_t* n_envs, int* device);
+// The same block for the rollout kernel of the layer-wise widths (rollout_step_kernel), which also steps population env handles: accepts a
+// handle with bound population stages or dock stage records, reports its replica count (0: unbound) and whether kp1_step would launch the
+// population form of the step kernel on it (pop_form).  Fails as above, and for a bound handle whose mode kp1_step refuses.
+int env_step_args_f32_population(kp1_env* env, void* out, size_t out_bytes, float* obs, void* reward, uint8_t* done, float* terminal_obs,
+                                 int auto_reset, int* mode, int64_t* n_envs, int* device, int* pop_replicas, int* pop_form);
 }  // namespace kp1
 
 #define HIP_TRY(expr)                                                                                              \

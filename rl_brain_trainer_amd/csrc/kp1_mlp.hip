@@ -1432,6 +1432,7 @@ __global__ void anchor_count_kernel(int* __restrict__ actor_extra) { *actor_extr
 
 #include "kp1_env_step.inc"
 #include "kp1_eval_step.inc"
+#include "kp1_rollout_step.inc"
 #include "kp1_mlp_tile.inc"
 #include "kp1_mlp_fused.inc"
 
@@ -1992,10 +1993,64 @@ int kp1_mlp_forward(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n,
   return KP1_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// kp1_mlp_forward_env_step on an Hp = 128 handle (hidden 64 / 128, K = 1 or a population): rollout_step_kernel
+int forward_env_step_layers(kp1_mlp* m, kp1_env* env, const float* obs, int32_t obs_stride, const float* noise, float* value, float* action,
+                            float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, hipStream_t stream) {
+  if (m->L.INP != ES_INP)
+    return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_env_step needs the 56-float observation (padded to 64); the 80-float route observation takes the launch sequence");
+  if (!noise) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_forward_env_step (the layer-wise form samples: noise is required)");
+  if (obs_stride != m->L.IN && obs_stride != m->L.INP) return fail(KP1_ERR_INVALID, "obs_stride must be 56 or 64");
+  if (next_obs == obs) return fail(KP1_ERR_INVALID, "kp1_mlp_forward_env_step: the layer-wise form reads obs from two workgroups per tile, next_obs must not be obs");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  RolloutStepArgs a{};
+  int mode = 0, device = 0, pop_replicas = 0, pop_form = 0;
+  int64_t n_envs = 0;
+  // refuses f64 handles, recorded reward components and a bound handle in a mode kp1_step refuses
+  rc = kp1::env_step_args_f32_population(env, &a.env, sizeof a.env, next_obs, reward, done, terminal_obs, 1, &mode, &n_envs, &device, &pop_replicas, &pop_form);
+  if (rc != KP1_OK) return rc;
+  if (device != m->device) return fail(KP1_ERR_INVALID, "the env handle and the MLP workspace live on different devices");
+  if (mode != KP1_MODE_APPROACH && mode != KP1_MODE_DOCK) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_env_step steps the approach or the dock mode");
+  if (pop_replicas > 0 && pop_replicas != m->K)
+    return fail(KP1_ERR_INVALID, "kp1_mlp_forward_env_step: the env handle's population replica count differs from the MLP handle's");
+  if (n_envs <= 0 || n_envs % m->K != 0) return fail(KP1_ERR_INVALID, "kp1_mlp_forward_env_step: the env count must be a multiple of the handle's replica count");
+  if (n_envs / m->K > m->max_batch) return fail(KP1_ERR_INVALID, "more envs than the workspace max_batch");
+  {  // the value net's workgroups read obs rows while the policy net's write next_obs / terminal_obs rows of other tiles: no overlap at all
+    const float* obs_end = obs + n_envs * obs_stride;
+    const int64_t out_floats = n_envs * a.env.obs_stride;
+    auto overlaps = [&](const float* p) { return p && p < obs_end && obs < p + out_floats; };
+    if (overlaps(next_obs) || overlaps(terminal_obs))
+      return fail(KP1_ERR_INVALID, "kp1_mlp_forward_env_step: next_obs and terminal_obs must not overlap obs in the layer-wise form");
+  }
+  const int Hp = m->Hp, INP = m->L.INP;
+  a.obs = obs; a.obs_stride = obs_stride;
+  a.w1 = m->k.w1p; a.b1 = m->k.b1; a.w2 = m->k.w2; a.b2 = m->k.b2; a.w3 = m->k.w3; a.b3 = m->k.b3; a.log_std = m->k.log_std;
+  a.r_w1 = (unsigned)(2 * Hp * INP); a.r_w2 = (unsigned)(2 * Hp * Hp); a.r_b = (unsigned)(2 * Hp); a.r_w3 = (unsigned)(HEADS * Hp); a.r_b3 = (unsigned)HEADS;
+  a.n_w1 = (unsigned)(Hp * INP); a.n_w2 = (unsigned)(Hp * Hp); a.n_b = (unsigned)Hp;
+  a.noise = noise; a.value = value; a.action = action; a.log_prob = log_prob;
+  a.n = (int)(n_envs / m->K);
+  a.Kreal = obs_stride >= INP ? INP : m->L.IN;
+  const dim3 grid((unsigned)((a.n + ES_BM - 1) / ES_BM), (unsigned)m->K, value ? 2u : 1u);
+  const bool pop = pop_form != 0, dock = mode == KP1_MODE_DOCK;
+  if (pop && dock) hipLaunchKernelGGL((rollout_step_kernel<KP1_MODE_DOCK, true>), grid, dim3(ES_NTH), 0, stream, a);
+  else if (pop) hipLaunchKernelGGL((rollout_step_kernel<KP1_MODE_APPROACH, true>), grid, dim3(ES_NTH), 0, stream, a);
+  else if (dock) hipLaunchKernelGGL((rollout_step_kernel<KP1_MODE_DOCK, false>), grid, dim3(ES_NTH), 0, stream, a);
+  else hipLaunchKernelGGL((rollout_step_kernel<KP1_MODE_APPROACH, false>), grid, dim3(ES_NTH), 0, stream, a);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+}  // namespace
+
+extern "C" {
+
 int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t obs_stride, const float* noise, float* value, float* action,
                              float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream) {
   if (!m || !env || !obs || !action || !next_obs || !reward || !done) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_forward_env_step");
-  if (m->K > 1) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_env_step is not available on population handles");
+  // hidden 64 / 128 (K = 1 or a population): the layer-wise form; every population handle has this layout
+  if (m->Hp == ES_HP) return forward_env_step_layers(m, env, obs, obs_stride, noise, value, action, log_prob, next_obs, reward, done, terminal_obs, (hipStream_t)stream);
   if (!(m->fused && m->Hp == FU_HP) || m->L.INP != 64)
     return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_env_step needs the 2x256 tile kernels and the 56-float observation (padded to 64)");
   if (obs_stride != m->L.IN && obs_stride != m->L.INP) return fail(KP1_ERR_INVALID, "obs_stride must be 56 or 64");

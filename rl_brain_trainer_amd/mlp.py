@@ -124,8 +124,19 @@ class MlpKernels:
         native.check(self.L.kp1_mlp_forward(self._h, _p(obs), stride, n, _p(noise), _p(mean), _p(value), _p(action), _p(clipped), _p(log_prob), self._stream()))
 
     def forward_env_step(self, env, obs: torch.Tensor, *, noise, value, action, log_prob, next_obs, reward, done, terminal_obs) -> None:
-        """One rollout step in one launch (kp1_mlp_forward_env_step): policy.forward on `obs` (row m = env m of `env`, an fp32
-        ArmKinematicVecEnv), sampling, and VecEnv.step of every env with auto-reset, written into the caller's rollout buffers."""
+        """One rollout step in one launch (kp1_mlp_forward_env_step): policy.forward on `obs` (row m = env m of `env`), sampling, and
+        VecEnv.step of every env with auto-reset, written into the caller's rollout buffers.
+
+        hidden 256: a K = 1 handle on the tile kernels and a plain fp32 ArmKinematicVecEnv.  hidden 64 / 128: a K = 1 or a population handle
+        (replica k owns rows [k n, (k + 1) n) of every buffer, n = env.n_envs / K) and an fp32 ArmKinematicVecEnv or an
+        ArmKinematicPopulationVecEnv of K replicas whose bound trackers give each replica its own stage; ``next_obs`` and ``terminal_obs`` must not overlap ``obs``.
+        ``value``, ``log_prob`` and ``terminal_obs`` may be None.  Refused: the 80-float route observation and route envs (they have no
+        kp1_env step of their own), f64 envs, recorded reward components, modes other than approach / dock, a replica-count mismatch."""
+        from .vec_env import ArmKinematicVecEnv
+
+        if not isinstance(env, ArmKinematicVecEnv):
+            raise TypeError(f"forward_env_step steps an ArmKinematicVecEnv or an ArmKinematicPopulationVecEnv handle; {type(env).__name__} "
+                            "(route envs wrap their base env in a route step of their own) takes forward + step_into")
         assert obs.is_contiguous() and obs.dtype == torch.float32 and obs.shape[0] == env.n_envs
         native.check(self.L.kp1_mlp_forward_env_step(self._h, env._handle, _p(obs), obs.shape[1], _p(noise), _p(value), _p(action), _p(log_prob),
                                                      _p(next_obs), _p(reward), _p(done), _p(terminal_obs), self._stream()))

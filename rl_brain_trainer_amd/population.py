@@ -25,13 +25,14 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import os
 import time
 from typing import Any, Callable
 
 import torch
 
 from . import native
-from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig
+from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig, fused_rollout_covered
 
 MAX_REPLICAS = 16     # KP1_MLP_MAX_REPLICAS
 
@@ -348,7 +349,24 @@ class OneHandlePopulationPPO(PopulationPPO):
         if which is None or which:
             self.obs_buf[0].copy_(self.pop_env.reset())
 
+    # whether the env handle is one kp1_mlp_forward_env_step steps (ApproachPopulationPPO, DockPopulationPPO: an ArmKinematicPopulationVecEnv;
+    # the route env has no kp1_env step of its own and the 80-float observation, so RoutePopulationPPO keeps the launch sequence)
+    fused_env_type_ok = False
+
+    @property
+    def _fused_env_step(self) -> bool:
+        env = self.pop_env
+        return fused_rollout_covered(self.fused_env_type_ok, env.dtype, self.cfg.hidden, self.obs_dim,
+                                     getattr(env, "_reward_components_on", False), os.environ.get("KP1_FUSED_ROLLOUT"),
+                                     default_on=True)     # measured on both one-handle trainers
+
     def _policy_env_step(self, t: int) -> None:
+        if self._fused_env_step:
+            # all replicas' policy forward + sampling + env step (auto-reset on each replica's own stage) in ONE launch
+            self._mlp.forward_env_step(self.pop_env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
+                                       log_prob=self.logp_buf[t], next_obs=self.obs_buf[t + 1], reward=self.rew_buf[t], done=self.done_buf[t],
+                                       terminal_obs=self.term_obs_buf[t])
+            return
         self._mlp.forward(self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t], clipped=self.clip_act,
                           log_prob=self.logp_buf[t])
         self.pop_env.step_into(self.clip_act, self.obs_buf[t + 1], self.rew_buf[t], self.done_buf[t], self.term_obs_buf[t], True)
@@ -454,6 +472,8 @@ class ApproachPopulationPPO(OneHandlePopulationPPO):
     launch (and a wave).  Replica k is bit-identical to ``PPO(ArmKinematicVecEnv(..., seed=s_k), curriculum=PointCurriculum)`` on the same
     config (tests/test_approach_population_gpu.py), and to replica k of the K-handle ``PopulationPPO``."""
 
+    fused_env_type_ok = True
+
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
                  teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:
         from .curriculum import PointCurriculumPopulation
@@ -521,6 +541,8 @@ class DockPopulationPPO(OneHandlePopulationPPO):
     plain dock step over K N envs.  Replica k is bit-identical to ``PPO(ArmKinematicVecEnv(..., seed=s_k), curriculum=DockReverseCurriculum)``
     on the same config (tests/test_dock_population_gpu.py).  ``load_init_checkpoint`` / ``load_init_checkpoints`` start the replicas from one
     checkpoint or one each (train_dock --seeds --resume-from).  The caller owns (and closes) the env and the tracker."""
+
+    fused_env_type_ok = True
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
                  teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:

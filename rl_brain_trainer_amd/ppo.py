@@ -452,6 +452,23 @@ def restore_saved_hyperparameters(cfg: "PPOConfig", data: dict[str, Any]) -> dic
     return taken
 
 
+# The widths kp1_mlp_forward_env_step covers: 256 (the tile kernels' rollout form), 64 / 128 (rollout_step_kernel)
+FUSED_ROLLOUT_WIDTHS = (64, 128, 256)
+
+
+def fused_rollout_covered(env_type_ok: bool, dtype: Any, hidden: int, obs_dim: int, components_on: bool, env_var: str | None, *,
+                          default_on: bool = True) -> bool:
+    """Whether a rollout step runs as ONE launch (policy forward + sampling + env step with auto-reset) instead of forward + step_into.
+    ``env_type_ok``: the env is one the entry point steps (the plain fp32 vectorised env, or an Approach / dock population env on one
+    handle); ``dtype``: the env's real type; ``obs_dim``: 56 is covered, the 80-float route observation is not; ``components_on``: recorded
+    reward components need the env's own step kernel; ``env_var``: KP1_FUSED_ROLLOUT ("0": the launch sequence, kept as the A/B and test
+    reference; any other value: the one-launch form wherever it exists; None = unset: ``default_on``, the calling trainer's measured
+    default -- on only where its rollout beat the launch sequence by more than the run-to-run spread)."""
+    if not env_type_ok or dtype != torch.float32 or hidden not in FUSED_ROLLOUT_WIDTHS or obs_dim > 64 or components_on:
+        return False
+    return bool(default_on) if env_var is None else env_var != "0"
+
+
 class PPO:
     """One PPO run.  PopulationPPO (population.py) is the same engine with K replicas: everything per replica below is a list (``envs``,
     ``curricula``, ``policies``, ``gens``) or a replica axis (rollout columns [k N, (k + 1) N), ``perm[k]``, ``stats_dev[k]``); here K = 1."""
@@ -480,11 +497,17 @@ class PPO:
             self._record_stage = None
             if curriculum is not None and getattr(curriculum, "needs_episode_records", False):
                 self._record_stage = torch.zeros((self.done_chunk, N), dtype=torch.uint8, device=dev)
-        # one launch per rollout step for policy forward + env step where the env is the plain fp32 vectorised env and the tile kernels run
-        # (KP1_FUSED_ROLLOUT=0: the two-launch form, kept as the A/B and test reference)
-        self._fused_env_step = bool(type(env) is ArmKinematicVecEnv and env.dtype == torch.float32 and cfg.hidden == 256
-                                    and self.obs_dim <= 64 and not getattr(env, "_reward_components_on", False)
-                                    and os.environ.get("KP1_FUSED_ROLLOUT", "1") != "0")
+
+    @property
+    def _fused_env_step(self) -> bool:
+        """whether the next rollout step is the one-launch form (fused_rollout_covered on the env's current state: the reward-component
+        switch may be thrown after construction, which bumps ``launch_args_version`` and re-captures the rollout)"""
+        env = self.env
+        # default: hidden 256 (measured, DESIGN section 4.5); the single-seed PPO at hidden 64 / 128 was not measured and opts in with
+        # KP1_FUSED_ROLLOUT=1 (DESIGN section 21)
+        return fused_rollout_covered(type(env) is ArmKinematicVecEnv, env.dtype, self.cfg.hidden, self.obs_dim,
+                                     getattr(env, "_reward_components_on", False), os.environ.get("KP1_FUSED_ROLLOUT"),
+                                     default_on=self.cfg.hidden == 256)
 
     def _setup(self, cfg: PPOConfig, seeds: list[int], envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool, *,
                min_batch: int, stacked: bool) -> None:

@@ -1,0 +1,471 @@
+"""One-launch rollout step of the layer-wise widths (kp1_mlp_forward_env_step on a hidden 64 / 128 handle, rollout_step_kernel), on the GPU:
+bit for bit the launch sequence kp1_mlp_forward + kp1_step on a twin env -- K = 1, Approach and dock populations on one env handle with
+promoting trackers, and the trainers that use it (graphs on).  Every comparison is torch.equal / np.array_equal."""
+from __future__ import annotations
+
+import ctypes as C
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, load_golden_config
+from rl_brain_trainer_amd import config as kcfg
+from rl_brain_trainer_amd import native
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda", 0)
+KP1_ERR_INVALID, KP1_ERR_UNSUPPORTED = -1, -4     # include/kp1.h
+DOCK_CFG = "dock_workspace_handoff_noop_ft_12env_raw"     # 36-step episodes, handoff-state resets from the golden buffer
+BUFFERS = ("obs_buf", "act_buf", "logp_buf", "val_buf", "rew_buf", "done_buf", "adv_buf", "ret_buf", "term_obs_buf")
+
+
+def _approach_cfg():
+    cfg = kcfg.to_env_config(kcfg.load_workspace_expansion_config(kcfg.builtin_config_dir() / "workspace_expansion_bigtrain.yaml"))
+    assert cfg.c.curriculum_enabled and cfg.n_stages >= 8 and cfg.c.termination.max_episode_steps == 96
+    return cfg
+
+
+def _bytes(obj) -> bytes:
+    return bytes(C.string_at(C.addressof(obj), C.sizeof(obj)))
+
+
+def _dock_stages(min_episodes: int) -> list[dict]:
+    """a synthetic reverse curriculum that promotes on every `min_episodes` finished episodes (threshold 0) and overrides every value a stage
+    can hold, the handoff filter included"""
+    return [
+        {"name": "close", "min_episodes": min_episodes, "window_episodes": 4, "success_rate_threshold": 0.0, "dock_residual_action_limit": 0.2,
+         "close_bucket_probability": 1.0, "close_bucket_max_pos_error_m": 0.003, "handoff_state_probability": 0.3,
+         "init_q_noise": [0.002] * 7},
+        {"name": "mid", "min_episodes": min_episodes, "success_rate_threshold": 0.0, "action_delta_scale": 0.012, "close_bucket_probability": 0.5,
+         "close_init_q_noise": [0.004, 0.006, 0.008, 0.006, 0.004, 0.004, 0.003], "close_bucket_max_ori_error_rad": 0.03,
+         "close_bucket_min_pos_error_m": 0.001, "handoff_state_probability": 0.6, "handoff_state_max_action_l2": 0.3},
+        {"name": "wide", "dock_delta_q_change_limit_scale": 0.5, "dock_residual_action_limit": 0.35, "close_bucket_probability": 0.1,
+         "handoff_state_probability": 0.9, "handoff_state_max_action_l2": 0.5},
+    ]
+
+
+def _random_policy(hidden: int, K: int, seed: int) -> torch.Tensor:
+    """[K, P] parameters: orthogonal weights, an action head large enough for the mean to matter, random biases, log_std well away from 0"""
+    from rl_brain_trainer_amd.ppo import ActorCritic
+
+    g = torch.Generator(device="cpu").manual_seed(1000 + seed)
+    rows = []
+    for k in range(K):
+        pol = ActorCritic(hidden, DEV, seed=seed + k)
+        pol.views["action_net.weight"].mul_(25.0)
+        for name, v in pol.views.items():
+            if name.endswith("bias"):
+                v.copy_((torch.rand(v.shape, generator=g) * 0.2 - 0.1).to(DEV))
+        pol.views["log_std"].copy_((-1.3 + 1.1 * torch.rand(7, generator=g)).to(DEV))
+        rows.append(pol.flat.clone())
+    return torch.stack(rows).contiguous()
+
+
+def _mlp(hidden: int, K: int, max_batch: int, seed: int):
+    from rl_brain_trainer_amd.mlp import MlpKernels
+
+    mlp = MlpKernels(hidden, DEV, max_batch=max_batch, replicas=K)
+    flat = _random_policy(hidden, K, seed)
+    mlp.pack(flat if K > 1 else flat[0].contiguous())
+    return mlp, flat
+
+
+def _step_parity(mlp, env_a, env_b, steps: int, *, after_a=None, after_b=None, with_value: bool = True, with_log_prob: bool = True,
+                 seed: int = 0) -> int:
+    """Twin A takes forward_env_step, twin B forward + step_into(auto_reset=True), on the same noise; every output of every step, then every
+    info plane and the PCG64 words.  ``after_*``: the tracker launch that follows a step (given its done bytes).  Returns the number of
+    finished episodes."""
+    n, w = env_a.n_envs, env_a.obs_stride
+    z = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=DEV)   # noqa: E731
+    obs_a, obs_b = env_a.reset().clone(), env_b.reset().clone()
+    assert obs_a.shape == (n, w) and torch.equal(obs_a, obs_b)
+    gen = torch.Generator(device=DEV).manual_seed(99 + seed)
+    finished = 0
+    for t in range(steps):
+        noise = torch.randn((n, 7), generator=gen, device=DEV)
+        a = {"value": z(n), "action": z(n, 7), "log_prob": z(n), "next_obs": z(n, w), "reward": z(n), "done": z(n, dt=torch.uint8),
+             "terminal_obs": z(n, w)}
+        b = {k: torch.zeros_like(v) for k, v in a.items()}
+        clipped = z(n, 7)
+        mlp.forward_env_step(env_a, obs_a, noise=noise, value=a["value"] if with_value else None, action=a["action"],
+                             log_prob=a["log_prob"] if with_log_prob else None, next_obs=a["next_obs"], reward=a["reward"], done=a["done"],
+                             terminal_obs=a["terminal_obs"])
+        mlp.forward(obs_b, noise=noise, value=b["value"], action=b["action"], clipped=clipped, log_prob=b["log_prob"])
+        env_b.step_into(clipped, b["next_obs"], b["reward"], b["done"], b["terminal_obs"], True)
+        if after_a is not None:
+            after_a(a["done"])
+            after_b(b["done"])
+        if not with_value:
+            assert not a["value"].any()
+            b["value"].zero_()
+        if not with_log_prob:
+            assert not a["log_prob"].any()
+            b["log_prob"].zero_()
+        for k in a:
+            assert torch.equal(a[k], b[k]), (t, k)
+        finished += int((b["done"] & 3 != 0).sum())
+        obs_a, obs_b = a["next_obs"], b["next_obs"]
+    ia, ib = env_a.info(), env_b.info()
+    for k in ib:
+        assert torch.equal(ia[k], ib[k]), k
+    assert np.array_equal(env_a.rng_state(), env_b.rng_state())
+    return finished
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1. K = 1
+@pytest.mark.parametrize("E", [1, 32, 33, 70])
+@pytest.mark.parametrize("pitch", [56, 64])
+@pytest.mark.parametrize("mode", ["approach", "dock"])
+@pytest.mark.parametrize("hidden", [64, 128])
+def test_step_parity_single(hidden, mode, pitch, E):
+    """E = 1: one live row; 32: one full tile; 33: a second tile with one row; 70: three tiles, the last ragged.  Approach: stage 5 of
+    workspace_expansion_bigtrain, 200 steps of 96-step episodes; dock: 80 steps of 36-step episodes -- every env auto-resets at least twice.
+    One case runs without the value plane and one without log_prob."""
+    from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv
+
+    envs = []
+    for _ in range(2):
+        if mode == "approach":
+            env = ArmKinematicVecEnv(_approach_cfg(), E, seed=31)
+            env.set_curriculum_stage(5)
+        else:
+            env = ArmKinematicVecEnv(load_golden_config(DOCK_CFG), E, seed=31)
+        env.set_obs_stride(pitch)
+        envs.append(env)
+    mlp, _ = _mlp(hidden, 1, 128, seed=hidden + E)
+    no_value = (hidden, mode, pitch, E) == (64, "approach", 64, 33)
+    no_logp = (hidden, mode, pitch, E) == (128, "dock", 56, 70)
+    finished = _step_parity(mlp, envs[0], envs[1], 200 if mode == "approach" else 80, with_value=not no_value, with_log_prob=not no_logp, seed=E)
+    assert finished >= 2 * E
+    mlp.close()
+    for env in envs:
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2. Approach population
+@pytest.mark.parametrize("N", [16, 40, 96])
+@pytest.mark.parametrize("hidden", [64, 128])
+def test_step_parity_approach_population(hidden, N):
+    """K = 3 replicas on stages [0, 2, 5] with a promoting population tracker (threshold 0, a promotion per N finished episodes): N = 16 a
+    half-empty tile per replica, 40 a ragged second tile, 96 full tiles.  The auto-reset of env i reads the stage of replica i / N."""
+    from rl_brain_trainer_amd.curriculum import PointCurriculumPopulation
+    from rl_brain_trainer_amd.vec_env import ArmKinematicPopulationVecEnv
+
+    seeds, initial = [7, 8, 9], [0, 2, 5]
+    cfg = _approach_cfg()
+    kw = {"success_rate_threshold": 0.0, "window_episodes": 16, "min_episodes_per_stage": N, "max_stage_index": cfg.n_stages - 1}
+    envs, curs = [], []
+    for _ in range(2):
+        env = ArmKinematicPopulationVecEnv(_approach_cfg(), seeds, N)
+        cur = PointCurriculumPopulation(**kw, initial_stage_indices=initial)
+        cur.attach(env)
+        env.set_obs_stride(64)
+        envs.append(env)
+        curs.append(cur)
+    mlp, _ = _mlp(hidden, 3, 128, seed=hidden + N)
+    finished = _step_parity(mlp, envs[0], envs[1], 300, after_a=lambda d: curs[0].observe(d, N), after_b=lambda d: curs[1].observe(d, N), seed=N)
+    assert finished >= 3 * 3 * N
+    for k in range(3):
+        assert _bytes(curs[0].read(k)) == _bytes(curs[1].read(k)), k
+        assert curs[0].read(k).stage_index != initial[k], (k, "the stage never moved")
+    mlp.close()
+    for cur, env in zip(curs, envs):
+        cur.close()
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3. dock population
+@pytest.mark.parametrize("N", [6, 40])
+@pytest.mark.parametrize("hidden", [64, 128])
+def test_step_parity_dock_population(hidden, N):
+    """K = 2 replicas of the dock env with a promoting reverse curriculum: env i steps and resets with the live stage record of replica i / N"""
+    from rl_brain_trainer_amd import finisher_tools as ft
+    from rl_brain_trainer_amd.vec_env import ArmKinematicPopulationVecEnv
+
+    seeds = [7, 8]
+    envs, curs = [], []
+    for _ in range(2):
+        env = ArmKinematicPopulationVecEnv(load_golden_config(DOCK_CFG), seeds, N, mode="dock")
+        cur = ft.DockReverseCurriculumPopulation(stages=_dock_stages(N), window_episodes=4, n_replicas=2, handoff_base_dirs=(GOLDEN,))
+        cur.attach(env)
+        env.set_obs_stride(64)
+        envs.append(env)
+        curs.append(cur)
+    mlp, _ = _mlp(hidden, 2, 128, seed=hidden + N)
+    finished = _step_parity(mlp, envs[0], envs[1], 120, after_a=lambda d: curs[0].observe(d, N), after_b=lambda d: curs[1].observe(d, N), seed=N)
+    assert finished >= 2 * 3 * N
+    for k in range(2):
+        assert _bytes(curs[0].read(k)) == _bytes(curs[1].read(k)), k
+        assert int(curs[0].read(k).stage_index) > 0, (k, "the stage never moved")
+    live = [curs[0].live_records(), curs[1].live_records()]
+    for k in range(2):
+        assert _bytes(live[0][k]) == _bytes(live[1][k]), k
+    mlp.close()
+    for cur, env in zip(curs, envs):
+        cur.close()
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4. trainers
+def _count_fused_calls(monkeypatch) -> list[int]:
+    from rl_brain_trainer_amd.mlp import MlpKernels
+
+    calls = [0]
+    orig = MlpKernels.forward_env_step
+
+    def counted(self, *args, **kwargs):
+        calls[0] += 1
+        return orig(self, *args, **kwargs)
+
+    monkeypatch.setattr(MlpKernels, "forward_env_step", counted)
+    return calls
+
+
+def _trainer_state(ppo, rng_env, trackers) -> dict:
+    torch.cuda.synchronize()
+    out = {name: getattr(ppo, name).clone() for name in BUFFERS}
+    out.update(flat=ppo.flat.clone(), adam_m=ppo.adam_m.clone(), adam_v=ppo.adam_v.clone())
+    out["rng"] = rng_env.rng_state()
+    out["trackers"] = [_bytes(t) for t in trackers]
+    return out
+
+
+def _assert_same(a: dict, b: dict, what) -> None:
+    for k in a:
+        if isinstance(a[k], torch.Tensor):
+            assert torch.equal(a[k], b[k]), (what, k)
+        elif isinstance(a[k], np.ndarray):
+            assert np.array_equal(a[k], b[k]), (what, k)
+        else:
+            assert a[k] == b[k], (what, k)
+
+
+def _run_single(form: str, monkeypatch, toggle_components: bool = False):
+    from rl_brain_trainer_amd.curriculum import PointCurriculum
+    from rl_brain_trainer_amd.ppo import PPO, PPOConfig
+    from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv
+
+    monkeypatch.setenv("KP1_FUSED_ROLLOUT", form)
+    calls = _count_fused_calls(monkeypatch)
+    cfg = _approach_cfg()
+    env = ArmKinematicVecEnv(cfg, 48, seed=21)
+    cur = PointCurriculum(success_rate_threshold=0.0, window_episodes=8, min_episodes_per_stage=8, max_stage_index=cfg.n_stages - 1, initial_stage_index=3)
+    ppo = PPO(env, PPOConfig(n_steps=64, batch_size=768, n_epochs=2, hidden=64, learning_rate=3e-4, seed=5), curriculum=cur)
+    assert ppo.use_graphs and ppo._fused_env_step == (form == "1")
+    states, counts = [], []
+    for it in range(3 if toggle_components else 2):          # the first rollout captures, the second replays
+        if toggle_components and it == 1:
+            env.enable_reward_components(True)               # the next rollout re-captures, as forward + step_into
+            assert not ppo._fused_env_step
+        ppo.collect_rollouts()
+        states.append(_trainer_state(ppo, env, [cur.read()]))
+        counts.append(calls[0])
+    ppo.train()
+    states.append(_trainer_state(ppo, env, [cur.read()]))
+    stage = int(cur.read().stage_index)
+    cur.close()
+    env.close()
+    ppo._mlp.close()
+    return states, counts, stage
+
+
+def test_ppo_hidden64_fused_rollout_equals_launch_sequence(monkeypatch):
+    """PPO(hidden=64), 48 envs x 64 steps, a promoting PointCurriculum, graphs on: two rollouts (capture, replay) and one train() with
+    KP1_FUSED_ROLLOUT=1 against 0"""
+    s1, c1, stage1 = _run_single("1", monkeypatch)
+    s0, c0, stage0 = _run_single("0", monkeypatch)
+    assert c1[0] >= 64 and c0[-1] == 0, (c1, c0)      # warm-up + capture went through forward_env_step; the reference never did
+    assert stage1 == stage0 and stage1 > 3, "the tracker never promoted"
+    for i, (x, y) in enumerate(zip(s1, s0)):
+        _assert_same(x, y, i)
+
+
+def test_reward_components_toggled_after_construction(monkeypatch):
+    """enable_reward_components(True) after the first rollout: the re-captured rollout falls back to forward + step_into (recorded
+    components need the env's own step kernel) and equals a KP1_FUSED_ROLLOUT=0 run that made the same toggle"""
+    s1, c1, _ = _run_single("1", monkeypatch, toggle_components=True)
+    s0, c0, _ = _run_single("0", monkeypatch, toggle_components=True)
+    assert c1[0] >= 64 and c1[1] == c1[0] and c1[2] == c1[0], c1      # no one-launch step after the toggle
+    assert c0[-1] == 0
+    for i, (x, y) in enumerate(zip(s1, s0)):
+        _assert_same(x, y, i)
+
+
+def _run_population(kind: str, form: str, monkeypatch):
+    from rl_brain_trainer_amd import finisher_tools as ft
+    from rl_brain_trainer_amd.curriculum import PointCurriculumPopulation
+    from rl_brain_trainer_amd.population import ApproachPopulationPPO, DockPopulationPPO
+    from rl_brain_trainer_amd.ppo import PPOConfig
+    from rl_brain_trainer_amd.vec_env import ArmKinematicPopulationVecEnv
+
+    monkeypatch.setenv("KP1_FUSED_ROLLOUT", form)
+    calls = _count_fused_calls(monkeypatch)
+    if kind == "approach":
+        seeds, N = [7, 8, 9], 16
+        cfg = _approach_cfg()
+        env = ArmKinematicPopulationVecEnv(cfg, seeds, N)
+        cur = PointCurriculumPopulation(success_rate_threshold=0.0, window_episodes=8, min_episodes_per_stage=N, max_stage_index=cfg.n_stages - 1,
+                                        initial_stage_indices=[0, 2, 5])
+        pop = ApproachPopulationPPO(seeds, PPOConfig(n_steps=128, batch_size=256, n_epochs=2, hidden=64, learning_rate=3e-4, ent_coef=1e-3), env,
+                                    curriculum=cur)
+    else:
+        seeds, N = [7, 8], 12
+        env = ArmKinematicPopulationVecEnv(load_golden_config(DOCK_CFG), seeds, N, mode="dock")
+        cur = ft.DockReverseCurriculumPopulation(stages=_dock_stages(N), window_episodes=4, n_replicas=2, handoff_base_dirs=(GOLDEN,))
+        pop = DockPopulationPPO(seeds, PPOConfig(n_steps=64, batch_size=128, n_epochs=2, hidden=64, learning_rate=3e-4, ent_coef=1e-3), env,
+                                curriculum=cur)
+    K = len(seeds)
+    assert pop.use_graphs and pop._fused_env_step == (form == "1")
+    states = []
+    for _ in range(2):
+        pop.collect_rollouts()
+        states.append(_trainer_state(pop, env, [cur.read(k) for k in range(K)]))
+    pop.train()
+    states.append(_trainer_state(pop, env, [cur.read(k) for k in range(K)]))
+    stages = [int(cur.read(k).stage_index) for k in range(K)]
+    n_calls = calls[0]
+    pop._mlp.close()
+    cur.close()
+    env.close()
+    return states, n_calls, stages
+
+
+@pytest.mark.parametrize("kind", ["approach", "dock"])
+def test_population_ppo_fused_rollout_equals_launch_sequence(kind, monkeypatch):
+    """ApproachPopulationPPO (K = 3, N = 16) and DockPopulationPPO (K = 2, N = 12), promoting trackers, graphs on: two rollouts (capture,
+    replay) and one train() with KP1_FUSED_ROLLOUT=1 against 0"""
+    s1, n1, st1 = _run_population(kind, "1", monkeypatch)
+    s0, n0, st0 = _run_population(kind, "0", monkeypatch)
+    assert n1 >= 64 and n0 == 0, (n1, n0)
+    assert st1 == st0 and (st1 != [0, 2, 5] if kind == "approach" else all(s > 0 for s in st1)), st1
+    for i, (x, y) in enumerate(zip(s1, s0)):
+        _assert_same(x, y, i)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 6. refusals
+def _raw_call(mlp, env_handle, *, obs, noise, value, action, log_prob, next_obs, reward, done, terminal_obs, stride=None):
+    L = native.load()
+    L.kp1_last_error.restype = C.c_char_p
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    rc = L.kp1_mlp_forward_env_step(mlp._h, env_handle, p(obs), obs.shape[1] if stride is None else stride, p(noise), p(value), p(action),
+                                    p(log_prob), p(next_obs), p(reward), p(done), p(terminal_obs), mlp._stream())
+    return rc, L.kp1_last_error().decode(errors="replace")
+
+
+def _marked(n: int, w: int) -> dict:
+    """call arguments whose outputs carry a marker, so that a refused call can be seen to have written nothing"""
+    f = lambda *shape, v=0.0: torch.full(shape, v, dtype=torch.float32, device=DEV)   # noqa: E731
+    return {"obs": f(n, w), "noise": f(n, 7), "value": f(n, v=-7.5), "action": f(n, 7, v=-7.5), "log_prob": f(n, v=-7.5),
+            "next_obs": f(n, w, v=-7.5), "reward": f(n, v=-7.5), "done": torch.full((n,), 200, dtype=torch.uint8, device=DEV),
+            "terminal_obs": f(n, w, v=-7.5)}
+
+
+def _untouched(args: dict) -> bool:
+    """(an output that shares its storage with obs carries no marker: the call was refused for it, and the caller checks that storage)"""
+    torch.cuda.synchronize()
+    base = args["obs"].untyped_storage().data_ptr()
+    outs = [(k, args[k]) for k in ("value", "action", "log_prob", "next_obs", "reward", "done", "terminal_obs")
+            if args[k] is not None and args[k].untyped_storage().data_ptr() != base]
+    return all(bool((t == (200 if k == "done" else -7.5)).all()) for k, t in outs)
+
+
+def test_refusals():
+    """every refusal of the layer-wise form, before any launch: status, kp1_last_error text, outputs untouched; and the hidden-256 form still
+    refuses population env handles"""
+    from rl_brain_trainer_amd import finisher_tools as ft
+    from rl_brain_trainer_amd.curriculum import PointCurriculumPopulation
+    from rl_brain_trainer_amd.mlp import MlpKernels
+    from rl_brain_trainer_amd.vec_env import ArmKinematicPopulationVecEnv, ArmKinematicVecEnv
+
+    acfg = _approach_cfg()
+    mlp, _ = _mlp(64, 1, 128, seed=1)
+    env = ArmKinematicVecEnv(acfg, 12, seed=1)
+    env.set_obs_stride(64)
+    env.reset()
+
+    def refused(m, handle, args, status, text, **kw):
+        rc, msg = _raw_call(m, handle, **args, **kw)
+        assert rc == status and text in msg, (rc, msg)
+        assert _untouched(args), text
+
+    a = _marked(12, 64)
+    # NULL required arguments
+    for key in ("noise", "action", "next_obs", "reward", "done"):
+        refused(mlp, env._handle, {**a, key: None}, KP1_ERR_INVALID, "NULL argument")
+    rc = native.load().kp1_mlp_forward_env_step(mlp._h, env._handle, None, 64, None, None, None, None, None, None, None, None, None)
+    assert rc == KP1_ERR_INVALID
+    # obs_stride, next_obs == obs
+    refused(mlp, env._handle, a, KP1_ERR_INVALID, "obs_stride must be 56 or 64", stride=60)
+    refused(mlp, env._handle, {**a, "next_obs": a["obs"]}, KP1_ERR_INVALID, "next_obs must not be obs")
+    # next_obs or terminal_obs overlapping obs partly
+    big = torch.zeros((18, 64), dtype=torch.float32, device=DEV)
+    refused(mlp, env._handle, {**a, "obs": big[:12], "next_obs": big[6:]}, KP1_ERR_INVALID, "must not overlap obs")
+    refused(mlp, env._handle, {**a, "obs": big[6:], "terminal_obs": big[:12]}, KP1_ERR_INVALID, "must not overlap obs")
+    assert not big.any()
+    # the 80-float observation (K = 1 and a population handle)
+    for K in (1, 2):
+        m80 = MlpKernels(64, DEV, max_batch=128, obs_dim=80, replicas=K)
+        refused(m80, env._handle, a, KP1_ERR_UNSUPPORTED, "56-float observation", stride=128)
+        m80.close()
+    # recorded reward components
+    env.enable_reward_components(True)
+    refused(mlp, env._handle, a, KP1_ERR_UNSUPPORTED, "reward components")
+    env.enable_reward_components(False)
+    # f64 env handles
+    e64 = ArmKinematicVecEnv(acfg, 12, seed=1, real="f64")
+    refused(mlp, e64._handle, a, KP1_ERR_UNSUPPORTED, "fp32 handle")
+    e64.close()
+    # the env count is no multiple of K; a bound population of another replica count
+    m2, _ = _mlp(64, 2, 128, seed=2)
+    e13 = ArmKinematicVecEnv(acfg, 13, seed=1)
+    e13.set_obs_stride(64)
+    refused(m2, e13._handle, _marked(13, 64), KP1_ERR_INVALID, "multiple of the handle's replica count")
+    e13.close()
+    penv = ArmKinematicPopulationVecEnv(acfg, [1, 2, 3], 4)
+    pcur = PointCurriculumPopulation(success_rate_threshold=0.5, window_episodes=4, min_episodes_per_stage=4, max_stage_index=acfg.n_stages - 1,
+                                     initial_stage_indices=[0, 1, 2])
+    pcur.attach(penv)
+    penv.set_obs_stride(64)
+    refused(m2, penv._handle, a, KP1_ERR_INVALID, "replica count differs")
+    refused(mlp, penv._handle, a, KP1_ERR_INVALID, "replica count differs")
+    # a mode the bound handle's own step refuses (the ABI has the approach and the dock mode only: kp1_set_mode refuses any other, so the
+    # entry point's own mode check cannot be reached from here)
+    m3, _ = _mlp(64, 3, 128, seed=3)
+    native.check(native.load().kp1_set_mode(penv._handle, kcfg.MODE_NAMES["dock"]))
+    refused(m3, penv._handle, a, KP1_ERR_UNSUPPORTED, "approach mode only")
+    native.check(native.load().kp1_set_mode(penv._handle, kcfg.MODE_NAMES["approach"]))
+    m3.close()
+    # hidden 256 on population env handles: unchanged
+    m256 = MlpKernels(256, DEV, max_batch=64)
+    refused(m256, penv._handle, a, KP1_ERR_UNSUPPORTED, "no per-replica stage (population env handle)")
+    pcur.close()
+    penv.close()
+    denv = ArmKinematicPopulationVecEnv(load_golden_config(DOCK_CFG), [1, 2], 6, mode="dock")
+    dcur = ft.DockReverseCurriculumPopulation(stages=_dock_stages(6), window_episodes=4, n_replicas=2, handoff_base_dirs=(GOLDEN,))
+    dcur.attach(denv)
+    denv.set_obs_stride(64)
+    refused(m256, denv._handle, a, KP1_ERR_UNSUPPORTED, "no per-replica dock stage (dock population env handle)")
+    refused(mlp, denv._handle, a, KP1_ERR_INVALID, "replica count differs")
+    dcur.close()
+    denv.close()
+    m256.close()
+    m2.close()
+    # route envs have no kp1_env step of their own: refused on the host
+    class NotAnArmEnv:
+        n_envs, _handle = 12, env._handle
+
+    with pytest.raises(TypeError, match="route envs"):
+        mlp.forward_env_step(NotAnArmEnv(), a["obs"], **{k: v for k, v in a.items() if k != "obs"})
+    assert _untouched(a)
+    # different devices: needs a second GPU; on a one-GPU machine say so in the test report
+    if torch.cuda.device_count() > 1:
+        m_other = MlpKernels(64, torch.device("cuda", 1), max_batch=128)
+        refused(m_other, env._handle, a, KP1_ERR_INVALID, "different devices")
+        m_other.close()
+    else:
+        warnings.warn("kp1_mlp_forward_env_step's different-devices refusal was not exercised: this machine has one GPU")
+    mlp.close()
+    env.close()
+
