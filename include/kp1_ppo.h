@@ -252,7 +252,8 @@ int kp1_mlp_forward(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n,
  *                    (the value net's workgroups read rows that the policy net's workgroups would overwrite).
  * Refused before any launch: the 80-float route observation, f64 env handles, recorded reward components, modes other than approach and
  * dock, a replica-count mismatch, an env count that is no multiple of K, next_obs == obs or any overlap of next_obs / terminal_obs with obs (layer-wise form), different devices, NULL required
- * arguments, obs_stride other than 56 or 64.  (A kp1_route handle is not a kp1_env and has no step of its own here.) */
+ * arguments, obs_stride other than 56 or 64.  (A kp1_route handle is not a kp1_env and has no step of its own here: its
+ * one-launch rollout step is kp1_mlp_forward_route_step, include/kp1_route.h.) */
 int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t obs_stride, const float* noise, float* value, float* action,
                              float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream);
 

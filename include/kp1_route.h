@@ -222,6 +222,21 @@ typedef struct kp1_route_chain_view {  /* device pointers, valid until kp1_route
 } kp1_route_chain_view;
 int kp1_route_chain_get_view(kp1_route_chain* chain, kp1_route_chain_view* out);
 
+/* ---- one-launch rollout step (kp1_ppo.h: kp1_mlp handles) -----------------------------------------------------------
+ * kp1_mlp_forward(m, obs, ..., noise, ..., clipped_action, ...) followed by kp1_route_step(r, clipped_action, next_obs, reward, done,
+ * terminal_obs, 1), bit for bit, as ONE kernel launch on `stream`: the policy workgroup of a 32-row tile samples the actions, steps the tile's
+ * base envs, scans the route for the nearest waypoint and runs the route step with its auto-reset.
+ * m: a K = 1 or a population handle at hidden 64 / 128 whose obs_dim is the route handle's (56 or 80); K = kp1_route_num_replicas(r); row i of
+ * every buffer is env i of r (replica-major).  obs_stride: obs_dim or its padded width (64 / 128), and the stride set with
+ * kp1_route_set_obs_stride (next_obs and terminal_obs have that pitch).  value, log_prob and terminal_obs may be NULL; noise is required.
+ * Refused before any launch (status + kp1_last_error, outputs untouched): hidden 256, an fp64 base env, recorded route reward components, an
+ * obs_dim / obs_stride / replica-count mismatch, an env count that is no multiple of K, n_waypoints > KP1_ROUTE_FUSED_MAX_WAYPOINTS,
+ * next_obs == obs or any overlap of next_obs / terminal_obs with obs, different devices, NULL required arguments, a live kp1_route_chain. */
+#define KP1_ROUTE_FUSED_MAX_WAYPOINTS 914   /* the joint table (n_waypoints x 7 floats) overlays the kernel's 32 x 68 + 32 x 132 float tiles */
+struct kp1_mlp;
+int kp1_mlp_forward_route_step(struct kp1_mlp* m, kp1_route* r, const float* obs, int32_t obs_stride, const float* noise, float* value,
+                               float* action, float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

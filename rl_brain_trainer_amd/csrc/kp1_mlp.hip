@@ -19,9 +19,12 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "../../include/kp1_ppo.h"
+#include "../../include/kp1_route.h"
+#include "../../include/kp1_ziggurat_tables.h"
 #include "kp1_device.hpp"
 #include "kp1_host.hpp"
 
@@ -1435,8 +1438,13 @@ __global__ void anchor_count_kernel(int* __restrict__ actor_extra) { *actor_extr
 #include "kp1_rollout_step.inc"
 #include "kp1_mlp_tile.inc"
 #include "kp1_mlp_fused.inc"
+// (new kernels go after the tile kernels: including them earlier moved the tile kernels' addresses)
+#include "kp1_route_step.inc"
+#include "kp1_route_rollout_step.inc"
 
 }  // namespace
+
+#include "kp1_route_host.hpp"
 
 // ============================================================================================ host
 struct kp1_mlp {
@@ -2043,6 +2051,83 @@ int forward_env_step_layers(kp1_mlp* m, kp1_env* env, const float* obs, int32_t 
   return KP1_OK;
 }
 }  // namespace
+
+namespace {
+template <int INP>
+void launch_route_rollout_step(bool pop, dim3 grid, hipStream_t stream, const RouteRolloutStepArgs& a) {
+  if (pop) hipLaunchKernelGGL((route_rollout_step_kernel<INP, true>), grid, dim3(ES_NTH), 0, stream, a);
+  else hipLaunchKernelGGL((route_rollout_step_kernel<INP, false>), grid, dim3(ES_NTH), 0, stream, a);
+}
+}  // namespace
+
+extern "C" {
+
+// kp1_mlp_forward + kp1_route_step(auto_reset = 1) in one launch (include/kp1_route.h): route_rollout_step_kernel
+int kp1_mlp_forward_route_step(kp1_mlp* m, kp1_route* r, const float* obs, int32_t obs_stride, const float* noise, float* value, float* action,
+                               float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream) {
+  if (!m || !r || !obs || !noise || !action || !next_obs || !reward || !done) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_forward_route_step");
+  if (m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step covers hidden 64 / 128 (the layer-wise layout); hidden 256 takes the launch sequence");
+  const int obs_dim = r->cfg.include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM;
+  if (m->L.IN != obs_dim) return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: the MLP handle's obs_dim differs from the route handle's");
+  if (obs_stride != m->L.IN && obs_stride != m->L.INP)
+    return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: obs_stride must be the observation width (56 / 80) or its padded width (64 / 128)");
+  if (obs_stride != r->obs_stride)
+    return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: obs_stride differs from the route handle's (kp1_route_set_obs_stride)");
+  if (r->comps_enabled) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step does not record route reward components (kp1_route_enable_reward_components is on)");
+  if (r->n_chains > 0) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step: the route handle has a live kp1_route_chain");
+  if (r->n_waypoints > KP1_ROUTE_FUSED_MAX_WAYPOINTS)
+    return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step: the route has more than KP1_ROUTE_FUSED_MAX_WAYPOINTS waypoints (the joint table overlays the kernel's LDS tiles)");
+  if (r->n_replicas != m->K) return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: the route handle's replica count differs from the MLP handle's");
+  if (next_obs == obs) return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step reads obs from two workgroups per tile, next_obs must not be obs");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  RouteRolloutStepArgs a{};
+  int mode = 0, device = 0, pop_replicas = 0, pop_form = 0;
+  int64_t n_envs = 0;
+  // the base step as route_launch_step launches it: the wrapper's scratch at pitch 56, no terminal observation, no auto-reset.  Refuses f64
+  // base handles, recorded base reward components and a bound handle in a mode kp1_step refuses.
+  rc = kp1::env_step_args_f32_population(r->base, &a.fwd.env, sizeof a.fwd.env, r->base_obs, r->base_reward, r->bytes + 4 * r->n, nullptr, 0, &mode, &n_envs,
+                                         &device, &pop_replicas, &pop_form);
+  if (rc != KP1_OK) return rc;
+  a.fwd.env.obs_stride = KP1_OBS_DIM;
+  if (device != m->device) return fail(KP1_ERR_INVALID, "the route handle and the MLP workspace live on different devices");
+  if (mode != KP1_MODE_APPROACH) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step: the route wrappers drive an approach-mode base env");
+  if (pop_replicas > 0 && pop_replicas != m->K)
+    return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: the base env's population replica count differs from the MLP handle's");
+  if (n_envs != r->n || n_envs <= 0 || n_envs % m->K != 0)
+    return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: the env count must be a multiple of the handle's replica count");
+  if (n_envs / m->K > m->max_batch) return fail(KP1_ERR_INVALID, "more envs than the workspace max_batch");
+  if (!r->fused_actions) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step runs on an fp32 route handle");
+  {  // the value net's workgroups read obs rows while the policy net's write next_obs / terminal_obs rows of other tiles: no overlap at all
+    const float* obs_end = obs + n_envs * obs_stride;
+    const int64_t out_floats = n_envs * r->obs_stride;
+    auto overlaps = [&](const float* p) { return p && p < obs_end && obs < p + out_floats; };
+    if (overlaps(next_obs) || overlaps(terminal_obs))
+      return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: next_obs and terminal_obs must not overlap obs");
+  }
+  const int Hp = m->Hp, INP = m->L.INP;
+  RolloutStepArgs& f = a.fwd;
+  f.obs = obs; f.obs_stride = obs_stride;
+  f.w1 = m->k.w1p; f.b1 = m->k.b1; f.w2 = m->k.w2; f.b2 = m->k.b2; f.w3 = m->k.w3; f.b3 = m->k.b3; f.log_std = m->k.log_std;
+  f.r_w1 = (unsigned)(2 * Hp * INP); f.r_w2 = (unsigned)(2 * Hp * Hp); f.r_b = (unsigned)(2 * Hp); f.r_w3 = (unsigned)(HEADS * Hp); f.r_b3 = (unsigned)HEADS;
+  f.n_w1 = (unsigned)(Hp * INP); f.n_w2 = (unsigned)(Hp * Hp); f.n_b = (unsigned)Hp;
+  f.noise = noise; f.value = value; f.action = action; f.log_prob = log_prob;
+  f.n = (int)(n_envs / m->K);
+  f.Kreal = obs_stride >= INP ? INP : m->L.IN;
+  RouteStepArgs<float>& s = a.route;
+  s.st = f.env.st; s.cfg = f.env.cfg; s.smp = f.env.smp; s.rc = r->dev_cfg; s.rt = route_table_of(r); s.rs = route_state_of<float>(r);
+  s.actions = r->fused_actions; s.base_done = r->bytes + 4 * r->n; s.obs = next_obs; s.reward = reward; s.done = done; s.terminal_obs = terminal_obs;
+  s.obs_dim = obs_dim; s.obs_stride = r->obs_stride; s.auto_reset = 1;
+  a.clipped = r->fused_actions;
+  const dim3 grid((unsigned)((f.n + ES_BM - 1) / ES_BM), (unsigned)m->K, value ? 2u : 1u);
+  if (INP == ES_INP) launch_route_rollout_step<ES_INP>(pop_form != 0, grid, (hipStream_t)stream, a);
+  else if (INP == RR_MAX_INP) launch_route_rollout_step<RR_MAX_INP>(pop_form != 0, grid, (hipStream_t)stream, a);
+  else return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step: unexpected padded observation width");
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+}  // extern "C"
 
 extern "C" {
 

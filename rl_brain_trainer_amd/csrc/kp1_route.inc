@@ -11,220 +11,7 @@
 
 namespace {
 
-__device__ const uint64_t ZIG_KI[256] = KP1_ZIGGURAT_KI;
-__device__ const double ZIG_WI[256] = KP1_ZIGGURAT_WI;
-__device__ const double ZIG_FI[256] = KP1_ZIGGURAT_FI;
-
-// numpy random_standard_normal (256-layer ziggurat): one 64-bit word per draw in 99.3 % of the cases
-__device__ __forceinline__ double pcg_standard_normal(Pcg& g) {
-  for (;;) {
-    uint64_t r = pcg_next64(g);
-    const int idx = (int)(r & 0xff);
-    r >>= 8;
-    const int sign = (int)(r & 0x1);
-    const uint64_t rabs = (r >> 1) & 0x000fffffffffffffULL;
-    double x = (double)rabs * ZIG_WI[idx];
-    if (sign) x = -x;
-    if (rabs < ZIG_KI[idx]) return x;
-    if (idx == 0) {
-      for (;;) {
-        const double xx = -KP1_ZIGGURAT_NOR_INV_R * log1p(-pcg_double(g));
-        const double yy = -log1p(-pcg_double(g));
-        if (yy + yy > xx * xx) return ((rabs >> 8) & 0x1) ? -(KP1_ZIGGURAT_NOR_R + xx) : KP1_ZIGGURAT_NOR_R + xx;
-      }
-    } else {
-      if (((ZIG_FI[idx - 1] - ZIG_FI[idx]) * pcg_double(g) + ZIG_FI[idx]) < exp(-0.5 * x * x)) return x;
-    }
-  }
-}
-__device__ __forceinline__ double normal_scaled(Pcg& g, double std) {
-#pragma clang fp contract(off)
-  const double z = pcg_standard_normal(g);
-  const double prod = std * z;   // loc + scale * z with loc = 0.0, product rounded before the add like numpy
-  return 0.0 + prod;
-}
-
-struct RouteTable {  // device, fp64
-  const double* q;        // [W][7]
-  const double* pose;     // [W][6]
-  const double* next_dq;  // [W][7]
-  const double* progress; // [W]
-  int n;
-};
-
-template <typename R>
-struct RouteState {
-  int32_t *cur, *start, *last, *streak, *completed, *reset_mode;
-  uint8_t *ready, *wp_success, *regression, *ori_hit;
-  R *q_error, *nearest;
-  R* prev;          // SoA [27][N]: prev_q 7, prev_dq 7, prev_action 7, prev_pose 6
-  uint64_t* rng64;  // [4][N]
-  uint32_t* rng32;  // [2][N]
-  double* scratch;  // [N][4*7] explicit-reset values for reset_env
-  R* comps;         // [17][N] or nullptr
-};
-constexpr int RP_Q = 0, RP_DQ = 7, RP_ACT = 14, RP_POSE = 21, RP_NUM = 27;
-
-struct RouteDevCfg {
-  kp1_route_config c;   // (c.reset.min / max_route_index: the host's last set_window; the kernels read `window`)
-  int success_dwell_steps, terminate_on_success;
-  // reset window of each replica of a population handle: env i resets inside window[i / n_per_replica] (a single handle: n_per_replica = N,
-  // window 0).  The prefix tracker of replica k rewrites window[k] on promotion.
-  int n_per_replica, pad_;
-  int32_t window[KP1_ROUTE_MAX_REPLICAS][2];   // [min_route_index, max_route_index]
-};
-
-// the reset window of env i
-__device__ __forceinline__ void route_window_of(const RouteDevCfg& rc, int64_t i, int& lo, int& hi) {
-  const int k = (int)i / rc.n_per_replica;
-  lo = rc.window[k][0];
-  hi = rc.window[k][1];
-}
-
-__device__ __forceinline__ int rclipi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// route_reset_samplers.py:47-117 on the wrapper's stream; all values fp64
-struct RouteSampleDev {
-  double initial_q[NJ], initial_dq[NJ], initial_prev_action[NJ];
-  int route_index, start_index, mode;
-};
-// (win_min / win_max: the env's reset window, in place of c.min_route_index / c.max_route_index)
-__device__ __forceinline__ void sample_route_reset_dev(Pcg& g, const RouteTable& rt, const DevSampler& smp, const kp1_route_reset_cfg& c, int win_min,
-                                                       int win_max, RouteSampleDev& out) {
-  const int max_index = rt.n - 1;
-  const int lo = rclipi(win_min, 1, max_index);
-  const int hi = rclipi(win_max, lo, max_index);
-  double ratios[5] = {fmax(c.prefix_start_reset_ratio, 0.0), fmax(c.random_prefix_reset_ratio, 0.0), fmax(c.segment_reset_ratio, 0.0),
-                      fmax(c.replay_reset_ratio, 0.0), fmax(c.recovery_reset_ratio, 0.0)};
-  double total = 0.0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) total += ratios[i];
-  if (total > 0.0) {
-#pragma unroll
-    for (int i = 0; i < 5; ++i) ratios[i] /= total;
-  } else {
-    ratios[0] = 0.0; ratios[1] = 1.0; ratios[2] = 0.0; ratios[3] = 0.0; ratios[4] = 0.0;
-  }
-  // Generator.choice(p=): cdf = cumsum(p) / cdf[-1]; searchsorted(cdf, random(), side="right")
-  double cdf[5], acc = 0.0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    acc += ratios[i];
-    cdf[i] = acc;
-  }
-#pragma unroll
-  for (int i = 0; i < 5; ++i) cdf[i] /= acc;
-  const double u = pcg_double(g);
-  int mode = 0;  // searchsorted(side="right") = number of cdf entries <= u (cdf is non-decreasing)
-#pragma unroll
-  for (int i = 0; i < 5; ++i) mode += cdf[i] <= u ? 1 : 0;
-  if (c.mode >= 1 && c.mode <= 5) mode = c.mode - 1;
-  int route_index, start_index;
-  if (mode == KP1_ROUTE_MODE_PREFIX_START) {
-    route_index = pcg_integers(g, lo, hi + 1);
-    start_index = 0;
-  } else if (mode == KP1_ROUTE_MODE_SEGMENT) {
-    const int seg_lo = rclipi(c.segment_start_index, 1, max_index);
-    const int seg_hi = rclipi(c.segment_end_index, seg_lo, max_index);
-    route_index = pcg_integers(g, seg_lo, (seg_hi < hi ? seg_hi : hi) + 1);
-    start_index = route_index - 1 > 0 ? route_index - 1 : 0;
-  } else if (mode == KP1_ROUTE_MODE_REPLAY) {
-    const int rlo = rclipi(c.replay_start_index, 1, max_index);
-    const int rhi = rclipi(c.replay_end_index, rlo, max_index);
-    route_index = pcg_integers(g, rlo, (rhi < hi ? rhi : hi) + 1);
-    start_index = route_index - 1 > 0 ? route_index - 1 : 0;
-  } else {
-    route_index = pcg_integers(g, lo, hi + 1);
-    start_index = route_index - 1 > 0 ? route_index - 1 : 0;
-  }
-  const int src = rclipi(mode == KP1_ROUTE_MODE_RECOVERY ? route_index : start_index, 0, max_index);
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) {
-    const double noise = c.q_noise_std > 0.0 ? normal_scaled(g, c.q_noise_std) : 0.0;
-    out.initial_q[k] = dclip(rt.q[src * NJ + k] + noise, smp.lower[k], smp.upper[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) out.initial_dq[k] = c.dq_noise_std > 0.0 ? normal_scaled(g, c.dq_noise_std) : 0.0;
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) out.initial_prev_action[k] = dclip(c.prev_action_noise_std > 0.0 ? normal_scaled(g, c.prev_action_noise_std) : 0.0, -1.0, 1.0);
-  out.route_index = route_index;
-  out.start_index = start_index;
-  out.mode = mode;
-}
-
-// 56 base floats -> the wrapper's observation row (route_observation.py:31-61 in the key-sorted flat layout)
-template <typename R>
-__device__ __forceinline__ void store_route_obs(float* __restrict__ obs, int64_t i, int obs_dim, int obs_stride, const float* o, const DevCfg<R>& cfg, const RouteTable& rt,
-                                                int cur, const R* q) {
-  float* dst = obs + i * obs_stride;   // row pitch >= obs_dim (the padding of the PPO buffers is never written and stays zero)
-  if (obs_dim == KP1_OBS_DIM) {
-#pragma unroll
-    for (int k = 0; k < KP1_OBS_DIM; ++k) dst[k] = o[k];
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < 47; ++k) dst[k] = o[k];
-  const int w = rclipi(cur, 0, rt.n - 1), wt = rclipi(cur - 1 > 0 ? cur - 1 : 0, 0, rt.n - 1);
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) {
-    const R goal = (R)rt.q[w * NJ + k], tangent = (R)rt.next_dq[wt * NJ + k];
-    const R span = kp_max<R>(cfg.upper[k] - cfg.lower[k], (R)1e-9), dl = kp_max<R>(cfg.dlim[k], (R)1e-9);
-    dst[47 + k] = (float)kp_clip<R>((goal - q[k]) / dl, (R)-1, (R)1);                                  // route_q_error
-    dst[54 + k] = (float)kp_clip<R>((R)2 * ((goal - cfg.lower[k]) / span) - (R)1, (R)-1, (R)1);         // route_q_goal
-    dst[64 + k] = (float)kp_clip<R>(tangent / dl, (R)-1, (R)1);                                         // route_tangent
-  }
-  const int max_route_index = rt.n - 1;
-  const R s0 = (R)cur / (R)(max_route_index > 1 ? max_route_index : 1);
-  const R s1 = (R)rt.progress[w] / kp_max<R>((R)rt.progress[rt.n - 1], (R)1e-9);
-  dst[61] = (float)kp_clip<R>(s0, (R)0, (R)1);
-  dst[62] = (float)kp_clip<R>(s1, (R)0, (R)1);
-  dst[63] = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) dst[71 + k] = o[47 + k];
-}
-
-// shared tail of reset and auto-reset: base reset with explicit state, wrapper bookkeeping, observation
-template <typename R>
-__device__ __forceinline__ void route_reset_env(const EnvState<R>& st, const DevCfg<R>& cfg, const DevSampler& smp, const RouteDevCfg& rc, const RouteTable& rt,
-                                                const RouteState<R>& rs, int64_t i, int first_target, int start_index, int mode, const double* q0,
-                                                const double* dq0, const double* pa0, float* obs, int obs_dim, int obs_stride, int win_max) {
-  const int64_t n = st.n;
-  int cur = first_target, last = first_target;
-  if (rc.c.sequence_enabled) {
-    const int max_index = win_max < rt.n - 1 ? win_max : rt.n - 1;
-    const int seq_len = rc.c.sequence_length > 1 ? rc.c.sequence_length : 1;
-    cur = rclipi(first_target, 1, max_index);
-    last = max_index < cur + seq_len - 1 ? max_index : cur + seq_len - 1;
-  }
-  // explicit-state arrays for reset_env, four [N][7] planes (it indexes them with i * 7 + k)
-  double* s_q = rs.scratch, *s_dq = rs.scratch + NJ * n, *s_pa = rs.scratch + 2 * NJ * n, *s_goal = rs.scratch + 3 * NJ * n;
-  const int w = rclipi(cur, 0, rt.n - 1);
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) {
-    s_q[i * NJ + k] = q0[k];
-    s_dq[i * NJ + k] = dq0[k];
-    s_pa[i * NJ + k] = pa0[k];
-    s_goal[i * NJ + k] = rt.q[w * NJ + k];
-  }
-  ResetOptsDev o;
-  o.initial_q = s_q; o.initial_dq = s_dq; o.initial_prev_action = s_pa; o.goal_q = s_goal;
-  o.goal_pose6 = nullptr;
-  o.flags = OPT_INITIAL_Q | OPT_INITIAL_DQ | OPT_INITIAL_PREV_ACTION | OPT_GOAL_Q;
-  float ob[KP1_OBS_DIM];
-  reset_env<R, KP1_MODE_APPROACH>(st, cfg, smp, nullptr, o, 0, i, ob);
-  rs.cur[i] = cur; rs.start[i] = start_index; rs.last[i] = last; rs.streak[i] = 0; rs.completed[i] = 0; rs.reset_mode[i] = mode;
-  R q[NJ];
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) {
-    q[k] = st.r(F_Q + k, i);
-    rs.prev[(RP_Q + k) * n + i] = q[k];
-    rs.prev[(RP_DQ + k) * n + i] = st.r(F_DQ + k, i);
-    rs.prev[(RP_ACT + k) * n + i] = st.r(F_PREV_ACTION + k, i);
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) rs.prev[(RP_POSE + k) * n + i] = st.r(F_EE_POSE + k, i);
-  if (obs) store_route_obs<R>(obs, i, obs_dim, obs_stride, ob, cfg, rt, cur, q);
-}
+#include "kp1_route_step.inc"
 
 template <typename R>
 struct RouteResetArgs {
@@ -269,16 +56,9 @@ __global__ void __launch_bounds__(256) kp1_route_reset_kernel(const RouteResetAr
   route_reset_env<R>(a.st, *a.cfg, *a.smp, rc, a.rt, a.rs, i, first_target, start, mode, q0, dq0, pa0, a.obs, a.obs_dim, a.obs_stride, win_max);
 }
 
-template <typename R>
-struct RouteStepArgs {
-  EnvState<R> st; const DevCfg<R>* cfg; const DevSampler* smp; const RouteDevCfg* rc; RouteTable rt; RouteState<R> rs;
-  const R* actions; const uint8_t* base_done; float* obs; R* reward; uint8_t* done; float* terminal_obs; int obs_dim, obs_stride, auto_reset;
-};
-
-// Nearest waypoint in joint space, min over the whole route of ||Q_w - q|| (route_env.py: nearest_route_q_distance): the one O(W) piece
-// of the wrapper step.  As a per-env serial scan inside the step kernel it was a 484-iteration latency chain on a handful of waves
-// (the whole step 76 us at 2048 envs); here 8 lanes share an env (waypoints w = sub, sub + 8, ...), the route table sits in LDS in the
-// env's real type, and three xor-shuffles combine the partial minima.  Same per-waypoint arithmetic, min is order-free: bitwise identical.
+// The nearest-waypoint scan (route_nearest_group) over all envs.  As a per-env serial scan inside the step kernel it was a 484-iteration latency
+// chain on a handful of waves (the whole step 76 us at 2048 envs); here 8 lanes share an env and the route table sits in LDS in the env's real
+// type.  Same per-waypoint arithmetic, min is order-free: bitwise identical.
 constexpr size_t KP1_ROUTE_MAX_TABLE_LDS_BYTES = 128 * 1024;   // of the CU's 160 KB
 template <typename R>
 __global__ void __launch_bounds__(256) kp1_route_nearest_kernel(const EnvState<R> st, const RouteTable rt, R* __restrict__ nearest) {
@@ -294,22 +74,8 @@ __global__ void __launch_bounds__(256) kp1_route_nearest_kernel(const EnvState<R
   R q[NJ];
 #pragma unroll
   for (int k = 0; k < NJ; ++k) q[k] = st.r(F_Q + k, ic);
-  R best = std::numeric_limits<R>::infinity();
-  for (int wv = sub; wv < W; wv += 8) {
-    R s = (R)0;
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) {
-      const R d = route_q[wv * NJ + k] - q[k];
-      s += d * d;
-    }
-    best = s < best ? s : best;
-  }
-#pragma unroll
-  for (int off = 1; off < 8; off <<= 1) {
-    const R o = __shfl_xor(best, off);
-    best = o < best ? o : best;
-  }
-  if (sub == 0 && i < n) nearest[i] = kp_sqrt(best);   // sqrt is monotone: taken once
+  const R d = route_nearest_group<R>(route_q, W, sub, q);
+  if (sub == 0 && i < n) nearest[i] = d;
 }
 
 // route_env.py:124-192 / route_sequence_env.py:150-236, after the base step kernel has advanced the base env
@@ -320,233 +86,15 @@ __global__ void __launch_bounds__(256) kp1_route_step_kernel(const RouteStepArgs
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t n = a.st.n;
   if (i >= n) return;
-  const DevCfg<R>& cfg = *a.cfg;
-  const RouteDevCfg& rc = *a.rc;
-  const kp1_route_reward& w = rc.c.reward;
-  const EnvState<R>& st = a.st;
-  const RouteState<R>& rs = a.rs;
-  const R Z = (R)0;
-
-  R prev_q[NJ], prev_dq[NJ], prev_action[NJ], prev_pose[6], act[NJ], q[NJ], dq[NJ], pose[6];
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) {
-    prev_q[k] = rs.prev[(RP_Q + k) * n + i];
-    prev_dq[k] = rs.prev[(RP_DQ + k) * n + i];
-    prev_action[k] = rs.prev[(RP_ACT + k) * n + i];
-    act[k] = a.actions[i * NJ + k];          // the wrappers use the raw action (np.asarray(action)), not the base env's clipped copy
-    q[k] = st.r(F_Q + k, i);
-    dq[k] = st.r(F_DQ + k, i);
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    prev_pose[k] = rs.prev[(RP_POSE + k) * n + i];
-    pose[k] = st.r(F_EE_POSE + k, i);
-  }
-  const int target = rs.cur[i];
-  const int wt = rclipi(target, 0, W - 1), wtan = rclipi(target - 1 > 0 ? target - 1 : 0, 0, W - 1);
-  R goal_q[NJ], goal_pose[6], tangent[NJ];
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) {
-    goal_q[k] = (R)route_q[wt * NJ + k];
-    tangent[k] = (R)a.rt.next_dq[wtan * NJ + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) goal_pose[k] = (R)a.rt.pose[wt * 6 + k];
-
-  R d[NJ];
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) d[k] = goal_q[k] - q[k];
-  const R curr_q_err = norm7<R>(d);
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) d[k] = goal_q[k] - prev_q[k];
-  const R prev_q_err = norm7<R>(d);
-  const R action_norm = norm7<R>(act), dq_norm = norm7<R>(dq), tangent_norm = norm7<R>(tangent);
-  const R nearest = rs.nearest[i];   // kp1_route_nearest_kernel, launched between the base step and this kernel
-  const R base_pos = st.r(F_POS_ERR, i), base_ori = st.r(F_ORI_ERR, i);  // info["position_error_norm"] etc. of the base step
-  const bool ready = curr_q_err <= (R)w.route_ready_q_threshold && base_pos <= (R)w.route_ready_pos_threshold_m &&
-                     base_ori <= (R)w.route_ready_ori_threshold_rad && action_norm <= (R)w.route_ready_action_threshold &&
-                     dq_norm <= (R)w.route_ready_dq_threshold;
-  int streak = ready ? rs.streak[i] + 1 : 0;
-
-  // compute_route_reward (reward_route.py:54-143)
-  R pe[3], oe[3], prev_pos, prev_ori, curr_pos, curr_ori;
-  pose_error_norms<R>(prev_pose, goal_pose, pe, oe, &prev_pos, &prev_ori);
-  pose_error_norms<R>(pose, goal_pose, pe, oe, &curr_pos, &curr_ori);
-  R dot = Z;
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) dot += (q[k] - prev_q[k]) * tangent[k];
-  const R tangent_progress = tangent_norm > Z ? dot / kp_max<R>(tangent_norm, (R)1e-9) : Z;
-  const bool ready_r = curr_q_err <= (R)w.route_ready_q_threshold && curr_pos <= (R)w.route_ready_pos_threshold_m &&
-                       curr_ori <= (R)w.route_ready_ori_threshold_rad && action_norm <= (R)w.route_ready_action_threshold &&
-                       dq_norm <= (R)w.route_ready_dq_threshold;
-  R low_motion = Z;
-  if (curr_pos <= (R)2 * (R)w.route_ready_pos_threshold_m && curr_ori <= (R)2 * (R)w.route_ready_ori_threshold_rad) {
-    const R action_clean = kp_max<R>((R)1 - action_norm / kp_max<R>((R)w.route_ready_action_threshold, (R)1e-9), Z);
-    const R dq_clean = kp_max<R>((R)1 - dq_norm / kp_max<R>((R)w.route_ready_dq_threshold, (R)1e-9), Z);
-    low_motion = (R)w.low_motion_near_waypoint_bonus * (R)0.5 * (action_clean + dq_clean);
-  }
-  R a2 = Z, da2 = Z;
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) {
-    a2 += act[k] * act[k];
-    const R t = act[k] - prev_action[k];
-    da2 += t * t;
-  }
-  R comps[KP1_ROUTE_N_COMPONENTS];
-  comps[0] = (R)w.q_goal_progress_weight * (prev_q_err - curr_q_err);
-  comps[1] = (R)w.ee_position_progress_weight * (prev_pos - curr_pos);
-  comps[2] = (R)w.ee_orientation_progress_weight * (prev_ori - curr_ori);
-  comps[3] = (R)w.route_tangent_progress_weight * kp_max<R>(tangent_progress, Z);
-  comps[4] = ready_r ? (R)w.same_step_route_ready_bonus : Z;
-  comps[5] = (ready_r && streak >= 1) ? (R)w.route_ready_dwell_bonus : Z;
-  comps[6] = low_motion;
-  comps[7] = -(R)w.orientation_regression_penalty_weight * kp_max<R>(curr_ori - prev_ori, Z);
-  comps[8] = -(R)w.q_route_regression_penalty_weight * kp_max<R>(curr_q_err - prev_q_err, Z);
-  comps[9] = -(R)w.off_route_penalty_weight * kp_max<R>(nearest, Z);
-  comps[10] = -(R)w.action_magnitude_weight * (a2 / (R)7) + -(R)w.action_delta_weight * (da2 / (R)7);
-  comps[11] = -(R)w.dq_penalty_weight * dq_norm;
-  comps[12] = (curr_q_err >= prev_q_err && curr_pos >= prev_pos && curr_ori >= prev_ori) ? -(R)w.no_progress_penalty : Z;
-  comps[13] = curr_q_err; comps[14] = curr_pos; comps[15] = curr_ori; comps[16] = ready_r ? (R)1 : Z;
-  R reward = Z;
-#pragma unroll
-  for (int k = 0; k < 13; ++k) reward += comps[k];
-  if (rs.comps) {
-#pragma unroll
-    for (int k = 0; k < KP1_ROUTE_N_COMPONENTS; ++k) rs.comps[(int64_t)k * n + i] = comps[k];
-  }
-
-  const uint8_t bd = a.base_done[i];
-  const bool base_terminated = (bd & KP1_DONE_TERMINATED) != 0, truncated = (bd & KP1_DONE_TRUNCATED) != 0;
-  const bool base_success = (bd & KP1_DONE_SUCCESS) != 0 && (bd & KP1_DONE_INVALID) == 0;
-  const bool reached = ready && streak >= rc.success_dwell_steps;
-  bool terminated = false, success = false, retarget = false;
-  int cur = target, completed = rs.completed[i];
-  if (rc.c.sequence_enabled) {
-    if (reached) {
-      completed += 1;
-      if (target >= rs.last[i]) {
-        success = true;
-        terminated = true;
-      } else {
-        cur = target + 1;  // _advance_target (route_sequence_env.py:253-257)
-        retarget = true;
-        if (rc.c.reset_ready_streak_on_advance) streak = 0;
-      }
-    }
-    if (base_terminated && !terminated && !base_success) terminated = true;
-  } else {
-    success = reached;
-    terminated = base_terminated;
-    if (base_terminated && base_success && !success) terminated = false;
-    if (success && rc.terminate_on_success) terminated = true;
-  }
-
-  float o[KP1_OBS_DIM];
-  R pa_now[NJ];
-#pragma unroll
-  for (int k = 0; k < NJ; ++k) pa_now[k] = st.r(F_PREV_ACTION + k, i);
-  if (retarget) {
-    const int wn = rclipi(cur, 0, W - 1);
-    R ng[6];
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) st.r(F_GOAL_Q + k, i) = (R)route_q[wn * NJ + k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      ng[k] = (R)a.rt.pose[wn * 6 + k];
-      st.r(F_GOAL_POSE + k, i) = ng[k];
-    }
-    R pn, on;
-    pose_error_norms<R>(pose, ng, pe, oe, &pn, &on);
-    st.r(F_ENTRY + 0, i) = pn;          // _capture_entry_metrics (arm_kinematic_env.py:425-430)
-    st.r(F_ENTRY + 1, i) = on;
-    st.r(F_ENTRY + 2, i) = norm7<R>(pa_now);
-    st.r(F_ENTRY + 3, i) = norm7<R>(dq);
-  } else {
-    R cg[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) cg[k] = st.r(F_GOAL_POSE + k, i);
-    R pn, on;
-    pose_error_norms<R>(pose, cg, pe, oe, &pn, &on);
-  }
-  build_observation<R>(cfg, KP1_MODE_APPROACH, q, dq, pa_now, pe, oe, st.iv(I_STEP, i), st.iv(I_DWELL, i), o);
-
-  rs.ready[i] = ready; rs.wp_success[i] = reached; rs.regression[i] = curr_q_err > prev_q_err;
-  rs.ori_hit[i] = base_ori <= (R)w.route_ready_ori_threshold_rad;
-  rs.q_error[i] = curr_q_err; rs.nearest[i] = nearest;
-  rs.cur[i] = cur; rs.streak[i] = streak; rs.completed[i] = completed;
-  a.reward[i] = reward;
-  a.done[i] = (uint8_t)((terminated ? KP1_DONE_TERMINATED : 0) | (truncated ? KP1_DONE_TRUNCATED : 0) | (success ? KP1_DONE_SUCCESS : 0) |
-                        ((bd & KP1_DONE_INVALID) ? KP1_DONE_INVALID : 0));
-  if ((terminated || truncated) && a.auto_reset) {
-    if (a.terminal_obs) store_route_obs<R>(a.terminal_obs, i, a.obs_dim, a.obs_stride, o, cfg, a.rt, cur, q);
-    Pcg g;
-    rng_load(rs.rng64, rs.rng32, n, i, g);
-    int win_min, win_max;
-    route_window_of(rc, i, win_min, win_max);
-    RouteSampleDev s;
-    sample_route_reset_dev(g, a.rt, *a.smp, rc.c.reset, win_min, win_max, s);
-    rng_store(rs.rng64, rs.rng32, n, i, g);
-    route_reset_env<R>(st, cfg, *a.smp, rc, a.rt, rs, i, s.route_index, s.start_index, s.mode, s.initial_q, s.initial_dq, s.initial_prev_action, a.obs,
-                       a.obs_dim, a.obs_stride, win_max);
-    // the finished episode's info stays readable, like the base env's auto-reset
-    rs.cur[i] = rs.cur[i];
-  } else {
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) {
-      rs.prev[(RP_Q + k) * n + i] = q[k];
-      rs.prev[(RP_DQ + k) * n + i] = dq[k];
-      rs.prev[(RP_ACT + k) * n + i] = pa_now[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) rs.prev[(RP_POSE + k) * n + i] = pose[k];
-    store_route_obs<R>(a.obs, i, a.obs_dim, a.obs_stride, o, cfg, a.rt, cur, q);
-  }
+#include "kp1_route_step_body.inc"
 }
 
 }  // namespace
 
 // ============================================================================================ host
-struct kp1_route {
-  kp1_env* base = nullptr;
-  kp1_route_config cfg;
-  int32_t n_waypoints = 0;
-  double *q = nullptr, *pose = nullptr, *next_dq = nullptr, *progress = nullptr;  // device
-  std::vector<double> h_q, h_pose, h_next, h_progress;
-  std::vector<int32_t> h_chunk;
-  RouteDevCfg* dev_cfg = nullptr;
-  int32_t* ints = nullptr;     // [6][N]
-  uint8_t* bytes = nullptr;    // [4][N] flags + [N] base done
-  void* reals = nullptr;       // R[2 + 27][N]
-  uint64_t* rng64 = nullptr;
-  uint32_t* rng32 = nullptr;
-  double* scratch = nullptr;   // [N][28]
-  double* opt_scratch = nullptr;  // explicit reset options: 3 * [N][7] doubles
-  int32_t* opt_ints = nullptr;    // 2 * [N]
-  float* base_obs = nullptr;   // [N][56]
-  void* base_reward = nullptr; // R[N]
-  void* comps = nullptr;       // R[17][N]
-  bool comps_enabled = false;
-  int32_t obs_stride = 0;      // row pitch of caller observation buffers (kp1_route_set_obs_stride; default = obs_dim)
-  int32_t n_replicas = 1, n_per_replica = 0;   // population handle: K blocks of N envs (a single handle: 1 x N)
-  std::vector<int32_t> win;    // host copy of the reset windows [K][2]
-  int32_t n_trackers = 0;      // prefix trackers created on this handle and not yet destroyed (a chain refuses a tracked handle)
-  std::vector<void*> allocs;
-};
+#include "kp1_route_host.hpp"
 
 namespace {
-
-template <typename R>
-RouteState<R> route_state_of(const kp1_route* r) {
-  const int64_t n = r->base->n;
-  RouteState<R> s;
-  s.cur = r->ints; s.start = r->ints + n; s.last = r->ints + 2 * n; s.streak = r->ints + 3 * n; s.completed = r->ints + 4 * n; s.reset_mode = r->ints + 5 * n;
-  s.ready = r->bytes; s.wp_success = r->bytes + n; s.regression = r->bytes + 2 * n; s.ori_hit = r->bytes + 3 * n;
-  s.q_error = (R*)r->reals; s.nearest = (R*)r->reals + n; s.prev = (R*)r->reals + 2 * n;
-  s.rng64 = r->rng64; s.rng32 = r->rng32; s.scratch = r->scratch;
-  s.comps = (r->comps_enabled && r->comps) ? (R*)r->comps : nullptr;
-  return s;
-}
-RouteTable route_table_of(const kp1_route* r) { return RouteTable{r->q, r->pose, r->next_dq, r->progress, r->n_waypoints}; }
 
 int route_upload_cfg(kp1_route* r) {
   RouteDevCfg d;
@@ -901,6 +449,7 @@ int kp1_route_create(kp1_env* base, const kp1_route_config* cfg, const double* r
   HIP_TRY(hipSetDevice(base->device));
   kp1_route* r = new kp1_route();
   r->base = base;
+  r->n = base->n;
   r->cfg = *cfg;
   r->obs_stride = cfg->include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM;
   r->n_waypoints = n_waypoints;
@@ -930,6 +479,7 @@ int kp1_route_create(kp1_env* base, const kp1_route_config* cfg, const double* r
   alloc((void**)&r->base_obs, sizeof(float) * KP1_OBS_DIM * n);
   alloc((void**)&r->base_reward, base->real_size() * n);
   alloc((void**)&r->comps, base->real_size() * KP1_ROUTE_N_COMPONENTS * n);
+  if (base->real_type == KP1_REAL_F32) alloc((void**)&r->fused_actions, sizeof(float) * NJ * n);
   if (rc != KP1_OK) { kp1_route_destroy(r); return rc; }
   // load_route_dataset: FK per waypoint on the device in fp64, then path length / tangents / chunks on the host
   r->h_q.assign(route_q_host, route_q_host + W * NJ);
@@ -1388,6 +938,7 @@ struct kp1_route_chain {
   int32_t n_rows = 0;
   double* init_q = nullptr;    // [R][7] route_q[max(start - 1, 0)]
   int32_t* zeros = nullptr;    // [R] start_route_index = 0
+  bool counted = false;        // in kp1_route::n_chains
   std::vector<void*> allocs;
 };
 
@@ -1448,12 +999,15 @@ int kp1_route_chain_create(kp1_route* r, const int32_t* start_host, const int32_
     kp1_route_chain_destroy(r, c);
     return fail(KP1_ERR_NO_DEVICE, "hipMemcpy failed in kp1_route_chain_create");
   }
+  c->counted = true;
+  r->n_chains += 1;
   *out = c;
   return KP1_OK;
 }
 
 int kp1_route_chain_destroy(kp1_route* r, kp1_route_chain* c) {
   if (!c) return KP1_OK;
+  if (r && c->counted && r->n_chains > 0) r->n_chains -= 1;
   if (r && r->base) { (void)hipSetDevice(r->base->device); (void)hipStreamSynchronize(r->base->stream); }
   for (void* p : c->allocs) (void)hipFree(p);
   delete c;

@@ -31,6 +31,7 @@ class MlpKernels:
         L.kp1_mlp_pack_weights.argtypes = [vp, vp, vp]
         L.kp1_mlp_forward.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         L.kp1_mlp_forward_env_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.kp1_mlp_forward_route_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.kp1_mlp_loss_grad.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, f32, f32, vp, f32, f32, f32, f32, vp, vp, i32, vp]
         L.kp1_mlp_adam_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, i32, i32, vp]
         L.kp1_mlp_time_kernels.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
@@ -140,6 +141,24 @@ class MlpKernels:
         assert obs.is_contiguous() and obs.dtype == torch.float32 and obs.shape[0] == env.n_envs
         native.check(self.L.kp1_mlp_forward_env_step(self._h, env._handle, _p(obs), obs.shape[1], _p(noise), _p(value), _p(action), _p(log_prob),
                                                      _p(next_obs), _p(reward), _p(done), _p(terminal_obs), self._stream()))
+
+    def forward_route_step(self, env, obs: torch.Tensor, *, noise, value, action, log_prob, next_obs, reward, done, terminal_obs) -> None:
+        """One rollout step of a route env in one launch (kp1_mlp_forward_route_step, include/kp1_route.h): ``forward`` on `obs` (row m = env
+        m of `env`) with sampling, then ``env.step_into(clipped, next_obs, reward, done, terminal_obs, True)``, bit for bit.
+
+        ``env``: a RouteVecEnv, or a RoutePopulationVecEnv of K replicas with a population handle of K (replica k owns rows [k n, (k + 1) n)
+        of every buffer).  hidden 64 / 128; the handle's obs_dim is the env's (56 or 80) and ``obs``'s pitch the one set with
+        ``env.set_obs_stride``; ``next_obs`` and ``terminal_obs`` must not overlap ``obs``.  ``value``, ``log_prob`` and ``terminal_obs`` may
+        be None.  Refused: hidden 256, f64 envs, recorded reward components, routes longer than ROUTE_FUSED_MAX_WAYPOINTS, a live RouteChain,
+        a replica-count, obs_dim or pitch mismatch."""
+        from .route_env import RouteVecEnv
+
+        if not isinstance(env, RouteVecEnv):
+            raise TypeError(f"forward_route_step steps a RouteVecEnv or a RoutePopulationVecEnv handle; {type(env).__name__} takes "
+                            "forward_env_step (arm envs) or forward + step_into")
+        assert obs.is_contiguous() and obs.dtype == torch.float32 and obs.shape[0] == env.n_envs
+        native.check(self.L.kp1_mlp_forward_route_step(self._h, env._handle, _p(obs), obs.shape[1], _p(noise), _p(value), _p(action), _p(log_prob),
+                                                       _p(next_obs), _p(reward), _p(done), _p(terminal_obs), self._stream()))
 
     def mean_value(self, obs: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         n = obs.shape[0]

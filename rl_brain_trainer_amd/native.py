@@ -122,6 +122,7 @@ def load() -> C.CDLL:
     L.kp1_route_chain_begin.argtypes = [vp, vp, vp]
     L.kp1_route_chain_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.kp1_route_chain_get_view.argtypes = [vp, C.POINTER(RouteChainView)]
+    L.kp1_mlp_forward_route_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.kp1_mlp_anchor_loss_grad.argtypes = [vp, vp, i32, vp, i32, vp, f32, vp, vp, vp]
     L.kp1_mlp_anchor_adam_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, i32, vp]
     if L.kp1_config_size() != C.sizeof(kcfg.Kp1Config):

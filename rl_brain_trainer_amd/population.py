@@ -32,7 +32,7 @@ from typing import Any, Callable
 import torch
 
 from . import native
-from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig, fused_rollout_covered
+from .ppo import ACT_DIM, FUSED_ROUTE_ROLLOUT_ENV, OBS_DIM, Dist, PPO, PPOConfig, fused_rollout_covered, fused_route_rollout_covered
 
 MAX_REPLICAS = 16     # KP1_MLP_MAX_REPLICAS
 
@@ -360,7 +360,26 @@ class OneHandlePopulationPPO(PopulationPPO):
                                      getattr(env, "_reward_components_on", False), os.environ.get("KP1_FUSED_ROLLOUT"),
                                      default_on=True)     # measured on both one-handle trainers
 
+    # whether the env handle is one kp1_mlp_forward_route_step steps (RoutePopulationPPO: a RoutePopulationVecEnv)
+    fused_route_env_type_ok = False
+
+    @property
+    def _fused_route_step(self) -> bool:
+        """the one-launch ROUTE form (fused_route_rollout_covered; opt-in with KP1_FUSED_ROUTE_ROLLOUT, read before any attribute of the env)"""
+        var = os.environ.get(FUSED_ROUTE_ROLLOUT_ENV)
+        if var is None or var == "0" or not self.fused_route_env_type_ok:
+            return False
+        env = self.pop_env
+        return fused_route_rollout_covered(True, env.dtype, self.cfg.hidden, self.obs_dim, bool(getattr(env, "_reward_components_on", False)),
+                                           int(getattr(env, "n_waypoints", 0)), self.dist.enabled, var)
+
     def _policy_env_step(self, t: int) -> None:
+        if self._fused_route_step:
+            # all replicas' policy forward + sampling + base step + nearest scan + route step (auto-reset in each replica's window) in ONE launch
+            self._mlp.forward_route_step(self.pop_env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
+                                         log_prob=self.logp_buf[t], next_obs=self.obs_buf[t + 1], reward=self.rew_buf[t], done=self.done_buf[t],
+                                         terminal_obs=self.term_obs_buf[t])
+            return
         if self._fused_env_step:
             # all replicas' policy forward + sampling + env step (auto-reset on each replica's own stage) in ONE launch
             self._mlp.forward_env_step(self.pop_env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
@@ -507,6 +526,8 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
     Replica k is bit-identical to ``PPO(RouteVecEnv(..., seed=s_k), curriculum=RoutePrefixCurriculumDevice)`` on the same config
     (tests/test_route_population_gpu.py).  ``load_init_checkpoint`` (OneHandlePopulationPPO's) starts every replica from one checkpoint as
     train_route does.  The caller owns (and closes) the env and the tracker."""
+
+    fused_route_env_type_ok = True
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
                  teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:

@@ -469,6 +469,28 @@ def fused_rollout_covered(env_type_ok: bool, dtype: Any, hidden: int, obs_dim: i
     return bool(default_on) if env_var is None else env_var != "0"
 
 
+# kp1_mlp_forward_route_step: the widths, the observation widths and the route length it covers
+FUSED_ROUTE_ROLLOUT_WIDTHS = (64, 128)
+FUSED_ROUTE_ROLLOUT_OBS_DIMS = (56, 80)
+ROUTE_FUSED_MAX_WAYPOINTS = 914        # include/kp1_route.h KP1_ROUTE_FUSED_MAX_WAYPOINTS
+FUSED_ROUTE_ROLLOUT_ENV = "KP1_FUSED_ROUTE_ROLLOUT"
+
+
+def fused_route_rollout_covered(env_type_ok: bool, dtype: Any, hidden: int, obs_dim: int, components_on: bool, n_waypoints: int,
+                                dist_enabled: bool, env_var: str | None) -> bool:
+    """Whether a rollout step on a ROUTE env runs as ONE launch (``MlpKernels.forward_route_step``) instead of forward + step_into.  Opt-in:
+    ``env_var`` is KP1_FUSED_ROUTE_ROLLOUT, and unset or "0" is the launch sequence (KP1_FUSED_ROLLOUT, the arm envs' switch, is never
+    consulted here).  Covered: a RouteVecEnv / RoutePopulationVecEnv (``env_type_ok``) at fp32, hidden 64 / 128, the 56- or 80-float
+    observation, reward components off, a route of at most ROUTE_FUSED_MAX_WAYPOINTS waypoints, and a run that is not data parallel."""
+    if env_var is None or env_var == "0":
+        return False
+    if not env_type_ok or dtype != torch.float32 or hidden not in FUSED_ROUTE_ROLLOUT_WIDTHS or obs_dim not in FUSED_ROUTE_ROLLOUT_OBS_DIMS:
+        return False
+    if components_on or dist_enabled or n_waypoints > ROUTE_FUSED_MAX_WAYPOINTS:
+        return False
+    return True
+
+
 class PPO:
     """One PPO run.  PopulationPPO (population.py) is the same engine with K replicas: everything per replica below is a list (``envs``,
     ``curricula``, ``policies``, ``gens``) or a replica axis (rollout columns [k N, (k + 1) N), ``perm[k]``, ``stats_dev[k]``); here K = 1."""
@@ -508,6 +530,20 @@ class PPO:
         return fused_rollout_covered(type(env) is ArmKinematicVecEnv, env.dtype, self.cfg.hidden, self.obs_dim,
                                      getattr(env, "_reward_components_on", False), os.environ.get("KP1_FUSED_ROLLOUT"),
                                      default_on=self.cfg.hidden == 256)
+
+    @property
+    def _fused_route_step(self) -> bool:
+        """whether the next rollout step is the one-launch ROUTE form (fused_route_rollout_covered; opt-in with KP1_FUSED_ROUTE_ROLLOUT).  The
+        variable is read first: without it no attribute of the env is touched."""
+        var = os.environ.get(FUSED_ROUTE_ROLLOUT_ENV)
+        if var is None or var == "0":
+            return False
+        from .route_env import RoutePopulationVecEnv, RouteVecEnv
+
+        env = self.env
+        return fused_route_rollout_covered(isinstance(env, RouteVecEnv) and not isinstance(env, RoutePopulationVecEnv), env.dtype,
+                                           self.cfg.hidden, self.obs_dim, bool(getattr(env, "_reward_components_on", False)),
+                                           int(getattr(env, "n_waypoints", 0)), self.dist.enabled, var)
 
     def _setup(self, cfg: PPOConfig, seeds: list[int], envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool, *,
                min_batch: int, stacked: bool) -> None:
@@ -783,7 +819,12 @@ class PPO:
         self._curriculum_observe(t)
 
     def _policy_env_step(self, t: int) -> None:
-        if self._fused_env_step:
+        if self._fused_route_step:
+            # a RouteVecEnv: policy forward + sampling + base step + nearest scan + route step (auto-reset included) in ONE launch
+            self._mlp.forward_route_step(self.env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
+                                         log_prob=self.logp_buf[t], next_obs=self.obs_buf[t + 1], reward=self.rew_buf[t], done=self.done_buf[t],
+                                         terminal_obs=self.term_obs_buf[t])
+        elif self._fused_env_step:
             # policy forward + sampling + env step (auto-reset included) in ONE launch: the tile's policy workgroup steps its 32 envs itself
             self._mlp.forward_env_step(self.env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
                                        log_prob=self.logp_buf[t], next_obs=self.obs_buf[t + 1], reward=self.rew_buf[t], done=self.done_buf[t],

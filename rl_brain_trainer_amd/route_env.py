@@ -104,6 +104,8 @@ class RouteVecEnv:
         native.check(self.L.kp1_route_get_dataset(self._handle, C.c_void_p(self.poses6.ctypes.data), C.c_void_p(self.route_progress_m.ctypes.data),
                                                   C.c_void_p(self.next_q_delta.ctypes.data), C.c_void_p(self.chunk_id.ctypes.data)))
         self._keep: list[Any] = []
+        self._reward_components_on = False
+        self.launch_args_version = 0     # bumped by setters that change which kernels a step launches (PPO re-captures its rollout graph)
         if reward_components:
             self.enable_reward_components(True)
 
@@ -233,6 +235,8 @@ class RouteVecEnv:
 
     def enable_reward_components(self, enable: bool = True) -> None:
         native.check(self.L.kp1_route_enable_reward_components(self._handle, int(enable)))
+        self._reward_components_on = bool(enable)     # the one-launch rollout step does not record them: the trainers fall back
+        self.launch_args_version += 1
 
     def reward_components(self) -> tuple[list[str], torch.Tensor]:
         p = C.c_void_p()
@@ -366,7 +370,6 @@ class RouteReplicaEnv:
         self.device, self.dtype, self.obs_dim, self.config = pop.device, pop.dtype, pop.obs_dim, pop.config
         self.route_q, self.n_waypoints, self.route_progress_m = pop.route_q, pop.n_waypoints, pop.route_progress_m
         self.seed = pop.seeds[self.k]
-        self.launch_args_version = 0
 
     @property
     def route_cfg(self) -> rcfg.RouteConfig:
@@ -377,6 +380,10 @@ class RouteReplicaEnv:
     @property
     def obs_stride(self) -> int:
         return self.pop.obs_stride
+
+    @property
+    def launch_args_version(self) -> int:
+        return self.pop.launch_args_version
 
     def set_obs_stride(self, stride: int) -> None:
         if int(stride) != self.pop.obs_stride:

@@ -72,6 +72,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--device", type=int, default=0, help="GPU of a single-process run (under torchrun: LOCAL_RANK)")
     p.add_argument("--log-every", type=int, default=0)
+    p.add_argument("--one-launch-rollout", action="store_true", help="run every rollout step as ONE launch (kp1_mlp_forward_route_step: sets "
+                   "KP1_FUSED_ROUTE_ROLLOUT=1; fp32, hidden 64 / 128, reward components off, not data parallel -- otherwise the launch "
+                   "sequence stays); bit-identical to the default, for --seed and --seeds runs")
     p.add_argument("--per-replica-eval", action="store_true", help="with --seeds: run the final sequential evaluations and gates one replica and "
                    "one prefix after another on the host-driven evaluator, instead of one device chain per replica in lock step")
     return p
@@ -81,6 +84,8 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
     if args.sweep and args.seeds is None:
         raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
+    if args.one_launch_rollout:
+        os.environ["KP1_FUSED_ROUTE_ROLLOUT"] = "1"     # read by PPO / RoutePopulationPPO at every rollout step (ppo.fused_route_rollout_covered)
     import torch.distributed as dist
 
     # WORLD_SIZE / RANK / LOCAL_RANK as torchrun sets them; a process group the caller already initialised is used as it is

@@ -57,6 +57,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 import sys
 import time
 from pathlib import Path
@@ -208,6 +209,9 @@ def measure(K: int, args, build=None) -> dict:
         up.append(t2 - t1)
     rollout_ms, update_ms = 1e3 * sum(ro) / len(ro), 1e3 * sum(up) / len(up)
     steps = K * args.n_envs * args.n_steps
+    ro_sorted = sorted(1e3 * v for v in ro)
+    rollout_stats = {"rollout_ms_median": ro_sorted[len(ro_sorted) // 2], "rollout_ms_spread": ro_sorted[-1] - ro_sorted[0],
+                     "us_per_env_step": 1e3 * ro_sorted[len(ro_sorted) // 2] / args.n_steps}   # one env step = one step of all K x n_envs envs
     _close(pop)
     # per-kernel durations from one eager update with event pairs on the launches
     eager = build(K, args.n_envs, args.n_steps, args.batch, args.hidden, False)
@@ -219,7 +223,8 @@ def measure(K: int, args, build=None) -> dict:
     eager._mlp.set_profile(False)
     _close(eager)
     return {"K": K, "rollout_ms": rollout_ms, "update_ms": update_ms, "iteration_ms": rollout_ms + update_ms,
-            "aggregate_env_steps_per_s": steps / ((rollout_ms + update_ms) * 1e-3), "env_steps_per_iteration": steps, "kernel_us_in_situ": prof}
+            "aggregate_env_steps_per_s": steps / ((rollout_ms + update_ms) * 1e-3), "env_steps_per_iteration": steps, "kernel_us_in_situ": prof,
+            **rollout_stats}
 
 
 def main_eval(args) -> None:
@@ -502,6 +507,8 @@ def main() -> None:
     ap.add_argument("--handoff-confirm-steps", type=int, default=2, help="with --eval: the evaluator's handoff_confirm_steps (2, the gate's; 0 hands "
                     "every episode over at step 1, so the Finisher phase runs over all rows whatever the policy has learnt)")
     ap.add_argument("--route", action="store_true", help="the route reference-scale iteration (RoutePopulationPPO)")
+    ap.add_argument("--one-launch-rollout", action="store_true", help="with --route: every rollout step as one launch (sets "
+                    "KP1_FUSED_ROUTE_ROLLOUT=1: kp1_mlp_forward_route_step, DESIGN section 22); default: the launch sequence")
     ap.add_argument("--one-handle", action="store_true", help="the Approach iteration on one env handle (ApproachPopulationPPO)")
     ap.add_argument("--dock", action="store_true", help="the Finisher reference shape, one handle (DockPopulationPPO) and K handles")
     ap.add_argument("--no-curriculum", action="store_true", help="with --dock: no reverse-curriculum tracker")
@@ -521,6 +528,10 @@ def main() -> None:
         if not args.one_handle:
             ap.error("--sweep is measured on the --one-handle Approach iteration")
         SWEEP[:] = parse_sweep(args.sweep)
+    if args.one_launch_rollout:
+        if not args.route:
+            ap.error("--one-launch-rollout is the route form's switch (the arm envs answer to KP1_FUSED_ROLLOUT)")
+        os.environ["KP1_FUSED_ROUTE_ROLLOUT"] = "1"
     if args.route and args.one_handle:
         ap.error("--one-handle is the Approach form; --route is always one handle")
     if args.eval and (args.route or args.dock or args.sweep):
