@@ -94,14 +94,15 @@ def reference(flat: torch.Tensor, spec, obs_dim: int, buf: dict, sel: torch.Tens
         a = (a - float(np.float32(adv_stats[0]))) * float(np.float32(adv_stats[1]))
     else:
         assert adv_mode == "raw"
-    ratio = torch.exp(logp - buf["old_logp"][sel].double())
+    log_ratio = logp - buf["old_logp"][sel].double()
+    ratio = torch.exp(log_ratio)
     pl = -torch.min(a * ratio, a * torch.clamp(ratio, 1 - clip_range, 1 + clip_range)).mean()
     vl = torch.nn.functional.mse_loss(buf["ret"][sel].double(), value)
     entropy = (0.5 + 0.5 * math.log(2 * math.pi) + Pv["log_std"]).sum()
     loss = pl + ent_coef * (-entropy) + vf_coef * vl
     (grad,) = torch.autograd.grad(loss, f)
     return {"grad": grad, "policy_loss": pl.item(), "value_loss": vl.item(), "entropy": entropy.item(), "mean": mean.detach(), "value": value.detach(),
-            "frac_clipped": ((ratio - 1).abs() > clip_range).double().mean().item()}
+            "frac_clipped": ((ratio - 1).abs() > clip_range).double().mean().item(), "approx_kl": ((ratio - 1) - log_ratio).mean().item()}
 
 
 def norm_shares(grad: torch.Tensor, spec) -> dict[str, float]:

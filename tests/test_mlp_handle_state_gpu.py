@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import mlp_handle_state as S
+import row_attribution as R
 from rl_brain_trainer_amd import ppo as P
 from rl_brain_trainer_amd.mlp import MlpKernels
 
@@ -193,6 +194,17 @@ def test_population_probe_is_independent_of_history_and_matches_single_handles(h
     want = _probe(fresh, w)
     fresh.close()
     assert all(torch.isfinite(t).all() for t in want.values())
+    # stats_out [K][4]: each replica's approx_kl against its own fp64 reference (its own policy on its own rows); the K references differ
+    cpu, kls = {name: t.cpu() for name, t in w.buf.items()}, []
+    for r in range(K):
+        sel = w.idx33[r].cpu()
+        klb = R.approx_kl_bound(w.flat0[r], w.spec, obs_dim, cpu["obs"][sel], cpu["act"][sel], cpu["old_logp"][sel])
+        ref = S.reference(w.flat0[r], w.spec, obs_dim, cpu, sel, adv_mode="minibatch", **KW)
+        assert abs(klb["kl64"] - ref["approx_kl"]) <= 1e-12 * ref["approx_kl"]
+        ratio = _check_kl(want["stats33"][r, 3].item(), klb, (kind, "replica", r))
+        print(f"{kind} replica {r}: approx_kl {want['stats33'][r, 3].item():.6e} error / bound {ratio:.3f}")
+        kls.append(klb)
+    assert all(abs(kls[a]["kl64"] - kls[b]["kl64"]) > kls[a]["bound"] + kls[b]["bound"] for a in range(K) for b in range(a + 1, K))
     k = _handle(kind, replicas=K)
     for which in ("a", "b", "e"):
         _history(k, w, which)
@@ -449,7 +461,19 @@ def edge_world():
         k.close()
 
 
-def _check_grad(grad, stats, ref, spec, what):
+def _check_kl(slot3: float, klb: dict, what, calls: int = 1) -> float:
+    """stats_out[3] after `calls` accumulating calls against approx_kl = mean((ratio - 1) - log ratio) in fp64.  This comparison has no project
+    tolerance; the bound is R.approx_kl_bound's 8 * max(e32, floor): e32 = the error of the same expression evaluated with P.mlp_forward /
+    P.gaussian_log_prob in float32 on the CPU, floor = 2^-23 * max(1, max|logp|) * mean|log ratio| (log ratio inherits one fp32 spacing of
+    the log-prob, and d kl / d log ratio = ratio - 1 ~ log ratio).  The value is > 100 x the bound (also asserted by the CPU companion), so a
+    missing inv_count, another slot or the second-order formula cannot pass.  Returns error / bound."""
+    assert klb["kl64"] > 100 * klb["bound"], (what, klb)
+    err = abs(slot3 - calls * klb["kl64"])
+    assert err <= calls * klb["bound"], f"{what} approx_kl: got {slot3} for {calls} call(s) of {klb['kl64']}, error {err:.3e} bound {calls * klb['bound']:.3e}"
+    return err / (calls * klb["bound"])
+
+
+def _check_grad(grad, stats, ref, spec, what, klb):
     g = grad.cpu().double()
     worst = 0.0
     for name, sl in S.slices_of(spec).items():
@@ -461,13 +485,15 @@ def _check_grad(grad, stats, ref, spec, what):
     assert abs(st[0].item() - ref["policy_loss"]) <= 1e-4 * (abs(ref["policy_loss"]) + 1), what
     assert abs(st[1].item() - ref["value_loss"]) <= 1e-4 * (abs(ref["value_loss"]) + 1), what
     assert abs(st[2].item() - ref["entropy"]) <= 1e-5, what
-    return worst
+    assert abs(klb["kl64"] - ref["approx_kl"]) <= 1e-12 * abs(ref["approx_kl"]), what
+    return worst, _check_kl(st[3].item(), klb, what)
 
 
 @pytest.mark.parametrize("kind,n,max_batch", EDGE_CASES, ids=[f"{S.KIND_IDS[S.KINDS.index(kd)]}-n{n}" for kd, n, _ in EDGE_CASES])
 def test_batch_size_edges_against_fp64_autograd(edge_world, kind, n, max_batch):
     """loss_grad and forward at n rows against torch autograd in fp64 on the CPU, under the project's tolerances for this comparison
-    (gradient per tensor 2e-4 * max|ref| + 1e-7, losses 1e-4 * (|x| + 1), forward rtol 1e-4 / atol 2e-5, 1e-4 for log_prob).  n >= 2:
+    (gradient per tensor 2e-4 * max|ref| + 1e-7, losses 1e-4 * (|x| + 1), forward rtol 1e-4 / atol 2e-5, 1e-4 for log_prob), and
+    stats_out[3] against approx_kl in fp64 under _check_kl's bound, after one call and after two into the same buffer.  n >= 2:
     per-minibatch normalisation (SB3's unbiased std) and raw advantages; n = 1, where torch's std is NaN: raw and supplied statistics."""
     hidden, obs_dim, _ = kind
     k, pol, buf, dbuf, total = edge_world(kind, max_batch)
@@ -479,12 +505,18 @@ def test_batch_size_edges_against_fp64_autograd(edge_world, kind, n, max_batch):
     else:
         given = (0.37, 1.9)
         modes.append(("given", dict(adv_stats=torch.tensor(given, device=DEV)), given))
+    klb = R.approx_kl_bound(pol.flat, pol.spec, obs_dim, buf["obs"][sel], buf["act"][sel], buf["old_logp"][sel])
     for mode, extra, given in modes:
         ref = S.reference(pol.flat, pol.spec, obs_dim, buf, sel, adv_mode=mode, adv_stats=given, **KW)
         grad, stats = torch.full((k.num_params,), NAN, device=DEV), torch.zeros(4, device=DEV)
         _loss_grad(k, dbuf, idx, n, grad, stats, **extra)
-        worst = _check_grad(grad, stats, ref, pol.spec, (kind, n, mode))
-        print(f"{kind} n={n} {mode}: worst gradient error / tolerance {worst:.3f}")
+        worst, kl = _check_grad(grad, stats, ref, pol.spec, (kind, n, mode), klb)
+        print(f"{kind} n={n} {mode}: worst gradient error / tolerance {worst:.3f}, approx_kl {stats[3].item():.6e} error / bound {kl:.3f}")
+    # stats_out accumulates: a second call into the same buffer leaves twice one call's approx_kl
+    one = stats[3].item()
+    _loss_grad(k, dbuf, idx, n, grad, stats, **extra)
+    assert abs(stats[3].item() - 2 * one) <= klb["bound"], (kind, n, stats[3].item(), one)
+    _check_kl(stats[3].item(), klb, (kind, n, "two calls"), calls=2)
     # forward over the same rows
     obs = dbuf["obs"][idx].contiguous()
     noise = dbuf["noise"][idx].contiguous()

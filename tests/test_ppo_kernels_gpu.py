@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import row_attribution as R
 from conftest import load_golden_config
 from rl_brain_trainer_amd import ppo as P
 from rl_brain_trainer_amd.curriculum import PointCurriculum
@@ -171,6 +172,14 @@ def test_mlp_loss_grad_vs_torch_autograd(n, total, gather, fused, obs_dim):
     assert abs(stats[0].item() - pl.item()) <= 1e-4 * (abs(pl.item()) + 1)
     assert abs(stats[1].item() - vl.item()) <= 1e-4 * (abs(vl.item()) + 1)
     assert abs(stats[2].item() - entropy.item()) <= 1e-5
+    # stats_out[3] = approx_kl = mean((ratio - 1) - log ratio), against fp64 on the CPU.  No project tolerance exists for it: the bound is
+    # 8 * max(e32, floor), e32 the error of the same expression in float32 torch on the CPU, floor = 2^-23 * max(1, max|logp|) * mean|log ratio|
+    # (the log ratio inherits one fp32 spacing of the log-prob and d kl / d log ratio ~ log ratio; tests/row_attribution.py)
+    klb = R.approx_kl_bound(pol.flat, pol.spec, D, obs[sel], act[sel], old_logp[sel])
+    kl_err = abs(stats[3].item() - klb["kl64"])
+    print(f"approx_kl {stats[3].item():.6e} fp64 {klb['kl64']:.6e}: error {kl_err:.3e} / bound {klb['bound']:.3e} = {kl_err / klb['bound']:.3f}")
+    assert klb["kl64"] > 100 * klb["bound"], klb       # so that a missing inv_count, another slot or a second-order formula cannot pass
+    assert kl_err <= klb["bound"], (stats[3].item(), klb)
     k.close()
 
 
