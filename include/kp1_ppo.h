@@ -277,6 +277,22 @@ int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t
 int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* done, const kp1_eval_buffers* buffers, int32_t step,
                   const double* ready_thresholds /* [4] or NULL */, int32_t confirm_steps, void* stream);
 
+/* Env steps first_step .. last_step of the same evaluator in ONE launch: a workgroup carries its 32 rows through all of them by itself and
+ * leaves when its last episode has ended (nothing crosses a row tile in the evaluator, so workgroups never wait for each other).  Same
+ * handles, arguments and refusals as kp1_eval_step, plus: first_step < 1, last_step < first_step, and a span of more than
+ * KP1_EVAL_EPISODES_MAX_STEPS steps (the bound of one launch; the host splits a longer limit into consecutive calls).  Everything is
+ * refused before any launch.  n_alive is zeroed and afterwards holds the episodes still alive after last_step.
+ *   Both forms run the same action norm and the same bookkeeping on the same env step, so EVERY kp1_eval_buffers array -- the action-norm
+ * columns included -- is bit-equal to the one the same steps made by kp1_eval_step leave, for any split of [1, limit] into consecutive calls
+ * (tests/test_eval_episodes_gpu.py).
+ *   One deliberate difference in the env handle: an episode that has ended (or was never active) is NOT stepped again, whereas kp1_eval_step
+ * steps every row for as long as the host keeps calling it.  After the call env i has been stepped counters[0][i] - (its count at entry)
+ * times; its handle fields, observation row, reward[i] and done[i] are those of its last step, whatever its neighbours did; a row that was
+ * never alive is untouched, and so is everything of a tile without a live episode. */
+#define KP1_EVAL_EPISODES_MAX_STEPS 256
+int kp1_eval_episodes(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* done, const kp1_eval_buffers* buffers,
+                      int32_t first_step, int32_t last_step, const double* ready_thresholds /* [4] or NULL */, int32_t confirm_steps, void* stream);
+
 /* one PPO minibatch: forward + loss + full backward.  Rows are gathered through idx (int64 [n] into the [total] axis, or
  * NULL = rows 0..n).  grad_out f32 [num_params] receives d loss / d params in SB3 order (overwritten), with
  *   loss = sum_i[-min(r_i A_i, clip(r_i, 1-c, 1+c) A_i)] * inv_count + vf_coef * sum_i (R_i - V_i)^2 * inv_count - ent_coef * H,

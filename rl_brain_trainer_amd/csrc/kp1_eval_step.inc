@@ -33,6 +33,7 @@ struct EvalStepArgs {
   int step, confirm;
   int track_ready;
   double thr_pos, thr_ori, thr_act, thr_dq;
+  int last_step;                       // episode form: env steps step .. last_step in this launch
 };
 
 // one 32 x 32 block of tanh(A W^T + bias): A = ES_BM rows at LDS pitch `apitch`, W k-slab major with N = ES_HP rows, columns [32 wave, +32)
@@ -76,7 +77,62 @@ __device__ __forceinline__ double es_action_norm(const float* __restrict__ a) {
   return sqrt(s);
 }
 
-template <int MODE, bool POP>
+// EPISODE (kp1_eval_episodes): the workgroup carries its ES_BM rows through env steps a.step .. a.last_step by itself and leaves when its last
+// episode has ended.  Nothing crosses a tile (frozen policy, no auto-reset, no tracker, no RNG; every kp1_eval_buffers entry of episode i is
+// written by the lane that steps env i), so there is no synchronisation between workgroups and the loop is bounded by the step span.
+//   * A row is stepped only while its episode is alive (flags[0][i]); the step form steps every row for as long as the host launches.  After
+//     the call env i has been stepped counters[0][i] - (its count at entry) times and its handle fields, observation row, reward and done
+//     are those of its last step.  A tile without a live episode returns before it writes anything.
+//   * A finished row's observation must stay what its last step left, and a lane that does not step has no fresh `o`.  Two equivalent
+//     ways: the lane re-reads its row into `o` and store_obs_tile stores the whole tile as in the step form, or only the stepped rows are
+//     stored (store_obs_rows).  Which one a mode takes (ES_EPISODE_REREADS) is NOT a matter of taste.  The env step's fp32 sums and reward
+//     are not contraction-pinned, and what surrounds the step decides how the compiler fuses them: with the re-read the approach forms
+//     reproduce the step form bit for bit and the dock forms differ in the last bit of reward / action_l2 in a few rows; with the row
+//     store it is the other way round (every instantiation of both kernels, measured by tests/test_eval_episodes_gpu.py, which is the
+//     guard: after a compiler change that test says which choice holds).
+//   * Observation hand-over: wave 0 stores the tile's rows to a.env.obs and all four waves load them as the next x tile.  Between the two
+//     stands the __syncthreads at the bottom of the loop: a workgroup-scope release (wave 0's stores have completed) and acquire around the
+//     barrier.  The waves of a workgroup share one CU and its L1, which the stores write through, so workgroup scope is sufficient; the
+//     rows are in HBM-backed memory when the workgroup leaves, as after the step form.
+//   * The env's index and its config block are loop-invariant.  Left alone, the compiler lifts the ~100 state-plane addresses of env i and
+//     the config reads out of the loop, holds them across the forward (hundreds of spilled registers, written before the loop and re-read
+//     in it) and, with multiplies of config terms in another block than their adds, contracts the reward arithmetic differently from the
+//     step form (the reward's last bit then differs).  So the env index and the config address carry a run-time zero that the loop
+//     produces (the sign bit of the tile's alive count): addresses and config reads stay inside the iteration, as in the step form.
+//   * go_on: wave 0 ballots the episodes still alive into one LDS word; every thread reads it after the barrier (a workgroup-uniform exit).
+// which episode forms keep a finished row's observation by re-reading it (see eval_step_kernel's comment)
+template <int MODE> constexpr bool ES_EPISODE_REREADS = MODE == KP1_MODE_APPROACH;
+
+// store_obs_tile for the episode forms that do not: only the rows whose bit is set in `rows` (the lanes that have just stepped, at most 32) are parked
+// and stored; every other row of the block keeps what the env's buffer holds.  EVERY lane of the wave must call this.
+__device__ __forceinline__ void store_obs_rows(float* obs, int64_t i0, unsigned rows, const float* o, int stride, float* __restrict__ tile) {
+  const int lane = (int)(threadIdx.x & 63u);
+  if (lane < 32 && ((rows >> lane) & 1u)) {
+    float4* row = reinterpret_cast<float4*>(tile + lane * OBS_TILE_PITCH);
+#pragma unroll
+    for (int k = 0; k < KP1_OBS_DIM / 4; ++k) row[k] = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+    row[14] = make_float4(0.f, 0.f, 0.f, 0.f);
+    row[15] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  float4* dst = reinterpret_cast<float4*>(obs + i0 * stride);
+  const int q4 = stride >> 2;                 // float4 per row: 14 or 16
+  for (int f = lane; f < 32 * q4; f += 64) {  // rows 0 .. 31 of the block; unset rows (and rows past the tile's last) are skipped
+    const int r = f / q4, c = f - r * q4;
+    if ((rows >> r) & 1u) dst[f] = *reinterpret_cast<const float4*>(tile + r * OBS_TILE_PITCH + 4 * c);
+  }
+}
+
+__device__ __forceinline__ StepArgs<float> es_episode_env(const StepArgs<float>& e, unsigned runtime_zero) {
+  StepArgs<float> env = e;
+  env.cfg = reinterpret_cast<const DevCfg<float>*>(reinterpret_cast<const char*>(e.cfg) + runtime_zero);
+  env.st.n = e.st.n + runtime_zero;    // the plane stride: the scalar halves of the state addresses
+  return env;
+}
+
+template <int MODE, bool POP, bool EPISODE = false>
 __global__ void __launch_bounds__(ES_NTH) eval_step_kernel(const EvalStepArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[ES_LDS_FLOATS];
   float* xs = lds;
@@ -87,11 +143,23 @@ __global__ void __launch_bounds__(ES_NTH) eval_step_kernel(const EvalStepArgs a)
   const unsigned rep = POP ? blockIdx.y : 0u;
   const int m0 = blockIdx.x * ES_BM;
   const int64_t env0 = (int64_t)rep * a.n + m0;          // env of the tile's row 0
+  const int rows_live = min(ES_BM, a.n - m0);
+  const bool live = lane < rows_live;
+  // the x-tile load reads what store_obs_tile wrote in the previous iteration: no __restrict__ on it in the episode form
+  using ObsPtr = std::conditional_t<EPISODE, const float*, const float* __restrict__>;
+  ObsPtr obs = a.env.obs + (int64_t)rep * a.n * a.env.obs_stride;
+  bool alive = false;                  // EPISODE: this lane's episode (every wave holds the tile's flags; wave 0 keeps them current)
+  if constexpr (EPISODE) {
+    alive = live && a.b.flags[env0 + lane] != 0;
+    if (!__ballot(alive)) return;      // the same answer in all four waves: nothing has written a flag yet
+  }
+  int step = a.step, n_alive_tile = 0;
+  unsigned runtime_zero = 0;           // EPISODE: see es_episode_env
 
+  do {
   // ---- 1. the tile's observation rows -> LDS (rows past the replica's last and columns >= Kreal read as zero, as gemm_nt_kernel masks them)
   {
     constexpr int XQ = ES_INP / 4, X_LOADS = ES_BM * XQ / ES_NTH;
-    const float* __restrict__ obs = a.env.obs + (int64_t)rep * a.n * a.env.obs_stride;
     f32x4 xv[X_LOADS];
 #pragma unroll
     for (int j = 0; j < X_LOADS; ++j) {
@@ -123,23 +191,50 @@ __global__ void __launch_bounds__(ES_NTH) eval_step_kernel(const EvalStepArgs a)
     acts[row * 8 + out] = v;
   }
   __syncthreads();
-  if (wave != 0) return;
+  if constexpr (!EPISODE) {
+    if (wave != 0) return;
+  }
 
   // ---- 3.-6. lane r of wave 0: action norm, env step, bookkeeping of env env0 + r; then the wave stores the tile's next observations
-  const int rows_live = min(ES_BM, a.n - m0);
-  const bool live = lane < rows_live;
-  float o[KP1_OBS_DIM];
-  int alive_after = 0;
-  if (live) {
-    const int64_t i = env0 + lane;
-    const double an = es_action_norm(acts + lane * 8);
-    step_env_lane<float, MODE, false>(a.env, i, acts + lane * 8, o);
-    // the fields the step has just stored are read back from the handle by the lane that stored them
-    alive_after = eval_account_step<float>(a.env.st.real, (int)a.env.st.n, (int)i, a.b, an, a.env.done[i], a.step, a.track_ready != 0, a.thr_pos,
-                                           a.thr_ori, a.thr_act, a.thr_dq, a.confirm);
+  if (!EPISODE || wave == 0) {
+    float o[KP1_OBS_DIM];
+    int alive_after = 0;
+    if (EPISODE ? alive : live) {
+      const int64_t i = env0 + lane + (EPISODE ? runtime_zero : 0u);
+      const double an = es_action_norm(acts + lane * 8);
+      if constexpr (EPISODE) step_env_lane<float, MODE, false>(es_episode_env(a.env, runtime_zero), i, acts + lane * 8, o);
+      else step_env_lane<float, MODE, false>(a.env, i, acts + lane * 8, o);
+      // the fields the step has just stored are read back from the handle by the lane that stored them
+      alive_after = eval_account_step<float>(a.env.st.real, (int)a.env.st.n, (int)i, a.b, an, a.env.done[i], step, a.track_ready != 0, a.thr_pos,
+                                             a.thr_ori, a.thr_act, a.thr_dq, a.confirm);
+    } else if (EPISODE && ES_EPISODE_REREADS<MODE> && live) {
+      // a finished (or never started) episode is not stepped: its row of the tile is its current observation
+      const f32x4* src = reinterpret_cast<const f32x4*>(obs + (int64_t)(m0 + lane) * a.env.obs_stride);
+#pragma unroll
+      for (int k = 0; k < KP1_OBS_DIM / 4; ++k) {
+        const f32x4 v = src[k];
+        o[4 * k] = v.x; o[4 * k + 1] = v.y; o[4 * k + 2] = v.z; o[4 * k + 3] = v.w;
+      }
+    }
+    const unsigned long long bal = __ballot(alive_after != 0);
+    if constexpr (!EPISODE) {
+      if (lane == 0 && bal) atomicAdd(a.b.n_alive, __popcll(bal));
+    }
+    // x and h1 were last read two barriers ago
+    if constexpr (EPISODE && !ES_EPISODE_REREADS<MODE>) store_obs_rows(a.env.obs, env0, (unsigned)__ballot(alive), o, a.env.obs_stride, lds);
+    else store_obs_tile(a.env.obs, env0, rows_live, o, live, a.env.obs_stride, lds);
+    if constexpr (EPISODE) {
+      alive = alive_after != 0;
+      if (lane == 0) reinterpret_cast<int*>(acts)[0] = __popcll(bal);   // acts: this wave alone read it, and has finished
+    }
   }
-  const unsigned long long bal = __ballot(alive_after != 0);
-  if (lane == 0 && bal) atomicAdd(a.b.n_alive, __popcll(bal));
-  // x and h1 were last read two barriers ago
-  store_obs_tile(a.env.obs, env0, rows_live, o, live, a.env.obs_stride, lds);
+  if constexpr (EPISODE) {
+    __syncthreads();                   // the tile's new observation rows and the alive count, for all four waves
+    n_alive_tile = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(acts)[0]);
+    runtime_zero = (unsigned)n_alive_tile >> 31;   // a count is never negative
+  }
+  } while (EPISODE && n_alive_tile != 0 && step++ < a.last_step);
+  if constexpr (EPISODE) {
+    if (tid == 0 && n_alive_tile) atomicAdd(a.b.n_alive, n_alive_tile);
+  }
 }

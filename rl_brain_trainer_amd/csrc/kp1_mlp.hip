@@ -1667,6 +1667,20 @@ int launch_fused_eval_env(const FusedArgs& fa, int env_mode, hipStream_t stream)
   return KP1_OK;
 }
 
+// whole-episode evaluation of a 2x256 policy in one launch (kp1_eval_episodes): env steps fa.ev.step .. fa.ev.last_step, one workgroup per tile
+int launch_fused_eval_episodes(const FusedArgs& fa, int env_mode, hipStream_t stream) {
+  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;
+  const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, 1);
+  if (env_mode == KP1_MODE_DOCK) {
+    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 6>), grid, dim3(FU_NTH), bytes, stream, fa);
+  } else {
+    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 5>), grid, dim3(FU_NTH), bytes, stream, fa);
+  }
+  return KP1_OK;
+}
+
 int launch_fused_infer(const FusedArgs& fa, hipStream_t stream) {
   const size_t bytes = sizeof(float) * FU_LDS_FLOATS;   // 32-row tiles, 4 waves, two workgroups per CU
   // the value net is skipped when no value is asked for (deterministic evaluators), the policy net when only values are
@@ -2157,18 +2171,39 @@ int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t
   return KP1_OK;
 }
 
-int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* done, const kp1_eval_buffers* b, int32_t step,
-                  const double* ready_thresholds, int32_t confirm_steps, void* stream) {
+}  // extern "C"
+
+namespace {
+// what kp1_eval_step and kp1_eval_episodes share: every refusal, and the launch arguments of the handle's form
+struct EvalLaunch {
+  bool tile;                // hidden 256: the evaluation forms of the tile kernel; hidden 64 / 128: eval_step_kernel
+  int mode, K;
+  EvalStepArgs a;
+  FusedArgs fa;
+};
+
+// refuses what neither entry point can run (nothing has been launched); on KP1_OK *L holds the arguments of env steps step .. last_step.
+// The step range is checked where kp1_eval_step has always checked its step: after the NULL checks, before a handle is looked at
+int eval_prepare(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* done, const kp1_eval_buffers* b, int32_t step, int32_t last_step,
+                 bool episodes, const double* ready_thresholds, int32_t confirm_steps, EvalLaunch* L) {
   if (!m || !env || !obs || !reward || !done || !b) return fail(KP1_ERR_INVALID, "NULL argument to kp1_eval_step");
   if (!b->metrics || !b->counters || !b->flags || !b->state || !b->n_alive) return fail(KP1_ERR_INVALID, "kp1_eval_step: NULL buffer");
   if (b->hand_metrics && (!b->hand_step || !b->hand_success || !b->hand_state)) return fail(KP1_ERR_INVALID, "kp1_eval_step: incomplete handoff buffers");
-  if (step < 1) return fail(KP1_ERR_INVALID, "kp1_eval_step accounts env steps 1, 2, ...: step 0 (the initialisation after a reset) is kp1_eval_accumulate's");
-  const bool tile = m->Hp == FU_HP;    // hidden 256: the evaluation form of the tile kernel; hidden 64 / 128: eval_step_kernel
+  if (!episodes) {
+    if (step < 1) return fail(KP1_ERR_INVALID, "kp1_eval_step accounts env steps 1, 2, ...: step 0 (the initialisation after a reset) is kp1_eval_accumulate's");
+  } else {
+    if (step < 1) return fail(KP1_ERR_INVALID, "kp1_eval_episodes: first_step must be at least 1 (step 0, the initialisation after a reset, is kp1_eval_accumulate's)");
+    if (last_step < step) return fail(KP1_ERR_INVALID, "kp1_eval_episodes: last_step is below first_step");
+    if ((int64_t)last_step - step + 1 > KP1_EVAL_EPISODES_MAX_STEPS)
+      return fail(KP1_ERR_INVALID, "kp1_eval_episodes: one call runs at most KP1_EVAL_EPISODES_MAX_STEPS (256) env steps; split a longer span into consecutive calls");
+  }
+  const bool tile = m->Hp == FU_HP;
   if (!tile && m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step covers hidden 64 / 128 (layer-wise layout) and 256 (tile kernels)");
   if (tile && (m->K > 1 || !m->fused))
     return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step: the 256 form needs the tile kernels (a K = 1 handle with the tile path on); this handle runs the layer-wise kernels");
   if (m->L.INP != ES_INP) return fail(KP1_ERR_UNSUPPORTED, "kp1_eval_step needs the 56-float observation (padded to 64)");
-  EvalStepArgs a{};
+  EvalStepArgs& a = L->a;
+  a = EvalStepArgs{};
   int mode = 0, device = 0;
   int64_t n_envs = 0;
   // refuses f64 handles, recorded reward components and env handles with bound population stages
@@ -2181,20 +2216,17 @@ int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* 
   rc = mlp_check_device(m);
   if (rc != KP1_OK) return rc;
   const int Hp = m->Hp, INP = m->L.INP;
-  hipStream_t st = (hipStream_t)stream;
+  L->tile = tile; L->mode = mode; L->K = m->K;
   if (tile) {
-    FusedArgs fa{};
+    FusedArgs& fa = L->fa;
+    fa = FusedArgs{};
     fa.env = a.env;
     fa.obs = obs; fa.obs_stride = a.env.obs_stride; fa.Kreal = a.env.obs_stride >= INP ? INP : m->L.IN; fa.inp = INP; fa.idx = nullptr; fa.n = (int)n_envs;
     fa.k = m->k;
     fa.ev.b = *b;
-    fa.ev.step = step; fa.ev.confirm = confirm_steps;
+    fa.ev.step = step; fa.ev.last_step = last_step; fa.ev.confirm = confirm_steps;
     fa.ev.track_ready = ready_thresholds != nullptr;
     if (ready_thresholds) { fa.ev.thr_pos = ready_thresholds[0]; fa.ev.thr_ori = ready_thresholds[1]; fa.ev.thr_act = ready_thresholds[2]; fa.ev.thr_dq = ready_thresholds[3]; }
-    HIP_TRY(hipMemsetAsync(b->n_alive, 0, sizeof(int32_t), st));
-    rc = launch_fused_eval_env(fa, mode, st);   // obs is read (x tile, before the first barrier) and overwritten (after the last) in place
-    if (rc != KP1_OK) return rc;
-    HIP_TRY(kp1::launch_status());
     return KP1_OK;
   }
   a.b = *b;
@@ -2202,18 +2234,52 @@ int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* 
   a.r_w1 = (unsigned)(2 * Hp * INP); a.r_w2 = (unsigned)(2 * Hp * Hp); a.r_b = (unsigned)(2 * Hp); a.r_w3 = (unsigned)(HEADS * Hp); a.r_b3 = (unsigned)HEADS;
   a.n = (int)(n_envs / m->K);
   a.Kreal = a.env.obs_stride >= INP ? INP : m->L.IN;
-  a.step = step; a.confirm = confirm_steps;
+  a.step = step; a.last_step = last_step; a.confirm = confirm_steps;
   a.track_ready = ready_thresholds != nullptr;
   if (ready_thresholds) { a.thr_pos = ready_thresholds[0]; a.thr_ori = ready_thresholds[1]; a.thr_act = ready_thresholds[2]; a.thr_dq = ready_thresholds[3]; }
-  HIP_TRY(hipMemsetAsync(b->n_alive, 0, sizeof(int32_t), st));
-  const dim3 grid((unsigned)((a.n + ES_BM - 1) / ES_BM), (unsigned)m->K);
-  const bool pop = m->K > 1, dock = mode == KP1_MODE_DOCK;
-  if (pop && dock) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_DOCK, true>), grid, dim3(ES_NTH), 0, st, a);
-  else if (pop) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_APPROACH, true>), grid, dim3(ES_NTH), 0, st, a);
-  else if (dock) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_DOCK, false>), grid, dim3(ES_NTH), 0, st, a);
-  else hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_APPROACH, false>), grid, dim3(ES_NTH), 0, st, a);
+  return KP1_OK;
+}
+
+// zeroes n_alive, then the one launch of the prepared form: the step kernels, or (EPISODE) the whole-episode ones
+template <bool EPISODE>
+int eval_launch(const EvalLaunch& L, hipStream_t st) {
+  if (L.tile) {
+    HIP_TRY(hipMemsetAsync(L.fa.ev.b.n_alive, 0, sizeof(int32_t), st));
+    // obs is read (x tile, before the first barrier) and overwritten (after the last) in place
+    const int rc = EPISODE ? launch_fused_eval_episodes(L.fa, L.mode, st) : launch_fused_eval_env(L.fa, L.mode, st);
+    if (rc != KP1_OK) return rc;
+    HIP_TRY(kp1::launch_status());
+    return KP1_OK;
+  }
+  const EvalStepArgs& a = L.a;
+  HIP_TRY(hipMemsetAsync(a.b.n_alive, 0, sizeof(int32_t), st));
+  const dim3 grid((unsigned)((a.n + ES_BM - 1) / ES_BM), (unsigned)L.K);
+  const bool pop = L.K > 1, dock = L.mode == KP1_MODE_DOCK;
+  if (pop && dock) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_DOCK, true, EPISODE>), grid, dim3(ES_NTH), 0, st, a);
+  else if (pop) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_APPROACH, true, EPISODE>), grid, dim3(ES_NTH), 0, st, a);
+  else if (dock) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_DOCK, false, EPISODE>), grid, dim3(ES_NTH), 0, st, a);
+  else hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_APPROACH, false, EPISODE>), grid, dim3(ES_NTH), 0, st, a);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kp1_eval_step(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* done, const kp1_eval_buffers* b, int32_t step,
+                  const double* ready_thresholds, int32_t confirm_steps, void* stream) {
+  EvalLaunch L;
+  const int rc = eval_prepare(m, env, obs, reward, done, b, step, step, false, ready_thresholds, confirm_steps, &L);
+  if (rc != KP1_OK) return rc;
+  return eval_launch<false>(L, (hipStream_t)stream);
+}
+
+int kp1_eval_episodes(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* done, const kp1_eval_buffers* b, int32_t first_step,
+                      int32_t last_step, const double* ready_thresholds, int32_t confirm_steps, void* stream) {
+  EvalLaunch L;
+  const int rc = eval_prepare(m, env, obs, reward, done, b, first_step, last_step, true, ready_thresholds, confirm_steps, &L);
+  if (rc != KP1_OK) return rc;
+  return eval_launch<true>(L, (hipStream_t)stream);
 }
 
 int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const int64_t* idx, int32_t n, const float* actions,

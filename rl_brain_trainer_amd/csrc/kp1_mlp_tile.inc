@@ -39,6 +39,7 @@
 struct FusedEvalArgs {
   kp1_eval_buffers b;
   int step, confirm, track_ready;
+  int last_step;                      // ENV = 5 / 6 (kp1_eval_episodes): env steps step .. last_step in this launch
   double thr_pos, thr_ori, thr_act, thr_dq;
 };
 
@@ -128,12 +129,29 @@ static_assert(FU_LDS_FLOATS * 4 * 2 <= 160 * 1024, "the two training tiles of on
 // In place: a.obs is read only by the x-tile load of the prologue (before the first barrier; rows past n re-read row n - 1, a row of the
 // same last tile) and observations are written only by store_obs_tile at the very end, each workgroup its own rows, and no value-net
 // plane reads them in another workgroup -- a.env.obs == a.obs is legal, and is how kp1_eval_step launches it.
+// ENV = 5 / 6: the whole-episode evaluation (kp1_eval_episodes; approach / dock mode) -- the ENV = 3 / 4 form with its body inside a loop over
+// env steps a.ev.step .. a.ev.last_step, written as `do { ... } while (EPISODE && ...)` so that the loop does not exist in any other
+// instantiation.  Nothing crosses a tile in the evaluator (frozen policy, no auto-reset, no tracker, no RNG, every kp1_eval_buffers entry of
+// episode i written by the lane of env i): a workgroup carries its 32 rows through all steps alone, leaves when its last episode has ended
+// (or at once when none is alive at entry, nothing written), and adds its alive count to n_alive once.  The loop is bounded by the step span.
+//   * A row is stepped only while its episode is alive.  A finished row's observation stays what its last step left: ENV = 5 re-reads it
+//     and stores the whole tile, ENV = 6 stores the stepped rows only (ES_EPISODE_REREADS / store_obs_rows; eval_step_kernel's comment in
+//     kp1_eval_step.inc says why the two modes differ).
+//   * Observation hand-over: wave 0 stores the tile's rows to a.env.obs, all four waves load them as the next iteration's x tile.  The
+//     __syncthreads at the bottom of the loop stands between the two: workgroup-scope release (the stores have completed) and acquire.
+//     The waves of a workgroup share one CU and its write-through L1, so workgroup scope is sufficient; when the workgroup leaves, the
+//     rows are where the ENV = 3 / 4 form leaves them.
+//   * The env index and the address of the env config block carry a run-time zero that the loop produces (eval_step_kernel's comment,
+//     kp1_eval_step.inc, says why): state addresses and config reads stay inside the iteration, as in the ENV = 3 / 4 form.
+//   * The same barrier publishes the alive count wave 0 ballots into one LDS word (misc[2]): the exit is workgroup-uniform.
 // SPLIT (training only, [r3 experiment]): the activations leave as three bf16 planes instead of the fp32 k8-fragment copies.  A separate
 // instantiation: the exact kernel carries none of its code (as run-time branches in one kernel the extra stores cost the exact path 1 us per launch).
 template <bool TRAIN, int K1S, int ENV = 0, bool SPLIT = false>
 __global__ void __launch_bounds__(FU_NTH, ENV ? 1 : 2) mlp_tile_kernel(const FusedArgs a) {
   static_assert(!(TRAIN && ENV), "the env step rides on the inference tile only");
   static_assert(TRAIN || !SPLIT, "split planes are written by the training tile");
+  constexpr bool EVAL = ENV >= 3 && ENV <= 6, EPISODE = ENV == 5 || ENV == 6;
+  constexpr int EVAL_MODE = (ENV == 3 || ENV == 5) ? KP1_MODE_APPROACH : KP1_MODE_DOCK;
   constexpr int NW = FU_NW, CB = FU_CB, BM = FU_BM, NTH = FU_NTH, CW = 32 * CB;
   constexpr int INP = K1S * FU_BKS, FU_XP = INP + 4, GS_L2 = K1S, GS_BW = K1S + 8, GS_END = K1S + 16;
   constexpr int KG = FU_BKS / 8, NB = CB * KG;  // B-operand float4 per lane per stage
@@ -277,6 +295,15 @@ __global__ void __launch_bounds__(FU_NTH, ENV ? 1 : 2) mlp_tile_kernel(const Fus
       while (wall_clock64() - t0_ < (unsigned long long)a.stagger_ticks) __builtin_amdgcn_s_sleep(16);
     }
   }
+  // EPISODE: this lane's episode (wave 0 keeps it current), the env step in hand, the tile's alive count after it
+  bool ep_alive = false;
+  int ep_step = a.ev.step, ep_n_alive = 0;
+  unsigned ep_zero = 0;
+  if constexpr (EPISODE) {
+    ep_alive = lane < BM && m0 + lane < a.n && a.ev.b.flags[m0 + lane] != 0;
+    if (!__ballot(ep_alive)) return;   // the same answer in all four waves: nothing has written a flag yet
+  }
+  do {   // (not indented: one pass for every instantiation but the episode forms)
   FU_BLOAD(0)
   FU_BLOAD(1)
   __builtin_amdgcn_sched_barrier(0);
@@ -461,7 +488,7 @@ __global__ void __launch_bounds__(FU_NTH, ENV ? 1 : 2) mlp_tile_kernel(const Fus
           store_obs_tile(a.env.obs, (int64_t)m0, min(BM, a.n - m0), o, live, a.env.obs_stride, bufA);
         }
       }
-      if constexpr (ENV == 3 || ENV == 4) {
+      if constexpr (EVAL) {
         // evaluation step: the clamped mean (the clamp a.clipped gets above) -> LDS, then lane r of wave 0 is episode m0 + r
         dout[l_row * 8 + l_out] = (l_ok && l_out < ACT) ? fminf(fmaxf(v, -1.f), 1.f) : 0.f;
         __syncthreads();
@@ -469,24 +496,46 @@ __global__ void __launch_bounds__(FU_NTH, ENV ? 1 : 2) mlp_tile_kernel(const Fus
           const bool live = lane < BM && m0 + lane < a.n;
           float o[KP1_OBS_DIM];
           int alive_after = 0;
-          if (live) {
-            const int64_t i = (int64_t)(m0 + lane);
+          if (EPISODE ? ep_alive : live) {
+            const int64_t i = (int64_t)(m0 + lane) + (EPISODE ? ep_zero : 0u);
             const double an = es_action_norm(dout + lane * 8);
-            step_env_lane<float, ENV == 3 ? KP1_MODE_APPROACH : KP1_MODE_DOCK, false>(a.env, i, dout + lane * 8, o);
+            if constexpr (EPISODE) step_env_lane<float, EVAL_MODE, false>(es_episode_env(a.env, ep_zero), i, dout + lane * 8, o);
+            else step_env_lane<float, EVAL_MODE, false>(a.env, i, dout + lane * 8, o);
             // the fields the step has just stored are read back from the handle by the lane that stored them
-            alive_after = eval_account_step<float>(a.env.st.real, (int)a.env.st.n, (int)i, a.ev.b, an, a.env.done[i], a.ev.step, a.ev.track_ready != 0,
-                                                   a.ev.thr_pos, a.ev.thr_ori, a.ev.thr_act, a.ev.thr_dq, a.ev.confirm);
+            alive_after = eval_account_step<float>(a.env.st.real, (int)a.env.st.n, (int)i, a.ev.b, an, a.env.done[i], EPISODE ? ep_step : a.ev.step,
+                                                   a.ev.track_ready != 0, a.ev.thr_pos, a.ev.thr_ori, a.ev.thr_act, a.ev.thr_dq, a.ev.confirm);
+          } else if (EPISODE && ES_EPISODE_REREADS<EVAL_MODE> && live) {
+            // a finished (or never started) episode is not stepped: its row of the tile is its current observation
+            const f32x4* src = reinterpret_cast<const f32x4*>(a.env.obs + (int64_t)(m0 + lane) * a.env.obs_stride);
+#pragma unroll
+            for (int k = 0; k < KP1_OBS_DIM / 4; ++k) {
+              const f32x4 v4 = src[k];
+              o[4 * k] = v4.x; o[4 * k + 1] = v4.y; o[4 * k + 2] = v4.z; o[4 * k + 3] = v4.w;
+            }
           }
           const unsigned long long bal = __ballot(alive_after != 0);
-          if (lane == 0 && bal) atomicAdd(a.ev.b.n_alive, __popcll(bal));
-          // the tile's next observations; bufA (h1) was last read in G2, two barriers ago.  This is the launch's only write to a.env.obs
-          store_obs_tile(a.env.obs, (int64_t)m0, min(BM, a.n - m0), o, live, a.env.obs_stride, bufA);
+          if constexpr (!EPISODE) {
+            if (lane == 0 && bal) atomicAdd(a.ev.b.n_alive, __popcll(bal));
+          }
+          // the tile's next observations; bufA (h1) was last read in G2, two barriers ago.  This is the step's only write to a.env.obs
+          if constexpr (EPISODE && !ES_EPISODE_REREADS<EVAL_MODE>) store_obs_rows(a.env.obs, (int64_t)m0, (unsigned)__ballot(ep_alive), o, a.env.obs_stride, bufA);
+          else store_obs_tile(a.env.obs, (int64_t)m0, min(BM, a.n - m0), o, live, a.env.obs_stride, bufA);
+          if constexpr (EPISODE) {
+            ep_alive = alive_after != 0;
+            if (lane == 0) reinterpret_cast<int*>(misc)[2] = __popcll(bal);
+          }
+        }
+        if constexpr (EPISODE) {
+          __syncthreads();             // the tile's new observation rows and the alive count, for all four waves
+          ep_n_alive = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(misc)[2]);
+          ep_zero = (unsigned)ep_n_alive >> 31;   // a count is never negative
         }
       }
     } else if (l_ok && l_out == 7 && a.value) {
       a.value[l_src] = v;
     }
-    return;
+    if constexpr (EPISODE) continue;   // to the loop's condition
+    else return;
   }
   {
     const int row_l = l_row, out = l_out;
@@ -661,6 +710,10 @@ __global__ void __launch_bounds__(FU_NTH, ENV ? 1 : 2) mlp_tile_kernel(const Fus
   FU_STORE_ACC_SPLIT(a.sp_dz1, a.sp_plane)
   KP1_TR(6)
   KP1_CLK(0, 1)
+  } while (EPISODE && ep_n_alive != 0 && ep_step++ < a.ev.last_step);
+  if constexpr (EPISODE) {
+    if (tid == 0 && ep_n_alive) atomicAdd(a.ev.b.n_alive, ep_n_alive);
+  }
 #undef FU_BLOAD
 #undef FU_INIT_ACC
 #undef FU_GEMM

@@ -391,23 +391,58 @@ def _one_launch_mlp(policy: Any, env: Any, one_launch: bool | None, what: str) -
     return None
 
 
-def run_phase(env: ArmKinematicVecEnv, policy: Any, reset_options: dict[str, Any], *, one_launch: bool | None, what: str, **kw):
-    """one evaluation phase through run_episodes_fused when ``one_launch`` allows it and the phase is covered, else through run_episodes"""
+# Which entry points run their covered phases through kp1_eval_episodes (all env steps of a phase in one launch) when their
+# ``whole_episodes`` keyword is None.  Set by the acceptance rule of DESIGN section 20 applied to tools/eval_episode_bench.py
+# (profiles/eval_episodes.json): True only where the whole-episode median beats the per-step median by more than the
+# per-step form's own max - min spread; an entry point that was not measured stays False.
+WHOLE_EPISODES_DEFAULT: dict[str, bool] = {
+    "evaluate_workspace_expansion": False,               # gate evaluation: 9.46 -> 9.03 ms (spread 0.19) at confirm 2, but 11.14 -> 11.25 (3.01) at confirm 0
+    "run_pairs": False,                                  # 8192 pairs: 8.45 -> 7.35 ms, inside the per-step form's spread of 1.48 ms
+    "evaluate_workspace_expansion_population": False,    # not measured
+    "evaluate_dock": True,                               # 512 episodes: 1.60 -> 1.54 ms (spread 0.05)
+}
+# env steps of one kp1_eval_episodes call (a longer limit is split into consecutive calls)
+_EPISODES_CAP = native.EVAL_EPISODES_MAX_STEPS
+
+
+def whole_episodes_default(entry: str, whole_episodes: bool | None) -> bool:
+    """an entry point's ``whole_episodes`` keyword resolved: None is the entry point's row of WHOLE_EPISODES_DEFAULT"""
+    return WHOLE_EPISODES_DEFAULT[entry] if whole_episodes is None else bool(whole_episodes)
+
+
+def _uncovered_whole_episodes(what: str) -> ValueError:
+    return ValueError(f"whole_episodes=True: the {what} phase is not covered by the whole-episode evaluation kernel (it covers what the one-launch "
+                      "evaluation step covers, and one_launch must not be False)")
+
+
+def run_phase(env: ArmKinematicVecEnv, policy: Any, reset_options: dict[str, Any], *, one_launch: bool | None, what: str,
+              whole_episodes: bool | None = None, entry: str | None = None, **kw):
+    """one evaluation phase through run_episodes_fused when ``one_launch`` allows it and the phase is covered, else through run_episodes.
+    ``whole_episodes`` (None: the default of ``entry``, False without one) picks kp1_eval_episodes for a covered phase; True on a phase
+    that is not covered raises ValueError, as ``one_launch=True`` does."""
     mlp = _one_launch_mlp(policy, env, one_launch, what)
     if mlp is not None:
-        return run_episodes_fused(env, mlp, reset_options, **kw)
+        whole = bool(whole_episodes) if (whole_episodes is not None or entry is None) else WHOLE_EPISODES_DEFAULT[entry]
+        return run_episodes_fused(env, mlp, reset_options, whole_episodes=whole, **kw)
+    if whole_episodes:
+        raise _uncovered_whole_episodes(what)
     return run_episodes(env, policy, reset_options, **kw)
 
 
 def run_episodes_fused(env: ArmKinematicVecEnv, mlp: Any, reset_options: dict[str, Any], *, ready_cfg=None, handoff_confirm_steps: int | None = None,
-                       active: torch.Tensor | None = None, max_steps: int | None = None) -> tuple[dict[str, torch.Tensor], dict[str, torch.Tensor] | None]:
+                       active: torch.Tensor | None = None, max_steps: int | None = None,
+                       whole_episodes: bool = False) -> tuple[dict[str, torch.Tensor], dict[str, torch.Tensor] | None]:
     """run_episodes with the whole env step in ONE launch (kp1_eval_step): the deterministic policy of ``mlp`` (an MlpKernels of hidden 64 /
     128: a K = 1 handle, or a population handle of K replicas over ``env``'s K x n envs, block k of the envs stepping under replica k's
     weights; or a K = 1 handle of hidden 256 with the tile path on, a training handle included: the step reads its packed weights and
     touches no workspace), the fp64 norm of the clipped action, the env step and the per-episode bookkeeping.  The observations stay in the env's own
     buffer, which the launch reads and overwrites.  Same return value as run_episodes; every tensor not derived from the action norm is
     bit-equal to it, and the action-norm tensors are the norm summed in index order (tests/test_population_eval_gpu.py,
-    tests/test_eval_step_h256_gpu.py)."""
+    tests/test_eval_step_h256_gpu.py).
+
+    ``whole_episodes=True`` replaces the per-step loop and its counter read-backs by kp1_eval_episodes: all env steps in one launch per
+    256 steps of the limit (a later call is skipped once no episode is alive).  Every returned tensor is bit-equal to the per-step form's
+    (tests/test_eval_episodes_gpu.py); the env handle is left with every episode at its own last step instead of stepped on in lock step."""
     if not isinstance(env, ArmKinematicVecEnv):
         raise TypeError("run_episodes_fused drives an ArmKinematicVecEnv (kp1_eval_step steps its handle)")
     E = env.n_envs
@@ -438,10 +473,17 @@ def run_episodes_fused(env: ArmKinematicVecEnv, mlp: Any, reset_options: dict[st
     act_mask = None if active is None else active.to(dev).to(u8).contiguous()
     native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs), None, None, ptr(act_mask), 0, thr, confirm, stream))
     limit = int(max_steps or (env.config.c.termination.max_episode_steps + 1))
-    for step in range(1, limit + 1):
-        if (step - 1) % _ALIVE_CHECK_EVERY == 0 and int(n_alive.item()) == 0:
-            break
-        native.check(L.kp1_eval_step(mlp._h, env._handle, ptr(env.obs), ptr(env.reward), ptr(env.done), C.byref(bufs), step, thr, confirm, stream))
+    if whole_episodes:
+        for first in range(1, limit + 1, _EPISODES_CAP):
+            if first > 1 and int(n_alive.item()) == 0:
+                break
+            native.check(L.kp1_eval_episodes(mlp._h, env._handle, ptr(env.obs), ptr(env.reward), ptr(env.done), C.byref(bufs), first,
+                                             min(first + _EPISODES_CAP - 1, limit), thr, confirm, stream))
+    else:
+        for step in range(1, limit + 1):
+            if (step - 1) % _ALIVE_CHECK_EVERY == 0 and int(n_alive.item()) == 0:
+                break
+            native.check(L.kp1_eval_step(mlp._h, env._handle, ptr(env.obs), ptr(env.reward), ptr(env.done), C.byref(bufs), step, thr, confirm, stream))
     res = {
         "success": flags[1].bool(), "final_position_error": metrics[0], "final_orientation_error": metrics[1], "min_position_error": metrics[2],
         "min_orientation_error": metrics[3], "final_action_magnitude": metrics[4], "final_dq_norm": metrics[5], "sum_action": metrics[6],
@@ -481,8 +523,12 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
                                  finisher_cfg: kcfg.EnvConfig | None, episodes: int = 50, seed: int = 700001,
                                  stage_indices: list[int] | None = None, handoff_confirm_steps: int = 2, gate_config: dict[str, Any] | None = None,
                                  artifact_root: str | Path | None = None, device: int = 0, obs_stride: int = 56,
-                                 one_launch: bool | None = None) -> dict[str, Any]:
+                                 one_launch: bool | None = None, whole_episodes: bool | None = None) -> dict[str, Any]:
     """evaluate_workspace_expansion_checkpoint with policies passed as callables (checkpoint loading is the caller's).
+
+    ``whole_episodes``: None (default) is this entry point's row of WHOLE_EPISODES_DEFAULT; True runs every phase through kp1_eval_episodes
+    (all env steps of the phase in one launch, same payload bit for bit) and raises ValueError for a phase that is not covered; False keeps
+    one launch per env step.
 
     ``one_launch``: None (default) runs a phase through run_episodes_fused -- one launch per env step -- when its policy is an InferencePolicy /
     PPO (or a bound ``predict`` of one) on a handle the step covers, and through run_episodes otherwise; False always takes run_episodes; True
@@ -500,7 +546,8 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
     if obs_stride != 56:
         env.set_obs_stride(obs_stride)
     a_res, hand = run_phase(env, approach_policy, {"initial_q": cat["initial_q"], "goal_q": cat["goal_q"], "goal_pose6": cat["goal_pose6"],
-                                                   "policy_mode": "approach"}, one_launch=one_launch, what="Approach", ready_cfg=r,
+                                                   "policy_mode": "approach"}, one_launch=one_launch, what="Approach",
+                            whole_episodes=whole_episodes, entry="evaluate_workspace_expansion", ready_cfg=r,
                             handoff_confirm_steps=handoff_confirm_steps)
     env.close()
     final_ready, has_hand, src = _handoff_sources(a_res, hand, r)
@@ -511,7 +558,8 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
             fenv.set_obs_stride(obs_stride)
         # rows without a handoff still need finite reset inputs; they are masked out of every result
         safe = {k: torch.where(has_hand[:, None], v, a_res[k]) for k, v in src.items()}
-        f_res, _ = run_phase(fenv, finisher_policy, _handoff_options(safe, "dock"), one_launch=one_launch, what="Finisher", active=has_hand)
+        f_res, _ = run_phase(fenv, finisher_policy, _handoff_options(safe, "dock"), one_launch=one_launch, what="Finisher",
+                             whole_episodes=whole_episodes, entry="evaluate_workspace_expansion", active=has_hand)
         fenv.close()
     cols = _eval_columns(a_res, final_ready, has_hand, f_res, handoff_confirm_steps)
     return _workspace_payload(cols, cat["goal_pose6"], approach_cfg=approach_cfg, stages=stages, episodes=episodes, seed=seed,
@@ -634,7 +682,8 @@ def check_population_eval(population: Any, artifact_roots: list[Any] | None) -> 
 def evaluate_workspace_expansion_population(*, population: Any, finisher_policy: Any, approach_cfg: kcfg.EnvConfig, finisher_cfg: kcfg.EnvConfig | None,
                                             episodes: int = 50, seed: int = 700001, stage_indices: list[int] | None = None,
                                             handoff_confirm_steps: int = 2, gate_config: dict[str, Any] | None = None,
-                                            artifact_roots: list[str | Path] | None = None, device: int = 0) -> list[dict[str, Any]]:
+                                            artifact_roots: list[str | Path] | None = None, device: int = 0,
+                                            whole_episodes: bool | None = None) -> list[dict[str, Any]]:
     """evaluate_workspace_expansion of every replica of a PopulationPPO at once: K payloads (and K sets of JSON files under
     ``artifact_roots[k]``), each what ``evaluate_workspace_expansion(approach_policy=population.replica(k).predict, ...)`` returns up to
     the summation order of the action norm.
@@ -644,8 +693,12 @@ def evaluate_workspace_expansion_population(*, population: Any, finisher_policy:
     The Finisher phase is one run over all K x E rows with the shared Finisher policy (``finisher_policy``: an InferencePolicy, stepped in
     one launch when kp1_eval_step covers its handle -- 64 / 128 wide, or 2x256 on the tile kernels -- and through run_episodes otherwise).
     Episodes of different replicas run in lock step until none of any replica is alive; a finished episode's bookkeeping is frozen, so the
-    extra steps change nothing in its block."""
+    extra steps change nothing in its block.
+
+    ``whole_episodes`` as in evaluate_workspace_expansion (None: this entry point's row of WHOLE_EPISODES_DEFAULT): True runs both phases
+    through kp1_eval_episodes and raises ValueError when the Finisher policy's handle is not covered."""
     K = check_population_eval(population, artifact_roots)
+    whole = whole_episodes_default("evaluate_workspace_expansion_population", whole_episodes)
     n_stages = approach_cfg.n_stages
     stages = stage_indices if stage_indices is not None else list(range(n_stages))
     stages = [int(np.clip(s, 0, n_stages - 1)) for s in stages]
@@ -659,7 +712,8 @@ def evaluate_workspace_expansion_population(*, population: Any, finisher_policy:
     if obs_stride != 56:
         env.set_obs_stride(obs_stride)
     tiled = {k: np.tile(cat[k], (K, 1)) for k in ("initial_q", "goal_q", "goal_pose6")}
-    a_res, hand = run_episodes_fused(env, population._mlp, {**tiled, "policy_mode": "approach"}, ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps)
+    a_res, hand = run_episodes_fused(env, population._mlp, {**tiled, "policy_mode": "approach"}, ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps,
+                                     whole_episodes=whole)
     env.close()
     final_ready, has_hand, src = _handoff_sources(a_res, hand, r)
     f_res = None
@@ -671,7 +725,9 @@ def evaluate_workspace_expansion_population(*, population: Any, finisher_policy:
         safe = {k: torch.where(has_hand[:, None], v, a_res[k]) for k, v in src.items()}
         fmlp = getattr(finisher_policy, "_mlp", None)
         if _is_fused_width(fmlp) and int(getattr(fmlp, "replicas", 1)) == 1:
-            f_res, _ = run_episodes_fused(fenv, fmlp, _handoff_options(safe, "dock"), active=has_hand)
+            f_res, _ = run_episodes_fused(fenv, fmlp, _handoff_options(safe, "dock"), active=has_hand, whole_episodes=whole)
+        elif whole_episodes:
+            raise _uncovered_whole_episodes("Finisher")
         else:
             f_res, _ = run_episodes(fenv, finisher_policy, _handoff_options(safe, "dock"), active=has_hand)
         fenv.close()

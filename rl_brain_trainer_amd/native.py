@@ -17,6 +17,7 @@ LIB_PATH = PKG_DIR / "libkp1.so"
 
 KP1_OK = 0
 REAL_F32, REAL_F64 = 0, 1
+EVAL_EPISODES_MAX_STEPS = 256   # include/kp1_ppo.h KP1_EVAL_EPISODES_MAX_STEPS: env steps of one kp1_eval_episodes call
 DONE_TERMINATED, DONE_TRUNCATED, DONE_SUCCESS, DONE_INVALID = 1, 2, 4, 8
 FLAG_PRE_NEAR_HIT, FLAG_NEAR_HIT, FLAG_SUCCESS = 1, 2, 4
 
@@ -83,6 +84,7 @@ def load() -> C.CDLL:
     L.kp1_get_info.argtypes = [vp, C.POINTER(kcfg.InfoView)]
     L.kp1_eval_accumulate.argtypes = [vp, C.POINTER(EvalBuffers), vp, vp, vp, i32, vp, i32, vp]
     L.kp1_eval_step.argtypes = [vp, vp, vp, vp, vp, C.POINTER(EvalBuffers), i32, vp, i32, vp]
+    L.kp1_eval_episodes.argtypes = [vp, vp, vp, vp, vp, C.POINTER(EvalBuffers), i32, i32, vp, i32, vp]
     L.kp1_get_reward_components.argtypes = [vp, C.POINTER(vp), C.POINTER(i32)]
     L.kp1_enable_reward_components.argtypes = [vp, i32]
     L.kp1_component_name.argtypes = [i32, i32]

@@ -53,6 +53,13 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--learning-rate", type=float)
     p.add_argument("--log-every", type=int, default=1)
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--whole-episode-eval", dest="whole_episode_eval", action="store_const", const=True, default=None,
+                   help="run the gate and final evaluations with all env steps of a phase in one launch (kp1_eval_episodes) where the one-launch "
+                        "step covers the phase; same results bit for bit")
+    g.add_argument("--per-step-eval", dest="whole_episode_eval", action="store_const", const=False,
+                   help="keep one launch per env step (kp1_eval_step) in those evaluations; without either flag every evaluation takes its "
+                        "measured default (evaluate.WHOLE_EPISODES_DEFAULT), so the flag that names the default is a no-op")
     p.add_argument("--multi-launch-eval", action="store_true",
                    help="with --seed: run the gate and final evaluations as the launch sequence per env step (evaluate.run_episodes) instead of "
                         "the one-launch step (kp1_eval_step); the two forms agree bit for bit except in the action-magnitude floats "
@@ -72,7 +79,8 @@ class WorkspaceEvalGate:
     envs; here the check runs after every PPO iteration (n_envs * n_steps timesteps), so evaluations land on iteration boundaries."""
 
     def __init__(self, *, artifact_root: Path, approach_cfg: kcfg.EnvConfig, finisher_policy, finisher_cfg: kcfg.EnvConfig | None, eval_interval: int,
-                 episodes: int, seed: int, stage_indices: list[int], gate_config: dict[str, Any], device: int = 0, one_launch: bool | None = None) -> None:
+                 episodes: int, seed: int, stage_indices: list[int], gate_config: dict[str, Any], device: int = 0, one_launch: bool | None = None,
+                 whole_episodes: bool | None = None) -> None:
         self.artifact_root = artifact_root
         self.approach_cfg, self.finisher_policy, self.finisher_cfg = approach_cfg, finisher_policy, finisher_cfg
         self.eval_interval = max(int(eval_interval), 1)
@@ -82,6 +90,7 @@ class WorkspaceEvalGate:
         self.gate_config = dict(gate_config)
         self.device = device
         self.one_launch = one_launch        # evaluate.evaluate_workspace_expansion's switch (None: the one-launch step where covered)
+        self.whole_episodes = whole_episodes    # likewise (None: the entry point's measured default)
         self.candidates_dir = artifact_root / "gate_candidates"
         self.eval_dir = artifact_root / "gate_evals"
         self.best_dir = artifact_root / "best_checkpoint"
@@ -129,7 +138,8 @@ class WorkspaceEvalGate:
         summary = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, finisher_policy=self.finisher_policy, approach_cfg=self.approach_cfg,
                                                   finisher_cfg=self.finisher_cfg, episodes=self.episodes, seed=self.seed, stage_indices=self.stage_indices,
                                                   gate_config=self.gate_config, artifact_root=self.eval_root(ppo.num_timesteps),
-                                                  device=self.device, obs_stride=ppo.obs_w, one_launch=self.one_launch)
+                                                  device=self.device, obs_stride=ppo.obs_w, one_launch=self.one_launch,
+                                                  whole_episodes=self.whole_episodes)
         return self.record(ppo, env_cfg, candidate, summary)
 
 
@@ -148,7 +158,7 @@ def population_gate_iteration(gates: dict[int, WorkspaceEvalGate], pop, env_cfg:
     payloads = ev.evaluate_workspace_expansion_population(population=pop, finisher_policy=g0.finisher_policy, approach_cfg=g0.approach_cfg,
                                                           finisher_cfg=g0.finisher_cfg, episodes=g0.episodes, seed=g0.seed, stage_indices=g0.stage_indices,
                                                           gate_config=g0.gate_config, artifact_roots=[gates[k].eval_root(pop.num_timesteps) for k in range(pop.K)],
-                                                          device=g0.device)
+                                                          device=g0.device, whole_episodes=g0.whole_episodes)
     return [gates[k].record(reps[k], env_cfg, candidates[k], payloads[k]) for k in range(pop.K)]
 
 
@@ -203,7 +213,8 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     finisher_policy, finisher_cfg = _load_finisher(ws, local_rank)
     gate_cfg = dict(ws.get("gate", {}) or {})
     if rank == 0 and not args.no_gate_callback and finisher_policy is not None:
-        gate = _make_gate(root, env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, local_rank, one_launch=False if args.multi_launch_eval else None)
+        gate = _make_gate(root, env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, local_rank, one_launch=False if args.multi_launch_eval else None,
+                          whole_episodes=args.whole_episode_eval)
 
     t0 = time.time()
     total = int(algo.get("total_timesteps", 100_000))
@@ -267,11 +278,11 @@ def _load_finisher(ws: dict[str, Any], device: int):
 
 
 def _make_gate(root: Path, env_cfg: kcfg.EnvConfig, finisher_policy, finisher_cfg, ws: dict[str, Any], gate_cfg: dict[str, Any], device: int,
-               one_launch: bool | None = None) -> WorkspaceEvalGate:
+               one_launch: bool | None = None, whole_episodes: bool | None = None) -> WorkspaceEvalGate:
     return WorkspaceEvalGate(artifact_root=root, approach_cfg=env_cfg, finisher_policy=finisher_policy, finisher_cfg=finisher_cfg,
                              eval_interval=int(ws.get("eval_interval", 200_000)), episodes=int(ws.get("gate_eval_episodes", 24)),
                              seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)), gate_config=gate_cfg, device=device,
-                             one_launch=one_launch)
+                             one_launch=one_launch, whole_episodes=whole_episodes)
 
 
 def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, n_envs: int, world: int, curriculum, finisher_policy, finisher_cfg,
@@ -293,7 +304,8 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, 
                                                          finisher_cfg=finisher_cfg, episodes=int(ws.get("final_eval_episodes", 80)),
                                                          seed=int(ws.get("eval_seed", 700001)), stage_indices=list(range(env_cfg.n_stages)),
                                                          gate_config=gate_cfg, artifact_root=root / "final_eval", device=device, obs_stride=ppo.obs_w,
-                                                         one_launch=False if getattr(args, "multi_launch_eval", False) else None)
+                                                         one_launch=False if getattr(args, "multi_launch_eval", False) else None,
+                                                         whole_episodes=getattr(args, "whole_episode_eval", None))
         final_eval = {k: v for k, v in final_eval.items() if k != "target_rows"}
         for name in ("stage_metrics.json", "workspace_failure_report.json", "best_model_selection_summary.json"):
             if (root / "final_eval" / name).exists():
@@ -346,7 +358,8 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
     gate_cfg = dict(ws.get("gate", {}) or {})
     gates = {}
     if not args.no_gate_callback and finisher_policy is not None:
-        gates = {k: _make_gate(roots[k], env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, device) for k in range(len(seeds))}
+        gates = {k: _make_gate(roots[k], env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, device, whole_episodes=args.whole_episode_eval)
+                 for k in range(len(seeds))}
 
     fused_eval = not args.per_replica_eval
 
@@ -367,7 +380,8 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
         finals = ev.evaluate_workspace_expansion_population(population=pop, finisher_policy=finisher_policy, approach_cfg=env_cfg, finisher_cfg=finisher_cfg,
                                                             episodes=int(ws.get("final_eval_episodes", 80)), seed=int(ws.get("eval_seed", 700001)),
                                                             stage_indices=list(range(env_cfg.n_stages)), gate_config=gate_cfg,
-                                                            artifact_roots=[r / "final_eval" for r in roots], device=device)
+                                                            artifact_roots=[r / "final_eval" for r in roots], device=device,
+                                                            whole_episodes=getattr(args, "whole_episode_eval", None))
     for k, s in enumerate(seeds):
         rep = pop.replica(k)
         extra = {"seed": s} if overrides is None else {"seed": s, "replica": names[k], "overrides": dict(overrides[k])}

@@ -46,6 +46,13 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--eval-episodes", type=int, default=512)
     p.add_argument("--log-every", type=int, default=1)
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--whole-episode-eval", dest="whole_episode_eval", action="store_const", const=True, default=None,
+                   help="run the final dock evaluation with all its env steps in one launch (kp1_eval_episodes; implies --one-launch-eval); "
+                        "same summary as --one-launch-eval")
+    g.add_argument("--per-step-eval", dest="whole_episode_eval", action="store_const", const=False,
+                   help="keep one launch per env step (kp1_eval_step) in that evaluation; without either flag it takes its "
+                        "measured default (evaluate.WHOLE_EPISODES_DEFAULT), so the flag that names the default is a no-op")
     p.add_argument("--one-launch-eval", action="store_true",
                    help="run the final dock evaluation with the one-launch step (kp1_eval_step) instead of the launch sequence per env step "
                         "(evaluate.run_episodes, the default here: the one-launch form has not been timed on this workload); the summaries "
@@ -53,15 +60,17 @@ def build_arg_parser() -> argparse.ArgumentParser:
     return p
 
 
-def evaluate_dock(ppo: PPO, env_cfg: kcfg.EnvConfig, *, episodes: int, seed: int, device: int, one_launch: bool | None = None) -> dict[str, Any]:
+def evaluate_dock(ppo: PPO, env_cfg: kcfg.EnvConfig, *, episodes: int, seed: int, device: int, one_launch: bool | None = None,
+                  whole_episodes: bool | None = None) -> dict[str, Any]:
     """Deterministic dock evaluation on freshly sampled dock resets (eval_dock.py's summary keys that downstream scripts read).
-    ``one_launch`` as in evaluate.evaluate_workspace_expansion; either way the resets are drawn by env.reset(options=None) from the env's RNG."""
+    ``one_launch`` and ``whole_episodes`` as in evaluate.evaluate_workspace_expansion (None: the "evaluate_dock" row of
+    evaluate.WHOLE_EPISODES_DEFAULT); either way the resets are drawn by env.reset(options=None) from the env's RNG."""
     from . import evaluate as ev
 
     env = ArmKinematicVecEnv(env_cfg, episodes, device=device, seed=seed)
     if ppo.obs_w != 56:
         env.set_obs_stride(ppo.obs_w)
-    res, _ = ev.run_phase(env, ppo.predict, None, one_launch=one_launch, what="dock")
+    res, _ = ev.run_phase(env, ppo.predict, None, one_launch=one_launch, what="dock", whole_episodes=whole_episodes, entry="evaluate_dock")
     env.close()
     succ = res["success"].float()
     return {"episodes": int(episodes), "success_rate": float(succ.mean()), "mean_final_position_error": float(res["final_position_error"].mean()),
@@ -150,7 +159,8 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, cfg: dic
     latest = root / "model_latest"
     checkpoint.save(latest, ppo, env_cfg)
     eval_summary = evaluate_dock(ppo, env_cfg, episodes=args.eval_episodes, seed=seed + 10_000, device=device,
-                                 one_launch=None if getattr(args, "one_launch_eval", False) else False)
+                                 one_launch=None if getattr(args, "one_launch_eval", False) or getattr(args, "whole_episode_eval", None) else False,
+                                 whole_episodes=getattr(args, "whole_episode_eval", None))
     (root / "dock_eval").mkdir(exist_ok=True)
     (root / "dock_eval" / "dock_eval_summary.json").write_text(json.dumps(eval_summary, indent=2))
     summary = {"policy_type": "dock", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "config": cfg, "model_path": str(latest) + ".zip",

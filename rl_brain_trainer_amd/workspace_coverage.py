@@ -496,10 +496,12 @@ _COLS = ("success", "ready_hit", "ready_dwell", "coarse_dwell",
 
 
 def _run_pairs_columns(*, pairs, starts_by_id, targets_by_id, approach_policy, approach_cfg, finisher_policy, finisher_cfg, handoff_confirm_steps: int,
-                       device: int, obs_stride: int, seed: int, first_env_id: int = 0, one_launch: bool | None = None):
+                       device: int, obs_stride: int, seed: int, first_env_id: int = 0, one_launch: bool | None = None,
+                       whole_episodes: bool | None = None):
     """one vectorised Approach run over `pairs` (explicit initial state and goal per env), then the handed-off ones continue in a
     vectorised Finisher run -> f64 [len(pairs), len(_COLS)] on the device.  Env k of this call is global env first_env_id + k.
-    ``one_launch`` as in evaluate.evaluate_workspace_expansion, for both phases."""
+    ``one_launch`` and ``whole_episodes`` as in evaluate.evaluate_workspace_expansion, for both phases (``whole_episodes=None``: the
+    "run_pairs" row of evaluate.WHOLE_EPISODES_DEFAULT)."""
     import torch
 
     from . import evaluate as ev
@@ -527,7 +529,8 @@ def _run_pairs_columns(*, pairs, starts_by_id, targets_by_id, approach_policy, a
     env = ArmKinematicVecEnv(approach_cfg, E, device=device, seed=seed, first_env_id=first_env_id)
     if obs_stride != 56:
         env.set_obs_stride(obs_stride)
-    a_res, hand = ev.run_phase(env, approach_policy, opts, one_launch=one_launch, what="Approach", ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps)
+    a_res, hand = ev.run_phase(env, approach_policy, opts, one_launch=one_launch, what="Approach", whole_episodes=whole_episodes, entry="run_pairs",
+                               ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps)
     env.close()
     final_ready = ev.finisher_ready(a_res["final_position_error"], a_res["final_orientation_error"], a_res["final_action_magnitude"], a_res["final_dq_norm"], r)
     has_hand = final_ready | hand["valid"]
@@ -542,7 +545,8 @@ def _run_pairs_columns(*, pairs, starts_by_id, targets_by_id, approach_policy, a
         if obs_stride != 56:
             fenv.set_obs_stride(obs_stride)
         safe = {k: torch.where(has_hand[:, None], v, a_res[k]) for k, v in src.items()}
-        f_res, _ = ev.run_phase(fenv, finisher_policy, ev._handoff_options(safe, "dock"), one_launch=one_launch, what="Finisher", active=has_hand)
+        f_res, _ = ev.run_phase(fenv, finisher_policy, ev._handoff_options(safe, "dock"), one_launch=one_launch, what="Finisher",
+                                whole_episodes=whole_episodes, entry="run_pairs", active=has_hand)
         fenv.close()
         for k in final:
             final[k] = torch.where(has_hand, f_res[k], final[k])
@@ -578,9 +582,11 @@ def _rows_from_columns(pairs: list[dict[str, Any]], cols: np.ndarray, r) -> list
 
 def run_pairs(*, pairs: list[dict[str, Any]], starts_by_id: dict[str, dict[str, Any]], targets_by_id: dict[str, dict[str, Any]], approach_policy,
               approach_cfg: kcfg.EnvConfig, finisher_policy=None, finisher_cfg: kcfg.EnvConfig | None = None, handoff_confirm_steps: int = 2,
-              device: int = 0, obs_stride: int = 56, seed: int = 0, dist=None, one_launch: bool | None = None) -> list[dict[str, Any]]:
+              device: int = 0, obs_stride: int = 56, seed: int = 0, dist=None, one_launch: bool | None = None,
+              whole_episodes: bool | None = None) -> list[dict[str, Any]]:
     """_run_pairs: every pair is one env of a vectorised Approach run, then the handed-off ones continue in a vectorised Finisher run.
-    ``one_launch`` as in evaluate.evaluate_workspace_expansion (None: one launch per env step where the policy's handle is covered).
+    ``one_launch`` as in evaluate.evaluate_workspace_expansion (None: one launch per env step where the policy's handle is covered);
+    ``whole_episodes`` likewise (None: the "run_pairs" row of evaluate.WHOLE_EPISODES_DEFAULT; True: all env steps of a phase in one launch).
 
     Data parallel (``dist`` = ppo.Dist of an initialised process group; BASELINE configs[3]: 65536 envs = 8 x 8192): the pair list --
     identical on every rank, it is a function of the seed -- is cut into contiguous rank blocks, each rank runs its block on its own GPU
@@ -593,7 +599,7 @@ def run_pairs(*, pairs: list[dict[str, Any]], starts_by_id: dict[str, dict[str, 
         return []
     common = dict(starts_by_id=starts_by_id, targets_by_id=targets_by_id, approach_policy=approach_policy, approach_cfg=approach_cfg,
                   finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, handoff_confirm_steps=handoff_confirm_steps, device=device,
-                  obs_stride=obs_stride, seed=seed, one_launch=one_launch)
+                  obs_stride=obs_stride, seed=seed, one_launch=one_launch, whole_episodes=whole_episodes)
     if dist is not None and dist.enabled:
         world, per = dist.world_size, (E + dist.world_size - 1) // dist.world_size
         lo = min(dist.rank * per, E)
@@ -623,10 +629,11 @@ def evaluate_full_workspace_coverage(*, approach_policy, approach_cfg: kcfg.EnvC
                                      finisher_cfg: kcfg.EnvConfig | None = None, seed: int = 940001, episodes_per_split: int = 96,
                                      stage_samples_per_stage: int = 96, random_target_samples: int = 384, random_start_samples: int = 384,
                                      pair_count: int = 2048, handoff_confirm_steps: int = 2, include_home_stage_eval: bool = True, device: int = 0,
-                                     obs_stride: int = 56, dist=None, one_launch: bool | None = None) -> dict[str, Any]:
+                                     obs_stride: int = 56, dist=None, one_launch: bool | None = None,
+                                     whole_episodes: bool | None = None) -> dict[str, Any]:
     """evaluate_full_workspace_coverage with policies passed as callables (checkpoint loading is the caller's); same artefact
     files under ``artifact_root`` (maps/, *_random_start_eval_summary.json, workspace_bucket_metrics.json,
-    full_workspace_coverage_summary.json, workspace_failure_report.json, home_start_stage_eval/).  ``one_launch`` as in
+    full_workspace_coverage_summary.json, workspace_failure_report.json, home_start_stage_eval/).  ``one_launch`` and ``whole_episodes`` as in
     evaluate.evaluate_workspace_expansion, for every episode run."""
     from . import evaluate as ev
 
@@ -655,7 +662,8 @@ def evaluate_full_workspace_coverage(*, approach_policy, approach_cfg: kcfg.EnvC
         selected = select_pairs(pairs, mode=split, limit=episodes_per_split, rng=rng)
         rows = run_pairs(pairs=selected, starts_by_id=starts_by_id, targets_by_id=targets_by_id, approach_policy=approach_policy, approach_cfg=approach_cfg,
                          finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, handoff_confirm_steps=handoff_confirm_steps, device=device,
-                         obs_stride=obs_stride, seed=seed, dist=dist, one_launch=one_launch)
+                         obs_stride=obs_stride, seed=seed, dist=dist, one_launch=one_launch,
+                         whole_episodes=whole_episodes)
         split_rows[split] = rows
         if root is not None:
             _write_json(root / f"{split}_random_start_eval_summary.json", {"summary": summarize(rows), "episode_rows": rows})
@@ -685,7 +693,7 @@ def evaluate_full_workspace_coverage(*, approach_policy, approach_cfg: kcfg.EnvC
                                                finisher_cfg=finisher_cfg, episodes=max(8, min(episodes_per_split // 4, 32)), seed=seed + 4,
                                                stage_indices=list(range(approach_cfg.n_stages)), handoff_confirm_steps=handoff_confirm_steps,
                                                artifact_root=(root / "home_start_stage_eval") if root is not None else None, device=device, obs_stride=obs_stride,
-                                               one_launch=one_launch)
+                                               one_launch=one_launch, whole_episodes=whole_episodes)
         coverage["home_start_stage_metrics"] = home["stage_metrics"]
     if root is not None:
         _write_json(root / "full_workspace_coverage_summary.json", coverage)
