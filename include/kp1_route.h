@@ -237,6 +237,28 @@ struct kp1_mlp;
 int kp1_mlp_forward_route_step(struct kp1_mlp* m, kp1_route* r, const float* obs, int32_t obs_stride, const float* noise, float* value,
                                float* action, float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream);
 
+/* ---- the chained evaluator's lock step in ONE launch (route_chain_step_kernel, hidden 64 / 128, fp32) ------------------------------------------
+ * kp1_mlp_forward_route_chain_step = kp1_mlp_forward(m, obs, noise NULL, clipped -> action) + kp1_route_chain_step(r, chain, action, next_obs,
+ * reward, done, tags), bit for bit for every row whose chain is alive.  The one difference: a row whose chain has ended is NOT stepped; it gets
+ * its {-1, -1} tag and nothing else of it is written (env planes, next_obs / action / reward / done entries).  kp1_route_chain_run makes n_steps
+ * such lock steps in one launch, in place on obs; a tile whose rows have all ended leaves early.  Both clear and then leave in the chain's
+ * n_alive the rows still running after the last step, and launch on `stream`.
+ * Refused before any launch (status + kp1_last_error, outputs untouched): NULL required arguments, hidden 256, what kp1_route_chain_step
+ * refuses (an fp64 base env, a sequence handle, recorded reward components, an attached prefix tracker), an obs_dim / obs_stride / replica-count
+ * mismatch (a single route handle of K C envs serves K replicas), a stride different from kp1_route_set_obs_stride, an env count that is no
+ * multiple of K, n_waypoints > KP1_ROUTE_FUSED_MAX_WAYPOINTS, different devices, a chain of another handle or env count, next_obs overlapping
+ * obs partially (next_obs == obs is the evaluator's normal use), n_steps outside [1, KP1_ROUTE_CHAIN_RUN_MAX_STEPS]. */
+#define KP1_ROUTE_CHAIN_RUN_MAX_STEPS 1024   /* lock steps of one launch; the host splits longer chains into consecutive calls */
+
+/* kp1_mlp_forward(m, obs, noise NULL, clipped -> action) + kp1_route_chain_step(r, chain, action, next_obs, reward, done, tags), ONE launch.
+ * next_obs == obs (in place) or disjoint from obs; action and tags may be NULL. */
+int kp1_mlp_forward_route_chain_step(struct kp1_mlp* m, kp1_route* r, kp1_route_chain* chain, const float* obs, int32_t obs_stride,
+                                     float* action, float* next_obs, float* reward, uint8_t* done, int32_t* tags, void* stream);
+
+/* n_steps lock steps in ONE launch, in place on obs; leaves in the chain's n_alive the rows still running after the last step */
+int kp1_route_chain_run(struct kp1_mlp* m, kp1_route* r, kp1_route_chain* chain, float* obs, int32_t obs_stride,
+                        float* reward, uint8_t* done, int32_t n_steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

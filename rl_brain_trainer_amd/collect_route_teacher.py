@@ -62,7 +62,7 @@ def anchor_dataset_arrays(tags: np.ndarray, obs: np.ndarray, actions: np.ndarray
 
 
 def collect_teacher_rollout(*, checkpoint_path: Path, config_path: Path, route_path: Path, artifact_root: Path, start_index: int = 1,
-                            end_index: int = 120, device: int = 0, block_steps: int = BLOCK_STEPS) -> dict[str, Any]:
+                            end_index: int = 120, device: int = 0, block_steps: int = BLOCK_STEPS, one_launch: bool = False) -> dict[str, Any]:
     import torch
 
     from .ppo import InferencePolicy
@@ -101,8 +101,11 @@ def collect_teacher_rollout(*, checkpoint_path: Path, config_path: Path, route_p
         while taken < bound:
             n = min(S, bound - taken)
             for s in range(n):      # step s reads slice s and writes slice s + 1
-                mlp.forward(obs_buf[s], clipped=act_buf[s])
-                chain.step(act_buf[s], obs_buf[s + 1], reward, done, tag_buf[s])
+                if one_launch:
+                    chain.forward_step(mlp, obs_buf[s], obs_buf[s + 1], reward, done, action=act_buf[s], tags=tag_buf[s])
+                else:
+                    mlp.forward(obs_buf[s], clipped=act_buf[s])
+                    chain.step(act_buf[s], obs_buf[s + 1], reward, done, tag_buf[s])
             taken += n
             tags.append(tag_buf[:n].cpu().numpy())
             obs_rows.append(obs_buf[:n].cpu().numpy())
@@ -143,13 +146,16 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--start-index", type=int, default=1)
     p.add_argument("--end-index", type=int, default=120)
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--one-launch", action="store_true", help="forward, step and hand-over of every lock step in ONE launch "
+                   "(RouteChain.forward_step; hidden 64 / 128); the files are byte-equal to the default's")
     return p
 
 
 def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
     return collect_teacher_rollout(checkpoint_path=Path(args.checkpoint), config_path=Path(args.config), route_path=Path(args.route_path),
-                                   artifact_root=Path(args.artifact_root), start_index=args.start_index, end_index=args.end_index, device=args.device)
+                                   artifact_root=Path(args.artifact_root), start_index=args.start_index, end_index=args.end_index, device=args.device,
+                                   one_launch=args.one_launch)
 
 
 if __name__ == "__main__":

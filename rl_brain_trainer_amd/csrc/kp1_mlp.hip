@@ -1441,6 +1441,7 @@ __global__ void anchor_count_kernel(int* __restrict__ actor_extra) { *actor_extr
 // (new kernels go after the tile kernels: including them earlier moved the tile kernels' addresses)
 #include "kp1_route_step.inc"
 #include "kp1_route_rollout_step.inc"
+#include "kp1_route_chain_step.inc"
 
 }  // namespace
 
@@ -2139,6 +2140,99 @@ int kp1_mlp_forward_route_step(kp1_mlp* m, kp1_route* r, const float* obs, int32
   else return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step: unexpected padded observation width");
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
+}
+
+}  // extern "C"
+
+namespace {
+template <int INP, bool EPISODE>
+void launch_route_chain_step(bool pop, dim3 grid, hipStream_t stream, const RouteChainStepArgs& a) {
+  if (pop) hipLaunchKernelGGL((route_chain_step_kernel<INP, true, EPISODE>), grid, dim3(ES_NTH), 0, stream, a);
+  else hipLaunchKernelGGL((route_chain_step_kernel<INP, false, EPISODE>), grid, dim3(ES_NTH), 0, stream, a);
+}
+
+// kp1_mlp_forward_route_chain_step (EPISODE false, one lock step) and kp1_route_chain_run (EPISODE true, n_steps of them in place): every refusal,
+// then the counter's memset and the one launch
+template <bool EPISODE>
+int route_chain_step_launch(const char* who, kp1_mlp* m, kp1_route* r, kp1_route_chain* c, const float* obs, int32_t obs_stride, float* action,
+                            float* next_obs, float* reward, uint8_t* done, int32_t* tags, int32_t n_steps, hipStream_t stream) {
+  const std::string w(who);
+  if (!m || !r || !c || !obs || !next_obs || !reward || !done) return fail(KP1_ERR_INVALID, "NULL argument to " + w);
+  if (m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, w + " covers hidden 64 / 128 (the layer-wise layout); hidden 256 takes the launch sequence");
+  if (const char* why = kp1::route_chain_refusal(r)) return fail(KP1_ERR_UNSUPPORTED, why);
+  if (c->owner != r) return fail(KP1_ERR_INVALID, w + ": the chain belongs to another route handle");
+  if ((int64_t)c->n_rows != r->n) return fail(KP1_ERR_INVALID, w + ": the chain was created for another env count");
+  const int obs_dim = r->cfg.include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM;
+  if (m->L.IN != obs_dim) return fail(KP1_ERR_INVALID, w + ": the MLP handle's obs_dim differs from the route handle's");
+  if (obs_stride != m->L.IN && obs_stride != m->L.INP)
+    return fail(KP1_ERR_INVALID, w + ": obs_stride must be the observation width (56 / 80) or its padded width (64 / 128)");
+  if (obs_stride != r->obs_stride) return fail(KP1_ERR_INVALID, w + ": obs_stride differs from the route handle's (kp1_route_set_obs_stride)");
+  if (r->n_waypoints > KP1_ROUTE_FUSED_MAX_WAYPOINTS)
+    return fail(KP1_ERR_UNSUPPORTED, w + ": the route has more than KP1_ROUTE_FUSED_MAX_WAYPOINTS waypoints (the joint table overlays the kernel's LDS tiles)");
+  // a chain's rows are replica-major on any handle: a single route handle of K C envs serves a policy handle of K replicas
+  if (r->n_replicas != 1 && r->n_replicas != m->K) return fail(KP1_ERR_INVALID, w + ": the route handle's replica count differs from the MLP handle's");
+  if (EPISODE && (n_steps < 1 || n_steps > KP1_ROUTE_CHAIN_RUN_MAX_STEPS))
+    return fail(KP1_ERR_INVALID, w + ": n_steps must be in [1, KP1_ROUTE_CHAIN_RUN_MAX_STEPS] (1024); split a longer chain into consecutive calls");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  RouteChainStepArgs a{};
+  int mode = 0, device = 0, pop_replicas = 0, pop_form = 0;
+  int64_t n_envs = 0;
+  // the base step as route_launch_step launches it: the wrapper's scratch at pitch 56, no terminal observation, no auto-reset.  Refuses f64
+  // base handles, recorded base reward components and a bound handle in a mode kp1_step refuses.
+  rc = kp1::env_step_args_f32_population(r->base, &a.fwd.env, sizeof a.fwd.env, r->base_obs, r->base_reward, r->bytes + 4 * r->n, nullptr, 0, &mode, &n_envs,
+                                         &device, &pop_replicas, &pop_form);
+  if (rc != KP1_OK) return rc;
+  a.fwd.env.obs_stride = KP1_OBS_DIM;
+  if (device != m->device) return fail(KP1_ERR_INVALID, "the route handle and the MLP workspace live on different devices");
+  if (mode != KP1_MODE_APPROACH) return fail(KP1_ERR_UNSUPPORTED, w + ": the route wrappers drive an approach-mode base env");
+  if (pop_replicas > 0 && pop_replicas != m->K) return fail(KP1_ERR_INVALID, w + ": the base env's population replica count differs from the MLP handle's");
+  if (n_envs != r->n || n_envs <= 0 || n_envs % m->K != 0) return fail(KP1_ERR_INVALID, w + ": the env count must be a multiple of the handle's replica count");
+  if (n_envs / m->K > m->max_batch) return fail(KP1_ERR_INVALID, "more envs than the workspace max_batch");
+  if (!r->fused_actions) return fail(KP1_ERR_UNSUPPORTED, w + " runs on an fp32 route handle");
+  if (next_obs != obs) {  // a workgroup reads and writes its own rows only, all reads before the writes: exact aliasing is the evaluator's normal use
+    const float* obs_end = obs + n_envs * obs_stride;
+    if (next_obs < obs_end && obs < next_obs + n_envs * (int64_t)r->obs_stride)
+      return fail(KP1_ERR_INVALID, w + ": next_obs must be obs itself (in place) or not overlap it");
+  }
+  const int Hp = m->Hp, INP = m->L.INP;
+  RolloutStepArgs& f = a.fwd;
+  f.obs = obs; f.obs_stride = obs_stride;
+  f.w1 = m->k.w1p; f.b1 = m->k.b1; f.w2 = m->k.w2; f.b2 = m->k.b2; f.w3 = m->k.w3; f.b3 = m->k.b3; f.log_std = m->k.log_std;
+  f.r_w1 = (unsigned)(2 * Hp * INP); f.r_w2 = (unsigned)(2 * Hp * Hp); f.r_b = (unsigned)(2 * Hp); f.r_w3 = (unsigned)(HEADS * Hp); f.r_b3 = (unsigned)HEADS;
+  f.n_w1 = (unsigned)(Hp * INP); f.n_w2 = (unsigned)(Hp * Hp); f.n_b = (unsigned)Hp;
+  f.noise = nullptr; f.value = nullptr; f.action = action; f.log_prob = nullptr;
+  f.n = (int)(n_envs / m->K);
+  f.Kreal = obs_stride >= INP ? INP : m->L.IN;
+  RouteStepArgs<float>& s = a.route;
+  s.st = f.env.st; s.cfg = f.env.cfg; s.smp = f.env.smp; s.rc = r->dev_cfg; s.rt = route_table_of(r); s.rs = route_state_of<float>(r);
+  s.actions = r->fused_actions; s.base_done = r->bytes + 4 * r->n; s.obs = next_obs; s.reward = reward; s.done = done; s.terminal_obs = nullptr;
+  s.obs_dim = obs_dim; s.obs_stride = r->obs_stride; s.auto_reset = 0;
+  a.ch = c->d; a.tags = tags; a.clipped = r->fused_actions; a.n_steps = EPISODE ? n_steps : 1;
+  if (INP != ES_INP && INP != RR_MAX_INP) return fail(KP1_ERR_UNSUPPORTED, w + ": unexpected padded observation width");
+  HIP_TRY(hipMemsetAsync(c->d.n_alive, 0, sizeof(int32_t), stream));
+  const dim3 grid((unsigned)((f.n + ES_BM - 1) / ES_BM), (unsigned)m->K);
+  if (INP == ES_INP) launch_route_chain_step<ES_INP, EPISODE>(pop_form != 0, grid, stream, a);
+  else launch_route_chain_step<RR_MAX_INP, EPISODE>(pop_form != 0, grid, stream, a);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// kp1_mlp_forward (noise NULL, clipped) + kp1_route_chain_step in one launch (include/kp1_route.h): route_chain_step_kernel<.., false>
+int kp1_mlp_forward_route_chain_step(kp1_mlp* m, kp1_route* r, kp1_route_chain* chain, const float* obs, int32_t obs_stride, float* action,
+                                     float* next_obs, float* reward, uint8_t* done, int32_t* tags, void* stream) {
+  return route_chain_step_launch<false>("kp1_mlp_forward_route_chain_step", m, r, chain, obs, obs_stride, action, next_obs, reward, done, tags, 1,
+                                        (hipStream_t)stream);
+}
+
+// n_steps lock steps in one launch, in place on obs: route_chain_step_kernel<.., true>
+int kp1_route_chain_run(kp1_mlp* m, kp1_route* r, kp1_route_chain* chain, float* obs, int32_t obs_stride, float* reward, uint8_t* done,
+                        int32_t n_steps, void* stream) {
+  return route_chain_step_launch<true>("kp1_route_chain_run", m, r, chain, obs, obs_stride, nullptr, obs, reward, done, nullptr, n_steps,
+                                       (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -826,37 +826,7 @@ int kp1_route_curriculum_read_replica(kp1_route* r, const kp1_route_curriculum_s
 // stream: an explicit-state reset with a goal takes no branch of reset_env that loads one.
 namespace {
 
-struct RouteChainDev {   // device arrays [R] unless noted
-  const int32_t *start, *end;
-  int32_t *wp, *steps, *first_ready, *max_streak, *n_records;
-  uint8_t* alive;
-  float *min_pos, *min_ori, *min_q;
-  kp1_route_chain_record* records;   // [R][max_len]
-  int32_t* n_alive;                  // [1]
-  int max_len, stop_on_failure;
-};
-
-template <typename R>
-struct RouteChainArgs {
-  EnvState<R> st; const DevCfg<R>* cfg; const DevSampler* smp; const RouteDevCfg* rc; RouteTable rt; RouteState<R> rs;
-  RouteChainDev ch; const uint8_t* done; float* obs; int32_t* tags; int obs_dim, obs_stride;
-};
-
-// the bookkeeping of a fresh episode: the minima of position and orientation error start from the planes reset_env wrote, and the record
-// keeps q as the reset left it (the evaluator's initial joint-space error is taken from it on the host)
-template <typename R>
-__device__ __forceinline__ void route_chain_open(const EnvState<R>& st, const RouteChainDev& ch, int64_t i, int waypoint) {
-  ch.wp[i] = waypoint; ch.steps[i] = 0; ch.first_ready[i] = -1; ch.max_streak[i] = 0;
-  ch.min_pos[i] = (float)st.r(F_POS_ERR, i);
-  ch.min_ori[i] = (float)st.r(F_ORI_ERR, i);
-  ch.min_q[i] = std::numeric_limits<float>::infinity();
-  const int slot = waypoint - ch.start[i];
-  if (slot >= 0 && slot < ch.max_len) {
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) ch.records[i * ch.max_len + slot].start_q[k] = st.q_load(k, i);
-  }
-}
-
+// RouteChainDev, RouteChainArgs and route_chain_open: kp1_route_step.inc (kp1_mlp.hip runs the chain step inside its one-launch kernel too)
 template <typename R>
 __global__ void __launch_bounds__(64) kp1_route_chain_begin_kernel(const EnvState<R> st, const RouteChainDev ch) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -874,58 +844,7 @@ __global__ void __launch_bounds__(64) kp1_route_chain_kernel(const RouteChainArg
   const RouteChainDev& ch = a.ch;
   int alive_after = 0;
   if (i < st.n) {
-    if (!ch.alive[i]) {
-      if (a.tags) { a.tags[2 * i] = -1; a.tags[2 * i + 1] = -1; }
-    } else {
-      // 1. the step just taken (_roll_one's loop body)
-      const int waypoint = ch.wp[i];
-      const int steps = ch.steps[i] + 1;
-      const float pos = (float)st.r(F_POS_ERR, i), ori = (float)st.r(F_ORI_ERR, i), qerr = (float)a.rs.q_error[i];
-      const float min_pos = fminf(ch.min_pos[i], pos), min_ori = fminf(ch.min_ori[i], ori), min_q = fminf(ch.min_q[i], qerr);
-      int first_ready = ch.first_ready[i];
-      if (a.rs.ready[i] != 0 && first_ready < 0) first_ready = steps;
-      const int streak = a.rs.streak[i];
-      const int max_streak = ch.max_streak[i] > streak ? ch.max_streak[i] : streak;
-      if (a.tags) { a.tags[2 * i] = waypoint; a.tags[2 * i + 1] = steps - 1; }
-      const uint8_t d = a.done[i];
-      alive_after = 1;
-      if (!(d & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED))) {
-        ch.steps[i] = steps; ch.first_ready[i] = first_ready; ch.max_streak[i] = max_streak;
-        ch.min_pos[i] = min_pos; ch.min_ori[i] = min_ori; ch.min_q[i] = min_q;
-      } else {
-        // 2. the waypoint's record, then the hand-over
-        const bool success = (d & KP1_DONE_SUCCESS) != 0;
-        double q0[NJ], dq0[NJ], pa0[NJ];
-#pragma unroll
-        for (int k = 0; k < NJ; ++k) {
-          q0[k] = st.q_load(k, i);
-          dq0[k] = (double)st.r(F_DQ + k, i);
-          pa0[k] = (double)st.r(F_PREV_ACTION + k, i);
-        }
-        const int slot = waypoint - ch.start[i];
-        if (slot >= 0 && slot < ch.max_len) {
-          kp1_route_chain_record& rec = ch.records[i * ch.max_len + slot];
-          rec.route_index = waypoint; rec.success = success ? 1 : 0; rec.route_ready_hit = first_ready >= 0 ? 1 : 0;
-          rec.max_ready_streak = max_streak; rec.first_ready_step = first_ready; rec.steps = steps;
-          rec.final_position_error = (double)pos; rec.final_orientation_error = (double)ori; rec.final_q_error = (double)qerr;
-          rec.min_position_error = (double)min_pos; rec.min_orientation_error = (double)min_ori; rec.min_q_error = (double)min_q;
-          rec.final_action_magnitude = (double)st.r(F_ACTION_L2, i); rec.final_dq_norm = (double)st.r(F_EXEC_DQ, i);
-#pragma unroll
-          for (int k = 0; k < NJ; ++k) { rec.final_q[k] = q0[k]; rec.final_dq[k] = dq0[k]; rec.final_prev_action[k] = pa0[k]; }
-          ch.n_records[i] = slot + 1;
-        }
-        if (waypoint >= ch.end[i] || (ch.stop_on_failure && !success)) {
-          ch.alive[i] = 0;
-          alive_after = 0;
-        } else {
-          int win_min, win_max;
-          route_window_of(*a.rc, i, win_min, win_max);
-          route_reset_env<R>(st, *a.cfg, *a.smp, *a.rc, a.rt, a.rs, i, waypoint + 1, 0, KP1_ROUTE_MODE_EXPLICIT, q0, dq0, pa0, a.obs, a.obs_dim,
-                             a.obs_stride, win_max);
-          route_chain_open<R>(st, ch, i, waypoint + 1);
-        }
-      }
-    }
+#include "kp1_route_chain_body.inc"
   }
   const unsigned long long bal = __ballot(alive_after != 0);
   if (threadIdx.x == 0 && bal) atomicAdd(ch.n_alive, __popcll(bal));
@@ -933,17 +852,10 @@ __global__ void __launch_bounds__(64) kp1_route_chain_kernel(const RouteChainArg
 
 }  // namespace
 
-struct kp1_route_chain {
-  RouteChainDev d{};
-  int32_t n_rows = 0;
-  double* init_q = nullptr;    // [R][7] route_q[max(start - 1, 0)]
-  int32_t* zeros = nullptr;    // [R] start_route_index = 0
-  bool counted = false;        // in kp1_route::n_chains
-  std::vector<void*> allocs;
-};
+// struct kp1_route_chain: kp1_route_host.hpp
 
-namespace {
-// what a chain cannot run on; text for kp1_last_error, or nullptr
+namespace kp1 {
+// what a chain cannot run on; text for kp1_last_error, or nullptr (declared in kp1_host.hpp: kp1_mlp.hip asks too)
 const char* route_chain_refusal(const kp1_route* r) {
   if (r->base->real_type != KP1_REAL_F32) return "a route chain drives an f32 base env (the f64 handle keeps the host evaluator)";
   if (r->cfg.sequence_enabled) return "a route chain runs the single-waypoint wrapper: the handle has route.sequence enabled";
@@ -951,7 +863,8 @@ const char* route_chain_refusal(const kp1_route* r) {
   if (r->n_trackers > 0) return "a route chain cannot run on a handle with a prefix curriculum tracker attached";
   return nullptr;
 }
-}  // namespace
+}  // namespace kp1
+using kp1::route_chain_refusal;
 
 extern "C" {
 
@@ -970,6 +883,7 @@ int kp1_route_chain_create(kp1_route* r, const int32_t* start_host, const int32_
   HIP_TRY(hipSetDevice(r->base->device));
   kp1_route_chain* c = new kp1_route_chain();
   c->n_rows = n_rows;
+  c->owner = r;
   const size_t n = (size_t)n_rows;
   int rc = KP1_OK;
   auto alloc = [&](void** p, size_t bytes) {

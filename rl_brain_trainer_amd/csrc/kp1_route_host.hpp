@@ -1,6 +1,6 @@
 // kp1_route_host.hpp -- the route handle (include/kp1_route.h) as the translation units of libkp1.so see it: kp1_env.hip owns its entry
 // points, kp1_mlp.hip steps it from the route rollout kernel (kp1_mlp_forward_route_step).  Include after kp1_route_step.inc (RouteDevCfg,
-// RouteState, RouteTable).
+// RouteState, RouteTable, RouteChainDev).
 #pragma once
 
 #include <vector>
@@ -34,6 +34,16 @@ struct kp1_route {
   std::vector<int32_t> win;    // host copy of the reset windows [K][2]
   int32_t n_trackers = 0;      // prefix trackers created on this handle and not yet destroyed (a chain refuses a tracked handle)
   int32_t n_chains = 0;        // kp1_route_chain objects created on this handle and not yet destroyed (kp1_mlp_forward_route_step refuses them)
+  std::vector<void*> allocs;
+};
+
+struct kp1_route_chain {
+  RouteChainDev d{};
+  int32_t n_rows = 0;
+  const kp1_route* owner = nullptr;   // the handle it was created on
+  double* init_q = nullptr;    // [R][7] route_q[max(start - 1, 0)]
+  int32_t* zeros = nullptr;    // [R] start_route_index = 0
+  bool counted = false;        // in kp1_route::n_chains
   std::vector<void*> allocs;
 };
 

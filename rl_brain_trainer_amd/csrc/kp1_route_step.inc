@@ -258,3 +258,49 @@ __device__ __forceinline__ void route_step_lane(const RouteStepArgs<R>& a, int64
   const int64_t n = a.st.n;
 #include "kp1_route_step_body.inc"
 }
+
+// ---- chained sequential evaluation (kp1_route_chain_*): what kp1_route_chain_kernel (kp1_route.inc) and the one-launch chain step of kp1_mlp.hip
+// (kp1_route_chain_step.inc) share
+struct RouteChainDev {   // device arrays [R] unless noted
+  const int32_t *start, *end;
+  int32_t *wp, *steps, *first_ready, *max_streak, *n_records;
+  uint8_t* alive;
+  float *min_pos, *min_ori, *min_q;
+  kp1_route_chain_record* records;   // [R][max_len]
+  int32_t* n_alive;                  // [1]
+  int max_len, stop_on_failure;
+};
+
+template <typename R>
+struct RouteChainArgs {
+  EnvState<R> st; const DevCfg<R>* cfg; const DevSampler* smp; const RouteDevCfg* rc; RouteTable rt; RouteState<R> rs;
+  RouteChainDev ch; const uint8_t* done; float* obs; int32_t* tags; int obs_dim, obs_stride;
+};
+
+// the bookkeeping of a fresh episode: the minima of position and orientation error start from the planes reset_env wrote, and the record
+// keeps q as the reset left it (the evaluator's initial joint-space error is taken from it on the host)
+template <typename R>
+__device__ __forceinline__ void route_chain_open(const EnvState<R>& st, const RouteChainDev& ch, int64_t i, int waypoint) {
+  ch.wp[i] = waypoint; ch.steps[i] = 0; ch.first_ready[i] = -1; ch.max_streak[i] = 0;
+  ch.min_pos[i] = (float)st.r(F_POS_ERR, i);
+  ch.min_ori[i] = (float)st.r(F_ORI_ERR, i);
+  ch.min_q[i] = std::numeric_limits<float>::infinity();
+  const int slot = waypoint - ch.start[i];
+  if (slot >= 0 && slot < ch.max_len) {
+#pragma unroll
+    for (int k = 0; k < NJ; ++k) ch.records[i * ch.max_len + slot].start_q[k] = st.q_load(k, i);
+  }
+}
+
+// one chain step of row i after its route step (kp1_route_chain_kernel's statements after kp1_route_chain_kernel's declarations: the same text,
+// see kp1_route_chain_body.inc); returns whether the row is still running
+template <typename R>
+__device__ __forceinline__ int route_chain_lane(const RouteChainArgs<R>& a, int64_t i) {
+  const EnvState<R>& st = a.st;
+  const RouteChainDev& ch = a.ch;
+  int alive_after = 0;
+  {
+#include "kp1_route_chain_body.inc"
+  }
+  return alive_after;
+}

@@ -424,6 +424,47 @@ def sequential_result(rows: list[dict[str, Any]], route_progress_m: np.ndarray, 
 
 # --------------------------------------------------------------------------------------------- chained evaluation of many rows at once
 _ALIVE_CHECK_EVERY = 32     # lock steps between two reads of the device's alive counter (the only host synchronisation of the loop)
+CHAIN_FORMS = ("launch_sequence", "one_launch_step", "whole_chain")
+# what evaluate_sequential_route_batch(form=None) takes where chain_fused_covered says yes (elsewhere the launch sequence, silently).  Chosen
+# by measurement (profiles/route_chain_fused.json): both one-launch forms beat the launch sequence's median by more
+# than its own spread at K = 1, 8, 16, and one launch per lock step is the faster of the two.  All forms give the same rows, summaries and
+# files, bit for bit.
+CHAIN_FORM_DEFAULT = "one_launch_step"
+CHAIN_FUSED_WIDTHS = (64, 128)
+CHAIN_FUSED_MAX_WAYPOINTS = 914      # include/kp1_route.h KP1_ROUTE_FUSED_MAX_WAYPOINTS
+CHAIN_RUN_MAX_STEPS = 1024           # include/kp1_route.h KP1_ROUTE_CHAIN_RUN_MAX_STEPS
+
+
+def chain_fused_covered(dtype: Any, hidden: int, obs_dim: int, pitch: int, components_on: bool, n_waypoints: int) -> bool:
+    """Whether the chained evaluator's lock step runs as ONE launch (RouteChain.forward_step / RouteChain.run): an fp32 handle, hidden
+    64 / 128, the 56-float observation at pitch 56 / 64 or the 80-float one at pitch 80 / 128, reward components off and a route of at
+    most CHAIN_FUSED_MAX_WAYPOINTS waypoints.  Plain values only: no handle is touched."""
+    if dtype != torch.float32 or int(hidden) not in CHAIN_FUSED_WIDTHS or components_on:
+        return False
+    if (int(obs_dim), int(pitch)) not in ((56, 56), (56, 64), (80, 80), (80, 128)):
+        return False
+    return int(n_waypoints) <= CHAIN_FUSED_MAX_WAYPOINTS
+
+
+def chain_form_selected(form: str | None, covered: bool) -> str:
+    """the form evaluate_sequential_route_batch runs: ``None`` takes CHAIN_FORM_DEFAULT and falls back silently to the launch sequence where
+    the one-launch kernels do not cover the handles; a form asked for by name and not covered raises"""
+    if form is not None and form not in CHAIN_FORMS:
+        raise ValueError(f"form must be None or one of {CHAIN_FORMS}, got {form!r}")
+    if form is None:
+        return CHAIN_FORM_DEFAULT if (covered or CHAIN_FORM_DEFAULT == "launch_sequence") else "launch_sequence"
+    if form != "launch_sequence" and not covered:
+        raise ValueError(f"form={form!r} needs the one-launch chain kernels: an fp32 route handle, hidden 64 / 128, the 56- or 80-float "
+                         "observation at its own or its padded pitch, reward components off and at most "
+                         f"{CHAIN_FUSED_MAX_WAYPOINTS} waypoints (form=None falls back to the launch sequence)")
+    return form
+
+
+def chain_lock_steps(needed: int, steps_per_launch: int, bound: int) -> int:
+    """lock steps ISSUED by the whole-chain form for a chain whose last row ends at lock step ``needed``: whole spans of ``steps_per_launch``
+    until the alive counter reads zero, never past ``bound``"""
+    span = max(int(steps_per_launch), 1)
+    return min(-(-int(needed) // span) * span, int(bound))
 
 
 def rows_from_chain_records(records: np.ndarray, route_q: np.ndarray, success_dwell_steps: int) -> list[dict[str, Any]]:
@@ -467,12 +508,19 @@ def check_chain_request(*, replicas: int, n_waypoints: int, start_index, end_ind
 
 def evaluate_sequential_route_batch(*, mlp, cfg: dict[str, Any], route_q: np.ndarray, start_index=1, end_indices: Sequence[int],
                                     rows_per_replica: int = 1, device: int | torch.device = 0, artifact_roots: Sequence[str | Path | None] | None = None,
-                                    **single_only: Any) -> list[dict[str, Any]]:
+                                    form: str | None = None, steps_per_launch: int = _ALIVE_CHECK_EVERY, **single_only: Any) -> list[dict[str, Any]]:
     """evaluate_sequential_route for K * C chains in lock step: ``mlp`` is a kp1_mlp wrapper (mlp.MlpKernels) of K replicas whose packed
     weights are the policies under test; row r = k C + c runs waypoints ``start_index .. end_indices[r]`` under replica k's policy.  One f32
     route handle of K C envs with ``sequence`` forced off; per lock step one policy forward over all rows and one kp1_route_chain_step, and
     the alive counter is read every _ALIVE_CHECK_EVERY steps.  Returns, per row, what evaluate_sequential_route returns, plus ``final_qs``
-    (the final q of every waypoint, for sliced_evaluate) and ``lock_steps``."""
+    (the final q of every waypoint, for sliced_evaluate) and ``lock_steps``.
+
+    ``form``: "launch_sequence" (the loop above), "one_launch_step" (RouteChain.forward_step: forward, step and hand-over of a lock step in
+    one launch) or "whole_chain" (RouteChain.run: ``min(steps_per_launch, remaining bound)`` lock steps per launch, the alive counter read
+    after each); ``None`` takes CHAIN_FORM_DEFAULT and falls back silently to the launch sequence where chain_fused_covered says no, a form
+    given by name that is not covered raises ValueError.  The three forms give equal rows, summaries and files.  ``lock_steps`` is the count
+    of lock steps ISSUED: with ``steps_per_launch`` = 32 (the default) the whole-chain form reports the launch-sequence form's value
+    exactly, with a larger span that count rounded up to the span (and never more than the bound)."""
     if single_only:
         raise TypeError(f"evaluate_sequential_route_batch takes packed policy handles and per-row end indices; {sorted(single_only)} belong to "
                         "evaluate_sequential_route (one policy callable, one chain)")
@@ -490,6 +538,11 @@ def evaluate_sequential_route_batch(*, mlp, cfg: dict[str, Any], route_q: np.nda
     obs_dim = rcfg.ROUTE_OBS_DIM if rc.include_route_keys else kcfg.OBS_DIM
     if int(mlp.obs_dim) != obs_dim:
         raise ValueError(f"the policy handle reads {int(mlp.obs_dim)}-float observations, the route config produces {obs_dim}")
+    # the handle below is fp32 at the policy handle's padded pitch, reward components off: decided before any device work
+    form = chain_form_selected(form, chain_fused_covered(torch.float32, int(mlp.hidden), obs_dim, int(mlp.obs_pad), False, W))
+    span = int(steps_per_launch)
+    if form == "whole_chain" and not 1 <= span <= CHAIN_RUN_MAX_STEPS:
+        raise ValueError(f"steps_per_launch must be in [1, {CHAIN_RUN_MAX_STEPS}], got {span}")
     from . import native
 
     base = kcfg.to_env_config(cfg)
@@ -513,12 +566,23 @@ def evaluate_sequential_route_batch(*, mlp, cfg: dict[str, Any], route_q: np.nda
         bound = int((end - start + 1).max()) * max_steps
         chain.begin(obs)
         steps = 0
-        while steps < bound:
-            mlp.forward(obs, clipped=act)
-            chain.step(act, obs, reward, done)
-            steps += 1
-            if steps % _ALIVE_CHECK_EVERY == 0 and chain.alive() == 0:
-                break
+        if form == "whole_chain":
+            while steps < bound:
+                n = min(span, bound - steps)
+                chain.run(mlp, obs, reward, done, n)
+                steps += n
+                if chain.alive() == 0:
+                    break
+        else:
+            while steps < bound:
+                if form == "one_launch_step":
+                    chain.forward_step(mlp, obs, obs, reward, done)
+                else:
+                    mlp.forward(obs, clipped=act)
+                    chain.step(act, obs, reward, done)
+                steps += 1
+                if steps % _ALIVE_CHECK_EVERY == 0 and chain.alive() == 0:
+                    break
         records = chain.records()
         progress = env.route_progress_m.copy()
     finally:

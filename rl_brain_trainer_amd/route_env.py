@@ -269,7 +269,9 @@ class RouteChain:
     """Chain state of a route handle (include/kp1_route.h, kp1_route_chain_*): row r runs the sequential evaluation of the waypoints
     ``start_index[r] .. end_index[r]``, each episode starting from the previous one's final (q, dq, prev_action).  ``begin`` resets every row to
     its first waypoint; ``step`` is one route step of all rows plus kp1_route_chain_kernel (bookkeeping, records, hand-over), with no host read.
-    ``alive()`` reads the device counter of running rows; ``records()`` the finished waypoints of every row."""
+    ``forward_step`` is the policy forward and ``step`` in ONE launch and ``run`` a span of such lock steps in one launch (hidden 64 / 128;
+    neither steps a row whose chain has ended).  ``alive()`` reads the device counter of running rows; ``records()`` the finished waypoints
+    of every row."""
 
     def __init__(self, env: RouteVecEnv, start_index, end_index, *, stop_on_failure: bool = False) -> None:
         n = env.n_envs
@@ -296,6 +298,24 @@ class RouteChain:
         native.check(self.env.L.kp1_route_chain_step(self.env._handle, self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
                                                      C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()),
                                                      C.c_void_p(tags.data_ptr()) if tags is not None else None))
+
+    def forward_step(self, mlp, obs: torch.Tensor, next_obs: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, *,
+                     action: torch.Tensor | None = None, tags: torch.Tensor | None = None) -> None:
+        """``mlp.forward(obs, clipped=action)`` + ``step(action, next_obs, reward, done, tags)`` in ONE launch (kp1_mlp_forward_route_chain_step),
+        bit for bit for every row whose chain is alive.  ``mlp``: an mlp.MlpKernels handle at hidden 64 / 128 whose replicas own the rows
+        replica-major; ``obs`` at the pitch set with ``env.set_obs_stride``; ``next_obs`` is ``obs`` itself (in place) or disjoint from it.  A
+        row whose chain has ended is not stepped: it gets its {-1, -1} tag and nothing else of it is written."""
+        assert obs.is_contiguous() and obs.dtype == torch.float32 and obs.shape[0] == self.env.n_envs
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+        native.check(self.env.L.kp1_mlp_forward_route_chain_step(mlp._h, self.env._handle, self._h, p(obs), int(obs.shape[1]), p(action), p(next_obs),
+                                                                 p(reward), p(done), p(tags), mlp._stream()))
+
+    def run(self, mlp, obs: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, n_steps: int) -> None:
+        """``n_steps`` lock steps (1 .. native.ROUTE_CHAIN_RUN_MAX_STEPS) of ``forward_step`` in ONE launch, in place on ``obs``
+        (kp1_route_chain_run); ``alive()`` afterwards is the number of rows still running after the last step."""
+        assert obs.is_contiguous() and obs.dtype == torch.float32 and obs.shape[0] == self.env.n_envs
+        native.check(self.env.L.kp1_route_chain_run(mlp._h, self.env._handle, self._h, C.c_void_p(obs.data_ptr()), int(obs.shape[1]),
+                                                    C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), int(n_steps), mlp._stream()))
 
     def alive(self) -> int:
         """rows still running after the last step (synchronises)"""

@@ -77,6 +77,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
                    "sequence stays); bit-identical to the default, for --seed and --seeds runs")
     p.add_argument("--per-replica-eval", action="store_true", help="with --seeds: run the final sequential evaluations and gates one replica and "
                    "one prefix after another on the host-driven evaluator, instead of one device chain per replica in lock step")
+    p.add_argument("--chain-eval-form", choices=("launch-sequence", "one-launch-step", "whole-chain"), default=None, help="with --seeds: how the "
+                   "chained final evaluation issues its lock steps -- the launch sequence, one launch per lock step "
+                   "(kp1_mlp_forward_route_chain_step) or one launch per span of lock steps (kp1_route_chain_run); same files bit for bit. "
+                   "Default: route_curriculum.CHAIN_FORM_DEFAULT.  --per-replica-eval and --seed keep their evaluators")
     return p
 
 
@@ -261,7 +265,8 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
             # the gate's prefixes, the full route) is then a slice of that chain's rows
             t_batch = time.time()
             ends = [_chain_end_index(route_cfg, cs, W) for cs in curriculum_summaries]
-            chains = evaluate_sequential_route_batch(mlp=pop._mlp, cfg=cfg, route_q=route_q, start_index=1, end_indices=ends, device=device)
+            chains = evaluate_sequential_route_batch(mlp=pop._mlp, cfg=cfg, route_q=route_q, start_index=1, end_indices=ends, device=device,
+                                                     form=args.chain_eval_form.replace("-", "_") if args.chain_eval_form else None)
             evaluators = [sliced_evaluate(c["rows"], c["final_qs"], env.route_progress_m) for c in chains]
             batch_share = (time.time() - t_batch) / pop.K
         for k, s in enumerate(seeds):   # the artefacts and the gate verdicts are written one seed after another, as single runs write them

@@ -375,6 +375,82 @@ def main_route_eval(args) -> None:
     print(json.dumps({"route_evaluation_median_ms": {r["K"]: {f: round(r[f]["median_ms"], 1) for f in ("per_replica", "batch")} for r in rows}}))
 
 
+def main_route_chain_forms(args) -> None:
+    """--route-eval --chain-form: the chained evaluation's forms against each other (the launch sequence is the reference IN THE SAME RUN), the
+    whole-chain form once per --steps-per-launch value; results asserted equal before anything is timed, then alternated in one process"""
+    import statistics
+
+    from rl_brain_trainer_amd import route_config as rcfg
+    from rl_brain_trainer_amd.route_curriculum import evaluate_sequential_route_batch
+
+    args.ks = args.ks or "1,8,16"
+    args.batch = args.batch or 512
+    cfg = json.loads(ROUTE_CONFIG.read_text())
+    route_q = rcfg.load_route_q(ROUTE_PATH)
+    E = int(args.end_index)
+    forms = [f.strip().replace("-", "_") for f in args.chain_form.split(",")]
+    spans = [int(v) for v in args.steps_per_launch.split(",")]
+    legs = []
+    for f in forms:
+        legs += [(f"{f}@{sp}", f, sp) for sp in spans] if f == "whole_chain" else [(f, f, 32)]
+    if "launch_sequence" not in forms:
+        legs.insert(0, ("launch_sequence", "launch_sequence", 32))
+
+    rows = []
+    for K in (int(k) for k in args.ks.split(",")):
+        pop = build_route(K, args.n_envs, args.n_steps, args.batch, args.hidden, True)
+        pop.collect_rollouts()
+        pop.train()      # one training iteration: the replicas' weights differ
+        torch.cuda.synchronize()
+        seen = {}
+
+        def run(name, form, span):
+            chains = evaluate_sequential_route_batch(mlp=pop._mlp, cfg=cfg, route_q=route_q, start_index=1, end_indices=[E] * K, form=form,
+                                                     steps_per_launch=span)
+            seen[name] = chains
+
+        def timed(leg) -> float:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(*leg)
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0)
+
+        for leg in legs:      # warm-up of every leg; all must agree with the launch sequence before any is timed
+            run(*leg)
+        ref = seen["launch_sequence"]
+        for name, _, span in legs:
+            for a, b in zip(seen[name], ref):
+                assert {k: v for k, v in a.items() if k != "lock_steps"} == {k: v for k, v in b.items() if k != "lock_steps"}, (K, name)
+                assert span > 32 or a["lock_steps"] == b["lock_steps"], (K, name, a["lock_steps"], b["lock_steps"])
+        t = {name: [] for name, _, _ in legs}
+        for _ in range(args.repeats):
+            for leg in legs:
+                t[leg[0]].append(timed(leg))
+        _close(pop)
+        row = {"K": K, "end_index": E}
+        for name, _, _ in legs:
+            ms = t[name]
+            steps = seen[name][0]["lock_steps"]
+            med = statistics.median(ms)
+            row[name] = {"ms": ms, "median_ms": med, "spread_ms": max(ms) - min(ms), "lock_steps": steps, "us_per_lock_step": 1e3 * med / max(steps, 1)}
+        base = row["launch_sequence"]
+        for name, _, _ in legs[1:] if legs[0][0] == "launch_sequence" else legs:
+            if name != "launch_sequence":
+                row[name]["beats_launch_sequence_by_more_than_its_spread"] = base["median_ms"] - row[name]["median_ms"] > base["spread_ms"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    result = {"workload": f"chained final evaluation of a train_route --seeds run on synthetic_route.json (route_curriculum_prefix120_routeobs_sequence2): "
+                          f"one chain per replica to waypoint {E}, RoutePopulationPPO of K replicas, {args.n_envs} envs x {args.n_steps} steps per replica, "
+                          f"minibatch {args.batch}, 2x{args.hidden}, after one iteration; evaluate_sequential_route_batch(form=...), whole_chain@S = "
+                          f"steps_per_launch S; results equal before timing; legs alternated in one process, one warm-up, {args.repeats} repeats; host "
+                          "clock around a device synchronise; no artifact files",
+              "device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
+    print(json.dumps({"route_chain_median_ms": {r["K"]: {n: round(r[n]["median_ms"], 1) for n, _, _ in legs} for r in rows}}))
+
+
 def _record_servo_dataset(path: Path, max_route_index: int) -> None:
     """a teacher-anchor dataset as collect_route_teacher writes it: 64 device envs under a servo toward the route goal, 32 steps"""
     import numpy as np
@@ -501,6 +577,9 @@ def main() -> None:
                     "with the device anchor step, and the device step against the torch step of one single PPO")
     ap.add_argument("--route-eval", action="store_true", help="the final sequential evaluations of a route --seeds run: K x (prefixes + full) "
                     "per-replica evaluations against one chained batch evaluation")
+    ap.add_argument("--chain-form", default=None, help="with --route-eval: comma list of launch-sequence, one-launch-step, whole-chain -- time the "
+                    "chained evaluation's forms against the launch sequence in one process (the per-replica form is not run)")
+    ap.add_argument("--steps-per-launch", default="32", help="with --chain-form whole-chain: comma list of lock steps per launch (1 .. 1024)")
     ap.add_argument("--end-index", type=int, default=40, help="with --route-eval: the largest route index evaluated (the 'full route' of the bench)")
     ap.add_argument("--eval", action="store_true", help="one gate evaluation of a --seeds run: K per-replica evaluations against one population evaluation")
     ap.add_argument("--repeats", type=int, default=5, help="with --eval: timed repeats of each form")
@@ -548,6 +627,10 @@ def main() -> None:
         return main_dock(args)
     if args.route_anchor:
         return main_route_anchor(args)
+    if args.chain_form and not args.route_eval:
+        ap.error("--chain-form belongs to --route-eval")
+    if args.route_eval and args.chain_form:
+        return main_route_chain_forms(args)
     if args.route_eval:
         return main_route_eval(args)
     if args.eval:
