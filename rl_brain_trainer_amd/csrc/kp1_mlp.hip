@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/kp1_ppo.h"
@@ -1561,6 +1562,107 @@ int mlp_check_device(const kp1_mlp* m) {
   return KP1_OK;
 }
 
+// ---- argument builders: each block of kernel arguments that more than one entry point fills is filled here, once
+
+// the n / obs_stride checks that open kp1_mlp_forward, kp1_mlp_loss_grad and kp1_mlp_anchor_loss_grad
+int check_batch_args(const kp1_mlp* m, int n, int obs_stride) {
+  if (n <= 0 || n > m->max_batch) return fail(KP1_ERR_INVALID, "n exceeds the workspace max_batch");
+  if (obs_stride != m->L.IN && obs_stride != m->L.INP)
+    return fail(KP1_ERR_INVALID, "obs_stride must be the observation width or its padded width (56 / 64, or 80 / 128)");
+  return KP1_OK;
+}
+
+// floats of an observation row that layer 1 loads: the padded width when the rows are stored padded, else the real one
+int kreal(const kp1_mlp* m, int obs_stride) {
+  const int IN = m->L.IN, INP = m->L.INP;
+  return obs_stride >= INP ? INP : IN;
+}
+
+// FusedArgs: the observation rows and the weights, common to every form of the tile kernel
+void fill_fused_head(FusedArgs& fa, const kp1_mlp* m, const float* obs, int obs_stride, const int64_t* idx, int n) {
+  fa.obs = obs; fa.obs_stride = obs_stride; fa.Kreal = kreal(m, obs_stride); fa.inp = m->L.INP; fa.idx = idx; fa.n = n;
+  fa.k = m->k;
+}
+
+// weights, biases and per-replica strides of a layer-wise argument block (net 0, the policy, leads every array).  EvalStepArgs runs the policy
+// net only and the mean action: it has no per-net strides and no log_std.
+template <class Args>
+void fill_layer_weights(Args& a, const kp1_mlp* m) {
+  const int Hp = m->Hp, INP = m->L.INP;
+  a.w1 = m->k.w1p; a.b1 = m->k.b1; a.w2 = m->k.w2; a.b2 = m->k.b2; a.w3 = m->k.w3; a.b3 = m->k.b3;
+  a.r_w1 = (unsigned)(2 * Hp * INP); a.r_w2 = (unsigned)(2 * Hp * Hp); a.r_b = (unsigned)(2 * Hp); a.r_w3 = (unsigned)(HEADS * Hp); a.r_b3 = (unsigned)HEADS;
+  if constexpr (std::is_same_v<Args, RolloutStepArgs>) {
+    a.log_std = m->k.log_std;
+    a.n_w1 = (unsigned)(Hp * INP); a.n_w2 = (unsigned)(Hp * Hp); a.n_b = (unsigned)Hp;
+  }
+}
+
+// the forward half of a RolloutStepArgs (its env block is the caller's): n rows per replica
+void fill_rollout_forward(RolloutStepArgs& f, const kp1_mlp* m, const float* obs, int obs_stride, const float* noise, float* value, float* action,
+                          float* log_prob, int n) {
+  f.obs = obs; f.obs_stride = obs_stride;
+  fill_layer_weights(f, m);
+  f.noise = noise; f.value = value; f.action = action; f.log_prob = log_prob;
+  f.n = n;
+  f.Kreal = kreal(m, obs_stride);
+}
+
+// dZ1 = (dZ2 W2) * (1 - h1^2), bias-1 gradient partials = per-row-tile column sums of dZ1 (launch_nt<EPI_DTANH>)
+GemmNT backward_nt_args(const kp1_mlp* m, int n) {
+  const int Hp = m->Hp;
+  const int64_t act_stride = (int64_t)m->max_batch * Hp;
+  GemmNT g{};
+  g.A = m->dz2; g.lda = Hp; g.strideA = act_stride; g.gather = nullptr;
+  g.W = m->k.w2t; g.strideW = (int64_t)Hp * Hp;
+  g.bias = nullptr; g.strideBias = 0;
+  g.C = m->dz1; g.ldc = Hp; g.strideC = act_stride;
+  g.aux = m->h1; g.strideAux = act_stride;
+  g.colsum = m->bslab; g.strideColsum = Hp;
+  g.M = n; g.N = Hp; g.K = Hp; g.Kreal = Hp;
+  g.reps = m->K;
+  g.r_A = g.r_C = g.r_aux = (unsigned)(2 * act_stride); g.r_W = (unsigned)(2 * Hp * Hp);
+  g.r_colsum = (unsigned)((m->max_batch / 32) * 2 * Hp);
+  return g;
+}
+
+// weight gradients of the tile path: the dW2 / dW1 slabs and the batch chunking of gemm_tn_split_kernel (and of its bf16x3 form)
+TnFragArgs tn_frag_args(const kp1_mlp* m, int n) {
+  const int Hp = m->Hp, INP = m->L.INP;
+  TnFragArgs t{};
+  t.inp = INP;
+  t.dz2 = m->dz2; t.h1 = m->h1; t.dz1 = m->dz1; t.act_stride = (int64_t)m->max_batch * Hp; t.xf = m->xf;
+  t.slab2 = m->slab; t.s2_net = (int64_t)Hp * Hp; t.s2_chunk = 2 * t.s2_net;
+  t.slab1 = m->slab1; t.s1_net = (int64_t)Hp * INP; t.s1_chunk = 2 * t.s1_net;
+  t.groups = (n + FU_BM - 1) / FU_BM * (FU_BM / 8);   // the tile kernel writes whole 32-row tiles
+  auto up8 = [](int v) { return (v + 7) / 8 * 8; };
+  t.cg2 = up8((t.groups + TN_SPLIT2 - 1) / TN_SPLIT2);
+  t.cg1 = up8((t.groups + TN_SPLIT1 - 1) / TN_SPLIT1);
+  t.n_chunks2 = (t.groups + t.cg2 - 1) / t.cg2;
+  t.n_chunks1 = (t.groups + t.cg1 - 1) / t.cg1;
+  return t;
+}
+
+// number of row tiles launch_nt uses for an n-row GEMM with N = Hp columns (the bias-partial count of the backward GEMM)
+int nt_row_tiles(int n, int Hp) {
+  (void)Hp;
+  return (n + 63) / 64;
+}
+
+// FinalizeArgs: where the gradient's parts lie (slabs, bias and head partials, per-replica strides) after an n-row backward pass with s2_n / s1_n
+// batch chunks.  b_n is the layer-wise row-tile count; the loss terms, the outputs and the sum-of-squares buffer are the caller's.
+void fill_finalize(FinalizeArgs& f, const kp1_mlp* m, int n, int s2_n, int s1_n, float* grad) {
+  const int Hp = m->Hp, INP = m->L.INP;
+  f.L = m->L;
+  f.slab2 = m->slab; f.s2_ld = Hp; f.s2_net = (int64_t)Hp * Hp; f.s2_chunk = 2 * f.s2_net; f.s2_n = s2_n;
+  f.slab1 = m->slab1; f.s1_ld = INP; f.s1_net = (int64_t)Hp * INP; f.s1_chunk = 2 * f.s1_net; f.s1_n = s1_n;
+  f.bslab = m->bslab; f.b_net = Hp; f.b_tile = 2 * Hp; f.b_n = nt_row_tiles(n, Hp);
+  f.hpart = m->hpart; f.h_stride = 10 * Hp + 32; f.h_n = (n + HEAD_ROWS - 1) / HEAD_ROWS;
+  f.log_std = m->k.log_std;
+  f.grad = grad;
+  f.r_slab2 = (unsigned)(64 * f.s2_chunk); f.r_slab1 = (unsigned)(64 * f.s1_chunk); f.r_bslab = (unsigned)((m->max_batch / 32) * 2 * Hp);
+  f.r_hpart = (unsigned)((int64_t)(m->max_batch / 32) * (10 * Hp + 32));
+}
+
 constexpr size_t TN_LDS_BYTES = sizeof(float) * 2 * 2 * 64 * (128 + 4);
 
 // Tile shapes.  Wide (whole hidden width per workgroup, large batches): 64 rows x 256 columns, 32-deep W stages, 512
@@ -1579,12 +1681,6 @@ int launch_nt_inst(const GemmNT& g, hipStream_t stream) {
   HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_kernel<BN, EPI, K, NTH, BM, BKS, POP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   hipLaunchKernelGGL((gemm_nt_kernel<BN, EPI, K, NTH, BM, BKS, POP>), dim3((g.M + BM - 1) / BM, g.N / BN, POP ? 2 * g.reps : 2), dim3(NTH), bytes, stream, g);
   return KP1_OK;
-}
-
-// number of row tiles launch_nt uses for an n-row GEMM with N = Hp columns (the bias-partial count of the backward GEMM)
-int nt_row_tiles(int n, int Hp) {
-  (void)Hp;
-  return (n + 63) / 64;
 }
 
 template <int EPI>
@@ -1608,6 +1704,17 @@ int launch_nt(const GemmNT& g, hipStream_t stream) {
 // dW (both nets) = D^T X over n rows: split-B partial tiles into m->slab, then the fixed-order reduce into G
 int launch_tn(kp1_mlp* m, GemmTN t, int n_o_tiles, int slab_cols, float* slab, int* n_chunks_out, hipStream_t stream);
 
+// Every launch of mlp_tile_kernel: the dynamic-LDS attribute, then the launch.  Only the training forms go through KP1_LAUNCH: they are the ones
+// the optimiser step's profile covers.
+template <bool TRAIN, int K1S, int ENV = 0, bool SPLIT = false>
+int launch_tile(dim3 grid, const FusedArgs& fa, hipStream_t stream) {
+  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;   // 32-row tiles, 4 waves
+  HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<TRAIN, K1S, ENV, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if constexpr (TRAIN) KP1_LAUNCH((mlp_tile_kernel<TRAIN, K1S, ENV, SPLIT>), grid, dim3(FU_NTH), bytes, stream, fa);
+  else hipLaunchKernelGGL((mlp_tile_kernel<TRAIN, K1S, ENV, SPLIT>), grid, dim3(FU_NTH), bytes, stream, fa);
+  return KP1_OK;
+}
+
 int launch_fused(const FusedArgs& fa_in, hipStream_t stream) {
   FusedArgs fa = fa_in;
   static const int stagger_us = [] { const char* e = std::getenv("KP1_FU_STAGGER_US"); return e ? std::atoi(e) : 11; }();  // tuning knob; re-swept in round 3 (profiles/r03_ab_tile_stagger.log): 10-13 us within 0.4 us of each other, a cliff at 14 (+6 us)
@@ -1619,71 +1726,30 @@ int launch_fused(const FusedArgs& fa_in, hipStream_t stream) {
   const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, 2);
   fa.n_cus = n_cus;
   fa.stagger_ticks = (int)(grid.x * grid.z) > n_cus ? stagger_us * 100 : 0;   // only when CUs hold two workgroups at once
-  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;
-  if (fa.sp_h1 != nullptr) {   // [r3 experiment] bf16 x 3 planes instead of the fp32 activation copies
-    if (fa.inp == 64) {
-      HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<true, 2, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-      KP1_LAUNCH((mlp_tile_kernel<true, 2, 0, true>), grid, dim3(FU_NTH), bytes, stream, fa);
-    } else {
-      HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<true, 4, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-      KP1_LAUNCH((mlp_tile_kernel<true, 4, 0, true>), grid, dim3(FU_NTH), bytes, stream, fa);
-    }
-    return KP1_OK;
-  }
-  if (fa.inp == 64) {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    KP1_LAUNCH((mlp_tile_kernel<true, 2>), grid, dim3(FU_NTH), bytes, stream, fa);
-  } else {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    KP1_LAUNCH((mlp_tile_kernel<true, 4>), grid, dim3(FU_NTH), bytes, stream, fa);
-  }
-  return KP1_OK;
+  if (fa.sp_h1 != nullptr)   // [r3 experiment] bf16 x 3 planes instead of the fp32 activation copies
+    return fa.inp == 64 ? launch_tile<true, 2, 0, true>(grid, fa, stream) : launch_tile<true, 4, 0, true>(grid, fa, stream);
+  return fa.inp == 64 ? launch_tile<true, 2>(grid, fa, stream) : launch_tile<true, 4>(grid, fa, stream);
 }
 
 // policy forward + env step in one launch (kp1_mlp_forward_env_step): env_mode = KP1_MODE_APPROACH / KP1_MODE_DOCK, 64-float observation rows
 int launch_fused_infer_env(const FusedArgs& fa, int env_mode, hipStream_t stream) {
-  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;
   const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, fa.value ? 2 : 1);
-  if (env_mode == KP1_MODE_DOCK) {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 2>), grid, dim3(FU_NTH), bytes, stream, fa);
-  } else {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 1>), grid, dim3(FU_NTH), bytes, stream, fa);
-  }
-  return KP1_OK;
+  return env_mode == KP1_MODE_DOCK ? launch_tile<false, 2, 2>(grid, fa, stream) : launch_tile<false, 2, 1>(grid, fa, stream);
 }
 
 // deterministic evaluation step of a 2x256 policy in one launch (kp1_eval_step): policy net only, the bookkeeping of fa.ev in the tail
 int launch_fused_eval_env(const FusedArgs& fa, int env_mode, hipStream_t stream) {
-  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;
   const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, 1);
-  if (env_mode == KP1_MODE_DOCK) {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 4>), grid, dim3(FU_NTH), bytes, stream, fa);
-  } else {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 3>), grid, dim3(FU_NTH), bytes, stream, fa);
-  }
-  return KP1_OK;
+  return env_mode == KP1_MODE_DOCK ? launch_tile<false, 2, 4>(grid, fa, stream) : launch_tile<false, 2, 3>(grid, fa, stream);
 }
 
 // whole-episode evaluation of a 2x256 policy in one launch (kp1_eval_episodes): env steps fa.ev.step .. fa.ev.last_step, one workgroup per tile
 int launch_fused_eval_episodes(const FusedArgs& fa, int env_mode, hipStream_t stream) {
-  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;
   const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, 1);
-  if (env_mode == KP1_MODE_DOCK) {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 6>), grid, dim3(FU_NTH), bytes, stream, fa);
-  } else {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2, 5>), grid, dim3(FU_NTH), bytes, stream, fa);
-  }
-  return KP1_OK;
+  return env_mode == KP1_MODE_DOCK ? launch_tile<false, 2, 6>(grid, fa, stream) : launch_tile<false, 2, 5>(grid, fa, stream);
 }
 
 int launch_fused_infer(const FusedArgs& fa, hipStream_t stream) {
-  const size_t bytes = sizeof(float) * FU_LDS_FLOATS;   // 32-row tiles, 4 waves, two workgroups per CU
   // the value net is skipped when no value is asked for (deterministic evaluators), the policy net when only values are
   const bool want_pi = fa.mean || fa.action || fa.clipped || fa.log_prob;
   if (!want_pi && !fa.value) return KP1_OK;
@@ -1691,14 +1757,7 @@ int launch_fused_infer(const FusedArgs& fa, hipStream_t stream) {
   const bool both = want_pi && fa.value;
   if (!both) f.net_base = want_pi ? 0 : 1;
   const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, both ? 2 : 1);
-  if (fa.inp == 64) {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 2>), grid, dim3(FU_NTH), bytes, stream, f);
-  } else {
-    HIP_TRY(hipFuncSetAttribute((const void*)mlp_tile_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    hipLaunchKernelGGL((mlp_tile_kernel<false, 4>), grid, dim3(FU_NTH), bytes, stream, f);
-  }
-  return KP1_OK;
+  return fa.inp == 64 ? launch_tile<false, 2>(grid, f, stream) : launch_tile<false, 4>(grid, f, stream);
 }
 
 int launch_tn_frag(const TnFragArgs& t, hipStream_t stream) {
@@ -1712,7 +1771,7 @@ int launch_tn_frag(const TnFragArgs& t, hipStream_t stream) {
 // forward layers 1 and 2 for n rows (both nets): h1, h2 filled
 // (population: n rows per replica; without idx replica r reads obs rows [r n, (r + 1) n), with idx its index row idx[r][0..n))
 int launch_forward_layers(kp1_mlp* m, const float* obs, int obs_stride, const int64_t* idx, int n, hipStream_t stream) {
-  const int Hp = m->Hp, IN = m->L.IN, INP = m->L.INP;
+  const int Hp = m->Hp, INP = m->L.INP;
   const int64_t act_stride = (int64_t)m->max_batch * Hp;
   GemmNT g{};
   g.reps = m->K;
@@ -1723,7 +1782,7 @@ int launch_forward_layers(kp1_mlp* m, const float* obs, int obs_stride, const in
   g.bias = m->k.b1; g.strideBias = Hp;
   g.C = m->h1; g.ldc = Hp; g.strideC = act_stride;
   g.aux = nullptr; g.strideAux = 0; g.colsum = nullptr; g.strideColsum = 0;
-  g.M = n; g.N = Hp; g.K = INP; g.Kreal = obs_stride >= INP ? INP : IN;
+  g.M = n; g.N = Hp; g.K = INP; g.Kreal = kreal(m, obs_stride);
   int rc = launch_nt<EPI_BIAS_TANH>(g, stream);
   if (rc != KP1_OK) return rc;
   g.A = m->h1; g.lda = Hp; g.strideA = act_stride; g.gather = nullptr;
@@ -1756,22 +1815,35 @@ int launch_tn(kp1_mlp* m, GemmTN t, int n_o_tiles, int slab_cols, float* slab, i
     t.r_X = t.gatherX ? 0u : t.r_D;
     t.r_gather = (unsigned)t.B;
     t.r_slab = (unsigned)(64 * t.slab_chunk_stride);
-    if (t.gatherX) {
-      HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES));
-      hipLaunchKernelGGL((gemm_tn_kernel<true, true>), grid, dim3(256), TN_LDS_BYTES, stream, t);
-    } else {
-      HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES));
-      hipLaunchKernelGGL((gemm_tn_kernel<false, true>), grid, dim3(256), TN_LDS_BYTES, stream, t);
-    }
-  } else if (t.gatherX) {
-    HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES));
-    hipLaunchKernelGGL(gemm_tn_kernel<true>, grid, dim3(256), TN_LDS_BYTES, stream, t);
-  } else {
-    HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES));
-    hipLaunchKernelGGL(gemm_tn_kernel<false>, grid, dim3(256), TN_LDS_BYTES, stream, t);
   }
+  const bool gather = t.gatherX != nullptr;
+  // the four gemm_tn_kernel instantiations share the LDS size
+  auto* kernel = m->K > 1 ? (gather ? gemm_tn_kernel<true, true> : gemm_tn_kernel<false, true>) : (gather ? gemm_tn_kernel<true> : gemm_tn_kernel<false>);
+  HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES));
+  hipLaunchKernelGGL(kernel, grid, dim3(256), TN_LDS_BYTES, stream, t);
   if (n_chunks_out) *n_chunks_out = n_chunks;
   return KP1_OK;
+}
+
+// weight gradients of the layer-wise path (split over the batch axis): the dW2 and dW1 slabs of an n-row backward pass, *s2_n / *s1_n chunks
+int launch_layer_wgrads(kp1_mlp* m, const float* obs, int obs_stride, const int64_t* idx, int n, int* s2_n, int* s1_n, hipStream_t stream) {
+  const int Hp = m->Hp;
+  const int64_t act_stride = (int64_t)m->max_batch * Hp;
+  GemmTN t{};
+  t.B = n;
+  t.chunk = tn_chunk_rows(n, (Hp / 128) * (Hp / 128) * 2);
+  // dW2[o][i] = sum_b dZ2[b][o] h1[b][i]
+  t.D = m->dz2; t.ldd = Hp; t.strideD = act_stride;
+  t.X = m->h1; t.ldx = Hp; t.strideX = act_stride; t.gatherX = nullptr;
+  t.Nload = Hp; t.n_i_tiles = Hp / 128;
+  int rc = launch_tn(m, t, Hp / 128, Hp, m->slab, s2_n, stream);
+  if (rc != KP1_OK) return rc;
+  // dW1[o][i] = sum_b dZ1[b][o] x[b][i]   (i < 56)
+  t.D = m->dz1;
+  t.X = obs; t.ldx = obs_stride; t.strideX = 0; t.gatherX = idx;
+  t.Nload = kreal(m, obs_stride); t.n_i_tiles = 1;
+  t.chunk = tn_chunk_rows(n, (Hp / 128) * 2);  // few tiles: more, shorter batch chunks keep the CUs busy
+  return launch_tn(m, t, Hp / 128, m->L.INP, m->slab1, s1_n, stream);
 }
 }  // namespace
 
@@ -1985,15 +2057,13 @@ int kp1_mlp_pack_weights(kp1_mlp* m, const float* params, void* stream) {
 int kp1_mlp_forward(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n, const float* noise, float* mean, float* value, float* action,
                     float* clipped_action, float* log_prob, void* stream) {
   if (!m || !obs) return fail(KP1_ERR_INVALID, "NULL argument");
-  if (n <= 0 || n > m->max_batch) return fail(KP1_ERR_INVALID, "n exceeds the workspace max_batch");
-  const int IN = m->L.IN, INP = m->L.INP;
-  if (obs_stride != IN && obs_stride != INP) return fail(KP1_ERR_INVALID, "obs_stride must be the observation width or its padded width (56 / 64, or 80 / 128)");
-  int rc = mlp_check_device(m);
+  int rc = check_batch_args(m, n, obs_stride);
+  if (rc != KP1_OK) return rc;
+  rc = mlp_check_device(m);
   if (rc != KP1_OK) return rc;
   if (m->fused && m->Hp == FU_HP) {
     FusedArgs fa{};
-    fa.obs = obs; fa.obs_stride = obs_stride; fa.Kreal = obs_stride >= INP ? INP : IN; fa.inp = INP; fa.idx = nullptr; fa.n = n;
-    fa.k = m->k;
+    fill_fused_head(fa, m, obs, obs_stride, nullptr, n);
     fa.noise = noise; fa.mean = mean; fa.value = value; fa.action = action; fa.clipped = clipped_action; fa.log_prob = log_prob;
     rc = launch_fused_infer(fa, (hipStream_t)stream);
     if (rc != KP1_OK) return rc;
@@ -2006,12 +2076,10 @@ int kp1_mlp_forward(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n,
   a.h2 = m->h2; a.strideH = (int64_t)m->max_batch * m->Hp; a.Hp = m->Hp; a.n = n; a.H = m->H;
   a.w3 = m->k.w3; a.b3 = m->k.b3; a.log_std = m->k.log_std;
   a.noise = noise; a.mean = mean; a.value = value; a.action = action; a.clipped = clipped_action; a.log_prob = log_prob;
-  if (m->K > 1) {
-    a.r_act = (unsigned)(2 * a.strideH);
-    hipLaunchKernelGGL(head_infer_kernel<true>, dim3((n + HEAD_ROWS - 1) / HEAD_ROWS, m->K), dim3(256), sizeof(float) * HEADS * m->Hp, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL(head_infer_kernel<false>, dim3((n + HEAD_ROWS - 1) / HEAD_ROWS), dim3(256), sizeof(float) * HEADS * m->Hp, (hipStream_t)stream, a);
-  }
+  const bool pop = m->K > 1;
+  if (pop) a.r_act = (unsigned)(2 * a.strideH);
+  hipLaunchKernelGGL(pop ? head_infer_kernel<true> : head_infer_kernel<false>, dim3((n + HEAD_ROWS - 1) / HEAD_ROWS, m->K), dim3(256),
+                     sizeof(float) * HEADS * m->Hp, (hipStream_t)stream, a);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
@@ -2048,20 +2116,12 @@ int forward_env_step_layers(kp1_mlp* m, kp1_env* env, const float* obs, int32_t 
     if (overlaps(next_obs) || overlaps(terminal_obs))
       return fail(KP1_ERR_INVALID, "kp1_mlp_forward_env_step: next_obs and terminal_obs must not overlap obs in the layer-wise form");
   }
-  const int Hp = m->Hp, INP = m->L.INP;
-  a.obs = obs; a.obs_stride = obs_stride;
-  a.w1 = m->k.w1p; a.b1 = m->k.b1; a.w2 = m->k.w2; a.b2 = m->k.b2; a.w3 = m->k.w3; a.b3 = m->k.b3; a.log_std = m->k.log_std;
-  a.r_w1 = (unsigned)(2 * Hp * INP); a.r_w2 = (unsigned)(2 * Hp * Hp); a.r_b = (unsigned)(2 * Hp); a.r_w3 = (unsigned)(HEADS * Hp); a.r_b3 = (unsigned)HEADS;
-  a.n_w1 = (unsigned)(Hp * INP); a.n_w2 = (unsigned)(Hp * Hp); a.n_b = (unsigned)Hp;
-  a.noise = noise; a.value = value; a.action = action; a.log_prob = log_prob;
-  a.n = (int)(n_envs / m->K);
-  a.Kreal = obs_stride >= INP ? INP : m->L.IN;
+  fill_rollout_forward(a, m, obs, obs_stride, noise, value, action, log_prob, (int)(n_envs / m->K));
   const dim3 grid((unsigned)((a.n + ES_BM - 1) / ES_BM), (unsigned)m->K, value ? 2u : 1u);
-  const bool pop = pop_form != 0, dock = mode == KP1_MODE_DOCK;
-  if (pop && dock) hipLaunchKernelGGL((rollout_step_kernel<KP1_MODE_DOCK, true>), grid, dim3(ES_NTH), 0, stream, a);
-  else if (pop) hipLaunchKernelGGL((rollout_step_kernel<KP1_MODE_APPROACH, true>), grid, dim3(ES_NTH), 0, stream, a);
-  else if (dock) hipLaunchKernelGGL((rollout_step_kernel<KP1_MODE_DOCK, false>), grid, dim3(ES_NTH), 0, stream, a);
-  else hipLaunchKernelGGL((rollout_step_kernel<KP1_MODE_APPROACH, false>), grid, dim3(ES_NTH), 0, stream, a);
+  const bool dock = mode == KP1_MODE_DOCK;
+  auto* kernel = pop_form != 0 ? (dock ? rollout_step_kernel<KP1_MODE_DOCK, true> : rollout_step_kernel<KP1_MODE_APPROACH, true>)
+                               : (dock ? rollout_step_kernel<KP1_MODE_DOCK, false> : rollout_step_kernel<KP1_MODE_APPROACH, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(ES_NTH), 0, stream, a);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
@@ -2073,6 +2133,52 @@ void launch_route_rollout_step(bool pop, dim3 grid, hipStream_t stream, const Ro
   if (pop) hipLaunchKernelGGL((route_rollout_step_kernel<INP, true>), grid, dim3(ES_NTH), 0, stream, a);
   else hipLaunchKernelGGL((route_rollout_step_kernel<INP, false>), grid, dim3(ES_NTH), 0, stream, a);
 }
+
+// ---- what the route one-launch forms share (kp1_mlp_forward_route_step; kp1_mlp_forward_route_chain_step / kp1_route_chain_run), in two phases
+// that each caller interleaves with its own refusals.  `who` names the entry point in the refusal texts; they are only built on a refusal.
+
+std::string refusal_text(const char* head, const char* tail) { return std::string(head) + tail; }
+
+// phase 1: the observation layout of the policy handle against the route handle's; *obs_dim = the route observation's width
+int route_fwd_check_obs(const char* who, const kp1_mlp* m, const kp1_route* r, int obs_stride, int* obs_dim) {
+  *obs_dim = r->cfg.include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM;
+  if (m->L.IN != *obs_dim) return fail(KP1_ERR_INVALID, refusal_text(who, ": the MLP handle's obs_dim differs from the route handle's"));
+  if (obs_stride != m->L.IN && obs_stride != m->L.INP)
+    return fail(KP1_ERR_INVALID, refusal_text(who, ": obs_stride must be the observation width (56 / 80) or its padded width (64 / 128)"));
+  if (obs_stride != r->obs_stride) return fail(KP1_ERR_INVALID, refusal_text(who, ": obs_stride differs from the route handle's (kp1_route_set_obs_stride)"));
+  return KP1_OK;
+}
+
+// phase 2, after the caller's last refusal that needs no device: the device, the base env's argument block and the refusals that read it, then the
+// forward fields of f and the route step's block s.  Nothing is launched.  The caller still applies its overlap rule (over r->n rows) and
+// dispatches on the padded width; *pop_form != 0: the base env steps in its population form.
+int route_fwd_prepare(const char* who, kp1_mlp* m, kp1_route* r, int obs_dim, const float* obs, int obs_stride, const float* noise, float* value,
+                      float* action, float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, int auto_reset,
+                      RolloutStepArgs& f, RouteStepArgs<float>& s, int* pop_form) {
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  int mode = 0, device = 0, pop_replicas = 0;
+  int64_t n_envs = 0;
+  // the base step as route_launch_step launches it: the wrapper's scratch at pitch 56, no terminal observation, no auto-reset.  Refuses f64
+  // base handles, recorded base reward components and a bound handle in a mode kp1_step refuses.
+  rc = kp1::env_step_args_f32_population(r->base, &f.env, sizeof f.env, r->base_obs, r->base_reward, r->bytes + 4 * r->n, nullptr, 0, &mode, &n_envs,
+                                         &device, &pop_replicas, pop_form);
+  if (rc != KP1_OK) return rc;
+  f.env.obs_stride = KP1_OBS_DIM;
+  if (device != m->device) return fail(KP1_ERR_INVALID, "the route handle and the MLP workspace live on different devices");
+  if (mode != KP1_MODE_APPROACH) return fail(KP1_ERR_UNSUPPORTED, refusal_text(who, ": the route wrappers drive an approach-mode base env"));
+  if (pop_replicas > 0 && pop_replicas != m->K)
+    return fail(KP1_ERR_INVALID, refusal_text(who, ": the base env's population replica count differs from the MLP handle's"));
+  if (n_envs != r->n || n_envs <= 0 || n_envs % m->K != 0)
+    return fail(KP1_ERR_INVALID, refusal_text(who, ": the env count must be a multiple of the handle's replica count"));
+  if (n_envs / m->K > m->max_batch) return fail(KP1_ERR_INVALID, "more envs than the workspace max_batch");
+  if (!r->fused_actions) return fail(KP1_ERR_UNSUPPORTED, refusal_text(who, " runs on an fp32 route handle"));
+  fill_rollout_forward(f, m, obs, obs_stride, noise, value, action, log_prob, (int)(n_envs / m->K));
+  s.st = f.env.st; s.cfg = f.env.cfg; s.smp = f.env.smp; s.rc = r->dev_cfg; s.rt = route_table_of(r); s.rs = route_state_of<float>(r);
+  s.actions = r->fused_actions; s.base_done = r->bytes + 4 * r->n; s.obs = next_obs; s.reward = reward; s.done = done; s.terminal_obs = terminal_obs;
+  s.obs_dim = obs_dim; s.obs_stride = r->obs_stride; s.auto_reset = auto_reset;
+  return KP1_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2082,57 +2188,29 @@ int kp1_mlp_forward_route_step(kp1_mlp* m, kp1_route* r, const float* obs, int32
                                float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream) {
   if (!m || !r || !obs || !noise || !action || !next_obs || !reward || !done) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_forward_route_step");
   if (m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step covers hidden 64 / 128 (the layer-wise layout); hidden 256 takes the launch sequence");
-  const int obs_dim = r->cfg.include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM;
-  if (m->L.IN != obs_dim) return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: the MLP handle's obs_dim differs from the route handle's");
-  if (obs_stride != m->L.IN && obs_stride != m->L.INP)
-    return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: obs_stride must be the observation width (56 / 80) or its padded width (64 / 128)");
-  if (obs_stride != r->obs_stride)
-    return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: obs_stride differs from the route handle's (kp1_route_set_obs_stride)");
+  const char* who = "kp1_mlp_forward_route_step";
+  int obs_dim = 0;
+  int rc = route_fwd_check_obs(who, m, r, obs_stride, &obs_dim);
+  if (rc != KP1_OK) return rc;
   if (r->comps_enabled) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step does not record route reward components (kp1_route_enable_reward_components is on)");
   if (r->n_chains > 0) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step: the route handle has a live kp1_route_chain");
   if (r->n_waypoints > KP1_ROUTE_FUSED_MAX_WAYPOINTS)
     return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step: the route has more than KP1_ROUTE_FUSED_MAX_WAYPOINTS waypoints (the joint table overlays the kernel's LDS tiles)");
   if (r->n_replicas != m->K) return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: the route handle's replica count differs from the MLP handle's");
   if (next_obs == obs) return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step reads obs from two workgroups per tile, next_obs must not be obs");
-  int rc = mlp_check_device(m);
-  if (rc != KP1_OK) return rc;
   RouteRolloutStepArgs a{};
-  int mode = 0, device = 0, pop_replicas = 0, pop_form = 0;
-  int64_t n_envs = 0;
-  // the base step as route_launch_step launches it: the wrapper's scratch at pitch 56, no terminal observation, no auto-reset.  Refuses f64
-  // base handles, recorded base reward components and a bound handle in a mode kp1_step refuses.
-  rc = kp1::env_step_args_f32_population(r->base, &a.fwd.env, sizeof a.fwd.env, r->base_obs, r->base_reward, r->bytes + 4 * r->n, nullptr, 0, &mode, &n_envs,
-                                         &device, &pop_replicas, &pop_form);
+  RolloutStepArgs& f = a.fwd;
+  int pop_form = 0;
+  rc = route_fwd_prepare(who, m, r, obs_dim, obs, obs_stride, noise, value, action, log_prob, next_obs, reward, done, terminal_obs, 1, f, a.route, &pop_form);
   if (rc != KP1_OK) return rc;
-  a.fwd.env.obs_stride = KP1_OBS_DIM;
-  if (device != m->device) return fail(KP1_ERR_INVALID, "the route handle and the MLP workspace live on different devices");
-  if (mode != KP1_MODE_APPROACH) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step: the route wrappers drive an approach-mode base env");
-  if (pop_replicas > 0 && pop_replicas != m->K)
-    return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: the base env's population replica count differs from the MLP handle's");
-  if (n_envs != r->n || n_envs <= 0 || n_envs % m->K != 0)
-    return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: the env count must be a multiple of the handle's replica count");
-  if (n_envs / m->K > m->max_batch) return fail(KP1_ERR_INVALID, "more envs than the workspace max_batch");
-  if (!r->fused_actions) return fail(KP1_ERR_UNSUPPORTED, "kp1_mlp_forward_route_step runs on an fp32 route handle");
   {  // the value net's workgroups read obs rows while the policy net's write next_obs / terminal_obs rows of other tiles: no overlap at all
-    const float* obs_end = obs + n_envs * obs_stride;
-    const int64_t out_floats = n_envs * r->obs_stride;
+    const float* obs_end = obs + r->n * obs_stride;
+    const int64_t out_floats = r->n * r->obs_stride;
     auto overlaps = [&](const float* p) { return p && p < obs_end && obs < p + out_floats; };
     if (overlaps(next_obs) || overlaps(terminal_obs))
       return fail(KP1_ERR_INVALID, "kp1_mlp_forward_route_step: next_obs and terminal_obs must not overlap obs");
   }
-  const int Hp = m->Hp, INP = m->L.INP;
-  RolloutStepArgs& f = a.fwd;
-  f.obs = obs; f.obs_stride = obs_stride;
-  f.w1 = m->k.w1p; f.b1 = m->k.b1; f.w2 = m->k.w2; f.b2 = m->k.b2; f.w3 = m->k.w3; f.b3 = m->k.b3; f.log_std = m->k.log_std;
-  f.r_w1 = (unsigned)(2 * Hp * INP); f.r_w2 = (unsigned)(2 * Hp * Hp); f.r_b = (unsigned)(2 * Hp); f.r_w3 = (unsigned)(HEADS * Hp); f.r_b3 = (unsigned)HEADS;
-  f.n_w1 = (unsigned)(Hp * INP); f.n_w2 = (unsigned)(Hp * Hp); f.n_b = (unsigned)Hp;
-  f.noise = noise; f.value = value; f.action = action; f.log_prob = log_prob;
-  f.n = (int)(n_envs / m->K);
-  f.Kreal = obs_stride >= INP ? INP : m->L.IN;
-  RouteStepArgs<float>& s = a.route;
-  s.st = f.env.st; s.cfg = f.env.cfg; s.smp = f.env.smp; s.rc = r->dev_cfg; s.rt = route_table_of(r); s.rs = route_state_of<float>(r);
-  s.actions = r->fused_actions; s.base_done = r->bytes + 4 * r->n; s.obs = next_obs; s.reward = reward; s.done = done; s.terminal_obs = terminal_obs;
-  s.obs_dim = obs_dim; s.obs_stride = r->obs_stride; s.auto_reset = 1;
+  const int INP = m->L.INP;
   a.clipped = r->fused_actions;
   const dim3 grid((unsigned)((f.n + ES_BM - 1) / ES_BM), (unsigned)m->K, value ? 2u : 1u);
   if (INP == ES_INP) launch_route_rollout_step<ES_INP>(pop_form != 0, grid, (hipStream_t)stream, a);
@@ -2156,60 +2234,33 @@ void launch_route_chain_step(bool pop, dim3 grid, hipStream_t stream, const Rout
 template <bool EPISODE>
 int route_chain_step_launch(const char* who, kp1_mlp* m, kp1_route* r, kp1_route_chain* c, const float* obs, int32_t obs_stride, float* action,
                             float* next_obs, float* reward, uint8_t* done, int32_t* tags, int32_t n_steps, hipStream_t stream) {
-  const std::string w(who);
-  if (!m || !r || !c || !obs || !next_obs || !reward || !done) return fail(KP1_ERR_INVALID, "NULL argument to " + w);
-  if (m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, w + " covers hidden 64 / 128 (the layer-wise layout); hidden 256 takes the launch sequence");
+  if (!m || !r || !c || !obs || !next_obs || !reward || !done) return fail(KP1_ERR_INVALID, refusal_text("NULL argument to ", who));
+  if (m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, refusal_text(who, " covers hidden 64 / 128 (the layer-wise layout); hidden 256 takes the launch sequence"));
   if (const char* why = kp1::route_chain_refusal(r)) return fail(KP1_ERR_UNSUPPORTED, why);
-  if (c->owner != r) return fail(KP1_ERR_INVALID, w + ": the chain belongs to another route handle");
-  if ((int64_t)c->n_rows != r->n) return fail(KP1_ERR_INVALID, w + ": the chain was created for another env count");
-  const int obs_dim = r->cfg.include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM;
-  if (m->L.IN != obs_dim) return fail(KP1_ERR_INVALID, w + ": the MLP handle's obs_dim differs from the route handle's");
-  if (obs_stride != m->L.IN && obs_stride != m->L.INP)
-    return fail(KP1_ERR_INVALID, w + ": obs_stride must be the observation width (56 / 80) or its padded width (64 / 128)");
-  if (obs_stride != r->obs_stride) return fail(KP1_ERR_INVALID, w + ": obs_stride differs from the route handle's (kp1_route_set_obs_stride)");
+  if (c->owner != r) return fail(KP1_ERR_INVALID, refusal_text(who, ": the chain belongs to another route handle"));
+  if ((int64_t)c->n_rows != r->n) return fail(KP1_ERR_INVALID, refusal_text(who, ": the chain was created for another env count"));
+  int obs_dim = 0;
+  int rc = route_fwd_check_obs(who, m, r, obs_stride, &obs_dim);
+  if (rc != KP1_OK) return rc;
   if (r->n_waypoints > KP1_ROUTE_FUSED_MAX_WAYPOINTS)
-    return fail(KP1_ERR_UNSUPPORTED, w + ": the route has more than KP1_ROUTE_FUSED_MAX_WAYPOINTS waypoints (the joint table overlays the kernel's LDS tiles)");
+    return fail(KP1_ERR_UNSUPPORTED, refusal_text(who, ": the route has more than KP1_ROUTE_FUSED_MAX_WAYPOINTS waypoints (the joint table overlays the kernel's LDS tiles)"));
   // a chain's rows are replica-major on any handle: a single route handle of K C envs serves a policy handle of K replicas
-  if (r->n_replicas != 1 && r->n_replicas != m->K) return fail(KP1_ERR_INVALID, w + ": the route handle's replica count differs from the MLP handle's");
+  if (r->n_replicas != 1 && r->n_replicas != m->K) return fail(KP1_ERR_INVALID, refusal_text(who, ": the route handle's replica count differs from the MLP handle's"));
   if (EPISODE && (n_steps < 1 || n_steps > KP1_ROUTE_CHAIN_RUN_MAX_STEPS))
-    return fail(KP1_ERR_INVALID, w + ": n_steps must be in [1, KP1_ROUTE_CHAIN_RUN_MAX_STEPS] (1024); split a longer chain into consecutive calls");
-  int rc = mlp_check_device(m);
-  if (rc != KP1_OK) return rc;
+    return fail(KP1_ERR_INVALID, refusal_text(who, ": n_steps must be in [1, KP1_ROUTE_CHAIN_RUN_MAX_STEPS] (1024); split a longer chain into consecutive calls"));
   RouteChainStepArgs a{};
-  int mode = 0, device = 0, pop_replicas = 0, pop_form = 0;
-  int64_t n_envs = 0;
-  // the base step as route_launch_step launches it: the wrapper's scratch at pitch 56, no terminal observation, no auto-reset.  Refuses f64
-  // base handles, recorded base reward components and a bound handle in a mode kp1_step refuses.
-  rc = kp1::env_step_args_f32_population(r->base, &a.fwd.env, sizeof a.fwd.env, r->base_obs, r->base_reward, r->bytes + 4 * r->n, nullptr, 0, &mode, &n_envs,
-                                         &device, &pop_replicas, &pop_form);
-  if (rc != KP1_OK) return rc;
-  a.fwd.env.obs_stride = KP1_OBS_DIM;
-  if (device != m->device) return fail(KP1_ERR_INVALID, "the route handle and the MLP workspace live on different devices");
-  if (mode != KP1_MODE_APPROACH) return fail(KP1_ERR_UNSUPPORTED, w + ": the route wrappers drive an approach-mode base env");
-  if (pop_replicas > 0 && pop_replicas != m->K) return fail(KP1_ERR_INVALID, w + ": the base env's population replica count differs from the MLP handle's");
-  if (n_envs != r->n || n_envs <= 0 || n_envs % m->K != 0) return fail(KP1_ERR_INVALID, w + ": the env count must be a multiple of the handle's replica count");
-  if (n_envs / m->K > m->max_batch) return fail(KP1_ERR_INVALID, "more envs than the workspace max_batch");
-  if (!r->fused_actions) return fail(KP1_ERR_UNSUPPORTED, w + " runs on an fp32 route handle");
-  if (next_obs != obs) {  // a workgroup reads and writes its own rows only, all reads before the writes: exact aliasing is the evaluator's normal use
-    const float* obs_end = obs + n_envs * obs_stride;
-    if (next_obs < obs_end && obs < next_obs + n_envs * (int64_t)r->obs_stride)
-      return fail(KP1_ERR_INVALID, w + ": next_obs must be obs itself (in place) or not overlap it");
-  }
-  const int Hp = m->Hp, INP = m->L.INP;
   RolloutStepArgs& f = a.fwd;
-  f.obs = obs; f.obs_stride = obs_stride;
-  f.w1 = m->k.w1p; f.b1 = m->k.b1; f.w2 = m->k.w2; f.b2 = m->k.b2; f.w3 = m->k.w3; f.b3 = m->k.b3; f.log_std = m->k.log_std;
-  f.r_w1 = (unsigned)(2 * Hp * INP); f.r_w2 = (unsigned)(2 * Hp * Hp); f.r_b = (unsigned)(2 * Hp); f.r_w3 = (unsigned)(HEADS * Hp); f.r_b3 = (unsigned)HEADS;
-  f.n_w1 = (unsigned)(Hp * INP); f.n_w2 = (unsigned)(Hp * Hp); f.n_b = (unsigned)Hp;
-  f.noise = nullptr; f.value = nullptr; f.action = action; f.log_prob = nullptr;
-  f.n = (int)(n_envs / m->K);
-  f.Kreal = obs_stride >= INP ? INP : m->L.IN;
-  RouteStepArgs<float>& s = a.route;
-  s.st = f.env.st; s.cfg = f.env.cfg; s.smp = f.env.smp; s.rc = r->dev_cfg; s.rt = route_table_of(r); s.rs = route_state_of<float>(r);
-  s.actions = r->fused_actions; s.base_done = r->bytes + 4 * r->n; s.obs = next_obs; s.reward = reward; s.done = done; s.terminal_obs = nullptr;
-  s.obs_dim = obs_dim; s.obs_stride = r->obs_stride; s.auto_reset = 0;
+  int pop_form = 0;
+  rc = route_fwd_prepare(who, m, r, obs_dim, obs, obs_stride, nullptr, nullptr, action, nullptr, next_obs, reward, done, nullptr, 0, f, a.route, &pop_form);
+  if (rc != KP1_OK) return rc;
+  if (next_obs != obs) {  // a workgroup reads and writes its own rows only, all reads before the writes: exact aliasing is the evaluator's normal use
+    const float* obs_end = obs + r->n * obs_stride;
+    if (next_obs < obs_end && obs < next_obs + r->n * (int64_t)r->obs_stride)
+      return fail(KP1_ERR_INVALID, refusal_text(who, ": next_obs must be obs itself (in place) or not overlap it"));
+  }
+  const int INP = m->L.INP;
   a.ch = c->d; a.tags = tags; a.clipped = r->fused_actions; a.n_steps = EPISODE ? n_steps : 1;
-  if (INP != ES_INP && INP != RR_MAX_INP) return fail(KP1_ERR_UNSUPPORTED, w + ": unexpected padded observation width");
+  if (INP != ES_INP && INP != RR_MAX_INP) return fail(KP1_ERR_UNSUPPORTED, refusal_text(who, ": unexpected padded observation width"));
   HIP_TRY(hipMemsetAsync(c->d.n_alive, 0, sizeof(int32_t), stream));
   const dim3 grid((unsigned)((f.n + ES_BM - 1) / ES_BM), (unsigned)m->K);
   if (INP == ES_INP) launch_route_chain_step<ES_INP, EPISODE>(pop_form != 0, grid, stream, a);
@@ -2256,8 +2307,7 @@ int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t
   if (rc != KP1_OK) return rc;
   if (device != m->device) return fail(KP1_ERR_INVALID, "the env handle and the MLP workspace live on different devices");
   if (n_envs > m->max_batch) return fail(KP1_ERR_INVALID, "more envs than the workspace max_batch");
-  fa.obs = obs; fa.obs_stride = obs_stride; fa.Kreal = obs_stride >= m->L.INP ? m->L.INP : m->L.IN; fa.inp = m->L.INP; fa.idx = nullptr; fa.n = (int)n_envs;
-  fa.k = m->k;
+  fill_fused_head(fa, m, obs, obs_stride, nullptr, (int)n_envs);
   fa.noise = noise; fa.value = value; fa.action = action; fa.log_prob = log_prob;
   rc = launch_fused_infer_env(fa, mode, (hipStream_t)stream);
   if (rc != KP1_OK) return rc;
@@ -2309,14 +2359,12 @@ int eval_prepare(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* d
   if (n_envs <= 0 || n_envs % m->K != 0) return fail(KP1_ERR_INVALID, "kp1_eval_step: the env count must be a multiple of the handle's replica count");
   rc = mlp_check_device(m);
   if (rc != KP1_OK) return rc;
-  const int Hp = m->Hp, INP = m->L.INP;
   L->tile = tile; L->mode = mode; L->K = m->K;
   if (tile) {
     FusedArgs& fa = L->fa;
     fa = FusedArgs{};
     fa.env = a.env;
-    fa.obs = obs; fa.obs_stride = a.env.obs_stride; fa.Kreal = a.env.obs_stride >= INP ? INP : m->L.IN; fa.inp = INP; fa.idx = nullptr; fa.n = (int)n_envs;
-    fa.k = m->k;
+    fill_fused_head(fa, m, obs, a.env.obs_stride, nullptr, (int)n_envs);
     fa.ev.b = *b;
     fa.ev.step = step; fa.ev.last_step = last_step; fa.ev.confirm = confirm_steps;
     fa.ev.track_ready = ready_thresholds != nullptr;
@@ -2324,10 +2372,9 @@ int eval_prepare(kp1_mlp* m, kp1_env* env, float* obs, float* reward, uint8_t* d
     return KP1_OK;
   }
   a.b = *b;
-  a.w1 = m->k.w1p; a.b1 = m->k.b1; a.w2 = m->k.w2; a.b2 = m->k.b2; a.w3 = m->k.w3; a.b3 = m->k.b3;   // net 0 (policy) leads every array
-  a.r_w1 = (unsigned)(2 * Hp * INP); a.r_w2 = (unsigned)(2 * Hp * Hp); a.r_b = (unsigned)(2 * Hp); a.r_w3 = (unsigned)(HEADS * Hp); a.r_b3 = (unsigned)HEADS;
+  fill_layer_weights(a, m);
   a.n = (int)(n_envs / m->K);
-  a.Kreal = a.env.obs_stride >= INP ? INP : m->L.IN;
+  a.Kreal = kreal(m, a.env.obs_stride);
   a.step = step; a.last_step = last_step; a.confirm = confirm_steps;
   a.track_ready = ready_thresholds != nullptr;
   if (ready_thresholds) { a.thr_pos = ready_thresholds[0]; a.thr_ori = ready_thresholds[1]; a.thr_act = ready_thresholds[2]; a.thr_dq = ready_thresholds[3]; }
@@ -2349,10 +2396,9 @@ int eval_launch(const EvalLaunch& L, hipStream_t st) {
   HIP_TRY(hipMemsetAsync(a.b.n_alive, 0, sizeof(int32_t), st));
   const dim3 grid((unsigned)((a.n + ES_BM - 1) / ES_BM), (unsigned)L.K);
   const bool pop = L.K > 1, dock = L.mode == KP1_MODE_DOCK;
-  if (pop && dock) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_DOCK, true, EPISODE>), grid, dim3(ES_NTH), 0, st, a);
-  else if (pop) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_APPROACH, true, EPISODE>), grid, dim3(ES_NTH), 0, st, a);
-  else if (dock) hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_DOCK, false, EPISODE>), grid, dim3(ES_NTH), 0, st, a);
-  else hipLaunchKernelGGL((eval_step_kernel<KP1_MODE_APPROACH, false, EPISODE>), grid, dim3(ES_NTH), 0, st, a);
+  auto* kernel = pop ? (dock ? eval_step_kernel<KP1_MODE_DOCK, true, EPISODE> : eval_step_kernel<KP1_MODE_APPROACH, true, EPISODE>)
+                     : (dock ? eval_step_kernel<KP1_MODE_DOCK, false, EPISODE> : eval_step_kernel<KP1_MODE_APPROACH, false, EPISODE>);
+  hipLaunchKernelGGL(kernel, grid, dim3(ES_NTH), 0, st, a);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
@@ -2381,13 +2427,12 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
                       const float* adv_stats_dev, float clip_range, float ent_coef, float vf_coef, float inv_count, float* grad_out,
                       float* stats_out, int32_t grad_is_zero, void* stream_) {
   if (!m || !obs || !actions || !old_log_prob || !advantages || !returns || !grad_out) return fail(KP1_ERR_INVALID, "NULL argument");
-  if (n <= 0 || n > m->max_batch) return fail(KP1_ERR_INVALID, "n exceeds the workspace max_batch");
-  const int IN = m->L.IN, INP = m->L.INP;
-  if (obs_stride != IN && obs_stride != INP) return fail(KP1_ERR_INVALID, "obs_stride must be the observation width or its padded width (56 / 64, or 80 / 128)");
-  int rc = mlp_check_device(m);
+  int rc = check_batch_args(m, n, obs_stride);
+  if (rc != KP1_OK) return rc;
+  rc = mlp_check_device(m);
   if (rc != KP1_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  const int Hp = m->Hp, H = m->H;
+  const int Hp = m->Hp, H = m->H, INP = m->L.INP;
   const int64_t act_stride = (int64_t)m->max_batch * Hp;
   const ParamLayout& L = m->L;
   (void)grad_is_zero;  // every gradient element is written (not accumulated) by grad_finalize_kernel
@@ -2399,17 +2444,13 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
   if (adv_stats_dev) adv_mode = 2;
   else if (adv_inv_std > 0.f) adv_mode = 3;
   else if (adv_inv_std == 0.f) adv_mode = 1;
-  if (adv_mode == 1) {
-    if (pop)
-      hipLaunchKernelGGL(adv_partials_kernel<true>, dim3(N_PARTIALS, m->K), dim3(256), 0, stream, advantages, idx, n, m->partials, (unsigned)PARTIALS_STRIDE);
-    else
-      hipLaunchKernelGGL(adv_partials_kernel<false>, dim3(N_PARTIALS), dim3(256), 0, stream, advantages, idx, n, m->partials, 0u);
-  }
+  if (adv_mode == 1)
+    hipLaunchKernelGGL(pop ? adv_partials_kernel<true> : adv_partials_kernel<false>, dim3(N_PARTIALS, m->K), dim3(256), 0, stream, advantages, idx, n,
+                       m->partials, pop ? (unsigned)PARTIALS_STRIDE : 0u);
   const int hpart_stride = 10 * Hp + 32;
   if (fused) {
     FusedArgs fa{};
-    fa.obs = obs; fa.obs_stride = obs_stride; fa.Kreal = obs_stride >= INP ? INP : IN; fa.inp = INP; fa.idx = idx; fa.n = n;
-    fa.k = m->k;
+    fill_fused_head(fa, m, obs, obs_stride, idx, n);
     fa.actions = actions; fa.old_logp = old_log_prob; fa.adv = advantages; fa.ret = returns;
     fa.adv_partials = m->partials; fa.n_adv_partials = N_PARTIALS; fa.adv_stats = adv_stats_dev; fa.adv_mean = adv_mean; fa.adv_inv_std = adv_inv_std;
     fa.adv_mode = adv_mode;
@@ -2442,47 +2483,20 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     {
       const dim3 hgrid((n + HEAD_ROWS - 1) / HEAD_ROWS, m->K);
       const size_t hbytes = sizeof(float) * (HEADS * Hp + HEAD_ROWS * 8 + 84 + 2 * HEAD_ROWS * (Hp + 4));
-      if (pop) {   // Hp = 128 (kp1_mlp_create_population)
-        HIP_TRY(hipFuncSetAttribute((const void*)head_train_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hbytes));
-        hipLaunchKernelGGL((head_train_kernel<128, true>), hgrid, dim3(256), hbytes, stream, a);
-      } else if (Hp == 256) {
-        HIP_TRY(hipFuncSetAttribute((const void*)head_train_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hbytes));
-        hipLaunchKernelGGL(head_train_kernel<256>, hgrid, dim3(256), hbytes, stream, a);
-      } else {
-        HIP_TRY(hipFuncSetAttribute((const void*)head_train_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hbytes));
-        hipLaunchKernelGGL(head_train_kernel<128>, hgrid, dim3(256), hbytes, stream, a);
-      }
+      // pop: Hp = 128 (kp1_mlp_create_population)
+      auto* kernel = head_train_kernel<128, true>;
+      if (!pop) kernel = Hp == 256 ? head_train_kernel<256> : head_train_kernel<128>;
+      HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hbytes));
+      hipLaunchKernelGGL(kernel, hgrid, dim3(256), hbytes, stream, a);
     }
-    // dZ1 = (dZ2 W2) * (1 - h1^2), bias-1 gradient partials = per-row-tile column sums of dZ1
-    GemmNT g{};
-    g.A = m->dz2; g.lda = Hp; g.strideA = act_stride; g.gather = nullptr;
-    g.W = m->k.w2t; g.strideW = (int64_t)Hp * Hp;
-    g.bias = nullptr; g.strideBias = 0;
-    g.C = m->dz1; g.ldc = Hp; g.strideC = act_stride;
-    g.aux = m->h1; g.strideAux = act_stride;
-    g.colsum = m->bslab; g.strideColsum = Hp;
-    g.M = n; g.N = Hp; g.K = Hp; g.Kreal = Hp;
-    g.reps = m->K;
-    g.r_A = g.r_C = g.r_aux = (unsigned)(2 * act_stride); g.r_W = (unsigned)(2 * Hp * Hp);
-    g.r_colsum = (unsigned)((m->max_batch / 32) * 2 * Hp);
-    rc = launch_nt<EPI_DTANH>(g, stream);
+    rc = launch_nt<EPI_DTANH>(backward_nt_args(m, n), stream);
     if (rc != KP1_OK) return rc;
   }
 
   // weight gradients (split over the batch axis)
   int s2_n = 0, s1_n = 0;
   if (fused) {
-    TnFragArgs t{};
-    t.inp = INP;
-    t.dz2 = m->dz2; t.h1 = m->h1; t.dz1 = m->dz1; t.act_stride = act_stride; t.xf = m->xf;
-    t.slab2 = m->slab; t.s2_net = (int64_t)Hp * Hp; t.s2_chunk = 2 * t.s2_net;
-    t.slab1 = m->slab1; t.s1_net = (int64_t)Hp * INP; t.s1_chunk = 2 * t.s1_net;
-    t.groups = (n + FU_BM - 1) / FU_BM * (FU_BM / 8);   // the tile kernel writes whole 32-row tiles
-    auto up8 = [](int v) { return (v + 7) / 8 * 8; };
-    t.cg2 = up8((t.groups + TN_SPLIT2 - 1) / TN_SPLIT2);
-    t.cg1 = up8((t.groups + TN_SPLIT1 - 1) / TN_SPLIT1);
-    t.n_chunks2 = (t.groups + t.cg2 - 1) / t.cg2;
-    t.n_chunks1 = (t.groups + t.cg1 - 1) / t.cg1;
+    const TnFragArgs t = tn_frag_args(m, n);
     if (m->bf16x3) {   // [r3 experiment] same slabs, same chunking in 16-row fragments
       TnBf16Args b{};
       b.dz2 = m->sp_dz2; b.h1 = m->sp_h1; b.dz1 = m->sp_dz1; b.plane = (int64_t)2 * m->max_batch * Hp; b.net = (int64_t)m->max_batch * Hp;
@@ -2501,44 +2515,24 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     s2_n = t.n_chunks2;
     s1_n = t.n_chunks1;
   } else {
-    GemmTN t{};
-    t.B = n;
-    t.chunk = tn_chunk_rows(n, (Hp / 128) * (Hp / 128) * 2);
-    // dW2[o][i] = sum_b dZ2[b][o] h1[b][i]
-    t.D = m->dz2; t.ldd = Hp; t.strideD = act_stride;
-    t.X = m->h1; t.ldx = Hp; t.strideX = act_stride; t.gatherX = nullptr;
-    t.Nload = Hp; t.n_i_tiles = Hp / 128;
-    rc = launch_tn(m, t, Hp / 128, Hp, m->slab, &s2_n, stream);
-    if (rc != KP1_OK) return rc;
-    // dW1[o][i] = sum_b dZ1[b][o] x[b][i]   (i < 56)
-    t.D = m->dz1;
-    t.X = obs; t.ldx = obs_stride; t.strideX = 0; t.gatherX = idx;
-    t.Nload = obs_stride >= INP ? INP : IN; t.n_i_tiles = 1;
-    t.chunk = tn_chunk_rows(n, (Hp / 128) * 2);  // few tiles: more, shorter batch chunks keep the CUs busy
-    rc = launch_tn(m, t, Hp / 128, INP, m->slab1, &s1_n, stream);
+    rc = launch_layer_wgrads(m, obs, obs_stride, idx, n, &s2_n, &s1_n, stream);
     if (rc != KP1_OK) return rc;
   }
   FinalizeArgs f{};
-  f.L = L;
-  f.slab2 = m->slab; f.s2_ld = Hp; f.s2_net = (int64_t)Hp * Hp; f.s2_chunk = 2 * f.s2_net; f.s2_n = s2_n;
-  f.slab1 = m->slab1; f.s1_ld = INP; f.s1_net = (int64_t)Hp * INP; f.s1_chunk = 2 * f.s1_net; f.s1_n = s1_n;
-  f.bslab = m->bslab; f.b_net = Hp; f.b_tile = 2 * Hp; f.b_n = fused ? (n + FU_BM - 1) / FU_BM * (FU_BM / 32) : nt_row_tiles(n, Hp);
-  f.hpart = m->hpart; f.h_stride = 10 * Hp + 32; f.h_n = (n + HEAD_ROWS - 1) / HEAD_ROWS;
-  f.ent_coef = ent_coef; f.inv_count = inv_count; f.log_std = m->k.log_std;
-  f.grad = grad_out; f.stats = stats_out; f.sumsq = m->partials + 2 * N_PARTIALS;
+  fill_finalize(f, m, n, s2_n, s1_n, grad_out);
+  if (fused) f.b_n = (n + FU_BM - 1) / FU_BM * (FU_BM / 32);   // the tile kernel's 32-row tiles
+  f.ent_coef = ent_coef; f.inv_count = inv_count;
+  f.stats = stats_out; f.sumsq = m->partials + 2 * N_PARTIALS;
   f.step_counter = m->step_dev;
-  f.r_slab2 = (unsigned)(64 * f.s2_chunk); f.r_slab1 = (unsigned)(64 * f.s1_chunk); f.r_bslab = (unsigned)((m->max_batch / 32) * 2 * Hp);
-  f.r_hpart = (unsigned)hpart_rep; f.r_sumsq = (unsigned)PARTIALS_STRIDE;
+  f.r_sumsq = (unsigned)PARTIALS_STRIDE;
   f.hparams = pop && m->hparams_on ? m->hparams_dev : nullptr;
   const int n_main = (int)((finalize_vec_items(L) + 255) / 256);
   m->n_finalize_blocks = n_main + (int)((finalize_wide_count(L) + 3 + 31) / 32);
   if (m->n_finalize_blocks > 2048) return fail(KP1_ERR_INVALID, "parameter vector too large for the sum-of-squares partial buffer");
   {
     ProfScope ps(m, KP1_MLP_PROFILE_FINALIZE, stream);
-    if (pop)
-      KP1_LAUNCH(grad_finalize_kernel<true>, dim3(m->n_finalize_blocks, m->K), dim3(256), 0, stream, f, n_main);
-    else
-      KP1_LAUNCH(grad_finalize_kernel<false>, dim3(m->n_finalize_blocks), dim3(256), 0, stream, f, n_main);
+    auto* kernel = pop ? grad_finalize_kernel<true> : grad_finalize_kernel<false>;
+    KP1_LAUNCH(kernel, dim3(m->n_finalize_blocks, m->K), dim3(256), 0, stream, f, n_main);
   }
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
@@ -2571,7 +2565,7 @@ int kp1_mlp_time_kernels(kp1_mlp* m, const float* obs, int32_t obs_stride, int32
   int rc = mlp_check_device(m);
   if (rc != KP1_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  const int Hp = m->Hp, IN = m->L.IN, INP = m->L.INP;
+  const int Hp = m->Hp, INP = m->L.INP;
   const int64_t act_stride = (int64_t)m->max_batch * Hp;
   hipEvent_t e0, e1;
   HIP_TRY(hipEventCreate(&e0));
@@ -2589,8 +2583,8 @@ int kp1_mlp_time_kernels(kp1_mlp* m, const float* obs, int32_t obs_stride, int32
         g.C = m->h2; g.K = Hp; g.Kreal = Hp;
         if (launch_nt<EPI_BIAS_TANH>(g, stream) != KP1_OK) return KP1_ERR_NO_DEVICE;
       } else if (which == 1) {
-        g.A = m->dz2; g.lda = Hp; g.strideA = act_stride; g.W = m->k.w2t; g.strideW = (int64_t)Hp * Hp; g.C = m->dz1; g.aux = m->h1;
-        g.strideAux = act_stride; g.K = Hp; g.Kreal = Hp;
+        g = backward_nt_args(m, n);
+        g.colsum = nullptr;   // this figure is the GEMM without the bias-1 partials
         if (launch_nt<EPI_DTANH>(g, stream) != KP1_OK) return KP1_ERR_NO_DEVICE;
       } else if (which == 2) {
         GemmTN t{};
@@ -2600,13 +2594,12 @@ int kp1_mlp_time_kernels(kp1_mlp* m, const float* obs, int32_t obs_stride, int32
         if (launch_tn(m, t, Hp / 128, Hp, m->slab, nullptr, stream) != KP1_OK) return KP1_ERR_NO_DEVICE;
       } else if (which == 3) {
         g.A = obs; g.lda = obs_stride; g.strideA = 0; g.W = m->k.w1p; g.strideW = (int64_t)Hp * INP; g.bias = m->k.b1; g.strideBias = Hp;
-        g.C = m->h1; g.K = INP; g.Kreal = obs_stride >= INP ? INP : IN;
+        g.C = m->h1; g.K = INP; g.Kreal = kreal(m, obs_stride);
         if (launch_nt<EPI_BIAS_TANH>(g, stream) != KP1_OK) return KP1_ERR_NO_DEVICE;
       } else if (which == 4) {
         // the fused tile kernel on this workspace: rows 0..n of obs, loss inputs = finite scratch values (layer-2 activations)
         FusedArgs fa{};
-        fa.obs = obs; fa.obs_stride = obs_stride; fa.Kreal = obs_stride >= INP ? INP : IN; fa.inp = INP; fa.idx = nullptr; fa.n = n;
-        fa.k = m->k;
+        fill_fused_head(fa, m, obs, obs_stride, nullptr, n);
         fa.actions = m->h2; fa.old_logp = m->h2 + (int64_t)ACT * n; fa.adv = m->h2 + (int64_t)(ACT + 1) * n; fa.ret = m->h2 + (int64_t)(ACT + 2) * n;
         fa.adv_mode = 3; fa.adv_mean = 0.f; fa.adv_inv_std = 1.f;
         fa.clip_range = 0.2f; fa.vf_coef = 0.5f; fa.inv_count = 1.f / n;
@@ -2614,17 +2607,7 @@ int kp1_mlp_time_kernels(kp1_mlp* m, const float* obs, int32_t obs_stride, int32
         fa.bslab = m->bslab; fa.hpart = m->hpart; fa.hpart_stride = 10 * Hp + 32;
         if (launch_fused(fa, stream) != KP1_OK) return KP1_ERR_NO_DEVICE;
       } else {
-        TnFragArgs t{};
-    t.inp = INP;
-        t.dz2 = m->dz2; t.h1 = m->h1; t.dz1 = m->dz1; t.act_stride = act_stride; t.xf = m->xf;
-        t.slab2 = m->slab; t.s2_net = (int64_t)Hp * Hp; t.s2_chunk = 2 * t.s2_net;
-        t.slab1 = m->slab1; t.s1_net = (int64_t)Hp * INP; t.s1_chunk = 2 * t.s1_net;
-        t.groups = (n + FU_BM - 1) / FU_BM * (FU_BM / 8);   // the tile kernel writes whole 32-row tiles
-        t.cg2 = ((t.groups + TN_SPLIT2 - 1) / TN_SPLIT2 + 7) / 8 * 8;
-        t.cg1 = ((t.groups + TN_SPLIT1 - 1) / TN_SPLIT1 + 7) / 8 * 8;
-        t.n_chunks2 = (t.groups + t.cg2 - 1) / t.cg2;
-        t.n_chunks1 = (t.groups + t.cg1 - 1) / t.cg1;
-        if (launch_tn_frag(t, stream) != KP1_OK) return KP1_ERR_NO_DEVICE;
+        if (launch_tn_frag(tn_frag_args(m, n), stream) != KP1_OK) return KP1_ERR_NO_DEVICE;
       }
     }
     HIP_TRY(hipEventRecord(e1, stream));
@@ -2759,12 +2742,11 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   const int n_norm_partials = fused_norm ? m->n_finalize_blocks : N_PARTIALS;
   ProfScope ps(m, KP1_MLP_PROFILE_ADAM, stream);
   const bool pop = m->K > 1;
-  if (!fused_norm) {
-    if (pop)
-      hipLaunchKernelGGL(sumsq_partials_kernel<true>, dim3(N_PARTIALS, m->K), dim3(256), 0, stream, grad, n, m->partials + N_PARTIALS, (unsigned)PARTIALS_STRIDE);
-    else
-      hipLaunchKernelGGL(sumsq_partials_kernel<false>, dim3(N_PARTIALS), dim3(256), 0, stream, grad, n, m->partials + N_PARTIALS, 0u);
-  }
+  const unsigned r_partials = pop ? (unsigned)PARTIALS_STRIDE : 0u;   // per-replica strides and the hyper-parameter table: population forms only
+  const float* hparams = pop && m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr;
+  if (!fused_norm)
+    hipLaunchKernelGGL(pop ? sumsq_partials_kernel<true> : sumsq_partials_kernel<false>, dim3(N_PARTIALS, m->K), dim3(256), 0, stream, grad, n,
+                       m->partials + N_PARTIALS, r_partials);
   zero_grad = 0;  // gradients are overwritten by the next finalize; nothing to clear
   // step <= 0: use the device-resident counter that kp1_mlp_loss_grad's finalize kernel increments (graph-replay safe)
   const int host_step = step > 0 ? step : 1;
@@ -2776,14 +2758,10 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   m->last_params = params;
   if (frag_only) m->slab_stale = true;
   const int* step_arg = step > 0 ? (const int*)nullptr : (const int*)m->step_dev;
-  if (pop)
-    KP1_LAUNCH(adam_kernel<true>, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK), m->K), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n,
-               norm_partials, n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step,
-               (const int*)m->step_dev + 1, (unsigned)PARTIALS_STRIDE, m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr);
-  else
-    KP1_LAUNCH(adam_kernel<false>, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK)), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
-               n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1, 0u,
-               (const float*)nullptr);
+  auto* kernel = pop ? adam_kernel<true> : adam_kernel<false>;
+  KP1_LAUNCH(kernel, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK), m->K), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
+             n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1, r_partials,
+             hparams);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
@@ -2791,15 +2769,14 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
 int kp1_mlp_anchor_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const int64_t* idx, int32_t n, const float* teacher_actions,
                              float loss_weight, float* grad_out, float* loss_out, void* stream_) {
   if (!m || !obs || !teacher_actions || !grad_out || !loss_out) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_anchor_loss_grad");
-  if (n <= 0 || n > m->max_batch) return fail(KP1_ERR_INVALID, "n exceeds the workspace max_batch");
-  const int IN = m->L.IN, INP = m->L.INP;
-  if (obs_stride != IN && obs_stride != INP) return fail(KP1_ERR_INVALID, "obs_stride must be the observation width or its padded width (56 / 64, or 80 / 128)");
+  int rc = check_batch_args(m, n, obs_stride);
+  if (rc != KP1_OK) return rc;
   if (m->Hp != 128) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step runs on the layer-wise kernels: hidden must be 64 or 128");
   const bool pop = m->K > 1;
   if (pop && !idx) return fail(KP1_ERR_INVALID, "population handles gather their rows through idx [K][n]");
   const int n_blocks = (int)((m->L.total + 255) / 256);
   if (n_blocks > ANCHOR_PARTIALS) return fail(KP1_ERR_INVALID, "parameter vector too large for the anchor sum-of-squares partials");
-  int rc = mlp_check_device(m);
+  rc = mlp_check_device(m);
   if (rc != KP1_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   constexpr int Hp = 128;
@@ -2818,55 +2795,22 @@ int kp1_mlp_anchor_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, c
   {
     const dim3 hgrid((n + HEAD_ROWS - 1) / HEAD_ROWS, m->K);
     const size_t hbytes = sizeof(float) * (HEADS * Hp + HEAD_ROWS * 8 + 48 + HEAD_ROWS * (Hp + 4));
-    if (pop)
-      hipLaunchKernelGGL((head_anchor_kernel<Hp, true>), hgrid, dim3(256), hbytes, stream, a);
-    else
-      hipLaunchKernelGGL((head_anchor_kernel<Hp, false>), hgrid, dim3(256), hbytes, stream, a);
+    auto* kernel = pop ? head_anchor_kernel<Hp, true> : head_anchor_kernel<Hp, false>;
+    hipLaunchKernelGGL(kernel, hgrid, dim3(256), hbytes, stream, a);
   }
   // dZ1 = (dZ2 W2) * (1 - h1^2) and the bias-1 partials, then dW2 and dW1: kp1_mlp_loss_grad's launches (the value net's are all zeros)
-  GemmNT g{};
-  g.A = m->dz2; g.lda = Hp; g.strideA = act_stride; g.gather = nullptr;
-  g.W = m->k.w2t; g.strideW = (int64_t)Hp * Hp;
-  g.bias = nullptr; g.strideBias = 0;
-  g.C = m->dz1; g.ldc = Hp; g.strideC = act_stride;
-  g.aux = m->h1; g.strideAux = act_stride;
-  g.colsum = m->bslab; g.strideColsum = Hp;
-  g.M = n; g.N = Hp; g.K = Hp; g.Kreal = Hp;
-  g.reps = m->K;
-  g.r_A = g.r_C = g.r_aux = (unsigned)(2 * act_stride); g.r_W = (unsigned)(2 * Hp * Hp);
-  g.r_colsum = (unsigned)((m->max_batch / 32) * 2 * Hp);
-  rc = launch_nt<EPI_DTANH>(g, stream);
+  rc = launch_nt<EPI_DTANH>(backward_nt_args(m, n), stream);
   if (rc != KP1_OK) return rc;
   int s2_n = 0, s1_n = 0;
-  GemmTN t{};
-  t.B = n;
-  t.chunk = tn_chunk_rows(n, 2);
-  t.D = m->dz2; t.ldd = Hp; t.strideD = act_stride;
-  t.X = m->h1; t.ldx = Hp; t.strideX = act_stride; t.gatherX = nullptr;
-  t.Nload = Hp; t.n_i_tiles = 1;
-  rc = launch_tn(m, t, 1, Hp, m->slab, &s2_n, stream);
-  if (rc != KP1_OK) return rc;
-  t.D = m->dz1;
-  t.X = obs; t.ldx = obs_stride; t.strideX = 0; t.gatherX = idx;
-  t.Nload = obs_stride >= INP ? INP : IN;
-  rc = launch_tn(m, t, 1, INP, m->slab1, &s1_n, stream);
+  rc = launch_layer_wgrads(m, obs, obs_stride, idx, n, &s2_n, &s1_n, stream);
   if (rc != KP1_OK) return rc;
   AnchorFinalizeArgs fa{};
   FinalizeArgs& f = fa.f;
-  f.L = m->L;
-  f.slab2 = m->slab; f.s2_ld = Hp; f.s2_net = (int64_t)Hp * Hp; f.s2_chunk = 2 * f.s2_net; f.s2_n = s2_n;
-  f.slab1 = m->slab1; f.s1_ld = INP; f.s1_net = (int64_t)Hp * INP; f.s1_chunk = 2 * f.s1_net; f.s1_n = s1_n;
-  f.bslab = m->bslab; f.b_net = Hp; f.b_tile = 2 * Hp; f.b_n = nt_row_tiles(n, Hp);
-  f.hpart = m->hpart; f.h_stride = hpart_stride; f.h_n = (n + HEAD_ROWS - 1) / HEAD_ROWS;
-  f.log_std = m->k.log_std;
-  f.grad = grad_out; f.sumsq = m->anchor_partials;
-  f.r_slab2 = (unsigned)(64 * f.s2_chunk); f.r_slab1 = (unsigned)(64 * f.s1_chunk); f.r_bslab = (unsigned)((m->max_batch / 32) * 2 * Hp);
-  f.r_hpart = (unsigned)hpart_rep; f.r_sumsq = (unsigned)ANCHOR_PARTIALS;
+  fill_finalize(f, m, n, s2_n, s1_n, grad_out);
+  f.sumsq = m->anchor_partials;
+  f.r_sumsq = (unsigned)ANCHOR_PARTIALS;
   fa.loss_out = loss_out;
-  if (pop)
-    hipLaunchKernelGGL(anchor_finalize_kernel<true>, dim3(n_blocks, m->K), dim3(256), 0, stream, fa);
-  else
-    hipLaunchKernelGGL(anchor_finalize_kernel<false>, dim3(n_blocks), dim3(256), 0, stream, fa);
+  hipLaunchKernelGGL(pop ? anchor_finalize_kernel<true> : anchor_finalize_kernel<false>, dim3(n_blocks, m->K), dim3(256), 0, stream, fa);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
@@ -2883,14 +2827,10 @@ int kp1_mlp_anchor_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_
   Packed kfmt = m->k;
   kfmt.formats = PACK_SLAB | PACK_FRAG;
   m->last_params = params;
-  if (m->K > 1)
-    hipLaunchKernelGGL(anchor_adam_kernel<true>, dim3(n_blocks, m->K), dim3(ADAM_BLOCK), 0, stream, params, (const float*)grad, exp_avg, exp_avg_sq,
-                       (const double*)m->anchor_partials, n_blocks, lr, eps, max_grad_norm, m->L, kfmt, (const int*)m->step_dev, (int)step,
-                       (unsigned)ANCHOR_PARTIALS, m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr);
-  else
-    hipLaunchKernelGGL(anchor_adam_kernel<false>, dim3(n_blocks), dim3(ADAM_BLOCK), 0, stream, params, (const float*)grad, exp_avg, exp_avg_sq,
-                       (const double*)m->anchor_partials, n_blocks, lr, eps, max_grad_norm, m->L, kfmt, (const int*)m->step_dev, (int)step, 0u,
-                       (const float*)nullptr);
+  const bool pop = m->K > 1;
+  hipLaunchKernelGGL(pop ? anchor_adam_kernel<true> : anchor_adam_kernel<false>, dim3(n_blocks, m->K), dim3(ADAM_BLOCK), 0, stream, params, (const float*)grad,
+                     exp_avg, exp_avg_sq, (const double*)m->anchor_partials, n_blocks, lr, eps, max_grad_norm, m->L, kfmt, (const int*)m->step_dev, (int)step,
+                     pop ? (unsigned)ANCHOR_PARTIALS : 0u, pop && m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr);
   hipLaunchKernelGGL(anchor_count_kernel, dim3(1), dim3(1), 0, stream, m->step_dev + 1);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;

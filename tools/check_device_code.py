@@ -9,10 +9,11 @@ into its kernel; this script makes that a checked property instead of a conventi
   * every `s_setpc_b64` is a long-branch expansion (preceded by `s_getpc_b64` in the same kernel), not a return;
   * prints per-kernel scratch (private segment) sizes so a jump in spill volume is visible in the build log.
 
-Exit status 1 on a violation.  Needs only llvm-objdump / llvm-readelf from /opt/rocm (no GPU).
+Exit status 1 on a violation.  `--digest` instead prints one line of SHA-256 digests per code object (see digest()).  Needs only llvm-objdump / llvm-readelf from /opt/rocm (no GPU).
 """
 from __future__ import annotations
 
+import hashlib
 import re
 import shutil
 import subprocess
@@ -59,8 +60,20 @@ def check(lib: Path, verbose: bool = False) -> int:
     return bad
 
 
+def digest(lib: Path) -> int:
+    """Per code object: SHA-256 of its whole disassembly (without the line naming the file) and of its notes; equal for equal device code."""
+    with tempfile.TemporaryDirectory() as tmp:
+        for co in device_code_objects(lib, Path(tmp)):
+            dis, notes = (subprocess.run([str(LLVM / t), f, str(co)], check=True, capture_output=True, text=True).stdout for t, f in (("llvm-objdump", "-d"), ("llvm-readelf", "--notes")))
+            dis = "\n".join(line for line in dis.splitlines() if "file format" not in line)
+            print(co.name, "disassembly", hashlib.sha256(dis.encode()).hexdigest(), "notes", hashlib.sha256(notes.encode()).hexdigest())
+    return 0
+
+
 def main() -> int:
-    lib = Path(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else Path(__file__).resolve().parent.parent / "rl_brain_trainer_amd" / "libkp1.so"
+    lib = Path(next((a for a in sys.argv[1:] if not a.startswith("-")), Path(__file__).resolve().parent.parent / "rl_brain_trainer_amd" / "libkp1.so"))
+    if "--digest" in sys.argv:
+        return digest(lib)
     bad = check(lib, verbose="-v" in sys.argv)
     if bad:
         print(f"[check_device_code] {bad} violation(s) in {lib}", file=sys.stderr)
