@@ -257,6 +257,30 @@ int kp1_mlp_forward(kp1_mlp* m, const float* obs, int32_t obs_stride, int32_t n,
 int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t obs_stride, const float* noise, float* value, float* action,
                              float* log_prob, float* next_obs, float* reward, uint8_t* done, float* terminal_obs, void* stream);
 
+/* ALL env steps of a rollout span in one launch (hidden 64 / 128, approach mode): n_steps times what
+ * kp1_mlp_forward_env_step (and, with `trackers`, kp1_curriculum_observe / kp1_curriculum_observe_population after it) does per step, bit for
+ * bit -- every buffer, the env handle and the trackers.  A workgroup carries its 32 rows through all steps; value[t] of the whole span is
+ * computed by a second, wide launch behind it, and only if `value` is given.
+ *   Every buffer is the contiguous rollout buffer from the slice of the span's first step on, a slice being the K n rows of one step
+ * (replica-major, as kp1_mlp_forward_env_step takes them): obs holds n_steps + 1 slices at pitch obs_stride, slice t + 1 being step t's
+ * next_obs; noise [n_steps][K n][7], action likewise, value / log_prob / reward / done [n_steps][K n], terminal_obs [n_steps][K n][obs_stride].
+ * value, log_prob and terminal_obs may be NULL.  Two consecutive calls over [0, a) and [a, T) (the second on the buffers from slice a on) leave
+ * everything exactly as one call over [0, T).
+ *   trackers: NULL, or the tracker(s) the env handle's resets are bound to -- one state for K = 1 (bound with kp1_bind_stage_ptr to its
+ * stage_index), the K contiguous states of a population (kp1_bind_population_stages).  The workgroup that steps a replica's envs then replays
+ * each step's done bytes into the replica's tracker by kp1_curriculum_observe's rule, every clock advancing by steps_per_call per env step,
+ * and a promotion in step t moves the resets of step t + 1.  This needs a replica to be one row tile: at most 32 envs per replica.  With
+ * trackers == NULL a bound handle is accepted and its stage does not move during the span (nothing observes).
+ *   Refused before any launch, outputs untouched: hidden 256, the 80-float observation, f64 handles, recorded reward components, the dock
+ * mode and handles bound to dock stage records, a replica-count mismatch, an env count that is no multiple of K, obs_stride other than 56 or
+ * 64 or than the env handle's pitch, NULL required arguments (noise included), n_steps < 1 or above KP1_ROLLOUT_RUN_MAX_STEPS, terminal_obs
+ * overlapping the obs buffer, different devices, trackers that are not the handle's bound stage source, trackers with more than 32 envs per
+ * replica, trackers with a negative steps_per_call. */
+#define KP1_ROLLOUT_RUN_MAX_STEPS 2048   /* the longest n_steps of a committed config; the host splits a longer rollout */
+int kp1_rollout_run(kp1_mlp* m, kp1_env* env, float* obs, int32_t obs_stride, const float* noise, float* value, float* action,
+                    float* log_prob, float* reward, uint8_t* done, float* terminal_obs, int32_t n_steps,
+                    kp1_curriculum_state* trackers, int32_t steps_per_call, void* stream);
+
 /* One step of the batched deterministic evaluator (kp1_eval_accumulate's episodes) in ONE launch: the deterministic policy of `m` on the
  * current observations of ALL envs of `env`, action = clip(mean, -1, 1), its fp64 norm sqrt(a0^2 + ... + a6^2) (products and sums in index
  * order, uncontracted), the env step without auto-reset, and kp1_eval_accumulate's bookkeeping of env step number `step` for every buffer

@@ -695,6 +695,11 @@ int env_step_args_f32(kp1_env* e, void* out, size_t out_bytes, const void* actio
   if (rc == KP1_OK) static_cast<StepArgs<float>*>(out)->actions = (const float*)actions;
   return rc;
 }
+
+void env_bound_stage_source(const kp1_env* e, const void** stage_ptr, const void** pop_states) {
+  *stage_ptr = e->stage_ptr;
+  *pop_states = e->pop_states;
+}
 }  // namespace kp1
 
 extern "C" {

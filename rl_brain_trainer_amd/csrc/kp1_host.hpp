@@ -56,6 +56,9 @@ int env_step_args_f32(kp1_env* env, void* out, size_t out_bytes, const void* act
 // population form of the step kernel on it (pop_form).  Fails as above, and for a bound handle whose mode kp1_step refuses.
 int env_step_args_f32_population(kp1_env* env, void* out, size_t out_bytes, float* obs, void* reward, uint8_t* done, float* terminal_obs,
                                  int auto_reset, int* mode, int64_t* n_envs, int* device, int* pop_replicas, int* pop_form);
+// what the handle's auto-resets follow: the device stage word of kp1_bind_stage_ptr and the tracker array of kp1_bind_population_stages (either
+// may be nullptr), whether or not the config has curriculum stages.  kp1_rollout_run checks them against the trackers it is asked to drive.
+void env_bound_stage_source(const kp1_env* env, const void** stage_ptr, const void** pop_states);
 // kp1_env.hip -> kp1_mlp.hip: what a route chain cannot run on (an fp64 base env, route.sequence, recorded reward components, an attached prefix
 // tracker); text for kp1_last_error, or nullptr
 const char* route_chain_refusal(const kp1_route* r);

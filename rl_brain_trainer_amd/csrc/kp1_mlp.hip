@@ -1443,6 +1443,7 @@ __global__ void anchor_count_kernel(int* __restrict__ actor_extra) { *actor_extr
 #include "kp1_route_step.inc"
 #include "kp1_route_rollout_step.inc"
 #include "kp1_route_chain_step.inc"
+#include "kp1_rollout_run.inc"       // last: every kernel above keeps its place in the code object
 
 }  // namespace
 
@@ -2311,6 +2312,65 @@ int kp1_mlp_forward_env_step(kp1_mlp* m, kp1_env* env, const float* obs, int32_t
   fa.noise = noise; fa.value = value; fa.action = action; fa.log_prob = log_prob;
   rc = launch_fused_infer_env(fa, mode, (hipStream_t)stream);
   if (rc != KP1_OK) return rc;
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+// all env steps of a rollout span in one launch, the critic of the span in a second: rollout_run_kernel +
+// rollout_value_kernel.  Every refusal comes before the first launch.
+int kp1_rollout_run(kp1_mlp* m, kp1_env* env, float* obs, int32_t obs_stride, const float* noise, float* value, float* action, float* log_prob,
+                    float* reward, uint8_t* done, float* terminal_obs, int32_t n_steps, kp1_curriculum_state* trackers, int32_t steps_per_call,
+                    void* stream) {
+  if (!m || !env || !obs || !noise || !action || !reward || !done) return fail(KP1_ERR_INVALID, "NULL argument to kp1_rollout_run");
+  if (n_steps < 1 || n_steps > KP1_ROLLOUT_RUN_MAX_STEPS)
+    return fail(KP1_ERR_INVALID, "kp1_rollout_run: one call runs 1 to KP1_ROLLOUT_RUN_MAX_STEPS (2048) env steps; split a longer rollout into consecutive calls");
+  if (m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, "kp1_rollout_run covers hidden 64 / 128; hidden 256 takes kp1_mlp_forward_env_step per step");
+  if (m->L.INP != ES_INP) return fail(KP1_ERR_UNSUPPORTED, "kp1_rollout_run needs the 56-float observation (padded to 64), not the 80-float route observation");
+  if (obs_stride != m->L.IN && obs_stride != m->L.INP) return fail(KP1_ERR_INVALID, "kp1_rollout_run: obs_stride must be 56 or 64");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  RolloutRunArgs a{};
+  int mode = 0, device = 0, pop_replicas = 0, pop_form = 0;
+  int64_t n_envs = 0;
+  // refuses f64 handles, recorded reward components and a bound handle in a mode kp1_step refuses
+  rc = kp1::env_step_args_f32_population(env, &a.s.env, sizeof a.s.env, nullptr, reward, done, terminal_obs, 1, &mode, &n_envs, &device, &pop_replicas, &pop_form);
+  if (rc != KP1_OK) return rc;
+  if (device != m->device) return fail(KP1_ERR_INVALID, "the env handle and the MLP workspace live on different devices");
+  if (mode != KP1_MODE_APPROACH || a.s.env.pop_dock)
+    return fail(KP1_ERR_UNSUPPORTED, "kp1_rollout_run steps the approach mode; the dock mode and handles bound to dock stage records take kp1_mlp_forward_env_step per step");
+  if (pop_replicas > 0 && pop_replicas != m->K)
+    return fail(KP1_ERR_INVALID, "kp1_rollout_run: the env handle's population replica count differs from the MLP handle's");
+  if (n_envs <= 0 || n_envs % m->K != 0) return fail(KP1_ERR_INVALID, "kp1_rollout_run: the env count must be a multiple of the handle's replica count");
+  const int64_t n = n_envs / m->K;
+  if (n > m->max_batch) return fail(KP1_ERR_INVALID, "more envs than the workspace max_batch");
+  if (a.s.env.obs_stride != obs_stride)
+    return fail(KP1_ERR_INVALID, "kp1_rollout_run: obs_stride must be the env handle's observation pitch (step t + 1 reads what step t's env step wrote)");
+  if (terminal_obs) {
+    const float* obs_end = obs + (int64_t)(n_steps + 1) * n_envs * obs_stride;
+    if (terminal_obs < obs_end && obs < terminal_obs + (int64_t)n_steps * n_envs * obs_stride)
+      return fail(KP1_ERR_INVALID, "kp1_rollout_run: terminal_obs must not overlap the obs buffer");
+  }
+  if (trackers) {
+    if (n > ES_BM)
+      return fail(KP1_ERR_UNSUPPORTED, "kp1_rollout_run folds the tracker in only when a replica is one tile (at most 32 envs per replica); observe per step above that");
+    const void *bound_stage = nullptr, *bound_pop = nullptr;
+    kp1::env_bound_stage_source(env, &bound_stage, &bound_pop);
+    const bool ours = m->K == 1 ? (bound_stage == (const void*)&trackers->stage_index || bound_pop == (const void*)trackers) : bound_pop == (const void*)trackers;
+    if (!ours)
+      return fail(KP1_ERR_INVALID, "kp1_rollout_run: the env handle's bound stage source is not `trackers` (&trackers->stage_index for K = 1, the K states for a population)");
+    if (steps_per_call < 0) return fail(KP1_ERR_INVALID, "kp1_rollout_run: steps_per_call is negative");
+  }
+  fill_rollout_forward(a.s, m, obs, obs_stride, noise, value, action, log_prob, (int)n);
+  a.s.env.obs = obs + n_envs * obs_stride;          // slice 1: step 0's next_obs
+  a.rows = n_envs;
+  a.n_steps = n_steps;
+  a.steps_per_call = steps_per_call;
+  a.trackers = trackers;
+  a.track_stage = (a.s.env.stage_ptr != nullptr || pop_form != 0) ? 1 : 0;
+  const dim3 grid((unsigned)((a.s.n + ES_BM - 1) / ES_BM), (unsigned)m->K);
+  auto* kernel = trackers ? rollout_run_kernel<false, true> : (pop_form != 0 ? rollout_run_kernel<true, false> : rollout_run_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(ES_NTH), 0, (hipStream_t)stream, a);
+  if (value) hipLaunchKernelGGL(rollout_value_kernel, dim3(grid.x, grid.y, (unsigned)n_steps), dim3(ES_NTH), 0, (hipStream_t)stream, a);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }

@@ -44,6 +44,12 @@ class PointCurriculum:
         """device address of the int32 current stage (first word of the state)"""
         return int(self._st.value)
 
+    @property
+    def device_state(self) -> int:
+        """device address of the tracker state (a PointCurriculumPopulation: of its K contiguous states), what kp1_rollout_run takes as
+        ``trackers``"""
+        return int(self._st.value)
+
     def attach(self, env) -> None:
         """_on_training_start: the envs follow this tracker's stage from now on (callbacks.py:68-69)."""
         native.check(self.L.kp1_bind_stage_ptr(env._handle, C.c_void_p(self.stage_ptr)))

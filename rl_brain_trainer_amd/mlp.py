@@ -14,6 +14,13 @@ def _p(t: torch.Tensor | None):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def span_split(first_step: int, n_steps: int, cap: int) -> list[tuple[int, int]]:
+    """[first_step, first_step + n_steps) as consecutive (start, count) spans of at most ``cap`` steps"""
+    if n_steps < 1 or cap < 1:
+        raise ValueError("span_split needs n_steps >= 1 and cap >= 1")
+    return [(t0, min(cap, first_step + n_steps - t0)) for t0 in range(first_step, first_step + n_steps, cap)]
+
+
 class MlpKernels:
     def __init__(self, hidden: int, device: torch.device, max_batch: int = 8192, obs_dim: int = OBS_DIM, replicas: int = 1) -> None:
         """replicas > 1: a population handle (kp1_mlp_create_population) -- K independent nets trained through one launch sequence; every
@@ -32,6 +39,7 @@ class MlpKernels:
         L.kp1_mlp_forward.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         L.kp1_mlp_forward_env_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.kp1_mlp_forward_route_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.kp1_rollout_run.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]
         L.kp1_mlp_loss_grad.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, f32, f32, vp, f32, f32, f32, f32, vp, vp, i32, vp]
         L.kp1_mlp_adam_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, i32, i32, vp]
         L.kp1_mlp_time_kernels.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
@@ -141,6 +149,36 @@ class MlpKernels:
         assert obs.is_contiguous() and obs.dtype == torch.float32 and obs.shape[0] == env.n_envs
         native.check(self.L.kp1_mlp_forward_env_step(self._h, env._handle, _p(obs), obs.shape[1], _p(noise), _p(value), _p(action), _p(log_prob),
                                                      _p(next_obs), _p(reward), _p(done), _p(terminal_obs), self._stream()))
+
+    def rollout_run(self, env, obs_buf: torch.Tensor, *, noise, value, action, log_prob, reward, done, terminal_obs, first_step: int, n_steps: int,
+                    trackers=None, steps_per_call: int = 0) -> None:
+        """Env steps ``first_step .. first_step + n_steps - 1`` of a rollout in one launch per span (kp1_rollout_run), plus one wide launch
+        for the critic when ``value`` is given: per step exactly what ``forward_env_step`` (and ``trackers.observe`` after it) does, bit for
+        bit.  ``obs_buf`` [T + 1, K n, pitch] is the whole rollout buffer (slice t + 1 is step t's next_obs); ``noise`` / ``action``
+        [T, K n, 7], ``value`` / ``log_prob`` / ``reward`` / ``done`` [T, K n] and ``terminal_obs`` [T, K n, pitch] likewise, all contiguous;
+        ``value``, ``log_prob`` and ``terminal_obs`` may be None.  A span longer than ``native.ROLLOUT_RUN_MAX_STEPS`` is split into
+        consecutive calls, which leave everything as one call would.
+
+        Covered: hidden 64 / 128, a K = 1 or a population handle, an fp32 ArmKinematicVecEnv / ArmKinematicPopulationVecEnv in approach mode,
+        the 56-float observation at pitch 56 or 64.  ``trackers``: the PointCurriculum (K = 1) or PointCurriculumPopulation attached to
+        ``env``; the launch then also runs the tracker (every clock + ``steps_per_call`` per env step), which needs at most 32 envs per
+        replica.  None: nothing observes, a bound env's stage stays where it is.  Refused: hidden 256, route envs and the 80-float
+        observation, f64 envs, recorded reward components, the dock mode, a replica-count mismatch, trackers the env is not attached to."""
+        from .vec_env import ArmKinematicVecEnv
+
+        if not isinstance(env, ArmKinematicVecEnv):
+            raise TypeError(f"rollout_run steps an ArmKinematicVecEnv or an ArmKinematicPopulationVecEnv handle; {type(env).__name__} "
+                            "(route envs wrap their base env in a route step of their own) takes the per-step rollout")
+        T = obs_buf.shape[0] - 1
+        assert obs_buf.is_contiguous() and obs_buf.dtype == torch.float32 and obs_buf.dim() == 3 and obs_buf.shape[1] == env.n_envs
+        assert 0 <= first_step and n_steps >= 1 and first_step + n_steps <= T
+        for buf in (noise, value, action, log_prob, reward, done, terminal_obs):
+            assert buf is None or (buf.is_contiguous() and buf.shape[0] >= first_step + n_steps and buf.shape[1] == env.n_envs)
+        st = C.c_void_p(trackers.device_state) if trackers is not None else None
+        for t0, cnt in span_split(first_step, n_steps, native.ROLLOUT_RUN_MAX_STEPS):
+            sl = lambda buf: _p(buf[t0]) if buf is not None else None   # noqa: E731
+            native.check(self.L.kp1_rollout_run(self._h, env._handle, sl(obs_buf), obs_buf.shape[2], sl(noise), sl(value), sl(action), sl(log_prob),
+                                                sl(reward), sl(done), sl(terminal_obs), cnt, st, int(steps_per_call), self._stream()))
 
     def forward_route_step(self, env, obs: torch.Tensor, *, noise, value, action, log_prob, next_obs, reward, done, terminal_obs) -> None:
         """One rollout step of a route env in one launch (kp1_mlp_forward_route_step, include/kp1_route.h): ``forward`` on `obs` (row m = env

@@ -19,6 +19,7 @@ KP1_OK = 0
 REAL_F32, REAL_F64 = 0, 1
 EVAL_EPISODES_MAX_STEPS = 256   # include/kp1_ppo.h KP1_EVAL_EPISODES_MAX_STEPS: env steps of one kp1_eval_episodes call
 ROUTE_CHAIN_RUN_MAX_STEPS = 1024  # include/kp1_route.h KP1_ROUTE_CHAIN_RUN_MAX_STEPS: lock steps of one kp1_route_chain_run call
+ROLLOUT_RUN_MAX_STEPS = 2048      # include/kp1_ppo.h KP1_ROLLOUT_RUN_MAX_STEPS: env steps of one kp1_rollout_run call
 DONE_TERMINATED, DONE_TRUNCATED, DONE_SUCCESS, DONE_INVALID = 1, 2, 4, 8
 FLAG_PRE_NEAR_HIT, FLAG_NEAR_HIT, FLAG_SUCCESS = 1, 2, 4
 
@@ -128,6 +129,7 @@ def load() -> C.CDLL:
     L.kp1_mlp_forward_route_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.kp1_mlp_forward_route_chain_step.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.kp1_route_chain_run.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp]
+    L.kp1_rollout_run.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     L.kp1_mlp_anchor_loss_grad.argtypes = [vp, vp, i32, vp, i32, vp, f32, vp, vp, vp]
     L.kp1_mlp_anchor_adam_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, i32, vp]
     if L.kp1_config_size() != C.sizeof(kcfg.Kp1Config):

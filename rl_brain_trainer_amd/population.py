@@ -253,6 +253,10 @@ class PopulationPPO(PPO):
     last_stats = property(_per_replica("last_stats"))
 
     # ------------------------------------------------------------------ rollout
+    # the whole-rollout form (kp1_rollout_run) steps ONE env handle: the K-handle population, and the dock and route one-handle populations,
+    # keep the per-step loop; ApproachPopulationPPO takes PPO's predicate back
+    _whole_rollout = False
+
     def _draw_noise(self) -> None:
         for k in range(self.K):
             self.noise_rep[k].normal_(generator=self.gens[k])
@@ -492,6 +496,18 @@ class ApproachPopulationPPO(OneHandlePopulationPPO):
     config (tests/test_approach_population_gpu.py), and to replica k of the K-handle ``PopulationPPO``."""
 
     fused_env_type_ok = True
+
+    # all env steps of a rollout in one launch per span (PPO's rollout_run_covered predicate on pop_env / pop_curriculum; KP1_ROLLOUT_RUN)
+    _whole_rollout = PPO._whole_rollout
+
+    def _rollout_env(self) -> Any:
+        return self.pop_env
+
+    def _rollout_tracker(self) -> Any:
+        return self.pop_curriculum
+
+    def _rollout_env_type_ok(self) -> bool:
+        return True
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
                  teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:

@@ -469,6 +469,29 @@ def fused_rollout_covered(env_type_ok: bool, dtype: Any, hidden: int, obs_dim: i
     return bool(default_on) if env_var is None else env_var != "0"
 
 
+# kp1_rollout_run: all env steps of a rollout in one launch per span
+ROLLOUT_RUN_ENV = "KP1_ROLLOUT_RUN"
+ROLLOUT_RUN_WIDTHS = (64, 128)
+ROLLOUT_RUN_TRACKED_MAX_ENVS = 32      # a tracked replica must be one 32-row tile
+
+
+def rollout_run_covered(step_covered: bool, hidden: int, mode_name: str, dist_enabled: bool, has_step_callback: bool, tracker_attached: bool,
+                        envs_per_replica: int, env_var: str | None, *, tracker_ok: bool = True, default_on: bool = False) -> bool:
+    """Whether a rollout runs as ONE launch per span of env steps (``MlpKernels.rollout_run``, plus one launch for the critic) instead of
+    the per-step loop.  ``step_covered``: the configuration is one the one-launch step covers (fused_rollout_covered: env type, fp32, the
+    56-float observation, reward components off); ``hidden``: 64 / 128 (hidden 256, the tile path, keeps its step); ``mode_name``: approach
+    only; ``dist_enabled``: a data-parallel run exchanges done bytes per chunk and keeps the loop; ``has_step_callback``: a host hook after
+    every step keeps the loop; ``tracker_attached`` / ``envs_per_replica``: the launch runs the tracker itself only when a replica is one tile
+    (at most ROLLOUT_RUN_TRACKED_MAX_ENVS envs); ``tracker_ok``: the attached tracker is a PointCurriculum / PointCurriculumPopulation;
+    ``env_var``: KP1_ROLLOUT_RUN ("0": the per-step loop; any other value: the whole-rollout form wherever it is covered; None = unset:
+    ``default_on``, the calling trainer's default -- off everywhere until a measurement by DESIGN section 27's rule turns it on)."""
+    if not step_covered or hidden not in ROLLOUT_RUN_WIDTHS or mode_name != "approach" or dist_enabled or has_step_callback:
+        return False
+    if tracker_attached and (not tracker_ok or envs_per_replica > ROLLOUT_RUN_TRACKED_MAX_ENVS):
+        return False
+    return bool(default_on) if env_var is None else env_var != "0"
+
+
 # kp1_mlp_forward_route_step (DESIGN section 22): the widths, the observation widths and the route length it covers
 FUSED_ROUTE_ROLLOUT_WIDTHS = (64, 128)
 FUSED_ROUTE_ROLLOUT_OBS_DIMS = (56, 80)
@@ -530,6 +553,42 @@ class PPO:
         return fused_rollout_covered(type(env) is ArmKinematicVecEnv, env.dtype, self.cfg.hidden, self.obs_dim,
                                      getattr(env, "_reward_components_on", False), os.environ.get("KP1_FUSED_ROLLOUT"),
                                      default_on=self.cfg.hidden == 256)
+
+    # the trainer's default for the whole-rollout form while KP1_ROLLOUT_RUN is unset: off until a measurement by DESIGN section 27's rule
+    # turns it on
+    whole_rollout_default = False
+
+    @property
+    def _whole_rollout(self) -> bool:
+        """whether the next rollout is ONE launch per span of env steps (rollout_run_covered on the run's current state).  KP1_ROLLOUT_RUN is
+        read first: unset (and off by default) or "0", nothing else is looked at."""
+        var = os.environ.get(ROLLOUT_RUN_ENV)
+        if var == "0" or (var is None and not self.whole_rollout_default):
+            return False
+        env, cur = self._rollout_env(), self._rollout_tracker()
+        step_covered = fused_rollout_covered(self._rollout_env_type_ok(), env.dtype, self.cfg.hidden, self.obs_dim,
+                                             getattr(env, "_reward_components_on", False), None, default_on=True)
+        return rollout_run_covered(step_covered, self.cfg.hidden, getattr(env, "_mode_name", ""), self.dist.enabled, self.step_callback is not None,
+                                   cur is not None, self.n_envs, var, tracker_ok=isinstance(cur, PointCurriculum),
+                                   default_on=self.whole_rollout_default)
+
+    def _rollout_env(self) -> Any:
+        """the env handle a one-launch rollout steps"""
+        return self.env
+
+    def _rollout_tracker(self) -> Any:
+        """the tracker a whole-rollout launch drives (None: no tracker attached)"""
+        return self.curriculum
+
+    def _rollout_env_type_ok(self) -> bool:
+        return type(self.env) is ArmKinematicVecEnv
+
+    def _rollout_whole(self, n_steps: int | None = None, *, tracked: bool = True) -> None:
+        """env steps 0 .. n_steps - 1 (default: the whole rollout) as one launch per span, the attached tracker included"""
+        self._mlp.rollout_run(self._rollout_env(), self.obs_buf, noise=self.noise_all, value=self.val_buf, action=self.act_buf,
+                              log_prob=self.logp_buf, reward=self.rew_buf, done=self.done_buf, terminal_obs=self.term_obs_buf, first_step=0,
+                              n_steps=self.cfg.n_steps if n_steps is None else n_steps, trackers=self._rollout_tracker() if tracked else None,
+                              steps_per_call=self.n_envs)
 
     @property
     def _fused_route_step(self) -> bool:
@@ -781,15 +840,18 @@ class PPO:
         self._draw_noise()
         if graph_rollout:
             key = (tuple(getattr(env, "launch_args_version", 0) for env in self.envs), tuple(cur is not None for cur in self.curricula),
-                   cfg.gamma, cfg.gae_lambda)   # what a capture freezes
+                   cfg.gamma, cfg.gae_lambda, self._whole_rollout)   # what a capture freezes
             if self._rollout_graph is None or self._rollout_graph_key != key:
                 self._capture_rollout()
                 self._rollout_graph_key = key
             self._replay_checked("rollout", self._rollout_graph)
-        for t in range(0 if not graph_rollout else T, T):
-            self._rollout_step_hip(t)      # the launch sequence the captured rollout replays
-            if self.step_callback is not None:
-                self.step_callback(self.done_buf[t])
+        if not graph_rollout and self._whole_rollout:
+            self._rollout_whole()          # one launch per span of env steps (never with a step callback), as the captured rollout replays it
+        else:
+            for t in range(0 if not graph_rollout else T, T):
+                self._rollout_step_hip(t)      # the launch sequence the captured rollout replays
+                if self.step_callback is not None:
+                    self.step_callback(self.done_buf[t])
         if not graph_rollout:
             self._kernels_warm = True
         self.num_timesteps += T * N * world
@@ -849,7 +911,10 @@ class PPO:
                     env.use_current_stream()
                     if hasattr(env, "snapshot"):
                         env.snapshot()       # the warm-up step below must not move the episodes or the random streams
-                self._policy_env_step(0)
+                if self._whole_rollout:
+                    self._rollout_whole(1, tracked=False)     # (a bound env steps without its tracker: nothing observes this step)
+                else:
+                    self._policy_env_step(0)
                 self._warm_curricula()
                 self._post_rollout()         # the graph's tail, once eagerly (its buffers are rewritten by the real rollout)
                 fresh = []
@@ -867,9 +932,14 @@ class PPO:
             self._kernels_warm = True
         torch.cuda.synchronize(self.device)
 
+        whole = self._whole_rollout
+
         def body() -> None:
-            for t in range(T):
-                self._rollout_step_hip(t)
+            if whole:
+                self._rollout_whole()      # two launches per span: the env steps (tracker included), the critic
+            else:
+                for t in range(T):
+                    self._rollout_step_hip(t)
             self._post_rollout()
 
         self._rollout_graph = self._capture(body, on_begin=self._envs_use_current_stream)

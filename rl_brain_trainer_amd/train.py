@@ -60,6 +60,13 @@ def build_arg_parser() -> argparse.ArgumentParser:
     g.add_argument("--per-step-eval", dest="whole_episode_eval", action="store_const", const=False,
                    help="keep one launch per env step (kp1_eval_step) in those evaluations; without either flag every evaluation takes its "
                         "measured default (evaluate.WHOLE_EPISODES_DEFAULT), so the flag that names the default is a no-op")
+    r = p.add_mutually_exclusive_group()
+    r.add_argument("--whole-rollout", dest="whole_rollout", action="store_const", const=True, default=None,
+                   help="run all env steps of a rollout in one launch per span (kp1_rollout_run; sets KP1_ROLLOUT_RUN=1) where it is covered: "
+                        "hidden 64 / 128, one process, no tracker or at most 32 envs per seed; same results bit for bit")
+    r.add_argument("--per-step-rollout", dest="whole_rollout", action="store_const", const=False,
+                   help="keep one launch per env step (sets KP1_ROLLOUT_RUN=0); without either flag KP1_ROLLOUT_RUN decides, and unset it is "
+                        "the trainer's default (the per-step loop)")
     p.add_argument("--multi-launch-eval", action="store_true",
                    help="with --seed: run the gate and final evaluations as the launch sequence per env step (evaluate.run_episodes) instead of "
                         "the one-launch step (kp1_eval_step); the two forms agree bit for bit except in the action-magnitude floats "
@@ -166,6 +173,8 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
     if args.sweep and args.seeds is None:
         raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
+    if args.whole_rollout is not None:
+        os.environ["KP1_ROLLOUT_RUN"] = "1" if args.whole_rollout else "0"     # read by PPO / ApproachPopulationPPO at every rollout
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))

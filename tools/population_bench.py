@@ -114,6 +114,19 @@ def build_approach_one_handle(K: int, n_envs: int, n_steps: int, batch: int, hid
     return pop
 
 
+def build_single_seed(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, use_graphs: bool):
+    """the single-seed trainer on the Approach iteration: PPO(ArmKinematicVecEnv, PointCurriculum), seed 7 (K is 1)"""
+    from rl_brain_trainer_amd.ppo import PPO
+
+    assert K == 1, "--single-seed is one PPO run"
+    env_cfg, pcfg, tracker = _approach_setup(n_steps, batch, hidden)
+    env = ArmKinematicVecEnv(env_cfg, n_envs, seed=7)
+    cur = PointCurriculum(**tracker) if tracker else None
+    ppo = PPO(env, pcfg, curriculum=cur, use_graphs=use_graphs)
+    ppo._bench_owned = [c for c in (cur, env) if c is not None]
+    return ppo
+
+
 ROUTE_CONFIG = ROOT / "tests" / "golden" / "configs" / "route_curriculum_prefix120_routeobs_sequence2.json"
 ROUTE_PATH = ROOT / "tests" / "golden" / "synthetic_route.json"
 
@@ -185,13 +198,17 @@ def build_dock_k_handles(K: int, n_envs: int, n_steps: int, batch: int, hidden: 
 
 
 def _close(pop) -> None:
-    pop.close()
+    if hasattr(pop, "close"):
+        pop.close()
+    else:
+        pop._mlp.close()     # a single PPO has no close() of its own
     for obj in getattr(pop, "_bench_owned", []):
         obj.close()
 
 
 def measure(K: int, args, build=None) -> dict:
-    build = build or (build_route if args.route else (build_approach_one_handle if args.one_handle else build_approach))
+    build = build or (build_route if args.route else build_single_seed if args.single_seed else
+                      (build_approach_one_handle if args.one_handle else build_approach))
     pop = build(K, args.n_envs, args.n_steps, args.batch, args.hidden, True)
     pop.collect_rollouts()
     pop.train()      # warm-up: captures both graphs
@@ -589,6 +606,10 @@ def main() -> None:
     ap.add_argument("--one-launch-rollout", action="store_true", help="with --route: every rollout step as one launch (sets "
                     "KP1_FUSED_ROUTE_ROLLOUT=1: kp1_mlp_forward_route_step, DESIGN section 22); default: the launch sequence")
     ap.add_argument("--one-handle", action="store_true", help="the Approach iteration on one env handle (ApproachPopulationPPO)")
+    ap.add_argument("--single-seed", action="store_true", help="the Approach iteration of the single-seed trainer (PPO, one env handle, K = 1)")
+    ap.add_argument("--rollout-form", choices=("per-step", "whole"), default=None, help="with --one-handle or --single-seed: the rollout as one "
+                    "launch sequence per env step (sets KP1_ROLLOUT_RUN=0) or as one launch per span of env steps (KP1_ROLLOUT_RUN=1: "
+                    "kp1_rollout_run, DESIGN section 27); default: the trainer's own choice")
     ap.add_argument("--dock", action="store_true", help="the Finisher reference shape, one handle (DockPopulationPPO) and K handles")
     ap.add_argument("--no-curriculum", action="store_true", help="with --dock: no reverse-curriculum tracker")
     ap.add_argument("--ks", default="")
@@ -611,6 +632,14 @@ def main() -> None:
         if not args.route:
             ap.error("--one-launch-rollout is the route form's switch (the arm envs answer to KP1_FUSED_ROLLOUT)")
         os.environ["KP1_FUSED_ROUTE_ROLLOUT"] = "1"
+    if args.rollout_form:
+        if not (args.one_handle or args.single_seed):
+            ap.error("--rollout-form selects the rollout of the --one-handle and --single-seed iterations (the other trainers have one form)")
+        os.environ["KP1_ROLLOUT_RUN"] = "1" if args.rollout_form == "whole" else "0"
+    if args.single_seed:
+        if args.route or args.one_handle or args.dock or args.eval or args.route_eval or args.route_anchor or args.sweep:
+            ap.error("--single-seed measures the single-seed Approach iteration on its own")
+        args.ks = "1"
     if args.route and args.one_handle:
         ap.error("--one-handle is the Approach form; --route is always one handle")
     if args.eval and (args.route or args.dock or args.sweep):
@@ -647,10 +676,13 @@ def main() -> None:
     workload = (f"route_curriculum_prefix120_routeobs_sequence2 on synthetic_route.json (RoutePopulationPPO: one route env handle of K x {args.n_envs} envs)"
                 if args.route else
                 f"workspace_expansion_bigtrain.yaml Approach iteration (ApproachPopulationPPO: one env handle of K x {args.n_envs} envs)"
-                if args.one_handle else "workspace_expansion_bigtrain.yaml Approach iteration (PopulationPPO: one env handle per replica)")
+                if args.one_handle else
+                f"workspace_expansion_bigtrain.yaml Approach iteration (PPO: the single-seed trainer, {args.n_envs} envs)"
+                if args.single_seed else "workspace_expansion_bigtrain.yaml Approach iteration (PopulationPPO: one env handle per replica)")
     result = {"workload": f"{workload}, {args.n_envs} envs x {args.n_steps} steps per replica, "
                           f"minibatch {args.batch}, 2x{args.hidden}, curriculum on; seeds 7..7+K-1"
-                          + (f"; sweep {dict(SWEEP)} (replica k takes value k % n)" if SWEEP else ""), "device": torch.cuda.get_device_name(0), "rows": rows}
+                          + (f"; sweep {dict(SWEEP)} (replica k takes value k % n)" if SWEEP else "")
+                          + (f"; rollout form {args.rollout_form}" if args.rollout_form else ""), "device": torch.cuda.get_device_name(0), "rows": rows}
     if args.out:
         Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
     print(json.dumps({"aggregate_env_steps_per_s": {r["K"]: round(r["aggregate_env_steps_per_s"]) for r in rows}}))
