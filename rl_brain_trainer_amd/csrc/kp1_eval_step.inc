@@ -1,7 +1,8 @@
 // kp1_eval_step.inc -- one step of the batched deterministic evaluator in ONE launch (kp1_eval_step): deterministic policy forward of a row
 // tile, the fp64 norm of its clipped action, the env step of the tile's envs and the evaluator's per-episode bookkeeping.
 // Included by kp1_mlp.hip inside its anonymous namespace after kp1_env_step.inc (uses kp_tanh, head_dot, f32x16, step_env_lane,
-// store_obs_tile) and includes the bookkeeping it shares with eval_accumulate_kernel (kp1_eval_account.inc).
+// store_obs_tile) and includes the bookkeeping it shares with eval_accumulate_kernel (kp1_eval_account.inc) and the statements it shares with
+// the other tile kernels (kp1_x_tile_body.inc, kp1_row_reread_body.inc; DESIGN.md section 28).
 //
 // The layer-wise widths (hidden 64 / 128, both in the Hp = 128 layout of struct Packed; observation 56 padded to INP = 64), policy net only.
 // grid = (row tiles of ES_BM rows, replicas); row m of replica k is env k n + m of the handle.  A workgroup reads only its own observation
@@ -159,20 +160,9 @@ __global__ void __launch_bounds__(ES_NTH) eval_step_kernel(const EvalStepArgs a)
   do {
   // ---- 1. the tile's observation rows -> LDS (rows past the replica's last and columns >= Kreal read as zero, as gemm_nt_kernel masks them)
   {
-    constexpr int XQ = ES_INP / 4, X_LOADS = ES_BM * XQ / ES_NTH;
-    f32x4 xv[X_LOADS];
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, k = 4 * (f % XQ);
-      const int m = min(m0 + f / XQ, a.n - 1);
-      xv[j] = *reinterpret_cast<const f32x4*>(obs + (int64_t)m * a.env.obs_stride + (k < a.Kreal ? k : 0));
-    }
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, row = f / XQ, k = 4 * (f % XQ);
-      const float keep = (m0 + row < a.n && k < a.Kreal) ? 1.f : 0.f;
-      *reinterpret_cast<f32x4*>(xs + row * ES_XP + k) = xv[j] * keep;
-    }
+    constexpr int X_INP = ES_INP, X_PITCH = ES_XP;
+    const int x_n = a.n, x_stride = a.env.obs_stride, x_kreal = a.Kreal;
+#include "kp1_x_tile_body.inc"
   }
   __syncthreads();
 
@@ -210,11 +200,7 @@ __global__ void __launch_bounds__(ES_NTH) eval_step_kernel(const EvalStepArgs a)
     } else if (EPISODE && ES_EPISODE_REREADS<MODE> && live) {
       // a finished (or never started) episode is not stepped: its row of the tile is its current observation
       const f32x4* src = reinterpret_cast<const f32x4*>(obs + (int64_t)(m0 + lane) * a.env.obs_stride);
-#pragma unroll
-      for (int k = 0; k < KP1_OBS_DIM / 4; ++k) {
-        const f32x4 v = src[k];
-        o[4 * k] = v.x; o[4 * k + 1] = v.y; o[4 * k + 2] = v.z; o[4 * k + 3] = v.w;
-      }
+#include "kp1_row_reread_body.inc"
     }
     const unsigned long long bal = __ballot(alive_after != 0);
     if constexpr (!EPISODE) {

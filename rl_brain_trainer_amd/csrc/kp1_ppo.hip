@@ -271,48 +271,19 @@ __device__ __forceinline__ void curriculum_scan(kp1_curriculum_state* __restrict
         continue;
       }
     }
+    // the replay's prologue; the limits are copied here, in front of the loop: inside the lane-0 branch they move the listing
     int stage = c.stage, count = c.count, len = c.len, head = c.head, sum = c.sum, n_events = c.n_events;
-    const int window = c.window;
+    const int window = c.window, max_stage = c.max_stage, min_episodes = c.min_episodes;
+    const double threshold = c.threshold;
+    const long long timesteps = c.timesteps;
+    constexpr bool TRK_STORES_STAGE = false;               // tracker_store writes the stage when the scan is over
     while (busy) {   // lanes that saw a finished episode, in lane (= env) order
       const int src = __ffsll((long long)busy) - 1;
       busy &= busy - 1;
       unsigned long long m = __shfl(dmask, src);
       const unsigned long long sm = __shfl(smask, src);
       if (lane != 0) continue;
-      while (m) {
-        const int b = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const int success = (int)((sm >> b) & 1ull);
-        count += 1;
-        if (len < window) {
-          ring[head + len < window ? head + len : head + len - window] = success;
-          len += 1;
-          sum += success;
-        } else {
-          sum += success - ring[head];
-          ring[head] = success;
-          head = head + 1 < window ? head + 1 : 0;
-        }
-        if (stage >= c.max_stage) continue;
-        if (count < c.min_episodes) continue;
-        if (len < window) continue;
-        const double rate = (double)sum / (double)len;
-        if (rate >= c.threshold) {
-          if (n_events < KP1_CURRICULUM_MAX_HISTORY) {
-            kp1_curriculum_event& ev = st->events[n_events];
-            ev.total_timesteps = c.timesteps;
-            ev.from_stage = stage;
-            ev.to_stage = stage + 1;
-            ev.trigger_success_rate = rate;
-          }
-          n_events += 1;
-          stage += 1;
-          count = 0;
-          len = 0;
-          head = 0;
-          sum = 0;
-        }
-      }
+#include "kp1_tracker_replay_body.inc"
     }
     c.stage = __shfl(stage, 0); c.count = __shfl(count, 0); c.len = __shfl(len, 0); c.head = __shfl(head, 0);
     c.sum = __shfl(sum, 0); c.n_events = __shfl(n_events, 0);

@@ -1,7 +1,7 @@
 // kp1_rollout_run.inc -- ALL env steps of a PPO rollout span in one launch (kp1_rollout_run on an Hp = 128 handle, approach mode), and the
 // critic of the whole span in a second, wide launch.  Included by kp1_mlp.hip inside its anonymous namespace as the last kernel file (uses
-// RolloutStepArgs of kp1_rollout_step.inc, es_layer and the ES_* geometry, es_episode_env, head_dot, step_env_lane, store_obs_tile).
-// DESIGN.md section 27.
+// RolloutStepArgs of kp1_rollout_step.inc, es_layer and the ES_* geometry, es_episode_env, head_dot, step_env_lane, store_obs_tile, and the
+// statement files it shares with the other tile kernels: x tile, sampling tail, row re-read, tracker replay).  DESIGN.md sections 27, 28.
 //
 // rollout_run_kernel: grid = (row tiles of ES_BM rows, replicas), 256 threads, no z-plane.  A workgroup carries its ES_BM rows through steps
 // t = 0 .. n_steps - 1; one iteration is plane 0 of rollout_step_kernel on slice t of every rollout buffer (the buffers are contiguous
@@ -18,9 +18,8 @@
 //     afterwards, blockIdx.z = t, with the code of rollout_step_kernel's plane 1.
 // TRACK (the replica is one tile: n <= ES_BM): the workgroup that steps a replica's envs is also its PointCurriculum tracker.  After the env
 // step wave 0 reads back the done bytes its lanes have just stored and lane 0 replays them by curriculum_kernel's rule (kp1_ppo.hip; only the
-// serial branch of curriculum_scan can be reached below TRK_PARALLEL_MIN = 192 episodes, and it is restated here: num_timesteps +=
-// steps_per_call; episodes in env order; ring, window sum, promotion test in double; event record; reset of count and window).  The scalar
-// state lives in LDS across the span and is written back once at the end; the ring is updated in place in the tracker (lane 0 is its only
+// serial branch of curriculum_scan can be reached below TRK_PARALLEL_MIN = 192 episodes, and it is shared: one text included by both,
+// kp1_tracker_replay_body.inc, after num_timesteps += steps_per_call).  The scalar state lives in LDS across the span and is written back once at the end; the ring is updated in place in the tracker (lane 0 is its only
 // reader and writer during the launch); stage_index is also stored at every promotion.  The env step takes its reset stage from the LDS copy
 // (StepArgs::stage_index of the iteration, clipped as the bound-pointer form clips it), so no load of the stage can be lifted out of the loop
 // and no cache stands between a promotion in step t and a reset in step t + 1.  Without TRACK a bound handle's stage does not move during the
@@ -84,21 +83,10 @@ __global__ void __launch_bounds__(ES_NTH) rollout_run_kernel(const RolloutRunArg
     const int64_t off = (int64_t)t * a.rows;             // slice t of a buffer starts `off` rows behind slice 0
     // ---- 1. the tile's rows of obs[t] -> LDS.  They are what wave 0 stored in the previous iteration: no __restrict__ on the pointer
     {
-      constexpr int XQ = ES_INP / 4, X_LOADS = ES_BM * XQ / ES_NTH;
+      constexpr int X_INP = ES_INP, X_PITCH = ES_XP;
+      const int x_n = a.s.n, x_stride = stride, x_kreal = a.s.Kreal;
       const float* obs = a.s.obs + (off + (int64_t)rep * a.s.n) * stride;
-      f32x4 xv[X_LOADS];
-#pragma unroll
-      for (int j = 0; j < X_LOADS; ++j) {
-        const int f = tid + ES_NTH * j, k = 4 * (f % XQ);
-        const int m = min(m0 + f / XQ, a.s.n - 1);
-        xv[j] = *reinterpret_cast<const f32x4*>(obs + (int64_t)m * stride + (k < a.s.Kreal ? k : 0));
-      }
-#pragma unroll
-      for (int j = 0; j < X_LOADS; ++j) {
-        const int f = tid + ES_NTH * j, r = f / XQ, k = 4 * (f % XQ);
-        const float keep = (m0 + r < a.s.n && k < a.s.Kreal) ? 1.f : 0.f;
-        *reinterpret_cast<f32x4*>(xs + r * ES_XP + k) = xv[j] * keep;
-      }
+#include "kp1_x_tile_body.inc"
     }
     __syncthreads();
 
@@ -112,23 +100,11 @@ __global__ void __launch_bounds__(ES_NTH) rollout_run_kernel(const RolloutRunArg
     {
       const float* __restrict__ w3 = a.s.w3 + rep * a.s.r_w3;
       const float* __restrict__ b3 = a.s.b3 + rep * a.s.r_b3;
-      float v = 0.f;
-      if (ok && out < ACT) v = head_dot(h2s + row * ES_HPITCH, w3 + out * ES_HP, ES_HP) + b3[out];
-      float lp = 0.f, clipped = 0.f;
-      if (ok && out < ACT) {
-        const int64_t e = (off + env0 + row) * ACT + out;
-        const float ls = a.s.log_std[rep * a.s.r_b3 + out];
-        const float nz = a.s.noise[e];
-        const float act = fmaf(expf(ls), nz, v);
-        lp = -0.5f * nz * nz - ls - LOG_SQRT_2PI;
-        a.s.action[e] = act;
-        clipped = fminf(fmaxf(act, -1.f), 1.f);
-      }
-      acts[row * 8 + out] = clipped;
-      lp += __shfl_xor(lp, 1);
-      lp += __shfl_xor(lp, 2);
-      lp += __shfl_xor(lp, 4);
-      if (ok && out == 0 && a.s.log_prob) a.s.log_prob[off + env0 + row] = lp;
+      constexpr bool TAIL_STORES_CLIPPED = false;
+      const RolloutStepArgs fw = a.s;  // a copy, not a reference: see the fragment's header
+      const int64_t tail_off = off;
+      float* const tail_clipped = nullptr;
+#include "kp1_sample_tail_body.inc"
     }
     __syncthreads();
 
@@ -156,11 +132,7 @@ __global__ void __launch_bounds__(ES_NTH) rollout_run_kernel(const RolloutRunArg
         // that info plane on the GPU); with it the listing has the step form's chain in every instantiation.  tests/test_rollout_run_gpu.py
         // is the guard: after a compiler change that test says whether the choice still holds.
         const f32x4* src = reinterpret_cast<const f32x4*>(a.s.obs + (off + (int64_t)rep * a.s.n + min(m0 + lane, a.s.n - 1)) * stride);
-#pragma unroll
-        for (int k = 0; k < KP1_OBS_DIM / 4; ++k) {
-          const f32x4 v = src[k];
-          o[4 * k] = v.x; o[4 * k + 1] = v.y; o[4 * k + 2] = v.z; o[4 * k + 3] = v.w;
-        }
+#include "kp1_row_reread_body.inc"
       }
       // x and h1 were last read two barriers ago
       store_obs_tile(a.s.env.obs + off * stride, env0, rows_live, o, live, stride, lds);
@@ -179,41 +151,9 @@ __global__ void __launch_bounds__(ES_NTH) rollout_run_kernel(const RolloutRunArg
             int n_events = trk[RR_TRK_EVENTS], sum = trk[RR_TRK_SUM];
             const int window = st->window_episodes, min_episodes = st->min_episodes_per_stage, max_stage = st->max_stage_index;
             const double threshold = st->success_rate_threshold;
-            while (m) {                                    // finished episodes in env order
-              const int b = __ffsll((long long)m) - 1;
-              m &= m - 1;
-              const int success = (int)((sm >> b) & 1ull);
-              count += 1;
-              if (len < window) {
-                st->ring[head + len < window ? head + len : head + len - window] = success;
-                len += 1;
-                sum += success;
-              } else {
-                sum += success - st->ring[head];
-                st->ring[head] = success;
-                head = head + 1 < window ? head + 1 : 0;
-              }
-              if (stage >= max_stage) continue;
-              if (count < min_episodes) continue;
-              if (len < window) continue;
-              const double rate = (double)sum / (double)len;
-              if (rate >= threshold) {
-                if (n_events < KP1_CURRICULUM_MAX_HISTORY) {
-                  kp1_curriculum_event& ev = st->events[n_events];
-                  ev.total_timesteps = timesteps;
-                  ev.from_stage = stage;
-                  ev.to_stage = stage + 1;
-                  ev.trigger_success_rate = rate;
-                }
-                n_events += 1;
-                stage += 1;
-                count = 0;
-                len = 0;
-                head = 0;
-                sum = 0;
-                st->stage_index = stage;
-              }
-            }
+            auto& ring = st->ring;                         // updated in place: lane 0 is its only reader and writer during the launch
+            constexpr bool TRK_STORES_STAGE = true;        // the env steps that follow in this launch reset into the new stage
+#include "kp1_tracker_replay_body.inc"
             trk[RR_TRK_STAGE] = stage; trk[RR_TRK_COUNT] = count; trk[RR_TRK_LEN] = len; trk[RR_TRK_HEAD] = head;
             trk[RR_TRK_EVENTS] = n_events; trk[RR_TRK_SUM] = sum;
           }
@@ -248,21 +188,10 @@ __global__ void __launch_bounds__(ES_NTH) rollout_value_kernel(const RolloutRunA
   const int64_t off = (int64_t)blockIdx.z * a.rows;
   const int64_t env0 = (int64_t)rep * a.s.n + m0;
   {
-    constexpr int XQ = ES_INP / 4, X_LOADS = ES_BM * XQ / ES_NTH;
+    constexpr int X_INP = ES_INP, X_PITCH = ES_XP;
+    const int x_n = a.s.n, x_stride = a.s.obs_stride, x_kreal = a.s.Kreal;
     const float* __restrict__ obs = a.s.obs + (off + (int64_t)rep * a.s.n) * a.s.obs_stride;
-    f32x4 xv[X_LOADS];
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, k = 4 * (f % XQ);
-      const int m = min(m0 + f / XQ, a.s.n - 1);
-      xv[j] = *reinterpret_cast<const f32x4*>(obs + (int64_t)m * a.s.obs_stride + (k < a.s.Kreal ? k : 0));
-    }
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, r = f / XQ, k = 4 * (f % XQ);
-      const float keep = (m0 + r < a.s.n && k < a.s.Kreal) ? 1.f : 0.f;
-      *reinterpret_cast<f32x4*>(xs + r * ES_XP + k) = xv[j] * keep;
-    }
+#include "kp1_x_tile_body.inc"
   }
   __syncthreads();
   es_layer<ES_INP>(xs, ES_XP, a.s.w1 + rep * a.s.r_w1 + a.s.n_w1, a.s.b1 + rep * a.s.r_b + a.s.n_b, h1s, wave, lane);

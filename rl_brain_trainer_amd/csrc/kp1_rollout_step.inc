@@ -1,7 +1,7 @@
 // kp1_rollout_step.inc -- one rollout step of the layer-wise widths in ONE launch (kp1_mlp_forward_env_step on an Hp = 128 handle): stochastic
 // policy forward of a row tile (both nets), Gaussian sampling, and the env step of the tile's envs with its fused auto-reset.
 // Included by kp1_mlp.hip inside its anonymous namespace after kp1_eval_step.inc (uses es_layer and the ES_* geometry, head_dot, kp_tanh,
-// step_env_lane, store_obs_tile).
+// step_env_lane, store_obs_tile; x tile and sampling tail are the statement files every tile kernel includes, DESIGN.md section 28).
 //
 // Hidden 64 / 128, both in the Hp = 128 layout of struct Packed; observation 56 at pitch 56 or 64 (INP = 64).
 // grid = (row tiles of ES_BM rows, replicas, value ? 2 : 1), 256 threads; row m of replica k is env k n + m of the env handle.  Plane z = 0 runs
@@ -16,10 +16,10 @@
 //  * heads: head_infer_kernel computes head `out` of a row as head_dot over the Hp floats of the row's h2 (the policy net's for out 0..6, the
 //    value net's for out 7) against row `out` of w3, plus b3[out].  head_dot is a sequential fmaf over k: reading w3 and h2 from LDS or global
 //    memory, or the row from one plane or the other, does not change it.  value[row] is that number for out 7, stored unchanged.
-//  * sampling tail: head_infer_kernel's expressions verbatim -- act = fmaf(expf(ls), nz, v), lp = -0.5f nz nz - ls - LOG_SQRT_2PI per action
-//    lane, 0 for lane 7, then the three __shfl_xor sums over the 8-lane group.  The thread = (row = t / 8, out = t % 8) mapping is
-//    head_infer_kernel's, so every shuffle adds the same two partial sums in the same order.  Rows past the replica's last carry lp = 0 there
-//    and here and are never stored; a group never mixes rows.
+//  * sampling tail: head_infer_kernel's expressions, in the one text every one-launch rollout form includes (kp1_sample_tail_body.inc): the
+//    action, the log-density term per action lane and 0 for lane 7, then the three __shfl_xor sums over the 8-lane group.  The thread =
+//    (row = t / 8, out = t % 8) mapping is head_infer_kernel's, so every shuffle adds the same two partial sums in the same order.  Rows past
+//    the replica's last carry lp = 0 there and here and are never stored; a group never mixes rows.
 //  * env step: the launch sequence hands kp1_step_kernel clipped = fminf(fmaxf(act, -1.f), 1.f) through global memory; the same value goes to
 //    the row's lane through LDS (so a NaN action clips as it does there), and step_env_lane is the body of kp1_step_kernel.
 // No float atomics anywhere; every output element has one writer.
@@ -56,21 +56,10 @@ __global__ void __launch_bounds__(ES_NTH) rollout_step_kernel(const RolloutStepA
 
   // ---- 1. the tile's observation rows -> LDS (rows past the replica's last and columns >= Kreal read as zero, as gemm_nt_kernel masks them)
   {
-    constexpr int XQ = ES_INP / 4, X_LOADS = ES_BM * XQ / ES_NTH;
+    constexpr int X_INP = ES_INP, X_PITCH = ES_XP;
+    const int x_n = a.n, x_stride = a.obs_stride, x_kreal = a.Kreal;
     const float* __restrict__ obs = a.obs + (int64_t)rep * a.n * a.obs_stride;
-    f32x4 xv[X_LOADS];
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, k = 4 * (f % XQ);
-      const int m = min(m0 + f / XQ, a.n - 1);
-      xv[j] = *reinterpret_cast<const f32x4*>(obs + (int64_t)m * a.obs_stride + (k < a.Kreal ? k : 0));
-    }
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, row = f / XQ, k = 4 * (f % XQ);
-      const float keep = (m0 + row < a.n && k < a.Kreal) ? 1.f : 0.f;
-      *reinterpret_cast<f32x4*>(xs + row * ES_XP + k) = xv[j] * keep;
-    }
+#include "kp1_x_tile_body.inc"
   }
   __syncthreads();
 
@@ -93,23 +82,11 @@ __global__ void __launch_bounds__(ES_NTH) rollout_step_kernel(const RolloutStepA
 
   // ---- 3. z = 0: action heads and head_infer_kernel's sampling tail
   {
-    float v = 0.f;
-    if (ok && out < ACT) v = head_dot(h2s + row * ES_HPITCH, w3 + out * ES_HP, ES_HP) + b3[out];
-    float lp = 0.f, clipped = 0.f;
-    if (ok && out < ACT) {
-      const int64_t e = (env0 + row) * ACT + out;
-      const float ls = a.log_std[rep * a.r_b3 + out];
-      const float nz = a.noise[e];
-      const float act = fmaf(expf(ls), nz, v);
-      lp = -0.5f * nz * nz - ls - LOG_SQRT_2PI;
-      a.action[e] = act;
-      clipped = fminf(fmaxf(act, -1.f), 1.f);
-    }
-    acts[row * 8 + out] = clipped;
-    lp += __shfl_xor(lp, 1);
-    lp += __shfl_xor(lp, 2);
-    lp += __shfl_xor(lp, 4);
-    if (ok && out == 0 && a.log_prob) a.log_prob[env0 + row] = lp;
+    constexpr bool TAIL_STORES_CLIPPED = false;
+    const RolloutStepArgs fw = a;      // a copy, not a reference: see the fragment's header
+    const int64_t tail_off = 0;
+    float* const tail_clipped = nullptr;
+#include "kp1_sample_tail_body.inc"
   }
   __syncthreads();
   if (wave != 0) return;

@@ -24,7 +24,8 @@
 //
 // Bit-identity with kp1_mlp_forward (noise NULL, clipped) + kp1_route_chain_step for every alive row: the forward and the clamp are
 // eval_step_kernel's (head_infer_kernel with noise = NULL: act = v); base step, table conversion, scan and route step are
-// route_rollout_step_kernel's, phase by phase, with auto_reset 0 as route_launch_step passes it; the chain step is kp1_route_chain_kernel's text
+// route_rollout_step_kernel's, phase by phase (x tile and scan as the same included text: kp1_x_tile_body.inc,
+// kp1_route_nearest_scan_body.inc), with auto_reset 0 as route_launch_step passes it; the chain step is kp1_route_chain_kernel's text
 // (kp1_route_chain_body.inc) on the same inputs read from the same places.  In the EPISODE form the env index, the config address and the
 // plane stride carry the loop's run-time zero (es_episode_env's reason: addresses and config reads stay inside the iteration).
 
@@ -78,20 +79,9 @@ __global__ void __launch_bounds__(ES_NTH) route_chain_step_kernel(const RouteCha
   const float* __restrict__ b3 = a.b3 + rep * a.r_b3;
   // ---- 1. the tile's observation rows -> LDS (rows past the replica's last and columns >= Kreal read as zero, as gemm_nt_kernel masks them)
   {
-    constexpr int XQ = INP / 4, X_LOADS = ES_BM * XQ / ES_NTH;
-    f32x4 xv[X_LOADS];
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, k = 4 * (f % XQ);
-      const int m = min(m0 + f / XQ, a.n - 1);
-      xv[j] = *reinterpret_cast<const f32x4*>(obs + (int64_t)m * a.obs_stride + (k < a.Kreal ? k : 0));
-    }
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, r = f / XQ, k = 4 * (f % XQ);
-      const float keep = (m0 + r < a.n && k < a.Kreal) ? 1.f : 0.f;
-      *reinterpret_cast<f32x4*>(xs + r * G::XP + k) = xv[j] * keep;
-    }
+    constexpr int X_INP = INP, X_PITCH = G::XP;
+    const int x_n = a.n, x_stride = a.obs_stride, x_kreal = a.Kreal;
+#include "kp1_x_tile_body.inc"
   }
   __syncthreads();
 
@@ -142,12 +132,8 @@ __global__ void __launch_bounds__(ES_NTH) route_chain_step_kernel(const RouteCha
 
   // ---- 4. the nearest-waypoint scan: thread t = (row t / 8, sub-lane t % 8)
   {
-    const int64_t ic = env0 + min(row, rows_live - 1);   // whole groups of 8 lanes stay in the shuffles
-    float q[NJ];
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) q[k] = ra.route.st.r(F_Q + k, ic);
-    const float d = route_nearest_group<float>(route_q, W, out, q);
-    if (out == 0 && row_alive) ra.route.rs.nearest[env0 + row] = d;
+    const bool scan_store = row_alive;
+#include "kp1_route_nearest_scan_body.inc"
   }
   __syncthreads();
 

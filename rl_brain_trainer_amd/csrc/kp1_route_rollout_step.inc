@@ -11,7 +11,8 @@
 // Every barrier is reached by all 256 threads: dead rows are masked, never exited.
 //
 // Bit-identity with launch_forward_layers + head_infer_kernel + kp1_step_kernel + kp1_route_nearest_kernel + kp1_route_step_kernel:
-//  * forward, heads, sampling tail: the argument at the top of kp1_rollout_step.inc; layer 1 at INP = 128 is es_layer<128>, the chain layer 2
+//  * forward, heads, sampling tail: the argument at the top of kp1_rollout_step.inc, and for the x tile and the tail its very text
+//    (kp1_x_tile_body.inc, kp1_sample_tail_body.inc; the scan below is kp1_route_nearest_scan_body.inc, shared with the chain kernel); layer 1 at INP = 128 is es_layer<128>, the chain layer 2
 //    issues at either width (all k groups, the zero columns past the observation width included, as gemm_nt_kernel issues them).
 //  * base step: step_env_lane is the body of kp1_step_kernel; as there, its observation row is stored (to the wrapper's scratch, which nothing
 //    reads; row by row, which leaves LDS to the table) so that the same values stay live in both kernels, and its done byte goes to the
@@ -60,21 +61,10 @@ __global__ void __launch_bounds__(ES_NTH) route_rollout_step_kernel(const RouteR
 
   // ---- 1. the tile's observation rows -> LDS (rows past the replica's last and columns >= Kreal read as zero, as gemm_nt_kernel masks them)
   {
-    constexpr int XQ = INP / 4, X_LOADS = ES_BM * XQ / ES_NTH;
+    constexpr int X_INP = INP, X_PITCH = G::XP;
+    const int x_n = a.n, x_stride = a.obs_stride, x_kreal = a.Kreal;
     const float* __restrict__ obs = a.obs + (int64_t)rep * a.n * a.obs_stride;
-    f32x4 xv[X_LOADS];
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, k = 4 * (f % XQ);
-      const int m = min(m0 + f / XQ, a.n - 1);
-      xv[j] = *reinterpret_cast<const f32x4*>(obs + (int64_t)m * a.obs_stride + (k < a.Kreal ? k : 0));
-    }
-#pragma unroll
-    for (int j = 0; j < X_LOADS; ++j) {
-      const int f = tid + ES_NTH * j, row = f / XQ, k = 4 * (f % XQ);
-      const float keep = (m0 + row < a.n && k < a.Kreal) ? 1.f : 0.f;
-      *reinterpret_cast<f32x4*>(xs + row * G::XP + k) = xv[j] * keep;
-    }
+#include "kp1_x_tile_body.inc"
   }
   __syncthreads();
 
@@ -97,24 +87,11 @@ __global__ void __launch_bounds__(ES_NTH) route_rollout_step_kernel(const RouteR
 
   // ---- 3. z = 0: action heads and head_infer_kernel's sampling tail
   {
-    float v = 0.f;
-    if (ok && out < ACT) v = head_dot(h2s + row * ES_HPITCH, w3 + out * ES_HP, ES_HP) + b3[out];
-    float lp = 0.f, clipped = 0.f;
-    if (ok && out < ACT) {
-      const int64_t e = (env0 + row) * ACT + out;
-      const float ls = a.log_std[rep * a.r_b3 + out];
-      const float nz = a.noise[e];
-      const float act = fmaf(expf(ls), nz, v);
-      lp = -0.5f * nz * nz - ls - LOG_SQRT_2PI;
-      a.action[e] = act;
-      clipped = fminf(fmaxf(act, -1.f), 1.f);
-      ra.clipped[e] = clipped;           // what the route step reads as its caller's action
-    }
-    acts[row * 8 + out] = clipped;
-    lp += __shfl_xor(lp, 1);
-    lp += __shfl_xor(lp, 2);
-    lp += __shfl_xor(lp, 4);
-    if (ok && out == 0 && a.log_prob) a.log_prob[env0 + row] = lp;
+    constexpr bool TAIL_STORES_CLIPPED = true;   // what the route step reads as its caller's action
+    const RolloutStepArgs& fw = a;
+    const int64_t tail_off = 0;
+    float* const tail_clipped = ra.clipped;
+#include "kp1_sample_tail_body.inc"
   }
   __syncthreads();
 
@@ -137,12 +114,8 @@ __global__ void __launch_bounds__(ES_NTH) route_rollout_step_kernel(const RouteR
 
   // ---- 5. the nearest-waypoint scan: thread t = (row t / 8, sub-lane t % 8)
   {
-    const int64_t ic = env0 + min(row, rows_live - 1);   // whole groups of 8 lanes stay in the shuffles
-    float q[NJ];
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) q[k] = ra.route.st.r(F_Q + k, ic);
-    const float d = route_nearest_group<float>(route_q, W, out, q);
-    if (out == 0 && ok) ra.route.rs.nearest[env0 + row] = d;
+    const bool scan_store = ok;
+#include "kp1_route_nearest_scan_body.inc"
   }
   __syncthreads();
 

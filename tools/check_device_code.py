@@ -9,10 +9,12 @@ into its kernel; this script makes that a checked property instead of a conventi
   * every `s_setpc_b64` is a long-branch expansion (preceded by `s_getpc_b64` in the same kernel), not a return;
   * prints per-kernel scratch (private segment) sizes so a jump in spill volume is visible in the build log.
 
-Exit status 1 on a violation.  `--digest` instead prints one line of SHA-256 digests per code object (see digest()).  Needs only llvm-objdump / llvm-readelf from /opt/rocm (no GPU).
+Exit status 1 on a violation.  `--digest` instead prints one line of SHA-256 digests per code object (see digest()), and
+`--compare LIB_A LIB_B` names the kernels whose instruction text differs between two builds (see compare()).  Needs only llvm-objdump / llvm-readelf from /opt/rocm (no GPU).
 """
 from __future__ import annotations
 
+import difflib
 import hashlib
 import re
 import shutil
@@ -70,7 +72,61 @@ def digest(lib: Path) -> int:
     return 0
 
 
+def kernel_listings(dis: str) -> dict[str, list[str]]:
+    """Instruction text per symbol of one `llvm-objdump -d` output: the address and everything from `//` on (the encoding) are dropped."""
+    out: dict[str, list[str]] = {}
+    cur = None
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:", line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+            continue
+        text = re.sub(r"^\s*[0-9a-f]+:\s", "", line.split("//")[0]).strip()
+        if cur is not None and text:
+            cur.append(text)
+    return out
+
+
+def compare_disassembly(dis_a: str, dis_b: str) -> tuple[list[tuple[str, int, int, int]], list[str], list[str], int]:
+    """(differing kernels as (name, instructions in A, in B, differing lines), only in A, only in B, kernels in A or B).  Text equality only."""
+    a, b = kernel_listings(dis_a), kernel_listings(dis_b)
+    differ = []
+    for name in sorted(a.keys() & b.keys()):
+        if a[name] != b[name]:
+            ops = difflib.SequenceMatcher(None, a[name], b[name], autojunk=False).get_opcodes()
+            differ.append((name, len(a[name]), len(b[name]), sum(max(i2 - i1, j2 - j1) for tag, i1, i2, j1, j2 in ops if tag != "equal")))
+    return differ, sorted(a.keys() - b.keys()), sorted(b.keys() - a.keys()), len(a.keys() | b.keys())
+
+
+def compare(lib_a: Path, lib_b: Path) -> int:
+    """Per code object and kernel symbol: which kernels of LIB_A and LIB_B differ in instruction text.  Exit status 1 when any does."""
+    n_bad = n_all = 0
+    with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
+        cos_a, cos_b = device_code_objects(lib_a, Path(ta)), device_code_objects(lib_b, Path(tb))
+        if len(cos_a) != len(cos_b):
+            print(f"[check_device_code] {len(cos_a)} code objects in {lib_a}, {len(cos_b)} in {lib_b}")
+            return 1
+        for co_a, co_b in zip(cos_a, cos_b):
+            dis_a, dis_b = (subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], check=True, capture_output=True, text=True).stdout for co in (co_a, co_b))
+            differ, only_a, only_b, total = compare_disassembly(dis_a, dis_b)
+            for name, na, nb, nd in differ:
+                print(f"[check_device_code] {co_a.name}: differs  A {na:6d}  B {nb:6d} instructions, {nd:6d} lines differ  {name}")
+            for side, names in (("A", only_a), ("B", only_b)):
+                for name in names:
+                    print(f"[check_device_code] {co_a.name}: only in {side}  {name}")
+            n_bad += len(differ) + len(only_a) + len(only_b)
+            n_all += total
+    print(f"[check_device_code] {n_bad} of {n_all} kernels differ")
+    return 1 if n_bad else 0
+
+
 def main() -> int:
+    if "--compare" in sys.argv:
+        libs = [Path(a) for a in sys.argv[1:] if not a.startswith("-")]
+        if len(libs) != 2:
+            print("usage: check_device_code.py --compare LIB_A LIB_B", file=sys.stderr)
+            return 2
+        return compare(*libs)
     lib = Path(next((a for a in sys.argv[1:] if not a.startswith("-")), Path(__file__).resolve().parent.parent / "rl_brain_trainer_amd" / "libkp1.so"))
     if "--digest" in sys.argv:
         return digest(lib)
