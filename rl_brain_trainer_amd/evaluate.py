@@ -194,6 +194,77 @@ _STATE_SLICES = (("q", 0, 7), ("dq", 7, 14), ("prev_action", 14, 21), ("goal_q",
 _ALIVE_CHECK_EVERY = 8      # env steps between two reads of the device's alive-episode counter
 
 
+def _ptr(t: torch.Tensor | None) -> C.c_void_p | None:
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class EpisodeBuffers:
+    """The per-episode accumulators of the batched evaluator (include/kp1.h kp1_eval_buffers) over ``n_episodes`` episodes: the tensors as
+    attributes named after the fields of native.EvalBuffers, ``struct`` the native.EvalBuffers over them (the object keeps the tensors alive
+    as long as the struct), and ``results()`` the meaning of every plane row.  The four ``hand_*`` tensors are None (NULL in the struct)
+    without ``want_hand``.  Nothing here calls the library, so it works on a CPU device too (tests/test_eval_buffers_cpu.py)."""
+    NAMES = tuple(name for name, _ in native.EvalBuffers._fields_)
+
+    def __init__(self, n_episodes: int, device: torch.device, want_hand: bool) -> None:
+        n, f64, i32, u8 = int(n_episodes), torch.float64, torch.int32, torch.uint8
+        layout = {"metrics": ((8, n), f64), "counters": ((4, n), i32), "flags": ((4, n), u8), "state": ((n, 34), f64),
+                  "hand_metrics": ((8, n), f64), "hand_step": ((n,), i32), "hand_success": ((n,), u8), "hand_state": ((n, 34), f64),
+                  "n_alive": ((1,), i32)}
+        self.want_hand = bool(want_hand)
+        for name in self.NAMES:
+            shape, dtype = layout[name]
+            if name.startswith("hand_") and not self.want_hand:
+                setattr(self, name, None)
+            else:       # the kernels write every element of an active episode; only the alive counter is read before it is written
+                setattr(self, name, (torch.zeros if name == "n_alive" else torch.empty)(shape, dtype=dtype, device=device))
+        self.struct = native.EvalBuffers(*[_ptr(getattr(self, name)) for name in self.NAMES])
+
+    @staticmethod
+    def thresholds(ready_cfg):
+        """the four dock_coarse_ready thresholds (pos, ori, action, dq) as the library takes them; None without a ready config"""
+        if ready_cfg is None:
+            return None
+        return (C.c_double * 4)(ready_cfg.dock_coarse_ready_pos_threshold_m, ready_cfg.dock_coarse_ready_ori_threshold_rad,
+                                ready_cfg.dock_coarse_ready_action_threshold, ready_cfg.dock_coarse_ready_dq_threshold)
+
+    def results(self) -> tuple[dict[str, torch.Tensor], dict[str, torch.Tensor] | None]:
+        """(final_result, handoff_result) of run_episodes: which row of which plane is which key; handoff_result None without handoff buffers"""
+        metrics, counters, flags = self.metrics, self.counters, self.flags
+        res = {
+            "success": flags[1].bool(), "final_position_error": metrics[0], "final_orientation_error": metrics[1], "min_position_error": metrics[2],
+            "min_orientation_error": metrics[3], "final_action_magnitude": metrics[4], "final_dq_norm": metrics[5], "sum_action": metrics[6],
+            "sum_dq": metrics[7], "ready_hit": flags[2].bool(), "max_ready_streak": counters[1], "first_ready_step": counters[2], "step_count": counters[0],
+        }
+        steps = res["step_count"].clamp_min(1).double()
+        res["mean_action_magnitude"] = res["sum_action"] / steps
+        res["mean_dq_norm"] = res["sum_dq"] / steps
+        for k, lo, hi in _STATE_SLICES:
+            res["state_" + k] = self.state[:, lo:hi].contiguous()
+        if not self.want_hand:
+            return res, None
+        hand_metrics = self.hand_metrics
+        hand = {"valid": flags[3].bool(), "final_position_error": hand_metrics[0], "final_orientation_error": hand_metrics[1],
+                "final_action_magnitude": hand_metrics[2], "final_dq_norm": hand_metrics[3], "min_position_error": hand_metrics[4],
+                "min_orientation_error": hand_metrics[5], "step_count": self.hand_step, "success": self.hand_success.bool()}
+        hsteps = self.hand_step.clamp_min(1).double()
+        hand["mean_action_magnitude"] = hand_metrics[6] / hsteps
+        hand["mean_dq_norm"] = hand_metrics[7] / hsteps
+        for k, lo, hi in _STATE_SLICES:
+            hand["state_" + k] = self.hand_state[:, lo:hi].contiguous()
+        return res, hand
+
+
+def _start_episodes(L, env: ArmKinematicVecEnv, ready_cfg, handoff_confirm_steps: int | None, active: torch.Tensor | None, stream):
+    """what both runners do between the reset and their loop: the buffers of ``env``'s episodes (handoff buffers when there are a confirm count
+    and a ready config), and kp1_eval_accumulate's step 0 under the ``active`` mask on ``stream`` -> (bufs, thr, confirm)"""
+    bufs = EpisodeBuffers(env.n_envs, env.device, want_hand=handoff_confirm_steps is not None and ready_cfg is not None)
+    thr = bufs.thresholds(ready_cfg)
+    confirm = int(handoff_confirm_steps or 0)
+    bufs.active = None if active is None else active.to(env.device).to(torch.uint8).contiguous()    # lives as long as the buffers: the launch reads it
+    native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs.struct), None, None, _ptr(bufs.active), 0, thr, confirm, stream))
+    return bufs, thr, confirm
+
+
 def run_episodes(env: ArmKinematicVecEnv, policy: PolicyFn, reset_options: dict[str, Any], *, ready_cfg=None, handoff_confirm_steps: int | None = None,
                  active: torch.Tensor | None = None, max_steps: int | None = None) -> tuple[dict[str, torch.Tensor], dict[str, torch.Tensor] | None]:
     """All episodes in lock step until each has terminated or truncated (_run_policy / _run_approach_with_handoff).
@@ -209,62 +280,20 @@ def run_episodes(env: ArmKinematicVecEnv, policy: PolicyFn, reset_options: dict[
     form (_run_episodes_reference; tests/test_eval_checkpoint_gpu.py)."""
     if not isinstance(env, ArmKinematicVecEnv):
         raise TypeError("run_episodes drives an ArmKinematicVecEnv (kp1_eval_accumulate reads its handle); the route wrappers have their own evaluator")
-    E = env.n_envs
-    dev = env.device
     L = native.load()
     env.use_current_stream()
     obs = env.reset(options=reset_options).clone()
-    f64, i32, u8 = torch.float64, torch.int32, torch.uint8
-    metrics = torch.empty((8, E), dtype=f64, device=dev)
-    counters = torch.empty((4, E), dtype=i32, device=dev)
-    flags = torch.empty((4, E), dtype=u8, device=dev)
-    state = torch.empty((E, 34), dtype=f64, device=dev)
-    n_alive = torch.zeros(1, dtype=i32, device=dev)
-    want_hand = handoff_confirm_steps is not None and ready_cfg is not None
-    confirm = int(handoff_confirm_steps or 0)
-    hand_metrics = torch.empty((8, E), dtype=f64, device=dev) if want_hand else None
-    hand_step = torch.empty(E, dtype=i32, device=dev) if want_hand else None
-    hand_success = torch.empty(E, dtype=u8, device=dev) if want_hand else None
-    hand_state = torch.empty((E, 34), dtype=f64, device=dev) if want_hand else None
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    bufs = native.EvalBuffers(ptr(metrics), ptr(counters), ptr(flags), ptr(state), ptr(hand_metrics), ptr(hand_step), ptr(hand_success), ptr(hand_state),
-                              ptr(n_alive))
-    thr = None
-    if ready_cfg is not None:
-        thr = (C.c_double * 4)(ready_cfg.dock_coarse_ready_pos_threshold_m, ready_cfg.dock_coarse_ready_ori_threshold_rad,
-                               ready_cfg.dock_coarse_ready_action_threshold, ready_cfg.dock_coarse_ready_dq_threshold)
-    act_mask = None if active is None else active.to(dev).to(u8).contiguous()
-    native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs), None, None, ptr(act_mask), 0, thr, confirm, None))
+    bufs, thr, confirm = _start_episodes(L, env, ready_cfg, handoff_confirm_steps, active, None)
     limit = int(max_steps or (env.config.c.termination.max_episode_steps + 1))
     for step in range(1, limit + 1):
-        if (step - 1) % _ALIVE_CHECK_EVERY == 0 and int(n_alive.item()) == 0:
+        if (step - 1) % _ALIVE_CHECK_EVERY == 0 and int(bufs.n_alive.item()) == 0:
             break
         action = policy(obs)
         a_norm = torch.linalg.vector_norm(action.double(), dim=1).contiguous()
         obs, _, done = env.step(action, auto_reset=False)
         obs = obs.clone()
-        native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs), ptr(a_norm), ptr(done), None, step, thr, confirm, None))
-    res = {
-        "success": flags[1].bool(), "final_position_error": metrics[0], "final_orientation_error": metrics[1], "min_position_error": metrics[2],
-        "min_orientation_error": metrics[3], "final_action_magnitude": metrics[4], "final_dq_norm": metrics[5], "sum_action": metrics[6],
-        "sum_dq": metrics[7], "ready_hit": flags[2].bool(), "max_ready_streak": counters[1], "first_ready_step": counters[2], "step_count": counters[0],
-    }
-    steps = res["step_count"].clamp_min(1).double()
-    res["mean_action_magnitude"] = res["sum_action"] / steps
-    res["mean_dq_norm"] = res["sum_dq"] / steps
-    for k, lo, hi in _STATE_SLICES:
-        res["state_" + k] = state[:, lo:hi].contiguous()
-    hand = None
-    if want_hand:
-        hand = {"valid": flags[3].bool(), "final_position_error": hand_metrics[0], "final_orientation_error": hand_metrics[1],
-                "final_action_magnitude": hand_metrics[2], "final_dq_norm": hand_metrics[3], "min_position_error": hand_metrics[4],
-                "min_orientation_error": hand_metrics[5], "step_count": hand_step, "success": hand_success.bool()}
-        hsteps = hand_step.clamp_min(1).double()
-        hand["mean_action_magnitude"] = hand_metrics[6] / hsteps
-        hand["mean_dq_norm"] = hand_metrics[7] / hsteps
-        for k, lo, hi in _STATE_SLICES:
-            hand["state_" + k] = hand_state[:, lo:hi].contiguous()
-    return res, hand
+        native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs.struct), _ptr(a_norm), _ptr(done), None, step, thr, confirm, None))
+    return bufs.results()
 
 
 def _run_episodes_reference(env: ArmKinematicVecEnv, policy: PolicyFn, reset_options: dict[str, Any], *, ready_cfg=None, handoff_confirm_steps: int | None = None,
@@ -445,66 +474,25 @@ def run_episodes_fused(env: ArmKinematicVecEnv, mlp: Any, reset_options: dict[st
     (tests/test_eval_episodes_gpu.py); the env handle is left with every episode at its own last step instead of stepped on in lock step."""
     if not isinstance(env, ArmKinematicVecEnv):
         raise TypeError("run_episodes_fused drives an ArmKinematicVecEnv (kp1_eval_step steps its handle)")
-    E = env.n_envs
-    dev = env.device
     L = native.load()
     env.use_current_stream()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
     env.reset(options=reset_options)
-    f64, i32, u8 = torch.float64, torch.int32, torch.uint8
-    metrics = torch.empty((8, E), dtype=f64, device=dev)
-    counters = torch.empty((4, E), dtype=i32, device=dev)
-    flags = torch.empty((4, E), dtype=u8, device=dev)
-    state = torch.empty((E, 34), dtype=f64, device=dev)
-    n_alive = torch.zeros(1, dtype=i32, device=dev)
-    want_hand = handoff_confirm_steps is not None and ready_cfg is not None
-    confirm = int(handoff_confirm_steps or 0)
-    hand_metrics = torch.empty((8, E), dtype=f64, device=dev) if want_hand else None
-    hand_step = torch.empty(E, dtype=i32, device=dev) if want_hand else None
-    hand_success = torch.empty(E, dtype=u8, device=dev) if want_hand else None
-    hand_state = torch.empty((E, 34), dtype=f64, device=dev) if want_hand else None
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    bufs = native.EvalBuffers(ptr(metrics), ptr(counters), ptr(flags), ptr(state), ptr(hand_metrics), ptr(hand_step), ptr(hand_success), ptr(hand_state),
-                              ptr(n_alive))
-    thr = None
-    if ready_cfg is not None:
-        thr = (C.c_double * 4)(ready_cfg.dock_coarse_ready_pos_threshold_m, ready_cfg.dock_coarse_ready_ori_threshold_rad,
-                               ready_cfg.dock_coarse_ready_action_threshold, ready_cfg.dock_coarse_ready_dq_threshold)
-    act_mask = None if active is None else active.to(dev).to(u8).contiguous()
-    native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs), None, None, ptr(act_mask), 0, thr, confirm, stream))
+    bufs, thr, confirm = _start_episodes(L, env, ready_cfg, handoff_confirm_steps, active, stream)
     limit = int(max_steps or (env.config.c.termination.max_episode_steps + 1))
     if whole_episodes:
         for first in range(1, limit + 1, _EPISODES_CAP):
-            if first > 1 and int(n_alive.item()) == 0:
+            if first > 1 and int(bufs.n_alive.item()) == 0:
                 break
-            native.check(L.kp1_eval_episodes(mlp._h, env._handle, ptr(env.obs), ptr(env.reward), ptr(env.done), C.byref(bufs), first,
+            native.check(L.kp1_eval_episodes(mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(bufs.struct), first,
                                              min(first + _EPISODES_CAP - 1, limit), thr, confirm, stream))
     else:
         for step in range(1, limit + 1):
-            if (step - 1) % _ALIVE_CHECK_EVERY == 0 and int(n_alive.item()) == 0:
+            if (step - 1) % _ALIVE_CHECK_EVERY == 0 and int(bufs.n_alive.item()) == 0:
                 break
-            native.check(L.kp1_eval_step(mlp._h, env._handle, ptr(env.obs), ptr(env.reward), ptr(env.done), C.byref(bufs), step, thr, confirm, stream))
-    res = {
-        "success": flags[1].bool(), "final_position_error": metrics[0], "final_orientation_error": metrics[1], "min_position_error": metrics[2],
-        "min_orientation_error": metrics[3], "final_action_magnitude": metrics[4], "final_dq_norm": metrics[5], "sum_action": metrics[6],
-        "sum_dq": metrics[7], "ready_hit": flags[2].bool(), "max_ready_streak": counters[1], "first_ready_step": counters[2], "step_count": counters[0],
-    }
-    steps = res["step_count"].clamp_min(1).double()
-    res["mean_action_magnitude"] = res["sum_action"] / steps
-    res["mean_dq_norm"] = res["sum_dq"] / steps
-    for k, lo, hi in _STATE_SLICES:
-        res["state_" + k] = state[:, lo:hi].contiguous()
-    hand = None
-    if want_hand:
-        hand = {"valid": flags[3].bool(), "final_position_error": hand_metrics[0], "final_orientation_error": hand_metrics[1],
-                "final_action_magnitude": hand_metrics[2], "final_dq_norm": hand_metrics[3], "min_position_error": hand_metrics[4],
-                "min_orientation_error": hand_metrics[5], "step_count": hand_step, "success": hand_success.bool()}
-        hsteps = hand_step.clamp_min(1).double()
-        hand["mean_action_magnitude"] = hand_metrics[6] / hsteps
-        hand["mean_dq_norm"] = hand_metrics[7] / hsteps
-        for k, lo, hi in _STATE_SLICES:
-            hand["state_" + k] = hand_state[:, lo:hi].contiguous()
-    return res, hand
+            native.check(L.kp1_eval_step(mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(bufs.struct), step, thr, confirm,
+                                         stream))
+    return bufs.results()
 
 
 def _handoff_options(src: dict[str, torch.Tensor], mode: str) -> dict[str, Any]:
@@ -534,36 +522,66 @@ def evaluate_workspace_expansion(*, approach_policy: PolicyFn, finisher_policy: 
     PPO (or a bound ``predict`` of one) on a handle the step covers, and through run_episodes otherwise; False always takes run_episodes; True
     raises ValueError for a phase that is not covered.  The two forms agree bit for bit except in the action-magnitude floats, which may
     differ by an ulp (the norm is summed in index order instead of vector_norm's reduction)."""
+    stages, cat = _stage_suite(approach_cfg, seed, stage_indices, episodes, device)
+    E = cat["initial_q"].shape[0]
+    r = approach_cfg.c.reward
+    env_kw = dict(device=device, seed=seed, obs_stride=obs_stride)
+    phase = dict(one_launch=one_launch, whole_episodes=whole_episodes, entry="evaluate_workspace_expansion")
+
+    env = _phase_env(approach_cfg, E, **env_kw)
+    a_res, hand = run_phase(env, approach_policy, {"initial_q": cat["initial_q"], "goal_q": cat["goal_q"], "goal_pose6": cat["goal_pose6"],
+                                                   "policy_mode": "approach"}, what="Approach", ready_cfg=r,
+                            handoff_confirm_steps=handoff_confirm_steps, **phase)
+    env.close()
+    final_ready, has_hand, f_res = _finisher_phase(a_res, hand, r, finisher_policy, finisher_cfg, env_kw, **phase)
+    cols = _eval_columns(a_res, final_ready, has_hand, f_res, handoff_confirm_steps)
+    return _workspace_payload(cols, cat["goal_pose6"], approach_cfg=approach_cfg, stages=stages, episodes=episodes, seed=seed,
+                              handoff_confirm_steps=handoff_confirm_steps, gate_config=gate_config, artifact_root=artifact_root)
+
+
+def _stage_suite(approach_cfg: kcfg.EnvConfig, seed: int, stage_indices: list[int] | None, episodes: int, device) -> tuple[list[int], dict[str, np.ndarray]]:
+    """(stages, cat): the stage list clipped to the curriculum (every stage when none is given) and the curriculum-local suites of those
+    stages, ``episodes`` each, concatenated in that order"""
     n_stages = approach_cfg.n_stages
     stages = stage_indices if stage_indices is not None else list(range(n_stages))
     stages = [int(np.clip(s, 0, n_stages - 1)) for s in stages]
     suites = [build_curriculum_local_eval_suite(approach_cfg, seed=seed + s * 1009, stage_index=s, n_episodes=episodes, device=device) for s in stages]
-    cat = {k: np.concatenate([su[k] for su in suites]) for k in suites[0]}
-    E = cat["initial_q"].shape[0]
-    r = approach_cfg.c.reward
+    return stages, {k: np.concatenate([su[k] for su in suites]) for k in suites[0]}
 
-    env = ArmKinematicVecEnv(approach_cfg, E, device=device, seed=seed)
+
+def _phase_env(cfg: kcfg.EnvConfig, n: int, *, device, seed: int, obs_stride: int, first_env_id: int = 0) -> ArmKinematicVecEnv:
+    """the env of one evaluation phase: n envs of ``cfg`` (env k is global env first_env_id + k) at the policy's observation row pitch"""
+    env = ArmKinematicVecEnv(cfg, n, device=device, seed=seed, first_env_id=first_env_id)
     if obs_stride != 56:
         env.set_obs_stride(obs_stride)
-    a_res, hand = run_phase(env, approach_policy, {"initial_q": cat["initial_q"], "goal_q": cat["goal_q"], "goal_pose6": cat["goal_pose6"],
-                                                   "policy_mode": "approach"}, one_launch=one_launch, what="Approach",
-                            whole_episodes=whole_episodes, entry="evaluate_workspace_expansion", ready_cfg=r,
-                            handoff_confirm_steps=handoff_confirm_steps)
-    env.close()
+    return env
+
+
+def _finisher_phase(a_res: dict[str, torch.Tensor], hand: dict[str, torch.Tensor], r, finisher_policy: Any, finisher_cfg: kcfg.EnvConfig | None,
+                    env_kw: dict[str, Any], **phase) -> tuple[torch.Tensor, torch.Tensor, dict[str, torch.Tensor] | None]:
+    """the second half of a two-phase run, from the Approach results -> (final_ready, has_hand, f_res).  Where there are a Finisher policy and
+    config and any row hands over, a Finisher env like the Approach one (``env_kw``: _phase_env's keywords) is reset to the handoff sources
+    and run under ``active=has_hand`` by run_phase (``phase``: its one_launch / whole_episodes / entry); f_res is None otherwise."""
     final_ready, has_hand, src = _handoff_sources(a_res, hand, r)
     f_res = None
     if finisher_policy is not None and finisher_cfg is not None and bool(has_hand.any()):
-        fenv = ArmKinematicVecEnv(finisher_cfg, E, device=device, seed=seed)
-        if obs_stride != 56:
-            fenv.set_obs_stride(obs_stride)
+        fenv = _phase_env(finisher_cfg, has_hand.shape[0], **env_kw)
         # rows without a handoff still need finite reset inputs; they are masked out of every result
         safe = {k: torch.where(has_hand[:, None], v, a_res[k]) for k, v in src.items()}
-        f_res, _ = run_phase(fenv, finisher_policy, _handoff_options(safe, "dock"), one_launch=one_launch, what="Finisher",
-                             whole_episodes=whole_episodes, entry="evaluate_workspace_expansion", active=has_hand)
+        f_res, _ = run_phase(fenv, finisher_policy, _handoff_options(safe, "dock"), what="Finisher", active=has_hand, **phase)
         fenv.close()
-    cols = _eval_columns(a_res, final_ready, has_hand, f_res, handoff_confirm_steps)
-    return _workspace_payload(cols, cat["goal_pose6"], approach_cfg=approach_cfg, stages=stages, episodes=episodes, seed=seed,
-                              handoff_confirm_steps=handoff_confirm_steps, gate_config=gate_config, artifact_root=artifact_root)
+    return final_ready, has_hand, f_res
+
+
+def _merge_finisher(a_res: dict[str, torch.Tensor], has_hand: torch.Tensor, f_res: dict[str, torch.Tensor] | None) -> tuple[dict[str, torch.Tensor], torch.Tensor]:
+    """(final, success) of a two-phase run: the Approach's four finals and success, replaced by the Finisher's in the rows that were handed over"""
+    final = {k: a_res[k].clone() for k in ("final_position_error", "final_orientation_error", "final_action_magnitude", "final_dq_norm")}
+    success = a_res["success"].clone()
+    if f_res is not None:
+        for k in final:
+            final[k] = torch.where(has_hand, f_res[k], final[k])
+        success = torch.where(has_hand, f_res["success"], success)
+    return final, success
 
 
 def _handoff_sources(a_res: dict[str, torch.Tensor], hand: dict[str, torch.Tensor], r) -> tuple[torch.Tensor, torch.Tensor, dict[str, torch.Tensor]]:
@@ -582,12 +600,7 @@ def _eval_columns(a_res: dict[str, torch.Tensor], final_ready: torch.Tensor, has
                   handoff_confirm_steps: int, rows: slice = slice(None)) -> dict[str, Any]:
     """the per-episode host columns the row / summary code reads, for episodes ``rows`` of the run (a replica's block of a population run):
     the Approach results (A), the finals after the Finisher where one ran (F), success, ready hit / dwell and the two regression flags"""
-    final = {k: a_res[k].clone() for k in ("final_position_error", "final_orientation_error", "final_action_magnitude", "final_dq_norm")}
-    success = a_res["success"].clone()
-    if f_res is not None:
-        for k in final:
-            final[k] = torch.where(has_hand, f_res[k], final[k])
-        success = torch.where(has_hand, f_res["success"], success)
+    final, success = _merge_finisher(a_res, has_hand, f_res)
     ready_hit = a_res["ready_hit"] | final_ready
     ready_dwell = (a_res["max_ready_streak"] >= handoff_confirm_steps) | final_ready
     pos_reg = a_res["final_position_error"] > a_res["min_position_error"] + 0.002
@@ -691,7 +704,8 @@ def evaluate_workspace_expansion_population(*, population: Any, finisher_policy:
     The suite is built once and tiled K times into one Approach handle of K x E envs; block k steps under replica k's weights as the
     population's own training handle holds them (no parameter copy, no repack), one kp1_eval_step launch per env step for all replicas.
     The Finisher phase is one run over all K x E rows with the shared Finisher policy (``finisher_policy``: an InferencePolicy, stepped in
-    one launch when kp1_eval_step covers its handle -- 64 / 128 wide, or 2x256 on the tile kernels -- and through run_episodes otherwise).
+    one launch when kp1_eval_step covers its handle -- 64 / 128 wide, or 2x256 on the tile kernels -- and through run_episodes otherwise;
+    run_phase decides, so a bound ``predict`` of one is looked through as in evaluate_workspace_expansion).
     Episodes of different replicas run in lock step until none of any replica is alive; a finished episode's bookkeeping is frozen, so the
     extra steps change nothing in its block.
 
@@ -699,38 +713,19 @@ def evaluate_workspace_expansion_population(*, population: Any, finisher_policy:
     through kp1_eval_episodes and raises ValueError when the Finisher policy's handle is not covered."""
     K = check_population_eval(population, artifact_roots)
     whole = whole_episodes_default("evaluate_workspace_expansion_population", whole_episodes)
-    n_stages = approach_cfg.n_stages
-    stages = stage_indices if stage_indices is not None else list(range(n_stages))
-    stages = [int(np.clip(s, 0, n_stages - 1)) for s in stages]
-    suites = [build_curriculum_local_eval_suite(approach_cfg, seed=seed + s * 1009, stage_index=s, n_episodes=episodes, device=device) for s in stages]
-    cat = {k: np.concatenate([su[k] for su in suites]) for k in suites[0]}
+    stages, cat = _stage_suite(approach_cfg, seed, stage_indices, episodes, device)
     E = cat["initial_q"].shape[0]
     r = approach_cfg.c.reward
-    obs_stride = int(population.obs_w)
+    env_kw = dict(device=device, seed=seed, obs_stride=int(population.obs_w))
 
-    env = ArmKinematicVecEnv(approach_cfg, K * E, device=device, seed=seed)
-    if obs_stride != 56:
-        env.set_obs_stride(obs_stride)
+    env = _phase_env(approach_cfg, K * E, **env_kw)
     tiled = {k: np.tile(cat[k], (K, 1)) for k in ("initial_q", "goal_q", "goal_pose6")}
     a_res, hand = run_episodes_fused(env, population._mlp, {**tiled, "policy_mode": "approach"}, ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps,
                                      whole_episodes=whole)
     env.close()
-    final_ready, has_hand, src = _handoff_sources(a_res, hand, r)
-    f_res = None
-    if finisher_policy is not None and finisher_cfg is not None and bool(has_hand.any()):
-        fenv = ArmKinematicVecEnv(finisher_cfg, K * E, device=device, seed=seed)
-        if obs_stride != 56:
-            fenv.set_obs_stride(obs_stride)
-        # rows without a handoff still need finite reset inputs; they are masked out of every result
-        safe = {k: torch.where(has_hand[:, None], v, a_res[k]) for k, v in src.items()}
-        fmlp = getattr(finisher_policy, "_mlp", None)
-        if _is_fused_width(fmlp) and int(getattr(fmlp, "replicas", 1)) == 1:
-            f_res, _ = run_episodes_fused(fenv, fmlp, _handoff_options(safe, "dock"), active=has_hand, whole_episodes=whole)
-        elif whole_episodes:
-            raise _uncovered_whole_episodes("Finisher")
-        else:
-            f_res, _ = run_episodes(fenv, finisher_policy, _handoff_options(safe, "dock"), active=has_hand)
-        fenv.close()
+    # the shared Finisher policy picks its runner as in evaluate_workspace_expansion(one_launch=None) (DESIGN section 29)
+    final_ready, has_hand, f_res = _finisher_phase(a_res, hand, r, finisher_policy, finisher_cfg, env_kw, one_launch=None,
+                                                   whole_episodes=whole_episodes, entry="evaluate_workspace_expansion_population")
     payloads = []
     for k in range(K):
         cols = _eval_columns(a_res, final_ready, has_hand, f_res, handoff_confirm_steps, rows=slice(k * E, (k + 1) * E))

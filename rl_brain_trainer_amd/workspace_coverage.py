@@ -505,7 +505,6 @@ def _run_pairs_columns(*, pairs, starts_by_id, targets_by_id, approach_policy, a
     import torch
 
     from . import evaluate as ev
-    from .vec_env import ArmKinematicVecEnv
 
     E = len(pairs)
     dev = torch.device("cuda", device)
@@ -526,34 +525,16 @@ def _run_pairs_columns(*, pairs, starts_by_id, targets_by_id, approach_policy, a
     ti = np.fromiter((t_row[p["target_id"]] for p in pairs), dtype=np.int64, count=E)
     opts = {"initial_q": s_q[si], "initial_dq": s_dq[si], "initial_prev_action": s_pa[si], "goal_q": t_q[ti], "goal_pose6": t_pose[ti], "policy_mode": "approach"}
     r = approach_cfg.c.reward
-    env = ArmKinematicVecEnv(approach_cfg, E, device=device, seed=seed, first_env_id=first_env_id)
-    if obs_stride != 56:
-        env.set_obs_stride(obs_stride)
-    a_res, hand = ev.run_phase(env, approach_policy, opts, one_launch=one_launch, what="Approach", whole_episodes=whole_episodes, entry="run_pairs",
-                               ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps)
+    env_kw = dict(device=device, seed=seed, obs_stride=obs_stride, first_env_id=first_env_id)
+    phase = dict(one_launch=one_launch, whole_episodes=whole_episodes, entry="run_pairs")
+    env = ev._phase_env(approach_cfg, E, **env_kw)
+    a_res, hand = ev.run_phase(env, approach_policy, opts, what="Approach", ready_cfg=r, handoff_confirm_steps=handoff_confirm_steps, **phase)
     env.close()
-    final_ready = ev.finisher_ready(a_res["final_position_error"], a_res["final_orientation_error"], a_res["final_action_magnitude"], a_res["final_dq_norm"], r)
-    has_hand = final_ready | hand["valid"]
-    src = {}
-    for k in ("state_q", "state_dq", "state_prev_action", "state_goal_q", "state_goal_pose6"):
-        src[k] = torch.where(final_ready[:, None], a_res[k], hand.get(k, torch.zeros_like(a_res[k])))
-    finals = ("final_position_error", "final_orientation_error", "final_action_magnitude", "final_dq_norm")
-    final = {k: a_res[k].clone() for k in finals}
-    success = a_res["success"].clone()
-    if finisher_policy is not None and finisher_cfg is not None and bool(has_hand.any()):
-        fenv = ArmKinematicVecEnv(finisher_cfg, E, device=device, seed=seed, first_env_id=first_env_id)
-        if obs_stride != 56:
-            fenv.set_obs_stride(obs_stride)
-        safe = {k: torch.where(has_hand[:, None], v, a_res[k]) for k, v in src.items()}
-        f_res, _ = ev.run_phase(fenv, finisher_policy, ev._handoff_options(safe, "dock"), one_launch=one_launch, what="Finisher",
-                                whole_episodes=whole_episodes, entry="run_pairs", active=has_hand)
-        fenv.close()
-        for k in final:
-            final[k] = torch.where(has_hand, f_res[k], final[k])
-        success = torch.where(has_hand, f_res["success"], success)
+    final_ready, has_hand, f_res = ev._finisher_phase(a_res, hand, r, finisher_policy, finisher_cfg, env_kw, **phase)
+    final, success = ev._merge_finisher(a_res, has_hand, f_res)
     coarse_dwell = a_res["max_ready_streak"] >= handoff_confirm_steps
     cols = [success, a_res["ready_hit"] | final_ready, coarse_dwell | final_ready, coarse_dwell,
-            *[a_res[k] for k in finals], a_res["min_position_error"], a_res["min_orientation_error"], *[final[k] for k in finals],
+            *[a_res[k] for k in final], a_res["min_position_error"], a_res["min_orientation_error"], *final.values(),
             a_res["step_count"]]
     return torch.stack([c.to(torch.float64) for c in cols], dim=1).contiguous()
 

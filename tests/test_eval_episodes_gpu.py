@@ -22,13 +22,14 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import types
 
 import numpy as np
 import pytest
 import torch
 
+import eval_forms as F
 from conftest import load_golden_config
+from eval_forms import DEV, NAMES, READY, THR
 from rl_brain_trainer_amd import evaluate as ev
 from rl_brain_trainer_amd import native
 from rl_brain_trainer_amd import ppo as P
@@ -37,12 +38,9 @@ from rl_brain_trainer_amd.mlp import MlpKernels
 from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 E, K, N_POP = 70, 3, 35
-THR = (0.30, 1.0, 2.0, 0.0)        # ready predicate: pos, ori, |action| (exercises the norm), dq clause skipped
 SUCCESS_RADIUS = 0.04
 INVALID, UNSUPPORTED = -1, -4
-NAMES = ("metrics", "counters", "flags", "state", "hand_metrics", "hand_step", "hand_success", "hand_state", "n_alive")
 
 
 def _cfg(mode: str, early_ends: bool = True):
@@ -53,20 +51,13 @@ def _cfg(mode: str, early_ends: bool = True):
     return cfg
 
 
-def _state_dict(hidden: int, seed: int) -> dict[str, torch.Tensor]:
-    pol = P.ActorCritic(hidden, DEV, seed=seed)
-    pol.views["action_net.weight"].mul_(250.0)       # SB3's action head starts at gain 0.01: means of ~0.01 would never meet the clamp
-    pol.views["action_net.bias"].copy_(torch.linspace(-0.3, 0.3, 7, device=DEV))
-    return pol.state_dict()
-
-
 @pytest.fixture(scope="module")
 def handles():
     """name -> (MlpKernels, replicas): K = 1 handles of hidden 256 / 64 / 128 and a hidden-64 population of three"""
-    pols = {"h256": P.InferencePolicy(_state_dict(256, 21), device=DEV, max_batch=128),
-            "h64": P.InferencePolicy(_state_dict(64, 11), device=DEV, max_batch=128),
-            "h128": P.InferencePolicy(_state_dict(128, 11), device=DEV, max_batch=128)}
-    rest = [P.InferencePolicy(_state_dict(64, 11 + k), device=DEV, max_batch=128) for k in (1, 2)]
+    pols = {"h256": P.InferencePolicy(F.state_dict(256, 21), device=DEV, max_batch=128),
+            "h64": P.InferencePolicy(F.state_dict(64, 11), device=DEV, max_batch=128),
+            "h128": P.InferencePolicy(F.state_dict(128, 11), device=DEV, max_batch=128)}
+    rest = [P.InferencePolicy(F.state_dict(64, 11 + k), device=DEV, max_batch=128) for k in (1, 2)]
     pop = MlpKernels(64, DEV, max_batch=64, replicas=K)
     pop.pack(torch.stack([p.policy.flat for p in (pols["h64"], *rest)]).contiguous())
     out = {k: (v._mlp, 1) for k, v in pols.items()}
@@ -78,9 +69,7 @@ def handles():
 @pytest.fixture(scope="module")
 def suite():
     """70 explicit resets: 35 episodes each of two stages of workspace_expansion_bigtrain's curriculum-local suite"""
-    cfg = _cfg("approach")
-    parts = [ev.build_curriculum_local_eval_suite(cfg, seed=700001 + 1009 * s, stage_index=s, n_episodes=E // 2) for s in (1, 4)]
-    return {k: np.concatenate([p[k] for p in parts]) for k in ("initial_q", "goal_q", "goal_pose6")}
+    return F.build_suite(_cfg("approach"), E // 2)
 
 
 def _opts(suite, mode: str, n: int, reps: int = 1) -> dict:
@@ -91,52 +80,6 @@ def _opts(suite, mode: str, n: int, reps: int = 1) -> dict:
     return {**{k: np.tile(v, (reps, 1)) for k, v in o.items()}, "policy_mode": mode}
 
 
-def _active_mask(n: int) -> torch.Tensor:
-    """partly zero wherever there is more than one row"""
-    m = np.random.default_rng(2).random(n) < 0.85
-    m[0] = True
-    if n > 1:
-        m[1] = False
-    return torch.tensor(m, device=DEV).to(torch.uint8).contiguous()
-
-
-class _Bufs:
-    """kp1_eval_buffers over n episodes, handoff buffers on"""
-
-    def __init__(self, n: int) -> None:
-        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
-        self.metrics = torch.empty((8, n), dtype=f64, device=DEV)
-        self.counters = torch.empty((4, n), dtype=i32, device=DEV)
-        self.flags = torch.empty((4, n), dtype=u8, device=DEV)
-        self.state = torch.empty((n, 34), dtype=f64, device=DEV)
-        self.hand_metrics = torch.empty((8, n), dtype=f64, device=DEV)
-        self.hand_step = torch.empty(n, dtype=i32, device=DEV)
-        self.hand_success = torch.empty(n, dtype=u8, device=DEV)
-        self.hand_state = torch.empty((n, 34), dtype=f64, device=DEV)
-        self.n_alive = torch.zeros(1, dtype=i32, device=DEV)
-        self.c = native.EvalBuffers(*[C.c_void_p(getattr(self, k).data_ptr()) for k in NAMES])
-
-    def snapshot(self) -> dict[str, torch.Tensor]:
-        return {k: getattr(self, k).clone() for k in NAMES}
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _make_env(cfg, n: int, stride: int, opts: dict, **kw) -> ArmKinematicVecEnv:
-    env = ArmKinematicVecEnv(cfg, n, seed=3, **kw)
-    if stride != 56:
-        env.set_obs_stride(stride)
-    env.use_current_stream()
-    env.reset(options=opts)
-    return env
-
-
 def _env_snapshot(env) -> dict[str, torch.Tensor]:
     """obs / reward / done / every info field, cloned; the env axis is the FIRST of obs and the LAST of everything else"""
     return {"obs": env.obs.clone(), "reward": env.reward.clone(), "done": env.done.clone(), **{"info_" + k: v.clone() for k, v in env.info().items()}}
@@ -145,11 +88,11 @@ def _env_snapshot(env) -> dict[str, torch.Tensor]:
 def _started(mlp, mode: str, stride: int, confirm: int, n: int, suite, reps: int = 1, active=None):
     """a freshly reset env of reps x n rows with kp1_eval_accumulate's step 0 made under the active mask"""
     L = native.load()
-    env = _make_env(_cfg(mode), reps * n, stride, _opts(suite, mode, n, reps))
-    b = _Bufs(reps * n)
+    env = F.make_env(_cfg(mode), reps * n, stride, _opts(suite, mode, n, reps))
+    b = ev.EpisodeBuffers(reps * n, DEV, want_hand=True)
     thr = (C.c_double * 4)(*THR)
-    active = _active_mask(reps * n) if active is None else active
-    native.check(L.kp1_eval_accumulate(env._handle, C.byref(b.c), None, None, _ptr(active), 0, thr, confirm, _stream()))
+    active = F.forced_active_mask(reps * n) if active is None else active
+    native.check(L.kp1_eval_accumulate(env._handle, C.byref(b.struct), None, None, F.ptr(active), 0, thr, confirm, F.stream()))
     return env, b, thr, active
 
 
@@ -165,7 +108,7 @@ def _reference(handles, name: str, mode: str, stride: int, confirm: int, n: int,
     mlp, reps = handles[name]
     active = None
     if active_key == "tile1_off":
-        active = _active_mask(reps * n)
+        active = F.forced_active_mask(reps * n)
         active[32:64] = 0
     env, b, thr, active = _started(mlp, mode, stride, confirm, n, suite, reps, active)
     post_reset = _env_snapshot(env)
@@ -173,19 +116,19 @@ def _reference(handles, name: str, mode: str, stride: int, confirm: int, n: int,
     limit = env.config.c.termination.max_episode_steps
     for step in range(1, limit + 2):
         alive = b.flags[0].bool().clone()                  # alive BEFORE this step
-        native.check(L.kp1_eval_step(mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(b.c), step, thr, confirm, _stream()))
+        native.check(L.kp1_eval_step(mlp._h, env._handle, F.ptr(env.obs), F.ptr(env.reward), F.ptr(env.done), C.byref(b.struct), step, thr, confirm, F.stream()))
         last["obs"][alive] = env.obs[alive]
         last["reward"][alive] = env.reward[alive]
         last["done"][alive] = env.done[alive]
         for k, v in env.info().items():
             last["info_" + k][..., alive] = v[..., alive]
-    ref = {"bufs": b.snapshot(), "last": last, "post_reset": post_reset, "active": active, "limit": limit, "rows": n, "reps": reps}
+    ref = {"bufs": F.snapshot(b), "last": last, "post_reset": post_reset, "active": active, "limit": limit, "rows": n, "reps": reps}
     env.close()
     _REFERENCES[key] = ref
     return ref
 
 
-def _assert_equal_to_reference(env, b: _Bufs, ref: dict, what) -> None:
+def _assert_equal_to_reference(env, b: ev.EpisodeBuffers, ref: dict, what) -> None:
     for k in NAMES:
         assert torch.equal(getattr(b, k), ref["bufs"][k]), (what, k)
     got = _env_snapshot(env)
@@ -208,8 +151,8 @@ def _episodes(handles, name, mode, stride, confirm, n, suite, segments, active=N
     mlp, reps = handles[name]
     env, b, thr, _ = _started(mlp, mode, stride, confirm, n, suite, reps, active)
     for first, last in segments:
-        native.check(L.kp1_eval_episodes(mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(b.c), first, last, thr, confirm,
-                                         _stream()))
+        native.check(L.kp1_eval_episodes(mlp._h, env._handle, F.ptr(env.obs), F.ptr(env.reward), F.ptr(env.done), C.byref(b.struct), first, last, thr, confirm,
+                                         F.stream()))
     return env, b
 
 
@@ -277,8 +220,8 @@ def test_segments_equal_the_single_call(handles, suite, name, mode):
     _assert_equal_to_reference(env, b, ref, (name, mode, "segments"))
     mlp = handles[name][0]
     thr = (C.c_double * 4)(*THR)
-    native.check(native.load().kp1_eval_episodes(mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(b.c), limit + 2, limit + 9,
-                                                 thr, 2, _stream()))
+    native.check(native.load().kp1_eval_episodes(mlp._h, env._handle, F.ptr(env.obs), F.ptr(env.reward), F.ptr(env.done), C.byref(b.struct), limit + 2, limit + 9,
+                                                 thr, 2, F.stream()))
     assert int(b.n_alive) == 0
     _assert_equal_to_reference(env, b, ref, (name, mode, "after the end"))
     env.close()
@@ -321,17 +264,13 @@ def _count_library_calls(monkeypatch):
     return calls
 
 
-READY = types.SimpleNamespace(dock_coarse_ready_pos_threshold_m=THR[0], dock_coarse_ready_ori_threshold_rad=THR[1],
-                              dock_coarse_ready_action_threshold=THR[2], dock_coarse_ready_dq_threshold=THR[3])
-
-
 def _run_fused(handles, suite, name, mode, confirm, whole, max_steps=None):
     mlp, reps = handles[name]
     n = N_POP if reps > 1 else E
     env = ArmKinematicVecEnv(_cfg(mode), reps * n, seed=3)
     env.set_obs_stride(64)
     out = ev.run_episodes_fused(env, mlp, _opts(suite, mode, n, reps), ready_cfg=READY, handoff_confirm_steps=confirm,
-                                active=_active_mask(reps * n).bool(), max_steps=max_steps, whole_episodes=whole)
+                                active=F.forced_active_mask(reps * n).bool(), max_steps=max_steps, whole_episodes=whole)
     env.close()
     return out
 
@@ -423,7 +362,7 @@ def test_population_evaluator_whole_episodes_equals_per_step(monkeypatch):
     penv = ArmKinematicPopulationVecEnv(env_cfg, seeds, 16)
     pop = ApproachPopulationPPO(seeds, P.PPOConfig(n_steps=32, batch_size=128, n_epochs=2, hidden=64, learning_rate=3e-3), penv)
     pop.learn(pop.n_envs * pop.cfg.n_steps)
-    fin = P.InferencePolicy(_state_dict(64, 5), device=DEV)
+    fin = P.InferencePolicy(F.state_dict(64, 5), device=DEV)
     kw = dict(population=pop, finisher_policy=fin, approach_cfg=env_cfg, finisher_cfg=_cfg("dock", False), episodes=4, seed=700001, stage_indices=[0, 3],
               handoff_confirm_steps=0, gate_config={"score_stage_index": 3})
     calls = _count_library_calls(monkeypatch)
@@ -451,14 +390,6 @@ def test_evaluate_dock_whole_episodes_equals_per_step():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. training handle
-def _trained_ppo():
-    env = ArmKinematicVecEnv(_cfg("approach", False), 256, seed=806)
-    env.set_curriculum_stage(3)
-    ppo = P.PPO(env, P.PPOConfig(n_steps=8, batch_size=1024, n_epochs=2, hidden=256, learning_rate=3e-3, seed=5), use_graphs=True)
-    ppo.learn(256 * 8)
-    return ppo, env
-
-
 _TRAIN_EVAL_KW = dict(finisher_policy=None, finisher_cfg=None, episodes=4, seed=700001, stage_indices=[0, 3], handoff_confirm_steps=2, whole_episodes=True)
 
 
@@ -467,7 +398,7 @@ def test_whole_episode_evaluation_on_the_training_handle():
     [iteration, iteration], and the evaluation equals the one through a fresh InferencePolicy of the same weights"""
     out = []
     for evaluate in (True, False):
-        ppo, env = _trained_ppo()
+        ppo, env = F.trained_ppo(_cfg("approach", False))
         if evaluate:
             assert ev.policy_mlp(ppo.predict) is ppo._mlp
             got = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, approach_cfg=_cfg("approach", False), obs_stride=ppo.obs_w, **_TRAIN_EVAL_KW)
@@ -485,15 +416,14 @@ def test_whole_episode_evaluation_on_the_training_handle():
 def _refused(mlp_h, env, status: int, text: str, first: int = 1, last: int = 4, mutate=None) -> None:
     """kp1_eval_episodes refuses with `status` and `text` in kp1_last_error and launches nothing: no buffer, observation or env field changes"""
     L = native.load()
-    b = _Bufs(env.n_envs)
+    b = ev.EpisodeBuffers(env.n_envs, DEV, want_hand=True)
     for k in NAMES:
         getattr(b, k).fill_(7)
-    bufs = native.EvalBuffers(*[C.c_void_p(getattr(b, k).data_ptr()) for k in NAMES])
-    args = [mlp_h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(bufs)]
+    args = [mlp_h, env._handle, F.ptr(env.obs), F.ptr(env.reward), F.ptr(env.done), C.byref(b.struct)]
     if mutate is not None:
-        mutate(args, bufs)
+        mutate(args, b.struct)
     before = _env_snapshot(env)
-    rc = L.kp1_eval_episodes(*args, first, last, None, 0, _stream())
+    rc = L.kp1_eval_episodes(*args, first, last, None, 0, F.stream())
     assert rc == status, (rc, L.kp1_last_error())
     assert text in L.kp1_last_error().decode(), L.kp1_last_error()
     torch.cuda.synchronize()
@@ -506,7 +436,7 @@ def _refused(mlp_h, env, status: int, text: str, first: int = 1, last: int = 4, 
 def test_refusals(handles, suite):
     opts = _opts(suite, "approach", 8)
     cfg = _cfg("approach")
-    env = _make_env(cfg, 8, 56, opts)
+    env = F.make_env(cfg, 8, 56, opts)
     h256, h64, pop = handles["h256"][0], handles["h64"][0], handles["pop64"][0]
     for mlp in (h256, h64):
         # the three of kp1_eval_episodes
@@ -531,12 +461,12 @@ def test_refusals(handles, suite):
     _refused(wide._h, env, UNSUPPORTED, "56-float observation")
     wide.close()
     stage = torch.zeros(1, dtype=torch.int32, device=DEV)
-    native.check(native.load().kp1_bind_stage_ptr(env._handle, _ptr(stage)))
+    native.check(native.load().kp1_bind_stage_ptr(env._handle, F.ptr(stage)))
     _refused(h256._h, env, UNSUPPORTED, "bound to a curriculum tracker")
     env.close()
-    env64 = _make_env(cfg, 8, 56, opts, real="f64")
+    env64 = F.make_env(cfg, 8, 56, opts, real="f64")
     _refused(h256._h, env64, UNSUPPORTED, "fp32 handle")
     env64.close()
-    comps = _make_env(cfg, 8, 56, opts, reward_components=True)
+    comps = F.make_env(cfg, 8, 56, opts, reward_components=True)
     _refused(h64._h, comps, UNSUPPORTED, "reward components")
     comps.close()

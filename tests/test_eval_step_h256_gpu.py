@@ -9,13 +9,14 @@ from __future__ import annotations
 
 import ctypes as C
 import json
-import types
 
 import numpy as np
 import pytest
 import torch
 
+import eval_forms as F
 from conftest import load_golden_config
+from eval_forms import DEV, NORM_RTOL, THR
 from rl_brain_trainer_amd import evaluate as ev
 from rl_brain_trainer_amd import native
 from rl_brain_trainer_amd import ppo as P
@@ -24,27 +25,14 @@ from rl_brain_trainer_amd.mlp import MlpKernels
 from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 E = 70
-THR = (0.30, 1.0, 2.0, 0.0)        # ready predicate of the step tests: pos, ori, |action| (exercises the norm), dq clause skipped
-# Action-norm tensors, one-launch against the launch sequence: two orders of a 7-term fp64 sum plus a square root differ by a few ulp per
-# step, summed over at most ~200 steps: about 2e-14 relative; 1e-13 is the bound
-NORM_RTOL = 1e-13
-NORM_KEYS = ("final_action_magnitude", "sum_action", "mean_action_magnitude")
 UNSUPPORTED = -4          # KP1_ERR_UNSUPPORTED
-
-
-def _state_dict(seed: int, obs_dim: int = 56, scale: float = 250.0) -> dict[str, torch.Tensor]:
-    pol = P.ActorCritic(256, DEV, seed=seed, obs_dim=obs_dim)
-    pol.views["action_net.weight"].mul_(scale)       # SB3's action head starts at gain 0.01: means of ~0.01 would never meet the clamp
-    pol.views["action_net.bias"].copy_(torch.linspace(-0.3, 0.3, 7, device=DEV))
-    return pol.state_dict()
 
 
 @pytest.fixture(scope="module")
 def policies():
     """three differently seeded 2x256 InferencePolicy; their MlpKernels are the K = 1 handles of the one-launch runs"""
-    return [P.InferencePolicy(_state_dict(21 + k), device=DEV, max_batch=128) for k in range(3)]
+    return [P.InferencePolicy(F.state_dict(256, 21 + k), device=DEV, max_batch=128) for k in range(3)]
 
 
 def _cfg(mode: str):
@@ -54,86 +42,34 @@ def _cfg(mode: str):
 @pytest.fixture(scope="module")
 def suite():
     """70 explicit resets: 35 episodes each of two stages of workspace_expansion_bigtrain's curriculum-local suite"""
-    cfg = _cfg("approach")
-    parts = [ev.build_curriculum_local_eval_suite(cfg, seed=700001 + 1009 * s, stage_index=s, n_episodes=E // 2) for s in (1, 4)]
-    return {k: np.concatenate([p[k] for p in parts]) for k in ("initial_q", "goal_q", "goal_pose6")}
+    return F.build_suite(_cfg("approach"), E // 2)
 
 
 def _opts(suite, mode: str, n: int = E) -> dict:
     return {**{k: v[:n] for k, v in suite.items()}, "policy_mode": mode}
 
 
-class _Bufs:
-    """kp1_eval_buffers over n episodes, handoff buffers on"""
-    NAMES = ("metrics", "counters", "flags", "state", "hand_metrics", "hand_step", "hand_success", "hand_state", "n_alive")
-
-    def __init__(self, n: int) -> None:
-        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
-        self.metrics = torch.empty((8, n), dtype=f64, device=DEV)
-        self.counters = torch.empty((4, n), dtype=i32, device=DEV)
-        self.flags = torch.empty((4, n), dtype=u8, device=DEV)
-        self.state = torch.empty((n, 34), dtype=f64, device=DEV)
-        self.hand_metrics = torch.empty((8, n), dtype=f64, device=DEV)
-        self.hand_step = torch.empty(n, dtype=i32, device=DEV)
-        self.hand_success = torch.empty(n, dtype=u8, device=DEV)
-        self.hand_state = torch.empty((n, 34), dtype=f64, device=DEV)
-        self.n_alive = torch.zeros(1, dtype=i32, device=DEV)
-        self.c = native.EvalBuffers(*[C.c_void_p(getattr(self, k).data_ptr()) for k in self.NAMES])
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _make_env(mode: str, n: int, stride: int, opts: dict, **kw) -> ArmKinematicVecEnv:
-    env = ArmKinematicVecEnv(_cfg(mode), n, seed=3, **kw)
-    if stride != 56:
-        env.set_obs_stride(stride)
-    env.use_current_stream()
-    env.reset(options=opts)
-    return env
-
-
-def _norm_in_index_order(action: torch.Tensor) -> torch.Tensor:
-    a = action.double()
-    s = a[:, 0] * a[:, 0]
-    for k in range(1, 7):
-        s = s + a[:, k] * a[:, k]
-    return s.sqrt().contiguous()
-
-
-def _active_mask(n: int) -> torch.Tensor:
-    """partly zero wherever there is more than one row"""
-    m = np.random.default_rng(2).random(n) < 0.85
-    m[0] = True
-    if n > 1:
-        m[1] = False
-    return torch.tensor(m, device=DEV).to(torch.uint8).contiguous()
-
-
 # ---------------------------------------------------------------------------------------------------------------- 1. step parity
 def _step_parity(pol, suite, mode: str, stride: int, confirm: int, n: int) -> None:
     L = native.load()
     opts = _opts(suite, mode, n)
-    active = _active_mask(n)
-    env, ref_env = _make_env(mode, n, stride, opts), _make_env(mode, n, stride, opts)
-    b, rb = _Bufs(n), _Bufs(n)
+    active = F.forced_active_mask(n)
+    env, ref_env = F.make_env(_cfg(mode), n, stride, opts), F.make_env(_cfg(mode), n, stride, opts)
+    b, rb = ev.EpisodeBuffers(n, DEV, want_hand=True), ev.EpisodeBuffers(n, DEV, want_hand=True)
     thr = (C.c_double * 4)(*THR)
     for e_, b_ in ((env, b), (ref_env, rb)):
-        native.check(L.kp1_eval_accumulate(e_._handle, C.byref(b_.c), None, None, _ptr(active), 0, thr, confirm, _stream()))
+        native.check(L.kp1_eval_accumulate(e_._handle, C.byref(b_.struct), None, None, F.ptr(active), 0, thr, confirm, F.stream()))
     at_clamp = inside = 0
     for step in range(1, env.config.c.termination.max_episode_steps + 2):      # to the episode limit + 1
-        native.check(L.kp1_eval_step(pol._mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(b.c), step, thr, confirm, _stream()))
+        native.check(L.kp1_eval_step(pol._mlp._h, env._handle, F.ptr(env.obs), F.ptr(env.reward), F.ptr(env.done), C.byref(b.struct), step, thr, confirm,
+                                     F.stream()))
         action = pol.predict(ref_env.obs)
         at_clamp += int((action.abs() == 1.0).sum())
         inside += int((action.abs() < 1.0).sum())
-        an = _norm_in_index_order(action)
+        an = F.norm_in_index_order(action)
         ref_env.step(action, auto_reset=False)
-        native.check(L.kp1_eval_accumulate(ref_env._handle, C.byref(rb.c), _ptr(an), _ptr(ref_env.done), None, step, thr, confirm, _stream()))
+        native.check(L.kp1_eval_accumulate(ref_env._handle, C.byref(rb.struct), F.ptr(an), F.ptr(ref_env.done), None, step, thr, confirm,
+                                           F.stream()))
         assert torch.equal(env.obs, ref_env.obs), ("obs", step)
         assert torch.equal(env.done, ref_env.done), ("done", step)
         assert torch.equal(env.reward, ref_env.reward), ("reward", step)
@@ -141,7 +77,7 @@ def _step_parity(pol, suite, mode: str, stride: int, confirm: int, n: int) -> No
         for k in ri:
             assert torch.equal(fi[k], ri[k]), (k, step)
         assert torch.equal(b.n_alive, rb.n_alive), ("n_alive", step)
-    for name in _Bufs.NAMES:
+    for name in F.NAMES:
         assert torch.equal(getattr(b, name), getattr(rb, name)), name
     if n == E:
         assert at_clamp > 0 and inside > 0                                  # the clamp was met, and not everywhere
@@ -170,24 +106,11 @@ def test_eval_step_h256_row_counts(policies, suite, n):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. runner and evaluators
-def _assert_results_match(res, ref, what: str) -> None:
-    assert set(res) == set(ref), what
-    for k in ref:
-        assert res[k].dtype == ref[k].dtype and res[k].shape == ref[k].shape, (what, k)
-        if k in NORM_KEYS:
-            rel = ((res[k] - ref[k]).abs() / ref[k].abs().clamp_min(1e-300)).max().item() if ref[k].numel() else 0.0
-            print(f"{what} {k}: max relative difference {rel:.3e}, bit-equal {torch.equal(res[k], ref[k])}")
-            assert torch.allclose(res[k], ref[k], rtol=NORM_RTOL, atol=0.0), (what, k, rel)
-        else:
-            assert torch.equal(res[k], ref[k]), (what, k)
-
-
 @pytest.mark.parametrize("mode,confirm", [("approach", 2), ("approach", None), ("dock", 2), ("dock", None)])
 def test_run_episodes_fused_h256_equals_run_episodes(policies, suite, mode, confirm):
     pol = policies[1]
-    ready = types.SimpleNamespace(dock_coarse_ready_pos_threshold_m=THR[0], dock_coarse_ready_ori_threshold_rad=THR[1],
-                                  dock_coarse_ready_action_threshold=THR[2], dock_coarse_ready_dq_threshold=THR[3])
-    active = _active_mask(E).bool()
+    ready = F.READY
+    active = F.forced_active_mask(E).bool()
     assert ev._is_fused_width(pol._mlp) and ev.policy_mlp(pol.predict) is pol._mlp and ev.policy_mlp(pol) is pol._mlp
     out = []
     for fused in (True, False):
@@ -199,30 +122,11 @@ def test_run_episodes_fused_h256_equals_run_episodes(policies, suite, mode, conf
             out.append(ev.run_episodes(env, pol.predict, _opts(suite, mode), ready_cfg=ready, handoff_confirm_steps=confirm, active=active))
         env.close()
     (res, hand), (ref, ref_hand) = out
-    _assert_results_match(res, ref, "final")
+    F.assert_results_match(res, ref, "final")
     assert (hand is None) == (ref_hand is None) == (confirm is None)
     if hand is not None:
-        _assert_results_match(hand, ref_hand, "handoff")
+        F.assert_results_match(hand, ref_hand, "handoff")
     assert int(ref["step_count"].max()) >= 2
-
-
-ACTION_FLOATS = ("final_action_magnitude", "mean_final_action_magnitude")
-
-
-def _assert_payload_match(a, b, path="") -> None:
-    """payloads equal; the action-magnitude floats to NORM_RTOL"""
-    if isinstance(b, dict):
-        assert isinstance(a, dict) and a.keys() == b.keys(), path
-        for k in b:
-            _assert_payload_match(a[k], b[k], f"{path}/{k}")
-    elif isinstance(b, list):
-        assert isinstance(a, list) and len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            _assert_payload_match(x, y, f"{path}[{i}]")
-    elif isinstance(b, float) and path.rsplit("/", 1)[-1] in ACTION_FLOATS:
-        assert abs(a - b) <= NORM_RTOL * abs(b), (path, a, b)
-    else:
-        assert a == b and type(a) is type(b), (path, a, b)
 
 
 def _count_calls(monkeypatch):
@@ -254,7 +158,7 @@ def test_evaluate_workspace_expansion_one_launch_equals_multi_launch(tmp_path, m
     assert calls == {"fused": 2, "launches": 0}
     ref = ev.evaluate_workspace_expansion(artifact_root=tmp_path / "multi", one_launch=False, **kw)
     assert calls == {"fused": 2, "launches": 2}
-    _assert_payload_match(got, ref)
+    F.assert_payload_match(got, ref)
     assert len(got["target_rows"]) == 8
     for root, payload in ((tmp_path / "one", got), (tmp_path / "multi", ref)):
         assert json.loads((root / "workspace_eval_summary.json").read_text()) == json.loads(json.dumps(payload))
@@ -287,14 +191,6 @@ def test_run_pairs_columns_one_launch_equals_multi_launch(monkeypatch, policies)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. training handle
-def _trained_ppo():
-    env = ArmKinematicVecEnv(_cfg("approach"), 256, seed=806)
-    env.set_curriculum_stage(3)
-    ppo = P.PPO(env, P.PPOConfig(n_steps=8, batch_size=1024, n_epochs=2, hidden=256, learning_rate=3e-3, seed=5), use_graphs=True)
-    ppo.learn(256 * 8)
-    return ppo, env
-
-
 _TRAIN_EVAL_KW = dict(finisher_policy=None, finisher_cfg=None, episodes=4, seed=700001, stage_indices=[0, 3], handoff_confirm_steps=2)
 
 
@@ -303,7 +199,7 @@ def test_training_handle_evaluates_like_a_fresh_inference_policy(monkeypatch):
     fresh InferencePolicy built from the state dict (same weights packed anew): every float, the action magnitudes included -- both run the
     same kernel"""
     calls = _count_calls(monkeypatch)
-    ppo, env = _trained_ppo()
+    ppo, env = F.trained_ppo(_cfg("approach"))
     assert ev.policy_mlp(ppo.predict) is ppo._mlp and ev._is_fused_width(ppo._mlp)
     got = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, approach_cfg=_cfg("approach"), obs_stride=ppo.obs_w, **_TRAIN_EVAL_KW)
     fresh = P.InferencePolicy({k: v.clone() for k, v in ppo.policy.state_dict().items()}, device=DEV)
@@ -311,7 +207,7 @@ def test_training_handle_evaluates_like_a_fresh_inference_policy(monkeypatch):
     assert calls == {"fused": 2, "launches": 0}
     assert got == ref
     multi = ev.evaluate_workspace_expansion(approach_policy=ppo.predict, approach_cfg=_cfg("approach"), obs_stride=ppo.obs_w, one_launch=False, **_TRAIN_EVAL_KW)
-    _assert_payload_match(got, multi)
+    F.assert_payload_match(got, multi)
     env.close()
 
 
@@ -320,7 +216,7 @@ def test_evaluation_on_the_training_handle_leaves_training_untouched():
     [iteration, iteration]: the step reads the training handle's packed weights and writes nothing of the handle's"""
     out = []
     for evaluate in (True, False):
-        ppo, env = _trained_ppo()
+        ppo, env = F.trained_ppo(_cfg("approach"))
         if evaluate:
             ev.evaluate_workspace_expansion(approach_policy=ppo.predict, approach_cfg=_cfg("approach"), obs_stride=ppo.obs_w, **_TRAIN_EVAL_KW)
         ppo.learn(256 * 8)
@@ -337,23 +233,23 @@ def test_evaluation_on_the_training_handle_leaves_training_untouched():
 def _refused(mlp: MlpKernels, env: ArmKinematicVecEnv, status: int, text: str) -> None:
     """kp1_eval_step refuses with `status` and `text` in kp1_last_error, and launches nothing: no buffer, observation or env field changes"""
     L = native.load()
-    b = _Bufs(env.n_envs)
-    for name in _Bufs.NAMES:
+    b = ev.EpisodeBuffers(env.n_envs, DEV, want_hand=True)
+    for name in F.NAMES:
         getattr(b, name).fill_(7)
     before = (env.obs.clone(), {k: v.clone() for k, v in env.info().items()})
     L.kp1_last_error.restype = C.c_char_p
-    rc = L.kp1_eval_step(mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(b.c), 1, None, 0, _stream())
+    rc = L.kp1_eval_step(mlp._h, env._handle, F.ptr(env.obs), F.ptr(env.reward), F.ptr(env.done), C.byref(b.struct), 1, None, 0, F.stream())
     assert rc == status, (rc, L.kp1_last_error())
     assert text in L.kp1_last_error().decode(), L.kp1_last_error()
     torch.cuda.synchronize()
-    for name in _Bufs.NAMES:
+    for name in F.NAMES:
         assert bool((getattr(b, name) == 7).all()), name
     assert torch.equal(env.obs, before[0]) and all(torch.equal(v, before[1][k]) for k, v in env.info().items())
 
 
 def test_refusals(policies, suite):
     opts = _opts(suite, "approach", 8)
-    env = _make_env("approach", 8, 56, opts)
+    env = F.make_env(_cfg("approach"), 8, 56, opts)
     off = MlpKernels(256, DEV, max_batch=64)
     off.pack(policies[0].policy.flat)
     assert ev._is_fused_width(off)
@@ -366,10 +262,10 @@ def test_refusals(policies, suite):
     _refused(wide, env, UNSUPPORTED, "56-float observation")
     wide.close()
     env.close()
-    env64 = _make_env("approach", 8, 56, opts, real="f64")
+    env64 = F.make_env(_cfg("approach"), 8, 56, opts, real="f64")
     _refused(policies[0]._mlp, env64, UNSUPPORTED, "fp32 handle")
     env64.close()
-    comps = _make_env("approach", 8, 56, opts, reward_components=True)
+    comps = F.make_env(_cfg("approach"), 8, 56, opts, reward_components=True)
     _refused(policies[0]._mlp, comps, UNSUPPORTED, "reward components")
     comps.close()
 

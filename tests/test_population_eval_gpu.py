@@ -7,13 +7,14 @@ from __future__ import annotations
 
 import ctypes as C
 import json
-import types
 
 import numpy as np
 import pytest
 import torch
 
+import eval_forms as F
 from conftest import load_golden_config
+from eval_forms import DEV, THR
 from rl_brain_trainer_amd import config as kcfg
 from rl_brain_trainer_amd import evaluate as ev
 from rl_brain_trainer_amd import native
@@ -22,34 +23,19 @@ from rl_brain_trainer_amd.mlp import MlpKernels
 from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 E, K = 70, 3
-THR = (0.30, 1.0, 2.0, 0.0)        # ready predicate of the step tests: pos, ori, |action| (exercises the norm), dq clause skipped
-# Action-norm tensors, fused against the shipped evaluator: two orders of a 7-term fp64 sum plus a square root differ by a few ulp per
-# step, summed over at most ~200 steps: about 2e-14 relative; 1e-13 is the bound
-NORM_RTOL = 1e-13
-NORM_KEYS = ("final_action_magnitude", "sum_action", "mean_action_magnitude")
-
-
-def _state_dict(hidden: int, seed: int) -> dict[str, torch.Tensor]:
-    pol = P.ActorCritic(hidden, DEV, seed=seed)
-    pol.views["action_net.weight"].mul_(250.0)       # SB3's action head starts at gain 0.01: means of ~0.01 would never meet the clamp
-    pol.views["action_net.bias"].copy_(torch.linspace(-0.3, 0.3, 7, device=DEV))
-    return pol.state_dict()
 
 
 @pytest.fixture(scope="module")
 def policies():
     """hidden -> the three K = 1 InferencePolicy of the three seeds (their MlpKernels are the K = 1 handles of the fused runs)"""
-    return {h: [P.InferencePolicy(_state_dict(h, 11 + k), device=DEV, max_batch=128) for k in range(K)] for h in (64, 128)}
+    return {h: [P.InferencePolicy(F.state_dict(h, 11 + k), device=DEV, max_batch=128) for k in range(K)] for h in (64, 128)}
 
 
 @pytest.fixture(scope="module")
 def suite():
     """70 explicit resets: 35 episodes each of two stages of approach_default's curriculum-local suite"""
-    cfg = load_golden_config("approach_default")
-    parts = [ev.build_curriculum_local_eval_suite(cfg, seed=700001 + 1009 * s, stage_index=s, n_episodes=E // 2) for s in (1, 4)]
-    return {k: np.concatenate([p[k] for p in parts]) for k in ("initial_q", "goal_q", "goal_pose6")}
+    return F.build_suite(load_golden_config("approach_default"), E // 2)
 
 
 def _opts(suite, mode: str, reps: int = 1) -> dict:
@@ -60,61 +46,18 @@ def _cfg(mode: str):
     return load_golden_config("approach_default" if mode == "approach" else "dock_default")
 
 
-class _Bufs:
-    """kp1_eval_buffers over n episodes, handoff buffers on"""
-    NAMES = ("metrics", "counters", "flags", "state", "hand_metrics", "hand_step", "hand_success", "hand_state", "n_alive")
-
-    def __init__(self, n: int) -> None:
-        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
-        self.metrics = torch.empty((8, n), dtype=f64, device=DEV)
-        self.counters = torch.empty((4, n), dtype=i32, device=DEV)
-        self.flags = torch.empty((4, n), dtype=u8, device=DEV)
-        self.state = torch.empty((n, 34), dtype=f64, device=DEV)
-        self.hand_metrics = torch.empty((8, n), dtype=f64, device=DEV)
-        self.hand_step = torch.empty(n, dtype=i32, device=DEV)
-        self.hand_success = torch.empty(n, dtype=u8, device=DEV)
-        self.hand_state = torch.empty((n, 34), dtype=f64, device=DEV)
-        self.n_alive = torch.zeros(1, dtype=i32, device=DEV)
-        self.c = native.EvalBuffers(*[C.c_void_p(getattr(self, k).data_ptr()) for k in self.NAMES])
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _make_env(mode: str, n: int, stride: int, opts: dict) -> ArmKinematicVecEnv:
-    env = ArmKinematicVecEnv(_cfg(mode), n, seed=3)
-    if stride != 56:
-        env.set_obs_stride(stride)
-    env.use_current_stream()
-    env.reset(options=opts)
-    return env
-
-
-def _fused_run(mlp: MlpKernels, mode: str, stride: int, opts: dict, n: int, confirm: int, active: torch.Tensor, on_step=None) -> tuple[_Bufs, ArmKinematicVecEnv]:
+def _fused_run(mlp: MlpKernels, mode: str, stride: int, opts: dict, n: int, confirm: int, active: torch.Tensor, on_step=None) -> tuple[ev.EpisodeBuffers, ArmKinematicVecEnv]:
     """episodes to the step limit through kp1_eval_step on the env's own buffers"""
     L = native.load()
-    env = _make_env(mode, n, stride, opts)
-    b = _Bufs(n)
+    env = F.make_env(_cfg(mode), n, stride, opts)
+    b = ev.EpisodeBuffers(n, DEV, want_hand=True)
     thr = (C.c_double * 4)(*THR)
-    native.check(L.kp1_eval_accumulate(env._handle, C.byref(b.c), None, None, _ptr(active), 0, thr, confirm, _stream()))
+    native.check(L.kp1_eval_accumulate(env._handle, C.byref(b.struct), None, None, F.ptr(active), 0, thr, confirm, F.stream()))
     for step in range(1, env.config.c.termination.max_episode_steps + 2):
-        native.check(L.kp1_eval_step(mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(b.c), step, thr, confirm, _stream()))
+        native.check(L.kp1_eval_step(mlp._h, env._handle, F.ptr(env.obs), F.ptr(env.reward), F.ptr(env.done), C.byref(b.struct), step, thr, confirm, F.stream()))
         if on_step is not None:
             on_step(step, env, b)
     return b, env
-
-
-def _norm_in_index_order(action: torch.Tensor) -> torch.Tensor:
-    a = action.double()
-    s = a[:, 0] * a[:, 0]
-    for k in range(1, 7):
-        s = s + a[:, k] * a[:, k]
-    return s.sqrt().contiguous()
 
 
 def _active_mask(n: int) -> torch.Tensor:
@@ -136,19 +79,20 @@ def test_eval_step_equals_the_launch_sequence(policies, suite, hidden, mode, str
     pol = policies[hidden][0]
     opts = _opts(suite, mode)
     active = _active_mask(E)
-    ref_env = _make_env(mode, E, stride, opts)
-    rb = _Bufs(E)
+    ref_env = F.make_env(_cfg(mode), E, stride, opts)
+    rb = ev.EpisodeBuffers(E, DEV, want_hand=True)
     thr = (C.c_double * 4)(*THR)
-    native.check(L.kp1_eval_accumulate(ref_env._handle, C.byref(rb.c), None, None, _ptr(active), 0, thr, confirm, _stream()))
+    native.check(L.kp1_eval_accumulate(ref_env._handle, C.byref(rb.struct), None, None, F.ptr(active), 0, thr, confirm, F.stream()))
     clamped = {"lo": 0, "in": 0}
 
     def on_step(step, env, b):
         action = pol.predict(ref_env.obs)
         clamped["lo"] += int((action.abs() == 1.0).sum())
         clamped["in"] += int((action.abs() < 1.0).sum())
-        an = _norm_in_index_order(action)
+        an = F.norm_in_index_order(action)
         ref_env.step(action, auto_reset=False)
-        native.check(L.kp1_eval_accumulate(ref_env._handle, C.byref(rb.c), _ptr(an), _ptr(ref_env.done), None, step, thr, confirm, _stream()))
+        native.check(L.kp1_eval_accumulate(ref_env._handle, C.byref(rb.struct), F.ptr(an), F.ptr(ref_env.done), None, step, thr, confirm,
+                                           F.stream()))
         assert torch.equal(env.obs, ref_env.obs), ("obs", step)
         assert torch.equal(env.done, ref_env.done), ("done", step)
         fi, ri = env.info(), ref_env.info()
@@ -157,7 +101,7 @@ def test_eval_step_equals_the_launch_sequence(policies, suite, hidden, mode, str
         assert torch.equal(b.n_alive, rb.n_alive), ("n_alive", step)
 
     b, env = _fused_run(pol._mlp, mode, stride, opts, E, confirm, active, on_step)
-    for name in _Bufs.NAMES:
+    for name in F.NAMES:
         assert torch.equal(getattr(b, name), getattr(rb, name)), name
     assert clamped["lo"] > 0 and clamped["in"] > 0                      # the clamp was met, and not everywhere
     assert int(rb.n_alive) == 0 and int(rb.counters[0].max()) >= 2       # episodes ran, and to their end
@@ -197,24 +141,11 @@ def test_population_block_equals_single_fused_run(policies, suite, hidden):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. against the shipped evaluator
-def _assert_results_match(res, ref, what: str) -> None:
-    assert set(res) == set(ref), what
-    for k in ref:
-        assert res[k].dtype == ref[k].dtype and res[k].shape == ref[k].shape, (what, k)
-        if k in NORM_KEYS:
-            rel = ((res[k] - ref[k]).abs() / ref[k].abs().clamp_min(1e-300)).max().item() if ref[k].numel() else 0.0
-            print(f"{what} {k}: max relative difference {rel:.3e}, bit-equal {torch.equal(res[k], ref[k])}")
-            assert torch.allclose(res[k], ref[k], rtol=NORM_RTOL, atol=0.0), (what, k, rel)
-        else:
-            assert torch.equal(res[k], ref[k]), (what, k)
-
-
 @pytest.mark.parametrize("hidden,mode,confirm", [(64, "approach", 2), (128, "approach", 0), (128, "dock", None)])
 def test_run_episodes_fused_equals_run_episodes(policies, suite, hidden, mode, confirm):
     pol = policies[hidden][1]
     cfg = _cfg(mode)
-    ready = types.SimpleNamespace(dock_coarse_ready_pos_threshold_m=THR[0], dock_coarse_ready_ori_threshold_rad=THR[1],
-                                  dock_coarse_ready_action_threshold=THR[2], dock_coarse_ready_dq_threshold=THR[3])
+    ready = F.READY
     active = _active_mask(E).bool()
     out = []
     for fused in (True, False):
@@ -226,33 +157,14 @@ def test_run_episodes_fused_equals_run_episodes(policies, suite, hidden, mode, c
             out.append(ev.run_episodes(env, pol.predict, _opts(suite, mode), ready_cfg=ready, handoff_confirm_steps=confirm, active=active))
         env.close()
     (res, hand), (ref, ref_hand) = out
-    _assert_results_match(res, ref, "final")
+    F.assert_results_match(res, ref, "final")
     assert (hand is None) == (ref_hand is None) == (confirm is None)
     if hand is not None:
-        _assert_results_match(hand, ref_hand, "handoff")
+        F.assert_results_match(hand, ref_hand, "handoff")
     assert int(ref["step_count"].max()) >= 2
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. / 5. evaluator on a population
-ACTION_FLOATS = ("final_action_magnitude", "mean_final_action_magnitude")
-
-
-def _assert_payload_match(a, b, path="") -> None:
-    """payloads equal; the action-magnitude floats to NORM_RTOL"""
-    if isinstance(b, dict):
-        assert isinstance(a, dict) and a.keys() == b.keys(), path
-        for k in b:
-            _assert_payload_match(a[k], b[k], f"{path}/{k}")
-    elif isinstance(b, list):
-        assert isinstance(a, list) and len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            _assert_payload_match(x, y, f"{path}[{i}]")
-    elif isinstance(b, float) and path.rsplit("/", 1)[-1] in ACTION_FLOATS:
-        assert abs(a - b) <= NORM_RTOL * abs(b), (path, a, b)
-    else:
-        assert a == b and type(a) is type(b), (path, a, b)
-
-
 def _bigtrain_cfg():
     return kcfg.to_env_config(kcfg.load_workspace_expansion_config(kcfg.builtin_config_dir() / "workspace_expansion_bigtrain.yaml"))
 
@@ -293,7 +205,7 @@ def test_population_evaluator_equals_per_replica_evaluations(tmp_path, finisher)
     for k in range(3):
         ref = ev.evaluate_workspace_expansion(approach_policy=pop.replica(k).predict, finisher_policy=fin, approach_cfg=env_cfg, finisher_cfg=fcfg,
                                               artifact_root=tmp_path / f"ref{k}", obs_stride=pop.obs_w, **EVAL_KW)
-        _assert_payload_match(got[k], ref)
+        F.assert_payload_match(got[k], ref)
         assert json.loads((roots[k] / "workspace_eval_summary.json").read_text()) == json.loads(json.dumps(got[k]))
         assert json.loads((roots[k] / "stage_metrics.json").read_text()) == json.loads(json.dumps(got[k]["stage_metrics"]))
         assert json.loads((roots[k] / "best_model_selection_summary.json").read_text()) == json.loads(json.dumps(got[k]["best_model_selection"]))
@@ -368,8 +280,8 @@ def test_train_cli_seeds_gate_equals_single_seed_runs(tmp_path):
         assert [h["timesteps"] for h in ha] == [4096, 8192] == [h["timesteps"] for h in hb]
         for x, y in zip(ha, hb):
             x.pop("candidate"), y.pop("candidate")
-            _assert_payload_match(x, y, f"seed_{s}/history")
+            F.assert_payload_match(x, y, f"seed_{s}/history")
         ta, tb = (json.loads((r / "training_summary.json").read_text()) for r in (rep, single))
-        _assert_payload_match(ta["final_workspace_eval"]["stage_metrics"], tb["final_workspace_eval"]["stage_metrics"], f"seed_{s}/final")
+        F.assert_payload_match(ta["final_workspace_eval"]["stage_metrics"], tb["final_workspace_eval"]["stage_metrics"], f"seed_{s}/final")
     summ = json.loads((pop_root / "population_summary.json").read_text())
     assert [r["seed"] for r in summ["per_seed"]] == [7, 8]
