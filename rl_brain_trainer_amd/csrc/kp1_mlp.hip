@@ -109,9 +109,10 @@ __device__ __forceinline__ f32x4 load16_sc1(const float* __restrict__ base, int6
 // tools/mfma_valu_mix.hip, profiles/r02_mfma_valu_mix.log.  Every vector instruction of an epilogue is therefore paid in MFMA time, and
 // the 64 tanh evaluations per lane were 38 % of the tile kernel's vector instructions in the round-1 form (14 instructions each: odd
 // polynomial below |x| = 0.25, exp form above, select, copysign).  Saturates correctly (2^(+big) = inf -> -1, 2^(-big) = 0 -> +1), NaN
-// propagates.  Absolute error <= ~1.5e-7 everywhere (the rounding of 1 + t and of the final 2r - 1), i.e. fp32 epsilon of the result's
-// scale; the RELATIVE error grows as |x| -> 0 (result ~ x +- 1e-7), which a tanh hidden unit's consumers -- dot products of 256 such
-// values, and 1 - h^2 in the backward pass -- do not resolve.  Checked against torch.tanh in tests/test_ppo_kernels_gpu.py.
+// propagates.  Absolute error <= ~1.8e-7 on [-20, 20] with exact exp2 and rcp (the rounding of 1 + t and of the final 2r - 1), i.e. fp32
+// epsilon of the result's scale; the RELATIVE error grows as |x| -> 0 (result ~ x +- 1e-7), which a tanh hidden unit's consumers -- dot
+// products of 256 such values, and 1 - h^2 in the backward pass -- do not resolve.  Held against fp64 up to |x| ~ 49 and at |x| ~ 1e18 by
+// tests/test_trained_regime_gpu.py (through the kernels that use it); DESIGN.md, "Parity on trained-scale policies".
 __device__ __forceinline__ float kp_tanh(float x) {
   const float t = __builtin_amdgcn_exp2f(x * -2.8853900817779268f);
   return fmaf(2.0f, __builtin_amdgcn_rcpf(t + 1.0f), -1.0f);

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import eval_forms as F
+import trained_regime as T
 from conftest import load_golden_config
 from eval_forms import DEV, NORM_RTOL, THR
 from rl_brain_trainer_amd import evaluate as ev
@@ -50,7 +51,9 @@ def _opts(suite, mode: str, n: int = E) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. step parity
-def _step_parity(pol, suite, mode: str, stride: int, confirm: int, n: int) -> None:
+def _step_parity(pol, suite, mode: str, stride: int, confirm: int, n: int, fp64_flat: torch.Tensor | None = None) -> None:
+    """``fp64_flat``: the policy's parameters, for a check of the first step's deterministic action against an fp64 forward of the
+    observations the env holds at that step, under the forward tolerances"""
     L = native.load()
     opts = _opts(suite, mode, n)
     active = F.forced_active_mask(n)
@@ -64,6 +67,8 @@ def _step_parity(pol, suite, mode: str, stride: int, confirm: int, n: int) -> No
         native.check(L.kp1_eval_step(pol._mlp._h, env._handle, F.ptr(env.obs), F.ptr(env.reward), F.ptr(env.done), C.byref(b.struct), step, thr, confirm,
                                      F.stream()))
         action = pol.predict(ref_env.obs)
+        if fp64_flat is not None and step == 1:
+            T.assert_step_against_fp64(fp64_flat, 256, 56, ref_env.obs, None, {"clipped": action}, "step 1, deterministic action")
         at_clamp += int((action.abs() == 1.0).sum())
         inside += int((action.abs() < 1.0).sum())
         an = F.norm_in_index_order(action)
@@ -103,6 +108,15 @@ def test_eval_step_h256_equals_the_launch_sequence(policies, suite, mode, stride
 def test_eval_step_h256_row_counts(policies, suite, n):
     """one row, exactly one tile, one tile and one row"""
     _step_parity(policies[0], suite, "approach", 56, 2, n)
+
+
+def test_eval_step_h256_trained_scale(suite):
+    """the T4 policy of tests/trained_regime.py (40 % of the second-layer units beyond |h| = 0.999) on one tile and one row: the same bit
+    equality after every step, and the first step's action against fp64.  (The action reaches the env only through the one-launch step on
+    one twin and through predict on the other, and the observations after the step are equal bit for bit.)"""
+    trained = T.trained_policy(256, 56, "T4")
+    pol = P.InferencePolicy(trained.state_dict(), device=DEV, max_batch=128)
+    _step_parity(pol, suite, "approach", 56, 2, 33, fp64_flat=trained.flat)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. runner and evaluators

@@ -24,22 +24,10 @@ from rl_brain_trainer_amd import ppo as P
 from rl_brain_trainer_amd.mlp import MlpKernels
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-KW = dict(clip_range=0.2, ent_coef=1e-2, vf_coef=0.5)
+DEV, KW = S.DEV, S.KW
+_handle, _dev, _loss_grad, _check_kl = S.handle, S.dev, S.loss_grad, S.check_kl      # the call helpers shared with test_trained_regime_gpu.py
 ADAM_KW = dict(lr=3e-4, eps=1e-5, max_grad_norm=0.5)
 NAN = float("nan")
-
-
-def _handle(kind, max_batch=512, replicas=1) -> MlpKernels:
-    hidden, obs_dim, path = kind
-    k = MlpKernels(hidden, DEV, max_batch=max_batch, obs_dim=obs_dim, replicas=replicas)
-    if hidden == 256:
-        k.set_fused(path == "fused")
-    return k
-
-
-def _dev(buf: dict) -> dict:
-    return {name: t.to(DEV).contiguous() for name, t in buf.items()}
 
 
 def _bits(t: torch.Tensor) -> torch.Tensor:
@@ -87,11 +75,6 @@ class _World:
         w.flat0, w.idx33, w.idx1 = self.flat0[r:r + 1].contiguous(), self.idx33[r:r + 1].contiguous(), self.idx1[r:r + 1].contiguous()
         w.fobs, w.fnoise = self.fobs[40 * r:40 * (r + 1)].contiguous(), self.fnoise[40 * r:40 * (r + 1)].contiguous()
         return w
-
-
-def _loss_grad(k: MlpKernels, buf: dict, idx, n: int, grad, stats, obs=None, **over):
-    k.loss_grad(buf["obs"] if obs is None else obs, idx, n, buf["act"], buf["old_logp"], buf["adv"], buf["ret"], inv_count=1.0 / n, grad_out=grad,
-                stats_out=stats, **{**KW, **over})
 
 
 def _probe(k: MlpKernels, w: _World) -> dict[str, torch.Tensor]:
@@ -459,18 +442,6 @@ def edge_world():
     yield get
     for k, *_ in cache.values():
         k.close()
-
-
-def _check_kl(slot3: float, klb: dict, what, calls: int = 1) -> float:
-    """stats_out[3] after `calls` accumulating calls against approx_kl = mean((ratio - 1) - log ratio) in fp64.  This comparison has no project
-    tolerance; the bound is R.approx_kl_bound's 8 * max(e32, floor): e32 = the error of the same expression evaluated with P.mlp_forward /
-    P.gaussian_log_prob in float32 on the CPU, floor = 2^-23 * max(1, max|logp|) * mean|log ratio| (log ratio inherits one fp32 spacing of
-    the log-prob, and d kl / d log ratio = ratio - 1 ~ log ratio).  The value is > 100 x the bound (also asserted by the CPU companion), so a
-    missing inv_count, another slot or the second-order formula cannot pass.  Returns error / bound."""
-    assert klb["kl64"] > 100 * klb["bound"], (what, klb)
-    err = abs(slot3 - calls * klb["kl64"])
-    assert err <= calls * klb["bound"], f"{what} approx_kl: got {slot3} for {calls} call(s) of {klb['kl64']}, error {err:.3e} bound {calls * klb['bound']:.3e}"
-    return err / (calls * klb["bound"])
 
 
 def _check_grad(grad, stats, ref, spec, what, klb):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import trained_regime as TR
 from conftest import GOLDEN, load_golden_config
 from rl_brain_trainer_amd import config as kcfg
 from rl_brain_trainer_amd import native
@@ -36,9 +37,12 @@ def _bytes(obj) -> bytes:
     return bytes(C.string_at(C.addressof(obj), C.sizeof(obj)))
 
 
-def _random_policy(hidden: int, K: int, seed: int) -> torch.Tensor:
+def _random_policy(hidden: int, K: int, seed: int, regime: str | None = None) -> torch.Tensor:
+    """``regime``: the trained-scale policies of tests/trained_regime.py in place of the drawn ones"""
     from rl_brain_trainer_amd.ppo import ActorCritic
 
+    if regime is not None:
+        return torch.stack([TR.trained_policy(hidden, 56, regime, seed=seed + k).flat for k in range(K)]).to(DEV).contiguous()
     g = torch.Generator(device="cpu").manual_seed(1000 + seed)
     rows = []
     for k in range(K):
@@ -52,11 +56,11 @@ def _random_policy(hidden: int, K: int, seed: int) -> torch.Tensor:
     return torch.stack(rows).contiguous()
 
 
-def _mlp(hidden: int, K: int, seed: int, max_batch: int = 128):
+def _mlp(hidden: int, K: int, seed: int, max_batch: int = 128, regime: str | None = None):
     from rl_brain_trainer_amd.mlp import MlpKernels
 
     mlp = MlpKernels(hidden, DEV, max_batch=max_batch, replicas=K)
-    flat = _random_policy(hidden, K, seed)
+    flat = _random_policy(hidden, K, seed, regime)
     mlp.pack(flat if K > 1 else flat[0].contiguous())
     return mlp
 
@@ -121,14 +125,14 @@ def _final_state(env, cur, K: int) -> dict:
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(hidden: int, pitch: int, n: int, K: int, T: int, tracker_key: tuple | None, episode_steps: int = EPISODE_STEPS):
+def _reference(hidden: int, pitch: int, n: int, K: int, T: int, tracker_key: tuple | None, episode_steps: int = EPISODE_STEPS, regime: str | None = None):
     """the per-step path on a twin: forward_env_step + observe for T steps.  Returns (buffers, final state, per-step tracker records).  Computed
     once per case and shared; nothing modifies it."""
     tracker = dict(tracker_key) if tracker_key is not None else None
     if tracker is not None and isinstance(tracker["initial"], tuple):
         tracker["initial"] = list(tracker["initial"])
     env, cur = _make(K, n, pitch, tracker, episode_steps)
-    mlp = _mlp(hidden, K, seed=hidden + n)
+    mlp = _mlp(hidden, K, seed=hidden + n, regime=regime)
     rows = K * n
     b = _buffers(T, rows, pitch)
     noise = _noise(T, rows, n)
@@ -149,10 +153,11 @@ def _reference(hidden: int, pitch: int, n: int, K: int, T: int, tracker_key: tup
     return b, final, steps
 
 
-def _run(hidden: int, pitch: int, n: int, K: int, T: int, tracker: dict | None, *, spans=None, skip: tuple = (), episode_steps: int = EPISODE_STEPS):
+def _run(hidden: int, pitch: int, n: int, K: int, T: int, tracker: dict | None, *, spans=None, skip: tuple = (), episode_steps: int = EPISODE_STEPS,
+         regime: str | None = None):
     """the code under test on a fresh twin: rollout_run over ``spans`` (default: one span [0, T)); outputs named in ``skip`` are passed as None"""
     env, cur = _make(K, n, pitch, tracker, episode_steps)
-    mlp = _mlp(hidden, K, seed=hidden + n)
+    mlp = _mlp(hidden, K, seed=hidden + n, regime=regime)
     rows = K * n
     b = _buffers(T, rows, pitch)
     noise = _noise(T, rows, n)
@@ -207,6 +212,18 @@ def test_single_step_span():
     """T = 1: the loop runs once; obs[1] is the only next observation"""
     ref = _reference(64, 64, 33, 1, 1, None)
     _assert_equal(_run(64, 64, 33, 1, 1, None), ref[:2])
+
+
+def test_trained_scale_span():
+    """the T4 policy of tests/trained_regime.py (saturated hidden units, sigma ~ 0.06), n = 33, T = 2: the same bit equality with the
+    per-step path, and step 0 of the whole-rollout launch against an fp64 forward of obs[0]"""
+    hidden, n = 64, 33
+    ref = _reference(hidden, 64, n, 1, 2, None, regime="T4")
+    got = _run(hidden, 64, n, 1, 2, None, regime="T4")
+    _assert_equal(got, ref[:2])
+    b = got[0]
+    TR.assert_step_against_fp64(TR.trained_policy(hidden, 56, "T4", seed=hidden + n).flat, hidden, 56, b["obs"][0], _noise(2, n, n)[0],
+                               {k: b[k][0] for k in ("value", "log_prob", "action")}, "step 0")
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. tracker folded in, K = 1

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import trained_regime as T
 from conftest import GOLDEN, load_golden_config
 from rl_brain_trainer_amd import config as kcfg
 from rl_brain_trainer_amd import native
@@ -46,10 +47,13 @@ def _dock_stages(min_episodes: int) -> list[dict]:
     ]
 
 
-def _random_policy(hidden: int, K: int, seed: int) -> torch.Tensor:
-    """[K, P] parameters: orthogonal weights, an action head large enough for the mean to matter, random biases, log_std well away from 0"""
+def _random_policy(hidden: int, K: int, seed: int, regime: str | None = None) -> torch.Tensor:
+    """[K, P] parameters: orthogonal weights, an action head large enough for the mean to matter, random biases, log_std well away from 0.
+    ``regime``: the trained-scale policies of tests/trained_regime.py in their place"""
     from rl_brain_trainer_amd.ppo import ActorCritic
 
+    if regime is not None:
+        return torch.stack([T.trained_policy(hidden, 56, regime, seed=seed + k).flat for k in range(K)]).to(DEV).contiguous()
     g = torch.Generator(device="cpu").manual_seed(1000 + seed)
     rows = []
     for k in range(K):
@@ -63,20 +67,21 @@ def _random_policy(hidden: int, K: int, seed: int) -> torch.Tensor:
     return torch.stack(rows).contiguous()
 
 
-def _mlp(hidden: int, K: int, max_batch: int, seed: int):
+def _mlp(hidden: int, K: int, max_batch: int, seed: int, regime: str | None = None):
     from rl_brain_trainer_amd.mlp import MlpKernels
 
     mlp = MlpKernels(hidden, DEV, max_batch=max_batch, replicas=K)
-    flat = _random_policy(hidden, K, seed)
+    flat = _random_policy(hidden, K, seed, regime)
     mlp.pack(flat if K > 1 else flat[0].contiguous())
     return mlp, flat
 
 
 def _step_parity(mlp, env_a, env_b, steps: int, *, after_a=None, after_b=None, with_value: bool = True, with_log_prob: bool = True,
-                 seed: int = 0) -> int:
+                 seed: int = 0, fp64_flat: torch.Tensor | None = None) -> int:
     """Twin A takes forward_env_step, twin B forward + step_into(auto_reset=True), on the same noise; every output of every step, then every
-    info plane and the PCG64 words.  ``after_*``: the tracker launch that follows a step (given its done bytes).  Returns the number of
-    finished episodes."""
+    info plane and the PCG64 words.  ``after_*``: the tracker launch that follows a step (given its done bytes).  ``fp64_flat`` (K = 1): the
+    parameters, for a check of step 0's value, log_prob and unclipped action against an fp64 forward of the observations the env holds at
+    that step, under the forward tolerances.  Returns the number of finished episodes."""
     n, w = env_a.n_envs, env_a.obs_stride
     z = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=DEV)   # noqa: E731
     obs_a, obs_b = env_a.reset().clone(), env_b.reset().clone()
@@ -105,6 +110,8 @@ def _step_parity(mlp, env_a, env_b, steps: int, *, after_a=None, after_b=None, w
             b["log_prob"].zero_()
         for k in a:
             assert torch.equal(a[k], b[k]), (t, k)
+        if fp64_flat is not None and t == 0:
+            T.assert_step_against_fp64(fp64_flat, mlp.hidden, 56, obs_a, noise, {k: a[k] for k in ("value", "log_prob", "action")}, "step 0")
         finished += int((b["done"] & 3 != 0).sum())
         obs_a, obs_b = a["next_obs"], b["next_obs"]
     ia, ib = env_a.info(), env_b.info()
@@ -139,6 +146,26 @@ def test_step_parity_single(hidden, mode, pitch, E):
     no_logp = (hidden, mode, pitch, E) == (128, "dock", 56, 70)
     finished = _step_parity(mlp, envs[0], envs[1], 200 if mode == "approach" else 80, with_value=not no_value, with_log_prob=not no_logp, seed=E)
     assert finished >= 2 * E
+    mlp.close()
+    for env in envs:
+        env.close()
+
+
+@pytest.mark.parametrize("hidden", [64, 128])
+def test_step_parity_trained_scale(hidden):
+    """the T4 policy of tests/trained_regime.py (saturated hidden units, sigma ~ 0.06) on E = 33: the same bit equality over 200 steps, and
+    step 0 against fp64"""
+    from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv
+
+    envs = []
+    for _ in range(2):
+        env = ArmKinematicVecEnv(_approach_cfg(), 33, seed=31)
+        env.set_curriculum_stage(5)
+        env.set_obs_stride(64)
+        envs.append(env)
+    mlp, flat = _mlp(hidden, 1, 128, seed=3, regime="T4")
+    finished = _step_parity(mlp, envs[0], envs[1], 200, seed=33, fp64_flat=flat[0])
+    assert finished >= 2 * 33
     mlp.close()
     for env in envs:
         env.close()

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import trained_regime as T
 from conftest import GOLDEN
 from rl_brain_trainer_amd import config as kcfg
 from rl_brain_trainer_amd import native
@@ -58,15 +59,19 @@ def _bytes(obj) -> bytes:
     return bytes(C.string_at(C.addressof(obj), C.sizeof(obj)))
 
 
-def _mlp(hidden: int, K: int, obs_dim: int, seed: int, max_batch: int = 128):
+def _mlp(hidden: int, K: int, obs_dim: int, seed: int, max_batch: int = 128, regime: str | None = None):
     """a K-replica handle with [K, P] parameters: orthogonal weights, an action head large enough for the mean to matter (means of a few
-    hundredths), random biases, log_std near -1 (the action-norm distribution the route-ready threshold was chosen for)"""
+    hundredths), random biases, log_std near -1 (the action-norm distribution the route-ready threshold was chosen for).  ``regime``: the
+    trained-scale policies of tests/trained_regime.py in their place (another action-norm distribution)"""
     from rl_brain_trainer_amd.mlp import MlpKernels
     from rl_brain_trainer_amd.ppo import ActorCritic
 
     g = torch.Generator(device="cpu").manual_seed(1000 + seed)
     rows = []
     for k in range(K):
+        if regime is not None:
+            rows.append(T.trained_policy(hidden, obs_dim, regime, seed=seed + k).flat.to(DEV))
+            continue
         pol = ActorCritic(hidden, DEV, seed=seed + k, obs_dim=obs_dim)
         pol.views["action_net.weight"].mul_(5.0)
         for name, v in pol.views.items():
@@ -81,10 +86,13 @@ def _mlp(hidden: int, K: int, obs_dim: int, seed: int, max_batch: int = 128):
 
 
 def _step_parity(mlp, env_a, env_b, n_per_replica: int, *, sequence: bool, after_a=None, after_b=None, with_value: bool = True,
-                 with_log_prob: bool = True, with_terminal_obs: bool = True, seed: int = 0) -> None:
+                 with_log_prob: bool = True, with_terminal_obs: bool = True, seed: int = 0, fp64_flat: torch.Tensor | None = None) -> None:
     """Twin A takes forward_route_step, twin B forward + step_into(auto_reset=True), on the same weights and noise: every output of every
     step (whole buffers, padding columns included), then every info plane (route and base) and both PCG64 streams.  ``after_*``: the tracker
-    launch that follows a step.  The branch counts are taken on twin B, per 32-row tile of each replica."""
+    launch that follows a step.  The branch counts are taken on twin B, per 32-row tile of each replica.  ``fp64_flat`` (K = 1): the
+    parameters of a trained-scale policy, for a check of step 0's value, log_prob and unclipped action against an fp64 forward of the
+    observations the env holds at that step; its actions are not the ones the route-ready threshold was chosen for, so of the branch
+    conditions only the resets are required of it."""
     n, w = env_a.n_envs, env_a.obs_stride
     z = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=DEV)   # noqa: E731
     obs_a, obs_b = env_a.reset().clone(), env_b.reset().clone()
@@ -113,6 +121,8 @@ def _step_parity(mlp, env_a, env_b, n_per_replica: int, *, sequence: bool, after
             b["log_prob"].zero_()
         for k in a:
             assert torch.equal(a[k], b[k]), (t, k)
+        if fp64_flat is not None and t == 0:
+            T.assert_step_against_fp64(fp64_flat, mlp.hidden, mlp.obs_dim, obs_a, noise, {k: a[k] for k in ("value", "log_prob", "action")}, "step 0")
         done = b["done"]
         wp = env_b.info()["route_waypoint_success"].ne(0)
         term, trunc = (done & TERMINATED).ne(0), (done & TRUNCATED).ne(0)
@@ -132,6 +142,8 @@ def _step_parity(mlp, env_a, env_b, n_per_replica: int, *, sequence: bool, after
     assert np.array_equal(env_a.base.rng_state(), env_b.base.rng_state())           # the base env's (kp1_rng_get)
     # branch coverage is a condition: overall, and with `sequence` on in every tile of every replica
     assert int(counts["reset"].min()) >= 2, "an env auto-reset fewer than twice"
+    if fp64_flat is not None:
+        return
     needed = ("waypoint_success", "advance", "sequence_success", "truncation") if sequence else ("waypoint_success", "truncation")
     for name in needed:
         assert int(counts[name].sum()) > 0, f"no {name} in the run"
@@ -164,6 +176,18 @@ def test_step_parity_single(hidden, obs_dim, pitch, sequence, E):
     case = (hidden, obs_dim, pitch, sequence, E)
     _step_parity(mlp, envs[0], envs[1], E, sequence=sequence, with_value=case != (64, 80, 80, True, 33),
                  with_log_prob=case != (128, 80, 80, False, 70), with_terminal_obs=case != (64, 56, 56, False, 70), seed=E)
+    mlp.close()
+    for env in envs:
+        env.close()
+
+
+def test_step_parity_trained_scale():
+    """the T4 policy of tests/trained_regime.py (saturated hidden units, sigma ~ 0.06) on the 80-float observation at pitch 128, E = 33: the
+    same bit equality over every step, and step 0 against fp64"""
+    cfgd = _cfg(True, True)
+    envs = [_single_env(cfgd, 33, 128) for _ in range(2)]
+    mlp = _mlp(128, 1, 80, seed=3, regime="T4")
+    _step_parity(mlp, envs[0], envs[1], 33, sequence=True, seed=33, fp64_flat=T.trained_policy(128, 80, "T4", seed=3).flat)
     mlp.close()
     for env in envs:
         env.close()
