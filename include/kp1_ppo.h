@@ -197,7 +197,8 @@ int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t m
  * gradient partials -- trained through ONE launch sequence with the replica on a grid axis (z = 2 * replica + net, or grid.y).  hidden 64 or
  * 128 (the layer-wise Hp = 128 kernels); obs_dim 56 (padded to 64) or 80 (the route observation, padded to 128: layer 1 and dW1 then run
  * over 128 input columns per replica).  Each replica computes exactly what a K = 1 handle computes on the same
- * inputs: reductions keep a single handle's order and chunking per replica.  kp1_mlp_create / _create_ex make K = 1 handles.
+ * inputs: reductions keep a single handle's order and chunking per replica, under KP1_MLP_OPT_TRAIN_TILE too (its chunking is a function of
+ * n alone).  kp1_mlp_create / _create_ex make K = 1 handles.
  * Buffer layout of the entry points below for a K-replica handle (K = 1: the layouts documented at each entry point):
  *   kp1_mlp_pack_weights, kp1_mlp_adam_step: params, grad, exp_avg, exp_avg_sq are [K][num_params]; one clip norm per replica, one shared
  *     Adam step count (all replicas step together);
@@ -332,8 +333,9 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
 /* Options.  KP1_MLP_OPT_FUSED (default 1): for hidden = 256, kp1_mlp_loss_grad runs layer 1, layer 2, the heads, the PPO loss
  * and the activation backward of a 32-row minibatch tile in one workgroup (mlp_tile_kernel<true>) instead of four
  * chip-synchronous launches, and kp1_mlp_forward runs layer 1, layer 2, the heads and the Gaussian sampling in one launch
- * (mlp_tile_kernel<false>) instead of three; 0 selects the layer-wise kernels (always used for hidden = 128).  Same results up
- * to fp32 summation order of the per-tile partials. */
+ * (mlp_tile_kernel<false>) instead of three; 0 selects the layer-wise kernels.  Hidden 64 / 128 handles do not read this option: they run
+ * the layer-wise kernels, or train_tile128_kernel under KP1_MLP_OPT_TRAIN_TILE.  Same results up to fp32 summation order of the per-tile
+ * partials. */
 #define KP1_MLP_OPT_FUSED 1
 /* KP1_MLP_OPT_ACTOR_EXTRA_STEPS (default 0): optimiser steps the actor tensors (mlp_extractor.policy_net.*, action_net.*) have taken
  * on top of the common count -- torch.optim.Adam counts per tensor, and the route trainer's teacher-anchor callback
@@ -353,8 +355,16 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
  * (gemm_tn_bf16x3_kernel) instead of the exact fp32 MFMA kernel.  Not bit-identical to the exact path: error table in DESIGN.md / bench.py's
  * `experiment_bf16x3_wgrad` block.  bench.py's `value` and `dtype` never use it. */
 #define KP1_MLP_OPT_BF16X3_WGRAD 5
+/* KP1_MLP_OPT_TRAIN_TILE (default 0): hidden 64 / 128 handles (K = 1 or a population, obs_dim 56 or 80).  While it is on, kp1_mlp_loss_grad of
+ * a minibatch of n <= 2048 rows per replica launches [adv_partials ->] train_tile128_kernel -> grad_finalize where it launched the five
+ * layer-wise kernels (two forward GEMMs, the head kernel, the backward GEMM, two weight-gradient GEMMs): a workgroup carries one 32-row tile
+ * of one net through forward, loss and backward and leaves one partial of every gradient.  A larger n takes the layer-wise launches.  Every
+ * argument of kp1_mlp_loss_grad behaves as documented; stats_out and the gradients of log_std, action_net, value_net and the layer-2 biases
+ * are bit-equal to the layer-wise result, the weight and layer-1 bias gradients are other fp32 sums of the same terms.  A hidden 256 handle
+ * returns KP1_ERR_UNSUPPORTED (its tile path is KP1_MLP_OPT_FUSED).  KP1_MLP_PROFILE_TILE times the launch. */
+#define KP1_MLP_OPT_TRAIN_TILE 6
 #define KP1_MLP_PROFILE_SLOTS 4
-#define KP1_MLP_PROFILE_TILE 0      /* mlp_tile_kernel<true, .>: forward + loss + activation backward of both nets */
+#define KP1_MLP_PROFILE_TILE 0      /* mlp_tile_kernel<true, .>: forward + loss + activation backward of both nets; train_tile128_kernel */
 #define KP1_MLP_PROFILE_WGRAD 1     /* gemm_tn_frag_kernel: dW2 + dW1 of both nets */
 #define KP1_MLP_PROFILE_FINALIZE 2  /* grad_finalize_kernel */
 #define KP1_MLP_PROFILE_ADAM 3      /* (sum of squares +) adam_kernel */

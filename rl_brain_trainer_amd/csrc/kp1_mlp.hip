@@ -612,36 +612,7 @@ __global__ void __launch_bounds__(256) head_train_kernel(const HeadArgs a_) {
       *reinterpret_cast<f32x4*>(h2s + (net * HEAD_ROWS + r) * hpitch + 4 * c4) = v[j];
     }
   }
-  // fixed-order parallel reduction of the per-block advantage partials (wave 0; a.n_adv_partials <= 128)
-  double ps = 0.0, pss = 0.0;
-  if (a.adv_mode == 1 && threadIdx.x < 64) {
-    for (int k = threadIdx.x; k < a.n_adv_partials; k += 64) {
-      ps += a.adv_partials[2 * k];
-      pss += a.adv_partials[2 * k + 1];
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      ps += __shfl_xor(ps, off);
-      pss += __shfl_xor(pss, off);
-    }
-  }
-  if (threadIdx.x == 0) {
-    float mean = 0.f, inv_std = 1.f;
-    if (a.adv_mode == 1) {  // statistics of this minibatch, torch .mean() / .std() (unbiased)
-      const double s = ps, ss = pss;
-      const double m = s / a.n;
-      const double var = a.n > 1 ? fmax((ss - a.n * m * m) / (a.n - 1), 0.0) : 0.0;
-      mean = (float)m;
-      inv_std = (float)(1.0 / (sqrt(var) + 1e-8));
-    } else if (a.adv_mode == 2) {
-      mean = a.adv_stats[0];
-      inv_std = a.adv_stats[1];
-    } else if (a.adv_mode == 3) {
-      mean = a.adv_mean;
-      inv_std = a.adv_inv_std;
-    }
-    adv_ms[0] = mean;
-    adv_ms[1] = inv_std;
-  }
+#include "kp1_head_adv_body.inc"
   __syncthreads();
   const int row_l = threadIdx.x >> 3, out = threadIdx.x & 7;
   const int row = blockIdx.x * HEAD_ROWS + row_l;
@@ -649,68 +620,7 @@ __global__ void __launch_bounds__(256) head_train_kernel(const HeadArgs a_) {
   const int64_t src = ok ? (a.idx ? a.idx[row] : (int64_t)row) : 0;
   float v = 0.f;
   if (ok) v = head_dot(h2s + ((out == 7 ? HEAD_ROWS : 0) + row_l) * hpitch, w3s + out * a.Hp, a.Hp) + a.b3[out];
-  // Gaussian log-prob of the stored action under the current policy
-  float z = 0.f, inv_sd = 1.f, lp = 0.f;
-  if (ok && out < ACT) {
-    const float ls = a.log_std[out];
-    inv_sd = expf(-ls);
-    z = (a.actions[src * ACT + out] - v) * inv_sd;
-    lp = -0.5f * z * z - ls - LOG_SQRT_2PI;
-  }
-  lp += __shfl_xor(lp, 1);
-  lp += __shfl_xor(lp, 2);
-  lp += __shfl_xor(lp, 4);
-  float g_logp = 0.f, d = 0.f, pl = 0.f, vl = 0.f, kl = 0.f;
-  if (ok) {
-    const float old = a.old_logp[src];
-    const float A = (a.adv[src] - adv_ms[0]) * adv_ms[1];
-    const float lr_ = lp - old;
-    const float ratio = expf(lr_);
-    const float rc = fminf(fmaxf(ratio, 1.f - a.clip_range), 1.f + a.clip_range);
-    const float s1 = ratio * A, s2 = rc * A;
-    // d/dlogp of -min(s1, s2): the unclipped branch carries the gradient unless the clipped one is strictly smaller
-    const bool inside = ratio >= 1.f - a.clip_range && ratio <= 1.f + a.clip_range;
-    g_logp = (inside || s1 < s2) ? -A * ratio * a.inv_count : 0.f;
-    if (out < ACT) {
-      d = g_logp * z * inv_sd;                           // d loss / d mean_out
-    } else {
-      const float R = a.ret[src];
-      d = a.vf_coef * 2.f * (v - R) * a.inv_count;       // d loss / d value
-      vl = (R - v) * (R - v);
-      pl = -fminf(s1, s2);
-      kl = (ratio - 1.f) - lr_;
-    }
-  }
-  dout[row_l * 8 + out] = ok ? d : 0.f;
-  // per-block sums over rows of: d loss/d log_std_out, d loss/d head bias_out, loss terms.  Lanes with equal (t & 7) hold
-  // the same `out`: reduce inside the wave by shuffles, across the 4 waves through per-wave LDS slots summed in a fixed order.
-  float gls = (ok && out < ACT) ? g_logp * (z * z - 1.f) : 0.f;
-  gls += __shfl_xor(gls, 8);
-  gls += __shfl_xor(gls, 16);
-  gls += __shfl_xor(gls, 32);
-  float dsum = ok ? d : 0.f;
-  dsum += __shfl_xor(dsum, 8);
-  dsum += __shfl_xor(dsum, 16);
-  dsum += __shfl_xor(dsum, 32);
-  // per-wave partials in LDS, combined in a fixed order below (no float atomics: bitwise reproducible run to run).
-  // red layout: [wave 0..3][20] = 3 loss sums, pad, 8 bias grads at +4, 7 log_std grads at +12
-  float pl_w = out == 7 ? pl : 0.f, vl_w = out == 7 ? vl : 0.f, kl_w = out == 7 ? kl : 0.f;
-#pragma unroll
-  for (int off = 8; off < 64; off <<= 1) {
-    pl_w += __shfl_xor(pl_w, off);
-    vl_w += __shfl_xor(vl_w, off);
-    kl_w += __shfl_xor(kl_w, off);
-  }
-  const int wave_ = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) < 8) {
-    red[wave_ * 20 + 4 + out] = dsum;
-    if (out < ACT) red[wave_ * 20 + 12 + out] = gls;
-    if (out == 7) {
-      red[wave_ * 20 + 0] = pl_w;
-      red[wave_ * 20 + 1] = vl_w;
-      red[wave_ * 20 + 2] = kl_w;
-    }
-  }
+#include "kp1_head_loss_body.inc"
   __syncthreads();
   float* part = a.hpart + (int64_t)blockIdx.x * a.hpart_stride;
   if (threadIdx.x < 18) {
@@ -1444,7 +1354,8 @@ __global__ void anchor_count_kernel(int* __restrict__ actor_extra) { *actor_extr
 #include "kp1_route_step.inc"
 #include "kp1_route_rollout_step.inc"
 #include "kp1_route_chain_step.inc"
-#include "kp1_rollout_run.inc"       // last: every kernel above keeps its place in the code object
+#include "kp1_rollout_run.inc"       // behind every kernel of its parent: each of those keeps its place in the code object
+#include "kp1_train_tile.inc"        // last, for the same reason
 
 }  // namespace
 
@@ -1478,6 +1389,7 @@ struct kp1_mlp {
   float* hparams_dev = nullptr;
   bool hparams_on = false;
   int last_s2_n = 0, last_s1_n = 0;
+  int train_tile = 0;          // KP1_MLP_OPT_TRAIN_TILE: kp1_mlp_loss_grad of an Hp = 128 handle in one tile launch (train_tile128_kernel)
   int fused = 1;               // KP1_MLP_OPT_FUSED: one workgroup carries a row tile through the whole chain (H = 256 only)
   // While the fused path is selected the Adam kernel refreshes only the fragment-major weight copies (the transposed / slab copies are
   // scattered 4-byte writes and were half of the kernel's HBM write traffic); the k-slab copies are then stale until the next full pack, which switching the
@@ -1847,6 +1759,9 @@ int launch_layer_wgrads(kp1_mlp* m, const float* obs, int obs_stride, const int6
   t.chunk = tn_chunk_rows(n, (Hp / 128) * 2);  // few tiles: more, shorter batch chunks keep the CUs busy
   return launch_tn(m, t, Hp / 128, m->L.INP, m->slab1, s1_n, stream);
 }
+
+// KP1_MLP_OPT_TRAIN_TILE (defined at the end of this file, see there)
+int launch_train_tile(kp1_mlp* m, const HeadArgs& heads, const float* obs, int obs_stride, int chunks, float* grad, hipStream_t stream);
 }  // namespace
 
 extern "C" {
@@ -1991,6 +1906,11 @@ int kp1_mlp_set_option(kp1_mlp* m, int32_t option, int32_t value) {
       HIP_TRY(hipMemset(m->sp_xf, 0, xb));
     }
     m->bf16x3 = value ? 1 : 0;
+    return KP1_OK;
+  }
+  if (option == KP1_MLP_OPT_TRAIN_TILE) {
+    if (m->Hp != ES_HP) return fail(KP1_ERR_UNSUPPORTED, "KP1_MLP_OPT_TRAIN_TILE is for hidden 64 / 128 handles: hidden 256 has its own tile path (KP1_MLP_OPT_FUSED)");
+    m->train_tile = value ? 1 : 0;
     return KP1_OK;
   }
   if (option == KP1_MLP_OPT_PROFILE) {
@@ -2509,6 +2429,8 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     hipLaunchKernelGGL(pop ? adv_partials_kernel<true> : adv_partials_kernel<false>, dim3(N_PARTIALS, m->K), dim3(256), 0, stream, advantages, idx, n,
                        m->partials, pop ? (unsigned)PARTIALS_STRIDE : 0u);
   const int hpart_stride = 10 * Hp + 32;
+  // KP1_MLP_OPT_TRAIN_TILE: chunks of the one-launch tile, or 0 = the layer-wise launches (option off, or more rows than the slabs cover)
+  const int tt_chunks = m->train_tile && !fused ? train_tile_chunks(n) : 0;
   if (fused) {
     FusedArgs fa{};
     fill_fused_head(fa, m, obs, obs_stride, idx, n);
@@ -2528,8 +2450,6 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     }
     if (rc != KP1_OK) return rc;
   } else {
-    rc = launch_forward_layers(m, obs, obs_stride, idx, n, stream);
-    if (rc != KP1_OK) return rc;
     HeadArgs a{};
     a.h2 = m->h2; a.strideH = act_stride; a.Hp = Hp; a.n = n; a.H = H;
     a.w3 = m->k.w3; a.b3 = m->k.b3; a.log_std = m->k.log_std;
@@ -2541,7 +2461,13 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     a.hpart = m->hpart; a.hpart_stride = hpart_stride;
     a.r_act = (unsigned)(2 * act_stride); a.r_hpart = (unsigned)hpart_rep; a.r_partials = (unsigned)PARTIALS_STRIDE;
     a.hparams = pop && m->hparams_on ? m->hparams_dev : nullptr;
-    {
+    if (tt_chunks) {
+      ProfScope ps(m, KP1_MLP_PROFILE_TILE, stream);
+      rc = launch_train_tile(m, a, obs, obs_stride, tt_chunks, grad_out, stream);
+      if (rc != KP1_OK) return rc;
+    } else {
+      rc = launch_forward_layers(m, obs, obs_stride, idx, n, stream);
+      if (rc != KP1_OK) return rc;
       const dim3 hgrid((n + HEAD_ROWS - 1) / HEAD_ROWS, m->K);
       const size_t hbytes = sizeof(float) * (HEADS * Hp + HEAD_ROWS * 8 + 84 + 2 * HEAD_ROWS * (Hp + 4));
       // pop: Hp = 128 (kp1_mlp_create_population)
@@ -2549,9 +2475,9 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
       if (!pop) kernel = Hp == 256 ? head_train_kernel<256> : head_train_kernel<128>;
       HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hbytes));
       hipLaunchKernelGGL(kernel, hgrid, dim3(256), hbytes, stream, a);
+      rc = launch_nt<EPI_DTANH>(backward_nt_args(m, n), stream);
+      if (rc != KP1_OK) return rc;
     }
-    rc = launch_nt<EPI_DTANH>(backward_nt_args(m, n), stream);
-    if (rc != KP1_OK) return rc;
   }
 
   // weight gradients (split over the batch axis)
@@ -2575,6 +2501,8 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     if (rc != KP1_OK) return rc;
     s2_n = t.n_chunks2;
     s1_n = t.n_chunks1;
+  } else if (tt_chunks) {
+    s2_n = s1_n = tt_chunks;   // train_tile128_kernel left one slab of each per chunk
   } else {
     rc = launch_layer_wgrads(m, obs, obs_stride, idx, n, &s2_n, &s1_n, stream);
     if (rc != KP1_OK) return rc;
@@ -2582,6 +2510,7 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
   FinalizeArgs f{};
   fill_finalize(f, m, n, s2_n, s1_n, grad_out);
   if (fused) f.b_n = (n + FU_BM - 1) / FU_BM * (FU_BM / 32);   // the tile kernel's 32-row tiles
+  if (tt_chunks) f.b_n = tt_chunks;                            // one b1 partial row per chunk (= f.h_n: a chunk is one 32-row block)
   f.ent_coef = ent_coef; f.inv_count = inv_count;
   f.stats = stats_out; f.sumsq = m->partials + 2 * N_PARTIALS;
   f.step_counter = m->step_dev;
@@ -2898,3 +2827,31 @@ int kp1_mlp_anchor_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_
 }
 
 }  // extern "C"
+
+namespace {
+// KP1_MLP_OPT_TRAIN_TILE: forward, loss and backward of an Hp = 128 handle in one launch.  `heads` is the HeadArgs block of the layer-wise
+// path; the partial buffers are taken from the FinalizeArgs that grad_finalize_kernel will read them through.
+// The definition stands behind every other launch site of the file: the kernels are emitted in the order in which they are first named,
+// and the ones emitted behind a new kernel move (their pc-relative constant addresses change).
+int launch_train_tile(kp1_mlp* m, const HeadArgs& heads, const float* obs, int obs_stride, int chunks, float* grad, hipStream_t stream) {
+  const int Hp = m->Hp, INP = m->L.INP;
+  TrainTile128Args t{};
+  t.h = heads;
+  t.h.h2 = nullptr; t.h.dz2 = nullptr; t.h.r_act = 0u;   // the activations stay in LDS
+  t.obs = obs; t.obs_stride = obs_stride; t.Kreal = kreal(m, obs_stride);
+  fill_layer_weights(t, m);
+  t.w2t = m->k.w2t;
+  t.n_w1 = (unsigned)(Hp * INP); t.n_w2 = (unsigned)(Hp * Hp); t.n_b = (unsigned)Hp;
+  FinalizeArgs f{};
+  fill_finalize(f, m, heads.n, chunks, chunks, grad);
+  t.slab2 = m->slab; t.s2_ld = f.s2_ld; t.s2_net = f.s2_net; t.s2_chunk = f.s2_chunk;
+  t.slab1 = m->slab1; t.s1_ld = f.s1_ld; t.s1_net = f.s1_net; t.s1_chunk = f.s1_chunk;
+  t.bslab = m->bslab; t.b_net = f.b_net; t.b_tile = f.b_tile;
+  t.r_slab2 = f.r_slab2; t.r_slab1 = f.r_slab1; t.r_bslab = f.r_bslab;
+  const bool pop = m->K > 1;
+  auto* kernel = INP == 64 ? (pop ? train_tile128_kernel<64, true> : train_tile128_kernel<64, false>)
+                           : (pop ? train_tile128_kernel<128, true> : train_tile128_kernel<128, false>);
+  KP1_LAUNCH(kernel, dim3(chunks, m->K, 2), dim3(ES_NTH), 0, stream, t);   // static LDS: no attribute call, capture-safe
+  return KP1_OK;
+}
+}  // namespace

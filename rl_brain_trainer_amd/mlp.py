@@ -54,6 +54,7 @@ class MlpKernels:
         self.obs_dim = int(obs_dim)                      # 56, or 80 with the route observation keys
         self.obs_pad = 64 if self.obs_dim <= 64 else 128   # row pitch the kernels also accept (zero padded)
         self.fused = True                                # what set_fused last set (hidden 256: the tile kernels; the handle's default is on)
+        self.train_tile = False                          # what set_train_tile last set (hidden 64 / 128: train_tile128_kernel; default off)
         if replicas == 1:
             native.check(L.kp1_mlp_create_ex(device.index or 0, hidden, self.obs_dim, self.max_batch, C.byref(self._h)))
         else:
@@ -91,6 +92,15 @@ class MlpKernels:
         """EXPERIMENT (default off): weight-gradient GEMMs on operands pre-split into three bf16 pieces, six bf16 MFMAs per product block
         (gemm_tn_bf16x3_kernel).  Not the exact path; bench.py's value never uses it."""
         native.check(self.L.kp1_mlp_set_option(self._h, self.OPT_BF16X3_WGRAD, int(bool(on))))
+
+    OPT_TRAIN_TILE = 6
+
+    def set_train_tile(self, on: bool) -> None:
+        """hidden 64 / 128 (default off): loss_grad of a minibatch of at most 2048 rows per replica runs forward, loss and backward of a 32-row
+        tile of one net in ONE launch (train_tile128_kernel) in place of the five layer-wise launches; larger minibatches keep those.
+        hidden 256 refuses (its tile path is ``set_fused``)."""
+        native.check(self.L.kp1_mlp_set_option(self._h, self.OPT_TRAIN_TILE, int(bool(on))))
+        self.train_tile = bool(on)
 
     OPT_PROFILE = 4
     PROFILE_SLOTS = ("mlp_train_tile", "gemm_tn_split", "grad_finalize", "adam")

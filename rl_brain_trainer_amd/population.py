@@ -108,6 +108,7 @@ class ReplicaView:
     num_timesteps = property(lambda self: self._pop.num_timesteps)
     n_train_calls = property(lambda self: self._pop.n_train_calls)
     last_stats = property(lambda self: self._pop.replica_stats(self.k))
+    update_form = property(lambda self: self._pop.update_form)
 
     @torch.no_grad()
     def predict(self, obs: torch.Tensor, deterministic: bool = True) -> torch.Tensor:

@@ -492,6 +492,27 @@ def rollout_run_covered(step_covered: bool, hidden: int, mode_name: str, dist_en
     return bool(default_on) if env_var is None else env_var != "0"
 
 
+# KP1_MLP_OPT_TRAIN_TILE: the optimiser step's forward, loss and backward as one tile launch at the layer-wise widths
+TRAIN_TILE_WIDTHS = (64, 128)
+TRAIN_TILE_ENV = "KP1_TRAIN_TILE"
+TRAIN_TILE_MAX_ROWS = 2048             # csrc/kp1_train_tile.inc TT_MAX_ROWS: 64 chunks of one 32-row tile
+
+
+def train_tile_covered(hidden: int, env_var: str | None, *, default_on: bool = False) -> bool:
+    """Whether a trainer switches ``MlpKernels.set_train_tile`` on.  ``hidden``: 64 / 128 (hidden 256 has its own tile path); ``env_var``:
+    KP1_TRAIN_TILE, "1" is on and any other value off; None = unset: ``default_on``, the trainer's default (off until a measurement by
+    DESIGN section 20's rule turns it on)."""
+    if hidden not in TRAIN_TILE_WIDTHS:
+        return False
+    return bool(default_on) if env_var is None else env_var == "1"
+
+
+def train_tile_chunks(n: int) -> int:
+    """Chunks (= 32-row tiles) of an n-row minibatch under KP1_MLP_OPT_TRAIN_TILE, or 0: the layer-wise launches take it
+    (csrc/kp1_train_tile.inc train_tile_chunks).  A function of n alone."""
+    return (n + 31) // 32 if 1 <= n <= TRAIN_TILE_MAX_ROWS else 0
+
+
 # kp1_mlp_forward_route_step (DESIGN section 22): the widths, the observation widths and the route length it covers
 FUSED_ROUTE_ROLLOUT_WIDTHS = (64, 128)
 FUSED_ROUTE_ROLLOUT_OBS_DIMS = (56, 80)
@@ -553,6 +574,17 @@ class PPO:
         return fused_rollout_covered(type(env) is ArmKinematicVecEnv, env.dtype, self.cfg.hidden, self.obs_dim,
                                      getattr(env, "_reward_components_on", False), os.environ.get("KP1_FUSED_ROLLOUT"),
                                      default_on=self.cfg.hidden == 256)
+
+    # the trainer's default for the one-launch training tile while KP1_TRAIN_TILE is unset: off until a measurement by DESIGN section 20's
+    # rule turns it on
+    train_tile_default = False
+
+    @property
+    def update_form(self) -> str:
+        """which kernels the optimiser step's forward / loss / backward runs: recorded in training_summary.json"""
+        if self.cfg.hidden == 256:
+            return "tile 2x256 (mlp_tile_kernel)" if self._mlp.fused else "layer-wise"
+        return "train tile (train_tile128_kernel)" if self._mlp.train_tile else "layer-wise"
 
     # the trainer's default for the whole-rollout form while KP1_ROLLOUT_RUN is unset: off until a measurement by DESIGN section 27's rule
     # turns it on
@@ -669,6 +701,8 @@ class PPO:
         if os.environ.get("KP1_BF16X3_WGRAD", "0") == "1" and cfg.hidden == 256:
             # round-3 EXPERIMENT (off by default, never used by bench.py's value): weight-gradient GEMMs on bf16 x 3 operands
             self._mlp.set_bf16x3_wgrad(True)
+        if train_tile_covered(cfg.hidden, os.environ.get(TRAIN_TILE_ENV), default_on=self.train_tile_default):
+            self._mlp.set_train_tile(True)
         # hipGraph replay of the rollout (T x 3 launches) and of one update epoch.  Data parallel: graph segments with eager collectives
         # between them, or (opt-in) the RCCL collectives captured inside the graphs: Dist.graph_mode.
         self.use_graphs = bool(use_graphs)
@@ -725,7 +759,7 @@ class PPO:
     def _epoch_key(self) -> tuple:
         c = self.cfg
         return (c.learning_rate, c.clip_range, c.ent_coef, c.vf_coef, c.max_grad_norm, c.adam_eps, c.batch_size, c.n_steps, c.normalize_advantage,
-                self.dist.world_size)
+                self.dist.world_size, self._mlp.train_tile)
 
     def _curriculum_observe(self, t: int) -> None:
         """after env step t: feed the done bytes to the device tracker (single process: every step; data parallel: once per chunk -- a route

@@ -64,6 +64,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     r.add_argument("--whole-rollout", dest="whole_rollout", action="store_const", const=True, default=None,
                    help="run all env steps of a rollout in one launch per span (kp1_rollout_run; sets KP1_ROLLOUT_RUN=1) where it is covered: "
                         "hidden 64 / 128, one process, no tracker or at most 32 envs per seed; same results bit for bit")
+    r.add_argument("--train-tile", dest="train_tile", action="store_true",
+                   help="hidden 64 / 128: forward, loss and backward of the optimiser step in one tile launch (train_tile128_kernel; sets "
+                        "KP1_TRAIN_TILE=1); without the flag KP1_TRAIN_TILE decides, and unset it is the layer-wise kernels")
     r.add_argument("--per-step-rollout", dest="whole_rollout", action="store_const", const=False,
                    help="keep one launch per env step (sets KP1_ROLLOUT_RUN=0); without either flag KP1_ROLLOUT_RUN decides, and unset it is "
                         "the trainer's default (the per-step loop)")
@@ -173,6 +176,8 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
     if args.sweep and args.seeds is None:
         raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
+    if args.train_tile:
+        os.environ["KP1_TRAIN_TILE"] = "1"     # read by PPO._setup (every trainer class) when it creates the MLP handle
     if args.whole_rollout is not None:
         os.environ["KP1_ROLLOUT_RUN"] = "1" if args.whole_rollout else "0"     # read by PPO / ApproachPopulationPPO at every rollout
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -324,7 +329,7 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, resume, 
         "resume_from": str(resume) if resume else None, "n_envs": n_envs, "device": f"{world}x MI355X",
         "curriculum_summary": curriculum.summary() if curriculum is not None else None,
         "final_workspace_eval": final_eval, "num_timesteps": ppo.num_timesteps, "wall_seconds": wall,
-        "env_steps_per_second": ppo.num_timesteps / wall, "last_update_stats": ppo.last_stats, **(extra or {}),
+        "env_steps_per_second": ppo.num_timesteps / wall, "last_update_stats": ppo.last_stats, "update_form": ppo.update_form, **(extra or {}),
     }
     write_json(root / "training_summary.json", summary)
     print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "model_latest": str(latest) + ".zip",

@@ -57,6 +57,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
                    help="run the final dock evaluation with the one-launch step (kp1_eval_step) instead of the launch sequence per env step "
                         "(evaluate.run_episodes, the default here: the one-launch form has not been timed on this workload); the summaries "
                         "are equal, the two forms differ only in the action-magnitude floats, by an ulp")
+    p.add_argument("--train-tile", dest="train_tile", action="store_true", help="hidden 64 / 128: forward, loss and backward of the optimiser step in one tile launch "
+                   "(train_tile128_kernel; sets KP1_TRAIN_TILE=1); without the flag KP1_TRAIN_TILE decides, and unset it is the layer-wise kernels")
     return p
 
 
@@ -82,6 +84,8 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
     if args.sweep and args.seeds is None:
         raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
+    if args.train_tile:
+        os.environ["KP1_TRAIN_TILE"] = "1"     # read by PPO._setup (every trainer class) when it creates the MLP handle
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -166,7 +170,7 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, cfg: dic
     summary = {"policy_type": "dock", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "config": cfg, "model_path": str(latest) + ".zip",
                "resume_from": str(resume) if resume else None, "n_envs": n_envs, "device": f"{world}x MI355X",
                "dock_eval_summary": eval_summary, "dock_reverse_curriculum": curriculum.summary() if curriculum is not None else None,
-               "num_timesteps": ppo.num_timesteps, "wall_seconds": wall, "env_steps_per_second": ppo.num_timesteps / wall, **(extra or {})}
+               "num_timesteps": ppo.num_timesteps, "wall_seconds": wall, "env_steps_per_second": ppo.num_timesteps / wall, "update_form": ppo.update_form, **(extra or {})}
     (root / "training_summary.json").write_text(json.dumps(summary, indent=2))
     return summary
 

@@ -81,6 +81,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
                    "chained final evaluation issues its lock steps -- the launch sequence, one launch per lock step "
                    "(kp1_mlp_forward_route_chain_step) or one launch per span of lock steps (kp1_route_chain_run); same files bit for bit. "
                    "Default: route_curriculum.CHAIN_FORM_DEFAULT.  --per-replica-eval and --seed keep their evaluators")
+    p.add_argument("--train-tile", dest="train_tile", action="store_true", help="hidden 64 / 128: forward, loss and backward of the optimiser step in one tile launch "
+                   "(train_tile128_kernel; sets KP1_TRAIN_TILE=1); without the flag KP1_TRAIN_TILE decides, and unset it is the layer-wise kernels")
     return p
 
 
@@ -88,6 +90,8 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
     if args.sweep and args.seeds is None:
         raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
+    if args.train_tile:
+        os.environ["KP1_TRAIN_TILE"] = "1"     # read by PPO._setup (every trainer class) when it creates the MLP handle
     if args.one_launch_rollout:
         os.environ["KP1_FUSED_ROUTE_ROLLOUT"] = "1"     # read by PPO / RoutePopulationPPO at every rollout step (ppo.fused_route_rollout_covered)
     import torch.distributed as dist
@@ -359,7 +363,7 @@ def _write_run_artifacts(args, cfg: dict[str, Any], route_cfg: dict[str, Any], r
         "curriculum_summary": curriculum_summary, "teacher_anchor_summary": anchor_summary,
         "route_eval_sequential_summary": eval_summary, "route_gate_summary": gate_summary, "config": cfg,
         "num_timesteps": int(ppo.num_timesteps), "wall_seconds": wall, "env_steps_per_second": rate, "env_steps_per_s": rate,
-        "observation_dim": int(ppo.obs_dim),
+        "observation_dim": int(ppo.obs_dim), "update_form": ppo.update_form,
     }
     # the sequential evaluation and the gate, after training (a population's chained evaluation: its share of the one batch call + its own files)
     summary["evaluation_wall_seconds"] = time.time() - t_eval + evaluation_wall_offset

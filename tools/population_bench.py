@@ -610,6 +610,8 @@ def main() -> None:
     ap.add_argument("--rollout-form", choices=("per-step", "whole"), default=None, help="with --one-handle or --single-seed: the rollout as one "
                     "launch sequence per env step (sets KP1_ROLLOUT_RUN=0) or as one launch per span of env steps (KP1_ROLLOUT_RUN=1: "
                     "kp1_rollout_run, DESIGN section 27); default: the trainer's own choice")
+    ap.add_argument("--train-tile", action="store_true", help="hidden 64 / 128: the optimiser step's forward, loss and backward as one tile launch "
+                    "(train_tile128_kernel; sets KP1_TRAIN_TILE=1, which every trainer class reads when it creates its MLP handle)")
     ap.add_argument("--dock", action="store_true", help="the Finisher reference shape, one handle (DockPopulationPPO) and K handles")
     ap.add_argument("--no-curriculum", action="store_true", help="with --dock: no reverse-curriculum tracker")
     ap.add_argument("--ks", default="")
@@ -632,6 +634,8 @@ def main() -> None:
         if not args.route:
             ap.error("--one-launch-rollout is the route form's switch (the arm envs answer to KP1_FUSED_ROLLOUT)")
         os.environ["KP1_FUSED_ROUTE_ROLLOUT"] = "1"
+    if args.train_tile:
+        os.environ["KP1_TRAIN_TILE"] = "1"
     if args.rollout_form:
         if not (args.one_handle or args.single_seed):
             ap.error("--rollout-form selects the rollout of the --one-handle and --single-seed iterations (the other trainers have one form)")
@@ -682,7 +686,8 @@ def main() -> None:
     result = {"workload": f"{workload}, {args.n_envs} envs x {args.n_steps} steps per replica, "
                           f"minibatch {args.batch}, 2x{args.hidden}, curriculum on; seeds 7..7+K-1"
                           + (f"; sweep {dict(SWEEP)} (replica k takes value k % n)" if SWEEP else "")
-                          + (f"; rollout form {args.rollout_form}" if args.rollout_form else ""), "device": torch.cuda.get_device_name(0), "rows": rows}
+                          + (f"; rollout form {args.rollout_form}" if args.rollout_form else "")
+                          + ("; update form train tile" if args.train_tile else ""), "device": torch.cuda.get_device_name(0), "rows": rows}
     if args.out:
         Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
     print(json.dumps({"aggregate_env_steps_per_s": {r["K"]: round(r["aggregate_env_steps_per_s"]) for r in rows}}))
