@@ -804,7 +804,7 @@ struct FinalizeArgs {
   float ent_coef, inv_count;
   const float* log_std;
   float* grad; float* stats; double* sumsq;
-  int* step_counter;  // Adam step count kept on the device (hipGraph replays cannot change a scalar kernel argument)
+  int* step_counter;  // Adam step counts kept on the device, kp1_mlp::step_dev (hipGraph replays cannot change a scalar kernel argument)
   // population (POP kernel, grid.y = replica): partials at + r * r_*, grad at + r * total, stats at + 4 r, log_std at + 8 r; the shared
   // step counter is advanced by replica 0 only
   unsigned r_slab2, r_slab1, r_bslab, r_hpart, r_sumsq;
@@ -821,6 +821,40 @@ __device__ __forceinline__ FinalizeArgs finalize_args_replica(FinalizeArgs a, un
   if (rep != 0) a.step_counter = nullptr;
   return a;
 }
+
+// kp1_mlp::step_dev (STEP_DEV_INTS ints, one 64-byte line).  [CNT_STEP] is the common Adam step count and [CNT_EXTRA] the steps the actor
+// tensors have taken beyond it.  Behind them sits the Adam record: the bias corrections of exactly the counts named in its tags, written once
+// per optimiser step by the one thread that advances a count (grad_finalize_kernel, anchor_count_kernel) or that knows the count the next
+// Adam launch will use (anchor_finalize_kernel), so that no thread of an Adam launch evaluates a powf.  An Adam launch whose counts differ
+// from the tags (the host set a count in between, a step count given by the caller) evaluates the same expressions itself.
+constexpr int CNT_STEP = 0, CNT_EXTRA = 1;
+constexpr int REC_STEP = 4, REC_EXTRA = 5, REC_BC = 6;      // tags, then bc1, bc2_sqrt, bc1 (actor), bc2_sqrt (actor) as floats
+constexpr int AREC_ST = 10, AREC_BC2 = 11, AREC_BC1 = 12;   // anchor_adam_kernel: its step tag, sqrt(1 - 0.999^st) (float), 1 - 0.9^st (double)
+constexpr int STEP_DEV_INTS = 16;
+static_assert(REC_BC + 4 == AREC_ST && AREC_BC1 % 2 == 0 && AREC_BC1 + 2 <= STEP_DEV_INTS, "the record's fields");
+
+// the bias corrections of torch.optim.Adam at an fp32 step count: the one text of these expressions, for the record and for the launches
+// that evaluate them in place
+__device__ __forceinline__ void adam_bias(float step, float& bc1, float& bc2_sqrt) {
+  bc1 = 1.f - powf(0.9f, step);
+  bc2_sqrt = sqrtf(1.f - powf(0.999f, step));
+}
+// the actor tensors' pair: the common one unless they have taken `extra` more steps (torch keeps one count per tensor)
+__device__ __forceinline__ void adam_bias_actor(float step, int extra, float bc1, float bc2_sqrt, float& bc1_a, float& bc2_sqrt_a) {
+  bc1_a = bc1; bc2_sqrt_a = bc2_sqrt;
+  if (extra != 0) adam_bias(step + (float)extra, bc1_a, bc2_sqrt_a);
+}
+__device__ __forceinline__ void adam_record_write(int* cnt, int step, int extra) {
+  float bc[4];
+  adam_bias((float)step, bc[0], bc[1]);
+  adam_bias_actor((float)step, extra, bc[0], bc[1], bc[2], bc[3]);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) cnt[REC_BC + q] = __float_as_int(bc[q]);
+  cnt[REC_STEP] = step; cnt[REC_EXTRA] = extra;
+}
+// anchor_adam_kernel forms its corrections in f64 at st = common + actor extra + 1 (see there)
+__device__ __forceinline__ double anchor_bias1(int st) { return 1.0 - pow(0.9, (double)st); }
+__device__ __forceinline__ float anchor_bias2_sqrt(int st) { return (float)sqrt(1.0 - pow(0.999, (double)st)); }
 
 template <int UNROLL>
 __device__ __forceinline__ float sum_strided(const float* __restrict__ p, int64_t stride, int n) {
@@ -973,7 +1007,11 @@ __global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a
         gsq += (double)s[q] * (double)s[q];
       }
     }
-    if (a.step_counter && blockIdx.x == 0 && threadIdx.x == 0) *a.step_counter += 1;  // read by the adam kernel that follows
+    if (a.step_counter && blockIdx.x == 0 && threadIdx.x == 0) {  // read by the adam kernel that follows, with the bias corrections of the new count
+      const int step = a.step_counter[CNT_STEP] + 1;
+      a.step_counter[CNT_STEP] = step;
+      adam_record_write(a.step_counter, step, a.step_counter[CNT_EXTRA]);
+    }
     if (a.stats && blockIdx.x == 0 && threadIdx.x == 3) {  // entropy of the state-independent diagonal Gaussian
       float ent = 0.f;
       for (int k = 0; k < ACT; ++k) ent += 0.5f + LOG_SQRT_2PI + a.log_std[k];
@@ -1004,7 +1042,15 @@ __global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a
 #pragma unroll
         for (int u = 0; u < 32; ++u) part += v[u];
       }
-      for (; c < s.n; c += 8) part += s.p[(int64_t)c * s.stride];
+      // the rest, eight in flight (written `part += load` per tile it compiles to load, wait, add: one memory round trip per tile); a load
+      // past the end reads the strand's last tile and adds +0.0, which leaves the sum as it is
+      for (; c < s.n; c += 8 * 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = s.p[(int64_t)min(c + 8 * u, s.n - 1) * s.stride];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) part += c + 8 * u < s.n ? v[u] : 0.f;
+      }
     }
     red[strand][el] = part;
     __syncthreads();
@@ -1056,14 +1102,38 @@ __global__ void __launch_bounds__(256) sumsq_partials_kernel(const float* __rest
 // compiles to a different register assignment and load order than the measured one, so this form is kept.)
 // POP: grid.y = replica; p, g, m, v are [K][n], the norm partials of replica r sit at + r * r_partials, one clip norm per replica, one
 // shared step count
-constexpr int ADAM_BLOCK = 256, VEC = 1;
+constexpr int ADAM_BLOCK = 256, VEC = 1, NORM_BATCH = 4;
+// The sum of the norm partials, by one whole wave: lane l owns q = l, l + 64, ... and adds them in that order, NORM_BATCH of them in flight
+// before the first add, then the xor tree.  A load past the end reads the last partial and adds +0.0, which leaves a non-negative sum as it
+// is.  (A plain `q += 64` loop compiles to load, wait, add, branch: one exposed memory round trip per 64 partials, in front of the barrier every
+// thread of the workgroup waits at.)
+__device__ __forceinline__ double norm_partials_sum(const double* __restrict__ partials, int n_partials) {
+  double s = 0.0;
+  for (int q0 = threadIdx.x; q0 < n_partials; q0 += 64 * NORM_BATCH) {
+    double t[NORM_BATCH];
+#pragma unroll
+    for (int u = 0; u < NORM_BATCH; ++u) t[u] = partials[min(q0 + 64 * u, n_partials - 1)];
+#pragma unroll
+    for (int u = 0; u < NORM_BATCH; ++u) s += q0 + 64 * u < n_partials ? t[u] : 0.0;
+  }
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  return s;
+}
 template <bool POP = false>
 __global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                   int64_t n, const double* __restrict__ partials, int n_partials, float lr, float eps, float max_norm,
-                                                   float bc1, float bc2_sqrt, const ParamLayout L, const Packed k_, int zero_grad,
-                                                   const int* __restrict__ step_counter, int host_step, const int* __restrict__ actor_extra,
-                                                   unsigned r_partials, const float* __restrict__ hparams) {
+                                                   int64_t n, const double* __restrict__ partials, int n_partials, int host_step,
+                                                   const int* __restrict__ cnt, float lr, float eps, float max_norm, float bc1, float bc2_sqrt,
+                                                   int zero_grad, unsigned r_partials, const float* __restrict__ hparams, const ParamLayout L,
+                                                   const Packed k_) {
+  // (argument order: what the loads and the norm need stands in front of the two structs, which are read behind the reduction)
   __shared__ float scale_s;
+  // the counts and the record (kp1_mlp::step_dev, uniform loads, none of them behind a branch): host_step > 0 is the caller's step count, with
+  // bc1 / bc2_sqrt its corrections; otherwise the count is the device's and the corrections are the record's
+  const int dev_step = cnt[CNT_STEP], extra = cnt[CNT_EXTRA];
+  const int step = host_step > 0 ? host_step : dev_step;
+  const int rec_step = cnt[REC_STEP], rec_extra = cnt[REC_EXTRA];
+  const float rec_bc1 = __int_as_float(cnt[REC_BC]), rec_bc2_sqrt = __int_as_float(cnt[REC_BC + 1]);
+  const float rec_bc1_a = __int_as_float(cnt[REC_BC + 2]), rec_bc2_sqrt_a = __int_as_float(cnt[REC_BC + 3]);
   const Packed k = POP ? packed_replica(k_, L, blockIdx.y) : k_;
   if constexpr (POP) {
     const unsigned o = blockIdx.y * (unsigned)n;
@@ -1085,29 +1155,20 @@ __global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(float* __restrict__ p,
     const int64_t il = i0 + j < n ? i0 + j : n - 1;
     g_in[j] = g[il]; m_in[j] = m[il]; v_in[j] = v[il]; p_in[j] = p[il];
   }
-  const int extra = *actor_extra;
-  float base_step = (float)host_step;
-  if (step_counter) base_step = (float)*step_counter;
   double s = 0.0;
-  if (threadIdx.x < 64) {
-    for (int q = threadIdx.x; q < n_partials; q += 64) s += partials[q];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  }
+  if (threadIdx.x < 64) s = norm_partials_sum(partials, n_partials);
   if (threadIdx.x == 0) {
     const float norm = (float)sqrt(s);
     scale_s = max_norm > 0.f ? fminf(max_norm / (norm + 1e-6f), 1.f) : 1.f;
   }
-  if (step_counter) {  // bias corrections from the device-resident step count
-    bc1 = 1.f - powf(0.9f, base_step);
-    bc2_sqrt = sqrtf(1.f - powf(0.999f, base_step));
-  }
-  // torch.optim.Adam keeps one step count per tensor: the actor tensors (policy_net.*, action_net.*) have taken *actor_extra
+  // torch.optim.Adam keeps one step count per tensor: the actor tensors (policy_net.*, action_net.*) have taken `extra`
   // more steps than the rest when a teacher-anchor side loss updates them between rollouts (route/teacher_anchor.py:68-87)
-  float bc1_a = bc1, bc2_sqrt_a = bc2_sqrt;
-  if (extra != 0) {
-    const float st = base_step + (float)extra;
-    bc1_a = 1.f - powf(0.9f, st);
-    bc2_sqrt_a = sqrtf(1.f - powf(0.999f, st));
+  float bc1_a, bc2_sqrt_a;
+  if (host_step <= 0 && rec_step == step && rec_extra == extra) {   // the launch that advanced the count left the corrections (uniform branch)
+    bc1 = rec_bc1; bc2_sqrt = rec_bc2_sqrt; bc1_a = rec_bc1_a; bc2_sqrt_a = rec_bc2_sqrt_a;
+  } else {   // a count the host set since, or the caller's
+    if (host_step <= 0) adam_bias((float)step, bc1, bc2_sqrt);
+    adam_bias_actor((float)step, extra, bc1, bc2_sqrt, bc1_a, bc2_sqrt_a);
   }
   __syncthreads();
   const float scale = scale_s;
@@ -1261,9 +1322,10 @@ __device__ __forceinline__ bool is_actor_element(const ParamLayout& L, int64_t i
 
 // The anchor gradient in SB3 order: an actor element is the fixed-order sum of its producers' partials (finalize_source: the same places
 // grad_finalize_kernel reads), every other element is written as 0.  Block b leaves the f64 sum of squares of what it wrote in sumsq[b]
-// (the norm of the six actor tensors: the rest is zero), thread 0 of block 0 sums the loss partials.  Does not touch the step count.
+// (the norm of the six actor tensors: the rest is zero), thread 0 of block 0 sums the loss partials.  Does not touch the step count: it
+// reads the counts and leaves the bias corrections of the Adam launch that follows in the record behind them.
 struct AnchorFinalizeArgs {
-  FinalizeArgs f;      // stats, step_counter, hparams unused (NULL); sumsq = the handle's anchor partials
+  FinalizeArgs f;      // stats, hparams unused (NULL); step_counter = the handle's counts, read only; sumsq = the handle's anchor partials
   float* loss_out;     // [K]
 };
 
@@ -1285,6 +1347,14 @@ __global__ void __launch_bounds__(256) anchor_finalize_kernel(const AnchorFinali
     float t = 0.f;
     for (int c = 0; c < a.h_n; ++c) t += a.hpart[(int64_t)c * a.h_stride + 10 * L.Hp + 15];
     a_.loss_out[POP ? blockIdx.y : 0u] = t;
+  }
+  // the bias corrections of the anchor_adam_kernel launch that follows, on the device's counts (replica 0, in another wave than the loss sum)
+  if (a.step_counter && blockIdx.x == 0 && threadIdx.x == 64) {
+    int* cnt = a.step_counter;
+    const int st = cnt[CNT_STEP] + cnt[CNT_EXTRA] + 1;
+    *reinterpret_cast<double*>(cnt + AREC_BC1) = anchor_bias1(st);
+    cnt[AREC_BC2] = __float_as_int(anchor_bias2_sqrt(st));
+    cnt[AREC_ST] = st;
   }
   double w = (double)gval * (double)gval;
   for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off);
@@ -1319,16 +1389,18 @@ __global__ void __launch_bounds__(ADAM_BLOCK) anchor_adam_kernel(float* __restri
   const int64_t il = actor ? i : L.p_w1;   // the loads go out before the norm is known; threads without an element read a valid one
   const float g_in = g[il], m_in = m[il], v_in = v[il], p_in = p[il];
   double s = 0.0;
-  if (threadIdx.x < 64) {
-    for (int q = threadIdx.x; q < n_partials; q += 64) s += partials[q];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  }
+  if (threadIdx.x < 64) s = norm_partials_sum(partials, n_partials);
   if (threadIdx.x == 0) {
     const float norm = (float)sqrt(s);
-    const int st = (host_step > 0 ? host_step : step_dev[0]) + step_dev[1] + 1;
+    const int st = (host_step > 0 ? host_step : step_dev[CNT_STEP]) + step_dev[CNT_EXTRA] + 1;
     sh[0] = max_norm > 0.f ? fminf(max_norm / (norm + 1e-6f), 1.f) : 1.f;
-    sh[1] = (float)((double)lr / (1.0 - pow(0.9, (double)st)));
-    sh[2] = (float)sqrt(1.0 - pow(0.999, (double)st));
+    if (step_dev[AREC_ST] == st) {   // anchor_finalize_kernel left the corrections of this count (uniform branch)
+      sh[1] = (float)((double)lr / *reinterpret_cast<const double*>(step_dev + AREC_BC1));
+      sh[2] = __int_as_float(step_dev[AREC_BC2]);
+    } else {   // a step count given by the caller that is not the device's
+      sh[1] = (float)((double)lr / anchor_bias1(st));
+      sh[2] = anchor_bias2_sqrt(st);
+    }
   }
   __syncthreads();
   if (actor) {
@@ -1343,7 +1415,11 @@ __global__ void __launch_bounds__(ADAM_BLOCK) anchor_adam_kernel(float* __restri
 }
 
 // the actor tensors have taken one more step than the rest: a launch of its own, after every block of anchor_adam_kernel has read the count
-__global__ void anchor_count_kernel(int* __restrict__ actor_extra) { *actor_extra += 1; }
+__global__ void anchor_count_kernel(int* __restrict__ cnt) {
+  const int extra = cnt[CNT_EXTRA] + 1;
+  cnt[CNT_EXTRA] = extra;
+  adam_record_write(cnt, cnt[CNT_STEP], extra);   // an Adam launch on the device's counts finds its corrections whichever launch came last
+}
 
 #include "kp1_env_step.inc"
 #include "kp1_eval_step.inc"
@@ -1384,7 +1460,7 @@ struct kp1_mlp {
   float* bslab = nullptr;      // [max_batch/64 row tiles][2 nets][Hp] partial db1
   float* hpart = nullptr;      // [max_batch/32 blocks][10 Hp + 32] head partials
   int n_finalize_blocks = 0;   // sum-of-squares partials written by the last grad_finalize_kernel
-  int* step_dev = nullptr;     // device Adam step counter
+  int* step_dev = nullptr;     // device Adam step counts and the record of their bias corrections (CNT_*, REC_*, AREC_*)
   // population: per-replica hyper-parameter table [K][HP_FIELDS] (kp1_mlp_set_replica_hparams); the kernels read it while hparams_on
   float* hparams_dev = nullptr;
   bool hparams_on = false;
@@ -1845,7 +1921,7 @@ int mlp_create(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batc
   if (Hp == 128) MLP_ALLOC(m->anchor_partials, K * ANCHOR_PARTIALS);
   MLP_ALLOC(m->slab, K * 64 * 2 * Hp * Hp);
   MLP_ALLOC(m->slab1, K * 64 * 2 * Hp * INP);
-  MLP_ALLOC(m->step_dev, 4);
+  MLP_ALLOC(m->step_dev, STEP_DEV_INTS);
   if (K > 1) MLP_ALLOC(m->hparams_dev, K * HP_FIELDS);
   MLP_ALLOC(m->bslab, K * (mb / 32) * 2 * Hp);
   MLP_ALLOC(m->hpart, K * (mb / 32) * (10 * Hp + 32));
@@ -2747,11 +2823,10 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   kfmt.formats = frag_only ? PACK_FRAG : (PACK_SLAB | PACK_FRAG);
   m->last_params = params;
   if (frag_only) m->slab_stale = true;
-  const int* step_arg = step > 0 ? (const int*)nullptr : (const int*)m->step_dev;
   auto* kernel = pop ? adam_kernel<true> : adam_kernel<false>;
   KP1_LAUNCH(kernel, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK), m->K), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
-             n_norm_partials, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), m->L, kfmt, zero_grad, step_arg, host_step, (const int*)m->step_dev + 1, r_partials,
-             hparams);
+             n_norm_partials, step > 0 ? step : 0, (const int*)m->step_dev, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), zero_grad, r_partials, hparams,
+             m->L, kfmt);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
@@ -2799,6 +2874,7 @@ int kp1_mlp_anchor_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, c
   fill_finalize(f, m, n, s2_n, s1_n, grad_out);
   f.sumsq = m->anchor_partials;
   f.r_sumsq = (unsigned)ANCHOR_PARTIALS;
+  f.step_counter = m->step_dev;
   fa.loss_out = loss_out;
   hipLaunchKernelGGL(pop ? anchor_finalize_kernel<true> : anchor_finalize_kernel<false>, dim3(n_blocks, m->K), dim3(256), 0, stream, fa);
   HIP_TRY(kp1::launch_status());
@@ -2821,7 +2897,7 @@ int kp1_mlp_anchor_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_
   hipLaunchKernelGGL(pop ? anchor_adam_kernel<true> : anchor_adam_kernel<false>, dim3(n_blocks, m->K), dim3(ADAM_BLOCK), 0, stream, params, (const float*)grad,
                      exp_avg, exp_avg_sq, (const double*)m->anchor_partials, n_blocks, lr, eps, max_grad_norm, m->L, kfmt, (const int*)m->step_dev, (int)step,
                      pop ? (unsigned)ANCHOR_PARTIALS : 0u, pop && m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr);
-  hipLaunchKernelGGL(anchor_count_kernel, dim3(1), dim3(1), 0, stream, m->step_dev + 1);
+  hipLaunchKernelGGL(anchor_count_kernel, dim3(1), dim3(1), 0, stream, m->step_dev);
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
