@@ -417,6 +417,46 @@ int kp1_mlp_time_kernels(kp1_mlp* m, const float* obs, int32_t obs_stride, int32
 /* make kp1_step / kp1_reset write observation rows with this stride (56 default, 64 = MFMA-friendly, zero padded) */
 int kp1_set_obs_stride(kp1_env* env, int32_t stride);
 
+/* ---- device-resident training monitor: SB3's episode statistics (common/monitor.py Monitor.step +
+ * OnPolicyAlgorithm._update_info_buffer) and explained variance, fed from the rollout buffers --------------------
+ * make_vec_env wraps every env in a Monitor, which sums an episode's rewards and counts its steps; when the episode ends
+ * the (return, length) pair enters ep_info_buffer, a deque(maxlen = stats_window_size), whose mean SB3 logs as
+ * rollout/ep_rew_mean and rollout/ep_len_mean.  Here K replicas x N envs keep that state on the device: per env a carry (running return
+ * as double, running length as int32), per replica one kp1_monitor_state -- the ring of the newest `window` episodes and two totals. */
+#define KP1_MONITOR_MAX_WINDOW 1024
+#define KP1_MONITOR_MAX_STEPS 4096   /* largest max_steps of a handle (twice the longest n_steps of a committed config) */
+typedef struct kp1_monitor_state {
+  int32_t window, ring_len, ring_head, reserved0;   /* live entries: the ring_len slots from ring_head on (ring_head is 0 while the ring fills) */
+  int64_t total_episodes, total_successes;
+  double  ring_return[KP1_MONITOR_MAX_WINDOW];
+  int32_t ring_length[KP1_MONITOR_MAX_WINDOW];
+  uint8_t ring_success[KP1_MONITOR_MAX_WINDOW];
+} kp1_monitor_state;
+typedef struct kp1_monitor kp1_monitor;
+
+/* window in [1, KP1_MONITOR_MAX_WINDOW] (SB3's stats_window_size, default 100), n_replicas in [1, KP1_CURRICULUM_MAX_REPLICAS],
+ * n_per_replica >= 1, max_steps in [1, KP1_MONITOR_MAX_STEPS] = the largest T of an observe call (sizes the scratch). */
+int kp1_monitor_create(int32_t device, int32_t n_replicas, int32_t n_per_replica, int32_t window, int32_t max_steps, kp1_monitor** out);
+int kp1_monitor_destroy(kp1_monitor* mon);
+/* Feed T env steps: rewards f32 and dones u8 (KP1_DONE_* bits), both [T][K N], time-major with replica-major columns (the rollout buffers),
+ * 1 <= T <= max_steps.  Env i's episode ends at step t when dones[t][i] & (TERMINATED | TRUNCATED) (kp1_gae_scan's test); its return is the
+ * carry plus the rewards of its steps, each widened to double and added in step order, its length the number of those steps, its success
+ * KP1_DONE_SUCCESS of that byte; then the carry is zero again.  Replica k's episodes of the call enter its ring in (t, then env index)
+ * order -- the order the reference's callbacks and SB3's deque see -- and the ring keeps the newest `window`.  Two calls over [0, a) and
+ * [a, T) leave the states and carries exactly as one call over [0, T).  Two launches, no float atomics, one writer per element. */
+int kp1_monitor_observe(kp1_monitor* mon, const float* rewards, const uint8_t* dones, int32_t T, void* stream);
+/* clear the carries (after an explicit env reset: the running episodes were abandoned); rings and totals stay */
+int kp1_monitor_reset_carry(kp1_monitor* mon, void* stream);
+/* copy replica `replica`'s state to the host (waits for the stream) */
+int kp1_monitor_read(kp1_monitor* mon, int32_t replica, kp1_monitor_state* out_host, void* stream);
+
+/* stable_baselines3.common.utils.explained_variance's two variances per replica, in ONE launch: values / returns f32 [T][n_total] (the same
+ * layout; n_total = K n_per_replica), out f64 [K][2] (device) = (var(returns), var(returns - values)), population variances (np.var) of
+ * the inputs widened to double, accumulated in double as (sum, sum of squares) of the data shifted by the replica's first element, in a
+ * fixed order.  The host forms 1 - var_diff / var_y, nan when var_y == 0.  T * n_total < 2^31. */
+int kp1_explained_variance(int32_t device, const float* values, const float* returns, int32_t T, int32_t n_total, int32_t n_per_replica,
+                           double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -618,3 +618,280 @@ int kp1_curriculum_read(int32_t device, const kp1_curriculum_state* st_dev, kp1_
 }
 
 }  // extern "C"
+
+// ---- training monitor (include/kp1_ppo.h: kp1_monitor_*, kp1_explained_variance) ---------------------------------------------------------
+// SB3's Monitor + ep_info_buffer on the device.  An observe call is two launches:
+//   monitor_scan_kernel   one lane per env column, coalesced across a row like the GAE scan: walks t forward with the env's carry in
+//                         registers and leaves (return, length) at every position where an episode ends, in a [max_steps][K N] scratch;
+//   monitor_rank_kernel   one workgroup per replica: counts the ends of every row (ballots), prefix-sums the row counts in LDS, and gives the
+//                         episode at (t, env) the rank (ends of earlier rows) + (ends before it in its row), which is its place in the
+//                         (t, env) order; entry j of the call lands in ring slot (head + len + j) mod window, and only the newest `window`
+//                         entries are written, so every slot has one writer.
+// Nothing waits on another workgroup, every loop is bounded by T, N or the window, and the only arithmetic on a return is the scan's
+// sequential double add.
+struct kp1_monitor {
+  int device, K, N, window, max_steps;
+  kp1_monitor_state* states;   // [K]
+  double* carry_ret;           // [K N]
+  int32_t* carry_len;          // [K N]
+  double* ep_ret;              // [max_steps][K N], defined where an episode ended in the last observe call
+  int32_t* ep_len;
+};
+
+namespace {
+
+__global__ void __launch_bounds__(64) monitor_scan_kernel(const float* __restrict__ rewards, const uint8_t* __restrict__ dones,
+                                                          double* __restrict__ carry_ret, int32_t* __restrict__ carry_len,
+                                                          double* __restrict__ ep_ret, int32_t* __restrict__ ep_len, int T, int KN) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= KN) return;
+  double ret = carry_ret[i];
+  int len = carry_len[i];
+#pragma unroll 4
+  for (int t = 0; t < T; ++t) {
+    const int64_t p = (int64_t)t * KN + i;
+    ret += (double)rewards[p];
+    len += 1;
+    if (dones[p] & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) {
+      ep_ret[p] = ret;
+      ep_len[p] = len;
+      ret = 0.0;
+      len = 0;
+    }
+  }
+  carry_ret[i] = ret;
+  carry_len[i] = len;
+}
+
+constexpr int MON_THREADS = 1024, MON_WAVES = MON_THREADS / 64;
+
+__global__ void __launch_bounds__(MON_THREADS) monitor_rank_kernel(kp1_monitor_state* __restrict__ states, const uint8_t* __restrict__ dones,
+                                                                   const double* __restrict__ ep_ret, const int32_t* __restrict__ ep_len, int T,
+                                                                   int N, int KN) {
+  __shared__ int row_off[KP1_MONITOR_MAX_STEPS + 1];   // ends per row, then their exclusive prefix; [T] = all ends of the call
+  __shared__ int wave_succ[MON_WAVES];
+  __shared__ int hdr[3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t col0 = (int64_t)blockIdx.x * N;
+  kp1_monitor_state* __restrict__ st = states + blockIdx.x;
+  if (threadIdx.x == 0) {
+    hdr[0] = st->window;
+    hdr[1] = st->ring_len;
+    hdr[2] = st->ring_head;
+  }
+  // ends (and successes among them) of every row; wave w takes rows w, w + MON_WAVES, ...
+  int succ = 0;
+  for (int t = wave; t < T; t += MON_WAVES) {
+    const uint8_t* __restrict__ row = dones + (int64_t)t * KN + col0;
+    int cnt = 0;
+    for (int base = 0; base < N; base += 64) {
+      const int c = base + lane;
+      const uint8_t b = c < N ? row[c] : (uint8_t)0;
+      const bool end = (b & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) != 0;
+      cnt += __popcll(__ballot(end));
+      succ += __popcll(__ballot(end && (b & KP1_DONE_SUCCESS)));
+    }
+    if (lane == 0) row_off[t] = cnt;
+  }
+  if (lane == 0) wave_succ[wave] = succ;
+  __syncthreads();
+  if (wave == 0) {
+    int running = 0;
+    for (int base = 0; base < T; base += 64) {
+      const int t = base + lane;
+      const int v = t < T ? row_off[t] : 0;
+      int inc = v;
+      for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(inc, d);
+        if (lane >= d) inc += up;
+      }
+      if (t < T) row_off[t] = running + inc - v;
+      running += __shfl(inc, 63);
+    }
+    if (lane == 0) row_off[T] = running;
+  }
+  __syncthreads();
+  const int E = row_off[T];
+  if (E == 0) return;                                    // no episode ended: the state keeps every byte
+  const int W = hdr[0], len0 = hdr[1], head0 = hdr[2];
+  const int skip = E > W ? E - W : 0;                    // older entries of the call would be overwritten by its newer ones
+  const unsigned first_slot = (unsigned)(head0 + len0);
+  for (int t = wave; t < T; t += MON_WAVES) {
+    const int off = row_off[t], cnt = row_off[t + 1] - off;
+    if (cnt == 0 || off + cnt <= skip) continue;         // wave-uniform
+    const int64_t p0 = (int64_t)t * KN + col0;
+    int running = off;
+    for (int base = 0; base < N; base += 64) {
+      const int c = base + lane;
+      const uint8_t b = c < N ? dones[p0 + c] : (uint8_t)0;
+      const bool end = (b & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) != 0;
+      const unsigned long long m = __ballot(end);
+      const int rank = running + __popcll(m & ((1ull << lane) - 1ull));
+      if (end && rank >= skip) {
+        const unsigned slot = (first_slot + (unsigned)rank) % (unsigned)W;
+        st->ring_return[slot] = ep_ret[p0 + c];
+        st->ring_length[slot] = ep_len[p0 + c];
+        st->ring_success[slot] = (b & KP1_DONE_SUCCESS) ? (uint8_t)1 : (uint8_t)0;
+      }
+      running += __popcll(m);
+    }
+  }
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < MON_WAVES; ++w) s += wave_succ[w];
+    const long long filled = (long long)len0 + E;
+    if (filled > W) {
+      st->ring_head = (int)(((long long)head0 + (filled - W)) % W);
+      st->ring_len = W;
+    } else {
+      st->ring_len = (int)filled;
+    }
+    st->total_episodes += E;
+    st->total_successes += s;
+  }
+}
+
+// One workgroup per replica; thread j takes elements j, j + 1024, ... of the replica's T * N (element e = row e / N, column e % N), then a
+// fixed LDS tree: the same sums in the same order on every run.  Shifting by the replica's first element keeps the single-pass form
+// well conditioned (and makes a constant buffer's variance exactly 0).
+__global__ void __launch_bounds__(1024) explained_variance_kernel(const float* __restrict__ values, const float* __restrict__ returns, int T, int KN,
+                                                                  int N, double* __restrict__ out) {
+  __shared__ double sums[4][1024];
+  const int total = T * N;
+  const int64_t col0 = (int64_t)blockIdx.x * N;
+  const double y0 = (double)returns[col0], d0 = y0 - (double)values[col0];
+  double sy = 0.0, syy = 0.0, sd = 0.0, sdd = 0.0;
+  for (int e = threadIdx.x; e < total; e += 1024) {
+    const int t = e / N, c = e - t * N;
+    const int64_t p = (int64_t)t * KN + col0 + c;
+    const double y = (double)returns[p];
+    const double ys = y - y0, ds = (y - (double)values[p]) - d0;
+    sy += ys;
+    syy += ys * ys;
+    sd += ds;
+    sdd += ds * ds;
+  }
+  sums[0][threadIdx.x] = sy;
+  sums[1][threadIdx.x] = syy;
+  sums[2][threadIdx.x] = sd;
+  sums[3][threadIdx.x] = sdd;
+  __syncthreads();
+  for (int k = 512; k > 0; k >>= 1) {
+    if (threadIdx.x < k)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sums[q][threadIdx.x] += sums[q][threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double n = (double)total;
+    const double var_y = (sums[1][0] - sums[0][0] * sums[0][0] / n) / n, var_d = (sums[3][0] - sums[2][0] * sums[2][0] / n) / n;
+    out[2 * blockIdx.x] = var_y < 0.0 ? 0.0 : var_y;
+    out[2 * blockIdx.x + 1] = var_d < 0.0 ? 0.0 : var_d;
+  }
+}
+
+void monitor_free(kp1_monitor* m) {
+  (void)hipFree(m->states);
+  (void)hipFree(m->carry_ret);
+  (void)hipFree(m->carry_len);
+  (void)hipFree(m->ep_ret);
+  (void)hipFree(m->ep_len);
+  delete m;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kp1_monitor_create(int32_t device, int32_t n_replicas, int32_t n_per_replica, int32_t window, int32_t max_steps, kp1_monitor** out) {
+  if (!out) return fail(KP1_ERR_INVALID, "kp1_monitor_create: NULL argument");
+  if (n_replicas < 1 || n_replicas > KP1_CURRICULUM_MAX_REPLICAS)
+    return fail(KP1_ERR_INVALID, "kp1_monitor_create: n_replicas must be in [1, KP1_CURRICULUM_MAX_REPLICAS]");
+  if (n_per_replica < 1) return fail(KP1_ERR_INVALID, "kp1_monitor_create: n_per_replica must be at least 1");
+  if (window < 1 || window > KP1_MONITOR_MAX_WINDOW) return fail(KP1_ERR_INVALID, "kp1_monitor_create: window must be in [1, KP1_MONITOR_MAX_WINDOW]");
+  if (max_steps < 1 || max_steps > KP1_MONITOR_MAX_STEPS) return fail(KP1_ERR_INVALID, "kp1_monitor_create: max_steps must be in [1, KP1_MONITOR_MAX_STEPS]");
+  const int64_t kn = (int64_t)n_replicas * n_per_replica;
+  if (kn * max_steps >= ((int64_t)1 << 31)) return fail(KP1_ERR_INVALID, "kp1_monitor_create: max_steps * n_replicas * n_per_replica must stay below 2^31");
+  int rc = check_device(device);
+  if (rc != KP1_OK) return rc;
+  kp1_monitor* m = new kp1_monitor();
+  m->device = device; m->K = n_replicas; m->N = n_per_replica; m->window = window; m->max_steps = max_steps;
+  m->states = nullptr; m->carry_ret = nullptr; m->carry_len = nullptr; m->ep_ret = nullptr; m->ep_len = nullptr;
+  std::vector<kp1_monitor_state> h((size_t)n_replicas);
+  std::memset(h.data(), 0, sizeof(kp1_monitor_state) * h.size());
+  for (auto& s : h) s.window = window;
+  hipError_t e = hipMalloc((void**)&m->states, sizeof(kp1_monitor_state) * h.size());
+  if (e == hipSuccess) e = hipMalloc((void**)&m->carry_ret, sizeof(double) * (size_t)kn);
+  if (e == hipSuccess) e = hipMalloc((void**)&m->carry_len, sizeof(int32_t) * (size_t)kn);
+  if (e == hipSuccess) e = hipMalloc((void**)&m->ep_ret, sizeof(double) * (size_t)(kn * max_steps));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->ep_len, sizeof(int32_t) * (size_t)(kn * max_steps));
+  if (e == hipSuccess) e = hipMemcpy(m->states, h.data(), sizeof(kp1_monitor_state) * h.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(m->carry_ret, 0, sizeof(double) * (size_t)kn);
+  if (e == hipSuccess) e = hipMemset(m->carry_len, 0, sizeof(int32_t) * (size_t)kn);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    monitor_free(m);
+    return fail(kp1::status_of(e), std::string("kp1_monitor_create: ") + hipGetErrorString(e));
+  }
+  *out = m;
+  return KP1_OK;
+}
+
+int kp1_monitor_destroy(kp1_monitor* mon) {
+  if (!mon) return fail(KP1_ERR_INVALID, "kp1_monitor_destroy: NULL argument");
+  int rc = check_device(mon->device);
+  if (rc != KP1_OK) return rc;
+  monitor_free(mon);
+  return KP1_OK;
+}
+
+int kp1_monitor_observe(kp1_monitor* mon, const float* rewards, const uint8_t* dones, int32_t T, void* stream) {
+  if (!mon || !rewards || !dones) return fail(KP1_ERR_INVALID, "kp1_monitor_observe: NULL argument");
+  if (T < 1 || T > mon->max_steps) return fail(KP1_ERR_INVALID, "kp1_monitor_observe: T must be in [1, max_steps of the handle]");
+  int rc = check_device(mon->device);
+  if (rc != KP1_OK) return rc;
+  const int KN = mon->K * mon->N;
+  hipLaunchKernelGGL(monitor_scan_kernel, dim3((unsigned)((KN + 63) / 64)), dim3(64), 0, (hipStream_t)stream, rewards, dones, mon->carry_ret,
+                     mon->carry_len, mon->ep_ret, mon->ep_len, (int)T, KN);
+  HIP_TRY(kp1::launch_status());
+  hipLaunchKernelGGL(monitor_rank_kernel, dim3((unsigned)mon->K), dim3(MON_THREADS), 0, (hipStream_t)stream, mon->states, dones, mon->ep_ret,
+                     mon->ep_len, (int)T, mon->N, KN);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_monitor_reset_carry(kp1_monitor* mon, void* stream) {
+  if (!mon) return fail(KP1_ERR_INVALID, "kp1_monitor_reset_carry: NULL argument");
+  int rc = check_device(mon->device);
+  if (rc != KP1_OK) return rc;
+  const size_t kn = (size_t)mon->K * (size_t)mon->N;
+  HIP_TRY(hipMemsetAsync(mon->carry_ret, 0, sizeof(double) * kn, (hipStream_t)stream));
+  HIP_TRY(hipMemsetAsync(mon->carry_len, 0, sizeof(int32_t) * kn, (hipStream_t)stream));
+  return KP1_OK;
+}
+
+int kp1_monitor_read(kp1_monitor* mon, int32_t replica, kp1_monitor_state* out_host, void* stream) {
+  if (!mon || !out_host) return fail(KP1_ERR_INVALID, "kp1_monitor_read: NULL argument");
+  if (replica < 0 || replica >= mon->K) return fail(KP1_ERR_INVALID, "kp1_monitor_read: replica index out of range");
+  int rc = check_device(mon->device);
+  if (rc != KP1_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(out_host, mon->states + replica, sizeof *out_host, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return KP1_OK;
+}
+
+int kp1_explained_variance(int32_t device, const float* values, const float* returns, int32_t T, int32_t n_total, int32_t n_per_replica,
+                           double* out, void* stream) {
+  if (!values || !returns || !out) return fail(KP1_ERR_INVALID, "kp1_explained_variance: NULL argument");
+  if (T < 1 || n_total < 1 || n_per_replica < 1 || n_total % n_per_replica != 0)
+    return fail(KP1_ERR_INVALID, "kp1_explained_variance: T and n_total must be positive and n_total a multiple of n_per_replica");
+  if ((int64_t)T * n_total >= ((int64_t)1 << 31)) return fail(KP1_ERR_INVALID, "kp1_explained_variance: T * n_total must stay below 2^31");
+  int rc = check_device(device);
+  if (rc != KP1_OK) return rc;
+  hipLaunchKernelGGL(explained_variance_kernel, dim3((unsigned)(n_total / n_per_replica)), dim3(1024), 0, (hipStream_t)stream, values, returns,
+                     (int)T, (int)n_total, (int)n_per_replica, out);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+}  // extern "C"

@@ -34,6 +34,18 @@ class RouteChainView(C.Structure):
     _fields_ = [("records", C.c_void_p), ("n_records", C.c_void_p), ("n_alive", C.c_void_p), ("n_rows", C.c_int32), ("max_len", C.c_int32)]
 
 
+MONITOR_MAX_WINDOW = 1024    # include/kp1_ppo.h KP1_MONITOR_MAX_WINDOW
+MONITOR_MAX_STEPS = 4096     # include/kp1_ppo.h KP1_MONITOR_MAX_STEPS
+
+
+class MonitorState(C.Structure):
+    """include/kp1_ppo.h kp1_monitor_state: one replica's ring of the newest `window` episodes and its totals"""
+    _fields_ = [("window", C.c_int32), ("ring_len", C.c_int32), ("ring_head", C.c_int32), ("reserved0", C.c_int32),
+                ("total_episodes", C.c_int64), ("total_successes", C.c_int64),
+                ("ring_return", C.c_double * MONITOR_MAX_WINDOW), ("ring_length", C.c_int32 * MONITOR_MAX_WINDOW),
+                ("ring_success", C.c_uint8 * MONITOR_MAX_WINDOW)]
+
+
 class Kp1Error(RuntimeError):
     pass
 
@@ -132,6 +144,12 @@ def load() -> C.CDLL:
     L.kp1_rollout_run.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     L.kp1_mlp_anchor_loss_grad.argtypes = [vp, vp, i32, vp, i32, vp, f32, vp, vp, vp]
     L.kp1_mlp_anchor_adam_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, i32, vp]
+    L.kp1_monitor_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
+    L.kp1_monitor_destroy.argtypes = [vp]
+    L.kp1_monitor_observe.argtypes = [vp, vp, vp, i32, vp]
+    L.kp1_monitor_reset_carry.argtypes = [vp, vp]
+    L.kp1_monitor_read.argtypes = [vp, i32, C.POINTER(MonitorState), vp]
+    L.kp1_explained_variance.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp]
     if L.kp1_config_size() != C.sizeof(kcfg.Kp1Config):
         raise Kp1Error(f"kp1_config layout mismatch: library {L.kp1_config_size()} vs binding {C.sizeof(kcfg.Kp1Config)}")
     _lib = L

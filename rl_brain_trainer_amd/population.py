@@ -138,7 +138,7 @@ class PopulationPPO(PPO):
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env_factory: Callable[[int], Any], *,
                  curriculum_factory: Callable[[int], Any] | None = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:
+                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None, monitor: bool | int = False) -> None:
         seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides)
         envs: list[Any] = []
         try:
@@ -156,7 +156,7 @@ class PopulationPPO(PPO):
                 e.close()
             raise
         curricula = [curriculum_factory(s) if curriculum_factory is not None else None for s in seeds]
-        self._init_population(seeds, cfg, envs, curricula, dist, use_graphs, overrides)
+        self._init_population(seeds, cfg, envs, curricula, dist, use_graphs, overrides, monitor=monitor)
 
     @staticmethod
     def _check_population_args(seeds: list[int], cfg: PPOConfig, dist: Dist | None, teacher_anchor: Any,
@@ -188,13 +188,13 @@ class PopulationPPO(PPO):
         return seeds, dist, overrides
 
     def _init_population(self, seeds: list[int], cfg: PPOConfig, envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool,
-                         overrides: list[dict[str, float]] | None = None, *, min_batch: int = 0) -> None:
+                         overrides: list[dict[str, float]] | None = None, *, min_batch: int = 0, monitor: bool | int = False) -> None:
         """what a population holds once its K env views and trackers exist (``min_batch``: rows the MLP handle must hold besides its own needs)"""
         T, N, K = cfg.n_steps, envs[0].n_envs, len(seeds)
         max_steps = max(int(envs[0].config.c.termination.max_episode_steps), 1)
         self._trunc_cap = min(N * (T // max_steps + 1), T * N)
         # the MLP handle's max_batch holds the `_trunc_cap` rows per replica of the bootstrap's one forward
-        self._setup(cfg, seeds, envs, curricula, dist, use_graphs, min_batch=max(self._trunc_cap, int(min_batch)), stacked=True)
+        self._setup(cfg, seeds, envs, curricula, dist, use_graphs, min_batch=max(self._trunc_cap, int(min_batch)), stacked=True, monitor=monitor)
         self.seeds = seeds
         self.overrides = overrides if overrides is not None else [{} for _ in seeds]
         # a population with overrides keeps its per-replica constants on the device: the MLP handle's hyper-parameter table, (gamma, lambda)
@@ -231,6 +231,8 @@ class PopulationPPO(PPO):
         for e in self.envs:
             e.close()
         self._mlp.close()
+        if self.monitor is not None:
+            self.monitor.close()
 
     def infer_policy(self, k: int):
         """a K = 1 inference handle on replica k's current parameters (for predict / the evaluators)"""
@@ -297,6 +299,7 @@ class PopulationPPO(PPO):
             super()._post_rollout()
             return
         T, N, KN = self.cfg.n_steps, self.n_envs, self.K * self.n_envs
+        self._monitor_observe()
         self._bootstrap_truncated()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         last_v = torch.empty(KN, dtype=torch.float32, device=self.device)
@@ -305,6 +308,7 @@ class PopulationPPO(PPO):
                                                   C.c_void_p(self.done_buf.data_ptr()), C.c_void_p(last_v.data_ptr()),
                                                   C.c_void_p(self._gamma_lambda.data_ptr()), N, C.c_void_p(self.adv_buf.data_ptr()),
                                                   C.c_void_p(self.ret_buf.data_ptr()), T, KN, C.c_void_p(stream)))
+        self._monitor_explained_variance()
 
     # ------------------------------------------------------------------ update
     def _epoch_body(self) -> None:
@@ -353,6 +357,7 @@ class OneHandlePopulationPPO(PopulationPPO):
     def _reset_envs(self, which: list[int] | None = None) -> None:
         if which is None or which:
             self.obs_buf[0].copy_(self.pop_env.reset())
+            self._monitor_reset_carry()
 
     # whether the env handle is one kp1_mlp_forward_env_step steps (ApproachPopulationPPO, DockPopulationPPO: an ArmKinematicPopulationVecEnv;
     # the route env has no kp1_env step of its own and the 80-float observation, so RoutePopulationPPO keeps the launch sequence)
@@ -511,7 +516,7 @@ class ApproachPopulationPPO(OneHandlePopulationPPO):
         return True
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:
+                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None, monitor: bool | int = False) -> None:
         from .curriculum import PointCurriculumPopulation
         from .vec_env import ArmKinematicPopulationVecEnv
 
@@ -530,7 +535,7 @@ class ApproachPopulationPPO(OneHandlePopulationPPO):
         K = len(seeds)
         views = [env.replica(k) for k in range(K)]
         curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
-        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides)
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides, monitor=monitor)
 
 
 class RoutePopulationPPO(OneHandlePopulationPPO):
@@ -547,7 +552,7 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
     fused_route_env_type_ok = True
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:
+                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None, monitor: bool | int = False) -> None:
         from .route_curriculum import RoutePrefixCurriculumPopulation
         from .route_env import RoutePopulationVecEnv
 
@@ -566,7 +571,7 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
         curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
         # the MLP handle also holds one teacher-anchor batch per replica (PopulationTeacherAnchor steps it between rollout and update)
         self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides,
-                              min_batch=teacher_anchor.batch_rows if teacher_anchor is not None else 0)
+                              min_batch=teacher_anchor.batch_rows if teacher_anchor is not None else 0, monitor=monitor)
         self.teacher_anchor = teacher_anchor
         if teacher_anchor is not None:
             teacher_anchor.on_training_start(self)
@@ -583,7 +588,7 @@ class DockPopulationPPO(OneHandlePopulationPPO):
     fused_env_type_ok = True
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None) -> None:
+                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None, monitor: bool | int = False) -> None:
         from .finisher_tools import DockReverseCurriculumPopulation
         from .vec_env import ArmKinematicPopulationVecEnv
 
@@ -602,7 +607,7 @@ class DockPopulationPPO(OneHandlePopulationPPO):
         K = len(seeds)
         views = [env.replica(k) for k in range(K)]
         curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
-        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides)
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides, monitor=monitor)
 
 
 def resolve_resume_population(resume_from: str | None, seeds: list[int], names: list[str] | None = None) -> list[str] | None:
@@ -702,13 +707,20 @@ def learn_population(pop: PopulationPPO, total_timesteps: int, *, on_iteration=N
     after each (per-replica gates).  Returns the wall time in seconds."""
     t0 = time.time()
     start, it = pop.num_timesteps, 0
+    # with the monitor on: SB3's record per replica (its table under a line naming the replica, and a progress.csv row where
+    # pop.progress_csv_paths names the files) in place of today's line
+    loggers = pop.make_loggers(pop.progress_csv_paths) if pop.monitor is not None else None
     while pop.num_timesteps - start < total_timesteps:
         pop.collect_rollouts()
         pop.train()
         it += 1
         if on_iteration is not None:
             on_iteration(pop)
-        if log_every and it % log_every == 0:
+        if log_every and it % log_every == 0 and loggers is not None:
+            for k, row in enumerate(pop.monitor_rows()):
+                print(f"[{tag}] it={it} replica {replica_name(pop.seeds[k], pop.overrides[k])}", flush=True)
+                loggers[k].log(row, iteration=it, total_timesteps=pop.num_timesteps)
+        elif log_every and it % log_every == 0:
             stages = [c.read().stage_index if c is not None else -1 for c in pop.curricula]
             print(f"[{tag}] it={it} steps/replica={pop.num_timesteps} aggregate fps={pop.K * (pop.num_timesteps - start) / (time.time() - t0):,.0f} "
                   f"stages={stages}", flush=True)

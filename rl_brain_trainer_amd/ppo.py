@@ -539,17 +539,28 @@ class PPO:
     """One PPO run.  PopulationPPO (population.py) is the same engine with K replicas: everything per replica below is a list (``envs``,
     ``curricula``, ``policies``, ``gens``) or a replica axis (rollout columns [k N, (k + 1) N), ``perm[k]``, ``stats_dev[k]``); here K = 1."""
 
+    # the training monitor (monitor.py): None = off, the default, and then no launch, graph or printed line differs from a build without it
+    monitor = None
+    _monitor_live = True
+    progress_csv_paths = None      # with the monitor on: one progress.csv path per replica for learn() / learn_population (the CLIs set it)
+
     def __init__(self, env: ArmKinematicVecEnv, cfg: PPOConfig, *, curriculum: PointCurriculum | None = None,
-                 dist: Dist | None = None, backend: str = "hip", use_graphs: bool = True) -> None:
+                 dist: Dist | None = None, backend: str = "hip", use_graphs: bool = True, monitor: bool | int = False) -> None:
+        """``monitor``: False (off), True (SB3's episode and update statistics on the device, over the newest 100 episodes) or that
+        window; fixed at construction, read with ``monitor_rows()``"""
         if backend != "hip":
             raise ValueError("backend must be 'hip': the HIP kernels are the only training path")
         if getattr(env, "is_population", False):
             raise TypeError("PPO trains one seed; a population env (K replicas in one handle) is trained by population.ApproachPopulationPPO")
         if env.dtype != torch.float32:
             raise ValueError("PPO drives the production f32 env")
+        dist = dist or Dist()
+        from . import monitor as _monitor
+
+        _monitor.check_monitor(monitor, dist)     # a data-parallel run is refused before any device work
         self.env = env
         self.curriculum = curriculum
-        self._setup(cfg, [cfg.seed], [env], [curriculum], dist or Dist(), use_graphs, min_batch=8192, stacked=False)
+        self._setup(cfg, [cfg.seed], [env], [curriculum], dist, use_graphs, min_batch=8192, stacked=False, monitor=monitor)
         self.policy = self.policies[0]
         T, N, dev = cfg.n_steps, self.n_envs, self.device
         # data parallel: done bytes are exchanged once per `done_chunk` env steps (one all-gather of chunk x N bytes instead of one
@@ -637,7 +648,7 @@ class PPO:
                                            int(getattr(env, "n_waypoints", 0)), self.dist.enabled, var)
 
     def _setup(self, cfg: PPOConfig, seeds: list[int], envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool, *,
-               min_batch: int, stacked: bool) -> None:
+               min_batch: int, stacked: bool, monitor: bool | int = False) -> None:
         """What a run of K = len(seeds) replicas holds.  Replica k owns what PPO(seed=s_k) owns: the env handle envs[k] and its tracker
         curricula[k], the parameter init and the generators of rollout noise and shuffles.  Rollout buffers are [T(+1), K N, ...] with replica
         k's envs in columns [k N, (k + 1) N); one MLP handle with K replicas trains all of them.  ``min_batch``: lower bound of that handle's
@@ -722,6 +733,77 @@ class PPO:
         # optional host hook after every env step (done bits of that step, device tensor): what SB3 callbacks' _on_step sees.
         # Setting it makes the rollout eager (a host hook cannot live inside a hipGraph replay).
         self.step_callback = None
+        self._setup_monitor(monitor)
+
+    # ------------------------------------------------------------------ training monitor
+    def _setup_monitor(self, monitor: bool | int) -> None:
+        """``monitor=``: the device handle over the K x N rollout columns, the explained-variance output and the log_std snapshot.  The three
+        kernels run once here, on the still zeroed buffers (no episode ends, the carries are cleared again), so that a rollout capture finds
+        them loaded without the capture's warm-up step having to pass through them."""
+        from . import monitor as _monitor
+
+        window = _monitor.check_monitor(monitor, self.dist)
+        self.monitor = None
+        if not window:
+            return
+        T, K, N = self.cfg.n_steps, self.K, self.n_envs
+        self.monitor = _monitor.EpisodeMonitor(self.device, K, N, window=window, max_steps=T)
+        self._ev_dev = torch.zeros((K, 2), dtype=torch.float64, device=self.device)
+        self._log_std_snap = torch.zeros((K, ACT_DIM), dtype=torch.float32, device=self.device)
+        self.monitor.observe(self.rew_buf, self.done_buf, 1)
+        self.monitor.reset_carry()
+        self._monitor_explained_variance()
+
+    def _monitor_observe(self) -> None:
+        """first launch of the rollout tail: the episodes of this rollout, from the rewards as the env wrote them (before the time-limit
+        bootstrap adds gamma * V into them).  The capture warm-up's tail does not feed it: its one step is rolled back."""
+        if self.monitor is not None and self._monitor_live:
+            self.monitor.observe(self.rew_buf, self.done_buf, self.cfg.n_steps)
+
+    def _monitor_explained_variance(self) -> None:
+        """last launch of the rollout tail: var(returns) and var(returns - values) per replica (SB3 train(): explained_variance of the rollout
+        buffer's values and returns)"""
+        if self.monitor is None:
+            return
+        T, KN = self.cfg.n_steps, self.K * self.n_envs
+        native.check(self.L.kp1_explained_variance(self.device.index or 0, C.c_void_p(self.val_buf.data_ptr()), C.c_void_p(self.ret_buf.data_ptr()),
+                                                   T, KN, self.n_envs, C.c_void_p(self._ev_dev.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def monitor_rows(self) -> list[dict[str, Any]]:
+        """SB3's rollout/ and train/ keys of the last iteration, one dict per replica (monitor.KEYS without the time/ keys, which a
+        ``monitor.TrainLogger`` adds).  Reading it synchronises with the device, like ``last_stats``."""
+        if self.monitor is None:
+            raise RuntimeError("monitor_rows needs a trainer constructed with monitor=True (or a window size)")
+        from . import monitor as _monitor
+
+        ev = self._ev_dev.tolist()
+        std = torch.exp(self._log_std_snap).mean(dim=1).tolist()     # th.exp(policy.log_std).mean(), in fp32 as SB3 takes it
+        stats = self._stats_rows()
+        cfgs = getattr(self, "cfgs", None) or [self.cfg] * self.K
+        rows = []
+        for k in range(self.K):
+            row = _monitor.episode_record(self.monitor.read(k))
+            s = stats[k]
+            row.update({"train/approx_kl": s.get("approx_kl"), "train/clip_range": float(cfgs[k].clip_range),
+                        "train/entropy_loss": -s["entropy"] if "entropy" in s else None,
+                        "train/explained_variance": _monitor.explained_variance(ev[k][0], ev[k][1]),
+                        "train/learning_rate": float(cfgs[k].learning_rate), "train/n_updates": self.n_train_calls * self.cfg.n_epochs,
+                        "train/policy_gradient_loss": s.get("policy_loss"), "train/std": std[k] if self.n_train_calls else None,
+                        "train/value_loss": s.get("value_loss")})
+            rows.append(row)
+        return rows
+
+    def make_loggers(self, csv_paths: list[Any] | None = None) -> list[Any]:
+        """one ``monitor.TrainLogger`` per replica, on this run's current step clock (``csv_paths[k]``: replica k's progress.csv or None)"""
+        from . import monitor as _monitor
+
+        paths = csv_paths if csv_paths is not None else [None] * self.K
+        return [_monitor.TrainLogger(paths[k], start_timesteps=self.num_timesteps) for k in range(self.K)]
+
+    def log_monitor(self, loggers: list[Any], iteration: int) -> list[dict[str, Any]]:
+        """emit one record per replica (table and progress.csv row, as each logger is set up); returns the records"""
+        return [lg.log(row, iteration=iteration, total_timesteps=self.num_timesteps) for lg, row in zip(loggers, self.monitor_rows())]
 
     def _sl(self, k: int) -> slice:
         """replica k's columns of the rollout buffers"""
@@ -898,6 +980,7 @@ class PPO:
         was 0.5 ms per iteration)."""
         cfg = self.cfg
         T, KN = cfg.n_steps, self.K * self.n_envs
+        self._monitor_observe()
         self._bootstrap_truncated()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         dev = self.device.index or 0
@@ -907,6 +990,7 @@ class PPO:
         native.check(self.L.kp1_gae_scan(dev, C.c_void_p(self.rew_buf.data_ptr()), C.c_void_p(self.val_buf.data_ptr()),
                                          C.c_void_p(self.done_buf.data_ptr()), C.c_void_p(last_v.data_ptr()), cfg.gamma, cfg.gae_lambda,
                                          C.c_void_p(self.adv_buf.data_ptr()), C.c_void_p(self.ret_buf.data_ptr()), T, KN, C.c_void_p(stream)))
+        self._monitor_explained_variance()
 
     def _rollout_step_hip(self, t: int) -> None:
         # (running the tracker on a side stream under the next policy forward was measured: the fork / join inside the graph
@@ -950,7 +1034,11 @@ class PPO:
                 else:
                     self._policy_env_step(0)
                 self._warm_curricula()
-                self._post_rollout()         # the graph's tail, once eagerly (its buffers are rewritten by the real rollout)
+                self._monitor_live = False   # (the monitor's kernels ran at construction; this step is rolled back and is no episode data)
+                try:
+                    self._post_rollout()     # the graph's tail, once eagerly (its buffers are rewritten by the real rollout)
+                finally:
+                    self._monitor_live = True
                 fresh = []
                 for k, env in enumerate(self.envs):
                     env.use_current_stream()
@@ -983,6 +1071,12 @@ class PPO:
         """obs_buf[0] <- reset() of the env handles `which` (default: all), each into its replica's columns"""
         for k in range(len(self.envs)) if which is None else which:
             self.obs_buf[0, self._sl(k)].copy_(self.envs[k].reset())
+        self._monitor_reset_carry()
+
+    def _monitor_reset_carry(self) -> None:
+        """after an explicit env reset: the running episodes were abandoned, so their partial returns and lengths are dropped"""
+        if self.monitor is not None:
+            self.monitor.reset_carry()
 
     def _warm_curricula(self) -> None:
         """the capture warm-up's tracker launch: every tracker once on zeroed done bytes with a zero clock step (moves nothing; also loads
@@ -1070,6 +1164,9 @@ class PPO:
         # read back lazily (last_stats): a .tolist() here would make every iteration wait for its own update before the host can enqueue
         # the next rollout
         self._last_stats_dev = (self.stats_dev.clone(), n_mb * cfg.n_epochs)
+        if self.monitor is not None:
+            # train/std: exp(log_std) after the update; 7 floats per replica, device to device
+            self._log_std_snap.copy_(self.flat.view(self.K, -1)[:, :ACT_DIM])
 
     def _epoch_body(self) -> None:
         """one update epoch from the shuffle in self.perm: advantage statistics of all minibatches (+ ONE all-reduce of them), then per
@@ -1182,11 +1279,14 @@ class PPO:
         start_steps = self.num_timesteps
         it = 0
         t0 = time.time()
+        loggers = self.make_loggers(getattr(self, "progress_csv_paths", None)) if self.monitor is not None else None
         while self.num_timesteps - start_steps < total:
             self.collect_rollouts()
             self.train()
             it += 1
-            if log_every and it % log_every == 0 and self.dist.rank == 0:
+            if log_every and it % log_every == 0 and loggers is not None:
+                self.log_monitor(loggers, it)     # SB3's table (and progress.csv where progress_csv_paths names one per replica)
+            elif log_every and it % log_every == 0 and self.dist.rank == 0:
                 dt = time.time() - t0
                 stages = [cur.read().stage_index if cur is not None else -1 for cur in self.curricula]
                 stats = self._stats_rows()

@@ -74,6 +74,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
                    help="with --seed: run the gate and final evaluations as the launch sequence per env step (evaluate.run_episodes) instead of "
                         "the one-launch step (kp1_eval_step); the two forms agree bit for bit except in the action-magnitude floats "
                         "(final / mean action magnitude), which may differ by an ulp (and a ready bit, should a norm sit on its threshold to the last bit)")
+    from . import monitor as _monitor
+
+    _monitor.add_cli_flags(p)
     return p
 
 
@@ -213,10 +216,16 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     if rank == 0:
         _start_artifacts(root, args, cfg)
 
+    from . import monitor as _monitor
+
+    dist_glue = Dist()
+    monitor = _monitor.cli_monitor(args)          # False, or the episode window
+    _monitor.check_monitor(monitor, dist_glue)    # --monitor under data parallel: refused before any device work
     env = ArmKinematicVecEnv(env_cfg, n_envs, device=local_rank, seed=seed, first_env_id=rank * n_envs)
     curriculum = _make_curriculum(cfg, env_cfg, ws, local_rank)
     pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=hidden, seed=seed)
-    ppo = PPO(env, pcfg, curriculum=curriculum, dist=Dist(), backend="hip")     # 2x64 / 2x128 / 2x256 all run on the MFMA kernels
+    ppo = PPO(env, pcfg, curriculum=curriculum, dist=dist_glue, backend="hip", monitor=monitor)     # 2x64 / 2x128 / 2x256 all run on the MFMA kernels
+    loggers = ppo.make_loggers([root / "progress.csv"]) if monitor else None
     if resume and Path(resume).exists():
         # PPO.load(resume, env=vec_env): weights, Adam state and the saved algorithm constants; the YAML's learning rate is re-applied
         ppo.load_checkpoint(resume, restore_hyperparameters=True)
@@ -239,7 +248,9 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
         it += 1
         if gate is not None:
             gate.on_iteration(ppo, env_cfg)
-        if args.log_every and it % args.log_every == 0 and rank == 0:
+        if args.log_every and it % args.log_every == 0 and loggers is not None:
+            ppo.log_monitor(loggers, it)
+        elif args.log_every and it % args.log_every == 0 and rank == 0:
             stage = curriculum.read().stage_index if curriculum is not None else -1
             print(f"[ppo] it={it} steps={ppo.num_timesteps} fps={(ppo.num_timesteps - start_steps) / (time.time() - t0):,.0f} stage={stage} "
                   f"rew={ppo.rew_buf.mean().item():.4f} {ppo.last_stats}", flush=True)
@@ -362,7 +373,11 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
     curriculum = None
     if kw is not None:
         curriculum = PointCurriculumPopulation(**kw, initial_stage_indices=[int(ws.get("start_stage_index", 0))] * len(seeds), device=device)
-    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides)
+    from . import monitor as _monitor
+
+    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides, monitor=_monitor.cli_monitor(args))
+    if pop.monitor is not None:
+        pop.progress_csv_paths = [r / "progress.csv" for r in roots]
     if resume_paths is not None:
         pop.load_init_checkpoints(resume_paths, restore_timesteps=False)
         print(f"Resuming workspace expansion of every replica from {resume}")

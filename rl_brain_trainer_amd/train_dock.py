@@ -46,6 +46,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--eval-episodes", type=int, default=512)
     p.add_argument("--log-every", type=int, default=1)
+    from . import monitor as _monitor
+
+    _monitor.add_cli_flags(p)
     g = p.add_mutually_exclusive_group()
     g.add_argument("--whole-episode-eval", dest="whole_episode_eval", action="store_const", const=True, default=None,
                    help="run the final dock evaluation with all its env steps in one launch (kp1_eval_episodes; implies --one-launch-eval); "
@@ -112,6 +115,11 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
         root.mkdir(parents=True, exist_ok=True)
 
     n_envs = args.n_envs
+    from . import monitor as _monitor
+
+    dist_glue = Dist()
+    monitor = _monitor.cli_monitor(args)          # False, or the episode window
+    _monitor.check_monitor(monitor, dist_glue)    # --monitor under data parallel: refused before any device work
     env = ArmKinematicVecEnv(env_cfg, n_envs, device=local_rank, seed=seed, first_env_id=rank * n_envs)
     batch = args.batch_size or max(n_envs * args.n_steps * world // 64, 64)
     model_kwargs = {k: v for k, v in algo.items() if k not in ("total_timesteps", "n_steps", "batch_size")}
@@ -122,7 +130,7 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     if bool(cur_cfg.get("enabled", False)):
         curriculum = DockReverseCurriculum(stages=list(cur_cfg.get("stages", [])), window_episodes=int(cur_cfg.get("window_episodes", 100)),
                                            handoff_base_dirs=base_dirs)
-    ppo = PPO(env, pcfg, curriculum=curriculum, dist=Dist(), backend="hip")
+    ppo = PPO(env, pcfg, curriculum=curriculum, dist=dist_glue, backend="hip", monitor=monitor)
     if args.resume_from and Path(args.resume_from).exists():
         # PPO.load(resume, env=vec_env) + learn(reset_num_timesteps=False) (train_dock_policy.py:89-102)
         ppo.load_checkpoint(args.resume_from, restore_timesteps=True, restore_hyperparameters=True)
@@ -132,11 +140,14 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     total = int(algo.get("total_timesteps", 100_000))
     t0 = time.time()
     start, it = ppo.num_timesteps, 0
+    loggers = ppo.make_loggers([root / "progress.csv"]) if monitor else None
     while ppo.num_timesteps - start < total:
         ppo.collect_rollouts()
         ppo.train()
         it += 1
-        if args.log_every and it % args.log_every == 0 and rank == 0:
+        if args.log_every and it % args.log_every == 0 and loggers is not None:
+            ppo.log_monitor(loggers, it)
+        elif args.log_every and it % args.log_every == 0 and rank == 0:
             stage = curriculum.current_stage_index if curriculum is not None else -1
             print(f"[ppo-dock] it={it} steps={ppo.num_timesteps} fps={(ppo.num_timesteps - start) / (time.time() - t0):,.0f} stage={stage} "
                   f"rew={ppo.rew_buf.mean().item():.4f} {ppo.last_stats}", flush=True)
@@ -202,13 +213,17 @@ def _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root: Path, w
     if bool(cur_cfg.get("enabled", False)):
         curriculum = DockReverseCurriculumPopulation(stages=list(cur_cfg.get("stages", [])), window_episodes=int(cur_cfg.get("window_episodes", 100)),
                                                      n_replicas=len(seeds), handoff_base_dirs=base_dirs)
-    pop = DockPopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides)
+    from . import monitor as _monitor
+
+    pop = DockPopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides, monitor=_monitor.cli_monitor(args))
     if resume_paths is not None:
         pop.load_init_checkpoints(resume_paths)
         print(f"Resuming dock policies from {args.resume_from}")
     roots = [root / n for n in names]
     for r in roots:
         r.mkdir(parents=True, exist_ok=True)
+    if pop.monitor is not None:
+        pop.progress_csv_paths = [r / "progress.csv" for r in roots]
     wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), log_every=args.log_every, tag="ppo-dock-population")
     rows = []
     for k, s in enumerate(seeds):

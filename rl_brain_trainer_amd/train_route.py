@@ -72,6 +72,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--device", type=int, default=0, help="GPU of a single-process run (under torchrun: LOCAL_RANK)")
     p.add_argument("--log-every", type=int, default=0)
+    from . import monitor as _monitor
+
+    _monitor.add_cli_flags(p)
     p.add_argument("--one-launch-rollout", action="store_true", help="run every rollout step as ONE launch (kp1_mlp_forward_route_step: sets "
                    "KP1_FUSED_ROUTE_ROLLOUT=1; fp32, hidden 64 / 128, reward components off, not data parallel -- otherwise the launch "
                    "sequence stays); bit-identical to the default, for --seed and --seeds runs")
@@ -135,6 +138,11 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
         finally:
             if own_group:
                 dist.destroy_process_group()
+    from . import monitor as _monitor
+
+    dist_glue = Dist()
+    monitor = _monitor.cli_monitor(args)          # False, or the episode window
+    _monitor.check_monitor(monitor, dist_glue)    # --monitor under data parallel: refused before any device work
     env = RouteVecEnv(env_cfg, rcfg.route_config_from_dict(cfg, max_route_index=prefixes[0]), route_q, n_envs, device=device, seed=seed,
                       first_env_id=rank * n_envs)
 
@@ -146,7 +154,7 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     # the prefix curriculum: a device tracker after every env step (the rollout stays one hipGraph replay); data parallel: per-step episode
     # records, exchanged and replayed once per chunk of KP1_DONE_EXCHANGE_STEPS steps
     curriculum = RoutePrefixCurriculumDevice.from_config(cfg, W)
-    ppo = PPO(env, pcfg, curriculum=curriculum, dist=Dist(), backend="hip")
+    ppo = PPO(env, pcfg, curriculum=curriculum, dist=dist_glue, backend="hip", monitor=monitor)
     if init_checkpoint:
         # PPO.load(..., env=vec_env) + learn(reset_num_timesteps=False): weights, Adam state, step clock; the YAML's learning rate wins
         ppo.load_checkpoint(init_checkpoint, restore_timesteps=True, restore_hyperparameters=True)
@@ -164,6 +172,7 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
 
     t0 = time.time()
     start_steps, it = ppo.num_timesteps, 0
+    loggers = ppo.make_loggers([root / "progress.csv"]) if monitor else None
     while ppo.num_timesteps - start_steps < total:
         ppo.collect_rollouts()
         if anchor is not None:
@@ -174,7 +183,9 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
             if rank == 0:
                 checkpoint.save(root / "checkpoints" / f"model_{ppo.num_timesteps - start_steps}_steps", ppo, env_cfg)
             next_checkpoint += checkpoint_freq
-        if args.log_every and it % args.log_every == 0 and rank == 0:
+        if args.log_every and it % args.log_every == 0 and loggers is not None:
+            ppo.log_monitor(loggers, it)
+        elif args.log_every and it % args.log_every == 0 and rank == 0:
             s = curriculum.summary()
             print(f"[route] it={it} steps={ppo.num_timesteps} fps={(ppo.num_timesteps - start_steps) / (time.time() - t0):,.0f} prefix={s['prefix_end_index']} "
                   f"succ={s['recent_success_rate']:.3f} rew={ppo.rew_buf.mean().item():.4f} anchor={anchor.last_loss if anchor else 0.0:.5f}", flush=True)
@@ -234,7 +245,11 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
     curriculum = RoutePrefixCurriculumPopulation.from_config(cfg, W)
     pop = None
     try:
-        pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides, teacher_anchor=anchor)
+        from . import monitor as _monitor
+        from .population import replica_name
+
+        pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides, teacher_anchor=anchor, monitor=_monitor.cli_monitor(args))
+        loggers = pop.make_loggers([r / "progress.csv" for r in roots]) if pop.monitor is not None else None
         if init_checkpoint:
             pop.load_init_checkpoint(init_checkpoint)
             print(f"Resuming every route policy of the population from {init_checkpoint}")
@@ -252,7 +267,11 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
                 for k in range(pop.K):
                     checkpoint.save(roots[k] / "checkpoints" / f"model_{pop.num_timesteps - start_steps}_steps", pop.replica(k), env_cfg)
                 next_checkpoint += checkpoint_freq
-            if args.log_every and it % args.log_every == 0:
+            if args.log_every and it % args.log_every == 0 and loggers is not None:
+                for k, row in enumerate(pop.monitor_rows()):
+                    print(f"[route-population] it={it} replica {replica_name(pop.seeds[k], pop.overrides[k])}", flush=True)
+                    loggers[k].log(row, iteration=it, total_timesteps=pop.num_timesteps)
+            elif args.log_every and it % args.log_every == 0:
                 stages = [curriculum.summary(k)["prefix_end_index"] for k in range(pop.K)]
                 print(f"[route-population] it={it} steps/replica={pop.num_timesteps} aggregate fps="
                       f"{pop.K * (pop.num_timesteps - start_steps) / (time.time() - t0):,.0f} prefixes={stages}"

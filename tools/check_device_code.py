@@ -82,7 +82,9 @@ def kernel_listings(dis: str) -> dict[str, list[str]]:
             cur = out.setdefault(m.group(1), [])
             continue
         text = re.sub(r"^\s*[0-9a-f]+:\s", "", line.split("//")[0]).strip()
-        if cur is not None and text:
+        # `...` is objdump's mark for the zero padding up to the next symbol's alignment: it appears behind a kernel once another one follows
+        # it in the code object, and is no instruction
+        if cur is not None and text and text != "...":
             cur.append(text)
     return out
 

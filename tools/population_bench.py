@@ -94,6 +94,7 @@ def build_approach(K: int, n_envs: int, n_steps: int, batch: int, hidden: int, u
 
 
 SWEEP: list[tuple[str, list[float]]] = []     # --sweep: replica k takes value k % len(values) of every swept key
+MONITOR = [False]     # --monitor: the --one-handle and --single-seed iterations with the training monitor on (monitor.py)
 
 
 def _sweep_overrides(K: int) -> list[dict[str, float]] | None:
@@ -109,7 +110,7 @@ def build_approach_one_handle(K: int, n_envs: int, n_steps: int, batch: int, hid
     seeds = list(range(7, 7 + K))
     env = ArmKinematicPopulationVecEnv(env_cfg, seeds, n_envs)
     cur = PointCurriculumPopulation(**tracker, initial_stage_indices=[0] * K) if tracker else None
-    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=cur, use_graphs=use_graphs, overrides=_sweep_overrides(K))
+    pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=cur, use_graphs=use_graphs, overrides=_sweep_overrides(K), monitor=MONITOR[0])
     pop._bench_owned = [c for c in (cur, env) if c is not None]     # closed after the population (the caller owns them)
     return pop
 
@@ -122,7 +123,7 @@ def build_single_seed(K: int, n_envs: int, n_steps: int, batch: int, hidden: int
     env_cfg, pcfg, tracker = _approach_setup(n_steps, batch, hidden)
     env = ArmKinematicVecEnv(env_cfg, n_envs, seed=7)
     cur = PointCurriculum(**tracker) if tracker else None
-    ppo = PPO(env, pcfg, curriculum=cur, use_graphs=use_graphs)
+    ppo = PPO(env, pcfg, curriculum=cur, use_graphs=use_graphs, monitor=MONITOR[0])
     ppo._bench_owned = [c for c in (cur, env) if c is not None]
     return ppo
 
@@ -622,8 +623,14 @@ def main() -> None:
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--sweep", action="append", metavar="KEY=v1,v2", help="with --one-handle: per-replica hyper-parameters (replica k takes value "
                     "k %% n of each key; the per-replica table and GAE scan of a population with overrides)")
+    ap.add_argument("--monitor", action="store_true", help="with --one-handle or --single-seed: the training monitor on (two launches in front of "
+                    "the rollout tail, one behind it, and the log_std copy after the update)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.monitor:
+        if not (args.one_handle or args.single_seed):
+            ap.error("--monitor is measured on the --one-handle and --single-seed Approach iterations")
+        MONITOR[0] = True
     if args.sweep:
         from rl_brain_trainer_amd.population import parse_sweep
 
@@ -687,7 +694,7 @@ def main() -> None:
                           f"minibatch {args.batch}, 2x{args.hidden}, curriculum on; seeds 7..7+K-1"
                           + (f"; sweep {dict(SWEEP)} (replica k takes value k % n)" if SWEEP else "")
                           + (f"; rollout form {args.rollout_form}" if args.rollout_form else "")
-                          + ("; update form train tile" if args.train_tile else ""), "device": torch.cuda.get_device_name(0), "rows": rows}
+                          + ("; update form train tile" if args.train_tile else "") + ("; training monitor on" if args.monitor else ""), "device": torch.cuda.get_device_name(0), "rows": rows}
     if args.out:
         Path(args.out).write_text(json.dumps(result, indent=2) + "\n")
     print(json.dumps({"aggregate_env_steps_per_s": {r["K"]: round(r["aggregate_env_steps_per_s"]) for r in rows}}))
