@@ -25,14 +25,17 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import os
-import time
 from typing import Any, Callable
 
 import torch
 
 from . import native
-from .ppo import ACT_DIM, FUSED_ROUTE_ROLLOUT_ENV, OBS_DIM, Dist, PPO, PPOConfig, fused_rollout_covered, fused_route_rollout_covered
+from .curriculum import PointCurriculumPopulation
+from .finisher_tools import DockReverseCurriculumPopulation
+from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig
+from .route_curriculum import RoutePrefixCurriculumPopulation
+from .route_env import RoutePopulationVecEnv
+from .vec_env import ArmKinematicPopulationVecEnv
 
 MAX_REPLICAS = 16     # KP1_MLP_MAX_REPLICAS
 
@@ -227,6 +230,11 @@ class PopulationPPO(PPO):
     def replica(self, k: int) -> ReplicaView:
         return ReplicaView(self, k)
 
+    @property
+    def replica_names(self) -> list[str]:
+        """replica_name of every replica: its artefact directory, and what ppo.run_training calls it above its monitor record"""
+        return [replica_name(s, o) for s, o in zip(self.seeds, self.overrides)]
+
     def close(self) -> None:
         for e in self.envs:
             e.close()
@@ -347,62 +355,75 @@ class PopulationPPO(PPO):
 
 class OneHandlePopulationPPO(PopulationPPO):
     """A population whose K replicas share ONE env handle of K N envs (block k = replica k, the rollout buffers' replica-major layout) and
-    ONE population tracker: every env step is one env step launch and one tracker launch whatever K is.  Subclasses set ``pop_env`` /
-    ``pop_curriculum`` and build the per-replica views; noise, truncation bootstrap, the epoch body and graph capture are PopulationPPO's.
-    The caller owns (and closes) the env and the tracker."""
+    ONE population tracker: every env step is one env step launch and one tracker launch whatever K is.  The rollout step is PPO's own, on
+    ``pop_env`` / ``pop_curriculum``; noise, truncation bootstrap, the epoch body and graph capture are PopulationPPO's.  A subclass names
+    what it drives in the class attributes below.  The caller owns (and closes) the env and the tracker."""
 
     pop_env: Any = None
     pop_curriculum: Any = None
+
+    # what __init__ checks, in the order of its refusals: the env class, a further predicate on the env with the words that name such an env,
+    # the tracker class, whether the tracker's K must equal the seed count, whether a PopulationTeacherAnchor is accepted
+    env_class: type = type(None)
+    env_also = staticmethod(lambda env: True)
+    env_words = ""
+    tracker_class: type = type(None)
+    tracker_checks_k = True
+    accepts_anchor = False
+    # whether the env handle is one kp1_mlp_forward_env_step steps (an ArmKinematicPopulationVecEnv; the route env has no kp1_env step of its
+    # own and the 80-float observation, so RoutePopulationPPO keeps the launch sequence), and one kp1_mlp_forward_route_step steps
+    fused_env_type_ok = False
+    fused_route_env_type_ok = False
+
+    def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
+                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None, monitor: bool | int = False) -> None:
+        name, env_name, tracker_name = type(self).__name__, self.env_class.__name__, self.tracker_class.__name__
+        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides, accepts_anchor=self.accepts_anchor)
+        if not isinstance(env, self.env_class) or not self.env_also(env):
+            raise TypeError(f"{name} drives {self.env_words} (one handle for all replicas)")
+        if env.seeds != seeds:
+            raise ValueError(f"the {env_name} was made for seeds {env.seeds}, not {seeds}")
+        if curriculum is not None and not isinstance(curriculum, self.tracker_class):
+            raise TypeError(f"{name} takes a {tracker_name} (one tracker launch for all replicas)")
+        if curriculum is not None and self.tracker_checks_k and curriculum.K != len(seeds):
+            raise ValueError(f"the {tracker_name} holds {curriculum.K} trackers for {len(seeds)} seeds")
+        self.pop_env, self.pop_curriculum = env, curriculum
+        if curriculum is not None:
+            curriculum.attach(env)
+        K = len(seeds)
+        views = [env.replica(k) for k in range(K)]
+        curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
+        # with an anchor the MLP handle also holds one teacher-anchor batch per replica (PopulationTeacherAnchor steps it between rollout
+        # and update)
+        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides,
+                              min_batch=teacher_anchor.batch_rows if teacher_anchor is not None else 0, monitor=monitor)
+        self.teacher_anchor = teacher_anchor
+        if teacher_anchor is not None:
+            teacher_anchor.on_training_start(self)
 
     def _reset_envs(self, which: list[int] | None = None) -> None:
         if which is None or which:
             self.obs_buf[0].copy_(self.pop_env.reset())
             self._monitor_reset_carry()
 
-    # whether the env handle is one kp1_mlp_forward_env_step steps (ApproachPopulationPPO, DockPopulationPPO: an ArmKinematicPopulationVecEnv;
-    # the route env has no kp1_env step of its own and the 80-float observation, so RoutePopulationPPO keeps the launch sequence)
-    fused_env_type_ok = False
+    # PPO's rollout step (not the K-handle population's), on the one handle and the one tracker
+    _policy_env_step = PPO._policy_env_step
+    _curriculum_observe = PPO._curriculum_observe
 
-    @property
-    def _fused_env_step(self) -> bool:
-        env = self.pop_env
-        return fused_rollout_covered(self.fused_env_type_ok, env.dtype, self.cfg.hidden, self.obs_dim,
-                                     getattr(env, "_reward_components_on", False), os.environ.get("KP1_FUSED_ROLLOUT"),
-                                     default_on=True)     # measured on both one-handle trainers (DESIGN section 21)
+    def _rollout_env(self) -> Any:
+        return self.pop_env
 
-    # whether the env handle is one kp1_mlp_forward_route_step steps (RoutePopulationPPO: a RoutePopulationVecEnv)
-    fused_route_env_type_ok = False
+    def _rollout_tracker(self) -> Any:
+        return self.pop_curriculum
 
-    @property
-    def _fused_route_step(self) -> bool:
-        """the one-launch ROUTE form (fused_route_rollout_covered; opt-in with KP1_FUSED_ROUTE_ROLLOUT, read before any attribute of the env)"""
-        var = os.environ.get(FUSED_ROUTE_ROLLOUT_ENV)
-        if var is None or var == "0" or not self.fused_route_env_type_ok:
-            return False
-        env = self.pop_env
-        return fused_route_rollout_covered(True, env.dtype, self.cfg.hidden, self.obs_dim, bool(getattr(env, "_reward_components_on", False)),
-                                           int(getattr(env, "n_waypoints", 0)), self.dist.enabled, var)
+    def _rollout_env_type_ok(self) -> bool:
+        return self.fused_env_type_ok
 
-    def _policy_env_step(self, t: int) -> None:
-        if self._fused_route_step:
-            # all replicas' policy forward + sampling + base step + nearest scan + route step (auto-reset in each replica's window) in ONE launch
-            self._mlp.forward_route_step(self.pop_env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
-                                         log_prob=self.logp_buf[t], next_obs=self.obs_buf[t + 1], reward=self.rew_buf[t], done=self.done_buf[t],
-                                         terminal_obs=self.term_obs_buf[t])
-            return
-        if self._fused_env_step:
-            # all replicas' policy forward + sampling + env step (auto-reset on each replica's own stage) in ONE launch
-            self._mlp.forward_env_step(self.pop_env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
-                                       log_prob=self.logp_buf[t], next_obs=self.obs_buf[t + 1], reward=self.rew_buf[t], done=self.done_buf[t],
-                                       terminal_obs=self.term_obs_buf[t])
-            return
-        self._mlp.forward(self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t], clipped=self.clip_act,
-                          log_prob=self.logp_buf[t])
-        self.pop_env.step_into(self.clip_act, self.obs_buf[t + 1], self.rew_buf[t], self.done_buf[t], self.term_obs_buf[t], True)
+    def _route_env_type_ok(self) -> bool:
+        return self.fused_route_env_type_ok
 
-    def _curriculum_observe(self, t: int) -> None:
-        if self.pop_curriculum is not None:
-            self.pop_curriculum.observe(self.done_buf[t], self.n_envs)
+    def _fused_rollout_default(self) -> bool:
+        return True     # measured on both one-handle trainers (DESIGN section 21)
 
     def _warm_curricula(self) -> None:
         if self.pop_curriculum is not None:
@@ -501,41 +522,10 @@ class ApproachPopulationPPO(OneHandlePopulationPPO):
     launch (and a wave).  Replica k is bit-identical to ``PPO(ArmKinematicVecEnv(..., seed=s_k), curriculum=PointCurriculum)`` on the same
     config (tests/test_approach_population_gpu.py), and to replica k of the K-handle ``PopulationPPO``."""
 
+    env_class, env_words, tracker_class = ArmKinematicPopulationVecEnv, "an ArmKinematicPopulationVecEnv", PointCurriculumPopulation
     fused_env_type_ok = True
-
     # all env steps of a rollout in one launch per span (PPO's rollout_run_covered predicate on pop_env / pop_curriculum; KP1_ROLLOUT_RUN)
     _whole_rollout = PPO._whole_rollout
-
-    def _rollout_env(self) -> Any:
-        return self.pop_env
-
-    def _rollout_tracker(self) -> Any:
-        return self.pop_curriculum
-
-    def _rollout_env_type_ok(self) -> bool:
-        return True
-
-    def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None, monitor: bool | int = False) -> None:
-        from .curriculum import PointCurriculumPopulation
-        from .vec_env import ArmKinematicPopulationVecEnv
-
-        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides)
-        if not isinstance(env, ArmKinematicPopulationVecEnv):
-            raise TypeError("ApproachPopulationPPO drives an ArmKinematicPopulationVecEnv (one handle for all replicas)")
-        if env.seeds != seeds:
-            raise ValueError(f"the ArmKinematicPopulationVecEnv was made for seeds {env.seeds}, not {seeds}")
-        if curriculum is not None and not isinstance(curriculum, PointCurriculumPopulation):
-            raise TypeError("ApproachPopulationPPO takes a PointCurriculumPopulation (one tracker launch for all replicas)")
-        if curriculum is not None and curriculum.K != len(seeds):
-            raise ValueError(f"the PointCurriculumPopulation holds {curriculum.K} trackers for {len(seeds)} seeds")
-        self.pop_env, self.pop_curriculum = env, curriculum
-        if curriculum is not None:
-            curriculum.attach(env)
-        K = len(seeds)
-        views = [env.replica(k) for k in range(K)]
-        curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
-        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides, monitor=monitor)
 
 
 class RoutePopulationPPO(OneHandlePopulationPPO):
@@ -549,32 +539,10 @@ class RoutePopulationPPO(OneHandlePopulationPPO):
     (tests/test_route_population_gpu.py).  ``load_init_checkpoint`` (OneHandlePopulationPPO's) starts every replica from one checkpoint as
     train_route does.  The caller owns (and closes) the env and the tracker."""
 
+    env_class, env_words, tracker_class = RoutePopulationVecEnv, "a RoutePopulationVecEnv", RoutePrefixCurriculumPopulation
+    tracker_checks_k = False
+    accepts_anchor = True
     fused_route_env_type_ok = True
-
-    def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None, monitor: bool | int = False) -> None:
-        from .route_curriculum import RoutePrefixCurriculumPopulation
-        from .route_env import RoutePopulationVecEnv
-
-        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides, accepts_anchor=True)
-        if not isinstance(env, RoutePopulationVecEnv):
-            raise TypeError("RoutePopulationPPO drives a RoutePopulationVecEnv (one handle for all replicas)")
-        if env.seeds != seeds:
-            raise ValueError(f"the RoutePopulationVecEnv was made for seeds {env.seeds}, not {seeds}")
-        if curriculum is not None and not isinstance(curriculum, RoutePrefixCurriculumPopulation):
-            raise TypeError("RoutePopulationPPO takes a RoutePrefixCurriculumPopulation (one tracker launch for all replicas)")
-        self.pop_env, self.pop_curriculum = env, curriculum
-        if curriculum is not None:
-            curriculum.attach(env)
-        K = len(seeds)
-        views = [env.replica(k) for k in range(K)]
-        curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
-        # the MLP handle also holds one teacher-anchor batch per replica (PopulationTeacherAnchor steps it between rollout and update)
-        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides,
-                              min_batch=teacher_anchor.batch_rows if teacher_anchor is not None else 0, monitor=monitor)
-        self.teacher_anchor = teacher_anchor
-        if teacher_anchor is not None:
-            teacher_anchor.on_training_start(self)
 
 
 class DockPopulationPPO(OneHandlePopulationPPO):
@@ -585,29 +553,9 @@ class DockPopulationPPO(OneHandlePopulationPPO):
     on the same config (tests/test_dock_population_gpu.py).  ``load_init_checkpoint`` / ``load_init_checkpoints`` start the replicas from one
     checkpoint or one each (train_dock --seeds --resume-from).  The caller owns (and closes) the env and the tracker."""
 
+    env_class, env_words, tracker_class = ArmKinematicPopulationVecEnv, "a dock-mode ArmKinematicPopulationVecEnv", DockReverseCurriculumPopulation
+    env_also = staticmethod(lambda env: env.config.mode_name == "dock")
     fused_env_type_ok = True
-
-    def __init__(self, seeds: list[int], cfg: PPOConfig, env: Any, *, curriculum: Any = None, dist: Dist | None = None, use_graphs: bool = True,
-                 teacher_anchor: Any = None, overrides: list[dict[str, float]] | None = None, monitor: bool | int = False) -> None:
-        from .finisher_tools import DockReverseCurriculumPopulation
-        from .vec_env import ArmKinematicPopulationVecEnv
-
-        seeds, dist, overrides = self._check_population_args(seeds, cfg, dist, teacher_anchor, overrides)
-        if not isinstance(env, ArmKinematicPopulationVecEnv) or env.config.mode_name != "dock":
-            raise TypeError("DockPopulationPPO drives a dock-mode ArmKinematicPopulationVecEnv (one handle for all replicas)")
-        if env.seeds != seeds:
-            raise ValueError(f"the ArmKinematicPopulationVecEnv was made for seeds {env.seeds}, not {seeds}")
-        if curriculum is not None and not isinstance(curriculum, DockReverseCurriculumPopulation):
-            raise TypeError("DockPopulationPPO takes a DockReverseCurriculumPopulation (one tracker launch for all replicas)")
-        if curriculum is not None and curriculum.K != len(seeds):
-            raise ValueError(f"the DockReverseCurriculumPopulation holds {curriculum.K} trackers for {len(seeds)} seeds")
-        self.pop_env, self.pop_curriculum = env, curriculum
-        if curriculum is not None:
-            curriculum.attach(env)
-        K = len(seeds)
-        views = [env.replica(k) for k in range(K)]
-        curricula = [curriculum.replica(k) if curriculum is not None else None for k in range(K)]
-        self._init_population(seeds, cfg, views, curricula, dist, use_graphs, overrides, monitor=monitor)
 
 
 def resolve_resume_population(resume_from: str | None, seeds: list[int], names: list[str] | None = None) -> list[str] | None:
@@ -702,30 +650,10 @@ def plan_replicas(seeds_text: str | None, sweep_specs: list[str] | None) -> tupl
     return rep_seeds, overrides, [replica_name(s, o) for s, o in zip(rep_seeds, overrides)]
 
 
-def learn_population(pop: PopulationPPO, total_timesteps: int, *, on_iteration=None, log_every: int = 0, tag: str = "population") -> float:
-    """The trainers' loop for a population: iterations until every replica has taken `total_timesteps` env steps; ``on_iteration(pop)``
-    after each (per-replica gates).  Returns the wall time in seconds."""
-    t0 = time.time()
-    start, it = pop.num_timesteps, 0
-    # with the monitor on: SB3's record per replica (its table under a line naming the replica, and a progress.csv row where
-    # pop.progress_csv_paths names the files) in place of today's line
-    loggers = pop.make_loggers(pop.progress_csv_paths) if pop.monitor is not None else None
-    while pop.num_timesteps - start < total_timesteps:
-        pop.collect_rollouts()
-        pop.train()
-        it += 1
-        if on_iteration is not None:
-            on_iteration(pop)
-        if log_every and it % log_every == 0 and loggers is not None:
-            for k, row in enumerate(pop.monitor_rows()):
-                print(f"[{tag}] it={it} replica {replica_name(pop.seeds[k], pop.overrides[k])}", flush=True)
-                loggers[k].log(row, iteration=it, total_timesteps=pop.num_timesteps)
-        elif log_every and it % log_every == 0:
-            stages = [c.read().stage_index if c is not None else -1 for c in pop.curricula]
-            print(f"[{tag}] it={it} steps/replica={pop.num_timesteps} aggregate fps={pop.K * (pop.num_timesteps - start) / (time.time() - t0):,.0f} "
-                  f"stages={stages}", flush=True)
-    torch.cuda.synchronize(pop.device)
-    return time.time() - t0
+def population_status(pop: PopulationPPO, it: int, steps: int, elapsed: float, *, tag: str = "population") -> str:
+    """a population trainer's line at the logging cadence (ppo.run_training's ``status``; ``steps``: each replica's env steps of this run)"""
+    stages = [c.read().stage_index if c is not None else -1 for c in pop.curricula]
+    return f"[{tag}] it={it} steps/replica={pop.num_timesteps} aggregate fps={pop.K * steps / elapsed:,.0f} stages={stages}"
 
 
 def population_summary(pop: PopulationPPO, rows: list[dict[str, Any]], *, wall_seconds: float, selection: str) -> dict[str, Any]:

@@ -542,7 +542,6 @@ class PPO:
     # the training monitor (monitor.py): None = off, the default, and then no launch, graph or printed line differs from a build without it
     monitor = None
     _monitor_live = True
-    progress_csv_paths = None      # with the monitor on: one progress.csv path per replica for learn() / learn_population (the CLIs set it)
 
     def __init__(self, env: ArmKinematicVecEnv, cfg: PPOConfig, *, curriculum: PointCurriculum | None = None,
                  dist: Dist | None = None, backend: str = "hip", use_graphs: bool = True, monitor: bool | int = False) -> None:
@@ -579,12 +578,15 @@ class PPO:
     def _fused_env_step(self) -> bool:
         """whether the next rollout step is the one-launch form (fused_rollout_covered on the env's current state: the reward-component
         switch may be thrown after construction, which bumps ``launch_args_version`` and re-captures the rollout)"""
-        env = self.env
-        # default: hidden 256 (measured, DESIGN section 4.5); the single-seed PPO at hidden 64 / 128 was not measured and opts in with
-        # KP1_FUSED_ROLLOUT=1 (DESIGN section 21)
-        return fused_rollout_covered(type(env) is ArmKinematicVecEnv, env.dtype, self.cfg.hidden, self.obs_dim,
+        env = self._rollout_env()
+        return fused_rollout_covered(self._rollout_env_type_ok(), env.dtype, self.cfg.hidden, self.obs_dim,
                                      getattr(env, "_reward_components_on", False), os.environ.get("KP1_FUSED_ROLLOUT"),
-                                     default_on=self.cfg.hidden == 256)
+                                     default_on=self._fused_rollout_default())
+
+    def _fused_rollout_default(self) -> bool:
+        """the one-launch step while KP1_FUSED_ROLLOUT is unset: hidden 256 (measured); the single-seed PPO at hidden
+        64 / 128 was not measured and opts in with KP1_FUSED_ROLLOUT=1"""
+        return self.cfg.hidden == 256
 
     # the trainer's default for the one-launch training tile while KP1_TRAIN_TILE is unset: off until a measurement by DESIGN section 20's
     # rule turns it on (DESIGN section 31)
@@ -615,16 +617,25 @@ class PPO:
                                    cur is not None, self.n_envs, var, tracker_ok=isinstance(cur, PointCurriculum),
                                    default_on=self.whole_rollout_default)
 
+    # The env handle and the tracker of a rollout step, and which one-launch forms that handle's type admits: all that differs between
+    # this class and a one-handle population (population.OneHandlePopulationPPO) in the rollout step below.
     def _rollout_env(self) -> Any:
-        """the env handle a one-launch rollout steps"""
+        """the env handle a rollout step steps"""
         return self.env
 
     def _rollout_tracker(self) -> Any:
-        """the tracker a whole-rollout launch drives (None: no tracker attached)"""
+        """the tracker that follows every env step (None: no tracker attached)"""
         return self.curriculum
 
     def _rollout_env_type_ok(self) -> bool:
+        """an env kp1_mlp_forward_env_step / kp1_rollout_run step: the plain arm env, no subclass"""
         return type(self.env) is ArmKinematicVecEnv
+
+    def _route_env_type_ok(self) -> bool:
+        """an env kp1_mlp_forward_route_step steps: a single-seed route env"""
+        from .route_env import RoutePopulationVecEnv, RouteVecEnv
+
+        return isinstance(self.env, RouteVecEnv) and not isinstance(self.env, RoutePopulationVecEnv)
 
     def _rollout_whole(self, n_steps: int | None = None, *, tracked: bool = True) -> None:
         """env steps 0 .. n_steps - 1 (default: the whole rollout) as one launch per span, the attached tracker included"""
@@ -638,13 +649,10 @@ class PPO:
         """whether the next rollout step is the one-launch ROUTE form (fused_route_rollout_covered; opt-in with KP1_FUSED_ROUTE_ROLLOUT).  The
         variable is read first: without it no attribute of the env is touched."""
         var = os.environ.get(FUSED_ROUTE_ROLLOUT_ENV)
-        if var is None or var == "0":
+        if var is None or var == "0" or not self._route_env_type_ok():
             return False
-        from .route_env import RoutePopulationVecEnv, RouteVecEnv
-
-        env = self.env
-        return fused_route_rollout_covered(isinstance(env, RouteVecEnv) and not isinstance(env, RoutePopulationVecEnv), env.dtype,
-                                           self.cfg.hidden, self.obs_dim, bool(getattr(env, "_reward_components_on", False)),
+        env = self._rollout_env()
+        return fused_route_rollout_covered(True, env.dtype, self.cfg.hidden, self.obs_dim, bool(getattr(env, "_reward_components_on", False)),
                                            int(getattr(env, "n_waypoints", 0)), self.dist.enabled, var)
 
     def _setup(self, cfg: PPOConfig, seeds: list[int], envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool, *,
@@ -801,10 +809,6 @@ class PPO:
         paths = csv_paths if csv_paths is not None else [None] * self.K
         return [_monitor.TrainLogger(paths[k], start_timesteps=self.num_timesteps) for k in range(self.K)]
 
-    def log_monitor(self, loggers: list[Any], iteration: int) -> list[dict[str, Any]]:
-        """emit one record per replica (table and progress.csv row, as each logger is set up); returns the records"""
-        return [lg.log(row, iteration=iteration, total_timesteps=self.num_timesteps) for lg, row in zip(loggers, self.monitor_rows())]
-
     def _sl(self, k: int) -> slice:
         """replica k's columns of the rollout buffers"""
         return slice(k * self.n_envs, (k + 1) * self.n_envs)
@@ -846,10 +850,11 @@ class PPO:
     def _curriculum_observe(self, t: int) -> None:
         """after env step t: feed the done bytes to the device tracker (single process: every step; data parallel: once per chunk -- a route
         tracker gets the step's episode records, written every step, in place of the done bytes)"""
-        if self.curriculum is None:
+        cur = self._rollout_tracker()
+        if cur is None:
             return
         if not self.dist.enabled:
-            self.curriculum.observe(self.done_buf[t], self.n_envs)
+            cur.observe(self.done_buf[t], self.n_envs)
             return
         c = self.done_chunk
         if self._record_stage is not None:
@@ -999,20 +1004,23 @@ class PPO:
         self._curriculum_observe(t)
 
     def _policy_env_step(self, t: int) -> None:
+        env = self._rollout_env()
         if self._fused_route_step:
-            # a RouteVecEnv: policy forward + sampling + base step + nearest scan + route step (auto-reset included) in ONE launch
-            self._mlp.forward_route_step(self.env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
+            # a route env: policy forward + sampling + base step + nearest scan + route step (auto-reset included, a population's in each
+            # replica's window) in ONE launch
+            self._mlp.forward_route_step(env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
                                          log_prob=self.logp_buf[t], next_obs=self.obs_buf[t + 1], reward=self.rew_buf[t], done=self.done_buf[t],
                                          terminal_obs=self.term_obs_buf[t])
         elif self._fused_env_step:
-            # policy forward + sampling + env step (auto-reset included) in ONE launch: the tile's policy workgroup steps its 32 envs itself
-            self._mlp.forward_env_step(self.env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
+            # policy forward + sampling + env step (auto-reset included, a population's on each replica's own stage) in ONE launch: the
+            # tile's policy workgroup steps its 32 envs itself
+            self._mlp.forward_env_step(env, self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
                                        log_prob=self.logp_buf[t], next_obs=self.obs_buf[t + 1], reward=self.rew_buf[t], done=self.done_buf[t],
                                        terminal_obs=self.term_obs_buf[t])
         else:
             self._mlp.forward(self.obs_buf[t], noise=self.noise_all[t], value=self.val_buf[t], action=self.act_buf[t],
                               clipped=self.clip_act, log_prob=self.logp_buf[t])
-            self.env.step_into(self.clip_act, self.obs_buf[t + 1], self.rew_buf[t], self.done_buf[t], self.term_obs_buf[t], True)
+            env.step_into(self.clip_act, self.obs_buf[t + 1], self.rew_buf[t], self.done_buf[t], self.term_obs_buf[t], True)
 
     def _capture_rollout(self) -> None:
         """Record the T-step rollout (policy forward, env step, curriculum tracker; data parallel: the done-byte all-gather of every chunk)
@@ -1275,25 +1283,50 @@ class PPO:
     # ------------------------------------------------------------------ driver
     def learn(self, total_timesteps: int | None = None, log_every: int = 0) -> "PPO":
         """``total_timesteps`` and the logged steps / fps count each replica's own env steps"""
-        total = int(total_timesteps if total_timesteps is not None else self.cfg.total_timesteps)
-        start_steps = self.num_timesteps
-        it = 0
-        t0 = time.time()
-        loggers = self.make_loggers(getattr(self, "progress_csv_paths", None)) if self.monitor is not None else None
-        while self.num_timesteps - start_steps < total:
-            self.collect_rollouts()
-            self.train()
-            it += 1
-            if log_every and it % log_every == 0 and loggers is not None:
-                self.log_monitor(loggers, it)     # SB3's table (and progress.csv where progress_csv_paths names one per replica)
-            elif log_every and it % log_every == 0 and self.dist.rank == 0:
-                dt = time.time() - t0
-                stages = [cur.read().stage_index if cur is not None else -1 for cur in self.curricula]
-                stats = self._stats_rows()
-                print(f"[ppo] it={it} steps={self.num_timesteps} fps={(self.num_timesteps - start_steps) / dt:,.0f} "
-                      f"stage={stages[0] if self.K == 1 else stages} rew={self.rew_buf.mean().item():.4f} {stats[0] if self.K == 1 else stats}",
-                      flush=True)
+        run_training(self, int(total_timesteps if total_timesteps is not None else self.cfg.total_timesteps), log_every=log_every, status=status_line)
         return self
+
+
+def run_training(trainer: PPO, total_timesteps: int, *, after_rollout=None, after_update=None, log_every: int = 0, status=None,
+                 csv_paths: list[Any] | None = None, tag: str | None = None) -> tuple[float, int]:
+    """THE training loop of every trainer (PPO.learn, the three CLIs and their --seeds forms): iterations of rollout and update until
+    ``trainer`` (a PPO or any population; the step clock counts each replica's own env steps) has taken ``total_timesteps`` env steps from
+    where its clock stands.  Per iteration: ``collect_rollouts()``, ``after_rollout(trainer)`` (the teacher anchor), ``train()``,
+    ``after_update(trainer, steps_taken)`` (gates, periodic checkpoints); then every ``log_every`` iterations (0: never) either the
+    monitor's record per replica -- SB3's table, a row of ``csv_paths[k]`` where given, and under the line ``[tag] it=.. replica <name>``
+    where a population's caller passes ``tag`` -- or, without a monitor and on rank 0, the line ``status(trainer, it, steps_taken,
+    elapsed_seconds)``.  The loggers start here, on the clock as the loop finds it.  Returns (wall seconds after a device synchronise, env
+    steps taken)."""
+    t0 = time.time()
+    start, it = trainer.num_timesteps, 0
+    loggers = trainer.make_loggers(csv_paths) if trainer.monitor is not None else None
+    while trainer.num_timesteps - start < total_timesteps:
+        trainer.collect_rollouts()
+        if after_rollout is not None:
+            after_rollout(trainer)
+        trainer.train()
+        it += 1
+        if after_update is not None:
+            after_update(trainer, trainer.num_timesteps - start)
+        if not log_every or it % log_every:
+            continue
+        if loggers is not None:
+            for k, row in enumerate(trainer.monitor_rows()):
+                if tag is not None:
+                    print(f"[{tag}] it={it} replica {trainer.replica_names[k]}", flush=True)
+                loggers[k].log(row, iteration=it, total_timesteps=trainer.num_timesteps)
+        elif status is not None and trainer.dist.rank == 0:
+            print(status(trainer, it, trainer.num_timesteps - start, time.time() - t0), flush=True)
+    torch.cuda.synchronize(trainer.device)
+    return time.time() - t0, trainer.num_timesteps - start
+
+
+def status_line(ppo: PPO, it: int, steps: int, elapsed: float) -> str:
+    """PPO.learn's and train.py's line at the logging cadence (a population through learn(): the stages and statistics as lists)"""
+    stages = [cur.read().stage_index if cur is not None else -1 for cur in ppo.curricula]
+    stats = ppo._stats_rows()
+    return (f"[ppo] it={it} steps={ppo.num_timesteps} fps={steps / elapsed:,.0f} stage={stages[0] if ppo.K == 1 else stages} "
+            f"rew={ppo.rew_buf.mean().item():.4f} {stats[0] if ppo.K == 1 else stats}")
 
 
 class InferencePolicy:

@@ -14,19 +14,17 @@ config 2; the reference never sets net_arch, i.e. SB3's 64).
 from __future__ import annotations
 
 import argparse
+import functools
 import json
-import os
 import shutil
-import time
 from pathlib import Path
 from typing import Any
-
-import torch
 
 from . import checkpoint
 from . import config as kcfg
 from .curriculum import PointCurriculum
-from .ppo import PPO, Dist, PPOConfig
+from .ppo import PPO, Dist, PPOConfig, run_training, status_line
+from .trainer_cli import add_shared_flags, apply_switches, process_context, refuse_population_under_dp, replica_extra, write_json
 from .vec_env import ArmKinematicVecEnv
 
 
@@ -36,23 +34,14 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--run-id", default="workspace_expand_mi355x_001")
     p.add_argument("--artifact-root")
     p.add_argument("--total-timesteps", type=int)
-    seeds = p.add_mutually_exclusive_group()
-    seeds.add_argument("--seed", type=int)
-    seeds.add_argument("--seeds", help="comma-separated seeds trained together as one population (2x64 / 2x128 nets, one GPU); seed s writes "
-                                       "the artefacts of a --seed s run under <artifact-root>/seed_<s>/, plus population_summary.json")
     p.add_argument("--resume-from")
-    p.add_argument("--sweep", action="append", metavar="KEY=v1,v2", help="with --seeds: train every seed with each value of a PPO hyper-parameter "
-                   "(repeatable; replicas = seeds x values, seed-major, at most 16); each replica writes what --seed s with those settings writes "
-                   "under <artifact-root>/seed_<s>_<key>_<value>/")
     p.add_argument("--no-gate-callback", action="store_true")
     p.add_argument("--per-replica-eval", action="store_true", help="with --seeds: evaluate the replicas one after another (K gate evaluations per gate "
                    "instant) instead of all of them in one population evaluation")
     p.add_argument("--n-envs", type=int, default=4096, help="environments per GPU")
     p.add_argument("--n-steps", type=int, default=128)
     p.add_argument("--batch-size", type=int, default=0, help="global minibatch; 0 = n_envs*n_steps*world/64")
-    p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--learning-rate", type=float)
-    p.add_argument("--log-every", type=int, default=1)
     g = p.add_mutually_exclusive_group()
     g.add_argument("--whole-episode-eval", dest="whole_episode_eval", action="store_const", const=True, default=None,
                    help="run the gate and final evaluations with all env steps of a phase in one launch (kp1_eval_episodes) where the one-launch "
@@ -64,9 +53,6 @@ def build_arg_parser() -> argparse.ArgumentParser:
     r.add_argument("--whole-rollout", dest="whole_rollout", action="store_const", const=True, default=None,
                    help="run all env steps of a rollout in one launch per span (kp1_rollout_run; sets KP1_ROLLOUT_RUN=1) where it is covered: "
                         "hidden 64 / 128, one process, no tracker or at most 32 envs per seed; same results bit for bit")
-    r.add_argument("--train-tile", dest="train_tile", action="store_true",
-                   help="hidden 64 / 128: forward, loss and backward of the optimiser step in one tile launch (train_tile128_kernel; sets "
-                        "KP1_TRAIN_TILE=1); without the flag KP1_TRAIN_TILE decides, and unset it is the layer-wise kernels")
     r.add_argument("--per-step-rollout", dest="whole_rollout", action="store_const", const=False,
                    help="keep one launch per env step (sets KP1_ROLLOUT_RUN=0); without either flag KP1_ROLLOUT_RUN decides, and unset it is "
                         "the trainer's default (the per-step loop)")
@@ -74,15 +60,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
                    help="with --seed: run the gate and final evaluations as the launch sequence per env step (evaluate.run_episodes) instead of "
                         "the one-launch step (kp1_eval_step); the two forms agree bit for bit except in the action-magnitude floats "
                         "(final / mean action magnitude), which may differ by an ulp (and a ready bit, should a norm sit on its threshold to the last bit)")
-    from . import monitor as _monitor
-
-    _monitor.add_cli_flags(p)
+    add_shared_flags(p, artifact_flag="<artifact-root>", sweep_under="<artifact-root>/", train_tile_group=r)
     return p
-
-
-def write_json(path: Path, payload: dict[str, Any]) -> None:
-    path.parent.mkdir(parents=True, exist_ok=True)
-    path.write_text(json.dumps(payload, indent=2))
 
 
 class WorkspaceEvalGate:
@@ -177,22 +156,13 @@ def population_gate_iteration(gates: dict[int, WorkspaceEvalGate], pop, env_cfg:
 
 def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
-    if args.sweep and args.seeds is None:
-        raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
-    if args.train_tile:
-        os.environ["KP1_TRAIN_TILE"] = "1"     # read by PPO._setup (every trainer class) when it creates the MLP handle
-    if args.whole_rollout is not None:
-        os.environ["KP1_ROLLOUT_RUN"] = "1" if args.whole_rollout else "0"     # read by PPO / ApproachPopulationPPO at every rollout
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local_rank)
-    if world > 1:
-        import torch.distributed as dist
+    apply_switches(args)
+    with process_context(args) as proc:
+        return _main(args, proc)
 
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
 
+def _main(args, proc) -> dict[str, Any]:
+    world, rank, local_rank = proc.world, proc.rank, proc.device
     cfg = kcfg.load_workspace_expansion_config(args.config)
     env_cfg = kcfg.to_env_config(cfg)
     algo = kcfg.to_algorithm_kwargs(cfg, "ppo")
@@ -224,8 +194,7 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     env = ArmKinematicVecEnv(env_cfg, n_envs, device=local_rank, seed=seed, first_env_id=rank * n_envs)
     curriculum = _make_curriculum(cfg, env_cfg, ws, local_rank)
     pcfg = PPOConfig.from_algo_kwargs(model_kwargs, n_steps=args.n_steps, batch_size=batch, hidden=hidden, seed=seed)
-    ppo = PPO(env, pcfg, curriculum=curriculum, dist=dist_glue, backend="hip", monitor=monitor)     # 2x64 / 2x128 / 2x256 all run on the MFMA kernels
-    loggers = ppo.make_loggers([root / "progress.csv"]) if monitor else None
+    ppo = proc.trainer = PPO(env, pcfg, curriculum=curriculum, dist=dist_glue, backend="hip", monitor=monitor)     # 2x64 / 2x128 / 2x256 all run on the MFMA kernels
     if resume and Path(resume).exists():
         # PPO.load(resume, env=vec_env): weights, Adam state and the saved algorithm constants; the YAML's learning rate is re-applied
         ppo.load_checkpoint(resume, restore_hyperparameters=True)
@@ -239,34 +208,13 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
         gate = _make_gate(root, env_cfg, finisher_policy, finisher_cfg, ws, gate_cfg, local_rank, one_launch=False if args.multi_launch_eval else None,
                           whole_episodes=args.whole_episode_eval)
 
-    t0 = time.time()
-    total = int(algo.get("total_timesteps", 100_000))
-    start_steps, it = ppo.num_timesteps, 0
-    while ppo.num_timesteps - start_steps < total:     # PPO.learn, one iteration at a time so the gate can look in between
-        ppo.collect_rollouts()
-        ppo.train()
-        it += 1
-        if gate is not None:
-            gate.on_iteration(ppo, env_cfg)
-        if args.log_every and it % args.log_every == 0 and loggers is not None:
-            ppo.log_monitor(loggers, it)
-        elif args.log_every and it % args.log_every == 0 and rank == 0:
-            stage = curriculum.read().stage_index if curriculum is not None else -1
-            print(f"[ppo] it={it} steps={ppo.num_timesteps} fps={(ppo.num_timesteps - start_steps) / (time.time() - t0):,.0f} stage={stage} "
-                  f"rew={ppo.rew_buf.mean().item():.4f} {ppo.last_stats}", flush=True)
-    torch.cuda.synchronize()
-    wall = time.time() - t0
-    summary: dict[str, Any] = {}
-    if rank == 0:
-        summary = _final_artifacts(root, ppo, env_cfg, args=args, resume=resume, n_envs=n_envs * world, world=world, curriculum=curriculum,
-                                   finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, ws=ws, gate_cfg=gate_cfg, device=local_rank, wall=wall)
-    if world > 1:
-        import torch.distributed as dist
-
-        dist.barrier()
-        ppo.dist.close()
-        dist.destroy_process_group()
-    return summary
+    # PPO.learn, with the gate looking in after every iteration
+    wall, _ = run_training(ppo, int(algo.get("total_timesteps", 100_000)), after_update=None if gate is None else lambda p, _steps: gate.on_iteration(p, env_cfg),
+                           log_every=args.log_every, status=status_line, csv_paths=[root / "progress.csv"])
+    if rank != 0:
+        return {}
+    return _final_artifacts(root, ppo, env_cfg, args=args, resume=resume, n_envs=n_envs * world, world=world, curriculum=curriculum,
+                            finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, ws=ws, gate_cfg=gate_cfg, device=local_rank, wall=wall)
 
 
 def _start_artifacts(root: Path, args, cfg: dict[str, Any]) -> None:
@@ -356,12 +304,11 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
     the saved algorithm constants; the step clock starts at zero).  The gate and the final evaluation run once per gate instant for all
     replicas (evaluate_workspace_expansion_population); --per-replica-eval evaluates them one after another."""
     from .curriculum import PointCurriculumPopulation
-    from .population import ApproachPopulationPPO, learn_population, plan_replicas, population_summary, resolve_resume_population
+    from .population import ApproachPopulationPPO, plan_replicas, population_status, population_summary, resolve_resume_population
     from .vec_env import ArmKinematicPopulationVecEnv
 
     seeds, overrides, names = plan_replicas(args.seeds, args.sweep)
-    if world > 1:
-        raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
+    refuse_population_under_dp(world)
     # refusals before any device work: the replicas, the width, and the checkpoints a population cannot resume together
     resume_paths = resolve_resume_population(resume, seeds, names) if resume and Path(resume).exists() else None
     hidden = checkpoint.hidden_for_run(args.hidden, resume_paths[0] if resume_paths else None)
@@ -376,8 +323,6 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
     from . import monitor as _monitor
 
     pop = ApproachPopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides, monitor=_monitor.cli_monitor(args))
-    if pop.monitor is not None:
-        pop.progress_csv_paths = [r / "progress.csv" for r in roots]
     if resume_paths is not None:
         pop.load_init_checkpoints(resume_paths, restore_timesteps=False)
         print(f"Resuming workspace expansion of every replica from {resume}")
@@ -392,7 +337,7 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
 
     fused_eval = not args.per_replica_eval
 
-    def on_iteration(p) -> None:
+    def on_iteration(p, _steps) -> None:
         if gates and fused_eval:
             population_gate_iteration(gates, p, env_cfg)
             return
@@ -400,7 +345,9 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
             if k in gates:
                 gates[k].on_iteration(p.replica(k), env_cfg)
 
-    wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), on_iteration=on_iteration, log_every=args.log_every, tag="ppo-population")
+    tag = "ppo-population"
+    wall, _ = run_training(pop, int(algo.get("total_timesteps", 100_000)), after_update=on_iteration, log_every=args.log_every,
+                           status=functools.partial(population_status, tag=tag), csv_paths=[r / "progress.csv" for r in roots], tag=tag)
     rows = []
     finals: list[Any] = [None] * len(seeds)
     if finisher_policy is not None and fused_eval:      # the final evaluation of every replica: one population evaluation
@@ -413,10 +360,9 @@ def _main_population(args, cfg, env_cfg, algo, ws, root: Path, batch: int, model
                                                             whole_episodes=getattr(args, "whole_episode_eval", None))
     for k, s in enumerate(seeds):
         rep = pop.replica(k)
-        extra = {"seed": s} if overrides is None else {"seed": s, "replica": names[k], "overrides": dict(overrides[k])}
         summ = _final_artifacts(roots[k], rep, env_cfg, args=args, resume=resume_paths[k] if resume_paths else None, n_envs=args.n_envs, world=1,
                                 curriculum=pop.curricula[k], finisher_policy=finisher_policy, finisher_cfg=finisher_cfg, ws=ws, gate_cfg=gate_cfg,
-                                device=device, wall=wall, extra=extra, final_eval_payload=finals[k])
+                                device=device, wall=wall, extra=replica_extra(s, names[k], None if overrides is None else overrides[k]), final_eval_payload=finals[k])
         best = gates[k].best_score if k in gates and gates[k].best_score != float("-inf") else None
         rows.append({"seed": s, "artifact_root": str(roots[k]), "final_curriculum_stage": pop.curricula[k].read().stage_index if pop.curricula[k] else None,
                      "last_update_stats": summ["last_update_stats"], "best_score": best, "model_latest": summ["model_path"],

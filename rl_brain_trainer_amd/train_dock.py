@@ -10,18 +10,16 @@ flags, same artefact names) on the device engine, plus the dock reverse curricul
 from __future__ import annotations
 
 import argparse
+import functools
 import json
-import os
-import time
 from pathlib import Path
 from typing import Any
-
-import torch
 
 from . import checkpoint
 from . import config as kcfg
 from .finisher_tools import DockReverseCurriculum
-from .ppo import PPO, Dist, PPOConfig
+from .ppo import PPO, Dist, PPOConfig, run_training
+from .trainer_cli import add_shared_flags, apply_switches, process_context, refuse_population_under_dp, replica_extra, write_json
 from .vec_env import ArmKinematicVecEnv
 
 
@@ -31,24 +29,12 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--run-id", default="dock_policy")
     p.add_argument("--artifact-root")
     p.add_argument("--total-timesteps", type=int)
-    seeds = p.add_mutually_exclusive_group()
-    seeds.add_argument("--seed", type=int)
-    seeds.add_argument("--seeds", help="comma-separated seeds trained together as one population (2x64 / 2x128 nets, one GPU); seed s writes "
-                                       "the artefacts of a --seed s run under <artifact-root>/seed_<s>/, plus population_summary.json")
-    p.add_argument("--sweep", action="append", metavar="KEY=v1,v2", help="with --seeds: train every seed with each value of a PPO hyper-parameter "
-                   "(repeatable; replicas = seeds x values, seed-major, at most 16); each replica writes what --seed s with those settings writes "
-                   "under seed_<s>_<key>_<value>/")
     p.add_argument("--resume-from", help="a checkpoint zip; with --seeds also the artifact root of an earlier --seeds run (seed s resumes "
                                           "from seed_<s>/model_latest.zip)")
     p.add_argument("--n-envs", type=int, default=4096, help="environments per GPU")
     p.add_argument("--n-steps", type=int, default=64)
     p.add_argument("--batch-size", type=int, default=0, help="global minibatch; 0 = n_envs*n_steps*world/64")
-    p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--eval-episodes", type=int, default=512)
-    p.add_argument("--log-every", type=int, default=1)
-    from . import monitor as _monitor
-
-    _monitor.add_cli_flags(p)
     g = p.add_mutually_exclusive_group()
     g.add_argument("--whole-episode-eval", dest="whole_episode_eval", action="store_const", const=True, default=None,
                    help="run the final dock evaluation with all its env steps in one launch (kp1_eval_episodes; implies --one-launch-eval); "
@@ -60,8 +46,7 @@ def build_arg_parser() -> argparse.ArgumentParser:
                    help="run the final dock evaluation with the one-launch step (kp1_eval_step) instead of the launch sequence per env step "
                         "(evaluate.run_episodes, the default here: the one-launch form has not been timed on this workload); the summaries "
                         "are equal, the two forms differ only in the action-magnitude floats, by an ulp")
-    p.add_argument("--train-tile", dest="train_tile", action="store_true", help="hidden 64 / 128: forward, loss and backward of the optimiser step in one tile launch "
-                   "(train_tile128_kernel; sets KP1_TRAIN_TILE=1); without the flag KP1_TRAIN_TILE decides, and unset it is the layer-wise kernels")
+    add_shared_flags(p, artifact_flag="<artifact-root>")
     return p
 
 
@@ -83,21 +68,22 @@ def evaluate_dock(ppo: PPO, env_cfg: kcfg.EnvConfig, *, episodes: int, seed: int
             "mean_episode_length": float(res["step_count"].float().mean())}
 
 
+def status_line(ppo: PPO, it: int, steps: int, elapsed: float) -> str:
+    """the --seed run's line at the logging cadence"""
+    stage = ppo.curriculum.current_stage_index if ppo.curriculum is not None else -1
+    return (f"[ppo-dock] it={it} steps={ppo.num_timesteps} fps={steps / elapsed:,.0f} stage={stage} "
+            f"rew={ppo.rew_buf.mean().item():.4f} {ppo.last_stats}")
+
+
 def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
-    if args.sweep and args.seeds is None:
-        raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
-    if args.train_tile:
-        os.environ["KP1_TRAIN_TILE"] = "1"     # read by PPO._setup (every trainer class) when it creates the MLP handle
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local_rank)
-    if world > 1:
-        import torch.distributed as dist
+    apply_switches(args)
+    with process_context(args) as proc:
+        return _main(args, proc)
 
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
+
+def _main(args, proc) -> dict[str, Any]:
+    world, rank, local_rank = proc.world, proc.rank, proc.device
     cfg = kcfg.load_dock_config(args.config)
     base_dirs = (Path(args.config).parent,) if args.config else ()
     env_cfg = kcfg.to_env_config(cfg, handoff_base_dirs=base_dirs)
@@ -130,40 +116,20 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     if bool(cur_cfg.get("enabled", False)):
         curriculum = DockReverseCurriculum(stages=list(cur_cfg.get("stages", [])), window_episodes=int(cur_cfg.get("window_episodes", 100)),
                                            handoff_base_dirs=base_dirs)
-    ppo = PPO(env, pcfg, curriculum=curriculum, dist=dist_glue, backend="hip", monitor=monitor)
+    ppo = proc.trainer = PPO(env, pcfg, curriculum=curriculum, dist=dist_glue, backend="hip", monitor=monitor)
     if args.resume_from and Path(args.resume_from).exists():
         # PPO.load(resume, env=vec_env) + learn(reset_num_timesteps=False) (train_dock_policy.py:89-102)
         ppo.load_checkpoint(args.resume_from, restore_timesteps=True, restore_hyperparameters=True)
         if rank == 0:
             print(f"Resuming dock policy from {args.resume_from}")
 
-    total = int(algo.get("total_timesteps", 100_000))
-    t0 = time.time()
-    start, it = ppo.num_timesteps, 0
-    loggers = ppo.make_loggers([root / "progress.csv"]) if monitor else None
-    while ppo.num_timesteps - start < total:
-        ppo.collect_rollouts()
-        ppo.train()
-        it += 1
-        if args.log_every and it % args.log_every == 0 and loggers is not None:
-            ppo.log_monitor(loggers, it)
-        elif args.log_every and it % args.log_every == 0 and rank == 0:
-            stage = curriculum.current_stage_index if curriculum is not None else -1
-            print(f"[ppo-dock] it={it} steps={ppo.num_timesteps} fps={(ppo.num_timesteps - start) / (time.time() - t0):,.0f} stage={stage} "
-                  f"rew={ppo.rew_buf.mean().item():.4f} {ppo.last_stats}", flush=True)
-    torch.cuda.synchronize()
-    wall = time.time() - t0
-    summary: dict[str, Any] = {}
-    if rank == 0:
-        summary = _final_artifacts(root, ppo, env_cfg, args=args, cfg=cfg, curriculum=curriculum, resume=args.resume_from, n_envs=n_envs * world,
-                                   world=world, seed=seed, device=local_rank, wall=wall)
-        print(json.dumps(summary["dock_eval_summary"], indent=2))
-    if world > 1:
-        import torch.distributed as dist
-
-        dist.barrier()
-        ppo.dist.close()
-        dist.destroy_process_group()
+    wall, _ = run_training(ppo, int(algo.get("total_timesteps", 100_000)), log_every=args.log_every, status=status_line,
+                           csv_paths=[root / "progress.csv"])
+    if rank != 0:
+        return {}
+    summary = _final_artifacts(root, ppo, env_cfg, args=args, cfg=cfg, curriculum=curriculum, resume=args.resume_from, n_envs=n_envs * world,
+                               world=world, seed=seed, device=local_rank, wall=wall)
+    print(json.dumps(summary["dock_eval_summary"], indent=2))
     return summary
 
 
@@ -176,13 +142,12 @@ def _final_artifacts(root: Path, ppo, env_cfg: kcfg.EnvConfig, *, args, cfg: dic
     eval_summary = evaluate_dock(ppo, env_cfg, episodes=args.eval_episodes, seed=seed + 10_000, device=device,
                                  one_launch=None if getattr(args, "one_launch_eval", False) or getattr(args, "whole_episode_eval", None) else False,
                                  whole_episodes=getattr(args, "whole_episode_eval", None))
-    (root / "dock_eval").mkdir(exist_ok=True)
-    (root / "dock_eval" / "dock_eval_summary.json").write_text(json.dumps(eval_summary, indent=2))
+    write_json(root / "dock_eval" / "dock_eval_summary.json", eval_summary)
     summary = {"policy_type": "dock", "algorithm": "ppo", "run_id": args.run_id, "checkpoint_format": {"layout": "stable-baselines3 zip", "sb3_loadable": False, "finish_with": "tools/finish_sb3_zip.py (needs stable-baselines3==2.8.0)"}, "config": cfg, "model_path": str(latest) + ".zip",
                "resume_from": str(resume) if resume else None, "n_envs": n_envs, "device": f"{world}x MI355X",
                "dock_eval_summary": eval_summary, "dock_reverse_curriculum": curriculum.summary() if curriculum is not None else None,
                "num_timesteps": ppo.num_timesteps, "wall_seconds": wall, "env_steps_per_second": ppo.num_timesteps / wall, "update_form": ppo.update_form, **(extra or {})}
-    (root / "training_summary.json").write_text(json.dumps(summary, indent=2))
+    write_json(root / "training_summary.json", summary)
     return summary
 
 
@@ -193,12 +158,11 @@ def _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root: Path, w
     earlier --seeds run (seed s starts from seed_<s>/model_latest.zip).  The selection score of population_summary.json is each seed's dock
     evaluation success rate."""
     from .finisher_tools import DockReverseCurriculumPopulation
-    from .population import DockPopulationPPO, learn_population, plan_replicas, population_summary, resolve_resume_population
+    from .population import DockPopulationPPO, plan_replicas, population_status, population_summary, resolve_resume_population
     from .vec_env import ArmKinematicPopulationVecEnv
 
     seeds, overrides, names = plan_replicas(args.seeds, args.sweep)
-    if world > 1:
-        raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
+    refuse_population_under_dp(world)
     # refusals before any device work: the seeds, the width, and the checkpoints a population cannot resume together
     resume_paths = resolve_resume_population(args.resume_from, seeds, names)
     n_envs = args.n_envs
@@ -222,9 +186,9 @@ def _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root: Path, w
     roots = [root / n for n in names]
     for r in roots:
         r.mkdir(parents=True, exist_ok=True)
-    if pop.monitor is not None:
-        pop.progress_csv_paths = [r / "progress.csv" for r in roots]
-    wall = learn_population(pop, int(algo.get("total_timesteps", 100_000)), log_every=args.log_every, tag="ppo-dock-population")
+    tag = "ppo-dock-population"
+    wall, _ = run_training(pop, int(algo.get("total_timesteps", 100_000)), log_every=args.log_every,
+                           status=functools.partial(population_status, tag=tag), csv_paths=[r / "progress.csv" for r in roots], tag=tag)
     rows = []
     for k, s in enumerate(seeds):
         rep = pop.replica(k)
@@ -232,11 +196,11 @@ def _main_population(args, cfg, env_cfg, algo, runtime, base_dirs, root: Path, w
         cfg_k = cur.config if cur is not None else env_cfg
         resume = resume_paths[k] if resume_paths is not None else args.resume_from
         summ = _final_artifacts(roots[k], rep, cfg_k, args=args, cfg=cfg, curriculum=cur, resume=resume, n_envs=n_envs, world=1, seed=s,
-                                device=device, wall=wall, extra={"seed": s} if overrides is None else {"seed": s, "replica": names[k], "overrides": dict(overrides[k])})
+                                device=device, wall=wall, extra=replica_extra(s, names[k], None if overrides is None else overrides[k]))
         rows.append({"seed": s, "artifact_root": str(roots[k]), "final_curriculum_stage": cur.current_stage_index if cur is not None else None,
                      "last_update_stats": rep.last_stats, "best_score": summ["dock_eval_summary"]["success_rate"], "model_latest": summ["model_path"]})
     summary = population_summary(pop, rows, wall_seconds=wall, selection="dock evaluation success_rate")
-    (root / "population_summary.json").write_text(json.dumps(summary, indent=2))
+    write_json(root / "population_summary.json", summary)
     pop.close()
     if curriculum is not None:
         curriculum.close()

@@ -24,8 +24,8 @@ the sequential evaluation and the gate.
 from __future__ import annotations
 
 import argparse
+import functools
 import json
-import os
 import shutil
 import time
 from pathlib import Path
@@ -36,11 +36,12 @@ import torch
 from . import checkpoint
 from . import config as kcfg
 from . import route_config as rcfg
-from .ppo import PPO, Dist, PPOConfig
+from .ppo import PPO, Dist, PPOConfig, run_training
 from .route_curriculum import (RoutePrefixCurriculumDevice, evaluate_route_gate, evaluate_sequential_route, evaluate_sequential_route_batch,
                                sliced_evaluate)
 from .route_env import RouteVecEnv
 from .teacher_anchor import PopulationTeacherAnchor, RouteTeacherAnchor, TeacherAnchorConfig
+from .trainer_cli import add_shared_flags, apply_switches, process_context, refuse_population_under_dp, write_json
 
 
 def load_route_training_config(path: str | Path | None) -> dict[str, Any]:
@@ -56,25 +57,13 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--config", required=True)
     p.add_argument("--route-path")
     p.add_argument("--init-checkpoint")
-    p.add_argument("--sweep", action="append", metavar="KEY=v1,v2", help="with --seeds: train every seed with each value of a PPO hyper-parameter "
-                   "(repeatable; replicas = seeds x values, seed-major, at most 16); each replica writes what --seed s with those settings writes "
-                   "under seed_<s>_<key>_<value>/")
     p.add_argument("--run-id", default="route_curriculum")
     p.add_argument("--output-dir")
     p.add_argument("--total-timesteps", type=int)
-    seeds = p.add_mutually_exclusive_group()
-    seeds.add_argument("--seed", type=int)
-    seeds.add_argument("--seeds", help="comma-separated seeds trained together as one population (2x64 / 2x128 nets, one GPU); seed s writes "
-                                       "the artefacts of a --seed s run under <output-dir>/seed_<s>/, plus population_summary.json")
     p.add_argument("--n-envs", type=int, default=0, help="device environments (0 = training.n_envs of the YAML)")
     p.add_argument("--n-steps", type=int, default=0, help="rollout length (0 = the YAML's n_steps)")
     p.add_argument("--batch-size", type=int, default=0, help="minibatch (0 = the YAML's batch_size)")
-    p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--device", type=int, default=0, help="GPU of a single-process run (under torchrun: LOCAL_RANK)")
-    p.add_argument("--log-every", type=int, default=0)
-    from . import monitor as _monitor
-
-    _monitor.add_cli_flags(p)
     p.add_argument("--one-launch-rollout", action="store_true", help="run every rollout step as ONE launch (kp1_mlp_forward_route_step: sets "
                    "KP1_FUSED_ROUTE_ROLLOUT=1; fp32, hidden 64 / 128, reward components off, not data parallel -- otherwise the launch "
                    "sequence stays); bit-identical to the default, for --seed and --seeds runs")
@@ -84,33 +73,48 @@ def build_arg_parser() -> argparse.ArgumentParser:
                    "chained final evaluation issues its lock steps -- the launch sequence, one launch per lock step "
                    "(kp1_mlp_forward_route_chain_step) or one launch per span of lock steps (kp1_route_chain_run); same files bit for bit. "
                    "Default: route_curriculum.CHAIN_FORM_DEFAULT.  --per-replica-eval and --seed keep their evaluators")
-    p.add_argument("--train-tile", dest="train_tile", action="store_true", help="hidden 64 / 128: forward, loss and backward of the optimiser step in one tile launch "
-                   "(train_tile128_kernel; sets KP1_TRAIN_TILE=1); without the flag KP1_TRAIN_TILE decides, and unset it is the layer-wise kernels")
+    add_shared_flags(p, artifact_flag="<output-dir>", log_every=0)
     return p
+
+
+def _checkpoint_hook(checkpoint_freq: int, save):
+    """PeriodicCheckpointCallback (callbacks.py) as run_training's ``after_update``: ``save(trainer, steps_taken)`` whenever the steps of
+    this run pass the next multiple of ``checkpoint_freq``"""
+    due = checkpoint_freq
+
+    def after_update(trainer, steps: int) -> None:
+        nonlocal due
+        if steps >= due:
+            save(trainer, steps)
+            due += checkpoint_freq
+
+    return after_update
+
+
+def status_line(ppo: PPO, it: int, steps: int, elapsed: float, *, anchor=None) -> str:
+    """the --seed run's line at the logging cadence"""
+    s = ppo.curriculum.summary()
+    return (f"[route] it={it} steps={ppo.num_timesteps} fps={steps / elapsed:,.0f} prefix={s['prefix_end_index']} "
+            f"succ={s['recent_success_rate']:.3f} rew={ppo.rew_buf.mean().item():.4f} anchor={anchor.last_loss if anchor else 0.0:.5f}")
+
+
+def population_status_line(pop, it: int, steps: int, elapsed: float) -> str:
+    """the --seeds run's line at the logging cadence"""
+    stages = [pop.pop_curriculum.summary(k)["prefix_end_index"] for k in range(pop.K)]
+    anchor = pop.teacher_anchor
+    return (f"[route-population] it={it} steps/replica={pop.num_timesteps} aggregate fps={pop.K * steps / elapsed:,.0f} prefixes={stages}"
+            + (f" anchor={[round(v, 5) for v in anchor.last_loss]}" if anchor is not None else ""))
 
 
 def main(argv: list[str] | None = None) -> dict[str, Any]:
     args = build_arg_parser().parse_args(argv)
-    if args.sweep and args.seeds is None:
-        raise ValueError("--sweep needs --seeds: a sweep trains its settings together as one population")
-    if args.train_tile:
-        os.environ["KP1_TRAIN_TILE"] = "1"     # read by PPO._setup (every trainer class) when it creates the MLP handle
-    if args.one_launch_rollout:
-        os.environ["KP1_FUSED_ROUTE_ROLLOUT"] = "1"     # read by PPO / RoutePopulationPPO at every rollout step (ppo.fused_route_rollout_covered)
-    import torch.distributed as dist
+    apply_switches(args)
+    with process_context(args) as proc:     # WORLD_SIZE / RANK / LOCAL_RANK as torchrun sets them, or the caller's process group
+        return _main(args, proc)
 
-    # WORLD_SIZE / RANK / LOCAL_RANK as torchrun sets them; a process group the caller already initialised is used as it is
-    own_group = False
-    if dist.is_available() and dist.is_initialized():
-        world, rank = dist.get_world_size(), dist.get_rank()
-    else:
-        world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    device = int(os.environ["LOCAL_RANK"]) if "LOCAL_RANK" in os.environ else args.device
-    torch.cuda.set_device(device)
-    if world > 1 and not dist.is_initialized():
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group(backend="nccl", device_id=torch.device("cuda", device))
-        own_group = True
+
+def _main(args, proc) -> dict[str, Any]:
+    world, rank, device = proc.world, proc.rank, proc.device
     cfg = load_route_training_config(args.config)
     route_cfg = cfg.get("route", {}) or {}
     route_path = Path(args.route_path or route_cfg["route_path"])
@@ -132,12 +136,8 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     seed = int(algo.get("seed") or 0)
     n_envs = int(args.n_envs or runtime_cfg.get("n_envs", 1))     # per rank
     if args.seeds is not None:
-        try:
-            return _main_population(args, cfg, route_cfg, route_path, route_q, prefixes, env_cfg, runtime_cfg, algo, init_checkpoint, root, n_envs,
-                                    world, device)
-        finally:
-            if own_group:
-                dist.destroy_process_group()
+        return _main_population(args, cfg, route_cfg, route_path, route_q, prefixes, env_cfg, runtime_cfg, algo, init_checkpoint, root, n_envs,
+                                world, device)
     from . import monitor as _monitor
 
     dist_glue = Dist()
@@ -154,7 +154,7 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
     # the prefix curriculum: a device tracker after every env step (the rollout stays one hipGraph replay); data parallel: per-step episode
     # records, exchanged and replayed once per chunk of KP1_DONE_EXCHANGE_STEPS steps
     curriculum = RoutePrefixCurriculumDevice.from_config(cfg, W)
-    ppo = PPO(env, pcfg, curriculum=curriculum, dist=dist_glue, backend="hip", monitor=monitor)
+    ppo = proc.trainer = PPO(env, pcfg, curriculum=curriculum, dist=dist_glue, backend="hip", monitor=monitor)
     if init_checkpoint:
         # PPO.load(..., env=vec_env) + learn(reset_num_timesteps=False): weights, Adam state, step clock; the YAML's learning rate wins
         ppo.load_checkpoint(init_checkpoint, restore_timesteps=True, restore_hyperparameters=True)
@@ -167,42 +167,21 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
         # every rank draws the same batch from the same default_rng(0) stream and steps identical parameters: the ranks stay in step
         anchor = RouteTeacherAnchor(anchor_cfg)
         anchor.on_training_start(ppo)
-    checkpoint_freq = max(int(runtime_cfg.get("checkpoint_freq", 250_000)), 1)
-    next_checkpoint = checkpoint_freq
 
-    t0 = time.time()
-    start_steps, it = ppo.num_timesteps, 0
-    loggers = ppo.make_loggers([root / "progress.csv"]) if monitor else None
-    while ppo.num_timesteps - start_steps < total:
-        ppo.collect_rollouts()
-        if anchor is not None:
-            anchor.on_rollout_end(ppo)            # BaseCallback._on_rollout_end: after the rollout, before the update
-        ppo.train()
-        it += 1
-        if ppo.num_timesteps - start_steps >= next_checkpoint:   # PeriodicCheckpointCallback (callbacks.py)
-            if rank == 0:
-                checkpoint.save(root / "checkpoints" / f"model_{ppo.num_timesteps - start_steps}_steps", ppo, env_cfg)
-            next_checkpoint += checkpoint_freq
-        if args.log_every and it % args.log_every == 0 and loggers is not None:
-            ppo.log_monitor(loggers, it)
-        elif args.log_every and it % args.log_every == 0 and rank == 0:
-            s = curriculum.summary()
-            print(f"[route] it={it} steps={ppo.num_timesteps} fps={(ppo.num_timesteps - start_steps) / (time.time() - t0):,.0f} prefix={s['prefix_end_index']} "
-                  f"succ={s['recent_success_rate']:.3f} rew={ppo.rew_buf.mean().item():.4f} anchor={anchor.last_loss if anchor else 0.0:.5f}", flush=True)
-    torch.cuda.synchronize()
-    wall = time.time() - t0
+    def save_checkpoint(p, steps: int) -> None:
+        if rank == 0:
+            checkpoint.save(root / "checkpoints" / f"model_{steps}_steps", p, env_cfg)
+
+    wall, steps = run_training(ppo, total, after_rollout=anchor.on_rollout_end if anchor is not None else None,     # (BaseCallback._on_rollout_end)
+                               after_update=_checkpoint_hook(max(int(runtime_cfg.get("checkpoint_freq", 250_000)), 1), save_checkpoint),
+                               log_every=args.log_every, status=functools.partial(status_line, anchor=anchor), csv_paths=[root / "progress.csv"])
     summary: dict[str, Any] = {}
     if rank == 0:     # the artefacts, the sequential evaluation and the gate
-        rate = (ppo.num_timesteps - start_steps) / max(wall, 1e-9)     # all ranks' env steps over the training loop
+        rate = steps / max(wall, 1e-9)     # all ranks' env steps over the training loop
         summary = _write_run_artifacts(args, cfg, route_cfg, route_path, route_q, env_cfg, init_checkpoint, root, ppo, curriculum.summary(),
                                        anchor.summary() if anchor is not None else {"enabled": False}, n_envs * world, world, wall, rate, device)
-    if ppo.dist.enabled:
-        dist.barrier()                           # the other ranks wait for rank 0's evaluation and artefacts
-        ppo.dist.close()
     curriculum.close()
     env.close()
-    if own_group:
-        dist.destroy_process_group()
     return summary
 
 
@@ -219,8 +198,7 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
     from .route_env import RoutePopulationVecEnv
 
     seeds, overrides, names = plan_replicas(args.seeds, args.sweep)
-    if world > 1:
-        raise ValueError("--seeds trains a population on one GPU; it does not combine with data parallel")
+    refuse_population_under_dp(world)
     hidden = checkpoint.hidden_for_run(args.hidden, init_checkpoint)
     if hidden not in (64, 128):
         raise ValueError(f"--seeds trains 2x64 / 2x128 nets: pass --hidden 64 or 128, or an --init-checkpoint of such a net (got a 2x{hidden} policy)")
@@ -246,39 +224,22 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
     pop = None
     try:
         from . import monitor as _monitor
-        from .population import replica_name
 
         pop = RoutePopulationPPO(seeds, pcfg, env, curriculum=curriculum, overrides=overrides, teacher_anchor=anchor, monitor=_monitor.cli_monitor(args))
-        loggers = pop.make_loggers([r / "progress.csv" for r in roots]) if pop.monitor is not None else None
         if init_checkpoint:
             pop.load_init_checkpoint(init_checkpoint)
             print(f"Resuming every route policy of the population from {init_checkpoint}")
-        checkpoint_freq = max(int(runtime_cfg.get("checkpoint_freq", 250_000)), 1)
-        next_checkpoint = checkpoint_freq
-        t0 = time.time()
-        start_steps, it = pop.num_timesteps, 0
-        while pop.num_timesteps - start_steps < total:
-            pop.collect_rollouts()
-            if anchor is not None:
-                anchor.on_rollout_end(pop)            # after the rollout, before the update, as the --seed loop does
-            pop.train()
-            it += 1
-            if pop.num_timesteps - start_steps >= next_checkpoint:
-                for k in range(pop.K):
-                    checkpoint.save(roots[k] / "checkpoints" / f"model_{pop.num_timesteps - start_steps}_steps", pop.replica(k), env_cfg)
-                next_checkpoint += checkpoint_freq
-            if args.log_every and it % args.log_every == 0 and loggers is not None:
-                for k, row in enumerate(pop.monitor_rows()):
-                    print(f"[route-population] it={it} replica {replica_name(pop.seeds[k], pop.overrides[k])}", flush=True)
-                    loggers[k].log(row, iteration=it, total_timesteps=pop.num_timesteps)
-            elif args.log_every and it % args.log_every == 0:
-                stages = [curriculum.summary(k)["prefix_end_index"] for k in range(pop.K)]
-                print(f"[route-population] it={it} steps/replica={pop.num_timesteps} aggregate fps="
-                      f"{pop.K * (pop.num_timesteps - start_steps) / (time.time() - t0):,.0f} prefixes={stages}"
-                      + (f" anchor={[round(v, 5) for v in anchor.last_loss]}" if anchor is not None else ""), flush=True)
-        torch.cuda.synchronize()
-        wall = time.time() - t0
-        rate = (pop.num_timesteps - start_steps) / max(wall, 1e-9)     # env steps of one replica per second of the population's training loop
+
+        def save_checkpoints(p, steps: int) -> None:
+            for k in range(p.K):
+                checkpoint.save(roots[k] / "checkpoints" / f"model_{steps}_steps", p.replica(k), env_cfg)
+
+        # (the anchor steps after the rollout, before the update, as in the --seed loop)
+        wall, steps = run_training(pop, total, after_rollout=anchor.on_rollout_end if anchor is not None else None,
+                                   after_update=_checkpoint_hook(max(int(runtime_cfg.get("checkpoint_freq", 250_000)), 1), save_checkpoints),
+                                   log_every=args.log_every, status=population_status_line, csv_paths=[r / "progress.csv" for r in roots],
+                                   tag="route-population")
+        rate = steps / max(wall, 1e-9)     # env steps of one replica per second of the population's training loop
         rows = []
         curriculum_summaries = [curriculum.summary(k) for k in range(pop.K)]
         evaluators: list[Any] = [None] * pop.K
@@ -307,7 +268,7 @@ def _main_population(args, cfg: dict[str, Any], route_cfg: dict[str, Any], route
         out = population_summary(pop, rows, wall_seconds=wall, selection=POPULATION_SELECTION)
         out["aggregate_env_steps_per_second"] = pop.K * rate     # the steps of this run, not the init checkpoint's clock
         out["teacher_anchor_steps"] = int(pop.actor_extra_steps)   # anchor steps every replica's actor tensors took on top of the common count
-        (root / "population_summary.json").write_text(json.dumps(out, indent=2, default=str))
+        write_json(root / "population_summary.json", out, default=str)
         print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "seeds": seeds, "best_seed": out["best_seed"],
                           "aggregate_env_steps_per_second": out["aggregate_env_steps_per_second"]}, indent=2))
         return out
@@ -345,7 +306,7 @@ def _write_run_artifacts(args, cfg: dict[str, Any], route_cfg: dict[str, Any], r
     W = int(route_q.shape[0])
     latest = root / "model_latest"
     checkpoint.save(latest, ppo, env_cfg)
-    (root / "curriculum_history.json").write_text(json.dumps(curriculum_summary, indent=2))
+    write_json(root / "curriculum_history.json", curriculum_summary)
 
     def policy(obs: torch.Tensor) -> torch.Tensor:
         return ppo.predict(obs.float().contiguous(), deterministic=True)
@@ -386,7 +347,7 @@ def _write_run_artifacts(args, cfg: dict[str, Any], route_cfg: dict[str, Any], r
     }
     # the sequential evaluation and the gate, after training (a population's chained evaluation: its share of the one batch call + its own files)
     summary["evaluation_wall_seconds"] = time.time() - t_eval + evaluation_wall_offset
-    (root / "training_summary.json").write_text(json.dumps(summary, indent=2, default=str))
+    write_json(root / "training_summary.json", summary, default=str)
     print(json.dumps({"run_id": args.run_id, "artifact_root": str(root), "model_latest": str(latest) + ".zip", "prefix_end_index": curriculum_summary["prefix_end_index"],
                       "env_steps_per_second": summary["env_steps_per_second"]}, indent=2))
     return summary
