@@ -201,7 +201,7 @@ int kp1_mlp_create_ex(int32_t device, int32_t hidden, int32_t obs_dim, int32_t m
  * n alone).  kp1_mlp_create / _create_ex make K = 1 handles.
  * Buffer layout of the entry points below for a K-replica handle (K = 1: the layouts documented at each entry point):
  *   kp1_mlp_pack_weights, kp1_mlp_adam_step: params, grad, exp_avg, exp_avg_sq are [K][num_params]; one clip norm per replica, one shared
- *     Adam step count (all replicas step together);
+ *     Adam step count (all replicas step together) unless a KL gate is set (kp1_mlp_set_kl_gate: one count per replica);
  *   kp1_mlp_forward: obs holds K * n rows, replica-major (replica r = rows [r n, (r + 1) n)); n = rows per replica; every output likewise
  *     [K][n][...];
  *   kp1_mlp_loss_grad: idx (required) is int64 [K][n], row indices into the shared obs / actions / old_log_prob / advantages / returns
@@ -377,6 +377,38 @@ int kp1_mlp_profile_read(kp1_mlp* m, float* out_us /* [KP1_MLP_PROFILE_SLOTS] */
  * produced it (no all-reduce in between), so the norm partials that call left are reused instead of a reduction launch. */
 int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, float* exp_avg_sq, float lr, float eps,
                       float max_grad_norm, int32_t step, int32_t flags, void* stream);
+
+/* ---- KL early stop (SB3 PPO's target_kl) as a device decision, per replica ---------------
+ * SB3's train() leaves its epochs once a minibatch's approx_kl exceeds 1.5 * target_kl: that minibatch's loss terms are logged, its
+ * optimiser step and everything after it are not taken.  An update replayed from a hipGraph cannot ask the host, so the handle keeps one
+ * record per replica and, while a gate is set, kp1_mlp_loss_grad and kp1_mlp_adam_step launch the gated forms of their last kernels:
+ *   finalize  the gradient and the norm partials as always.  A replica that has not stopped adds the minibatch to stats_out and counts it;
+ *             then, if (double)kl > threshold with kl = (KL sum) * inv_count as a float -- exactly what a zeroed stats_out[3] would receive --
+ *             it stops (stop_index = n_seen, stop_kl = kl), otherwise it advances ITS Adam step count.  A stopped replica adds nothing to
+ *             stats_out.  n_seen advances in every launch.
+ *   Adam      a stopped replica's launch returns before any store; the others step on their own count.
+ * The tile, GEMM and head kernels in front of them run as before (after a stop they compute a gradient nobody uses).  The step count is
+ * kept per replica from the moment a gate is set: KP1_MLP_OPT_STEP_COUNT then sets every replica's, kp1_mlp_kl_gate_read returns them. */
+typedef struct kp1_kl_gate {
+  double threshold;    /* 1.5 * target_kl, formed on the host; +inf = this replica never stops */
+  int32_t stopped;     /* 1 from the stopping minibatch on */
+  int32_t n_counted;   /* minibatches whose statistics entered stats_out since the gate was armed (the stopping one included) */
+  int32_t n_seen;      /* kp1_mlp_loss_grad calls since the gate was armed */
+  int32_t stop_index;  /* n_seen at the stopping minibatch, 0-based */
+  float stop_kl;       /* its approx_kl */
+  int32_t reserved0;
+} kp1_kl_gate;
+/* Set (n = K: one target per replica, host memory; NaN or <= 0 = no target for that replica) or clear (n = 0; target_kl_host may be NULL)
+ * the gate of a handle.  Setting it arms every record and, if no gate was set, gives every replica the handle's step count.  Refused
+ * before anything is written: NULL arguments, n other than 0 or K, a handle whose KP1_MLP_OPT_ACTOR_EXTRA_STEPS is non-zero, a `stream`
+ * that is being captured, and clearing while the replicas' step counts differ (KP1_ERR_INVALID: one shared count cannot hold them).
+ * While a gate is set kp1_mlp_anchor_loss_grad / kp1_mlp_anchor_adam_step return KP1_ERR_UNSUPPORTED (they read the shared count) and
+ * KP1_MLP_OPT_ACTOR_EXTRA_STEPS refuses a non-zero value.  Waits for `stream`. */
+int kp1_mlp_set_kl_gate(kp1_mlp* m, const double* target_kl_host, int32_t n, void* stream);
+/* a new train() call: clears stopped, n_counted, n_seen, stop_index and stop_kl of every replica in one launch (capturable) */
+int kp1_mlp_kl_gate_arm(kp1_mlp* m, void* stream);
+/* copy the K records and the K step counts to the host (either may be NULL); waits for `stream` */
+int kp1_mlp_kl_gate_read(kp1_mlp* m, kp1_kl_gate* out_host, int32_t* out_steps, void* stream);
 
 /* The route trainer's teacher-anchor side loss as a device step (handles on the layer-wise path: hidden 64 or 128, K = 1 or a population;
  * hidden 256 returns KP1_ERR_UNSUPPORTED).  For replica k

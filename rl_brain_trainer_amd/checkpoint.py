@@ -71,9 +71,10 @@ def _policy_data(ppo, env_cfg: kcfg.EnvConfig | None) -> dict[str, Any]:
         "n_steps": int(cfg.n_steps), "batch_size": int(cfg.batch_size), "n_epochs": int(cfg.n_epochs),
         "gamma": float(cfg.gamma), "gae_lambda": float(cfg.gae_lambda), "ent_coef": float(cfg.ent_coef), "vf_coef": float(cfg.vf_coef),
         "max_grad_norm": float(cfg.max_grad_norm), "normalize_advantage": bool(cfg.normalize_advantage),
-        "use_sde": False, "sde_sample_freq": -1, "target_kl": None, "clip_range_vf": None,
-        # SB3: self._n_updates += self.n_epochs once per train() call (ppo.py train()); the Adam step count lives in policy.optimizer.pth
-        "_n_updates": int(getattr(ppo, "n_train_calls", 0)) * int(cfg.n_epochs),
+        "use_sde": False, "sde_sample_freq": -1, "target_kl": None if getattr(cfg, "target_kl", None) is None else float(cfg.target_kl), "clip_range_vf": None,
+        # SB3: self._n_updates += 1 per epoch begun (ppo.py train()): n_epochs per train() call unless target_kl ended it early; the Adam
+        # step count lives in policy.optimizer.pth
+        "_n_updates": int(ppo.n_updates()) if hasattr(ppo, "n_updates") else int(getattr(ppo, "n_train_calls", 0)) * int(cfg.n_epochs),
         # the rest of BaseAlgorithm / OnPolicyAlgorithm.__dict__ as SB3 2.8 saves it (values a freshly constructed model holds)
         "device": "auto", "verbose": 0, "_num_timesteps_at_start": 0, "action_noise": None, "start_time": 0, "tensorboard_log": None,
         "_last_obs": None, "_last_episode_starts": None, "_last_original_obs": None, "_episode_num": 0, "_current_progress_remaining": 1.0,
@@ -85,7 +86,7 @@ def _policy_data(ppo, env_cfg: kcfg.EnvConfig | None) -> dict[str, Any]:
                        "needs": "the pickled members are assembled without gymnasium / SB3 (rl_brain_trainer_amd/sb3_pickle.py) and have never been read by "
                                 "the real PPO.load: until one has, treat tools/finish_sb3_zip.py on a host with stable-baselines3==" + SB3_VERSION_PIN +
                                 " as the route that is correct by construction",
-                       "adam_steps": int(ppo.adam_t), "mode": env_cfg.mode_name if env_cfg else None},
+                       "adam_steps": int(ppo.adam_step_count()) if hasattr(ppo, "adam_step_count") else int(ppo.adam_t), "mode": env_cfg.mode_name if env_cfg else None},
     }
 
 
@@ -130,11 +131,12 @@ def optimizer_state_dict(ppo) -> dict[str, Any]:
     """torch.optim.Adam.state_dict() of the flat Adam moments, one entry per SB3 parameter (policy.parameters() order)."""
     state, off = {}, 0
     extra = int(getattr(ppo, "actor_extra_steps", 0))   # teacher-anchor steps reach only the actor tensors (torch counts per tensor)
+    adam_t = int(ppo.adam_step_count()) if hasattr(ppo, "adam_step_count") else int(ppo.adam_t)   # (a target_kl run: the steps actually taken)
     for i, (name, shape) in enumerate(ppo.policy.spec):
         n = 1
         for d in shape:
             n *= d
-        step = torch.tensor(float(ppo.adam_t + (extra if name.startswith(("mlp_extractor.policy_net", "action_net")) else 0)))
+        step = torch.tensor(float(adam_t + (extra if name.startswith(("mlp_extractor.policy_net", "action_net")) else 0)))
         state[i] = {"step": step.clone(), "exp_avg": ppo.adam_m[off:off + n].view(shape).detach().cpu().clone(),
                     "exp_avg_sq": ppo.adam_v[off:off + n].view(shape).detach().cpu().clone()}
         off += n

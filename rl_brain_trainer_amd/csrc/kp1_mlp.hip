@@ -946,133 +946,32 @@ __device__ __forceinline__ int64_t finalize_wide_index(const ParamLayout& L, int
 __host__ __device__ inline int64_t finalize_vec_items(const ParamLayout& L) { return 2 * ((int64_t)L.H * L.H / 4 + (int64_t)L.H * L.IN / 4); }
 // (a form with 2 or 4 lanes splitting the chunks of one item was measured and removed: DESIGN.md 4.3)
 
+//
+// GATE (grad_finalize_gated_kernel): the KL early stop of SB3's PPO.train() as a device decision.  `gate` holds one
+// kp1_kl_gate per replica and a_.step_counter one STEP_DEV_INTS line per replica.  All four statistics of a minibatch are owned by lanes of
+// wave 0 of ONE wide block (the three loss sums and, in this form, the entropy term: finalize_gate_layout_ok), and the lane of the KL sum
+// decides there: nothing else in the launch that takes the decision reads it, every later launch does.  The gradient and the norm partials
+// are written whatever the gate says.
+__host__ __device__ inline bool finalize_gate_layout_ok(const ParamLayout& L) { return finalize_wide_count(L) % 32 + 3 < 32; }
+
 template <bool POP = false>
 __global__ void __launch_bounds__(256) grad_finalize_kernel(const FinalizeArgs a_, int n_main) {
-  const FinalizeArgs a = POP ? finalize_args_replica(a_, blockIdx.y) : a_;
-  const ParamLayout& L = a.L;
-  __shared__ double sq[4];
-  __shared__ float red[8][32];
-  float gval = 0.f;
-  double gsq = 0.0;
-  if ((int)blockIdx.x < n_main) {
-    const int64_t j = (int64_t)(blockIdx.x * 256u + threadIdx.x);
-    const int64_t per2 = (int64_t)L.H * L.H / 4, per1 = (int64_t)L.H * L.IN / 4;
-    if (j < 2 * (per2 + per1)) {
-      const float* src;
-      int64_t stride, dst;
-      int n;
-      if (j < 2 * per2) {
-        const int net = j >= per2;
-        const unsigned rem = (unsigned)(j - net * per2), q4 = (unsigned)(L.H / 4), row = rem / q4, c4 = rem - row * q4;   // 32-bit: see pack_one
-        src = a.slab2 + net * a.s2_net + (int64_t)row * a.s2_ld + 4 * c4;
-        stride = a.s2_chunk; n = a.s2_n;
-        dst = (net ? L.v_w2 : L.p_w2) + (int64_t)row * L.H + 4 * c4;
-      } else {
-        const int64_t k = j - 2 * per2;
-        const int net = k >= per1;
-        const unsigned rem = (unsigned)(k - net * per1), q4 = (unsigned)(L.IN / 4), row = rem / q4, c4 = rem - row * q4;
-        src = a.slab1 + net * a.s1_net + (int64_t)row * a.s1_ld + 4 * c4;
-        stride = a.s1_chunk; n = a.s1_n;
-        dst = (net ? L.v_w1 : L.p_w1) + (int64_t)row * L.IN + 4 * c4;
-      }
-      f32x4 s = {0.f, 0.f, 0.f, 0.f};
-      int c = 0;
-      // the kernel is bound by memory round trips, not bandwidth: 32 partials (one whole dW2 element at the default batch split) are in
-      // flight before the first add; the adds keep the chunk order 0, 1, 2, ... whatever the unroll
-      for (; c + 32 <= n; c += 32) {
-        f32x4 v[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) v[u] = *reinterpret_cast<const f32x4*>(src + (int64_t)(c + u) * stride);
-#pragma unroll
-        for (int u = 0; u < 32; ++u) s += v[u];
-      }
-      for (; c + 16 <= n; c += 16) {
-        f32x4 v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = *reinterpret_cast<const f32x4*>(src + (int64_t)(c + u) * stride);
-#pragma unroll
-        for (int u = 0; u < 16; ++u) s += v[u];
-      }
-      for (; c + 8 <= n; c += 8) {
-        f32x4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4*>(src + (int64_t)(c + u) * stride);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-      }
-      for (; c < n; ++c) s += *reinterpret_cast<const f32x4*>(src + (int64_t)c * stride);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        a.grad[dst + q] = s[q];
-        gsq += (double)s[q] * (double)s[q];
-      }
-    }
-    if (a.step_counter && blockIdx.x == 0 && threadIdx.x == 0) {  // read by the adam kernel that follows, with the bias corrections of the new count
-      const int step = a.step_counter[CNT_STEP] + 1;
-      a.step_counter[CNT_STEP] = step;
-      adam_record_write(a.step_counter, step, a.step_counter[CNT_EXTRA]);
-    }
-    if (a.stats && blockIdx.x == 0 && threadIdx.x == 3) {  // entropy of the state-independent diagonal Gaussian
-      float ent = 0.f;
-      for (int k = 0; k < ACT; ++k) ent += 0.5f + LOG_SQRT_2PI + a.log_std[k];
-      a.stats[2] += ent;
-    }
-  } else {
-    const int64_t n_wide = finalize_wide_count(L);
-    const int el = threadIdx.x & 31, strand = threadIdx.x >> 5;
-    const int64_t e = (int64_t)(blockIdx.x - n_main) * 32 + el;
-    // elements n_wide .. n_wide+2 are the three loss sums (policy, value, kl), not gradients
-    const bool is_grad = e < n_wide, is_stat = !is_grad && e < n_wide + 3;
-    PartialSrc s{};
-    int64_t flat = 0;
-    if (is_grad) {
-      flat = finalize_wide_index(L, e);
-      s = finalize_source(a, flat);
-    } else if (is_stat) {
-      s.p = a.hpart + 10 * L.Hp + 15 + (e - n_wide);
-      s.stride = a.h_stride; s.n = a.h_n; s.add = 0.f;
-    }
-    float part = 0.f;
-    if (is_grad || is_stat) {
-      int c = strand;
-      for (; c + 8 * 31 < s.n; c += 8 * 32) {
-        float v[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) v[u] = s.p[(int64_t)(c + 8 * u) * s.stride];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) part += v[u];
-      }
-      // the rest, eight in flight (written `part += load` per tile it compiles to load, wait, add: one memory round trip per tile); a load
-      // past the end reads the strand's last tile and adds +0.0, which leaves the sum as it is
-      for (; c < s.n; c += 8 * 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = s.p[(int64_t)min(c + 8 * u, s.n - 1) * s.stride];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) part += c + 8 * u < s.n ? v[u] : 0.f;
-      }
-    }
-    red[strand][el] = part;
-    __syncthreads();
-    if (threadIdx.x < 32) {
-      float t = red[0][el];
-#pragma unroll
-      for (int k = 1; k < 8; ++k) t += red[k][el];
-      if (is_grad) {
-        gval = t + s.add;
-        a.grad[flat] = gval;
-      } else if (is_stat && a.stats) {
-        const int k = (int)(e - n_wide);
-        a.stats[k == 2 ? 3 : k] += t * a.inv_count;  // single writer
-      }
-    }
+  constexpr bool GATE = false;
+  constexpr kp1_kl_gate* gate = nullptr;
+#include "kp1_grad_finalize_body.inc"
+}
+template <bool POP = false>
+__global__ void __launch_bounds__(256) grad_finalize_gated_kernel(const FinalizeArgs a_, int n_main, kp1_kl_gate* gate) {
+  constexpr bool GATE = true;
+#include "kp1_grad_finalize_body.inc"
+}
+
+// kp1_mlp_kl_gate_arm: a new train() call begins; the thresholds stay
+__global__ void kl_gate_arm_kernel(kp1_kl_gate* __restrict__ gate, int n) {
+  const int r = (int)threadIdx.x;
+  if (r < n) {
+    gate[r].stopped = 0; gate[r].n_counted = 0; gate[r].n_seen = 0; gate[r].stop_index = 0; gate[r].stop_kl = 0.f;
   }
-  // block sum of squares: shuffles inside a wave, the four wave sums through LDS (fixed order) -- one barrier instead of nine
-  double w = gsq + (double)gval * (double)gval;
-  for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off);
-  if ((threadIdx.x & 63) == 0) sq[threadIdx.x >> 6] = w;
-  __syncthreads();
-  if (threadIdx.x == 0) a.sumsq[blockIdx.x] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
 }
 
 template <bool POP = false>
@@ -1119,80 +1018,26 @@ __device__ __forceinline__ double norm_partials_sum(const double* __restrict__ p
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
   return s;
 }
+// GATE (adam_gated_kernel): `cnt` holds one line per replica, and a replica whose gate has stopped leaves before any store -- parameters,
+// moments and packed weights stay as the last step taken left them.
 template <bool POP = false>
 __global__ void __launch_bounds__(ADAM_BLOCK) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                    int64_t n, const double* __restrict__ partials, int n_partials, int host_step,
                                                    const int* __restrict__ cnt, float lr, float eps, float max_norm, float bc1, float bc2_sqrt,
                                                    int zero_grad, unsigned r_partials, const float* __restrict__ hparams, const ParamLayout L,
                                                    const Packed k_) {
-  // (argument order: what the loads and the norm need stands in front of the two structs, which are read behind the reduction)
-  __shared__ float scale_s;
-  // the counts and the record (kp1_mlp::step_dev, uniform loads, none of them behind a branch): host_step > 0 is the caller's step count, with
-  // bc1 / bc2_sqrt its corrections; otherwise the count is the device's and the corrections are the record's
-  const int dev_step = cnt[CNT_STEP], extra = cnt[CNT_EXTRA];
-  const int step = host_step > 0 ? host_step : dev_step;
-  const int rec_step = cnt[REC_STEP], rec_extra = cnt[REC_EXTRA];
-  const float rec_bc1 = __int_as_float(cnt[REC_BC]), rec_bc2_sqrt = __int_as_float(cnt[REC_BC + 1]);
-  const float rec_bc1_a = __int_as_float(cnt[REC_BC + 2]), rec_bc2_sqrt_a = __int_as_float(cnt[REC_BC + 3]);
-  const Packed k = POP ? packed_replica(k_, L, blockIdx.y) : k_;
-  if constexpr (POP) {
-    const unsigned o = blockIdx.y * (unsigned)n;
-    p += o; g += o; m += o; v += o;
-    partials += blockIdx.y * r_partials;
-    if (hparams) {   // replica blockIdx.y's entry of the hyper-parameter table (uniform load at kernel entry); same arithmetic below
-      const float* e = hparams + blockIdx.y * (unsigned)HP_FIELDS;
-      lr = e[HP_LR];
-      eps = e[HP_EPS];
-      max_norm = e[HP_MAX_NORM];
-    }
-  }
-  // this thread's elements: their loads do not depend on the norm, so they go out first and share one memory round trip with the
-  // step count and the norm partials below (the kernel is a chain of round trips: it moves 2.6 MB)
-  const int64_t i0 = ((int64_t)blockIdx.x * ADAM_BLOCK + threadIdx.x) * VEC;
-  float g_in[VEC], m_in[VEC], v_in[VEC], p_in[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    const int64_t il = i0 + j < n ? i0 + j : n - 1;
-    g_in[j] = g[il]; m_in[j] = m[il]; v_in[j] = v[il]; p_in[j] = p[il];
-  }
-  double s = 0.0;
-  if (threadIdx.x < 64) s = norm_partials_sum(partials, n_partials);
-  if (threadIdx.x == 0) {
-    const float norm = (float)sqrt(s);
-    scale_s = max_norm > 0.f ? fminf(max_norm / (norm + 1e-6f), 1.f) : 1.f;
-  }
-  // torch.optim.Adam keeps one step count per tensor: the actor tensors (policy_net.*, action_net.*) have taken `extra`
-  // more steps than the rest when a teacher-anchor side loss updates them between rollouts (route/teacher_anchor.py:68-87)
-  float bc1_a, bc2_sqrt_a;
-  if (host_step <= 0 && rec_step == step && rec_extra == extra) {   // the launch that advanced the count left the corrections (uniform branch)
-    bc1 = rec_bc1; bc2_sqrt = rec_bc2_sqrt; bc1_a = rec_bc1_a; bc2_sqrt_a = rec_bc2_sqrt_a;
-  } else {   // a count the host set since, or the caller's
-    if (host_step <= 0) adam_bias((float)step, bc1, bc2_sqrt);
-    adam_bias_actor((float)step, extra, bc1, bc2_sqrt, bc1_a, bc2_sqrt_a);
-  }
-  __syncthreads();
-  const float scale = scale_s;
-  float pn[VEC], mn[VEC], vn[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    const int64_t i = i0 + j;
-    const bool actor = extra != 0 && ((i >= L.p_w1 && i < L.v_w1) || (i >= L.a_w && i < L.c_w));
-    const float b1 = actor ? bc1_a : bc1, b2 = actor ? bc2_sqrt_a : bc2_sqrt;
-    const float gi = g_in[j] * scale;
-    mn[j] = 0.9f * m_in[j] + 0.1f * gi;
-    vn[j] = 0.999f * v_in[j] + 0.001f * gi * gi;
-    const float denom = sqrtf(vn[j]) / b2 + eps;
-    pn[j] = p_in[j] - (lr / b1) * (mn[j] / denom);
-  }
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    const int64_t i = i0 + j;
-    if (i < n) {
-      m[i] = mn[j]; v[i] = vn[j]; p[i] = pn[j];
-      pack_one(i, pn[j], L, k);
-      if (zero_grad) g[i] = 0.f;
-    }
-  }
+  constexpr bool GATE = false;
+  constexpr const kp1_kl_gate* gate = nullptr;
+#include "kp1_adam_body.inc"
+}
+template <bool POP = false>
+__global__ void __launch_bounds__(ADAM_BLOCK) adam_gated_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                   int64_t n, const double* __restrict__ partials, int n_partials, int host_step,
+                                                   const int* __restrict__ cnt, float lr, float eps, float max_norm, float bc1, float bc2_sqrt,
+                                                   int zero_grad, unsigned r_partials, const float* __restrict__ hparams, const ParamLayout L,
+                                                   const Packed k_, const kp1_kl_gate* __restrict__ gate) {
+  constexpr bool GATE = true;
+#include "kp1_adam_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------- teacher-anchor side loss
@@ -1460,7 +1305,11 @@ struct kp1_mlp {
   float* bslab = nullptr;      // [max_batch/64 row tiles][2 nets][Hp] partial db1
   float* hpart = nullptr;      // [max_batch/32 blocks][10 Hp + 32] head partials
   int n_finalize_blocks = 0;   // sum-of-squares partials written by the last grad_finalize_kernel
-  int* step_dev = nullptr;     // device Adam step counts and the record of their bias corrections (CNT_*, REC_*, AREC_*)
+  int* step_dev = nullptr;     // device Adam step counts and the record of their bias corrections (CNT_*, REC_*, AREC_*): K lines, line 0 the shared one
+  // KL early stop (kp1_mlp_set_kl_gate): one record per replica; while gate_on, finalize and Adam run their gated forms on line r of step_dev
+  kp1_kl_gate* gate_dev = nullptr;
+  bool gate_on = false;
+  int actor_extra_host = 0;    // host mirror of [CNT_EXTRA] (set_option + one per anchor Adam step): a gate refuses a non-zero one
   // population: per-replica hyper-parameter table [K][HP_FIELDS] (kp1_mlp_set_replica_hparams); the kernels read it while hparams_on
   float* hparams_dev = nullptr;
   bool hparams_on = false;
@@ -1921,7 +1770,8 @@ int mlp_create(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batc
   if (Hp == 128) MLP_ALLOC(m->anchor_partials, K * ANCHOR_PARTIALS);
   MLP_ALLOC(m->slab, K * 64 * 2 * Hp * Hp);
   MLP_ALLOC(m->slab1, K * 64 * 2 * Hp * INP);
-  MLP_ALLOC(m->step_dev, STEP_DEV_INTS);
+  MLP_ALLOC(m->step_dev, K * STEP_DEV_INTS);
+  MLP_ALLOC(m->gate_dev, K);
   if (K > 1) MLP_ALLOC(m->hparams_dev, K * HP_FIELDS);
   MLP_ALLOC(m->bslab, K * (mb / 32) * 2 * Hp);
   MLP_ALLOC(m->hpart, K * (mb / 32) * (10 * Hp + 32));
@@ -1997,13 +1847,16 @@ int kp1_mlp_set_option(kp1_mlp* m, int32_t option, int32_t value) {
   if (option == KP1_MLP_OPT_STEP_COUNT) {   // optimiser steps taken so far (resuming from a checkpoint's Adam state)
     if (value < 0) return fail(KP1_ERR_INVALID, "step count must be >= 0");
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpy(m->step_dev, &value, sizeof(int), hipMemcpyHostToDevice));
+    // a gated handle counts per replica: every line (line 0 is the one every ungated kernel reads)
+    for (int r = 0; r < (m->gate_on ? m->K : 1); ++r) HIP_TRY(hipMemcpy(m->step_dev + r * STEP_DEV_INTS, &value, sizeof(int), hipMemcpyHostToDevice));
     return KP1_OK;
   }
   if (option == KP1_MLP_OPT_ACTOR_EXTRA_STEPS) {
     if (value < 0) return fail(KP1_ERR_INVALID, "actor extra steps must be >= 0");
+    if (value && m->gate_on) return fail(KP1_ERR_UNSUPPORTED, "actor extra steps are not covered while a KL gate is set on the handle");
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipMemcpy(m->step_dev + 1, &value, sizeof(int), hipMemcpyHostToDevice));
+    m->actor_extra_host = value;
     return KP1_OK;
   }
   return fail(KP1_ERR_INVALID, "unknown kp1_mlp option");
@@ -2597,8 +2450,13 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
   if (m->n_finalize_blocks > 2048) return fail(KP1_ERR_INVALID, "parameter vector too large for the sum-of-squares partial buffer");
   {
     ProfScope ps(m, KP1_MLP_PROFILE_FINALIZE, stream);
-    auto* kernel = pop ? grad_finalize_kernel<true> : grad_finalize_kernel<false>;
-    KP1_LAUNCH(kernel, dim3(m->n_finalize_blocks, m->K), dim3(256), 0, stream, f, n_main);
+    if (m->gate_on) {
+      auto* kernel = pop ? grad_finalize_gated_kernel<true> : grad_finalize_gated_kernel<false>;
+      KP1_LAUNCH(kernel, dim3(m->n_finalize_blocks, m->K), dim3(256), 0, stream, f, n_main, m->gate_dev);
+    } else {
+      auto* kernel = pop ? grad_finalize_kernel<true> : grad_finalize_kernel<false>;
+      KP1_LAUNCH(kernel, dim3(m->n_finalize_blocks, m->K), dim3(256), 0, stream, f, n_main);
+    }
   }
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
@@ -2823,17 +2681,92 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   kfmt.formats = frag_only ? PACK_FRAG : (PACK_SLAB | PACK_FRAG);
   m->last_params = params;
   if (frag_only) m->slab_stale = true;
-  auto* kernel = pop ? adam_kernel<true> : adam_kernel<false>;
-  KP1_LAUNCH(kernel, dim3((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK), m->K), dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials,
-             n_norm_partials, step > 0 ? step : 0, (const int*)m->step_dev, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), zero_grad, r_partials, hparams,
-             m->L, kfmt);
+  const dim3 grid((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK), m->K);
+  if (m->gate_on) {
+    auto* kernel = pop ? adam_gated_kernel<true> : adam_gated_kernel<false>;
+    KP1_LAUNCH(kernel, grid, dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials, n_norm_partials, step > 0 ? step : 0,
+               (const int*)m->step_dev, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), zero_grad, r_partials, hparams, m->L, kfmt,
+               (const kp1_kl_gate*)m->gate_dev);
+  } else {
+    auto* kernel = pop ? adam_kernel<true> : adam_kernel<false>;
+    KP1_LAUNCH(kernel, grid, dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials, n_norm_partials, step > 0 ? step : 0,
+               (const int*)m->step_dev, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), zero_grad, r_partials, hparams, m->L, kfmt);
+  }
   HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_mlp_set_kl_gate(kp1_mlp* m, const double* target_kl_host, int32_t n, void* stream_) {
+  static_assert(sizeof(kp1_kl_gate) == 32 && offsetof(kp1_kl_gate, stopped) == 8 && offsetof(kp1_kl_gate, stop_kl) == 24, "kp1_kl_gate layout");
+  if (!m) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_set_kl_gate");
+  if (n != 0 && !target_kl_host) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_set_kl_gate");
+  if (n != 0 && n != m->K) return fail(KP1_ERR_INVALID, "kp1_mlp_set_kl_gate needs one target per replica (n = K), or n = 0 to clear the gate");
+  if (n != 0 && m->actor_extra_host != 0)
+    return fail(KP1_ERR_UNSUPPORTED, "a KL gate is not covered on a handle whose actor tensors have taken extra steps (KP1_MLP_OPT_ACTOR_EXTRA_STEPS)");
+  if (n != 0 && !finalize_gate_layout_ok(m->L)) return fail(KP1_ERR_UNSUPPORTED, "the loss statistics of this layout do not share one finalize block");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIP_TRY(hipStreamIsCapturing(stream, &cap));
+  if (cap != hipStreamCaptureStatusNone) return fail(KP1_ERR_INVALID, "kp1_mlp_set_kl_gate cannot run while the stream is being captured");
+  const int K = m->K;
+  if (n == 0) {
+    if (!m->gate_on) return KP1_OK;
+    std::vector<int> lines((size_t)K * STEP_DEV_INTS);
+    HIP_TRY(hipMemcpyAsync(lines.data(), m->step_dev, sizeof(int) * lines.size(), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int r = 1; r < K; ++r)
+      if (lines[(size_t)r * STEP_DEV_INTS + CNT_STEP] != lines[CNT_STEP])
+        return fail(KP1_ERR_INVALID, "the replicas' Adam step counts differ: the gate cannot be cleared back to one shared count");
+    m->gate_on = false;
+    return KP1_OK;
+  }
+  std::vector<kp1_kl_gate> rec((size_t)K);
+  for (int r = 0; r < K; ++r) {
+    const double t = target_kl_host[r];
+    rec[r] = kp1_kl_gate{};
+    rec[r].threshold = (t > 0.0 && std::isfinite(t)) ? 1.5 * t : std::numeric_limits<double>::infinity();   // NaN fails t > 0
+  }
+  HIP_TRY(hipMemcpyAsync(m->gate_dev, rec.data(), sizeof(kp1_kl_gate) * (size_t)K, hipMemcpyHostToDevice, stream));
+  if (!m->gate_on)   // from one shared count to one per replica
+    for (int r = 1; r < K; ++r)
+      HIP_TRY(hipMemcpyAsync(m->step_dev + r * STEP_DEV_INTS, m->step_dev, sizeof(int) * STEP_DEV_INTS, hipMemcpyDeviceToDevice, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  m->gate_on = true;
+  return KP1_OK;
+}
+
+int kp1_mlp_kl_gate_arm(kp1_mlp* m, void* stream_) {
+  if (!m) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_kl_gate_arm");
+  if (!m->gate_on) return fail(KP1_ERR_INVALID, "kp1_mlp_kl_gate_arm: no KL gate is set on the handle");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  hipLaunchKernelGGL(kl_gate_arm_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, m->gate_dev, m->K);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+int kp1_mlp_kl_gate_read(kp1_mlp* m, kp1_kl_gate* out_host, int32_t* out_steps, void* stream_) {
+  if (!m) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_kl_gate_read");
+  if (!m->gate_on) return fail(KP1_ERR_INVALID, "kp1_mlp_kl_gate_read: no KL gate is set on the handle");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  const int K = m->K;
+  std::vector<int> lines((size_t)K * STEP_DEV_INTS);
+  if (out_host) HIP_TRY(hipMemcpyAsync(out_host, m->gate_dev, sizeof(kp1_kl_gate) * (size_t)K, hipMemcpyDeviceToHost, stream));
+  if (out_steps) HIP_TRY(hipMemcpyAsync(lines.data(), m->step_dev, sizeof(int) * lines.size(), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (out_steps)
+    for (int r = 0; r < K; ++r) out_steps[r] = lines[(size_t)r * STEP_DEV_INTS + CNT_STEP];
   return KP1_OK;
 }
 
 int kp1_mlp_anchor_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const int64_t* idx, int32_t n, const float* teacher_actions,
                              float loss_weight, float* grad_out, float* loss_out, void* stream_) {
   if (!m || !obs || !teacher_actions || !grad_out || !loss_out) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_anchor_loss_grad");
+  if (m->gate_on) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step is not covered while a KL gate is set on the handle (it reads the shared step count)");
   int rc = check_batch_args(m, n, obs_stride);
   if (rc != KP1_OK) return rc;
   if (m->Hp != 128) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step runs on the layer-wise kernels: hidden must be 64 or 128");
@@ -2884,6 +2817,7 @@ int kp1_mlp_anchor_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, c
 int kp1_mlp_anchor_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, float* exp_avg_sq, float lr, float eps, float max_grad_norm,
                              int32_t step, void* stream_) {
   if (!m || !params || !grad || !exp_avg || !exp_avg_sq) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_anchor_adam_step");
+  if (m->gate_on) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step is not covered while a KL gate is set on the handle (it reads the shared step count)");
   if (m->Hp != 128) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step runs on the layer-wise kernels: hidden must be 64 or 128");
   const int n_blocks = (int)((m->L.total + 255) / 256);
   if (n_blocks > ANCHOR_PARTIALS) return fail(KP1_ERR_INVALID, "parameter vector too large for the anchor sum-of-squares partials");
@@ -2898,6 +2832,7 @@ int kp1_mlp_anchor_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_
                      exp_avg, exp_avg_sq, (const double*)m->anchor_partials, n_blocks, lr, eps, max_grad_norm, m->L, kfmt, (const int*)m->step_dev, (int)step,
                      pop ? (unsigned)ANCHOR_PARTIALS : 0u, pop && m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr);
   hipLaunchKernelGGL(anchor_count_kernel, dim3(1), dim3(1), 0, stream, m->step_dev);
+  m->actor_extra_host += 1;
   HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }

@@ -55,6 +55,7 @@ class MlpKernels:
         self.obs_pad = 64 if self.obs_dim <= 64 else 128   # row pitch the kernels also accept (zero padded)
         self.fused = True                                # what set_fused last set (hidden 256: the tile kernels; the handle's default is on)
         self.train_tile = False                          # what set_train_tile last set (hidden 64 / 128: train_tile128_kernel; default off)
+        self.kl_gate = False                             # whether set_kl_gate has a gate set (default: none)
         if replicas == 1:
             native.check(L.kp1_mlp_create_ex(device.index or 0, hidden, self.obs_dim, self.max_batch, C.byref(self._h)))
         else:
@@ -126,6 +127,33 @@ class MlpKernels:
             return
         table = (C.c_float * (len(rows) * len(self.HPARAM_FIELDS)))(*[float(r[f]) for r in rows for f in self.HPARAM_FIELDS])
         native.check(self.L.kp1_mlp_set_replica_hparams(self._h, C.cast(table, C.c_void_p), len(rows), self._stream()))
+
+    def set_kl_gate(self, targets: list[float | None] | None) -> None:
+        """SB3 PPO's ``target_kl`` as a device decision (kp1_mlp_set_kl_gate): one target per replica, None = that replica never stops.
+        While a gate is set, a replica whose minibatch approx_kl exceeds 1.5 * target takes neither that minibatch's Adam step nor any
+        later one until ``kl_gate_arm``, and adds nothing more to ``stats_out``; the Adam step count is kept per replica.  ``None`` (the
+        argument) clears the gate, which is refused while the replicas' step counts differ."""
+        if targets is None:
+            native.check(self.L.kp1_mlp_set_kl_gate(self._h, None, 0, self._stream()))
+            self.kl_gate = False
+            return
+        arr = (C.c_double * len(targets))(*[float("nan") if t is None else float(t) for t in targets])
+        native.check(self.L.kp1_mlp_set_kl_gate(self._h, C.cast(arr, C.c_void_p), len(targets), self._stream()))
+        self.kl_gate = True
+
+    def kl_gate_arm(self) -> None:
+        """a new train() call: every replica's record is cleared in one launch (kp1_mlp_kl_gate_arm; the thresholds stay)"""
+        native.check(self.L.kp1_mlp_kl_gate_arm(self._h, self._stream()))
+
+    def kl_gate_read(self, stream: torch.cuda.Stream | None = None) -> tuple[list[dict[str, float | int]], list[int]]:
+        """(one record per replica -- threshold, stopped, n_counted, n_seen, stop_index, stop_kl --, the replicas' Adam step counts); waits
+        for ``stream`` (default: the current one)"""
+        rec = (native.KlGate * self.replicas)()
+        steps = (C.c_int32 * self.replicas)()
+        st = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        native.check(self.L.kp1_mlp_kl_gate_read(self._h, C.cast(rec, C.c_void_p), C.cast(steps, C.c_void_p), st))
+        fields = [f for f, _ in native.KlGate._fields_ if f != "reserved0"]
+        return [{f: getattr(r, f) for f in fields} for r in rec], [int(v) for v in steps]
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

@@ -197,6 +197,9 @@ class TrainLogger:
 
     def log(self, stats: dict[str, Any], *, iteration: int, total_timesteps: int) -> dict[str, Any]:
         row = self.row(stats, iteration=iteration, total_timesteps=total_timesteps)
+        stop = stats.get("kl_stop")
+        if stop:      # SB3's PPO.train() (verbose >= 1), for an update that target_kl ended early
+            print(f"Early stopping at step {stop['stop_epoch']} due to reaching max kl: {stop['stop_kl']:.2f}", file=self.out or sys.stdout, flush=True)
         print(format_table(row), file=self.out or sys.stdout, flush=True)
         if self.csv_path is not None:
             self.csv_path.parent.mkdir(parents=True, exist_ok=True)

@@ -46,6 +46,12 @@ class MonitorState(C.Structure):
                 ("ring_success", C.c_uint8 * MONITOR_MAX_WINDOW)]
 
 
+class KlGate(C.Structure):
+    """include/kp1_ppo.h kp1_kl_gate: one replica's KL early-stop record (SB3 PPO's target_kl as a device decision)"""
+    _fields_ = [("threshold", C.c_double), ("stopped", C.c_int32), ("n_counted", C.c_int32), ("n_seen", C.c_int32), ("stop_index", C.c_int32),
+                ("stop_kl", C.c_float), ("reserved0", C.c_int32)]
+
+
 class Kp1Error(RuntimeError):
     pass
 
@@ -144,6 +150,9 @@ def load() -> C.CDLL:
     L.kp1_rollout_run.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]
     L.kp1_mlp_anchor_loss_grad.argtypes = [vp, vp, i32, vp, i32, vp, f32, vp, vp, vp]
     L.kp1_mlp_anchor_adam_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, i32, vp]
+    L.kp1_mlp_set_kl_gate.argtypes = [vp, vp, i32, vp]
+    L.kp1_mlp_kl_gate_arm.argtypes = [vp, vp]
+    L.kp1_mlp_kl_gate_read.argtypes = [vp, vp, vp, vp]
     L.kp1_monitor_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.kp1_monitor_destroy.argtypes = [vp]
     L.kp1_monitor_observe.argtypes = [vp, vp, vp, i32, vp]

@@ -32,7 +32,7 @@ import torch
 from . import native
 from .curriculum import PointCurriculumPopulation
 from .finisher_tools import DockReverseCurriculumPopulation
-from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig
+from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig, check_target_kl
 from .route_curriculum import RoutePrefixCurriculumPopulation
 from .route_env import RoutePopulationVecEnv
 from .vec_env import ArmKinematicPopulationVecEnv
@@ -40,8 +40,11 @@ from .vec_env import ArmKinematicPopulationVecEnv
 MAX_REPLICAS = 16     # KP1_MLP_MAX_REPLICAS
 
 # Per-replica PPO hyper-parameters a population can sweep (``overrides``): the six the MLP kernels read from the handle's table
-# (kp1_mlp_set_replica_hparams) and the two of the per-replica GAE scan / bootstrap.  The geometry the replicas share is refused.
-SWEEPABLE = ("learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "adam_eps", "gamma", "gae_lambda")
+# (kp1_mlp_set_replica_hparams), the two of the per-replica GAE scan / bootstrap, and target_kl, which reaches the handle as the [K] target
+# array of its KL gate (kp1_mlp_set_kl_gate) and is the one key that also takes None ("none": no early stop for that replica).  The
+# geometry the replicas share is refused.
+SWEEPABLE = ("learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "adam_eps", "gamma", "gae_lambda", "target_kl")
+NONE_WORDS = ("none", "null", "off")     # target_kl=none
 SHAPE_KEYS = ("n_steps", "batch_size", "n_epochs", "hidden", "normalize_advantage")
 
 
@@ -67,6 +70,9 @@ def check_overrides(seeds: list[int], overrides: list[dict[str, float]] | None) 
                                      f"({', '.join(SHAPE_KEYS)})")
                 if key not in SWEEPABLE:
                     raise ValueError(f"unknown override {key!r} (sweepable: {', '.join(SWEEPABLE)})")
+                if key == "target_kl" and (v is None or (isinstance(v, str) and v.strip().lower() in NONE_WORDS)):
+                    row[key] = None
+                    continue
                 if isinstance(v, bool):
                     raise ValueError(f"override {key}={v!r} of replica {k} is not a number")
                 try:
@@ -75,9 +81,11 @@ def check_overrides(seeds: list[int], overrides: list[dict[str, float]] | None) 
                     raise ValueError(f"override {key}={v!r} of replica {k} is not a number") from exc
                 if not math.isfinite(fv):
                     raise ValueError(f"override {key}={v!r} of replica {k} is not finite")
+                if key == "target_kl" and fv <= 0.0:
+                    raise ValueError(f"override target_kl={v!r} of replica {k} must be positive (or none)")
                 row[key] = fv
             out.append(row)
-    pairs = [(s, tuple(sorted(o.items()))) for s, o in zip(seeds, out)]
+    pairs = [(s, tuple(sorted(o.items(), key=lambda kv: kv[0]))) for s, o in zip(seeds, out)]
     if len(set(pairs)) != len(pairs):
         raise ValueError(f"(seed, overrides) pairs must be distinct (seeds {list(seeds)}, overrides {out}): equal pairs train identical replicas")
     return out
@@ -106,12 +114,16 @@ class ReplicaView:
         self.backend = "hip"
         self.device = pop.device
 
-    adam_t = property(lambda self: self._pop.adam_t)
+    adam_t = property(lambda self: self._pop.adam_step_count(self.k))     # the replica's own count where target_kl lets the replicas differ
     actor_extra_steps = property(lambda self: int(self._pop.actor_extra_steps))   # shared: every replica takes the same teacher-anchor steps
     num_timesteps = property(lambda self: self._pop.num_timesteps)
     n_train_calls = property(lambda self: self._pop.n_train_calls)
     last_stats = property(lambda self: self._pop.replica_stats(self.k))
     update_form = property(lambda self: self._pop.update_form)
+
+    def n_updates(self, k: int = 0) -> int:
+        """SB3's ``_n_updates`` of this replica"""
+        return self._pop.n_updates(self.k)
 
     @torch.no_grad()
     def predict(self, obs: torch.Tensor, deterministic: bool = True) -> torch.Tensor:
@@ -188,6 +200,7 @@ class PopulationPPO(PPO):
         dist = dist or Dist()
         if dist.enabled:
             raise ValueError("PopulationPPO is single-process: data parallel (a torch.distributed process group) is not supported")
+        check_target_kl([o.get("target_kl", cfg.target_kl) for o in overrides], dist, teacher_anchor)
         return seeds, dist, overrides
 
     def _init_population(self, seeds: list[int], cfg: PPOConfig, envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool,
@@ -207,6 +220,7 @@ class PopulationPPO(PPO):
         dev = self.device
         self._gamma_lambda = torch.zeros((K, 2), dtype=torch.float32, device=dev) if self.has_overrides else None
         self._apply_overrides()
+        self._setup_kl_gate(check_target_kl([c.target_kl for c in self.cfgs], dist))
         self.noise_rep = torch.zeros((K, T, N, ACT_DIM), dtype=torch.float32, device=dev)   # replica k's draw, as PPO.noise_all
         # minibatch i of replica k = local positions [start_i, end_i) of its shuffle; the kernels read minibatch i as ONE [K][n_i] index
         # block at K * start_i of the gathered index vector
@@ -513,6 +527,7 @@ class OneHandlePopulationPPO(PopulationPPO):
                 self.n_train_calls = int(data["_n_updates"]) // saved_epochs
         restored["hyperparameters"] = restore_saved_hyperparameters(self.cfg, data)
         self._apply_overrides()     # swept values beat both the config and the checkpoint
+        self._kl_after_load()
         return restored
 
 
@@ -600,7 +615,7 @@ def parse_sweep(specs: list[str] | None) -> list[tuple[str, list[float]]]:
     given twice and values that are not finite numbers"""
     import math
 
-    out: list[tuple[str, list[float]]] = []
+    out: list[tuple[str, list[Any]]] = []
     for spec in specs or []:
         key, sep, values = str(spec).partition("=")
         key = key.strip()
@@ -612,11 +627,12 @@ def parse_sweep(specs: list[str] | None) -> list[tuple[str, list[float]]]:
             raise ValueError(f"--sweep: unknown key {key!r} (sweepable: {', '.join(SWEEPABLE)})")
         if any(k == key for k, _ in out):
             raise ValueError(f"--sweep {key} is given twice: list all its values in one --sweep {key}=v1,v2")
+        none_ok = key == "target_kl"     # target_kl=0.01,0.03,none: a replica without the early stop
         try:
-            vals = [float(v) for v in values.split(",") if v.strip()]
+            vals = [None if none_ok and v.strip().lower() in NONE_WORDS else float(v) for v in values.split(",") if v.strip()]
         except ValueError as exc:
             raise ValueError(f"--sweep {key}: values must be numbers, got {values!r}") from exc
-        if not vals or not all(math.isfinite(v) for v in vals):
+        if not vals or not all(v is None or math.isfinite(v) for v in vals):
             raise ValueError(f"--sweep {key}: needs at least one finite value, got {values!r}")
         out.append((key, vals))
     return out
@@ -625,7 +641,7 @@ def parse_sweep(specs: list[str] | None) -> list[tuple[str, list[float]]]:
 def replica_name(seed: int, overrides: dict[str, float]) -> str:
     """the artifact directory of a replica: seed_<s> without overrides, else seed_<s>_<key>_<repr(value)> per override in order
     (seed_7_learning_rate_0.0001)"""
-    return "_".join([f"seed_{int(seed)}"] + [f"{k}_{float(v)!r}" for k, v in overrides.items()])
+    return "_".join([f"seed_{int(seed)}"] + [f"{k}_{'none' if v is None else repr(float(v))}" for k, v in overrides.items()])
 
 
 def plan_replicas(seeds_text: str | None, sweep_specs: list[str] | None) -> tuple[list[int], list[dict[str, float]] | None, list[str]]:

@@ -59,6 +59,9 @@ class PPOConfig:
     hidden: int = 64            # SB3 default net_arch = dict(pi=[64, 64], vf=[64, 64])
     normalize_advantage: bool = True
     total_timesteps: int = 100_000
+    # SB3's target_kl: train() leaves its epochs once a minibatch's approx_kl exceeds 1.5 * target_kl (None: never).  Decided on the device
+    # (DESIGN section 35); last, so positional use of the fields above is unchanged
+    target_kl: float | None = None
 
     @classmethod
     def from_algo_kwargs(cls, kwargs: dict[str, Any], **overrides: Any) -> "PPOConfig":
@@ -456,6 +459,20 @@ def restore_saved_hyperparameters(cfg: "PPOConfig", data: dict[str, Any]) -> dic
 FUSED_ROLLOUT_WIDTHS = (64, 128, 256)
 
 
+def check_target_kl(targets: list[float | None], dist: Any, teacher_anchor: Any = None) -> list[float | None]:
+    """The refusals of ``target_kl`` (one entry per replica) before any device work.  Returns the targets with "no target" as None: None,
+    NaN and values <= 0 (what the handle takes as none).  A KL stop is a per-process decision -- under data parallel the ranks would leave
+    an update at different minibatches and diverge, and SB3 has no counterpart -- and the teacher-anchor step reads the one shared Adam
+    count that a gated handle no longer keeps."""
+    out = [None if t is None or not float(t) > 0.0 else float(t) for t in targets]
+    if any(t is not None for t in out):
+        if dist is not None and getattr(dist, "enabled", False):
+            raise ValueError("target_kl is not supported under data parallel: each rank would stop on its own shard's KL and the ranks would diverge")
+        if teacher_anchor is not None:
+            raise ValueError("target_kl is not supported together with a teacher anchor: the anchor step reads the shared Adam step count")
+    return out
+
+
 def fused_rollout_covered(env_type_ok: bool, dtype: Any, hidden: int, obs_dim: int, components_on: bool, env_var: str | None, *,
                           default_on: bool = True) -> bool:
     """Whether a rollout step runs as ONE launch (policy forward + sampling + env step with auto-reset) instead of forward + step_into.
@@ -557,10 +574,12 @@ class PPO:
         from . import monitor as _monitor
 
         _monitor.check_monitor(monitor, dist)     # a data-parallel run is refused before any device work
+        targets = check_target_kl([cfg.target_kl], dist)
         self.env = env
         self.curriculum = curriculum
         self._setup(cfg, [cfg.seed], [env], [curriculum], dist, use_graphs, min_batch=8192, stacked=False, monitor=monitor)
         self.policy = self.policies[0]
+        self._setup_kl_gate(targets)
         T, N, dev = cfg.n_steps, self.n_envs, self.device
         # data parallel: done bytes are exchanged once per `done_chunk` env steps (one all-gather of chunk x N bytes instead of one
         # latency-bound collective per 45 us env step); the device tracker replays the chunk in the reference's order
@@ -743,6 +762,81 @@ class PPO:
         self.step_callback = None
         self._setup_monitor(monitor)
 
+    # ------------------------------------------------------------------ KL early stop (target_kl)
+    # None = off, the default, and then no launch, graph or printed line differs from a build without it
+    kl_targets: list[float | None] | None = None
+
+    def _setup_kl_gate(self, targets: list[float | None]) -> None:
+        """``target_kl`` of every replica (None: that replica never stops).  With any target set the MLP handle gets its gate here, for the
+        trainer's life: the update's finalize and Adam launches are then the gated instantiations, the Adam step count lives on the device
+        per replica, and what the host needs of a train() call -- the steps taken, the epochs begun, the minibatches that entered the
+        statistics -- is read back lazily from the replicas' records (``_resolve_kl``)."""
+        if not any(t is not None for t in targets):
+            return
+        self.kl_targets = list(targets)
+        self._mlp.set_kl_gate(self.kl_targets)
+        self.adam_steps = [int(self.adam_t)] * self.K            # resolved per-replica Adam step counts
+        self.kl_n_updates = [self.n_train_calls * self.cfg.n_epochs] * self.K     # SB3's _n_updates per replica: epochs begun
+        self._kl_records: list[dict[str, Any]] = [{} for _ in range(self.K)]     # kl_stops() of the last resolved train() call
+        self._kl_pending: Any = None      # the event behind the last train() call while its records are unread
+        self._kl_fresh = [False] * self.K     # replicas whose stop the monitor has not reported yet
+        self._kl_stream = torch.cuda.Stream(self.device)
+
+    def _resolve_kl(self) -> None:
+        """bring the host up to the last train() call: per replica the Adam step count, the epochs begun and the stop record.  Waits for that
+        update only (a side stream behind its event), not for launches queued since."""
+        if self.kl_targets is None or self._kl_pending is None:
+            return
+        self._kl_stream.wait_event(self._kl_pending)
+        records, steps = self._mlp.kl_gate_read(self._kl_stream)
+        self._kl_pending = None
+        n_mb = self._n_minibatches()
+        for k, (r, st) in enumerate(zip(records, steps)):
+            stopped = bool(r["stopped"])
+            self._kl_records[k] = {"early_stop": stopped, "stop_epoch": r["stop_index"] // n_mb if stopped else None,
+                                   "stop_minibatch": r["stop_index"] % n_mb if stopped else None, "stop_kl": float(r["stop_kl"]) if stopped else None,
+                                   "n_counted": int(r["n_counted"])}
+            self.kl_n_updates[k] += r["stop_index"] // n_mb + 1 if stopped else self.cfg.n_epochs
+            self.adam_steps[k] = st
+            self._kl_fresh[k] = stopped
+        self.adam_t = self.adam_steps[0]
+
+    def _n_minibatches(self) -> int:
+        """optimiser steps per epoch"""
+        total = self.cfg.n_steps * self.n_envs
+        local_bs = max(self.cfg.batch_size // self.dist.world_size, 1)
+        return (total + local_bs - 1) // local_bs
+
+    def kl_stops(self) -> list[dict[str, Any]]:
+        """per replica, how the last train() call ended under ``target_kl``: ``early_stop``, and where it stopped (``stop_epoch``,
+        ``stop_minibatch``, the minibatch's ``stop_kl``; None without a stop).  Reading it synchronises with that update."""
+        if self.kl_targets is None:
+            raise RuntimeError("kl_stops needs a trainer whose config sets target_kl")
+        self._resolve_kl()
+        return [{k: v for k, v in r.items() if k != "n_counted"} for r in self._kl_records]
+
+    def n_updates(self, k: int = 0) -> int:
+        """SB3's ``_n_updates`` of replica k: n_epochs per train() call, or the epochs begun where ``target_kl`` ended a call early"""
+        if self.kl_targets is None:
+            return self.n_train_calls * self.cfg.n_epochs
+        self._resolve_kl()
+        return self.kl_n_updates[k]
+
+    def adam_step_count(self, k: int = 0) -> int:
+        """optimiser steps replica k has taken (torch.optim.Adam's ``step``)"""
+        if self.kl_targets is None:
+            return int(self.adam_t)
+        self._resolve_kl()
+        return self.adam_steps[k]
+
+    def _kl_after_load(self) -> None:
+        """a restored optimiser state and step clock: every replica continues from them"""
+        if self.kl_targets is None:
+            return
+        self._resolve_kl()
+        self.adam_steps = [int(self.adam_t)] * self.K
+        self.kl_n_updates = [self.n_train_calls * self.cfg.n_epochs] * self.K
+
     # ------------------------------------------------------------------ training monitor
     def _setup_monitor(self, monitor: bool | int) -> None:
         """``monitor=``: the device handle over the K x N rollout columns, the explained-variance output and the log_std snapshot.  The three
@@ -796,9 +890,12 @@ class PPO:
             row.update({"train/approx_kl": s.get("approx_kl"), "train/clip_range": float(cfgs[k].clip_range),
                         "train/entropy_loss": -s["entropy"] if "entropy" in s else None,
                         "train/explained_variance": _monitor.explained_variance(ev[k][0], ev[k][1]),
-                        "train/learning_rate": float(cfgs[k].learning_rate), "train/n_updates": self.n_train_calls * self.cfg.n_epochs,
+                        "train/learning_rate": float(cfgs[k].learning_rate), "train/n_updates": self.n_updates(k),
                         "train/policy_gradient_loss": s.get("policy_loss"), "train/std": std[k] if self.n_train_calls else None,
                         "train/value_loss": s.get("value_loss")})
+            if self.kl_targets is not None and self._kl_fresh[k]:     # reported once: TrainLogger prints SB3's early-stopping line
+                row["kl_stop"] = {q: self._kl_records[k][q] for q in ("stop_epoch", "stop_minibatch", "stop_kl")}
+                self._kl_fresh[k] = False
             rows.append(row)
         return rows
 
@@ -844,8 +941,11 @@ class PPO:
 
     def _epoch_key(self) -> tuple:
         c = self.cfg
-        return (c.learning_rate, c.clip_range, c.ent_coef, c.vf_coef, c.max_grad_norm, c.adam_eps, c.batch_size, c.n_steps, c.normalize_advantage,
-                self.dist.world_size, self._mlp.train_tile)
+        key = (c.learning_rate, c.clip_range, c.ent_coef, c.vf_coef, c.max_grad_norm, c.adam_eps, c.batch_size, c.n_steps, c.normalize_advantage,
+               self.dist.world_size, self._mlp.train_tile)
+        if self.kl_targets is not None:     # a gated trainer captured the gated launches; the last element stays the train-tile flag
+            key = key[:-1] + (("kl_gate", tuple(self.kl_targets)),) + key[-1:]
+        return key
 
     def _curriculum_observe(self, t: int) -> None:
         """after env step t: feed the done bytes to the device tracker (single process: every step; data parallel: once per chunk -- a route
@@ -898,6 +998,7 @@ class PPO:
                 if self._epoch_graph is not None or self.adam_t != restored.get("adam_steps", self.adam_t):
                     raise RuntimeError("restore_hyperparameters must happen before the first update")
                 restored["hyperparameters"] = restore_saved_hyperparameters(self.cfg, data)
+        self._kl_after_load()
         return restored
 
     # ------------------------------------------------------------------ policy evaluation
@@ -1141,12 +1242,19 @@ class PPO:
         total = cfg.n_steps * self.n_envs
         local_bs = max(cfg.batch_size // self.dist.world_size, 1)
         n_mb = (total + local_bs - 1) // local_bs     # optimiser steps per epoch
+        gated = self.kl_targets is not None
+        if gated:
+            self._resolve_kl()      # the previous call's records, before arming clears them
         self.n_train_calls += 1
         self.stats_dev.zero_()
+        if gated:
+            self._mlp.kl_gate_arm()
         for _epoch in range(cfg.n_epochs):
             for k in range(self.K):
                 self._draw_perm(k)
-            if not self.use_graphs:
+            if gated and not self.use_graphs:
+                self._epoch_body()     # the device's per-replica counts are the truth: the host mirror follows them (_resolve_kl)
+            elif not self.use_graphs:
                 # the eager epoch steps Adam from the device-resident step count too, exactly as the captured epoch does (bias corrections
                 # computed by the same device arithmetic): eager and replayed training stay bit-identical.  The count is set from the host
                 # mirror first, so loss_grad calls made outside train() cannot have moved it.
@@ -1168,10 +1276,14 @@ class PPO:
                 else:
                     self._replay_checked("epoch", self._epoch_graph)
                 self._segmented_epoch_timed()
-            self.adam_t += n_mb
+            if not gated:
+                self.adam_t += n_mb
         # read back lazily (last_stats): a .tolist() here would make every iteration wait for its own update before the host can enqueue
         # the next rollout
         self._last_stats_dev = (self.stats_dev.clone(), n_mb * cfg.n_epochs)
+        if gated:
+            self._kl_pending = torch.cuda.Event()
+            self._kl_pending.record(torch.cuda.current_stream(self.device))
         if self.monitor is not None:
             # train/std: exp(log_std) after the update; 7 floats per replica, device to device
             self._log_std_snap.copy_(self.flat.view(self.K, -1)[:, :ACT_DIM])
@@ -1237,8 +1349,17 @@ class PPO:
         """last_stats of every replica"""
         if self._last_stats_dev is not None:
             stats, n_updates = self._last_stats_dev
-            rows = (stats / max(n_updates, 1)).tolist()
-            self._last_stats_host = [dict(zip(("policy_loss", "value_loss", "entropy", "approx_kl"), r), n_updates=n_updates) for r in rows]
+            names = ("policy_loss", "value_loss", "entropy", "approx_kl")
+            if self.kl_targets is None:
+                rows = (stats / max(n_updates, 1)).tolist()
+                self._last_stats_host = [dict(zip(names, r), n_updates=n_updates) for r in rows]
+            else:     # the means are over the minibatches that entered the statistics: up to and including the one that stopped
+                self._resolve_kl()
+                counts = [r["n_counted"] for r in self._kl_records]
+                div = torch.tensor([max(c, 1) for c in counts], dtype=torch.float32, device=stats.device).view(-1, 1)
+                rows = (stats / div).tolist()
+                self._last_stats_host = [dict(zip(names, r), n_updates=c, **{q: v for q, v in rec.items() if q != "n_counted"})
+                                         for r, c, rec in zip(rows, counts, self._kl_records)]
             self._last_stats_dev = None
         return self._last_stats_host
 
