@@ -9,7 +9,8 @@ __device__ const uint64_t ZIG_KI[256] = KP1_ZIGGURAT_KI;
 __device__ const double ZIG_WI[256] = KP1_ZIGGURAT_WI;
 __device__ const double ZIG_FI[256] = KP1_ZIGGURAT_FI;
 
-// numpy random_standard_normal (256-layer ziggurat): one 64-bit word per draw in 99.3 % of the cases
+// numpy random_standard_normal (256-layer ziggurat): one 64-bit word per draw in 98.5 % of the cases (numpy, 300,000 draws); the
+// wedge, the tail (2.3e-4 per draw) and a repeated tail loop (1.3e-5) are forced on purpose by tests/test_forced_rng_*.py
 __device__ __forceinline__ double pcg_standard_normal(Pcg& g) {
   for (;;) {
     uint64_t r = pcg_next64(g);
