@@ -223,6 +223,18 @@ typedef struct kp1_replica_hparams {
   float learning_rate, adam_eps, max_grad_norm, clip_range, ent_coef, vf_coef;
 } kp1_replica_hparams;
 int kp1_mlp_set_replica_hparams(kp1_mlp* m, const kp1_replica_hparams* host, int32_t n, void* stream);
+/* The same table written by ONE small launch, for every handle, K = 1 included: n must equal K; the K entries travel
+ * as kernel arguments and the launch writes the handle's table with plain vector stores.  No copy from caller memory is queued and nothing
+ * waits for `stream`: `host` is free on return.  Stream ordered -- launches already queued read the old values, later ones the new -- and
+ * capturable (the captured values are then the baked ones; call it eagerly to change what a captured graph reads).  From the first
+ * successful call on, replica k's kernels read entry k in place of the scalar arguments, exactly as after kp1_mlp_set_replica_hparams, and
+ * a K = 1 handle does so too: it launches the table-reading forms of those kernels for its one replica (hidden 256: mlp_tile_line_kernel
+ * and head_train_kernel<256, true>), bit for bit what the scalar forms compute on the same values.  kp1_mlp_set_replica_hparams(m, NULL, 0,
+ * ...) returns any handle to its scalar arguments.  Refused before anything is written: NULL arguments, n != K, a non-finite field, and a
+ * K = 1 handle with KP1_MLP_OPT_BF16X3_WGRAD on (KP1_ERR_UNSUPPORTED: the experiment has no line form; the option is likewise refused
+ * while a line is on).  While a K = 1 handle reads its line kp1_mlp_anchor_loss_grad / kp1_mlp_anchor_adam_step return
+ * KP1_ERR_UNSUPPORTED (their K = 1 forms take scalars). */
+int kp1_mlp_hparams_store(kp1_mlp* m, const kp1_replica_hparams* host, int32_t n, void* stream);
 int kp1_mlp_destroy(kp1_mlp* m);
 /* number of f32 parameters in SB3 state_dict order (log_std, pi.0.w, pi.0.b, pi.2.w, pi.2.b, vf.0.w, ..., action_net.w/b, value_net.w/b) */
 int64_t kp1_mlp_num_params(int32_t hidden);

@@ -40,8 +40,21 @@ from . import sb3_pickle as sbp
 SB3_VERSION_PIN = "2.8.0"
 
 
+def _schedule_entry(start: float, sched: dict[str, float] | None) -> dict[str, Any]:
+    """the ``lr_schedule`` / ``clip_range`` member: FloatSchedule(ConstantSchedule(start)), or with a schedule {end, end_fraction}
+    FloatSchedule(LinearSchedule(start, end, end_fraction)) and the three numbers in plain sight"""
+    entry = {":type:": "<class 'stable_baselines3.common.utils.FloatSchedule'>"}
+    if sched is None:
+        entry.update({":serialized:": sbp.serialized(sbp.float_schedule(start)), "value": float(start)})
+    else:
+        entry.update({":serialized:": sbp.serialized(sbp.linear_schedule(start, sched["end"], sched["end_fraction"])), "value": float(start),
+                      "end": float(sched["end"]), "end_fraction": float(sched["end_fraction"])})
+    return entry
+
+
 def _policy_data(ppo, env_cfg: kcfg.EnvConfig | None) -> dict[str, Any]:
     cfg = ppo.cfg
+    schedules = getattr(ppo, "hparam_schedules", None) or {}     # a scheduled trainer (DESIGN section 37); {} = constants, today's archive
     H = cfg.hidden
     layout = kcfg.OBS_LAYOUT
     if getattr(ppo, "obs_dim", kcfg.OBS_DIM) != kcfg.OBS_DIM:   # route wrappers with include_route_keys (route_observation.py:18-28)
@@ -64,10 +77,8 @@ def _policy_data(ppo, env_cfg: kcfg.EnvConfig | None) -> dict[str, Any]:
         "_total_timesteps": int(cfg.total_timesteps),
         "seed": int(cfg.seed),
         "learning_rate": float(cfg.learning_rate),
-        "lr_schedule": {":type:": "<class 'stable_baselines3.common.utils.FloatSchedule'>", ":serialized:": sbp.serialized(sbp.float_schedule(cfg.learning_rate)),
-                        "value": float(cfg.learning_rate)},
-        "clip_range": {":type:": "<class 'stable_baselines3.common.utils.FloatSchedule'>", ":serialized:": sbp.serialized(sbp.float_schedule(cfg.clip_range)),
-                       "value": float(cfg.clip_range)},
+        "lr_schedule": _schedule_entry(cfg.learning_rate, schedules.get("learning_rate")),
+        "clip_range": _schedule_entry(cfg.clip_range, schedules.get("clip_range")),
         "n_steps": int(cfg.n_steps), "batch_size": int(cfg.batch_size), "n_epochs": int(cfg.n_epochs),
         "gamma": float(cfg.gamma), "gae_lambda": float(cfg.gae_lambda), "ent_coef": float(cfg.ent_coef), "vf_coef": float(cfg.vf_coef),
         "max_grad_norm": float(cfg.max_grad_norm), "normalize_advantage": bool(cfg.normalize_advantage),
@@ -77,7 +88,8 @@ def _policy_data(ppo, env_cfg: kcfg.EnvConfig | None) -> dict[str, Any]:
         "_n_updates": int(ppo.n_updates()) if hasattr(ppo, "n_updates") else int(getattr(ppo, "n_train_calls", 0)) * int(cfg.n_epochs),
         # the rest of BaseAlgorithm / OnPolicyAlgorithm.__dict__ as SB3 2.8 saves it (values a freshly constructed model holds)
         "device": "auto", "verbose": 0, "_num_timesteps_at_start": 0, "action_noise": None, "start_time": 0, "tensorboard_log": None,
-        "_last_obs": None, "_last_episode_starts": None, "_last_original_obs": None, "_episode_num": 0, "_current_progress_remaining": 1.0,
+        "_last_obs": None, "_last_episode_starts": None, "_last_original_obs": None, "_episode_num": 0,
+        "_current_progress_remaining": float(ppo.progress_remaining) if schedules else 1.0,
         "_stats_window_size": 100, "ep_info_buffer": None, "ep_success_buffer": None,
         "rollout_buffer_class": {":type:": "<class 'abc.ABCMeta'>", "__module__": "stable_baselines3.common.buffers", "__name__": "DictRolloutBuffer",
                                  ":serialized:": sbp.serialized(sbp.ROLLOUT_BUFFER_CLASS)},
@@ -140,7 +152,9 @@ def optimizer_state_dict(ppo) -> dict[str, Any]:
         state[i] = {"step": step.clone(), "exp_avg": ppo.adam_m[off:off + n].view(shape).detach().cpu().clone(),
                     "exp_avg_sq": ppo.adam_v[off:off + n].view(shape).detach().cpu().clone()}
         off += n
-    group = {"lr": float(ppo.cfg.learning_rate), "betas": (0.9, 0.999), "eps": float(ppo.cfg.adam_eps), "weight_decay": 0, "amsgrad": False,
+    # (a scheduled trainer: the learning rate its last train() call used, what SB3's _update_learning_rate left in the group)
+    lr = ppo.current_hparams()["learning_rate"] if getattr(ppo, "hparam_schedules", None) else float(ppo.cfg.learning_rate)
+    group = {"lr": float(lr), "betas": (0.9, 0.999), "eps": float(ppo.cfg.adam_eps), "weight_decay": 0, "amsgrad": False,
              "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
              "params": list(range(len(ppo.policy.spec)))}
     return {"state": state, "param_groups": [group]}

@@ -62,6 +62,13 @@ void env_bound_stage_source(const kp1_env* env, const void** stage_ptr, const vo
 // kp1_env.hip -> kp1_mlp.hip: what a route chain cannot run on (an fp64 base env, route.sequence, recorded reward components, an attached prefix
 // tracker); text for kp1_last_error, or nullptr
 const char* route_chain_refusal(const kp1_route* r);
+// kp1_mlp_line.hip <- kp1_mlp.hip: the launches only a handle with a hyper-parameter line makes (kp1_mlp_hparams_store).  Their kernels live in
+// a code object of their own; the argument blocks (FusedArgs of kp1_mlp_tile.inc, HeadArgs of kp1_mlp.hip: the same text in both units) travel
+// as bytes, as StepArgs does above.  start / stop: the profile events of the launch, or nullptr.
+int mlp_line_launch_tile(const void* fused_args, size_t bytes, const float* line, dim3 grid, hipEvent_t start, hipEvent_t stop, hipStream_t stream);
+int mlp_line_launch_head_train256(const void* head_args, size_t bytes, dim3 grid, size_t lds_bytes, hipStream_t stream);
+// table[0 .. n_floats) = v[0 .. n_floats), the values as kernel arguments of one launch; n_floats <= KP1_MLP_MAX_REPLICAS entries
+int mlp_line_store(float* table, const float* v, int n_floats, hipStream_t stream);
 }  // namespace kp1
 
 #define HIP_TRY(expr)                                                                                              \

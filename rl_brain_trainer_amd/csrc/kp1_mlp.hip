@@ -966,6 +966,7 @@ __global__ void __launch_bounds__(256) grad_finalize_gated_kernel(const Finalize
 #include "kp1_grad_finalize_body.inc"
 }
 
+#ifndef KP1_MLP_LINE_TU   // a kernel that is no template is emitted wherever it is read: not into kp1_mlp_line.hip's code object
 // kp1_mlp_kl_gate_arm: a new train() call begins; the thresholds stay
 __global__ void kl_gate_arm_kernel(kp1_kl_gate* __restrict__ gate, int n) {
   const int r = (int)threadIdx.x;
@@ -973,6 +974,7 @@ __global__ void kl_gate_arm_kernel(kp1_kl_gate* __restrict__ gate, int n) {
     gate[r].stopped = 0; gate[r].n_counted = 0; gate[r].n_seen = 0; gate[r].stop_index = 0; gate[r].stop_kl = 0.f;
   }
 }
+#endif
 
 template <bool POP = false>
 __global__ void __launch_bounds__(256) sumsq_partials_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partials, unsigned r_partials) {
@@ -1260,16 +1262,23 @@ __global__ void __launch_bounds__(ADAM_BLOCK) anchor_adam_kernel(float* __restri
 }
 
 // the actor tensors have taken one more step than the rest: a launch of its own, after every block of anchor_adam_kernel has read the count
+#ifndef KP1_MLP_LINE_TU
 __global__ void anchor_count_kernel(int* __restrict__ cnt) {
   const int extra = cnt[CNT_EXTRA] + 1;
   cnt[CNT_EXTRA] = extra;
   adam_record_write(cnt, cnt[CNT_STEP], extra);   // an Adam launch on the device's counts finds its corrections whichever launch came last
 }
+#endif
 
 #include "kp1_env_step.inc"
 #include "kp1_eval_step.inc"
 #include "kp1_rollout_step.inc"
 #include "kp1_mlp_tile.inc"
+#ifdef KP1_MLP_LINE_TU
+// kp1_mlp_line.hip includes this file for the text above and nothing else: it instantiates the kernels only a handle with a hyper-parameter
+// line launches in a code object of its own, so that this file's code object is not touched by them
+}  // namespace
+#else
 #include "kp1_mlp_fused.inc"
 // (new kernels go after the tile kernels: including them earlier moved the tile kernels' addresses)
 #include "kp1_route_step.inc"
@@ -1310,7 +1319,8 @@ struct kp1_mlp {
   kp1_kl_gate* gate_dev = nullptr;
   bool gate_on = false;
   int actor_extra_host = 0;    // host mirror of [CNT_EXTRA] (set_option + one per anchor Adam step): a gate refuses a non-zero one
-  // population: per-replica hyper-parameter table [K][HP_FIELDS] (kp1_mlp_set_replica_hparams); the kernels read it while hparams_on
+  // hyper-parameter table [K][HP_FIELDS] (kp1_mlp_set_replica_hparams; kp1_mlp_hparams_store, which also gives a K = 1 handle its one
+  // line); the kernels read it while hparams_on -- a K = 1 handle then launches the forms that read it (line_on below)
   float* hparams_dev = nullptr;
   bool hparams_on = false;
   int last_s2_n = 0, last_s1_n = 0;
@@ -1554,8 +1564,8 @@ int launch_tile(dim3 grid, const FusedArgs& fa, hipStream_t stream) {
   return KP1_OK;
 }
 
-int launch_fused(const FusedArgs& fa_in, hipStream_t stream) {
-  FusedArgs fa = fa_in;
+// the training tile's grid, and the hold-back of the second workgroup of every CU
+dim3 fused_train_shape(FusedArgs& fa) {
   static const int stagger_us = [] { const char* e = std::getenv("KP1_FU_STAGGER_US"); return e ? std::atoi(e) : 11; }();  // tuning knob; re-swept in round 3 (profiles/r03_ab_tile_stagger.log): 10-13 us within 0.4 us of each other, a cliff at 14 (+6 us)
   static const int n_cus = [] {
     int dev = 0, n = 0;
@@ -1565,6 +1575,12 @@ int launch_fused(const FusedArgs& fa_in, hipStream_t stream) {
   const dim3 grid((fa.n + FU_BM - 1) / FU_BM, 1, 2);
   fa.n_cus = n_cus;
   fa.stagger_ticks = (int)(grid.x * grid.z) > n_cus ? stagger_us * 100 : 0;   // only when CUs hold two workgroups at once
+  return grid;
+}
+
+int launch_fused(const FusedArgs& fa_in, hipStream_t stream) {
+  FusedArgs fa = fa_in;
+  const dim3 grid = fused_train_shape(fa);
   if (fa.sp_h1 != nullptr)   // [r3 experiment] bf16 x 3 planes instead of the fp32 activation copies
     return fa.inp == 64 ? launch_tile<true, 2, 0, true>(grid, fa, stream) : launch_tile<true, 4, 0, true>(grid, fa, stream);
   return fa.inp == 64 ? launch_tile<true, 2>(grid, fa, stream) : launch_tile<true, 4>(grid, fa, stream);
@@ -1687,6 +1703,17 @@ int launch_layer_wgrads(kp1_mlp* m, const float* obs, int obs_stride, const int6
 
 // KP1_MLP_OPT_TRAIN_TILE (defined at the end of this file, see there)
 int launch_train_tile(kp1_mlp* m, const HeadArgs& heads, const float* obs, int obs_stride, int chunks, float* grad, hipStream_t stream);
+// the training tile of a K = 1 hidden-256 handle with a hyper-parameter line (kp1_mlp_hparams_store): the launch is kp1_mlp_line.hip's
+int launch_fused_line(const FusedArgs& fa_in, const float* line, hipStream_t stream) {
+  FusedArgs fa = fa_in;
+  const dim3 grid = fused_train_shape(fa);
+  hipEvent_t start = nullptr, stop = nullptr;   // KP1_LAUNCH's profile events, handed across
+  if (tl_prof.a != nullptr && !tl_prof.attached) {
+    tl_prof.attached = true;
+    start = tl_prof.a; stop = tl_prof.b;
+  }
+  return kp1::mlp_line_launch_tile(&fa, sizeof(fa), line, grid, start, stop, stream);
+}
 }  // namespace
 
 extern "C" {
@@ -1775,6 +1802,8 @@ int mlp_create(int32_t device, int32_t hidden, int32_t obs_dim, int32_t max_batc
   if (K > 1) MLP_ALLOC(m->hparams_dev, K * HP_FIELDS);
   MLP_ALLOC(m->bslab, K * (mb / 32) * 2 * Hp);
   MLP_ALLOC(m->hpart, K * (mb / 32) * (10 * Hp + 32));
+  // a K = 1 handle's one line (kp1_mlp_hparams_store), behind everything else: the allocations above keep the order they always had
+  if (K == 1) MLP_ALLOC(m->hparams_dev, HP_FIELDS);
 #undef MLP_ALLOC
   if (rc != KP1_OK) {
     kp1_mlp_destroy(m);
@@ -1821,6 +1850,7 @@ int kp1_mlp_set_option(kp1_mlp* m, int32_t option, int32_t value) {
   if (option == KP1_MLP_OPT_BF16X3_WGRAD) {
     if (value && m->K > 1) return fail(KP1_ERR_UNSUPPORTED, "the bf16x3 weight-gradient experiment is not available on population handles");
     if (value && !(m->fused && m->Hp == FU_HP)) return fail(KP1_ERR_UNSUPPORTED, "the bf16x3 weight-gradient experiment needs the 2x256 tile kernels");
+    if (value && m->hparams_on) return fail(KP1_ERR_UNSUPPORTED, "the bf16x3 weight-gradient experiment has no hyper-parameter line form (kp1_mlp_hparams_store)");
     if (value && !m->sp_h1) {
       HIP_TRY(hipSetDevice(m->device));
       const size_t act = (size_t)3 * 2 * m->max_batch * m->Hp * sizeof(unsigned short), xb = (size_t)3 * m->max_batch * m->L.INP * sizeof(unsigned short);
@@ -2348,6 +2378,9 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
   (void)grad_is_zero;  // every gradient element is written (not accumulated) by grad_finalize_kernel
   const bool fused = m->fused && Hp == FU_HP;
   const bool pop = m->K > 1;
+  // a handle whose kernels read the hyper-parameter table: a population with a table, or a K = 1 handle with its line on, which launches
+  // the population forms of those kernels with grid.y = 1 (replica 0: every per-replica offset is zero) and the line forms at hidden 256
+  const bool table = m->hparams_on, line_on = table && !pop;
   if (pop && !idx) return fail(KP1_ERR_INVALID, "population handles gather their rows through idx [K][n]");
   const int64_t hpart_rep = (int64_t)(m->max_batch / 32) * (10 * Hp + 32);
   int adv_mode = 0;
@@ -2375,7 +2408,7 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     }
     {
       ProfScope ps(m, KP1_MLP_PROFILE_TILE, stream);
-      rc = launch_fused(fa, stream);
+      rc = line_on ? launch_fused_line(fa, m->hparams_dev, stream) : launch_fused(fa, stream);
     }
     if (rc != KP1_OK) return rc;
   } else {
@@ -2389,7 +2422,7 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
     a.dz2 = m->dz2;
     a.hpart = m->hpart; a.hpart_stride = hpart_stride;
     a.r_act = (unsigned)(2 * act_stride); a.r_hpart = (unsigned)hpart_rep; a.r_partials = (unsigned)PARTIALS_STRIDE;
-    a.hparams = pop && m->hparams_on ? m->hparams_dev : nullptr;
+    a.hparams = table ? m->hparams_dev : nullptr;
     if (tt_chunks) {
       ProfScope ps(m, KP1_MLP_PROFILE_TILE, stream);
       rc = launch_train_tile(m, a, obs, obs_stride, tt_chunks, grad_out, stream);
@@ -2401,9 +2434,14 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
       const size_t hbytes = sizeof(float) * (HEADS * Hp + HEAD_ROWS * 8 + 84 + 2 * HEAD_ROWS * (Hp + 4));
       // pop: Hp = 128 (kp1_mlp_create_population)
       auto* kernel = head_train_kernel<128, true>;
-      if (!pop) kernel = Hp == 256 ? head_train_kernel<256> : head_train_kernel<128>;
-      HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hbytes));
-      hipLaunchKernelGGL(kernel, hgrid, dim3(256), hbytes, stream, a);
+      if (!pop && !line_on) kernel = Hp == 256 ? head_train_kernel<256> : head_train_kernel<128>;
+      if (line_on && Hp == 256) {
+        rc = kp1::mlp_line_launch_head_train256(&a, sizeof(a), hgrid, hbytes, stream);   // head_train_kernel<256, true>: kp1_mlp_line.hip
+        if (rc != KP1_OK) return rc;
+      } else {
+        HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hbytes));
+        hipLaunchKernelGGL(kernel, hgrid, dim3(256), hbytes, stream, a);
+      }
       rc = launch_nt<EPI_DTANH>(backward_nt_args(m, n), stream);
       if (rc != KP1_OK) return rc;
     }
@@ -2444,17 +2482,17 @@ int kp1_mlp_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, const in
   f.stats = stats_out; f.sumsq = m->partials + 2 * N_PARTIALS;
   f.step_counter = m->step_dev;
   f.r_sumsq = (unsigned)PARTIALS_STRIDE;
-  f.hparams = pop && m->hparams_on ? m->hparams_dev : nullptr;
+  f.hparams = table ? m->hparams_dev : nullptr;
   const int n_main = (int)((finalize_vec_items(L) + 255) / 256);
   m->n_finalize_blocks = n_main + (int)((finalize_wide_count(L) + 3 + 31) / 32);
   if (m->n_finalize_blocks > 2048) return fail(KP1_ERR_INVALID, "parameter vector too large for the sum-of-squares partial buffer");
   {
     ProfScope ps(m, KP1_MLP_PROFILE_FINALIZE, stream);
     if (m->gate_on) {
-      auto* kernel = pop ? grad_finalize_gated_kernel<true> : grad_finalize_gated_kernel<false>;
+      auto* kernel = pop || line_on ? grad_finalize_gated_kernel<true> : grad_finalize_gated_kernel<false>;
       KP1_LAUNCH(kernel, dim3(m->n_finalize_blocks, m->K), dim3(256), 0, stream, f, n_main, m->gate_dev);
     } else {
-      auto* kernel = pop ? grad_finalize_kernel<true> : grad_finalize_kernel<false>;
+      auto* kernel = pop || line_on ? grad_finalize_kernel<true> : grad_finalize_kernel<false>;
       KP1_LAUNCH(kernel, dim3(m->n_finalize_blocks, m->K), dim3(256), 0, stream, f, n_main);
     }
   }
@@ -2667,7 +2705,8 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   ProfScope ps(m, KP1_MLP_PROFILE_ADAM, stream);
   const bool pop = m->K > 1;
   const unsigned r_partials = pop ? (unsigned)PARTIALS_STRIDE : 0u;   // per-replica strides and the hyper-parameter table: population forms only
-  const float* hparams = pop && m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr;
+  const bool line_on = m->hparams_on && !pop;   // a K = 1 handle with its line on: the population forms of the Adam kernels, grid.y = 1
+  const float* hparams = m->hparams_on ? (const float*)m->hparams_dev : (const float*)nullptr;
   if (!fused_norm)
     hipLaunchKernelGGL(pop ? sumsq_partials_kernel<true> : sumsq_partials_kernel<false>, dim3(N_PARTIALS, m->K), dim3(256), 0, stream, grad, n,
                        m->partials + N_PARTIALS, r_partials);
@@ -2683,12 +2722,12 @@ int kp1_mlp_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_avg, fl
   if (frag_only) m->slab_stale = true;
   const dim3 grid((unsigned)((n + ADAM_BLOCK - 1) / ADAM_BLOCK), m->K);
   if (m->gate_on) {
-    auto* kernel = pop ? adam_gated_kernel<true> : adam_gated_kernel<false>;
+    auto* kernel = pop || line_on ? adam_gated_kernel<true> : adam_gated_kernel<false>;
     KP1_LAUNCH(kernel, grid, dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials, n_norm_partials, step > 0 ? step : 0,
                (const int*)m->step_dev, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), zero_grad, r_partials, hparams, m->L, kfmt,
                (const kp1_kl_gate*)m->gate_dev);
   } else {
-    auto* kernel = pop ? adam_kernel<true> : adam_kernel<false>;
+    auto* kernel = pop || line_on ? adam_kernel<true> : adam_kernel<false>;
     KP1_LAUNCH(kernel, grid, dim3(ADAM_BLOCK), 0, stream, params, grad, exp_avg, exp_avg_sq, n, norm_partials, n_norm_partials, step > 0 ? step : 0,
                (const int*)m->step_dev, lr, eps, max_grad_norm, bc1, std::sqrt(bc2), zero_grad, r_partials, hparams, m->L, kfmt);
   }
@@ -2767,6 +2806,8 @@ int kp1_mlp_anchor_loss_grad(kp1_mlp* m, const float* obs, int32_t obs_stride, c
                              float loss_weight, float* grad_out, float* loss_out, void* stream_) {
   if (!m || !obs || !teacher_actions || !grad_out || !loss_out) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_anchor_loss_grad");
   if (m->gate_on) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step is not covered while a KL gate is set on the handle (it reads the shared step count)");
+  if (m->K == 1 && m->hparams_on)
+    return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step is not covered while a K = 1 handle reads a hyper-parameter line (its K = 1 kernels take scalars)");
   int rc = check_batch_args(m, n, obs_stride);
   if (rc != KP1_OK) return rc;
   if (m->Hp != 128) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step runs on the layer-wise kernels: hidden must be 64 or 128");
@@ -2818,6 +2859,8 @@ int kp1_mlp_anchor_adam_step(kp1_mlp* m, float* params, float* grad, float* exp_
                              int32_t step, void* stream_) {
   if (!m || !params || !grad || !exp_avg || !exp_avg_sq) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_anchor_adam_step");
   if (m->gate_on) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step is not covered while a KL gate is set on the handle (it reads the shared step count)");
+  if (m->K == 1 && m->hparams_on)
+    return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step is not covered while a K = 1 handle reads a hyper-parameter line (its K = 1 kernels take scalars)");
   if (m->Hp != 128) return fail(KP1_ERR_UNSUPPORTED, "the teacher-anchor step runs on the layer-wise kernels: hidden must be 64 or 128");
   const int n_blocks = (int)((m->L.total + 255) / 256);
   if (n_blocks > ANCHOR_PARTIALS) return fail(KP1_ERR_INVALID, "parameter vector too large for the anchor sum-of-squares partials");
@@ -2859,10 +2902,30 @@ int launch_train_tile(kp1_mlp* m, const HeadArgs& heads, const float* obs, int o
   t.slab1 = m->slab1; t.s1_ld = f.s1_ld; t.s1_net = f.s1_net; t.s1_chunk = f.s1_chunk;
   t.bslab = m->bslab; t.b_net = f.b_net; t.b_tile = f.b_tile;
   t.r_slab2 = f.r_slab2; t.r_slab1 = f.r_slab1; t.r_bslab = f.r_bslab;
-  const bool pop = m->K > 1;
+  const bool pop = m->K > 1 || m->hparams_on;   // a K = 1 handle with its hyper-parameter line on runs the population form, grid.y = 1
   auto* kernel = INP == 64 ? (pop ? train_tile128_kernel<64, true> : train_tile128_kernel<64, false>)
                            : (pop ? train_tile128_kernel<128, true> : train_tile128_kernel<128, false>);
   KP1_LAUNCH(kernel, dim3(chunks, m->K, 2), dim3(ES_NTH), 0, stream, t);   // static LDS: no attribute call, capture-safe
   return KP1_OK;
 }
 }  // namespace
+
+extern "C" int kp1_mlp_hparams_store(kp1_mlp* m, const kp1_replica_hparams* host, int32_t n, void* stream) {
+  if (!m || !host) return fail(KP1_ERR_INVALID, "NULL argument to kp1_mlp_hparams_store");
+  if (n != m->K) return fail(KP1_ERR_INVALID, "kp1_mlp_hparams_store needs one entry per replica (n = K)");
+  for (int r = 0; r < n; ++r) {
+    const kp1_replica_hparams& h = host[r];
+    for (float v : {h.learning_rate, h.adam_eps, h.max_grad_norm, h.clip_range, h.ent_coef, h.vf_coef})
+      if (!std::isfinite(v)) return fail(KP1_ERR_INVALID, "kp1_mlp_hparams_store: hyper-parameters must be finite");
+  }
+  if (m->K == 1 && m->bf16x3) return fail(KP1_ERR_UNSUPPORTED, "the bf16x3 weight-gradient experiment has no hyper-parameter line form (kp1_mlp_hparams_store)");
+  int rc = mlp_check_device(m);
+  if (rc != KP1_OK) return rc;
+  // the entries travel as kernel arguments (kp1_mlp_line.hip's hparams_store_kernel): no copy from caller memory is queued, `host` is free on
+  // return and nothing waits for the stream
+  rc = kp1::mlp_line_store(m->hparams_dev, reinterpret_cast<const float*>(host), n * HP_FIELDS, (hipStream_t)stream);
+  if (rc != KP1_OK) return rc;
+  m->hparams_on = true;
+  return KP1_OK;
+}
+#endif  // KP1_MLP_LINE_TU

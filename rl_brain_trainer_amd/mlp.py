@@ -56,6 +56,7 @@ class MlpKernels:
         self.fused = True                                # what set_fused last set (hidden 256: the tile kernels; the handle's default is on)
         self.train_tile = False                          # what set_train_tile last set (hidden 64 / 128: train_tile128_kernel; default off)
         self.kl_gate = False                             # whether set_kl_gate has a gate set (default: none)
+        self.hparam_line = False                         # whether the kernels read the handle's hyper-parameter table (hparams_store / set_replica_hparams)
         if replicas == 1:
             native.check(L.kp1_mlp_create_ex(device.index or 0, hidden, self.obs_dim, self.max_batch, C.byref(self._h)))
         else:
@@ -124,9 +125,21 @@ class MlpKernels:
         replica; replica k's loss / Adam kernels then read row k in place of the scalar arguments.  None clears the table."""
         if rows is None:
             native.check(self.L.kp1_mlp_set_replica_hparams(self._h, None, 0, self._stream()))
+            self.hparam_line = False
             return
         table = (C.c_float * (len(rows) * len(self.HPARAM_FIELDS)))(*[float(r[f]) for r in rows for f in self.HPARAM_FIELDS])
         native.check(self.L.kp1_mlp_set_replica_hparams(self._h, C.cast(table, C.c_void_p), len(rows), self._stream()))
+        self.hparam_line = True
+
+    def hparams_store(self, rows: list[dict[str, float]]) -> None:
+        """Every handle, K = 1 included: the same table written by one small launch on the current stream (kp1_mlp_hparams_store) -- no copy
+        from host memory, no wait; launches queued before it read the old values, later ones (and later replays of a captured graph, which
+        holds only the table's address) the new.  One dict with every HPARAM_FIELDS key per replica, rounded to fp32 here as a scalar
+        argument would be.  From the first call on the kernels read the table in place of loss_grad's and adam_step's scalars;
+        ``set_replica_hparams(None)`` returns the handle to them."""
+        table = (C.c_float * (len(rows) * len(self.HPARAM_FIELDS)))(*[float(r[f]) for r in rows for f in self.HPARAM_FIELDS])
+        native.check(self.L.kp1_mlp_hparams_store(self._h, C.cast(table, C.c_void_p), len(rows), self._stream()))
+        self.hparam_line = True
 
     def set_kl_gate(self, targets: list[float | None] | None) -> None:
         """SB3 PPO's ``target_kl`` as a device decision (kp1_mlp_set_kl_gate): one target per replica, None = that replica never stops.

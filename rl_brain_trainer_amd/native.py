@@ -153,6 +153,7 @@ def load() -> C.CDLL:
     L.kp1_mlp_set_kl_gate.argtypes = [vp, vp, i32, vp]
     L.kp1_mlp_kl_gate_arm.argtypes = [vp, vp]
     L.kp1_mlp_kl_gate_read.argtypes = [vp, vp, vp, vp]
+    L.kp1_mlp_hparams_store.argtypes = [vp, vp, i32, vp]
     L.kp1_monitor_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.kp1_monitor_destroy.argtypes = [vp]
     L.kp1_monitor_observe.argtypes = [vp, vp, vp, i32, vp]

@@ -32,7 +32,7 @@ import torch
 from . import native
 from .curriculum import PointCurriculumPopulation
 from .finisher_tools import DockReverseCurriculumPopulation
-from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig, check_target_kl
+from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig, check_schedules, check_target_kl
 from .route_curriculum import RoutePrefixCurriculumPopulation
 from .route_env import RoutePopulationVecEnv
 from .vec_env import ArmKinematicPopulationVecEnv
@@ -120,6 +120,13 @@ class ReplicaView:
     n_train_calls = property(lambda self: self._pop.n_train_calls)
     last_stats = property(lambda self: self._pop.replica_stats(self.k))
     update_form = property(lambda self: self._pop.update_form)
+    # a scheduled population: the shared schedules and clock, this replica's values of the last train() call
+    hparam_schedules = property(lambda self: self._pop.hparam_schedules)
+    progress_remaining = property(lambda self: self._pop.progress_remaining)
+
+    def current_hparams(self, k: int = 0) -> dict[str, float]:
+        """this replica's learning rate and clip range as the last train() call used them"""
+        return self._pop.current_hparams(self.k)
 
     def n_updates(self, k: int = 0) -> int:
         """SB3's ``_n_updates`` of this replica"""
@@ -201,6 +208,7 @@ class PopulationPPO(PPO):
         if dist.enabled:
             raise ValueError("PopulationPPO is single-process: data parallel (a torch.distributed process group) is not supported")
         check_target_kl([o.get("target_kl", cfg.target_kl) for o in overrides], dist, teacher_anchor)
+        check_schedules(cfg, teacher_anchor)
         return seeds, dist, overrides
 
     def _init_population(self, seeds: list[int], cfg: PPOConfig, envs: list[Any], curricula: list[Any], dist: Dist, use_graphs: bool,
@@ -221,6 +229,8 @@ class PopulationPPO(PPO):
         self._gamma_lambda = torch.zeros((K, 2), dtype=torch.float32, device=dev) if self.has_overrides else None
         self._apply_overrides()
         self._setup_kl_gate(check_target_kl([c.target_kl for c in self.cfgs], dist))
+        # every replica anneals from its own start (cfgs[k].learning_rate / clip_range: the sweep's value) to the shared end
+        self._setup_schedules(check_schedules(cfg))
         self.noise_rep = torch.zeros((K, T, N, ACT_DIM), dtype=torch.float32, device=dev)   # replica k's draw, as PPO.noise_all
         # minibatch i of replica k = local positions [start_i, end_i) of its shuffle; the kernels read minibatch i as ONE [K][n_i] index
         # block at K * start_i of the gathered index vector

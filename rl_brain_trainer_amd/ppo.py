@@ -59,6 +59,13 @@ class PPOConfig:
     hidden: int = 64            # SB3 default net_arch = dict(pi=[64, 64], vf=[64, 64])
     normalize_advantage: bool = True
     total_timesteps: int = 100_000
+    # SB3's LinearSchedule for the learning rate / the clip range: {end, end_fraction}, the value running from
+    # `learning_rate` / `clip_range` (the start, which --learning-rate, --sweep and "the YAML learning rate wins on resume" keep addressing)
+    # to `end` over the first `end_fraction` of the run.  None: a constant, and then nothing differs from a build without them.
+    # Keyword-only: in the constructor they stand behind target_kl, so positional use of every other field is unchanged.  Hence
+    # dataclasses.fields / astuple list them in front of target_kl, not in the constructor's order; nothing here relies on either order
+    learning_rate_schedule: dict | None = field(default=None, kw_only=True)
+    clip_range_schedule: dict | None = field(default=None, kw_only=True)
     # SB3's target_kl: train() leaves its epochs once a minibatch's approx_kl exceeds 1.5 * target_kl (None: never).  Decided on the device
     # (DESIGN section 35); last, so positional use of the fields above is unchanged
     target_kl: float | None = None
@@ -473,6 +480,58 @@ def check_target_kl(targets: list[float | None], dist: Any, teacher_anchor: Any 
     return out
 
 
+SCHEDULE_KEYS = ("end", "end_fraction")
+
+
+def linear_schedule(start: float, end: float, end_fraction: float, progress_remaining: float) -> float:
+    """stable_baselines3.common.utils.LinearSchedule(start, end, end_fraction)(progress_remaining), in Python floats (restated from SB3 2.8;
+    parity unpinned)"""
+    if (1 - progress_remaining) > end_fraction:
+        return end
+    return start + (1 - progress_remaining) * (end - start) / end_fraction
+
+
+def check_schedule(name: str, sched: Any, *, end_may_be_zero: bool) -> dict[str, float] | None:
+    """one ``PPOConfig.*_schedule`` mapping as {end, end_fraction} floats, or None (unset).  ValueError: not a mapping, unknown or missing
+    keys, non-finite values, end_fraction outside (0, 1], a negative end (``end_may_be_zero``: the learning rate may reach 0, the clip
+    range must stay positive)."""
+    if sched is None:
+        return None
+    if not isinstance(sched, dict):
+        raise ValueError(f"{name} must be a mapping {{end, end_fraction}} (got {type(sched).__name__})")
+    unknown, missing = sorted(set(sched) - set(SCHEDULE_KEYS)), [k for k in SCHEDULE_KEYS if k not in sched]
+    if unknown:
+        raise ValueError(f"{name} has unknown keys {unknown}: a schedule is {{end, end_fraction}}, its start is the field it anneals")
+    if missing:
+        raise ValueError(f"{name} needs the keys {list(SCHEDULE_KEYS)} (missing {missing})")
+    try:
+        end, frac = float(sched["end"]), float(sched["end_fraction"])
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} needs numbers for end and end_fraction (got {sched!r})") from None
+    if not (math.isfinite(end) and math.isfinite(frac)):
+        raise ValueError(f"{name} must be finite (got {sched!r})")
+    if not 0.0 < frac <= 1.0:
+        raise ValueError(f"{name}: end_fraction must lie in (0, 1] (got {frac!r})")
+    if end < 0.0 or (end == 0.0 and not end_may_be_zero):
+        raise ValueError(f"{name}: end must be {'>= 0' if end_may_be_zero else '> 0'} (got {end!r})")
+    return {"end": end, "end_fraction": frac}
+
+
+def check_schedules(cfg: "PPOConfig", teacher_anchor: Any = None) -> dict[str, dict[str, float]] | None:
+    """The refusals of ``learning_rate_schedule`` / ``clip_range_schedule`` before any device work.  Returns {field: {end, end_fraction}} of
+    the schedules set, or None when both are unset.  The reference's teacher-anchor callback steps with whatever learning rate the
+    optimiser last held; that is not restated, so an anchor together with a schedule is refused."""
+    out = {}
+    for fld, zero_ok in (("learning_rate", True), ("clip_range", False)):
+        s = check_schedule(f"{fld}_schedule", getattr(cfg, f"{fld}_schedule", None), end_may_be_zero=zero_ok)
+        if s is not None:
+            out[fld] = s
+    if out and teacher_anchor is not None:
+        raise ValueError("a learning-rate / clip-range schedule is not supported together with a teacher anchor: the anchor step's learning "
+                         "rate under a schedule is not restated")
+    return out or None
+
+
 def fused_rollout_covered(env_type_ok: bool, dtype: Any, hidden: int, obs_dim: int, components_on: bool, env_var: str | None, *,
                           default_on: bool = True) -> bool:
     """Whether a rollout step runs as ONE launch (policy forward + sampling + env step with auto-reset) instead of forward + step_into.
@@ -575,11 +634,13 @@ class PPO:
 
         _monitor.check_monitor(monitor, dist)     # a data-parallel run is refused before any device work
         targets = check_target_kl([cfg.target_kl], dist)
+        schedules = check_schedules(cfg)
         self.env = env
         self.curriculum = curriculum
         self._setup(cfg, [cfg.seed], [env], [curriculum], dist, use_graphs, min_batch=8192, stacked=False, monitor=monitor)
         self.policy = self.policies[0]
         self._setup_kl_gate(targets)
+        self._setup_schedules(schedules)
         T, N, dev = cfg.n_steps, self.n_envs, self.device
         # data parallel: done bytes are exchanged once per `done_chunk` env steps (one all-gather of chunk x N bytes instead of one
         # latency-bound collective per 45 us env step); the device tracker replays the chunk in the reference's order
@@ -837,6 +898,51 @@ class PPO:
         self.adam_steps = [int(self.adam_t)] * self.K
         self.kl_n_updates = [self.n_train_calls * self.cfg.n_epochs] * self.K
 
+    # ------------------------------------------------------------------ learning-rate / clip-range schedules
+    # None = no schedule, the default, and then no launch, graph or archive byte differs from a build without them
+    hparam_schedules: dict[str, dict[str, float]] | None = None
+    # SB3's _current_progress_remaining: run_training sets it after every rollout; a caller driving collect_rollouts() / train() sets it itself
+    progress_remaining: float = 1.0
+
+    def _setup_schedules(self, schedules: dict[str, dict[str, float]] | None) -> None:
+        """With a schedule set, every train() call writes the replicas' hyper-parameters of that call into the MLP handle's table with one
+        small launch (``_store_scheduled_hparams``) and the update's kernels read them there: the captured epoch graph holds the table's
+        address, so a value that changes from iteration to iteration costs neither a synchronisation nor a re-capture."""
+        if not schedules:
+            return
+        self.hparam_schedules = dict(schedules)
+        self.scheduled_values: list[dict[str, float]] | None = None     # per replica, what the last train() call used (Python floats)
+
+    def scheduled_hparams(self, k: int = 0) -> dict[str, float]:
+        """replica k's learning rate and clip range at ``progress_remaining``: SB3's ``lr_schedule(p)`` / ``clip_range(p)``, in Python floats"""
+        c = (getattr(self, "cfgs", None) or [self.cfg] * self.K)[k]
+        out = {"learning_rate": float(c.learning_rate), "clip_range": float(c.clip_range)}
+        for fld, s in (self.hparam_schedules or {}).items():
+            out[fld] = linear_schedule(out[fld], s["end"], s["end_fraction"], self.progress_remaining)
+        return out
+
+    def _store_scheduled_hparams(self) -> None:
+        """a scheduled trainer's train() begins here (SB3: _update_learning_rate and clip_range(p), held for all epochs of the call): every
+        replica's six hyper-parameters -- what the kernels otherwise get as scalars, ent_coef / world included -- into the handle's table,
+        one eager launch, no host wait"""
+        cfgs = getattr(self, "cfgs", None) or [self.cfg] * self.K
+        self.scheduled_values = [self.scheduled_hparams(k) for k in range(self.K)]
+        rows = []
+        for c, now in zip(cfgs, self.scheduled_values):
+            row = {f: float(getattr(c, f)) for f in self._mlp.HPARAM_FIELDS}
+            row.update(now)
+            row["ent_coef"] = c.ent_coef / self.dist.world_size
+            rows.append(row)
+        self._mlp.hparams_store(rows)
+
+    def current_hparams(self, k: int = 0) -> dict[str, float]:
+        """replica k's learning rate and clip range as the last train() call used them (SB3's train/learning_rate, train/clip_range; the
+        optimiser group's lr): the config's constants without a schedule or before the first call"""
+        c = (getattr(self, "cfgs", None) or [self.cfg] * self.K)[k]
+        if self.hparam_schedules is not None and self.scheduled_values is not None:
+            return dict(self.scheduled_values[k])
+        return {"learning_rate": float(c.learning_rate), "clip_range": float(c.clip_range)}
+
     # ------------------------------------------------------------------ training monitor
     def _setup_monitor(self, monitor: bool | int) -> None:
         """``monitor=``: the device handle over the K x N rollout columns, the explained-variance output and the log_std snapshot.  The three
@@ -882,15 +988,15 @@ class PPO:
         ev = self._ev_dev.tolist()
         std = torch.exp(self._log_std_snap).mean(dim=1).tolist()     # th.exp(policy.log_std).mean(), in fp32 as SB3 takes it
         stats = self._stats_rows()
-        cfgs = getattr(self, "cfgs", None) or [self.cfg] * self.K
         rows = []
         for k in range(self.K):
             row = _monitor.episode_record(self.monitor.read(k))
             s = stats[k]
-            row.update({"train/approx_kl": s.get("approx_kl"), "train/clip_range": float(cfgs[k].clip_range),
+            now = self.current_hparams(k)      # under a schedule: the values the last train() used
+            row.update({"train/approx_kl": s.get("approx_kl"), "train/clip_range": now["clip_range"],
                         "train/entropy_loss": -s["entropy"] if "entropy" in s else None,
                         "train/explained_variance": _monitor.explained_variance(ev[k][0], ev[k][1]),
-                        "train/learning_rate": float(cfgs[k].learning_rate), "train/n_updates": self.n_updates(k),
+                        "train/learning_rate": now["learning_rate"], "train/n_updates": self.n_updates(k),
                         "train/policy_gradient_loss": s.get("policy_loss"), "train/std": std[k] if self.n_train_calls else None,
                         "train/value_loss": s.get("value_loss")})
             if self.kl_targets is not None and self._kl_fresh[k]:     # reported once: TrainLogger prints SB3's early-stopping line
@@ -943,6 +1049,10 @@ class PPO:
         c = self.cfg
         key = (c.learning_rate, c.clip_range, c.ent_coef, c.vf_coef, c.max_grad_norm, c.adam_eps, c.batch_size, c.n_steps, c.normalize_advantage,
                self.dist.world_size, self._mlp.train_tile)
+        if self.hparam_schedules is not None:
+            # a scheduled trainer's kernels read learning rate and clip range from the handle's table: the graph froze its address, so the key
+            # carries which of the two are scheduled in place of the values
+            key = key[2:-1] + (("hparam_line", tuple(sorted(self.hparam_schedules))),) + key[-1:]
         if self.kl_targets is not None:     # a gated trainer captured the gated launches; the last element stays the train-tile flag
             key = key[:-1] + (("kl_gate", tuple(self.kl_targets)),) + key[-1:]
         return key
@@ -1249,6 +1359,8 @@ class PPO:
         self.stats_dev.zero_()
         if gated:
             self._mlp.kl_gate_arm()
+        if self.hparam_schedules is not None:
+            self._store_scheduled_hparams()
         for _epoch in range(cfg.n_epochs):
             for k in range(self.K):
                 self._draw_perm(k)
@@ -1412,7 +1524,9 @@ def run_training(trainer: PPO, total_timesteps: int, *, after_rollout=None, afte
                  csv_paths: list[Any] | None = None, tag: str | None = None) -> tuple[float, int]:
     """THE training loop of every trainer (PPO.learn, the three CLIs and their --seeds forms): iterations of rollout and update until
     ``trainer`` (a PPO or any population; the step clock counts each replica's own env steps) has taken ``total_timesteps`` env steps from
-    where its clock stands.  Per iteration: ``collect_rollouts()``, ``after_rollout(trainer)`` (the teacher anchor), ``train()``,
+    where its clock stands.  Per iteration: ``collect_rollouts()``, ``after_rollout(trainer)`` (the teacher anchor), SB3's
+    ``_update_current_progress_remaining`` (``trainer.progress_remaining = 1 - num_timesteps / (start + total_timesteps)``, ``start`` the
+    clock as the loop found it: what ``learn(reset_num_timesteps=False)`` computes; the schedules of ``train()`` read it), ``train()``,
     ``after_update(trainer, steps_taken)`` (gates, periodic checkpoints); then every ``log_every`` iterations (0: never) either the
     monitor's record per replica -- SB3's table, a row of ``csv_paths[k]`` where given, and under the line ``[tag] it=.. replica <name>``
     where a population's caller passes ``tag`` -- or, without a monitor and on rank 0, the line ``status(trainer, it, steps_taken,
@@ -1425,6 +1539,7 @@ def run_training(trainer: PPO, total_timesteps: int, *, after_rollout=None, afte
         trainer.collect_rollouts()
         if after_rollout is not None:
             after_rollout(trainer)
+        trainer.progress_remaining = 1.0 - float(trainer.num_timesteps) / float(start + total_timesteps)
         trainer.train()
         it += 1
         if after_update is not None:

@@ -12,6 +12,7 @@ State written (pins: gymnasium==1.2.3, stable-baselines3==2.8.0, final_codes_doc
                                 (Space.__setstate__ updates __dict__; Box.__setstate__ only fills missing *_repr)
   gymnasium.spaces.dict.Dict    spaces (key-sorted dict, as Dict.__init__ sorts a plain dict), _shape = None, dtype = None, _np_random = None
   stable_baselines3.common.utils.FloatSchedule     value_schedule = ConstantSchedule(val)   (what FloatSchedule(float) builds)
+                                                   or LinearSchedule(start, end, end_fraction): attributes start, end, end_fraction
   classes by reference          stable_baselines3.common.policies.MultiInputActorCriticPolicy, stable_baselines3.common.buffers.DictRolloutBuffer
 
 PARITY UNPINNED: neither library is importable in this image and the reference tree holds no archive to compare with, so the attribute sets
@@ -45,6 +46,10 @@ class _ConstantScheduleStandIn:
     pass
 
 
+class _LinearScheduleStandIn:
+    pass
+
+
 class _PolicyClassStandIn:
     pass
 
@@ -59,6 +64,7 @@ _REAL = {
     "_DictStandIn": ("gymnasium.spaces.dict", "Dict"),
     "_FloatScheduleStandIn": ("stable_baselines3.common.utils", "FloatSchedule"),
     "_ConstantScheduleStandIn": ("stable_baselines3.common.utils", "ConstantSchedule"),
+    "_LinearScheduleStandIn": ("stable_baselines3.common.utils", "LinearSchedule"),
     "_PolicyClassStandIn": ("stable_baselines3.common.policies", "MultiInputActorCriticPolicy"),
     "_RolloutBufferClassStandIn": ("stable_baselines3.common.buffers", "DictRolloutBuffer"),
 }
@@ -92,6 +98,16 @@ def float_schedule(value: float) -> _FloatScheduleStandIn:
     c.__dict__.update({"val": float(value)})
     s = _FloatScheduleStandIn()
     s.__dict__.update({"value_schedule": c})
+    return s
+
+
+def linear_schedule(start: float, end: float, end_fraction: float) -> _FloatScheduleStandIn:
+    """FloatSchedule(LinearSchedule(start, end, end_fraction)): what SB3 holds as ``lr_schedule`` / ``clip_range`` for a linearly annealed
+    value (PPOConfig.learning_rate_schedule / clip_range_schedule)"""
+    lin = _LinearScheduleStandIn()
+    lin.__dict__.update({"start": float(start), "end": float(end), "end_fraction": float(end_fraction)})
+    s = _FloatScheduleStandIn()
+    s.__dict__.update({"value_schedule": lin})
     return s
 
 

@@ -82,6 +82,9 @@ class RouteTeacherAnchor:
         if getattr(ppo, "kl_targets", None) is not None:
             raise ValueError("the teacher anchor is not supported on a trainer whose config sets target_kl: its step reads the shared Adam step "
                              "count that a KL-gated handle keeps per replica")
+        if getattr(ppo, "hparam_schedules", None) is not None:
+            raise ValueError("the teacher anchor is not supported on a trainer whose config sets a learning-rate / clip-range schedule: the "
+                             "anchor step's learning rate under a schedule is not restated")
         flat_obs, actions = load_anchor_dataset(self.config.dataset_path, int(self.config.max_route_index), ppo.obs_dim)
         self.actor_extra_steps = int(getattr(ppo, "actor_extra_steps", 0))   # a resumed teacher-anchored run carries its count
         self._obs = torch.as_tensor(flat_obs, device=ppo.device)

@@ -4,7 +4,7 @@
 # part 2 (GPU box): bash tools/ab_run.sh name1 name2 ... -- <command>   copies each variant over rl_brain_trainer_amd/libkp1.so and runs the command
 cd "$(dirname "$0")/.."
 mkdir -p build_ab
-S="rl_brain_trainer_amd/csrc/kp1_env.hip rl_brain_trainer_amd/csrc/kp1_ppo.hip rl_brain_trainer_amd/csrc/kp1_mlp.hip"
+S="rl_brain_trainer_amd/csrc/kp1_env.hip rl_brain_trainer_amd/csrc/kp1_ppo.hip rl_brain_trainer_amd/csrc/kp1_mlp.hip rl_brain_trainer_amd/csrc/kp1_mlp_line.hip"
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -mllvm -amdgpu-function-calls=false"
 pids=()
 while [ $# -gt 1 ]; do

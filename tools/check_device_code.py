@@ -101,23 +101,38 @@ def compare_disassembly(dis_a: str, dis_b: str) -> tuple[list[tuple[str, int, in
 
 
 def compare(lib_a: Path, lib_b: Path) -> int:
-    """Per code object and kernel symbol: which kernels of LIB_A and LIB_B differ in instruction text.  Exit status 1 when any does."""
+    """Per code object and kernel symbol: which kernels of LIB_A and LIB_B differ in instruction text.  Exit status 1 when any does.
+    Code objects are paired by the kernel symbols they share (a translation unit added to or removed from one build shifts the numbering);
+    the kernels of a code object without a partner are listed as being in one build only."""
     n_bad = n_all = 0
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        cos_a, cos_b = device_code_objects(lib_a, Path(ta)), device_code_objects(lib_b, Path(tb))
-        if len(cos_a) != len(cos_b):
-            print(f"[check_device_code] {len(cos_a)} code objects in {lib_a}, {len(cos_b)} in {lib_b}")
-            return 1
-        for co_a, co_b in zip(cos_a, cos_b):
-            dis_a, dis_b = (subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], check=True, capture_output=True, text=True).stdout for co in (co_a, co_b))
-            differ, only_a, only_b, total = compare_disassembly(dis_a, dis_b)
-            for name, na, nb, nd in differ:
-                print(f"[check_device_code] {co_a.name}: differs  A {na:6d}  B {nb:6d} instructions, {nd:6d} lines differ  {name}")
+        dis_a, dis_b = ([(co.name, subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(co)], check=True, capture_output=True, text=True).stdout)
+                         for co in device_code_objects(lib, Path(tmp))] for lib, tmp in ((lib_a, ta), (lib_b, tb)))
+        names_b = [set(kernel_listings(d)) for _, d in dis_b]
+        free_b = set(range(len(dis_b)))
+        for name_a, d_a in dis_a:
+            shared = {j: len(set(kernel_listings(d_a)) & names_b[j]) for j in free_b}
+            j = max(shared, key=shared.get, default=None)
+            if j is None or shared[j] == 0:
+                name, d_b = "-", ""
+            else:
+                free_b.discard(j)
+                name, d_b = dis_b[j]
+            if name != name_a:
+                print(f"[check_device_code] {name_a} of A against {name} of B")
+            differ, only_a, only_b, total = compare_disassembly(d_a, d_b)
+            for kernel, na, nb, nd in differ:
+                print(f"[check_device_code] {name_a}: differs  A {na:6d}  B {nb:6d} instructions, {nd:6d} lines differ  {kernel}")
             for side, names in (("A", only_a), ("B", only_b)):
-                for name in names:
-                    print(f"[check_device_code] {co_a.name}: only in {side}  {name}")
+                for kernel in names:
+                    print(f"[check_device_code] {name_a}: only in {side}  {kernel}")
             n_bad += len(differ) + len(only_a) + len(only_b)
             n_all += total
+        for j in sorted(free_b):
+            for kernel in sorted(names_b[j]):
+                print(f"[check_device_code] {dis_b[j][0]}: only in B  {kernel}")
+            n_bad += len(names_b[j])
+            n_all += len(names_b[j])
     print(f"[check_device_code] {n_bad} of {n_all} kernels differ")
     return 1 if n_bad else 0
 

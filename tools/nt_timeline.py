@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 out_dir = os.path.join(ROOT, "gpurun_out")
 os.makedirs(out_dir, exist_ok=True)
 lib = os.path.join(out_dir, "libkp1_trace.so")
-srcs = [os.path.join(ROOT, "rl_brain_trainer_amd/csrc", f) for f in ("kp1_env.hip", "kp1_ppo.hip", "kp1_mlp.hip")]
+srcs = [os.path.join(ROOT, "rl_brain_trainer_amd/csrc", f) for f in ("kp1_env.hip", "kp1_ppo.hip", "kp1_mlp.hip", "kp1_mlp_line.hip")]
 extra = [f"-D{d}" for d in os.environ.get("KP1_TRACE_DEFS", "").split() if d]   # e.g. KP1_FU_NOMFMA
 if os.environ.get("KP1_TRACE_LIB"):      # a library already built with -DKP1_NT_TRACE (tools/ab_build.sh)
     lib = os.path.join(ROOT, os.environ["KP1_TRACE_LIB"])
