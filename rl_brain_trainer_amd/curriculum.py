@@ -13,8 +13,8 @@ import torch
 
 from . import native
 
-MAX_WINDOW = 1024
-MAX_HISTORY = 64
+MAX_WINDOW = native.header_int("KP1_CURRICULUM_MAX_WINDOW")
+MAX_HISTORY = native.header_int("KP1_CURRICULUM_MAX_HISTORY")
 
 
 class _Event(C.Structure):

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import config as kcfg
+from . import native
 
 # keys a reverse-curriculum stage may override (callbacks.py:131-150): three env scalars, the dock_reset block
 _STAGE_ENV_KEYS = ("action_delta_scale", "dock_residual_action_limit", "dock_delta_q_change_limit_scale")
@@ -30,7 +31,7 @@ _STAGE_RESET_VECTORS = ("close_init_q_noise", "init_q_noise")
 _STAGE_BUFFER_KEYS = ("handoff_state_buffer_path", "handoff_state_max_position_error_m", "handoff_state_max_orientation_error_rad", "handoff_state_max_action_l2")
 _BUFFER_DEFAULTS = {"handoff_state_buffer_path": "", "handoff_state_max_position_error_m": 1.0, "handoff_state_max_orientation_error_rad": 10.0,
                     "handoff_state_max_action_l2": 10.0}   # DockResetConfig defaults, reset_samplers.py:109-113
-MAX_STAGES, MAX_WINDOW, MAX_HISTORY = 16, 1024, 32
+MAX_STAGES, MAX_WINDOW, MAX_HISTORY = (native.header_int("KP1_DOCK_CURRICULUM_MAX_" + n) for n in ("STAGES", "WINDOW", "HISTORY"))
 
 
 class _Stage(C.Structure):
@@ -116,14 +117,7 @@ class DockReverseCurriculum:
     # ---------------------------------------------------------------- device side
     def attach(self, env: Any) -> None:
         """_on_training_start: allocate the tracker next to the env; stage 0 is applied on the device before the first reset"""
-        from . import native
-
         L = env.L
-        vp, i32 = C.c_void_p, C.c_int32
-        L.kp1_dock_curriculum_create.argtypes = [vp, C.POINTER(_Stage), i32, i32, C.POINTER(vp)]
-        L.kp1_dock_curriculum_destroy.argtypes = [vp, vp]
-        L.kp1_dock_curriculum_observe.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-        L.kp1_dock_curriculum_read.argtypes = [vp, vp, C.POINTER(_State), vp]
         self.env = env
         buffers = self.stage_buffers(env.config)
         if buffers is not None:
@@ -139,15 +133,11 @@ class DockReverseCurriculum:
         self.observe_chunk(dones, int(dones.numel()), 1, 1)
 
     def observe_chunk(self, dones_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
-        from . import native
-
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
         native.check(self.env.L.kp1_dock_curriculum_observe(self.env._handle, self._st, C.c_void_p(dones_all.data_ptr()), int(n_local), int(chunk_steps),
                                                             int(world), C.c_void_p(stream)))
 
     def read(self) -> _State:
-        from . import native
-
         out = _State()
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
         native.check(self.env.L.kp1_dock_curriculum_read(self.env._handle, self._st, C.byref(out), C.c_void_p(stream)))
@@ -208,8 +198,6 @@ class DockReverseCurriculumPopulation(DockReverseCurriculum):
         self.configs: list[kcfg.EnvConfig] = []
 
     def attach(self, env: Any) -> None:
-        from . import native
-
         if not getattr(env, "is_population", False):
             raise TypeError("DockReverseCurriculumPopulation tracks the replicas of an ArmKinematicPopulationVecEnv")
         if env.config.mode_name != "dock":
@@ -217,11 +205,6 @@ class DockReverseCurriculumPopulation(DockReverseCurriculum):
         if getattr(env, "K", self.K) != self.K or env.n_envs % self.K != 0:
             raise ValueError(f"a population env of {env.n_envs} envs does not split into this tracker's {self.K} replicas")
         L = env.L
-        vp, i32 = C.c_void_p, C.c_int32
-        L.kp1_dock_curriculum_create_population.argtypes = [vp, C.POINTER(_Stage), i32, i32, i32, C.POINTER(vp)]
-        L.kp1_dock_curriculum_observe_population.argtypes = [vp, vp, vp, i32, i32, vp]
-        L.kp1_dock_curriculum_read_replica.argtypes = [vp, vp, i32, i32, C.POINTER(_State), vp]
-        L.kp1_dock_curriculum_destroy.argtypes = [vp, vp]
         buffers = self.stage_buffers(env.config)
         if buffers is not None:
             env.set_handoff_states([state for stage_states in buffers for state in stage_states])
@@ -237,8 +220,6 @@ class DockReverseCurriculumPopulation(DockReverseCurriculum):
 
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
         """dones: the K N done bytes of one population step (replica-major); every clock advances by N whatever ``steps_per_call`` says"""
-        from . import native
-
         if dones.numel() % self.K != 0 or dones.dtype != torch.uint8 or not dones.is_contiguous():
             raise ValueError(f"observe() takes the contiguous uint8 done bytes of all {self.K} replicas")
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
@@ -250,8 +231,6 @@ class DockReverseCurriculumPopulation(DockReverseCurriculum):
 
     def read(self, k: int = 0) -> _State:
         """tracker k; brings replica k's config copy in step with its stage (the handle's shared config is left as it is)"""
-        from . import native
-
         out = _State()
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
         native.check(self.env.L.kp1_dock_curriculum_read_replica(self.env._handle, self._st, self.K, int(k), C.byref(out), C.c_void_p(stream)))

@@ -27,30 +27,10 @@ class MlpKernels:
         per-net buffer gains a leading replica axis (include/kp1_ppo.h documents the layouts)."""
         self.L = native.load()
         L = self.L
-        vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-        L.kp1_mlp_create_ex.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
-        L.kp1_mlp_create_population.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
-        L.kp1_mlp_replicas.argtypes = [vp]
-        L.kp1_mlp_replicas.restype = i32
-        L.kp1_mlp_destroy.argtypes = [vp]
-        L.kp1_mlp_num_params_ex.argtypes = [i32, i32]
-        L.kp1_mlp_num_params_ex.restype = C.c_int64
-        L.kp1_mlp_pack_weights.argtypes = [vp, vp, vp]
-        L.kp1_mlp_forward.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-        L.kp1_mlp_forward_env_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.kp1_mlp_forward_route_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.kp1_rollout_run.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]
-        L.kp1_mlp_loss_grad.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, f32, f32, vp, f32, f32, f32, f32, vp, vp, i32, vp]
-        L.kp1_mlp_adam_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, i32, i32, vp]
-        L.kp1_mlp_time_kernels.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-        L.kp1_mlp_placement_check.argtypes = [i32, i32, vp, vp]
-        L.kp1_mlp_set_option.argtypes = [vp, i32, i32]
-        L.kp1_mlp_profile_read.argtypes = [vp, vp, vp]
-        L.kp1_mlp_set_replica_hparams.argtypes = [vp, vp, i32, vp]
         self.hidden = hidden
         self.device = device
         self.max_batch = int(max_batch)
-        self._h = vp()
+        self._h = C.c_void_p()
         self.obs_dim = int(obs_dim)                      # 56, or 80 with the route observation keys
         self.obs_pad = 64 if self.obs_dim <= 64 else 128   # row pitch the kernels also accept (zero padded)
         self.fused = True                                # what set_fused last set (hidden 256: the tile kernels; the handle's default is on)
@@ -69,33 +49,33 @@ class MlpKernels:
             self.L.kp1_mlp_destroy(self._h)
             self._h = C.c_void_p()
 
-    OPT_FUSED = 1
+    OPT_FUSED = native.header_int("KP1_MLP_OPT_FUSED")
 
     def set_fused(self, on: bool) -> None:
         """hidden = 256: whole activation chain of a 32-row tile in one workgroup (default) vs the layer-wise kernels."""
         native.check(self.L.kp1_mlp_set_option(self._h, self.OPT_FUSED, int(bool(on))))
         self.fused = bool(on)
 
-    OPT_ACTOR_EXTRA_STEPS = 2
+    OPT_ACTOR_EXTRA_STEPS = native.header_int("KP1_MLP_OPT_ACTOR_EXTRA_STEPS")
 
     def set_actor_extra_steps(self, steps: int) -> None:
         """Adam steps the actor tensors have taken beyond the common count (teacher-anchor side updates, teacher_anchor.py)."""
         native.check(self.L.kp1_mlp_set_option(self._h, self.OPT_ACTOR_EXTRA_STEPS, int(steps)))
 
-    OPT_STEP_COUNT = 3
+    OPT_STEP_COUNT = native.header_int("KP1_MLP_OPT_STEP_COUNT")
 
     def set_step_count(self, steps: int) -> None:
         """Device-resident optimiser step count (restoring a checkpoint's Adam state)."""
         native.check(self.L.kp1_mlp_set_option(self._h, self.OPT_STEP_COUNT, int(steps)))
 
-    OPT_BF16X3_WGRAD = 5
+    OPT_BF16X3_WGRAD = native.header_int("KP1_MLP_OPT_BF16X3_WGRAD")
 
     def set_bf16x3_wgrad(self, on: bool) -> None:
         """EXPERIMENT (default off): weight-gradient GEMMs on operands pre-split into three bf16 pieces, six bf16 MFMAs per product block
         (gemm_tn_bf16x3_kernel).  Not the exact path; bench.py's value never uses it."""
         native.check(self.L.kp1_mlp_set_option(self._h, self.OPT_BF16X3_WGRAD, int(bool(on))))
 
-    OPT_TRAIN_TILE = 6
+    OPT_TRAIN_TILE = native.header_int("KP1_MLP_OPT_TRAIN_TILE")
 
     def set_train_tile(self, on: bool) -> None:
         """hidden 64 / 128 (default off): loss_grad of a minibatch of at most 2048 rows per replica runs forward, loss and backward of a 32-row
@@ -104,7 +84,7 @@ class MlpKernels:
         native.check(self.L.kp1_mlp_set_option(self._h, self.OPT_TRAIN_TILE, int(bool(on))))
         self.train_tile = bool(on)
 
-    OPT_PROFILE = 4
+    OPT_PROFILE = native.header_int("KP1_MLP_OPT_PROFILE")
     PROFILE_SLOTS = ("mlp_train_tile", "gemm_tn_split", "grad_finalize", "adam")
 
     def set_profile(self, on: bool) -> None:

@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in include/kp1.h (librl kp1: rl_brain_trainer_amd/libkp1.so).
+"""ctypes binding of the C ABI in include/kp1.h, kp1_ppo.h and kp1_route.h (rl_brain_trainer_amd/libkp1.so), derived from those headers:
+signatures from their prototypes, constants from their defines ("The C ABI is bound from the headers").
 
 The product path has no CPU fallback: importing this module never touches ``oracle/`` and
 ``load()`` raises if the HIP library has not been built (run ``python -c "import
@@ -7,6 +8,7 @@ __graft_entry__ as g; g.build()"`` or ``make -C rl_brain_trainer_amd``).
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import re
 from pathlib import Path
 
@@ -17,11 +19,91 @@ LIB_PATH = PKG_DIR / "libkp1.so"
 
 KP1_OK = 0
 REAL_F32, REAL_F64 = 0, 1
-EVAL_EPISODES_MAX_STEPS = 256   # include/kp1_ppo.h KP1_EVAL_EPISODES_MAX_STEPS: env steps of one kp1_eval_episodes call
-ROUTE_CHAIN_RUN_MAX_STEPS = 1024  # include/kp1_route.h KP1_ROUTE_CHAIN_RUN_MAX_STEPS: lock steps of one kp1_route_chain_run call
-ROLLOUT_RUN_MAX_STEPS = 2048      # include/kp1_ppo.h KP1_ROLLOUT_RUN_MAX_STEPS: env steps of one kp1_rollout_run call
 DONE_TERMINATED, DONE_TRUNCATED, DONE_SUCCESS, DONE_INVALID = 1, 2, 4, 8
 FLAG_PRE_NEAR_HIT, FLAG_NEAR_HIT, FLAG_SUCCESS = 1, 2, 4
+
+
+class Kp1Error(RuntimeError):
+    pass
+
+
+# ----------------------------------------------------------------------------- the headers are the one text of the C ABI
+HEADERS = ("kp1.h", "kp1_ppo.h", "kp1_route.h")
+_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+# the functions whose int32_t* is a host integer (or host list) passed typed; every other int32_t* is a buffer and travels as void*
+_INT32_HOST = {"kp1_get_stage", "kp1_get_reward_components", "kp1_route_curriculum_create", "kp1_route_curriculum_create_population"}
+_PROTO_RE = re.compile(r"^[ \t]*((?:const\s+)?\w+[\s*]+)(kp1_\w+)\s*\(([^()]*)\)\s*;", re.M)
+
+
+def strip_comments(text: str) -> str:
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+@functools.lru_cache(maxsize=None)
+def header_text() -> str:
+    """The three API headers, comments removed."""
+    parts = []
+    for name in HEADERS:
+        path = kcfg.repo_root() / "include" / name
+        if not path.exists():
+            raise Kp1Error(f"{path} is missing: the binding is derived from the API headers")
+        parts.append(strip_comments(path.read_text()))
+    return "\n".join(parts)
+
+
+def header_int(name: str, text: str | None = None) -> int:
+    """Value of the integer ``#define name`` of the API headers: decimal, hex or ``(1 << n)``."""
+    m = re.search(rf"^[ \t]*#[ \t]*define[ \t]+{re.escape(name)}[ \t]+(.*?)[ \t]*$", header_text() if text is None else strip_comments(text), flags=re.M)
+    if m is None:
+        raise Kp1Error(f"the API headers do not define {name}")
+    shift = re.fullmatch(r"\(\s*1\s*<<\s*(\d+)\s*\)", m.group(1))
+    if shift:
+        return 1 << int(shift.group(1))
+    if not re.fullmatch(r"\d+|0[xX][0-9a-fA-F]+", m.group(1)):
+        raise Kp1Error(f"#define {name} {m.group(1)}: not a decimal, hex or (1 << n) integer")
+    return int(m.group(1), 0)
+
+
+def _ctype(func: str, decl: str, structs: dict, ret: bool = False):
+    words = decl.replace("*", " * ").split()
+    stars = words.count("*")
+    words = [w for w in words if w not in ("const", "struct", "*")]    # what is left: the type, then the parameter's name if it has one
+    base = words[0] if words else ""
+    if "[" not in decl and 1 <= len(words) <= (1 if ret else 2):
+        if stars == 0 and base in _SCALARS:
+            return _SCALARS[base]
+        if stars == 0 and ret and base == "void":
+            return None
+        if stars == 1 and ret and base == "char":
+            return C.c_char_p
+        if stars == 1 and not ret:
+            if base in structs and not words[-1].endswith("_dev"):      # the headers' *_dev parameters are device memory: a handle, never a mirror
+                return C.POINTER(structs[base])
+            return C.POINTER(C.c_int32) if base == "int32_t" and func in _INT32_HOST else C.c_void_p
+        if stars == 2 and not ret:
+            return C.POINTER(C.c_void_p)
+    raise Kp1Error(f"{func}: no ctypes type for {'return type' if ret else 'parameter'} '{' '.join(decl.split())}'")
+
+
+def parse_prototypes(text: str, structs: dict) -> dict[str, tuple]:
+    """{name: (restype, [argtypes])} of every ``kp1_*`` function declaration in ``text`` (C, comments allowed)."""
+    out = {}
+    for ret, name, params in _PROTO_RE.findall(strip_comments(text)):
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (_ctype(name, ret, structs, ret=True), [_ctype(name, p, structs) for p in params])
+    return out
+
+
+def declared_symbols() -> list[str]:
+    """Every function the API headers declare."""
+    return [name for _, name, _ in _PROTO_RE.findall(header_text())]
+
+
+EVAL_EPISODES_MAX_STEPS = header_int("KP1_EVAL_EPISODES_MAX_STEPS")          # env steps of one kp1_eval_episodes call
+ROUTE_CHAIN_RUN_MAX_STEPS = header_int("KP1_ROUTE_CHAIN_RUN_MAX_STEPS")      # lock steps of one kp1_route_chain_run call
+ROLLOUT_RUN_MAX_STEPS = header_int("KP1_ROLLOUT_RUN_MAX_STEPS")              # env steps of one kp1_rollout_run call
+MONITOR_MAX_WINDOW = header_int("KP1_MONITOR_MAX_WINDOW")
+MONITOR_MAX_STEPS = header_int("KP1_MONITOR_MAX_STEPS")
 
 
 class EvalBuffers(C.Structure):
@@ -32,10 +114,6 @@ class EvalBuffers(C.Structure):
 class RouteChainView(C.Structure):
     """include/kp1_route.h kp1_route_chain_view: device pointers of a chain's record table and counters"""
     _fields_ = [("records", C.c_void_p), ("n_records", C.c_void_p), ("n_alive", C.c_void_p), ("n_rows", C.c_int32), ("max_len", C.c_int32)]
-
-
-MONITOR_MAX_WINDOW = 1024    # include/kp1_ppo.h KP1_MONITOR_MAX_WINDOW
-MONITOR_MAX_STEPS = 4096     # include/kp1_ppo.h KP1_MONITOR_MAX_STEPS
 
 
 class MonitorState(C.Structure):
@@ -52,25 +130,19 @@ class KlGate(C.Structure):
                 ("stop_kl", C.c_float), ("reserved0", C.c_int32)]
 
 
-class Kp1Error(RuntimeError):
-    pass
+def struct_registry() -> dict[str, type[C.Structure]]:
+    """C struct name -> ctypes mirror of every struct a function takes by pointer from a host caller that builds the mirror; a parameter
+    of such a type binds as ``POINTER(mirror)``.  (The modules that own the route and curriculum mirrors import this one, hence the late import.)"""
+    from . import finisher_tools, route_config, route_curriculum, route_env
+
+    return {"kp1_config": kcfg.Kp1Config, "kp1_reset_opts": kcfg.ResetOpts, "kp1_info_view": kcfg.InfoView, "kp1_rng_state": kcfg.RngState,
+            "kp1_eval_buffers": EvalBuffers, "kp1_route_chain_view": RouteChainView, "kp1_monitor_state": MonitorState,
+            "kp1_route_config": route_config.RouteConfig, "kp1_route_reset_opts": route_env._RouteResetOpts,
+            "kp1_route_info_view": route_env._RouteInfoView, "kp1_route_curriculum_state": route_curriculum._CurriculumState,
+            "kp1_dock_curriculum_stage": finisher_tools._Stage, "kp1_dock_curriculum_state": finisher_tools._State}
 
 
 _lib: C.CDLL | None = None
-
-
-def declared_symbols() -> list[str]:
-    """Every function include/kp1.h and include/kp1_ppo.h declare (used by the CPU symbol-export test)."""
-    names: list[str] = []
-    for header in sorted((kcfg.repo_root() / "include").glob("*.h")):
-        text = re.sub(r"/\*.*?\*/", "", header.read_text(), flags=re.S)
-        names += re.findall(r"\b(kp1_[a-z0-9_]+)\s*\(", text)
-    seen, out = set(), []
-    for n in names:
-        if n not in seen and not n.endswith("_t"):
-            seen.add(n)
-            out.append(n)
-    return out
 
 
 def load() -> C.CDLL:
@@ -83,83 +155,11 @@ def load() -> C.CDLL:
             "build it with `python -c 'import __graft_entry__ as g; g.build()'`."
         )
     L = C.CDLL(str(LIB_PATH))
-    vp, i32, u64, i64 = C.c_void_p, C.c_int32, C.c_uint64, C.c_int64
-    L.kp1_last_error.restype = C.c_char_p
-    L.kp1_abi_version.restype = C.c_int
-    L.kp1_config_size.restype = u64
-    L.kp1_config_default.argtypes = [C.POINTER(kcfg.Kp1Config)]
-    L.kp1_create.argtypes = [C.POINTER(kcfg.Kp1Config), i32, i32, i32, u64, u64, vp, C.POINTER(vp)]
-    L.kp1_destroy.argtypes = [vp]
-    L.kp1_set_stream.argtypes = [vp, vp]
-    L.kp1_num_envs.argtypes = [vp]
-    L.kp1_set_stage.argtypes = [vp, i32]
-    L.kp1_get_stage.argtypes = [vp, C.POINTER(i32)]
-    L.kp1_set_mode.argtypes = [vp, i32]
-    L.kp1_update_config.argtypes = [vp, C.POINTER(kcfg.Kp1Config)]
-    L.kp1_set_handoff_states.argtypes = [vp, vp, i32]
-    L.kp1_seed.argtypes = [vp, u64, u64]
-    L.kp1_reset.argtypes = [vp, vp, C.POINTER(kcfg.ResetOpts), vp]
-    L.kp1_step.argtypes = [vp, vp, vp, vp, vp, vp, i32]
-    L.kp1_observe.argtypes = [vp, vp]
-    L.kp1_get_info.argtypes = [vp, C.POINTER(kcfg.InfoView)]
-    L.kp1_eval_accumulate.argtypes = [vp, C.POINTER(EvalBuffers), vp, vp, vp, i32, vp, i32, vp]
-    L.kp1_eval_step.argtypes = [vp, vp, vp, vp, vp, C.POINTER(EvalBuffers), i32, vp, i32, vp]
-    L.kp1_eval_episodes.argtypes = [vp, vp, vp, vp, vp, C.POINTER(EvalBuffers), i32, i32, vp, i32, vp]
-    L.kp1_get_reward_components.argtypes = [vp, C.POINTER(vp), C.POINTER(i32)]
-    L.kp1_enable_reward_components.argtypes = [vp, i32]
-    L.kp1_component_name.argtypes = [i32, i32]
-    L.kp1_component_name.restype = C.c_char_p
-    L.kp1_num_components.argtypes = [i32]
-    L.kp1_get_state.argtypes = [vp] + [vp] * 5
-    L.kp1_set_state.argtypes = [vp] + [vp] * 5 + [i32]
-    L.kp1_rng_get.argtypes = [vp, vp]
-    L.kp1_rng_set.argtypes = [vp, vp]
-    L.kp1_state_snapshot.argtypes = [vp]
-    L.kp1_state_restore.argtypes = [vp]
-    L.kp1_fk_pose6.argtypes = [i32, i32, vp, vp, i64, vp]
-    L.kp1_pose_error.argtypes = [i32, i32, vp, vp, vp, vp, vp, i64, vp]
-    L.kp1_joint_utils.argtypes = [i32, i32, C.POINTER(kcfg.Kp1Config), vp, vp, vp, vp, vp, vp, i64, vp]
-    L.kp1_rng_seed_state.argtypes = [u64, C.POINTER(kcfg.RngState)]
-    f32 = C.c_float
-    L.kp1_gae_scan.argtypes = [i32, vp, vp, vp, vp, f32, f32, vp, vp, i32, i32, vp]
-    L.kp1_gae_scan_replicas.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp]
-    L.kp1_bootstrap_truncated.argtypes = [i32, vp, vp, vp, f32, i64, vp]
-    L.kp1_adv_minibatch_sums.argtypes = [i32, vp, vp, i64, i64, vp, vp]
-    L.kp1_adv_minibatch_stats.argtypes = [i32, vp, i64, vp, vp]
-    L.kp1_random_permutation.argtypes = [i32, i64, vp, vp, vp]
-    L.kp1_curriculum_create.argtypes = [i32, C.c_double, i32, i32, i32, i32, C.POINTER(vp)]
-    L.kp1_curriculum_destroy.argtypes = [i32, vp]
-    L.kp1_curriculum_observe.argtypes = [i32, vp, vp, i32, i32, vp]
-    L.kp1_curriculum_observe_chunk.argtypes = [i32, vp, vp, i32, i32, i32, vp]
-    L.kp1_curriculum_read.argtypes = [i32, vp, vp, vp]
-    L.kp1_bind_stage_ptr.argtypes = [vp, vp]
-    L.kp1_curriculum_create_population.argtypes = [i32, i32, C.c_double, i32, i32, i32, vp, C.POINTER(vp)]
-    L.kp1_curriculum_observe_population.argtypes = [i32, vp, vp, i32, i32, i32, vp]
-    L.kp1_curriculum_read_replica.argtypes = [i32, vp, i32, i32, vp, vp]
-    L.kp1_bind_population_stages.argtypes = [vp, vp, i32]
-    L.kp1_seed_blocks.argtypes = [vp, vp, i32, i32]
-    L.kp1_set_obs_stride.argtypes = [vp, i32]
-    L.kp1_route_chain_create.argtypes = [vp, vp, vp, i32, i32, C.POINTER(vp)]
-    L.kp1_route_chain_destroy.argtypes = [vp, vp]
-    L.kp1_route_chain_begin.argtypes = [vp, vp, vp]
-    L.kp1_route_chain_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.kp1_route_chain_get_view.argtypes = [vp, C.POINTER(RouteChainView)]
-    L.kp1_mlp_forward_route_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.kp1_mlp_forward_route_chain_step.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
-    L.kp1_route_chain_run.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp]
-    L.kp1_rollout_run.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]
-    L.kp1_mlp_anchor_loss_grad.argtypes = [vp, vp, i32, vp, i32, vp, f32, vp, vp, vp]
-    L.kp1_mlp_anchor_adam_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, i32, vp]
-    L.kp1_mlp_set_kl_gate.argtypes = [vp, vp, i32, vp]
-    L.kp1_mlp_kl_gate_arm.argtypes = [vp, vp]
-    L.kp1_mlp_kl_gate_read.argtypes = [vp, vp, vp, vp]
-    L.kp1_mlp_hparams_store.argtypes = [vp, vp, i32, vp]
-    L.kp1_monitor_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
-    L.kp1_monitor_destroy.argtypes = [vp]
-    L.kp1_monitor_observe.argtypes = [vp, vp, vp, i32, vp]
-    L.kp1_monitor_reset_carry.argtypes = [vp, vp]
-    L.kp1_monitor_read.argtypes = [vp, i32, C.POINTER(MonitorState), vp]
-    L.kp1_explained_variance.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp]
+    for name, (restype, argtypes) in parse_prototypes(header_text(), struct_registry()).items():
+        if not hasattr(L, name):
+            raise Kp1Error(f"{LIB_PATH} does not export {name}, which the API headers declare")
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.kp1_config_size() != C.sizeof(kcfg.Kp1Config):
         raise Kp1Error(f"kp1_config layout mismatch: library {L.kp1_config_size()} vs binding {C.sizeof(kcfg.Kp1Config)}")
     _lib = L

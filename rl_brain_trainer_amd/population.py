@@ -37,7 +37,7 @@ from .route_curriculum import RoutePrefixCurriculumPopulation
 from .route_env import RoutePopulationVecEnv
 from .vec_env import ArmKinematicPopulationVecEnv
 
-MAX_REPLICAS = 16     # KP1_MLP_MAX_REPLICAS
+MAX_REPLICAS = native.header_int("KP1_MLP_MAX_REPLICAS")
 
 # Per-replica PPO hyper-parameters a population can sweep (``overrides``): the six the MLP kernels read from the handle's table
 # (kp1_mlp_set_replica_hparams), the two of the per-replica GAE scan / bootstrap, and target_kl, which reaches the handle as the [K] target

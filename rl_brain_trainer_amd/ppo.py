@@ -592,7 +592,7 @@ def train_tile_chunks(n: int) -> int:
 # kp1_mlp_forward_route_step: the widths, the observation widths and the route length it covers
 FUSED_ROUTE_ROLLOUT_WIDTHS = (64, 128)
 FUSED_ROUTE_ROLLOUT_OBS_DIMS = (56, 80)
-ROUTE_FUSED_MAX_WAYPOINTS = 914        # include/kp1_route.h KP1_ROUTE_FUSED_MAX_WAYPOINTS
+ROUTE_FUSED_MAX_WAYPOINTS = native.header_int("KP1_ROUTE_FUSED_MAX_WAYPOINTS")
 FUSED_ROUTE_ROLLOUT_ENV = "KP1_FUSED_ROUTE_ROLLOUT"
 
 

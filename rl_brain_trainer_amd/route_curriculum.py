@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import config as kcfg
+from . import native
 from . import route_config as rcfg
 from .route_env import RoutePopulationVecEnv, RouteVecEnv
 
@@ -35,7 +36,7 @@ def build_prefix_stages(prefixes: Sequence[int]) -> list[RouteCurriculumStage]:
 
 
 # --------------------------------------------------------------------------------------------- the same callback on the device
-MAX_STAGES, MAX_WINDOW, MAX_HISTORY = 16, 1024, 32
+MAX_STAGES, MAX_WINDOW, MAX_HISTORY = (native.header_int("KP1_ROUTE_CURRICULUM_MAX_" + n) for n in ("STAGES", "WINDOW", "HISTORY"))
 
 
 class _CurriculumEvent(C.Structure):
@@ -98,25 +99,14 @@ class RoutePrefixCurriculumDevice:
 
     def attach(self, env: RouteVecEnv) -> None:
         """_on_training_start: allocate the tracker next to the env and apply the first prefix."""
-        from . import native
-
         self.env = env
         L = env.L
-        vp, i32, f64 = C.c_void_p, C.c_int32, C.c_double
-        L.kp1_route_curriculum_create.argtypes = [vp, C.POINTER(i32), i32, f64, f64, f64, f64, i32, i32, C.POINTER(vp)]
-        L.kp1_route_curriculum_destroy.argtypes = [vp, vp]
-        L.kp1_route_curriculum_observe.argtypes = [vp, vp, vp, i32, vp]
-        L.kp1_route_episode_records.argtypes = [vp, vp, vp, vp]
-        L.kp1_route_curriculum_observe_chunk.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-        L.kp1_route_curriculum_read.argtypes = [vp, vp, C.POINTER(_CurriculumState), vp]
-        prefixes = (i32 * len(self.stages))(*[int(s.prefix_end_index) for s in self.stages])
+        prefixes = (C.c_int32 * len(self.stages))(*[int(s.prefix_end_index) for s in self.stages])
         with torch.cuda.device(env.device):
             native.check(L.kp1_route_curriculum_create(env._handle, prefixes, len(self.stages), *self._args, C.byref(self._st)))
         env.route_cfg.reset.min_route_index, env.route_cfg.reset.max_route_index = 1, int(self.stages[0].prefix_end_index)
 
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
-        from . import native
-
         if dones.numel() != self.env.n_envs:
             raise ValueError("observe() tracks one process's envs from the env's own flags; data parallel goes through record() + observe_chunk()")
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
@@ -125,8 +115,6 @@ class RoutePrefixCurriculumDevice:
     def record(self, dones: torch.Tensor, out: torch.Tensor) -> None:
         """out[N] <- this step's episode records: the KP1_DONE_* bits of ``dones`` | route_ready << 4 | orientation hit << 5 | regression << 6,
         the flags read from the env's planes on the device (call after the step, before the next one rewrites them)"""
-        from . import native
-
         n = self.env.n_envs
         if dones.numel() != n or out.numel() != n or out.dtype != torch.uint8 or not (dones.is_contiguous() and out.is_contiguous()):
             raise ValueError(f"record() takes the {n} done bytes of one step and a contiguous uint8 [{n}] output")
@@ -136,8 +124,6 @@ class RoutePrefixCurriculumDevice:
     def observe_chunk(self, records_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
         """data-parallel rollouts: the all-gathered [world, chunk_steps, n_local] episode records of a chunk of env steps, replayed in the
         reference's order (step by step, global env id order inside a step); a promotion moves this rank's reset window"""
-        from . import native
-
         if not (records_all.numel() == world * chunk_steps * n_local and records_all.dtype == torch.uint8 and records_all.is_contiguous()):
             raise ValueError(f"observe_chunk() takes contiguous uint8 records of shape [{world}, {chunk_steps}, {n_local}]")
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
@@ -145,8 +131,6 @@ class RoutePrefixCurriculumDevice:
                                                                    int(chunk_steps), int(world), C.c_void_p(stream)))
 
     def read(self) -> _CurriculumState:
-        from . import native
-
         out = _CurriculumState()
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
         native.check(self.env.L.kp1_route_curriculum_read(self.env._handle, self._st, C.byref(out), C.c_void_p(stream)))
@@ -191,18 +175,11 @@ class RoutePrefixCurriculumPopulation(RoutePrefixCurriculumDevice):
 
     def attach(self, env: RoutePopulationVecEnv) -> None:
         """_on_training_start of every replica: K trackers next to the population env, every window set to the first prefix"""
-        from . import native
-
         if not isinstance(env, RoutePopulationVecEnv):
             raise TypeError("RoutePrefixCurriculumPopulation tracks the replicas of a RoutePopulationVecEnv")
         self.env = env
         L = env.L
-        vp, i32, f64 = C.c_void_p, C.c_int32, C.c_double
-        L.kp1_route_curriculum_create_population.argtypes = [vp, C.POINTER(i32), i32, f64, f64, f64, f64, i32, i32, C.POINTER(vp)]
-        L.kp1_route_curriculum_destroy.argtypes = [vp, vp]
-        L.kp1_route_curriculum_observe_population.argtypes = [vp, vp, vp, i32, vp]
-        L.kp1_route_curriculum_read_replica.argtypes = [vp, vp, i32, C.POINTER(_CurriculumState), vp]
-        prefixes = (i32 * len(self.stages))(*[int(s.prefix_end_index) for s in self.stages])
+        prefixes = (C.c_int32 * len(self.stages))(*[int(s.prefix_end_index) for s in self.stages])
         with torch.cuda.device(env.device):
             native.check(L.kp1_route_curriculum_create_population(env._handle, prefixes, len(self.stages), *self._args, C.byref(self._st)))
         env.route_cfg.reset.min_route_index, env.route_cfg.reset.max_route_index = 1, int(self.stages[0].prefix_end_index)
@@ -214,8 +191,6 @@ class RoutePrefixCurriculumPopulation(RoutePrefixCurriculumDevice):
 
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
         """dones: the K N done bytes of one population step; steps_per_call: env steps per replica this call stands for (N)"""
-        from . import native
-
         if dones.numel() != self.env.n_envs or dones.dtype != torch.uint8 or not dones.is_contiguous():
             raise ValueError(f"observe() takes the contiguous uint8 done bytes of all {self.env.n_envs} envs of the population")
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
@@ -229,8 +204,6 @@ class RoutePrefixCurriculumPopulation(RoutePrefixCurriculumDevice):
         raise TypeError("the population tracker has no data-parallel form")
 
     def read(self, k: int = 0) -> _CurriculumState:
-        from . import native
-
         out = _CurriculumState()
         stream = torch.cuda.current_stream(self.env.device).cuda_stream
         native.check(self.env.L.kp1_route_curriculum_read_replica(self.env._handle, self._st, int(k), C.byref(out), C.c_void_p(stream)))
@@ -431,8 +404,8 @@ CHAIN_FORMS = ("launch_sequence", "one_launch_step", "whole_chain")
 # files, bit for bit.
 CHAIN_FORM_DEFAULT = "one_launch_step"
 CHAIN_FUSED_WIDTHS = (64, 128)
-CHAIN_FUSED_MAX_WAYPOINTS = 914      # include/kp1_route.h KP1_ROUTE_FUSED_MAX_WAYPOINTS
-CHAIN_RUN_MAX_STEPS = 1024           # include/kp1_route.h KP1_ROUTE_CHAIN_RUN_MAX_STEPS
+CHAIN_FUSED_MAX_WAYPOINTS = native.header_int("KP1_ROUTE_FUSED_MAX_WAYPOINTS")
+CHAIN_RUN_MAX_STEPS = native.ROUTE_CHAIN_RUN_MAX_STEPS
 
 
 def chain_fused_covered(dtype: Any, hidden: int, obs_dim: int, pitch: int, components_on: bool, n_waypoints: int) -> bool:
@@ -543,8 +516,6 @@ def evaluate_sequential_route_batch(*, mlp, cfg: dict[str, Any], route_q: np.nda
     span = int(steps_per_launch)
     if form == "whole_chain" and not 1 <= span <= CHAIN_RUN_MAX_STEPS:
         raise ValueError(f"steps_per_launch must be in [1, {CHAIN_RUN_MAX_STEPS}], got {span}")
-    from . import native
-
     base = kcfg.to_env_config(cfg)
     env = RouteVecEnv(base, rc, route_q, R, device=device, seed=0, real="f32")
     chain = None

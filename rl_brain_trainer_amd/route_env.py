@@ -40,34 +40,6 @@ CHAIN_RECORD = np.dtype([(n, "<i4") for n in ("route_index", "success", "route_r
 assert CHAIN_RECORD.itemsize == 312
 
 
-def _bind(L) -> None:
-    if getattr(L, "_kp1_route_bound", False):
-        return
-    vp, i32, u64 = C.c_void_p, C.c_int32, C.c_uint64
-    L.kp1_route_create.argtypes = [vp, C.POINTER(rcfg.RouteConfig), vp, i32, u64, u64, C.POINTER(vp)]
-    L.kp1_route_destroy.argtypes = [vp]
-    L.kp1_route_get_dataset.argtypes = [vp, vp, vp, vp, vp]
-    L.kp1_route_set_window.argtypes = [vp, i32, i32]
-    L.kp1_route_seed.argtypes = [vp, u64, u64]
-    L.kp1_route_obs_dim.argtypes = [vp]
-    L.kp1_route_set_obs_stride.argtypes = [vp, C.c_int32]
-    L.kp1_route_reset.argtypes = [vp, vp, C.POINTER(_RouteResetOpts), vp]
-    L.kp1_route_step.argtypes = [vp, vp, vp, vp, vp, vp, i32]
-    L.kp1_route_get_info.argtypes = [vp, C.POINTER(_RouteInfoView)]
-    L.kp1_route_enable_reward_components.argtypes = [vp, i32]
-    L.kp1_route_get_reward_components.argtypes = [vp, C.POINTER(vp)]
-    L.kp1_route_component_name.argtypes = [i32]
-    L.kp1_route_component_name.restype = C.c_char_p
-    L.kp1_route_rng_get.argtypes = [vp, vp]
-    L.kp1_route_rng_set.argtypes = [vp, vp]
-    L.kp1_route_config_default.argtypes = [C.POINTER(rcfg.RouteConfig)]
-    L.kp1_seed_blocks.argtypes = [vp, vp, i32, i32]
-    L.kp1_route_create_population.argtypes = [vp, C.POINTER(rcfg.RouteConfig), vp, i32, vp, i32, C.POINTER(vp)]
-    L.kp1_route_num_replicas.argtypes = [vp]
-    L.kp1_route_set_replica_window.argtypes = [vp, i32, i32, i32]
-    L._kp1_route_bound = True
-
-
 class RouteVecEnv:
     """``route_q``: [W, 7] joint goals of the dense route (route_config.load_route_q); ``base_config``: the env block of the route
     YAML (approach mode); ``route_cfg``: route_config.route_config_from_dict(cfg, max_route_index=first prefix)."""
@@ -76,7 +48,6 @@ class RouteVecEnv:
                  seed: int = 0, first_env_id: int = 0, real: str = "f32", reward_components: bool = False) -> None:
         self.base = ArmKinematicVecEnv(base_config, n_envs, device=device, seed=seed, first_env_id=first_env_id, real=real)
         self.L = self.base.L
-        _bind(self.L)
         self.config = base_config
         self.route_cfg = route_cfg
         self.n_envs = int(n_envs)
@@ -246,7 +217,7 @@ class RouteVecEnv:
 
     def rng_state(self) -> np.ndarray:
         arr = (kcfg.RngState * self.n_envs)()
-        native.check(self.L.kp1_route_rng_get(self._handle, C.cast(arr, C.c_void_p)))
+        native.check(self.L.kp1_route_rng_get(self._handle, arr))
         return np.array([[s.state_hi, s.state_lo, s.inc_hi, s.inc_lo, s.has_uint32, s.uinteger] for s in arr], dtype=np.uint64)
 
     def set_rng_state(self, words: np.ndarray) -> None:
@@ -255,7 +226,7 @@ class RouteVecEnv:
         for i in range(self.n_envs):
             (arr[i].state_hi, arr[i].state_lo, arr[i].inc_hi, arr[i].inc_lo) = (int(w) for w in words[i][:4])
             arr[i].has_uint32, arr[i].uinteger = int(words[i][4]), int(words[i][5])
-        native.check(self.L.kp1_route_rng_set(self._handle, C.cast(arr, C.c_void_p)))
+        native.check(self.L.kp1_route_rng_set(self._handle, arr))
 
     def get_state(self) -> dict[str, np.ndarray]:
         return self.base.get_state()

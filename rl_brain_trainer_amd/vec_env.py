@@ -285,7 +285,7 @@ class ArmKinematicVecEnv:
     def rng_state(self) -> np.ndarray:
         """[N,6] uint64 words (state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger) of each env's PCG64 stream."""
         arr = (kcfg.RngState * self.n_envs)()
-        native.check(self.L.kp1_rng_get(self._handle, C.cast(arr, C.c_void_p)))
+        native.check(self.L.kp1_rng_get(self._handle, arr))
         return np.array([[s.state_hi, s.state_lo, s.inc_hi, s.inc_lo, s.has_uint32, s.uinteger] for s in arr], dtype=np.uint64)
 
     def set_rng_state(self, words: np.ndarray) -> None:
@@ -293,11 +293,11 @@ class ArmKinematicVecEnv:
         for i in range(self.n_envs):
             (arr[i].state_hi, arr[i].state_lo, arr[i].inc_hi, arr[i].inc_lo) = (int(w) for w in words[i][:4])
             arr[i].has_uint32, arr[i].uinteger = int(words[i][4]), int(words[i][5])
-        native.check(self.L.kp1_rng_set(self._handle, C.cast(arr, C.c_void_p)))
+        native.check(self.L.kp1_rng_set(self._handle, arr))
 
 
 
-MAX_REPLICAS = 16     # KP1_CURRICULUM_MAX_REPLICAS / KP1_MLP_MAX_REPLICAS
+MAX_REPLICAS = native.header_int("KP1_CURRICULUM_MAX_REPLICAS")     # = KP1_MLP_MAX_REPLICAS
 
 
 class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):

@@ -10,7 +10,7 @@ import types
 
 import pytest
 
-from rl_brain_trainer_amd import config as kcfg
+import abi
 from rl_brain_trainer_amd import evaluate as ev
 from rl_brain_trainer_amd import native, train, train_dock
 from rl_brain_trainer_amd import workspace_coverage as wc
@@ -23,8 +23,8 @@ def test_symbol_is_exported_declared_and_bound_as_the_header_says():
     L = native.load()
     assert hasattr(C.CDLL(str(native.LIB_PATH)), "kp1_eval_episodes")
     assert "kp1_eval_episodes" in native.declared_symbols()
-    header = re.sub(r"/\*.*?\*/", "", (kcfg.repo_root() / "include" / "kp1_ppo.h").read_text(), flags=re.S)
-    params = [p.strip() for p in re.search(r"\bint\s+kp1_eval_episodes\s*\(([^)]*)\)", header).group(1).split(",")]
+    header = abi.header("kp1_ppo.h")
+    params = abi.params("kp1_eval_episodes", "kp1_ppo.h")
     assert len(params) == len(L.kp1_eval_episodes.argtypes) == 11
     for text, ctype in zip(params, L.kp1_eval_episodes.argtypes):
         decl = text.rsplit(None, 1)[0]                     # drop the parameter name

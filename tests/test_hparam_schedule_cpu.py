@@ -19,6 +19,7 @@ import pytest
 import torch
 import yaml
 
+import abi
 from rl_brain_trainer_amd import checkpoint
 from rl_brain_trainer_amd import config as kcfg
 from rl_brain_trainer_amd import mlp as kmlp
@@ -30,13 +31,11 @@ from rl_brain_trainer_amd import sb3_pickle as sbp
 
 
 def _header() -> str:
-    return re.sub(r"/\*.*?\*/", "", (kcfg.repo_root() / "include" / "kp1_ppo.h").read_text(), flags=re.S)
+    return abi.header("kp1_ppo.h")
 
 
 def test_symbol_declared_exported_and_bound():
-    m = re.search(r"\bint\s+kp1_mlp_hparams_store\s*\(([^)]*)\)\s*;", _header())
-    assert m, "kp1_mlp_hparams_store is not declared in include/kp1_ppo.h"
-    args = [a.strip() for a in m.group(1).split(",")]
+    args = abi.params("kp1_mlp_hparams_store", "kp1_ppo.h")      # raises if include/kp1_ppo.h does not declare it
     assert args == ["kp1_mlp* m", "const kp1_replica_hparams* host", "int32_t n", "void* stream"]
     assert "kp1_mlp_hparams_store" in native.declared_symbols()
     L = native.load()

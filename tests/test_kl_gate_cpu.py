@@ -11,7 +11,7 @@ import types
 import pytest
 import torch
 
-from rl_brain_trainer_amd import config as kcfg
+import abi
 from rl_brain_trainer_amd import mlp as kmlp
 from rl_brain_trainer_amd import monitor as kmon
 from rl_brain_trainer_amd import native
@@ -23,15 +23,12 @@ CTYPES = {"double": C.c_double, "int32_t": C.c_int32, "float": C.c_float}
 
 
 def _header() -> str:
-    return re.sub(r"/\*.*?\*/", "", (kcfg.repo_root() / "include" / "kp1_ppo.h").read_text(), flags=re.S)
+    return abi.header("kp1_ppo.h")
 
 
 def test_symbols_declared_exported_and_bound():
-    text = _header()
     for name, n_args in SYMBOLS.items():
-        m = re.search(rf"\bint\s+{name}\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/kp1_ppo.h"
-        assert len([a for a in m.group(1).split(",") if a.strip()]) == n_args, name
+        assert len(abi.params(name, "kp1_ppo.h")) == n_args, name        # raises if include/kp1_ppo.h does not declare it
         assert name in native.declared_symbols()
     L = native.load()
     for name, n_args in SYMBOLS.items():

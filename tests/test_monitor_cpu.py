@@ -13,13 +13,14 @@ import numpy as np
 import pytest
 import torch
 
+import abi
 from rl_brain_trainer_amd import monitor as kmon
 from rl_brain_trainer_amd import native
 from rl_brain_trainer_amd import ppo as kppo
 
 SYMBOLS = {"kp1_monitor_create": 6, "kp1_monitor_destroy": 1, "kp1_monitor_observe": 5, "kp1_monitor_reset_carry": 2, "kp1_monitor_read": 4,
            "kp1_explained_variance": 8}
-HEADER = re.sub(r"/\*.*?\*/", "", (native.PKG_DIR.parent / "include" / "kp1_ppo.h").read_text(), flags=re.S)
+HEADER = abi.header("kp1_ppo.h")
 
 
 def same_value(a, b) -> bool:
@@ -37,7 +38,7 @@ def test_symbols_exported_declared_and_bound():
     for name, n_args in SYMBOLS.items():
         assert hasattr(lib, name), name
         assert name in native.declared_symbols(), name
-        params = re.search(rf"\bint\s+{name}\s*\(([^)]*)\)", HEADER).group(1).split(",")
+        params = abi.params(name, "kp1_ppo.h")
         assert len(getattr(L, name).argtypes) == len(params) == n_args, name
         for text, ctype in zip(params, getattr(L, name).argtypes):
             if "kp1_monitor_state" in text:

@@ -4,11 +4,11 @@ the host; the populations' refusals."""
 from __future__ import annotations
 
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
 
+import abi
 from rl_brain_trainer_amd import native
 from rl_brain_trainer_amd import route_config as rcfg
 from rl_brain_trainer_amd.ppo import PPOConfig
@@ -19,12 +19,11 @@ ANCHOR_SYMBOLS = {"kp1_mlp_anchor_loss_grad": 10, "kp1_mlp_anchor_adam_step": 10
 
 def test_anchor_symbols_exported_declared_and_bound():
     lib = C.CDLL(str(native.LIB_PATH))
-    header = re.sub(r"/\*.*?\*/", "", (native.PKG_DIR.parent / "include" / "kp1_ppo.h").read_text(), flags=re.S)
     L = native.load()
     for name, n_args in ANCHOR_SYMBOLS.items():
         assert hasattr(lib, name), name
         assert name in native.declared_symbols(), name
-        params = re.search(rf"\bint\s+{name}\s*\(([^)]*)\)", header).group(1).split(",")
+        params = abi.params(name, "kp1_ppo.h")
         assert len(getattr(L, name).argtypes) == len(params) == n_args, name
         for text, ctype in zip(params, getattr(L, name).argtypes):
             if "*" in text:

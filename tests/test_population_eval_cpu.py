@@ -5,12 +5,12 @@ from __future__ import annotations
 
 import ctypes as C
 import json
-import re
 import types
 
 import numpy as np
 import pytest
 
+import abi
 from conftest import GOLDEN, load_golden_config
 from rl_brain_trainer_amd import evaluate as ev
 from rl_brain_trainer_amd import native
@@ -20,8 +20,7 @@ def test_eval_step_symbol_exported_declared_and_bound():
     lib = C.CDLL(str(native.LIB_PATH))
     assert hasattr(lib, "kp1_eval_step")
     assert "kp1_eval_step" in native.declared_symbols()
-    header = re.sub(r"/\*.*?\*/", "", (native.PKG_DIR.parent / "include" / "kp1_ppo.h").read_text(), flags=re.S)
-    params = re.search(r"\bint\s+kp1_eval_step\s*\(([^)]*)\)", header).group(1).split(",")
+    params = abi.params("kp1_eval_step", "kp1_ppo.h")
     L = native.load()
     assert len(L.kp1_eval_step.argtypes) == len(params) == 10
     for text, ctype in zip(params, L.kp1_eval_step.argtypes):

@@ -11,6 +11,7 @@ import types
 import numpy as np
 import pytest
 
+import abi
 from rl_brain_trainer_amd import collect_route_teacher as rec
 from rl_brain_trainer_amd import native
 from rl_brain_trainer_amd import route_config as rcfg
@@ -23,12 +24,11 @@ CHAIN_SYMBOLS = {"kp1_route_chain_create": 6, "kp1_route_chain_destroy": 2, "kp1
 
 def test_chain_symbols_exported_declared_and_bound():
     lib = C.CDLL(str(native.LIB_PATH))
-    header = re.sub(r"/\*.*?\*/", "", (native.PKG_DIR.parent / "include" / "kp1_route.h").read_text(), flags=re.S)
     L = native.load()
     for name, n_args in CHAIN_SYMBOLS.items():
         assert hasattr(lib, name), name
         assert name in native.declared_symbols(), name
-        params = re.search(rf"\bint\s+{name}\s*\(([^)]*)\)", header).group(1).split(",")
+        params = abi.params(name, "kp1_route.h")
         assert len(getattr(L, name).argtypes) == len(params) == n_args, name
         for text, ctype in zip(params, getattr(L, name).argtypes):
             if "kp1_route_chain_view" in text:
