@@ -517,7 +517,8 @@ int kp1_num_components(int32_t mode);
 
 /* direct state access for handoff / route re-target (callers poke _q, _dq, _prev_action, _goal_q,
  * _goal_pose6 then _capture_entry_metrics(); eval_three_stage.py:122, route_sequence_env.py:255-257).
- * Host f64 arrays [N][7] / [N][6]; NULL pointers are skipped.  set recomputes ee_pose6 = FK(q). */
+ * Host f64 arrays [N][7] / [N][6]; NULL pointers are skipped.  set recomputes ee_pose6 = FK(q), and the info view's position /
+ * orientation error norms whenever q or goal_pose6 is given (with or without capture_entry_metrics); it keeps the episode counters. */
 int kp1_get_state(kp1_env* env, double* q, double* dq, double* prev_action, double* goal_q, double* goal_pose6);
 int kp1_set_state(kp1_env* env, const double* q, const double* dq, const double* prev_action,
                   const double* goal_q, const double* goal_pose6, int32_t capture_entry_metrics);

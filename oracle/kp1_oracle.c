@@ -702,6 +702,9 @@ void kp1o_env_reset(kp1o_env* e, const kp1o_reset_opts* opts, float obs[KP1_OBS_
   e->policy_mode = o->policy_mode >= 0 ? o->policy_mode : cfg->env.mode;
   if (o->initial_q) {
     kp1o_clip_q(&cfg->joints, o->initial_q, e->q);
+    /* no stage is sampled: the episode's stage is the env's own, which is what the reference reports for it
+       (info["curriculum_stage_index"], arm_kinematic_env.py:416) and what the handle writes (reset_env, I_STAGE) */
+    e->last_reset_stage = e->curriculum_stage_index;
   } else {
     if (e->policy_mode == KP1_MODE_DOCK) sample_dock_reset(e, e->curriculum_stage_index, &rs);
     else sample_approach_reset(e, e->curriculum_stage_index, &rs);

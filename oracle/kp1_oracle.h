@@ -45,7 +45,7 @@ typedef struct kp1o_env {
   double goal_q[7], goal_pose6[6], ee_pose6[6];
   int curriculum_stage_index;
   int policy_mode;
-  int last_reset_stage; /* stage index the last sampling reset drew from (diagnostic) */
+  int last_reset_stage; /* stage of the running episode: the one a sampling reset drew from, the env's own after a reset with initial_q */
 } kp1o_env;
 
 typedef struct kp1o_reset_opts {

@@ -177,21 +177,25 @@ __global__ void kp1_set_state_kernel(const EnvState<R> st, const DevCfg<R>* cfg,
   if (pa) for (int k = 0; k < NJ; ++k) st.r(F_PREV_ACTION + k, i) = (R)pa[i * NJ + k];
   if (goal_q) for (int k = 0; k < NJ; ++k) st.r(F_GOAL_Q + k, i) = (R)goal_q[i * NJ + k];
   if (goal_pose) for (int k = 0; k < 6; ++k) st.r(F_GOAL_POSE + k, i) = (R)goal_pose[i * 6 + k];
-  if (capture_entry) {
+  // the error norms of the info view follow a moved pose whether or not the entry metrics are captured (_base_info computes them from the
+  // current poses, arm_kinematic_env.py:385-387; kp1_eval_accumulate's step 0 reads them)
+  if (capture_entry || q || goal_pose) {
     R ee[6], goal[6], pe[3], oe[3], pn, on, v[NJ];
     for (int k = 0; k < 6; ++k) {
       ee[k] = st.r(F_EE_POSE + k, i);
       goal[k] = st.r(F_GOAL_POSE + k, i);
     }
     pose_error_norms<R>(ee, goal, pe, oe, &pn, &on);
-    st.r(F_ENTRY + 0, i) = pn;
-    st.r(F_ENTRY + 1, i) = on;
-    for (int k = 0; k < NJ; ++k) v[k] = st.r(F_PREV_ACTION + k, i);
-    st.r(F_ENTRY + 2, i) = norm7<R>(v);
-    for (int k = 0; k < NJ; ++k) v[k] = st.r(F_DQ + k, i);
-    st.r(F_ENTRY + 3, i) = norm7<R>(v);
     st.r(F_POS_ERR, i) = pn;
     st.r(F_ORI_ERR, i) = on;
+    if (capture_entry) {
+      st.r(F_ENTRY + 0, i) = pn;
+      st.r(F_ENTRY + 1, i) = on;
+      for (int k = 0; k < NJ; ++k) v[k] = st.r(F_PREV_ACTION + k, i);
+      st.r(F_ENTRY + 2, i) = norm7<R>(v);
+      for (int k = 0; k < NJ; ++k) v[k] = st.r(F_DQ + k, i);
+      st.r(F_ENTRY + 3, i) = norm7<R>(v);
+    }
   }
 }
 

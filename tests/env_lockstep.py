@@ -438,7 +438,7 @@ def reference_pass(cfgd: dict, stage: int, actions: np.ndarray | None = None, n:
     R.cfg, R.cfgd, R.stage, R.mode, R.T, R.n, R.seed, R.cls = cfg, cfgd, stage, mode, T, n, seed, cls
     R.limit_ids, R.limit_q, R.limit_goal_q = ids, q_init, q_goal
     q0, stage0 = ora.fields("q", "last_reset_stage")
-    # a reset with an explicit initial_q samples no stage: the device reports the curriculum stage for it, the oracle keeps its old diagnostic
+    # a reset with an explicit initial_q samples no stage: device and oracle report the curriculum stage for it (tests/test_env_control_gpu.py)
     explicit_stage = min(max(int(stage), 0), int(cfg.c.n_stages) - 1)
     stage0[ids] = explicit_stage
     R.reset0 = {"obs": ora.obs.copy(), "rng": ora.rng_words(), "q": q0, "stage": stage0}
