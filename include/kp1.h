@@ -457,6 +457,16 @@ int kp1_set_mode(kp1_env* env, int32_t mode);
 int kp1_update_config(kp1_env* env, const kp1_config* cfg);
 /* DockResetConfig._handoff_states (already filtered by the caller); reset_samplers.py:131-165 */
 int kp1_set_handoff_states(kp1_env* env, const kp1_handoff_state* states_host, int32_t n_states);
+/* env.route_reset (RouteResetConfig + sample_route_approach_reset; reset_samplers.py:86-102, 393-423): Approach resets take start and goal
+   from the dense joint-space route route_q_host[n_points][7], `stride` waypoints apart, the stride range being the env's stage's
+   (min/max_stride_by_stage, each clamped to its own length).  Ahead of random-start pairs and the stage mixer; dock resets ignore it.
+   n_points == 0 or a NULL route switches it off.  KP1_ERR_INVALID: one point, a stride list outside 1..KP1_MAX_STAGES entries, a negative
+   noise, or a stage whose lower stride exceeds n_points - 1 (the reference's ValueError at its first reset).  The table is copied to the
+   device on the handle's stream; the live sampler block is rewritten in place, so a captured graph replayed after a second call samples from
+   the new table.  Replaced tables are freed by kp1_destroy; kp1_update_config leaves the route in place. */
+int kp1_set_route_stride_reset(kp1_env* env, const double* route_q_host, int32_t n_points, const int32_t* min_stride_by_stage, int32_t n_min,
+                               const int32_t* max_stride_by_stage, int32_t n_max, const double* start_q_noise, const double* goal_q_noise,
+                               double reverse_probability);
 /* re-seed env streams: env i <- default_rng(seed0 + first_env_id + i); reset(seed=...) :103-104 */
 int kp1_seed(kp1_env* env, uint64_t seed0, uint64_t first_env_id);
 /* block-structured seeding: env i of block k = i / n_per_block gets default_rng(seeds[k] + i % n_per_block); blocks * n_per_block = N */

@@ -281,15 +281,93 @@ def _vec7(values: Any, what: str) -> list[float]:
     return data
 
 
+def _resolve_data_path(path_str: str, base_dirs: tuple[Path, ...]) -> Path:
+    """a data file a config names: absolute, else under the working directory, else under the first base dir that holds it"""
+    path = Path(path_str)
+    if not path.is_absolute() and not path.exists():
+        for d in base_dirs:
+            if (d / path).exists():
+                return d / path
+    return path
+
+
+def load_route_q(path_str: str, *, base_dirs: tuple[Path, ...] = ()) -> tuple[tuple[float, ...], ...]:
+    """The dense joint-space route of env.route_reset; envs/reset_samplers.py:114-128.  ``{"route_q": [...]}``, ``{"waypoints": [...]}`` or a
+    bare list; items 7-lists or ``{"q": [...]}``."""
+    if not path_str:
+        return ()
+    path = _resolve_data_path(path_str, base_dirs)
+    if not path.exists():
+        raise FileNotFoundError(f"Route reset path does not exist: {path}")
+    payload = json.loads(path.read_text())
+    if isinstance(payload, dict):
+        raw_points = payload.get("route_q", payload.get("waypoints", []))
+    else:
+        raw_points = payload if isinstance(payload, list) else []
+    points = []
+    for item in raw_points:
+        points.append(tuple(_vec7(item.get("q") if isinstance(item, dict) else item, "Phase 1B reset samplers")))
+    if len(points) < 2:
+        raise ValueError(f"Route reset path must contain at least two q waypoints: {path}")
+    return tuple(points)
+
+
+@dataclass
+class RouteResetConfig:
+    """env.route_reset: the route-stride Approach reset sampler (RouteResetConfig, envs/reset_samplers.py:85-102).  ``route_q`` is the
+    loaded route (empty while disabled), handed to the env handle by kp1_set_route_stride_reset."""
+
+    enabled: bool = False
+    route_path: str = ""
+    min_stride_by_stage: tuple[int, ...] = (1,)
+    max_stride_by_stage: tuple[int, ...] = (1,)
+    start_q_noise: tuple[float, ...] = (0.0,) * NJ
+    goal_q_noise: tuple[float, ...] = (0.0,) * NJ
+    reverse_probability: float = 0.0
+    route_q: tuple[tuple[float, ...], ...] = ()
+
+    def __post_init__(self) -> None:
+        self.enabled = bool(self.enabled)
+        self.route_path = str(self.route_path or "")
+        self.min_stride_by_stage = tuple(int(v) for v in self.min_stride_by_stage)
+        self.max_stride_by_stage = tuple(int(v) for v in self.max_stride_by_stage)
+        self.start_q_noise = tuple(_vec7(self.start_q_noise, "Phase 1B reset samplers"))
+        self.goal_q_noise = tuple(_vec7(self.goal_q_noise, "Phase 1B reset samplers"))
+        self.reverse_probability = float(self.reverse_probability)
+        self.route_q = tuple(tuple(_vec7(p, "Phase 1B reset samplers")) for p in self.route_q) if self.enabled else ()
+
+    @property
+    def active(self) -> bool:
+        """sample_approach_reset :179: enabled and a route is loaded"""
+        return self.enabled and len(self.route_q) > 0
+
+    def check(self) -> None:
+        """What kp1_set_route_stride_reset refuses, raised when the config is read.  A stage whose lower stride exceeds P - 1 makes
+        the reference raise ``ValueError: low >= high`` at that stage's first reset; every stage a curriculum could reach is checked here."""
+        if not self.active:
+            return
+        for name, strides in (("min_stride_by_stage", self.min_stride_by_stage), ("max_stride_by_stage", self.max_stride_by_stage)):
+            if not 1 <= len(strides) <= MAX_STAGES:
+                raise ValueError(f"route_reset.{name} holds 1..{MAX_STAGES} entries (got {len(strides)})")
+        if min(self.start_q_noise + self.goal_q_noise) < 0.0:
+            raise ValueError("route_reset q noise must not be negative")   # numpy: uniform(low > high) is not an error, the C ABI refuses it
+        for s in range(MAX_STAGES):
+            lo = max(self.min_stride_by_stage[min(s, len(self.min_stride_by_stage) - 1)], 1)
+            if lo > len(self.route_q) - 1:
+                raise ValueError(f"route_reset: stage {s} needs a stride of at least {lo}, the route of {len(self.route_q)} points "
+                                 f"allows {len(self.route_q) - 1} (low >= high)")
+
+
 @dataclass
 class EnvConfig:
-    """Resolved env config: the C struct plus the host-only pieces (names, handoff buffer)."""
+    """Resolved env config: the C struct plus the host-only pieces (names, handoff buffer, route-stride reset block)."""
 
     c: Kp1Config
     mode_name: str = "approach"
     stage_names: list[str] = field(default_factory=list)
     handoff_states: list[dict[str, list[float]]] = field(default_factory=list)
     source: dict[str, Any] = field(default_factory=dict)
+    route_reset: RouteResetConfig = field(default_factory=RouteResetConfig)
 
     @property
     def n_stages(self) -> int:
@@ -309,7 +387,7 @@ class EnvConfig:
         c = Kp1Config()
         C.memmove(C.byref(c), C.byref(self.c), C.sizeof(Kp1Config))
         return EnvConfig(c=c, mode_name=self.mode_name, stage_names=list(self.stage_names),
-                         handoff_states=list(self.handoff_states), source=self.source)
+                         handoff_states=list(self.handoff_states), source=self.source, route_reset=self.route_reset)
 
 
 def default_config() -> Kp1Config:
@@ -489,10 +567,16 @@ def to_env_config(config: dict[str, Any], *, handoff_base_dirs: tuple[Path, ...]
             max_action_l2=float(dr_cfg.get("handoff_state_max_action_l2", 10.0)),
             base_dirs=handoff_base_dirs,
         )
-    rr = env_cfg.get("route_reset", {}) or {}
+    # route-stride Approach resets (policy_config.py:103, 159): the route is loaded only when the block is enabled
+    rr = dict(env_cfg.get("route_reset", {}) or {})
+    unknown = set(rr) - {"enabled", "route_path", "min_stride_by_stage", "max_stride_by_stage", "start_q_noise", "goal_q_noise", "reverse_probability"}
+    if unknown:
+        raise TypeError(f"RouteResetConfig.__init__() got an unexpected keyword argument '{sorted(unknown)[0]}'")
     if bool(rr.get("enabled", False)):
-        raise NotImplementedError("route_reset sampling is handled by the route layer, not the base env")
-    return EnvConfig(c=c, mode_name=mode_name, stage_names=stage_names, handoff_states=handoff_states, source=config)
+        rr["route_q"] = load_route_q(str(rr.get("route_path", "") or ""), base_dirs=handoff_base_dirs)
+    route_reset = RouteResetConfig(**rr)
+    route_reset.check()
+    return EnvConfig(c=c, mode_name=mode_name, stage_names=stage_names, handoff_states=handoff_states, source=config, route_reset=route_reset)
 
 
 def to_algorithm_kwargs(config: dict[str, Any], algorithm: str = "ppo") -> dict[str, Any]:

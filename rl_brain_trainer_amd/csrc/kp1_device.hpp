@@ -192,6 +192,10 @@ __device__ __forceinline__ const T* scalar_cache_warm(const T* __restrict__ bloc
 struct DevSampler {
   double lower[NJ], upper[NJ];
   int curriculum_enabled, n_stages;
+  // route-stride Approach resets (kp1_set_route_stride_reset): the device table [route_points][7], or nullptr: the sampler is off.  It sits
+  // here, in the 64-byte line of curriculum_enabled / n_stages that every Approach reset reads anyway, so the test for it costs a reset with
+  // the sampler off no scalar-cache line of its own
+  const double* route_q;
   kp1_stage stages[KP1_MAX_STAGES];
   kp1_stage_sampling ss;
   kp1_random_start rs;
@@ -200,6 +204,13 @@ struct DevSampler {
   int n_handoff;        // states a dock reset may draw from: handoff[handoff_offset .. handoff_offset + n_handoff)
   int handoff_offset;   // 0 unless the dock reverse curriculum selected a stage-specific slice of the buffer
   DevFk<double> fk;  // goal_q -> goal_pose6 is part of the sampled state; close-bucket rejection needs fp64 FK
+  // the rest of the route-stride block (RouteResetConfig, reset_samplers.py:86-102), read only while route_q is set.  Live fields like the
+  // dock curriculum's: a captured graph replayed after a second call reads the new table.
+  int route_points;        // P >= 2 when route_q is set
+  int route_n_min, route_n_max;   // entries of the two stride lists, 1..KP1_MAX_STAGES each
+  int route_min_stride[KP1_MAX_STAGES], route_max_stride[KP1_MAX_STAGES];
+  double route_start_noise[NJ], route_goal_noise[NJ];
+  double route_reverse_probability;
 };
 
 // ---- per-env state layout (SoA [field][N]) -------------------------------------------------
@@ -971,6 +982,27 @@ __device__ __forceinline__ void sample_random_start_pair(const DevSampler& __res
     o.initial_q[i] = dclip(start_q[i], s.lower[i], s.upper[i]);
   }
   o.stage = target_stage;
+}
+
+// KP1/envs/reset_samplers.py:393-423: start and goal are two points of a dense joint-space route, `stride` waypoints apart; the stride range
+// is the stage's.  stage_index is the env's own stage (already clamped to the stage list); the two stride lists clamp it again to their own
+// lengths.  Draw for draw as numpy: a range of one draws nothing (pcg_integers), the reverse uniform is drawn only when the probability is
+// positive, the noises only when one of the seven is.  kp1_set_route_stride_reset has refused every table on which a stage's lower stride
+// exceeds P - 1 (the reference's ValueError), so 1 <= stride <= P - 1 and both indices lie inside the table.
+// This is the index half (steps 1-5); the two points then take their noise and clip through sample_stage_joint_target, in sample_reset, with
+// the code the stage mixer uses for its own two points (:413-422 and curriculum.py:90-101 are the same draws).
+__device__ __forceinline__ void sample_route_stride_indices(const DevSampler& __restrict__ s, Pcg& r, int stage_index, int& start, int& goal) {
+  const int si = kp_maxi(stage_index, 0);
+  const int lo = kp_maxi(s.route_min_stride[kp_mini(si, s.route_n_min - 1)], 1);
+  const int hi = kp_mini(kp_maxi(s.route_max_stride[kp_mini(si, s.route_n_max - 1)], lo), s.route_points - 1);
+  const int stride = pcg_integers(r, lo, hi + 1);
+  start = pcg_integers(r, 0, s.route_points - stride);
+  goal = start + stride;
+  if (s.route_reverse_probability > 0.0 && pcg_double(r) < s.route_reverse_probability) {
+    const int t = start;
+    start = goal;
+    goal = t;
+  }
 }
 
 }  // namespace kp1

@@ -10,6 +10,7 @@
 // There is no CPU fallback: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -449,7 +450,17 @@ struct kp1_env {
   DevSampler* dev_smp = nullptr;
   kp1_handoff_state* dev_handoff = nullptr;
   int32_t n_handoff = 0;
-  void* snapshot = nullptr;    // kp1_state_snapshot: real | ints | rng64 | rng32, allocated on first use
+  // kp1_set_route_stride_reset: the live table and the host mirror of its scalars (upload_cfg writes them into every new DevSampler).
+  // A replaced table stays allocated until kp1_destroy: a launch already queued may still read it.
+  struct RouteStride {
+    double* dev_q = nullptr;
+    int32_t n_points = 0, n_min = 0, n_max = 0;
+    int32_t min_stride[KP1_MAX_STAGES] = {}, max_stride[KP1_MAX_STAGES] = {};
+    double start_noise[KP1_NJ] = {}, goal_noise[KP1_NJ] = {};
+    double reverse_probability = 0.0;
+  } route_stride;
+  std::vector<double*> route_tables;   // every table ever uploaded, the live one included
+  void* snapshot = nullptr;   // kp1_state_snapshot: real | ints | rng64 | rng32, allocated on first use
   kp1_dock_curriculum_state* dock_tracker = nullptr;   // device tracker attached by kp1_dock_curriculum_create (its stage survives upload_cfg)
   double* opt_scratch = nullptr;  // 4*[N][7] + [N][6] doubles for explicit reset options / set_state
   const int32_t* stage_ptr = nullptr;  // kp1_bind_stage_ptr
@@ -495,6 +506,18 @@ int upload_cfg(kp1_env* e) {
   }
   DevSampler s;
   make_dev_sampler(e->cfg, e->n_handoff, &s);
+  {
+    const kp1_env::RouteStride& r = e->route_stride;
+    s.route_q = r.dev_q;
+    s.route_points = r.n_points;
+    s.route_n_min = r.n_min;
+    s.route_n_max = r.n_max;
+    std::memcpy(s.route_min_stride, r.min_stride, sizeof r.min_stride);
+    std::memcpy(s.route_max_stride, r.max_stride, sizeof r.max_stride);
+    std::memcpy(s.route_start_noise, r.start_noise, sizeof r.start_noise);
+    std::memcpy(s.route_goal_noise, r.goal_noise, sizeof r.goal_noise);
+    s.route_reverse_probability = r.reverse_probability;
+  }
   HIP_TRY(hipMemcpyAsync(e->dev_smp, &s, sizeof s, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));  // d / s are stack objects
   return reapply_dock_stage(e);
@@ -794,6 +817,7 @@ int kp1_destroy(kp1_env* e) {
   for (void* p : {(void*)e->real, (void*)e->ints, (void*)e->rng64, (void*)e->rng32, e->dev_cfg, (void*)e->dev_smp, (void*)e->dev_handoff,
                   (void*)e->opt_scratch, e->comps, e->snapshot})
     (void)hipFree(p);
+  for (double* p : e->route_tables) (void)hipFree(p);
   delete e;
   return KP1_OK;
 }
@@ -869,6 +893,45 @@ int kp1_set_handoff_states(kp1_env* e, const kp1_handoff_state* states, int32_t 
     HIP_TRY(hipMalloc((void**)&e->dev_handoff, sizeof(kp1_handoff_state) * (size_t)n_states));
     HIP_TRY(hipMemcpy(e->dev_handoff, states, sizeof(kp1_handoff_state) * (size_t)n_states, hipMemcpyHostToDevice));
   }
+  return upload_cfg(e);
+}
+int kp1_set_route_stride_reset(kp1_env* e, const double* route_q, int32_t n_points, const int32_t* min_stride_by_stage, int32_t n_min,
+                               const int32_t* max_stride_by_stage, int32_t n_max, const double* start_q_noise, const double* goal_q_noise,
+                               double reverse_probability) {
+  if (!e) return fail(KP1_ERR_INVALID, "env is NULL");
+  HIP_TRY(hipSetDevice(e->device));
+  if (!route_q || n_points == 0) {   // off: the Approach reset falls through to random-start pairs / the stage mixer again
+    e->route_stride = kp1_env::RouteStride();
+    return upload_cfg(e);
+  }
+  if (n_points < 2) return fail(KP1_ERR_INVALID, "kp1_set_route_stride_reset: a route needs at least two q waypoints");
+  if (!min_stride_by_stage || !max_stride_by_stage || n_min < 1 || n_min > KP1_MAX_STAGES || n_max < 1 || n_max > KP1_MAX_STAGES)
+    return fail(KP1_ERR_INVALID, "kp1_set_route_stride_reset: each stride list holds 1.." + std::to_string(KP1_MAX_STAGES) + " entries");
+  if (!start_q_noise || !goal_q_noise) return fail(KP1_ERR_INVALID, "kp1_set_route_stride_reset: the two noise vectors are required");
+  for (int k = 0; k < NJ; ++k)
+    if (!(start_q_noise[k] >= 0.0) || !(goal_q_noise[k] >= 0.0)) return fail(KP1_ERR_INVALID, "kp1_set_route_stride_reset: a q noise is negative");
+  if (!(reverse_probability == reverse_probability)) return fail(KP1_ERR_INVALID, "kp1_set_route_stride_reset: reverse_probability is NaN");
+  // numpy's integers(lo, hi + 1) raises "low >= high" at the first reset of such a stage; here the table is refused before any kernel sees it
+  for (int s = 0; s < KP1_MAX_STAGES; ++s) {
+    const int lo = std::max(min_stride_by_stage[std::min(s, n_min - 1)], 1);
+    if (lo > n_points - 1)
+      return fail(KP1_ERR_INVALID, "kp1_set_route_stride_reset: stage " + std::to_string(s) + " needs a stride of at least " + std::to_string(lo) +
+                                       ", the route of " + std::to_string(n_points) + " points allows " + std::to_string(n_points - 1));
+  }
+  kp1_env::RouteStride r;
+  const size_t bytes = sizeof(double) * (size_t)n_points * NJ;
+  HIP_TRY(hipMalloc((void**)&r.dev_q, bytes));
+  e->route_tables.push_back(r.dev_q);
+  HIP_TRY(hipMemcpyAsync(r.dev_q, route_q, bytes, hipMemcpyHostToDevice, e->stream));   // upload_cfg synchronizes the stream before it returns
+  r.n_points = n_points;
+  r.n_min = n_min;
+  r.n_max = n_max;
+  std::memcpy(r.min_stride, min_stride_by_stage, sizeof(int32_t) * (size_t)n_min);
+  std::memcpy(r.max_stride, max_stride_by_stage, sizeof(int32_t) * (size_t)n_max);
+  std::memcpy(r.start_noise, start_q_noise, sizeof r.start_noise);
+  std::memcpy(r.goal_noise, goal_q_noise, sizeof r.goal_noise);
+  r.reverse_probability = reverse_probability;
+  e->route_stride = r;
   return upload_cfg(e);
 }
 int kp1_seed(kp1_env* e, uint64_t seed0, uint64_t first_env_id) {

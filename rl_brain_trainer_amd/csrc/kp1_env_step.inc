@@ -192,16 +192,36 @@ __device__ __forceinline__ void sample_reset(const DevSampler& __restrict__ s, c
 #undef KP1_DOCK_SLICE
 #undef KP1_DOCK_STAGE
   } else {
-    if (s.rs.enabled && s.curriculum_enabled && s.n_stages > 0) {
+    // env.route_reset is ahead of the other two, as sample_approach_reset :179 takes it.  It and the stage mixer end in the same two draws
+    // -- a point plus uniform noise, clipped -- so each only chooses the two points and noises (per-lane pointers either way: the mixer's
+    // stage is per lane too) and ONE copy of the fourteen uniforms serves both: the route branch adds its index draws to these kernels
+    // and nothing else.
+    const bool route = __builtin_expect(s.route_q != nullptr, 0);
+    if (!route && s.rs.enabled && s.curriculum_enabled && s.n_stages > 0) {
       sample_random_start_pair(s, rng, stage_index, o);
       has_dq_pa = true;
       return;
     }
-    if (s.curriculum_enabled && s.n_stages > 0) {
-      int idx = sample_workspace_stage_index(s, rng, stage_index);
-      sample_stage_joint_target(s, rng, s.stages[idx].start_q, s.stages[idx].start_noise, o.initial_q);
-      sample_stage_joint_target(s, rng, s.stages[idx].goal_q, s.stages[idx].goal_noise, o.goal_q);
-      o.stage = idx;
+    if (route || (s.curriculum_enabled && s.n_stages > 0)) {
+      const double *start_q, *start_noise, *goal_q, *goal_noise;
+      if (route) {
+        int start, goal;
+        sample_route_stride_indices(s, rng, stage_index, start, goal);
+        start_q = s.route_q + (size_t)start * NJ;
+        goal_q = s.route_q + (size_t)goal * NJ;
+        start_noise = s.route_start_noise;
+        goal_noise = s.route_goal_noise;
+        o.stage = stage_index;
+      } else {
+        const int idx = sample_workspace_stage_index(s, rng, stage_index);
+        start_q = s.stages[idx].start_q;
+        goal_q = s.stages[idx].goal_q;
+        start_noise = s.stages[idx].start_noise;
+        goal_noise = s.stages[idx].goal_noise;
+        o.stage = idx;
+      }
+      sample_stage_joint_target(s, rng, start_q, start_noise, o.initial_q);
+      sample_stage_joint_target(s, rng, goal_q, goal_noise, o.goal_q);
     } else {
       sample_joint_configuration(s, rng, s.start_sample_margin_fraction, o.initial_q);
       sample_joint_configuration(s, rng, s.goal_sample_margin_fraction, o.goal_q);

@@ -164,7 +164,8 @@ def main(argv: list[str] | None = None) -> dict[str, Any]:
 def _main(args, proc) -> dict[str, Any]:
     world, rank, local_rank = proc.world, proc.rank, proc.device
     cfg = kcfg.load_workspace_expansion_config(args.config)
-    env_cfg = kcfg.to_env_config(cfg)
+    # env.route_reset.route_path: absolute, under the working directory, or next to the config file
+    env_cfg = kcfg.to_env_config(cfg, handoff_base_dirs=(Path(args.config).resolve().parent,) if args.config else ())
     algo = kcfg.to_algorithm_kwargs(cfg, "ppo")
     ws = cfg.get("workspace_expansion", {})
     if args.total_timesteps is not None:

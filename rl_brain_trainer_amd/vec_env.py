@@ -59,6 +59,8 @@ class ArmKinematicVecEnv:
         if config.handoff_states:
             arr = config.handoff_array()
             native.check(self.L.kp1_set_handoff_states(self._handle, C.cast(arr, C.c_void_p), len(config.handoff_states)))
+        if config.route_reset.active:
+            self.set_route_stride_reset(config.route_reset)
         n = self.n_envs
         self.obs = torch.zeros((n, kcfg.OBS_DIM), dtype=torch.float32, device=self.device)
         self.terminal_obs = torch.zeros((n, kcfg.OBS_DIM), dtype=torch.float32, device=self.device)
@@ -139,6 +141,23 @@ class ArmKinematicVecEnv:
         arr = self.config.handoff_array()
         native.check(self.L.kp1_set_handoff_states(self._handle, C.cast(arr, C.c_void_p), len(self.config.handoff_states)))
         self.launch_args_version += 1
+
+    def set_route_stride_reset(self, route_reset: "kcfg.RouteResetConfig | None") -> None:
+        """env.route_reset (reset_samplers.py:393-423): Approach resets draw start and goal from the route, a stage-dependent stride apart.
+        ``None``, a disabled block or one without points switches the sampler off.  The handle's sampler block is rewritten in place: a
+        captured rollout graph replayed afterwards samples from the new table, and replaced tables live until ``close()``."""
+        rr = route_reset if route_reset is not None else kcfg.RouteResetConfig()
+        if not rr.active:
+            native.check(self.L.kp1_set_route_stride_reset(self._handle, None, 0, None, 0, None, 0, None, None, 0.0))
+        else:
+            q = (C.c_double * (kcfg.NJ * len(rr.route_q)))(*[v for p in rr.route_q for v in p])
+            lo = (C.c_int32 * len(rr.min_stride_by_stage))(*rr.min_stride_by_stage)
+            hi = (C.c_int32 * len(rr.max_stride_by_stage))(*rr.max_stride_by_stage)
+            sn, gn = (C.c_double * kcfg.NJ)(*rr.start_q_noise), (C.c_double * kcfg.NJ)(*rr.goal_q_noise)
+            native.check(self.L.kp1_set_route_stride_reset(self._handle, C.cast(q, C.c_void_p), len(rr.route_q), C.cast(lo, C.c_void_p), len(lo),
+                                                           C.cast(hi, C.c_void_p), len(hi), C.cast(sn, C.c_void_p), C.cast(gn, C.c_void_p),
+                                                           float(rr.reverse_probability)))
+        self.config.route_reset = rr
 
     def set_obs_stride(self, stride: int) -> None:
         """Row pitch of every observation buffer handed to reset/step (56, or 64 = zero-padded for the MFMA GEMMs)."""
