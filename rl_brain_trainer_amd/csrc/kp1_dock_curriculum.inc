@@ -141,15 +141,14 @@ __global__ void __launch_bounds__(64) dock_curriculum_apply_kernel(const kp1_doc
 
 // upload_cfg (kp1_update_config, kp1_set_handoff_states) rewrites the device config and sampler from the host mirror, i.e. with the BASE
 // scalars and the whole handoff buffer: while a tracker is attached its current stage (scalars + handoff slice) is applied again on top.
-int reapply_dock_stage(kp1_env* env) {
-  if (!env->dock_tracker) return KP1_OK;
-  if (env->real_type == KP1_REAL_F64)
-    hipLaunchKernelGGL(dock_curriculum_apply_kernel<double>, dim3(1), dim3(64), 0, env->stream, env->dock_tracker, (DevCfg<double>*)env->dev_cfg, env->dev_smp);
-  else
-    hipLaunchKernelGGL(dock_curriculum_apply_kernel<float>, dim3(1), dim3(64), 0, env->stream, env->dock_tracker, (DevCfg<float>*)env->dev_cfg, env->dev_smp);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+// the stage tracker `st` stands at -> the handle's device config and sampler (one wave, lane 0 writes)
+int apply_dock_stage(kp1_env* env, const kp1_dock_curriculum_state* st) {
+  return with_real(env->real_type, [&](auto real) {
+    using R = decltype(real);
+    return launch_env(dock_curriculum_apply_kernel<R>, 64, 64, 0, env->stream, st, (DevCfg<R>*)env->dev_cfg, env->dev_smp);
+  });
 }
+int reapply_dock_stage(kp1_env* env) { return env->dock_tracker ? apply_dock_stage(env, env->dock_tracker) : (int)KP1_OK; }
 
 }  // namespace
 
@@ -185,11 +184,11 @@ int kp1_dock_curriculum_create(kp1_env* env, const kp1_dock_curriculum_stage* st
     return fail(kp1::status_of(e), std::string("kp1_dock_curriculum_create: ") + hipGetErrorString(e));
   }
   // _on_training_start: the first stage is applied before the first reset (callbacks.py:128-129)
-  if (env->real_type == KP1_REAL_F64)
-    hipLaunchKernelGGL(dock_curriculum_apply_kernel<double>, dim3(1), dim3(64), 0, env->stream, d, (DevCfg<double>*)env->dev_cfg, env->dev_smp);
-  else
-    hipLaunchKernelGGL(dock_curriculum_apply_kernel<float>, dim3(1), dim3(64), 0, env->stream, d, (DevCfg<float>*)env->dev_cfg, env->dev_smp);
-  HIP_TRY(kp1::launch_status());
+  const int rc = apply_dock_stage(env, d);
+  if (rc != KP1_OK) {
+    (void)hipFree(d);
+    return rc;
+  }
   env->dock_tracker = d;
   *out_dev = d;
   return KP1_OK;
@@ -242,8 +241,11 @@ int kp1_dock_curriculum_create_population(kp1_env* env, const kp1_dock_curriculu
   }
   // _on_training_start of every replica: stage 0 into the shared config before the first reset, as kp1_dock_curriculum_create does (what no
   // stage overrides is read from there; the population forms read the rest from the live records)
-  hipLaunchKernelGGL(dock_curriculum_apply_kernel<float>, dim3(1), dim3(64), 0, env->stream, d, (DevCfg<float>*)env->dev_cfg, env->dev_smp);
-  HIP_TRY(kp1::launch_status());
+  const int rc = apply_dock_stage(env, d);
+  if (rc != KP1_OK) {
+    (void)hipFree(d);
+    return rc;
+  }
   env->pop_dock_states = d;   // not env->dock_tracker: upload_cfg must not copy one replica's stage into the shared config
   env->pop_replicas = n_replicas;
   *out_dev = d;
@@ -255,10 +257,8 @@ int kp1_dock_curriculum_observe_population(kp1_env* env, kp1_dock_curriculum_sta
   if (!env || !states_dev || !dones || n_per_replica <= 0 || n_replicas < 1 || n_replicas > KP1_CURRICULUM_MAX_REPLICAS)
     return fail(KP1_ERR_INVALID, "bad argument to kp1_dock_curriculum_observe_population");
   HIP_TRY(hipSetDevice(env->device));
-  hipLaunchKernelGGL(dock_curriculum_population_kernel, dim3((unsigned)n_replicas), dim3(64), 0, (hipStream_t)stream, states_dev,
-                     reinterpret_cast<kp1_dock_curriculum_stage*>(states_dev + n_replicas), dones, n_per_replica);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch_env(dock_curriculum_population_kernel, 64 * n_replicas, 64, 0, (hipStream_t)stream, states_dev,
+                    reinterpret_cast<kp1_dock_curriculum_stage*>(states_dev + n_replicas), dones, n_per_replica);   // one wave per tracker
 }
 
 int kp1_dock_curriculum_read_replica(kp1_env* env, const kp1_dock_curriculum_state* states_dev, int32_t n_replicas, int32_t k,
@@ -289,14 +289,11 @@ int kp1_dock_curriculum_observe(kp1_env* env, kp1_dock_curriculum_state* st_dev,
   if (!env || !st_dev || !dones || n_local <= 0 || chunk_steps <= 0 || world <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_dock_curriculum_observe");
   HIP_TRY(hipSetDevice(env->device));
   const int clock = n_local * world;
-  if (env->real_type == KP1_REAL_F64)
-    hipLaunchKernelGGL(dock_curriculum_kernel<double>, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, dones, n_local, chunk_steps, world, clock,
-                       (DevCfg<double>*)env->dev_cfg, env->dev_smp);
-  else
-    hipLaunchKernelGGL(dock_curriculum_kernel<float>, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, dones, n_local, chunk_steps, world, clock,
-                       (DevCfg<float>*)env->dev_cfg, env->dev_smp);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return with_real(env->real_type, [&](auto real) {
+    using R = decltype(real);
+    return launch_env(dock_curriculum_kernel<R>, 64, 64, 0, (hipStream_t)stream, st_dev, dones, n_local, chunk_steps, world, clock, (DevCfg<R>*)env->dev_cfg,
+                      env->dev_smp);
+  });
 }
 
 int kp1_dock_curriculum_read(kp1_env* env, const kp1_dock_curriculum_state* st_dev, kp1_dock_curriculum_state* out_host, void* stream) {

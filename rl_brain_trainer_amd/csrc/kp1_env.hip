@@ -478,8 +478,38 @@ namespace {
 // One wave per workgroup at every size: the step kernel holds 500 vector registers, so a CU runs four waves (one per SIMD), and a 256-thread
 // workgroup can only be replaced when all four of its waves have finished.  64-thread workgroups let every SIMD take its next wave by itself:
 // 117.5 -> 99.1 us at 524 288 envs, 33.8 -> 31.3 us at 131 072 (profiles/r03_ab_env_block_size.log).
-int block_for(int64_t) { return 64; }
+constexpr int ENV_BLOCK = 64;
+// The stateless utilities and eval_accumulate hold a few dozen registers per lane, so nothing waits on a workgroup's slowest wave: they keep the
+// usual four waves per workgroup (eval_accumulate_kernel computes its lane from a block of 256).
+constexpr int UTIL_BLOCK = 256;
 
+// The one launch of this file: ceil(lanes / block) workgroups of `block` lanes, then the launch check of kp1_host.hpp.  `lanes` is the env
+// count where a lane is an env; the curriculum trackers run one 64-lane wave each (lanes = 64 * trackers, block = 64).
+template <typename... Params, typename... Args>
+int launch_env(void (*kernel)(Params...), int64_t lanes, int block, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((lanes + block - 1) / block)), dim3(block), lds_bytes, stream, args...);
+  HIP_TRY(kp1::launch_status());
+  return KP1_OK;
+}
+
+// real_type -> the type itself: f(R()) with R = double or float, anything else refused.  The return types are deduced, here and in the callables
+// (write no `-> int` on them): the bodies are then instantiated where with_real is called and not at the end of the file, so the kernels a callable
+// names are first named at the call, in file order, which is what decides their place in the code object (DESIGN.md sections 26 and 41).
+template <class F>
+auto with_real(int real_type, F&& f) {
+  if (real_type == KP1_REAL_F64) return f(double());
+  if (real_type == KP1_REAL_F32) return f(float());
+  return fail(KP1_ERR_INVALID, "real_type must be KP1_REAL_F32 or KP1_REAL_F64");
+}
+
+// the stateless entry points and kp1_create: the device they run on
+int use_device(int device) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(KP1_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
+  if (device < 0 || device >= count) return fail(KP1_ERR_INVALID, "device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  return KP1_OK;
+}
 
 template <typename R>
 EnvState<R> state_of(const kp1_env* e) {
@@ -495,15 +525,6 @@ EnvState<R> state_of(const kp1_env* e) {
 int reapply_dock_stage(kp1_env* env);   // kp1_dock_curriculum.inc
 
 int upload_cfg(kp1_env* e) {
-  if (e->real_type == KP1_REAL_F64) {
-    DevCfg<double> d;
-    make_dev_cfg<double>(e->cfg, &d);
-    HIP_TRY(hipMemcpyAsync(e->dev_cfg, &d, sizeof d, hipMemcpyHostToDevice, e->stream));
-  } else {
-    DevCfg<float> d;
-    make_dev_cfg<float>(e->cfg, &d);
-    HIP_TRY(hipMemcpyAsync(e->dev_cfg, &d, sizeof d, hipMemcpyHostToDevice, e->stream));
-  }
   DevSampler s;
   make_dev_sampler(e->cfg, e->n_handoff, &s);
   {
@@ -518,29 +539,60 @@ int upload_cfg(kp1_env* e) {
     std::memcpy(s.route_goal_noise, r.goal_noise, sizeof r.goal_noise);
     s.route_reverse_probability = r.reverse_probability;
   }
-  HIP_TRY(hipMemcpyAsync(e->dev_smp, &s, sizeof s, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));  // d / s are stack objects
-  return reapply_dock_stage(e);
+  const int rc = with_real(e->real_type, [&](auto real) {
+    DevCfg<decltype(real)> d;
+    make_dev_cfg(e->cfg, &d);
+    HIP_TRY(hipMemcpyAsync(e->dev_cfg, &d, sizeof d, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->dev_smp, &s, sizeof s, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));  // d / s are stack objects
+    return (int)KP1_OK;
+  });
+  return rc != KP1_OK ? rc : reapply_dock_stage(e);
 }
 
-// env i <- default_rng(seed_of(i))
+// ---- the PCG64 streams of N envs on the device: [4][N] u64 (state_hi, state_lo, inc_hi, inc_lo) + [2][N] u32 (has_uint32, uinteger) ----
+void pack_rng_planes(const kp1_rng_state* rows, size_t n, std::vector<uint64_t>& r64, std::vector<uint32_t>& r32) {
+  r64.resize(4 * n);
+  r32.resize(2 * n);
+  for (size_t i = 0; i < n; ++i) {
+    r64[0 * n + i] = rows[i].state_hi; r64[1 * n + i] = rows[i].state_lo; r64[2 * n + i] = rows[i].inc_hi; r64[3 * n + i] = rows[i].inc_lo;
+    r32[0 * n + i] = rows[i].has_uint32; r32[1 * n + i] = rows[i].uinteger;
+  }
+}
+void unpack_rng_planes(const std::vector<uint64_t>& r64, const std::vector<uint32_t>& r32, size_t n, kp1_rng_state* rows) {
+  for (size_t i = 0; i < n; ++i) {
+    rows[i].state_hi = r64[0 * n + i]; rows[i].state_lo = r64[1 * n + i]; rows[i].inc_hi = r64[2 * n + i]; rows[i].inc_lo = r64[3 * n + i];
+    rows[i].has_uint32 = r32[0 * n + i]; rows[i].uinteger = r32[1 * n + i];
+  }
+}
+int upload_rng_planes(uint64_t* dst64, uint32_t* dst32, const kp1_rng_state* rows, size_t n, hipStream_t stream) {
+  std::vector<uint64_t> r64;
+  std::vector<uint32_t> r32;
+  pack_rng_planes(rows, n, r64, r32);
+  HIP_TRY(hipMemcpyAsync(dst64, r64.data(), r64.size() * 8, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(dst32, r32.data(), r32.size() * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return KP1_OK;
+}
+int download_rng_planes(const uint64_t* src64, const uint32_t* src32, kp1_rng_state* rows, size_t n, hipStream_t stream) {
+  std::vector<uint64_t> r64(4 * n);
+  std::vector<uint32_t> r32(2 * n);
+  HIP_TRY(hipMemcpyAsync(r64.data(), src64, r64.size() * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(r32.data(), src32, r32.size() * 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  unpack_rng_planes(r64, r32, n, rows);
+  return KP1_OK;
+}
+// stream i <- default_rng(seed_of(i))
+template <typename SeedOf>
+int seed_planes_by(uint64_t* dst64, uint32_t* dst32, int64_t n, hipStream_t stream, SeedOf seed_of) {
+  std::vector<kp1_rng_state> rows((size_t)n);
+  for (int64_t i = 0; i < n; ++i) pcg64_seed(seed_of(i), &rows[(size_t)i]);
+  return upload_rng_planes(dst64, dst32, rows.data(), rows.size(), stream);
+}
 template <typename SeedOf>
 int seed_streams_by(kp1_env* e, SeedOf seed_of) {
-  const int64_t n = e->n;
-  std::vector<uint64_t> r64(4 * (size_t)n);
-  std::vector<uint32_t> r32(2 * (size_t)n, 0u);
-  for (int64_t i = 0; i < n; ++i) {
-    kp1_rng_state s;
-    pcg64_seed(seed_of(i), &s);
-    r64[0 * n + i] = s.state_hi;
-    r64[1 * n + i] = s.state_lo;
-    r64[2 * n + i] = s.inc_hi;
-    r64[3 * n + i] = s.inc_lo;
-  }
-  HIP_TRY(hipMemcpyAsync(e->rng64, r64.data(), r64.size() * 8, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->rng32, r32.data(), r32.size() * 4, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return KP1_OK;
+  return seed_planes_by(e->rng64, e->rng32, e->n, e->stream, seed_of);
 }
 
 int seed_streams(kp1_env* e, uint64_t seed0, uint64_t first_env_id) {
@@ -578,69 +630,43 @@ StepArgs<R> make_step_args(kp1_env* e, const void* actions, float* obs, void* re
 template <typename R>
 int launch_step(kp1_env* e, const void* actions, float* obs, void* reward, uint8_t* done, float* terminal_obs, int auto_reset) {
   const StepArgs<R> a = make_step_args<R>(e, actions, obs, reward, done, terminal_obs, auto_reset);
-  const int block = block_for(e->n);
-  const dim3 grid((unsigned)((e->n + block - 1) / block));
   const bool comps = e->comps_enabled && e->comps;
-  const size_t lds = sizeof(float) * OBS_TILE_FLOATS * (size_t)(block / 64);   // one observation tile per wave (store_obs_tile)
-  if (e->pop_dock_states) {
-    // per-replica dock stages: the f32 dock form (kp1_dock_curriculum_create_population checks type and mode; kp1_set_mode may change the mode)
-    if (e->mode != KP1_MODE_DOCK) return fail(KP1_ERR_UNSUPPORTED, "a dock population env handle steps in the dock mode only");
-    if constexpr (std::is_same<R, float>::value) {
-      if (comps) hipLaunchKernelGGL((kp1_step_kernel<float, KP1_MODE_DOCK, true, true>), grid, dim3(block), lds, e->stream, a);
-      else hipLaunchKernelGGL((kp1_step_kernel<float, KP1_MODE_DOCK, false, true>), grid, dim3(block), lds, e->stream, a);
-      HIP_TRY(kp1::launch_status());
-      return KP1_OK;
-    } else {
-      return fail(KP1_ERR_UNSUPPORTED, "a population env handle is f32");
-    }
+  constexpr bool F32 = std::is_same<R, float>::value;
+  // the eight (MODE, COMPS, POP) forms share a signature: choose one (first named here = first in the code object), launch once
+  void (*kernel)(const StepArgs<R>) = nullptr;
+  if (e->pop_dock_states || e->pop_states) {
+    // Per-replica stages exist as f32 forms only: the dock form for a dock population, the approach form for bound approach trackers (the two
+    // creators check type and mode; kp1_set_mode may change the mode later).  Approach without curriculum stages never reads the stage, and
+    // the ordinary form below does the same work.
+    if (e->pop_dock_states && e->mode != KP1_MODE_DOCK) return fail(KP1_ERR_UNSUPPORTED, "a dock population env handle steps in the dock mode only");
+    if (!e->pop_dock_states && e->mode != KP1_MODE_APPROACH) return fail(KP1_ERR_UNSUPPORTED, "a population env handle steps in the approach mode only");
+    if constexpr (!F32) return fail(KP1_ERR_UNSUPPORTED, "a population env handle is f32");
+    else if (e->pop_dock_states) kernel = comps ? kp1_step_kernel<float, KP1_MODE_DOCK, true, true> : kp1_step_kernel<float, KP1_MODE_DOCK, false, true>;
+    else if (e->cfg.curriculum_enabled) kernel = comps ? kp1_step_kernel<float, KP1_MODE_APPROACH, true, true> : kp1_step_kernel<float, KP1_MODE_APPROACH, false, true>;
   }
-  if (e->pop_states) {
-    // per-replica stages: only the f32 approach form exists (kp1_bind_population_stages checks type and mode; kp1_set_mode may change the
-    // mode later).  Without curriculum stages the stage is never read, and the ordinary form below does the same work.
-    if (e->mode != KP1_MODE_APPROACH) return fail(KP1_ERR_UNSUPPORTED, "a population env handle steps in the approach mode only");
-    if constexpr (std::is_same<R, float>::value) {
-      if (e->cfg.curriculum_enabled) {
-        if (comps) hipLaunchKernelGGL((kp1_step_kernel<float, KP1_MODE_APPROACH, true, true>), grid, dim3(block), lds, e->stream, a);
-        else hipLaunchKernelGGL((kp1_step_kernel<float, KP1_MODE_APPROACH, false, true>), grid, dim3(block), lds, e->stream, a);
-        HIP_TRY(kp1::launch_status());
-        return KP1_OK;
-      }
-    } else {
-      return fail(KP1_ERR_UNSUPPORTED, "a population env handle is f32");
-    }
+  if (!kernel) {
+    if (e->mode == KP1_MODE_DOCK) kernel = comps ? kp1_step_kernel<R, KP1_MODE_DOCK, true, false> : kp1_step_kernel<R, KP1_MODE_DOCK, false, false>;
+    else kernel = comps ? kp1_step_kernel<R, KP1_MODE_APPROACH, true, false> : kp1_step_kernel<R, KP1_MODE_APPROACH, false, false>;
   }
-  if (e->mode == KP1_MODE_DOCK) {
-    if (comps) hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_DOCK, true, false>), grid, dim3(block), lds, e->stream, a);
-    else hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_DOCK, false, false>), grid, dim3(block), lds, e->stream, a);
-  } else {
-    if (comps) hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_APPROACH, true, false>), grid, dim3(block), lds, e->stream, a);
-    else hipLaunchKernelGGL((kp1_step_kernel<R, KP1_MODE_APPROACH, false, false>), grid, dim3(block), lds, e->stream, a);
-  }
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  const size_t lds = sizeof(float) * OBS_TILE_FLOATS * (size_t)(ENV_BLOCK / 64);   // one observation tile per wave (store_obs_tile)
+  return launch_env(kernel, e->n, ENV_BLOCK, lds, e->stream, a);
 }
 
 template <typename R>
 int launch_reset(kp1_env* e, const uint8_t* mask, const ResetOptsDev& opts, int mode, float* obs) {
-  const int block = block_for(e->n);
-  const dim3 grid((unsigned)((e->n + block - 1) / block));
-  const kp1_dock_curriculum_stage* live = dock_population_live(e);
-  const int n_per_replica = e->pop_replicas > 0 ? e->n / e->pop_replicas : 0;
-  if (mode == KP1_MODE_DOCK && live) {
-    // a dock population samples each replica's resets with its own live stage (the shared config holds stage 0 only)
-    if constexpr (std::is_same<R, float>::value)
-      hipLaunchKernelGGL((kp1_reset_kernel<float, KP1_MODE_DOCK, true>), grid, dim3(block), 0, e->stream, state_of<float>(e),
-                         (const DevCfg<float>*)e->dev_cfg, e->dev_smp, e->dev_handoff, mask, opts, e->stage, obs, e->obs_stride, live, n_per_replica);
-    else
-      return fail(KP1_ERR_UNSUPPORTED, "a population env handle is f32");
-  } else if (mode == KP1_MODE_DOCK)
-    hipLaunchKernelGGL((kp1_reset_kernel<R, KP1_MODE_DOCK>), grid, dim3(block), 0, e->stream, state_of<R>(e),
-                       (const DevCfg<R>*)e->dev_cfg, e->dev_smp, e->dev_handoff, mask, opts, e->stage, obs, e->obs_stride, nullptr, 0);
-  else
-    hipLaunchKernelGGL((kp1_reset_kernel<R, KP1_MODE_APPROACH>), grid, dim3(block), 0, e->stream, state_of<R>(e),
-                       (const DevCfg<R>*)e->dev_cfg, e->dev_smp, e->dev_handoff, mask, opts, e->stage, obs, e->obs_stride, nullptr, 0);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  // a dock population samples each replica's resets with its own live stage (the shared config holds stage 0 only)
+  const kp1_dock_curriculum_stage* live = mode == KP1_MODE_DOCK ? dock_population_live(e) : nullptr;
+  decltype(&kp1_reset_kernel<R, KP1_MODE_DOCK>) kernel;   // the three forms share a signature
+  if (live) {
+    if constexpr (std::is_same<R, float>::value) kernel = kp1_reset_kernel<float, KP1_MODE_DOCK, true>;
+    else return fail(KP1_ERR_UNSUPPORTED, "a population env handle is f32");
+  } else if (mode == KP1_MODE_DOCK) {
+    kernel = kp1_reset_kernel<R, KP1_MODE_DOCK>;
+  } else {
+    kernel = kp1_reset_kernel<R, KP1_MODE_APPROACH>;
+  }
+  return launch_env(kernel, e->n, ENV_BLOCK, 0, e->stream, state_of<R>(e), (const DevCfg<R>*)e->dev_cfg, e->dev_smp, e->dev_handoff, mask, opts, e->stage, obs,
+                    e->obs_stride, live, live ? e->n / e->pop_replicas : 0);
 }
 
 // ---------------------------------------------------------------------------------------------- evaluator bookkeeping (kp1_eval_accumulate)
@@ -680,8 +706,31 @@ __global__ void __launch_bounds__(256) eval_accumulate_kernel(const R* __restric
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(b.n_alive, __popcll(bal));
 }
 
-int ensure_scratch(kp1_env* e) {
-  if (!e->opt_scratch) HIP_TRY(hipMalloc((void**)&e->opt_scratch, sizeof(double) * (size_t)e->n * (4 * NJ + 6)));
+// opt_scratch: five row-major fp64 blocks, one per optional array of kp1_reset_opts / kp1_set_state / kp1_get_state, in their order
+// (q, dq, prev_action, goal_q: [N][7]; goal_pose6: [N][6]).  Allocated on first use.
+struct OptScratch {
+  double* dev[5];
+  size_t bytes[5];
+};
+int ensure_scratch(kp1_env* e, OptScratch* s) {
+  const int width[5] = {NJ, NJ, NJ, NJ, 6};
+  size_t total = 0;
+  for (int k = 0; k < 5; ++k) total += s->bytes[k] = sizeof(double) * (size_t)e->n * width[k];
+  if (!e->opt_scratch) HIP_TRY(hipMalloc((void**)&e->opt_scratch, total));
+  s->dev[0] = e->opt_scratch;
+  for (int k = 1; k < 5; ++k) s->dev[k] = s->dev[k - 1] + (size_t)e->n * width[k - 1];
+  return KP1_OK;
+}
+// the rows the caller gave (src[k], host) into their blocks; dev[k] = the block, or nullptr where src[k] is
+int upload_opt_rows(kp1_env* e, const double* const src[5], const double* dev[5]) {
+  OptScratch s;
+  const int rc = ensure_scratch(e, &s);
+  if (rc != KP1_OK) return rc;
+  for (int k = 0; k < 5; ++k) {
+    dev[k] = src[k] ? s.dev[k] : nullptr;
+    if (src[k]) HIP_TRY(hipMemcpyAsync(s.dev[k], src[k], s.bytes[k], hipMemcpyHostToDevice, e->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));  // host source buffers are the caller's
   return KP1_OK;
 }
 
@@ -763,10 +812,8 @@ int kp1_create(const kp1_config* cfg, int32_t n_envs, int32_t device, int32_t re
     if (std::memcmp(&fk, FKG_CHECK, sizeof fk) != 0)
       return fail(KP1_ERR_UNSUPPORTED, "csrc/kp1_fk_generated.inc does not match the robot constants of kp1_env.hip: run python3 tools/gen_fk_chain.py and rebuild");
   }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(KP1_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-  if (device < 0 || device >= count) return fail(KP1_ERR_INVALID, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
+  int rc = use_device(device);
+  if (rc != KP1_OK) return rc;
   kp1_env* e = new kp1_env();
   e->cfg = *cfg;
   e->n = n_envs;
@@ -789,21 +836,16 @@ int kp1_create(const kp1_config* cfg, int32_t n_envs, int32_t device, int32_t re
   KP1_ALLOC(e->dev_cfg, ((real_type == KP1_REAL_F64 ? sizeof(DevCfg<double>) : sizeof(DevCfg<float>)) + KP1_WARM_BYTES - 1) / KP1_WARM_BYTES * KP1_WARM_BYTES);
   KP1_ALLOC(e->dev_smp, sizeof(DevSampler));
 #undef KP1_ALLOC
-  int rc = upload_cfg(e);
+  rc = upload_cfg(e);
   if (rc == KP1_OK) rc = seed_streams(e, seed0, first_env_id);
+  if (rc == KP1_OK)
+    rc = with_real(real_type, [&](auto real) {
+      using R = decltype(real);
+      return launch_env(kp1_init_kernel<R>, e->n, ENV_BLOCK, 0, e->stream, state_of<R>(e), (const DevCfg<R>*)e->dev_cfg);
+    });
   if (rc != KP1_OK) {
     cleanup();
     return rc;
-  }
-  const int block = block_for(e->n);
-  const dim3 grid((unsigned)((e->n + block - 1) / block));
-  if (real_type == KP1_REAL_F64)
-    hipLaunchKernelGGL(kp1_init_kernel<double>, grid, dim3(block), 0, e->stream, state_of<double>(e), (const DevCfg<double>*)e->dev_cfg);
-  else
-    hipLaunchKernelGGL(kp1_init_kernel<float>, grid, dim3(block), 0, e->stream, state_of<float>(e), (const DevCfg<float>*)e->dev_cfg);
-  if (hipGetLastError() != hipSuccess) {
-    cleanup();
-    return fail(KP1_ERR_NO_DEVICE, "init kernel launch failed");
   }
   *out = e;
   return KP1_OK;
@@ -958,50 +1000,35 @@ int kp1_reset(kp1_env* e, const uint8_t* mask_dev, const kp1_reset_opts* opts, f
       if (opts->policy_mode != KP1_MODE_APPROACH && opts->policy_mode != KP1_MODE_DOCK) return fail(KP1_ERR_INVALID, "Unsupported policy mode");
       mode = opts->policy_mode;
     }
-    const bool any = opts->initial_q || opts->initial_dq || opts->initial_prev_action || opts->goal_q || opts->goal_pose6;
-    if (any) {
-      int rc = ensure_scratch(e);
+    const double* const src[5] = {opts->initial_q, opts->initial_dq, opts->initial_prev_action, opts->goal_q, opts->goal_pose6};
+    if (src[0] || src[1] || src[2] || src[3] || src[4]) {
+      const double* dev[5];
+      const int rc = upload_opt_rows(e, src, dev);
       if (rc != KP1_OK) return rc;
-      const size_t n = (size_t)e->n;
-      double* base = e->opt_scratch;
-      struct Item { const double* src; const double** dst; int w; int flag; } items[5] = {
-          {opts->initial_q, &d.initial_q, NJ, OPT_INITIAL_Q}, {opts->initial_dq, &d.initial_dq, NJ, OPT_INITIAL_DQ},
-          {opts->initial_prev_action, &d.initial_prev_action, NJ, OPT_INITIAL_PREV_ACTION},
-          {opts->goal_q, &d.goal_q, NJ, OPT_GOAL_Q}, {opts->goal_pose6, &d.goal_pose6, 6, OPT_GOAL_POSE6}};
-      for (auto& it : items) {
-        if (it.src) {
-          HIP_TRY(hipMemcpyAsync(base, it.src, sizeof(double) * n * it.w, hipMemcpyHostToDevice, e->stream));
-          *it.dst = base;
-          d.flags |= it.flag;
-        }
-        base += n * it.w;
-      }
-      HIP_TRY(hipStreamSynchronize(e->stream));  // host source buffers are the caller's
+      const int flag[5] = {OPT_INITIAL_Q, OPT_INITIAL_DQ, OPT_INITIAL_PREV_ACTION, OPT_GOAL_Q, OPT_GOAL_POSE6};
+      d = {dev[0], dev[1], dev[2], dev[3], dev[4], 0};
+      for (int k = 0; k < 5; ++k)
+        if (dev[k]) d.flags |= flag[k];
     }
   }
   e->mode = mode;
-  return e->real_type == KP1_REAL_F64 ? launch_reset<double>(e, mask_dev, d, mode, obs_dev) : launch_reset<float>(e, mask_dev, d, mode, obs_dev);
+  return with_real(e->real_type, [&](auto real) { return launch_reset<decltype(real)>(e, mask_dev, d, mode, obs_dev); });
 }
 
 int kp1_step(kp1_env* e, const void* actions_dev, float* obs_dev, void* reward_dev, uint8_t* done_dev, float* terminal_obs_dev,
              int32_t auto_reset) {
   if (!e || !actions_dev || !obs_dev || !reward_dev || !done_dev) return fail(KP1_ERR_INVALID, "NULL buffer passed to kp1_step");
   HIP_TRY(hipSetDevice(e->device));
-  return e->real_type == KP1_REAL_F64 ? launch_step<double>(e, actions_dev, obs_dev, reward_dev, done_dev, terminal_obs_dev, auto_reset)
-                                      : launch_step<float>(e, actions_dev, obs_dev, reward_dev, done_dev, terminal_obs_dev, auto_reset);
+  return with_real(e->real_type, [&](auto real) { return launch_step<decltype(real)>(e, actions_dev, obs_dev, reward_dev, done_dev, terminal_obs_dev, auto_reset); });
 }
 
 int kp1_observe(kp1_env* e, float* obs_dev) {
   if (!e || !obs_dev) return fail(KP1_ERR_INVALID, "NULL argument");
   HIP_TRY(hipSetDevice(e->device));
-  const int block = block_for(e->n);
-  const dim3 grid((unsigned)((e->n + block - 1) / block));
-  if (e->real_type == KP1_REAL_F64)
-    hipLaunchKernelGGL(kp1_observe_kernel<double>, grid, dim3(block), 0, e->stream, state_of<double>(e), (const DevCfg<double>*)e->dev_cfg, e->mode, obs_dev, e->obs_stride);
-  else
-    hipLaunchKernelGGL(kp1_observe_kernel<float>, grid, dim3(block), 0, e->stream, state_of<float>(e), (const DevCfg<float>*)e->dev_cfg, e->mode, obs_dev, e->obs_stride);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return with_real(e->real_type, [&](auto real) {
+    using R = decltype(real);
+    return launch_env(kp1_observe_kernel<R>, e->n, ENV_BLOCK, 0, e->stream, state_of<R>(e), (const DevCfg<R>*)e->dev_cfg, e->mode, obs_dev, e->obs_stride);
+  });
 }
 
 int kp1_get_info(kp1_env* e, kp1_info_view* v) {
@@ -1044,15 +1071,11 @@ int kp1_eval_accumulate(kp1_env* e, const kp1_eval_buffers* b, const double* act
   const bool track = ready_thresholds != nullptr;
   const double t0 = track ? ready_thresholds[0] : 0.0, t1 = track ? ready_thresholds[1] : 0.0, t2 = track ? ready_thresholds[2] : 0.0,
                t3 = track ? ready_thresholds[3] : 0.0;
-  const dim3 grid((unsigned)((e->n + 255) / 256));
-  if (e->real_type == KP1_REAL_F64)
-    hipLaunchKernelGGL(eval_accumulate_kernel<double>, grid, dim3(256), 0, st, (const double*)e->real, e->n, *b, action_norm, done, active, step, track, t0, t1,
-                       t2, t3, handoff_confirm_steps);
-  else
-    hipLaunchKernelGGL(eval_accumulate_kernel<float>, grid, dim3(256), 0, st, (const float*)e->real, e->n, *b, action_norm, done, active, step, track, t0, t1, t2,
-                       t3, handoff_confirm_steps);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return with_real(e->real_type, [&](auto real) {
+    using R = decltype(real);
+    return launch_env(eval_accumulate_kernel<R>, e->n, UTIL_BLOCK, 0, st, (const R*)e->real, e->n, *b, action_norm, done, active, step, track, t0, t1, t2, t3,
+                      handoff_confirm_steps);
+  });
 }
 
 int kp1_enable_reward_components(kp1_env* e, int32_t enable) {
@@ -1113,23 +1136,17 @@ const char* kp1_component_name(int32_t mode, int32_t index) {
 int kp1_get_state(kp1_env* e, double* q, double* dq, double* prev_action, double* goal_q, double* goal_pose6) {
   if (!e) return fail(KP1_ERR_INVALID, "env is NULL");
   HIP_TRY(hipSetDevice(e->device));
-  int rc = ensure_scratch(e);
+  OptScratch s;
+  int rc = ensure_scratch(e, &s);
+  if (rc == KP1_OK)
+    rc = with_real(e->real_type, [&](auto real) {
+      using R = decltype(real);
+      return launch_env(kp1_get_state_kernel<R>, e->n, ENV_BLOCK, 0, e->stream, state_of<R>(e), s.dev[0], s.dev[1], s.dev[2], s.dev[3], s.dev[4]);
+    });
   if (rc != KP1_OK) return rc;
-  const size_t n = (size_t)e->n;
-  double* b = e->opt_scratch;
-  double *dq_q = b, *dq_dq = b + n * NJ, *dq_pa = b + 2 * n * NJ, *dq_gq = b + 3 * n * NJ, *dq_gp = b + 4 * n * NJ;
-  const int block = block_for(e->n);
-  const dim3 grid((unsigned)((e->n + block - 1) / block));
-  if (e->real_type == KP1_REAL_F64)
-    hipLaunchKernelGGL(kp1_get_state_kernel<double>, grid, dim3(block), 0, e->stream, state_of<double>(e), dq_q, dq_dq, dq_pa, dq_gq, dq_gp);
-  else
-    hipLaunchKernelGGL(kp1_get_state_kernel<float>, grid, dim3(block), 0, e->stream, state_of<float>(e), dq_q, dq_dq, dq_pa, dq_gq, dq_gp);
-  HIP_TRY(kp1::launch_status());
-  if (q) HIP_TRY(hipMemcpyAsync(q, dq_q, sizeof(double) * n * NJ, hipMemcpyDeviceToHost, e->stream));
-  if (dq) HIP_TRY(hipMemcpyAsync(dq, dq_dq, sizeof(double) * n * NJ, hipMemcpyDeviceToHost, e->stream));
-  if (prev_action) HIP_TRY(hipMemcpyAsync(prev_action, dq_pa, sizeof(double) * n * NJ, hipMemcpyDeviceToHost, e->stream));
-  if (goal_q) HIP_TRY(hipMemcpyAsync(goal_q, dq_gq, sizeof(double) * n * NJ, hipMemcpyDeviceToHost, e->stream));
-  if (goal_pose6) HIP_TRY(hipMemcpyAsync(goal_pose6, dq_gp, sizeof(double) * n * 6, hipMemcpyDeviceToHost, e->stream));
+  double* const dst[5] = {q, dq, prev_action, goal_q, goal_pose6};
+  for (int k = 0; k < 5; ++k)
+    if (dst[k]) HIP_TRY(hipMemcpyAsync(dst[k], s.dev[k], s.bytes[k], hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return KP1_OK;
 }
@@ -1138,70 +1155,26 @@ int kp1_set_state(kp1_env* e, const double* q, const double* dq, const double* p
                   const double* goal_pose6, int32_t capture_entry_metrics) {
   if (!e) return fail(KP1_ERR_INVALID, "env is NULL");
   HIP_TRY(hipSetDevice(e->device));
-  int rc = ensure_scratch(e);
+  const double* const src[5] = {q, dq, prev_action, goal_q, goal_pose6};
+  const double* dev[5];
+  const int rc = upload_opt_rows(e, src, dev);
   if (rc != KP1_OK) return rc;
-  const size_t n = (size_t)e->n;
-  double* b = e->opt_scratch;
-  const double* src[5] = {q, dq, prev_action, goal_q, goal_pose6};
-  const double* dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int k = 0; k < 5; ++k) {
-    const int w = k == 4 ? 6 : NJ;
-    if (src[k]) {
-      HIP_TRY(hipMemcpyAsync(b, src[k], sizeof(double) * n * w, hipMemcpyHostToDevice, e->stream));
-      dev[k] = b;
-    }
-    b += n * NJ;
-  }
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int block = block_for(e->n);
-  const dim3 grid((unsigned)((e->n + block - 1) / block));
-  if (e->real_type == KP1_REAL_F64)
-    hipLaunchKernelGGL(kp1_set_state_kernel<double>, grid, dim3(block), 0, e->stream, state_of<double>(e), (const DevCfg<double>*)e->dev_cfg,
-                       dev[0], dev[1], dev[2], dev[3], dev[4], capture_entry_metrics);
-  else
-    hipLaunchKernelGGL(kp1_set_state_kernel<float>, grid, dim3(block), 0, e->stream, state_of<float>(e), (const DevCfg<float>*)e->dev_cfg,
-                       dev[0], dev[1], dev[2], dev[3], dev[4], capture_entry_metrics);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return with_real(e->real_type, [&](auto real) {
+    using R = decltype(real);
+    return launch_env(kp1_set_state_kernel<R>, e->n, ENV_BLOCK, 0, e->stream, state_of<R>(e), (const DevCfg<R>*)e->dev_cfg, dev[0], dev[1], dev[2], dev[3], dev[4],
+                      capture_entry_metrics);
+  });
 }
 
 int kp1_rng_get(kp1_env* e, kp1_rng_state* out) {
   if (!e || !out) return fail(KP1_ERR_INVALID, "NULL argument");
   HIP_TRY(hipSetDevice(e->device));
-  const size_t n = (size_t)e->n;
-  std::vector<uint64_t> r64(4 * n);
-  std::vector<uint32_t> r32(2 * n);
-  HIP_TRY(hipMemcpyAsync(r64.data(), e->rng64, r64.size() * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(r32.data(), e->rng32, r32.size() * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  for (size_t i = 0; i < n; ++i) {
-    out[i].state_hi = r64[0 * n + i];
-    out[i].state_lo = r64[1 * n + i];
-    out[i].inc_hi = r64[2 * n + i];
-    out[i].inc_lo = r64[3 * n + i];
-    out[i].has_uint32 = r32[0 * n + i];
-    out[i].uinteger = r32[1 * n + i];
-  }
-  return KP1_OK;
+  return download_rng_planes(e->rng64, e->rng32, out, (size_t)e->n, e->stream);
 }
 int kp1_rng_set(kp1_env* e, const kp1_rng_state* in) {
   if (!e || !in) return fail(KP1_ERR_INVALID, "NULL argument");
   HIP_TRY(hipSetDevice(e->device));
-  const size_t n = (size_t)e->n;
-  std::vector<uint64_t> r64(4 * n);
-  std::vector<uint32_t> r32(2 * n);
-  for (size_t i = 0; i < n; ++i) {
-    r64[0 * n + i] = in[i].state_hi;
-    r64[1 * n + i] = in[i].state_lo;
-    r64[2 * n + i] = in[i].inc_hi;
-    r64[3 * n + i] = in[i].inc_lo;
-    r32[0 * n + i] = in[i].has_uint32;
-    r32[1 * n + i] = in[i].uinteger;
-  }
-  HIP_TRY(hipMemcpyAsync(e->rng64, r64.data(), r64.size() * 8, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->rng32, r32.data(), r32.size() * 4, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return KP1_OK;
+  return upload_rng_planes(e->rng64, e->rng32, in, (size_t)e->n, e->stream);
 }
 
 static int state_copy(kp1_env* e, bool save) {
@@ -1239,25 +1212,22 @@ int kp1_debug_env_trace(unsigned long long* out, int clear) {
 int kp1_fk_pose6(int32_t device, int32_t real_type, const void* q_dev, void* pose6_dev, int64_t n, void* stream) {
   if (!q_dev || !pose6_dev || n < 0) return fail(KP1_ERR_INVALID, "bad argument");
   if (n == 0) return KP1_OK;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(KP1_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-  HIP_TRY(hipSetDevice(device));
-  const int block = 256;
-  const dim3 grid((unsigned)((n + block - 1) / block));
-  void* dfk = nullptr;
-  if (real_type != KP1_REAL_F64 && real_type != KP1_REAL_F32) return fail(KP1_ERR_INVALID, "real_type must be KP1_REAL_F32 or KP1_REAL_F64");
+  int rc = use_device(device);
+  if (rc != KP1_OK) return rc;
   DevFk<double> fk;   // the chain itself is fp64 for both real types; real_type is the type of q and pose6 in memory
   fold_fk<double>(&fk);
-  HIP_TRY(hipMalloc(&dfk, sizeof fk));
-  HIP_TRY(hipMemcpy(dfk, &fk, sizeof fk, hipMemcpyHostToDevice));
-  if (real_type == KP1_REAL_F64)
-    hipLaunchKernelGGL(kp1_fk_kernel<double>, grid, dim3(block), 0, (hipStream_t)stream, (const DevFk<double>*)dfk, (const double*)q_dev, (double*)pose6_dev, n);
-  else
-    hipLaunchKernelGGL(kp1_fk_kernel<float>, grid, dim3(block), 0, (hipStream_t)stream, (const DevFk<double>*)dfk, (const float*)q_dev, (float*)pose6_dev, n);
-  hipError_t le = hipGetLastError();
+  struct DevBuf {   // freed on every return (hipFree waits for the kernel that reads it)
+    void* p = nullptr;
+    ~DevBuf() { (void)hipFree(p); }
+  } dfk;
+  HIP_TRY(hipMalloc(&dfk.p, sizeof fk));
+  HIP_TRY(hipMemcpy(dfk.p, &fk, sizeof fk, hipMemcpyHostToDevice));
+  rc = with_real(real_type, [&](auto real) {
+    using R = decltype(real);
+    return launch_env(kp1_fk_kernel<R>, n, UTIL_BLOCK, 0, (hipStream_t)stream, (const DevFk<double>*)dfk.p, (const R*)q_dev, (R*)pose6_dev, n);
+  });
+  if (rc != KP1_OK) return rc;
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  (void)hipFree(dfk);
-  if (le != hipSuccess) return fail(KP1_ERR_NO_DEVICE, hipGetErrorString(le));
   return KP1_OK;
 }
 
@@ -1265,46 +1235,28 @@ int kp1_pose_error(int32_t device, int32_t real_type, const void* curr_dev, cons
                    void* norms_dev, int64_t n, void* stream) {
   if (!curr_dev || !goal_dev || n < 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_pose_error");
   if (n == 0) return KP1_OK;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(KP1_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-  HIP_TRY(hipSetDevice(device));
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if (real_type == KP1_REAL_F64) {
-    hipLaunchKernelGGL(kp1_pose_error_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (const double*)curr_dev, (const double*)goal_dev,
-                       (double*)pos_err_dev, (double*)ori_err_dev, (double*)norms_dev, n);
-  } else if (real_type == KP1_REAL_F32) {
-    hipLaunchKernelGGL(kp1_pose_error_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)curr_dev, (const float*)goal_dev,
-                       (float*)pos_err_dev, (float*)ori_err_dev, (float*)norms_dev, n);
-  } else {
-    return fail(KP1_ERR_INVALID, "real_type must be KP1_REAL_F32 or KP1_REAL_F64");
-  }
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  const int rc = use_device(device);
+  if (rc != KP1_OK) return rc;
+  return with_real(real_type, [&](auto real) {
+    using R = decltype(real);
+    return launch_env(kp1_pose_error_kernel<R>, n, UTIL_BLOCK, 0, (hipStream_t)stream, (const R*)curr_dev, (const R*)goal_dev, (R*)pos_err_dev, (R*)ori_err_dev,
+                      (R*)norms_dev, n);
+  });
 }
 
 int kp1_joint_utils(int32_t device, int32_t real_type, const kp1_config* cfg, const void* q_dev, const void* dq_dev, void* clipped_dev,
                     void* margin_dev, void* q_norm_dev, void* dq_norm_dev, int64_t n, void* stream) {
   if (!cfg || (!q_dev && !dq_dev) || n < 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_joint_utils");
   if (n == 0) return KP1_OK;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(KP1_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-  HIP_TRY(hipSetDevice(device));
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if (real_type == KP1_REAL_F64) {
-    JointLimitsDev<double> lim;
-    for (int k = 0; k < NJ; ++k) { lim.lower[k] = cfg->joints.lower[k]; lim.upper[k] = cfg->joints.upper[k]; lim.dlim[k] = cfg->joints.delta_limit[k]; }
-    hipLaunchKernelGGL(kp1_joint_utils_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, lim, (const double*)q_dev, (const double*)dq_dev,
-                       (double*)clipped_dev, (double*)margin_dev, (double*)q_norm_dev, (double*)dq_norm_dev, n);
-  } else if (real_type == KP1_REAL_F32) {
-    JointLimitsDev<float> lim;
-    for (int k = 0; k < NJ; ++k) { lim.lower[k] = (float)cfg->joints.lower[k]; lim.upper[k] = (float)cfg->joints.upper[k]; lim.dlim[k] = (float)cfg->joints.delta_limit[k]; }
-    hipLaunchKernelGGL(kp1_joint_utils_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, lim, (const float*)q_dev, (const float*)dq_dev,
-                       (float*)clipped_dev, (float*)margin_dev, (float*)q_norm_dev, (float*)dq_norm_dev, n);
-  } else {
-    return fail(KP1_ERR_INVALID, "real_type must be KP1_REAL_F32 or KP1_REAL_F64");
-  }
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  const int rc = use_device(device);
+  if (rc != KP1_OK) return rc;
+  return with_real(real_type, [&](auto real) {
+    using R = decltype(real);
+    JointLimitsDev<R> lim;
+    for (int k = 0; k < NJ; ++k) { lim.lower[k] = (R)cfg->joints.lower[k]; lim.upper[k] = (R)cfg->joints.upper[k]; lim.dlim[k] = (R)cfg->joints.delta_limit[k]; }
+    return launch_env(kp1_joint_utils_kernel<R>, n, UTIL_BLOCK, 0, (hipStream_t)stream, lim, (const R*)q_dev, (const R*)dq_dev, (R*)clipped_dev, (R*)margin_dev,
+                      (R*)q_norm_dev, (R*)dq_norm_dev, n);
+  });
 }
 
 }  // extern "C"

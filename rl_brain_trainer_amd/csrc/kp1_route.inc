@@ -113,18 +113,22 @@ int route_upload_cfg(kp1_route* r) {
   return KP1_OK;
 }
 
+// what RouteResetArgs<R>, RouteStepArgs<R> and RouteChainArgs<R> have in common: the base env's state and config, the route's, the caller's
+// observation rows
+template <typename R, typename Args>
+void fill_route_args(Args& a, const kp1_route* r, float* obs) {
+  const kp1_env* e = r->base;
+  a.st = state_of<R>(e); a.cfg = (const DevCfg<R>*)e->dev_cfg; a.smp = e->dev_smp; a.rc = r->dev_cfg; a.rt = route_table_of(r); a.rs = route_state_of<R>(r);
+  a.obs = obs; a.obs_dim = kp1_route_obs_dim(r); a.obs_stride = r->obs_stride;
+}
+
 template <typename R>
 int route_launch_reset(kp1_route* r, const uint8_t* mask, const int32_t* ri, const int32_t* si, const double* q0, const double* dq0, const double* pa0,
                        int evaluator_state, float* obs) {
-  kp1_env* e = r->base;
   RouteResetArgs<R> a;
-  a.st = state_of<R>(e); a.cfg = (const DevCfg<R>*)e->dev_cfg; a.smp = e->dev_smp; a.rc = r->dev_cfg; a.rt = route_table_of(r); a.rs = route_state_of<R>(r);
-  a.mask = mask; a.route_index = ri; a.start_index = si; a.initial_q = q0; a.initial_dq = dq0; a.initial_pa = pa0;
-  a.obs = obs; a.obs_dim = r->cfg.include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM; a.obs_stride = r->obs_stride; a.evaluator_state = evaluator_state;
-  const int block = block_for(e->n);
-  hipLaunchKernelGGL(kp1_route_reset_kernel<R>, dim3((unsigned)((e->n + block - 1) / block)), dim3(block), 0, e->stream, a);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  fill_route_args<R>(a, r, obs);
+  a.mask = mask; a.route_index = ri; a.start_index = si; a.initial_q = q0; a.initial_dq = dq0; a.initial_pa = pa0; a.evaluator_state = evaluator_state;
+  return launch_env(kp1_route_reset_kernel<R>, r->n, ENV_BLOCK, 0, r->base->stream, a);
 }
 
 template <typename R>
@@ -138,34 +142,20 @@ int route_launch_step(kp1_route* r, const void* actions, float* obs, void* rewar
   e->obs_stride = saved_stride;
   if (rc != KP1_OK) return rc;
   RouteStepArgs<R> a;
-  a.st = state_of<R>(e); a.cfg = (const DevCfg<R>*)e->dev_cfg; a.smp = e->dev_smp; a.rc = r->dev_cfg; a.rt = route_table_of(r); a.rs = route_state_of<R>(r);
-  a.actions = (const R*)actions; a.base_done = base_done; a.obs = obs; a.reward = (R*)reward; a.done = done; a.terminal_obs = terminal_obs;
-  a.obs_dim = r->cfg.include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM; a.obs_stride = r->obs_stride; a.auto_reset = auto_reset;
-  const int block = block_for(n);
+  fill_route_args<R>(a, r, obs);
+  a.actions = (const R*)actions; a.base_done = base_done; a.reward = (R*)reward; a.done = done; a.terminal_obs = terminal_obs; a.auto_reset = auto_reset;
   // the joint table of the whole route lives in LDS in the env's real type (27 KB at W = 484 in fp64): above the 64 KB a launch gets by
   // default the limit has to be raised explicitly, and kp1_route_create refuses tables that cannot fit the CU's 160 KB at all
   const size_t lds = sizeof(R) * (size_t)r->n_waypoints * NJ;
   if (lds > KP1_ROUTE_MAX_TABLE_LDS_BYTES) return fail(KP1_ERR_INVALID, "route joint table exceeds the LDS budget of kp1_route_nearest_kernel");
   if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kp1_route_nearest_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kp1_route_nearest_kernel<R>, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), lds, e->stream, a.st, a.rt, a.rs.nearest);
-  hipLaunchKernelGGL(kp1_route_step_kernel<R>, dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, e->stream, a);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  // 8 lanes per env; the 32 envs of a 256-lane workgroup share one LDS copy of the table
+  rc = launch_env(kp1_route_nearest_kernel<R>, n * 8, 256, lds, e->stream, a.st, a.rt, a.rs.nearest);
+  return rc != KP1_OK ? rc : launch_env(kp1_route_step_kernel<R>, n, ENV_BLOCK, 0, e->stream, a);
 }
 
 int route_seed_streams(kp1_route* r, uint64_t seed0, uint64_t first_env_id) {
-  const int64_t n = r->base->n;
-  std::vector<uint64_t> r64(4 * (size_t)n);
-  std::vector<uint32_t> r32(2 * (size_t)n, 0u);
-  for (int64_t i = 0; i < n; ++i) {
-    kp1_rng_state s;
-    pcg64_seed(seed0 + first_env_id + (uint64_t)i, &s);
-    r64[0 * n + i] = s.state_hi; r64[1 * n + i] = s.state_lo; r64[2 * n + i] = s.inc_hi; r64[3 * n + i] = s.inc_lo;
-  }
-  HIP_TRY(hipMemcpyAsync(r->rng64, r64.data(), r64.size() * 8, hipMemcpyHostToDevice, r->base->stream));
-  HIP_TRY(hipMemcpyAsync(r->rng32, r32.data(), r32.size() * 4, hipMemcpyHostToDevice, r->base->stream));
-  HIP_TRY(hipStreamSynchronize(r->base->stream));
-  return KP1_OK;
+  return seed_planes_by(r->rng64, r->rng32, r->n, r->base->stream, [=](int64_t i) { return seed0 + first_env_id + (uint64_t)i; });
 }
 
 }  // namespace
@@ -576,20 +566,7 @@ int kp1_route_create_population(kp1_env* base, const kp1_route_config* cfg, cons
   rc = route_upload_cfg(r);
   // both streams of env i in block k <- default_rng(seeds[k] + i), the base env's (reset(seed=) semantics of kp1_route_seed) and the wrapper's
   if (rc == KP1_OK) rc = kp1_seed_blocks(base, seeds, replicas, npb);
-  if (rc == KP1_OK) {
-    const int64_t n = base->n;
-    std::vector<uint64_t> r64(4 * (size_t)n);
-    std::vector<uint32_t> r32(2 * (size_t)n, 0u);
-    for (int64_t i = 0; i < n; ++i) {
-      kp1_rng_state st;
-      pcg64_seed(seeds[i / npb] + (uint64_t)(i % npb), &st);
-      r64[0 * n + i] = st.state_hi; r64[1 * n + i] = st.state_lo; r64[2 * n + i] = st.inc_hi; r64[3 * n + i] = st.inc_lo;
-    }
-    if (hipMemcpyAsync(r->rng64, r64.data(), r64.size() * 8, hipMemcpyHostToDevice, base->stream) != hipSuccess ||
-        hipMemcpyAsync(r->rng32, r32.data(), r32.size() * 4, hipMemcpyHostToDevice, base->stream) != hipSuccess ||
-        hipStreamSynchronize(base->stream) != hipSuccess)
-      rc = fail(KP1_ERR_RUNTIME, "kp1_route_create_population: seeding the wrapper streams failed");
-  }
+  if (rc == KP1_OK) rc = seed_planes_by(r->rng64, r->rng32, r->n, base->stream, [=](int64_t i) { return seeds[i / npb] + (uint64_t)(i % npb); });
   if (rc != KP1_OK) { kp1_route_destroy(r); return rc; }
   *out = r;
   return KP1_OK;
@@ -622,15 +599,13 @@ int kp1_route_reset(kp1_route* r, const uint8_t* mask, const kp1_route_reset_opt
     ri = opts->route_index; si = opts->start_route_index; q0 = opts->initial_q; dq0 = opts->initial_dq; pa0 = opts->initial_prev_action;
     ev = opts->evaluator_state;
   }
-  return e->real_type == KP1_REAL_F64 ? route_launch_reset<double>(r, mask, ri, si, q0, dq0, pa0, ev, obs)
-                                      : route_launch_reset<float>(r, mask, ri, si, q0, dq0, pa0, ev, obs);
+  return with_real(e->real_type, [&](auto real) { return route_launch_reset<decltype(real)>(r, mask, ri, si, q0, dq0, pa0, ev, obs); });
 }
 
 int kp1_route_step(kp1_route* r, const void* actions, float* obs, void* reward, uint8_t* done, float* terminal_obs, int32_t auto_reset) {
   if (!r || !actions || !obs || !reward || !done) return fail(KP1_ERR_INVALID, "NULL argument to kp1_route_step");
   HIP_TRY(hipSetDevice(r->base->device));
-  return r->base->real_type == KP1_REAL_F64 ? route_launch_step<double>(r, actions, obs, reward, done, terminal_obs, auto_reset)
-                                            : route_launch_step<float>(r, actions, obs, reward, done, terminal_obs, auto_reset);
+  return with_real(r->base->real_type, [&](auto real) { return route_launch_step<decltype(real)>(r, actions, obs, reward, done, terminal_obs, auto_reset); });
 }
 
 int kp1_route_get_info(kp1_route* r, kp1_route_info_view* out) {
@@ -657,31 +632,13 @@ int kp1_route_get_reward_components(kp1_route* r, const void** comps) {
 
 int kp1_route_rng_get(kp1_route* r, kp1_rng_state* out_host) {
   if (!r || !out_host) return fail(KP1_ERR_INVALID, "NULL argument");
-  const int64_t n = r->base->n;
-  std::vector<uint64_t> r64(4 * (size_t)n);
-  std::vector<uint32_t> r32(2 * (size_t)n);
-  HIP_TRY(hipMemcpyAsync(r64.data(), r->rng64, r64.size() * 8, hipMemcpyDeviceToHost, r->base->stream));
-  HIP_TRY(hipMemcpyAsync(r32.data(), r->rng32, r32.size() * 4, hipMemcpyDeviceToHost, r->base->stream));
-  HIP_TRY(hipStreamSynchronize(r->base->stream));
-  for (int64_t i = 0; i < n; ++i) {
-    out_host[i].state_hi = r64[0 * n + i]; out_host[i].state_lo = r64[1 * n + i]; out_host[i].inc_hi = r64[2 * n + i]; out_host[i].inc_lo = r64[3 * n + i];
-    out_host[i].has_uint32 = r32[0 * n + i]; out_host[i].uinteger = r32[1 * n + i];
-  }
-  return KP1_OK;
+  HIP_TRY(hipSetDevice(r->base->device));
+  return download_rng_planes(r->rng64, r->rng32, out_host, (size_t)r->n, r->base->stream);
 }
 int kp1_route_rng_set(kp1_route* r, const kp1_rng_state* in_host) {
   if (!r || !in_host) return fail(KP1_ERR_INVALID, "NULL argument");
-  const int64_t n = r->base->n;
-  std::vector<uint64_t> r64(4 * (size_t)n);
-  std::vector<uint32_t> r32(2 * (size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    r64[0 * n + i] = in_host[i].state_hi; r64[1 * n + i] = in_host[i].state_lo; r64[2 * n + i] = in_host[i].inc_hi; r64[3 * n + i] = in_host[i].inc_lo;
-    r32[0 * n + i] = in_host[i].has_uint32; r32[1 * n + i] = in_host[i].uinteger;
-  }
-  HIP_TRY(hipMemcpyAsync(r->rng64, r64.data(), r64.size() * 8, hipMemcpyHostToDevice, r->base->stream));
-  HIP_TRY(hipMemcpyAsync(r->rng32, r32.data(), r32.size() * 4, hipMemcpyHostToDevice, r->base->stream));
-  HIP_TRY(hipStreamSynchronize(r->base->stream));
-  return KP1_OK;
+  HIP_TRY(hipSetDevice(r->base->device));
+  return upload_rng_planes(r->rng64, r->rng32, in_host, (size_t)r->n, r->base->stream);
 }
 
 int kp1_route_curriculum_create(kp1_route* r, const int32_t* prefix_end_index, int32_t n_stages, double promotion_success_rate,
@@ -752,10 +709,8 @@ int kp1_route_curriculum_observe(kp1_route* r, kp1_route_curriculum_state* st_de
   if (!r || !st_dev || !dones) return fail(KP1_ERR_INVALID, "bad argument to kp1_route_curriculum_observe");
   if (r->n_replicas != 1) return fail(KP1_ERR_UNSUPPORTED, "a population route handle takes kp1_route_curriculum_observe_population");
   const int64_t n = r->base->n;
-  hipLaunchKernelGGL(route_curriculum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, r->dev_cfg, dones, r->bytes, r->bytes + 3 * n, r->bytes + 2 * n,
-                     (int)n, (int)steps_per_call);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch_env(route_curriculum_kernel, 64, 64, 0, (hipStream_t)stream, st_dev, r->dev_cfg, dones, r->bytes, r->bytes + 3 * n, r->bytes + 2 * n, (int)n,
+                    (int)steps_per_call);
 }
 
 int kp1_route_episode_records(kp1_route* r, const uint8_t* dones, uint8_t* records, void* stream) {
@@ -763,10 +718,7 @@ int kp1_route_episode_records(kp1_route* r, const uint8_t* dones, uint8_t* recor
   const int64_t n = r->base->n;
   if (n > (int64_t)(UINT32_MAX / 4u)) return fail(KP1_ERR_INVALID, "kp1_route_episode_records: N too large for 32-bit plane offsets");
   const int words_ok = (n % 4 == 0) && ((reinterpret_cast<uintptr_t>(dones) | reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(r->bytes)) & 3) == 0;
-  hipLaunchKernelGGL(route_episode_records_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, dones, r->bytes, records,
-                     (unsigned int)n, words_ok);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch_env(route_episode_records_kernel, (n + 3) / 4, UTIL_BLOCK, 0, (hipStream_t)stream, dones, r->bytes, records, (unsigned int)n, words_ok);   // 4 envs per lane
 }
 
 int kp1_route_curriculum_observe_chunk(kp1_route* r, kp1_route_curriculum_state* st_dev, const uint8_t* records, int32_t n_local, int32_t chunk_steps,
@@ -774,10 +726,7 @@ int kp1_route_curriculum_observe_chunk(kp1_route* r, kp1_route_curriculum_state*
   if (!r || !st_dev || !records || n_local <= 0 || chunk_steps <= 0 || world <= 0)
     return fail(KP1_ERR_INVALID, "bad argument to kp1_route_curriculum_observe_chunk");
   if (r->n_replicas != 1) return fail(KP1_ERR_UNSUPPORTED, "the data-parallel chunk tracker has no population form");
-  hipLaunchKernelGGL(route_curriculum_chunk_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, r->dev_cfg, records, (int)n_local, (int)chunk_steps,
-                     (int)world);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch_env(route_curriculum_chunk_kernel, 64, 64, 0, (hipStream_t)stream, st_dev, r->dev_cfg, records, (int)n_local, (int)chunk_steps, (int)world);
 }
 
 int kp1_route_curriculum_read(kp1_route* r, const kp1_route_curriculum_state* st_dev, kp1_route_curriculum_state* out_host, void* stream) {
@@ -795,10 +744,8 @@ int kp1_route_curriculum_read(kp1_route* r, const kp1_route_curriculum_state* st
 int kp1_route_curriculum_observe_population(kp1_route* r, kp1_route_curriculum_state* st_dev, const uint8_t* dones, int32_t steps_per_call, void* stream) {
   if (!r || !st_dev || !dones) return fail(KP1_ERR_INVALID, "bad argument to kp1_route_curriculum_observe_population");
   const int64_t n = r->base->n;
-  hipLaunchKernelGGL(route_curriculum_kernel, dim3((unsigned)r->n_replicas), dim3(64), 0, (hipStream_t)stream, st_dev, r->dev_cfg, dones, r->bytes,
-                     r->bytes + 3 * n, r->bytes + 2 * n, (int)r->n_per_replica, (int)steps_per_call);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch_env(route_curriculum_kernel, 64 * r->n_replicas, 64, 0, (hipStream_t)stream, st_dev, r->dev_cfg, dones, r->bytes, r->bytes + 3 * n,
+                    r->bytes + 2 * n, (int)r->n_per_replica, (int)steps_per_call);   // one wave per tracker
 }
 
 int kp1_route_curriculum_read_replica(kp1_route* r, const kp1_route_curriculum_state* st_dev, int32_t replica, kp1_route_curriculum_state* out_host,
@@ -936,9 +883,7 @@ int kp1_route_chain_begin(kp1_route* r, kp1_route_chain* c, float* obs) {
   HIP_TRY(hipSetDevice(e->device));
   const int rc = route_launch_reset<float>(r, nullptr, c->d.start, c->zeros, c->init_q, nullptr, nullptr, 1, obs);
   if (rc != KP1_OK) return rc;
-  hipLaunchKernelGGL(kp1_route_chain_begin_kernel<float>, dim3((unsigned)((e->n + 63) / 64)), dim3(64), 0, e->stream, state_of<float>(e), c->d);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch_env(kp1_route_chain_begin_kernel<float>, e->n, ENV_BLOCK, 0, e->stream, state_of<float>(e), c->d);
 }
 
 int kp1_route_chain_step(kp1_route* r, kp1_route_chain* c, const float* actions, float* obs, float* reward, uint8_t* done, int32_t* tags) {
@@ -951,12 +896,9 @@ int kp1_route_chain_step(kp1_route* r, kp1_route_chain* c, const float* actions,
   if (rc != KP1_OK) return rc;
   HIP_TRY(hipMemsetAsync(c->d.n_alive, 0, sizeof(int32_t), e->stream));
   RouteChainArgs<float> a;
-  a.st = state_of<float>(e); a.cfg = (const DevCfg<float>*)e->dev_cfg; a.smp = e->dev_smp; a.rc = r->dev_cfg; a.rt = route_table_of(r);
-  a.rs = route_state_of<float>(r); a.ch = c->d; a.done = done; a.obs = obs; a.tags = tags;
-  a.obs_dim = r->cfg.include_route_keys ? KP1_ROUTE_OBS_DIM : KP1_OBS_DIM; a.obs_stride = r->obs_stride;
-  hipLaunchKernelGGL(kp1_route_chain_kernel<float>, dim3((unsigned)((e->n + 63) / 64)), dim3(64), 0, e->stream, a);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  fill_route_args<float>(a, r, obs);
+  a.ch = c->d; a.done = done; a.tags = tags;
+  return launch_env(kp1_route_chain_kernel<float>, e->n, ENV_BLOCK, 0, e->stream, a);
 }
 
 int kp1_route_chain_get_view(kp1_route_chain* c, kp1_route_chain_view* out) {

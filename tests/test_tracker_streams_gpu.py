@@ -213,7 +213,7 @@ def _assert_applied(config, record, where) -> None:
         assert list(getattr(c.dock_reset, key)[:]) == list(getattr(record, key)[:]), (where, key)
 
 
-def _dock_single(name: str, offset: int) -> None:
+def _dock_single(name: str, offset: int, real: str = "f32") -> None:
     from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv
 
     spec = ts.fixture()[name]["spec"]
@@ -222,7 +222,7 @@ def _dock_single(name: str, offset: int) -> None:
     steps = _steps(spec)
     table = _dock_table(spec)
     assert len({(t.dock_residual_action_limit, t.close_bucket_probability) for t in table}) == len(table)     # every stage tells
-    env = ArmKinematicVecEnv(load_golden_config(DOCK_CFG), 8, seed=3)       # the tracker takes n_local per call: any N on an 8-env handle
+    env = ArmKinematicVecEnv(load_golden_config(DOCK_CFG), 8, seed=3, real=real)       # the tracker takes n_local per call: any N on an 8-env handle
     cb = ft.DockReverseCurriculum(stages=spec["params"]["stages"], window_episodes=spec["params"]["window"])
     cb.attach(env)
     before = _frozen(cb.read())
@@ -257,6 +257,11 @@ def test_dock_observe(name, offset):
 def test_dock_observe_chunk(name):
     """world > 1 and chunk_steps > 1: step by step, rank by rank; the clock advances once per env step"""
     _dock_single(name, 0)
+
+
+def test_dock_observe_f64_handle():
+    """the tracker kernel's fp64 form (it writes a promotion into a DevCfg<double>): the same stream, the same records"""
+    _dock_single("dock_obs_65", 0, real="f64")
 
 
 @pytest.mark.parametrize("names", [("dock_pop_12_a", "dock_pop_12_b", "dock_quiet_12_long"), ("dock_pop_65_a", "dock_pop_65_b", "dock_pop_65_c")],
