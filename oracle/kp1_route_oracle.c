@@ -388,6 +388,21 @@ void kp1o_route_env_step(kp1o_route_env* e, const double action[7], float* obs, 
   out->completed_waypoints = e->completed_waypoints;
   out->q_error_norm = q_error_norm;
   out->nearest_route_q_distance = nearest;
+  {  /* the same expressions kp1o_route_reward forms, for the tie classification of the fp32 comparison */
+    double pe[3], oe[3];
+    kp1o_pose_error(prev_pose6, goal_pose6, pe, oe);
+    const double prev_pos = norm3(pe), prev_ori = norm3(oe);
+    kp1o_pose_error(curr_pose6, goal_pose6, pe, oe);
+    out->error_growth[0] = q_error_norm - prev_q_error_norm;
+    out->error_growth[1] = norm3(pe) - prev_pos;
+    out->error_growth[2] = norm3(oe) - prev_ori;
+    out->action_norm = action_norm;
+    out->dq_norm = dq_norm;
+    out->tangent_norm = norm7(tangent);
+    out->base_terminated = so.terminated;
+    out->base_success = so.success;
+    out->base_invalid = so.invalid;
+  }
   memcpy(e->prev_q, curr_q, sizeof e->prev_q);
   memcpy(e->prev_dq, curr_dq, sizeof e->prev_dq);
   if (obs) augment(e, base_obs, obs);

@@ -55,6 +55,11 @@ typedef struct kp1o_route_step_out {
   int terminated, truncated, success, route_ready, ready_streak, waypoint_success, route_regression, orientation_hit, route_index, completed_waypoints;
   double q_error_norm, nearest_route_q_distance;
   double components[KP1_ROUTE_N_COMPONENTS];
+  /* what the fp32 tie classification reads (tests/route_lockstep.py): curr - prev of (q, position, orientation) error, the gated norms,
+   * and the base env's own verdict before the wrapper overrides it */
+  double error_growth[3];
+  double action_norm, dq_norm, tangent_norm;
+  int base_terminated, base_success, base_invalid;
 } kp1o_route_step_out;
 
 void kp1o_route_env_init(kp1o_route_env* e, const kp1_config* base_cfg, const kp1_route_config* cfg, const kp1o_route* route);

@@ -22,7 +22,9 @@ class RouteSample(C.Structure):
 class RouteStepOut(C.Structure):
     _fields_ = [("reward", C.c_double)] + [(n, C.c_int) for n in ("terminated", "truncated", "success", "route_ready", "ready_streak", "waypoint_success",
                                                                      "route_regression", "orientation_hit", "route_index", "completed_waypoints")] + \
-               [("q_error_norm", C.c_double), ("nearest_route_q_distance", C.c_double), ("components", C.c_double * N_COMP)]
+               [("q_error_norm", C.c_double), ("nearest_route_q_distance", C.c_double), ("components", C.c_double * N_COMP),
+                ("error_growth", C.c_double * 3), ("action_norm", C.c_double), ("dq_norm", C.c_double), ("tangent_norm", C.c_double),
+                ("base_terminated", C.c_int), ("base_success", C.c_int), ("base_invalid", C.c_int)]
 
 
 _bound = False

@@ -56,7 +56,7 @@ from conftest import GOLDEN
 from oracle import oracle as orc
 from rl_brain_trainer_amd import config as kcfg
 from test_env_parity_gpu import _two_float
-from test_route_env_f32_gpu import _and_ambiguous
+from route_lockstep import _and_ambiguous
 
 N_ENVS = 200
 SEED = 4242

@@ -17,8 +17,6 @@ Observed on the MI355X: every error 5x or more below its bound (the test docstri
 """
 from __future__ import annotations
 
-import json
-
 import numpy as np
 import pytest
 import torch
@@ -28,24 +26,13 @@ from oracle import route_oracle as ro
 from rl_brain_trainer_amd import config as kcfg
 from rl_brain_trainer_amd import route_config as rcfg
 from rl_brain_trainer_amd.route_env import RoutePopulationVecEnv, RouteVecEnv
+from route_lockstep import (ERR_TOL, OBS_TOL, RESET_OBS_TOL, OracleBatch, Ties, Worst, _and_ambiguous, _check_resets, _check_step, _policy)  # noqa: F401
 from test_env_parity_gpu import _two_float
 from test_route_env_gpu import _cfg_dict, _golden_words
 
 pytestmark = pytest.mark.gpu
 
-# ---- tolerances of the fp32 handle (q is stored as a two-float pair, the kinematic chain is fp64; q, poses and all route arithmetic
-# are fp32 in the route kernels)
-# An fp32 value |x| < 4 is rounded by at most 2^-22 / 2 = 2.4e-7.  q error = ||goal - q|| over 7 joints with both operands rounded:
-# <= sqrt(7) * 2 * 2.4e-7 = 1.3e-6 in the worst case, ~3e-7 typically; position error from fp32 poses (|x| < 1.5 m): ~1e-7;
-# orientation error from fp32 angles (|a| <= pi): <= 2 * 2.4e-7 per axis, ~5e-7 on the norm.
-DELTA_GATE = 2e-6    # a gated quantity this close to its threshold is a tie: >= 1.5x the worst q-error bound, 4x the orientation one
-DELTA_DIFF = 4e-6    # curr - prev of two such errors (no_progress, regression): two independent roundings, 2 x DELTA_GATE
-OBS_TOL = 2e-5       # route_q_error = (goal - q) / dl with dl = 0.024 on joint 1 (|q| up to pi): 2 * 2.4e-7 / 0.024 = 2e-5 worst case
-RESET_OBS_TOL = 2e-6  # at a reset q is the two-float rounding of the fp64 draw and the route keys index the fp64 table: fp32 output rounding
-ERR_TOL = 1e-5       # q_error_norm, nearest_route_q_distance, components 13-15: north_star's fp32 pose bar
-COMP_TOL = 2e-5      # components 0-12: largest weight 8.5 (ee_orientation_progress) x (2 x 5e-7 orientation noise) = 8.5e-6, 2.3x margin
-REWARD_TOL = 5e-5    # sum of 13 components, each within COMP_TOL but in practice one or two dominate: 2.5 x COMP_TOL
-
+# the tolerances of the fp32 handle, the tie classes and the step check live in route_lockstep.py, next to the randomised-config cases
 CONFIGS = [("seq_prefix120", "route_curriculum_prefix120_routeobs_sequence2", 120),
            ("seq_prefix170", "route_curriculum_prefix170_routeobs_sequence2", 170),   # BASELINE configs[4]
            ("seq_prefix20", "route_curriculum_prefix20_sequence2", 20),
@@ -61,77 +48,6 @@ def _configs(cfg_name: str, max_index: int) -> tuple[kcfg.EnvConfig, rcfg.RouteC
     """(base env config, route config for the device, an independent copy for the oracle)"""
     cfgd = _cfg_dict(cfg_name)
     return kcfg.to_env_config(cfgd), rcfg.route_config_from_dict(cfgd, max_route_index=max_index), rcfg.route_config_from_dict(cfgd, max_route_index=max_index)
-
-
-def _and_ambiguous(vals: np.ndarray, thrs: np.ndarray, delta: float) -> np.ndarray:
-    """all(vals[j] <= thrs[j]) evaluated on fp32-noisy vals ([m, N]): can the two precisions disagree?  Yes iff some term lies within
-    delta of its threshold and every other term holds."""
-    vals = np.atleast_2d(vals)
-    tied = np.abs(vals - thrs[:, None]) < delta
-    holds = vals <= thrs[:, None]
-    return tied.any(axis=0) & (holds | tied).all(axis=0)
-
-
-class Ties:
-    """The gates of one route config, evaluated on the reference side (fp64)."""
-
-    def __init__(self, base: kcfg.EnvConfig, rc: rcfg.RouteConfig) -> None:
-        w, br, bt = rc.reward, base.c.reward, base.c.termination
-        self.ready_thr = np.array([w.route_ready_q_threshold, w.route_ready_pos_threshold_m, w.route_ready_ori_threshold_rad,
-                                   w.route_ready_action_threshold, w.route_ready_dq_threshold])
-        self.low_motion_thr = 2.0 * np.array([w.route_ready_pos_threshold_m, w.route_ready_ori_threshold_rad])
-        self.ori_hit_thr = float(w.route_ready_ori_threshold_rad)
-        # base env: near-goal (dwell counter -> observation) and success gates on (position, orientation)
-        ori_gate = bool(br.use_orientation_gate)
-        self.base_gates = [np.array([br.near_goal_pos_threshold_m, br.near_goal_ori_threshold_rad if ori_gate else np.inf]),
-                           np.array([bt.success_pos_threshold_m, bt.success_ori_threshold_rad if bt.require_orientation else np.inf])]
-        self.progress_w = np.array([w.q_goal_progress_weight, w.ee_position_progress_weight, w.ee_orientation_progress_weight])
-        assert np.all(self.progress_w != 0.0)   # prev - curr of the three errors is read back from components 0-2
-
-    def of(self, comps: np.ndarray, action: np.ndarray, dq: np.ndarray) -> dict[str, np.ndarray]:
-        """comps [N, 17] fp64 reference components, action / dq [N, 7] fp64 -> bool [N] per tie class"""
-        q_err, pos, ori = comps[:, 13], comps[:, 14], comps[:, 15]
-        act_n, dq_n = np.linalg.norm(action, axis=1), np.linalg.norm(dq, axis=1)
-        ready = _and_ambiguous(np.stack([q_err, pos, ori, act_n, dq_n]), self.ready_thr, DELTA_GATE)
-        base = np.zeros_like(ready)
-        for thr in self.base_gates:
-            base |= _and_ambiguous(np.stack([pos, ori]), thr, DELTA_GATE)
-        growth = -comps[:, :3] / self.progress_w          # curr - prev of q error, position error, orientation error
-        return {"state": ready | base,
-                "low_motion": _and_ambiguous(np.stack([pos, ori]), self.low_motion_thr, DELTA_GATE),
-                "no_progress": _and_ambiguous(-growth.T, np.zeros(3), DELTA_DIFF),   # all(curr >= prev) = all(-(curr - prev) <= 0)
-                "regression": np.abs(growth[:, 0]) < DELTA_DIFF,
-                "ori_hit": np.abs(ori - self.ori_hit_thr) < DELTA_GATE}
-
-
-class Worst:
-    """worst |device - reference| per quantity, for the docstrings and the failure messages"""
-
-    def __init__(self) -> None:
-        self.v: dict[str, float] = {}
-
-    def check(self, key: str, diff, tol: float, ctx) -> None:
-        d = float(np.max(np.abs(diff))) if np.size(diff) else 0.0
-        self.v[key] = max(self.v.get(key, 0.0), d)
-        assert d <= tol, (ctx, key, d, tol)
-
-    def __repr__(self) -> str:
-        return json.dumps({k: float(f"{v:.3g}") for k, v in sorted(self.v.items())})
-
-
-def _check_step(worst: Worst, ctx, tie: dict, comps_dev: np.ndarray, comps_ref: np.ndarray, r_dev, r_ref, q_err_dev, q_err_ref, near_dev, near_ref) -> None:
-    """the continuous outputs of one untainted step (one env or a batch of envs as rows)"""
-    comps_dev, comps_ref = np.atleast_2d(comps_dev), np.atleast_2d(comps_ref)
-    worst.check("q_error_norm", np.asarray(q_err_dev) - q_err_ref, ERR_TOL, ctx)
-    worst.check("nearest_route_q_distance", np.asarray(near_dev) - near_ref, ERR_TOL, ctx)
-    worst.check("components_13_15", comps_dev[:, 13:16] - comps_ref[:, 13:16], ERR_TOL, ctx)
-    worst.check("component_16_route_ready", comps_dev[:, 16] - comps_ref[:, 16], 0.0, ctx)
-    lm, npg = np.atleast_1d(tie["low_motion"]), np.atleast_1d(tie["no_progress"])
-    for k in range(13):
-        skip = lm if k == 6 else (npg if k == 12 else np.zeros_like(lm))
-        worst.check(f"component_{k:02d}", (comps_dev[:, k] - comps_ref[:, k])[~skip], COMP_TOL, (ctx, rcfg.COMPONENT_NAMES[k]))
-    ok = ~(lm | npg)
-    worst.check("reward", (np.atleast_1d(r_dev) - np.atleast_1d(r_ref))[ok], REWARD_TOL, ctx)
 
 
 # ============================================================================== 1. the reference traces on the fp32 handle
@@ -176,7 +92,7 @@ def test_route_env_replays_reference_trace_f32(route_q, name, cfg_name, max_inde
             _, out = ora.step(a64)
             comps_ref = g["components"][row]
             assert np.max(np.abs(np.array(out.components[:]) - comps_ref)) <= 1e-12, ctx   # lockstep oracle = trace
-            tie = ties.of(comps_ref[None], a64[None], ora.base_state()["dq"][None])
+            tie = ties.of(comps_ref[None], a64[None], ora.base_state()["dq"][None], np.array(out.error_growth[:])[None])
             tie = {key: bool(v[0]) for key, v in tie.items()}
             tainted = tainted or tie["state"]
             state_ties += int(tie["state"])
@@ -214,49 +130,6 @@ def test_route_env_replays_reference_trace_f32(route_q, name, cfg_name, max_inde
 
 
 # ============================================================================== 2. lockstep batch vs the fp64 oracle
-def _policy(rng: np.random.Generator, group: np.ndarray, goal: np.ndarray, q: np.ndarray, dl: np.ndarray) -> np.ndarray:
-    """noisy servo toward the current waypoint (70 %), near-zero actions (20 %: ready, dwell and the low-motion bonus), uniform noise (10 %)"""
-    n = q.shape[0]
-    a = np.clip(0.8 * (goal - q) / dl + rng.normal(0, 0.03, (n, 7)), -1, 1)
-    still = group >= 7
-    a[still] = rng.normal(0, 0.01, (int(still.sum()), 7))
-    noise = group == 9
-    a[noise] = rng.uniform(-1, 1, (int(noise.sum()), 7))
-    return a.astype(np.float32)
-
-
-class OracleBatch:
-    """N serial fp64 oracle envs with env i seeded seed + i, as the device handle seeds its streams"""
-
-    def __init__(self, base, rc, route_q, n: int, seed: int) -> None:
-        route = ro.Route(route_q)
-        self.envs = [ro.OracleRouteEnv(base, rc, route) for _ in range(n)]
-        self.obs = np.stack([e.reset(seed=seed + i) for i, e in enumerate(self.envs)])
-
-    def state(self, key: str) -> np.ndarray:
-        return np.stack([e.base_state()[key] for e in self.envs])
-
-    def fields(self, *names: str) -> list[np.ndarray]:
-        return [np.array([e.field(nm) for e in self.envs]) for nm in names]
-
-
-def _check_resets(env: RouteVecEnv, ob: OracleBatch, idx: np.ndarray, dev_obs: np.ndarray, worst: Worst, ctx) -> None:
-    """device state right after a reset of envs idx (initial or inside the step launch) against the oracle after its reset"""
-    if idx.size == 0:
-        return
-    info = env.info()
-    cur, start, mode = ob.fields("current_route_index", "start_route_index", "reset_mode")
-    for key, ref in (("route_index", cur), ("start_route_index", start), ("route_reset_mode", mode)):
-        dev = info[key].cpu().numpy()[idx]
-        assert np.array_equal(dev, ref[idx]), (ctx, key, idx[dev != ref[idx]][:8])
-    assert np.all(info["route_ready_streak"].cpu().numpy()[idx] == 0) and np.all(info["route_completed_waypoints"].cpu().numpy()[idx] == 0), ctx
-    words = env.rng_state()[idx]
-    ref_words = np.stack([ob.envs[i].rng_words() for i in idx])
-    assert np.array_equal(words, ref_words), (ctx, idx[np.any(words != ref_words, axis=1)][:8])
-    assert np.array_equal(env.get_state()["q"][idx], _two_float(ob.state("q")[idx])), ctx
-    worst.check("reset_obs", dev_obs[idx] - ob.obs[idx], RESET_OBS_TOL, ctx)
-
-
 @pytest.mark.parametrize("name,cfg_name,max_index", CONFIGS)
 def test_route_env_f32_lockstep_batch_vs_oracle(route_q, name, cfg_name, max_index):
     """300 fp32 device envs (ragged: not a multiple of the nearest kernel's 32 envs per block nor of the step kernel's block) and 300
@@ -304,7 +177,7 @@ def test_route_env_f32_lockstep_batch_vs_oracle(route_q, name, cfg_name, max_ind
                                                                          "waypoint_success", "route_regression", "orientation_hit", "route_index",
                                                                          "completed_waypoints", "q_error_norm", "nearest_route_q_distance")}
         c_ref = np.array([out.components[:] for out in outs])
-        tie = ties.of(c_ref, a.astype(np.float64), dq)
+        tie = ties.of(c_ref, a.astype(np.float64), dq, np.array([out.error_growth[:] for out in outs]))
         alive &= ~tie["state"]
         step_ties += int(np.sum(alive & (tie["low_motion"] | tie["no_progress"] | tie["regression"] | tie["ori_hit"])))
         s = np.flatnonzero(alive)

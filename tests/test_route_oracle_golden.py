@@ -137,3 +137,60 @@ def test_route_env_traces(route, name, cfg_name, max_index):
             t += 1
     assert worst_r <= 1e-12 and worst_c <= 1e-12, (worst_r, worst_c)
     assert int(g["waypoint_success"].sum()) > 0     # the traces exercise waypoint hand-over / success
+
+
+def test_route_env_config_fuzz_traces():
+    """Every case of route_config_fuzz.npz (randomised route configs, directed route_ready clauses, windows at the end of the route, a
+    repeated waypoint; make_golden_route_config_fuzz.py) replayed on OracleRouteEnv: integers, flags, indices and RNG words exact, reward
+    and components within 1e-12, q within 1e-15, observations (recorded on a subset of the rows) within 1e-9 absolute -- the float32
+    observation is not bit equal between the two: entries of ~1e-16 in fp64 on one side are 0 on the other."""
+    import route_lockstep as rl
+    g = rl.fixture()
+    assert [str(s) for s in g["component_names"]] == rcfg.COMPONENT_NAMES
+    flag = {str(n): k for k, n in enumerate(g["flag_names"])}
+    worst = {"reward": 0.0, "components": 0.0, "q": 0.0, "obs": 0.0}
+    handovers = successes = obs_rows = 0
+    for case in rl.all_cases():
+        cfgd = rl.config_dict(case)
+        base, rc = rl.build_configs(cfgd)
+        env = ro.OracleRouteEnv(base, rc, ro.Route(rl.route_of(case)))
+        assert env.obs_dim == case.obs_dim
+        r0, r1 = int(g["row_start"][case.index]), int(g["row_start"][case.index + 1])
+        k = int(g["reset_start"][case.index])
+        o0, o1 = int(g["obs_start"][case.index]), int(g["obs_start"][case.index + 1])
+        obs_of = {r0 + int(r): j for j, r in enumerate(g["obs_rows"][o0:o1])}
+        obs_table = g[f"obs{case.obs_dim}"]
+        obs_base = sum(int(g["obs_start"][c.index + 1] - g["obs_start"][c.index]) for c in rl.all_cases()[:case.index] if c.obs_dim == case.obs_dim)
+        first = True
+        for row in range(r0, r1):
+            ctx = (case.name, row - r0)
+            f = g["flags"][row]
+            if g["is_reset"][row]:
+                if not first:  # before the first reset the reference's stream is entropy-seeded
+                    assert np.array_equal(env.rng_words(), _golden_words(g["rng_before"][k])), ctx
+                obs = env.reset(seed=case.seed if first else None)
+                first = False
+                assert np.array_equal(env.rng_words(), _golden_words(g["rng_after"][k])), ctx
+                assert env.field("reset_mode") == int(g["reset_mode"][k]) and env.field("start_route_index") == int(g["start_index"][k]), ctx
+                if g["last_index"][k] >= 0:
+                    assert env.field("last_route_index") == int(g["last_index"][k]), ctx
+                assert env.field("current_route_index") == int(f[flag["route_index"]]), ctx
+                k += 1
+            else:
+                obs, out = env.step(g["action"][row].astype(np.float64))
+                worst["reward"] = max(worst["reward"], float(abs(out.reward - g["reward"][row])))
+                worst["components"] = max(worst["components"], float(np.max(np.abs(np.array(out.components[:]) - g["components"][row]))))
+                for key, val in (("terminated", out.terminated), ("truncated", out.truncated), ("success", out.success), ("ready", out.route_ready),
+                                 ("streak", out.ready_streak), ("waypoint_success", out.waypoint_success), ("completed", out.completed_waypoints),
+                                 ("route_index", out.route_index)):
+                    assert int(val) == int(f[flag[key]]), (ctx, key, val, f[flag[key]])
+                handovers += int(out.waypoint_success and not out.success)
+                successes += int(out.success)
+            worst["q"] = max(worst["q"], float(np.max(np.abs(env.base_state()["q"] - g["q"][row]))))
+            if row in obs_of:
+                obs_rows += 1
+                worst["obs"] = max(worst["obs"], float(np.max(np.abs(obs.astype(np.float64) - obs_table[obs_base + obs_of[row]]))))
+        assert k == int(g["reset_start"][case.index + 1])
+    print(f"\n{len(rl.all_cases())} cases, {int(g['row_start'][-1])} rows, {handovers} hand-overs, {successes} successes, worst {worst}")
+    assert worst["reward"] <= 1e-12 and worst["components"] <= 1e-12 and worst["q"] <= 1e-15 and worst["obs"] <= 1e-9, worst
+    assert handovers > 100 and successes > 100 and obs_rows == int(g["obs_start"][-1])
