@@ -502,15 +502,6 @@ auto with_real(int real_type, F&& f) {
   return fail(KP1_ERR_INVALID, "real_type must be KP1_REAL_F32 or KP1_REAL_F64");
 }
 
-// the stateless entry points and kp1_create: the device they run on
-int use_device(int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(KP1_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-  if (device < 0 || device >= count) return fail(KP1_ERR_INVALID, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
-  return KP1_OK;
-}
-
 template <typename R>
 EnvState<R> state_of(const kp1_env* e) {
   EnvState<R> st;

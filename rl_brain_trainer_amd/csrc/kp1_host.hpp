@@ -76,3 +76,14 @@ int mlp_line_store(float* table, const float* v, int n_floats, hipStream_t strea
     hipError_t _e = (expr);                                                                                        \
     if (_e != hipSuccess) return kp1::fail(kp1::status_of(_e), std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
+
+namespace kp1 {
+// the device of an entry point that takes a device index (the stateless ones, and the creators of handles): refused when out of range, else current
+inline int use_device(int device) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(KP1_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
+  if (device < 0 || device >= count) return fail(KP1_ERR_INVALID, "device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  return KP1_OK;
+}
+}  // namespace kp1

@@ -1,5 +1,5 @@
-// kp1_ppo.hip -- PPO-side device kernels (include/kp1_ppo.h): GAE scan, time-limit bootstrap,
-// device-resident curriculum tracker.  The actor-critic MLP kernels live in kp1_mlp.hip.
+// kp1_ppo.hip -- PPO-side device kernels (include/kp1_ppo.h): GAE scan, time-limit bootstrap, epoch permutation and per-minibatch advantage
+// statistics, device-resident curriculum tracker, training monitor with explained variance.  The actor-critic MLP kernels live in kp1_mlp.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -9,16 +9,15 @@
 #include "kp1_host.hpp"
 
 using kp1::fail;
+using kp1::use_device;
 
 namespace {
 
 // One lane per env; every [t] row access is a fully coalesced wave instruction (4 B/lane f32, 1 B/lane done).
 // Algorithmic traffic: read r, V, done (9 B) + write A, R (8 B) per sample.
-__global__ void __launch_bounds__(256) gae_scan_kernel(const float* __restrict__ rewards, const float* __restrict__ values,
-                                                       const uint8_t* __restrict__ dones, const float* __restrict__ last_values,
-                                                       float gamma, float lam, float* __restrict__ adv, float* __restrict__ ret, int T, int N) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
+__device__ __forceinline__ void gae_column(const float* __restrict__ rewards, const float* __restrict__ values, const uint8_t* __restrict__ dones,
+                                           const float* __restrict__ last_values, float gamma, float lam, float* __restrict__ adv,
+                                           float* __restrict__ ret, int T, int N, int i) {
   float next_value = last_values[i];
   float last_gae = 0.0f;
   // prefetch-friendly reverse walk; T is small (<= a few thousand)
@@ -34,8 +33,16 @@ __global__ void __launch_bounds__(256) gae_scan_kernel(const float* __restrict__
   }
 }
 
-// gae_scan_kernel with (gamma, lambda) of column i's replica read from gamma_lambda [K][2]; the loop body is gae_scan_kernel's, expression for
-// expression, so a column computes bit for bit what the single scan computes with its replica's two scalars
+__global__ void __launch_bounds__(256) gae_scan_kernel(const float* __restrict__ rewards, const float* __restrict__ values,
+                                                       const uint8_t* __restrict__ dones, const float* __restrict__ last_values,
+                                                       float gamma, float lam, float* __restrict__ adv, float* __restrict__ ret, int T, int N) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  gae_column(rewards, values, dones, last_values, gamma, lam, adv, ret, T, N, i);
+}
+
+// gae_scan_kernel with (gamma, lambda) of column i's replica read from gamma_lambda [K][2]: the same gae_column, so a column computes bit for
+// bit what the single scan computes with its replica's two scalars
 __global__ void __launch_bounds__(256) gae_scan_replicas_kernel(const float* __restrict__ rewards, const float* __restrict__ values,
                                                                 const uint8_t* __restrict__ dones, const float* __restrict__ last_values,
                                                                 const float* __restrict__ gamma_lambda, int n_per_replica, float* __restrict__ adv,
@@ -43,19 +50,7 @@ __global__ void __launch_bounds__(256) gae_scan_replicas_kernel(const float* __r
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const int r = i / n_per_replica;
-  const float gamma = gamma_lambda[2 * r], lam = gamma_lambda[2 * r + 1];
-  float next_value = last_values[i];
-  float last_gae = 0.0f;
-  for (int t = T - 1; t >= 0; --t) {
-    const int64_t k = (int64_t)t * N + i;
-    const float nonterm = (dones[k] & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) ? 0.0f : 1.0f;
-    const float v = values[k];
-    const float delta = rewards[k] + gamma * next_value * nonterm - v;
-    last_gae = delta + gamma * lam * nonterm * last_gae;
-    adv[k] = last_gae;
-    ret[k] = last_gae + v;
-    next_value = v;
-  }
+  gae_column(rewards, values, dones, last_values, gamma_lambda[2 * r], gamma_lambda[2 * r + 1], adv, ret, T, N, i);
 }
 
 __global__ void __launch_bounds__(256) bootstrap_kernel(float* __restrict__ rewards, const float* __restrict__ tv,
@@ -292,39 +287,8 @@ __device__ __forceinline__ void curriculum_scan(kp1_curriculum_state* __restrict
 
 __global__ void __launch_bounds__(64) curriculum_kernel(kp1_curriculum_state* __restrict__ st, const uint8_t* __restrict__ dones, int n,
                                                         int steps_per_call) {
-  __shared__ int ring[KP1_CURRICULUM_MAX_WINDOW];
-  __shared__ uint8_t sbit[TRK_BLOCK];
-  __shared__ uint16_t pfx[TRK_BLOCK + KP1_CURRICULUM_MAX_WINDOW + 1];
-  const TrackerScratch ws = {sbit, pfx};
-  // [r3] the common VecEnv step ends no episode: then the only state that changes is num_timesteps, and the kernel is ONE round of loads (the
-  // done bytes) + a fire-and-forget add instead of three dependent round trips (state -> window -> done bytes) + the state stores
-  {
-    const int lane = threadIdx.x;
-    bool any = false;
-    for (int base = 0; base < n; base += 64 * 64) {
-      const int first = base + lane * 64;
-      if (first + 64 <= n && (reinterpret_cast<uintptr_t>(dones + first) & 15) == 0) {
-        const uint4* p = reinterpret_cast<const uint4*>(dones + first);
-        unsigned int acc = 0u;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint4 w = p[q];
-          acc |= w.x | w.y | w.z | w.w;
-        }
-        any |= (acc & (0x01010101u * (unsigned)(KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED))) != 0u;
-      } else {
-        for (int b = 0; b < 64 && first + b < n; ++b) any |= (dones[first + b] & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) != 0;
-      }
-    }
-    if (__ballot(any) == 0ull) {
-      if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&st->num_timesteps), (unsigned long long)(long long)steps_per_call);
-      return;
-    }
-  }
-  TrackerCtx c;
-  tracker_load(st, ring, c);
-  curriculum_scan(st, ring, c, ws, dones, n, steps_per_call);
-  tracker_store(st, ring, c);
+#include "kp1_tracker_scratch.inc"
+#include "kp1_tracker_step_body.inc"
 }
 
 // Data-parallel rollouts exchange the done bytes once per CHUNK of env steps instead of once per step: `dones` is the all-gathered
@@ -333,10 +297,7 @@ __global__ void __launch_bounds__(64) curriculum_kernel(kp1_curriculum_state* __
 // env id order (callbacks.py:78-91).  One wave; the state stays in registers / LDS across the whole chunk.
 __global__ void __launch_bounds__(64) curriculum_chunk_kernel(kp1_curriculum_state* __restrict__ st, const uint8_t* __restrict__ dones, int n_local,
                                                               int chunk_steps, int world, int steps_per_env_step) {
-  __shared__ int ring[KP1_CURRICULUM_MAX_WINDOW];
-  __shared__ uint8_t sbit[TRK_BLOCK];
-  __shared__ uint16_t pfx[TRK_BLOCK + KP1_CURRICULUM_MAX_WINDOW + 1];
-  const TrackerScratch ws = {sbit, pfx};
+#include "kp1_tracker_scratch.inc"
   TrackerCtx c;
   tracker_load(st, ring, c);
   for (int t = 0; t < chunk_steps; ++t)
@@ -346,52 +307,27 @@ __global__ void __launch_bounds__(64) curriculum_chunk_kernel(kp1_curriculum_sta
 }
 
 // K trackers in one launch (kp1_curriculum_observe_population): workgroup k is curriculum_kernel on tracker k and the done bytes
-// [k n, (k + 1) n) of its replica, early-out included.  (curriculum_kernel keeps its own copy of the early-out: the single tracker runs
-// the benchmark's rollout, and its code stays as it was.)
+// [k n, (k + 1) n) of its replica, early-out included: both include the same step body.
 __global__ void __launch_bounds__(64) curriculum_population_kernel(kp1_curriculum_state* __restrict__ states, const uint8_t* __restrict__ dones_all,
                                                                    int n, int steps_per_call) {
-  __shared__ int ring[KP1_CURRICULUM_MAX_WINDOW];
-  __shared__ uint8_t sbit[TRK_BLOCK];
-  __shared__ uint16_t pfx[TRK_BLOCK + KP1_CURRICULUM_MAX_WINDOW + 1];
-  const TrackerScratch ws = {sbit, pfx};
+#include "kp1_tracker_scratch.inc"
   kp1_curriculum_state* __restrict__ st = states + blockIdx.x;
   const uint8_t* __restrict__ dones = dones_all + (int64_t)blockIdx.x * n;
-  {
-    const int lane = threadIdx.x;
-    bool any = false;
-    for (int base = 0; base < n; base += 64 * 64) {
-      const int first = base + lane * 64;
-      if (first + 64 <= n && (reinterpret_cast<uintptr_t>(dones + first) & 15) == 0) {
-        const uint4* p = reinterpret_cast<const uint4*>(dones + first);
-        unsigned int acc = 0u;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint4 w = p[q];
-          acc |= w.x | w.y | w.z | w.w;
-        }
-        any |= (acc & (0x01010101u * (unsigned)(KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED))) != 0u;
-      } else {
-        for (int b = 0; b < 64 && first + b < n; ++b) any |= (dones[first + b] & (KP1_DONE_TERMINATED | KP1_DONE_TRUNCATED)) != 0;
-      }
-    }
-    if (__ballot(any) == 0ull) {
-      if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&st->num_timesteps), (unsigned long long)(long long)steps_per_call);
-      return;
-    }
-  }
-  TrackerCtx c;
-  tracker_load(st, ring, c);
-  curriculum_scan(st, ring, c, ws, dones, n, steps_per_call);
-  tracker_store(st, ring, c);
+#include "kp1_tracker_step_body.inc"
 }
 
-int check_device(int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(KP1_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
-  if (device < 0 || device >= count) return fail(KP1_ERR_INVALID, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
+// The one launch of this file: `blocks` workgroups of `block` lanes (every grid here is one-dimensional and no kernel takes dynamic LDS), then the
+// launch check of kp1_host.hpp.  kp1_env.hip's launch_env derives its grid from a lane count and passes LDS bytes; half the sites here state a
+// workgroup count (one per tracker, replica or minibatch), so each unit keeps its own five lines.
+template <typename... Params, typename... Args>
+int launch(void (*kernel)(Params...), int64_t blocks, int block, void* stream, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)block), 0, (hipStream_t)stream, args...);
+  HIP_TRY(kp1::launch_status());
   return KP1_OK;
 }
+
+// lanes per workgroup of the two GAE scans (one lane per env column): one wave per workgroup up to 16384 columns, four beyond
+constexpr int gae_block(int N) { return N <= 16384 ? 64 : 256; }
 
 }  // namespace
 
@@ -400,13 +336,10 @@ extern "C" {
 int kp1_gae_scan(int32_t device, const float* rewards, const float* values, const uint8_t* dones, const float* last_values, float gamma,
                  float gae_lambda, float* advantages, float* returns, int32_t T, int32_t N, void* stream) {
   if (!rewards || !values || !dones || !last_values || !advantages || !returns || T <= 0 || N <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_gae_scan");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
-  const int block = N <= 16384 ? 64 : 256;
-  hipLaunchKernelGGL(gae_scan_kernel, dim3((N + block - 1) / block), dim3(block), 0, (hipStream_t)stream, rewards, values, dones, last_values,
-                     gamma, gae_lambda, advantages, returns, T, N);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  const int block = gae_block(N);
+  return launch(gae_scan_kernel, (N + block - 1) / block, block, stream, rewards, values, dones, last_values, gamma, gae_lambda, advantages, returns, T, N);
 }
 
 int kp1_gae_scan_replicas(int32_t device, const float* rewards, const float* values, const uint8_t* dones, const float* last_values,
@@ -414,13 +347,11 @@ int kp1_gae_scan_replicas(int32_t device, const float* rewards, const float* val
   if (!rewards || !values || !dones || !last_values || !gamma_lambda || !advantages || !returns || T <= 0 || N <= 0)
     return fail(KP1_ERR_INVALID, "bad argument to kp1_gae_scan_replicas");
   if (n_per_replica <= 0 || N % n_per_replica != 0) return fail(KP1_ERR_INVALID, "kp1_gae_scan_replicas: N must be a multiple of n_per_replica");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
-  const int block = N <= 16384 ? 64 : 256;
-  hipLaunchKernelGGL(gae_scan_replicas_kernel, dim3((N + block - 1) / block), dim3(block), 0, (hipStream_t)stream, rewards, values, dones,
-                     last_values, gamma_lambda, n_per_replica, advantages, returns, T, N);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  const int block = gae_block(N);
+  return launch(gae_scan_replicas_kernel, (N + block - 1) / block, block, stream, rewards, values, dones, last_values, gamma_lambda, n_per_replica,
+                advantages, returns, T, N);
 }
 
 }  // extern "C"
@@ -492,7 +423,7 @@ extern "C" {
 
 int kp1_random_permutation(int32_t device, int64_t n, const uint32_t* keys, int64_t* out, void* stream) {
   if (!keys || !out || n <= 0 || n > ((int64_t)1 << 31)) return fail(KP1_ERR_INVALID, "bad argument to kp1_random_permutation");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
   int bits = 1;
   while (((int64_t)1 << bits) < n) ++bits;
@@ -501,41 +432,30 @@ int kp1_random_permutation(int32_t device, int64_t n, const uint32_t* keys, int6
     k.mul[r] = keys[r] | 1u;     // odd: invertible modulo 2^bits
     k.add[r] = keys[4 + r];
   }
-  hipLaunchKernelGGL(permutation_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n, bits, k);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch(permutation_kernel, (n + 255) / 256, 256, stream, out, n, bits, k);
 }
 
 int kp1_adv_minibatch_stats(int32_t device, const double* sums, int64_t n_minibatches, float* out_stats, void* stream) {
   if (!sums || !out_stats || n_minibatches <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_adv_minibatch_stats");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
-  hipLaunchKernelGGL(adv_minibatch_stats_kernel, dim3((unsigned)((n_minibatches + 63) / 64)), dim3(64), 0, (hipStream_t)stream, sums, n_minibatches,
-                     out_stats);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch(adv_minibatch_stats_kernel, (n_minibatches + 63) / 64, 64, stream, sums, n_minibatches, out_stats);
 }
 
 int kp1_adv_minibatch_sums(int32_t device, const float* advantages, const int64_t* idx, int64_t total, int64_t minibatch, double* out_sums,
                            void* stream) {
   if (!advantages || !out_sums || total <= 0 || minibatch <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_adv_minibatch_sums");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
-  const int64_t n_mb = (total + minibatch - 1) / minibatch;
-  hipLaunchKernelGGL(adv_minibatch_sums_kernel, dim3((unsigned)n_mb), dim3(256), 0, (hipStream_t)stream, advantages, idx, total, minibatch, out_sums);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch(adv_minibatch_sums_kernel, (total + minibatch - 1) / minibatch, 256, stream, advantages, idx, total, minibatch, out_sums);
 }
 
 int kp1_bootstrap_truncated(int32_t device, float* rewards, const float* terminal_values, const uint8_t* dones, float gamma, int64_t count,
                             void* stream) {
   if (!rewards || !terminal_values || !dones || count <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_bootstrap_truncated");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
-  hipLaunchKernelGGL(bootstrap_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rewards, terminal_values, dones,
-                     gamma, count);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch(bootstrap_kernel, (count + 255) / 256, 256, stream, rewards, terminal_values, dones, gamma, count);
 }
 
 int kp1_curriculum_create(int32_t device, double success_rate_threshold, int32_t window_episodes, int32_t min_episodes_per_stage,
@@ -548,7 +468,7 @@ int kp1_curriculum_create_population(int32_t device, int32_t n_replicas, double 
                                      kp1_curriculum_state** out_dev) {
   if (!out_dev || !initial_stages) return fail(KP1_ERR_INVALID, "NULL argument");
   if (n_replicas < 1 || n_replicas > KP1_CURRICULUM_MAX_REPLICAS) return fail(KP1_ERR_INVALID, "n_replicas must be in [1, KP1_CURRICULUM_MAX_REPLICAS]");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
   std::vector<kp1_curriculum_state> h((size_t)n_replicas);
   for (int k = 0; k < n_replicas; ++k) {
@@ -564,43 +484,41 @@ int kp1_curriculum_create_population(int32_t device, int32_t n_replicas, double 
   }
   kp1_curriculum_state* d = nullptr;
   HIP_TRY(hipMalloc((void**)&d, sizeof(kp1_curriculum_state) * h.size()));
+  struct Unowned {   // frees the trackers unless they reached the caller
+    void* p;
+    ~Unowned() { (void)hipFree(p); }
+  } unowned = {d};
   HIP_TRY(hipMemcpy(d, h.data(), sizeof(kp1_curriculum_state) * h.size(), hipMemcpyHostToDevice));
   *out_dev = d;
+  unowned.p = nullptr;
   return KP1_OK;
 }
 int kp1_curriculum_destroy(int32_t device, kp1_curriculum_state* st_dev) {
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
   HIP_TRY(hipFree(st_dev));
   return KP1_OK;
 }
 int kp1_curriculum_observe(int32_t device, kp1_curriculum_state* st_dev, const uint8_t* dones, int32_t n, int32_t steps_per_call, void* stream) {
   if (!st_dev || !dones || n <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_curriculum_observe");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
-  hipLaunchKernelGGL(curriculum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, dones, n, steps_per_call);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch(curriculum_kernel, 1, 64, stream, st_dev, dones, n, steps_per_call);
 }
 int kp1_curriculum_observe_chunk(int32_t device, kp1_curriculum_state* st_dev, const uint8_t* dones, int32_t n_local, int32_t chunk_steps,
                                  int32_t world, void* stream) {
   if (!st_dev || !dones || n_local <= 0 || chunk_steps <= 0 || world <= 0) return fail(KP1_ERR_INVALID, "bad argument to kp1_curriculum_observe_chunk");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
-  hipLaunchKernelGGL(curriculum_chunk_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st_dev, dones, n_local, chunk_steps, world, n_local * world);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch(curriculum_chunk_kernel, 1, 64, stream, st_dev, dones, n_local, chunk_steps, world, n_local * world);
 }
 int kp1_curriculum_observe_population(int32_t device, kp1_curriculum_state* states_dev, const uint8_t* dones, int32_t n_per_replica,
                                       int32_t n_replicas, int32_t steps_per_call, void* stream) {
   if (!states_dev || !dones || n_per_replica <= 0 || n_replicas < 1 || n_replicas > KP1_CURRICULUM_MAX_REPLICAS)
     return fail(KP1_ERR_INVALID, "bad argument to kp1_curriculum_observe_population");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
-  hipLaunchKernelGGL(curriculum_population_kernel, dim3((unsigned)n_replicas), dim3(64), 0, (hipStream_t)stream, states_dev, dones, n_per_replica,
-                     steps_per_call);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch(curriculum_population_kernel, n_replicas, 64, stream, states_dev, dones, n_per_replica, steps_per_call);
 }
 int kp1_curriculum_read_replica(int32_t device, const kp1_curriculum_state* states_dev, int32_t n_replicas, int32_t k, kp1_curriculum_state* out_host,
                                 void* stream) {
@@ -610,7 +528,7 @@ int kp1_curriculum_read_replica(int32_t device, const kp1_curriculum_state* stat
 }
 int kp1_curriculum_read(int32_t device, const kp1_curriculum_state* st_dev, kp1_curriculum_state* out_host, void* stream) {
   if (!st_dev || !out_host) return fail(KP1_ERR_INVALID, "NULL argument");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
   HIP_TRY(hipMemcpyAsync(out_host, st_dev, sizeof *out_host, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -812,7 +730,7 @@ int kp1_monitor_create(int32_t device, int32_t n_replicas, int32_t n_per_replica
   if (max_steps < 1 || max_steps > KP1_MONITOR_MAX_STEPS) return fail(KP1_ERR_INVALID, "kp1_monitor_create: max_steps must be in [1, KP1_MONITOR_MAX_STEPS]");
   const int64_t kn = (int64_t)n_replicas * n_per_replica;
   if (kn * max_steps >= ((int64_t)1 << 31)) return fail(KP1_ERR_INVALID, "kp1_monitor_create: max_steps * n_replicas * n_per_replica must stay below 2^31");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
   kp1_monitor* m = new kp1_monitor();
   m->device = device; m->K = n_replicas; m->N = n_per_replica; m->window = window; m->max_steps = max_steps;
@@ -839,7 +757,7 @@ int kp1_monitor_create(int32_t device, int32_t n_replicas, int32_t n_per_replica
 
 int kp1_monitor_destroy(kp1_monitor* mon) {
   if (!mon) return fail(KP1_ERR_INVALID, "kp1_monitor_destroy: NULL argument");
-  int rc = check_device(mon->device);
+  int rc = use_device(mon->device);
   if (rc != KP1_OK) return rc;
   monitor_free(mon);
   return KP1_OK;
@@ -848,21 +766,16 @@ int kp1_monitor_destroy(kp1_monitor* mon) {
 int kp1_monitor_observe(kp1_monitor* mon, const float* rewards, const uint8_t* dones, int32_t T, void* stream) {
   if (!mon || !rewards || !dones) return fail(KP1_ERR_INVALID, "kp1_monitor_observe: NULL argument");
   if (T < 1 || T > mon->max_steps) return fail(KP1_ERR_INVALID, "kp1_monitor_observe: T must be in [1, max_steps of the handle]");
-  int rc = check_device(mon->device);
+  int rc = use_device(mon->device);
   if (rc != KP1_OK) return rc;
   const int KN = mon->K * mon->N;
-  hipLaunchKernelGGL(monitor_scan_kernel, dim3((unsigned)((KN + 63) / 64)), dim3(64), 0, (hipStream_t)stream, rewards, dones, mon->carry_ret,
-                     mon->carry_len, mon->ep_ret, mon->ep_len, (int)T, KN);
-  HIP_TRY(kp1::launch_status());
-  hipLaunchKernelGGL(monitor_rank_kernel, dim3((unsigned)mon->K), dim3(MON_THREADS), 0, (hipStream_t)stream, mon->states, dones, mon->ep_ret,
-                     mon->ep_len, (int)T, mon->N, KN);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  rc = launch(monitor_scan_kernel, (KN + 63) / 64, 64, stream, rewards, dones, mon->carry_ret, mon->carry_len, mon->ep_ret, mon->ep_len, T, KN);
+  return rc != KP1_OK ? rc : launch(monitor_rank_kernel, mon->K, MON_THREADS, stream, mon->states, dones, mon->ep_ret, mon->ep_len, T, mon->N, KN);
 }
 
 int kp1_monitor_reset_carry(kp1_monitor* mon, void* stream) {
   if (!mon) return fail(KP1_ERR_INVALID, "kp1_monitor_reset_carry: NULL argument");
-  int rc = check_device(mon->device);
+  int rc = use_device(mon->device);
   if (rc != KP1_OK) return rc;
   const size_t kn = (size_t)mon->K * (size_t)mon->N;
   HIP_TRY(hipMemsetAsync(mon->carry_ret, 0, sizeof(double) * kn, (hipStream_t)stream));
@@ -873,7 +786,7 @@ int kp1_monitor_reset_carry(kp1_monitor* mon, void* stream) {
 int kp1_monitor_read(kp1_monitor* mon, int32_t replica, kp1_monitor_state* out_host, void* stream) {
   if (!mon || !out_host) return fail(KP1_ERR_INVALID, "kp1_monitor_read: NULL argument");
   if (replica < 0 || replica >= mon->K) return fail(KP1_ERR_INVALID, "kp1_monitor_read: replica index out of range");
-  int rc = check_device(mon->device);
+  int rc = use_device(mon->device);
   if (rc != KP1_OK) return rc;
   HIP_TRY(hipMemcpyAsync(out_host, mon->states + replica, sizeof *out_host, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -886,12 +799,9 @@ int kp1_explained_variance(int32_t device, const float* values, const float* ret
   if (T < 1 || n_total < 1 || n_per_replica < 1 || n_total % n_per_replica != 0)
     return fail(KP1_ERR_INVALID, "kp1_explained_variance: T and n_total must be positive and n_total a multiple of n_per_replica");
   if ((int64_t)T * n_total >= ((int64_t)1 << 31)) return fail(KP1_ERR_INVALID, "kp1_explained_variance: T * n_total must stay below 2^31");
-  int rc = check_device(device);
+  int rc = use_device(device);
   if (rc != KP1_OK) return rc;
-  hipLaunchKernelGGL(explained_variance_kernel, dim3((unsigned)(n_total / n_per_replica)), dim3(1024), 0, (hipStream_t)stream, values, returns,
-                     (int)T, (int)n_total, (int)n_per_replica, out);
-  HIP_TRY(kp1::launch_status());
-  return KP1_OK;
+  return launch(explained_variance_kernel, n_total / n_per_replica, 1024, stream, values, returns, T, n_total, n_per_replica, out);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 """The rollout-tail kernels of kp1_ppo.hip at their edges, through the C ABI: kp1_gae_scan (one row, one column, both block sizes of the
 launcher, every done byte), kp1_gae_scan_replicas at the large block size, kp1_bootstrap_truncated on all sixteen done bytes,
-kp1_adv_minibatch_sums without idx / with a short, a one-row and an exact last minibatch, kp1_adv_minibatch_stats on two workgroups.
-test_ppo_kernels_gpu.py holds the one-shape tests of the same kernels; tolerances here are theirs."""
+kp1_adv_minibatch_sums without idx / with a short, a one-row and an exact last minibatch, kp1_adv_minibatch_stats on two workgroups; and the two refusals of the unit that need a device (a curriculum window above the maximum, a device
+index past the last device).  test_ppo_kernels_gpu.py holds the one-shape tests of the same kernels; tolerances here are theirs."""
 from __future__ import annotations
 
 import ctypes as C
@@ -181,3 +181,39 @@ def test_adv_minibatch_stats_on_two_workgroups():
         sel = adv[perm[b * mb:(b + 1) * mb]].double()
         assert abs(st[b, 0] - sel.mean().item()) <= 1e-6 and abs(st[b, 1] - 1.0 / (sel.std().item() + 1e-8)) <= 1e-5 * st[b, 1]
     assert s[64, 2] == 27
+
+
+def test_curriculum_window_above_the_maximum_is_refused():
+    """the one argument check of kp1_curriculum_create_population behind the device selection (the other refusals of the unit need no device:
+    test_ppo_unit_refusals_cpu.py); the largest window is accepted, nothing is allocated for the refused one"""
+    L = native.load()
+    max_window = native.header_int("KP1_CURRICULUM_MAX_WINDOW")
+    stages = (C.c_int32 * 2)(0, 1)
+    out = C.c_void_p()
+    assert L.kp1_curriculum_create_population(0, 2, 0.8, max_window + 1, 5, 3, C.cast(stages, C.c_void_p), C.byref(out)) == -1
+    assert L.kp1_last_error().decode() == "window_episodes exceeds KP1_CURRICULUM_MAX_WINDOW" and out.value is None
+    native.check(L.kp1_curriculum_create_population(0, 2, 0.8, max_window, 5, 3, C.cast(stages, C.c_void_p), C.byref(out)))
+    assert out.value
+    native.check(L.kp1_curriculum_destroy(0, out))
+
+
+def test_device_index_equal_to_the_device_count_is_refused():
+    """every kind of entry point of the unit (a launch, a creator, a read, the monitor's creator) with acceptable arguments and the first device
+    index past the last device: KP1_ERR_INVALID before anything is launched, allocated or copied"""
+    L = native.load()
+    count = torch.cuda.device_count()
+    buf = torch.full((64,), -7.0, dtype=torch.float32, device=DEV)
+    host = (C.c_char * 65536)()
+    stages = (C.c_int32 * 1)(0)
+    out = C.c_void_p()
+    calls = [lambda: L.kp1_gae_scan(count, _p(buf), _p(buf), _p(buf), _p(buf), GAMMA, LAM, _p(buf), _p(buf), 1, 8, _stream()),
+             lambda: L.kp1_adv_minibatch_stats(count, _p(buf), 1, _p(buf), _stream()),
+             lambda: L.kp1_curriculum_observe(count, _p(buf), _p(buf), 64, 1, _stream()),
+             lambda: L.kp1_curriculum_read(count, _p(buf), C.cast(host, C.c_void_p), _stream()),
+             lambda: L.kp1_curriculum_create_population(count, 1, 0.8, 10, 5, 3, C.cast(stages, C.c_void_p), C.byref(out)),
+             lambda: L.kp1_monitor_create(count, 1, 8, 100, 4, C.byref(out)),
+             lambda: L.kp1_explained_variance(count, _p(buf), _p(buf), 1, 8, 8, _p(buf), _stream())]
+    for call in calls:
+        assert call() == -1 and L.kp1_last_error().decode() == "device index out of range"
+    torch.cuda.synchronize()
+    assert out.value is None and (buf == -7.0).all() and bytes(host) == bytes(65536)
