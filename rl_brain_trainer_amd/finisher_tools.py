@@ -20,6 +20,8 @@ import torch
 
 from . import config as kcfg
 from . import native
+from .curriculum import DeviceTracker, TrackerPopulation, TrackerReplica, window_mean
+from .vec_env import _view
 
 # keys a reverse-curriculum stage may override (callbacks.py:131-150): three env scalars, the dock_reset block
 _STAGE_ENV_KEYS = ("action_delta_scale", "dock_residual_action_limit", "dock_delta_q_change_limit_scale")
@@ -50,10 +52,12 @@ class _State(C.Structure):
                [("num_timesteps", C.c_int64), ("stages", _Stage * MAX_STAGES), ("events", _Event * MAX_HISTORY), ("ring", C.c_uint8 * MAX_WINDOW)]
 
 
-class DockReverseCurriculum:
+class DockReverseCurriculum(DeviceTracker):
     """The Finisher's reverse curriculum (``training.dock_reverse_curriculum`` of the YAML: ``stages`` + ``window_episodes``) as a device tracker.
     ``PPO(curriculum=...)`` calls ``attach(env)`` once and ``observe(done_bytes, steps)`` after every env step on the rollout stream, so the
     dock rollout is one hipGraph replay; ``summary()`` has the reference callback's keys."""
+
+    State = _State
 
     def __init__(self, *, stages: list[dict[str, object]], window_episodes: int, handoff_base_dirs: tuple[Path, ...] = ()) -> None:
         if not stages:
@@ -115,16 +119,19 @@ class DockReverseCurriculum:
         return out
 
     # ---------------------------------------------------------------- device side
-    def attach(self, env: Any) -> None:
-        """_on_training_start: allocate the tracker next to the env; stage 0 is applied on the device before the first reset"""
-        L = env.L
-        self.env = env
+    def _stage_table(self, env: Any):
+        """attach's prologue: every stage's handoff list in the env's buffer, back to back, and the resolved stage table over them"""
         buffers = self.stage_buffers(env.config)
         if buffers is not None:
             env.set_handoff_states([state for stage_states in buffers for state in stage_states])
-        table = self.resolved_stages(env.config, buffers)
+        return self.resolved_stages(env.config, buffers)
+
+    def attach(self, env: Any) -> None:
+        """_on_training_start: allocate the tracker next to the env; stage 0 is applied on the device before the first reset"""
+        self.env = env
+        table = self._stage_table(env)
         with torch.cuda.device(env.device):
-            native.check(L.kp1_dock_curriculum_create(env._handle, table, len(self.stages), self.window_episodes, C.byref(self._st)))
+            native.check(env.L.kp1_dock_curriculum_create(env._handle, table, len(self.stages), self.window_episodes, C.byref(self._st)))
         env.launch_args_version = getattr(env, "launch_args_version", 0) + 1
 
     on_training_start = attach
@@ -133,23 +140,15 @@ class DockReverseCurriculum:
         self.observe_chunk(dones, int(dones.numel()), 1, 1)
 
     def observe_chunk(self, dones_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
         native.check(self.env.L.kp1_dock_curriculum_observe(self.env._handle, self._st, C.c_void_p(dones_all.data_ptr()), int(n_local), int(chunk_steps),
-                                                            int(world), C.c_void_p(stream)))
+                                                            int(world), self._stream()))
 
-    def read(self) -> _State:
-        out = _State()
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
-        native.check(self.env.L.kp1_dock_curriculum_read(self.env._handle, self._st, C.byref(out), C.c_void_p(stream)))
-        # the Python-side config mirror follows the stage the device applied (the C handle's mirror was updated by the call above)
-        live, c = out.stages[out.stage_index], self.env.config.c
-        for key in _STAGE_ENV_KEYS:
-            setattr(c.env, key, float(getattr(live, key)))
-        for key in _STAGE_RESET_SCALARS:
-            setattr(c.dock_reset, key, float(getattr(live, key)))
-        for key in _STAGE_RESET_VECTORS:
-            getattr(c.dock_reset, key)[:] = list(getattr(live, key)[:])
-        return out
+    def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:
+        return self.env.L.kp1_dock_curriculum_read(self.env._handle, self._st, out, stream)
+
+    def _follow(self, st: _State, k: int) -> None:
+        """the Python-side config mirror follows the stage the device applied (the C handle's mirror was updated by the read)"""
+        _follow_stage(self.env.config.c, st.stages[st.stage_index])
 
     @property
     def current_stage_index(self) -> int:
@@ -158,26 +157,29 @@ class DockReverseCurriculum:
     def _name(self, index: int) -> object:
         return self.stages[index].get("name", f"stage_{index}")
 
-    def summary(self) -> dict[str, object]:
-        return self._summary_of(self.read())
-
     def _summary_of(self, st: _State) -> dict[str, object]:
-        n, cap, head = int(st.ring_len), int(st.window_episodes), int(st.ring_head)
-        wins = sum(int(st.ring[(head + j) % cap]) for j in range(n))
         events = [st.events[k] for k in range(min(int(st.n_events), MAX_HISTORY))]
         return {"stage_index": int(st.stage_index), "stage_name": self._name(int(st.stage_index)), "stage_episode_count": int(st.stage_episode_count),
-                "recent_success_rate": float(wins) / float(n) if n else 0.0,
+                "recent_success_rate": window_mean(st, st.ring),
                 "history": [{"from_stage_index": int(e.from_stage), "from_stage_name": self._name(int(e.from_stage)), "to_stage_index": int(e.to_stage),
                              "to_stage_name": self._name(int(e.to_stage)), "trigger_success_rate": float(e.trigger_success_rate),
                              "stage_episode_count": int(e.stage_episode_count), "total_timesteps": int(e.total_timesteps)} for e in events]}
 
-    def close(self) -> None:
-        if self.env is not None and self._st.value:
-            self.env.L.kp1_dock_curriculum_destroy(self.env._handle, self._st)
-            self._st = C.c_void_p()
+    def _destroy(self) -> None:
+        self.env.L.kp1_dock_curriculum_destroy(self.env._handle, self._st)
 
 
-class DockReverseCurriculumPopulation(DockReverseCurriculum):
+def _follow_stage(c: Any, live: _Stage) -> None:
+    """copy what a live stage record overrides (_STAGE_ENV_KEYS, _STAGE_RESET_SCALARS, _STAGE_RESET_VECTORS) into the config struct ``c``"""
+    for key in _STAGE_ENV_KEYS:
+        setattr(c.env, key, float(getattr(live, key)))
+    for key in _STAGE_RESET_SCALARS:
+        setattr(c.dock_reset, key, float(getattr(live, key)))
+    for key in _STAGE_RESET_VECTORS:
+        getattr(c.dock_reset, key)[:] = list(getattr(live, key)[:])
+
+
+class DockReverseCurriculumPopulation(TrackerPopulation, DockReverseCurriculum):
     """K DockReverseCurriculum trackers of one stage table, one per replica of a dock-mode ArmKinematicPopulationVecEnv (include/kp1_ppo.h,
     kp1_dock_curriculum_*_population).  ``attach(env)`` builds the stage buffers and the resolved table once, applies stage 0 to the shared
     config and binds the handle: env i then steps and resets with replica i / N's live stage record, which only that replica's promotions
@@ -186,7 +188,7 @@ class DockReverseCurriculumPopulation(DockReverseCurriculum):
 
     Each replica owns an ``EnvConfig`` copy of the attached env's config (concatenated handoff list included): ``replica(k).read()`` brings
     copy k in step with tracker k's stage, as ``DockReverseCurriculum.read()`` does with a single run's config, so replica k is evaluated on
-    its own stage.  ``replica(k)`` has ``read()``, ``current_stage_index`` and ``summary()`` with DockReverseCurriculum's keys."""
+    its own stage.  ``replica(k)`` has ``read()``, ``current_stage_index``, ``summary()`` with DockReverseCurriculum's keys and ``config``."""
 
     def __init__(self, *, stages: list[dict[str, object]], window_episodes: int, n_replicas: int, handoff_base_dirs: tuple[Path, ...] = ()) -> None:
         from .vec_env import MAX_REPLICAS
@@ -204,13 +206,9 @@ class DockReverseCurriculumPopulation(DockReverseCurriculum):
             raise ValueError("the dock reverse curriculum drives a dock-mode env")
         if getattr(env, "K", self.K) != self.K or env.n_envs % self.K != 0:
             raise ValueError(f"a population env of {env.n_envs} envs does not split into this tracker's {self.K} replicas")
-        L = env.L
-        buffers = self.stage_buffers(env.config)
-        if buffers is not None:
-            env.set_handoff_states([state for stage_states in buffers for state in stage_states])
-        table = self.resolved_stages(env.config, buffers)
+        table = self._stage_table(env)
         with torch.cuda.device(env.device):
-            native.check(L.kp1_dock_curriculum_create_population(env._handle, table, len(self.stages), self.window_episodes, self.K, C.byref(self._st)))
+            native.check(env.L.kp1_dock_curriculum_create_population(env._handle, table, len(self.stages), self.window_episodes, self.K, C.byref(self._st)))
         self.env = env
         env.dock_population = self
         env.launch_args_version += 1     # a captured rollout froze the step kernel (and its stage source) into the graph
@@ -220,28 +218,16 @@ class DockReverseCurriculumPopulation(DockReverseCurriculum):
 
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
         """dones: the K N done bytes of one population step (replica-major); every clock advances by N whatever ``steps_per_call`` says"""
-        if dones.numel() % self.K != 0 or dones.dtype != torch.uint8 or not dones.is_contiguous():
-            raise ValueError(f"observe() takes the contiguous uint8 done bytes of all {self.K} replicas")
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        self._check_done_bytes(dones, dones.numel() % self.K == 0)
         native.check(self.env.L.kp1_dock_curriculum_observe_population(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), dones.numel() // self.K,
-                                                                       self.K, C.c_void_p(stream)))
+                                                                       self.K, self._stream()))
 
-    def observe_chunk(self, dones_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
-        raise TypeError("the dock population tracker has no data-parallel form")
+    def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:
+        return self.env.L.kp1_dock_curriculum_read_replica(self.env._handle, self._st, self.K, k, out, stream)
 
-    def read(self, k: int = 0) -> _State:
-        """tracker k; brings replica k's config copy in step with its stage (the handle's shared config is left as it is)"""
-        out = _State()
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
-        native.check(self.env.L.kp1_dock_curriculum_read_replica(self.env._handle, self._st, self.K, int(k), C.byref(out), C.c_void_p(stream)))
-        live, c = out.stages[out.stage_index], self.configs[int(k)].c
-        for key in _STAGE_ENV_KEYS:
-            setattr(c.env, key, float(getattr(live, key)))
-        for key in _STAGE_RESET_SCALARS:
-            setattr(c.dock_reset, key, float(getattr(live, key)))
-        for key in _STAGE_RESET_VECTORS:
-            getattr(c.dock_reset, key)[:] = list(getattr(live, key)[:])
-        return out
+    def _follow(self, st: _State, k: int) -> None:
+        """replica k's config copy follows tracker k's stage (the handle's shared config is left as it is)"""
+        _follow_stage(self.configs[k].c, st.stages[st.stage_index])
 
     @property
     def current_stage_index(self) -> int:
@@ -249,54 +235,18 @@ class DockReverseCurriculumPopulation(DockReverseCurriculum):
 
     def live_records(self) -> list[_Stage]:
         """host copies of the K live stage records the population kernels read (record k = the stage tracker k is on)"""
-        from .vec_env import _view
-
         ptr = self._st.value + self.K * C.sizeof(_State)
         raw = _view(ptr, (self.K * C.sizeof(_Stage),), "|u1", self.env.device).cpu().numpy().tobytes()
         return [_Stage.from_buffer_copy(raw, k * C.sizeof(_Stage)) for k in range(self.K)]
 
-    def summary(self, k: int = 0) -> dict[str, object]:
-        return self._summary_of(self.read(k))
-
-    def replica(self, k: int) -> "DockReverseCurriculumReplica":
-        if not 0 <= int(k) < self.K:
-            raise IndexError(f"replica {k} of a population of {self.K}")
-        return DockReverseCurriculumReplica(self, int(k))
-
     def close(self) -> None:
-        if self.env is not None and self._st.value:
-            self.env.L.kp1_dock_curriculum_destroy(self.env._handle, self._st)
-            self._st = C.c_void_p()
+        if self._st.value:
+            super().close()
             self.env.dock_population = None
             self.env.launch_args_version += 1
 
 
-class DockReverseCurriculumReplica:
-    """Replica k of a DockReverseCurriculumPopulation: read() / current_stage_index / summary() of its tracker, and ``config``, the replica's
-    own EnvConfig copy that read() keeps in step.  The population observes all replicas at once."""
-
-    def __init__(self, pop: DockReverseCurriculumPopulation, k: int) -> None:
-        self.pop, self.k = pop, int(k)
-
-    @property
-    def config(self) -> kcfg.EnvConfig:
-        return self.pop.configs[self.k]
-
-    def attach(self, env: Any) -> None:
-        """(the population tracker is attached to the population env)"""
-
-    def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
-        raise TypeError("replica trackers are observed through DockReverseCurriculumPopulation.observe (one launch for all replicas)")
-
-    def read(self) -> _State:
-        return self.pop.read(self.k)
-
-    @property
-    def current_stage_index(self) -> int:
-        return int(self.read().stage_index)
-
-    def summary(self) -> dict[str, object]:
-        return self.pop.summary(self.k)
+DockReverseCurriculumReplica = TrackerReplica
 
 
 def build_finisher_handoff_state_buffer(*, approach_policy, approach_cfg: kcfg.EnvConfig, artifact_root: str | Path | None = None, episodes: int = 500,

@@ -558,7 +558,7 @@ def rollout_run_covered(step_covered: bool, hidden: int, mode_name: str, dist_en
     56-float observation, reward components off); ``hidden``: 64 / 128 (hidden 256, the tile path, keeps its step); ``mode_name``: approach
     only; ``dist_enabled``: a data-parallel run exchanges done bytes per chunk and keeps the loop; ``has_step_callback``: a host hook after
     every step keeps the loop; ``tracker_attached`` / ``envs_per_replica``: the launch runs the tracker itself only when a replica is one tile
-    (at most ROLLOUT_RUN_TRACKED_MAX_ENVS envs); ``tracker_ok``: the attached tracker is a PointCurriculum / PointCurriculumPopulation;
+    (at most ROLLOUT_RUN_TRACKED_MAX_ENVS envs); ``tracker_ok``: the attached tracker's ``runs_in_rollout_launch`` (the point trackers');
     ``env_var``: KP1_ROLLOUT_RUN ("0": the per-step loop; any other value: the whole-rollout form wherever it is covered; None = unset:
     ``default_on``, the calling trainer's default -- off everywhere until a measurement by DESIGN section 27's rule turns it on)."""
     if not step_covered or hidden not in ROLLOUT_RUN_WIDTHS or mode_name != "approach" or dist_enabled or has_step_callback:
@@ -651,7 +651,7 @@ class PPO:
             # a route tracker also reads per-env flags that every step overwrites: each step's episode records are staged in slot t % chunk
             # and the staging buffer is exchanged instead of the done bytes
             self._record_stage = None
-            if curriculum is not None and getattr(curriculum, "needs_episode_records", False):
+            if curriculum is not None and curriculum.needs_episode_records:
                 self._record_stage = torch.zeros((self.done_chunk, N), dtype=torch.uint8, device=dev)
 
     @property
@@ -694,7 +694,7 @@ class PPO:
         step_covered = fused_rollout_covered(self._rollout_env_type_ok(), env.dtype, self.cfg.hidden, self.obs_dim,
                                              getattr(env, "_reward_components_on", False), None, default_on=True)
         return rollout_run_covered(step_covered, self.cfg.hidden, getattr(env, "_mode_name", ""), self.dist.enabled, self.step_callback is not None,
-                                   cur is not None, self.n_envs, var, tracker_ok=isinstance(cur, PointCurriculum),
+                                   cur is not None, self.n_envs, var, tracker_ok=cur is not None and cur.runs_in_rollout_launch,
                                    default_on=self.whole_rollout_default)
 
     # The env handle and the tracker of a rollout step, and which one-launch forms that handle's type admits: all that differs between

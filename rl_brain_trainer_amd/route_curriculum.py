@@ -22,6 +22,7 @@ import torch
 from . import config as kcfg
 from . import native
 from . import route_config as rcfg
+from .curriculum import DeviceTracker, TrackerPopulation, TrackerReplica, window_mean
 from .route_env import RoutePopulationVecEnv, RouteVecEnv
 
 
@@ -53,14 +54,14 @@ class _CurriculumState(C.Structure):
                 ("ring", (C.c_uint8 * MAX_WINDOW) * 4), ("events", _CurriculumEvent * MAX_HISTORY)]
 
 
-class RoutePrefixCurriculumDevice:
+class RoutePrefixCurriculumDevice(DeviceTracker):
     """RoutePrefixCurriculum with the per-step scan on the device (include/kp1_route.h, kp1_route_curriculum_*): same promotion rule and
     history, no host synchronisation per step, so the PPO rollout stays one hipGraph replay.  Plugs into ``PPO(curriculum=...)``.
 
     Data parallel: the tracker needs the wrapper's per-env flags as well as the done bytes, and the flags are overwritten by every step, so
     PPO records each step (``record``: one byte per env, done bits + flags) and exchanges those records once per chunk (``observe_chunk``)."""
 
-    # PPO's data-parallel rollout exchanges per-step episode records (record / observe_chunk) for this tracker instead of the done bytes
+    State = _CurriculumState
     needs_episode_records = True
 
     def __init__(self, *, stages: list[RouteCurriculumStage], promotion_success_rate: float, promotion_route_ready_hit_rate: float,
@@ -97,20 +98,23 @@ class RoutePrefixCurriculumDevice:
     def promotion_max_regression_rate(self) -> float:
         return float(self._args[3])
 
-    def attach(self, env: RouteVecEnv) -> None:
-        """_on_training_start: allocate the tracker next to the env and apply the first prefix."""
+    def _create(self, env: RouteVecEnv, create: Callable[..., int]) -> tuple[int, int]:
+        """attach: the tracker(s) next to the env by ``create``, and the env's reset window on the first prefix; returns that window"""
         self.env = env
-        L = env.L
         prefixes = (C.c_int32 * len(self.stages))(*[int(s.prefix_end_index) for s in self.stages])
         with torch.cuda.device(env.device):
-            native.check(L.kp1_route_curriculum_create(env._handle, prefixes, len(self.stages), *self._args, C.byref(self._st)))
-        env.route_cfg.reset.min_route_index, env.route_cfg.reset.max_route_index = 1, int(self.stages[0].prefix_end_index)
+            native.check(create(env._handle, prefixes, len(self.stages), *self._args, C.byref(self._st)))
+        env.route_cfg.reset.min_route_index, env.route_cfg.reset.max_route_index = first = (1, int(prefixes[0]))
+        return first
+
+    def attach(self, env: RouteVecEnv) -> None:
+        """_on_training_start: allocate the tracker next to the env and apply the first prefix."""
+        self._create(env, env.L.kp1_route_curriculum_create)
 
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
         if dones.numel() != self.env.n_envs:
             raise ValueError("observe() tracks one process's envs from the env's own flags; data parallel goes through record() + observe_chunk()")
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
-        native.check(self.env.L.kp1_route_curriculum_observe(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), int(steps_per_call), C.c_void_p(stream)))
+        native.check(self.env.L.kp1_route_curriculum_observe(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), int(steps_per_call), self._stream()))
 
     def record(self, dones: torch.Tensor, out: torch.Tensor) -> None:
         """out[N] <- this step's episode records: the KP1_DONE_* bits of ``dones`` | route_ready << 4 | orientation hit << 5 | regression << 6,
@@ -118,34 +122,23 @@ class RoutePrefixCurriculumDevice:
         n = self.env.n_envs
         if dones.numel() != n or out.numel() != n or out.dtype != torch.uint8 or not (dones.is_contiguous() and out.is_contiguous()):
             raise ValueError(f"record() takes the {n} done bytes of one step and a contiguous uint8 [{n}] output")
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
-        native.check(self.env.L.kp1_route_episode_records(self.env._handle, C.c_void_p(dones.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        native.check(self.env.L.kp1_route_episode_records(self.env._handle, C.c_void_p(dones.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()))
 
     def observe_chunk(self, records_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
         """data-parallel rollouts: the all-gathered [world, chunk_steps, n_local] episode records of a chunk of env steps, replayed in the
         reference's order (step by step, global env id order inside a step); a promotion moves this rank's reset window"""
         if not (records_all.numel() == world * chunk_steps * n_local and records_all.dtype == torch.uint8 and records_all.is_contiguous()):
             raise ValueError(f"observe_chunk() takes contiguous uint8 records of shape [{world}, {chunk_steps}, {n_local}]")
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
         native.check(self.env.L.kp1_route_curriculum_observe_chunk(self.env._handle, self._st, C.c_void_p(records_all.data_ptr()), int(n_local),
-                                                                   int(chunk_steps), int(world), C.c_void_p(stream)))
+                                                                   int(chunk_steps), int(world), self._stream()))
 
-    def read(self) -> _CurriculumState:
-        out = _CurriculumState()
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
-        native.check(self.env.L.kp1_route_curriculum_read(self.env._handle, self._st, C.byref(out), C.c_void_p(stream)))
-        self.env.route_cfg.reset.min_route_index, self.env.route_cfg.reset.max_route_index = 1, int(out.prefix_end_index[out.stage_index])
-        return out
+    def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:
+        return self.env.L.kp1_route_curriculum_read(self.env._handle, self._st, out, stream)
 
-    def summary(self) -> dict[str, object]:
-        return self._summary_of(self.read())
+    def _follow(self, st: _CurriculumState, k: int) -> None:
+        self.env.route_cfg.reset.min_route_index, self.env.route_cfg.reset.max_route_index = 1, int(st.prefix_end_index[st.stage_index])
 
     def _summary_of(self, st: _CurriculumState) -> dict[str, object]:
-        n = int(st.ring_len)
-
-        def mean(q: int) -> float:
-            return float(sum(st.ring[q][k] for k in range(n))) / float(n) if n else 0.0
-
         history = []
         for k in range(min(int(st.n_events), MAX_HISTORY)):
             e = st.events[k]
@@ -155,35 +148,26 @@ class RoutePrefixCurriculumDevice:
                             "recent_route_ready_hit_rate": float(e.recent_route_ready_hit_rate),
                             "recent_orientation_hit_rate": float(e.recent_orientation_hit_rate), "recent_regression_rate": float(e.recent_regression_rate)})
         stage = self.stages[int(st.stage_index)]
+        mean = [window_mean(st, st.ring[q]) for q in range(4)]
         return {"stage_index": int(st.stage_index), "stage_name": stage.name, "prefix_end_index": int(stage.prefix_end_index),
-                "stage_episode_count": int(st.stage_episode_count), "recent_success_rate": mean(0), "recent_route_ready_hit_rate": mean(1),
-                "recent_orientation_hit_rate": mean(2), "recent_regression_rate": mean(3), "history": history}
+                "stage_episode_count": int(st.stage_episode_count), "recent_success_rate": mean[0], "recent_route_ready_hit_rate": mean[1],
+                "recent_orientation_hit_rate": mean[2], "recent_regression_rate": mean[3], "history": history}
 
-    def close(self) -> None:
-        if self.env is not None and self._st.value:
-            self.env.L.kp1_route_curriculum_destroy(self.env._handle, self._st)
-            self._st = C.c_void_p()
+    def _destroy(self) -> None:
+        self.env.L.kp1_route_curriculum_destroy(self.env._handle, self._st)
 
 
-class RoutePrefixCurriculumPopulation(RoutePrefixCurriculumDevice):
+class RoutePrefixCurriculumPopulation(TrackerPopulation, RoutePrefixCurriculumDevice):
     """K device trackers, one per replica of a RoutePopulationVecEnv (include/kp1_route.h, kp1_route_curriculum_*_population).  ONE
     ``observe(dones[K N])`` launch per env step: workgroup k scans replica k's envs in env order, advances its clock by N and on promotion moves
     replica k's reset window only.  ``read(k)`` / ``summary(k)`` are RoutePrefixCurriculumDevice's of replica k; ``replica(k)`` is a view
     with read() / summary() for the per-replica lists of a population run.  There is no data-parallel (chunk) form."""
 
-    needs_episode_records = False
-
     def attach(self, env: RoutePopulationVecEnv) -> None:
         """_on_training_start of every replica: K trackers next to the population env, every window set to the first prefix"""
         if not isinstance(env, RoutePopulationVecEnv):
             raise TypeError("RoutePrefixCurriculumPopulation tracks the replicas of a RoutePopulationVecEnv")
-        self.env = env
-        L = env.L
-        prefixes = (C.c_int32 * len(self.stages))(*[int(s.prefix_end_index) for s in self.stages])
-        with torch.cuda.device(env.device):
-            native.check(L.kp1_route_curriculum_create_population(env._handle, prefixes, len(self.stages), *self._args, C.byref(self._st)))
-        env.route_cfg.reset.min_route_index, env.route_cfg.reset.max_route_index = 1, int(self.stages[0].prefix_end_index)
-        env._windows = [(1, int(self.stages[0].prefix_end_index))] * env.K
+        env._windows = [self._create(env, env.L.kp1_route_curriculum_create_population)] * env.K
 
     @property
     def K(self) -> int:
@@ -191,53 +175,18 @@ class RoutePrefixCurriculumPopulation(RoutePrefixCurriculumDevice):
 
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
         """dones: the K N done bytes of one population step; steps_per_call: env steps per replica this call stands for (N)"""
-        if dones.numel() != self.env.n_envs or dones.dtype != torch.uint8 or not dones.is_contiguous():
-            raise ValueError(f"observe() takes the contiguous uint8 done bytes of all {self.env.n_envs} envs of the population")
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
+        self._check_done_bytes(dones, dones.numel() == self.env.n_envs)
         native.check(self.env.L.kp1_route_curriculum_observe_population(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), int(steps_per_call),
-                                                                        C.c_void_p(stream)))
+                                                                        self._stream()))
 
-    def record(self, dones: torch.Tensor, out: torch.Tensor) -> None:
-        raise TypeError("the population tracker has no data-parallel form")
+    def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:
+        return self.env.L.kp1_route_curriculum_read_replica(self.env._handle, self._st, k, out, stream)
 
-    def observe_chunk(self, records_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
-        raise TypeError("the population tracker has no data-parallel form")
-
-    def read(self, k: int = 0) -> _CurriculumState:
-        out = _CurriculumState()
-        stream = torch.cuda.current_stream(self.env.device).cuda_stream
-        native.check(self.env.L.kp1_route_curriculum_read_replica(self.env._handle, self._st, int(k), C.byref(out), C.c_void_p(stream)))
-        self.env._windows[k] = (1, int(out.prefix_end_index[out.stage_index]))
-        return out
-
-    def summary(self, k: int = 0) -> dict[str, object]:
-        return self._summary_of(self.read(k))
-
-    def replica(self, k: int) -> "RouteCurriculumReplica":
-        return RouteCurriculumReplica(self, k)
+    def _follow(self, st: _CurriculumState, k: int) -> None:
+        self.env._windows[k] = (1, int(st.prefix_end_index[st.stage_index]))
 
 
-class RouteCurriculumReplica:
-    """Replica k of a RoutePrefixCurriculumPopulation: read() / summary() of its tracker.  The population observes all replicas at once."""
-
-    def __init__(self, pop: RoutePrefixCurriculumPopulation, k: int) -> None:
-        self.pop, self.k = pop, int(k)
-        self.stages = pop.stages
-
-    def attach(self, env: Any) -> None:
-        """(the population tracker is attached to the population env)"""
-
-    def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
-        raise TypeError("replica trackers are observed through RoutePrefixCurriculumPopulation.observe (one launch for all replicas)")
-
-    def read(self) -> _CurriculumState:
-        return self.pop.read(self.k)
-
-    def summary(self) -> dict[str, object]:
-        return self.pop.summary(self.k)
-
-    def close(self) -> None:
-        """(the population tracker owns the device state)"""
+RouteCurriculumReplica = TrackerReplica
 
 
 # --------------------------------------------------------------------------------------------- sequential evaluator

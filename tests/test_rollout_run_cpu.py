@@ -12,6 +12,8 @@ from rl_brain_trainer_amd import native
 from rl_brain_trainer_amd import population as kpop
 from rl_brain_trainer_amd import ppo as kppo
 from rl_brain_trainer_amd.curriculum import PointCurriculum, PointCurriculumPopulation
+from rl_brain_trainer_amd.finisher_tools import DockReverseCurriculum
+from rl_brain_trainer_amd.route_curriculum import RoutePrefixCurriculumDevice
 from rl_brain_trainer_amd.vec_env import ArmKinematicVecEnv
 
 COVERED = dict(step_covered=True, hidden=64, mode_name="approach", dist_enabled=False, has_step_callback=False, tracker_attached=False,
@@ -138,7 +140,8 @@ def test_ppo_chooses_its_path(monkeypatch):
     assert _fake_ppo(kppo.PPO, hidden=128, n_envs=4096)._whole_rollout   # no tracker: any env count
     assert _fake_ppo(kppo.PPO, tracker=point, n_envs=32)._whole_rollout
     assert not _fake_ppo(kppo.PPO, tracker=point, n_envs=40)._whole_rollout
-    assert not _fake_ppo(kppo.PPO, tracker=object(), n_envs=16)._whole_rollout     # some other tracker (route, dock): its own launches
+    for other in (RoutePrefixCurriculumDevice, DockReverseCurriculum):              # some other tracker: its own launches
+        assert not _fake_ppo(kppo.PPO, tracker=object.__new__(other), n_envs=16)._whole_rollout
     assert not _fake_ppo(kppo.PPO, hidden=256)._whole_rollout
     assert not _fake_ppo(kppo.PPO, mode="dock")._whole_rollout
     assert not _fake_ppo(kppo.PPO, dist_enabled=True)._whole_rollout
