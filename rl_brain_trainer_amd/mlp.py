@@ -10,8 +10,7 @@ from . import native
 OBS_DIM, OBS_PAD, ACT_DIM = 56, 64, 7
 
 
-def _p(t: torch.Tensor | None):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+_p = native.ptr
 
 
 def span_split(first_step: int, n_steps: int, cap: int) -> list[tuple[int, int]]:

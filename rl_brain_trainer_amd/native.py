@@ -174,6 +174,11 @@ def check(rc: int) -> None:
         raise Kp1Error(f"kp1 error {rc}: {msg}")
 
 
+def ptr(t):
+    """a tensor's device address as the ``void*`` argument of a C entry point; None (NULL) for None"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def component_names(mode: int) -> list[str]:
     L = load()
     return [L.kp1_component_name(mode, i).decode() for i in range(L.kp1_num_components(mode))]

@@ -18,7 +18,7 @@ import torch
 from . import config as kcfg
 from . import native
 from . import route_config as rcfg
-from .vec_env import ArmKinematicVecEnv, _view
+from .vec_env import ArmKinematicVecEnv, DeviceEnvHandle, PopulationEnvHandle, ReplicaEnv, _view
 
 
 class _RouteResetOpts(C.Structure):
@@ -40,7 +40,7 @@ CHAIN_RECORD = np.dtype([(n, "<i4") for n in ("route_index", "success", "route_r
 assert CHAIN_RECORD.itemsize == 312
 
 
-class RouteVecEnv:
+class RouteVecEnv(DeviceEnvHandle):
     """``route_q``: [W, 7] joint goals of the dense route (route_config.load_route_q); ``base_config``: the env block of the route
     YAML (approach mode); ``route_cfg``: route_config.route_config_from_dict(cfg, max_route_index=first prefix)."""
 
@@ -61,12 +61,7 @@ class RouteVecEnv:
         with torch.cuda.device(self.device):
             self._create(route_cfg, seed, first_env_id)
         self.obs_dim = int(self.L.kp1_route_obs_dim(self._handle))
-        self.obs_stride = self.obs_dim
-        n = self.n_envs
-        self.obs = torch.zeros((n, self.obs_dim), dtype=torch.float32, device=self.device)
-        self.terminal_obs = torch.zeros_like(self.obs)
-        self.reward = torch.zeros(n, dtype=self.dtype, device=self.device)
-        self.done = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self._alloc_buffers(self.obs_dim)
         W = self.n_waypoints
         self.poses6 = np.zeros((W, 6))
         self.route_progress_m = np.zeros(W)
@@ -84,27 +79,32 @@ class RouteVecEnv:
         native.check(self.L.kp1_route_create(self.base._handle, C.byref(route_cfg), C.c_void_p(self.route_q.ctypes.data), self.n_waypoints, int(seed),
                                              int(first_env_id), C.byref(self._handle)))
 
-    def close(self) -> None:
-        if getattr(self, "_handle", None) is not None and self._handle.value:
-            self.L.kp1_route_destroy(self._handle)
-            self._handle = C.c_void_p()
-        self.base.close()
+    # ------------------------------------------------------------------ the family's C calls behind DeviceEnvHandle
+    def _step_call(self, *ptrs: Any) -> int:
+        return self.L.kp1_route_step(self._handle, *ptrs)
 
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _rng_get_call(self, arr: Any) -> int:
+        return self.L.kp1_route_rng_get(self._handle, arr)
+
+    def _rng_set_call(self, arr: Any) -> int:
+        return self.L.kp1_route_rng_set(self._handle, arr)
+
+    def _set_obs_stride_call(self, stride: int) -> int:
+        return self.L.kp1_route_set_obs_stride(self._handle, stride)      # (unlike the arm handle's, no launch_args_version bump)
+
+    def _destroy(self) -> None:
+        self.L.kp1_route_destroy(self._handle)
+
+    def close(self) -> None:
+        """the wrapper first, then the base handle it was made on"""
+        super().close()
+        self.base.close()
 
     # ------------------------------------------------------------------ reference API
     def set_route_window(self, *, max_route_index: int, min_route_index: int = 1) -> None:
         native.check(self.L.kp1_route_set_window(self._handle, int(min_route_index), int(max_route_index)))
         self.route_cfg.reset.min_route_index = int(min_route_index)
         self.route_cfg.reset.max_route_index = int(max_route_index)
-
-    def env_method(self, name: str, *args: Any, **kwargs: Any) -> list[Any]:
-        result = getattr(self, name)(*args, **kwargs)
-        return [result] * self.n_envs
 
     def seed(self, seed: int, first_env_id: int = 0) -> None:
         native.check(self.L.kp1_route_seed(self._handle, int(seed), int(first_env_id)))
@@ -135,40 +135,15 @@ class RouteVecEnv:
             for key in ("initial_q", "initial_dq", "initial_prev_action"):
                 setattr(opts, key, mats(options[key]) if key in options else None)
             opts.evaluator_state = int(bool(options.get("evaluator_state", False)))
-        m = None
-        if mask is not None:
-            m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        m = self._reset_mask(mask)
+        if m is not None:
             self._keep.append(m)
-        native.check(self.L.kp1_route_reset(self._handle, C.c_void_p(m.data_ptr()) if m is not None else None, C.byref(opts) if opts is not None else None,
-                                            C.c_void_p(self.obs.data_ptr())))
+        native.check(self.L.kp1_route_reset(self._handle, native.ptr(m), C.byref(opts) if opts is not None else None, native.ptr(self.obs)))
         return self.obs
 
     def use_current_stream(self) -> None:
         """Order this handle's launches on torch's current stream (the wrapper kernels run on the base handle's stream)."""
         self.base.use_current_stream()
-
-    def set_obs_stride(self, stride: int) -> None:
-        """Row pitch of every observation buffer handed to reset / step (obs_dim, or the MFMA kernels' padded 64 / 128)."""
-        native.check(self.L.kp1_route_set_obs_stride(self._handle, int(stride)))
-        self.obs_stride = int(stride)
-        self.obs = torch.zeros((self.n_envs, self.obs_stride), dtype=torch.float32, device=self.device)
-        self.terminal_obs = torch.zeros_like(self.obs)
-
-    def step_into(self, actions: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, terminal_obs: torch.Tensor | None,
-                  auto_reset: bool = True) -> None:
-        """Zero-copy variant used by the PPO rollout loop (ArmKinematicVecEnv.step_into): outputs go into caller-owned buffers."""
-        native.check(self.L.kp1_route_step(self._handle, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()), C.c_void_p(reward.data_ptr()),
-                                           C.c_void_p(done.data_ptr()), C.c_void_p(terminal_obs.data_ptr()) if terminal_obs is not None else None,
-                                           int(auto_reset)))
-
-    def step(self, actions: torch.Tensor, *, auto_reset: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """actions [N, 7] in the env's real type; returns (obs [N, obs_dim], reward [N], done bits [N] uint8)."""
-        if actions.shape != (self.n_envs, kcfg.NJ):
-            raise ValueError(f"Expected action shape {(self.n_envs, kcfg.NJ)}, got {tuple(actions.shape)}")
-        a = actions.to(device=self.device, dtype=self.dtype).contiguous()
-        native.check(self.L.kp1_route_step(self._handle, C.c_void_p(a.data_ptr()), C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.reward.data_ptr()),
-                                           C.c_void_p(self.done.data_ptr()), C.c_void_p(self.terminal_obs.data_ptr()), int(auto_reset)))
-        return self.obs, self.reward, self.done
 
     @staticmethod
     def obs_dict(obs: torch.Tensor) -> dict[str, torch.Tensor]:
@@ -179,8 +154,7 @@ class RouteVecEnv:
         """Base env info (ArmKinematicVecEnv.info) plus the wrapper's keys; tensors are views of device state."""
         v = _RouteInfoView()
         native.check(self.L.kp1_route_get_info(self._handle, C.byref(v)))
-        n = self.n_envs
-        ts = "<f4" if self.dtype == torch.float32 else "<f8"
+        n, ts = self.n_envs, self._typestr
         out = dict(self.base.info())
         for key, name in (("route_index", "route_index"), ("start_route_index", "start_route_index"), ("last_route_index", "last_route_index"),
                           ("route_reset_mode", "reset_mode"), ("route_ready_streak", "ready_streak"), ("route_completed_waypoints", "completed_waypoints")):
@@ -212,21 +186,7 @@ class RouteVecEnv:
     def reward_components(self) -> tuple[list[str], torch.Tensor]:
         p = C.c_void_p()
         native.check(self.L.kp1_route_get_reward_components(self._handle, C.byref(p)))
-        ts = "<f4" if self.dtype == torch.float32 else "<f8"
-        return list(rcfg.COMPONENT_NAMES), _view(p.value, (len(rcfg.COMPONENT_NAMES), self.n_envs), ts, self.device)
-
-    def rng_state(self) -> np.ndarray:
-        arr = (kcfg.RngState * self.n_envs)()
-        native.check(self.L.kp1_route_rng_get(self._handle, arr))
-        return np.array([[s.state_hi, s.state_lo, s.inc_hi, s.inc_lo, s.has_uint32, s.uinteger] for s in arr], dtype=np.uint64)
-
-    def set_rng_state(self, words: np.ndarray) -> None:
-        """the wrapper's PCG64 streams <- [N, 6] words in rng_state()'s layout"""
-        arr = (kcfg.RngState * self.n_envs)()
-        for i in range(self.n_envs):
-            (arr[i].state_hi, arr[i].state_lo, arr[i].inc_hi, arr[i].inc_lo) = (int(w) for w in words[i][:4])
-            arr[i].has_uint32, arr[i].uinteger = int(words[i][4]), int(words[i][5])
-        native.check(self.L.kp1_route_rng_set(self._handle, arr))
+        return list(rcfg.COMPONENT_NAMES), _view(p.value, (len(rcfg.COMPONENT_NAMES), self.n_envs), self._typestr, self.device)
 
     def get_state(self) -> dict[str, np.ndarray]:
         return self.base.get_state()
@@ -262,13 +222,12 @@ class RouteChain:
         self._n_alive = _view(v.n_alive, (1,), "<i4", env.device)
 
     def begin(self, obs: torch.Tensor) -> None:
-        native.check(self.env.L.kp1_route_chain_begin(self.env._handle, self._h, C.c_void_p(obs.data_ptr())))
+        native.check(self.env.L.kp1_route_chain_begin(self.env._handle, self._h, native.ptr(obs)))
 
     def step(self, actions: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, tags: torch.Tensor | None = None) -> None:
         """actions [R, 7] f32 (read), obs [R, stride] (next observations), reward [R], done [R] uint8, tags [R, 2] int32 or None"""
-        native.check(self.env.L.kp1_route_chain_step(self.env._handle, self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
-                                                     C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()),
-                                                     C.c_void_p(tags.data_ptr()) if tags is not None else None))
+        p = native.ptr
+        native.check(self.env.L.kp1_route_chain_step(self.env._handle, self._h, p(actions), p(obs), p(reward), p(done), p(tags)))
 
     def forward_step(self, mlp, obs: torch.Tensor, next_obs: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, *,
                      action: torch.Tensor | None = None, tags: torch.Tensor | None = None) -> None:
@@ -277,7 +236,7 @@ class RouteChain:
         replica-major; ``obs`` at the pitch set with ``env.set_obs_stride``; ``next_obs`` is ``obs`` itself (in place) or disjoint from it.  A
         row whose chain has ended is not stepped: it gets its {-1, -1} tag and nothing else of it is written."""
         assert obs.is_contiguous() and obs.dtype == torch.float32 and obs.shape[0] == self.env.n_envs
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+        p = native.ptr
         native.check(self.env.L.kp1_mlp_forward_route_chain_step(mlp._h, self.env._handle, self._h, p(obs), int(obs.shape[1]), p(action), p(next_obs),
                                                                  p(reward), p(done), p(tags), mlp._stream()))
 
@@ -285,8 +244,8 @@ class RouteChain:
         """``n_steps`` lock steps (1 .. native.ROUTE_CHAIN_RUN_MAX_STEPS) of ``forward_step`` in ONE launch, in place on ``obs``
         (kp1_route_chain_run); ``alive()`` afterwards is the number of rows still running after the last step."""
         assert obs.is_contiguous() and obs.dtype == torch.float32 and obs.shape[0] == self.env.n_envs
-        native.check(self.env.L.kp1_route_chain_run(mlp._h, self.env._handle, self._h, C.c_void_p(obs.data_ptr()), int(obs.shape[1]),
-                                                    C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), int(n_steps), mlp._stream()))
+        native.check(self.env.L.kp1_route_chain_run(mlp._h, self.env._handle, self._h, native.ptr(obs), int(obs.shape[1]), native.ptr(reward),
+                                                    native.ptr(done), int(n_steps), mlp._stream()))
 
     def alive(self) -> int:
         """rows still running after the last step (synchronises)"""
@@ -304,36 +263,42 @@ class RouteChain:
             self._h = C.c_void_p()
 
 
-class RoutePopulationVecEnv(RouteVecEnv):
+class RouteReplicaEnv(ReplicaEnv):
+    """Replica k of a RoutePopulationVecEnv: with the route dataset the evaluators read, and the route config as this replica sees it.  (No
+    ``snapshot`` / ``restore``: PPO rolls a graph warm-up on a route env back with a fresh reset.)"""
+
+    def __init__(self, pop: "RoutePopulationVecEnv", k: int) -> None:
+        super().__init__(pop, k)
+        self.route_q, self.n_waypoints, self.route_progress_m = pop.route_q, pop.n_waypoints, pop.route_progress_m
+
+    @property
+    def route_cfg(self) -> rcfg.RouteConfig:
+        """a copy of the shared config with replica k's reset window"""
+        cfg = rcfg.RouteConfig.from_buffer_copy(self.pop.route_cfg)
+        cfg.reset.min_route_index, cfg.reset.max_route_index = self.pop.window(self.k)
+        return cfg
+
+
+class RoutePopulationVecEnv(PopulationEnvHandle, RouteVecEnv):
     """K route envs of ``n_per_replica`` envs each in ONE handle (include/kp1_route.h, kp1_route_create_population): block k = rows
     [k N, (k + 1) N) is replica k, and is bit for bit ``RouteVecEnv(..., n_per_replica, seed=seeds[k])``.  One ``step_into`` / ``reset``
     covers all K N rows, so a population rollout is one route step per env step whatever K is -- the [K N, obs_w] buffers are the population
     rollout's replica-major layout.  The config is shared except the reset window, which each replica has of its own (``set_route_window``
     sets every window, ``set_replica_window`` one).  ``replica(k)`` is a view with what PPO's setup and ``checkpoint.save`` read."""
 
+    replica_type = RouteReplicaEnv
+
     def __init__(self, base_config: kcfg.EnvConfig, route_cfg: rcfg.RouteConfig, route_q: np.ndarray, seeds: list[int], n_per_replica: int, *,
                  device: int | torch.device = 0, reward_components: bool = False) -> None:
-        self.seeds = [int(s) for s in seeds]
-        if not self.seeds:
-            raise ValueError("RoutePopulationVecEnv needs at least one seed")
-        self.K = len(self.seeds)
-        self.n_per_replica = int(n_per_replica)
-        if self.n_per_replica < 1:
-            raise ValueError("n_per_replica must be positive")
+        self._take_seeds(seeds)
+        n_envs = self._take_blocks(n_per_replica)
         self._windows = [(int(route_cfg.reset.min_route_index), int(route_cfg.reset.max_route_index))] * self.K
-        super().__init__(base_config, route_cfg, route_q, self.K * self.n_per_replica, device=device, seed=self.seeds[0], real="f32",
-                         reward_components=reward_components)
+        super().__init__(base_config, route_cfg, route_q, n_envs, device=device, seed=self.seeds[0], real="f32", reward_components=reward_components)
 
     def _create(self, route_cfg: rcfg.RouteConfig, seed: int, first_env_id: int) -> None:
         seeds = (C.c_uint64 * self.K)(*self.seeds)
         native.check(self.L.kp1_route_create_population(self.base._handle, C.byref(route_cfg), C.c_void_p(self.route_q.ctypes.data), self.n_waypoints,
                                                         C.cast(seeds, C.c_void_p), self.K, C.byref(self._handle)))
-
-    def replica(self, k: int) -> "RouteReplicaEnv":
-        return RouteReplicaEnv(self, k)
-
-    def rows(self, k: int) -> slice:
-        return slice(k * self.n_per_replica, (k + 1) * self.n_per_replica)
 
     def set_route_window(self, *, max_route_index: int, min_route_index: int = 1) -> None:
         super().set_route_window(max_route_index=max_route_index, min_route_index=min_route_index)
@@ -346,45 +311,3 @@ class RoutePopulationVecEnv(RouteVecEnv):
     def window(self, k: int) -> tuple[int, int]:
         """host copy of replica k's reset window (a tracker promotion moves the device copy; RoutePrefixCurriculumPopulation.read(k) syncs it)"""
         return self._windows[k]
-
-    def seed(self, seed: int, first_env_id: int = 0) -> None:
-        raise ValueError("a population route env keeps the per-block seeds it was created with (env i of replica k: seeds[k] + i)")
-
-
-class RouteReplicaEnv:
-    """Replica k of a RoutePopulationVecEnv: the attributes PPO's setup, ReplicaView and ``checkpoint.save`` read.  Stepping and resetting
-    go through the population handle (one launch for all replicas)."""
-
-    def __init__(self, pop: RoutePopulationVecEnv, k: int) -> None:
-        self.pop, self.k = pop, int(k)
-        self.n_envs = pop.n_per_replica
-        self.device, self.dtype, self.obs_dim, self.config = pop.device, pop.dtype, pop.obs_dim, pop.config
-        self.route_q, self.n_waypoints, self.route_progress_m = pop.route_q, pop.n_waypoints, pop.route_progress_m
-        self.seed = pop.seeds[self.k]
-
-    @property
-    def route_cfg(self) -> rcfg.RouteConfig:
-        cfg = rcfg.RouteConfig.from_buffer_copy(self.pop.route_cfg)
-        cfg.reset.min_route_index, cfg.reset.max_route_index = self.pop.window(self.k)
-        return cfg
-
-    @property
-    def obs_stride(self) -> int:
-        return self.pop.obs_stride
-
-    @property
-    def launch_args_version(self) -> int:
-        return self.pop.launch_args_version
-
-    def set_obs_stride(self, stride: int) -> None:
-        if int(stride) != self.pop.obs_stride:
-            self.pop.set_obs_stride(stride)
-
-    def use_current_stream(self) -> None:
-        self.pop.use_current_stream()
-
-    def reset(self, **_: Any) -> torch.Tensor:
-        raise TypeError("a replica of a RoutePopulationVecEnv is reset through the population handle (one reset of all replicas)")
-
-    def close(self) -> None:
-        """(the population handle owns the envs)"""

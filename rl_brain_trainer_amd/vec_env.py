@@ -31,7 +31,90 @@ def _view(ptr: int, shape: tuple[int, ...], typestr: str, device: torch.device) 
     return torch.as_tensor(_DevView(ptr, shape, typestr), device=device)
 
 
-class ArmKinematicVecEnv:
+def _stream_arg(device: torch.device) -> C.c_void_p:
+    """torch's current stream on ``device`` as the ``hipStream_t`` argument of a launch"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+class DeviceEnvHandle:
+    """What the env handle families share: the handle-owned step outputs, ``step`` / ``step_into``, the PCG64 state
+    round trip, the reset mask, ``env_method`` and the lifetime.  A family sets ``L``, ``_handle``, ``n_envs``, ``device`` and ``dtype``,
+    makes its create call, and supplies the one-line methods that hold its C calls: ``_step_call(*ptrs)``, ``_rng_get_call(arr)``,
+    ``_rng_set_call(arr)``, ``_set_obs_stride_call(stride)`` and ``_destroy()``."""
+
+    _typestr = property(lambda self: "<f4" if self.dtype == torch.float32 else "<f8")     # of a _view of the handle's real-typed state
+
+    def _alloc_obs(self, stride: int) -> None:
+        self.obs_stride = int(stride)
+        self.obs = torch.zeros((self.n_envs, self.obs_stride), dtype=torch.float32, device=self.device)
+        self.terminal_obs = torch.zeros_like(self.obs)
+
+    def _alloc_buffers(self, stride: int) -> None:
+        """the buffers ``reset`` and ``step`` write: observation rows at pitch ``stride``, reward in the env's real type, done bits"""
+        self._alloc_obs(stride)
+        self.reward = torch.zeros(self.n_envs, dtype=self.dtype, device=self.device)
+        self.done = torch.zeros(self.n_envs, dtype=torch.uint8, device=self.device)
+
+    def set_obs_stride(self, stride: int) -> None:
+        """Row pitch of every observation buffer handed to reset / step (the observation width, or the MFMA kernels' zero-padded 64 / 128)."""
+        native.check(self._set_obs_stride_call(int(stride)))
+        self._alloc_obs(stride)
+
+    def close(self) -> None:
+        if getattr(self, "_handle", None) is not None and self._handle.value:
+            self._destroy()
+            self._handle = C.c_void_p()
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def env_method(self, name: str, *args: Any, **kwargs: Any) -> list[Any]:
+        """VecEnv.env_method: the trainers only broadcast (callbacks.py:55,69,162)."""
+        result = getattr(self, name)(*args, **kwargs)
+        return [result] * self.n_envs
+
+    def _reset_mask(self, mask: torch.Tensor | None) -> torch.Tensor | None:
+        """reset(mask=) as contiguous bytes on the handle's device (the caller keeps them alive over the call)"""
+        return None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+
+    def _host_rows(self, val: Any, width: int, keep: list[np.ndarray]) -> int:
+        """address of ``val`` broadcast to [N, width] contiguous float64 rows in host memory, which ``keep`` holds alive over the call"""
+        keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(val, dtype=np.float64), (self.n_envs, width))))
+        return keep[-1].ctypes.data
+
+    def step(self, actions: torch.Tensor, *, auto_reset: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """step(actions[N,7]) -> (obs[N,stride] f32, reward[N], done[N] u8 bitmask).  Finished episodes are reset in the
+        same launch (VecEnv semantics); their last observation is in ``self.terminal_obs``."""
+        if actions.shape != (self.n_envs, kcfg.NJ):
+            raise ValueError(f"Expected action shape {(self.n_envs, kcfg.NJ)}, got {tuple(actions.shape)}")
+        self.step_into(actions.to(device=self.device, dtype=self.dtype).contiguous(), self.obs, self.reward, self.done, self.terminal_obs, auto_reset)
+        return self.obs, self.reward, self.done
+
+    def step_into(self, actions: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor, done: torch.Tensor,
+                  terminal_obs: torch.Tensor | None, auto_reset: bool = True) -> None:
+        """Zero-copy variant used by the rollout loop: outputs go straight into caller-owned (rollout) buffers."""
+        native.check(self._step_call(native.ptr(actions), native.ptr(obs), native.ptr(reward), native.ptr(done), native.ptr(terminal_obs),
+                                     int(auto_reset)))
+
+    def rng_state(self) -> np.ndarray:
+        """[N,6] uint64 words (state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger) of each env's PCG64 stream."""
+        arr = (kcfg.RngState * self.n_envs)()
+        native.check(self._rng_get_call(arr))
+        return np.array([[s.state_hi, s.state_lo, s.inc_hi, s.inc_lo, s.has_uint32, s.uinteger] for s in arr], dtype=np.uint64)
+
+    def set_rng_state(self, words: np.ndarray) -> None:
+        """the handle's PCG64 streams <- [N, 6] words in rng_state()'s layout"""
+        arr = (kcfg.RngState * self.n_envs)()
+        for i in range(self.n_envs):
+            (arr[i].state_hi, arr[i].state_lo, arr[i].inc_hi, arr[i].inc_lo) = (int(w) for w in words[i][:4])
+            arr[i].has_uint32, arr[i].uinteger = int(words[i][4]), int(words[i][5])
+        native.check(self._rng_set_call(arr))
+
+
+class ArmKinematicVecEnv(DeviceEnvHandle):
     """N kinematic_phase1 environments on one MI355X.
 
     Parameters mirror ``make_vec_env(ArmKinematicEnv, n_envs, seed)``: env ``i`` owns the numpy
@@ -50,42 +133,38 @@ class ArmKinematicVecEnv:
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.real_type = {"f32": native.REAL_F32, "f64": native.REAL_F64}[real]
         self.dtype = torch.float32 if real == "f32" else torch.float64
-        self._typestr = "<f4" if real == "f32" else "<f8"
         self._handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
             native.check(self.L.kp1_create(C.byref(config.c), self.n_envs, self.device.index or 0, self.real_type,
-                                           int(seed), int(first_env_id), C.c_void_p(stream), C.byref(self._handle)))
+                                           int(seed), int(first_env_id), _stream_arg(self.device), C.byref(self._handle)))
         if config.handoff_states:
             arr = config.handoff_array()
             native.check(self.L.kp1_set_handoff_states(self._handle, C.cast(arr, C.c_void_p), len(config.handoff_states)))
         if config.route_reset.active:
             self.set_route_stride_reset(config.route_reset)
-        n = self.n_envs
-        self.obs = torch.zeros((n, kcfg.OBS_DIM), dtype=torch.float32, device=self.device)
-        self.terminal_obs = torch.zeros((n, kcfg.OBS_DIM), dtype=torch.float32, device=self.device)
-        self.reward = torch.zeros(n, dtype=self.dtype, device=self.device)
-        self.done = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self._alloc_buffers(kcfg.OBS_DIM)
         self._mode_name = config.mode_name
-        self.obs_stride = kcfg.OBS_DIM
-        self._components = False
         # bumped by every setter whose value a captured hipGraph of kp1_step would have frozen into kernel arguments (stage, mode, config,
         # reward-component switch, handoff buffer, observation pitch): ppo.PPO re-captures its rollout graph when it changes
         self.launch_args_version = 0
         if reward_components:
             self.enable_reward_components(True)
 
-    # ------------------------------------------------------------------ lifecycle
-    def close(self) -> None:
-        if getattr(self, "_handle", None) is not None and self._handle.value:
-            self.L.kp1_destroy(self._handle)
-            self._handle = C.c_void_p()
+    # ------------------------------------------------------------------ the family's C calls behind DeviceEnvHandle
+    def _step_call(self, *ptrs: Any) -> int:
+        return self.L.kp1_step(self._handle, *ptrs)
 
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _rng_get_call(self, arr: Any) -> int:
+        return self.L.kp1_rng_get(self._handle, arr)
+
+    def _rng_set_call(self, arr: Any) -> int:
+        return self.L.kp1_rng_set(self._handle, arr)
+
+    def _set_obs_stride_call(self, stride: int) -> int:
+        return self.L.kp1_set_obs_stride(self._handle, stride)
+
+    def _destroy(self) -> None:
+        self.L.kp1_destroy(self._handle)
 
     # ------------------------------------------------------------------ reference API
     def set_curriculum_stage(self, stage_index: int) -> None:
@@ -103,11 +182,6 @@ class ArmKinematicVecEnv:
         native.check(self.L.kp1_set_mode(self._handle, kcfg.MODE_NAMES[mode_name]))
         self._mode_name = mode_name
         self.launch_args_version += 1
-
-    def env_method(self, name: str, *args: Any) -> list[Any]:
-        """VecEnv.env_method: the trainers only broadcast (callbacks.py:55,69,162)."""
-        result = getattr(self, name)(*args)
-        return [result] * self.n_envs
 
     def apply_dock_training_stage(self, stage_updates: dict[str, Any]) -> None:
         """arm_kinematic_env.py:459-487: env scalar + dock_reset overrides for the dock curriculum."""
@@ -160,12 +234,9 @@ class ArmKinematicVecEnv:
         self.config.route_reset = rr
 
     def set_obs_stride(self, stride: int) -> None:
-        """Row pitch of every observation buffer handed to reset/step (56, or 64 = zero-padded for the MFMA GEMMs)."""
-        native.check(self.L.kp1_set_obs_stride(self._handle, int(stride)))
-        self.obs_stride = int(stride)
+        """(56, or 64 = zero-padded for the MFMA GEMMs; the pitch is a kernel argument of kp1_step, hence the bump)"""
+        super().set_obs_stride(stride)
         self.launch_args_version += 1
-        self.obs = torch.zeros((self.n_envs, self.obs_stride), dtype=torch.float32, device=self.device)
-        self.terminal_obs = torch.zeros_like(self.obs)
 
     def seed(self, seed: int, first_env_id: int = 0) -> None:
         native.check(self.L.kp1_seed(self._handle, int(seed), int(first_env_id)))
@@ -185,13 +256,10 @@ class ArmKinematicVecEnv:
                 if val is None:
                     continue
                 arr = np.asarray(val, dtype=np.float64)
-                if arr.ndim == 1:
-                    arr = np.broadcast_to(arr, (self.n_envs, arr.shape[0]))
-                if arr.shape != (self.n_envs, width):
-                    raise ValueError(f"options['{key}'] must have shape ({self.n_envs}, {width}), got {arr.shape}")
-                arr = np.ascontiguousarray(arr)
-                keep.append(arr)
-                setattr(o, key, arr.ctypes.data)
+                shape = (self.n_envs, arr.shape[0]) if arr.ndim == 1 else arr.shape      # one row stands for every env
+                if shape != (self.n_envs, width):
+                    raise ValueError(f"options['{key}'] must have shape ({self.n_envs}, {width}), got {shape}")
+                setattr(o, key, self._host_rows(arr, width, keep))
             pm = options.get("policy_mode")
             if pm is not None:
                 if pm not in kcfg.MODE_NAMES:
@@ -201,27 +269,13 @@ class ArmKinematicVecEnv:
             opts_p = C.byref(o)
         else:
             self._mode_name = self.config.mode_name
-        mask_ptr = None
-        if mask is not None:
-            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mask_ptr = C.c_void_p(mask.data_ptr())
-        native.check(self.L.kp1_reset(self._handle, mask_ptr, opts_p, C.c_void_p(self.obs.data_ptr())))
+        mask = self._reset_mask(mask)
+        native.check(self.L.kp1_reset(self._handle, native.ptr(mask), opts_p, native.ptr(self.obs)))
         return self.obs
-
-    def step(self, actions: torch.Tensor, *, auto_reset: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """step(actions[N,7]) -> (obs[N,56] f32, reward[N], done[N] u8 bitmask).  Finished episodes are reset in the
-        same launch (VecEnv semantics); their last observation is in ``self.terminal_obs``."""
-        if actions.shape != (self.n_envs, kcfg.NJ):
-            raise ValueError(f"Expected action shape {(self.n_envs, kcfg.NJ)}, got {tuple(actions.shape)}")
-        a = actions.to(device=self.device, dtype=self.dtype).contiguous()
-        native.check(self.L.kp1_step(self._handle, C.c_void_p(a.data_ptr()), C.c_void_p(self.obs.data_ptr()),
-                                     C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                     C.c_void_p(self.terminal_obs.data_ptr()), int(auto_reset)))
-        return self.obs, self.reward, self.done
 
     def use_current_stream(self) -> None:
         """Order this handle's launches on torch's current stream (call inside torch.cuda.graph capture / stream contexts)."""
-        native.check(self.L.kp1_set_stream(self._handle, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        native.check(self.L.kp1_set_stream(self._handle, _stream_arg(self.device)))
 
     def snapshot(self) -> None:
         """Device-side copy of the whole env state (all fields, counters and PCG64 streams), ordered on the handle's stream."""
@@ -231,16 +285,9 @@ class ArmKinematicVecEnv:
         """Put the state of the last snapshot() back (episodes and random streams continue exactly from there)."""
         native.check(self.L.kp1_state_restore(self._handle))
 
-    def step_into(self, actions: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor, done: torch.Tensor,
-                  terminal_obs: torch.Tensor | None, auto_reset: bool = True) -> None:
-        """Zero-copy variant used by the rollout loop: outputs go straight into caller-owned (rollout) buffers."""
-        native.check(self.L.kp1_step(self._handle, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
-                                     C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()),
-                                     C.c_void_p(terminal_obs.data_ptr()) if terminal_obs is not None else None, int(auto_reset)))
-
     def current_observation(self) -> torch.Tensor:
         out = torch.empty_like(self.obs)
-        native.check(self.L.kp1_observe(self._handle, C.c_void_p(out.data_ptr())))
+        native.check(self.L.kp1_observe(self._handle, native.ptr(out)))
         return out
 
     @staticmethod
@@ -275,7 +322,6 @@ class ArmKinematicVecEnv:
     def enable_reward_components(self, enable: bool = True) -> None:
         native.check(self.L.kp1_enable_reward_components(self._handle, int(enable)))
         self._reward_components_on = bool(enable)
-        self._components = bool(enable)
         self.launch_args_version += 1
 
     def reward_components(self) -> tuple[list[str], torch.Tensor]:
@@ -291,35 +337,93 @@ class ArmKinematicVecEnv:
         return out
 
     def set_state(self, *, q=None, dq=None, prev_action=None, goal_q=None, goal_pose6=None, capture_entry_metrics: bool = True) -> None:
-        ptrs, keep = [], []
-        for val, w in ((q, 7), (dq, 7), (prev_action, 7), (goal_q, 7), (goal_pose6, 6)):
-            if val is None:
-                ptrs.append(None)
-                continue
-            arr = np.ascontiguousarray(np.broadcast_to(np.asarray(val, dtype=np.float64), (self.n_envs, w)))
-            keep.append(arr)
-            ptrs.append(arr.ctypes.data)
+        keep: list[np.ndarray] = []
+        ptrs = [None if val is None else self._host_rows(val, w, keep) for val, w in ((q, 7), (dq, 7), (prev_action, 7), (goal_q, 7), (goal_pose6, 6))]
         native.check(self.L.kp1_set_state(self._handle, *ptrs, int(capture_entry_metrics)))
 
-    def rng_state(self) -> np.ndarray:
-        """[N,6] uint64 words (state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger) of each env's PCG64 stream."""
-        arr = (kcfg.RngState * self.n_envs)()
-        native.check(self.L.kp1_rng_get(self._handle, arr))
-        return np.array([[s.state_hi, s.state_lo, s.inc_hi, s.inc_lo, s.has_uint32, s.uinteger] for s in arr], dtype=np.uint64)
 
-    def set_rng_state(self, words: np.ndarray) -> None:
-        arr = (kcfg.RngState * self.n_envs)()
-        for i in range(self.n_envs):
-            (arr[i].state_hi, arr[i].state_lo, arr[i].inc_hi, arr[i].inc_lo) = (int(w) for w in words[i][:4])
-            arr[i].has_uint32, arr[i].uinteger = int(words[i][4]), int(words[i][5])
-        native.check(self.L.kp1_rng_set(self._handle, arr))
+class ReplicaEnv:
+    """Replica k of a population handle: the attributes PPO's setup, ReplicaView, ``checkpoint.save`` and the evaluators read.  Stepping and
+    resetting go through the population handle (one launch for all replicas).  A family's view adds what only that family has."""
 
+    def __init__(self, pop: Any, k: int) -> None:
+        self.pop, self.k = pop, int(k)
+        self.n_envs = pop.n_per_replica
+        self.device, self.dtype, self.config = pop.device, pop.dtype, pop.config
+        self.obs_dim = getattr(pop, "obs_dim", kcfg.OBS_DIM)
+        self.seed = pop.seeds[self.k]
+
+    @property
+    def launch_args_version(self) -> int:
+        return self.pop.launch_args_version
+
+    @property
+    def obs_stride(self) -> int:
+        return self.pop.obs_stride
+
+    def set_obs_stride(self, stride: int) -> None:
+        if int(stride) != self.pop.obs_stride:
+            self.pop.set_obs_stride(stride)
+
+    def use_current_stream(self) -> None:
+        self.pop.use_current_stream()
+
+    def reset(self, **_: Any) -> torch.Tensor:
+        name = type(self.pop).__name__
+        raise TypeError(f"a replica of {'an' if name[0] in 'AEIOU' else 'a'} {name} is reset through the population handle (one reset of all replicas)")
+
+    def close(self) -> None:
+        """(the population handle owns the envs)"""
+
+
+class ArmKinematicReplicaEnv(ReplicaEnv):
+    """Replica k of an ArmKinematicPopulationVecEnv.  It has ``snapshot`` / ``restore``, by which PPO rolls a graph warm-up back (a view
+    without them gets a fresh reset): the whole population handle's, so every replica's view takes the same snapshot."""
+
+    def snapshot(self) -> None:
+        self.pop.snapshot()
+
+    def restore(self) -> None:
+        self.pop.restore()
+
+
+class PopulationEnvHandle:
+    """The population half of an env handle, in front of the family's single class (``class XPopulationVecEnv(PopulationEnvHandle, XVecEnv)``):
+    K replicas of ``n_per_replica`` envs each in ONE handle, block k = rows [k N, (k + 1) N), created with per-block seeds that it keeps.
+    The family's constructor calls ``_take_seeds``, makes the refusals of its own, calls ``_take_blocks`` and creates its handle with
+    ``seeds[0]`` before it seeds the blocks; ``replica_type`` is its view."""
+
+    replica_type: type = ReplicaEnv
+
+    def _take_seeds(self, seeds: Any) -> None:
+        self.seeds = [int(s) for s in seeds]
+        if not self.seeds:
+            raise ValueError(f"{type(self).__name__} needs at least one seed")
+
+    def _take_blocks(self, n_per_replica: int) -> int:
+        """-> the handle's env count K N"""
+        self.K = len(self.seeds)
+        self.n_per_replica = int(n_per_replica)
+        if self.n_per_replica < 1:
+            raise ValueError("n_per_replica must be positive")
+        return self.K * self.n_per_replica
+
+    def replica(self, k: int) -> ReplicaEnv:
+        if not 0 <= int(k) < self.K:
+            raise IndexError(f"replica {k} of a population of {self.K}")
+        return self.replica_type(self, int(k))
+
+    def rows(self, k: int) -> slice:
+        return slice(k * self.n_per_replica, (k + 1) * self.n_per_replica)
+
+    def seed(self, seed: int, first_env_id: int = 0) -> None:
+        raise ValueError("a population env keeps the per-block seeds it was created with (env i of replica k: seeds[k] + i)")
 
 
 MAX_REPLICAS = native.header_int("KP1_CURRICULUM_MAX_REPLICAS")     # = KP1_MLP_MAX_REPLICAS
 
 
-class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
+class ArmKinematicPopulationVecEnv(PopulationEnvHandle, ArmKinematicVecEnv):
     """K Approach or Finisher (dock-mode) envs of ``n_per_replica`` envs each in ONE handle: block k = rows [k N, (k + 1) N) is replica k, and
     is bit for bit ``ArmKinematicVecEnv(config, n_per_replica, seed=seeds[k])`` (env i of replica k owns ``default_rng(seeds[k] + i)``,
     kp1_seed_blocks; with ``repeated_seeds=True`` seeds may repeat -- a hyper-parameter sweep runs several replicas on one seed -- and equal
@@ -334,12 +438,11 @@ class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
     for a Finisher population).  f32 only; the handle keeps its per-block seeds (``seed()`` is refused) and runs its config's mode.  ``replica(k)`` is a view with what PPO's setup, ReplicaView and ``checkpoint.save`` read."""
 
     is_population = True
+    replica_type = ArmKinematicReplicaEnv
 
     def __init__(self, config: kcfg.EnvConfig, seeds: list[int], n_per_replica: int, *, device: int | torch.device = 0, real: str = "f32",
                  reward_components: bool = False, mode: str = "approach", repeated_seeds: bool = False) -> None:
-        self.seeds = [int(s) for s in seeds]
-        if not self.seeds:
-            raise ValueError("ArmKinematicPopulationVecEnv needs at least one seed")
+        self._take_seeds(seeds)
         if len(self.seeds) > MAX_REPLICAS:
             raise ValueError(f"ArmKinematicPopulationVecEnv holds at most {MAX_REPLICAS} replicas (got {len(self.seeds)} seeds)")
         if not repeated_seeds and len(set(self.seeds)) != len(self.seeds):
@@ -352,25 +455,10 @@ class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
                              "with mode='dock' (its per-replica stages come from a DockReverseCurriculumPopulation, not from K DockReverseCurriculum)")
         if real != "f32":
             raise ValueError("ArmKinematicPopulationVecEnv is the f32 env (the population step kernel has no f64 form)")
-        self.K = len(self.seeds)
-        self.n_per_replica = int(n_per_replica)
-        if self.n_per_replica < 1:
-            raise ValueError("n_per_replica must be positive")
-        super().__init__(config, self.K * self.n_per_replica, device=device, seed=self.seeds[0], real="f32", reward_components=reward_components)
+        super().__init__(config, self._take_blocks(n_per_replica), device=device, seed=self.seeds[0], real="f32", reward_components=reward_components)
         seeds_c = (C.c_uint64 * self.K)(*self.seeds)
         native.check(self.L.kp1_seed_blocks(self._handle, C.cast(seeds_c, C.c_void_p), self.K, self.n_per_replica))
         self.dock_population: Any = None     # the DockReverseCurriculumPopulation attached to a dock-mode population
-
-    def replica(self, k: int) -> "ArmKinematicReplicaEnv":
-        if not 0 <= int(k) < self.K:
-            raise IndexError(f"replica {k} of a population of {self.K}")
-        return ArmKinematicReplicaEnv(self, int(k))
-
-    def rows(self, k: int) -> slice:
-        return slice(k * self.n_per_replica, (k + 1) * self.n_per_replica)
-
-    def seed(self, seed: int, first_env_id: int = 0) -> None:
-        raise ValueError("a population env keeps the per-block seeds it was created with (env i of replica k: seeds[k] + i)")
 
     def set_policy_mode(self, mode_name: str) -> None:
         if mode_name != self.config.mode_name:
@@ -389,59 +477,16 @@ class ArmKinematicPopulationVecEnv(ArmKinematicVecEnv):
         super().apply_dock_training_stage(stage_updates)
 
 
-class ArmKinematicReplicaEnv:
-    """Replica k of an ArmKinematicPopulationVecEnv: the attributes PPO's setup, ReplicaView and ``checkpoint.save`` read.  Stepping,
-    resetting and snapshots go through the population handle (one launch for all replicas)."""
-
-    def __init__(self, pop: ArmKinematicPopulationVecEnv, k: int) -> None:
-        self.pop, self.k = pop, int(k)
-        self.n_envs = pop.n_per_replica
-        self.device, self.dtype, self.config = pop.device, pop.dtype, pop.config
-        self.obs_dim = kcfg.OBS_DIM
-        self.seed = pop.seeds[self.k]
-
-    @property
-    def launch_args_version(self) -> int:
-        return self.pop.launch_args_version
-
-    @property
-    def obs_stride(self) -> int:
-        return self.pop.obs_stride
-
-    def set_obs_stride(self, stride: int) -> None:
-        if int(stride) != self.pop.obs_stride:
-            self.pop.set_obs_stride(stride)
-
-    def use_current_stream(self) -> None:
-        self.pop.use_current_stream()
-
-    def snapshot(self) -> None:
-        """(the whole population handle: every replica's view takes the same snapshot)"""
-        self.pop.snapshot()
-
-    def restore(self) -> None:
-        self.pop.restore()
-
-    def reset(self, **_: Any) -> torch.Tensor:
-        raise TypeError("a replica of an ArmKinematicPopulationVecEnv is reset through the population handle (one reset of all replicas)")
-
-    def close(self) -> None:
-        """(the population handle owns the envs)"""
-
 def fk_pose6(q: torch.Tensor) -> torch.Tensor:
     """compute_ee_pose6 batched on the GPU (kinematics/fk_interface.py:21-22): q[n,7] -> pose6[n,6]."""
     if q.ndim != 2 or q.shape[1] != kcfg.NJ:
         raise ValueError("Expected q of shape (n, 7)")
     if not q.is_cuda:
         raise native.Kp1Error("fk_pose6 needs a device tensor; there is no CPU fallback")
-    L = native.load()
+    rt = _real_type(q)
     q = q.contiguous()
-    rt = native.REAL_F64 if q.dtype == torch.float64 else native.REAL_F32
-    if q.dtype not in (torch.float32, torch.float64):
-        raise ValueError("q must be float32 or float64")
     out = torch.empty((q.shape[0], 6), dtype=q.dtype, device=q.device)
-    stream = torch.cuda.current_stream(q.device).cuda_stream
-    native.check(L.kp1_fk_pose6(q.device.index or 0, rt, C.c_void_p(q.data_ptr()), C.c_void_p(out.data_ptr()), q.shape[0], C.c_void_p(stream)))
+    native.check(native.load().kp1_fk_pose6(q.device.index or 0, rt, native.ptr(q), native.ptr(out), q.shape[0], _stream_arg(q.device)))
     return out
 
 
@@ -462,9 +507,8 @@ def pose_error_components(curr_pose6: torch.Tensor, goal_pose6: torch.Tensor) ->
     c, g = curr_pose6.contiguous(), goal_pose6.contiguous()
     n = c.shape[0]
     pe, oe, nr = (torch.empty((n, k), dtype=c.dtype, device=c.device) for k in (3, 3, 2))
-    stream = torch.cuda.current_stream(c.device).cuda_stream
-    native.check(native.load().kp1_pose_error(c.device.index or 0, rt, C.c_void_p(c.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(pe.data_ptr()),
-                                              C.c_void_p(oe.data_ptr()), C.c_void_p(nr.data_ptr()), n, C.c_void_p(stream)))
+    native.check(native.load().kp1_pose_error(c.device.index or 0, rt, native.ptr(c), native.ptr(g), native.ptr(pe), native.ptr(oe), native.ptr(nr), n,
+                                              _stream_arg(c.device)))
     return pe, oe, nr
 
 
@@ -476,8 +520,7 @@ def joint_utils(config: kcfg.EnvConfig, q: torch.Tensor, dq: torch.Tensor) -> di
     rt = _real_type(q)
     q, dq = q.contiguous(), dq.contiguous()
     out = {k: torch.empty_like(q) for k in ("clipped", "margin", "q_norm", "dq_norm")}
-    stream = torch.cuda.current_stream(q.device).cuda_stream
-    native.check(native.load().kp1_joint_utils(q.device.index or 0, rt, C.byref(config.c), C.c_void_p(q.data_ptr()), C.c_void_p(dq.data_ptr()),
-                                               *(C.c_void_p(out[k].data_ptr()) for k in ("clipped", "margin", "q_norm", "dq_norm")), q.shape[0],
-                                               C.c_void_p(stream)))
+    native.check(native.load().kp1_joint_utils(q.device.index or 0, rt, C.byref(config.c), native.ptr(q), native.ptr(dq),
+                                               *(native.ptr(out[k]) for k in ("clipped", "margin", "q_norm", "dq_norm")), q.shape[0],
+                                               _stream_arg(q.device)))
     return out

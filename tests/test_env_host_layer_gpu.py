@@ -8,6 +8,8 @@ N = 1 (one lane), 64 (one full 64-thread workgroup) and 65 (one workgroup plus o
   ``seeds[k] + i``, and a set -> get round trip returns every word, the buffered 32-bit half included; the base env's streams do not move.
 - ``kp1_route_seed`` and through it ``kp1_seed`` (no other GPU test re-seeds a handle): both streams of env i restart at
   ``kp1_rng_seed_state(seed + first_env_id + i)``.
+- ``step`` and ``step_into`` of the four handle classes (one text in ``DeviceEnvHandle`` for both families): the
+  same bits in the handle's own buffers and in caller-owned ones at the padded pitch, and the same random streams afterwards.
 """
 from __future__ import annotations
 
@@ -103,3 +105,47 @@ def test_route_population_rng_set_get(replicas, n_per_replica):
     pop.set_rng_state(seeded)
     assert np.array_equal(pop.rng_state(), seeded)
     pop.close()
+
+
+def _make_handle(family: str, real: str):
+    from rl_brain_trainer_amd.route_env import RoutePopulationVecEnv, RouteVecEnv
+    from rl_brain_trainer_amd.vec_env import ArmKinematicPopulationVecEnv, ArmKinematicVecEnv
+
+    if family == "arm":
+        return ArmKinematicVecEnv(load_golden_config("approach_default"), 64, seed=806, real=real)
+    if family == "arm_population":
+        return ArmKinematicPopulationVecEnv(load_golden_config("approach_default"), [806, 2**32 + 5], 32)
+    if family == "route":
+        return RouteVecEnv(*_route_parts(), 64, seed=806, real=real)
+    return RoutePopulationVecEnv(*_route_parts(), [806, 2**32 + 5], 32)
+
+
+@pytest.mark.parametrize("family,real", [("arm", "f32"), ("arm", "f64"), ("arm_population", "f32"), ("route", "f32"), ("route_population", "f32")])
+def test_step_and_step_into_are_the_same_step(family, real):
+    """``step`` into the handle's own buffers and ``step_into`` caller-owned ones at the padded pitch (64; 128 for the 80-float route
+    observation) are one text in DeviceEnvHandle over the family's step call: two handles made from the same seed and stepped three times
+    with the same actions give the same bits and leave the same random streams"""
+    import torch
+
+    own, into = _make_handle(family, real), _make_handle(family, real)
+    n, width = own.n_envs, getattr(own, "obs_dim", kcfg.OBS_DIM)
+    pitch = 64 if width <= 64 else 128
+    assert n == 64 and width == (80 if family.startswith("route") else 56)
+    own.set_obs_stride(pitch)
+    into.set_obs_stride(pitch)
+    assert torch.equal(own.reset(), into.reset())
+    obs, term = (torch.zeros((n, pitch), dtype=torch.float32, device=own.device) for _ in range(2))
+    reward, done = torch.zeros(n, dtype=own.dtype, device=own.device), torch.zeros(n, dtype=torch.uint8, device=own.device)
+    gen = torch.Generator().manual_seed(45)
+    for t in range(3):
+        actions = (torch.rand((n, kcfg.NJ), generator=gen, dtype=torch.float64) * 2 - 1).to(device=own.device, dtype=own.dtype)
+        got = own.step(actions)
+        assert got[0] is own.obs and got[1] is own.reward and got[2] is own.done
+        into.step_into(actions, obs, reward, done, term)
+        for name, a, b in (("obs", own.obs, obs), ("reward", own.reward, reward), ("done", own.done, done), ("terminal_obs", own.terminal_obs, term)):
+            assert a.shape == b.shape and a.dtype == b.dtype and torch.equal(a, b), (family, real, t, name)
+    assert np.array_equal(own.rng_state(), into.rng_state())
+    if family.startswith("route"):
+        assert np.array_equal(own.base.rng_state(), into.base.rng_state())
+    own.close()
+    into.close()
