@@ -57,7 +57,7 @@ class DeviceTracker:
 
     def _stream(self) -> C.c_void_p:
         """the current stream of the tracker's device: what every launch and read of the tracker is ordered on"""
-        return C.c_void_p(torch.cuda.current_stream(self._device()).cuda_stream)
+        return native.stream_arg(self._device())
 
     def _follow(self, st: Any, k: int) -> None:
         """what the host side keeps in step with the state just read (nothing here)"""
@@ -142,7 +142,7 @@ class PointCurriculum(DeviceTracker):
         self.L = native.load()
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self._st = C.c_void_p()
-        native.check(self.L.kp1_curriculum_create(self.device.index or 0, float(success_rate_threshold), int(window_episodes),
+        native.check(self.L.kp1_curriculum_create(native.device_index(self.device), float(success_rate_threshold), int(window_episodes),
                                                   int(min_episodes_per_stage), int(max_stage_index), int(initial_stage_index), C.byref(self._st)))
 
     def _device(self) -> torch.device:
@@ -164,18 +164,18 @@ class PointCurriculum(DeviceTracker):
         native.check(self.L.kp1_bind_stage_ptr(env._handle, C.c_void_p(self.stage_ptr)))
 
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
-        native.check(self.L.kp1_curriculum_observe(self.device.index or 0, self._st, C.c_void_p(dones.data_ptr()), int(dones.numel()),
+        native.check(self.L.kp1_curriculum_observe(native.device_index(self.device), self._st, native.ptr(dones), int(dones.numel()),
                                                    int(steps_per_call), self._stream()))
 
     def observe_chunk(self, dones_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
         """data-parallel rollouts: the all-gathered [world, chunk_steps, n_local] done bytes of a chunk of env steps, replayed in the
         reference's order (step by step, global env id order inside a step)"""
         assert dones_all.numel() == world * chunk_steps * n_local and dones_all.dtype == torch.uint8 and dones_all.is_contiguous()
-        native.check(self.L.kp1_curriculum_observe_chunk(self.device.index or 0, self._st, C.c_void_p(dones_all.data_ptr()), int(n_local), int(chunk_steps),
+        native.check(self.L.kp1_curriculum_observe_chunk(native.device_index(self.device), self._st, native.ptr(dones_all), int(n_local), int(chunk_steps),
                                                          int(world), self._stream()))
 
     def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:
-        return self.L.kp1_curriculum_read(self.device.index or 0, self._st, out, stream)
+        return self.L.kp1_curriculum_read(native.device_index(self.device), self._st, out, stream)
 
     @staticmethod
     def _summary_of(st: CurriculumState) -> dict[str, object]:
@@ -192,7 +192,7 @@ class PointCurriculum(DeviceTracker):
         }
 
     def _destroy(self) -> None:
-        self.L.kp1_curriculum_destroy(self.device.index or 0, self._st)
+        self.L.kp1_curriculum_destroy(native.device_index(self.device), self._st)
 
 
 class PointCurriculumPopulation(TrackerPopulation, PointCurriculum):
@@ -215,7 +215,7 @@ class PointCurriculumPopulation(TrackerPopulation, PointCurriculum):
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self._st = C.c_void_p()
         init = (C.c_int32 * self.K)(*stages)
-        native.check(self.L.kp1_curriculum_create_population(self.device.index or 0, self.K, float(success_rate_threshold), int(window_episodes),
+        native.check(self.L.kp1_curriculum_create_population(native.device_index(self.device), self.K, float(success_rate_threshold), int(window_episodes),
                                                              int(min_episodes_per_stage), int(max_stage_index), C.cast(init, C.c_void_p),
                                                              C.byref(self._st)))
 
@@ -236,11 +236,11 @@ class PointCurriculumPopulation(TrackerPopulation, PointCurriculum):
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
         """dones: the K N done bytes of one population step (replica-major); steps_per_call: env steps per replica this call stands for (N)"""
         self._check_done_bytes(dones, dones.numel() % self.K == 0)
-        native.check(self.L.kp1_curriculum_observe_population(self.device.index or 0, self._st, C.c_void_p(dones.data_ptr()), dones.numel() // self.K,
+        native.check(self.L.kp1_curriculum_observe_population(native.device_index(self.device), self._st, native.ptr(dones), dones.numel() // self.K,
                                                               self.K, int(steps_per_call), self._stream()))
 
     def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:
-        return self.L.kp1_curriculum_read_replica(self.device.index or 0, self._st, self.K, k, out, stream)
+        return self.L.kp1_curriculum_read_replica(native.device_index(self.device), self._st, self.K, k, out, stream)
 
 
 PointCurriculumReplica = TrackerReplica

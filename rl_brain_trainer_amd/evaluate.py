@@ -194,10 +194,6 @@ _STATE_SLICES = (("q", 0, 7), ("dq", 7, 14), ("prev_action", 14, 21), ("goal_q",
 _ALIVE_CHECK_EVERY = 8      # env steps between two reads of the device's alive-episode counter
 
 
-def _ptr(t: torch.Tensor | None) -> C.c_void_p | None:
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class EpisodeBuffers:
     """The per-episode accumulators of the batched evaluator (include/kp1.h kp1_eval_buffers) over ``n_episodes`` episodes: the tensors as
     attributes named after the fields of native.EvalBuffers, ``struct`` the native.EvalBuffers over them (the object keeps the tensors alive
@@ -217,7 +213,7 @@ class EpisodeBuffers:
                 setattr(self, name, None)
             else:       # the kernels write every element of an active episode; only the alive counter is read before it is written
                 setattr(self, name, (torch.zeros if name == "n_alive" else torch.empty)(shape, dtype=dtype, device=device))
-        self.struct = native.EvalBuffers(*[_ptr(getattr(self, name)) for name in self.NAMES])
+        self.struct = native.EvalBuffers(*[native.ptr(getattr(self, name)) for name in self.NAMES])
 
     @staticmethod
     def thresholds(ready_cfg):
@@ -261,7 +257,7 @@ def _start_episodes(L, env: ArmKinematicVecEnv, ready_cfg, handoff_confirm_steps
     thr = bufs.thresholds(ready_cfg)
     confirm = int(handoff_confirm_steps or 0)
     bufs.active = None if active is None else active.to(env.device).to(torch.uint8).contiguous()    # lives as long as the buffers: the launch reads it
-    native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs.struct), None, None, _ptr(bufs.active), 0, thr, confirm, stream))
+    native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs.struct), None, None, native.ptr(bufs.active), 0, thr, confirm, stream))
     return bufs, thr, confirm
 
 
@@ -292,7 +288,7 @@ def run_episodes(env: ArmKinematicVecEnv, policy: PolicyFn, reset_options: dict[
         a_norm = torch.linalg.vector_norm(action.double(), dim=1).contiguous()
         obs, _, done = env.step(action, auto_reset=False)
         obs = obs.clone()
-        native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs.struct), _ptr(a_norm), _ptr(done), None, step, thr, confirm, None))
+        native.check(L.kp1_eval_accumulate(env._handle, C.byref(bufs.struct), native.ptr(a_norm), native.ptr(done), None, step, thr, confirm, None))
     return bufs.results()
 
 
@@ -476,7 +472,7 @@ def run_episodes_fused(env: ArmKinematicVecEnv, mlp: Any, reset_options: dict[st
         raise TypeError("run_episodes_fused drives an ArmKinematicVecEnv (kp1_eval_step steps its handle)")
     L = native.load()
     env.use_current_stream()
-    stream = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+    stream = native.stream_arg(env.device)
     env.reset(options=reset_options)
     bufs, thr, confirm = _start_episodes(L, env, ready_cfg, handoff_confirm_steps, active, stream)
     limit = int(max_steps or (env.config.c.termination.max_episode_steps + 1))
@@ -484,13 +480,13 @@ def run_episodes_fused(env: ArmKinematicVecEnv, mlp: Any, reset_options: dict[st
         for first in range(1, limit + 1, _EPISODES_CAP):
             if first > 1 and int(bufs.n_alive.item()) == 0:
                 break
-            native.check(L.kp1_eval_episodes(mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(bufs.struct), first,
+            native.check(L.kp1_eval_episodes(mlp._h, env._handle, native.ptr(env.obs), native.ptr(env.reward), native.ptr(env.done), C.byref(bufs.struct), first,
                                              min(first + _EPISODES_CAP - 1, limit), thr, confirm, stream))
     else:
         for step in range(1, limit + 1):
             if (step - 1) % _ALIVE_CHECK_EVERY == 0 and int(bufs.n_alive.item()) == 0:
                 break
-            native.check(L.kp1_eval_step(mlp._h, env._handle, _ptr(env.obs), _ptr(env.reward), _ptr(env.done), C.byref(bufs.struct), step, thr, confirm,
+            native.check(L.kp1_eval_step(mlp._h, env._handle, native.ptr(env.obs), native.ptr(env.reward), native.ptr(env.done), C.byref(bufs.struct), step, thr, confirm,
                                          stream))
     return bufs.results()
 

@@ -140,7 +140,7 @@ class DockReverseCurriculum(DeviceTracker):
         self.observe_chunk(dones, int(dones.numel()), 1, 1)
 
     def observe_chunk(self, dones_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
-        native.check(self.env.L.kp1_dock_curriculum_observe(self.env._handle, self._st, C.c_void_p(dones_all.data_ptr()), int(n_local), int(chunk_steps),
+        native.check(self.env.L.kp1_dock_curriculum_observe(self.env._handle, self._st, native.ptr(dones_all), int(n_local), int(chunk_steps),
                                                             int(world), self._stream()))
 
     def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:
@@ -219,7 +219,7 @@ class DockReverseCurriculumPopulation(TrackerPopulation, DockReverseCurriculum):
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
         """dones: the K N done bytes of one population step (replica-major); every clock advances by N whatever ``steps_per_call`` says"""
         self._check_done_bytes(dones, dones.numel() % self.K == 0)
-        native.check(self.env.L.kp1_dock_curriculum_observe_population(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), dones.numel() // self.K,
+        native.check(self.env.L.kp1_dock_curriculum_observe_population(self.env._handle, self._st, native.ptr(dones), dones.numel() // self.K,
                                                                        self.K, self._stream()))
 
     def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:

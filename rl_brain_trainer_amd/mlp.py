@@ -37,9 +37,9 @@ class MlpKernels:
         self.kl_gate = False                             # whether set_kl_gate has a gate set (default: none)
         self.hparam_line = False                         # whether the kernels read the handle's hyper-parameter table (hparams_store / set_replica_hparams)
         if replicas == 1:
-            native.check(L.kp1_mlp_create_ex(device.index or 0, hidden, self.obs_dim, self.max_batch, C.byref(self._h)))
+            native.check(L.kp1_mlp_create_ex(native.device_index(device), hidden, self.obs_dim, self.max_batch, C.byref(self._h)))
         else:
-            native.check(L.kp1_mlp_create_population(device.index or 0, hidden, self.obs_dim, self.max_batch, int(replicas), C.byref(self._h)))
+            native.check(L.kp1_mlp_create_population(native.device_index(device), hidden, self.obs_dim, self.max_batch, int(replicas), C.byref(self._h)))
         self.replicas = int(L.kp1_mlp_replicas(self._h))
         self.num_params = int(L.kp1_mlp_num_params_ex(hidden, self.obs_dim))
 
@@ -148,7 +148,7 @@ class MlpKernels:
         return [{f: getattr(r, f) for f in fields} for r in rec], [int(v) for v in steps]
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return native.stream_arg(self.device)
 
     def pack(self, flat_params: torch.Tensor) -> None:
         assert flat_params.numel() == self.replicas * self.num_params and flat_params.dtype == torch.float32 and flat_params.is_contiguous()
@@ -239,12 +239,12 @@ class MlpKernels:
 
     def loss_grad(self, obs: torch.Tensor, idx: torch.Tensor | None, n: int, actions, old_logp, adv, ret, *, clip_range: float, ent_coef: float,
                   vf_coef: float, inv_count: float, grad_out: torch.Tensor, stats_out: torch.Tensor | None, adv_stats: torch.Tensor | None = None,
-                  normalize: bool = True, grad_is_zero: bool = False) -> None:
+                  normalize: bool = True) -> None:
         assert obs.is_contiguous() and grad_out.numel() == self.replicas * self.num_params
         assert self.replicas == 1 or (idx is not None and idx.numel() == self.replicas * n)
         inv_std = 0.0 if normalize else -1.0
         native.check(self.L.kp1_mlp_loss_grad(self._h, _p(obs), obs.shape[-1], _p(idx), n, _p(actions), _p(old_logp), _p(adv), _p(ret), 0.0, inv_std,
-                                              _p(adv_stats), clip_range, ent_coef, vf_coef, inv_count, _p(grad_out), _p(stats_out), int(grad_is_zero), self._stream()))
+                                              _p(adv_stats), clip_range, ent_coef, vf_coef, inv_count, _p(grad_out), _p(stats_out), 0, self._stream()))
 
     def adam_step(self, params, grad, exp_avg, exp_avg_sq, *, lr: float, eps: float, max_grad_norm: float, step: int,
                   fused_norm: bool = False) -> None:
@@ -275,7 +275,7 @@ class MlpKernels:
         """where the hardware puts the workgroups of a training-tile launch for an n_rows minibatch (the two placement assumptions the update
         kernels' SPEED rests on: include/kp1_ppo.h kp1_mlp_placement_check)"""
         out = (C.c_int32 * 8)()
-        native.check(self.L.kp1_mlp_placement_check(self.device.index or 0, int(n_rows), C.cast(out, C.c_void_p), self._stream()))
+        native.check(self.L.kp1_mlp_placement_check(native.device_index(self.device), int(n_rows), C.cast(out, C.c_void_p), self._stream()))
         wgs, pairs, same, rr, cus, used, arrived, xcds = (int(v) for v in out)
         return {"workgroups": wgs, "compute_units": cus, "compute_units_used": used, "second_tile_on_same_cu": same, "second_tile_pairs": pairs,
                 "on_xcd_of_block_index_mod_8": rr, "xcds_among_first_8_blocks": xcds, "all_resident": arrived == wgs}

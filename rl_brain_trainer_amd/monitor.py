@@ -97,12 +97,10 @@ class EpisodeMonitor:
         self.K, self.N, self.window, self.max_steps = int(n_replicas), int(n_per_replica), int(window), int(max_steps)
         self.L = native.load()
         self._h = C.c_void_p()
-        native.check(self.L.kp1_monitor_create(self.device.index or 0, self.K, self.N, self.window, self.max_steps, C.byref(self._h)))
+        native.check(self.L.kp1_monitor_create(native.device_index(self.device), self.K, self.N, self.window, self.max_steps, C.byref(self._h)))
 
     def _stream(self) -> C.c_void_p:
-        import torch
-
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return native.stream_arg(self.device)
 
     def observe(self, rewards: Any, dones: Any, T: int | None = None) -> None:
         import torch
@@ -112,7 +110,7 @@ class EpisodeMonitor:
         steps = int(rewards.shape[0]) if T is None else int(T)
         if rewards.numel() < steps * self.K * self.N or dones.numel() < steps * self.K * self.N:
             raise ValueError(f"EpisodeMonitor.observe: the buffers hold fewer than {steps} x {self.K * self.N} elements")
-        native.check(self.L.kp1_monitor_observe(self._h, C.c_void_p(rewards.data_ptr()), C.c_void_p(dones.data_ptr()), steps, self._stream()))
+        native.check(self.L.kp1_monitor_observe(self._h, native.ptr(rewards), native.ptr(dones), steps, self._stream()))
 
     def reset_carry(self) -> None:
         native.check(self.L.kp1_monitor_reset_carry(self._h, self._stream()))

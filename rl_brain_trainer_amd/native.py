@@ -179,6 +179,18 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def stream_arg(device) -> C.c_void_p:
+    """the current stream of ``device`` as the ``stream`` argument of a C entry point (torch is imported here: this module needs none)"""
+    import torch
+
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def device_index(device) -> int:
+    """the ``device`` argument of a C entry point: a torch device's ordinal, 0 where it carries none"""
+    return device.index or 0
+
+
 def component_names(mode: int) -> list[str]:
     L = load()
     return [L.kp1_component_name(mode, i).decode() for i in range(L.kp1_num_components(mode))]

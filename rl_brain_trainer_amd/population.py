@@ -17,13 +17,12 @@ Replica k of a population is bit-identical to ``PPO(seed=s_k)`` on the same conf
 The one-handle forms (``ApproachPopulationPPO``, ``RoutePopulationPPO``) step all replicas in ONE env handle of K N envs instead, block k
 being replica k, with one population tracker: every env step is one env launch and one tracker launch whatever K is.
 
-``PopulationPPO`` is a ``PPO`` with K replicas: it runs PPO's rollout, graph capture and update loop and overrides only the steps that
-depend on K.  ``replica(k)`` is a view with what ``checkpoint.save`` and the evaluators read, so a replica saves as an ordinary
-single-policy archive.
+``PopulationPPO`` is a ``PPO`` with K replicas: it runs PPO's rollout, graph capture, rollout tail, optimiser step and update loop and
+overrides only the steps that depend on K.  ``replica(k)`` is a view with what ``checkpoint.save`` and the evaluators read, so a replica
+saves as an ordinary single-policy archive.
 """
 from __future__ import annotations
 
-import ctypes as C
 import dataclasses
 from typing import Any, Callable
 
@@ -32,7 +31,7 @@ import torch
 from . import native
 from .curriculum import PointCurriculumPopulation
 from .finisher_tools import DockReverseCurriculumPopulation
-from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig, check_schedules, check_target_kl
+from .ppo import ACT_DIM, OBS_DIM, Dist, PPO, PPOConfig, check_schedules, check_target_kl, truncation_cap
 from .route_curriculum import RoutePrefixCurriculumPopulation
 from .route_env import RoutePopulationVecEnv
 from .vec_env import ArmKinematicPopulationVecEnv
@@ -154,9 +153,10 @@ class PopulationPPO(PPO):
     """K = len(seeds) PPO runs of one PPOConfig, trained together.  ``env_factory(seed)`` builds replica k's env handle (first env id 0);
     ``curriculum_factory(seed)`` (optional) its PointCurriculum / DockReverseCurriculum, attached to that handle.
 
-    PPO's rollout, graph capture and update loop run unchanged on K replicas; what depends on K is overridden here: the env step and the
-    tracker per replica slice, the per-replica compacted bootstrap, the noise draw from each replica's generator, and the epoch body that
-    reads minibatch i of every replica as one [K][n] index block."""
+    PPO's rollout, graph capture, rollout tail, optimiser step and update loop run unchanged on K replicas; what depends on K is overridden
+    here: the env step and the tracker per replica slice, the per-replica compacted bootstrap, the noise draw from each replica's generator,
+    the GAE scan where overrides give the replicas their own (gamma, lambda), and the index preparation of the epoch body, which hands
+    PPO's optimiser step minibatch i of every replica as one [K][n] index block (``_global_rows``: the one replica-major row mapping)."""
 
     def __init__(self, seeds: list[int], cfg: PPOConfig, env_factory: Callable[[int], Any], *,
                  curriculum_factory: Callable[[int], Any] | None = None, dist: Dist | None = None, use_graphs: bool = True,
@@ -215,8 +215,7 @@ class PopulationPPO(PPO):
                          overrides: list[dict[str, float]] | None = None, *, min_batch: int = 0, monitor: bool | int = False) -> None:
         """what a population holds once its K env views and trackers exist (``min_batch``: rows the MLP handle must hold besides its own needs)"""
         T, N, K = cfg.n_steps, envs[0].n_envs, len(seeds)
-        max_steps = max(int(envs[0].config.c.termination.max_episode_steps), 1)
-        self._trunc_cap = min(N * (T // max_steps + 1), T * N)
+        self._trunc_cap = truncation_cap(T, N, envs[0])
         # the MLP handle's max_batch holds the `_trunc_cap` rows per replica of the bootstrap's one forward
         self._setup(cfg, seeds, envs, curricula, dist, use_graphs, min_batch=max(self._trunc_cap, int(min_batch)), stacked=True, monitor=monitor)
         self.seeds = seeds
@@ -240,6 +239,12 @@ class PopulationPPO(PPO):
         self._mb_src = torch.cat(src).to(dev)
         self._rep_off = (torch.arange(K, device=dev, dtype=torch.int64) * N).view(K, 1)
         self._infer: dict[int, Any] = {}
+
+    def _global_rows(self, loc: torch.Tensor) -> torch.Tensor:
+        """[K, n] positions p in [0, T N) of each replica's own rollout (row k: replica k's) -> rows of the [T, K N] buffers: step p // N,
+        column k N + p % N"""
+        N = self.n_envs
+        return (loc // N) * (self.K * N) + self._rep_off + loc % N
 
     def _apply_overrides(self) -> None:
         """cfgs[k] = cfg with replica k's seed and overrides; a population with overrides writes them to the device (at construction and
@@ -314,7 +319,7 @@ class PopulationPPO(PPO):
         K, T, N, cap = self.K, self.cfg.n_steps, self.n_envs, self._trunc_cap
         trunc = ((self.done_buf.view(T, K, N).permute(1, 0, 2) & 3) == 2).reshape(K, T * N)
         loc = torch.stack([torch.nonzero_static(trunc[k], size=cap, fill_value=0).view(-1) for k in range(K)])
-        gidx = (loc // N) * (K * N) + self._rep_off + loc % N
+        gidx = self._global_rows(loc)
         valid = torch.arange(cap, device=self.device).view(1, cap) < trunc.sum(dim=1, keepdim=True)
         sel = self.term_obs_buf.view(T * K * N, self.obs_w).index_select(0, gidx.view(-1))
         tv = torch.empty(K * cap, dtype=torch.float32, device=self.device)
@@ -325,56 +330,30 @@ class PopulationPPO(PPO):
         disc = self.cfg.gamma * tv if not self.has_overrides else (self._gamma_lambda[:, :1] * tv.view(K, cap)).view(-1)
         self.rew_buf.view(-1).index_add_(0, gidx.view(-1), torch.where(valid.view(-1), disc, torch.zeros_like(tv)))
 
-    def _post_rollout(self) -> None:
-        """PPO._post_rollout; with overrides the GAE scan reads each replica's (gamma, lambda) (kp1_gae_scan_replicas, one launch)"""
+    def _gae_scan(self, last_v: torch.Tensor) -> None:
+        """with overrides the scan reads each replica's (gamma, lambda) (kp1_gae_scan_replicas, one launch)"""
         if not self.has_overrides:
-            super()._post_rollout()
-            return
-        T, N, KN = self.cfg.n_steps, self.n_envs, self.K * self.n_envs
-        self._monitor_observe()
-        self._bootstrap_truncated()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        last_v = torch.empty(KN, dtype=torch.float32, device=self.device)
-        self._mlp.forward(self.obs_buf[T], value=last_v)   # value net only
-        native.check(self.L.kp1_gae_scan_replicas(self.device.index or 0, C.c_void_p(self.rew_buf.data_ptr()), C.c_void_p(self.val_buf.data_ptr()),
-                                                  C.c_void_p(self.done_buf.data_ptr()), C.c_void_p(last_v.data_ptr()),
-                                                  C.c_void_p(self._gamma_lambda.data_ptr()), N, C.c_void_p(self.adv_buf.data_ptr()),
-                                                  C.c_void_p(self.ret_buf.data_ptr()), T, KN, C.c_void_p(stream)))
-        self._monitor_explained_variance()
+            return super()._gae_scan(last_v)
+        native.check(self.L.kp1_gae_scan_replicas(native.device_index(self.device), native.ptr(self.rew_buf), native.ptr(self.val_buf),
+                                                  native.ptr(self.done_buf), native.ptr(last_v), native.ptr(self._gamma_lambda), self.n_envs,
+                                                  native.ptr(self.adv_buf), native.ptr(self.ret_buf), self.cfg.n_steps, self.K * self.n_envs,
+                                                  native.stream_arg(self.device)))
 
     # ------------------------------------------------------------------ update
     def _epoch_body(self) -> None:
-        """one update epoch from the shuffles in self.perm: global row indices, per-replica minibatch advantage statistics, then per minibatch
-        loss_grad + Adam of all replicas (with overrides the kernels read each replica's constants from the handle's table; the shared
-        scalars below are then unused)"""
-        cfg, K, N = self.cfg, self.K, self.n_envs
+        """one update epoch from the shuffles in self.perm: global row indices, minibatch i of every replica as one [K][n_i] index block, the
+        per-replica minibatch advantage statistics, then PPO's optimiser step per minibatch"""
+        cfg = self.cfg
         T = cfg.n_steps
-        total = T * N
         obs = self.obs_buf[:T].view(-1, self.obs_w)
         act = self.act_buf.view(-1, ACT_DIM)
         old_logp, adv, ret = self.logp_buf.view(-1), self.adv_buf.view(-1), self.ret_buf.view(-1)
-        gperm = (self.perm // N) * (K * N) + self._rep_off + self.perm % N          # [K, T N] global rows
+        gperm = self._global_rows(self.perm)                                          # [K, T N] global rows
         mb_idx = gperm.view(-1).index_select(0, self._mb_src)
-        stats = None
-        if cfg.normalize_advantage:
-            n_mb = len(self._mb)
-            sums = torch.empty((K, n_mb, 3), dtype=torch.float64, device=self.device)
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            dev = self.device.index or 0
-            for k in range(K):
-                native.check(self.L.kp1_adv_minibatch_sums(dev, C.c_void_p(adv.data_ptr()), C.c_void_p(gperm[k].data_ptr()), total, cfg.batch_size,
-                                                           C.c_void_p(sums[k].data_ptr()), stream))
-            st = torch.empty((K, n_mb, 2), dtype=torch.float32, device=self.device)
-            native.check(self.L.kp1_adv_minibatch_stats(dev, C.c_void_p(sums.data_ptr()), K * n_mb, C.c_void_p(st.data_ptr()), stream))
-            stats = st.permute(1, 0, 2).contiguous()                                  # [n_mb][K][2]
+        stats = self._epoch_adv_stats(adv, gperm, T * self.n_envs, cfg.batch_size)
         for i, (s0, e0) in enumerate(self._mb):
-            n = e0 - s0
-            idx = mb_idx[K * s0:K * e0]
-            self._mlp.loss_grad(obs, idx, n, act, old_logp, adv, ret, clip_range=cfg.clip_range, ent_coef=cfg.ent_coef, vf_coef=cfg.vf_coef,
-                                inv_count=1.0 / n, grad_out=self.grad, stats_out=self.stats_dev, adv_stats=None if stats is None else stats[i],
-                                normalize=cfg.normalize_advantage)
-            self._mlp.adam_step(self.flat, self.grad, self.adam_m, self.adam_v, lr=cfg.learning_rate, eps=cfg.adam_eps,
-                                max_grad_norm=cfg.max_grad_norm, step=0, fused_norm=True)
+            self._hip_minibatch_step(obs, mb_idx[self.K * s0:self.K * e0], act, old_logp, adv, ret, device_step=True,
+                                     adv_stats=None if stats is None else stats[i])
 
 
 class OneHandlePopulationPPO(PopulationPPO):

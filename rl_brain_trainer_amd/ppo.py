@@ -18,6 +18,9 @@ Everything stays on the device: the env kernel writes straight into the rollout 
 tracker is a device kernel, and the only host synchronisation per iteration is the logging read-back.
 Under torch.distributed (backend "nccl" = RCCL) env ranges are sharded by rank and gradients are summed
 with one flat all-reduce per optimiser step.
+
+``PPO`` is the engine of every trainer: rollout loop, graph capture, rollout tail (``_post_rollout``), minibatch
+advantage statistics (``_epoch_adv_stats``) and optimiser step (``_hip_minibatch_step``) stand here once, for one run and for a population.
 """
 from __future__ import annotations
 
@@ -611,9 +614,18 @@ def fused_route_rollout_covered(env_type_ok: bool, dtype: Any, hidden: int, obs_
     return True
 
 
+def truncation_cap(n_steps: int, n_envs: int, env: Any) -> int:
+    """Rows per replica of the time-limit bootstrap's index list.  Only truncated steps need the critic, and an env truncates at most
+    n_steps // max_episode_steps + 1 times per rollout, so a replica's truncated positions fit a list of this fixed size
+    (torch.nonzero_static: no device->host size query)."""
+    return min(n_envs * (n_steps // max(int(env.config.c.termination.max_episode_steps), 1) + 1), n_steps * n_envs)
+
+
 class PPO:
     """One PPO run.  PopulationPPO (population.py) is the same engine with K replicas: everything per replica below is a list (``envs``,
-    ``curricula``, ``policies``, ``gens``) or a replica axis (rollout columns [k N, (k + 1) N), ``perm[k]``, ``stats_dev[k]``); here K = 1."""
+    ``curricula``, ``policies``, ``gens``) or a replica axis (rollout columns [k N, (k + 1) N), ``perm[k]``, ``stats_dev[k]``); here K = 1.
+    A trainer class overrides ``_rollout_env``, ``_rollout_tracker``, the type predicates and, if it must, ``_gae_scan``,
+    ``_bootstrap_truncated``, ``_draw_noise`` and ``_epoch_body``'s index preparation; never the rollout tail or the optimiser step."""
 
     # the training monitor (monitor.py): None = off, the default, and then no launch, graph or printed line differs from a build without it
     monitor = None
@@ -639,6 +651,7 @@ class PPO:
         self.curriculum = curriculum
         self._setup(cfg, [cfg.seed], [env], [curriculum], dist, use_graphs, min_batch=8192, stacked=False, monitor=monitor)
         self.policy = self.policies[0]
+        self._trunc_cap = truncation_cap(cfg.n_steps, self.n_envs, env)
         self._setup_kl_gate(targets)
         self._setup_schedules(schedules)
         T, N, dev = cfg.n_steps, self.n_envs, self.device
@@ -658,10 +671,13 @@ class PPO:
     def _fused_env_step(self) -> bool:
         """whether the next rollout step is the one-launch form (fused_rollout_covered on the env's current state: the reward-component
         switch may be thrown after construction, which bumps ``launch_args_version`` and re-captures the rollout)"""
+        return fused_rollout_covered(*self._step_coverage(), os.environ.get("KP1_FUSED_ROLLOUT"), default_on=self._fused_rollout_default())
+
+    def _step_coverage(self) -> tuple[bool, Any, int, int, bool]:
+        """what fused_rollout_covered asks about the run's current state: the env handle's type and real type, the two widths, whether
+        reward components are recorded"""
         env = self._rollout_env()
-        return fused_rollout_covered(self._rollout_env_type_ok(), env.dtype, self.cfg.hidden, self.obs_dim,
-                                     getattr(env, "_reward_components_on", False), os.environ.get("KP1_FUSED_ROLLOUT"),
-                                     default_on=self._fused_rollout_default())
+        return self._rollout_env_type_ok(), env.dtype, self.cfg.hidden, self.obs_dim, getattr(env, "_reward_components_on", False)
 
     def _fused_rollout_default(self) -> bool:
         """the one-launch step while KP1_FUSED_ROLLOUT is unset: hidden 256 (measured); the single-seed PPO at hidden
@@ -691,8 +707,7 @@ class PPO:
         if var == "0" or (var is None and not self.whole_rollout_default):
             return False
         env, cur = self._rollout_env(), self._rollout_tracker()
-        step_covered = fused_rollout_covered(self._rollout_env_type_ok(), env.dtype, self.cfg.hidden, self.obs_dim,
-                                             getattr(env, "_reward_components_on", False), None, default_on=True)
+        step_covered = fused_rollout_covered(*self._step_coverage(), None, default_on=True)
         return rollout_run_covered(step_covered, self.cfg.hidden, getattr(env, "_mode_name", ""), self.dist.enabled, self.step_callback is not None,
                                    cur is not None, self.n_envs, var, tracker_ok=cur is not None and cur.runs_in_rollout_launch,
                                    default_on=self.whole_rollout_default)
@@ -974,9 +989,8 @@ class PPO:
         if self.monitor is None:
             return
         T, KN = self.cfg.n_steps, self.K * self.n_envs
-        native.check(self.L.kp1_explained_variance(self.device.index or 0, C.c_void_p(self.val_buf.data_ptr()), C.c_void_p(self.ret_buf.data_ptr()),
-                                                   T, KN, self.n_envs, C.c_void_p(self._ev_dev.data_ptr()),
-                                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        native.check(self.L.kp1_explained_variance(native.device_index(self.device), native.ptr(self.val_buf), native.ptr(self.ret_buf), T, KN, self.n_envs,
+                                                   native.ptr(self._ev_dev), native.stream_arg(self.device)))
 
     def monitor_rows(self) -> list[dict[str, Any]]:
         """SB3's rollout/ and train/ keys of the last iteration, one dict per replica (monitor.KEYS without the time/ keys, which a
@@ -1031,8 +1045,8 @@ class PPO:
             torch.randperm(total, device=self.device, generator=self.gens[k], out=out)
             return
         keys = self._perm_rngs[k].integers(0, 1 << 32, size=8, dtype=np.uint64).astype(np.uint32)
-        native.check(self.L.kp1_random_permutation(self.device.index or 0, total, keys.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
-                                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        native.check(self.L.kp1_random_permutation(native.device_index(self.device), total, keys.ctypes.data_as(C.c_void_p), native.ptr(out),
+                                                   native.stream_arg(self.device)))
 
     def _draw_noise(self) -> None:
         """the exploration noise of the whole rollout"""
@@ -1132,16 +1146,11 @@ class PPO:
         """SB3 collect_rollouts time-limit bootstrap: rewards[t, i] += gamma * V(terminal_observation) where step t of env i was
         truncated and not terminated.  ``dense`` = critic over all T * N terminal observations + kp1_bootstrap_truncated (kept as the
         reference for the compacted one)."""
-        cfg, env = self.cfg, self.env
+        cfg = self.cfg
         T, N = cfg.n_steps, self.n_envs
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        dev = self.device.index or 0
         if not dense:
-            # Only truncated steps need the critic.  An env truncates at most T // max_episode_steps + 1 times per rollout, so the
-            # truncated positions fit a fixed-size index list (torch.nonzero_static: no device->host size query) and the value net
-            # runs on N * (that bound) terminal observations instead of all T * N.
-            max_steps = max(int(env.config.c.termination.max_episode_steps), 1)
-            cap = min(N * (T // max_steps + 1), T * N)
+            # the value net runs on the _trunc_cap terminal observations of the index list instead of all T * N
+            cap = self._trunc_cap
             trunc = (self.done_buf.view(-1) & 3) == 2
             idx = torch.nonzero_static(trunc, size=cap, fill_value=0).view(-1)
             valid = torch.arange(cap, device=self.device) < trunc.sum()
@@ -1154,8 +1163,8 @@ class PPO:
         else:
             _, tv = self._forward(self.term_obs_buf.view(T * N, self.obs_w))
             tv = tv.contiguous()
-            native.check(self.L.kp1_bootstrap_truncated(dev, C.c_void_p(self.rew_buf.data_ptr()), C.c_void_p(tv.data_ptr()),
-                                                        C.c_void_p(self.done_buf.data_ptr()), cfg.gamma, T * N, C.c_void_p(stream)))
+            native.check(self.L.kp1_bootstrap_truncated(native.device_index(self.device), native.ptr(self.rew_buf), native.ptr(tv),
+                                                        native.ptr(self.done_buf), cfg.gamma, T * N, native.stream_arg(self.device)))
 
     # ------------------------------------------------------------------ rollout
     @torch.no_grad()
@@ -1194,19 +1203,19 @@ class PPO:
         """what SB3's collect_rollouts does after the last env step: time-limit bootstrap, value of the last observation, GAE.  Static shapes
         and no host synchronisation, so the captured rollout graph carries it as its tail (a dozen small launches whose host latency
         was 0.5 ms per iteration)."""
-        cfg = self.cfg
-        T, KN = cfg.n_steps, self.K * self.n_envs
         self._monitor_observe()
         self._bootstrap_truncated()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        dev = self.device.index or 0
-        last_v = torch.empty(KN, dtype=torch.float32, device=self.device)
-        self._mlp.forward(self.obs_buf[T], value=last_v)   # value net only
-        # GAE runs per column: one launch covers every replica
-        native.check(self.L.kp1_gae_scan(dev, C.c_void_p(self.rew_buf.data_ptr()), C.c_void_p(self.val_buf.data_ptr()),
-                                         C.c_void_p(self.done_buf.data_ptr()), C.c_void_p(last_v.data_ptr()), cfg.gamma, cfg.gae_lambda,
-                                         C.c_void_p(self.adv_buf.data_ptr()), C.c_void_p(self.ret_buf.data_ptr()), T, KN, C.c_void_p(stream)))
+        last_v = torch.empty(self.K * self.n_envs, dtype=torch.float32, device=self.device)
+        self._mlp.forward(self.obs_buf[self.cfg.n_steps], value=last_v)   # value net only
+        self._gae_scan(last_v)
         self._monitor_explained_variance()
+
+    def _gae_scan(self, last_v: torch.Tensor) -> None:
+        """GAE runs per column: one launch covers every replica (a population with overrides reads each replica's gamma and lambda)"""
+        cfg = self.cfg
+        native.check(self.L.kp1_gae_scan(native.device_index(self.device), native.ptr(self.rew_buf), native.ptr(self.val_buf), native.ptr(self.done_buf),
+                                         native.ptr(last_v), cfg.gamma, cfg.gae_lambda, native.ptr(self.adv_buf), native.ptr(self.ret_buf), cfg.n_steps,
+                                         self.K * self.n_envs, native.stream_arg(self.device)))
 
     def _rollout_step_hip(self, t: int) -> None:
         # (running the tracker on a side stream under the next policy forward was measured: the fork / join inside the graph
@@ -1348,10 +1357,7 @@ class PPO:
 
     # ------------------------------------------------------------------ update
     def train(self) -> None:
-        cfg = self.cfg
-        total = cfg.n_steps * self.n_envs
-        local_bs = max(cfg.batch_size // self.dist.world_size, 1)
-        n_mb = (total + local_bs - 1) // local_bs     # optimiser steps per epoch
+        cfg, n_mb = self.cfg, self._n_minibatches()
         gated = self.kl_targets is not None
         if gated:
             self._resolve_kl()      # the previous call's records, before arming clears them
@@ -1476,7 +1482,8 @@ class PPO:
         return self._last_stats_host
 
     def _epoch_adv_stats(self, adv, perm, total: int, local_bs: int):
-        """(mean, 1/(std + 1e-8)) of the advantages of every minibatch of this epoch, f32 [n_minibatches, 2] on the device.
+        """(mean, 1/(std + 1e-8)) of the advantages of every minibatch of this epoch, on the device: f32 [n_minibatches, 2] for one shuffle
+        ``perm`` [total]; [n_minibatches][K][2] for a population's [K, total] block of shuffles, each row summed by a launch of its own.
 
         SB3 normalises per minibatch (ppo.py train()).  One kernel sums all minibatches, and with data parallelism ONE
         all-reduce per epoch makes the statistics those of the global minibatch (all ranks' shards together), so the
@@ -1484,20 +1491,23 @@ class PPO:
         if not self.cfg.normalize_advantage:
             return None
         n_mb = (total + local_bs - 1) // local_bs
-        sums = torch.empty((n_mb, 3), dtype=torch.float64, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        native.check(self.L.kp1_adv_minibatch_sums(self.device.index or 0, C.c_void_p(adv.data_ptr()), C.c_void_p(perm.data_ptr()), total, local_bs,
-                                                   C.c_void_p(sums.data_ptr()), C.c_void_p(stream)))
+        one = perm.dim() == 1
+        lead = (n_mb,) if one else (perm.shape[0], n_mb)
+        sums = torch.empty((*lead, 3), dtype=torch.float64, device=self.device)
+        dev, stream = native.device_index(self.device), native.stream_arg(self.device)
+        rows = [(perm, sums)] if one else [(perm[k], sums[k]) for k in range(perm.shape[0])]
+        for row, out in rows:
+            native.check(self.L.kp1_adv_minibatch_sums(dev, native.ptr(adv), native.ptr(row), total, local_bs, native.ptr(out), stream))
         self.dist.all_reduce_sum(sums)
-        out = torch.empty((n_mb, 2), dtype=torch.float32, device=self.device)
-        native.check(self.L.kp1_adv_minibatch_stats(self.device.index or 0, C.c_void_p(sums.data_ptr()), n_mb, C.c_void_p(out.data_ptr()),
-                                                    C.c_void_p(stream)))
-        return out
+        stats = torch.empty((*lead, 2), dtype=torch.float32, device=self.device)
+        native.check(self.L.kp1_adv_minibatch_stats(dev, native.ptr(sums), sums.numel() // 3, native.ptr(stats), stream))
+        return stats if one else stats.permute(1, 0, 2).contiguous()
 
     def _hip_minibatch_step(self, obs, idx, act, old_logp, adv, ret, device_step: bool = False, adv_stats=None) -> None:
-        """one optimiser step, all on the device: gathered fwd + loss + bwd (MFMA), flat grad all-reduce, clip + Adam + repack"""
+        """THE optimiser step, all on the device: gathered fwd + loss + bwd (MFMA), flat grad all-reduce, clip + Adam + repack.  ``idx``: [n] rows,
+        or a population's [K][n] block (with overrides the kernels read each replica's constants from the handle's table, not these scalars)"""
         cfg = self.cfg
-        n = int(idx.numel())
+        n = int(idx.numel()) // self.K
         world = self.dist.world_size
         if adv_stats is None and cfg.normalize_advantage and self.dist.enabled:
             mean, inv_std = global_advantage_stats(adv[idx], self.dist)
@@ -1510,7 +1520,7 @@ class PPO:
             self.adam_t += 1
         # device_step: the Adam step count lives on the device (incremented by loss_grad's finalize kernel) so that the
         # launch sequence can be replayed from a hipGraph; the host mirror self.adam_t is advanced by the caller
-        self._mlp.adam_step(self.policy.flat, self.grad, self.adam_m, self.adam_v, lr=cfg.learning_rate, eps=cfg.adam_eps,
+        self._mlp.adam_step(self.flat, self.grad, self.adam_m, self.adam_v, lr=cfg.learning_rate, eps=cfg.adam_eps,
                             max_grad_norm=cfg.max_grad_norm, step=0 if device_step else self.adam_t, fused_norm=not self.dist.enabled)
 
     # ------------------------------------------------------------------ driver

@@ -21,6 +21,8 @@ import os
 
 import torch
 
+from . import native
+
 _NCCL_DTYPE = {torch.uint8: 1, torch.int32: 2, torch.int64: 4, torch.float32: 7, torch.float64: 8}
 _NCCL_SUM = 0
 
@@ -75,18 +77,18 @@ class RcclComm:
             raise RuntimeError(f"{what}: {self.L.ncclGetErrorString(rc).decode()} ({rc})")
 
     def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return native.stream_arg(self.device)
 
     def all_reduce_sum(self, t: torch.Tensor) -> None:
         """in place, on torch's current stream"""
         assert t.is_contiguous() and t.device == self.device
-        self._check(self.L.ncclAllReduce(C.c_void_p(t.data_ptr()), C.c_void_p(t.data_ptr()), t.numel(), _NCCL_DTYPE[t.dtype], _NCCL_SUM, self._comm, self._stream()),
+        self._check(self.L.ncclAllReduce(native.ptr(t), native.ptr(t), t.numel(), _NCCL_DTYPE[t.dtype], _NCCL_SUM, self._comm, self._stream()),
                     "ncclAllReduce")
 
     def all_gather(self, out: torch.Tensor, t: torch.Tensor) -> None:
         """out[world * t.numel()] <- every rank's t, rank-major, on torch's current stream"""
         assert t.is_contiguous() and out.is_contiguous() and out.numel() == self.world * t.numel() and out.dtype == t.dtype
-        self._check(self.L.ncclAllGather(C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()), t.numel(), _NCCL_DTYPE[t.dtype], self._comm, self._stream()),
+        self._check(self.L.ncclAllGather(native.ptr(t), native.ptr(out), t.numel(), _NCCL_DTYPE[t.dtype], self._comm, self._stream()),
                     "ncclAllGather")
 
     def self_test(self) -> bool:

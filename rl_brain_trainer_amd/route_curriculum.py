@@ -114,7 +114,7 @@ class RoutePrefixCurriculumDevice(DeviceTracker):
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
         if dones.numel() != self.env.n_envs:
             raise ValueError("observe() tracks one process's envs from the env's own flags; data parallel goes through record() + observe_chunk()")
-        native.check(self.env.L.kp1_route_curriculum_observe(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), int(steps_per_call), self._stream()))
+        native.check(self.env.L.kp1_route_curriculum_observe(self.env._handle, self._st, native.ptr(dones), int(steps_per_call), self._stream()))
 
     def record(self, dones: torch.Tensor, out: torch.Tensor) -> None:
         """out[N] <- this step's episode records: the KP1_DONE_* bits of ``dones`` | route_ready << 4 | orientation hit << 5 | regression << 6,
@@ -122,14 +122,14 @@ class RoutePrefixCurriculumDevice(DeviceTracker):
         n = self.env.n_envs
         if dones.numel() != n or out.numel() != n or out.dtype != torch.uint8 or not (dones.is_contiguous() and out.is_contiguous()):
             raise ValueError(f"record() takes the {n} done bytes of one step and a contiguous uint8 [{n}] output")
-        native.check(self.env.L.kp1_route_episode_records(self.env._handle, C.c_void_p(dones.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()))
+        native.check(self.env.L.kp1_route_episode_records(self.env._handle, native.ptr(dones), native.ptr(out), self._stream()))
 
     def observe_chunk(self, records_all: torch.Tensor, n_local: int, chunk_steps: int, world: int) -> None:
         """data-parallel rollouts: the all-gathered [world, chunk_steps, n_local] episode records of a chunk of env steps, replayed in the
         reference's order (step by step, global env id order inside a step); a promotion moves this rank's reset window"""
         if not (records_all.numel() == world * chunk_steps * n_local and records_all.dtype == torch.uint8 and records_all.is_contiguous()):
             raise ValueError(f"observe_chunk() takes contiguous uint8 records of shape [{world}, {chunk_steps}, {n_local}]")
-        native.check(self.env.L.kp1_route_curriculum_observe_chunk(self.env._handle, self._st, C.c_void_p(records_all.data_ptr()), int(n_local),
+        native.check(self.env.L.kp1_route_curriculum_observe_chunk(self.env._handle, self._st, native.ptr(records_all), int(n_local),
                                                                    int(chunk_steps), int(world), self._stream()))
 
     def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:
@@ -176,7 +176,7 @@ class RoutePrefixCurriculumPopulation(TrackerPopulation, RoutePrefixCurriculumDe
     def observe(self, dones: torch.Tensor, steps_per_call: int) -> None:
         """dones: the K N done bytes of one population step; steps_per_call: env steps per replica this call stands for (N)"""
         self._check_done_bytes(dones, dones.numel() == self.env.n_envs)
-        native.check(self.env.L.kp1_route_curriculum_observe_population(self.env._handle, self._st, C.c_void_p(dones.data_ptr()), int(steps_per_call),
+        native.check(self.env.L.kp1_route_curriculum_observe_population(self.env._handle, self._st, native.ptr(dones), int(steps_per_call),
                                                                         self._stream()))
 
     def _read_call(self, k: int, out: Any, stream: C.c_void_p) -> int:

@@ -31,9 +31,7 @@ def _view(ptr: int, shape: tuple[int, ...], typestr: str, device: torch.device) 
     return torch.as_tensor(_DevView(ptr, shape, typestr), device=device)
 
 
-def _stream_arg(device: torch.device) -> C.c_void_p:
-    """torch's current stream on ``device`` as the ``hipStream_t`` argument of a launch"""
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_stream_arg = native.stream_arg
 
 
 class DeviceEnvHandle:
@@ -135,7 +133,7 @@ class ArmKinematicVecEnv(DeviceEnvHandle):
         self.dtype = torch.float32 if real == "f32" else torch.float64
         self._handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            native.check(self.L.kp1_create(C.byref(config.c), self.n_envs, self.device.index or 0, self.real_type,
+            native.check(self.L.kp1_create(C.byref(config.c), self.n_envs, native.device_index(self.device), self.real_type,
                                            int(seed), int(first_env_id), _stream_arg(self.device), C.byref(self._handle)))
         if config.handoff_states:
             arr = config.handoff_array()
@@ -486,7 +484,7 @@ def fk_pose6(q: torch.Tensor) -> torch.Tensor:
     rt = _real_type(q)
     q = q.contiguous()
     out = torch.empty((q.shape[0], 6), dtype=q.dtype, device=q.device)
-    native.check(native.load().kp1_fk_pose6(q.device.index or 0, rt, native.ptr(q), native.ptr(out), q.shape[0], _stream_arg(q.device)))
+    native.check(native.load().kp1_fk_pose6(native.device_index(q.device), rt, native.ptr(q), native.ptr(out), q.shape[0], _stream_arg(q.device)))
     return out
 
 
@@ -507,7 +505,7 @@ def pose_error_components(curr_pose6: torch.Tensor, goal_pose6: torch.Tensor) ->
     c, g = curr_pose6.contiguous(), goal_pose6.contiguous()
     n = c.shape[0]
     pe, oe, nr = (torch.empty((n, k), dtype=c.dtype, device=c.device) for k in (3, 3, 2))
-    native.check(native.load().kp1_pose_error(c.device.index or 0, rt, native.ptr(c), native.ptr(g), native.ptr(pe), native.ptr(oe), native.ptr(nr), n,
+    native.check(native.load().kp1_pose_error(native.device_index(c.device), rt, native.ptr(c), native.ptr(g), native.ptr(pe), native.ptr(oe), native.ptr(nr), n,
                                               _stream_arg(c.device)))
     return pe, oe, nr
 
@@ -520,7 +518,7 @@ def joint_utils(config: kcfg.EnvConfig, q: torch.Tensor, dq: torch.Tensor) -> di
     rt = _real_type(q)
     q, dq = q.contiguous(), dq.contiguous()
     out = {k: torch.empty_like(q) for k in ("clipped", "margin", "q_norm", "dq_norm")}
-    native.check(native.load().kp1_joint_utils(q.device.index or 0, rt, C.byref(config.c), native.ptr(q), native.ptr(dq),
+    native.check(native.load().kp1_joint_utils(native.device_index(q.device), rt, C.byref(config.c), native.ptr(q), native.ptr(dq),
                                                *(native.ptr(out[k]) for k in ("clipped", "margin", "q_norm", "dq_norm")), q.shape[0],
                                                _stream_arg(q.device)))
     return out
